@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the scan benchmark BASELINE.json names.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch B] [--dump-outputs DIR]
 
 A step = one exact top-10 search of a batch of queries over the whole synthetic corpus (the hot
 path of perceive-core: lib.rs:63-77 similarity + search.rs:157-182 selection), corpus resident in
@@ -55,7 +55,13 @@ def parse():
                     "tools/profile_round.sh uses to put one leg of this file under rocprofv3 at a time")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N>1: strong = --rows is the whole corpus, sharded (BASELINE configs[3]); weak = --rows per GPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (ids, scores, counts of the top-k) as "
+                         "DIR/<name>.npy in float64 / float32, to compare two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def effective_cpus():
@@ -406,6 +412,27 @@ def native_check(pa, ctx, dist, torch, searcher, queries, args, rank, world, las
     return rec["native_ok"]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, result):
+    """--dump-outputs: the (ids, scores, counts) a search call returned, as DIR/ids.npy (float64: row ids are exact in it),
+    DIR/scores.npy (float32, as returned) and DIR/counts.npy (float64).  Past 64 MB in all, the same seeded sample of query
+    rows is kept of every array, and their indices go to DIR/sampled_queries.npy."""
+    ids, scores, counts = result
+    arrays = {"ids": np.asarray(ids, np.float64), "scores": np.asarray(scores, np.float32), "counts": np.asarray(counts, np.float64)}
+    n = ids.shape[0]
+    per_query = sum(a.nbytes for a in arrays.values()) / max(n, 1)
+    if per_query * n > DUMP_MAX_BYTES:
+        fit = int((DUMP_MAX_BYTES - 4096) // (per_query + 8))  # (4 KB: the .npy headers)
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, fit), replace=False))
+        arrays = {name: a[keep] for name, a in arrays.items()}
+        arrays["sampled_queries"] = keep.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def measured_traffic(leg, kernel, required_bytes):
     """HBM bytes per launch from the committed PMC passes of this file's legs (profiles/traffic.json, written by
     tools/summarize_profiles.py; FETCH_SIZE x2 + WRITE_SIZE per the gfx950 guide): the entry of THIS leg, and only if
@@ -572,6 +599,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     searcher.set_mid_copy("auto")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else "cuda")
