@@ -104,7 +104,7 @@ private:
 // (max(0, 1 - dot/len), ascending); Metric::Cosine is lib.rs:67-77.
 class Searcher {
 public:
-    std::unordered_set<int64_t> hidden;  // search.rs:31-34 (kept; search_vector does not consult it)
+    std::unordered_set<int64_t> hidden;  // search.rs:31-34 (kept; search_vector does not consult it — hide_items keeps it in step)
 
     Searcher(Context& ctx, int dim, Metric metric = Metric::Dot) : dim_(dim) {
         check(pcv_searcher_create(ctx.handle(), dim, (int)metric, &h_));
@@ -179,6 +179,20 @@ public:
         int64_t rows = 0;
         const int64_t src = only_source.value_or(0);
         check(pcv_searcher_load_sqlite(h_, db_path.c_str(), model_id, model_version, only_source ? &src : nullptr, &rows));
+        return rows;
+    }
+    // hidden items (pcv_searcher_hide_ids): rows carrying one of `ids` are no result of any search until unhidden (no
+    // rebuild; the library's set persists across finalize and rebuild_source).  `hidden` follows.  Returns the rows changed.
+    int64_t hide_items(const std::vector<int64_t>& ids) {
+        int64_t rows = 0;
+        check(pcv_searcher_hide_ids(h_, ids.data(), (int64_t)ids.size(), &rows));
+        hidden.insert(ids.begin(), ids.end());
+        return rows;
+    }
+    int64_t unhide_items(const std::vector<int64_t>& ids) {
+        int64_t rows = 0;
+        check(pcv_searcher_unhide_ids(h_, ids.data(), (int64_t)ids.size(), &rows));
+        for (int64_t id : ids) hidden.erase(id);
         return rows;
     }
     // capacity hint: the rows about to be added to `source_id` land in one device segment

@@ -165,6 +165,27 @@ pcv_status pcv_searcher_source_num_rows(pcv_searcher* s, int64_t source_id, int6
 pcv_status pcv_searcher_get_rows(pcv_searcher* s, const int64_t* positions, int64_t n, float* out_rows,
                                  int64_t* out_ids);
 
+/* Hidden items (Searcher::hidden, search.rs:31-34; `perceive hide <id>`, cmd/hide.rs:16-17): the searcher keeps a set of hidden
+ * item ids, and a row is a possible result of a search (pcv_searcher_search, _search_device, _search_device_begin[_dq] / _end,
+ * _search_sharded[_dq]) iff its id is not in the set and its norm is valid.  No rebuild: the rows stay where they are.
+ *   - by id, not by position: every row carrying a hidden id is hidden, in every source (rows staged under PCV_STAGING_SOURCE too);
+ *   - the set persists: ids that match no row are remembered, rows added later with a hidden id are hidden when
+ *     pcv_searcher_finalize gives them their scale, pcv_searcher_clear_source / _replace_source do not forget it;
+ *   - hidden rows keep their global positions: pcv_searcher_num_rows, _source_num_rows and _get_rows still count and read them;
+ *     the scores and tie order of the other rows are those of a searcher that never held the hidden ones, and a search returns
+ *     fewer than num_results hits only when fewer visible rows exist;
+ *   - unhiding returns the rows exactly: every search afterwards returns what it returned before they were hidden (ids, scores,
+ *     counts), for every kernel, screening copy, mid copy and num_results;
+ *   - with an empty set nothing runs differently (finalize does no extra work).
+ * hide_ids / unhide_ids add ids to / remove ids from the set (duplicates and ids not present allowed).  They need a finalized
+ * searcher (PCV_ERR_INVALID with pending rows, like pcv_searcher_source_num_rows) and no queued pass.  out_rows (may be NULL):
+ * rows whose state changed, i.e. rows carrying an id that entered / left the set. */
+pcv_status pcv_searcher_hide_ids(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows);
+pcv_status pcv_searcher_unhide_ids(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows);
+/* The hidden set, ascending: the first min(cap, *out_n) ids into out_ids, *out_n = its size (call with cap 0 to ask).
+ * out_hidden_rows (may be NULL): rows hidden now (rows added since the last finalize count from the next one on). */
+pcv_status pcv_searcher_hidden_ids(pcv_searcher* s, int64_t* out_ids, int64_t cap, int64_t* out_n, int64_t* out_hidden_rows);
+
 /* Which scan kernel pcv_searcher_search uses. AUTO: wave-reduction kernel for n_queries <= 4,
  * MFMA tile kernel otherwise (up to 128 queries per corpus pass at dim <= 640; 256 with the int8 screening copy at
  * dim <= 384; among the ranks of a sharded search a pass is 128 queries on every rank, whatever copies each holds).

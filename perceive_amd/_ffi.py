@@ -119,6 +119,9 @@ SYMBOLS = {
     "pcv_searcher_source_ids": (C.c_int, [_P, _I64P, C.c_int]),
     "pcv_searcher_source_num_rows": (C.c_int, [_P, C.c_int64, _I64P]),
     "pcv_searcher_get_rows": (C.c_int, [_P, _I64P, C.c_int64, _F32P, _I64P]),
+    "pcv_searcher_hide_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
+    "pcv_searcher_unhide_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
+    "pcv_searcher_hidden_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P, _I64P]),
     "pcv_searcher_set_kernel": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_screening_copy": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_mid_copy": (C.c_int, [_P, C.c_int]),

@@ -197,6 +197,29 @@ int mfma8_pass_queries(int Dp);  // queries one int8 MFMA pass can take (LDS-lim
 // the blocks' scales — or nullptr: row by row, each with its own)
 void launch_mid_pack(hipStream_t st, const float4* blk, const float* scale, const float* scale8, uint4* mid16, float* scale16,
                      uint32_t first_row, uint32_t nrows, int D4);
+// ---- hidden items (pcv_searcher_hide_ids) ----
+// A batch of ids is looked up in an open-addressed table: capacity a power of two (mask = capacity - 1), linear probing from
+// id_hash, kIdEmpty in free slots; a batch that holds kIdEmpty itself says so with has_empty instead of storing it.
+constexpr int64_t kIdEmpty = INT64_MIN;
+__host__ __device__ static inline uint32_t id_hash(int64_t id, uint32_t mask) {
+    return (uint32_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+}
+// rows [row0, row1) of a segment whose id is in the table -> out_rows (the first `cap`), their number -> *out_n (zeroed here)
+void launch_match_ids(hipStream_t st, const int64_t* ids, uint32_t row0, uint32_t row1, const int64_t* table, uint32_t tmask,
+                      bool has_empty, uint32_t* out_rows, uint32_t* out_n, uint32_t cap);
+// rows[0..n) become not searchable: scale 0, zeros in the screening copy (rows < copied_rows), mid scale NaN (rows < mid_rows)
+void launch_hide_rows(hipStream_t st, const uint32_t* rows, uint32_t n, float* scale, uint4* blk8, uint4* blk16, uint32_t copied_rows,
+                      float* scale16, uint32_t mid_rows, int D4);
+// rows[0..n) searchable again: their scales as launch_row_scales computes them
+void launch_restore_scales(hipStream_t st, const float4* blk, const uint32_t* rows, uint32_t n, int D4, int metric, float* scale);
+// ... the int8 copy of blocks[0..n), whole blocks (new block scales)
+void launch_repack8_blocks(hipStream_t st, const float4* blk, const float* scale, const uint32_t* blocks, uint32_t n, uint4* blk8,
+                           float* scale8, int D4);
+// ... the bf16 copy of rows[0..n)
+void launch_repack16_rows(hipStream_t st, const float4* blk, const float* scale, const uint32_t* rows, uint32_t n, uint4* blk16, int D4);
+// ... the mid copy: items are blocks (scale8 != nullptr: every row of each, with the block's scale) or rows; rows >= mid_rows skipped
+void launch_repack_mid(hipStream_t st, const float4* blk, const float* scale, const float* scale8, const uint32_t* items, uint32_t n,
+                       uint32_t mid_rows, uint4* mid16, float* scale16, int D4);
 void launch_synth_fill(hipStream_t st, float4* blk, uint32_t nrows, uint32_t row0, int D, int D4, uint64_t seed,
                        int64_t first_row, int normalize, uint32_t n_clusters, float noise, float amp_lo = 0.0f, float amp_hi = 0.0f);
 void launch_gather_rows(hipStream_t st, const SegDesc* d_segs, int nseg, const int64_t* d_pos, int64_t n, int D,

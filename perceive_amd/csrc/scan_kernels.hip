@@ -488,6 +488,211 @@ __global__ __launch_bounds__(64) void mid_pack_block_kernel(const float4* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// hidden items (pcv_searcher_hide_ids, DESIGN.md §3 "Hidden items"): rows found by id and switched to "not searchable"
+// (scale 0, zeros in the screening copies, NaN mid scale) in place, or back.  None of the kernels above is involved.
+// ------------------------------------------------------------------------------------------------
+
+// Rows [row0, row1) of a segment whose id is in the batch's hash table (scan.h: id_hash): their in-segment row numbers are
+// appended to out_rows (the first `cap` of them; *out_n counts all).  One id per lane, one atomic per wave.
+__global__ __launch_bounds__(256) void match_ids_kernel(const int64_t* __restrict__ ids, uint32_t row0, uint32_t row1,
+                                                        const int64_t* __restrict__ table, uint32_t tmask, int has_empty,
+                                                        uint32_t* __restrict__ out_rows, uint32_t* __restrict__ out_n, uint32_t cap) {
+    const int lane = threadIdx.x & 63;
+    for (uint64_t base = (uint64_t)row0 + (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); base < row1;
+         base += (uint64_t)gridDim.x * 256) {
+        const uint32_t row = (uint32_t)base + lane;
+        bool hit = false;
+        if (row < row1) {
+            const int64_t id = __builtin_nontemporal_load(&ids[row]);
+            if (id == kIdEmpty) {
+                hit = has_empty != 0;
+            } else {
+                for (uint32_t h = id_hash(id, tmask);; h = (h + 1) & tmask) {
+                    const int64_t t = table[h];
+                    if (t == id) {
+                        hit = true;
+                        break;
+                    }
+                    if (t == kIdEmpty) break;
+                }
+            }
+        }
+        const unsigned long long ball = __ballot(hit);
+        if (ball) {
+            uint32_t at = 0;
+            if (lane == 0) at = atomicAdd(out_n, (uint32_t)__popcll(ball));
+            at = __shfl(at, 0);
+            if (hit) {
+                const uint32_t i = at + (uint32_t)__popcll(ball & ((1ull << lane) - 1ull));
+                if (i < cap) out_rows[i] = row;
+            }
+        }
+    }
+}
+
+// Hide rows[0..n) of a segment, one wave per row: scale 0, its int8 / bf16 pieces zero (rows < copied_rows), its mid scale NaN
+// (rows < mid_rows).  The int8 block scale stays: fewer searchable rows under the same s_blk keep the bound of scan.h.
+__global__ __launch_bounds__(256) void hide_rows_kernel(const uint32_t* __restrict__ rows, uint32_t n, float* __restrict__ scale,
+                                                        uint4* __restrict__ blk8, uint4* __restrict__ blk16, uint32_t copied_rows,
+                                                        float* __restrict__ scale16, uint32_t mid_rows, int D4) {
+    const int lane = threadIdx.x & 63;
+    const int D8 = D4 >> 1, D16 = ((D4 * 4 + 127) & ~127) >> 4;
+    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+        const uint32_t row = rows[i], b = row >> 5, r = row & 31;
+        if (lane == 0) {
+            scale[row] = 0.0f;
+            if (scale16 && row < mid_rows) scale16[row] = __builtin_nanf("");
+        }
+        if (row < copied_rows) {
+            if (blk8)
+                for (int g = lane; g < D16; g += 64) blk8[((size_t)b * D16 + g) * 32 + r] = make_uint4(0, 0, 0, 0);
+            if (blk16)
+                for (int f8 = lane; f8 < D8; f8 += 64) blk16[((size_t)b * D8 + f8) * 32 + r] = make_uint4(0, 0, 0, 0);
+        }
+    }
+}
+
+// Unhide, step 1: the scale of rows[0..n), one thread per row — row_scales_kernel's arithmetic restated operation for operation
+// (f64 sum in feature order, the same clamps and rounding), so the restored scale is the one the row had.  The corpus bound
+// max_norm only grows: it already covers these rows.
+__global__ __launch_bounds__(256) void restore_scales_kernel(const float4* __restrict__ blk, const uint32_t* __restrict__ rows,
+                                                             uint32_t n, int D4, int metric, float* __restrict__ scale) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t row = rows[i];
+    const float4* base = blk + (size_t)(row >> 5) * D4 * 32 + (row & 31);
+    double nx = 0.0;
+    for (int f4 = 0; f4 < D4; ++f4) {
+        float4 v = base[(size_t)f4 * 32];
+        nx += (double)v.x * (double)v.x;
+        nx += (double)v.y * (double)v.y;
+        nx += (double)v.z * (double)v.z;
+        nx += (double)v.w * (double)v.w;
+    }
+    const bool finite = nx < __builtin_inf();
+    float out;
+    if (metric == PCV_METRIC_DOT) {
+        out = finite ? 1.0f : 0.0f;
+    } else {
+        out = (finite && nx >= 0x1p-126) ? (float)(1.0 / sqrt(nx)) : 0.0f;
+    }
+    scale[row] = out;
+}
+
+// Unhide, step 2 (int8 copy): blocks[0..n) re-packed whole, coarse_pack8_kernel's arithmetic over a list of blocks: s_blk is taken
+// again over the block's searchable rows, the returned ones among them (a finalize that appended rows to the block while they
+// were hidden set it without them: it may exceed 127 / max|y_i| of a returned row, whose values would then clip).
+__global__ __launch_bounds__(256) void repack8_blocks_kernel(const float4* __restrict__ blk, const float* __restrict__ scale,
+                                                             const uint32_t* __restrict__ blocks, uint32_t n, uint4* __restrict__ blk8,
+                                                             float* __restrict__ scale8, int D4) {
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int D16 = ((D4 * 4 + 127) & ~127) >> 4;
+    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+        const uint32_t b = blocks[i];
+        const float sc = scale[(size_t)b * 32 + r];
+        const float4* src = blk + (size_t)b * D4 * 32 + r;
+        float mx = 0.0f;
+        for (int g = h; g < D16; g += 2)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * g + e < D4) {
+                    const float4 v = src[(size_t)(4 * g + e) * 32];
+                    mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x * sc), fabsf(v.y * sc)), fmaxf(fabsf(v.z * sc), fabsf(v.w * sc))));
+                }
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const bool searchable = sc != 0.0f && mx < __builtin_inff();
+        float bm = searchable ? mx : 0.0f;
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) bm = fmaxf(bm, __shfl_xor(bm, off));
+        const bool any_row = __any(searchable);
+        const float s_blk = !any_row ? __builtin_nanf("") : (bm > 0.0f ? 127.0f / bm : 1.0f);
+        for (int g = h; g < D16; g += 2) {
+            uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (searchable && 4 * g + e < D4) {
+                    const float4 v = src[(size_t)(4 * g + e) * 32];
+                    const float y[4] = {v.x * sc, v.y * sc, v.z * sc, v.w * sc};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int qv = max(-127, min(127, (int)rintf(y[j] * s_blk)));
+                        w[e] |= (uint32_t)(qv & 0xff) << (8 * j);
+                    }
+                }
+            blk8[((size_t)b * D16 + g) * 32 + r] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        if (lane == 0) scale8[b] = s_blk;
+    }
+}
+
+// Unhide, step 2 (bf16 copy): the pieces of rows[0..n), one wave per row, coarse_pack_kernel's conversion (the piece is row-local).
+__global__ __launch_bounds__(256) void repack16_rows_kernel(const float4* __restrict__ blk, const float* __restrict__ scale,
+                                                            const uint32_t* __restrict__ rows, uint32_t n, uint4* __restrict__ blk16, int D4) {
+    const int lane = threadIdx.x & 63;
+    const int D8 = D4 >> 1;
+    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+        const uint32_t row = rows[i], b = row >> 5, r = row & 31;
+        const float sc = scale[row];
+        for (int f8 = lane; f8 < D8; f8 += 64) {
+            uint4 out = make_uint4(0, 0, 0, 0);
+            if (sc != 0.0f) {
+                const float4 lo = blk[((size_t)b * D4 + 2 * f8) * 32 + r], hi = blk[((size_t)b * D4 + 2 * f8 + 1) * 32 + r];
+                const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                out = __builtin_bit_cast(uint4, __builtin_convertvector(v * sc, bf16x8));
+            }
+            blk16[((size_t)b * D8 + f8) * 32 + r] = out;
+        }
+    }
+}
+
+// Unhide, step 3 (mid copy), one wave per row, rows < mid_rows only.  scale8 != nullptr (the segment has its int8 copy): items[]
+// are blocks and every row of each is re-quantised with s2 = scale8[b] * 32766 / 127 of the re-packed block, as
+// mid_pack_block_kernel does; otherwise items[] are rows, each with its own s2 = 32766 / max|y_i|, as mid_pack_kernel does.
+__global__ __launch_bounds__(256) void repack_mid_kernel(const float4* __restrict__ blk, const float* __restrict__ scale,
+                                                         const float* __restrict__ scale8, const uint32_t* __restrict__ items, uint32_t n,
+                                                         uint32_t mid_rows, uint4* __restrict__ mid16, float* __restrict__ scale16, int D4) {
+    const int lane = threadIdx.x & 63;
+    const int P8 = D4 >> 1;
+    const uint32_t per = scale8 ? 32u : 1u;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); t < (uint64_t)n * per; t += (uint64_t)gridDim.x * 4) {
+        const uint32_t row = scale8 ? items[t >> 5] * 32 + (uint32_t)(t & 31) : items[t];
+        if (row >= mid_rows) continue;
+        const float sc = scale[row];
+        const float4* src = blk + (size_t)(row >> 5) * D4 * 32 + (row & 31);
+        float s2;
+        bool searchable;
+        if (scale8) {
+            s2 = scale8[row >> 5] * (32766.0f / 127.0f);
+            searchable = sc != 0.0f && s2 == s2;
+        } else {
+            float mx = 0.0f;
+            for (int j = lane; j < P8; j += 64) {
+                const float4 a = src[(size_t)(2 * j) * 32], b = src[(size_t)(2 * j + 1) * 32];
+                mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(fabsf(a.x * sc), fabsf(a.y * sc)), fmaxf(fabsf(a.z * sc), fabsf(a.w * sc))),
+                                     fmaxf(fmaxf(fabsf(b.x * sc), fabsf(b.y * sc)), fmaxf(fabsf(b.z * sc), fabsf(b.w * sc)))));
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+            searchable = sc != 0.0f && mx < __builtin_inff();
+            s2 = !searchable ? 0.0f : (mx > 0.0f ? 32766.0f / mx : 1.0f);
+        }
+        for (int j = lane; j < P8; j += 64) {
+            const float4 a = src[(size_t)(2 * j) * 32], b = src[(size_t)(2 * j + 1) * 32];
+            const float y[8] = {a.x * sc, a.y * sc, a.z * sc, a.w * sc, b.x * sc, b.y * sc, b.z * sc, b.w * sc};
+            uint32_t w[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int lo = searchable ? max(-32767, min(32767, (int)rintf(y[2 * e] * s2))) : 0;
+                const int hi = searchable ? max(-32767, min(32767, (int)rintf(y[2 * e + 1] * s2))) : 0;
+                w[e] = ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16);
+            }
+            mid16[(size_t)row * P8 + j] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        if (lane == 0) scale16[row] = searchable ? s2 : __builtin_nanf("");
+    }
+}
+
 struct SynthShape {  // n_clusters == 0: plain i.i.d. rows, times a per-row amplitude in [amp_lo, amp_lo + amp_span) if amp_span >= 0
     uint32_t n_clusters;
     float noise, inv_sqrt_d;
@@ -3001,6 +3206,54 @@ void launch_mid_pack(hipStream_t st, const float4* blk, const float* scale, cons
     }
     const unsigned grid = (unsigned)std::min<uint32_t>((nrows - first_row + 3) / 4, 256u * 8 * 4);
     mid_pack_kernel<<<grid, 256, 0, st>>>(blk, scale, mid16, scale16, first_row, nrows, D4);
+    PCV_LAUNCHED();
+}
+
+void launch_match_ids(hipStream_t st, const int64_t* ids, uint32_t row0, uint32_t row1, const int64_t* table, uint32_t tmask,
+                      bool has_empty, uint32_t* out_rows, uint32_t* out_n, uint32_t cap) {
+    PCV_HIP(hipMemsetAsync(out_n, 0, sizeof(uint32_t), st));
+    if (row0 >= row1) return;
+    // enough waves to keep the id stream at HBM rate (8 KB of ids per workgroup and step), each walking a stretch of rows
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv64((int64_t)row1 - row0, 256), (int64_t)current_device_cus() * 16);
+    match_ids_kernel<<<grid, 256, 0, st>>>(ids, row0, row1, table, tmask, has_empty ? 1 : 0, out_rows, out_n, cap);
+    PCV_LAUNCHED();
+}
+
+void launch_hide_rows(hipStream_t st, const uint32_t* rows, uint32_t n, float* scale, uint4* blk8, uint4* blk16, uint32_t copied_rows,
+                      float* scale16, uint32_t mid_rows, int D4) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)std::min<uint32_t>((n + 3) / 4, 1u << 16);
+    hide_rows_kernel<<<grid, 256, 0, st>>>(rows, n, scale, blk8, blk16, copied_rows, scale16, mid_rows, D4);
+    PCV_LAUNCHED();
+}
+
+void launch_restore_scales(hipStream_t st, const float4* blk, const uint32_t* rows, uint32_t n, int D4, int metric, float* scale) {
+    if (n == 0) return;
+    restore_scales_kernel<<<cdiv64(n, 256), 256, 0, st>>>(blk, rows, n, D4, metric, scale);
+    PCV_LAUNCHED();
+}
+
+void launch_repack8_blocks(hipStream_t st, const float4* blk, const float* scale, const uint32_t* blocks, uint32_t n, uint4* blk8,
+                           float* scale8, int D4) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)std::min<uint32_t>((n + 3) / 4, 1u << 16);
+    repack8_blocks_kernel<<<grid, 256, 0, st>>>(blk, scale, blocks, n, blk8, scale8, D4);
+    PCV_LAUNCHED();
+}
+
+void launch_repack16_rows(hipStream_t st, const float4* blk, const float* scale, const uint32_t* rows, uint32_t n, uint4* blk16, int D4) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)std::min<uint32_t>((n + 3) / 4, 1u << 16);
+    repack16_rows_kernel<<<grid, 256, 0, st>>>(blk, scale, rows, n, blk16, D4);
+    PCV_LAUNCHED();
+}
+
+void launch_repack_mid(hipStream_t st, const float4* blk, const float* scale, const float* scale8, const uint32_t* items, uint32_t n,
+                       uint32_t mid_rows, uint4* mid16, float* scale16, int D4) {
+    if (n == 0) return;
+    const uint64_t waves = (uint64_t)n * (scale8 ? 32u : 1u);
+    const unsigned grid = (unsigned)std::min<uint64_t>((waves + 3) / 4, 1u << 16);
+    repack_mid_kernel<<<grid, 256, 0, st>>>(blk, scale, scale8, items, n, mid_rows, mid16, scale16, D4);
     PCV_LAUNCHED();
 }
 

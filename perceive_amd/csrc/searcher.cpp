@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <atomic>
 #include <memory>
@@ -40,6 +41,7 @@ struct Segment {
     int64_t pos0 = 0;
     uint32_t nrows = 0, cap_rows = 0, scaled_rows = 0;
     uint32_t copied_rows = 0;  // rows the screening copy covers
+    uint32_t hidden_rows = 0;  // rows whose id is in the searcher's hidden set (pcv_searcher_hide_ids)
     uint32_t nblocks() const { return (nrows + kBlockRows - 1) / kBlockRows; }
 };
 
@@ -97,6 +99,10 @@ struct pcv_searcher {
     std::mutex mu;
     pcv_scan_stats stats{};
     DevBuf<float> d_stage;  // ingestion staging (released by finalize)
+    // hidden items (pcv_searcher_hide_ids): the set, ascending, and the device scratch that applies a batch of it
+    std::vector<int64_t> hidden;
+    DevBuf<int64_t> d_idtab;         // the batch's hash table (scan.h: id_hash)
+    DevBuf<uint32_t> d_hrows, d_hblocks, d_hcnt;
 
     // per-search workspace (sized for one pass of <= 128 queries)
     DevBuf<float> d_qf32, d_qraw, d_margin, d_margin32;
@@ -645,14 +651,147 @@ void build_screening_copies(pcv_searcher* s, Source& src) {
     }
 }
 
+// ---- hidden items (pcv_searcher_hide_ids; DESIGN.md §3 "Hidden items") ----
+// A batch of ids (ascending, distinct) and, once a segment with an id column needs it, its hash table on the device.
+struct IdBatch {
+    const std::vector<int64_t>* ids = nullptr;
+    bool uploaded = false, has_empty = false;
+    uint32_t tmask = 0;
+};
+
+void upload_id_batch(pcv_searcher* s, IdBatch& b) {
+    if (b.uploaded) return;
+    size_t cap = 64;  // load <= 1/2: about one probe per id looked up
+    while (cap < 2 * b.ids->size()) cap <<= 1;
+    PCV_REQUIRE(cap <= ((size_t)1 << 32), "hide_ids: %zu ids in one batch", b.ids->size());
+    std::vector<int64_t> tab(cap, kIdEmpty);
+    b.tmask = (uint32_t)(cap - 1);
+    for (int64_t id : *b.ids) {
+        if (id == kIdEmpty) {
+            b.has_empty = true;
+            continue;
+        }
+        uint32_t h = id_hash(id, b.tmask);
+        while (tab[h] != kIdEmpty) h = (h + 1) & b.tmask;
+        tab[h] = id;
+    }
+    s->d_idtab.ensure(cap);
+    PCV_HIP(hipMemcpyAsync(s->d_idtab.p, tab.data(), cap * sizeof(int64_t), hipMemcpyHostToDevice, s->ctx->stream));
+    PCV_HIP(hipStreamSynchronize(s->ctx->stream));  // (tab goes out of scope)
+    b.uploaded = true;
+}
+
+// Rows [r0, r1) of segment g whose id is in the batch -> s->d_hrows[0..n), n returned.  Implicit ids (id0 + row) are found by
+// arithmetic on the host; an id column is streamed once by match_ids_kernel.
+uint32_t find_rows(pcv_searcher* s, const Segment& g, uint32_t r0, uint32_t r1, IdBatch& b) {
+    hipStream_t st = s->ctx->stream;
+    if (r0 >= r1) return 0;
+    if (!g.ids) {
+        const std::vector<int64_t>& v = *b.ids;
+        std::vector<uint32_t> rows;
+        for (auto it = std::lower_bound(v.begin(), v.end(), g.id0 + r0); it != v.end() && *it < g.id0 + r1; ++it)
+            rows.push_back((uint32_t)(*it - g.id0));
+        if (rows.empty()) return 0;
+        s->d_hrows.ensure(rows.size());
+        PCV_HIP(hipMemcpyAsync(s->d_hrows.p, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        return (uint32_t)rows.size();
+    }
+    upload_id_batch(s, b);
+    s->d_hcnt.ensure(1);
+    s->d_hrows.ensure(std::min<size_t>(r1 - r0, std::max<size_t>(4096, 2 * b.ids->size())));
+    for (;;) {
+        launch_match_ids(st, g.ids, r0, r1, s->d_idtab.p, b.tmask, b.has_empty, s->d_hrows.p, s->d_hcnt.p, (uint32_t)s->d_hrows.n);
+        uint32_t n = 0;
+        PCV_HIP(hipMemcpyAsync(&n, s->d_hcnt.p, sizeof(n), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        if (n <= s->d_hrows.n) return n;
+        s->d_hrows.ensure(n);  // (more rows carry these ids than the list had room for: once more with room for all)
+    }
+}
+
+void hide_found(pcv_searcher* s, Segment& g, uint32_t n) {
+    launch_hide_rows(s->ctx->stream, s->d_hrows.p, n, g.scale, g.blk8, g.blk16, g.copied_rows, g.mid16 ? g.scale16 : nullptr, g.mid_rows,
+                     s->D4);
+}
+
+// The rows come back: their scales, their bf16 pieces (row-local), and the WHOLE 32-row blocks of the int8 copy and of a mid copy
+// quantised with it — a finalize that appended rows to such a block while they were hidden quantised it without them.
+void unhide_found(pcv_searcher* s, Segment& g, uint32_t n) {
+    hipStream_t st = s->ctx->stream;
+    launch_restore_scales(st, g.blk, s->d_hrows.p, n, s->D4, s->metric, g.scale);
+    if (g.blk16) launch_repack16_rows(st, g.blk, g.scale, s->d_hrows.p, n, g.blk16, s->D4);
+    uint32_t nb = 0;
+    if (g.blk8) {
+        std::vector<uint32_t> rows(n);
+        PCV_HIP(hipMemcpyAsync(rows.data(), s->d_hrows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        std::vector<uint32_t> blocks;
+        for (uint32_t r : rows)
+            if (r < g.copied_rows) blocks.push_back(r / kBlockRows);
+        std::sort(blocks.begin(), blocks.end());
+        blocks.erase(std::unique(blocks.begin(), blocks.end()), blocks.end());
+        nb = (uint32_t)blocks.size();
+        if (nb) {
+            s->d_hblocks.ensure(nb);
+            PCV_HIP(hipMemcpyAsync(s->d_hblocks.p, blocks.data(), (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            launch_repack8_blocks(st, g.blk, g.scale, s->d_hblocks.p, nb, g.blk8, g.scale8, s->D4);
+        }
+        PCV_HIP(hipStreamSynchronize(st));  // (blocks goes out of scope)
+    }
+    if (g.mid16 && g.mid_rows > 0) {
+        if (g.blk8 && g.copied_rows >= g.nrows)  // the copy is quantised with the int8 copy's block scales (launch_mid_pack)
+            launch_repack_mid(st, g.blk, g.scale, g.scale8, s->d_hblocks.p, nb, g.mid_rows, g.mid16, g.scale16, s->D4);
+        else
+            launch_repack_mid(st, g.blk, g.scale, nullptr, s->d_hrows.p, n, g.mid_rows, g.mid16, g.scale16, s->D4);
+    }
+}
+
+// Hide (or unhide) every row, in every source, whose id is in `batch` (ascending, distinct, none of it in the set yet / all of it
+// in the set); the rows changed.
+int64_t apply_id_batch(pcv_searcher* s, const std::vector<int64_t>& batch, bool hide) {
+    if (batch.empty()) return 0;
+    IdBatch b;
+    b.ids = &batch;
+    int64_t changed = 0;
+    for (auto& src : s->sources)
+        for (auto& g : src.segs) {
+            const uint32_t n = find_rows(s, g, 0, g.nrows, b);
+            if (n == 0) continue;
+            if (hide)
+                hide_found(s, g, n);
+            else
+                unhide_found(s, g, n);
+            PCV_HIP(hipStreamSynchronize(s->ctx->stream));  // (d_hrows is the next segment's)
+            g.hidden_rows = hide ? g.hidden_rows + n : g.hidden_rows - n;
+            changed += n;
+        }
+    PCV_HIP(hipGetLastError());
+    return changed;
+}
+
 void do_finalize(pcv_searcher* s) {
     settle_mid_build(s, true);
     hipStream_t st = s->ctx->stream;
+    IdBatch hidden;  // (the hidden set, looked up only where new rows get their scale and only if it is not empty)
+    hidden.ids = &s->hidden;
     for (auto& src : s->sources) {
         for (auto& g : src.segs) {
             if (g.scaled_rows >= g.nrows) continue;
             launch_row_scales(st, g.blk, g.scaled_rows / kBlockRows, g.nblocks(), g.nrows, s->D4, s->metric, g.scale,
                               s->d_max_norm_bits);
+            if (!s->hidden.empty()) {
+                // row_scales_kernel starts at the block of the first new row: the hidden rows in front of it in that block lost their
+                // scale 0 again (already counted); the new rows with a hidden id are hidden before any copy is made of them
+                const uint32_t r0 = g.scaled_rows / kBlockRows * kBlockRows;
+                uint32_t n = find_rows(s, g, r0, g.scaled_rows, hidden);
+                if (n) hide_found(s, g, n);
+                PCV_HIP(hipStreamSynchronize(st));
+                n = find_rows(s, g, g.scaled_rows, g.nrows, hidden);
+                if (n) hide_found(s, g, n);
+                PCV_HIP(hipStreamSynchronize(st));
+                g.hidden_rows += n;
+            }
             g.scaled_rows = g.nrows;
         }
         build_screening_copies(s, src);
@@ -1331,6 +1470,10 @@ pcv_status pcv_searcher_destroy(pcv_searcher* s) {
         s->d_cnt.release();
         s->d_cand.release();
         s->d_hits.release();
+        s->d_idtab.release();
+        s->d_hrows.release();
+        s->d_hblocks.release();
+        s->d_hcnt.release();
         if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
         if (s->pin) (void)hipHostFree(s->pin);
         if (s->pin_pass) (void)hipHostFree(s->pin_pass);
@@ -1495,6 +1638,64 @@ pcv_status pcv_searcher_finalize(pcv_searcher* s) {
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_HIP(hipSetDevice(s->ctx->device));
         do_finalize(s);
+    });
+}
+
+static pcv_status hide_or_unhide(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows, bool hide) {
+    const char* who = hide ? "hide_ids" : "unhide_ids";
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
+        PCV_REQUIRE(n >= 0 && (ids != nullptr || n == 0), "%s: bad id list", who);
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
+        PCV_REQUIRE(!s->pending.active, "%s: a queued pass has not been collected", who);
+        if (out_rows) *out_rows = 0;
+        // the batch: the ids whose membership changes, ascending and distinct
+        std::vector<int64_t> batch(ids, ids + n);
+        std::sort(batch.begin(), batch.end());
+        batch.erase(std::unique(batch.begin(), batch.end()), batch.end());
+        std::vector<int64_t> batch_in;  // ... of it, the ones in the set
+        std::set_intersection(batch.begin(), batch.end(), s->hidden.begin(), s->hidden.end(), std::back_inserter(batch_in));
+        std::vector<int64_t> next;
+        if (hide) {
+            std::vector<int64_t> fresh;
+            std::set_difference(batch.begin(), batch.end(), batch_in.begin(), batch_in.end(), std::back_inserter(fresh));
+            batch.swap(fresh);
+            std::set_union(s->hidden.begin(), s->hidden.end(), batch.begin(), batch.end(), std::back_inserter(next));
+        } else {
+            batch.swap(batch_in);
+            std::set_difference(s->hidden.begin(), s->hidden.end(), batch.begin(), batch.end(), std::back_inserter(next));
+        }
+        if (batch.empty()) return;
+        PCV_HIP(hipSetDevice(s->ctx->device));
+        settle_mid_build(s, true);  // (the AUTO mid build reads the scales and writes the mid copy)
+        const int64_t changed = apply_id_batch(s, batch, hide);
+        s->hidden.swap(next);
+        if (out_rows) *out_rows = changed;
+    });
+}
+
+pcv_status pcv_searcher_hide_ids(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows) {
+    return hide_or_unhide(s, ids, n, out_rows, true);
+}
+
+pcv_status pcv_searcher_unhide_ids(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows) {
+    return hide_or_unhide(s, ids, n, out_rows, false);
+}
+
+pcv_status pcv_searcher_hidden_ids(pcv_searcher* s, int64_t* out_ids, int64_t cap, int64_t* out_n, int64_t* out_hidden_rows) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out_n != nullptr, "hidden_ids: NULL argument");
+        PCV_REQUIRE(cap >= 0 && (out_ids != nullptr || cap == 0), "hidden_ids: bad output buffer");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out_n = (int64_t)s->hidden.size();
+        std::copy_n(s->hidden.begin(), (size_t)std::min<int64_t>(cap, *out_n), out_ids);
+        if (out_hidden_rows) {
+            int64_t rows = 0;
+            for (const auto& src : s->sources)
+                for (const auto& g : src.segs) rows += g.hidden_rows;
+            *out_hidden_rows = rows;
+        }
     });
 }
 

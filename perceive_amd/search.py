@@ -330,6 +330,40 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_get_rows(self._handle, _ffi.i64p(pos), pos.size, _ffi.f32p(rows), _ffi.i64p(ids)))
         return rows, ids
 
+    # ---- hidden items (pcv_searcher_hide_ids) -------------------------------------------------------
+    # Unlike `self.hidden` above, these are consulted: rows carrying a hidden id are no result of any search until they are
+    # unhidden, without a rebuild.  The set persists across finalize / rebuild_source; rows keep their positions.
+    def hide_items(self, ids):
+        """Hide every row carrying one of `ids` (int64 1-D array or iterable); returns the rows that were hidden by it."""
+        return self._hide_call(_ffi.lib().pcv_searcher_hide_ids, ids)
+
+    def unhide_items(self, ids):
+        """Return the rows carrying one of `ids` to the results (exactly as before); returns the rows that came back."""
+        return self._hide_call(_ffi.lib().pcv_searcher_unhide_ids, ids)
+
+    def hidden_items(self):
+        """The hidden set, ascending (int64 array)."""
+        n = C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_hidden_ids(self._handle, None, 0, C.byref(n), None))
+        out = np.zeros(max(n.value, 1), dtype=np.int64)
+        _ffi.check(_ffi.lib().pcv_searcher_hidden_ids(self._handle, _ffi.i64p(out), out.size, C.byref(n), None))
+        return out[: n.value]
+
+    @property
+    def hidden_rows(self):
+        """Rows hidden now."""
+        n, rows = C.c_int64(), C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_hidden_ids(self._handle, None, 0, C.byref(n), C.byref(rows)))
+        return rows.value
+
+    def _hide_call(self, fn, ids):
+        a = np.ascontiguousarray(ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.int64), dtype=np.int64)
+        if a.ndim != 1:
+            raise ValueError("ids must be 1-D")
+        rows = C.c_int64()
+        _ffi.check(fn(self._handle, _ffi.i64p(a) if a.size else None, a.size, C.byref(rows)))
+        return rows.value
+
     def last_stats(self):
         st = _ffi.ScanStats()
         _ffi.check(_ffi.lib().pcv_searcher_last_stats(self._handle, C.byref(st)))

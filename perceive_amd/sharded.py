@@ -127,6 +127,17 @@ class ShardedSearcher:
         self._bufs = {}
         self._adopted = False
 
+    # hidden items: every rank applies the same ids to its local searcher (a rank that holds none of them changes nothing);
+    # the rows changed on this rank are returned
+    def hide_items(self, ids):
+        return self.searcher.hide_items(ids)
+
+    def unhide_items(self, ids):
+        return self.searcher.unhide_items(ids)
+
+    def hidden_items(self):
+        return self.searcher.hidden_items()
+
     def _buffers(self, B, k):
         import torch
 

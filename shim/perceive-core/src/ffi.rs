@@ -167,6 +167,9 @@ extern "C" {
     pub fn pcv_searcher_source_ids(s: *mut pcv_searcher, out_ids: *mut i64, cap: c_int) -> c_int;
     pub fn pcv_searcher_source_num_rows(s: *mut pcv_searcher, source_id: i64, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_get_rows(s: *mut pcv_searcher, positions: *const i64, n: i64, out_rows: *mut f32, out_ids: *mut i64) -> c_int;
+    pub fn pcv_searcher_hide_ids(s: *mut pcv_searcher, ids: *const i64, n: i64, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_unhide_ids(s: *mut pcv_searcher, ids: *const i64, n: i64, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_hidden_ids(s: *mut pcv_searcher, out_ids: *mut i64, cap: i64, out_n: *mut i64, out_hidden_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_set_kernel(s: *mut pcv_searcher, kernel: c_int) -> c_int;
     pub fn pcv_searcher_set_candidate_capacity(s: *mut pcv_searcher, n_candidates: u32) -> c_int;
     pub fn pcv_searcher_set_tuning(s: *mut pcv_searcher, flags: u32) -> c_int;

@@ -28,7 +28,8 @@ pub struct SearchItem {
 pub struct Searcher {
     handle: *mut ffi::pcv_searcher,
     /// ids hidden after the index was built (`perceive hide`, cmd/hide.rs:17).  Kept as the pub field it
-    /// is in the reference (search.rs:31-34), whose `search_vector` does not consult it either.
+    /// is in the reference (search.rs:31-34), whose `search_vector` does not consult it either; `hide_items` /
+    /// `unhide_items` keep it in step with the set the library does consult.
     pub hidden: HashSet<i64>,
 }
 
@@ -114,6 +115,9 @@ impl Searcher {
                 hip::check(unsafe {
                     ffi::pcv_searcher_create(ctx.0, (blob.len() / 4) as i32, ffi::PCV_METRIC_DOT, &mut self.handle)
                 })?;
+                // ids hidden (hide_items) before there was an index: the library's set starts with them
+                let ids: Vec<i64> = self.hidden.iter().copied().collect();
+                hip::check(unsafe { ffi::pcv_searcher_hide_ids(self.handle, ids.as_ptr(), ids.len() as i64, ptr::null_mut()) })?;
             }
             let (ids, bytes) = &mut pending[source_idx];
             ids.push(id);
@@ -175,6 +179,32 @@ impl Searcher {
         })
         .expect("search failed"); // the reference unwraps here too (NaN scores panic at search.rs:179)
         (0..count as usize).map(|i| SearchItem { id: ids[i], score: scores[i] }).collect()
+    }
+
+    /// Hide every row carrying one of `ids` from every later search, in place (no rebuild; the library keeps the
+    /// set, remembers ids no row has yet and hides rows added later with them).  `self.hidden` follows, so the pub field
+    /// keeps meaning what it meant.  `perceive hide <id>` (cmd/hide.rs:16-17) would call this where it now inserts into
+    /// `searcher.hidden`, right after setting `hidden_at`:
+    ///     `searcher.hide_items(&[id])?;`
+    pub fn hide_items(&mut self, ids: &[i64]) -> Result<(), HipError> {
+        if !self.handle.is_null() {
+            let mut rows: i64 = 0;
+            hip::check(unsafe { ffi::pcv_searcher_hide_ids(self.handle, ids.as_ptr(), ids.len() as i64, &mut rows) })?;
+        }
+        self.hidden.extend(ids.iter().copied());
+        Ok(())
+    }
+
+    /// The rows carrying one of `ids` are results again, exactly as before they were hidden.
+    pub fn unhide_items(&mut self, ids: &[i64]) -> Result<(), HipError> {
+        if !self.handle.is_null() {
+            let mut rows: i64 = 0;
+            hip::check(unsafe { ffi::pcv_searcher_unhide_ids(self.handle, ids.as_ptr(), ids.len() as i64, &mut rows) })?;
+        }
+        for id in ids {
+            self.hidden.remove(id);
+        }
+        Ok(())
     }
 
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
