@@ -195,6 +195,33 @@ public:
         for (int64_t id : ids) hidden.erase(id);
         return rows;
     }
+    // updated items (pcv_searcher_update_rows): rows carrying ids[i] take the vector rows[i*dim .. (i+1)*dim) in place (no
+    // rebuild).  `found` (if given) gets, per id, whether some row carries it.  Returns the rows rewritten.
+    int64_t update_items(const std::vector<int64_t>& ids, const std::vector<float>& rows, std::vector<bool>* found = nullptr) {
+        if (rows.size() != ids.size() * (size_t)dim_) throw Error(PCV_ERR_INVALID, "update_items: rows must be ids.size() x dim");
+        std::vector<uint8_t> f(ids.size());
+        int64_t changed = 0;
+        check(pcv_searcher_update_rows(h_, ids.data(), rows.data(), (int64_t)ids.size(), f.data(), &changed));
+        if (found) found->assign(f.begin(), f.end());
+        return changed;
+    }
+    // what a source scan produces: ids some row carries take their new vector, the others are added to `source_id`; then
+    // finalize.  Returns (rows replaced, rows appended).
+    std::pair<int64_t, int64_t> upsert_items(int64_t source_id, const std::vector<int64_t>& ids, const std::vector<float>& rows) {
+        std::vector<bool> found;
+        const int64_t replaced = update_items(ids, rows, &found);
+        std::vector<int64_t> new_ids;
+        std::vector<float> new_rows;
+        for (size_t i = 0; i < ids.size(); ++i)
+            if (!found[i]) {
+                new_ids.push_back(ids[i]);
+                new_rows.insert(new_rows.end(), rows.begin() + i * dim_, rows.begin() + (i + 1) * dim_);
+            }
+        if (!new_ids.empty())
+            check(pcv_searcher_add_rows(h_, source_id, new_ids.data(), new_rows.data(), (int64_t)new_ids.size()));
+        check(pcv_searcher_finalize(h_));
+        return {replaced, (int64_t)new_ids.size()};
+    }
     // capacity hint: the rows about to be added to `source_id` land in one device segment
     void reserve(int64_t source_id, int64_t n_rows) { check(pcv_searcher_reserve(h_, source_id, n_rows)); }
     // narrow screening copy of the rows next to the f32 rows (a half / a quarter of the bytes per scan, same results):

@@ -186,6 +186,29 @@ pcv_status pcv_searcher_unhide_ids(pcv_searcher* s, const int64_t* ids, int64_t 
  * out_hidden_rows (may be NULL): rows hidden now (rows added since the last finalize count from the next one on). */
 pcv_status pcv_searcher_hidden_ids(pcv_searcher* s, int64_t* out_ids, int64_t cap, int64_t* out_n, int64_t* out_hidden_rows);
 
+/* Updated items (update_db.rs upserts re-embedded items into item_embeddings; a source scan then needs their new vectors in the
+ * index): every row whose id is ids[i] takes rows[i] as its vector, in place.  No rebuild: the rows stay where they are.
+ *   - by id, like hide_ids: every source (rows staged under PCV_STAGING_SOURCE too), explicit-id and implicit-id segments
+ *     (pcv_searcher_add_rows with ids == NULL, synthetic rows: id = id0 + row);
+ *   - out_found (may be NULL): n bytes, out_found[i] = 1 iff some row carries ids[i]; out_rows (may be NULL): the rows
+ *     rewritten.  Ids that match no row change nothing and are not remembered (unlike the hidden set);
+ *   - exact: afterwards every search entry point returns bit for bit what a searcher built fresh from the updated rows returns
+ *     (ids, scores, counts, order), for every kernel, screening copy, mid copy, metric, num_results and source filter.
+ *     Positions, pcv_searcher_num_rows and _source_num_rows do not change; pcv_searcher_get_rows reads the new vector;
+ *   - a new vector a fresh build would not make searchable (non-finite norm; zero norm under PCV_METRIC_COSINE) makes the row
+ *     unsearchable; an unsearchable row that gets a valid vector becomes searchable.  A row whose id is hidden takes the new vector and stays hidden (unhiding returns it
+ *     with the new vector);
+ *   - all or nothing on bad input: duplicate ids in one call, n < 0, or NULL ids / rows with n > 0 give PCV_ERR_INVALID and
+ *     change nothing; n == 0 does nothing.  Every device buffer is allocated before the first row is written (a failed
+ *     allocation: PCV_ERR_DEVICE, nothing changed).  The rows go to the device through a bounded staging buffer, given back
+ *     at the end; the library keeps no host copy.
+ * Needs a finalized searcher (PCV_ERR_INVALID with pending rows) and no queued pass, as hide_ids does.  A mid copy that AUTO is
+ * building beside the searches is waited for first.  update_blobs takes n blobs of dim*4 bytes each, as add_blobs does. */
+pcv_status pcv_searcher_update_rows(pcv_searcher* s, const int64_t* ids, const float* rows, int64_t n, uint8_t* out_found,
+                                    int64_t* out_rows);
+pcv_status pcv_searcher_update_blobs(pcv_searcher* s, const int64_t* ids, const uint8_t* blobs, int64_t n, uint8_t* out_found,
+                                     int64_t* out_rows);
+
 /* Which scan kernel pcv_searcher_search uses. AUTO: wave-reduction kernel for n_queries <= 4,
  * MFMA tile kernel otherwise (up to 128 queries per corpus pass at dim <= 640; 256 with the int8 screening copy at
  * dim <= 384; among the ranks of a sharded search a pass is 128 queries on every rank, whatever copies each holds).

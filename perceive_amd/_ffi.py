@@ -122,6 +122,8 @@ SYMBOLS = {
     "pcv_searcher_hide_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
     "pcv_searcher_unhide_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
     "pcv_searcher_hidden_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P, _I64P]),
+    "pcv_searcher_update_rows": (C.c_int, [_P, _I64P, _F32P, C.c_int64, _U8P, _I64P]),
+    "pcv_searcher_update_blobs": (C.c_int, [_P, _I64P, _U8P, C.c_int64, _U8P, _I64P]),
     "pcv_searcher_set_kernel": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_screening_copy": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_mid_copy": (C.c_int, [_P, C.c_int]),

@@ -220,6 +220,16 @@ void launch_repack16_rows(hipStream_t st, const float4* blk, const float* scale,
 // ... the mid copy: items are blocks (scale8 != nullptr: every row of each, with the block's scale) or rows; rows >= mid_rows skipped
 void launch_repack_mid(hipStream_t st, const float4* blk, const float* scale, const float* scale8, const uint32_t* items, uint32_t n,
                        uint32_t mid_rows, uint4* mid16, float* scale16, int D4);
+// ---- updated items (pcv_searcher_update_rows) ----
+// launch_match_ids whose table also carries each id's slot in the batch (vals[h]; empty_slot for kIdEmpty): rows [row0, row1) of
+// a segment whose id is in the batch -> (out_rows[i], out_slots[i]) for the first `cap`, their number -> *out_n (zeroed here)
+void launch_match_id_slots(hipStream_t st, const int64_t* ids, uint32_t row0, uint32_t row1, const int64_t* table, const uint32_t* vals,
+                           uint32_t tmask, bool has_empty, uint32_t empty_slot, uint32_t* out_rows, uint32_t* out_slots,
+                           uint32_t* out_n, uint32_t cap);
+// rows[i] of a segment takes staged row (slots[i] & 0x7fffffff) - slot0 of `stage` ([.][D] f32) and its scale as launch_row_scales
+// computes it (max_norm_bits raised likewise); bit 31 of slots[i]: the row's id is hidden, its scale is 0
+void launch_update_rows(hipStream_t st, const float* stage, uint32_t slot0, const uint32_t* rows, const uint32_t* slots, uint32_t n,
+                        int D, int D4, int metric, float4* blk, float* scale, uint32_t* max_norm_bits);
 void launch_synth_fill(hipStream_t st, float4* blk, uint32_t nrows, uint32_t row0, int D, int D4, uint64_t seed,
                        int64_t first_row, int normalize, uint32_t n_clusters, float noise, float amp_lo = 0.0f, float amp_hi = 0.0f);
 void launch_gather_rows(hipStream_t st, const SegDesc* d_segs, int nseg, const int64_t* d_pos, int64_t n, int D,

@@ -693,6 +693,111 @@ __global__ __launch_bounds__(256) void repack_mid_kernel(const float4* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// updated items (pcv_searcher_update_rows, DESIGN.md §3 "Updated items"): new vectors written in place at the rows found by id;
+// the screening and mid copies are then re-packed by the unhide kernels above.  None of the scan kernels is involved.
+// ------------------------------------------------------------------------------------------------
+
+// match_ids_kernel with the batch index: the table carries, next to each id, its slot in the batch (vals[h] for table[h]; the
+// id kIdEmpty, if in the batch, has empty_slot).  Rows [row0, row1) of a segment whose id is in the batch -> (out_rows[i],
+// out_slots[i]) for the first `cap` of them; *out_n counts all.  One id per lane, one atomic per wave.
+__global__ __launch_bounds__(256) void match_id_slots_kernel(const int64_t* __restrict__ ids, uint32_t row0, uint32_t row1,
+                                                             const int64_t* __restrict__ table, const uint32_t* __restrict__ vals,
+                                                             uint32_t tmask, int has_empty, uint32_t empty_slot,
+                                                             uint32_t* __restrict__ out_rows, uint32_t* __restrict__ out_slots,
+                                                             uint32_t* __restrict__ out_n, uint32_t cap) {
+    const int lane = threadIdx.x & 63;
+    for (uint64_t base = (uint64_t)row0 + (uint64_t)blockIdx.x * 256 + (threadIdx.x & ~63u); base < row1;
+         base += (uint64_t)gridDim.x * 256) {
+        const uint32_t row = (uint32_t)base + lane;
+        bool hit = false;
+        uint32_t slot = 0;
+        if (row < row1) {
+            const int64_t id = __builtin_nontemporal_load(&ids[row]);
+            if (id == kIdEmpty) {
+                hit = has_empty != 0;
+                slot = empty_slot;
+            } else {
+                for (uint32_t h = id_hash(id, tmask);; h = (h + 1) & tmask) {
+                    const int64_t t = table[h];
+                    if (t == id) {
+                        hit = true;
+                        slot = vals[h];
+                        break;
+                    }
+                    if (t == kIdEmpty) break;
+                }
+            }
+        }
+        const unsigned long long ball = __ballot(hit);
+        if (ball) {
+            uint32_t at = 0;
+            if (lane == 0) at = atomicAdd(out_n, (uint32_t)__popcll(ball));
+            at = __shfl(at, 0);
+            if (hit) {
+                const uint32_t i = at + (uint32_t)__popcll(ball & ((1ull << lane) - 1ull));
+                if (i < cap) {
+                    out_rows[i] = row;
+                    out_slots[i] = slot;
+                }
+            }
+        }
+    }
+}
+
+// Write the new vectors, one wave per (rows[i], slots[i]) pair: staged row slots[i] - slot0 (row-major [.][D] f32; bit 31 of
+// slots[i] marks an id in the hidden set) goes into the blocked layout, zeros past D, as pack_rows_kernel stores it.  Lane 0
+// then gives the row its scale with row_scales_kernel's arithmetic restated operation for operation (f64 sum in feature order,
+// the same clamps and rounding; the same values, read from the staged row), raises max_norm as it does — hidden rows too, since
+// unhiding relies on max_norm covering them — and stores scale 0 for a hidden row.
+__global__ __launch_bounds__(256) void update_rows_kernel(const float* __restrict__ stage, uint32_t slot0,
+                                                          const uint32_t* __restrict__ rows, const uint32_t* __restrict__ slots,
+                                                          uint32_t n, int D, int D4, int metric, float4* __restrict__ blk,
+                                                          float* __restrict__ scale, uint32_t* max_norm_bits) {
+    const int lane = threadIdx.x & 63;
+    for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+        const uint32_t row = rows[i], sl = slots[i];
+        const bool hidden = (sl >> 31) != 0;
+        const float* src = stage + (size_t)((sl & 0x7fffffffu) - slot0) * D;
+        float4* dst = blk + (size_t)(row >> 5) * D4 * 32 + (row & 31);
+        for (int f4 = lane; f4 < D4; f4 += 64) {
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int f = f4 * 4 + j;
+                v[j] = f < D ? src[f] : 0.0f;
+            }
+            dst[(size_t)f4 * 32] = make_float4(v[0], v[1], v[2], v[3]);
+        }
+        if (lane == 0) {
+            double nx = 0.0;
+            for (int f4 = 0; f4 < D4; ++f4) {
+                float4 v;
+                v.x = 4 * f4 + 0 < D ? src[4 * f4 + 0] : 0.0f;
+                v.y = 4 * f4 + 1 < D ? src[4 * f4 + 1] : 0.0f;
+                v.z = 4 * f4 + 2 < D ? src[4 * f4 + 2] : 0.0f;
+                v.w = 4 * f4 + 3 < D ? src[4 * f4 + 3] : 0.0f;
+                nx += (double)v.x * (double)v.x;
+                nx += (double)v.y * (double)v.y;
+                nx += (double)v.z * (double)v.z;
+                nx += (double)v.w * (double)v.w;
+            }
+            const bool finite = nx < __builtin_inf();  // false for inf and NaN
+            float out;
+            if (metric == PCV_METRIC_DOT) {
+                out = finite ? 1.0f : 0.0f;
+            } else {
+                out = (finite && nx >= 0x1p-126) ? (float)(1.0 / sqrt(nx)) : 0.0f;
+            }
+            if (out != 0.0f) {
+                float nrm = (float)sqrt(nx) * 1.000001f;
+                atomicMax(max_norm_bits, __builtin_bit_cast(uint32_t, nrm));
+            }
+            scale[row] = hidden ? 0.0f : out;
+        }
+    }
+}
+
 struct SynthShape {  // n_clusters == 0: plain i.i.d. rows, times a per-row amplitude in [amp_lo, amp_lo + amp_span) if amp_span >= 0
     uint32_t n_clusters;
     float noise, inv_sqrt_d;
@@ -3254,6 +3359,25 @@ void launch_repack_mid(hipStream_t st, const float4* blk, const float* scale, co
     const uint64_t waves = (uint64_t)n * (scale8 ? 32u : 1u);
     const unsigned grid = (unsigned)std::min<uint64_t>((waves + 3) / 4, 1u << 16);
     repack_mid_kernel<<<grid, 256, 0, st>>>(blk, scale, scale8, items, n, mid_rows, mid16, scale16, D4);
+    PCV_LAUNCHED();
+}
+
+void launch_match_id_slots(hipStream_t st, const int64_t* ids, uint32_t row0, uint32_t row1, const int64_t* table, const uint32_t* vals,
+                           uint32_t tmask, bool has_empty, uint32_t empty_slot, uint32_t* out_rows, uint32_t* out_slots,
+                           uint32_t* out_n, uint32_t cap) {
+    PCV_HIP(hipMemsetAsync(out_n, 0, sizeof(uint32_t), st));
+    if (row0 >= row1) return;
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv64((int64_t)row1 - row0, 256), (int64_t)current_device_cus() * 16);
+    match_id_slots_kernel<<<grid, 256, 0, st>>>(ids, row0, row1, table, vals, tmask, has_empty ? 1 : 0, empty_slot, out_rows, out_slots,
+                                                out_n, cap);
+    PCV_LAUNCHED();
+}
+
+void launch_update_rows(hipStream_t st, const float* stage, uint32_t slot0, const uint32_t* rows, const uint32_t* slots, uint32_t n,
+                        int D, int D4, int metric, float4* blk, float* scale, uint32_t* max_norm_bits) {
+    if (n == 0) return;
+    const unsigned grid = (unsigned)std::min<uint32_t>((n + 3) / 4, 1u << 16);
+    update_rows_kernel<<<grid, 256, 0, st>>>(stage, slot0, rows, slots, n, D, D4, metric, blk, scale, max_norm_bits);
     PCV_LAUNCHED();
 }
 

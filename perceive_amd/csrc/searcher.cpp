@@ -14,6 +14,7 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <thread>
 #include <vector>
 
@@ -103,6 +104,8 @@ struct pcv_searcher {
     std::vector<int64_t> hidden;
     DevBuf<int64_t> d_idtab;         // the batch's hash table (scan.h: id_hash)
     DevBuf<uint32_t> d_hrows, d_hblocks, d_hcnt;
+    // updated items (pcv_searcher_update_rows): the slots next to d_idtab, the matches of a segment, the (row, slot) lists of a call
+    DevBuf<uint32_t> d_idslot, d_hslots, d_urows, d_uslots;
 
     // per-search workspace (sized for one pass of <= 128 queries)
     DevBuf<float> d_qf32, d_qraw, d_margin, d_margin32;
@@ -768,6 +771,176 @@ int64_t apply_id_batch(pcv_searcher* s, const std::vector<int64_t>& batch, bool 
         }
     PCV_HIP(hipGetLastError());
     return changed;
+}
+
+// ---- updated items (pcv_searcher_update_rows; DESIGN.md §3 "Updated items") ----
+constexpr uint32_t kSlotHidden = 0x80000000u;  // in a slot list: the slot's id is in the hidden set
+
+// The rows of one segment that a call rewrites: rows[i] takes the vector of batch slot slots[i] (ascending; kSlotHidden or-ed in),
+// and the blocks of the int8 copy they touch; off / boff: where the lists lie in d_urows / d_uslots and d_hblocks.
+struct UpdateSeg {
+    Segment* g = nullptr;
+    std::vector<uint32_t> rows, slots, blocks;
+    size_t off = 0, boff = 0;
+};
+
+// (row, slot) pairs of segment g for the batch ids[0..n): `by_id` lists the slots ascending by id, `sorted` their ids.  Implicit
+// ids (id0 + row) are found on the host; an id column is streamed once by match_id_slots_kernel (one round trip).
+std::vector<std::pair<uint32_t, uint32_t>> find_slots(pcv_searcher* s, const Segment& g, const int64_t* ids, int64_t n,
+                                                      const std::vector<uint32_t>& by_id, const std::vector<int64_t>& sorted,
+                                                      bool& table_up, uint32_t& tmask, bool& has_empty, uint32_t& empty_slot) {
+    hipStream_t st = s->ctx->stream;
+    std::vector<std::pair<uint32_t, uint32_t>> out;  // (slot, row)
+    if (!g.ids) {
+        for (auto it = std::lower_bound(sorted.begin(), sorted.end(), g.id0); it != sorted.end() && *it < g.id0 + (int64_t)g.nrows; ++it)
+            out.push_back({by_id[it - sorted.begin()], (uint32_t)(*it - g.id0)});
+        return out;
+    }
+    if (!table_up) {  // the batch's table, id -> slot (scan.h: id_hash)
+        size_t cap = 64;  // load <= 1/2
+        while (cap < 2 * (size_t)n) cap <<= 1;
+        std::vector<int64_t> tab(cap, kIdEmpty);
+        std::vector<uint32_t> val(cap, 0);
+        tmask = (uint32_t)(cap - 1);
+        for (int64_t i = 0; i < n; ++i) {
+            if (ids[i] == kIdEmpty) {
+                has_empty = true;
+                empty_slot = (uint32_t)i;
+                continue;
+            }
+            uint32_t h = id_hash(ids[i], tmask);
+            while (tab[h] != kIdEmpty) h = (h + 1) & tmask;
+            tab[h] = ids[i];
+            val[h] = (uint32_t)i;
+        }
+        PCV_HIP(hipMemcpyAsync(s->d_idtab.p, tab.data(), cap * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemcpyAsync(s->d_idslot.p, val.data(), cap * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipStreamSynchronize(st));  // (tab and val go out of scope)
+        table_up = true;
+    }
+    size_t cap = std::min<size_t>(g.nrows, std::max<size_t>(4096, 2 * (size_t)n));
+    for (;;) {
+        s->d_hrows.ensure(cap);
+        s->d_hslots.ensure(cap);
+        const uint32_t c = (uint32_t)std::min(s->d_hrows.n, s->d_hslots.n);
+        std::vector<uint32_t> rows(c), slots(c);
+        uint32_t cnt = 0;
+        launch_match_id_slots(st, g.ids, 0, g.nrows, s->d_idtab.p, s->d_idslot.p, tmask, has_empty, empty_slot, s->d_hrows.p,
+                              s->d_hslots.p, s->d_hcnt.p, c);
+        PCV_HIP(hipMemcpyAsync(&cnt, s->d_hcnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipMemcpyAsync(rows.data(), s->d_hrows.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipMemcpyAsync(slots.data(), s->d_hslots.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        if (cnt > c) {  // (more rows carry these ids than the lists had room for: once more with room for all)
+            cap = cnt;
+            continue;
+        }
+        out.reserve(cnt);
+        for (uint32_t i = 0; i < cnt; ++i) out.push_back({slots[i], rows[i]});
+        return out;
+    }
+}
+
+// Every row, in every source, whose id is ids[i] takes the vector rows[i] (n rows of D f32, or their little-endian blob bytes);
+// found[i] = 1 iff some row carries ids[i] (ids distinct, found zeroed).  Returns the rows rewritten.  Every row is found and every
+// buffer allocated before the first row is written.
+int64_t update_by_id(pcv_searcher* s, const int64_t* ids, const void* rows, int64_t n, const std::vector<uint32_t>& by_id,
+                     std::vector<uint8_t>& found) {
+    hipStream_t st = s->ctx->stream;
+    std::vector<int64_t> sorted(n);
+    for (int64_t i = 0; i < n; ++i) sorted[i] = ids[by_id[i]];
+    {
+        size_t cap = 64;
+        while (cap < 2 * (size_t)n) cap <<= 1;
+        PCV_REQUIRE(cap <= ((size_t)1 << 32), "update: %lld ids in one batch", (long long)n);
+        s->d_idtab.ensure(cap);
+        s->d_idslot.ensure(cap);
+        s->d_hcnt.ensure(1);
+    }
+    // 1. find the rows
+    bool table_up = false, has_empty = false;
+    uint32_t tmask = 0, empty_slot = 0;
+    std::vector<UpdateSeg> us;
+    size_t total = 0, total_blocks = 0;
+    for (auto& src : s->sources)
+        for (auto& g : src.segs) {
+            if (g.nrows == 0) continue;
+            auto pr = find_slots(s, g, ids, n, by_id, sorted, table_up, tmask, has_empty, empty_slot);
+            if (pr.empty()) continue;
+            std::sort(pr.begin(), pr.end());
+            UpdateSeg u;
+            u.g = &g;
+            for (const auto& p : pr) {
+                found[p.first] = 1;
+                const bool hidden = std::binary_search(s->hidden.begin(), s->hidden.end(), ids[p.first]);
+                u.rows.push_back(p.second);
+                u.slots.push_back(p.first | (hidden ? kSlotHidden : 0u));
+                if (g.blk8 && p.second < g.copied_rows) u.blocks.push_back(p.second / kBlockRows);
+            }
+            std::sort(u.blocks.begin(), u.blocks.end());
+            u.blocks.erase(std::unique(u.blocks.begin(), u.blocks.end()), u.blocks.end());
+            u.off = total;
+            u.boff = total_blocks;
+            total += u.rows.size();
+            total_blocks += u.blocks.size();
+            us.push_back(std::move(u));
+        }
+    if (total == 0) return 0;
+    // 2. every buffer the writes need
+    s->d_urows.ensure(total);
+    s->d_uslots.ensure(total);
+    if (total_blocks) s->d_hblocks.ensure(total_blocks);
+    s->d_stage.ensure((size_t)std::min<int64_t>(n, kStageRows) * s->D);
+    for (const auto& u : us) {
+        PCV_HIP(hipMemcpyAsync(s->d_urows.p + u.off, u.rows.data(), u.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemcpyAsync(s->d_uslots.p + u.off, u.slots.data(), u.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (!u.blocks.empty())
+            PCV_HIP(hipMemcpyAsync(s->d_hblocks.p + u.boff, u.blocks.data(), u.blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                   st));
+    }
+    // 3. the rows and their scales, the batch staged in steps of kStageRows slots (steps no row takes a vector from are skipped)
+    const size_t row_bytes = (size_t)s->D * sizeof(float);
+    auto slot_less = [](uint32_t a, uint32_t b) { return (a & ~kSlotHidden) < b; };
+    for (int64_t c0 = 0; c0 < n; c0 += kStageRows) {
+        const int64_t m = std::min<int64_t>(kStageRows, n - c0);
+        bool staged = false;
+        for (const auto& u : us) {
+            const size_t lo = std::lower_bound(u.slots.begin(), u.slots.end(), (uint32_t)c0, slot_less) - u.slots.begin();
+            const size_t hi = std::lower_bound(u.slots.begin(), u.slots.end(), (uint32_t)(c0 + m), slot_less) - u.slots.begin();
+            if (lo == hi) continue;
+            if (!staged) {
+                PCV_HIP(hipMemcpyAsync(s->d_stage.p, (const uint8_t*)rows + (size_t)c0 * row_bytes, (size_t)m * row_bytes,
+                                       hipMemcpyHostToDevice, st));
+                staged = true;
+            }
+            launch_update_rows(st, s->d_stage.p, (uint32_t)c0, s->d_urows.p + u.off + lo, s->d_uslots.p + u.off + lo, (uint32_t)(hi - lo),
+                               s->D, s->D4, s->metric, u.g->blk, u.g->scale, s->d_max_norm_bits);
+        }
+        if (staged) PCV_HIP(hipStreamSynchronize(st));  // the staging buffer (and the caller's memory) are free again
+    }
+    // 4. the copies, as unhide_found makes them: bf16 pieces row by row, the WHOLE blocks of the int8 copy (a new row may need a
+    // smaller s_blk) and of a mid copy quantised with it, other mid copies row by row
+    for (const auto& u : us) {
+        Segment& g = *u.g;
+        const uint32_t nr = (uint32_t)u.rows.size(), nb = (uint32_t)u.blocks.size();
+        const uint32_t* d_rows = s->d_urows.p + u.off;
+        const uint32_t* d_blocks = nb ? s->d_hblocks.p + u.boff : nullptr;
+        if (g.blk16) launch_repack16_rows(st, g.blk, g.scale, d_rows, nr, g.blk16, s->D4);
+        if (g.blk8 && nb) launch_repack8_blocks(st, g.blk, g.scale, d_blocks, nb, g.blk8, g.scale8, s->D4);
+        if (g.mid16 && g.mid_rows > 0) {
+            if (g.blk8 && g.copied_rows >= g.nrows)  // (launch_mid_pack quantised it with the int8 copy's block scales)
+                launch_repack_mid(st, g.blk, g.scale, g.scale8, d_blocks, nb, g.mid_rows, g.mid16, g.scale16, s->D4);
+            else
+                launch_repack_mid(st, g.blk, g.scale, nullptr, d_rows, nr, g.mid_rows, g.mid16, g.scale16, s->D4);
+        }
+    }
+    // 5. the corpus bound the dot-metric screens use (it only grows: update_rows_kernel raised it for the new rows)
+    uint32_t bits = 0;
+    PCV_HIP(hipMemcpyAsync(&bits, s->d_max_norm_bits, 4, hipMemcpyDeviceToHost, st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    std::memcpy(&s->max_norm, &bits, 4);
+    return (int64_t)total;
 }
 
 void do_finalize(pcv_searcher* s) {
@@ -1474,6 +1647,10 @@ pcv_status pcv_searcher_destroy(pcv_searcher* s) {
         s->d_hrows.release();
         s->d_hblocks.release();
         s->d_hcnt.release();
+        s->d_idslot.release();
+        s->d_hslots.release();
+        s->d_urows.release();
+        s->d_uslots.release();
         if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
         if (s->pin) (void)hipHostFree(s->pin);
         if (s->pin_pass) (void)hipHostFree(s->pin_pass);
@@ -1697,6 +1874,48 @@ pcv_status pcv_searcher_hidden_ids(pcv_searcher* s, int64_t* out_ids, int64_t ca
             *out_hidden_rows = rows;
         }
     });
+}
+
+static pcv_status update_call(pcv_searcher* s, const int64_t* ids, const void* rows, int64_t n, uint8_t* out_found, int64_t* out_rows,
+                              const char* who) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
+        PCV_REQUIRE(n >= 0 && ((ids != nullptr && rows != nullptr) || n == 0), "%s: bad ids/rows/n (NULL with n > 0, or n < 0)", who);
+        PCV_REQUIRE(n <= 0x7fffffff, "%s: %lld ids in one call", who, (long long)n);
+        const uint32_t probe = 1;  // (blobs: little-endian f32, as pcv_searcher_add_blobs reads them)
+        PCV_REQUIRE(*reinterpret_cast<const uint8_t*>(&probe) == 1, "%s: big-endian host", who);
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
+        PCV_REQUIRE(!s->pending.active, "%s: a queued pass has not been collected", who);
+        if (out_rows) *out_rows = 0;
+        if (out_found && n > 0) std::memset(out_found, 0, (size_t)n);
+        if (n == 0) return;
+        std::vector<uint32_t> by_id(n);  // slots ascending by id: no id twice
+        std::iota(by_id.begin(), by_id.end(), 0u);
+        std::sort(by_id.begin(), by_id.end(), [&](uint32_t a, uint32_t b) { return ids[a] < ids[b]; });
+        for (int64_t i = 1; i < n; ++i)
+            PCV_REQUIRE(ids[by_id[i - 1]] != ids[by_id[i]], "%s: id %lld appears twice in the batch", who, (long long)ids[by_id[i]]);
+        PCV_HIP(hipSetDevice(s->ctx->device));
+        settle_mid_build(s, true);  // (the AUTO mid build reads the rows and scales and writes the mid copy)
+        std::vector<uint8_t> found((size_t)n, 0);
+        struct StageBack {  // the staging buffer goes back, whatever happens (as finalize gives it back)
+            pcv_searcher* s;
+            ~StageBack() { s->d_stage.release(); }
+        } stage_back{s};
+        const int64_t changed = update_by_id(s, ids, rows, n, by_id, found);
+        if (out_found) std::memcpy(out_found, found.data(), (size_t)n);
+        if (out_rows) *out_rows = changed;
+    });
+}
+
+pcv_status pcv_searcher_update_rows(pcv_searcher* s, const int64_t* ids, const float* rows, int64_t n, uint8_t* out_found,
+                                    int64_t* out_rows) {
+    return update_call(s, ids, rows, n, out_found, out_rows, "update_rows");
+}
+
+pcv_status pcv_searcher_update_blobs(pcv_searcher* s, const int64_t* ids, const uint8_t* blobs, int64_t n, uint8_t* out_found,
+                                     int64_t* out_rows) {
+    return update_call(s, ids, blobs, n, out_found, out_rows, "update_blobs");
 }
 
 pcv_status pcv_searcher_dim(pcv_searcher* s, int* out_dim) {

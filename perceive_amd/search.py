@@ -364,6 +364,51 @@ class Searcher:
         _ffi.check(fn(self._handle, _ffi.i64p(a) if a.size else None, a.size, C.byref(rows)))
         return rows.value
 
+    # ---- updated items (pcv_searcher_update_rows) ---------------------------------------------------
+    # A re-embedded item takes its new vector in place, in every row carrying its id, without a rebuild; searches afterwards return
+    # what a searcher built fresh from the updated rows returns.
+    def update_items(self, ids, rows):
+        """Rows carrying ids[i] take rows[i] ([n, dim] f32).  Returns (found: bool [n], rows_changed); ids no row carries change
+        nothing.  Needs a finalized searcher; duplicate ids are refused."""
+        ids = self._update_ids(ids)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.shape != (ids.size, self.dim):
+            raise ValueError(f"rows must be [{ids.size}, {self.dim}]")
+        return self._update_call(_ffi.lib().pcv_searcher_update_rows, ids, _ffi.f32p(rows) if ids.size else None)
+
+    def update_blobs(self, ids, blobs: bytes, n):
+        """update_items with the vectors as n embedding blobs of dim*4 bytes (serialize_embedding), as add_blobs takes them."""
+        ids = self._update_ids(ids)
+        b = np.frombuffer(blobs, dtype=np.uint8)
+        if ids.size != n or b.size != n * self.dim * 4:
+            raise ValueError("ids / blob bytes do not match n, n*dim*4")
+        return self._update_call(_ffi.lib().pcv_searcher_update_blobs, ids, _ffi.u8p(b) if n else None)
+
+    def upsert_items(self, source_id, ids, rows):
+        """What a source scan produces (update_db.rs upserts New / Changed embeddings): ids some row carries take their new vector
+        in place, the others are added to `source_id`; then finalize.  Returns (rows_replaced, rows_appended)."""
+        ids = self._update_ids(ids)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        found, replaced = self.update_items(ids, rows)
+        new = ~found
+        if new.any():
+            self.add_rows(source_id, rows[new], ids[new])
+        self.finalize()
+        return replaced, int(new.sum())
+
+    @staticmethod
+    def _update_ids(ids):
+        a = np.ascontiguousarray(ids if isinstance(ids, np.ndarray) else np.fromiter(ids, dtype=np.int64), dtype=np.int64)
+        if a.ndim != 1:
+            raise ValueError("ids must be 1-D")
+        return a
+
+    def _update_call(self, fn, ids, rows_p):
+        found = np.zeros(max(ids.size, 1), dtype=np.uint8)
+        n = C.c_int64()
+        _ffi.check(fn(self._handle, _ffi.i64p(ids) if ids.size else None, rows_p, ids.size, _ffi.u8p(found), C.byref(n)))
+        return found[: ids.size].astype(bool), n.value
+
     def last_stats(self):
         st = _ffi.ScanStats()
         _ffi.check(_ffi.lib().pcv_searcher_last_stats(self._handle, C.byref(st)))

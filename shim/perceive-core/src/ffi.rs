@@ -170,6 +170,8 @@ extern "C" {
     pub fn pcv_searcher_hide_ids(s: *mut pcv_searcher, ids: *const i64, n: i64, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_unhide_ids(s: *mut pcv_searcher, ids: *const i64, n: i64, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_hidden_ids(s: *mut pcv_searcher, out_ids: *mut i64, cap: i64, out_n: *mut i64, out_hidden_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_update_rows(s: *mut pcv_searcher, ids: *const i64, rows: *const f32, n: i64, out_found: *mut u8, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_update_blobs(s: *mut pcv_searcher, ids: *const i64, blobs: *const u8, n: i64, out_found: *mut u8, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_set_kernel(s: *mut pcv_searcher, kernel: c_int) -> c_int;
     pub fn pcv_searcher_set_candidate_capacity(s: *mut pcv_searcher, n_candidates: u32) -> c_int;
     pub fn pcv_searcher_set_tuning(s: *mut pcv_searcher, flags: u32) -> c_int;

@@ -207,6 +207,46 @@ impl Searcher {
         Ok(())
     }
 
+    /// Upsert the embeddings a source scan produced (update_db.rs:54-60,75-126 writes them to `item_embeddings` with
+    /// `ON CONFLICT ... DO UPDATE`): items the index holds take their new vector in place, in every row carrying their id
+    /// (no rebuild; searches afterwards return what an index built fresh from the new rows returns); the others are added
+    /// to `source_id`.  Hidden items take the new vector and stay hidden.  `perceive source scan` (cmd/source.rs:313) would
+    /// call this with the `New` / `Changed` embeddings of the scan where it now calls `rebuild_search`:
+    ///     `searcher.update_items(source.id, &embeddings)?;`
+    pub fn update_items(&mut self, source_id: i64, items: &[(i64, Vec<f32>)]) -> Result<(), HipError> {
+        if items.is_empty() {
+            return Ok(());
+        }
+        if self.handle.is_null() {
+            let ctx = hip::context()?;
+            hip::check(unsafe {
+                ffi::pcv_searcher_create(ctx.0, items[0].1.len() as i32, ffi::PCV_METRIC_DOT, &mut self.handle)
+            })?;
+            let ids: Vec<i64> = self.hidden.iter().copied().collect();
+            hip::check(unsafe { ffi::pcv_searcher_hide_ids(self.handle, ids.as_ptr(), ids.len() as i64, ptr::null_mut()) })?;
+        }
+        let ids: Vec<i64> = items.iter().map(|(id, _)| *id).collect();
+        let rows: Vec<f32> = items.iter().flat_map(|(_, v)| v.iter().copied()).collect();
+        let mut found = vec![0u8; items.len()];
+        let mut changed: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_update_rows(self.handle, ids.as_ptr(), rows.as_ptr(), ids.len() as i64, found.as_mut_ptr(), &mut changed)
+        })?;
+        let (mut new_ids, mut new_rows) = (Vec::new(), Vec::new());
+        for (i, (id, v)) in items.iter().enumerate() {
+            if found[i] == 0 {
+                new_ids.push(*id);
+                new_rows.extend_from_slice(v);
+            }
+        }
+        if !new_ids.is_empty() {
+            hip::check(unsafe {
+                ffi::pcv_searcher_add_rows(self.handle, source_id, new_ids.as_ptr(), new_rows.as_ptr(), new_ids.len() as i64)
+            })?;
+        }
+        hip::check(unsafe { ffi::pcv_searcher_finalize(self.handle) })
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
