@@ -100,6 +100,62 @@ private:
     pcv_comm* h_ = nullptr;
 };
 
+// Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
+// like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
+class SearcherView {
+public:
+    SearcherView(pcv_searcher* parent, const std::vector<int64_t>& ids) {
+        check(pcv_searcher_create_view(parent, ids.data(), (int64_t)ids.size(), &h_));
+    }
+    ~SearcherView() {
+        if (h_) pcv_searcher_destroy(h_);
+    }
+    SearcherView(SearcherView&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    SearcherView& operator=(SearcherView&& o) noexcept {
+        if (this != &o) {
+            if (h_) pcv_searcher_destroy(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    SearcherView(const SearcherView&) = delete;
+    SearcherView& operator=(const SearcherView&) = delete;
+
+    // Searcher::search_vector among the view's items
+    std::vector<SearchItem> search_vector(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector) const {
+        if (sources.empty()) return {};
+        std::vector<int64_t> ids(num_results);
+        std::vector<float> scores(num_results);
+        int count = 0;
+        check(pcv_searcher_search(h_, vector.data(), 1, sources.data(), (int)sources.size(), (int)num_results, ids.data(), scores.data(),
+                                  &count));
+        std::vector<SearchItem> out;
+        for (int i = 0; i < count; ++i) out.push_back({ids[i], scores[i]});
+        return out;
+    }
+    int64_t num_rows() const {
+        int64_t n = 0;
+        check(pcv_searcher_num_rows(h_, &n));
+        return n;
+    }
+    // copies of the parent's rows made since the view was created (one per parent change that a call of the view came after)
+    int refreshes() const {
+        int32_t r = 0;
+        check(pcv_searcher_view_stats(h_, nullptr, nullptr, &r, nullptr));
+        return r;
+    }
+    pcv_scan_stats last_stats() const {
+        pcv_scan_stats st;
+        check(pcv_searcher_last_stats(h_, &st));
+        return st;
+    }
+    pcv_searcher* handle() const { return h_; }
+
+private:
+    pcv_searcher* h_ = nullptr;
+};
+
 // search.rs:29-260.  Metric::Dot reproduces the reference Searcher's scores exactly
 // (max(0, 1 - dot/len), ascending); Metric::Cosine is lib.rs:67-77.
 class Searcher {
@@ -222,6 +278,8 @@ public:
         check(pcv_searcher_finalize(h_));
         return {replaced, (int64_t)new_ids.size()};
     }
+    // a search restricted to `ids` (the items of a tag, of an author, earlier results): SQL gives the ids, the view searches them
+    SearcherView view(const std::vector<int64_t>& ids) const { return SearcherView(h_, ids); }
     // capacity hint: the rows about to be added to `source_id` land in one device segment
     void reserve(int64_t source_id, int64_t n_rows) { check(pcv_searcher_reserve(h_, source_id, n_rows)); }
     // narrow screening copy of the rows next to the f32 rows (a half / a quarter of the bytes per scan, same results):

@@ -209,6 +209,37 @@ pcv_status pcv_searcher_update_rows(pcv_searcher* s, const int64_t* ids, const f
 pcv_status pcv_searcher_update_blobs(pcv_searcher* s, const int64_t* ids, const uint8_t* blobs, int64_t n, uint8_t* out_found,
                                      int64_t* out_rows);
 
+/* Views (a search restricted to a set of items: the items of a tag, of an author, "search again within these results"): a
+ * read-only searcher handle that holds a compact device copy of the rows of `parent` whose id is in ids[0..n).
+ *   - exact: every search of the view returns bit for bit what a searcher built fresh from only those rows returns (ids, scores,
+ *     counts, order) — the rows added in the parent's source order and row order, with the parent's hidden set applied —, for
+ *     every kernel, screening copy, metric, num_results and source filter;
+ *   - every search entry point takes a view (pcv_searcher_search, _search_device, _search_device_begin[_dq] / _end,
+ *     _search_sharded[_dq]), and so do _last_stats, _num_rows, _num_segments, _num_sources, _source_ids, _source_num_rows,
+ *     _set_kernel, _set_candidate_capacity, _set_tuning, _repeat_without_guess.  A view keeps one source per parent source
+ *     with matches, in parent order; the source filter behaves as on the parent (PCV_STAGING_SOURCE rows only for a search
+ *     that names that source);
+ *   - positions: a hit that carries one (pcv_hit.pos of _search_device, _begin / _end, the sharded exchange) carries the
+ *     PARENT's position, shard offset included, so view lists of several ranks merge with pcv_merge_topk* like parent lists;
+ *   - read-only: add / reserve / finalize / clear / replace / hide / unhide / update / set_shard_offset /
+ *     set_screening_copy / set_mid_copy and get_rows give PCV_ERR_INVALID on a view;
+ *   - never stale: every parent call that may change a result (finalize, hide / unhide, update, clear / replace source,
+ *     set_screening_copy OFF, set_shard_offset) makes the view copy the rows again, from its stored id list and under the
+ *     parent's lock, at the start of its next call.  Rows added to the parent later with an allowed id join the view after the
+ *     parent's finalize (a view call fails with PCV_ERR_INVALID while the parent has cleared rows without a finalize).  A
+ *     view must not be used concurrently with its parent;
+ *   - a view has its own pass workspace and statistics: searching it does not change how the parent's next search runs.
+ *     It keeps the screening copy its parent keeps, and a mid copy only if the parent's mode is PCV_MID_COPY_ON;
+ *   - pcv_searcher_destroy(view) frees it; pcv_searcher_destroy(parent) gives PCV_ERR_INVALID while views of it are alive.
+ * create_view needs a finalized parent without a queued pass.  Duplicate ids and ids that match no row are allowed; n == 0
+ * makes an empty view.  NULL ids with n > 0, n < 0, or a view as the parent give PCV_ERR_INVALID; a failed allocation
+ * PCV_ERR_DEVICE, with nothing left allocated. */
+pcv_status pcv_searcher_create_view(pcv_searcher* parent, const int64_t* ids, int64_t n, pcv_searcher** out_view);
+/* A view's state (after bringing it up to date with its parent): rows it holds (every source, PCV_STAGING_SOURCE included),
+ * distinct ids of its allow list, how many times it was copied again from its parent, and the device time in ms of its
+ * last copy.  Any pointer may be NULL.  PCV_ERR_INVALID for a searcher that is not a view. */
+pcv_status pcv_searcher_view_stats(pcv_searcher* view, int64_t* out_rows, int64_t* out_ids, int32_t* out_refreshes, float* out_build_ms);
+
 /* Which scan kernel pcv_searcher_search uses. AUTO: wave-reduction kernel for n_queries <= 4,
  * MFMA tile kernel otherwise (up to 128 queries per corpus pass at dim <= 640; 256 with the int8 screening copy at
  * dim <= 384; among the ranks of a sharded search a pass is 128 queries on every rank, whatever copies each holds).

@@ -6,6 +6,7 @@ from .context import Context, device_count  # noqa: F401
 from .search import (  # noqa: F401
     SearchItem,
     Searcher,
+    SearcherView,
     cosine_similarity_multi_query,
     cosine_similarity_single_query,
     deserialize_embedding,

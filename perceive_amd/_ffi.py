@@ -124,6 +124,8 @@ SYMBOLS = {
     "pcv_searcher_hidden_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P, _I64P]),
     "pcv_searcher_update_rows": (C.c_int, [_P, _I64P, _F32P, C.c_int64, _U8P, _I64P]),
     "pcv_searcher_update_blobs": (C.c_int, [_P, _I64P, _U8P, C.c_int64, _U8P, _I64P]),
+    "pcv_searcher_create_view": (C.c_int, [_P, _I64P, C.c_int64, C.POINTER(_P)]),
+    "pcv_searcher_view_stats": (C.c_int, [_P, _I64P, _I64P, _INTP, _F32P]),
     "pcv_searcher_set_kernel": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_screening_copy": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_mid_copy": (C.c_int, [_P, C.c_int]),

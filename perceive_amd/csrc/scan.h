@@ -230,6 +230,21 @@ void launch_match_id_slots(hipStream_t st, const int64_t* ids, uint32_t row0, ui
 // computes it (max_norm_bits raised likewise); bit 31 of slots[i]: the row's id is hidden, its scale is 0
 void launch_update_rows(hipStream_t st, const float* stage, uint32_t slot0, const uint32_t* rows, const uint32_t* slots, uint32_t n,
                         int D, int D4, int metric, float4* blk, float* scale, uint32_t* max_norm_bits);
+// ---- views (pcv_searcher_create_view) ----
+// Selection of the rows of a segment whose id is in the table, in row order: scratch flags4[view_tiles(nrows) * 256] and
+// tile_cnt[view_tiles(nrows)]; launch_view_select leaves the tiles' offsets in tile_cnt and the number of rows in *total, then
+// launch_view_compact writes the rows, ascending, to sel[0..*total).
+uint32_t view_tiles(uint32_t nrows);
+void launch_view_select(hipStream_t st, const int64_t* ids, uint32_t nrows, const int64_t* table, uint32_t tmask, bool has_empty,
+                        uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total);
+void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel);
+// rows [dst_row0, dst_row0 + n_sel) of a view segment take rows sel[0..n_sel) of a parent segment (pieces, scale, id; parent
+// position pos0 + row -> dst_ppos[row of the view segment]); rows [dst_row0 + n_sel, dst_end) become padding
+void launch_view_gather(hipStream_t st, const float4* src_blk, const float* src_scale, const int64_t* src_ids, int64_t src_id0,
+                        int64_t src_pos0, const uint32_t* sel, uint32_t n_sel, int D4, uint32_t dst_row0, uint32_t dst_end,
+                        float4* dst_blk, float* dst_scale, int64_t* dst_ids, int64_t* dst_ppos);
+// hits[0..n): pos in [0, nrows) -> ppos[pos]
+void launch_view_remap(hipStream_t st, pcv_hit_dev* hits, int64_t n, const int64_t* ppos, int64_t nrows);
 void launch_synth_fill(hipStream_t st, float4* blk, uint32_t nrows, uint32_t row0, int D, int D4, uint64_t seed,
                        int64_t first_row, int normalize, uint32_t n_clusters, float noise, float amp_lo = 0.0f, float amp_hi = 0.0f);
 void launch_gather_rows(hipStream_t st, const SegDesc* d_segs, int nseg, const int64_t* d_pos, int64_t n, int D,

@@ -798,6 +798,148 @@ __global__ __launch_bounds__(256) void update_rows_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// views (pcv_searcher_create_view, DESIGN.md §3 "Views"): the rows of a parent segment whose id is in an allow list, copied in
+// parent row order into the view's own blocked layout.  Selection keeps row order: a flag per row and a count per tile of
+// kViewTile rows (view_mark_kernel), an exclusive scan of the tile counts (view_scan_kernel), then each tile writes its rows at
+// its offset (view_compact_kernel).  None of the kernels above is involved.
+// ------------------------------------------------------------------------------------------------
+constexpr int kViewTile = 1024;  // rows per tile: 4 consecutive rows per thread of a 256-thread workgroup
+
+// Exclusive prefix of one value per thread over a 256-thread workgroup; *total = the sum.  `part`: 4 words of LDS.
+__device__ __forceinline__ uint32_t view_block_scan(uint32_t v, uint32_t* part, uint32_t& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) part[w] = x;
+    __syncthreads();
+    uint32_t base = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t p = part[i];
+        base += i < w ? p : 0u;
+        total += p;
+    }
+    __syncthreads();  // (part may be written again)
+    return base + x - v;
+}
+
+// Rows of a segment whose id is in the batch's hash table (scan.h: id_hash): flags4[tile * 256 + t] holds the flags of rows
+// tile * kViewTile + 4t .. 4t + 3 in bits 0, 8, 16, 24; tile_cnt[tile] = how many rows of the tile are flagged.
+__global__ __launch_bounds__(256) void view_mark_kernel(const int64_t* __restrict__ ids, uint32_t nrows, const int64_t* __restrict__ table,
+                                                        uint32_t tmask, int has_empty, uint32_t* __restrict__ flags4,
+                                                        uint32_t* __restrict__ tile_cnt) {
+    __shared__ uint32_t part[4];
+    const uint64_t r0 = (uint64_t)blockIdx.x * kViewTile + threadIdx.x * 4u;
+    uint32_t f = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint64_t row = r0 + j;
+        if (row >= nrows) break;
+        const int64_t id = __builtin_nontemporal_load(&ids[row]);
+        bool hit = false;
+        if (id == kIdEmpty) {
+            hit = has_empty != 0;
+        } else {
+            for (uint32_t h = id_hash(id, tmask);; h = (h + 1) & tmask) {
+                const int64_t t = table[h];
+                if (t == id) {
+                    hit = true;
+                    break;
+                }
+                if (t == kIdEmpty) break;
+            }
+        }
+        if (hit) f |= 1u << (8 * j);
+    }
+    flags4[(size_t)blockIdx.x * 256 + threadIdx.x] = f;
+    uint32_t total = 0;
+    (void)view_block_scan((uint32_t)__popc(f), part, total);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+}
+
+// tile_cnt[0..ntiles) -> their exclusive prefix sums in place, the sum -> *total.  One workgroup, each thread a contiguous run.
+__global__ __launch_bounds__(256) void view_scan_kernel(uint32_t* __restrict__ tile_cnt, uint32_t ntiles, uint32_t* __restrict__ total) {
+    __shared__ uint32_t part[4];
+    const uint32_t per = (ntiles + 255) / 256;
+    const uint32_t t0 = (uint32_t)std::min<uint64_t>((uint64_t)threadIdx.x * per, ntiles);
+    const uint32_t t1 = (uint32_t)std::min<uint64_t>((uint64_t)t0 + per, ntiles);
+    uint32_t s = 0;
+    for (uint32_t i = t0; i < t1; ++i) s += tile_cnt[i];
+    uint32_t sum = 0;
+    uint32_t at = view_block_scan(s, part, sum);
+    for (uint32_t i = t0; i < t1; ++i) {
+        const uint32_t c = tile_cnt[i];
+        tile_cnt[i] = at;
+        at += c;
+    }
+    if (threadIdx.x == 0) *total = sum;
+}
+
+// The flagged rows, ascending: tile `blockIdx.x` writes its rows from sel[tile_off[tile]] on.
+__global__ __launch_bounds__(256) void view_compact_kernel(const uint32_t* __restrict__ flags4, const uint32_t* __restrict__ tile_off,
+                                                           uint32_t* __restrict__ sel) {
+    __shared__ uint32_t part[4];
+    const uint32_t f = flags4[(size_t)blockIdx.x * 256 + threadIdx.x];
+    uint32_t total = 0;
+    uint32_t at = tile_off[blockIdx.x] + view_block_scan((uint32_t)__popc(f), part, total);
+    const uint32_t r0 = blockIdx.x * (uint32_t)kViewTile + threadIdx.x * 4u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if ((f >> (8 * j)) & 1u) sel[at++] = r0 + j;
+}
+
+// Rows [dst_row0, dst_end) of a view segment: row dst_row0 + i takes row sel[i] of a parent segment for i < n_sel — its 16-byte
+// pieces, its scale (0 keeps a hidden or unsearchable row unsearchable), its id (id0 + row for implicit ids) and its parent
+// position pos0 + row (dst_ppos[c]) —; the rows after those are padding (zeros, scale 0, id -1).  One thread per piece, as
+// pack_rows_kernel: lanes 0..31 are the 32 rows of a block, the two halves of a wave neighbouring pieces, so a wave writes 1 KB
+// contiguously (consecutive view rows); the reads are as contiguous as the selected rows are.
+__global__ __launch_bounds__(256) void view_gather_kernel(const float4* __restrict__ src_blk, const float* __restrict__ src_scale,
+                                                          const int64_t* __restrict__ src_ids, int64_t src_id0, int64_t src_pos0,
+                                                          const uint32_t* __restrict__ sel, uint32_t n_sel, int D4, uint32_t dst_row0,
+                                                          uint32_t dst_end, float4* __restrict__ dst_blk, float* __restrict__ dst_scale,
+                                                          int64_t* __restrict__ dst_ids, int64_t* __restrict__ dst_ppos, int64_t threads) {
+    const uint64_t first_blk = dst_row0 >> 5;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < threads; t += (int64_t)gridDim.x * 256) {
+        const uint32_t r = (uint32_t)(t & 31);
+        const int64_t u = t >> 5;
+        const int f4 = (int)(u % D4);
+        const uint64_t b = first_blk + (uint64_t)(u / D4);
+        const uint64_t c = b * 32 + r;
+        if (c < dst_row0 || c >= dst_end) continue;
+        const uint32_t i = (uint32_t)(c - dst_row0);
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (i < n_sel) {
+            const uint32_t row = sel[i];
+            v = src_blk[((size_t)(row >> 5) * D4 + f4) * 32 + (row & 31)];
+            if (f4 == 0) {
+                dst_scale[c] = src_scale[row];
+                dst_ids[c] = src_ids ? src_ids[row] : src_id0 + row;
+                dst_ppos[c] = src_pos0 + row;
+            }
+        } else if (f4 == 0) {
+            dst_scale[c] = 0.0f;
+            dst_ids[c] = -1;
+        }
+        dst_blk[(b * D4 + f4) * 32 + r] = v;
+    }
+}
+
+// Hit lists of a view: a position p in [0, nrows) (the view's own numbering) becomes its parent's position ppos[p]; empty slots
+// (p < 0) stay.
+__global__ __launch_bounds__(256) void view_remap_kernel(pcv_hit_dev* __restrict__ hits, int64_t n, const int64_t* __restrict__ ppos,
+                                                         int64_t nrows) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = hits[i].pos;
+    if (p >= 0 && p < nrows) hits[i].pos = ppos[p];
+}
+
 struct SynthShape {  // n_clusters == 0: plain i.i.d. rows, times a per-row amplitude in [amp_lo, amp_lo + amp_span) if amp_span >= 0
     uint32_t n_clusters;
     float noise, inv_sqrt_d;
@@ -3378,6 +3520,46 @@ void launch_update_rows(hipStream_t st, const float* stage, uint32_t slot0, cons
     if (n == 0) return;
     const unsigned grid = (unsigned)std::min<uint32_t>((n + 3) / 4, 1u << 16);
     update_rows_kernel<<<grid, 256, 0, st>>>(stage, slot0, rows, slots, n, D, D4, metric, blk, scale, max_norm_bits);
+    PCV_LAUNCHED();
+}
+
+uint32_t view_tiles(uint32_t nrows) { return (nrows + kViewTile - 1) / kViewTile; }
+
+void launch_view_select(hipStream_t st, const int64_t* ids, uint32_t nrows, const int64_t* table, uint32_t tmask, bool has_empty,
+                        uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total) {
+    const uint32_t nt = view_tiles(nrows);
+    if (nt == 0) {
+        PCV_HIP(hipMemsetAsync(total, 0, sizeof(uint32_t), st));
+        return;
+    }
+    view_mark_kernel<<<nt, 256, 0, st>>>(ids, nrows, table, tmask, has_empty ? 1 : 0, flags4, tile_cnt);
+    PCV_LAUNCHED();
+    view_scan_kernel<<<1, 256, 0, st>>>(tile_cnt, nt, total);
+    PCV_LAUNCHED();
+}
+
+void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel) {
+    const uint32_t nt = view_tiles(nrows);
+    if (nt == 0) return;
+    view_compact_kernel<<<nt, 256, 0, st>>>(flags4, tile_off, sel);
+    PCV_LAUNCHED();
+}
+
+void launch_view_gather(hipStream_t st, const float4* src_blk, const float* src_scale, const int64_t* src_ids, int64_t src_id0,
+                        int64_t src_pos0, const uint32_t* sel, uint32_t n_sel, int D4, uint32_t dst_row0, uint32_t dst_end,
+                        float4* dst_blk, float* dst_scale, int64_t* dst_ids, int64_t* dst_ppos) {
+    if (dst_end <= dst_row0) return;
+    const uint64_t first_blk = dst_row0 >> 5, last_blk = ((uint64_t)dst_end - 1) >> 5;
+    const int64_t threads = (int64_t)(last_blk - first_blk + 1) * D4 * 32;
+    const unsigned grid = (unsigned)std::min<int64_t>((threads + 255) / 256, (int64_t)current_device_cus() * 64);
+    view_gather_kernel<<<grid, 256, 0, st>>>(src_blk, src_scale, src_ids, src_id0, src_pos0, sel, n_sel, D4, dst_row0, dst_end, dst_blk,
+                                             dst_scale, dst_ids, dst_ppos, threads);
+    PCV_LAUNCHED();
+}
+
+void launch_view_remap(hipStream_t st, pcv_hit_dev* hits, int64_t n, const int64_t* ppos, int64_t nrows) {
+    if (n <= 0) return;
+    view_remap_kernel<<<cdiv64(n, 256), 256, 0, st>>>(hits, n, ppos, nrows);
     PCV_LAUNCHED();
 }
 

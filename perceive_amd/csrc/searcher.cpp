@@ -248,6 +248,18 @@ struct pcv_searcher {
         bool learned = false;   // the speculative threshold had a learned part
         bool guessing = false;  // the pass ran with a speculative threshold (and sent the seed statistics home)
     } pending;
+    // views (pcv_searcher_create_view; DESIGN.md §3 "Views").  As a parent: `gen` counts the calls that may have changed a search
+    // result, `live_views` the views that read its rows.  As a view: the parent, the allow list (ascending, distinct), the
+    // parent's `gen` the rows were copied at, and each row's parent position (d_ppos[view position]).
+    uint64_t gen = 0;
+    std::atomic<int> live_views{0};
+    pcv_searcher* view_parent = nullptr;
+    std::vector<int64_t> view_ids;
+    uint64_t view_gen = 0;
+    int32_t view_refreshes = 0;
+    float view_build_ms = 0.0f;
+    int64_t view_rows = 0;
+    DevBuf<int64_t> d_ppos;
 
     Source* find_source(int64_t id) {
         for (auto& s : sources)
@@ -998,6 +1010,7 @@ void do_finalize(pcv_searcher* s) {
     std::memcpy(&s->max_norm, &bits, 4);
     s->d_stage.release();
     s->dirty = false;
+    s->gen += 1;  // (views copy the rows again at their next call)
 }
 
 struct SelSeg {
@@ -1543,11 +1556,14 @@ void hits_to_outputs(int metric, int D, const pcv_hit_dev* hits, int n_queries, 
     }
 }
 
+void sync_view(pcv_searcher* v);
+
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.
 void device_begin(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, int k,
                   pcv_hit_dev* out, bool queries_on_device = false) {
     check_search_args(s, queries, n_queries, k, "search_device_begin");
     PCV_REQUIRE(!s->pending.active, "search_device_begin: the previous pass was not collected (search_device_end)");
+    sync_view(s);
     PCV_HIP(hipSetDevice(s->ctx->device));
     std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
     const int kernel = pick_kernel(s, n_queries);
@@ -1573,6 +1589,190 @@ void device_begin(pcv_searcher* s, const float* queries, int n_queries, const in
     }
     maybe_build_mid_copies(s);  // (each rank by its own statistics: the copy changes no result and no protocol)
     enqueue_pass(s, queries, n_queries, segs.data(), (int)segs.size(), k, kernel, out, false, out + n, nullptr, queries_on_device);
+    if (s->view_parent) launch_view_remap(s->ctx->stream, out, (int64_t)n, s->d_ppos.p, s->view_rows);  // (before any exchange)
+}
+
+// ---- views (pcv_searcher_create_view; DESIGN.md §3 "Views") ----
+// A view is read-only: every call that would change its rows or copies is refused.
+inline void refuse_view(const pcv_searcher* s, const char* who) {
+    PCV_REQUIRE(s->view_parent == nullptr, "%s: the searcher is a view (read-only): change its parent instead", who);
+}
+
+// the screening copy a view keeps: the kind its parent holds for all of its rows, none if the parent holds none
+int view_screen_mode(const pcv_searcher* p) {
+    return p->copies_kind == 2 ? PCV_SCREEN_COPY_INT8 : (p->copies_kind == 1 ? PCV_SCREEN_COPY_BF16 : PCV_SCREEN_COPY_OFF);
+}
+
+void drop_view_rows(pcv_searcher* v) {
+    for (auto& src : v->sources)
+        for (auto& g : src.segs) free_segment(g);
+    v->sources.clear();
+    v->d_ppos.release();
+    v->view_rows = 0;
+    v->copies_kind = 0;
+    v->mids_present = false;
+}
+
+// A view segment of exactly `rows` rows (rounded up to whole blocks); every byte of it is written by view_gather_kernel.
+Segment alloc_view_segment(pcv_searcher* v, int64_t rows) {
+    PCV_REQUIRE(rows > 0 && rows <= kMaxSegRows, "view: a source of %lld rows is out of range", (long long)rows);
+    Segment g;
+    const uint32_t nblk = (uint32_t)((rows + kBlockRows - 1) / kBlockRows);
+    g.cap_rows = nblk * kBlockRows;
+    try {
+        PCV_HIP(hipMalloc((void**)&g.blk, (size_t)nblk * v->D4 * 32 * sizeof(float4)));
+        PCV_HIP(hipMalloc((void**)&g.scale, (size_t)g.cap_rows * sizeof(float)));
+        PCV_HIP(hipMalloc((void**)&g.ids, (size_t)g.cap_rows * sizeof(int64_t)));
+    } catch (...) {
+        free_segment(g);
+        throw;
+    }
+    g.nrows = g.scaled_rows = (uint32_t)rows;
+    return g;
+}
+
+// (Re)build view v from its parent p (p->mu held): per parent source, the rows whose id is in the allow list become ONE view
+// segment, in parent source order and row order — so a view position grows with the parent position it stands for —, copied
+// with their scales (a hidden or unsearchable row keeps scale 0).  Then the screening copies the parent holds, and a mid copy if
+// the parent's mode is ON, are made from the view's own blocks: an int8 block scale depends on which rows share the block.  All
+// or nothing: if anything fails the view holds no rows (and stays stale, so its next call tries again).
+void build_view(pcv_searcher* v, pcv_searcher* p) {
+    PCV_REQUIRE(!p->dirty, "view: its parent has rows added or cleared without pcv_searcher_finalize");
+    hipStream_t st = v->ctx->stream;
+    PCV_HIP(hipSetDevice(v->ctx->device));
+    PCV_HIP(hipStreamSynchronize(st));  // (a pass of the view may still read the old rows)
+    drop_view_rows(v);
+    // a graph captured over the old rows must not replay over freed buffers: the next passes capture afresh
+    if (v->graph_exec) (void)hipGraphExecDestroy(v->graph_exec);
+    v->graph_exec = nullptr;
+    v->graph_shape = v->last_shape = pcv_searcher::PassShape{};
+    v->shape_seen = 0;
+    v->screen_copy = view_screen_mode(p);
+    v->screen_copy_gave_way = false;
+    v->mid_copy = p->mid_copy == PCV_MID_COPY_ON ? PCV_MID_COPY_ON : PCV_MID_COPY_OFF;
+    v->max_norm = p->max_norm;  // bounds every row of the parent, so every row of the view
+    for (auto& e : v->ev)
+        if (!e) PCV_HIP(hipEventCreate(&e));
+    PCV_HIP(hipEventRecord(v->ev[0], st));
+    struct Part {
+        const Segment* g;
+        DevBuf<uint32_t> sel;  // the rows of g, ascending
+        uint32_t n;
+    };
+    struct SrcPlan {
+        int64_t id;
+        std::vector<Part> parts;
+        int64_t rows;
+    };
+    std::vector<SrcPlan> plan;
+    DevBuf<uint32_t> flags4, tiles, total;
+    IdBatch b;
+    b.ids = &v->view_ids;
+    auto release_scratch = [&] {
+        for (auto& sp : plan)
+            for (auto& pt : sp.parts) pt.sel.release();
+        flags4.release();
+        tiles.release();
+        total.release();
+        v->d_idtab.release();
+    };
+    int64_t rows = 0;
+    try {
+        // 1. which rows: an id column is matched on the device (order-keeping selection), implicit ids (id0 + row) on the host
+        for (const auto& src : p->sources) {
+            SrcPlan sp{src.id, {}, 0};
+            for (const auto& g : src.segs) {
+                if (g.nrows == 0 || v->view_ids.empty()) continue;
+                Part pt{&g, {}, 0};
+                if (!g.ids) {
+                    const std::vector<int64_t>& ids = v->view_ids;
+                    std::vector<uint32_t> sel;
+                    for (auto it = std::lower_bound(ids.begin(), ids.end(), g.id0); it != ids.end() && *it < g.id0 + (int64_t)g.nrows; ++it)
+                        sel.push_back((uint32_t)(*it - g.id0));
+                    pt.n = (uint32_t)sel.size();
+                    if (pt.n) {
+                        pt.sel.ensure(pt.n);
+                        PCV_HIP(hipMemcpyAsync(pt.sel.p, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+                        PCV_HIP(hipStreamSynchronize(st));  // (sel goes out of scope)
+                    }
+                } else {
+                    upload_id_batch(v, b);
+                    const uint32_t nt = view_tiles(g.nrows);
+                    flags4.ensure((size_t)nt * 256);
+                    tiles.ensure(nt);
+                    total.ensure(1);
+                    launch_view_select(st, g.ids, g.nrows, v->d_idtab.p, b.tmask, b.has_empty, flags4.p, tiles.p, total.p);
+                    PCV_HIP(hipMemcpyAsync(&pt.n, total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                    PCV_HIP(hipStreamSynchronize(st));
+                    if (pt.n) {
+                        pt.sel.ensure(pt.n);
+                        launch_view_compact(st, flags4.p, tiles.p, g.nrows, pt.sel.p);
+                        PCV_HIP(hipStreamSynchronize(st));  // (flags4 / tiles are the next segment's)
+                    }
+                }
+                if (pt.n) {
+                    sp.rows += pt.n;
+                    sp.parts.push_back(pt);
+                }
+            }
+            if (sp.rows) plan.push_back(std::move(sp));
+        }
+        // 2. every buffer: the view's segments and the parent positions of their rows
+        for (const auto& sp : plan) {
+            Segment g = alloc_view_segment(v, sp.rows);
+            v->sources.emplace_back();
+            v->sources.back().id = sp.id;
+            v->sources.back().segs.push_back(g);
+            rows += sp.rows;
+        }
+        if (rows) v->d_ppos.ensure((size_t)rows);
+        assign_positions(v);  // (shard offset 0: a view numbers its rows from 0)
+        // 3. the rows, then the padding of each segment's last block
+        for (size_t i = 0; i < plan.size(); ++i) {
+            Segment& dst = v->sources[i].segs[0];
+            int64_t* ppos = v->d_ppos.p + dst.pos0;
+            uint32_t at = 0;
+            for (const Part& pt : plan[i].parts) {
+                launch_view_gather(st, pt.g->blk, pt.g->scale, pt.g->ids, pt.g->id0, pt.g->pos0, pt.sel.p, pt.n, v->D4, at, at + pt.n, dst.blk,
+                                   dst.scale, dst.ids, ppos);
+                at += pt.n;
+            }
+            launch_view_gather(st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, v->D4, at, dst.cap_rows, dst.blk, dst.scale, dst.ids, ppos);
+        }
+        // 4. the copies, from the view's own blocks, as a finalize of these rows makes them
+        for (auto& src : v->sources) build_screening_copies(v, src);
+        if (v->mid_copy == PCV_MID_COPY_ON && rows) build_mid_copies(v, true);
+        v->copies_kind = v->sources.empty() ? 0 : copy_kind_wanted(v);
+        for (const auto& src : v->sources)
+            for (const auto& g : src.segs)
+                if ((v->copies_kind == 1 ? g.blk16 == nullptr : g.blk8 == nullptr) || g.copied_rows < g.nrows) v->copies_kind = 0;
+        PCV_HIP(hipEventRecord(v->ev[3], st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+    } catch (...) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(st);
+        release_scratch();
+        drop_view_rows(v);
+        throw;
+    }
+    release_scratch();
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, v->ev[0], v->ev[3]);
+    v->view_build_ms = ms;
+    v->view_rows = rows;
+    v->view_gen = p->gen;
+}
+
+// Every call on a view starts here (v->mu held): if its parent changed since the rows were copied, they are copied again, under
+// the parent's lock.
+void sync_view(pcv_searcher* v) {
+    if (!v->view_parent) return;
+    pcv_searcher* p = v->view_parent;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (v->view_gen == p->gen) return;
+    build_view(v, p);
+    v->view_refreshes += 1;
 }
 
 }  // namespace
@@ -1611,60 +1811,122 @@ pcv_status pcv_searcher_create(pcv_ctx* ctx, int dim, int metric, pcv_searcher**
     });
 }
 
+namespace {
+// everything a searcher (or a view) holds; a view lets go of its parent
+void destroy_searcher(pcv_searcher* s) {
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    try {
+        settle_mid_build(s, true);
+    } catch (...) {
+    }
+    if (s->side) {
+        (void)hipStreamSynchronize(s->side);
+        (void)hipStreamDestroy(s->side);
+        (void)hipEventDestroy(s->side_go);
+        (void)hipEventDestroy(s->mid_done);
+    }
+    for (auto& src : s->sources)
+        for (auto& g : src.segs) free_segment(g);
+    s->d_stage.release();
+    s->d_qf32.release();
+    s->d_qraw.release();
+    s->d_margin.release();
+    s->d_margin32.release();
+    s->d_qbf16.release();
+    s->d_q8.release();
+    s->d_q8c.release();
+    s->d_spec.release();
+    s->d_cand_s.release();
+    s->d_tau.release();
+    s->d_slots.release();
+    s->d_cnt.release();
+    s->d_cand.release();
+    s->d_hits.release();
+    s->d_idtab.release();
+    s->d_hrows.release();
+    s->d_hblocks.release();
+    s->d_hcnt.release();
+    s->d_idslot.release();
+    s->d_hslots.release();
+    s->d_urows.release();
+    s->d_uslots.release();
+    if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
+    if (s->pin) (void)hipHostFree(s->pin);
+    if (s->pin_pass) (void)hipHostFree(s->pin_pass);
+    if (s->d_pass) (void)hipFree(s->d_pass);
+    if (s->d_max_norm_bits) (void)hipFree(s->d_max_norm_bits);
+    for (auto& e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    s->d_ppos.release();
+    if (s->view_parent) s->view_parent->live_views.fetch_sub(1);
+    delete s;
+}
+}  // namespace
+
 pcv_status pcv_searcher_destroy(pcv_searcher* s) {
     return guarded([&] {
         if (!s) return;
-        (void)hipSetDevice(s->ctx->device);
-        (void)hipStreamSynchronize(s->ctx->stream);
+        PCV_REQUIRE(s->live_views.load() == 0, "searcher_destroy: %d view(s) of this searcher are alive; destroy them first",
+                    s->live_views.load());
+        destroy_searcher(s);
+    });
+}
+
+pcv_status pcv_searcher_create_view(pcv_searcher* parent, const int64_t* ids, int64_t n, pcv_searcher** out_view) {
+    return guarded([&] {
+        PCV_REQUIRE(parent != nullptr && out_view != nullptr, "create_view: NULL argument");
+        *out_view = nullptr;
+        PCV_REQUIRE(n >= 0 && (ids != nullptr || n == 0), "create_view: bad id list (NULL with n > 0, or n < 0)");
+        PCV_REQUIRE(parent->view_parent == nullptr, "create_view: the parent is itself a view");
+        std::vector<int64_t> allow(ids, ids + n);
+        std::sort(allow.begin(), allow.end());
+        allow.erase(std::unique(allow.begin(), allow.end()), allow.end());
+        std::lock_guard<std::mutex> lk(parent->mu);
+        PCV_REQUIRE(!parent->dirty, "create_view: pending rows; call pcv_searcher_finalize first");
+        PCV_REQUIRE(!parent->pending.active, "create_view: a queued pass has not been collected");
+        PCV_HIP(hipSetDevice(parent->ctx->device));
+        pcv_searcher* v = new pcv_searcher();
+        v->ctx = parent->ctx;
+        v->D = parent->D;
+        v->Dp = parent->Dp;
+        v->D4 = parent->D4;
+        v->metric = parent->metric;
+        v->kernel = parent->kernel;
+        v->scan_flags = parent->scan_flags;
+        v->cand_cap = parent->cand_cap;
+        v->use_graph = parent->use_graph;
+        v->view_ids.swap(allow);
+        v->view_parent = parent;
+        parent->live_views.fetch_add(1);  // (given back by destroy_searcher, also if the build fails)
         try {
-            settle_mid_build(s, true);
+            build_view(v, parent);
         } catch (...) {
+            destroy_searcher(v);
+            throw;
         }
-        if (s->side) {
-            (void)hipStreamSynchronize(s->side);
-            (void)hipStreamDestroy(s->side);
-            (void)hipEventDestroy(s->side_go);
-            (void)hipEventDestroy(s->mid_done);
-        }
-        for (auto& src : s->sources)
-            for (auto& g : src.segs) free_segment(g);
-        s->d_stage.release();
-        s->d_qf32.release();
-        s->d_qraw.release();
-        s->d_margin.release();
-        s->d_margin32.release();
-        s->d_qbf16.release();
-        s->d_q8.release();
-        s->d_q8c.release();
-        s->d_spec.release();
-        s->d_cand_s.release();
-        s->d_tau.release();
-        s->d_slots.release();
-        s->d_cnt.release();
-        s->d_cand.release();
-        s->d_hits.release();
-        s->d_idtab.release();
-        s->d_hrows.release();
-        s->d_hblocks.release();
-        s->d_hcnt.release();
-        s->d_idslot.release();
-        s->d_hslots.release();
-        s->d_urows.release();
-        s->d_uslots.release();
-        if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
-        if (s->pin) (void)hipHostFree(s->pin);
-        if (s->pin_pass) (void)hipHostFree(s->pin_pass);
-        if (s->d_pass) (void)hipFree(s->d_pass);
-        if (s->d_max_norm_bits) (void)hipFree(s->d_max_norm_bits);
-        for (auto& e : s->ev)
-            if (e) (void)hipEventDestroy(e);
-        delete s;
+        *out_view = v;
+    });
+}
+
+pcv_status pcv_searcher_view_stats(pcv_searcher* v, int64_t* out_rows, int64_t* out_ids, int32_t* out_refreshes, float* out_build_ms) {
+    return guarded([&] {
+        PCV_REQUIRE(v != nullptr, "view_stats: searcher is NULL");
+        PCV_REQUIRE(v->view_parent != nullptr, "view_stats: the searcher is not a view");
+        std::lock_guard<std::mutex> lk(v->mu);
+        PCV_REQUIRE(!v->pending.active, "view_stats: a queued pass has not been collected");
+        sync_view(v);
+        if (out_rows) *out_rows = v->view_rows;
+        if (out_ids) *out_ids = (int64_t)v->view_ids.size();
+        if (out_refreshes) *out_refreshes = v->view_refreshes;
+        if (out_build_ms) *out_build_ms = v->view_build_ms;
     });
 }
 
 pcv_status pcv_searcher_reserve(pcv_searcher* s, int64_t source_id, int64_t n_rows) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "reserve: searcher is NULL");
+        refuse_view(s, "reserve");
         PCV_REQUIRE(n_rows >= 0, "reserve: negative row count");
         std::lock_guard<std::mutex> lk(s->mu);
         Source& src = s->get_or_add_source(source_id);
@@ -1676,6 +1938,7 @@ pcv_status pcv_searcher_add_rows(pcv_searcher* s, int64_t source_id, const int64
                                  int64_t n) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "add_rows: searcher is NULL");
+        refuse_view(s, "add_rows");
         PCV_REQUIRE(n >= 0 && (rows != nullptr || n == 0), "add_rows: bad rows/n");
         std::lock_guard<std::mutex> lk(s->mu);
         Source& src = s->get_or_add_source(source_id);
@@ -1689,6 +1952,7 @@ pcv_status pcv_searcher_add_blobs(pcv_searcher* s, int64_t source_id, const int6
                                   int64_t n) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "add_blobs: searcher is NULL");
+        refuse_view(s, "add_blobs");
         PCV_REQUIRE(n >= 0 && (blobs != nullptr || n == 0), "add_blobs: bad blobs/n");
         // deserialize_embedding (search.rs:281-286) reads little-endian f32; this library only runs on
         // little-endian hosts (x86-64 + gfx950), where that is the identity on the bytes
@@ -1706,6 +1970,7 @@ static pcv_status add_synthetic(pcv_searcher* s, int64_t source_id, int64_t n, u
                                 int normalize, int n_clusters, float noise, float amp_lo = 0.0f, float amp_hi = 0.0f) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "add_synthetic: searcher is NULL");
+        refuse_view(s, "add_synthetic");
         PCV_REQUIRE(n >= 0, "add_synthetic: negative row count");
         PCV_REQUIRE(n_clusters >= 0 && noise >= 0.0f && std::isfinite(noise), "add_synthetic: bad cluster shape");
         PCV_REQUIRE(std::isfinite(amp_lo) && std::isfinite(amp_hi) && amp_lo >= 0.0f && amp_hi >= amp_lo, "add_synthetic: bad amplitude range");
@@ -1759,6 +2024,7 @@ pcv_status pcv_searcher_add_synthetic_scaled(pcv_searcher* s, int64_t source_id,
 pcv_status pcv_searcher_clear_source(pcv_searcher* s, int64_t source_id) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "clear_source: searcher is NULL");
+        refuse_view(s, "clear_source");
         std::lock_guard<std::mutex> lk(s->mu);
         Source* src = s->find_source(source_id);
         if (!src) return;
@@ -1771,12 +2037,14 @@ pcv_status pcv_searcher_clear_source(pcv_searcher* s, int64_t source_id) {
         src->next_implicit_id = 0;
         src->reserve = 0;
         s->dirty = true;
+        s->gen += 1;
     });
 }
 
 pcv_status pcv_searcher_replace_source(pcv_searcher* s, int64_t from_source_id, int64_t to_source_id) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "replace_source: searcher is NULL");
+        refuse_view(s, "replace_source");
         PCV_REQUIRE(from_source_id != to_source_id, "replace_source: a source cannot replace itself");
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->pending.active, "replace_source: a queued pass has not been collected");
@@ -1806,12 +2074,14 @@ pcv_status pcv_searcher_replace_source(pcv_searcher* s, int64_t from_source_id, 
             to->reserve = 0;
         }
         s->dirty = true;  // positions are handed out again by finalize (an emptied source disappears there)
+        s->gen += 1;
     });
 }
 
 pcv_status pcv_searcher_finalize(pcv_searcher* s) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "finalize: searcher is NULL");
+        refuse_view(s, "finalize");
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_HIP(hipSetDevice(s->ctx->device));
         do_finalize(s);
@@ -1823,6 +2093,7 @@ static pcv_status hide_or_unhide(pcv_searcher* s, const int64_t* ids, int64_t n,
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
         PCV_REQUIRE(n >= 0 && (ids != nullptr || n == 0), "%s: bad id list", who);
+        refuse_view(s, who);
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
         PCV_REQUIRE(!s->pending.active, "%s: a queued pass has not been collected", who);
@@ -1848,6 +2119,7 @@ static pcv_status hide_or_unhide(pcv_searcher* s, const int64_t* ids, int64_t n,
         settle_mid_build(s, true);  // (the AUTO mid build reads the scales and writes the mid copy)
         const int64_t changed = apply_id_batch(s, batch, hide);
         s->hidden.swap(next);
+        s->gen += 1;
         if (out_rows) *out_rows = changed;
     });
 }
@@ -1882,6 +2154,7 @@ static pcv_status update_call(pcv_searcher* s, const int64_t* ids, const void* r
         PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
         PCV_REQUIRE(n >= 0 && ((ids != nullptr && rows != nullptr) || n == 0), "%s: bad ids/rows/n (NULL with n > 0, or n < 0)", who);
         PCV_REQUIRE(n <= 0x7fffffff, "%s: %lld ids in one call", who, (long long)n);
+        refuse_view(s, who);
         const uint32_t probe = 1;  // (blobs: little-endian f32, as pcv_searcher_add_blobs reads them)
         PCV_REQUIRE(*reinterpret_cast<const uint8_t*>(&probe) == 1, "%s: big-endian host", who);
         std::lock_guard<std::mutex> lk(s->mu);
@@ -1903,6 +2176,7 @@ static pcv_status update_call(pcv_searcher* s, const int64_t* ids, const void* r
             ~StageBack() { s->d_stage.release(); }
         } stage_back{s};
         const int64_t changed = update_by_id(s, ids, rows, n, by_id, found);
+        if (changed) s->gen += 1;
         if (out_found) std::memcpy(out_found, found.data(), (size_t)n);
         if (out_rows) *out_rows = changed;
     });
@@ -1929,6 +2203,7 @@ pcv_status pcv_searcher_num_rows(pcv_searcher* s, int64_t* out_rows) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && out_rows != nullptr, "num_rows: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
         int64_t n = 0;
         for (auto& src : s->sources)
             if (src.id != PCV_STAGING_SOURCE) n += src.rows();  // (staged rows are not the searcher's rows yet)
@@ -1940,6 +2215,7 @@ pcv_status pcv_searcher_num_segments(pcv_searcher* s, int* out_n) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && out_n != nullptr, "num_segments: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
         int n = 0;
         for (auto& src : s->sources) n += (int)src.segs.size();
         *out_n = n;
@@ -1950,6 +2226,7 @@ pcv_status pcv_searcher_num_sources(pcv_searcher* s, int* out_n) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && out_n != nullptr, "num_sources: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
         int n = 0;
         for (const auto& src : s->sources) n += src.id != PCV_STAGING_SOURCE ? 1 : 0;
         *out_n = n;
@@ -1960,6 +2237,7 @@ pcv_status pcv_searcher_source_ids(pcv_searcher* s, int64_t* out_ids, int cap) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && out_ids != nullptr, "source_ids: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
         size_t n = 0;
         for (const auto& src : s->sources) n += src.id != PCV_STAGING_SOURCE ? 1 : 0;
         PCV_REQUIRE(cap >= (int)n, "source_ids: capacity %d < %zu sources", cap, n);
@@ -1973,6 +2251,7 @@ pcv_status pcv_searcher_source_num_rows(pcv_searcher* s, int64_t source_id, int6
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && out_rows != nullptr, "source_num_rows: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
         PCV_REQUIRE(!s->dirty, "source_num_rows: pending rows; call pcv_searcher_finalize first");
         *out_rows = 0;
         if (Source* src = s->find_source(source_id)) *out_rows = src->rows();
@@ -1983,6 +2262,7 @@ pcv_status pcv_searcher_get_rows(pcv_searcher* s, const int64_t* positions, int6
                                  int64_t* out_ids) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && positions != nullptr && out_rows != nullptr && n >= 0, "get_rows: bad argument");
+        refuse_view(s, "get_rows");
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->dirty, "get_rows: pending rows; call pcv_searcher_finalize first");
         if (n == 0) return;
@@ -2033,12 +2313,14 @@ pcv_status pcv_searcher_set_kernel(pcv_searcher* s, int kernel) {
 pcv_status pcv_searcher_set_screening_copy(pcv_searcher* s, int mode) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "searcher_set_screening_copy: searcher is NULL");
+        refuse_view(s, "set_screening_copy");
         PCV_REQUIRE(mode >= PCV_SCREEN_COPY_OFF && mode <= PCV_SCREEN_COPY_INT8, "searcher_set_screening_copy: unknown mode %d", mode);
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_HIP(hipSetDevice(s->ctx->device));
         if (mode == PCV_SCREEN_COPY_OFF) {
             PCV_HIP(hipStreamSynchronize(s->ctx->stream));
             drop_screening_copies(s);
+            s->gen += 1;  // (a view keeps the copies its parent keeps)
         }
         s->screen_copy = mode;
         s->screen_copy_gave_way = false;
@@ -2048,6 +2330,7 @@ pcv_status pcv_searcher_set_screening_copy(pcv_searcher* s, int mode) {
 pcv_status pcv_searcher_set_mid_copy(pcv_searcher* s, int mode) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "searcher_set_mid_copy: searcher is NULL");
+        refuse_view(s, "set_mid_copy");
         PCV_REQUIRE(mode >= PCV_MID_COPY_OFF && mode <= PCV_MID_COPY_ON, "searcher_set_mid_copy: unknown mode %d", mode);
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->pending.active, "searcher_set_mid_copy: a queued pass has not been collected");
@@ -2108,9 +2391,11 @@ pcv_status pcv_searcher_set_tuning(pcv_searcher* s, uint32_t flags) {
 pcv_status pcv_searcher_set_shard_offset(pcv_searcher* s, int64_t first_global_pos) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "set_shard_offset: searcher is NULL");
+        refuse_view(s, "set_shard_offset");
         std::lock_guard<std::mutex> lk(s->mu);
         s->shard_offset = first_global_pos;
         assign_positions(s);
+        s->gen += 1;  // (the parent positions a view's hits carry)
     });
 }
 
@@ -2120,6 +2405,7 @@ pcv_status pcv_searcher_search(pcv_searcher* s, const float* queries, int n_quer
         PCV_REQUIRE(s != nullptr, "search: searcher is NULL");
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->pending.active, "search: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
         std::vector<pcv_hit_dev> hits;
         search_hits(s, queries, n_queries, source_ids, n_sources, k, hits);
         hits_to_outputs(s->metric, s->D, hits.data(), n_queries, k, out_ids, out_scores, out_counts);
@@ -2133,6 +2419,7 @@ pcv_status pcv_searcher_search_device(pcv_searcher* s, const float* queries, int
         std::lock_guard<std::mutex> lk(s->mu);
         check_search_args(s, queries, n_queries, k, "search_device");
         PCV_REQUIRE(!s->pending.active, "search_device: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
         PCV_HIP(hipSetDevice(s->ctx->device));
         std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
         const int kernel = pick_kernel(s, n_queries);
@@ -2152,7 +2439,9 @@ pcv_status pcv_searcher_search_device(pcv_searcher* s, const float* queries, int
         for (int q0 = 0; q0 < n_queries; q0 += qstep) {
             const int B = std::min(qstep, n_queries - q0);
             run_pass(s, queries + (size_t)q0 * s->D, B, segs.data(), (int)segs.size(), k, kernel, out + (size_t)q0 * k, false);
+            if (s->view_parent) launch_view_remap(s->ctx->stream, out + (size_t)q0 * k, (int64_t)B * k, s->d_ppos.p, s->view_rows);
         }
+        if (s->view_parent) PCV_HIP(hipStreamSynchronize(s->ctx->stream));
         (void)async;  // every pass has been collected: nothing is left in flight
     });
 }
@@ -2391,6 +2680,7 @@ static pcv_status search_sharded_impl(pcv_searcher* s, pcv_comm* c, const float*
         std::lock_guard<std::mutex> lk(s->mu);
         check_search_args(s, queries, n_queries, k, "search_sharded");
         PCV_REQUIRE(!s->pending.active, "search_sharded: a pass queued by search_device_begin has not been collected");
+        sync_view(s);  // (before the split into passes is chosen)
         const size_t n = (size_t)n_queries * k;
         hipStream_t st = s->ctx->stream;
         PCV_HIP(hipSetDevice(s->ctx->device));

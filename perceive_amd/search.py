@@ -4,6 +4,7 @@ C ABI.  Same names and argument meaning as the reference; the SQLite `Database` 
 (search.rs:87-113: `(items.id, source_id, embedding blob)`), because storage is out of scope.
 """
 import ctypes as C
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -414,6 +415,16 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_last_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.ScanStats._fields_}
 
+    # ---- views (pcv_searcher_create_view) -----------------------------------------------------------
+    def view(self, item_ids):
+        """A read-only searcher over the rows carrying one of `item_ids` (int64 1-D array or iterable; duplicates and unknown ids
+        allowed): it searches like a searcher built fresh from only those rows, in this searcher's source and row order, with its
+        hidden set applied, and follows every later change of this searcher.  Device hit lists carry this searcher's positions."""
+        a = self._update_ids(item_ids)
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().pcv_searcher_create_view(self._handle, _ffi.i64p(a) if a.size else None, a.size, C.byref(h)))
+        return SearcherView(self, h)
+
     @property
     def _handle(self):
         if not self._h:
@@ -422,6 +433,8 @@ class Searcher:
 
     def close(self):
         if self._h:
+            for v in list(getattr(self, "_views", ())):  # (the library refuses to destroy a searcher whose views are alive)
+                v.close()
             if self.ctx._h:  # a context that is gone took its handles with it
                 _ffi.lib().pcv_searcher_destroy(self._h)
             self._h = C.c_void_p()
@@ -431,6 +444,38 @@ class Searcher:
             self.close()
         except Exception:
             pass
+
+
+class SearcherView(Searcher):
+    """Searcher.view(item_ids): every search of Searcher (search_vector(s), search_device, the begin / end and sharded searches),
+    last_stats, num_rows, source_ids, source_num_rows and the kernel / tuning settings; what would change rows or copies
+    raises PcvError (status 1), as get_rows does.  Close it before its parent (the parent's close closes it)."""
+
+    def __init__(self, parent, handle):
+        self.ctx, self.dim, self.metric = parent.ctx, parent.dim, parent.metric
+        self.parent = parent
+        self._h = handle
+        self.hidden = set()
+        if not hasattr(parent, "_views"):
+            parent._views = weakref.WeakSet()
+        parent._views.add(self)
+        self.ctx._register(self)
+
+    def view_stats(self):
+        """{"rows": rows held now, "ids": distinct allowed ids, "refreshes": copies made again since the parent changed,
+        "build_ms": device time of the last copy}"""
+        rows, ids, ref, ms = C.c_int64(), C.c_int64(), C.c_int32(), C.c_float()
+        _ffi.check(_ffi.lib().pcv_searcher_view_stats(self._handle, C.byref(rows), C.byref(ids), C.byref(ref), C.byref(ms)))
+        return {"rows": rows.value, "ids": ids.value, "refreshes": ref.value, "build_ms": ms.value}
+
+    def view(self, item_ids):
+        raise _ffi.PcvError(1, "a view cannot be the parent of a view")
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                _ffi.lib().pcv_searcher_destroy(self._h)
+            self._h = C.c_void_p()
 
 
 def encode_query(model, query):

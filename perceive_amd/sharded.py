@@ -138,6 +138,13 @@ class ShardedSearcher:
     def hidden_items(self):
         return self.searcher.hidden_items()
 
+    # views: every rank makes a view of its local searcher from the same ids; the result searches like this sharded searcher
+    # restricted to those items (hit positions stay the parent's, so the ranks' lists merge as before)
+    def view(self, ids):
+        v = ShardedSearcher(self.dist, self.metric, self.dim, searcher=self.searcher.view(ids), ctx=self.ctx, device=self.device,
+                            local_search=None, comm=self.comm, all_gather=self._all_gather)
+        return v
+
     def _buffers(self, B, k):
         import torch
 

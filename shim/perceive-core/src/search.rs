@@ -5,6 +5,7 @@
 //!   `deserialize_embedding`, `serialize_embedding`                               (search.rs:18-294)
 //! Scores keep the reference's convention: `max(0, 1 - dot/len)`, ascending (PCV_METRIC_DOT).
 //! NOT COMPILED in this repository's build image (no Rust toolchain): see ../README.md.
+use std::marker::PhantomData;
 use std::ptr;
 use std::rc::Rc;
 
@@ -247,6 +248,18 @@ impl Searcher {
         hip::check(unsafe { ffi::pcv_searcher_finalize(self.handle) })
     }
 
+    /// A search restricted to `items` (the items of a tag, of an author, the results of an earlier search): a read-only view
+    /// that searches like an index built from only the rows carrying those ids, with the hidden items left out, and follows
+    /// every later change of this searcher (no rebuild).  The app turns its filter into ids with SQL first, e.g.
+    ///     `SELECT item_id FROM item_tags WHERE tag_id = ?`
+    pub fn view(&self, items: &[i64]) -> Result<SearcherView<'_>, HipError> {
+        let mut handle: *mut ffi::pcv_searcher = ptr::null_mut();
+        if !self.handle.is_null() {
+            hip::check(unsafe { ffi::pcv_searcher_create_view(self.handle, items.as_ptr(), items.len() as i64, &mut handle) })?;
+        }
+        Ok(SearcherView { handle, _parent: PhantomData })
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
@@ -318,6 +331,54 @@ fn item_from_row(row: &rusqlite::Row<'_>) -> rusqlite::Result<Item> {
 }
 
 impl Drop for Searcher {
+    fn drop(&mut self) {
+        if !self.handle.is_null() {
+            unsafe { ffi::pcv_searcher_destroy(self.handle) };
+        }
+    }
+}
+
+/// `Searcher::view`: borrows its searcher, so it is dropped (destroyed) before the searcher is.
+pub struct SearcherView<'a> {
+    handle: *mut ffi::pcv_searcher,
+    _parent: PhantomData<&'a Searcher>,
+}
+
+unsafe impl Send for SearcherView<'_> {}
+unsafe impl Sync for SearcherView<'_> {}
+
+impl SearcherView<'_> {
+    /// `Searcher::search_vector` among the view's items.
+    pub fn search_vector(&self, sources: &[i64], num_results: usize, vector: Vec<f32>) -> Vec<SearchItem> {
+        if self.handle.is_null() || num_results == 0 {
+            return Vec::new();
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        assert_eq!(vector.len(), dim as usize, "search_vector: the query has {} values, the index is {}-d", vector.len(), dim);
+        let k = num_results;
+        let mut ids = vec![-1i64; k];
+        let mut scores = vec![f32::NAN; k];
+        let mut count: i32 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search(
+                self.handle,
+                vector.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                k as i32,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut count,
+            )
+        })
+        .expect("search failed");
+        (0..count as usize).map(|i| SearchItem { id: ids[i], score: scores[i] }).collect()
+    }
+}
+
+impl Drop for SearcherView<'_> {
     fn drop(&mut self) {
         if !self.handle.is_null() {
             unsafe { ffi::pcv_searcher_destroy(self.handle) };
