@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the scan benchmark BASELINE.json names.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch B] [--dump-outputs DIR] [--full]
 
 A step = one exact top-10 search of a batch of queries over the whole synthetic corpus (the hot
 path of perceive-core: lib.rs:63-77 similarity + search.rs:157-182 selection), corpus resident in
@@ -9,6 +9,11 @@ HBM.  N=1 default workload: BASELINE configs[2] "100M x 384-d, batch=64 queries,
 (the configuration the >=70 %-of-HBM-roofline target is quoted on; it fits one 288 GB GPU).
 N>1 (launched by torch.distributed.run, one rank per GPU): the same 100M rows row-sharded over the
 ranks, per-shard exact top-k, RCCL all-gather of the [B][k] hit lists, merge — strong scaling.
+
+A plain run builds the corpus, warms up, times the K steps, writes --dump-outputs and prints the
+line.  --full adds what takes runs of its own: at N=1 the extra legs (other batch sizes, the f32
+rows and bf16 copy, clustered rows, 768-d dot, smaller corpora, the encoder, end to end) under
+`extra` and the CPU baseline; at N>1 the configs[4] end-to-end leg and the native-communicator check.
 
 Prints ONE JSON line on rank 0.
 """
@@ -39,19 +44,22 @@ def parse():
     ap.add_argument("--screen", default="auto", choices=["auto", "int8", "bf16", "off"],
                     help="resident screening copy of the rows (results do not depend on it): auto = int8; "
                          "off = the scan streams the f32 rows themselves (1536 B/vector)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the extra legs and the CPU baseline (N=1), the end-to-end leg "
+                         "and the native-communicator check (N>1)")
     ap.add_argument("--cpu-rows", type=int, default=int(os.environ.get("PCV_BENCH_CPU_ROWS", 1_000_000)))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--collective", default=os.environ.get("PCV_BENCH_COLLECTIVE", "torch"), choices=["torch", "native", "both"],
                     help="N>1 hit-list exchange of the TIMED steps: torch.distributed's RCCL group (default), or the library's own RCCL "
-                         "communicator (native).  With torch the same steps are run once more through the native communicator AFTER the "
-                         "JSON line is out (figures on stderr as a `native_check` line and in gpurun_out/native_check.json): a failure "
+                         "communicator (native).  With torch and --full the same steps are run once more through the native communicator "
+                         "AFTER the JSON line is out (figures on stderr as a `native_check` line, and in native_check.json): a failure "
                          "there leaves the line as printed; `both` makes such a failure the exit status")
-    ap.add_argument("--no-e2e", action="store_true", help="N>1: skip the configs[4] end-to-end leg (encode -> gather -> sharded search)")
+    ap.add_argument("--no-e2e", action="store_true", help="N>1 with --full: skip the configs[4] end-to-end leg (encode -> gather -> sharded search)")
     ap.add_argument("--normalized", action="store_true", help="store unit-norm rows (MiniLM-like)")
     ap.add_argument("--clustered", action="store_true",
                     help="main leg on clustered rows (centroid + noise: ~2e4 rows within 0.01 cosine of every query's top-k)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (config 2, shard, encoder, end to end, clustered)")
-    ap.add_argument("--only", default="", help="comma-separated names of the extra legs to run (default: all of them); what "
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra legs (config 2, shard, encoder, end to end, clustered)")
+    ap.add_argument("--only", default="", help="with --full: comma-separated names of the extra legs to run (default: all of them); what "
                     "tools/profile_round.sh uses to put one leg of this file under rocprofv3 at a time")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N>1: strong = --rows is the whole corpus, sharded (BASELINE configs[3]); weak = --rows per GPU")
@@ -61,6 +69,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only and not args.full:
+        ap.error("--only names legs that --full runs: add --full")
     return args
 
 
@@ -539,7 +549,7 @@ def main():
         # exchange of the [B][k] hit lists: torch.distributed's RCCL group (default), or the library's own
         # persistent RCCL communicator (pcv_comm_*; torch then only bootstraps the id and times the job)
         comm = pa.NativeComm.from_dist(ctx, dist) if args.collective == "native" else None
-        want_native_check = args.collective in ("torch", "both") and not rehearse  # (world 1: only under PCV_BENCH_FORCE_DIST, a rehearsal of this code)
+        want_native_check = args.full and args.collective in ("torch", "both") and not rehearse  # (world 1: only under PCV_BENCH_FORCE_DIST, a rehearsal of this code)
         gather = None
         if rehearse:  # gloo has no device all-gather: stage through the host (torch copies on the current stream)
             def gather(gathered, local):
@@ -641,6 +651,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "settle_passes": settle_passes,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
@@ -673,7 +684,7 @@ def main():
             "build_s": t_build,
             "sample_result": {"ids": [int(x) for x in ids[0][:3]], "scores": [float(x) for x in scores[0][:3]]},
         }
-        if world == 1 and not args.no_extra and not use_dist:  # (not in the one-rank rehearsal of the N > 1 path either)
+        if args.full and world == 1 and not args.no_extra and not use_dist:  # (not in the one-rank rehearsal of the N > 1 path either)
             # the other legs BASELINE.json names, measured in the same run (single GPU only)
             extra = {}
             only = only_legs
@@ -755,11 +766,11 @@ def main():
             if want("encoder_bertbase_64x256"):
                 extra["encoder_bertbase_64x256"] = encoder_leg(pa, ctx, "f32", batch=64, seq=256, shape="bert_base")
             out["extra"] = extra
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
         final_out = out
 
-    if use_dist and world > 1 and not args.no_e2e and args.dim == 384 and not args.clustered:
+    if args.full and use_dist and world > 1 and not args.no_e2e and args.dim == 384 and not args.clustered:
         # BASELINE configs[4] at this N: every rank encodes its share of 256 documents, the embeddings stay on the devices,
         # one all-gather completes them on every rank, two sharded passes of 128 queries read them from device memory.  After the
         # headline's figures are final and under a guard: this leg has not run on more than one GPU yet (gloo rehearsal only) —
@@ -802,7 +813,12 @@ def main():
     if use_dist and comm is not None:
         comm.close()
     if searcher is not None:
+        # wait out the driver's clear of the corpus before exiting: a bench started right after this one would otherwise build
+        # its corpus and time its steps while the clear runs (its build 6 s instead of 0.2 s, its scan kernel 2.6 % slower)
+        st = searcher.last_stats()
+        held = args.dim * 4 + 8 + {0: 0, 1: 2 * args.dim, 2: args.dim + 1}[st["screening_copy"]] + (2 * args.dim + 4 if st["mid_copy"] else 0)
         searcher.close()
+        settle((hi - lo) * held)
     ctx.close()
     if use_dist:
         dist.destroy_process_group()

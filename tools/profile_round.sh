@@ -1,5 +1,5 @@
 # Round profiles, as committed under profiles/ by tools/summarize_profiles.py <tag>: every leg bench.py reports, run
-# under rocprofv3 through bench.py itself (--no-extra for the headline-shaped legs, --only <leg> for the others), so the
+# under rocprofv3 through bench.py --full itself (--no-extra for the headline-shaped legs, --only <leg> for the others), so the
 # kernel each leg names has a kept kernel-trace summary, and the scan legs a FETCH_SIZE / WRITE_SIZE pass each
 # (counters in their own runs, kernel-trace only besides them).
 # Run on the GPU box, one part per call (a part takes 8-12 minutes):
@@ -31,7 +31,7 @@ PY
   echo "ok $d"
   sleep 7  # the driver clears the ~190 GB the run gave back at ~34 GB/s in the background: 2.6 % of HBM bandwidth meanwhile
 }
-BENCH="python3 $R/bench.py --no-cpu-baseline"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline"
 # leg name -> bench.py arguments (the leg's record is the headline of a --no-extra run, or extra[<leg>] of an --only run)
 legs=(
   "headline|--no-extra --steps 10"

@@ -143,7 +143,7 @@ def main():
         if prof_ms is None:
             prof_ms, n_timed = all_ms, int(row["Calls"])
         entry = {
-            "workload": rec["workload"], "command": "bench.py --no-cpu-baseline " + ("--only " + key if key else "--no-extra") + " (tools/profile_round.sh)",
+            "workload": rec["workload"], "command": "bench.py --full --no-cpu-baseline " + ("--only " + key if key else "--no-extra") + " (tools/profile_round.sh)",
             "kernel": short(row["Name"]), "bytes_per_launch": rec["bytes_per_launch"],
             "rocprof_avg_kernel_ms": prof_ms, "rocprof_timed_launches": n_timed,
             "rocprof_avg_kernel_ms_all_launches": all_ms, "rocprof_calls": int(row["Calls"]),
