@@ -243,7 +243,9 @@ pcv_status pcv_searcher_view_stats(pcv_searcher* view, int64_t* out_rows, int64_
 /* Which scan kernel pcv_searcher_search uses. AUTO: wave-reduction kernel for n_queries <= 4,
  * MFMA tile kernel otherwise (up to 128 queries per corpus pass at dim <= 640; 256 with the int8 screening copy at
  * dim <= 384; among the ranks of a sharded search a pass is 128 queries on every rank, whatever copies each holds).
- * More queries than one pass takes are searched in several passes. */
+ * More queries than one pass takes are searched in several passes.  Under AUTO a pass of 5..64 queries over rows of at most
+ * 384 features streams the 6-bit form of the int8 copy where every selected segment has one (pcv_searcher_set_screening_copy),
+ * re-screening its survivors against their int8 rows; MFMA pins the whole-int8 scan (same results, pcv_scan_stats.screen_bits 8). */
 enum { PCV_KERNEL_AUTO = 0, PCV_KERNEL_WAVE = 1, PCV_KERNEL_MFMA = 2 };
 pcv_status pcv_searcher_set_kernel(pcv_searcher* s, int kernel);
 
@@ -254,7 +256,8 @@ pcv_status pcv_searcher_set_candidate_capacity(pcv_searcher* s, uint32_t n_candi
 /* Diagnostic / comparison switches of one searcher; results never depend on them.  `flags` replaces what the
  * environment variable PCV_SCAN_FLAGS gave the searcher at creation (bit meanings: csrc/scan.h, ScanParams::flags —
  * bit 0 plain instead of non-temporal corpus loads, bit 3 the 128-query tile instead of the block-holding int8 scan,
- * bit 5 no speculative start threshold, bit 7 no learned part of it, bits 8..15 workgroups per CU, ...), plus
+ * bit 5 no speculative start threshold, bit 7 no learned part of it, bits 8..15 workgroups per CU, ..., bit 29 never build or
+ * stream the 6-bit screening copy, bit 31 let AUTO build it at any size instead of from 8M rows on), plus
  *   PCV_TUNE_FAIL_COPY_ALLOC : while set, every allocation of a screening copy is treated as failed (how the tests
  *                              reach the out-of-memory branches of pcv_searcher_finalize). */
 enum { PCV_TUNE_FAIL_COPY_ALLOC = 1073741824 }; /* bit 30 */
@@ -270,10 +273,14 @@ pcv_status pcv_searcher_set_tuning(pcv_searcher* s, uint32_t flags);
  *                          for 384-d unit rows (certified per row and query from the quantisation steps): more rows
  *                          reach the fine screen, a quarter of the bytes are streamed; dimensions up to 1024
  *   PCV_SCREEN_COPY_AUTO (default): INT8 (BF16 for rows wider than 1024 features), built at finalize; given up — for good, on this searcher — when an
- *                          allocation for rows or for a copy fails (the f32 rows are scanned then)
+ *                          allocation for rows or for a copy fails (the f32 rows are scanned then).  From 8M rows on (rows of at most
+ *                          384 features) AUTO also keeps a 6-bit form of the int8 copy, 3/4 of a byte per feature + 16 bytes per
+ *                          32 rows, screened with an L2 bound (pcv_searcher_set_kernel) — if a tenth of the device, at least
+ *                          4 GB, stays free after it.  It is the first copy to give way when an allocation for rows or for a
+ *                          copy fails, it is freed before AUTO builds a mid copy, and when the mode leaves AUTO
  *   PCV_SCREEN_COPY_OFF  : never built; existing copies are freed
  * BF16 / INT8 asked for explicitly: a failed copy allocation is an error at finalize.  Takes effect at the next
- * finalize (OFF: at once).  100M x 384: 153.6 GB of rows + 38.4 GB (INT8) or 76.8 GB (BF16). */
+ * finalize (OFF: at once).  100M x 384: 153.6 GB of rows + 38.4 GB (INT8) or 76.8 GB (BF16); AUTO: + 28.8 GB for the 6-bit form. */
 enum { PCV_SCREEN_COPY_OFF = 0, PCV_SCREEN_COPY_BF16 = 1, PCV_SCREEN_COPY_AUTO = 2, PCV_SCREEN_COPY_INT8 = 3 };
 pcv_status pcv_searcher_set_screening_copy(pcv_searcher* s, int mode);
 
@@ -434,7 +441,7 @@ typedef struct pcv_scan_stats {
     int32_t scan_launches;       /* scan kernel launches (reruns after overflow included)        */
     int32_t overflow_reruns;     /* passes repeated because a candidate list overflowed          */
     int32_t kernel_used;         /* PCV_KERNEL_WAVE or PCV_KERNEL_MFMA                           */
-    int32_t screening_copy;      /* what the scan streamed (last pass): 0 f32 rows, 1 bf16 copy, 2 int8 copy */
+    int32_t screening_copy;      /* what the scan streamed (last pass): 0 f32 rows, 1 bf16 copy, 2 int8 copy or its 6-bit form (screen_bits) */
     float host_enqueue_ms;       /* host time spent queueing the passes (copies + launches)      */
     float host_wait_ms;          /* host time blocked until the stream had drained               */
     int64_t bytes_streamed;      /* bytes the scan kernel(s) had to read from HBM, layout padding included: per 32-row block
@@ -445,6 +452,9 @@ typedef struct pcv_scan_stats {
     int64_t coarse_survivors;    /* MFMA scans: (row, query) pairs that passed the coarse screen and had their f32 row read
                                     by the fine screen, summed over queries and launches */
     int64_t mid_survivors;       /* ... and those of them that also passed the mid screen (= f32 rows read), when a mid copy exists */
+    int64_t narrow_survivors;    /* passes that streamed the 6-bit copy: (row, query) pairs that passed its screen and had their int8
+                                    row read (of them, coarse_survivors passed the int8 screen too), summed over queries and launches */
+    int32_t screen_bits;         /* width of the copy the coarse screen streamed (last pass): 8 int8, 6 its 6-bit form, 0 none */
 } pcv_scan_stats;
 pcv_status pcv_searcher_last_stats(pcv_searcher* s, pcv_scan_stats* out);
 

@@ -45,6 +45,8 @@ class ScanStats(C.Structure):
         ("mid_copy", C.c_int32),
         ("coarse_survivors", C.c_int64),
         ("mid_survivors", C.c_int64),
+        ("narrow_survivors", C.c_int64),
+        ("screen_bits", C.c_int32),
     ]
 
 

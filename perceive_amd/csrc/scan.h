@@ -31,6 +31,19 @@
 // 96 cache lines, 12 KB of traffic for 1536 bytes.  With the mid copy the fine screen first reads the row's 768 contiguous bytes
 // (6 lines) and drops it unless   q'.Y / s2  >=  tau - (|q'|_1 * 0.5002 / s2 + margin32 * 1.5)   — |y_i - Y_i / s2| <= 0.5002 / s2,
 // so the bound is ~1e-4 in cosine, the size of the f32 margin itself: what passes goes on to the f32 row as before.
+//
+// 6-bit screening copy (beside the int8 copy, built by AUTO for large sources): the int8 codes with their two low
+// bits dropped, h = x^ >> 2 in [-32, 31], stored biased as u = h + 32 in [0, 63]; u stands for 4h + 1.5 in int8 units, i.e.
+// x~ = (4h + 1.5) / s_blk in units of y.  Per block, chunk of 128 features and lane of the int8 layout (the 64 int8 values a lane
+// feeds its four MFMAs of the chunk: 16 dwords d = 4 ks + j), three 16-byte pieces — 3 KB per chunk instead of 4:
+//       blk6[((b * NCH + ch) * 3 + piece) * 64 + lane]      pieces 0, 1: low nibbles (dword i: d = 2i in bits 0-3, 2i + 1 in bits
+//                                                          4-7 of each byte);  piece 2: the 2-bit high parts (dword k: d = 4k + m
+//                                                          in bits 2m, 2m + 1 of each byte)
+//       scale6[b] = {s_blk, s_blk * r_blk, s_blk * n_blk, 0}    r_blk = max |y - x~|_2, n_blk = max |x~|_2 over the block's
+//                                                          searchable rows (rounded up)
+// The screen multiplies u with the int8 query (acc = sum u_i q^_i, exact) and keeps a row by the L2 (Cauchy-Schwarz) bound
+//       |c - (4 acc - 126.5 sum q^) / (s_blk s_q)|  <=  |q'|_2 r_blk + |e_q|_2 n_blk     (+ eps32),   e_q = q' - q^ / s_q
+// one number per (block, query) like the int8 test's.  Its survivors are screened again against their int8 row.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,7 +80,12 @@ struct SegDesc {
     const uint4* mid16;  // row-major 16-bit copy (see below), or nullptr
     const float* scale16;
     const float* scale8; // [nblocks] quantisation scale of the int8 copy's blocks (NaN = no searchable row in the block)
+    const uint4* blk6;   // 6-bit screening copy (above), or nullptr
+    const float4* scale6;  // [nblocks] its per-block constants
 };
+constexpr uint32_t kFlagSix = 1u << 31;      // ScanParams::flags: the pass streams the 6-bit copies (set by the searcher)
+constexpr uint32_t kTuneNoSix = 1u << 29;    // PCV_SCAN_FLAGS: never build or stream the 6-bit copy
+constexpr uint32_t kTuneForceSix = 1u << 31; // PCV_SCAN_FLAGS: AUTO builds it at any size
 
 struct pcv_hit_dev {
     double score;
@@ -109,7 +127,8 @@ struct ScanParams {
     float* qf32;             // [B][Dp]   scan-side query (normalised for cosine), zero padded
     uint16_t* qbf16;         // [128][Dp] same, rounded to bf16
     int8_t* q8;              // [128][Dp8] same, quantised per query to int8 (int8 screen; Dp8 = Dp rounded up to 128)
-    float* q8c;              // [256][4]  s_q (quantisation scale, 0 = dead query), V_q of the int8 test (scan_mfma8_kernel), |q'|_1 (mid screen), -
+    float* q8c;              // [256][4]  s_q (quantisation scale, 0 = dead query), V_q of the int8 test (scan_mfma8_kernel), |q'|_1 (mid screen), -;
+                             // then [256][4] of the 6-bit test: s_q |q'|_2, s_q |e_q|_2 (both rounded up), -W_q + slack (scan_mfma8_kernel), -
     float* qraw;             // [B][Dp]   original query values, zero padded (exact rescoring)
     float* margin;           // [B]  coarse screen: rows with s16 < tau - margin are dropped       (eps16 + eps32)
     float* margin32;         // [B]  fine screen:   rows with s32 < tau - margin32 are dropped     (2 * eps32)
@@ -192,6 +211,14 @@ void launch_coarse_pack8(hipStream_t st, const float4* blk, const float* scale, 
                          uint32_t nblocks, int D4);
 void launch_scan_mfma8(hipStream_t st, const ScanParams& p, const ScanParams* dp, int num_cus);  // quantises the queries first
 int mfma8_pass_queries(int Dp);  // queries one int8 MFMA pass can take (LDS-limited)
+// the 6-bit copy (scale6 included) of blocks [first_block, nblocks) / of blocks[0..n), from the int8 copy and the f32 rows
+void launch_pack6(hipStream_t st, const float4* blk, const float* scale, const uint4* blk8, const float* scale8, uint4* blk6, float4* scale6,
+                  uint32_t first_block, uint32_t nblocks, int D4);
+void launch_repack6_blocks(hipStream_t st, const float4* blk, const float* scale, const uint4* blk8, const float* scale8, const uint32_t* blocks,
+                           uint32_t n, uint4* blk6, float4* scale6, int D4);
+size_t six_copy_bytes(uint32_t nblocks, int Dp);  // bytes of blk6 for that many blocks
+// whether a pass of B queries over rows of Dp padded features streams the 6-bit copy when every segment has one (the DRAIN form)
+bool mfma8_six_pass(int B, int Dp, uint32_t flags, int nseg);
 // mid copy + its scales of rows [first_row, nrows) of a segment
 // (scale8: the quantisation scales of the segment's int8 copy if it covers these rows — the copy is then made block by block with
 // the blocks' scales — or nullptr: row by row, each with its own)

@@ -116,6 +116,8 @@ struct SegCursor {
     const float* scale8 = nullptr;
     const uint4* mid16 = nullptr;
     const float* scale16 = nullptr;
+    const uint4* blk6 = nullptr;
+    const float4* scale6 = nullptr;
 };
 __device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 template <class T>
@@ -146,6 +148,8 @@ __device__ __forceinline__ void seek_seg(const ScanParams& p, SegCursor& c, uint
     c.scale8 = uniform_ptr(gld(&p.seg[lo].scale8));
     c.mid16 = uniform_ptr(gld(&p.seg[lo].mid16));
     c.scale16 = uniform_ptr(gld(&p.seg[lo].scale16));
+    c.blk6 = uniform_ptr(gld(&p.seg[lo].blk6));
+    c.scale6 = uniform_ptr(gld(&p.seg[lo].scale6));
 }
 
 // slots[q][0..k) always hold f32 scores of k DISTINCT rows (or -inf), each slot only ever grows, so
@@ -403,6 +407,87 @@ __global__ __launch_bounds__(256) void coarse_pack8_kernel(const float4* __restr
             blk8[((size_t)b * D16 + g) * 32 + r] = make_uint4(w[0], w[1], w[2], w[3]);
         }
         if (lane == 0) scale8[b] = s_blk;
+    }
+}
+
+
+// 6-bit copy (scan.h) of blocks [first_block, nblocks) — or of blocks[0..n) when `blocks` is given — from the int8 copy: one wave per
+// block, lane (r, h) of the int8 layout packs the 64 codes it feeds the MFMAs of each chunk, u = (x^ >> 2) + 32, into its three
+// pieces.  r_blk and n_blk are measured against the f32 rows (f64 sums, maxima over the block's searchable rows, rounded up), so the
+// bound holds whatever the int8 copy's own rounding was.  Rows that are not searchable are left out of both (their int8 codes are
+// zeros; they end at the fine screen: scale 0).
+__global__ __launch_bounds__(256) void pack6_kernel(const float4* __restrict__ blk, const float* __restrict__ scale,
+                                                    const uint4* __restrict__ blk8, const float* __restrict__ scale8,
+                                                    const uint32_t* __restrict__ blocks, uint4* __restrict__ blk6,
+                                                    float4* __restrict__ scale6, uint32_t first_block, uint32_t nblocks, int D4) {
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int D16 = ((D4 * 4 + 127) & ~127) >> 4, NCH = D16 >> 3;
+    for (uint32_t i = (blocks ? 0u : first_block) + blockIdx.x * 4 + (threadIdx.x >> 6); i < nblocks; i += gridDim.x * 4) {
+        const uint32_t b = blocks ? blocks[i] : i;
+        const float sc = scale[(size_t)b * 32 + r];
+        const float s = scale8[b];
+        const bool searchable = sc != 0.0f && s == s;
+        const double inv_s = searchable ? 1.0 / (double)s : 0.0;
+        double e2 = 0.0, n2 = 0.0;
+        for (int ch = 0; ch < NCH; ++ch) {
+            uint32_t w[16];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int f16 = ch * 8 + 2 * ks + h;
+                const uint4 v = blk8[((size_t)b * D16 + f16) * 32 + r];
+                w[4 * ks] = v.x;
+                w[4 * ks + 1] = v.y;
+                w[4 * ks + 2] = v.z;
+                w[4 * ks + 3] = v.w;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {  // the 16 features of the piece against the f32 row
+                    const int f4 = 4 * f16 + e;
+                    if (!searchable || f4 >= D4) continue;
+                    const float4 x = blk[((size_t)b * D4 + f4) * 32 + r];
+                    const float y[4] = {x.x * sc, x.y * sc, x.z * sc, x.w * sc};
+                    const uint32_t word = w[4 * ks + e];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int x8 = (int)(int8_t)(word >> (8 * j));
+                        const double xt = (double)(4 * (x8 >> 2)) * inv_s + 1.5 * inv_s;
+                        const double d = (double)y[j] - xt;
+                        e2 += d * d;
+                        n2 += xt * xt;
+                    }
+                }
+            }
+            uint32_t u[16];
+#pragma unroll
+            for (int d = 0; d < 16; ++d) {  // per byte: (x^ >> 2) + 32, i.e. the top six bits of x^ + 128
+                const uint32_t biased = w[d] ^ 0x80808080u;  // x^ + 128 in each byte (no carries: x^ in [-127, 127])
+                u[d] = (biased >> 2) & 0x3f3f3f3fu;
+            }
+            uint32_t lo[8], hi[4];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) lo[k] = (u[2 * k] & 0x0f0f0f0fu) | ((u[2 * k + 1] & 0x0f0f0f0fu) << 4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                hi[k] = 0;
+#pragma unroll
+                for (int m = 0; m < 4; ++m) hi[k] |= ((u[4 * k + m] >> 4) & 0x03030303u) << (2 * m);
+            }
+            uint4* dst = blk6 + ((size_t)b * NCH + ch) * 3 * 64 + lane;
+            dst[0] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+            dst[64] = make_uint4(lo[4], lo[5], lo[6], lo[7]);
+            dst[128] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+        }
+        e2 += __shfl_xor(e2, 32);
+        n2 += __shfl_xor(n2, 32);
+#pragma unroll
+        for (int off = 16; off > 0; off >>= 1) {
+            e2 = fmax(e2, __shfl_xor(e2, off));
+            n2 = fmax(n2, __shfl_xor(n2, off));
+        }
+        if (lane == 0) {
+            const float up = 1.0f + 0x1p-19f;
+            const bool any = s == s;
+            scale6[b] = make_float4(s, any ? (float)(sqrt(e2) * (double)s) * up : 0.0f, any ? (float)(sqrt(n2) * (double)s) * up : 0.0f, 0.0f);
+        }
     }
 }
 
@@ -1033,6 +1118,7 @@ __global__ __launch_bounds__(256) void reset_scan_state_kernel(uint32_t* __restr
         cand_cnt[t * kHot] = 0;
         cand_cnt[t * kHot + 32] = 0;
         cand_cnt[t * kHot + 33] = 0;
+        cand_cnt[t * kHot + 34] = 0;
     }
 }
 
@@ -1869,15 +1955,41 @@ __global__ __launch_bounds__(256) void quantize_queries_kernel(const ScanParams*
     }
     const float s_q = (mx > 0.0f && mx < __builtin_inff() && l1 < __builtin_inff()) ? 127.0f / mx : 0.0f;
     int8_t* row = p.q8 + (size_t)q * Dp8;
+    // the 6-bit test's constants (scan.h) in f64: |q'|_2, |e_q|_2 = |q' - q^ / s_q|_2, sum q^, sum |q^|
+    double n2 = 0.0, e2 = 0.0;
+    int qs = 0, qa = 0;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int i = lane + 64 * j;
-        if (i < Dp8) row[i] = (int8_t)max(-127, min(127, (int)rintf((s_q != 0.0f ? x[j] : 0.0f) * s_q)));
+        const int qi = max(-127, min(127, (int)rintf((s_q != 0.0f ? x[j] : 0.0f) * s_q)));
+        if (i < Dp8) row[i] = (int8_t)qi;
+        const double e = s_q != 0.0f ? (double)x[j] - (double)qi / (double)s_q : 0.0;
+        n2 += (double)x[j] * (double)x[j];
+        e2 += e * e;
+        qs += qi;
+        qa += abs(qi);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        n2 += __shfl_xor(n2, off);
+        e2 += __shfl_xor(e2, off);
+        qs += __shfl_xor(qs, off);
+        qa += __shfl_xor(qa, off);
     }
     if (lane == 0) {
         p.q8c[4 * q] = s_q;
         p.q8c[4 * q + 1] = 0.5002f * l1 * s_q + 0.2501f * (float)Dp8 + 4.0f;
         p.q8c[4 * q + 2] = l1;
+        // 6-bit test, in units of 4 acc (acc = sum u_i q^_i): keep iff 4 acc + t2 + Wn >= s_blk T'_q, t2 = R_blk A_q + N_blk E_q.
+        // A, E rounded up; Wn = -126.5 sum q^ plus 2^-20 of the largest magnitude on the left (|4 acc| <= 252 sum |q^|), which
+        // covers the f32 roundings of the left-hand side.
+        const bool live = have && s_q != 0.0f;
+        const double W = 126.5 * (double)qs, M = 252.0 * (double)qa + fabs(W);
+        const float up = 1.0f + 0x1p-19f;
+        const float wn = (float)(-W + M * 0x1p-20);
+        p.q8c[4 * kMfmaQueries + 4 * q] = live ? (float)(sqrt(n2) * (double)s_q) * up : 0.0f;
+        p.q8c[4 * kMfmaQueries + 4 * q + 1] = live ? (float)(sqrt(e2) * (double)s_q) * up : 0.0f;
+        p.q8c[4 * kMfmaQueries + 4 * q + 2] = live ? wn + fabsf(wn) * 0x1p-22f : 0.0f;
     }
     set_guess(p, q, lane, have);
 }
@@ -1937,8 +2049,10 @@ __device__ __forceinline__ uint32_t lds_add(uint32_t* p, uint32_t v) {
 
 // The survivors of one lane (`m`: its surviving accumulators `acc` of query q, see fine_survivors) go into the ring.  Called by
 // all lanes of a streaming wave together.
+// SIX: 6-bit survivors; the entry carries the left-hand side of their test, 4 acc + off (scan_mfma8_kernel), as float bits.
+template <bool SIX = false>
 __device__ __forceinline__ void ring_push(SurvRing& ring, uint32_t m, const i32x16& acc, float sblk, uint32_t q, uint32_t hh, uint32_t si,
-                                          uint32_t elb) {
+                                          uint32_t elb, float off = 0.0f) {
     const uint32_t n = (uint32_t)__builtin_popcount(m);
     uint32_t pos = 0;
     if (m) pos = lds_add(&ring.tail, n);
@@ -1949,7 +2063,7 @@ __device__ __forceinline__ void ring_push(SurvRing& ring, uint32_t m, const i32x
         if (m & (1u << i)) {
             const uint32_t slot = pos & (kRing - 1);
             lds_st(&ring.lo[slot], elb);
-            ring.acc[slot] = acc[i];
+            ring.acc[slot] = SIX ? __builtin_bit_cast(int, fmaf(4.0f, (float)acc[i], off)) : acc[i];
             ring.sblk[slot] = sblk;
             PCV_LDS_ORDER();
             lds_st(&ring.hi[slot], hib + (uint32_t)((i & 3) + 8 * (i >> 2)));  // row of the block this accumulator holds
@@ -1977,9 +2091,15 @@ struct DrainStack {
     int acc[kStack];
     float sblk[kStack];
 };
-template <int NQ>
+// SIX: the ring holds 6-bit survivors.  They meet the 6-bit test again (left-hand side from the ring, T' of now), and what is left
+// has its int8 row read — P16 pieces of 16 bytes, eight lanes an entry, against the int8 query tile in LDS (lq8) — and goes on
+// as an int8 survivor would: the int8 test against the thresholds of now, likely ones at once, the others to the stack.
+constexpr int kSixMaxDp8 = 384;                  // widest rows (padded) the 6-bit form takes: mfma8_six_pass
+constexpr int kSixPieces = kSixMaxDp8 / 16 / 8;  // 16-byte int8 pieces a drain lane reads of a survivor's row
+template <int NQ, bool SIX = false>
 __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& ring, DrainStack& stk, const uint32_t* ltau0, const float* lsq,
-                                                const float* lvq, float* lU, int lane, int D4, uint32_t streaming, unsigned long long* stamp) {
+                                                const float* lvq, float* lU, int lane, int D4, uint32_t streaming, unsigned long long* stamp,
+                                                const uint4* lq8 = nullptr, int LDQ = 0, float* lT6 = nullptr) {
     static_assert(NQ <= 64, "one query per lane");
     // diagnostic build (-DPCV_STAMPS; stamp = this wave's 8 words): 0 entry, 3 end, 4 entries out of the ring, 5 ticks at work,
     // 6 rounds of eight worked, 7 entries shed by a repeated coarse test, 2 most entries waiting (ring: high word, stack: low word)
@@ -2131,7 +2251,7 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
     // wave used to fetch them for every block, a 64-line gather each — agent-scope loads that go past the L2 to the memory
     // side: 2816 waves x 64 requests per ~6 us beside the row stream.  That, not the survivors' round trips, was what set a
     // 64-query pass apart from a one-query pass: 0.94 -> 0.78 ms at 12.5M rows.)
-    float myU = __builtin_inff(), myT = -__builtin_inff();
+    float myU = __builtin_inff(), myT = -__builtin_inff(), myT6 = __builtin_inff();
     auto refresh = [&](bool fetch) {
         const uint32_t tau_now = my_tau;
         if (fetch) my_tau = ld_relaxed(&p.tau_c[ql]);
@@ -2139,6 +2259,10 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
         myU = ql < p.B ? (my_sq != 0.0f ? (T - fabsf(T) * 2e-6f) - c1 : dead) : __builtin_inff();
         myT = ql < p.B && my_sq != 0.0f ? T : -__builtin_inff();
         if (lane < NQ) __hip_atomic_store(&lU[lane], myU, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if constexpr (SIX) {  // the 6-bit test's right-hand side per unit of s_blk: T lowered by its f32 rounding, no L1 term
+            myT6 = ql < p.B ? (my_sq != 0.0f ? T - fabsf(T) * 2e-6f : dead) : __builtin_inff();
+            if (lane < NQ) __hip_atomic_store(&lT6[lane], myT6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
     };
     // the entries of the lanes in `set` (one per lane: ehi, elo), eight at a time
     auto work_set = [&](unsigned long long set, uint32_t ehi, uint32_t elo) {
@@ -2175,7 +2299,7 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
         if (tail != head) {
             idle = 0;
             const uint32_t n = min(tail - head, 64u);
-            const bool have = (uint32_t)lane < n;
+            bool have = (uint32_t)lane < n;
             uint32_t ehi = 0, elo = 0;
             int eacc = 0;
             float esb = 0.0f;
@@ -2194,12 +2318,67 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
             PCV_LDS_ORDER();
             if (lane == 0) lds_st(&ring.head, head);  // the producers may go on while these entries are worked on
             const int eq = (int)((ehi >> 5) & 0xffu);
+            if constexpr (SIX) {
+                if (have) g_atomic_add(&p.cand_cnt[eq * kHot + 34], 1u);  // statistics: 6-bit survivors
+                have = have && __builtin_bit_cast(float, eacc) >= esb * __shfl(myT6, eq);
+                const int P16 = ((D4 * 4 + 127) & ~127) >> 4;
+                unsigned long long set = __ballot(have);
+                while (set) {  // the int8 rows of the entries left, eight at a time
+                    const unsigned long long taken_from = set;
+                    int src = -1;
+#pragma unroll
+                    for (uint32_t j = 0; j < 8; ++j) {
+                        if (set) {
+                            const int s0 = __builtin_ctzll(set);
+                            set &= set - 1;
+                            if (g == j) src = s0;
+                        }
+                    }
+                    const unsigned long long taken = taken_from & ~set;
+                    const bool on = src >= 0;
+                    const uint32_t hi8 = (uint32_t)__shfl((int)ehi, on ? src : 0), lb8 = (uint32_t)__shfl((int)elo, on ? src : 0);
+                    const int q8q = (int)((hi8 >> 5) & 0xffu), rib = (int)(hi8 & 31u), si8 = (int)((hi8 >> 13) & ((1u << kRingSegBits) - 1u));
+                    int part = 0;
+                    float sb = 0.0f;
+                    if (on) {
+                        const uint4* b8 = gld(&p.seg[si8].blk8);
+                        sb = gld(gld(&p.seg[si8].scale8) + lb8);
+                        // (the 6-bit form runs at rows of up to 384 features, P16 <= 24: at most three pieces a lane.  Eight staged
+                        // pieces, enough for 1024 features, put the kernel at 168 registers with 60-68 bytes a lane spilled; with three
+                        // it takes 149, no scratch, against 140 for the int8 DRAIN form — three waves per SIMD either way)
+                        uint4 v[kSixPieces];
+#pragma unroll
+                        for (int j = 0; j < kSixPieces; ++j)
+                            if (sub + 8 * j < P16) v[j] = __builtin_bit_cast(uint4, gld4((const float4*)b8 + ((size_t)lb8 * P16 + sub + 8 * j) * 32 + rib));
+#pragma unroll
+                        for (int j = 0; j < kSixPieces; ++j)
+                            if (sub + 8 * j < P16) {
+                                const uint4 qv = lq8[(size_t)q8q * LDQ + sub + 8 * j];
+                                part = __builtin_amdgcn_sdot4((int)v[j].x, (int)qv.x, part, false);
+                                part = __builtin_amdgcn_sdot4((int)v[j].y, (int)qv.y, part, false);
+                                part = __builtin_amdgcn_sdot4((int)v[j].z, (int)qv.z, part, false);
+                                part = __builtin_amdgcn_sdot4((int)v[j].w, (int)qv.w, part, false);
+                            }
+                    }
+#pragma unroll
+                    for (int off = 4; off > 0; off >>= 1) part += __shfl_xor(part, off);
+                    // back to the entry's lane: the j-th entry taken went to lane group j
+                    const int rank = (int)__builtin_popcountll(taken & ((1ull << lane) - 1ull));
+                    const int a8 = __shfl(part, 8 * rank);
+                    const float s8 = __shfl(sb, 8 * rank);
+                    if ((taken >> lane) & 1ull) {
+                        eacc = a8;
+                        esb = s8;
+                    }
+                }
+            }
             const float U = __shfl(myU, eq), vq = __shfl(my_vq, eq), Tq = __shfl(myT, eq);
             const float rhs = fmaf(esb, U, -vq);
             const bool keep = have && (float)eacc >= rhs;
             // likely: the estimate clears the threshold by less than a quarter of the margin (margin = s_blk T - rhs)
             const bool likely = keep && (float)eacc >= fmaf(0.25f, rhs, 0.75f * esb * Tq);
-            if (have) g_atomic_add(&p.cand_cnt[eq * kHot + 32], 1u);  // statistics: coarse survivors
+            // statistics: coarse survivors (6-bit form: those that the int8 test lets through)
+            if (SIX ? keep : have) g_atomic_add(&p.cand_cnt[eq * kHot + 32], 1u);
             const unsigned long long wait = __ballot(keep && !likely);
             const uint32_t nw = (uint32_t)__builtin_popcountll(wait);
             PCV_DCOUNT(4, n)
@@ -2275,8 +2454,14 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
 // 30M x 512 / 128 queries, 8.4 against 7.0 ms at 50M x 768 while U was still read two steps before the test: there a block is
 // 16-24 KB and takes tens of microseconds, the 128-line gather per block is not what bounds it, and a keeper that is itself
 // busy in the fine screen keeps everybody's thresholds waiting.)
-template <int NT, bool NTL, int WPB, int NBUF, bool DRAIN, int NCHT>
+// SIX (DRAIN form, chunk count known): the streaming waves read the 6-bit copy (scan.h) — three 16-byte pieces per lane and chunk
+// instead of four, unpacked to the int8 fragment u = lo | hi << 4 in [0, 63] — and test a block by the L2 bound:
+//       keep  iff  4 acc + off  >=  s_blk T'_q,     off = (R_blk A_q + N_blk E_q)(1 + 2^-20) + Wn_q
+// (T'_q = (tau - eps32) s_q lowered by 2e-6 relative, as in the int8 test; A, E, Wn: quantize_queries_kernel; R = s_blk r_blk,
+// N = s_blk n_blk: pack6_kernel).  The drain wave re-screens the survivors against their int8 rows.
+template <int NT, bool NTL, int WPB, int NBUF, bool DRAIN, int NCHT, bool SIX = false>
 __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(const ScanParams* __restrict__ pp) {
+    static_assert(!SIX || (DRAIN && NCHT > 0), "the 6-bit screen exists in the DRAIN form with a known chunk count");
     const ScanParams& p = *pp;
     constexpr uint32_t SW = DRAIN ? WPB - 1 : WPB;  // streaming waves of a workgroup
     constexpr bool ULDS = DRAIN;                    // the test's U_q comes from LDS
@@ -2294,6 +2479,7 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
     __shared__ uint32_t stack_words[DRAIN ? sizeof(DrainStack) / 4 : 4];
     DrainStack& stack = *(DrainStack*)stack_words;
     __shared__ float lU[NT * 32];  // DRAIN form: U_q of the test (below) from the thresholds as the drain wave last saw them
+    __shared__ float lT6[SIX ? NT * 32 : 1];  // SIX: T'_q of the 6-bit test, likewise
     const int lane = threadIdx.x & 63;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     PCV_STAMP(0)
@@ -2325,24 +2511,38 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
         return (q < p.B) ? (sqq != 0.0f ? (T - fabsf(T) * 2e-6f) - c1 : dead_u) : __builtin_inff();
     };
     if constexpr (ULDS) {  // the first U of every query (the drain wave keeps them fresh from here on)
-        for (int q = threadIdx.x; q < NT * 32; q += WPB * 64) lU[q] = u_of(q, ld_relaxed(&p.tau_c[q]), q < p.B ? 0.5f * gld(&p.margin32[q]) : 0.0f);
+        for (int q = threadIdx.x; q < NT * 32; q += WPB * 64) {
+            const uint32_t tk = ld_relaxed(&p.tau_c[q]);
+            const float e32q = q < p.B ? 0.5f * gld(&p.margin32[q]) : 0.0f;
+            lU[q] = u_of(q, tk, e32q);
+            if constexpr (SIX) {
+                const float T = (key_f32(max(ltau0[q], tk)) - e32q) * lsq[q];
+                lT6[q] = (q < p.B) ? (lsq[q] != 0.0f ? T - fabsf(T) * 2e-6f : dead_u) : __builtin_inff();
+            }
+        }
         __syncthreads();
     }
     float sq[NT], vq[NT], e32[NT];
+    float a6[NT], e6[NT], w6[NT];  // SIX: the 6-bit test's constants of the lane's queries
     uint32_t tau0[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const bool live = 32 * t + c < p.B;
         sq[t] = lsq[32 * t + c];
         vq[t] = lvq[32 * t + c];
+        if constexpr (SIX) {
+            a6[t] = gld(&p.q8c[4 * kMfmaQueries + 4 * (32 * t + c)]);
+            e6[t] = gld(&p.q8c[4 * kMfmaQueries + 4 * (32 * t + c) + 1]);
+            w6[t] = gld(&p.q8c[4 * kMfmaQueries + 4 * (32 * t + c) + 2]);
+        }
         e32[t] = live ? 0.5f * gld(&p.margin32[32 * t + c]) : 0.0f;
         tau0[t] = ltau0[32 * t + c];
     }
 
     if constexpr (DRAIN) {
         if (wave == SW) {
-            drain_survivors<NT * 32>(p, ring, stack, ltau0, lsq, lvq, lU, lane, D4, SW,
-                                     p.stamps ? p.stamps + (size_t)(blockIdx.x * WPB + wave) * 8 : nullptr);
+            drain_survivors<NT * 32, SIX>(p, ring, stack, ltau0, lsq, lvq, lU, lane, D4, SW,
+                                          p.stamps ? p.stamps + (size_t)(blockIdx.x * WPB + wave) * 8 : nullptr, lq8, LDQ, lT6);
             return;
         }
     }
@@ -2374,7 +2574,10 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
 #if PCV_EXP == 7 || PCV_EXP == 9  // timing experiment (wrong results): the rows of 256 blocks over and over — they come out of the L2
             k.rows = row_rsrc((const float4*)k.sc.blk8 + (size_t)(k.lb & 255u) * P16 * 32, (uint32_t)P16 * 512u);
 #else
-            k.rows = row_rsrc((const float4*)k.sc.blk8 + (size_t)k.lb * P16 * 32, (uint32_t)P16 * 512u);
+            if constexpr (SIX)
+                k.rows = row_rsrc(k.sc.blk6 + (size_t)k.lb * NCH * 192, (uint32_t)NCH * 3072u);
+            else
+                k.rows = row_rsrc((const float4*)k.sc.blk8 + (size_t)k.lb * P16 * 32, (uint32_t)P16 * 512u);
 #endif
         }
     };
@@ -2399,6 +2602,7 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
     // lane (c, h) tests rows 4h + {0..3, 8..11, 16..19, 24..27} of the block
     uint32_t tauk[NT];
     float sblk = 0.0f;
+    float4 s6 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // SIX: the block's {s_blk, R, N, -}
     auto prefetch = [&]() __attribute__((always_inline)) {  // (before the step's row loads and untouched until the epilogue: see scan_mfma_kernel)
         if constexpr (ULDS) {
             // (U itself is read in the epilogue, at the moment of the test: an LDS read costs the block ~100 cycles, and while the
@@ -2407,7 +2611,10 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
 #pragma unroll
             for (int t = 0; t < NT; ++t) tauk[t] = ld_relaxed(&p.tau[(32 * t + c) * kHot]);
         }
-        sblk = gld(cons.sc.scale8 + cons.lb);
+        if constexpr (SIX)
+            s6 = gld4(cons.sc.scale6 + cons.lb);
+        else
+            sblk = gld(cons.sc.scale8 + cons.lb);
     };
 
 #ifdef PCV_STAMPS
@@ -2443,15 +2650,22 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
         }
         // One scale per block: the right-hand side s_blk U - V is the same for the 16 rows a lane tests, so the largest
         // accumulator decides whether the block has a survivor at all.  Nearly every block ends here.
-        float rhs[NT];
+        float rhs[NT], off6[NT];
         bool hot = false;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             int m = acc[t][0];
 #pragma unroll
             for (int i = 1; i < 16; ++i) m = max(m, acc[t][i]);
-            rhs[t] = fmaf(sblk, U[t], -vq[t]);  // (NaN scale: a block without a searchable row, no comparison succeeds)
-            hot |= (float)m >= rhs[t];
+            if constexpr (SIX) {  // 4 acc + off >= s_blk T' (the header above the kernel)
+                const float T6 = __hip_atomic_load(&lT6[32 * t + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                off6[t] = fmaf(fmaf(s6.y, a6[t], s6.z * e6[t]), 1.0f + 0x1p-20f, w6[t]);
+                rhs[t] = s6.x * T6;  // (NaN scale: a block without a searchable row, no comparison succeeds)
+                hot |= fmaf(4.0f, (float)m, off6[t]) >= rhs[t];
+            } else {
+                rhs[t] = fmaf(sblk, U[t], -vq[t]);  // (NaN scale: a block without a searchable row, no comparison succeeds)
+                hot |= (float)m >= rhs[t];
+            }
         }
 #if PCV_EXP == 8 || PCV_EXP == 9  // timing experiment (wrong results): every block ends at its test
         asm volatile("" ::"s"(__ballot(hot)));
@@ -2464,7 +2678,12 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
         for (int t = 0; t < NT; ++t) {
             mask[t] = 0;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) mask[t] |= ((float)acc[t][i] >= rhs[t]) ? (1u << i) : 0u;
+            for (int i = 0; i < 16; ++i) {
+                if constexpr (SIX)
+                    mask[t] |= (fmaf(4.0f, (float)acc[t][i], off6[t]) >= rhs[t]) ? (1u << i) : 0u;
+                else
+                    mask[t] |= ((float)acc[t][i] >= rhs[t]) ? (1u << i) : 0u;
+            }
         }
         bool any = false;
 #pragma unroll
@@ -2476,7 +2695,12 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
             if constexpr (DRAIN) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
-                    if (__any(mask[t] != 0)) ring_push(ring, mask[t], acc[t], sblk, (uint32_t)(32 * t + c), (uint32_t)h, (uint32_t)esc.si, elb);
+                    if (__any(mask[t] != 0)) {
+                        if constexpr (SIX)
+                            ring_push<true>(ring, mask[t], acc[t], s6.x, (uint32_t)(32 * t + c), (uint32_t)h, (uint32_t)esc.si, elb, off6[t]);
+                        else
+                            ring_push(ring, mask[t], acc[t], sblk, (uint32_t)(32 * t + c), (uint32_t)h, (uint32_t)esc.si, elb);
+                    }
             } else {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) fine_survivors(p, mask[t], t, esc, elb, ltau0, lane, D4);
@@ -2538,10 +2762,12 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
         // chunk count known: lcm(NCHT, NBUF) steps written out; step s consumes chunk s % NCHT of its block out of buffer
         // s % NBUF while chunk (s + NBUF - 1) % NCHT of a later block is requested into the buffer consumed a step ago
         constexpr int PERIOD = NCHT * NBUF / std::gcd(NCHT, NBUF);
+        constexpr int NPC = SIX ? 3 : 4;              // 16-byte pieces a lane loads per chunk
+        constexpr uint32_t CHB = SIX ? 3072u : 4096u;  // bytes of a chunk
 #pragma unroll
         for (int i = 0; i < NBUF - 1; ++i) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) buf[i][j] = ld_piece<NTL>(prod.rows, lane_off + (uint32_t)j * 1024u, (uint32_t)(i % NCHT) * 4096u);
+            for (int j = 0; j < NPC; ++j) buf[i][j] = ld_piece<NTL>(prod.rows, lane_off + (uint32_t)j * 1024u, (uint32_t)(i % NCHT) * CHB);
             if ((i % NCHT) == NCHT - 1 && prod.gb < p.total_blocks) enter_block(prod, prod.gb + total_waves);
         }
         auto step = [&](auto S) __attribute__((always_inline)) -> bool {  // true: the wave's stream is over
@@ -2551,16 +2777,36 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
                 {   // produce (always: see `produce`)
                     float4(&b)[4] = buf[(s + NBUF - 1) % NBUF];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) b[j] = ld_piece<NTL>(prod.rows, lane_off + (uint32_t)j * 1024u, (uint32_t)pch * 4096u);
+                    for (int j = 0; j < NPC; ++j) b[j] = ld_piece<NTL>(prod.rows, lane_off + (uint32_t)j * 1024u, (uint32_t)pch * CHB);
                     if constexpr (pch == NCHT - 1) {
                         if (prod.gb < p.total_blocks) enter_block(prod, prod.gb + total_waves);
                     }
                 }
                 {   // consume
                     const float4(&b)[4] = buf[s % NBUF];
+                    uint32_t u6[16];  // SIX: the int8 fragment, dword d = 4 ks + j: low nibbles | high parts << 4
+                    if constexpr (SIX) {
+                        const uint32_t lo[8] = {__builtin_bit_cast(uint32_t, b[0].x), __builtin_bit_cast(uint32_t, b[0].y),
+                                                __builtin_bit_cast(uint32_t, b[0].z), __builtin_bit_cast(uint32_t, b[0].w),
+                                                __builtin_bit_cast(uint32_t, b[1].x), __builtin_bit_cast(uint32_t, b[1].y),
+                                                __builtin_bit_cast(uint32_t, b[1].z), __builtin_bit_cast(uint32_t, b[1].w)};
+                        const uint32_t hi[4] = {__builtin_bit_cast(uint32_t, b[2].x), __builtin_bit_cast(uint32_t, b[2].y),
+                                                __builtin_bit_cast(uint32_t, b[2].z), __builtin_bit_cast(uint32_t, b[2].w)};
+#pragma unroll
+                        for (int d = 0; d < 16; ++d) {
+                            const uint32_t l = (d & 1) ? (lo[d >> 1] >> 4) : lo[d >> 1];
+                            const int sh = 2 * (d & 3);  // the 2-bit part sits at bits sh, sh + 1 of each byte; it goes to bits 4, 5
+                            const uint32_t hpart = sh <= 4 ? (hi[d >> 2] << (4 - sh)) : (hi[d >> 2] >> (sh - 4));
+                            u6[d] = (l & 0x0f0f0f0fu) | (hpart & 0x30303030u);
+                        }
+                    }
 #pragma unroll
                     for (int ks = 0; ks < 4; ++ks) {
-                        const i32x4 a = __builtin_bit_cast(i32x4, b[ks]);
+                        i32x4 a;
+                        if constexpr (SIX)
+                            a = i32x4{(int)u6[4 * ks], (int)u6[4 * ks + 1], (int)u6[4 * ks + 2], (int)u6[4 * ks + 3]};
+                        else
+                            a = __builtin_bit_cast(i32x4, b[ks]);
                         const int pc = 2 * (ch * 4 + ks) + h;
 #pragma unroll
                         for (int t = 0; t < NT; ++t) {
@@ -3043,9 +3289,11 @@ __global__ __launch_bounds__(256) void rescore_select_kernel(const ScanParams* _
         if (p.coarse_host) {
             p.coarse_host[q] = ld_relaxed(&p.cand_cnt[q * kHot + 32]);
             p.coarse_host[kMfmaQueries + q] = ld_relaxed(&p.cand_cnt[q * kHot + 33]);
+            p.coarse_host[2 * kMfmaQueries + q] = ld_relaxed(&p.cand_cnt[q * kHot + 34]);
         }
         st_relaxed(&p.cand_cnt[q * kHot + 32], 0u);
         st_relaxed(&p.cand_cnt[q * kHot + 33], 0u);
+        st_relaxed(&p.cand_cnt[q * kHot + 34], 0u);
         if ((raw_cnt > p.cand_cap || failed) && p.flag_rec) p.flag_rec->pos = 1;
         st_relaxed(&p.tau[q * kHot], kKeyNegInf);
         st_relaxed(&p.tau_c[q], kKeyNegInf);
@@ -3331,10 +3579,40 @@ int mfma8_pass_queries(int Dp) {
 
 // 64 queries: three chunk buffers (150 registers).  Since the row loads go through a buffer descriptor a fourth fits without
 // spilling (166 registers) and changes nothing: 6.259 against 6.251 ms at 100M x 384, 0.933 / 0.943 at 12.5M, 5.999 / 5.989 at 768-d.
-template <int NT, bool NTL, int WPB = 4, int NBUF = (NT == 2 ? 3 : 4), bool DRAIN = false, int NCHT = 0>
+template <int NT, bool NTL, int WPB = 4, int NBUF = (NT == 2 ? 3 : 4), bool DRAIN = false, int NCHT = 0, bool SIX = false>
 static void launch_mfma8_variant(hipStream_t st, const ScanParams* dp, unsigned grid, size_t lds) {
-    allow_dynamic_lds((const void*)scan_mfma8_kernel<NT, NTL, WPB, NBUF, DRAIN, NCHT>, lds);
-    scan_mfma8_kernel<NT, NTL, WPB, NBUF, DRAIN, NCHT><<<grid, WPB * 64, lds, st>>>(dp);
+    allow_dynamic_lds((const void*)scan_mfma8_kernel<NT, NTL, WPB, NBUF, DRAIN, NCHT, SIX>, lds);
+    scan_mfma8_kernel<NT, NTL, WPB, NBUF, DRAIN, NCHT, SIX><<<grid, WPB * 64, lds, st>>>(dp);
+}
+// The 6-bit form: 5..64 queries (the DRAIN form), rows of up to 384 features (chunk counts 1..3), non-temporal loads, four chunk
+// buffers — the shapes the copy is built for.  The searcher asks mfma8_six_pass before it sets kFlagSix.
+bool mfma8_six_pass(int B, int Dp, uint32_t flags, int nseg) {
+    const int nt = B <= 32 ? 1 : 2;
+    return B > 4 && B <= 64 && ((Dp + 127) & ~127) <= kSixMaxDp8 && !(flags & (1u << 28)) && !(flags & 1u) && (flags >> 24 & 0xf) != 3 &&
+           nseg < (1 << kRingSegBits) && mfma8_lds(nt, Dp) + 68 * 1024 <= 156 * 1024;
+}
+template <int NT>
+static void launch_mfma8_six(hipStream_t st, const ScanParams* dp, unsigned grid, size_t lds, int nch) {
+    switch (nch) {
+        case 1: launch_mfma8_variant<NT, true, 12, 4, true, 1, true>(st, dp, grid, lds); break;
+        case 2: launch_mfma8_variant<NT, true, 12, 4, true, 2, true>(st, dp, grid, lds); break;
+        case 3: launch_mfma8_variant<NT, true, 12, 4, true, 3, true>(st, dp, grid, lds); break;
+        default: PCV_FAIL(PCV_ERR_INTERNAL, "6-bit screen: %d chunks per block", nch);
+    }
+}
+size_t six_copy_bytes(uint32_t nblocks, int Dp) { return (size_t)nblocks * (size_t)(((Dp + 127) & ~127) >> 7) * 3072; }
+void launch_pack6(hipStream_t st, const float4* blk, const float* scale, const uint4* blk8, const float* scale8, uint4* blk6, float4* scale6,
+                  uint32_t first_block, uint32_t nblocks, int D4) {
+    if (first_block >= nblocks) return;
+    pack6_kernel<<<std::min<unsigned>(cdiv64((int64_t)(nblocks - first_block), 4), 1u << 16), 256, 0, st>>>(blk, scale, blk8, scale8, nullptr, blk6, scale6, first_block,
+                                                                              nblocks, D4);
+    PCV_LAUNCHED();
+}
+void launch_repack6_blocks(hipStream_t st, const float4* blk, const float* scale, const uint4* blk8, const float* scale8, const uint32_t* blocks,
+                           uint32_t n, uint4* blk6, float4* scale6, int D4) {
+    if (n == 0) return;
+    pack6_kernel<<<std::min<unsigned>(cdiv64((int64_t)n, 4), 1u << 16), 256, 0, st>>>(blk, scale, blk8, scale8, blocks, blk6, scale6, 0u, n, D4);
+    PCV_LAUNCHED();
 }
 // the DRAIN form, chunk count (dimension / 128, rounded up) as a template argument
 template <int NT, bool NTL, int NBUF>
@@ -3399,6 +3677,12 @@ void launch_scan_mfma8(hipStream_t st, const ScanParams& p, const ScanParams* dp
         constexpr unsigned kW = 12;
         unsigned g12 = (unsigned)num_cus * (gm ? gm : 1u);
         g12 = std::min(g12, (p.total_blocks + (kW - 2)) / (kW - 1));
+        if (p.flags & kFlagSix) {  // (the searcher set it only where mfma8_six_pass holds)
+            if (NT == 1) launch_mfma8_six<1>(st, dp, g12, lds, nch);
+            else launch_mfma8_six<2>(st, dp, g12, lds, nch);
+            PCV_LAUNCHED();
+            return;
+        }
         if (NT == 1) {
             if (ntl) launch_mfma8_drain<1, true, 4>(st, dp, g12, lds, nch);
             else launch_mfma8_drain<1, false, 4>(st, dp, g12, lds, nch);

@@ -38,6 +38,9 @@ struct Segment {
     uint4* mid16 = nullptr;  // row-major 16-bit copy (scan.h) + its per-row scales
     float* scale16 = nullptr;
     uint32_t mid_rows = 0;   // rows the mid copy covers
+    uint4* blk6 = nullptr;   // 6-bit screening copy beside the int8 one (scan.h; AUTO, large sources) + its per-block constants
+    float4* scale6 = nullptr;
+    uint32_t six_rows = 0;   // rows the 6-bit copy covers
     int64_t id0 = 0;
     int64_t pos0 = 0;
     uint32_t nrows = 0, cap_rows = 0, scaled_rows = 0;
@@ -168,7 +171,8 @@ struct pcv_searcher {
     // what one pass brings back: written by rescore_select_kernel straight into pinned memory
     struct Pinned {
         uint32_t cnt[kMfmaQueries];
-        uint32_t coarse[2 * kMfmaQueries];  // rows per query that passed the coarse screen, then those that also passed the mid screen (statistics)
+        uint32_t coarse[3 * kMfmaQueries];  // rows per query that passed the coarse screen, then those that also passed the mid screen, then
+                                            // those that passed the 6-bit screen (statistics)
         float spec_base[kMfmaQueries];  // median / best seed slot per query, k-th best exact score per query (scan.h: spec_gap)
         float spec_top[kMfmaQueries];
         float kth[kMfmaQueries];
@@ -212,6 +216,7 @@ struct pcv_searcher {
     std::unique_ptr<MidTask> mid_task;
     int screen_copy = PCV_SCREEN_COPY_AUTO;  // pcv_searcher_set_screening_copy
     bool screen_copy_gave_way = false;       // AUTO: the copies were dropped to make room for rows
+    bool six_gave_way = false;               // AUTO: the 6-bit copies were dropped to make room (rows, copies): not built again
     int copies_kind = 0;                     // 0: not every row of every segment is covered by a screening copy; 1 bf16; 2 int8
     bool wide_sharded = false;               // pcv_searcher_allow_wide_sharded_pass: the host vouches for int8 copies on every rank
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -244,6 +249,8 @@ struct pcv_searcher {
         bool mid = false;  // every selected segment had its mid copy
         int src = 0;  // what the scan streamed: 0 f32 rows, 1 bf16 copies, 2 int8 copies
         int64_t stream_bytes = 0;  // ... and how many bytes of it the scan kernel has to read, padding included
+        int64_t int8_bytes = 0;    // ... what the int8 copy would have been (the mid copy's trigger is the int8 screen's)
+        bool six = false;          // the scan streamed the 6-bit copies
         bool replayed = false;  // launched as a graph: only the pass as a whole was timed
         bool learned = false;   // the speculative threshold had a learned part
         bool guessing = false;  // the pass ran with a speculative threshold (and sent the seed statistics home)
@@ -285,6 +292,8 @@ void free_segment(Segment& g) {
     if (g.scale8) (void)hipFree(g.scale8);
     if (g.mid16) (void)hipFree(g.mid16);
     if (g.scale16) (void)hipFree(g.scale16);
+    if (g.blk6) (void)hipFree(g.blk6);
+    if (g.scale6) (void)hipFree(g.scale6);
     g = Segment();
 }
 
@@ -398,11 +407,44 @@ void drop_mid_copies(pcv_searcher* s) {
         }
 }
 
+// The 6-bit copies (scan.h) go: they give way first when memory is short, and before a mid copy (a crowded screen gains nothing
+// from them; 100M x 384 with both would not fit the device).
+void drop_six_copies(pcv_searcher* s) {
+    for (auto& src : s->sources)
+        for (auto& g : src.segs) {
+            if (g.blk6) (void)hipFree(g.blk6);
+            if (g.scale6) (void)hipFree(g.scale6);
+            g.blk6 = nullptr;
+            g.scale6 = nullptr;
+            g.six_rows = 0;
+        }
+}
+bool have_six_copies(const pcv_searcher* s) {
+    for (const auto& src : s->sources)
+        for (const auto& g : src.segs)
+            if (g.blk6) return true;
+    return false;
+}
+size_t six_bytes_held(const pcv_searcher* s) {
+    size_t n = 0;
+    for (const auto& src : s->sources)
+        for (const auto& g : src.segs)
+            if (g.blk6) n += six_copy_bytes(g.cap_rows / kBlockRows, s->Dp) + (size_t)(g.cap_rows / kBlockRows) * sizeof(float4);
+    return n;
+}
+// What the optional copies (mid, 6-bit) leave free of the device: rows, other searchers and models of the process, the candidate
+// lists of an overflow rerun — a tenth of it, at least 4 GB.
+size_t copy_headroom(size_t total_b) { return std::max<size_t>((size_t)4 << 30, total_b / 10); }
+
 // Mid copies (scan.h) of the rows that have their scale and no copy yet.  `must`: an allocation failure is an error
 // (PCV_MID_COPY_ON); otherwise it ends the attempt for good (mid_gave_way).
 void build_mid_copies(pcv_searcher* s, bool must) {
     settle_mid_build(s, true);
     hipStream_t st = s->ctx->stream;
+    if (have_six_copies(s)) {
+        PCV_HIP(hipStreamSynchronize(st));
+        drop_six_copies(s);
+    }
     for (auto& src : s->sources)
         for (auto& g : src.segs) {
             if (g.nrows == 0 || (g.mid16 && g.mid_rows >= g.scaled_rows)) continue;
@@ -446,12 +488,17 @@ void maybe_build_mid_copies(pcv_searcher* s) {
     // (only if the memory is plainly there: the copy is a convenience — a few per cent of a pass on Gaussian rows, a quarter on
     // clustered ones — and the headroom is for rows, for other searchers and models of the process, for the candidate lists of
     // an overflow rerun: a tenth of the device, at least 4 GB, stays free)
+    // (the 6-bit copies go before a mid copy is built — scan.h — so their bytes count as free; they are dropped only if it is)
     size_t free_b = 0, total_b = 0, need = 0;
     for (const auto& src : s->sources)
         for (const auto& g : src.segs) need += (size_t)g.cap_rows * ((size_t)s->Dp * 2 + 4);
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + std::max<size_t>((size_t)4 << 30, total_b / 10))
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + six_bytes_held(s) > need + copy_headroom(total_b)) {
+        if (have_six_copies(s)) {
+            PCV_HIP(hipStreamSynchronize(s->ctx->stream));
+            drop_six_copies(s);
+        }
         start_mid_build(s);  // beside the searches: this call and the next ones go on without it meanwhile
-    else
+    } else
         s->mid_gave_way = true;
     s->mid_hot_passes = 0;
 }
@@ -459,6 +506,7 @@ void maybe_build_mid_copies(pcv_searcher* s) {
 void drop_screening_copies(pcv_searcher* s) {
     settle_mid_build(s, true);  // (it reads the int8 copy's block scales)
     s->copies_kind = 0;
+    drop_six_copies(s);
     for (auto& src : s->sources)
         for (auto& g : src.segs) {
             if (g.blk16) (void)hipFree(g.blk16);
@@ -489,6 +537,14 @@ Segment alloc_segment(pcv_searcher* s, int64_t cap_rows, bool with_ids) {
     g.cap_rows = nblk * kBlockRows;
     const size_t bytes = (size_t)nblk * s->D4 * 32 * sizeof(float4);
     hipError_t e = hipMalloc((void**)&g.blk, bytes);
+    if (e != hipSuccess && have_six_copies(s)) {
+        // the rows themselves come first: the 6-bit copies go before anything else
+        (void)hipGetLastError();
+        PCV_HIP(hipStreamSynchronize(s->ctx->stream));
+        drop_six_copies(s);
+        s->six_gave_way = true;
+        e = hipMalloc((void**)&g.blk, bytes);
+    }
     if (e != hipSuccess && s->mids_present && s->mid_copy == PCV_MID_COPY_AUTO) {
         // the rows themselves come first: the mid copies go before the screening copies do
         (void)hipGetLastError();
@@ -606,6 +662,71 @@ void append_rows(pcv_searcher* s, Source& src, const int64_t* ids, const void* r
     src.next_implicit_id += n;
 }
 
+// AUTO builds the 6-bit copy for searchers of at least kSixRows rows (PCV_SCAN_FLAGS bit 31: at any size; bit 29: never), rows of
+// up to 384 features, and not beside a mid copy.
+constexpr int64_t kSixRows = (int64_t)8 << 20;
+bool six_wanted(const pcv_searcher* s) {
+    if (s->view_parent) return s->screen_copy == PCV_SCREEN_COPY_INT8 && have_six_copies(s->view_parent);  // a view keeps what its parent keeps
+    if (s->screen_copy != PCV_SCREEN_COPY_AUTO || s->screen_copy_gave_way || s->six_gave_way || (s->scan_flags & kTuneNoSix)) return false;
+    if (((s->Dp + 127) & ~127) > 384 || s->mids_present || s->mid_building || s->mid_copy == PCV_MID_COPY_ON) return false;
+    if (s->scan_flags & kTuneForceSix) return true;
+    int64_t rows = 0;
+    for (const auto& src : s->sources) rows += src.rows();
+    return rows >= kSixRows;
+}
+
+// The 6-bit copies of every segment's rows that have their int8 copy, derived from it (pack6_kernel), after the screening copies
+// of every source are built: a pass streams them only if every selected segment has one.  Like the mid copy they are built only
+// if the device keeps its headroom afterwards (copy_headroom), and an allocation failure or a lack of room drops them all for good
+// on this searcher (six_gave_way, until rows are given back): they are a speed-up, never a requirement.
+void build_six_copies(pcv_searcher* s) {
+    if (!six_wanted(s)) return;
+    hipStream_t st = s->ctx->stream;
+    size_t need = 0;
+    for (const auto& src : s->sources)
+        for (const auto& g : src.segs)
+            if (g.nrows > 0 && g.blk8 && !g.blk6)
+                need += six_copy_bytes(g.cap_rows / kBlockRows, s->Dp) + (size_t)(g.cap_rows / kBlockRows) * sizeof(float4);
+    size_t free_b = 0, total_b = 0;
+    if (need > 0 && !s->fail_copy_alloc &&
+        !(hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + copy_headroom(total_b))) {
+        (void)hipGetLastError();
+        PCV_HIP(hipStreamSynchronize(st));
+        drop_six_copies(s);
+        s->six_gave_way = true;
+        return;
+    }
+    for (auto& src : s->sources)
+        for (auto& g : src.segs) {
+            if (g.nrows == 0 || !g.blk8 || (g.blk6 && g.six_rows >= g.copied_rows)) continue;
+            if (!g.blk6) {
+                const uint32_t nblk = g.cap_rows / kBlockRows;
+                hipError_t e = s->fail_copy_alloc ? hipErrorOutOfMemory : hipMalloc((void**)&g.blk6, six_copy_bytes(nblk, s->Dp));
+                if (e == hipSuccess) {
+                    e = hipMalloc((void**)&g.scale6, (size_t)nblk * sizeof(float4));
+                    if (e != hipSuccess) {
+                        (void)hipFree(g.blk6);
+                        g.blk6 = nullptr;
+                    }
+                }
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    g.blk6 = nullptr;
+                    g.scale6 = nullptr;
+                    PCV_HIP(hipStreamSynchronize(st));
+                    drop_six_copies(s);
+                    s->six_gave_way = true;
+                    return;
+                }
+                g.six_rows = 0;
+            }
+            // (from the block of the first row not covered: the int8 copy re-packed that partial block with a new scale)
+            launch_pack6(st, g.blk, g.scale, g.blk8, g.scale8, g.blk6, g.scale6, g.six_rows / kBlockRows, (g.copied_rows + kBlockRows - 1) / kBlockRows,
+                         s->D4);
+            g.six_rows = g.copied_rows;
+        }
+}
+
 // Screening copies (scan.h) of the rows that got their scale since the last finalize.  Asked for explicitly: a failed
 // allocation is an error; AUTO: it switches the copies off for this searcher (the f32 rows are scanned instead).
 void build_screening_copies(pcv_searcher* s, Source& src) {
@@ -630,6 +751,14 @@ void build_screening_copies(pcv_searcher* s, Source& src) {
             const size_t bytes = kind == 1 ? nblk * (s->D4 / 2) * 32 * sizeof(uint4) : nblk * (size_t)(((s->Dp + 127) & ~127) / 16) * 32 * sizeof(uint4);
             hipError_t e = s->fail_copy_alloc ? hipErrorOutOfMemory  // (PCV_TUNE_FAIL_COPY_ALLOC)
                                               : hipMalloc(kind == 1 ? (void**)&g.blk16 : (void**)&g.blk8, bytes);
+            if (e != hipSuccess && !s->fail_copy_alloc && have_six_copies(s)) {
+                // the 6-bit copies give way first, to the copy they are derived from
+                (void)hipGetLastError();
+                PCV_HIP(hipStreamSynchronize(st));
+                drop_six_copies(s);
+                s->six_gave_way = true;
+                e = hipMalloc(kind == 1 ? (void**)&g.blk16 : (void**)&g.blk8, bytes);
+            }
             if (e != hipSuccess && !s->fail_copy_alloc && s->mids_present && s->mid_copy == PCV_MID_COPY_AUTO) {
                 // a mid copy AUTO built by itself gives way to the screening copy the host asked for
                 (void)hipGetLastError();
@@ -751,6 +880,7 @@ void unhide_found(pcv_searcher* s, Segment& g, uint32_t n) {
             s->d_hblocks.ensure(nb);
             PCV_HIP(hipMemcpyAsync(s->d_hblocks.p, blocks.data(), (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             launch_repack8_blocks(st, g.blk, g.scale, s->d_hblocks.p, nb, g.blk8, g.scale8, s->D4);
+            if (g.blk6) launch_repack6_blocks(st, g.blk, g.scale, g.blk8, g.scale8, s->d_hblocks.p, nb, g.blk6, g.scale6, s->D4);
         }
         PCV_HIP(hipStreamSynchronize(st));  // (blocks goes out of scope)
     }
@@ -939,6 +1069,7 @@ int64_t update_by_id(pcv_searcher* s, const int64_t* ids, const void* rows, int6
         const uint32_t* d_blocks = nb ? s->d_hblocks.p + u.boff : nullptr;
         if (g.blk16) launch_repack16_rows(st, g.blk, g.scale, d_rows, nr, g.blk16, s->D4);
         if (g.blk8 && nb) launch_repack8_blocks(st, g.blk, g.scale, d_blocks, nb, g.blk8, g.scale8, s->D4);
+        if (g.blk6 && nb) launch_repack6_blocks(st, g.blk, g.scale, g.blk8, g.scale8, d_blocks, nb, g.blk6, g.scale6, s->D4);
         if (g.mid16 && g.mid_rows > 0) {
             if (g.blk8 && g.copied_rows >= g.nrows)  // (launch_mid_pack quantised it with the int8 copy's block scales)
                 launch_repack_mid(st, g.blk, g.scale, g.scale8, d_blocks, nb, g.mid_rows, g.mid16, g.scale16, s->D4);
@@ -994,6 +1125,7 @@ void do_finalize(pcv_searcher* s) {
                      s->sources.end());
     if (s->mid_copy == PCV_MID_COPY_ON || (s->mid_copy == PCV_MID_COPY_AUTO && s->mids_present))
         build_mid_copies(s, s->mid_copy == PCV_MID_COPY_ON);  // new rows join the copy that is there
+    build_six_copies(s);  // (over every source: a pass streams them only if every selected segment has one)
     assign_positions(s);
     s->copies_kind = s->sources.empty() ? 0 : copy_kind_wanted(s);
     for (const auto& src : s->sources)
@@ -1040,7 +1172,7 @@ void ensure_workspace(pcv_searcher* s) {
     s->d_qraw.ensure(Q * s->Dp);
     s->d_qbf16.ensure(Q * s->Dp);
     s->d_q8.ensure(Q * (size_t)((s->Dp + 127) & ~127));
-    s->d_q8c.ensure(Q * 4);
+    s->d_q8c.ensure(Q * 8);  // (the int8 test's constants, then the 6-bit test's: scan.h)
     s->d_spec.ensure(Q);
     s->d_margin.ensure(Q);
     s->d_margin32.ensure(Q);
@@ -1105,7 +1237,7 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     p = ScanParams{};
     uint32_t blk0 = 0;
     int64_t rows = 0;
-    bool have_mid = true;
+    bool have_mid = true, have_six = true;
     // stream the screening copies iff every selected segment has one of the kind the searcher keeps
     int src_kind = (kernel == PCV_KERNEL_MFMA) ? copy_kind_wanted(s) : 0;
     if (src_kind == 2 && (mfma8_pass_queries(s->Dp) < B || s->Dp > 1024)) src_kind = 0;
@@ -1113,7 +1245,9 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     for (int i = 0; i < nseg; ++i) {
         const Segment& g = *segs[i].g;
         const bool mid = g.mid16 != nullptr && g.mid_rows >= g.nrows;  // (a copy that does not cover every row yet is not used)
-        tab[i] = SegDesc{g.blk, g.scale, g.ids, g.id0, g.pos0, g.nrows, g.nblocks(), blk0, 0, g.blk16, g.blk8, mid ? g.mid16 : nullptr, mid ? g.scale16 : nullptr, g.scale8};
+        tab[i] = SegDesc{g.blk, g.scale, g.ids, g.id0, g.pos0, g.nrows, g.nblocks(), blk0, 0, g.blk16, g.blk8, mid ? g.mid16 : nullptr, mid ? g.scale16 : nullptr, g.scale8,
+                         g.blk6, g.scale6};
+        have_six = have_six && g.blk6 != nullptr && g.six_rows >= g.nrows;
         have_mid = have_mid && mid;
         if ((src_kind == 1 ? g.blk16 == nullptr : (src_kind == 2 ? g.blk8 == nullptr : false)) || g.copied_rows < g.nrows) src_kind = 0;
         PCV_REQUIRE((uint64_t)blk0 + g.nblocks() < 0xffffff00ull, "search: more than 2^32 row blocks in one launch");
@@ -1163,7 +1297,11 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     p.coarse_host = s->pin->coarse;
     p.flag_rec = d_flag;
     p.cand_cap = s->cand_cap;
-    p.flags = (s->scan_flags & ~(16u | 64u)) | (src_kind == 1 ? 16u : 0u) | (src_kind == 2 ? 64u : 0u);
+    p.flags = (s->scan_flags & ~(16u | 64u | kFlagSix)) | (src_kind == 1 ? 16u : 0u) | (src_kind == 2 ? 64u : 0u);
+    // the 6-bit copies: AUTO's kernel choice only (PCV_KERNEL_MFMA pins the whole-int8 scan), 5..64 queries (scan.h)
+    const bool six = src_kind == 2 && have_six && nseg > 0 && s->kernel == PCV_KERNEL_AUTO && !(s->scan_flags & kTuneNoSix) &&
+                     mfma8_six_pass(B, s->Dp, p.flags, nseg);
+    if (six) p.flags |= kFlagSix;
     const uint32_t seed_parts = ((s->scan_flags >> 16) & 0xff) ? ((s->scan_flags >> 16) & 0xff) : kSeedParts;  // tuning
     p.seed_blocks = std::min<uint32_t>(std::min<uint32_t>(seed_parts, kSeedParts) * kSeedPartRows / kBlockRows, segs[0].g->nblocks());
     p.seed_shift = 0;  // the seed blocks are every 2^shift-th block of segment 0, the largest stride that fits
@@ -1305,11 +1443,15 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     s->pending.rows = rows;
     s->pending.src = src_kind;
     s->pending.mid = have_mid && nseg > 0;
-    // what the scan kernel of this pass must pull from HBM, per 32-row block: the int8 pieces + the block's scale; the bf16 pieces; or the f32 pieces + the 32 row scales
+    s->pending.six = six;
+    // what the scan kernel of this pass must pull from HBM, per 32-row block: the 6-bit pieces + the block's four constants; the
+    // int8 pieces + the block's scale; the bf16 pieces; or the f32 pieces + the 32 row scales
     const int64_t Dp8 = (s->Dp + 127) & ~127;
-    s->pending.stream_bytes = (int64_t)blk0 * (src_kind == 2 ? Dp8 * kBlockRows + (int64_t)kScale8Stride * 4
-                                               : src_kind == 1 ? (int64_t)s->Dp * 2 * kBlockRows
-                                                               : (int64_t)s->Dp * 4 * kBlockRows + kBlockRows * 4);
+    s->pending.int8_bytes = (int64_t)blk0 * (Dp8 * kBlockRows + (int64_t)kScale8Stride * 4);
+    s->pending.stream_bytes = six ? (int64_t)blk0 * (Dp8 * kBlockRows * 3 / 4 + (int64_t)sizeof(float4))
+                              : (int64_t)blk0 * (src_kind == 2 ? Dp8 * kBlockRows + (int64_t)kScale8Stride * 4
+                                                 : src_kind == 1 ? (int64_t)s->Dp * 2 * kBlockRows
+                                                                 : (int64_t)s->Dp * 4 * kBlockRows + kBlockRows * 4);
     s->pending.learned = p.spec_gap == p.spec_gap;
     s->pending.guessing = p.spec_rank > 0 || s->pending.learned;
     s->stats.host_enqueue_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
@@ -1355,6 +1497,7 @@ bool finish_pass(pcv_searcher* s) {
     s->stats.bytes_algorithmic += rows * (int64_t)s->D * 4;
     s->stats.bytes_streamed += s->pending.stream_bytes;
     s->stats.screening_copy = s->pending.src;
+    s->stats.screen_bits = s->pending.src == 2 ? (s->pending.six ? 6 : 8) : 0;
 
     const uint32_t* cnt = s->pin->cnt;
     uint32_t mx = 0;
@@ -1372,6 +1515,7 @@ bool finish_pass(pcv_searcher* s) {
     for (int b = 0; b < B; ++b) {
         coarse += s->pin->coarse[b];
         s->stats.mid_survivors += s->pin->coarse[kMfmaQueries + b];
+        if (s->pending.six) s->stats.narrow_survivors += s->pin->coarse[2 * kMfmaQueries + b];
     }
     s->stats.coarse_survivors += coarse;
     s->stats.mid_copy = s->pending.mid ? 1 : 0;
@@ -1381,7 +1525,7 @@ bool finish_pass(pcv_searcher* s) {
     // measured gain of the copy: 12.5M x 384 3.5 %, 50M x 768 3.8 %, nothing at 100M x 384 where the share is 1.2 %)
     const int64_t fine_bytes = coarse * (int64_t)s->Dp * 32;
     if (s->pending.src == 2 && !s->pending.mid &&
-        (coarse > kMidTrigger * (int64_t)B || fine_bytes * kMidShare > (int64_t)s->pending.stream_bytes))
+        (coarse > kMidTrigger * (int64_t)B || fine_bytes * kMidShare > (int64_t)s->pending.int8_bytes))
         s->mid_hot_passes += 1;
     else
         s->mid_hot_passes = 0;
@@ -1741,6 +1885,7 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
         }
         // 4. the copies, from the view's own blocks, as a finalize of these rows makes them
         for (auto& src : v->sources) build_screening_copies(v, src);
+        build_six_copies(v);
         if (v->mid_copy == PCV_MID_COPY_ON && rows) build_mid_copies(v, true);
         v->copies_kind = v->sources.empty() ? 0 : copy_kind_wanted(v);
         for (const auto& src : v->sources)
@@ -2031,7 +2176,7 @@ pcv_status pcv_searcher_clear_source(pcv_searcher* s, int64_t source_id) {
         PCV_HIP(hipSetDevice(s->ctx->device));
         PCV_HIP(hipStreamSynchronize(s->ctx->stream));
         settle_mid_build(s, true);
-        if (!src->segs.empty()) s->screen_copy_gave_way = s->mid_gave_way = false;  // rows are given back: AUTO may try its copies again
+        if (!src->segs.empty()) s->screen_copy_gave_way = s->mid_gave_way = s->six_gave_way = false;  // rows are given back: AUTO may try its copies again
         for (auto& g : src->segs) free_segment(g);
         src->segs.clear();
         src->next_implicit_id = 0;
@@ -2067,7 +2212,7 @@ pcv_status pcv_searcher_replace_source(pcv_searcher* s, int64_t from_source_id, 
             // (alloc_segment: the rows come first), the old rows going now is the room to have them again: the next finalize
             // tries — once; another failure gives them up again.  (Without this every later search of a searcher that once
             // rebuilt a large source on a nearly full device streamed the f32 rows, 4x the bytes, silently.)
-            if (!to->segs.empty()) s->screen_copy_gave_way = s->mid_gave_way = false;
+            if (!to->segs.empty()) s->screen_copy_gave_way = s->mid_gave_way = s->six_gave_way = false;
             for (auto& g : to->segs) free_segment(g);
             to->segs = std::move(fresh);
             to->next_implicit_id = next_id;
@@ -2322,8 +2467,14 @@ pcv_status pcv_searcher_set_screening_copy(pcv_searcher* s, int mode) {
             drop_screening_copies(s);
             s->gen += 1;  // (a view keeps the copies its parent keeps)
         }
+        if (mode != PCV_SCREEN_COPY_AUTO && have_six_copies(s)) {  // (the 6-bit copies are AUTO's alone)
+            PCV_HIP(hipStreamSynchronize(s->ctx->stream));
+            drop_six_copies(s);
+            s->gen += 1;
+        }
         s->screen_copy = mode;
         s->screen_copy_gave_way = false;
+        s->six_gave_way = false;
     });
 }
 
@@ -2384,7 +2535,7 @@ pcv_status pcv_searcher_set_tuning(pcv_searcher* s, uint32_t flags) {
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->pending.active, "set_tuning: a queued pass has not been collected");
         s->fail_copy_alloc = (flags & (uint32_t)PCV_TUNE_FAIL_COPY_ALLOC) != 0;
-        s->scan_flags = flags & 0x3fffffffu;
+        s->scan_flags = flags & ~(uint32_t)PCV_TUNE_FAIL_COPY_ALLOC;
     });
 }
 
@@ -2719,8 +2870,10 @@ static pcv_status search_sharded_impl(pcv_searcher* s, pcv_comm* c, const float*
             total.bytes_streamed += s->stats.bytes_streamed;
             total.coarse_survivors += s->stats.coarse_survivors;
             total.mid_survivors += s->stats.mid_survivors;
+            total.narrow_survivors += s->stats.narrow_survivors;
             total.mid_copy = s->stats.mid_copy;
             total.screening_copy = s->stats.screening_copy;
+            total.screen_bits = s->stats.screen_bits;
         };
         for (int q0 = 0; q0 < n_queries; q0 += qstep) {
             const int B = std::min(qstep, n_queries - q0);

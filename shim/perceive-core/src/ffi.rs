@@ -59,6 +59,8 @@ pub struct pcv_scan_stats {
     pub mid_copy: i32,
     pub coarse_survivors: i64,
     pub mid_survivors: i64,
+    pub narrow_survivors: i64,
+    pub screen_bits: i32,
 }
 
 #[repr(C)]
