@@ -251,6 +251,14 @@ public:
         for (int64_t id : ids) hidden.erase(id);
         return rows;
     }
+    // removed items (pcv_searcher_remove_ids): rows carrying one of `ids` leave the searcher, in every source; the rows behind
+    // them move down on the device (no rebuild, no upload; positions shift; the ids are not remembered).  Returns the rows
+    // removed.  A SearcherView has no such call: a view is read-only.
+    int64_t remove_items(const std::vector<int64_t>& ids) {
+        int64_t rows = 0;
+        check(pcv_searcher_remove_ids(h_, ids.data(), (int64_t)ids.size(), &rows));
+        return rows;
+    }
     // updated items (pcv_searcher_update_rows): rows carrying ids[i] take the vector rows[i*dim .. (i+1)*dim) in place (no
     // rebuild).  `found` (if given) gets, per id, whether some row carries it.  Returns the rows rewritten.
     int64_t update_items(const std::vector<int64_t>& ids, const std::vector<float>& rows, std::vector<bool>* found = nullptr) {

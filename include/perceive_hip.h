@@ -209,6 +209,36 @@ pcv_status pcv_searcher_update_rows(pcv_searcher* s, const int64_t* ids, const f
 pcv_status pcv_searcher_update_blobs(pcv_searcher* s, const int64_t* ids, const uint8_t* blobs, int64_t n, uint8_t* out_found,
                                      int64_t* out_rows);
 
+/* Removed items (the reference drops items by rebuilding a source from SQLite, Searcher::rebuild_source, search.rs:58-79): every
+ * row whose id is in ids[0..n) leaves the searcher, in every source (rows staged under PCV_STAGING_SOURCE too), explicit-id and
+ * implicit-id segments alike.  No rebuild and no upload: the rows behind a removed row move down inside their segment, on the
+ * device; source order and row order inside a source are kept.
+ *   - exact: afterwards every search entry point returns bit for bit what a searcher built fresh from the remaining rows returns
+ *     (ids, scores, counts, order) — the remaining rows added in the same source order and row order, with the same hidden set —,
+ *     for every kernel, screening copy (off, bf16, int8, its 6-bit form), mid copy mode, metric, num_results (beyond 128 too)
+ *     and source filter;
+ *   - positions shift: pcv_searcher_num_rows, _source_num_rows and _get_rows count and read the remaining rows at their new
+ *     global positions.  A sharded host must call pcv_searcher_set_shard_offset again on the ranks behind a rank that shrank;
+ *   - not remembered: unlike the hidden set, removed ids are forgotten — a later pcv_searcher_add_rows with the same id is a new
+ *     item.  The hidden set itself is left as it is (it persists independently of the rows);
+ *   - the ids of the remaining rows never change: an implicit-id segment (ids == NULL, synthetic rows: id0 + row) that loses a
+ *     row gets an id column on the device first (8 bytes per row, as an explicit-id segment carries);
+ *   - a segment that loses all its rows is freed; a source that loses all its rows stays known with 0 rows, as after
+ *     pcv_searcher_clear_source.  The tail room of a segment that shrank stays with it: the next add_rows to that source appends
+ *     into it;
+ *   - out_rows (may be NULL): the rows removed.  Duplicate ids and ids that match no row are allowed, as in hide_ids; n == 0
+ *     does nothing.  NULL s, NULL ids with n > 0, n < 0, a view as s, pending rows (no finalize) or a queued pass give
+ *     PCV_ERR_INVALID with nothing changed;
+ *   - every row is found and every device buffer is allocated before the first row moves (a failed allocation: PCV_ERR_DEVICE,
+ *     nothing changed).  The extra device memory of the call — one byte per row of flags, a bounce buffer of at most 2^18 rows,
+ *     the id table — is given back at the end; an id column a segment got stays.  Never a second copy of a segment;
+ *   - a mid copy that AUTO is building beside the searches is waited for first; a captured pass is dropped, so no replay runs
+ *     over moved rows.  The narrow copies are packed again from the block of the first moved row of each segment on;
+ *   - the call counts as a result-changing call for views: a view copies its rows again at its next call, removed ids then match
+ *     nothing, and its hits carry the parent's new positions.
+ * The dot-metric bound max_norm does not shrink (as after update_rows): results do not depend on it. */
+pcv_status pcv_searcher_remove_ids(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows);
+
 /* Views (a search restricted to a set of items: the items of a tag, of an author, "search again within these results"): a
  * read-only searcher handle that holds a compact device copy of the rows of `parent` whose id is in ids[0..n).
  *   - exact: every search of the view returns bit for bit what a searcher built fresh from only those rows returns (ids, scores,
@@ -221,9 +251,9 @@ pcv_status pcv_searcher_update_blobs(pcv_searcher* s, const int64_t* ids, const 
  *     that names that source);
  *   - positions: a hit that carries one (pcv_hit.pos of _search_device, _begin / _end, the sharded exchange) carries the
  *     PARENT's position, shard offset included, so view lists of several ranks merge with pcv_merge_topk* like parent lists;
- *   - read-only: add / reserve / finalize / clear / replace / hide / unhide / update / set_shard_offset /
+ *   - read-only: add / reserve / finalize / clear / replace / hide / unhide / update / remove / set_shard_offset /
  *     set_screening_copy / set_mid_copy and get_rows give PCV_ERR_INVALID on a view;
- *   - never stale: every parent call that may change a result (finalize, hide / unhide, update, clear / replace source,
+ *   - never stale: every parent call that may change a result (finalize, hide / unhide, update, remove, clear / replace source,
  *     set_screening_copy OFF, set_shard_offset) makes the view copy the rows again, from its stored id list and under the
  *     parent's lock, at the start of its next call.  Rows added to the parent later with an allowed id join the view after the
  *     parent's finalize (a view call fails with PCV_ERR_INVALID while the parent has cleared rows without a finalize).  A

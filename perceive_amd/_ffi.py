@@ -122,6 +122,7 @@ SYMBOLS = {
     "pcv_searcher_source_num_rows": (C.c_int, [_P, C.c_int64, _I64P]),
     "pcv_searcher_get_rows": (C.c_int, [_P, _I64P, C.c_int64, _F32P, _I64P]),
     "pcv_searcher_hide_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
+    "pcv_searcher_remove_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
     "pcv_searcher_unhide_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
     "pcv_searcher_hidden_ids": (C.c_int, [_P, _I64P, C.c_int64, _I64P, _I64P]),
     "pcv_searcher_update_rows": (C.c_int, [_P, _I64P, _F32P, C.c_int64, _U8P, _I64P]),

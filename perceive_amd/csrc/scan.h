@@ -261,15 +261,27 @@ void launch_update_rows(hipStream_t st, const float* stage, uint32_t slot0, cons
 // Selection of the rows of a segment whose id is in the table, in row order: scratch flags4[view_tiles(nrows) * 256] and
 // tile_cnt[view_tiles(nrows)]; launch_view_select leaves the tiles' offsets in tile_cnt and the number of rows in *total, then
 // launch_view_compact writes the rows, ascending, to sel[0..*total).
+// `invert`: the rows whose id is NOT in the table are selected (pcv_searcher_remove_ids: the rows that stay).  `off0`: flags4 and
+// tile_off point at a later tile of the segment; rows are then numbered from that tile's first row and written from
+// sel[tile_off[tile] - off0] on.
+constexpr int kViewTile = 1024;  // rows per tile
 uint32_t view_tiles(uint32_t nrows);
 void launch_view_select(hipStream_t st, const int64_t* ids, uint32_t nrows, const int64_t* table, uint32_t tmask, bool has_empty,
-                        uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total);
-void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel);
+                        uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total, bool invert = false);
+void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel,
+                         uint32_t off0 = 0);
 // rows [dst_row0, dst_row0 + n_sel) of a view segment take rows sel[0..n_sel) of a parent segment (pieces, scale, id; parent
-// position pos0 + row -> dst_ppos[row of the view segment]); rows [dst_row0 + n_sel, dst_end) become padding
+// position pos0 + row -> dst_ppos[row of the view segment], unless dst_ppos is nullptr); rows [dst_row0 + n_sel, dst_end) become
+// padding
 void launch_view_gather(hipStream_t st, const float4* src_blk, const float* src_scale, const int64_t* src_ids, int64_t src_id0,
                         int64_t src_pos0, const uint32_t* sel, uint32_t n_sel, int D4, uint32_t dst_row0, uint32_t dst_end,
                         float4* dst_blk, float* dst_scale, int64_t* dst_ids, int64_t* dst_ppos);
+// ---- removed items (pcv_searcher_remove_ids) ----
+// rows [dst_row0, dst_end) of a segment take the rows at the same place inside their blocks of a bounce buffer whose block 0
+// stands for block dst_row0 / 32 (pieces, scale, id): the second launch of a compaction chunk, after launch_view_gather filled
+// the bounce buffer with dst_row0 % 32 as its first row
+void launch_compact_store(hipStream_t st, const float4* bounce_blk, const float* bounce_scale, const int64_t* bounce_ids, int D4,
+                          uint32_t dst_row0, uint32_t dst_end, float4* dst_blk, float* dst_scale, int64_t* dst_ids);
 // hits[0..n): pos in [0, nrows) -> ppos[pos]
 void launch_view_remap(hipStream_t st, pcv_hit_dev* hits, int64_t n, const int64_t* ppos, int64_t nrows);
 void launch_synth_fill(hipStream_t st, float4* blk, uint32_t nrows, uint32_t row0, int D, int D4, uint64_t seed,

@@ -889,7 +889,7 @@ __global__ __launch_bounds__(256) void update_rows_kernel(const float* __restric
 // kViewTile rows (view_mark_kernel), an exclusive scan of the tile counts (view_scan_kernel), then each tile writes its rows at
 // its offset (view_compact_kernel).  None of the kernels above is involved.
 // ------------------------------------------------------------------------------------------------
-constexpr int kViewTile = 1024;  // rows per tile: 4 consecutive rows per thread of a 256-thread workgroup
+// (kViewTile, scan.h: rows per tile — 4 consecutive rows per thread of a 256-thread workgroup)
 
 // Exclusive prefix of one value per thread over a 256-thread workgroup; *total = the sum.  `part`: 4 words of LDS.
 __device__ __forceinline__ uint32_t view_block_scan(uint32_t v, uint32_t* part, uint32_t& total) {
@@ -915,9 +915,10 @@ __device__ __forceinline__ uint32_t view_block_scan(uint32_t v, uint32_t* part, 
 }
 
 // Rows of a segment whose id is in the batch's hash table (scan.h: id_hash): flags4[tile * 256 + t] holds the flags of rows
-// tile * kViewTile + 4t .. 4t + 3 in bits 0, 8, 16, 24; tile_cnt[tile] = how many rows of the tile are flagged.
+// tile * kViewTile + 4t .. 4t + 3 in bits 0, 8, 16, 24; tile_cnt[tile] = how many rows of the tile are flagged.  `invert`: the
+// rows whose id is NOT in the table are flagged (pcv_searcher_remove_ids: flag = the row stays); rows >= nrows are never flagged.
 __global__ __launch_bounds__(256) void view_mark_kernel(const int64_t* __restrict__ ids, uint32_t nrows, const int64_t* __restrict__ table,
-                                                        uint32_t tmask, int has_empty, uint32_t* __restrict__ flags4,
+                                                        uint32_t tmask, int has_empty, int invert, uint32_t* __restrict__ flags4,
                                                         uint32_t* __restrict__ tile_cnt) {
     __shared__ uint32_t part[4];
     const uint64_t r0 = (uint64_t)blockIdx.x * kViewTile + threadIdx.x * 4u;
@@ -940,7 +941,7 @@ __global__ __launch_bounds__(256) void view_mark_kernel(const int64_t* __restric
                 if (t == kIdEmpty) break;
             }
         }
-        if (hit) f |= 1u << (8 * j);
+        if (hit != (invert != 0)) f |= 1u << (8 * j);
     }
     flags4[(size_t)blockIdx.x * 256 + threadIdx.x] = f;
     uint32_t total = 0;
@@ -966,13 +967,14 @@ __global__ __launch_bounds__(256) void view_scan_kernel(uint32_t* __restrict__ t
     if (threadIdx.x == 0) *total = sum;
 }
 
-// The flagged rows, ascending: tile `blockIdx.x` writes its rows from sel[tile_off[tile]] on.
+// The flagged rows, ascending: tile `blockIdx.x` writes its rows from sel[tile_off[tile] - off0] on (off0 != 0: flags4 / tile_off
+// point at a later tile of the segment, and the rows are numbered from that tile's first row — a chunk of remove_ids).
 __global__ __launch_bounds__(256) void view_compact_kernel(const uint32_t* __restrict__ flags4, const uint32_t* __restrict__ tile_off,
-                                                           uint32_t* __restrict__ sel) {
+                                                           uint32_t off0, uint32_t* __restrict__ sel) {
     __shared__ uint32_t part[4];
     const uint32_t f = flags4[(size_t)blockIdx.x * 256 + threadIdx.x];
     uint32_t total = 0;
-    uint32_t at = tile_off[blockIdx.x] + view_block_scan((uint32_t)__popc(f), part, total);
+    uint32_t at = tile_off[blockIdx.x] - off0 + view_block_scan((uint32_t)__popc(f), part, total);
     const uint32_t r0 = blockIdx.x * (uint32_t)kViewTile + threadIdx.x * 4u;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -1005,13 +1007,44 @@ __global__ __launch_bounds__(256) void view_gather_kernel(const float4* __restri
             if (f4 == 0) {
                 dst_scale[c] = src_scale[row];
                 dst_ids[c] = src_ids ? src_ids[row] : src_id0 + row;
-                dst_ppos[c] = src_pos0 + row;
+                if (dst_ppos) dst_ppos[c] = src_pos0 + row;
             }
         } else if (f4 == 0) {
             dst_scale[c] = 0.0f;
             dst_ids[c] = -1;
         }
         dst_blk[(b * D4 + f4) * 32 + r] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// removed items (pcv_searcher_remove_ids, DESIGN.md §3 "Removed items"): a segment is compacted in place, chunk by chunk.  The
+// rows of a chunk that stay are marked and listed by the view kernels above (flag = the row stays) and gathered by
+// view_gather_kernel into a bounce buffer that already has the blocked layout of their destination; this kernel then writes the
+// bounce buffer to the destination.  Two launches in stream order, so no row is overwritten before it has been read.
+// ------------------------------------------------------------------------------------------------
+
+// Rows [dst_row0, dst_end) of a segment take the rows of the bounce buffer at the same place inside their blocks: block 0 of the
+// bounce buffer stands for block dst_row0 / 32 of the segment.  Pieces, scale and id, bit for bit.  One thread per 16-byte piece,
+// lanes 0..31 the rows of a block and the two halves of a wave neighbouring pieces: a wave reads and writes 1 KB contiguously.
+// Rows of the first and last block outside [dst_row0, dst_end) are left alone.
+__global__ __launch_bounds__(256) void compact_store_kernel(const float4* __restrict__ bounce_blk, const float* __restrict__ bounce_scale,
+                                                            const int64_t* __restrict__ bounce_ids, int D4, uint32_t dst_row0,
+                                                            uint32_t dst_end, float4* __restrict__ dst_blk, float* __restrict__ dst_scale,
+                                                            int64_t* __restrict__ dst_ids, int64_t threads) {
+    const uint64_t first_blk = dst_row0 >> 5;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < threads; t += (int64_t)gridDim.x * 256) {
+        const uint32_t r = (uint32_t)(t & 31);
+        const int64_t u = t >> 5;
+        const int f4 = (int)(u % D4);
+        const uint64_t lb = (uint64_t)(u / D4);
+        const uint64_t c = (first_blk + lb) * 32 + r;
+        if (c < dst_row0 || c >= dst_end) continue;
+        dst_blk[((first_blk + lb) * D4 + f4) * 32 + r] = bounce_blk[(lb * D4 + f4) * 32 + r];
+        if (f4 == 0) {
+            dst_scale[c] = bounce_scale[lb * 32 + r];
+            dst_ids[c] = bounce_ids[lb * 32 + r];
+        }
     }
 }
 
@@ -3810,22 +3843,22 @@ void launch_update_rows(hipStream_t st, const float* stage, uint32_t slot0, cons
 uint32_t view_tiles(uint32_t nrows) { return (nrows + kViewTile - 1) / kViewTile; }
 
 void launch_view_select(hipStream_t st, const int64_t* ids, uint32_t nrows, const int64_t* table, uint32_t tmask, bool has_empty,
-                        uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total) {
+                        uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total, bool invert) {
     const uint32_t nt = view_tiles(nrows);
     if (nt == 0) {
         PCV_HIP(hipMemsetAsync(total, 0, sizeof(uint32_t), st));
         return;
     }
-    view_mark_kernel<<<nt, 256, 0, st>>>(ids, nrows, table, tmask, has_empty ? 1 : 0, flags4, tile_cnt);
+    view_mark_kernel<<<nt, 256, 0, st>>>(ids, nrows, table, tmask, has_empty ? 1 : 0, invert ? 1 : 0, flags4, tile_cnt);
     PCV_LAUNCHED();
     view_scan_kernel<<<1, 256, 0, st>>>(tile_cnt, nt, total);
     PCV_LAUNCHED();
 }
 
-void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel) {
+void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel, uint32_t off0) {
     const uint32_t nt = view_tiles(nrows);
     if (nt == 0) return;
-    view_compact_kernel<<<nt, 256, 0, st>>>(flags4, tile_off, sel);
+    view_compact_kernel<<<nt, 256, 0, st>>>(flags4, tile_off, off0, sel);
     PCV_LAUNCHED();
 }
 
@@ -3838,6 +3871,17 @@ void launch_view_gather(hipStream_t st, const float4* src_blk, const float* src_
     const unsigned grid = (unsigned)std::min<int64_t>((threads + 255) / 256, (int64_t)current_device_cus() * 64);
     view_gather_kernel<<<grid, 256, 0, st>>>(src_blk, src_scale, src_ids, src_id0, src_pos0, sel, n_sel, D4, dst_row0, dst_end, dst_blk,
                                              dst_scale, dst_ids, dst_ppos, threads);
+    PCV_LAUNCHED();
+}
+
+void launch_compact_store(hipStream_t st, const float4* bounce_blk, const float* bounce_scale, const int64_t* bounce_ids, int D4,
+                          uint32_t dst_row0, uint32_t dst_end, float4* dst_blk, float* dst_scale, int64_t* dst_ids) {
+    if (dst_end <= dst_row0) return;
+    const uint64_t first_blk = dst_row0 >> 5, last_blk = ((uint64_t)dst_end - 1) >> 5;
+    const int64_t threads = (int64_t)(last_blk - first_blk + 1) * D4 * 32;
+    const unsigned grid = (unsigned)std::min<int64_t>((threads + 255) / 256, (int64_t)current_device_cus() * 64);
+    compact_store_kernel<<<grid, 256, 0, st>>>(bounce_blk, bounce_scale, bounce_ids, D4, dst_row0, dst_end, dst_blk, dst_scale, dst_ids,
+                                               threads);
     PCV_LAUNCHED();
 }
 

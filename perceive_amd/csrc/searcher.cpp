@@ -1086,6 +1086,218 @@ int64_t update_by_id(pcv_searcher* s, const int64_t* ids, const void* rows, int6
     return (int64_t)total;
 }
 
+// ---- removed items (pcv_searcher_remove_ids; DESIGN.md §3 "Removed items") ----
+// One segment that loses rows: the flags of its rows (1 = the row stays, view_mark_kernel's layout) and the tiles' offsets on the
+// device, the offsets on the host as well (off[t] = rows that stay in front of tile t; off[tiles] = keep).
+struct RemoveSeg {
+    Source* src = nullptr;
+    Segment* g = nullptr;
+    DevBuf<uint32_t> flags4, tiles;
+    std::vector<uint32_t> off;
+    int64_t* new_ids = nullptr;  // the id column an implicit-id segment gets (id0 + row), allocated and filled, not yet the segment's
+    uint32_t keep = 0;           // rows that stay
+    uint32_t first = 0;          // the first row that goes: the rows in front of it are not touched
+    uint32_t hidden_gone = 0;    // rows that go and whose id is in the hidden set
+};
+
+// rows per compaction chunk: the ingest staging's step (whole tiles).  PCV_REMOVE_CHUNK_ROWS (diagnostic, read at each call)
+// lowers it, so that small test corpora cross chunk boundaries.
+uint32_t remove_chunk_rows() {
+    int64_t rows = kStageRows;
+    if (const char* f = getenv("PCV_REMOVE_CHUNK_ROWS")) rows = std::min<int64_t>(kStageRows, std::max<int64_t>(1, strtoll(f, nullptr, 0)));
+    return (uint32_t)((rows + kViewTile - 1) / kViewTile * kViewTile);
+}
+
+// Every row, in every source, whose id is in `batch` (ascending, distinct, not empty) leaves the searcher; the rows behind it
+// move down inside their segment.  Returns the rows removed.  Every row is found and every buffer allocated before the first
+// row moves; the scratch (flags, offsets, id table, bounce buffer) is given back at the end, whatever happens.
+int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
+    hipStream_t st = s->ctx->stream;
+    const int D4 = s->D4;
+    std::vector<std::unique_ptr<RemoveSeg>> plan;
+    DevBuf<uint32_t> total, sel;
+    DevBuf<float4> b_blk;
+    DevBuf<float> b_scale;
+    DevBuf<int64_t> b_ids;
+    auto release_scratch = [&] {
+        for (auto& r : plan) {
+            r->flags4.release();
+            r->tiles.release();
+            if (r->new_ids) (void)hipFree(r->new_ids);
+            r->new_ids = nullptr;
+        }
+        total.release();
+        sel.release();
+        b_blk.release();
+        b_scale.release();
+        b_ids.release();
+        s->d_idtab.release();
+        s->d_hrows.release();
+        s->d_hcnt.release();
+    };
+    int64_t removed = 0;
+    try {
+        // 0. the rows that go AND are hidden, per segment (Segment::hidden_rows counts them): the ids of the batch that are in the set
+        std::vector<int64_t> both;
+        std::set_intersection(batch.begin(), batch.end(), s->hidden.begin(), s->hidden.end(), std::back_inserter(both));
+        std::vector<std::pair<Segment*, uint32_t>> hidden_gone;
+        if (!both.empty()) {
+            IdBatch hb;
+            hb.ids = &both;
+            for (auto& src : s->sources)
+                for (auto& g : src.segs)
+                    if (const uint32_t n = find_rows(s, g, 0, g.nrows, hb)) hidden_gone.push_back({&g, n});
+        }
+        // 1. which rows stay: flags and tile offsets per segment (view_mark_kernel with the sense inverted, view_scan_kernel);
+        //    an implicit-id segment (id0 + row) is intersected on the host and, if it loses a row, gets its id column first
+        IdBatch b;
+        b.ids = &batch;
+        uint32_t longest = 0;  // the most rows any segment has behind the tile of its first removed row
+        total.ensure(1);
+        for (auto& src : s->sources)
+            for (auto& g : src.segs) {
+                if (g.nrows == 0) continue;
+                auto r = std::make_unique<RemoveSeg>();
+                r->src = &src;
+                r->g = &g;
+                const int64_t* ids = g.ids;
+                if (!g.ids) {
+                    const auto lo = std::lower_bound(batch.begin(), batch.end(), g.id0);
+                    const auto hi = std::lower_bound(lo, batch.end(), g.id0 + (int64_t)g.nrows);
+                    if (lo == hi) continue;
+                    if ((uint32_t)(hi - lo) == g.nrows) {  // every row goes: no id column needed
+                        r->keep = 0;
+                        plan.push_back(std::move(r));
+                        continue;
+                    }
+                    PCV_HIP(hipMalloc((void**)&r->new_ids, (size_t)g.cap_rows * sizeof(int64_t)));
+                    PCV_HIP(hipMemsetAsync(r->new_ids, 0xff, (size_t)g.cap_rows * sizeof(int64_t), st));
+                    launch_iota_ids(st, r->new_ids, g.id0, g.nrows);
+                    ids = r->new_ids;
+                }
+                Segment* gp = &g;
+                plan.push_back(std::move(r));  // (from here on release_scratch frees what this segment holds)
+                RemoveSeg& rs = *plan.back();
+                upload_id_batch(s, b);
+                const uint32_t nt = view_tiles(gp->nrows);
+                rs.flags4.ensure((size_t)nt * 256);
+                rs.tiles.ensure(nt);
+                launch_view_select(st, ids, gp->nrows, s->d_idtab.p, b.tmask, b.has_empty, rs.flags4.p, rs.tiles.p, total.p, true);
+                rs.off.resize((size_t)nt + 1);
+                PCV_HIP(hipMemcpyAsync(&rs.keep, total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                PCV_HIP(hipMemcpyAsync(rs.off.data(), rs.tiles.p, (size_t)nt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                PCV_HIP(hipStreamSynchronize(st));
+                rs.off[nt] = rs.keep;
+                if (rs.keep == gp->nrows) {  // nothing of this segment goes
+                    rs.flags4.release();
+                    rs.tiles.release();
+                    if (rs.new_ids) (void)hipFree(rs.new_ids);
+                    plan.pop_back();
+                    continue;
+                }
+                if (rs.keep == 0) continue;
+                // the first row that goes: the first tile that is not full, then the first clear flag in it
+                uint32_t t0 = 0;
+                while (rs.off[t0 + 1] - rs.off[t0] == (uint32_t)kViewTile) ++t0;
+                std::vector<uint32_t> f(256);
+                PCV_HIP(hipMemcpyAsync(f.data(), rs.flags4.p + (size_t)t0 * 256, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                PCV_HIP(hipStreamSynchronize(st));
+                uint32_t i = 0;
+                while (i < (uint32_t)kViewTile && ((f[i >> 2] >> (8 * (i & 3))) & 1u)) ++i;
+                rs.first = t0 * (uint32_t)kViewTile + i;
+                longest = std::max(longest, gp->nrows - t0 * (uint32_t)kViewTile);
+            }
+        if (plan.empty()) {
+            release_scratch();
+            return 0;
+        }
+        // 2. every buffer the moves need: one chunk's row list and its bounce buffer (blocked like the destination, which may begin
+        //    inside a block: one block more)
+        const uint32_t chunk = std::min(remove_chunk_rows(), (longest + (uint32_t)kViewTile - 1) / (uint32_t)kViewTile * (uint32_t)kViewTile);
+        if (chunk) {
+            const size_t bb = (size_t)chunk / kBlockRows + 1;
+            sel.ensure(chunk);
+            b_blk.ensure(bb * D4 * 32);
+            b_scale.ensure(bb * 32);
+            b_ids.ensure(bb * 32);
+        }
+        // 3. the moves, segment by segment and chunk by chunk, ascending.  Chunk [s0, s1) of the old rows holds n rows that stay; they
+        //    go to [d0, d0 + n), d0 = rows that stay in front of s0 <= s0 and d0 + n <= s1: the gather reads only [s0, s1), the
+        //    store writes only in front of s1 and behind what the chunk before wrote, every later chunk reads from s1 on.
+        for (auto& rp : plan) {
+            RemoveSeg& r = *rp;
+            Segment& g = *r.g;
+            removed += g.nrows - r.keep;
+            if (r.keep == 0) continue;
+            int64_t* ids = r.new_ids ? r.new_ids : g.ids;
+            for (uint32_t s0 = r.first / (uint32_t)kViewTile * (uint32_t)kViewTile; s0 < g.nrows; s0 += chunk) {
+                const uint32_t s1 = (uint32_t)std::min<uint64_t>((uint64_t)s0 + chunk, g.nrows);
+                const uint32_t tile0 = s0 / (uint32_t)kViewTile, tile1 = view_tiles(s1);
+                const uint32_t d0 = r.off[tile0], n = r.off[tile1] - d0;
+                const uint32_t skip = s0 < r.first ? r.first - s0 : 0;  // (the first chunk: rows in front of the first removed one stay put)
+                if (n <= skip) continue;
+                const uint32_t dst0 = d0 + skip, m = n - skip;
+                launch_view_compact(st, r.flags4.p + (size_t)tile0 * 256, r.tiles.p + tile0, s1 - s0, sel.p, d0);
+                launch_view_gather(st, g.blk + (size_t)(s0 / kBlockRows) * D4 * 32, g.scale + s0, ids + s0, 0, 0, sel.p + skip, m, D4,
+                                   dst0 % kBlockRows, dst0 % kBlockRows + m, b_blk.p, b_scale.p, b_ids.p, nullptr);
+                launch_compact_store(st, b_blk.p, b_scale.p, b_ids.p, D4, dst0, dst0 + m, g.blk, g.scale, ids);
+            }
+            // the tail: padding up to the end of the last block a fresh build would have written; no scale behind it
+            const uint32_t end_new = (r.keep + kBlockRows - 1) / kBlockRows * kBlockRows, end_old = g.nblocks() * kBlockRows;
+            launch_view_gather(st, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, D4, r.keep, end_new, g.blk, g.scale, ids, nullptr);
+            if (end_old > end_new) PCV_HIP(hipMemsetAsync(g.scale + end_new, 0, (size_t)(end_old - end_new) * sizeof(float), st));
+        }
+        PCV_HIP(hipStreamSynchronize(st));
+        // 4. the segments' books; the narrow copies start again at the block of the first moved row
+        std::vector<Source*> touched;
+        for (auto& rp : plan) {
+            RemoveSeg& r = *rp;
+            Segment& g = *r.g;
+            for (const auto& h : hidden_gone)
+                if (h.first == &g) g.hidden_rows -= std::min(g.hidden_rows, h.second);
+            if (std::find(touched.begin(), touched.end(), r.src) == touched.end()) touched.push_back(r.src);
+            if (r.keep == 0) {
+                free_segment(g);  // (nrows 0: erased below)
+                continue;
+            }
+            if (r.new_ids) {
+                g.ids = r.new_ids;
+                r.new_ids = nullptr;
+            }
+            const uint32_t from = r.first / kBlockRows * kBlockRows;
+            g.nrows = g.scaled_rows = r.keep;
+            g.copied_rows = std::min(g.copied_rows, from);
+            g.six_rows = std::min(g.six_rows, from);
+            g.mid_rows = std::min(g.mid_rows, from);
+        }
+        for (Source* src : touched) {
+            src->segs.erase(std::remove_if(src->segs.begin(), src->segs.end(), [](const Segment& x) { return x.blk == nullptr; }), src->segs.end());
+            build_screening_copies(s, *src);
+            for (auto& g : src->segs) {
+                if (g.nrows == 0) continue;
+                if (g.blk6 && g.blk8 && g.six_rows < g.copied_rows) {
+                    launch_pack6(st, g.blk, g.scale, g.blk8, g.scale8, g.blk6, g.scale6, g.six_rows / kBlockRows, (g.copied_rows + kBlockRows - 1) / kBlockRows, D4);
+                    g.six_rows = g.copied_rows;
+                }
+                if (g.mid16 && g.mid_rows < g.scaled_rows) {
+                    launch_mid_pack(st, g.blk, g.scale, (g.blk8 && g.copied_rows >= g.scaled_rows) ? g.scale8 : nullptr, g.mid16, g.scale16, g.mid_rows,
+                                    g.scaled_rows, D4);
+                    g.mid_rows = g.scaled_rows;
+                }
+            }
+        }
+        assign_positions(s);
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+    } catch (...) {
+        (void)hipStreamSynchronize(st);
+        release_scratch();
+        throw;
+    }
+    release_scratch();
+    return removed;
+}
+
 void do_finalize(pcv_searcher* s) {
     settle_mid_build(s, true);
     hipStream_t st = s->ctx->stream;
@@ -2275,6 +2487,44 @@ pcv_status pcv_searcher_hide_ids(pcv_searcher* s, const int64_t* ids, int64_t n,
 
 pcv_status pcv_searcher_unhide_ids(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows) {
     return hide_or_unhide(s, ids, n, out_rows, false);
+}
+
+pcv_status pcv_searcher_remove_ids(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_rows) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "remove_ids: searcher is NULL");
+        PCV_REQUIRE(n >= 0 && (ids != nullptr || n == 0), "remove_ids: bad id list (NULL with n > 0, or n < 0)");
+        refuse_view(s, "remove_ids");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->dirty, "remove_ids: pending rows; call pcv_searcher_finalize first");
+        PCV_REQUIRE(!s->pending.active, "remove_ids: a queued pass has not been collected");
+        if (out_rows) *out_rows = 0;
+        if (n == 0) return;
+        std::vector<int64_t> batch(ids, ids + n);
+        std::sort(batch.begin(), batch.end());
+        batch.erase(std::unique(batch.begin(), batch.end()), batch.end());
+        PCV_HIP(hipSetDevice(s->ctx->device));
+        PCV_HIP(hipStreamSynchronize(s->ctx->stream));
+        settle_mid_build(s, true);  // (the AUTO mid build reads the rows and scales and writes the mid copy)
+        // a graph captured over the rows as they lay must not replay over moved or freed rows: the next passes capture afresh
+        if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
+        s->graph_exec = nullptr;
+        s->graph_shape = s->last_shape = pcv_searcher::PassShape{};
+        s->shape_seen = 0;
+        const int64_t removed = remove_by_id(s, batch);
+        // what finalize derives from the segments
+        s->copies_kind = copy_kind_wanted(s);
+        bool any = false;
+        for (const auto& src : s->sources)
+            for (const auto& g : src.segs) {
+                if (g.nrows == 0) continue;
+                any = true;
+                if ((s->copies_kind == 1 ? g.blk16 == nullptr : g.blk8 == nullptr) || g.copied_rows < g.nrows) s->copies_kind = 0;
+                if (!g.mid16 || g.mid_rows < g.nrows) s->mids_present = false;
+            }
+        if (!any) s->copies_kind = 0;
+        s->gen += 1;  // (views copy their rows again at their next call)
+        if (out_rows) *out_rows = removed;
+    });
 }
 
 pcv_status pcv_searcher_hidden_ids(pcv_searcher* s, int64_t* out_ids, int64_t cap, int64_t* out_n, int64_t* out_hidden_rows) {

@@ -365,6 +365,14 @@ class Searcher:
         _ffi.check(fn(self._handle, _ffi.i64p(a) if a.size else None, a.size, C.byref(rows)))
         return rows.value
 
+    # ---- removed items (pcv_searcher_remove_ids) ----------------------------------------------------
+    # An item that is gone for good leaves the device: its rows are dropped and the rows behind them move down, without a rebuild
+    # or an upload; searches afterwards return what a searcher built fresh from the remaining rows returns.  Positions shift.
+    def remove_items(self, ids):
+        """Remove every row carrying one of `ids` (int64 1-D array or iterable; duplicates and unknown ids allowed), in every
+        source; returns the rows removed.  Needs a finalized searcher.  The ids are not remembered (unlike hide_items)."""
+        return self._hide_call(_ffi.lib().pcv_searcher_remove_ids, ids)
+
     # ---- updated items (pcv_searcher_update_rows) ---------------------------------------------------
     # A re-embedded item takes its new vector in place, in every row carrying its id, without a rebuild; searches afterwards return
     # what a searcher built fresh from the updated rows returns.

@@ -174,6 +174,7 @@ extern "C" {
     pub fn pcv_searcher_hidden_ids(s: *mut pcv_searcher, out_ids: *mut i64, cap: i64, out_n: *mut i64, out_hidden_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_update_rows(s: *mut pcv_searcher, ids: *const i64, rows: *const f32, n: i64, out_found: *mut u8, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_update_blobs(s: *mut pcv_searcher, ids: *const i64, blobs: *const u8, n: i64, out_found: *mut u8, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_remove_ids(s: *mut pcv_searcher, ids: *const i64, n: i64, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_create_view(parent: *mut pcv_searcher, ids: *const i64, n: i64, out_view: *mut *mut pcv_searcher) -> c_int;
     pub fn pcv_searcher_view_stats(view: *mut pcv_searcher, out_rows: *mut i64, out_ids: *mut i64, out_refreshes: *mut i32, out_build_ms: *mut f32) -> c_int;
     pub fn pcv_searcher_set_kernel(s: *mut pcv_searcher, kernel: c_int) -> c_int;

@@ -208,6 +208,22 @@ impl Searcher {
         Ok(())
     }
 
+    /// Remove every row carrying one of `ids`, in every source: the rows leave the device and the rows behind them move down
+    /// in place (no rebuild, no upload; searches afterwards return what an index built fresh from the remaining rows
+    /// returns).  Returns the rows removed.  The reference drops items by rebuilding: `Searcher::rebuild_source`
+    /// (search.rs:58-79) reads the whole source from SQLite again without the rows that are gone, and `perceive source`
+    /// (cmd/source.rs, `rebuild_search`) calls it after deleting items; that call becomes
+    ///     `searcher.remove_items(&deleted_ids)?;`
+    /// Unlike `hide_items` the ids are not remembered: an item added later with the same id is a new item.
+    pub fn remove_items(&mut self, ids: &[i64]) -> Result<usize, HipError> {
+        if self.handle.is_null() || ids.is_empty() {
+            return Ok(0);
+        }
+        let mut rows: i64 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_remove_ids(self.handle, ids.as_ptr(), ids.len() as i64, &mut rows) })?;
+        Ok(rows as usize)
+    }
+
     /// Upsert the embeddings a source scan produced (update_db.rs:54-60,75-126 writes them to `item_embeddings` with
     /// `ON CONFLICT ... DO UPDATE`): items the index holds take their new vector in place, in every row carrying their id
     /// (no rebuild; searches afterwards return what an index built fresh from the new rows returns); the others are added
