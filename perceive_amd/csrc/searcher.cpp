@@ -12,7 +12,6 @@
 #include <iterator>
 #include <memory>
 #include <atomic>
-#include <memory>
 #include <mutex>
 #include <numeric>
 #include <thread>
@@ -61,10 +60,17 @@ struct Source {
     }
 };
 
+// A device buffer and its owner: freed when it goes out of scope.  (Whoever frees one that a queued kernel may still read
+// synchronises the stream first.)
 template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    ~DevBuf() { release(); }
     void ensure(size_t want) {
         if (want <= n) return;
         if (p) PCV_HIP(hipFree(p));
@@ -78,7 +84,24 @@ struct DevBuf {
         p = nullptr;
         n = 0;
     }
+    T* hand_over() {  // the memory is the caller's from here on
+        T* q = p;
+        p = nullptr;
+        n = 0;
+        return q;
+    }
 };
+
+// Runs `f` when the scope ends, however it ends.
+template <class F>
+struct AtExit {
+    F f;
+    ~AtExit() { f(); }
+};
+template <class F>
+AtExit<F> at_exit(F f) {
+    return {std::move(f)};
+}
 
 constexpr int64_t kStageRows = 1 << 18;                  // rows per H2D staging step (384-d: 400 MB)
 constexpr int64_t kMaxSegRows = (int64_t)0xffffffc0u;    // a candidate names its row in 32 bits
@@ -283,18 +306,125 @@ struct pcv_searcher {
 
 namespace {
 
+// ---- the derived copies of a segment (scan.h) ----
+// The screening copy (bf16, or int8 + block scales: `copied_rows`), the 6-bit copy made from the int8 one (`six_rows`) and the mid
+// copy (`mid_rows`).  How they are freed, allocated, extended to the rows that have a scale and repaired after rows changed is
+// said here, once: a new copy format or a new row-changing call has these functions to add to, and a miss is a screen that is no
+// longer certified.
+enum : unsigned { kCopyScreen = 1, kCopySix = 2, kCopyMid = 4, kCopyAll = 7 };
+
+// (the caller has seen to it that no queued kernel reads them any more)
+void free_copies(Segment& g, unsigned which) {
+    if (which & kCopyScreen) {
+        if (g.blk16) (void)hipFree(g.blk16);
+        if (g.blk8) (void)hipFree(g.blk8);
+        if (g.scale8) (void)hipFree(g.scale8);
+        g.blk16 = g.blk8 = nullptr;
+        g.scale8 = nullptr;
+        g.copied_rows = 0;
+    }
+    if (which & kCopySix) {
+        if (g.blk6) (void)hipFree(g.blk6);
+        if (g.scale6) (void)hipFree(g.scale6);
+        g.blk6 = nullptr;
+        g.scale6 = nullptr;
+        g.six_rows = 0;
+    }
+    if (which & kCopyMid) {
+        if (g.mid16) (void)hipFree(g.mid16);
+        if (g.scale16) (void)hipFree(g.scale16);
+        g.mid16 = nullptr;
+        g.scale16 = nullptr;
+        g.mid_rows = 0;
+    }
+}
+
 void free_segment(Segment& g) {
     if (g.blk) (void)hipFree(g.blk);
     if (g.scale) (void)hipFree(g.scale);
     if (g.ids) (void)hipFree(g.ids);
-    if (g.blk16) (void)hipFree(g.blk16);
-    if (g.blk8) (void)hipFree(g.blk8);
-    if (g.scale8) (void)hipFree(g.scale8);
-    if (g.mid16) (void)hipFree(g.mid16);
-    if (g.scale16) (void)hipFree(g.scale16);
-    if (g.blk6) (void)hipFree(g.blk6);
-    if (g.scale6) (void)hipFree(g.scale6);
+    free_copies(g, kCopyAll);
     g = Segment();
+}
+
+// A copy's buffer and the buffer of its scales: both or neither (then both pointers are null and the error is returned).
+// `refuse`: PCV_TUNE_FAIL_COPY_ALLOC.  Reads nothing of the searcher: the helper thread of the AUTO mid build calls it too.
+template <class A, class B>
+hipError_t alloc_with_scales(bool refuse, A** buf, size_t bytes, B** scales, size_t scale_bytes) {
+    hipError_t e = refuse ? hipErrorOutOfMemory : hipMalloc((void**)buf, bytes);
+    if (e == hipSuccess) {
+        e = hipMalloc((void**)scales, scale_bytes);
+        if (e != hipSuccess) (void)hipFree(*buf);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        *scales = nullptr;
+    }
+    return e;
+}
+hipError_t alloc_mid(bool refuse, uint32_t cap_rows, int Dp, uint4** mid16, float** scale16) {
+    return alloc_with_scales(refuse, mid16, (size_t)cap_rows * Dp * 2, scale16, (size_t)cap_rows * sizeof(float));
+}
+
+// What the mid copy of g lacks: rows [first, end) have their scale and no copy.  `scale8`: they are quantised with the int8 copy's
+// block scales, which launch_mid_pack does only if that copy covers them all.
+struct MidSpan {
+    uint32_t first, end;
+    const float* scale8;
+};
+MidSpan mid_span(const Segment& g) {
+    return {g.mid16 ? g.mid_rows : 0u, g.scaled_rows, (g.blk8 && g.copied_rows >= g.scaled_rows) ? g.scale8 : nullptr};
+}
+// The copy that is there catches up with the rows that have their scale.
+void extend_mid(hipStream_t st, Segment& g, int D4) {
+    if (!g.mid16 || g.mid_rows >= g.scaled_rows) return;
+    const MidSpan m = mid_span(g);
+    launch_mid_pack(st, g.blk, g.scale, m.scale8, g.mid16, g.scale16, m.first, m.end, D4);
+    g.mid_rows = g.scaled_rows;
+}
+// ... and the 6-bit copy with the int8 copy it is derived from
+void extend_six(hipStream_t st, Segment& g, int D4) {
+    if (!g.blk6 || !g.blk8 || g.six_rows >= g.copied_rows) return;
+    // (from the block of the first row not covered: the int8 copy re-packed that partial block with a new scale)
+    launch_pack6(st, g.blk, g.scale, g.blk8, g.scale8, g.blk6, g.scale6, g.six_rows / kBlockRows, (g.copied_rows + kBlockRows - 1) / kBlockRows, D4);
+    g.six_rows = g.copied_rows;
+}
+
+// The int8 blocks (and what is made from them) that hold `rows`: ascending, distinct, inside the copy.
+std::vector<uint32_t> touched_blocks(const Segment& g, const std::vector<uint32_t>& rows) {
+    std::vector<uint32_t> blocks;
+    if (!g.blk8) return blocks;
+    for (uint32_t r : rows)
+        if (r < g.copied_rows) blocks.push_back(r / kBlockRows);
+    std::sort(blocks.begin(), blocks.end());
+    blocks.erase(std::unique(blocks.begin(), blocks.end()), blocks.end());
+    return blocks;
+}
+
+// The f32 rows d_rows[0..nr) and their scales changed (a row came back from hiding, or got a new vector): the copies follow.
+// bf16 pieces row by row; the WHOLE 32-row blocks d_blocks[0..nb) (touched_blocks) of the int8 copy — a finalize that appended
+// rows to such a block while a row was hidden quantised it without that row, and a new row may need a smaller block scale —,
+// the 6-bit copy from those int8 blocks, and a mid copy by blocks if it was quantised with the int8 block scales, by rows otherwise.
+void repair_copies(pcv_searcher* s, Segment& g, const uint32_t* d_rows, uint32_t nr, const uint32_t* d_blocks, uint32_t nb) {
+    hipStream_t st = s->ctx->stream;
+    if (g.blk16) launch_repack16_rows(st, g.blk, g.scale, d_rows, nr, g.blk16, s->D4);
+    if (g.blk8 && nb) launch_repack8_blocks(st, g.blk, g.scale, d_blocks, nb, g.blk8, g.scale8, s->D4);
+    if (g.blk6 && nb) launch_repack6_blocks(st, g.blk, g.scale, g.blk8, g.scale8, d_blocks, nb, g.blk6, g.scale6, s->D4);
+    if (g.mid16 && g.mid_rows > 0) {
+        if (g.blk8 && g.copied_rows >= g.nrows)  // the copy is quantised with the int8 copy's block scales (launch_mid_pack)
+            launch_repack_mid(st, g.blk, g.scale, g.scale8, d_blocks, nb, g.mid_rows, g.mid16, g.scale16, s->D4);
+        else
+            launch_repack_mid(st, g.blk, g.scale, nullptr, d_rows, nr, g.mid_rows, g.mid16, g.scale16, s->D4);
+    }
+}
+
+// every row of every segment is covered by a mid copy (mids_present)
+bool mids_cover(const pcv_searcher* s) {
+    for (const auto& src : s->sources)
+        for (const auto& g : src.segs)
+            if (g.nrows > 0 && (!g.mid16 || g.mid_rows < g.nrows)) return false;
+    return true;
 }
 
 constexpr int64_t kMidTrigger = 4096;  // coarse survivors per query and pass above which AUTO builds the mid copy ...
@@ -330,10 +460,7 @@ void settle_mid_build(pcv_searcher* s, bool wait) {
         it.g->mid_rows = it.rows;
     }
     s->mid_task.reset();
-    s->mids_present = true;
-    for (auto& src : s->sources)
-        for (auto& g : src.segs)
-            if (g.nrows > 0 && (!g.mid16 || g.mid_rows < g.nrows)) s->mids_present = false;
+    s->mids_present = mids_cover(s);
 }
 
 // Queue the build of the mid copies of every segment beside the searches (AUTO): a helper thread allocates and launches on
@@ -352,8 +479,8 @@ void start_mid_build(pcv_searcher* s) {
     for (auto& src : s->sources)
         for (auto& g : src.segs) {
             if (g.nrows == 0 || (g.mid16 && g.mid_rows >= g.scaled_rows)) continue;
-            t.items.push_back({&g, g.blk, g.scale, (g.blk8 && g.copied_rows >= g.scaled_rows) ? g.scale8 : nullptr, g.cap_rows,
-                               g.mid16 ? g.mid_rows : 0u, g.scaled_rows, g.mid16, g.scale16, false});
+            const MidSpan m = mid_span(g);
+            t.items.push_back({&g, g.blk, g.scale, m.scale8, g.cap_rows, m.first, m.end, g.mid16, g.scale16, false});
         }
     const int device = s->ctx->device, D4 = s->D4, Dp = s->Dp;
     const bool fail = s->fail_copy_alloc;
@@ -366,11 +493,7 @@ void start_mid_build(pcv_searcher* s) {
             for (auto& it : tp->items) {
                 if (!ok) break;
                 if (!it.mid16) {
-                    ok = !fail && hipMalloc((void**)&it.mid16, (size_t)it.cap_rows * Dp * 2) == hipSuccess;
-                    if (ok) {
-                        it.own = true;
-                        ok = hipMalloc((void**)&it.scale16, (size_t)it.cap_rows * sizeof(float)) == hipSuccess;
-                    }
+                    ok = it.own = alloc_mid(fail, it.cap_rows, Dp, &it.mid16, &it.scale16) == hipSuccess;
                     if (!ok) break;
                 }
                 launch_mid_pack(side, it.blk, it.scale, it.scale8, it.mid16, it.scale16, it.first_row, it.rows, D4);
@@ -398,26 +521,14 @@ void drop_mid_copies(pcv_searcher* s) {
     settle_mid_build(s, true);
     s->mids_present = false;
     for (auto& src : s->sources)
-        for (auto& g : src.segs) {
-            if (g.mid16) (void)hipFree(g.mid16);
-            if (g.scale16) (void)hipFree(g.scale16);
-            g.mid16 = nullptr;
-            g.scale16 = nullptr;
-            g.mid_rows = 0;
-        }
+        for (auto& g : src.segs) free_copies(g, kCopyMid);
 }
 
 // The 6-bit copies (scan.h) go: they give way first when memory is short, and before a mid copy (a crowded screen gains nothing
 // from them; 100M x 384 with both would not fit the device).
 void drop_six_copies(pcv_searcher* s) {
     for (auto& src : s->sources)
-        for (auto& g : src.segs) {
-            if (g.blk6) (void)hipFree(g.blk6);
-            if (g.scale6) (void)hipFree(g.scale6);
-            g.blk6 = nullptr;
-            g.scale6 = nullptr;
-            g.six_rows = 0;
-        }
+        for (auto& g : src.segs) free_copies(g, kCopySix);
 }
 bool have_six_copies(const pcv_searcher* s) {
     for (const auto& src : s->sources)
@@ -449,21 +560,11 @@ void build_mid_copies(pcv_searcher* s, bool must) {
         for (auto& g : src.segs) {
             if (g.nrows == 0 || (g.mid16 && g.mid_rows >= g.scaled_rows)) continue;
             if (!g.mid16) {
-                const size_t bytes = (size_t)g.cap_rows * s->Dp * 2;
-                hipError_t e = s->fail_copy_alloc ? hipErrorOutOfMemory : hipMalloc((void**)&g.mid16, bytes);
-                if (e == hipSuccess) {
-                    e = hipMalloc((void**)&g.scale16, (size_t)g.cap_rows * sizeof(float));
-                    if (e != hipSuccess) {
-                        (void)hipFree(g.mid16);
-                        g.mid16 = nullptr;
-                    }
-                }
+                const hipError_t e = alloc_mid(s->fail_copy_alloc, g.cap_rows, s->Dp, &g.mid16, &g.scale16);
                 if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    g.mid16 = nullptr;
-                    g.scale16 = nullptr;
                     if (must)
-                        PCV_FAIL(PCV_ERR_DEVICE, "hipMalloc of %.2f GB for the mid copy of %u rows failed: %s", bytes / 1e9, g.cap_rows, hipGetErrorString(e));
+                        PCV_FAIL(PCV_ERR_DEVICE, "hipMalloc of %.2f GB for the mid copy of %u rows failed: %s", (size_t)g.cap_rows * s->Dp * 2 / 1e9, g.cap_rows,
+                                 hipGetErrorString(e));
                     PCV_HIP(hipStreamSynchronize(st));
                     drop_mid_copies(s);
                     s->mid_gave_way = true;
@@ -471,14 +572,9 @@ void build_mid_copies(pcv_searcher* s, bool must) {
                 }
                 g.mid_rows = 0;
             }
-            launch_mid_pack(st, g.blk, g.scale, (g.blk8 && g.copied_rows >= g.scaled_rows) ? g.scale8 : nullptr, g.mid16, g.scale16, g.mid_rows,
-                            g.scaled_rows, s->D4);
-            g.mid_rows = g.scaled_rows;
+            extend_mid(st, g, s->D4);
         }
-    s->mids_present = true;
-    for (const auto& src : s->sources)
-        for (const auto& g : src.segs)
-            if (g.nrows > 0 && (!g.mid16 || g.mid_rows < g.nrows)) s->mids_present = false;
+    s->mids_present = mids_cover(s);
 }
 
 // AUTO mid copy: called by every search entry point in front of its passes
@@ -506,16 +602,8 @@ void maybe_build_mid_copies(pcv_searcher* s) {
 void drop_screening_copies(pcv_searcher* s) {
     settle_mid_build(s, true);  // (it reads the int8 copy's block scales)
     s->copies_kind = 0;
-    drop_six_copies(s);
     for (auto& src : s->sources)
-        for (auto& g : src.segs) {
-            if (g.blk16) (void)hipFree(g.blk16);
-            if (g.blk8) (void)hipFree(g.blk8);
-            if (g.scale8) (void)hipFree(g.scale8);
-            g.blk16 = g.blk8 = nullptr;
-            g.scale8 = nullptr;
-            g.copied_rows = 0;
-        }
+        for (auto& g : src.segs) free_copies(g, kCopySix | kCopyScreen);
 }
 
 // the form AUTO stands for
@@ -528,6 +616,44 @@ inline int copy_kind_wanted(const pcv_searcher* s) {
     return 2;
 }
 
+// What the pass chooser reads, from the segments as they are: the kind of screening copy that covers every row of every segment
+// (copies_kind; 0: none does, or there are no rows), and whether the mid copies (still) do.  One rule for finalize, remove and a
+// view build: a segment without rows counts for nothing, and no rows at all is no kind.  (finalize used to ask for "no source"
+// instead: the same thing there, where every empty tail has just been freed and every empty source erased; a view has no
+// segment without rows.)  mids_present is only ever taken back here; the mid builds raise it (mids_cover).
+void refresh_copy_state(pcv_searcher* s) {
+    const int kind = copy_kind_wanted(s);
+    bool any = false, all = true;
+    for (const auto& src : s->sources)
+        for (const auto& g : src.segs) {
+            if (g.nrows == 0) continue;
+            any = true;
+            if ((kind == 1 ? g.blk16 == nullptr : g.blk8 == nullptr) || g.copied_rows < g.nrows) all = false;
+        }
+    s->copies_kind = any && all ? kind : 0;
+    s->mids_present = s->mids_present && mids_cover(s);
+}
+
+// hipMalloc that makes room when the device is full.  What gives way, in this order, each kind once and for good (its *_gave_way
+// flag), the stream drained before it is freed: the 6-bit copies — before anything else, also to the copy they are derived
+// from —; a mid copy AUTO built by itself — before the screening copies do, and to a screening copy the host asked for —; and,
+// `last_rung` (for rows only), AUTO's screening copies: the f32 rows are scanned from then on.  Copies asked for explicitly stay.
+hipError_t malloc_giving_way(pcv_searcher* s, void** ptr, size_t bytes, bool last_rung) {
+    hipError_t e = hipMalloc(ptr, bytes);
+    auto again_without = [&](void (*drop)(pcv_searcher*), bool& gave_way) {
+        (void)hipGetLastError();
+        PCV_HIP(hipStreamSynchronize(s->ctx->stream));
+        drop(s);
+        gave_way = true;
+        e = hipMalloc(ptr, bytes);
+    };
+    if (e != hipSuccess && have_six_copies(s)) again_without(drop_six_copies, s->six_gave_way);
+    if (e != hipSuccess && s->mids_present && s->mid_copy == PCV_MID_COPY_AUTO) again_without(drop_mid_copies, s->mid_gave_way);
+    if (e != hipSuccess && last_rung && s->screen_copy == PCV_SCREEN_COPY_AUTO && !s->screen_copy_gave_way)
+        again_without(drop_screening_copies, s->screen_copy_gave_way);
+    return e;
+}
+
 // Allocate a segment with room for `cap_rows` rows; zero-filled so padding rows / features are exact
 // zeros and no row is searchable before its scale has been computed.
 Segment alloc_segment(pcv_searcher* s, int64_t cap_rows, bool with_ids) {
@@ -536,31 +662,7 @@ Segment alloc_segment(pcv_searcher* s, int64_t cap_rows, bool with_ids) {
     const uint32_t nblk = (uint32_t)((cap_rows + kBlockRows - 1) / kBlockRows);
     g.cap_rows = nblk * kBlockRows;
     const size_t bytes = (size_t)nblk * s->D4 * 32 * sizeof(float4);
-    hipError_t e = hipMalloc((void**)&g.blk, bytes);
-    if (e != hipSuccess && have_six_copies(s)) {
-        // the rows themselves come first: the 6-bit copies go before anything else
-        (void)hipGetLastError();
-        PCV_HIP(hipStreamSynchronize(s->ctx->stream));
-        drop_six_copies(s);
-        s->six_gave_way = true;
-        e = hipMalloc((void**)&g.blk, bytes);
-    }
-    if (e != hipSuccess && s->mids_present && s->mid_copy == PCV_MID_COPY_AUTO) {
-        // the rows themselves come first: the mid copies go before the screening copies do
-        (void)hipGetLastError();
-        PCV_HIP(hipStreamSynchronize(s->ctx->stream));
-        drop_mid_copies(s);
-        s->mid_gave_way = true;
-        e = hipMalloc((void**)&g.blk, bytes);
-    }
-    if (e != hipSuccess && s->screen_copy == PCV_SCREEN_COPY_AUTO && !s->screen_copy_gave_way) {
-        // the rows themselves come first: give the screening copies back and scan the f32 rows from now on
-        (void)hipGetLastError();
-        PCV_HIP(hipStreamSynchronize(s->ctx->stream));
-        drop_screening_copies(s);
-        s->screen_copy_gave_way = true;
-        e = hipMalloc((void**)&g.blk, bytes);
-    }
+    const hipError_t e = malloc_giving_way(s, (void**)&g.blk, bytes, true);  // the rows themselves come first
     if (e != hipSuccess) {
         (void)hipGetLastError();
         PCV_FAIL(PCV_ERR_DEVICE, "hipMalloc of %.2f GB for %lld corpus rows failed: %s", bytes / 1e9,
@@ -701,18 +803,7 @@ void build_six_copies(pcv_searcher* s) {
             if (g.nrows == 0 || !g.blk8 || (g.blk6 && g.six_rows >= g.copied_rows)) continue;
             if (!g.blk6) {
                 const uint32_t nblk = g.cap_rows / kBlockRows;
-                hipError_t e = s->fail_copy_alloc ? hipErrorOutOfMemory : hipMalloc((void**)&g.blk6, six_copy_bytes(nblk, s->Dp));
-                if (e == hipSuccess) {
-                    e = hipMalloc((void**)&g.scale6, (size_t)nblk * sizeof(float4));
-                    if (e != hipSuccess) {
-                        (void)hipFree(g.blk6);
-                        g.blk6 = nullptr;
-                    }
-                }
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    g.blk6 = nullptr;
-                    g.scale6 = nullptr;
+                if (alloc_with_scales(s->fail_copy_alloc, &g.blk6, six_copy_bytes(nblk, s->Dp), &g.scale6, (size_t)nblk * sizeof(float4)) != hipSuccess) {
                     PCV_HIP(hipStreamSynchronize(st));
                     drop_six_copies(s);
                     s->six_gave_way = true;
@@ -720,10 +811,7 @@ void build_six_copies(pcv_searcher* s) {
                 }
                 g.six_rows = 0;
             }
-            // (from the block of the first row not covered: the int8 copy re-packed that partial block with a new scale)
-            launch_pack6(st, g.blk, g.scale, g.blk8, g.scale8, g.blk6, g.scale6, g.six_rows / kBlockRows, (g.copied_rows + kBlockRows - 1) / kBlockRows,
-                         s->D4);
-            g.six_rows = g.copied_rows;
+            extend_six(st, g, s->D4);
         }
 }
 
@@ -740,33 +828,12 @@ void build_screening_copies(pcv_searcher* s, Source& src) {
         const bool present = kind == 1 ? g.blk16 != nullptr : g.blk8 != nullptr;
         if (present && g.copied_rows >= g.scaled_rows) continue;
         if (!present) {
-            // (a copy of the other kind, left from a mode change, goes first)
-            if (g.blk16) (void)hipFree(g.blk16);
-            if (g.blk8) (void)hipFree(g.blk8);
-            if (g.scale8) (void)hipFree(g.scale8);
-            g.blk16 = g.blk8 = nullptr;
-            g.scale8 = nullptr;
-            g.copied_rows = 0;
+            free_copies(g, kCopyScreen);  // (a copy of the other kind, left from a mode change, goes first)
             const size_t nblk = g.cap_rows / kBlockRows;
             const size_t bytes = kind == 1 ? nblk * (s->D4 / 2) * 32 * sizeof(uint4) : nblk * (size_t)(((s->Dp + 127) & ~127) / 16) * 32 * sizeof(uint4);
+            // (the scales are allocated behind the ladder, not with alloc_with_scales: only the copy itself makes others give way)
             hipError_t e = s->fail_copy_alloc ? hipErrorOutOfMemory  // (PCV_TUNE_FAIL_COPY_ALLOC)
-                                              : hipMalloc(kind == 1 ? (void**)&g.blk16 : (void**)&g.blk8, bytes);
-            if (e != hipSuccess && !s->fail_copy_alloc && have_six_copies(s)) {
-                // the 6-bit copies give way first, to the copy they are derived from
-                (void)hipGetLastError();
-                PCV_HIP(hipStreamSynchronize(st));
-                drop_six_copies(s);
-                s->six_gave_way = true;
-                e = hipMalloc(kind == 1 ? (void**)&g.blk16 : (void**)&g.blk8, bytes);
-            }
-            if (e != hipSuccess && !s->fail_copy_alloc && s->mids_present && s->mid_copy == PCV_MID_COPY_AUTO) {
-                // a mid copy AUTO built by itself gives way to the screening copy the host asked for
-                (void)hipGetLastError();
-                PCV_HIP(hipStreamSynchronize(st));
-                drop_mid_copies(s);
-                s->mid_gave_way = true;
-                e = hipMalloc(kind == 1 ? (void**)&g.blk16 : (void**)&g.blk8, bytes);
-            }
+                                              : malloc_giving_way(s, kind == 1 ? (void**)&g.blk16 : (void**)&g.blk8, bytes, false);
             if (e == hipSuccess && kind == 2) {
                 e = hipMalloc((void**)&g.scale8, (size_t)(g.cap_rows / kBlockRows) * kScale8Stride * sizeof(float));
                 if (e != hipSuccess) {
@@ -796,33 +863,84 @@ void build_screening_copies(pcv_searcher* s, Source& src) {
 }
 
 // ---- hidden items (pcv_searcher_hide_ids; DESIGN.md §3 "Hidden items") ----
-// A batch of ids (ascending, distinct) and, once a segment with an id column needs it, its hash table on the device.
+// A batch of ids (ascending, distinct), optionally with a slot number per id (an update: the place of the id's vector in the
+// call), and, once a segment with an id column needs it, its open-addressing table on the device (scan.h: id_hash): the ids in
+// s->d_idtab and, with slots, each one's slot in the same cell of s->d_idslot.  kIdEmpty marks a free cell, so that id itself
+// travels beside the table (has_empty, empty_slot).
 struct IdBatch {
     const std::vector<int64_t>* ids = nullptr;
+    const std::vector<uint32_t>* slots = nullptr;  // slots[i] belongs to ids[i]; nullptr: no slots
     bool uploaded = false, has_empty = false;
-    uint32_t tmask = 0;
+    uint32_t tmask = 0, empty_slot = 0;
 };
 
 void upload_id_batch(pcv_searcher* s, IdBatch& b) {
     if (b.uploaded) return;
+    const std::vector<int64_t>& ids = *b.ids;
     size_t cap = 64;  // load <= 1/2: about one probe per id looked up
-    while (cap < 2 * b.ids->size()) cap <<= 1;
-    PCV_REQUIRE(cap <= ((size_t)1 << 32), "hide_ids: %zu ids in one batch", b.ids->size());
+    while (cap < 2 * ids.size()) cap <<= 1;
+    PCV_REQUIRE(cap <= ((size_t)1 << 32), "hide_ids: %zu ids in one batch", ids.size());
     std::vector<int64_t> tab(cap, kIdEmpty);
+    std::vector<uint32_t> val(b.slots ? cap : 0, 0);
     b.tmask = (uint32_t)(cap - 1);
-    for (int64_t id : *b.ids) {
-        if (id == kIdEmpty) {
+    for (size_t i = 0; i < ids.size(); ++i) {
+        if (ids[i] == kIdEmpty) {
             b.has_empty = true;
+            if (b.slots) b.empty_slot = (*b.slots)[i];
             continue;
         }
-        uint32_t h = id_hash(id, b.tmask);
+        uint32_t h = id_hash(ids[i], b.tmask);
         while (tab[h] != kIdEmpty) h = (h + 1) & b.tmask;
-        tab[h] = id;
+        tab[h] = ids[i];
+        if (b.slots) val[h] = (*b.slots)[i];
     }
     s->d_idtab.ensure(cap);
     PCV_HIP(hipMemcpyAsync(s->d_idtab.p, tab.data(), cap * sizeof(int64_t), hipMemcpyHostToDevice, s->ctx->stream));
-    PCV_HIP(hipStreamSynchronize(s->ctx->stream));  // (tab goes out of scope)
+    if (b.slots) {
+        s->d_idslot.ensure(cap);
+        PCV_HIP(hipMemcpyAsync(s->d_idslot.p, val.data(), cap * sizeof(uint32_t), hipMemcpyHostToDevice, s->ctx->stream));
+    }
+    PCV_HIP(hipStreamSynchronize(s->ctx->stream));  // (tab and val go out of scope)
     b.uploaded = true;
+}
+
+// The part [first, second) of an ascending id list that names rows [r0, r1) of a segment with implicit ids (id0 + row).
+std::pair<size_t, size_t> implicit_range(const std::vector<int64_t>& ids, const Segment& g, uint32_t r0, uint32_t r1) {
+    const auto lo = std::lower_bound(ids.begin(), ids.end(), g.id0 + (int64_t)r0);
+    const auto hi = std::lower_bound(lo, ids.end(), g.id0 + (int64_t)r1);
+    return {(size_t)(lo - ids.begin()), (size_t)(hi - ids.begin())};
+}
+
+// The id column of rows [r0, r1) of g, streamed once against the batch's table: the matching rows -> s->d_hrows[0..n), n returned;
+// with slots (match_id_slots_kernel; hide does not pay for them) each row's slot -> s->d_hslots as well, and both lists come to
+// the host with the count (one round trip).
+uint32_t match_id_column(pcv_searcher* s, const Segment& g, uint32_t r0, uint32_t r1, IdBatch& b, std::vector<uint32_t>* rows = nullptr,
+                         std::vector<uint32_t>* slots = nullptr) {
+    hipStream_t st = s->ctx->stream;
+    upload_id_batch(s, b);
+    s->d_hcnt.ensure(1);
+    size_t want = std::min<size_t>(r1 - r0, std::max<size_t>(4096, 2 * b.ids->size()));
+    for (;;) {
+        s->d_hrows.ensure(want);
+        if (b.slots) s->d_hslots.ensure(want);
+        const uint32_t cap = (uint32_t)(b.slots ? std::min(s->d_hrows.n, s->d_hslots.n) : s->d_hrows.n);
+        if (b.slots)
+            launch_match_id_slots(st, g.ids, r0, r1, s->d_idtab.p, s->d_idslot.p, b.tmask, b.has_empty, b.empty_slot, s->d_hrows.p, s->d_hslots.p,
+                                  s->d_hcnt.p, cap);
+        else
+            launch_match_ids(st, g.ids, r0, r1, s->d_idtab.p, b.tmask, b.has_empty, s->d_hrows.p, s->d_hcnt.p, cap);
+        uint32_t n = 0;
+        PCV_HIP(hipMemcpyAsync(&n, s->d_hcnt.p, sizeof(n), hipMemcpyDeviceToHost, st));
+        if (rows) {
+            rows->resize(cap);
+            slots->resize(cap);
+            PCV_HIP(hipMemcpyAsync(rows->data(), s->d_hrows.p, (size_t)cap * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            PCV_HIP(hipMemcpyAsync(slots->data(), s->d_hslots.p, (size_t)cap * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        PCV_HIP(hipStreamSynchronize(st));
+        if (n <= cap) return n;
+        want = n;  // (more rows carry these ids than the lists had room for: once more with room for all)
+    }
 }
 
 // Rows [r0, r1) of segment g whose id is in the batch -> s->d_hrows[0..n), n returned.  Implicit ids (id0 + row) are found by
@@ -830,28 +948,15 @@ void upload_id_batch(pcv_searcher* s, IdBatch& b) {
 uint32_t find_rows(pcv_searcher* s, const Segment& g, uint32_t r0, uint32_t r1, IdBatch& b) {
     hipStream_t st = s->ctx->stream;
     if (r0 >= r1) return 0;
-    if (!g.ids) {
-        const std::vector<int64_t>& v = *b.ids;
-        std::vector<uint32_t> rows;
-        for (auto it = std::lower_bound(v.begin(), v.end(), g.id0 + r0); it != v.end() && *it < g.id0 + r1; ++it)
-            rows.push_back((uint32_t)(*it - g.id0));
-        if (rows.empty()) return 0;
-        s->d_hrows.ensure(rows.size());
-        PCV_HIP(hipMemcpyAsync(s->d_hrows.p, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        PCV_HIP(hipStreamSynchronize(st));
-        return (uint32_t)rows.size();
-    }
-    upload_id_batch(s, b);
-    s->d_hcnt.ensure(1);
-    s->d_hrows.ensure(std::min<size_t>(r1 - r0, std::max<size_t>(4096, 2 * b.ids->size())));
-    for (;;) {
-        launch_match_ids(st, g.ids, r0, r1, s->d_idtab.p, b.tmask, b.has_empty, s->d_hrows.p, s->d_hcnt.p, (uint32_t)s->d_hrows.n);
-        uint32_t n = 0;
-        PCV_HIP(hipMemcpyAsync(&n, s->d_hcnt.p, sizeof(n), hipMemcpyDeviceToHost, st));
-        PCV_HIP(hipStreamSynchronize(st));
-        if (n <= s->d_hrows.n) return n;
-        s->d_hrows.ensure(n);  // (more rows carry these ids than the list had room for: once more with room for all)
-    }
+    if (g.ids) return match_id_column(s, g, r0, r1, b);
+    const auto in = implicit_range(*b.ids, g, r0, r1);
+    std::vector<uint32_t> rows;
+    for (size_t i = in.first; i < in.second; ++i) rows.push_back((uint32_t)((*b.ids)[i] - g.id0));
+    if (rows.empty()) return 0;
+    s->d_hrows.ensure(rows.size());
+    PCV_HIP(hipMemcpyAsync(s->d_hrows.p, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    PCV_HIP(hipStreamSynchronize(st));
+    return (uint32_t)rows.size();
 }
 
 void hide_found(pcv_searcher* s, Segment& g, uint32_t n) {
@@ -859,37 +964,23 @@ void hide_found(pcv_searcher* s, Segment& g, uint32_t n) {
                      s->D4);
 }
 
-// The rows come back: their scales, their bf16 pieces (row-local), and the WHOLE 32-row blocks of the int8 copy and of a mid copy
-// quantised with it — a finalize that appended rows to such a block while they were hidden quantised it without them.
+// The rows come back: their scales, then the copies (repair_copies).
 void unhide_found(pcv_searcher* s, Segment& g, uint32_t n) {
     hipStream_t st = s->ctx->stream;
     launch_restore_scales(st, g.blk, s->d_hrows.p, n, s->D4, s->metric, g.scale);
-    if (g.blk16) launch_repack16_rows(st, g.blk, g.scale, s->d_hrows.p, n, g.blk16, s->D4);
-    uint32_t nb = 0;
+    std::vector<uint32_t> blocks;
     if (g.blk8) {
         std::vector<uint32_t> rows(n);
         PCV_HIP(hipMemcpyAsync(rows.data(), s->d_hrows.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         PCV_HIP(hipStreamSynchronize(st));
-        std::vector<uint32_t> blocks;
-        for (uint32_t r : rows)
-            if (r < g.copied_rows) blocks.push_back(r / kBlockRows);
-        std::sort(blocks.begin(), blocks.end());
-        blocks.erase(std::unique(blocks.begin(), blocks.end()), blocks.end());
-        nb = (uint32_t)blocks.size();
-        if (nb) {
-            s->d_hblocks.ensure(nb);
-            PCV_HIP(hipMemcpyAsync(s->d_hblocks.p, blocks.data(), (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            launch_repack8_blocks(st, g.blk, g.scale, s->d_hblocks.p, nb, g.blk8, g.scale8, s->D4);
-            if (g.blk6) launch_repack6_blocks(st, g.blk, g.scale, g.blk8, g.scale8, s->d_hblocks.p, nb, g.blk6, g.scale6, s->D4);
+        blocks = touched_blocks(g, rows);
+        if (!blocks.empty()) {
+            s->d_hblocks.ensure(blocks.size());
+            PCV_HIP(hipMemcpyAsync(s->d_hblocks.p, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
-        PCV_HIP(hipStreamSynchronize(st));  // (blocks goes out of scope)
     }
-    if (g.mid16 && g.mid_rows > 0) {
-        if (g.blk8 && g.copied_rows >= g.nrows)  // the copy is quantised with the int8 copy's block scales (launch_mid_pack)
-            launch_repack_mid(st, g.blk, g.scale, g.scale8, s->d_hblocks.p, nb, g.mid_rows, g.mid16, g.scale16, s->D4);
-        else
-            launch_repack_mid(st, g.blk, g.scale, nullptr, s->d_hrows.p, n, g.mid_rows, g.mid16, g.scale16, s->D4);
-    }
+    repair_copies(s, g, s->d_hrows.p, n, s->d_hblocks.p, (uint32_t)blocks.size());
+    if (g.blk8) PCV_HIP(hipStreamSynchronize(st));  // (blocks goes out of scope)
 }
 
 // Hide (or unhide) every row, in every source, whose id is in `batch` (ascending, distinct, none of it in the set yet / all of it
@@ -926,61 +1017,20 @@ struct UpdateSeg {
     size_t off = 0, boff = 0;
 };
 
-// (row, slot) pairs of segment g for the batch ids[0..n): `by_id` lists the slots ascending by id, `sorted` their ids.  Implicit
-// ids (id0 + row) are found on the host; an id column is streamed once by match_id_slots_kernel (one round trip).
-std::vector<std::pair<uint32_t, uint32_t>> find_slots(pcv_searcher* s, const Segment& g, const int64_t* ids, int64_t n,
-                                                      const std::vector<uint32_t>& by_id, const std::vector<int64_t>& sorted,
-                                                      bool& table_up, uint32_t& tmask, bool& has_empty, uint32_t& empty_slot) {
-    hipStream_t st = s->ctx->stream;
-    std::vector<std::pair<uint32_t, uint32_t>> out;  // (slot, row)
+// (slot, row) pairs of segment g for the batch.  Implicit ids (id0 + row) are found on the host; an id column is streamed once by
+// match_id_slots_kernel.
+std::vector<std::pair<uint32_t, uint32_t>> find_slots(pcv_searcher* s, const Segment& g, IdBatch& b) {
+    std::vector<std::pair<uint32_t, uint32_t>> out;
     if (!g.ids) {
-        for (auto it = std::lower_bound(sorted.begin(), sorted.end(), g.id0); it != sorted.end() && *it < g.id0 + (int64_t)g.nrows; ++it)
-            out.push_back({by_id[it - sorted.begin()], (uint32_t)(*it - g.id0)});
+        const auto in = implicit_range(*b.ids, g, 0, g.nrows);
+        for (size_t i = in.first; i < in.second; ++i) out.push_back({(*b.slots)[i], (uint32_t)((*b.ids)[i] - g.id0)});
         return out;
     }
-    if (!table_up) {  // the batch's table, id -> slot (scan.h: id_hash)
-        size_t cap = 64;  // load <= 1/2
-        while (cap < 2 * (size_t)n) cap <<= 1;
-        std::vector<int64_t> tab(cap, kIdEmpty);
-        std::vector<uint32_t> val(cap, 0);
-        tmask = (uint32_t)(cap - 1);
-        for (int64_t i = 0; i < n; ++i) {
-            if (ids[i] == kIdEmpty) {
-                has_empty = true;
-                empty_slot = (uint32_t)i;
-                continue;
-            }
-            uint32_t h = id_hash(ids[i], tmask);
-            while (tab[h] != kIdEmpty) h = (h + 1) & tmask;
-            tab[h] = ids[i];
-            val[h] = (uint32_t)i;
-        }
-        PCV_HIP(hipMemcpyAsync(s->d_idtab.p, tab.data(), cap * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        PCV_HIP(hipMemcpyAsync(s->d_idslot.p, val.data(), cap * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        PCV_HIP(hipStreamSynchronize(st));  // (tab and val go out of scope)
-        table_up = true;
-    }
-    size_t cap = std::min<size_t>(g.nrows, std::max<size_t>(4096, 2 * (size_t)n));
-    for (;;) {
-        s->d_hrows.ensure(cap);
-        s->d_hslots.ensure(cap);
-        const uint32_t c = (uint32_t)std::min(s->d_hrows.n, s->d_hslots.n);
-        std::vector<uint32_t> rows(c), slots(c);
-        uint32_t cnt = 0;
-        launch_match_id_slots(st, g.ids, 0, g.nrows, s->d_idtab.p, s->d_idslot.p, tmask, has_empty, empty_slot, s->d_hrows.p,
-                              s->d_hslots.p, s->d_hcnt.p, c);
-        PCV_HIP(hipMemcpyAsync(&cnt, s->d_hcnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        PCV_HIP(hipMemcpyAsync(rows.data(), s->d_hrows.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        PCV_HIP(hipMemcpyAsync(slots.data(), s->d_hslots.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        PCV_HIP(hipStreamSynchronize(st));
-        if (cnt > c) {  // (more rows carry these ids than the lists had room for: once more with room for all)
-            cap = cnt;
-            continue;
-        }
-        out.reserve(cnt);
-        for (uint32_t i = 0; i < cnt; ++i) out.push_back({slots[i], rows[i]});
-        return out;
-    }
+    std::vector<uint32_t> rows, slots;
+    const uint32_t cnt = match_id_column(s, g, 0, g.nrows, b, &rows, &slots);
+    out.reserve(cnt);
+    for (uint32_t i = 0; i < cnt; ++i) out.push_back({slots[i], rows[i]});
+    return out;
 }
 
 // Every row, in every source, whose id is ids[i] takes the vector rows[i] (n rows of D f32, or their little-endian blob bytes);
@@ -991,23 +1041,16 @@ int64_t update_by_id(pcv_searcher* s, const int64_t* ids, const void* rows, int6
     hipStream_t st = s->ctx->stream;
     std::vector<int64_t> sorted(n);
     for (int64_t i = 0; i < n; ++i) sorted[i] = ids[by_id[i]];
-    {
-        size_t cap = 64;
-        while (cap < 2 * (size_t)n) cap <<= 1;
-        PCV_REQUIRE(cap <= ((size_t)1 << 32), "update: %lld ids in one batch", (long long)n);
-        s->d_idtab.ensure(cap);
-        s->d_idslot.ensure(cap);
-        s->d_hcnt.ensure(1);
-    }
-    // 1. find the rows
-    bool table_up = false, has_empty = false;
-    uint32_t tmask = 0, empty_slot = 0;
+    // 1. find the rows (n < 2^31, update_call: the batch's table has room)
+    IdBatch b;
+    b.ids = &sorted;
+    b.slots = &by_id;
     std::vector<UpdateSeg> us;
     size_t total = 0, total_blocks = 0;
     for (auto& src : s->sources)
         for (auto& g : src.segs) {
             if (g.nrows == 0) continue;
-            auto pr = find_slots(s, g, ids, n, by_id, sorted, table_up, tmask, has_empty, empty_slot);
+            auto pr = find_slots(s, g, b);
             if (pr.empty()) continue;
             std::sort(pr.begin(), pr.end());
             UpdateSeg u;
@@ -1017,10 +1060,8 @@ int64_t update_by_id(pcv_searcher* s, const int64_t* ids, const void* rows, int6
                 const bool hidden = std::binary_search(s->hidden.begin(), s->hidden.end(), ids[p.first]);
                 u.rows.push_back(p.second);
                 u.slots.push_back(p.first | (hidden ? kSlotHidden : 0u));
-                if (g.blk8 && p.second < g.copied_rows) u.blocks.push_back(p.second / kBlockRows);
             }
-            std::sort(u.blocks.begin(), u.blocks.end());
-            u.blocks.erase(std::unique(u.blocks.begin(), u.blocks.end()), u.blocks.end());
+            u.blocks = touched_blocks(g, u.rows);
             u.off = total;
             u.boff = total_blocks;
             total += u.rows.size();
@@ -1060,22 +1101,10 @@ int64_t update_by_id(pcv_searcher* s, const int64_t* ids, const void* rows, int6
         }
         if (staged) PCV_HIP(hipStreamSynchronize(st));  // the staging buffer (and the caller's memory) are free again
     }
-    // 4. the copies, as unhide_found makes them: bf16 pieces row by row, the WHOLE blocks of the int8 copy (a new row may need a
-    // smaller s_blk) and of a mid copy quantised with it, other mid copies row by row
+    // 4. the copies
     for (const auto& u : us) {
-        Segment& g = *u.g;
-        const uint32_t nr = (uint32_t)u.rows.size(), nb = (uint32_t)u.blocks.size();
-        const uint32_t* d_rows = s->d_urows.p + u.off;
-        const uint32_t* d_blocks = nb ? s->d_hblocks.p + u.boff : nullptr;
-        if (g.blk16) launch_repack16_rows(st, g.blk, g.scale, d_rows, nr, g.blk16, s->D4);
-        if (g.blk8 && nb) launch_repack8_blocks(st, g.blk, g.scale, d_blocks, nb, g.blk8, g.scale8, s->D4);
-        if (g.blk6 && nb) launch_repack6_blocks(st, g.blk, g.scale, g.blk8, g.scale8, d_blocks, nb, g.blk6, g.scale6, s->D4);
-        if (g.mid16 && g.mid_rows > 0) {
-            if (g.blk8 && g.copied_rows >= g.nrows)  // (launch_mid_pack quantised it with the int8 copy's block scales)
-                launch_repack_mid(st, g.blk, g.scale, g.scale8, d_blocks, nb, g.mid_rows, g.mid16, g.scale16, s->D4);
-            else
-                launch_repack_mid(st, g.blk, g.scale, nullptr, d_rows, nr, g.mid_rows, g.mid16, g.scale16, s->D4);
-        }
+        const uint32_t nb = (uint32_t)u.blocks.size();
+        repair_copies(s, *u.g, s->d_urows.p + u.off, (uint32_t)u.rows.size(), nb ? s->d_hblocks.p + u.boff : nullptr, nb);
     }
     // 5. the corpus bound the dot-metric screens use (it only grows: update_rows_kernel raised it for the new rows)
     uint32_t bits = 0;
@@ -1094,7 +1123,7 @@ struct RemoveSeg {
     Segment* g = nullptr;
     DevBuf<uint32_t> flags4, tiles;
     std::vector<uint32_t> off;
-    int64_t* new_ids = nullptr;  // the id column an implicit-id segment gets (id0 + row), allocated and filled, not yet the segment's
+    DevBuf<int64_t> new_ids;     // the id column an implicit-id segment gets (id0 + row), allocated and filled, not yet the segment's
     uint32_t keep = 0;           // rows that stay
     uint32_t first = 0;          // the first row that goes: the rows in front of it are not touched
     uint32_t hidden_gone = 0;    // rows that go and whose id is in the hidden set
@@ -1110,7 +1139,8 @@ uint32_t remove_chunk_rows() {
 
 // Every row, in every source, whose id is in `batch` (ascending, distinct, not empty) leaves the searcher; the rows behind it
 // move down inside their segment.  Returns the rows removed.  Every row is found and every buffer allocated before the first
-// row moves; the scratch (flags, offsets, id table, bounce buffer) is given back at the end, whatever happens.
+// row moves; the scratch (flags, offsets, id table, bounce buffer) is given back at the end, whatever happens: the local buffers
+// by going out of scope, the searcher's own by `give_back` — both behind the catch below, which drains the stream first.
 int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
     hipStream_t st = s->ctx->stream;
     const int D4 = s->D4;
@@ -1119,22 +1149,11 @@ int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
     DevBuf<float4> b_blk;
     DevBuf<float> b_scale;
     DevBuf<int64_t> b_ids;
-    auto release_scratch = [&] {
-        for (auto& r : plan) {
-            r->flags4.release();
-            r->tiles.release();
-            if (r->new_ids) (void)hipFree(r->new_ids);
-            r->new_ids = nullptr;
-        }
-        total.release();
-        sel.release();
-        b_blk.release();
-        b_scale.release();
-        b_ids.release();
+    const auto give_back = at_exit([s] {
         s->d_idtab.release();
         s->d_hrows.release();
         s->d_hcnt.release();
-    };
+    });
     int64_t removed = 0;
     try {
         // 0. the rows that go AND are hidden, per segment (Segment::hidden_rows counts them): the ids of the batch that are in the set
@@ -1160,24 +1179,25 @@ int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
                 auto r = std::make_unique<RemoveSeg>();
                 r->src = &src;
                 r->g = &g;
-                const int64_t* ids = g.ids;
                 if (!g.ids) {
-                    const auto lo = std::lower_bound(batch.begin(), batch.end(), g.id0);
-                    const auto hi = std::lower_bound(lo, batch.end(), g.id0 + (int64_t)g.nrows);
-                    if (lo == hi) continue;
-                    if ((uint32_t)(hi - lo) == g.nrows) {  // every row goes: no id column needed
+                    const auto in = implicit_range(batch, g, 0, g.nrows);
+                    if (in.first == in.second) continue;
+                    if (in.second - in.first == g.nrows) {  // every row goes: no id column needed
                         r->keep = 0;
                         plan.push_back(std::move(r));
                         continue;
                     }
-                    PCV_HIP(hipMalloc((void**)&r->new_ids, (size_t)g.cap_rows * sizeof(int64_t)));
-                    PCV_HIP(hipMemsetAsync(r->new_ids, 0xff, (size_t)g.cap_rows * sizeof(int64_t), st));
-                    launch_iota_ids(st, r->new_ids, g.id0, g.nrows);
-                    ids = r->new_ids;
                 }
                 Segment* gp = &g;
-                plan.push_back(std::move(r));  // (from here on release_scratch frees what this segment holds)
+                plan.push_back(std::move(r));  // (the plan owns what this segment holds: it is freed behind the catch's synchronise)
                 RemoveSeg& rs = *plan.back();
+                const int64_t* ids = g.ids;
+                if (!ids) {
+                    rs.new_ids.ensure(g.cap_rows);
+                    PCV_HIP(hipMemsetAsync(rs.new_ids.p, 0xff, (size_t)g.cap_rows * sizeof(int64_t), st));
+                    launch_iota_ids(st, rs.new_ids.p, g.id0, g.nrows);
+                    ids = rs.new_ids.p;
+                }
                 upload_id_batch(s, b);
                 const uint32_t nt = view_tiles(gp->nrows);
                 rs.flags4.ensure((size_t)nt * 256);
@@ -1189,9 +1209,6 @@ int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
                 PCV_HIP(hipStreamSynchronize(st));
                 rs.off[nt] = rs.keep;
                 if (rs.keep == gp->nrows) {  // nothing of this segment goes
-                    rs.flags4.release();
-                    rs.tiles.release();
-                    if (rs.new_ids) (void)hipFree(rs.new_ids);
                     plan.pop_back();
                     continue;
                 }
@@ -1207,10 +1224,7 @@ int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
                 rs.first = t0 * (uint32_t)kViewTile + i;
                 longest = std::max(longest, gp->nrows - t0 * (uint32_t)kViewTile);
             }
-        if (plan.empty()) {
-            release_scratch();
-            return 0;
-        }
+        if (plan.empty()) return 0;
         // 2. every buffer the moves need: one chunk's row list and its bounce buffer (blocked like the destination, which may begin
         //    inside a block: one block more)
         const uint32_t chunk = std::min(remove_chunk_rows(), (longest + (uint32_t)kViewTile - 1) / (uint32_t)kViewTile * (uint32_t)kViewTile);
@@ -1229,7 +1243,7 @@ int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
             Segment& g = *r.g;
             removed += g.nrows - r.keep;
             if (r.keep == 0) continue;
-            int64_t* ids = r.new_ids ? r.new_ids : g.ids;
+            int64_t* ids = r.new_ids.p ? r.new_ids.p : g.ids;
             for (uint32_t s0 = r.first / (uint32_t)kViewTile * (uint32_t)kViewTile; s0 < g.nrows; s0 += chunk) {
                 const uint32_t s1 = (uint32_t)std::min<uint64_t>((uint64_t)s0 + chunk, g.nrows);
                 const uint32_t tile0 = s0 / (uint32_t)kViewTile, tile1 = view_tiles(s1);
@@ -1260,10 +1274,7 @@ int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
                 free_segment(g);  // (nrows 0: erased below)
                 continue;
             }
-            if (r.new_ids) {
-                g.ids = r.new_ids;
-                r.new_ids = nullptr;
-            }
+            if (r.new_ids.p) g.ids = r.new_ids.hand_over();
             const uint32_t from = r.first / kBlockRows * kBlockRows;
             g.nrows = g.scaled_rows = r.keep;
             g.copied_rows = std::min(g.copied_rows, from);
@@ -1273,28 +1284,19 @@ int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch) {
         for (Source* src : touched) {
             src->segs.erase(std::remove_if(src->segs.begin(), src->segs.end(), [](const Segment& x) { return x.blk == nullptr; }), src->segs.end());
             build_screening_copies(s, *src);
-            for (auto& g : src->segs) {
+            for (auto& g : src->segs) {  // (behind the int8 copy: the 6-bit pack reads the blocks it has just re-packed)
                 if (g.nrows == 0) continue;
-                if (g.blk6 && g.blk8 && g.six_rows < g.copied_rows) {
-                    launch_pack6(st, g.blk, g.scale, g.blk8, g.scale8, g.blk6, g.scale6, g.six_rows / kBlockRows, (g.copied_rows + kBlockRows - 1) / kBlockRows, D4);
-                    g.six_rows = g.copied_rows;
-                }
-                if (g.mid16 && g.mid_rows < g.scaled_rows) {
-                    launch_mid_pack(st, g.blk, g.scale, (g.blk8 && g.copied_rows >= g.scaled_rows) ? g.scale8 : nullptr, g.mid16, g.scale16, g.mid_rows,
-                                    g.scaled_rows, D4);
-                    g.mid_rows = g.scaled_rows;
-                }
+                extend_six(st, g, D4);
+                extend_mid(st, g, D4);
             }
         }
         assign_positions(s);
         PCV_HIP(hipStreamSynchronize(st));
         PCV_HIP(hipGetLastError());
     } catch (...) {
-        (void)hipStreamSynchronize(st);
-        release_scratch();
+        (void)hipStreamSynchronize(st);  // (before anything queued work may still read is freed)
         throw;
     }
-    release_scratch();
     return removed;
 }
 
@@ -1339,14 +1341,7 @@ void do_finalize(pcv_searcher* s) {
         build_mid_copies(s, s->mid_copy == PCV_MID_COPY_ON);  // new rows join the copy that is there
     build_six_copies(s);  // (over every source: a pass streams them only if every selected segment has one)
     assign_positions(s);
-    s->copies_kind = s->sources.empty() ? 0 : copy_kind_wanted(s);
-    for (const auto& src : s->sources)
-        for (const auto& g : src.segs)
-            if (g.nrows > 0 && ((s->copies_kind == 1 ? g.blk16 == nullptr : g.blk8 == nullptr) || g.copied_rows < g.nrows)) s->copies_kind = 0;
-    if (s->mids_present)
-        for (const auto& src : s->sources)
-            for (const auto& g : src.segs)
-                if (g.nrows > 0 && (!g.mid16 || g.mid_rows < g.nrows)) s->mids_present = false;
+    refresh_copy_state(s);
     uint32_t bits = 0;
     PCV_HIP(hipMemcpyAsync(&bits, s->d_max_norm_bits, 4, hipMemcpyDeviceToHost, st));
     PCV_HIP(hipStreamSynchronize(st));
@@ -1954,6 +1949,21 @@ inline void refuse_view(const pcv_searcher* s, const char* who) {
     PCV_REQUIRE(s->view_parent == nullptr, "%s: the searcher is a view (read-only): change its parent instead", who);
 }
 
+// What hide, unhide, remove and update ask before they change a row (s->mu held).
+void begin_change(const pcv_searcher* s, const char* who) {
+    refuse_view(s, who);
+    PCV_REQUIRE(!s->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
+    PCV_REQUIRE(!s->pending.active, "%s: a queued pass has not been collected", who);
+}
+
+// A graph captured over rows that are about to move or to be freed must not replay: the next passes capture afresh.
+void drop_pass_graph(pcv_searcher* s) {
+    if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
+    s->graph_exec = nullptr;
+    s->graph_shape = s->last_shape = pcv_searcher::PassShape{};
+    s->shape_seen = 0;
+}
+
 // the screening copy a view keeps: the kind its parent holds for all of its rows, none if the parent holds none
 int view_screen_mode(const pcv_searcher* p) {
     return p->copies_kind == 2 ? PCV_SCREEN_COPY_INT8 : (p->copies_kind == 1 ? PCV_SCREEN_COPY_BF16 : PCV_SCREEN_COPY_OFF);
@@ -1998,11 +2008,7 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
     PCV_HIP(hipSetDevice(v->ctx->device));
     PCV_HIP(hipStreamSynchronize(st));  // (a pass of the view may still read the old rows)
     drop_view_rows(v);
-    // a graph captured over the old rows must not replay over freed buffers: the next passes capture afresh
-    if (v->graph_exec) (void)hipGraphExecDestroy(v->graph_exec);
-    v->graph_exec = nullptr;
-    v->graph_shape = v->last_shape = pcv_searcher::PassShape{};
-    v->shape_seen = 0;
+    drop_pass_graph(v);
     v->screen_copy = view_screen_mode(p);
     v->screen_copy_gave_way = false;
     v->mid_copy = p->mid_copy == PCV_MID_COPY_ON ? PCV_MID_COPY_ON : PCV_MID_COPY_OFF;
@@ -2020,18 +2026,11 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
         std::vector<Part> parts;
         int64_t rows;
     };
-    std::vector<SrcPlan> plan;
+    std::vector<SrcPlan> plan;  // (this and the scratch below are freed by scope, behind the catch's synchronise)
     DevBuf<uint32_t> flags4, tiles, total;
     IdBatch b;
     b.ids = &v->view_ids;
-    auto release_scratch = [&] {
-        for (auto& sp : plan)
-            for (auto& pt : sp.parts) pt.sel.release();
-        flags4.release();
-        tiles.release();
-        total.release();
-        v->d_idtab.release();
-    };
+    const auto give_back = at_exit([v] { v->d_idtab.release(); });
     int64_t rows = 0;
     try {
         // 1. which rows: an id column is matched on the device (order-keeping selection), implicit ids (id0 + row) on the host
@@ -2041,10 +2040,9 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
                 if (g.nrows == 0 || v->view_ids.empty()) continue;
                 Part pt{&g, {}, 0};
                 if (!g.ids) {
-                    const std::vector<int64_t>& ids = v->view_ids;
+                    const auto in = implicit_range(v->view_ids, g, 0, g.nrows);
                     std::vector<uint32_t> sel;
-                    for (auto it = std::lower_bound(ids.begin(), ids.end(), g.id0); it != ids.end() && *it < g.id0 + (int64_t)g.nrows; ++it)
-                        sel.push_back((uint32_t)(*it - g.id0));
+                    for (size_t i = in.first; i < in.second; ++i) sel.push_back((uint32_t)(v->view_ids[i] - g.id0));
                     pt.n = (uint32_t)sel.size();
                     if (pt.n) {
                         pt.sel.ensure(pt.n);
@@ -2068,7 +2066,7 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
                 }
                 if (pt.n) {
                     sp.rows += pt.n;
-                    sp.parts.push_back(pt);
+                    sp.parts.push_back(std::move(pt));
                 }
             }
             if (sp.rows) plan.push_back(std::move(sp));
@@ -2099,21 +2097,16 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
         for (auto& src : v->sources) build_screening_copies(v, src);
         build_six_copies(v);
         if (v->mid_copy == PCV_MID_COPY_ON && rows) build_mid_copies(v, true);
-        v->copies_kind = v->sources.empty() ? 0 : copy_kind_wanted(v);
-        for (const auto& src : v->sources)
-            for (const auto& g : src.segs)
-                if ((v->copies_kind == 1 ? g.blk16 == nullptr : g.blk8 == nullptr) || g.copied_rows < g.nrows) v->copies_kind = 0;
+        refresh_copy_state(v);
         PCV_HIP(hipEventRecord(v->ev[3], st));
         PCV_HIP(hipStreamSynchronize(st));
         PCV_HIP(hipGetLastError());
     } catch (...) {
         (void)hipGetLastError();
         (void)hipStreamSynchronize(st);
-        release_scratch();
         drop_view_rows(v);
         throw;
     }
-    release_scratch();
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, v->ev[0], v->ev[3]);
     v->view_build_ms = ms;
@@ -2185,29 +2178,6 @@ void destroy_searcher(pcv_searcher* s) {
     }
     for (auto& src : s->sources)
         for (auto& g : src.segs) free_segment(g);
-    s->d_stage.release();
-    s->d_qf32.release();
-    s->d_qraw.release();
-    s->d_margin.release();
-    s->d_margin32.release();
-    s->d_qbf16.release();
-    s->d_q8.release();
-    s->d_q8c.release();
-    s->d_spec.release();
-    s->d_cand_s.release();
-    s->d_tau.release();
-    s->d_slots.release();
-    s->d_cnt.release();
-    s->d_cand.release();
-    s->d_hits.release();
-    s->d_idtab.release();
-    s->d_hrows.release();
-    s->d_hblocks.release();
-    s->d_hcnt.release();
-    s->d_idslot.release();
-    s->d_hslots.release();
-    s->d_urows.release();
-    s->d_uslots.release();
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
     if (s->pin) (void)hipHostFree(s->pin);
     if (s->pin_pass) (void)hipHostFree(s->pin_pass);
@@ -2215,9 +2185,8 @@ void destroy_searcher(pcv_searcher* s) {
     if (s->d_max_norm_bits) (void)hipFree(s->d_max_norm_bits);
     for (auto& e : s->ev)
         if (e) (void)hipEventDestroy(e);
-    s->d_ppos.release();
     if (s->view_parent) s->view_parent->live_views.fetch_sub(1);
-    delete s;
+    delete s;  // (with every DevBuf of it)
 }
 }  // namespace
 
@@ -2450,10 +2419,8 @@ static pcv_status hide_or_unhide(pcv_searcher* s, const int64_t* ids, int64_t n,
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
         PCV_REQUIRE(n >= 0 && (ids != nullptr || n == 0), "%s: bad id list", who);
-        refuse_view(s, who);
         std::lock_guard<std::mutex> lk(s->mu);
-        PCV_REQUIRE(!s->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
-        PCV_REQUIRE(!s->pending.active, "%s: a queued pass has not been collected", who);
+        begin_change(s, who);
         if (out_rows) *out_rows = 0;
         // the batch: the ids whose membership changes, ascending and distinct
         std::vector<int64_t> batch(ids, ids + n);
@@ -2493,10 +2460,8 @@ pcv_status pcv_searcher_remove_ids(pcv_searcher* s, const int64_t* ids, int64_t 
     return guarded([&] {
         PCV_REQUIRE(s != nullptr, "remove_ids: searcher is NULL");
         PCV_REQUIRE(n >= 0 && (ids != nullptr || n == 0), "remove_ids: bad id list (NULL with n > 0, or n < 0)");
-        refuse_view(s, "remove_ids");
         std::lock_guard<std::mutex> lk(s->mu);
-        PCV_REQUIRE(!s->dirty, "remove_ids: pending rows; call pcv_searcher_finalize first");
-        PCV_REQUIRE(!s->pending.active, "remove_ids: a queued pass has not been collected");
+        begin_change(s, "remove_ids");
         if (out_rows) *out_rows = 0;
         if (n == 0) return;
         std::vector<int64_t> batch(ids, ids + n);
@@ -2505,23 +2470,9 @@ pcv_status pcv_searcher_remove_ids(pcv_searcher* s, const int64_t* ids, int64_t 
         PCV_HIP(hipSetDevice(s->ctx->device));
         PCV_HIP(hipStreamSynchronize(s->ctx->stream));
         settle_mid_build(s, true);  // (the AUTO mid build reads the rows and scales and writes the mid copy)
-        // a graph captured over the rows as they lay must not replay over moved or freed rows: the next passes capture afresh
-        if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
-        s->graph_exec = nullptr;
-        s->graph_shape = s->last_shape = pcv_searcher::PassShape{};
-        s->shape_seen = 0;
+        drop_pass_graph(s);
         const int64_t removed = remove_by_id(s, batch);
-        // what finalize derives from the segments
-        s->copies_kind = copy_kind_wanted(s);
-        bool any = false;
-        for (const auto& src : s->sources)
-            for (const auto& g : src.segs) {
-                if (g.nrows == 0) continue;
-                any = true;
-                if ((s->copies_kind == 1 ? g.blk16 == nullptr : g.blk8 == nullptr) || g.copied_rows < g.nrows) s->copies_kind = 0;
-                if (!g.mid16 || g.mid_rows < g.nrows) s->mids_present = false;
-            }
-        if (!any) s->copies_kind = 0;
+        refresh_copy_state(s);
         s->gen += 1;  // (views copy their rows again at their next call)
         if (out_rows) *out_rows = removed;
     });
@@ -2549,12 +2500,10 @@ static pcv_status update_call(pcv_searcher* s, const int64_t* ids, const void* r
         PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
         PCV_REQUIRE(n >= 0 && ((ids != nullptr && rows != nullptr) || n == 0), "%s: bad ids/rows/n (NULL with n > 0, or n < 0)", who);
         PCV_REQUIRE(n <= 0x7fffffff, "%s: %lld ids in one call", who, (long long)n);
-        refuse_view(s, who);
         const uint32_t probe = 1;  // (blobs: little-endian f32, as pcv_searcher_add_blobs reads them)
         PCV_REQUIRE(*reinterpret_cast<const uint8_t*>(&probe) == 1, "%s: big-endian host", who);
         std::lock_guard<std::mutex> lk(s->mu);
-        PCV_REQUIRE(!s->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
-        PCV_REQUIRE(!s->pending.active, "%s: a queued pass has not been collected", who);
+        begin_change(s, who);
         if (out_rows) *out_rows = 0;
         if (out_found && n > 0) std::memset(out_found, 0, (size_t)n);
         if (n == 0) return;
@@ -2566,10 +2515,7 @@ static pcv_status update_call(pcv_searcher* s, const int64_t* ids, const void* r
         PCV_HIP(hipSetDevice(s->ctx->device));
         settle_mid_build(s, true);  // (the AUTO mid build reads the rows and scales and writes the mid copy)
         std::vector<uint8_t> found((size_t)n, 0);
-        struct StageBack {  // the staging buffer goes back, whatever happens (as finalize gives it back)
-            pcv_searcher* s;
-            ~StageBack() { s->d_stage.release(); }
-        } stage_back{s};
+        const auto stage_back = at_exit([s] { s->d_stage.release(); });  // whatever happens (as finalize gives it back)
         const int64_t changed = update_by_id(s, ids, rows, n, by_id, found);
         if (changed) s->gen += 1;
         if (out_found) std::memcpy(out_found, found.data(), (size_t)n);
@@ -2670,29 +2616,16 @@ pcv_status pcv_searcher_get_rows(pcv_searcher* s, const int64_t* positions, int6
         DevBuf<SegDesc> d_segs;
         DevBuf<int64_t> d_pos, d_ids;
         DevBuf<float> d_rows;
-        try {
-            d_segs.ensure(segs.size() + 1);
-            d_pos.ensure(n);
-            d_ids.ensure(n);
-            d_rows.ensure((size_t)n * s->D);
-            PCV_HIP(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, st));
-            PCV_HIP(hipMemcpyAsync(d_pos.p, positions, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
-            launch_gather_rows(st, d_segs.p, (int)segs.size(), d_pos.p, n, s->D, s->D4, d_rows.p, d_ids.p);
-            PCV_HIP(hipMemcpyAsync(out_rows, d_rows.p, (size_t)n * s->D * sizeof(float), hipMemcpyDeviceToHost, st));
-            if (out_ids)
-                PCV_HIP(hipMemcpyAsync(out_ids, d_ids.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            PCV_HIP(hipStreamSynchronize(st));
-        } catch (...) {
-            d_segs.release();
-            d_pos.release();
-            d_ids.release();
-            d_rows.release();
-            throw;
-        }
-        d_segs.release();
-        d_pos.release();
-        d_ids.release();
-        d_rows.release();
+        d_segs.ensure(segs.size() + 1);
+        d_pos.ensure(n);
+        d_ids.ensure(n);
+        d_rows.ensure((size_t)n * s->D);
+        PCV_HIP(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemcpyAsync(d_pos.p, positions, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        launch_gather_rows(st, d_segs.p, (int)segs.size(), d_pos.p, n, s->D, s->D4, d_rows.p, d_ids.p);
+        PCV_HIP(hipMemcpyAsync(out_rows, d_rows.p, (size_t)n * s->D * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (out_ids) PCV_HIP(hipMemcpyAsync(out_ids, d_ids.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
     });
 }
 
@@ -3181,25 +3114,15 @@ static pcv_status similarity(pcv_ctx* ctx, const float* a, int B, const float* m
         PCV_REQUIRE(B > 0 && N > 0 && dim > 0, "similarity: empty input");
         PCV_HIP(hipSetDevice(ctx->device));
         DevBuf<float> d_a, d_m, d_o;
-        try {
-            d_a.ensure((size_t)B * dim);
-            d_m.ensure((size_t)N * dim);
-            d_o.ensure((size_t)B * N);
-            PCV_HIP(hipMemcpyAsync(d_a.p, a, (size_t)B * dim * 4, hipMemcpyHostToDevice, ctx->stream));
-            PCV_HIP(hipMemcpyAsync(d_m.p, m, (size_t)N * dim * 4, hipMemcpyHostToDevice, ctx->stream));
-            launch_similarity_matrix(ctx->stream, d_a.p, B, d_m.p, N, dim, cosine, d_o.p);
-            PCV_HIP(hipMemcpyAsync(out, d_o.p, (size_t)B * N * 4, hipMemcpyDeviceToHost, ctx->stream));
-            PCV_HIP(hipStreamSynchronize(ctx->stream));
-            PCV_HIP(hipGetLastError());
-        } catch (...) {
-            d_a.release();
-            d_m.release();
-            d_o.release();
-            throw;
-        }
-        d_a.release();
-        d_m.release();
-        d_o.release();
+        d_a.ensure((size_t)B * dim);
+        d_m.ensure((size_t)N * dim);
+        d_o.ensure((size_t)B * N);
+        PCV_HIP(hipMemcpyAsync(d_a.p, a, (size_t)B * dim * 4, hipMemcpyHostToDevice, ctx->stream));
+        PCV_HIP(hipMemcpyAsync(d_m.p, m, (size_t)N * dim * 4, hipMemcpyHostToDevice, ctx->stream));
+        launch_similarity_matrix(ctx->stream, d_a.p, B, d_m.p, N, dim, cosine, d_o.p);
+        PCV_HIP(hipMemcpyAsync(out, d_o.p, (size_t)B * N * 4, hipMemcpyDeviceToHost, ctx->stream));
+        PCV_HIP(hipStreamSynchronize(ctx->stream));
+        PCV_HIP(hipGetLastError());
     });
 }
 
