@@ -100,6 +100,24 @@ private:
     pcv_comm* h_ = nullptr;
 };
 
+// `perceive search --like <id>` (cmd/search.rs:64-86) on a searcher or a view handle: the stored embedding of `item_id` is the
+// query (pcv_searcher_search_like); nullopt when no row carries the id ("Item not found", cmd/search.rs:83).
+inline std::optional<std::vector<SearchItem>> search_like_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results,
+                                                                 int64_t item_id, bool exclude) {
+    const int64_t offsets[2] = {0, 1}, no_source = 0;
+    std::vector<int64_t> ids(num_results);
+    std::vector<float> scores(num_results);
+    int count = 0;
+    uint8_t found = 0;
+    // (an empty filter matches nothing, like `sources.contains(..)`: the pointer stays non-NULL)
+    check(pcv_searcher_search_like(h, &item_id, nullptr, offsets, 1, sources.empty() ? &no_source : sources.data(), (int)sources.size(),
+                                   (int)num_results, exclude ? 1 : 0, ids.data(), scores.data(), &count, &found));
+    if (!found) return std::nullopt;
+    std::vector<SearchItem> out;
+    for (int i = 0; i < count; ++i) out.push_back({ids[i], scores[i]});
+    return out;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -133,6 +151,11 @@ public:
         std::vector<SearchItem> out;
         for (int i = 0; i < count; ++i) out.push_back({ids[i], scores[i]});
         return out;
+    }
+    // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
+    std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
+                                                       bool exclude = false) const {
+        return search_like_handle(h_, sources, num_results, item_id, exclude);
     }
     int64_t num_rows() const {
         int64_t n = 0;
@@ -207,6 +230,12 @@ public:
         std::vector<SearchItem> out;
         for (int i = 0; i < count; ++i) out.push_back({ids[i], scores[i]});
         return out;
+    }
+    // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the
+    // item itself is the first hit unless `exclude`.  nullopt: no row carries the id.
+    std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
+                                                       bool exclude = false) const {
+        return search_like_handle(h_, sources, num_results, item_id, exclude);
     }
     // search_vector over every rank's shard: a collective, same arguments on all ranks; this rank's rows
     // start at global position `set_shard_offset`

@@ -358,6 +358,44 @@ pcv_status pcv_searcher_search(pcv_searcher* s, const float* queries, int n_quer
                                const int64_t* source_ids, int n_sources, int k, int64_t* out_ids,
                                float* out_scores, int* out_counts);
 
+/* Search by example (`perceive search --like <id>`, perceive-cli/cmd/search.rs:17-19, 64-86: the stored embedding of an item is
+ * the query): query vectors are built on the device from rows the searcher already holds, found by item id.
+ * Query q is built from the examples example_ids[offsets[q] .. offsets[q+1]) with the weights weights[...] (NULL: all 1);
+ * offsets has n_queries + 1 entries, ascending from 0.
+ *   - members: the members of a query are all rows carrying one of its example ids, in every source, explicit-id and implicit-id
+ *     segments alike (ids == NULL rows: id0 + row).  Rows staged under PCV_STAGING_SOURCE are left out.  Hidden rows count (their
+ *     f32 row is still stored).  An id listed twice in a group counts twice; the same id may appear in several groups;
+ *   - vector: component c of query q is the f32 value of acc = fmaf(w_i, x_r[c], acc), starting from zero, over the examples i in
+ *     the order given and, within an example, over that item's rows r in ascending global position; x is the stored f32 row, the
+ *     value pcv_searcher_get_rows returns.  The order is part of the contract: one example of weight 1 with one row reproduces that
+ *     row bit for bit (the sum starts from the zero that keeps the sign of a zero product, -0), and the same call gives the same
+ *     bits every time.  Nothing is normalised: under PCV_METRIC_DOT one example gives exactly the reference's --like query;
+ *   - not found: an example id that no row carries sets out_found[i] = 0 and contributes nothing; a query without any member is
+ *     the zero vector (+0) in like_queries, and has count 0, ids -1 and NaN scores in search_like.  Neither is an error;
+ *   - outputs of like_queries, each may be NULL: out_queries host [n_queries][dim], d_out_queries device [n_queries][dim] (both
+ *     complete when the call returns), out_found [offsets[n_queries]], out_member_rows [n_queries] rows that went into each query;
+ *   - search: search_like returns exactly what pcv_searcher_search returns for the vectors like_queries builds — same source
+ *     filter, metric, order, ties, exactness, any k —, on host arrays shaped like pcv_searcher_search's outputs;
+ *   - exclusion: with exclude_examples != 0 no row carrying one of query q's OWN example ids is a result of query q; the result is
+ *     the exact top-k of the remaining rows (counts below k only when fewer remain) and does not depend on how it is computed:
+ *     the call searches k + m, m = the most rows any query's example ids are carried by, and drops them by id — at most m rows of
+ *     a query are dropped, and num_results is not limited.  exclude_examples == 0 is the reference's behaviour (the item itself is
+ *     hit 1).  k + m may not pass 2^24;
+ *   - views: both calls take a view.  The examples are looked up in the view's PARENT (an example need not be among the allowed
+ *     items); the search runs over the view;
+ *   - state: a finalized searcher (PCV_ERR_INVALID with pending rows) and no queued pass, as hide_ids.  NULL s, NULL offsets,
+ *     NULL example_ids with examples, n_queries < 0, offsets[0] != 0, descending offsets or a non-finite weight give
+ *     PCV_ERR_INVALID before anything touches the device.  n_queries == 0 succeeds and writes nothing;
+ *   - read-only: rows, copies, the hidden set and the mid-copy statistics are as they were, apart from what a search books;
+ *     pcv_searcher_last_stats afterwards describes the search of search_like.
+ * A sharded host: an example lives on one rank; like_queries on each rank yields that rank's partial sums (no collective form). */
+pcv_status pcv_searcher_like_queries(pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets,
+                                     int n_queries, float* out_queries, void* d_out_queries, uint8_t* out_found,
+                                     int64_t* out_member_rows);
+pcv_status pcv_searcher_search_like(pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets,
+                                    int n_queries, const int64_t* source_ids, int n_sources, int k, int exclude_examples,
+                                    int64_t* out_ids, float* out_scores, int* out_counts, uint8_t* out_found);
+
 /* One entry of a per-shard result list, the unit exchanged between GPUs (all-gather payload). */
 typedef struct pcv_hit {
     double score;  /* canonical f64 score (cosine or dot)                 */

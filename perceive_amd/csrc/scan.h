@@ -288,6 +288,16 @@ void launch_synth_fill(hipStream_t st, float4* blk, uint32_t nrows, uint32_t row
                        int64_t first_row, int normalize, uint32_t n_clusters, float noise, float amp_lo = 0.0f, float amp_hi = 0.0f);
 void launch_gather_rows(hipStream_t st, const SegDesc* d_segs, int nseg, const int64_t* d_pos, int64_t n, int D,
                         int D4, float* out_rows, int64_t* out_ids);
+// ---- search by example (pcv_searcher_like_queries) ----
+// One stored row that goes into a query vector, with its weight: row `row` of segs[seg].
+struct LikeMember {
+    uint32_t seg, row;
+    float w;
+};
+// out[q][0..D) (row-major f32, device) = sum over members[first[q] .. first[q + 1]) of w * row, accumulated per component with one
+// f32 fused multiply-add per member, in list order (first: [n_queries + 1], ascending from 0).  Same input, same bits.
+void launch_like_queries(hipStream_t st, const SegDesc* d_segs, int nseg, const LikeMember* d_members, const uint32_t* d_first,
+                         int n_queries, int D, int D4, float* out);
 // `p` is the host copy (shapes for the launch geometry), `dp` the same struct resident in device memory.
 void launch_upload(hipStream_t st, const void* src_pinned, void* dst, size_t bytes);  // pinned host -> device, on the compute queue
 void launch_prep_seed(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SegDesc& seg0);

@@ -14,6 +14,7 @@
 // exact top-k however stale tau is.  rescore_select ranks the few survivors per query in exact f64.
 // HBM traffic = one pass over the rows (+ one extra row read per coarse survivor).
 #include <algorithm>
+#include <cassert>
 #include <cstdlib>
 #include <numeric>
 #include <type_traits>
@@ -1134,6 +1135,36 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const SegDesc* __restr
     for (int j = 0; j < 4; ++j)
         if (f4 * 4 + j < D) out_rows[i * D + f4 * 4 + j] = vv[j];
     if (f4 == 0 && out_ids) out_ids[i] = id;
+}
+
+// Search by example (pcv_searcher_like_queries, DESIGN.md §3 "Search by example"): query q is the weighted sum of the stored f32
+// rows members[first[q] .. first[q + 1]), out[q][c] = the f32 value of acc = fmaf(w, x[c], acc) over the members IN THAT ORDER.
+// One thread owns one 16-byte piece of one query from the first member to the last: no atomics, no cross-lane reduction, so the
+// order and the bits are fixed.  acc starts at -0.0f, the additive identity that keeps the sign of a zero product: one member of
+// weight 1 gives back its row bit for bit.  A query without members is +0.  A member outside the table is a host bug: the
+// assert fails the launch loudly, and no row outside a segment is read.
+__global__ __launch_bounds__(64) void like_queries_kernel(const SegDesc* __restrict__ segs, int nseg,
+                                                          const LikeMember* __restrict__ members,
+                                                          const uint32_t* __restrict__ first, int D, int D4,
+                                                          float* __restrict__ out) {
+    const int q = blockIdx.x;
+    const int f4 = blockIdx.y * 64 + threadIdx.x;
+    if (f4 * 4 >= D) return;
+    const uint32_t m0 = first[q], m1 = first[q + 1];
+    float acc[4] = {-0.0f, -0.0f, -0.0f, -0.0f};
+    for (uint32_t m = m0; m < m1; ++m) {
+        const LikeMember e = members[m];
+        const bool inside = e.seg < (uint32_t)nseg && e.row < segs[e.seg].nrows;
+        assert(inside && "like_queries_kernel: member outside the segment table");
+        if (!inside) continue;  // (a build without asserts: still no read out of bounds)
+        const float4 v = segs[e.seg].blk[((size_t)(e.row >> 5) * D4 + f4) * 32 + (e.row & 31)];
+        acc[0] = __builtin_fmaf(e.w, v.x, acc[0]);
+        acc[1] = __builtin_fmaf(e.w, v.y, acc[1]);
+        acc[2] = __builtin_fmaf(e.w, v.z, acc[2]);
+        acc[3] = __builtin_fmaf(e.w, v.w, acc[3]);
+    }
+    for (int j = 0; j < 4; ++j)
+        if (f4 * 4 + j < D) out[(size_t)q * D + f4 * 4 + j] = m1 > m0 ? acc[j] : 0.0f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3470,6 +3501,15 @@ void launch_gather_rows(hipStream_t st, const SegDesc* d_segs, int nseg, const i
     if (n <= 0) return;
     const int64_t threads = n * ((D + 3) / 4);
     gather_rows_kernel<<<cdiv64(threads, 256), 256, 0, st>>>(d_segs, nseg, d_pos, n, D, D4, out_rows, out_ids);
+    PCV_LAUNCHED();
+}
+
+void launch_like_queries(hipStream_t st, const SegDesc* d_segs, int nseg, const LikeMember* d_members, const uint32_t* d_first,
+                         int n_queries, int D, int D4, float* out) {
+    if (n_queries <= 0) return;
+    PCV_REQUIRE(D > 0 && D <= D4 * 4, "like_queries: bad shape (dim %d, %d pieces)", D, D4);  // (grid.x takes any int of queries)
+    const dim3 grid((unsigned)n_queries, (unsigned)(((D + 3) / 4 + 63) / 64));
+    like_queries_kernel<<<grid, 64, 0, st>>>(d_segs, nseg, d_members, d_first, D, D4, out);
     PCV_LAUNCHED();
 }
 

@@ -2125,6 +2125,138 @@ void sync_view(pcv_searcher* v) {
     v->view_refreshes += 1;
 }
 
+// ---- search by example (pcv_searcher_like_queries / _search_like; DESIGN.md §3 "Search by example") ----
+// What both entry points check before anything touches the searcher or the device; returns the number of examples.
+int64_t check_like_args(const pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets, int n_queries,
+                        const char* who) {
+    PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
+    PCV_REQUIRE(n_queries >= 0, "%s: n_queries < 0", who);
+    PCV_REQUIRE(offsets != nullptr, "%s: offsets is NULL", who);
+    PCV_REQUIRE(offsets[0] == 0, "%s: offsets[0] must be 0", who);
+    for (int q = 0; q < n_queries; ++q)
+        PCV_REQUIRE(offsets[q + 1] >= offsets[q], "%s: offsets are not ascending (offsets[%d] < offsets[%d])", who, q + 1, q);
+    const int64_t n = offsets[n_queries];
+    PCV_REQUIRE(n <= 0x7fffffff, "%s: %lld examples in one call", who, (long long)n);
+    PCV_REQUIRE(example_ids != nullptr || n == 0, "%s: example ids NULL with %lld examples", who, (long long)n);
+    if (weights)
+        for (int64_t i = 0; i < n; ++i) PCV_REQUIRE(std::isfinite(weights[i]), "%s: weight %lld is not finite", who, (long long)i);
+    return n;
+}
+
+// The searcher the examples are looked up in (a view: its parent — an example need not be among the allowed items), locked, in
+// the state both calls need.  The caller holds s->mu and has brought a view up to date.
+std::unique_lock<std::mutex> lock_like_owner(pcv_searcher* s, pcv_searcher*& owner, const char* who) {
+    PCV_REQUIRE(!s->pending.active, "%s: a queued pass has not been collected", who);
+    owner = s->view_parent ? s->view_parent : s;
+    std::unique_lock<std::mutex> lk;
+    if (owner != s) lk = std::unique_lock<std::mutex>(owner->mu);
+    PCV_REQUIRE(!owner->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
+    PCV_REQUIRE(!owner->pending.active, "%s: a queued pass has not been collected", who);
+    return lk;
+}
+
+// What the lookup of a call's examples gives back to the host.
+struct LikeBuilt {
+    std::vector<float> vectors;         // [n_queries][D], if asked for
+    std::vector<int64_t> member_rows;   // [n_queries] rows that went into each query
+    std::vector<int64_t> carrier_rows;  // [n_queries] ... plus the rows staged under PCV_STAGING_SOURCE that carry one of its ids
+    std::vector<uint8_t> found;         // [examples]
+};
+
+// Query vectors from stored items (p->mu held, p no view): the distinct ids of the call are looked up once in every segment
+// (find_slots: an id column is streamed against the batch's table, implicit ids are arithmetic), each id's rows listed in
+// ascending global position, the lists expanded per query in the order the examples were given, and like_queries_kernel sums
+// the rows.  Reads rows and ids only.
+void build_like_queries(pcv_searcher* p, const int64_t* example_ids, const float* weights, const int64_t* offsets, int n_queries,
+                        bool want_host, void* d_out, LikeBuilt& out) {
+    const int64_t n = offsets[n_queries];
+    out.member_rows.assign((size_t)n_queries, 0);
+    out.carrier_rows.assign((size_t)n_queries, 0);
+    out.found.assign((size_t)n, 0);
+    if (want_host) out.vectors.assign((size_t)n_queries * p->D, 0.0f);
+    if (n_queries == 0) return;
+    PCV_HIP(hipSetDevice(p->ctx->device));
+    hipStream_t st = p->ctx->stream;
+    // 1. one slot per distinct id
+    std::vector<int64_t> uniq(example_ids, example_ids + n);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    std::vector<uint32_t> slot_of(uniq.size());
+    std::iota(slot_of.begin(), slot_of.end(), 0u);
+    // 2. the rows of every slot: (segment of the table, row), ascending in global position — sources and segments are walked in
+    //    the order assign_positions numbers them, rows ascending inside a segment
+    std::vector<SegDesc> segs;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> rows_of(uniq.size());
+    std::vector<int64_t> staged_of(uniq.size(), 0);
+    if (!uniq.empty()) {
+        IdBatch b;
+        b.ids = &uniq;
+        b.slots = &slot_of;
+        for (const auto& src : p->sources)
+            for (const auto& g : src.segs) {
+                if (g.nrows == 0) continue;
+                auto pr = find_slots(p, g, b);
+                if (pr.empty()) continue;
+                if (src.id == PCV_STAGING_SOURCE) {  // nobody's rows yet: no members, but a search that names the source may meet them
+                    for (const auto& x : pr) staged_of[x.first] += 1;
+                    continue;
+                }
+                std::sort(pr.begin(), pr.end(), [](const auto& a, const auto& c) { return a.second < c.second; });
+                PCV_REQUIRE(segs.size() < 0x7fffffffu, "like_queries: too many segments");
+                const uint32_t si = (uint32_t)segs.size();
+                SegDesc d{};  // (like_queries_kernel reads the rows and their number; no copy is involved)
+                d.blk = g.blk;
+                d.scale = g.scale;
+                d.ids = g.ids;
+                d.id0 = g.id0;
+                d.pos0 = g.pos0;
+                d.nrows = g.nrows;
+                d.nblocks = g.nblocks();
+                segs.push_back(d);
+                for (const auto& x : pr) rows_of[x.first].push_back({si, x.second});
+            }
+    }
+    // 3. the member list, per query in the order given
+    std::vector<LikeMember> members;
+    std::vector<uint32_t> first((size_t)n_queries + 1, 0);
+    for (int q = 0; q < n_queries; ++q) {
+        for (int64_t i = offsets[q]; i < offsets[q + 1]; ++i) {
+            const size_t slot = (size_t)(std::lower_bound(uniq.begin(), uniq.end(), example_ids[i]) - uniq.begin());
+            const auto& rows = rows_of[slot];
+            out.found[(size_t)i] = rows.empty() ? 0 : 1;
+            out.carrier_rows[(size_t)q] += (int64_t)rows.size() + staged_of[slot];
+            PCV_REQUIRE(members.size() + rows.size() <= 0x7fffffffu, "like_queries: more than 2^31 member rows in one call");
+            for (const auto& r : rows) members.push_back(LikeMember{r.first, r.second, weights ? weights[i] : 1.0f});
+        }
+        first[(size_t)q + 1] = (uint32_t)members.size();
+        out.member_rows[(size_t)q] = (int64_t)(first[(size_t)q + 1] - first[(size_t)q]);
+    }
+    // 4. the sums
+    DevBuf<SegDesc> d_segs;
+    DevBuf<LikeMember> d_members;
+    DevBuf<uint32_t> d_first;
+    DevBuf<float> d_vec;
+    try {
+        d_segs.ensure(segs.size() + 1);
+        d_members.ensure(members.size() + 1);
+        d_first.ensure(first.size());
+        d_vec.ensure((size_t)n_queries * p->D);
+        if (!segs.empty()) PCV_HIP(hipMemcpyAsync(d_segs.p, segs.data(), segs.size() * sizeof(SegDesc), hipMemcpyHostToDevice, st));
+        if (!members.empty())
+            PCV_HIP(hipMemcpyAsync(d_members.p, members.data(), members.size() * sizeof(LikeMember), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemcpyAsync(d_first.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        launch_like_queries(st, d_segs.p, (int)segs.size(), d_members.p, d_first.p, n_queries, p->D, p->D4, d_vec.p);
+        const size_t bytes = (size_t)n_queries * p->D * sizeof(float);
+        if (want_host) PCV_HIP(hipMemcpyAsync(out.vectors.data(), d_vec.p, bytes, hipMemcpyDeviceToHost, st));
+        if (d_out) PCV_HIP(hipMemcpyAsync(d_out, d_vec.p, bytes, hipMemcpyDeviceToDevice, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+    } catch (...) {
+        (void)hipStreamSynchronize(st);  // (before the buffers queued work may still read are freed)
+        throw;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -2743,6 +2875,80 @@ pcv_status pcv_searcher_search(pcv_searcher* s, const float* queries, int n_quer
         std::vector<pcv_hit_dev> hits;
         search_hits(s, queries, n_queries, source_ids, n_sources, k, hits);
         hits_to_outputs(s->metric, s->D, hits.data(), n_queries, k, out_ids, out_scores, out_counts);
+    });
+}
+
+pcv_status pcv_searcher_like_queries(pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets,
+                                     int n_queries, float* out_queries, void* d_out_queries, uint8_t* out_found,
+                                     int64_t* out_member_rows) {
+    return guarded([&] {
+        const int64_t n = check_like_args(s, example_ids, weights, offsets, n_queries, "like_queries");
+        std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
+        pcv_searcher* owner = nullptr;
+        const auto owner_lock = lock_like_owner(s, owner, "like_queries");
+        LikeBuilt built;
+        build_like_queries(owner, example_ids, weights, offsets, n_queries, out_queries != nullptr, d_out_queries, built);
+        if (out_queries && n_queries > 0) std::memcpy(out_queries, built.vectors.data(), built.vectors.size() * sizeof(float));
+        if (out_found && n > 0) std::memcpy(out_found, built.found.data(), (size_t)n);
+        if (out_member_rows && n_queries > 0) std::memcpy(out_member_rows, built.member_rows.data(), (size_t)n_queries * sizeof(int64_t));
+    });
+}
+
+pcv_status pcv_searcher_search_like(pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets,
+                                    int n_queries, const int64_t* source_ids, int n_sources, int k, int exclude_examples,
+                                    int64_t* out_ids, float* out_scores, int* out_counts, uint8_t* out_found) {
+    return guarded([&] {
+        const int64_t n = check_like_args(s, example_ids, weights, offsets, n_queries, "search_like");
+        PCV_REQUIRE(k > 0 && k <= (1 << 24), "search_like: num_results %d outside [1,%d]", k, 1 << 24);
+        std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
+        LikeBuilt built;
+        {
+            pcv_searcher* owner = nullptr;
+            const auto owner_lock = lock_like_owner(s, owner, "search_like");
+            build_like_queries(owner, example_ids, weights, offsets, n_queries, true, nullptr, built);
+        }
+        if (out_found && n > 0) std::memcpy(out_found, built.found.data(), (size_t)n);
+        if (n_queries == 0) return;
+        // Exclusion: at most carrier_rows[q] rows carry one of q's example ids, so the first k + max_q carrier_rows[q] hits hold
+        // the k best of the others — exact whatever the surplus, since num_results is not limited.
+        int64_t spare = 0;
+        bool any = false;
+        for (int q = 0; q < n_queries; ++q) {
+            any = any || built.member_rows[(size_t)q] > 0;
+            if (exclude_examples) spare = std::max(spare, built.carrier_rows[(size_t)q]);
+        }
+        PCV_REQUIRE((int64_t)k + spare <= (1 << 24), "search_like: num_results %d plus %lld example rows to leave out is more than %d", k,
+                    (long long)spare, 1 << 24);
+        const int kk = k + (int)spare;
+        const pcv_hit_dev none{NAN, -1, -1};
+        std::vector<pcv_hit_dev> hits;
+        if (any)
+            search_hits(s, built.vectors.data(), n_queries, source_ids, n_sources, kk, hits);
+        else {  // no query has a member: nothing to search for
+            PCV_REQUIRE(!s->dirty, "search_like: rows were added or cleared without pcv_searcher_finalize");
+            hits.assign((size_t)n_queries * kk, none);
+            s->stats = pcv_scan_stats{};
+        }
+        std::vector<pcv_hit_dev> kept((size_t)n_queries * k, none);
+        std::vector<int64_t> own;
+        for (int q = 0; q < n_queries; ++q) {
+            if (built.member_rows[(size_t)q] == 0) continue;  // a query without members has no results
+            own.clear();
+            if (exclude_examples) {
+                own.assign(example_ids + offsets[q], example_ids + offsets[q + 1]);
+                std::sort(own.begin(), own.end());
+            }
+            int at = 0;
+            for (int j = 0; j < kk && at < k; ++j) {
+                const pcv_hit_dev& h = hits[(size_t)q * kk + j];
+                if (h.pos < 0) continue;
+                if (exclude_examples && std::binary_search(own.begin(), own.end(), h.id)) continue;
+                kept[(size_t)q * k + at++] = h;
+            }
+        }
+        hits_to_outputs(s->metric, s->D, kept.data(), n_queries, k, out_ids, out_scores, out_counts);
     });
 }
 

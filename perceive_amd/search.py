@@ -263,6 +263,74 @@ class Searcher:
         )
         return ids, scores, counts
 
+    # ---- search by example (pcv_searcher_like_queries / _search_like) ------------------------------
+    # `perceive search --like <id>` (cmd/search.rs:64-86): the query is the stored embedding of an item, or a weighted sum of
+    # several, built on the device from the rows this searcher holds.  A view looks the examples up in its parent.
+    @staticmethod
+    def _like_args(groups, weights):
+        """groups: a list of id lists, one per query; weights: None (all 1), or the same shape, or flat over all examples.
+        -> (ids int64 [n], weights f32 [n] or None, offsets int64 [len(groups) + 1])"""
+        groups = [np.asarray(g, dtype=np.int64).reshape(-1) for g in groups]
+        offsets = np.zeros(len(groups) + 1, dtype=np.int64)
+        if groups:
+            np.cumsum([g.size for g in groups], out=offsets[1:])
+        ids = np.ascontiguousarray(np.concatenate(groups) if groups else np.zeros(0, dtype=np.int64), dtype=np.int64)
+        w = None
+        if weights is not None:
+            if len(weights) == len(groups) and all(np.ndim(x) == 1 for x in weights):
+                weights = np.concatenate([np.asarray(x, dtype=np.float32) for x in weights]) if groups else []
+            w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            if w.size != ids.size:
+                raise ValueError(f"{w.size} weights for {ids.size} examples")
+        return ids, w, offsets
+
+    def like_queries(self, groups, weights=None, d_out=None):
+        """Query vectors made from stored items: query q is sum_i weights[q][i] * (rows carrying groups[q][i]), accumulated in f32
+        in the order given (one id of weight 1 with one row: that row, bit for bit).  Returns (vectors [B, dim] f32, found
+        bool [examples], member_rows int64 [B]); an id no row carries has found False and adds nothing.  d_out: a device
+        address that receives the same [B, dim] f32 as well."""
+        ids, w, offsets = self._like_args(groups, weights)
+        B = offsets.size - 1
+        vec = np.zeros((B, self.dim), dtype=np.float32)
+        found = np.zeros(max(ids.size, 1), dtype=np.uint8)
+        members = np.zeros(max(B, 1), dtype=np.int64)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_like_queries(
+                self._handle, _ffi.i64p(ids) if ids.size else None, _ffi.f32p(w) if w is not None and w.size else None,
+                _ffi.i64p(offsets), B, _ffi.f32p(vec) if B else None, C.c_void_p(d_out) if d_out else None, _ffi.u8p(found),
+                _ffi.i64p(members),
+            )
+        )
+        return vec, found[: ids.size].astype(bool), members[:B]
+
+    def search_like(self, sources, num_results, groups, weights=None, exclude_examples=True):
+        """search_vectors with the vectors like_queries builds, in one call.  exclude_examples: no row carrying one of a
+        query's own example ids is a result of that query (the exact top-k of the rest).  Returns (ids [B,k], scores [B,k],
+        counts [B], found bool [examples]); a query none of whose examples exists has count 0."""
+        ids_in, w, offsets = self._like_args(groups, weights)
+        B, k = offsets.size - 1, int(num_results)
+        ids = np.full((B, k), -1, dtype=np.int64)
+        scores = np.full((B, k), np.nan, dtype=np.float32)
+        counts = np.zeros(max(B, 1), dtype=np.int32)
+        found = np.zeros(max(ids_in.size, 1), dtype=np.uint8)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_like(
+                self._handle, _ffi.i64p(ids_in) if ids_in.size else None, _ffi.f32p(w) if w is not None and w.size else None,
+                _ffi.i64p(offsets), B, src, nsrc, k, 1 if exclude_examples else 0, _ffi.i64p(ids), _ffi.f32p(scores),
+                _ffi.i32p(counts), _ffi.u8p(found),
+            )
+        )
+        return ids, scores, counts[:B], found[: ids_in.size].astype(bool)
+
+    def search_like_item(self, sources, num_results, item_id, exclude=False):
+        """`perceive search --like <id>` (cmd/search.rs:64-86): search with the stored embedding of `item_id`; as there, the item
+        itself is the first hit unless `exclude`.  KeyError("Item not found") when no row carries the id (cmd/search.rs:83)."""
+        ids, scores, counts, found = self.search_like(sources, num_results, [[int(item_id)]], exclude_examples=exclude)
+        if not found[0]:
+            raise KeyError("Item not found")
+        return [SearchItem(int(ids[0, j]), float(scores[0, j])) for j in range(int(counts[0]))]
+
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):
         _ffi.check(_ffi.lib().pcv_searcher_set_kernel(self._handle, _KERNELS[kernel]))
@@ -455,9 +523,10 @@ class Searcher:
 
 
 class SearcherView(Searcher):
-    """Searcher.view(item_ids): every search of Searcher (search_vector(s), search_device, the begin / end and sharded searches),
-    last_stats, num_rows, source_ids, source_num_rows and the kernel / tuning settings; what would change rows or copies
-    raises PcvError (status 1), as get_rows does.  Close it before its parent (the parent's close closes it)."""
+    """Searcher.view(item_ids): every search of Searcher (search_vector(s), search_device, the begin / end and sharded searches,
+    like_queries / search_like / search_like_item with the examples looked up in the parent), last_stats, num_rows,
+    source_ids, source_num_rows and the kernel / tuning settings; what would change rows or copies raises PcvError
+    (status 1), as get_rows does.  Close it before its parent (the parent's close closes it)."""
 
     def __init__(self, parent, handle):
         self.ctx, self.dim, self.metric = parent.ctx, parent.dim, parent.metric

@@ -276,6 +276,46 @@ impl Searcher {
         Ok(SearcherView { handle, _parent: PhantomData })
     }
 
+    /// `perceive search --like <id>` (cmd/search.rs:64-86): search with the stored embedding of `item_id`.  The reference reads
+    /// the blob from SQLite (`db.read_item_embedding`), deserializes it and calls `search_vector`; here the query is built on
+    /// the device from the row the index already holds, so nothing is fetched or uploaded.  As in the reference the item
+    /// itself is the first hit.  `None`: no row carries the id (cmd/search.rs:83 reports "Item not found").  The CLI's branch
+    /// becomes
+    ///     `searcher.search_like(&sources, args.num_results, id).ok_or_else(|| eyre!("Item not found"))?`
+    pub fn search_like(&self, sources: &[i64], num_results: usize, item_id: i64) -> Option<Vec<SearchItem>> {
+        if self.handle.is_null() || num_results == 0 {
+            return None;
+        }
+        let k = num_results;
+        let offsets: [i64; 2] = [0, 1];
+        let mut ids = vec![-1i64; k];
+        let mut scores = vec![f32::NAN; k];
+        let mut count: i32 = 0;
+        let mut found: u8 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_like(
+                self.handle,
+                &item_id,
+                ptr::null(),
+                offsets.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                k as i32,
+                0,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut count,
+                &mut found,
+            )
+        })
+        .expect("search_like failed");
+        if found == 0 {
+            return None;
+        }
+        Some((0..count as usize).map(|i| SearchItem { id: ids[i], score: scores[i] }).collect())
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
