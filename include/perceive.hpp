@@ -118,6 +118,24 @@ inline std::optional<std::vector<SearchItem>> search_like_handle(pcv_searcher* h
     return out;
 }
 
+// Range search on a searcher or a view handle (pcv_searcher_search_range): the items whose reported score passes `bound` (cosine:
+// score >= bound; Dot: distance <= bound), best first, at most max_results.  `more`, if given: more items are in range.
+inline std::vector<SearchItem> search_range_handle(pcv_searcher* h, const std::vector<int64_t>& sources, float bound, size_t max_results,
+                                                   const std::vector<float>& vector, bool* more) {
+    if (more) *more = false;
+    if (sources.empty() || max_results == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing (as the Rust twin)
+    std::vector<int64_t> ids(max_results);
+    std::vector<float> scores(max_results);
+    int64_t count = 0;
+    uint8_t m = 0;
+    check(pcv_searcher_search_range(h, vector.data(), 1, sources.data(), (int)sources.size(), &bound, (int64_t)max_results, ids.data(),
+                                    scores.data(), &count, &m));
+    if (more) *more = m != 0;
+    std::vector<SearchItem> out;
+    for (int64_t i = 0; i < count; ++i) out.push_back({ids[(size_t)i], scores[(size_t)i]});
+    return out;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -151,6 +169,11 @@ public:
         std::vector<SearchItem> out;
         for (int i = 0; i < count; ++i) out.push_back({ids[i], scores[i]});
         return out;
+    }
+    // every item of the view within a score bound (search_range_handle)
+    std::vector<SearchItem> search_range(const std::vector<int64_t>& sources, float bound, size_t max_results, const std::vector<float>& vector,
+                                         bool* more = nullptr) const {
+        return search_range_handle(h_, sources, bound, max_results, vector, more);
     }
     // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
     std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
@@ -230,6 +253,11 @@ public:
         std::vector<SearchItem> out;
         for (int i = 0; i < count; ++i) out.push_back({ids[i], scores[i]});
         return out;
+    }
+    // every item within a score bound instead of the best k (search_range_handle)
+    std::vector<SearchItem> search_range(const std::vector<int64_t>& sources, float bound, size_t max_results, const std::vector<float>& vector,
+                                         bool* more = nullptr) const {
+        return search_range_handle(h_, sources, bound, max_results, vector, more);
     }
     // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the
     // item itself is the first hit unless `exclude`.  nullopt: no row carries the id.

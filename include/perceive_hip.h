@@ -358,6 +358,38 @@ pcv_status pcv_searcher_search(pcv_searcher* s, const float* queries, int n_quer
                                const int64_t* source_ids, int n_sources, int k, int64_t* out_ids,
                                float* out_scores, int* out_counts);
 
+/* Range search: every item within a score bound, in one pass over the rows.
+ * Per query q with bound bounds[q], the in-range rows are the searchable rows (in the selected sources, not hidden, with a
+ * canonical score: as in pcv_searcher_search) whose REPORTED f32 score passes the test
+ *   COSINE : score >= bounds[q]        DOT : distance <= bounds[q]
+ * where the reported score is the value pcv_searcher_search would return for that row: (float)c for cosine, max(0, 1 - c/dim) in
+ * f32 for the dot metric, c the canonical f64 score.  Results are the in-range rows in the canonical order —
+ * descending c, ties -> lower global position —, at most max_results per query; out_more[q] is 1 exactly when more in-range rows
+ * exist than were returned.  This is what pcv_searcher_search returns with num_results = the number of searchable rows, cut after
+ * the last hit that passes the test: ids and scores agree bit for bit.
+ *   queries, source_ids, n_sources : as in pcv_searcher_search (NULL = all sources; an empty list matches nothing)
+ *   bounds       [n_queries]; infinite bounds are legal and mean everything or nothing; a negative DOT bound matches nothing
+ *   max_results  1 .. PCV_MAX_RANGE_ROWS
+ *   out_ids      [n_queries][max_results], -1 behind the results;  out_scores likewise, NaN behind them (may be NULL)
+ *   out_counts   [n_queries] results returned;  out_more [n_queries] (may be NULL)
+ * A NULL searcher, NULL queries, n_queries <= 0, NULL bounds, a NaN bound or max_results outside its range give PCV_ERR_INVALID
+ * before any device work; a searcher with pending rows fails as in pcv_searcher_search.
+ * The scan runs with thresholds that are fixed from the start (DESIGN.md §4 "Range search"), so a call costs one pass per group
+ * of queries — two if a candidate list was too short (pcv_scan_stats.overflow_reruns) — however many rows match; the settings of
+ * set_kernel, set_screening_copy, set_mid_copy, set_tuning and set_candidate_capacity hold, pcv_searcher_last_stats describes
+ * the call, and a view searches its own rows.  If the pass of a query lists more than PCV_MAX_RANGE_ROWS rows the call returns
+ * PCV_ERR_UNSUPPORTED, naming the query and the count, before any list of that size is allocated; the searcher stays usable.  For
+ * such a bound use pcv_searcher_search, which pages through the rows PCV_MAX_RESULTS at a time.
+ * Memory: the lists and the result block of a call grow with the rows its passes list — up to 0.4 GB on the device and 0.8 GB of
+ * pinned host memory for the widest bounds.  What exceeds 64 MB is released when the call returns; smaller blocks are kept for
+ * the next call.
+ * The sharded and device-list entry points (pcv_searcher_search_device*, pcv_searcher_search_sharded*, pcv_merge_topk*) exchange
+ * fixed-size lists and have no range form. */
+enum { PCV_MAX_RANGE_ROWS = 16777216 }; /* 2^24: the limit pcv_searcher_search already puts on num_results */
+pcv_status pcv_searcher_search_range(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                     const float* bounds, int64_t max_results, int64_t* out_ids, float* out_scores,
+                                     int64_t* out_counts, uint8_t* out_more);
+
 /* Search by example (`perceive search --like <id>`, perceive-cli/cmd/search.rs:17-19, 64-86: the stored embedding of an item is
  * the query): query vectors are built on the device from rows the searcher already holds, found by item id.
  * Query q is built from the examples example_ids[offsets[q] .. offsets[q+1]) with the weights weights[...] (NULL: all 1);

@@ -109,6 +109,15 @@ struct CeilRec {
     float lo, hi;
 };
 
+// A range pass (pcv_searcher_search_range; DESIGN.md §4 "Range search"): every row is of class 1 of a CeilRec (lo = -inf,
+// hi = +inf: listed, never raising a threshold), and the thresholds are fixed before the scan, one per query.
+//   bound : the caller's bound on the REPORTED f32 score (cosine: score >= bound; dot: distance <= bound)
+//   tau   : the canonical value of the bound in f32, rounded towards "keeps more": no in-range row has c < tau
+struct RangeRec {
+    float bound, tau;
+};
+constexpr int kRangeRun = 4096;  // survivors one workgroup of range_select_kernel scores and sorts in LDS
+
 // Everything one pass needs, resident in device memory (uploaded with the segment table and the
 // queries in ONE copy): the kernels index p.seg[] at run time, which a by-value kernel argument would
 // force through scratch memory.
@@ -183,6 +192,13 @@ struct ScanParams {
     float* spec_base_host;   // [128] pinned: median seed slot per query (NaN: none)
     float* spec_top_host;    // [128] pinned: best seed slot per query
     float* kth_host;         // [128] pinned: k-th best exact score per query (NaN: fewer than k hits)
+    // A range pass (RangeRec above; nullptr: a top-k pass).  range_select_kernel takes the place of rescore_select_kernel: the
+    // in-range rows of run r of query q (listed survivors [r * kRangeRun, +kRangeRun)) in canonical order.
+    const RangeRec* range;   // [B]
+    pcv_hit_dev* range_out;  // pinned host [B][range_runs][range_keep]: the first range_keep in-range rows of each run
+    uint32_t* range_cnt;     // pinned host [B][range_runs]: in-range rows of the run (not capped by range_keep)
+    uint32_t range_runs;     // runs per query the lists have room for: ceil(cand_cap / kRangeRun)
+    uint32_t range_keep;     // min(kRangeRun, max_results)
 };
 constexpr uint32_t kSpecFailed = 0xffffffffu;  // cnt_host value of a query whose speculative threshold did not hold
 
@@ -196,6 +212,17 @@ __host__ __device__ static inline float key_f32(uint32_t k) {
     return __builtin_bit_cast(float, u);
 }
 constexpr uint32_t kKeyNegInf = 0x007fffffu;  // f32_key(-inf)
+
+// The f32 score a result carries, from the canonical f64 score c (the reference's convention: cosine (float)c; dot: the distance
+// max(0, 1 - c/D), search.rs:275-277).  The one copy of this arithmetic: the top-k outputs, the range outputs and the in-range
+// test of range_select_kernel all call it, which is what makes a range result bit-for-bit a cut top-k result.
+__host__ __device__ static inline float reported_score(int metric, int D, double c) {
+    if (metric == PCV_METRIC_DOT) {
+        const double d = 1.0 - c / (double)D;
+        return (float)(d > 0.0 ? d : 0.0);
+    }
+    return (float)c;
+}
 
 // ---- launchers (scan_kernels.hip); they throw pcv::Error on a bad shape or a failed HIP call ----
 void launch_pack_rows(hipStream_t st, const float* rows_rowmajor, int64_t n, int D, int D4, float4* blk, uint32_t row0);
@@ -306,6 +333,9 @@ void launch_scan_mfma(hipStream_t st, const ScanParams& p, const ScanParams* dp,
 int mfma_pass_queries(int Dp);   // queries one MFMA pass can take at this padded dim (LDS-limited), 0 = none
 uint32_t mfma_tile_rows(int B);  // rows of the bf16 query tile the MFMA kernel stages for B queries
 void launch_rescore_select(hipStream_t st, const ScanParams& p, const ScanParams* dp);
+// ---- range search (pcv_searcher_search_range) ----
+void launch_range_thresholds(hipStream_t st, const ScanParams& p, const ScanParams* dp);  // RangeRec::tau -> tau, tau_c
+void launch_range_select(hipStream_t st, const ScanParams& p, const ScanParams* dp);
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);
 void launch_merge(hipStream_t st, const pcv_hit_dev* lists, int n_shards, int B, int k, pcv_hit_dev* out,
                   int flagged = 0);

@@ -1183,6 +1183,7 @@ __global__ __launch_bounds__(256) void reset_scan_state_kernel(uint32_t* __restr
         cand_cnt[t * kHot + 32] = 0;
         cand_cnt[t * kHot + 33] = 0;
         cand_cnt[t * kHot + 34] = 0;
+        cand_cnt[t * kHot + 35] = 0;  // (range_select_kernel: finished runs)
     }
 }
 
@@ -2384,7 +2385,11 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
             const int eq = (int)((ehi >> 5) & 0xffu);
             if constexpr (SIX) {
                 if (have) g_atomic_add(&p.cand_cnt[eq * kHot + 34], 1u);  // statistics: 6-bit survivors
-                have = have && __builtin_bit_cast(float, eacc) >= esb * __shfl(myT6, eq);
+                // (the shuffle by every lane, in front of the test: behind `have &&` the lanes without an entry sit it out, and a
+                // query whose T' lives on such a lane — the ring held fewer entries than that lane's number — reads 0 for it:
+                // harmless while thresholds are positive, rows lost under the negative or -inf thresholds of a range pass)
+                const float T6now = __shfl(myT6, eq);
+                have = have && __builtin_bit_cast(float, eacc) >= esb * T6now;
                 const int P16 = ((D4 * 4 + 127) & ~127) >> 4;
                 unsigned long long set = __ballot(have);
                 while (set) {  // the int8 rows of the entries left, eight at a time
@@ -3123,6 +3128,93 @@ __device__ __forceinline__ bool better(double sa, int64_t pa, double sb, int64_t
     return sa > sb || (sa == sb && pa < pb);
 }
 
+// canonical score from the two feature-order f64 sums (oracle/scan.c:orc_canonical_score); NaN: undefined
+__device__ __forceinline__ double finish_score(int metric, double dot, double nx, double nq) {
+    const double inf = __builtin_inf();
+    if (metric == PCV_METRIC_DOT) return (dot < inf && dot > -inf && nq < inf) ? dot : __builtin_nan("");
+    if (nq >= 0x1p-126 && nq < inf && nx >= 0x1p-126 && nx < inf) {
+        const double cc = dot / (sqrt(nq) * sqrt(nx));
+        if (cc < inf && cc > -inf) return cc;
+    }
+    return __builtin_nan("");
+}
+
+// Canonical f64 scores of listed survivors 0..ns) of one query, by a workgroup of 256 threads: entry(si) = (segment << 32) | row,
+// keep(si, entry, score) is called once per survivor, by one thread.  `sq`: the raw query in LDS; `stage`: COOP only, LDS room for
+// 4 waves x 8 rows of D4 + 1 pieces.  The two sums of a row run in feature order whatever the form, so the bits do not depend on
+// who asks: rescore_select_kernel and range_select_kernel rank by the same numbers.
+template <bool COOP, class Entry, class Keep>
+__device__ __forceinline__ void score_listed(const ScanParams& p, uint32_t ns, const float4* sq, float4* stage, double nq, int tid,
+                                             Entry&& entry, Keep&& keep) {
+    const int D4 = p.D4, lane = tid & 63, wave = tid >> 6;
+    if constexpr (COOP) {
+        float4* rows = stage + (size_t)wave * 8 * (D4 + 1);
+        const int slot = lane >> 3, part = lane & 7;
+        for (uint32_t g = wave * 8; g < ns; g += 32) {
+            const uint32_t si = g + slot;
+            const bool live = si < ns;
+            const uint64_t e = live ? entry(si) : 0;
+            if (live) {
+                const SegDesc& sg = p.seg[(int)(e >> 32)];
+                const uint32_t row = (uint32_t)e;
+                const float4* src = sg.blk + (size_t)(row >> 5) * D4 * 32 + (row & 31);
+                // eight pieces per lane requested before any is stored (a load-store loop runs at one
+                // memory round trip per piece)
+                for (int f0 = part; f0 < D4; f0 += 64) {
+                    float4 t[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) t[u] = f0 + 8 * u < D4 ? gld4(src + (size_t)(f0 + 8 * u) * 32) : make_float4(0, 0, 0, 0);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (f0 + 8 * u < D4) rows[slot * (D4 + 1) + f0 + 8 * u] = t[u];
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_s_waitcnt(0);  // the row pieces of this wave are in LDS
+            // the two feature-order chains of a row run on two lanes: part 0 sums q*x, part 1 sums x*x
+            // (one instruction stream: the multiplicand is selected, not branched on)
+            double chain = 0.0;
+            if (live && part < 2) {
+                const float4* r = rows + slot * (D4 + 1);
+#pragma unroll 8
+                for (int f4 = 0; f4 < D4; ++f4) {  // unrolled: the LDS reads run ahead of the dependent f64 chain
+                    const float4 v = r[f4];
+                    const float4 m = part == 0 ? sq[f4] : v;
+                    chain += (double)m.x * (double)v.x;
+                    chain += (double)m.y * (double)v.y;
+                    chain += (double)m.z * (double)v.z;
+                    chain += (double)m.w * (double)v.w;
+                }
+            }
+            const double nx = __shfl(chain, (lane & ~7) | 1);
+            if (live && part == 0) keep(si, e, finish_score(p.metric, chain, nx, nq));
+            __builtin_amdgcn_wave_barrier();
+        }
+    } else {
+        for (uint32_t si = tid; si < ns; si += 256) {
+            const uint64_t e = entry(si);
+            const SegDesc& sg = p.seg[(int)(e >> 32)];
+            const uint32_t row = (uint32_t)e;
+            const float4* src = sg.blk + (size_t)(row >> 5) * D4 * 32 + (row & 31);
+            double dot = 0.0, nx = 0.0;
+#pragma unroll 8
+            for (int f4 = 0; f4 < D4; ++f4) {
+                const float4 v = src[(size_t)f4 * 32];
+                const float4 qv = sq[f4];
+                dot += (double)qv.x * (double)v.x;
+                nx += (double)v.x * (double)v.x;
+                dot += (double)qv.y * (double)v.y;
+                nx += (double)v.y * (double)v.y;
+                dot += (double)qv.z * (double)v.z;
+                nx += (double)v.z * (double)v.z;
+                dot += (double)qv.w * (double)v.w;
+                nx += (double)v.w * (double)v.w;
+            }
+            keep(si, e, finish_score(p.metric, dot, nx, nq));
+        }
+    }
+}
+
 // Exact ranking of one query's survivors, one workgroup per query:
 //   1. keep the survivors the FINAL threshold still admits (rows emitted while tau was low);
 //   2. canonical score of each: f64, products exact, sums in feature order — the definition of
@@ -3154,7 +3246,7 @@ __global__ __launch_bounds__(256) void rescore_select_kernel(const ScanParams* _
     __shared__ uint32_t nsurv, n_valid, n_spec;  // n_spec: survivors certainly at or above the speculative threshold
     __shared__ double s_nq, t_s;  // canonical |q|^2; score of the admission threshold
     __shared__ int64_t t_p;       // ... and its position
-    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x, tid = threadIdx.x;
     const int D4 = p.D4;
     const uint32_t raw_cnt = ld_relaxed(&p.cand_cnt[q * kHot]);
     const uint32_t cnt = min(raw_cnt, p.cand_cap);
@@ -3186,15 +3278,6 @@ __global__ __launch_bounds__(256) void rescore_select_kernel(const ScanParams* _
         for (int i = 0; i < p.D; ++i) nq += (double)f[i] * (double)f[i];
         s_nq = nq;
     }
-    const double inf = __builtin_inf();
-    auto finish_score = [&](double dot, double nx, double nq) -> double {
-        if (p.metric == PCV_METRIC_DOT) return (dot < inf && dot > -inf && nq < inf) ? dot : __builtin_nan("");
-        if (nq >= 0x1p-126 && nq < inf && nx >= 0x1p-126 && nx < inf) {
-            const double cc = dot / (sqrt(nq) * sqrt(nx));
-            if (cc < inf && cc > -inf) return cc;
-        }
-        return __builtin_nan("");
-    };
     // the pass's ceiling for this query (scan.h, CeilRec): only rows that rank strictly after it count
     const double ceil_s = p.ceil ? p.ceil[q].score : __builtin_inf();
     const int64_t ceil_p = p.ceil ? p.ceil[q].pos : -1;
@@ -3249,72 +3332,8 @@ __global__ __launch_bounds__(256) void rescore_select_kernel(const ScanParams* _
         __syncthreads();  // nsurv is final; s_nq is there
         const uint32_t ns = nsurv;
         const double nq = s_nq;
-        if constexpr (COOP) {
-            float4* rows = lds4 + D4 + (size_t)wave * 8 * (D4 + 1);
-            const int slot = lane >> 3, part = lane & 7;
-            for (uint32_t g = wave * 8; g < ns; g += 32) {
-                const uint32_t si = g + slot;
-                const bool live = si < ns;
-                const uint64_t e = live ? surv[si] : 0;
-                if (live) {
-                    const SegDesc& sg = p.seg[(int)(e >> 32)];
-                    const uint32_t row = (uint32_t)e;
-                    const float4* src = sg.blk + (size_t)(row >> 5) * D4 * 32 + (row & 31);
-                    // eight pieces per lane requested before any is stored (a load-store loop runs at one
-                    // memory round trip per piece)
-                    for (int f0 = part; f0 < D4; f0 += 64) {
-                        float4 t[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) t[u] = f0 + 8 * u < D4 ? gld4(src + (size_t)(f0 + 8 * u) * 32) : make_float4(0, 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 8; ++u)
-                            if (f0 + 8 * u < D4) rows[slot * (D4 + 1) + f0 + 8 * u] = t[u];
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_s_waitcnt(0);  // the row pieces of this wave are in LDS
-                // the two feature-order chains of a row run on two lanes: part 0 sums q*x, part 1 sums x*x
-                // (one instruction stream: the multiplicand is selected, not branched on)
-                double chain = 0.0;
-                if (live && part < 2) {
-                    const float4* r = rows + slot * (D4 + 1);
-#pragma unroll 8
-                    for (int f4 = 0; f4 < D4; ++f4) {  // unrolled: the LDS reads run ahead of the dependent f64 chain
-                        const float4 v = r[f4];
-                        const float4 m = part == 0 ? sq[f4] : v;
-                        chain += (double)m.x * (double)v.x;
-                        chain += (double)m.y * (double)v.y;
-                        chain += (double)m.z * (double)v.z;
-                        chain += (double)m.w * (double)v.w;
-                    }
-                }
-                const double nx = __shfl(chain, (lane & ~7) | 1);
-                if (live && part == 0) keep(e, finish_score(chain, nx, nq));
-                __builtin_amdgcn_wave_barrier();
-            }
-        } else {
-            for (uint32_t si = tid; si < ns; si += 256) {
-                const uint64_t e = surv[si];
-                const SegDesc& sg = p.seg[(int)(e >> 32)];
-                const uint32_t row = (uint32_t)e;
-                const float4* src = sg.blk + (size_t)(row >> 5) * D4 * 32 + (row & 31);
-                double dot = 0.0, nx = 0.0;
-#pragma unroll 8
-                for (int f4 = 0; f4 < D4; ++f4) {
-                    const float4 v = src[(size_t)f4 * 32];
-                    const float4 qv = sq[f4];
-                    dot += (double)qv.x * (double)v.x;
-                    nx += (double)v.x * (double)v.x;
-                    dot += (double)qv.y * (double)v.y;
-                    nx += (double)v.y * (double)v.y;
-                    dot += (double)qv.z * (double)v.z;
-                    nx += (double)v.z * (double)v.z;
-                    dot += (double)qv.w * (double)v.w;
-                    nx += (double)v.w * (double)v.w;
-                }
-                keep(e, finish_score(dot, nx, nq));
-            }
-        }
+        score_listed<COOP>(p, ns, sq, lds4 + D4, nq, tid, [&](uint32_t si) { return surv[si]; },
+                           [&](uint32_t, uint64_t e, double score) { keep(e, score); });
         __syncthreads();
         if (tid == 0) nsurv = 0;
         __syncthreads();
@@ -3364,6 +3383,137 @@ __global__ __launch_bounds__(256) void rescore_select_kernel(const ScanParams* _
         st_relaxed(&p.cand_cnt[q * kHot], 0u);
     }
     for (int j = tid; j < p.k; j += 256) st_relaxed(&p.slots[(size_t)q * kMaxK + j], kKeyNegInf);
+}
+
+// ---- range search (pcv_searcher_search_range; DESIGN.md §4 "Range search") ----
+// The fixed thresholds of a range pass, in front of its scan: nothing raises them afterwards (every row is of class 1 of the
+// pass's CeilRec: no seed slot, no offer; the searcher sets no speculative threshold under a ceiling).
+__global__ __launch_bounds__(kMfmaQueries) void range_thresholds_kernel(const ScanParams* __restrict__ pp) {
+    const ScanParams& p = *pp;
+    const int q = threadIdx.x;
+    if (q >= p.B) return;
+    const uint32_t key = f32_key(p.range[q].tau);
+    st_relaxed(&p.tau[q * kHot], key);
+    st_relaxed(&p.tau_c[q], key);
+}
+
+// The last kernel of a range pass, one workgroup per (run, query): run r is the listed survivors [r * kRangeRun, +kRangeRun) of
+// the query's list.
+//   1. canonical f64 score of every survivor of the run (score_listed: rescore_select_kernel's numbers);
+//   2. the reported f32 score from it, as the host computes it for a top-k hit (cosine: (float)c; dot: max(0, 1 - c / D) in f64,
+//      then f32), and the in-range test on THAT: score >= bound / distance <= bound;
+//   3. the rows that pass collect in LDS — (c, position, place in the list): 20 bytes each, 80 KB for a run beside the query and
+//      the row staging of score_listed, inside the 160 KB of a CU — and are sorted there: bitonic network over the next power of
+//      two, padded with entries that sort last; order: c descending, ties -> lower global position (positions are unique);
+//   4. the first range_keep of them go straight to pinned host memory with the run's in-range count; the host merges the runs of
+//      a query (searcher.cpp: search_range);
+//   5. the workgroup that finishes last for its query reports the uncapped survivor count and the screens' statistics and
+//      leaves the query's scan state clean for the next pass (cand_cnt word 35 counts the finished runs).
+template <bool COOP>
+__global__ __launch_bounds__(256) void range_select_kernel(const ScanParams* __restrict__ pp) {
+    const ScanParams& p = *pp;
+    extern __shared__ float4 lds4[];  // [D4] raw query | COOP: 4 waves x 8 x (D4+1) row pieces | c_s, c_p, c_i [kRangeRun]
+    __shared__ uint32_t n_in, s_last;
+    __shared__ double s_nq;
+    const int q = blockIdx.y, tid = threadIdx.x;
+    const uint32_t run = blockIdx.x;
+    const int D4 = p.D4;
+    float4* sq = lds4;
+    float4* stage = lds4 + D4;
+    double* c_s = (double*)(stage + (COOP ? 4 * 8 * (D4 + 1) : 0));
+    int64_t* c_p = (int64_t*)(c_s + kRangeRun);
+    uint32_t* c_i = (uint32_t*)(c_p + kRangeRun);
+    const uint32_t raw_cnt = ld_relaxed(&p.cand_cnt[q * kHot]);
+    const uint32_t cnt = min(raw_cnt, p.cand_cap);
+    const uint32_t base = run * (uint32_t)kRangeRun;  // (run < range_runs = ceil(cand_cap / kRangeRun): no overflow)
+    const uint32_t ns = base < cnt ? min(cnt - base, (uint32_t)kRangeRun) : 0u;
+    const uint64_t* cand = p.cand + (size_t)q * p.cand_cap + base;
+    if (tid == 0) n_in = 0;
+    uint32_t n = 0;
+    if (ns > 0) {  // (same in every thread)
+        for (int i = tid; i < D4; i += 256) sq[i] = ((const float4*)(p.qraw + (size_t)q * D4 * 4))[i];
+        __syncthreads();
+        if (tid == 255) {  // canonical |q|^2: f64, feature order
+            double nq = 0.0;
+            const float* f = (const float*)sq;
+#pragma unroll 16
+            for (int i = 0; i < p.D; ++i) nq += (double)f[i] * (double)f[i];
+            s_nq = nq;
+        }
+        __syncthreads();
+        const float bound = p.range[q].bound;
+        score_listed<COOP>(p, ns, sq, stage, s_nq, tid, [&](uint32_t si) { return gld(&cand[si]); },
+                           [&](uint32_t si, uint64_t e, double score) {
+                               if (!(score == score)) return;  // NaN: undefined score
+                               const float rep = reported_score(p.metric, p.D, score);
+                               if (!(p.metric == PCV_METRIC_DOT ? rep <= bound : rep >= bound)) return;
+                               const uint32_t slot = atomicAdd(&n_in, 1u);  // < kRangeRun: one per survivor of the run
+                               c_s[slot] = score;
+                               c_p[slot] = p.seg[(int)(e >> 32)].pos0 + (int64_t)(uint32_t)e;
+                               c_i[slot] = si;
+                           });
+        __syncthreads();
+        n = n_in;
+        uint32_t np2 = 1;
+        while (np2 < n) np2 <<= 1;
+        for (uint32_t i = n + tid; i < np2; i += 256) {  // padding: sorts after every row
+            c_s[i] = -__builtin_inf();
+            c_p[i] = INT64_MAX;
+            c_i[i] = 0;
+        }
+        __syncthreads();
+        for (uint32_t k = 2; k <= np2; k <<= 1) {
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                for (uint32_t t = tid; t < (np2 >> 1); t += 256) {
+                    const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
+                    const double si = c_s[i], sl = c_s[l];
+                    const int64_t pi = c_p[i], pl = c_p[l];
+                    const bool swap = (i & k) == 0 ? better(sl, pl, si, pi) : better(si, pi, sl, pl);
+                    if (swap) {
+                        c_s[i] = sl;
+                        c_s[l] = si;
+                        c_p[i] = pl;
+                        c_p[l] = pi;
+                        const uint32_t ii = c_i[i];
+                        c_i[i] = c_i[l];
+                        c_i[l] = ii;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        pcv_hit_dev* out = p.range_out + ((size_t)q * p.range_runs + run) * p.range_keep;
+        for (uint32_t r = tid; r < min(n, p.range_keep); r += 256) {
+            const uint64_t e = gld(&cand[c_i[r]]);
+            const SegDesc& sg = p.seg[(int)(e >> 32)];
+            const uint32_t row = (uint32_t)e;
+            pcv_hit_dev hit;
+            hit.score = c_s[r];
+            hit.pos = c_p[r];
+            hit.id = sg.ids ? sg.ids[row] : sg.id0 + (int64_t)row;
+            out[r] = hit;
+        }
+    }
+    if (tid == 0) p.range_cnt[(size_t)q * p.range_runs + run] = n;
+    __syncthreads();  // every thread has its raw_cnt; the run's results are on their way
+    if (tid == 0) s_last = g_atomic_add(&p.cand_cnt[q * kHot + 35], 1u) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (s_last && tid == 0) {  // every run of this query has read the list's length: count, statistics, clean state
+        if (p.cnt_host) p.cnt_host[q] = raw_cnt;
+        if (p.coarse_host) {
+            p.coarse_host[q] = ld_relaxed(&p.cand_cnt[q * kHot + 32]);
+            p.coarse_host[kMfmaQueries + q] = ld_relaxed(&p.cand_cnt[q * kHot + 33]);
+            p.coarse_host[2 * kMfmaQueries + q] = ld_relaxed(&p.cand_cnt[q * kHot + 34]);
+        }
+        st_relaxed(&p.cand_cnt[q * kHot + 32], 0u);
+        st_relaxed(&p.cand_cnt[q * kHot + 33], 0u);
+        st_relaxed(&p.cand_cnt[q * kHot + 34], 0u);
+        st_relaxed(&p.cand_cnt[q * kHot + 35], 0u);
+        st_relaxed(&p.tau[q * kHot], kKeyNegInf);
+        st_relaxed(&p.tau_c[q], kKeyNegInf);
+        st_relaxed(&p.cand_cnt[q * kHot], 0u);
+        for (int j = 0; j < p.k; ++j) st_relaxed(&p.slots[(size_t)q * kMaxK + j], kKeyNegInf);
+    }
 }
 
 // merge of per-shard top-k lists after the all-gather: [n_shards][B][k] -> [B][k]; shards are `stride`
@@ -3948,6 +4098,31 @@ void launch_rescore_select(hipStream_t st, const ScanParams& p, const ScanParams
     } else {
         const size_t lds = (size_t)p.D4 * sizeof(float4);
         rescore_select_kernel<false><<<p.B, 256, lds, st>>>(dp);
+    }
+    PCV_LAUNCHED();
+}
+
+void launch_range_thresholds(hipStream_t st, const ScanParams& p, const ScanParams* dp) {
+    PCV_REQUIRE(p.range != nullptr && p.B <= kMfmaQueries, "range pass: no bounds, or %d queries", p.B);
+    range_thresholds_kernel<<<1, kMfmaQueries, 0, st>>>(dp);
+    PCV_LAUNCHED();
+}
+
+void launch_range_select(hipStream_t st, const ScanParams& p, const ScanParams* dp) {
+    const bool coop = p.D4 <= kCoopMaxD4;
+    const size_t lds = ((size_t)p.D4 + (coop ? 4 * 8 * ((size_t)p.D4 + 1) : 0)) * sizeof(float4) +
+                       (size_t)kRangeRun * (sizeof(double) + sizeof(int64_t) + sizeof(uint32_t));
+    PCV_REQUIRE(p.range != nullptr && p.range_out != nullptr && p.range_cnt != nullptr && p.range_runs > 0 && p.range_keep > 0 &&
+                    p.range_keep <= (uint32_t)kRangeRun && (uint64_t)p.range_runs * kRangeRun >= p.cand_cap,
+                "range pass: bad result layout (%u runs of %u for lists of %u)", p.range_runs, p.range_keep, p.cand_cap);
+    if (lds > 158 * 1024) PCV_FAIL(PCV_ERR_UNSUPPORTED, "search_range: dimension %d is too large for the LDS sort", p.D);
+    const dim3 grid(p.range_runs, (unsigned)p.B);
+    if (coop) {
+        allow_dynamic_lds((const void*)range_select_kernel<true>, lds);
+        range_select_kernel<true><<<grid, 256, lds, st>>>(dp);
+    } else {
+        allow_dynamic_lds((const void*)range_select_kernel<false>, lds);
+        range_select_kernel<false><<<grid, 256, lds, st>>>(dp);
     }
     PCV_LAUNCHED();
 }

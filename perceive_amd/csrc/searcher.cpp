@@ -5,6 +5,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -204,6 +205,12 @@ struct pcv_searcher {
     Pinned* pin = nullptr;
     bool state_clean = false;  // tau / slots / counters are in the state a pass starts from
     uint32_t cand_cap = 8192;
+    // range search (pcv_searcher_search_range): its lists start at cand_cap and keep what a call grew them to (0: not grown);
+    // range_select_kernel writes its sorted runs and their counts straight into these pinned blocks
+    uint32_t range_cap = 0;
+    pcv_hit_dev* pin_range = nullptr;
+    uint32_t* pin_range_cnt = nullptr;
+    size_t pin_range_n = 0, pin_range_cnt_n = 0;
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -277,6 +284,8 @@ struct pcv_searcher {
         bool replayed = false;  // launched as a graph: only the pass as a whole was timed
         bool learned = false;   // the speculative threshold had a learned part
         bool guessing = false;  // the pass ran with a speculative threshold (and sent the seed statistics home)
+        bool range = false;     // a range pass (fixed thresholds; scan.h, RangeRec) ...
+        uint32_t cap = 0;       // ... and the length its lists had
     } pending;
     // views (pcv_searcher_create_view; DESIGN.md §3 "Views").  As a parent: `gen` counts the calls that may have changed a search
     // result, `live_views` the views that read its rows.  As a view: the parent, the allow list (ascending, distinct), the
@@ -1396,7 +1405,7 @@ void ensure_workspace(pcv_searcher* s) {
 
 // offsets inside the pass block
 struct PassLayout {
-    size_t off_seg, off_ceil, off_q, total;
+    size_t off_seg, off_ceil, off_range, off_q, total;
 };
 // `with_ceil`: the pass has ceilings (scan.h, CeilRec: a search for more than kMaxK results) — their records sit between the
 // segment table and the queries, so that they travel with every attempt of the pass
@@ -1404,7 +1413,9 @@ PassLayout pass_layout(const pcv_searcher* s, size_t nseg, bool with_ceil) {
     PassLayout L;
     L.off_seg = align_up(sizeof(ScanParams));
     L.off_ceil = align_up(L.off_seg + nseg * sizeof(SegDesc));
-    L.off_q = with_ceil ? align_up(L.off_ceil + (size_t)kMfmaQueries * sizeof(CeilRec)) : L.off_ceil;
+    // (... and behind them the bounds and thresholds of a range pass, which is a pass under ceilings: scan.h, RangeRec)
+    L.off_range = with_ceil ? align_up(L.off_ceil + (size_t)kMfmaQueries * sizeof(CeilRec)) : L.off_ceil;
+    L.off_q = with_ceil ? align_up(L.off_range + (size_t)kMfmaQueries * sizeof(RangeRec)) : L.off_ceil;
     L.total = L.off_q + (size_t)kMfmaQueries * s->D * sizeof(float);
     return L;
 }
@@ -1427,9 +1438,16 @@ void ensure_pass_block(pcv_searcher* s, size_t nseg) {
 // rescore_select, which writes the [B][k] hits into `d_out` (nullptr = s->d_hits) and — if `download` —
 // into pinned host memory as well; the survivor counts always come back that way.  `d_flag` != nullptr
 // receives the overflow record (scan.h).
+// `range` != nullptr: a range pass (scan.h, RangeRec; DESIGN.md §4 "Range search") — every row of class 1 of a ceiling, the
+// thresholds fixed by launch_range_thresholds, lists of range->cap entries, range_select_kernel at the end; k, d_out, download,
+// d_flag and ceil_host are not used.
+struct RangePass {
+    const RangeRec* recs;  // [B]
+    uint32_t cap, keep;    // entries per list; hits kept per sorted run
+};
 void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSeg* segs, int nseg, int k, int kernel,
                   pcv_hit_dev* d_out, bool download, pcv_hit_dev* d_flag, const CeilRec* ceil_host = nullptr,
-                  bool queries_on_device = false) {
+                  bool queries_on_device = false, const RangePass* range = nullptr) {
     // `queries_on_device`: queries_host is a DEVICE pointer (embeddings that never left the GPU: encode -> gather -> search of
     // BASELINE configs[4]); the pass copies them device to device behind its parameter upload.
     const auto t_begin = std::chrono::steady_clock::now();
@@ -1438,7 +1456,7 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     ensure_pass_block(s, (size_t)nseg);
     if (!s->state_clean) launch_reset_scan_state(st, s->d_tau.p, s->d_slots.p, s->d_cnt.p);
     s->state_clean = false;  // until finish_pass has seen the pass through
-    const PassLayout L = pass_layout(s, (size_t)nseg, ceil_host != nullptr);
+    const PassLayout L = pass_layout(s, (size_t)nseg, ceil_host != nullptr || range != nullptr);
     ScanParams& p = *reinterpret_cast<ScanParams*>(s->pin_pass);
     SegDesc* tab = reinterpret_cast<SegDesc*>(s->pin_pass + L.off_seg);
     p = ScanParams{};
@@ -1485,6 +1503,36 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
         std::memcpy(s->pin_pass + L.off_ceil, ceil_host, (size_t)B * sizeof(CeilRec));
         p.ceil = reinterpret_cast<const CeilRec*>(s->d_pass + L.off_ceil);
     }
+    if (range) {
+        k = 1;
+        CeilRec* listed = reinterpret_cast<CeilRec*>(s->pin_pass + L.off_ceil);  // lo <= s <= hi for every s: listed, raises nothing
+        for (int q = 0; q < B; ++q) listed[q] = CeilRec{INFINITY, -1, -INFINITY, INFINITY};
+        p.ceil = reinterpret_cast<const CeilRec*>(s->d_pass + L.off_ceil);
+        std::memcpy(s->pin_pass + L.off_range, range->recs, (size_t)B * sizeof(RangeRec));
+        p.range = reinterpret_cast<const RangeRec*>(s->d_pass + L.off_range);
+        p.k = k;
+        p.range_runs = (range->cap + kRangeRun - 1) / kRangeRun;
+        p.range_keep = range->keep;
+        const size_t n_cnt = (size_t)B * p.range_runs, n_out = n_cnt * p.range_keep;
+        if (n_out > s->pin_range_n) {
+            if (s->pin_range) (void)hipHostFree(s->pin_range);
+            s->pin_range = nullptr;
+            s->pin_range_n = 0;
+            PCV_HIP(hipHostMalloc((void**)&s->pin_range, n_out * sizeof(pcv_hit_dev), hipHostMallocDefault));
+            s->pin_range_n = n_out;
+        }
+        if (n_cnt > s->pin_range_cnt_n) {
+            if (s->pin_range_cnt) (void)hipHostFree(s->pin_range_cnt);
+            s->pin_range_cnt = nullptr;
+            s->pin_range_cnt_n = 0;
+            PCV_HIP(hipHostMalloc((void**)&s->pin_range_cnt, n_cnt * sizeof(uint32_t), hipHostMallocDefault));
+            s->pin_range_cnt_n = n_cnt;
+        }
+        p.range_out = s->pin_range;
+        p.range_cnt = s->pin_range_cnt;
+        s->d_cand.ensure(std::max((size_t)kMfmaQueries * s->cand_cap, (size_t)B * range->cap));  // (the stream is idle: finish_pass waited)
+        s->d_cand_s.ensure(std::max((size_t)kMfmaQueries * s->cand_cap, (size_t)B * range->cap));
+    }
     p.qf32 = s->d_qf32.p;
     p.qbf16 = s->d_qbf16.p;
     p.q8 = s->d_q8.p;
@@ -1503,7 +1551,7 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     p.cnt_host = s->pin->cnt;
     p.coarse_host = s->pin->coarse;
     p.flag_rec = d_flag;
-    p.cand_cap = s->cand_cap;
+    p.cand_cap = range ? range->cap : s->cand_cap;
     p.flags = (s->scan_flags & ~(16u | 64u | kFlagSix)) | (src_kind == 1 ? 16u : 0u) | (src_kind == 2 ? 64u : 0u);
     // the 6-bit copies: AUTO's kernel choice only (PCV_KERNEL_MFMA pins the whole-int8 scan), 5..64 queries (scan.h)
     const bool six = src_kind == 2 && have_six && nseg > 0 && s->kernel == PCV_KERNEL_AUTO && !(s->scan_flags & kTuneNoSix) &&
@@ -1524,14 +1572,14 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     p.spec_base_host = s->pin->spec_base;
     p.spec_top_host = s->pin->spec_top;
     p.kth_host = s->pin->kth;
-    if (s->gap_rows != rows || s->gap_k != k || s->gap_nseg != nseg) {  // another shape: learn afresh
+    if (!range && (s->gap_rows != rows || s->gap_k != k || s->gap_nseg != nseg)) {  // another shape: learn afresh
         s->gap_rows = rows;
         s->gap_k = k;
         s->gap_nseg = nseg;
         s->gaps.reset();
     }
     // (no guess under a ceiling: the check at the end of the pass counts survivors, not survivors that count)
-    if (kernel == PCV_KERNEL_MFMA && !s->spec_hold && s->spec_rest == 0 && !(s->scan_flags & 32u) && k >= 2 && !ceil_host) {
+    if (kernel == PCV_KERNEL_MFMA && !s->spec_hold && s->spec_rest == 0 && !(s->scan_flags & 32u) && k >= 2 && !ceil_host && !range) {
         if (!(s->scan_flags & 128u)) p.spec_gap = s->gaps.gap();
         p.spec_spread = (float)s->gaps.spread;
         const double r = (double)std::min<int64_t>(tab[0].nrows, (int64_t)p.seed_blocks * kBlockRows) / (double)std::max<int64_t>(rows, 1);  // (seed rows) / rows
@@ -1572,6 +1620,7 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
         if (queries_dev)
             PCV_HIP(hipMemcpyAsync(s->d_pass + L.off_q, queries_dev, (size_t)B * s->D * sizeof(float), hipMemcpyDeviceToDevice, st));
         launch_prep_seed(st, p, dp, tab[0]);
+        if (range) launch_range_thresholds(st, p, dp);
         if (timed) PCV_HIP(hipEventRecord(s->ev[1], st));
         if (kernel == PCV_KERNEL_MFMA && src_kind == 2)
             launch_scan_mfma8(st, p, dp, s->ctx->num_cus);
@@ -1580,7 +1629,10 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
         else
             launch_scan_wave(st, p, dp, s->ctx->num_cus);
         if (timed) PCV_HIP(hipEventRecord(s->ev[2], st));
-        launch_rescore_select(st, p, dp);
+        if (range)
+            launch_range_select(st, p, dp);
+        else
+            launch_rescore_select(st, p, dp);
         if (timed) PCV_HIP(hipEventRecord(s->ev[3], st));
     };
     pcv_searcher::PassShape shape;
@@ -1588,7 +1640,7 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     shape.k = k;
     shape.kernel = kernel;
     shape.src_kind = src_kind;
-    shape.guess = (p.spec_rank > 0 || p.spec_gap == p.spec_gap) ? 1 : 0;
+    shape.guess = range ? 2 : ((p.spec_rank > 0 || p.spec_gap == p.spec_gap) ? 1 : 0);  // (2: a range pass, never replayed)
     shape.nseg = nseg;
     shape.total_blocks = blk0;
     shape.seed_blocks = p.seed_blocks;
@@ -1601,7 +1653,7 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     shape.seg0_scale = tab[0].scale;
     // only where queueing is a visible share of the pass: up to kGraphRows rows (a longer pass is launched plainly and
     // timed kernel by kernel, which is what the roofline figures are taken from)
-    const bool small = rows <= kGraphRows && s->use_graph && !ceil_host && !queries_dev;
+    const bool small = rows <= kGraphRows && s->use_graph && !ceil_host && !queries_dev && !range;
     bool replayed = false;
     if (small && s->graph_exec && shape == s->graph_shape) {
         PCV_HIP(hipEventRecord(s->ev[0], st));
@@ -1651,6 +1703,8 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     s->pending.src = src_kind;
     s->pending.mid = have_mid && nseg > 0;
     s->pending.six = six;
+    s->pending.range = range != nullptr;
+    s->pending.cap = p.cand_cap;
     // what the scan kernel of this pass must pull from HBM, per 32-row block: the 6-bit pieces + the block's four constants; the
     // int8 pieces + the block's scale; the bf16 pieces; or the f32 pieces + the 32 row scales
     const int64_t Dp8 = (s->Dp + 127) & ~127;
@@ -1726,6 +1780,16 @@ bool finish_pass(pcv_searcher* s) {
     }
     s->stats.coarse_survivors += coarse;
     s->stats.mid_copy = s->pending.mid ? 1 : 0;
+    if (s->pending.range) {
+        // a fixed threshold lists many rows by design: neither AUTO's mid-copy trigger nor the learned gaps hear of it, and the
+        // lists are search_range's to grow
+        if (mx <= s->pending.cap) {
+            s->stats.candidates += sum;
+            return false;
+        }
+        s->stats.overflow_reruns += 1;
+        return true;
+    }
     // AUTO: a corpus whose coarse screen keeps letting thousands of rows per query through gets its mid copy (built by the
     // next search call, before its passes: search_hits), and so does one where the survivors' f32 rows are a visible share
     // of the pass's traffic (a survivor pulls every 128-byte line its 16-byte pieces lie in: 12 KB at 384-d, 24 KB at 768-d;
@@ -1891,19 +1955,163 @@ void hits_to_outputs(int metric, int D, const pcv_hit_dev* hits, int n_queries, 
             if (ok) ++cnt;
             if (out_ids) out_ids[(size_t)q * k + j] = ok ? h.id : -1;
             if (out_scores) {
-                float v = NAN;
-                if (ok) {
-                    if (metric == PCV_METRIC_DOT) {
-                        const double d = 1.0 - h.score / (double)D;  // search.rs:275
-                        v = (float)(d > 0.0 ? d : 0.0);              // search.rs:277
-                    } else {
-                        v = (float)h.score;
-                    }
-                }
-                out_scores[(size_t)q * k + j] = v;
+                out_scores[(size_t)q * k + j] = ok ? reported_score(metric, D, h.score) : NAN;
             }
         }
         if (out_counts) out_counts[q] = cnt;
+    }
+}
+
+// ---- range search (pcv_searcher_search_range; DESIGN.md §4 "Range search") ----
+// The threshold of a range pass for one query: the canonical value of the bound, rounded towards "keeps more" — no row whose
+// REPORTED score passes the bound has c < tau (scan.h, RangeRec).
+//   cosine: (float)c >= b implies c > the f32 below b;
+//   dot:    (float)max(0, 1 - c/D) <= b implies 1 - c/D < the f32 above b, i.e. c > D (1 - that), less the roundings of the f64
+//           expression (1e-9 relative is generous); a negative bound admits nothing.
+// Capped at a value no score reaches (cosine: 4; dot: 2 |q| max|x|), so that "nothing" is a finite threshold like any other.
+RangeRec range_rec(const pcv_searcher* s, const float* q, float bound) {
+    RangeRec r{bound, -INFINITY};
+    float most = 4.0f;
+    if (s->metric == PCV_METRIC_DOT) {
+        double nq = 0.0;
+        for (int i = 0; i < s->D; ++i) nq += (double)q[i] * (double)q[i];
+        const double m = 2.0 * std::sqrt(nq) * (double)s->max_norm + 1e-30;
+        most = (m < (double)FLT_MAX) ? std::nextafterf((float)m, INFINITY) : FLT_MAX;  // (NaN: FLT_MAX)
+        if (bound < 0.0f) {
+            r.tau = most;
+        } else if (bound < INFINITY) {
+            const double T = (double)s->D * (1.0 - (double)std::nextafterf(bound, INFINITY));
+            const double Tl = T - std::fabs(T) * 1e-9;
+            r.tau = Tl > -(double)FLT_MAX ? std::nextafterf((float)Tl, -INFINITY) : -INFINITY;
+        }
+    } else if (bound > -INFINITY) {
+        r.tau = std::nextafterf(bound, -INFINITY);
+    }
+    if (r.tau > most) r.tau = most;
+    return r;
+}
+
+// What a range call leaves allocated for the next one.  Its lists and result blocks are sized from the data: up to kRangeBudget
+// list entries per pass (0.4 GB of device lists) and, with max_results >= kRangeRun, as many pcv_hit_dev of pinned host memory
+// (0.8 GB).  A searcher that once answered a wide bound does not hold that for good: whatever exceeds kRangeKeptBytes is given
+// back when the call ends, and the lists start from cand_cap again (at the price of one repeated pass for the next wide bound).
+constexpr size_t kRangeKeptBytes = (size_t)64 << 20;
+void trim_range_memory(pcv_searcher* s) {
+    const bool pinned = s->pin_range_n * sizeof(pcv_hit_dev) > kRangeKeptBytes;
+    const bool lists = s->d_cand.n * sizeof(*s->d_cand.p) > kRangeKeptBytes && s->d_cand.n > (size_t)kMfmaQueries * s->cand_cap;
+    if (!pinned && !lists) return;
+    (void)hipStreamSynchronize(s->ctx->stream);  // (a call that failed may have left its pass in flight)
+    if (pinned) {
+        (void)hipHostFree(s->pin_range);
+        s->pin_range = nullptr;
+        s->pin_range_n = 0;
+    }
+    if (lists) {  // (every pass sizes them again: ensure_workspace, enqueue_pass)
+        s->d_cand.release();
+        s->d_cand_s.release();
+        s->range_cap = 0;
+    }
+}
+
+// Every searchable row of the selected sources whose reported score passes the query's bound, in the canonical order, at most
+// max_results per query.  One pass per group of queries (a second one if a list was too short: the thresholds are fixed, so the
+// uncapped counts of the first are exactly what the second needs); range_select_kernel leaves each list as sorted runs of
+// kRangeRun in pinned memory, merged here.
+void search_range(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, const float* bounds,
+                  int64_t max_results, int64_t* out_ids, float* out_scores, int64_t* out_counts, uint8_t* out_more) {
+    PCV_REQUIRE(!s->dirty, "search_range: rows were added or cleared without pcv_searcher_finalize");
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    s->stats = pcv_scan_stats{};
+    const int kernel = pick_kernel(s, n_queries);
+    s->stats.kernel_used = kernel;
+    for (int q = 0; q < n_queries; ++q) {
+        if (out_counts) out_counts[q] = 0;
+        if (out_more) out_more[q] = 0;
+    }
+    auto blank = [&](int q, int64_t from) {
+        for (int64_t j = from; j < max_results; ++j) {
+            if (out_ids) out_ids[(size_t)q * max_results + j] = -1;
+            if (out_scores) out_scores[(size_t)q * max_results + j] = NAN;
+        }
+    };
+    if (segs.empty()) {
+        for (int q = 0; q < n_queries; ++q) blank(q, 0);
+        return;
+    }
+    maybe_build_mid_copies(s);
+    struct Trim {
+        pcv_searcher* s;
+        ~Trim() { trim_range_memory(s); }
+    } trim{s};
+    std::vector<RangeRec> recs((size_t)n_queries);
+    for (int q = 0; q < n_queries; ++q) recs[(size_t)q] = range_rec(s, queries + (size_t)q * s->D, bounds[q]);
+    // the lists of one pass hold at most kRangeBudget entries (12 bytes each): long lists take fewer queries per pass
+    constexpr uint64_t kRangeBudget = (uint64_t)1 << 25;
+    const uint32_t keep = (uint32_t)std::min<int64_t>(kRangeRun, max_results);
+    uint32_t cap = std::max(s->range_cap, s->cand_cap);
+    const int qmost = pass_queries(s, kernel);
+    struct Head {
+        const pcv_hit_dev* at;
+        const pcv_hit_dev* end;
+    };
+    std::vector<Head> heads;
+    for (int q0 = 0; q0 < n_queries;) {
+        int B = (int)std::min<uint64_t>((uint64_t)std::min(qmost, n_queries - q0), std::max<uint64_t>(1, kRangeBudget / cap));
+        const float* qs = queries + (size_t)q0 * s->D;
+        RangePass rp{recs.data() + q0, cap, keep};
+        enqueue_pass(s, qs, B, segs.data(), (int)segs.size(), 1, kernel, nullptr, false, nullptr, nullptr, false, &rp);
+        if (finish_pass(s)) {
+            uint32_t mx = 0;
+            int worst = 0;
+            for (int q = 0; q < B; ++q)
+                if (s->pin->cnt[q] > mx) mx = s->pin->cnt[q], worst = q0 + q;
+            if (mx > (uint32_t)PCV_MAX_RANGE_ROWS)
+                PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                         "search_range: the pass of query %d lists %u rows, more than PCV_MAX_RANGE_ROWS (%d): use pcv_searcher_search for "
+                         "such a bound",
+                         worst, mx, (int)PCV_MAX_RANGE_ROWS);
+            // as finish_pass grows the top-k lists: what the pass needed plus a quarter, at least twice what they were
+            uint64_t want = (uint64_t)mx + mx / 4 + 1024;
+            want = std::max<uint64_t>(want, (uint64_t)cap * 2);
+            cap = (uint32_t)std::max<uint64_t>(mx, std::min<uint64_t>(want, (uint64_t)PCV_MAX_RANGE_ROWS));
+            s->range_cap = cap;
+            B = (int)std::min<uint64_t>((uint64_t)B, std::max<uint64_t>(1, kRangeBudget / cap));
+            rp.cap = cap;
+            enqueue_pass(s, qs, B, segs.data(), (int)segs.size(), 1, kernel, nullptr, false, nullptr, nullptr, false, &rp);
+            PCV_REQUIRE(!finish_pass(s), "search_range: lists sized from the counts of a pass overflowed in its repeat");
+        }
+        const uint32_t runs = (cap + kRangeRun - 1) / kRangeRun;
+        for (int q = 0; q < B; ++q) {
+            const uint32_t listed = std::min(s->pin->cnt[q], cap);
+            const uint32_t used = (listed + kRangeRun - 1) / kRangeRun;
+            int64_t total = 0;
+            heads.clear();
+            for (uint32_t r = 0; r < used; ++r) {
+                const uint32_t n = s->pin_range_cnt[(size_t)q * runs + r];
+                total += n;
+                const pcv_hit_dev* at = s->pin_range + ((size_t)q * runs + r) * keep;
+                if (n > 0) heads.push_back({at, at + std::min(n, keep)});
+            }
+            const int64_t cnt = std::min(total, max_results);
+            const size_t o = (size_t)(q0 + q) * (size_t)max_results;
+            auto after = [](const Head& a, const Head& b) { return hit_better(*b.at, *a.at); };  // (heap: the best run on top)
+            std::make_heap(heads.begin(), heads.end(), after);
+            for (int64_t j = 0; j < cnt; ++j) {
+                std::pop_heap(heads.begin(), heads.end(), after);
+                Head& h = heads.back();
+                if (out_ids) out_ids[o + j] = h.at->id;
+                if (out_scores) out_scores[o + j] = reported_score(s->metric, s->D, h.at->score);
+                if (++h.at == h.end)
+                    heads.pop_back();
+                else
+                    std::push_heap(heads.begin(), heads.end(), after);
+            }
+            blank(q0 + q, cnt);
+            if (out_counts) out_counts[q0 + q] = cnt;
+            if (out_more) out_more[q0 + q] = total > max_results ? 1 : 0;
+        }
+        q0 += B;
     }
 }
 
@@ -2313,6 +2521,8 @@ void destroy_searcher(pcv_searcher* s) {
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
     if (s->pin) (void)hipHostFree(s->pin);
     if (s->pin_pass) (void)hipHostFree(s->pin_pass);
+    if (s->pin_range) (void)hipHostFree(s->pin_range);
+    if (s->pin_range_cnt) (void)hipHostFree(s->pin_range_cnt);
     if (s->d_pass) (void)hipFree(s->d_pass);
     if (s->d_max_norm_bits) (void)hipFree(s->d_max_norm_bits);
     for (auto& e : s->ev)
@@ -2839,6 +3049,7 @@ pcv_status pcv_searcher_set_candidate_capacity(pcv_searcher* s, uint32_t n_candi
         PCV_HIP(hipSetDevice(s->ctx->device));
         PCV_HIP(hipStreamSynchronize(s->ctx->stream));
         s->cand_cap = n_candidates;  // the lists are (re)sized to it by the next pass; a pass that needs more grows them
+        s->range_cap = 0;
         s->d_cand.release();
         s->d_cand_s.release();
     });
@@ -2875,6 +3086,23 @@ pcv_status pcv_searcher_search(pcv_searcher* s, const float* queries, int n_quer
         std::vector<pcv_hit_dev> hits;
         search_hits(s, queries, n_queries, source_ids, n_sources, k, hits);
         hits_to_outputs(s->metric, s->D, hits.data(), n_queries, k, out_ids, out_scores, out_counts);
+    });
+}
+
+pcv_status pcv_searcher_search_range(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                     const float* bounds, int64_t max_results, int64_t* out_ids, float* out_scores,
+                                     int64_t* out_counts, uint8_t* out_more) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "search_range: searcher is NULL");
+        PCV_REQUIRE(queries != nullptr && n_queries > 0, "search_range: no queries");
+        PCV_REQUIRE(bounds != nullptr, "search_range: bounds is NULL");
+        for (int q = 0; q < n_queries; ++q) PCV_REQUIRE(bounds[q] == bounds[q], "search_range: the bound of query %d is NaN", q);
+        PCV_REQUIRE(max_results >= 1 && max_results <= (int64_t)PCV_MAX_RANGE_ROWS, "search_range: max_results %lld outside [1,%d]",
+                    (long long)max_results, (int)PCV_MAX_RANGE_ROWS);
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "search_range: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        search_range(s, queries, n_queries, source_ids, n_sources, bounds, max_results, out_ids, out_scores, out_counts, out_more);
     });
 }
 

@@ -331,6 +331,46 @@ class Searcher:
             raise KeyError("Item not found")
         return [SearchItem(int(ids[0, j]), float(scores[0, j])) for j in range(int(counts[0]))]
 
+    # ---- range search (pcv_searcher_search_range) ----------------------------------------------------
+    # Every item within a score bound instead of the best k: near-duplicates, a "related" list with a quality cut-off.
+    def search_range(self, sources, bounds, vectors, max_results):
+        """Every searchable row whose reported score passes the bound (cosine: score >= bound; dot: distance <= bound), best
+        first, at most max_results per query: vectors [B, dim], bounds [B] or a scalar -> (ids [B, max_results] int64, scores
+        [B, max_results] f32, counts [B] int64, more [B] bool: more rows are in range than were returned).  Ids and scores are
+        those search_vectors returns for the same rows."""
+        q = np.ascontiguousarray(vectors, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [B, {self.dim}]")
+        B, m = q.shape[0], int(max_results)
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bounds, dtype=np.float32), (B,)))
+        if not 1 <= m <= (1 << 24):
+            raise ValueError("max_results outside [1, 2^24]")
+        ids = np.empty((B, m), dtype=np.int64)
+        scores = np.empty((B, m), dtype=np.float32)
+        counts = np.zeros(max(B, 1), dtype=np.int64)
+        more = np.zeros(max(B, 1), dtype=np.uint8)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_range(
+                self._handle, _ffi.f32p(q), B, src, nsrc, _ffi.f32p(b), m, _ffi.i64p(ids), _ffi.f32p(scores), _ffi.i64p(counts),
+                _ffi.u8p(more),
+            )
+        )
+        return ids, scores, counts[:B], more[:B].astype(bool)
+
+    def search_range_vector(self, sources, bound, vector, max_results):
+        """search_range for one vector -> list[SearchItem] (the `more` flag is dropped: ask search_range for it)."""
+        ids, scores, counts, _more = self.search_range(sources, bound, np.asarray(vector, dtype=np.float32)[None, :], max_results)
+        return [SearchItem(int(ids[0, j]), float(scores[0, j])) for j in range(int(counts[0]))]
+
+    def search_range_like_item(self, sources, bound, item_id, max_results):
+        """The items within `bound` of the stored embedding of `item_id` (like_queries + search_range); as in search_like_item the
+        item itself comes first.  KeyError("Item not found") when no row carries the id."""
+        vec, found, _members = self.like_queries([[int(item_id)]])
+        if not found[0]:
+            raise KeyError("Item not found")
+        return self.search_range_vector(sources, bound, vec[0], max_results)
+
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):
         _ffi.check(_ffi.lib().pcv_searcher_set_kernel(self._handle, _KERNELS[kernel]))

@@ -316,6 +316,39 @@ impl Searcher {
         Some((0..count as usize).map(|i| SearchItem { id: ids[i], score: scores[i] }).collect())
     }
 
+    /// Range search (`pcv_searcher_search_range`): every item whose reported score passes `bound` — distance <= bound for the
+    /// reference's dot metric — instead of the best `num_results`: near-duplicates of an item, a "related" list with a quality
+    /// cut-off.  Best first, at most `max_results`; the flag says whether more items are in range than were returned.
+    pub fn search_vector_range(&self, sources: &[i64], bound: f32, max_results: usize, vector: Vec<f32>) -> (Vec<SearchItem>, bool) {
+        if self.handle.is_null() || max_results == 0 {
+            return (Vec::new(), false);
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        assert_eq!(vector.len(), dim as usize, "search_vector_range: the query has {} values, the index is {}-d", vector.len(), dim);
+        let mut ids = vec![-1i64; max_results];
+        let mut scores = vec![f32::NAN; max_results];
+        let mut count: i64 = 0;
+        let mut more: u8 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_range(
+                self.handle,
+                vector.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                &bound,
+                max_results as i64,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut count,
+                &mut more,
+            )
+        })
+        .expect("search_range failed");
+        ((0..count as usize).map(|i| SearchItem { id: ids[i], score: scores[i] }).collect(), more != 0)
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
