@@ -83,9 +83,39 @@ struct SegDesc {
     const uint4* blk6;   // 6-bit screening copy (above), or nullptr
     const float4* scale6;  // [nblocks] its per-block constants
 };
-constexpr uint32_t kFlagSix = 1u << 31;      // ScanParams::flags: the pass streams the 6-bit copies (set by the searcher)
-constexpr uint32_t kTuneNoSix = 1u << 29;    // PCV_SCAN_FLAGS: never build or stream the 6-bit copy
-constexpr uint32_t kTuneForceSix = 1u << 31; // PCV_SCAN_FLAGS: AUTO builds it at any size
+// ---- ScanParams::flags, bit by bit ----
+// One word carries the user's tuning / comparison knobs (PCV_SCAN_FLAGS at searcher creation, pcv_searcher_set_tuning) and what the
+// searcher decides for the pass.  Tests, bench.py, tools/ab_scan.py and recorded profiles use the numeric words: no value moves.
+constexpr uint32_t kFlagPlainLoads = 1u << 0;   // plain (temporal) corpus loads instead of non-temporal ones
+constexpr uint32_t kFlagSeed16 = 1u << 1;       // 16 queries per seed workgroup (VALU seed)
+constexpr uint32_t kFlagValuSeed = 1u << 2;     // the VALU seed kernel instead of the MFMA one
+constexpr uint32_t kFlagTile128 = 1u << 3;      // the 128-query tile instead of the block-holding int8 scan
+constexpr uint32_t kFlagSrc16 = 1u << 4;        // searcher: every segment has its bf16 screening copy, the pass streams that
+constexpr uint32_t kFlagNoGuess = 1u << 5;      // no speculative start threshold
+constexpr uint32_t kFlagSrc8 = 1u << 6;         // searcher: every segment has its int8 screening copy, the pass streams that
+constexpr uint32_t kFlagNoLearnedGuess = 1u << 7;  // no learned part of the speculative threshold
+constexpr uint32_t kFlagFourWave = 1u << 28;    // the older 4-waves-a-workgroup int8 scan instead of the DRAIN form
+constexpr uint32_t kTuneNoSix = 1u << 29;       // never build or stream the 6-bit copy
+constexpr uint32_t kTuneFailCopyAlloc = 1u << 30;  // the public PCV_TUNE_FAIL_COPY_ALLOC: taken out of the word by set_tuning, never in a pass
+constexpr uint32_t kFlagSix = 1u << 31;         // searcher: the pass streams the 6-bit copies
+constexpr uint32_t kTuneForceSix = 1u << 31;    // user: AUTO builds the 6-bit copy at any size
+constexpr uint32_t flags_groups_per_cu(uint32_t f) { return (f >> 8) & 0xffu; }  // bits 8..15: workgroups per CU (0: the launcher's own)
+constexpr uint32_t flags_seed_parts(uint32_t f) { return (f >> 16) & 0xffu; }    // bits 16..23: seed workgroups (0: kSeedParts)
+constexpr uint32_t flags_chunk_bufs(uint32_t f) { return (f >> 24) & 0xfu; }     // bits 24..27: chunk buffers (0: the launcher's own)
+// The bits the searcher sets itself for every pass, whatever the user's word holds there.  Bit 31 has two readers: in the
+// searcher's tuning word it is the user's wish (kTuneForceSix, asked when the copies are built), in ScanParams::flags it is the
+// searcher's decision for this pass (kFlagSix) — a pass starts from the tuning word with these bits cleared.
+constexpr uint32_t kFlagsSearcherOwned = kFlagSrc16 | kFlagSrc8 | kFlagSix;
+static_assert(kFlagPlainLoads == 1u && kFlagSeed16 == 2u && kFlagValuSeed == 4u && kFlagTile128 == 8u && kFlagSrc16 == 16u &&
+                  kFlagNoGuess == 32u && kFlagSrc8 == 64u && kFlagNoLearnedGuess == 128u,
+              "the low flag bits are part of recorded PCV_SCAN_FLAGS words");
+static_assert(kFlagFourWave == 0x10000000u && kTuneNoSix == 0x20000000u && kTuneFailCopyAlloc == 0x40000000u &&
+                  kTuneFailCopyAlloc == (uint32_t)PCV_TUNE_FAIL_COPY_ALLOC && kFlagSix == 0x80000000u && kTuneForceSix == 0x80000000u,
+              "the high flag bits are part of recorded PCV_SCAN_FLAGS words");
+static_assert(kFlagsSearcherOwned == 0x80000050u, "bits 4, 6 and 31 are the searcher's");
+static_assert(flags_groups_per_cu(0x0000ab00u) == 0xabu && flags_seed_parts(0x00cd0000u) == 0xcdu && flags_chunk_bufs(0x0e000000u) == 0xeu &&
+                  flags_groups_per_cu(~0xff00u) == 0u && flags_seed_parts(~0xff0000u) == 0u && flags_chunk_bufs(~0x0f000000u) == 0u,
+              "the multi-bit fields are bits 8..15, 16..23 and 24..27");
 
 struct pcv_hit_dev {
     double score;
@@ -135,7 +165,7 @@ struct ScanParams {
     const float* queries;    // [B][D]    raw queries as the caller passed them
     float* qf32;             // [B][Dp]   scan-side query (normalised for cosine), zero padded
     uint16_t* qbf16;         // [128][Dp] same, rounded to bf16
-    int8_t* q8;              // [128][Dp8] same, quantised per query to int8 (int8 screen; Dp8 = Dp rounded up to 128)
+    int8_t* q8;              // [256][Dp8] same, quantised per query to int8 (int8 screen; Dp8 = Dp rounded up to 128)
     float* q8c;              // [256][4]  s_q (quantisation scale, 0 = dead query), V_q of the int8 test (scan_mfma8_kernel), |q'|_1 (mid screen), -;
                              // then [256][4] of the 6-bit test: s_q |q'|_2, s_q |e_q|_2 (both rounded up), -W_q + slack (scan_mfma8_kernel), -
     float* qraw;             // [B][Dp]   original query values, zero padded (exact rescoring)
@@ -161,12 +191,7 @@ struct ScanParams {
     uint32_t seed_blocks;    // blocks of segment 0 ranked by the seed kernel: blocks i << seed_shift, i < seed_blocks — spread
     uint32_t seed_shift;     // over the whole segment, so that rows stored in an order that goes with their content (by topic, by
                              // date) still give a sample of all of it
-    uint32_t flags;          // set by the searcher: bit 4: every segment has its bf16 screening copy, stream that; bit 6: every segment
-                             // has its int8 screening copy, stream that.  Tuning / comparison (PCV_SCAN_FLAGS at searcher creation):
-                             // bit 0: plain (temporal) corpus loads instead of nt; bit 1: 16 queries per seed workgroup (VALU seed);
-                             // bit 2: the VALU seed kernel; bit 3: the 128-query tile instead of the block-holding int8 scan;
-                             // bit 5: no speculative start threshold; bit 7: no learned part of it; bits 8..15: workgroups per CU;
-                             // bits 16..23: seed workgroups; bits 24..27: chunk buffers
+    uint32_t flags;          // kFlag* / kTune* bits and the flags_*() fields above
     unsigned long long* stamps;  // diagnostic build only (-DPCV_STAMPS, tools/build_stamps.sh): 8 words per wave of the scan launch, else nullptr
     float eps16, eps32;      // |s - c| bounds of the bf16 / f32 screening scores, relative to |q||x|
     float max_norm;          // upper bound of |x| over the corpus (dot metric margins)
@@ -185,13 +210,13 @@ struct ScanParams {
     // memory: kth_host, spec_base_host); a fraction of the smallest gap of the recent passes is added to the median
     // slot of the next queries.  Self-calibrating, and checked like the other: a corpus whose queries differ a lot
     // simply learns a small gap.
-    uint32_t* spec;          // [128] key of the guess per query (kKeyNegInf: none), written by set_guess
+    uint32_t* spec;          // [256] key of the guess per query (kKeyNegInf: none), written by set_guess
     int spec_rank;
     float spec_gap;
     float spec_spread;       // learned: mean (best - median) seed slot; a query takes the learned gap only if its own is within 50 %
-    float* spec_base_host;   // [128] pinned: median seed slot per query (NaN: none)
-    float* spec_top_host;    // [128] pinned: best seed slot per query
-    float* kth_host;         // [128] pinned: k-th best exact score per query (NaN: fewer than k hits)
+    float* spec_base_host;   // [256] pinned: median seed slot per query (NaN: none)
+    float* spec_top_host;    // [256] pinned: best seed slot per query
+    float* kth_host;         // [256] pinned: k-th best exact score per query (NaN: fewer than k hits)
     // A range pass (RangeRec above; nullptr: a top-k pass).  range_select_kernel takes the place of rescore_select_kernel: the
     // in-range rows of run r of query q (listed survivors [r * kRangeRun, +kRangeRun)) in canonical order.
     const RangeRec* range;   // [B]

@@ -3681,15 +3681,15 @@ void launch_prep_seed(hipStream_t st, const ScanParams& p, const ScanParams* dp,
     const size_t Dp = (size_t)p.D4 * 4;
     const size_t lds1 = Dp * sizeof(float) + kMaxK * sizeof(uint32_t);
     const size_t lds_mfma = 32 * (Dp + 4) * sizeof(float) + 32 * (size_t)p.k * sizeof(uint32_t);
-    if (lds_mfma <= 156 * 1024 && !(p.flags & 4)) {  // flag bit 2: the VALU form (tuning / comparison)
+    if (lds_mfma <= 156 * 1024 && !(p.flags & kFlagValuSeed)) {  // (the VALU form: tuning / comparison)
         allow_dynamic_lds((const void*)prep_seed_mfma_kernel, lds_mfma);
         const unsigned parts = (p.seed_blocks + 3) / 4;
         prep_seed_mfma_kernel<<<dim3(parts ? parts : 1, (p.B + 31) / 32), 256, lds_mfma, st>>>(dp, seg0.blk, seg0.scale, nseed);
     } else if (p.B <= 2 || 8 * lds1 > 64 * 1024) {  // few queries, or very wide rows: one query per workgroup
         prep_seed_kernel<1><<<dim3(nparts, p.B), 256, lds1, st>>>(dp, seg0.blk, seg0.scale, nseed);
-    } else if (p.B <= 32 || 16 * lds1 > 64 * 1024 || !(p.flags & 2)) {  // 8 queries share every seed row load
+    } else if (p.B <= 32 || 16 * lds1 > 64 * 1024 || !(p.flags & kFlagSeed16)) {  // 8 queries share every seed row load
         prep_seed_kernel<8><<<dim3(nparts, (p.B + 7) / 8), 256, 8 * lds1, st>>>(dp, seg0.blk, seg0.scale, nseed);
-    } else {  // tuning (flag bit 1): 16 do
+    } else {  // tuning (kFlagSeed16): 16 do
         prep_seed_kernel<16><<<dim3(nparts, (p.B + 15) / 16), 256, 16 * lds1, st>>>(dp, seg0.blk, seg0.scale, nseed);
     }
     PCV_LAUNCHED();
@@ -3698,11 +3698,11 @@ void launch_prep_seed(hipStream_t st, const ScanParams& p, const ScanParams* dp,
 void launch_scan_wave(hipStream_t st, const ScanParams& p, const ScanParams* dp, int num_cus) {
     if (p.total_blocks == 0) return;
     const size_t lds = (size_t)p.B * p.D4 * 4 * sizeof(float);
-    const unsigned gm = (p.flags >> 8) & 0xff;
+    const unsigned gm = flags_groups_per_cu(p.flags);
     unsigned grid = (unsigned)num_cus * (gm ? gm : 8);
     const unsigned need = (p.total_blocks + 3) / 4;
     if (grid > need) grid = need;
-    const bool ntl = (p.flags & 1) == 0;  // non-temporal corpus loads unless flag bit 0 is set
+    const bool ntl = (p.flags & kFlagPlainLoads) == 0;  // non-temporal corpus loads unless asked otherwise
     for (const void* f : {(const void*)scan_wave_kernel<1, true>, (const void*)scan_wave_kernel<2, true>, (const void*)scan_wave_kernel<3, true>,
                           (const void*)scan_wave_kernel<4, true>, (const void*)scan_wave_kernel<1, false>, (const void*)scan_wave_kernel<2, false>,
                           (const void*)scan_wave_kernel<3, false>, (const void*)scan_wave_kernel<4, false>})
@@ -3760,10 +3760,10 @@ void launch_scan_mfma(hipStream_t st, const ScanParams& p, const ScanParams* dp,
     if (p.total_blocks == 0) return;
     const int NT = p.B <= 32 ? 1 : (p.B <= 64 ? 2 : 4);
     const size_t lds = (size_t)NT * 32 * p.D4 * 4 * sizeof(uint16_t);
-    const unsigned gm = (p.flags >> 8) & 0xff;
-    const unsigned nbuf = (p.flags >> 24) & 0xf;
-    const bool ntl = (p.flags & 1) == 0;   // non-temporal corpus loads unless flag bit 0 is set
-    const bool src16 = (p.flags & 16) != 0;
+    const unsigned gm = flags_groups_per_cu(p.flags);
+    const unsigned nbuf = flags_chunk_bufs(p.flags);
+    const bool ntl = (p.flags & kFlagPlainLoads) == 0;   // non-temporal corpus loads unless asked otherwise
+    const bool src16 = (p.flags & kFlagSrc16) != 0;
     // small tiles: 256-thread workgroups, 3 per CU.  Tiles too big for that (B > 64, or dim > ~440):
     // 512-thread workgroups sharing one tile, as many per CU as the LDS holds.
     const bool wide = NT == 4 || lds * 3 > 156 * 1024;
@@ -3811,7 +3811,7 @@ static void launch_mfma8_variant(hipStream_t st, const ScanParams* dp, unsigned 
 // buffers — the shapes the copy is built for.  The searcher asks mfma8_six_pass before it sets kFlagSix.
 bool mfma8_six_pass(int B, int Dp, uint32_t flags, int nseg) {
     const int nt = B <= 32 ? 1 : 2;
-    return B > 4 && B <= 64 && ((Dp + 127) & ~127) <= kSixMaxDp8 && !(flags & (1u << 28)) && !(flags & 1u) && (flags >> 24 & 0xf) != 3 &&
+    return B > 4 && B <= 64 && ((Dp + 127) & ~127) <= kSixMaxDp8 && !(flags & kFlagFourWave) && !(flags & kFlagPlainLoads) && flags_chunk_bufs(flags) != 3 &&
            nseg < (1 << kRingSegBits) && mfma8_lds(nt, Dp) + 68 * 1024 <= 156 * 1024;
 }
 template <int NT>
@@ -3855,8 +3855,8 @@ void launch_scan_mfma8(hipStream_t st, const ScanParams& p, const ScanParams* dp
     if (p.total_blocks == 0) return;
     const int NT = p.B <= 32 ? 1 : (p.B <= 64 ? 2 : (p.B <= 128 ? 4 : 8));  // 8: the 256-query tile of the block-holding form
     const size_t lds = mfma8_lds(NT, p.D4 * 4);
-    const unsigned gm = (p.flags >> 8) & 0xff;
-    const bool ntl = (p.flags & 1) == 0;
+    const unsigned gm = flags_groups_per_cu(p.flags);
+    const bool ntl = (p.flags & kFlagPlainLoads) == 0;
     const unsigned most = NT == 4 ? 2 : 3;  // waves per SIMD the register budget allows = 256-thread workgroups per CU
     const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(most, (156 * 1024) / lds));
     // a 128-query tile that fits a CU only once (rows wider than 576 features: 100 KB at 768-d) is shared by eight waves,
@@ -3870,7 +3870,7 @@ void launch_scan_mfma8(hipStream_t st, const ScanParams& p, const ScanParams* dp
     quantize_queries_kernel<<<NT * 32 / 4, 256, 0, st>>>(dp);
     PCV_LAUNCHED();
     const int nch = ((p.D4 * 4 + 127) & ~127) >> 7;
-    if (p.B > 64 && nch <= 3 && (p.B > 128 || !(p.flags & 8u))) {  // (flag bit 3: the 128-query tile, for comparison)
+    if (p.B > 64 && nch <= 3 && (p.B > 128 || !(p.flags & kFlagTile128))) {  // (kFlagTile128: the 128-query tile, for comparison)
         const bool four = p.B > 128;
         // (+ 4 KB per wave where a chunk of the next block waits in LDS: the 256-query form at more than one chunk per block)
         const size_t ldsh = mfma8_lds(four ? 8 : 4, p.D4 * 4) + (four && nch >= 2 ? 12 * 4096 : 0);
@@ -3893,10 +3893,10 @@ void launch_scan_mfma8(hipStream_t st, const ScanParams& p, const ScanParams* dp
     }
     if (NT == 8) PCV_FAIL(PCV_ERR_UNSUPPORTED, "int8 screen: %d queries in one pass need rows of at most 384 features", p.B);
     // Up to 64 queries: ONE 12-wave workgroup per CU, eleven waves stream and the twelfth works off their coarse survivors
-    // (the survivor ring above).  Flag bit 28: the older form, three 4-wave workgroups per CU, every wave handling its own.
+    // (the survivor ring above).  kFlagFourWave: the older form, three 4-wave workgroups per CU, every wave handling its own.
     // (One to four queries keep the older form: their survivors are few, twelve streaming waves beat eleven — 10M x 768, one query:
     // 1.16 against 1.20 ms; from eight queries on the drain form is ahead, 0.63 against 0.67 ms at 10M x 384 / 16 queries.)
-    if (NT <= 2 && p.B > 4 && !(p.flags & (1u << 28)) && p.nseg < (1 << kRingSegBits) && lds + 68 * 1024 <= 156 * 1024) {
+    if (NT <= 2 && p.B > 4 && !(p.flags & kFlagFourWave) && p.nseg < (1 << kRingSegBits) && lds + 68 * 1024 <= 156 * 1024) {
         constexpr unsigned kW = 12;
         unsigned g12 = (unsigned)num_cus * (gm ? gm : 1u);
         g12 = std::min(g12, (p.total_blocks + (kW - 2)) / (kW - 1));
@@ -3910,7 +3910,7 @@ void launch_scan_mfma8(hipStream_t st, const ScanParams& p, const ScanParams* dp
             if (ntl) launch_mfma8_drain<1, true, 4>(st, dp, g12, lds, nch);
             else launch_mfma8_drain<1, false, 4>(st, dp, g12, lds, nch);
         } else {
-            if ((p.flags >> 24 & 0xf) == 3) {
+            if (flags_chunk_bufs(p.flags) == 3) {
                 if (ntl) launch_mfma8_drain<2, true, 3>(st, dp, g12, lds, nch);
                 else launch_mfma8_drain<2, false, 3>(st, dp, g12, lds, nch);
             } else {

@@ -93,6 +93,30 @@ struct DevBuf {
     }
 };
 
+// Its counterpart in pinned host memory (what kernels write results to and uploads are staged in).  The same rule: whoever lets
+// one go that queued work may still use synchronises the stream first.
+template <class T>
+struct PinBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
+    void ensure(size_t want) {
+        if (want <= n) return;
+        release();
+        PCV_HIP(hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault));
+        n = want;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    T* operator->() const { return p; }
+};
+
 // Runs `f` when the scope ends, however it ends.
 template <class F>
 struct AtExit {
@@ -134,7 +158,7 @@ struct pcv_searcher {
     // updated items (pcv_searcher_update_rows): the slots next to d_idtab, the matches of a segment, the (row, slot) lists of a call
     DevBuf<uint32_t> d_idslot, d_hslots, d_urows, d_uslots;
 
-    // per-search workspace (sized for one pass of <= 128 queries)
+    // per-search workspace (sized for one pass of <= kMfmaQueries = 256 queries)
     DevBuf<float> d_qf32, d_qraw, d_margin, d_margin32;
     DevBuf<uint16_t> d_qbf16;
     DevBuf<int8_t> d_q8;
@@ -189,9 +213,8 @@ struct pcv_searcher {
     DevBuf<pcv_hit_dev> d_hits;
     // what one pass takes up: ScanParams | SegDesc[nseg] | queries[B][D], built in pinned memory and
     // sent with ONE copy into its device mirror
-    uint8_t* pin_pass = nullptr;
-    uint8_t* d_pass = nullptr;
-    size_t pass_cap = 0;
+    PinBuf<uint8_t> pin_pass;
+    DevBuf<uint8_t> d_pass;
     // what one pass brings back: written by rescore_select_kernel straight into pinned memory
     struct Pinned {
         uint32_t cnt[kMfmaQueries];
@@ -202,15 +225,14 @@ struct pcv_searcher {
         float kth[kMfmaQueries];
         pcv_hit_dev hits[kMfmaQueries * kMaxK];
     };
-    Pinned* pin = nullptr;
+    PinBuf<Pinned> pin;
     bool state_clean = false;  // tau / slots / counters are in the state a pass starts from
     uint32_t cand_cap = 8192;
     // range search (pcv_searcher_search_range): its lists start at cand_cap and keep what a call grew them to (0: not grown);
     // range_select_kernel writes its sorted runs and their counts straight into these pinned blocks
     uint32_t range_cap = 0;
-    pcv_hit_dev* pin_range = nullptr;
-    uint32_t* pin_range_cnt = nullptr;
-    size_t pin_range_n = 0, pin_range_cnt_n = 0;
+    PinBuf<pcv_hit_dev> pin_range;
+    PinBuf<uint32_t> pin_range_cnt;
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -1398,7 +1420,7 @@ void ensure_workspace(pcv_searcher* s) {
     s->d_cand.ensure(Q * s->cand_cap);
     s->d_cand_s.ensure(Q * s->cand_cap);
     s->d_hits.ensure(Q * kMaxK);
-    if (!s->pin) PCV_HIP(hipHostMalloc((void**)&s->pin, sizeof(pcv_searcher::Pinned), hipHostMallocDefault));
+    s->pin.ensure(1);
     for (auto& e : s->ev)
         if (!e) PCV_HIP(hipEventCreate(&e));
 }
@@ -1421,117 +1443,128 @@ PassLayout pass_layout(const pcv_searcher* s, size_t nseg, bool with_ceil) {
 }
 void ensure_pass_block(pcv_searcher* s, size_t nseg) {
     const size_t want = pass_layout(s, nseg, true).total;
-    if (want <= s->pass_cap) return;
+    if (want <= s->pin_pass.n && want <= s->d_pass.n) return;
     PCV_HIP(hipStreamSynchronize(s->ctx->stream));
-    if (s->pin_pass) (void)hipHostFree(s->pin_pass);
-    if (s->d_pass) (void)hipFree(s->d_pass);
-    s->pin_pass = s->d_pass = nullptr;
-    s->pass_cap = 0;
     const size_t cap = want + want / 2;
-    PCV_HIP(hipHostMalloc((void**)&s->pin_pass, cap, hipHostMallocDefault));
-    PCV_HIP(hipMalloc((void**)&s->d_pass, cap));
-    s->pass_cap = cap;
+    s->pin_pass.ensure(cap);
+    s->d_pass.ensure(cap);
 }
 
-// Queue one pass (<= pass_queries() queries over any number of segments) on the context stream without
-// waiting for it: one H2D of (parameters, segment table, queries), then prep_seed, scan and
-// rescore_select, which writes the [B][k] hits into `d_out` (nullptr = s->d_hits) and — if `download` —
-// into pinned host memory as well; the survivor counts always come back that way.  `d_flag` != nullptr
-// receives the overflow record (scan.h).
-// `range` != nullptr: a range pass (scan.h, RangeRec; DESIGN.md §4 "Range search") — every row of class 1 of a ceiling, the
-// thresholds fixed by launch_range_thresholds, lists of range->cap entries, range_select_kernel at the end; k, d_out, download,
-// d_flag and ceil_host are not used.
-struct RangePass {
-    const RangeRec* recs;  // [B]
-    uint32_t cap, keep;    // entries per list; hits kept per sorted run
+// One pass (<= pass_queries() queries over any number of segments) as its caller asks for it: the queries and where they are,
+// the selected segments, the kernel, and exactly one of three kinds of result.
+struct PassRequest {
+    // kDevice: `queries` is a DEVICE pointer (embeddings that never left the GPU: encode -> gather -> search of BASELINE
+    // configs[4]), copied device to device behind the parameter upload.  kResident: the queries of the previous attempt are still
+    // in the device's pass block; `queries` is not read.
+    enum Where { kHost, kDevice, kResident };
+    // kCeilings: a top-k pass among the rows that rank after one ceiling per query (scan.h, CeilRec).  kRange: every row of class
+    // 1 of a ceiling, the thresholds fixed by launch_range_thresholds, range_select_kernel at the end (scan.h, RangeRec;
+    // DESIGN.md §4 "Range search").
+    enum Kind { kTopK, kCeilings, kRange };
+    struct TopK {
+        int k;
+        pcv_hit_dev* d_out;     // [B][k] hits (nullptr = s->d_hits)
+        bool download;          // ... into s->pin->hits as well (the survivor counts always come back that way)
+        pcv_hit_dev* d_flag;    // receives the overflow record (scan.h), or nullptr
+        const CeilRec* ceil;    // [B], kCeilings only
+    };
+    struct Range {
+        const RangeRec* recs;   // [B]
+        uint32_t cap, keep;     // entries per list; hits kept per sorted run
+    };
+    const float* queries;  // [B][D]
+    Where where = kHost;
+    int B;
+    const SelSeg* segs;
+    int nseg;
+    int kernel;
+    Kind kind = kTopK;
+    union {
+        TopK topk = {};
+        Range range;
+    };
+    PassRequest(const float* q, int B_, const std::vector<SelSeg>& sel, int kernel_)
+        : queries(q), B(B_), segs(sel.data()), nseg((int)sel.size()), kernel(kernel_) {}
+    PassRequest& top_k(int k, pcv_hit_dev* d_out, bool download, pcv_hit_dev* d_flag = nullptr, const CeilRec* ceil = nullptr) {
+        kind = ceil ? kCeilings : kTopK;
+        topk = TopK{k, d_out, download, d_flag, ceil};
+        return *this;
+    }
+    PassRequest& in_range(const RangeRec* recs, uint32_t cap, uint32_t keep) {
+        kind = kRange;
+        range = Range{recs, cap, keep};
+        return *this;
+    }
+    int k() const { return kind == kRange ? 1 : topk.k; }  // (a range pass ranks nothing: its thresholds are fixed)
 };
-void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSeg* segs, int nseg, int k, int kernel,
-                  pcv_hit_dev* d_out, bool download, pcv_hit_dev* d_flag, const CeilRec* ceil_host = nullptr,
-                  bool queries_on_device = false, const RangePass* range = nullptr) {
-    // `queries_on_device`: queries_host is a DEVICE pointer (embeddings that never left the GPU: encode -> gather -> search of
-    // BASELINE configs[4]); the pass copies them device to device behind its parameter upload.
-    const auto t_begin = std::chrono::steady_clock::now();
-    hipStream_t st = s->ctx->stream;
-    ensure_workspace(s);
-    ensure_pass_block(s, (size_t)nseg);
-    if (!s->state_clean) launch_reset_scan_state(st, s->d_tau.p, s->d_slots.p, s->d_cnt.p);
-    s->state_clean = false;  // until finish_pass has seen the pass through
-    const PassLayout L = pass_layout(s, (size_t)nseg, ceil_host != nullptr || range != nullptr);
-    ScanParams& p = *reinterpret_cast<ScanParams*>(s->pin_pass);
-    SegDesc* tab = reinterpret_cast<SegDesc*>(s->pin_pass + L.off_seg);
-    p = ScanParams{};
-    uint32_t blk0 = 0;
+
+// ---- enqueue_pass, step by step ----
+// 1. What the pass streams, decided while the segment table is filled.
+struct PassSource {
+    int src_kind = 0;      // 0 f32 rows, 1 bf16 copies, 2 int8 copies
+    bool have_mid = false; // every selected segment has its mid copy, and the pass uses it
+    bool six = false;      // the 6-bit copies are streamed in place of the int8 ones
+    uint32_t flags = 0;    // ScanParams::flags of the pass: the tuning word with the searcher's own bits (scan.h) set to this decision
+    uint32_t total_blocks = 0;
     int64_t rows = 0;
+};
+// The rule is here and nowhere else: a copy is streamed iff the searcher keeps that kind, EVERY selected segment has it and it
+// covers EVERY row of each (a copy that does not cover every row yet is not used).
+PassSource fill_segment_table(const pcv_searcher* s, const PassRequest& r, SegDesc* tab) {
+    PassSource src;
+    src.src_kind = (r.kernel == PCV_KERNEL_MFMA) ? copy_kind_wanted(s) : 0;
+    if (src.src_kind == 2 && (mfma8_pass_queries(s->Dp) < r.B || s->Dp > 1024)) src.src_kind = 0;
+    const int src_wanted = src.src_kind;
     bool have_mid = true, have_six = true;
-    // stream the screening copies iff every selected segment has one of the kind the searcher keeps
-    int src_kind = (kernel == PCV_KERNEL_MFMA) ? copy_kind_wanted(s) : 0;
-    if (src_kind == 2 && (mfma8_pass_queries(s->Dp) < B || s->Dp > 1024)) src_kind = 0;
-    const int src_wanted = src_kind;
-    for (int i = 0; i < nseg; ++i) {
-        const Segment& g = *segs[i].g;
-        const bool mid = g.mid16 != nullptr && g.mid_rows >= g.nrows;  // (a copy that does not cover every row yet is not used)
+    uint32_t blk0 = 0;
+    for (int i = 0; i < r.nseg; ++i) {
+        const Segment& g = *r.segs[i].g;
+        const bool mid = g.mid16 != nullptr && g.mid_rows >= g.nrows;
         tab[i] = SegDesc{g.blk, g.scale, g.ids, g.id0, g.pos0, g.nrows, g.nblocks(), blk0, 0, g.blk16, g.blk8, mid ? g.mid16 : nullptr, mid ? g.scale16 : nullptr, g.scale8,
                          g.blk6, g.scale6};
         have_six = have_six && g.blk6 != nullptr && g.six_rows >= g.nrows;
         have_mid = have_mid && mid;
-        if ((src_kind == 1 ? g.blk16 == nullptr : (src_kind == 2 ? g.blk8 == nullptr : false)) || g.copied_rows < g.nrows) src_kind = 0;
+        if ((src.src_kind == 1 ? g.blk16 == nullptr : (src.src_kind == 2 ? g.blk8 == nullptr : false)) || g.copied_rows < g.nrows) src.src_kind = 0;
         PCV_REQUIRE((uint64_t)blk0 + g.nblocks() < 0xffffff00ull, "search: more than 2^32 row blocks in one launch");
         blk0 += g.nblocks();
-        rows += g.nrows;
+        src.rows += g.nrows;
     }
-    if (src_kind != 2) {
+    if (src.src_kind != 2) {
         // the mid screen's bound uses |q'|_1, which only the int8 path's quantize_queries_kernel computes: passes that stream
         // the bf16 copy or the f32 rows (few coarse survivors anyway) go straight to the f32 row
-        for (int i = 0; i < nseg; ++i) {
+        for (int i = 0; i < r.nseg; ++i) {
             tab[i].mid16 = nullptr;
             tab[i].scale16 = nullptr;
         }
         have_mid = false;
     }
-    PCV_REQUIRE(B <= 128 || (kernel == PCV_KERNEL_MFMA && src_kind == 2 && src_wanted == 2), "search: %d queries in one pass without int8 copies of every selected row", B);
-    p.seg = reinterpret_cast<const SegDesc*>(s->d_pass + L.off_seg);
-    p.nseg = nseg;
-    p.total_blocks = blk0;
+    PCV_REQUIRE(r.B <= 128 || (r.kernel == PCV_KERNEL_MFMA && src.src_kind == 2 && src_wanted == 2), "search: %d queries in one pass without int8 copies of every selected row", r.B);
+    src.total_blocks = blk0;
+    src.have_mid = have_mid && r.nseg > 0;
+    src.flags = (s->scan_flags & ~kFlagsSearcherOwned) | (src.src_kind == 1 ? kFlagSrc16 : 0u) | (src.src_kind == 2 ? kFlagSrc8 : 0u);
+    // the 6-bit copies: AUTO's kernel choice only (PCV_KERNEL_MFMA pins the whole-int8 scan), 5..64 queries (scan.h)
+    src.six = src.src_kind == 2 && have_six && r.nseg > 0 && s->kernel == PCV_KERNEL_AUTO && !(s->scan_flags & kTuneNoSix) &&
+              mfma8_six_pass(r.B, s->Dp, src.flags, r.nseg);
+    if (src.six) src.flags |= kFlagSix;
+    return src;
+}
+
+// 2. The parameters of a top-k pass, from the workspace (a range pass: fill_range_part on top).  No guess yet.
+void fill_params(pcv_searcher* s, const PassRequest& r, const PassLayout& L, const PassSource& src, ScanParams& p) {
+    p = ScanParams{};
+    p.seg = reinterpret_cast<const SegDesc*>(s->d_pass.p + L.off_seg);
+    p.nseg = r.nseg;
+    p.total_blocks = src.total_blocks;
     p.D = s->D;
     p.D4 = s->D4;
-    p.B = B;
-    p.k = k;
+    p.B = r.B;
+    p.k = r.k();
     p.metric = s->metric;
-    p.tile_rows = kernel == PCV_KERNEL_MFMA ? mfma_tile_rows(B) : 0u;
-    p.queries = reinterpret_cast<const float*>(s->d_pass + L.off_q);
-    if (ceil_host) {
-        std::memcpy(s->pin_pass + L.off_ceil, ceil_host, (size_t)B * sizeof(CeilRec));
-        p.ceil = reinterpret_cast<const CeilRec*>(s->d_pass + L.off_ceil);
-    }
-    if (range) {
-        k = 1;
-        CeilRec* listed = reinterpret_cast<CeilRec*>(s->pin_pass + L.off_ceil);  // lo <= s <= hi for every s: listed, raises nothing
-        for (int q = 0; q < B; ++q) listed[q] = CeilRec{INFINITY, -1, -INFINITY, INFINITY};
-        p.ceil = reinterpret_cast<const CeilRec*>(s->d_pass + L.off_ceil);
-        std::memcpy(s->pin_pass + L.off_range, range->recs, (size_t)B * sizeof(RangeRec));
-        p.range = reinterpret_cast<const RangeRec*>(s->d_pass + L.off_range);
-        p.k = k;
-        p.range_runs = (range->cap + kRangeRun - 1) / kRangeRun;
-        p.range_keep = range->keep;
-        const size_t n_cnt = (size_t)B * p.range_runs, n_out = n_cnt * p.range_keep;
-        if (n_out > s->pin_range_n) {
-            if (s->pin_range) (void)hipHostFree(s->pin_range);
-            s->pin_range = nullptr;
-            s->pin_range_n = 0;
-            PCV_HIP(hipHostMalloc((void**)&s->pin_range, n_out * sizeof(pcv_hit_dev), hipHostMallocDefault));
-            s->pin_range_n = n_out;
-        }
-        if (n_cnt > s->pin_range_cnt_n) {
-            if (s->pin_range_cnt) (void)hipHostFree(s->pin_range_cnt);
-            s->pin_range_cnt = nullptr;
-            s->pin_range_cnt_n = 0;
-            PCV_HIP(hipHostMalloc((void**)&s->pin_range_cnt, n_cnt * sizeof(uint32_t), hipHostMallocDefault));
-            s->pin_range_cnt_n = n_cnt;
-        }
-        p.range_out = s->pin_range;
-        p.range_cnt = s->pin_range_cnt;
-        s->d_cand.ensure(std::max((size_t)kMfmaQueries * s->cand_cap, (size_t)B * range->cap));  // (the stream is idle: finish_pass waited)
-        s->d_cand_s.ensure(std::max((size_t)kMfmaQueries * s->cand_cap, (size_t)B * range->cap));
+    p.tile_rows = r.kernel == PCV_KERNEL_MFMA ? mfma_tile_rows(r.B) : 0u;
+    p.queries = reinterpret_cast<const float*>(s->d_pass.p + L.off_q);
+    if (r.kind == PassRequest::kCeilings) {
+        std::memcpy(s->pin_pass.p + L.off_ceil, r.topk.ceil, (size_t)r.B * sizeof(CeilRec));
+        p.ceil = reinterpret_cast<const CeilRec*>(s->d_pass.p + L.off_ceil);
     }
     p.qf32 = s->d_qf32.p;
     p.qbf16 = s->d_qbf16.p;
@@ -1546,25 +1579,21 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     p.cand_cnt = s->d_cnt.p;
     p.cand = s->d_cand.p;
     p.cand_s = s->d_cand_s.p;
-    p.out = d_out ? d_out : s->d_hits.p;
-    p.out_host = download ? s->pin->hits : nullptr;
+    p.cand_cap = s->cand_cap;
+    p.out = s->d_hits.p;
+    if (r.kind != PassRequest::kRange) {
+        if (r.topk.d_out) p.out = r.topk.d_out;
+        p.out_host = r.topk.download ? s->pin->hits : nullptr;
+        p.flag_rec = r.topk.d_flag;
+    }
     p.cnt_host = s->pin->cnt;
     p.coarse_host = s->pin->coarse;
-    p.flag_rec = d_flag;
-    p.cand_cap = range ? range->cap : s->cand_cap;
-    p.flags = (s->scan_flags & ~(16u | 64u | kFlagSix)) | (src_kind == 1 ? 16u : 0u) | (src_kind == 2 ? 64u : 0u);
-    // the 6-bit copies: AUTO's kernel choice only (PCV_KERNEL_MFMA pins the whole-int8 scan), 5..64 queries (scan.h)
-    const bool six = src_kind == 2 && have_six && nseg > 0 && s->kernel == PCV_KERNEL_AUTO && !(s->scan_flags & kTuneNoSix) &&
-                     mfma8_six_pass(B, s->Dp, p.flags, nseg);
-    if (six) p.flags |= kFlagSix;
-    const uint32_t seed_parts = ((s->scan_flags >> 16) & 0xff) ? ((s->scan_flags >> 16) & 0xff) : kSeedParts;  // tuning
-    p.seed_blocks = std::min<uint32_t>(std::min<uint32_t>(seed_parts, kSeedParts) * kSeedPartRows / kBlockRows, segs[0].g->nblocks());
+    p.flags = src.flags;
+    const uint32_t seed_parts = flags_seed_parts(s->scan_flags) ? flags_seed_parts(s->scan_flags) : kSeedParts;  // tuning
+    const uint32_t seg0_blocks = r.segs[0].g->nblocks();
+    p.seed_blocks = std::min<uint32_t>(std::min<uint32_t>(seed_parts, kSeedParts) * kSeedPartRows / kBlockRows, seg0_blocks);
     p.seed_shift = 0;  // the seed blocks are every 2^shift-th block of segment 0, the largest stride that fits
-    while (((uint64_t)p.seed_blocks << (p.seed_shift + 1)) <= segs[0].g->nblocks() && p.seed_shift < 20) ++p.seed_shift;
-    // |s - c| bounds of the screening scores, relative to |q||x| (DESIGN.md §screening error): an f32 FMA
-    // chain in any order, and one bf16 rounding per operand on top of it
-    // speculative start threshold (scan.h): the int8 scan only (its queue has the kernel that sets it); j-th largest
-    // seed slot with the smallest j whose guess fails with probability < 1e-6 on rows in an order unrelated to the query
+    while (((uint64_t)p.seed_blocks << (p.seed_shift + 1)) <= seg0_blocks && p.seed_shift < 20) ++p.seed_shift;
     p.spec = s->d_spec.p;
     p.spec_rank = 0;
     p.spec_gap = NAN;
@@ -1572,150 +1601,353 @@ void enqueue_pass(pcv_searcher* s, const float* queries_host, int B, const SelSe
     p.spec_base_host = s->pin->spec_base;
     p.spec_top_host = s->pin->spec_top;
     p.kth_host = s->pin->kth;
-    if (!range && (s->gap_rows != rows || s->gap_k != k || s->gap_nseg != nseg)) {  // another shape: learn afresh
-        s->gap_rows = rows;
-        s->gap_k = k;
-        s->gap_nseg = nseg;
-        s->gaps.reset();
-    }
-    // (no guess under a ceiling: the check at the end of the pass counts survivors, not survivors that count)
-    if (kernel == PCV_KERNEL_MFMA && !s->spec_hold && s->spec_rest == 0 && !(s->scan_flags & 32u) && k >= 2 && !ceil_host && !range) {
-        if (!(s->scan_flags & 128u)) p.spec_gap = s->gaps.gap();
-        p.spec_spread = (float)s->gaps.spread;
-        const double r = (double)std::min<int64_t>(tab[0].nrows, (int64_t)p.seed_blocks * kBlockRows) / (double)std::max<int64_t>(rows, 1);  // (seed rows) / rows
-        double binom = 1.0, rj = 1.0;
-        for (int j = 1; j < k && r < 0.25; ++j) {
-            binom *= (double)(k - j) / (double)j;  // C(k-1, j)
-            rj *= r;
-            if (binom * rj < 1e-6) {
-                p.spec_rank = j;
-                break;
-            }
-        }
-    }
 #ifdef PCV_STAMPS
     s->d_stamps.ensure(8 * 65536);
-    PCV_HIP(hipMemsetAsync(s->d_stamps.p, 0, 8 * 65536 * sizeof(unsigned long long), st));
+    PCV_HIP(hipMemsetAsync(s->d_stamps.p, 0, 8 * 65536 * sizeof(unsigned long long), s->ctx->stream));
     p.stamps = s->d_stamps.p;
 #endif
+    // |s - c| bounds of the screening scores, relative to |q||x| (DESIGN.md §screening error): an f32 FMA
+    // chain in any order, and one bf16 rounding per operand on top of it
     p.eps32 = (float)(s->Dp + 16) * 1.2e-7f;
     p.eps16 = 0.0039101f + 2.0f * p.eps32;
     p.max_norm = s->max_norm;
+}
 
-    size_t bytes = L.off_q;
-    const float* queries_dev = nullptr;
-    if (queries_host && queries_on_device) {
-        queries_dev = queries_host;
-    } else if (queries_host) {  // nullptr: the queries of the previous attempt are still on the device
-        std::memcpy(s->pin_pass + L.off_q, queries_host, (size_t)B * s->D * sizeof(float));
-        bytes += (size_t)B * s->D * sizeof(float);
+// 3. What a range pass has on top: every row listed and raising nothing, the bounds, lists of range.cap entries and the pinned
+// blocks range_select_kernel writes its runs to.
+void fill_range_part(pcv_searcher* s, const PassRequest& r, const PassLayout& L, ScanParams& p) {
+    CeilRec* listed = reinterpret_cast<CeilRec*>(s->pin_pass.p + L.off_ceil);  // lo <= s <= hi for every s: listed, raises nothing
+    for (int q = 0; q < r.B; ++q) listed[q] = CeilRec{INFINITY, -1, -INFINITY, INFINITY};
+    p.ceil = reinterpret_cast<const CeilRec*>(s->d_pass.p + L.off_ceil);
+    std::memcpy(s->pin_pass.p + L.off_range, r.range.recs, (size_t)r.B * sizeof(RangeRec));
+    p.range = reinterpret_cast<const RangeRec*>(s->d_pass.p + L.off_range);
+    p.range_runs = (r.range.cap + kRangeRun - 1) / kRangeRun;
+    p.range_keep = r.range.keep;
+    const size_t n_cnt = (size_t)r.B * p.range_runs;
+    s->pin_range.ensure(n_cnt * p.range_keep);
+    s->pin_range_cnt.ensure(n_cnt);
+    p.range_out = s->pin_range.p;
+    p.range_cnt = s->pin_range_cnt.p;
+    s->d_cand.ensure((size_t)r.B * r.range.cap);  // (never below ensure_workspace's size; the stream is idle: finish_pass waited)
+    s->d_cand_s.ensure((size_t)r.B * r.range.cap);
+    p.cand = s->d_cand.p;
+    p.cand_s = s->d_cand_s.p;
+    p.cand_cap = r.range.cap;
+}
+
+// 4. The speculative start threshold of the pass (scan.h): the int8 / MFMA scans only (their queue has the kernel that sets
+// it); the j-th largest seed slot with the smallest j whose guess fails with probability < 1e-6 on rows in an order unrelated
+// to the query, and the learned gap on top.  A pass of another shape than the last lets the searcher learn afresh.
+struct Guess {
+    int rank = 0;        // 0: none
+    float gap = NAN;     // NaN: no learned part
+    float spread = 0.0f;
+    bool learned() const { return gap == gap; }
+    bool any() const { return rank > 0 || learned(); }
+};
+Guess choose_guess(pcv_searcher* s, const PassRequest& r, int64_t rows, int64_t seed_rows) {
+    Guess g;
+    const int k = r.k();
+    if (r.kind != PassRequest::kRange && (s->gap_rows != rows || s->gap_k != k || s->gap_nseg != r.nseg)) {  // another shape: learn afresh
+        s->gap_rows = rows;
+        s->gap_k = k;
+        s->gap_nseg = r.nseg;
+        s->gaps.reset();
     }
-    const ScanParams* dp = reinterpret_cast<const ScanParams*>(s->d_pass);
-    // `timed`: with the event records around the scan kernel.  Records captured into a graph do not give times on
-    // replay, so a replayed pass is bracketed from outside (ev[0], ev[3]) and its scan time is taken as the share of that
-    // total which the scan kernel had in the plain launches of the same shape.
-    auto launch_pass = [&](bool timed) {
-        if (timed) PCV_HIP(hipEventRecord(s->ev[0], st));
-        launch_upload(st, s->pin_pass, s->d_pass, bytes);
-        if (queries_dev)
-            PCV_HIP(hipMemcpyAsync(s->d_pass + L.off_q, queries_dev, (size_t)B * s->D * sizeof(float), hipMemcpyDeviceToDevice, st));
-        launch_prep_seed(st, p, dp, tab[0]);
-        if (range) launch_range_thresholds(st, p, dp);
-        if (timed) PCV_HIP(hipEventRecord(s->ev[1], st));
-        if (kernel == PCV_KERNEL_MFMA && src_kind == 2)
-            launch_scan_mfma8(st, p, dp, s->ctx->num_cus);
-        else if (kernel == PCV_KERNEL_MFMA)
-            launch_scan_mfma(st, p, dp, s->ctx->num_cus);
-        else
-            launch_scan_wave(st, p, dp, s->ctx->num_cus);
-        if (timed) PCV_HIP(hipEventRecord(s->ev[2], st));
-        if (range)
-            launch_range_select(st, p, dp);
-        else
-            launch_rescore_select(st, p, dp);
-        if (timed) PCV_HIP(hipEventRecord(s->ev[3], st));
-    };
+    // (no guess under a ceiling: the check at the end of the pass counts survivors, not survivors that count)
+    if (r.kernel != PCV_KERNEL_MFMA || s->spec_hold || s->spec_rest != 0 || (s->scan_flags & kFlagNoGuess) || k < 2 || r.kind != PassRequest::kTopK) return g;
+    if (!(s->scan_flags & kFlagNoLearnedGuess)) g.gap = s->gaps.gap();
+    g.spread = (float)s->gaps.spread;
+    const double ratio = (double)seed_rows / (double)std::max<int64_t>(rows, 1);  // (seed rows) / rows
+    double binom = 1.0, rj = 1.0;
+    for (int j = 1; j < k && ratio < 0.25; ++j) {
+        binom *= (double)(k - j) / (double)j;  // C(k-1, j)
+        rj *= ratio;
+        if (binom * rj < 1e-6) {
+            g.rank = j;
+            break;
+        }
+    }
+    return g;
+}
+
+// 5. The launch sequence, and whether it is queued plainly or replayed from a captured graph.
+struct PassLaunch {
+    const PassRequest& r;
+    const PassLayout& L;
+    int src_kind;  // what the scan streams (PassSource)
+    size_t bytes;  // of the pass block to upload: parameters and tables, and the queries unless the device has them already
+};
+// the pass block in pinned memory: the parameters (dp: their device mirror) and the segment table
+inline ScanParams& pass_params(const pcv_searcher* s) { return *reinterpret_cast<ScanParams*>(s->pin_pass.p); }
+inline SegDesc* pass_table(const pcv_searcher* s, const PassLayout& L) { return reinterpret_cast<SegDesc*>(s->pin_pass.p + L.off_seg); }
+// `timed`: with the event records around the scan kernel.  Records captured into a graph do not give times on
+// replay, so a replayed pass is bracketed from outside (ev[0], ev[3]) and its scan time is taken as the share of that
+// total which the scan kernel had in the plain launches of the same shape.
+void launch_pass(pcv_searcher* s, const PassLaunch& l, bool timed) {
+    hipStream_t st = s->ctx->stream;
+    const ScanParams& p = pass_params(s);
+    const ScanParams* dp = reinterpret_cast<const ScanParams*>(s->d_pass.p);
+    if (timed) PCV_HIP(hipEventRecord(s->ev[0], st));
+    launch_upload(st, s->pin_pass.p, s->d_pass.p, l.bytes);
+    if (l.r.where == PassRequest::kDevice)
+        PCV_HIP(hipMemcpyAsync(s->d_pass.p + l.L.off_q, l.r.queries, (size_t)p.B * s->D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    launch_prep_seed(st, p, dp, pass_table(s, l.L)[0]);
+    if (p.range) launch_range_thresholds(st, p, dp);
+    if (timed) PCV_HIP(hipEventRecord(s->ev[1], st));
+    if (l.r.kernel == PCV_KERNEL_MFMA && l.src_kind == 2)
+        launch_scan_mfma8(st, p, dp, s->ctx->num_cus);
+    else if (l.r.kernel == PCV_KERNEL_MFMA)
+        launch_scan_mfma(st, p, dp, s->ctx->num_cus);
+    else
+        launch_scan_wave(st, p, dp, s->ctx->num_cus);
+    if (timed) PCV_HIP(hipEventRecord(s->ev[2], st));
+    if (p.range)
+        launch_range_select(st, p, dp);
+    else
+        launch_rescore_select(st, p, dp);
+    if (timed) PCV_HIP(hipEventRecord(s->ev[3], st));
+}
+
+pcv_searcher::PassShape pass_shape(const pcv_searcher* s, const PassLaunch& l, const Guess& g) {
+    const ScanParams& p = pass_params(s);
+    const SegDesc& seg0 = pass_table(s, l.L)[0];
     pcv_searcher::PassShape shape;
-    shape.B = B;
-    shape.k = k;
-    shape.kernel = kernel;
-    shape.src_kind = src_kind;
-    shape.guess = range ? 2 : ((p.spec_rank > 0 || p.spec_gap == p.spec_gap) ? 1 : 0);  // (2: a range pass, never replayed)
-    shape.nseg = nseg;
-    shape.total_blocks = blk0;
+    shape.B = p.B;
+    shape.k = p.k;
+    shape.kernel = l.r.kernel;
+    shape.src_kind = l.src_kind;
+    shape.guess = p.range ? 2 : (g.any() ? 1 : 0);  // (2: a range pass, never replayed)
+    shape.nseg = p.nseg;
+    shape.total_blocks = p.total_blocks;
     shape.seed_blocks = p.seed_blocks;
     shape.flags = p.flags;
-    shape.seg0_rows = tab[0].nrows;
-    shape.bytes = bytes;
-    shape.pin = s->pin_pass;
-    shape.dev = s->d_pass;
-    shape.seg0_blk = tab[0].blk;
-    shape.seg0_scale = tab[0].scale;
-    // only where queueing is a visible share of the pass: up to kGraphRows rows (a longer pass is launched plainly and
-    // timed kernel by kernel, which is what the roofline figures are taken from)
-    const bool small = rows <= kGraphRows && s->use_graph && !ceil_host && !queries_dev && !range;
-    bool replayed = false;
-    if (small && s->graph_exec && shape == s->graph_shape) {
+    shape.seg0_rows = seg0.nrows;
+    shape.bytes = l.bytes;
+    shape.pin = s->pin_pass.p;
+    shape.dev = s->d_pass.p;
+    shape.seg0_blk = seg0.blk;
+    shape.seg0_scale = seg0.scale;
+    return shape;
+}
+
+// Captures the launch sequence of `l` into a graph and launches that; false: capture is not possible here.
+bool capture_and_launch(pcv_searcher* s, const PassLaunch& l, const pcv_searcher::PassShape& shape) {
+    hipStream_t st = s->ctx->stream;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
+    if (ok) {
+        try {
+            launch_pass(s, l, false);
+        } catch (...) {
+            ok = false;
+        }
+        ok = (hipStreamEndCapture(st, &graph) == hipSuccess) && ok && graph != nullptr;
+    }
+    const auto drop = at_exit([&] {
+        if (graph) (void)hipGraphDestroy(graph);
+    });
+    if (!ok || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) return false;
+    if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
+    s->graph_exec = exec;
+    s->graph_shape = shape;
+    s->graph_fixed_ms = s->shape_fixed_ms;
+    PCV_HIP(hipGraphLaunch(exec, st));
+    return true;
+}
+
+// Queues the pass; true: as a graph (only the pass as a whole is timed).  A shape is captured on its third sighting in a row,
+// and only where queueing is a visible share of the pass (`may_replay`: up to kGraphRows rows — a longer pass is launched
+// plainly and timed kernel by kernel, which is what the roofline figures are taken from — and never under ceilings, with
+// device queries or for a range).
+bool launch_or_replay(pcv_searcher* s, const PassLaunch& l, const pcv_searcher::PassShape& shape, bool may_replay) {
+    hipStream_t st = s->ctx->stream;
+    if (may_replay && s->graph_exec && shape == s->graph_shape) {
         PCV_HIP(hipEventRecord(s->ev[0], st));
         PCV_HIP(hipGraphLaunch(s->graph_exec, st));
         PCV_HIP(hipEventRecord(s->ev[3], st));
-        replayed = true;
-    } else if (small && shape == s->last_shape && ++s->shape_seen >= 3 && s->shape_fixed_ms >= 0.0f) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        PCV_HIP(hipEventRecord(s->ev[0], st));
-        bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (ok) {
-            try {
-                launch_pass(false);
-            } catch (...) {
-                ok = false;
-            }
-            ok = (hipStreamEndCapture(st, &graph) == hipSuccess) && ok && graph != nullptr;
-        }
-        if (ok && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-            if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
-            s->graph_exec = exec;
-            s->graph_shape = shape;
-            s->graph_fixed_ms = s->shape_fixed_ms;
-            PCV_HIP(hipGraphLaunch(exec, st));
-            PCV_HIP(hipEventRecord(s->ev[3], st));
-            replayed = true;
-        } else {  // capture is not possible here: stay with plain launches for good
-            (void)hipGetLastError();
-            s->use_graph = false;
-            launch_pass(true);
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-    } else {
-        if (!(shape == s->last_shape)) {
-            s->last_shape = shape;
-            s->shape_seen = 1;
-            s->shape_fixed_ms = -1.0f;
-        }
-        launch_pass(true);
+        return true;
     }
-    s->pending.replayed = replayed;
-    s->pending.active = true;
-    s->pending.done = false;
-    s->pending.B = B;
-    s->pending.rows = rows;
-    s->pending.src = src_kind;
-    s->pending.mid = have_mid && nseg > 0;
-    s->pending.six = six;
-    s->pending.range = range != nullptr;
-    s->pending.cap = p.cand_cap;
-    // what the scan kernel of this pass must pull from HBM, per 32-row block: the 6-bit pieces + the block's four constants; the
-    // int8 pieces + the block's scale; the bf16 pieces; or the f32 pieces + the 32 row scales
-    const int64_t Dp8 = (s->Dp + 127) & ~127;
-    s->pending.int8_bytes = (int64_t)blk0 * (Dp8 * kBlockRows + (int64_t)kScale8Stride * 4);
-    s->pending.stream_bytes = six ? (int64_t)blk0 * (Dp8 * kBlockRows * 3 / 4 + (int64_t)sizeof(float4))
-                              : (int64_t)blk0 * (src_kind == 2 ? Dp8 * kBlockRows + (int64_t)kScale8Stride * 4
-                                                 : src_kind == 1 ? (int64_t)s->Dp * 2 * kBlockRows
-                                                                 : (int64_t)s->Dp * 4 * kBlockRows + kBlockRows * 4);
-    s->pending.learned = p.spec_gap == p.spec_gap;
-    s->pending.guessing = p.spec_rank > 0 || s->pending.learned;
+    if (may_replay && shape == s->last_shape && ++s->shape_seen >= 3 && s->shape_fixed_ms >= 0.0f) {
+        PCV_HIP(hipEventRecord(s->ev[0], st));
+        if (capture_and_launch(s, l, shape)) {
+            PCV_HIP(hipEventRecord(s->ev[3], st));
+            return true;
+        }
+        (void)hipGetLastError();  // capture is not possible here: stay with plain launches for good
+        s->use_graph = false;
+        launch_pass(s, l, true);
+        return false;
+    }
+    if (!(shape == s->last_shape)) {
+        s->last_shape = shape;
+        s->shape_seen = 1;
+        s->shape_fixed_ms = -1.0f;
+    }
+    launch_pass(s, l, true);
+    return false;
+}
+
+// 6. What finish_pass needs to know of the pass.
+// Bytes the scan kernel must pull from HBM per 32-row block of what it streams (0 f32 rows, 1 bf16 copies, 2 int8 copies,
+// 3 the 6-bit copies; scan.h): the f32 pieces + the 32 row scales; the bf16 pieces; the int8 pieces + the block's scale; the
+// 6-bit pieces + the block's four constants.
+int64_t block_bytes(int Dp, int streamed) {
+    const int64_t Dp8 = (Dp + 127) & ~127;
+    switch (streamed) {
+        case 3: return Dp8 * kBlockRows * 3 / 4 + (int64_t)sizeof(float4);
+        case 2: return Dp8 * kBlockRows + (int64_t)kScale8Stride * 4;
+        case 1: return (int64_t)Dp * 2 * kBlockRows;
+        default: return (int64_t)Dp * 4 * kBlockRows + kBlockRows * 4;
+    }
+}
+void book_pending(pcv_searcher* s, const PassSource& src, const ScanParams& p, const Guess& g, bool replayed) {
+    pcv_searcher::Pending& pd = s->pending;
+    pd.replayed = replayed;
+    pd.active = true;
+    pd.done = false;
+    pd.B = p.B;
+    pd.rows = src.rows;
+    pd.src = src.src_kind;
+    pd.mid = src.have_mid;
+    pd.six = src.six;
+    pd.range = p.range != nullptr;
+    pd.cap = p.cand_cap;
+    pd.int8_bytes = (int64_t)src.total_blocks * block_bytes(s->Dp, 2);
+    pd.stream_bytes = (int64_t)src.total_blocks * block_bytes(s->Dp, src.six ? 3 : src.src_kind);
+    pd.learned = g.learned();
+    pd.guessing = g.any();
+}
+
+// Queue one pass on the context stream without waiting for it: one H2D of (parameters, segment table, queries), then
+// prep_seed, scan and rescore_select (range_select for a range pass), which write the results where the request says.
+void enqueue_pass(pcv_searcher* s, const PassRequest& r) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    ensure_workspace(s);
+    ensure_pass_block(s, (size_t)r.nseg);
+    if (!s->state_clean) launch_reset_scan_state(s->ctx->stream, s->d_tau.p, s->d_slots.p, s->d_cnt.p);
+    s->state_clean = false;  // until finish_pass has seen the pass through
+    const PassLayout L = pass_layout(s, (size_t)r.nseg, r.kind != PassRequest::kTopK);
+    ScanParams& p = pass_params(s);
+    SegDesc* tab = pass_table(s, L);
+    const PassSource src = fill_segment_table(s, r, tab);
+    fill_params(s, r, L, src, p);
+    if (r.kind == PassRequest::kRange) fill_range_part(s, r, L, p);
+    const Guess g = choose_guess(s, r, src.rows, std::min<int64_t>(tab[0].nrows, (int64_t)p.seed_blocks * kBlockRows));
+    p.spec_rank = g.rank;
+    p.spec_gap = g.gap;
+    p.spec_spread = g.spread;
+
+    size_t bytes = L.off_q;
+    if (r.where == PassRequest::kHost) {
+        std::memcpy(s->pin_pass.p + L.off_q, r.queries, (size_t)r.B * s->D * sizeof(float));
+        bytes += (size_t)r.B * s->D * sizeof(float);
+    }
+    const PassLaunch l{r, L, src.src_kind, bytes};
+    const bool may_replay = src.rows <= kGraphRows && s->use_graph && r.kind == PassRequest::kTopK && r.where != PassRequest::kDevice;
+    const bool replayed = launch_or_replay(s, l, pass_shape(s, l, g), may_replay);
+    book_pending(s, src, p, g, replayed);
     s->stats.host_enqueue_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+}
+
+// ---- finish_pass, step by step ----
+// What the survivor counts of a pass say (s->pin, written by the last kernel of the pass).
+struct PassCounts {
+    uint32_t mx = 0;            // longest list any query needed
+    int64_t sum = 0, coarse = 0;
+    bool guess_failed = false;  // fewer than k rows at some query's speculative threshold (scan.h)
+};
+
+void time_pass(pcv_searcher* s) {
+    float ms_scan = 0, ms_total = 0;
+    (void)hipEventElapsedTime(&ms_total, s->ev[0], s->ev[3]);
+    if (s->pending.replayed) {
+        ms_scan = ms_total * s->graph_fixed_ms;
+    } else {
+        (void)hipEventElapsedTime(&ms_scan, s->ev[1], s->ev[2]);
+        s->shape_fixed_ms = ms_total > 0.0f ? std::min(1.0f, std::max(0.0f, ms_scan / ms_total)) : 0.0f;
+    }
+    s->stats.scan_ms += ms_scan;
+    s->stats.total_ms += ms_total;
+}
+
+PassCounts book_pass(pcv_searcher* s) {
+    const pcv_searcher::Pending& pd = s->pending;
+    s->stats.scan_launches += 1;
+    s->stats.rows_scanned += pd.rows;
+    s->stats.bytes_algorithmic += pd.rows * (int64_t)s->D * 4;
+    s->stats.bytes_streamed += pd.stream_bytes;
+    s->stats.screening_copy = pd.src;
+    s->stats.screen_bits = pd.src == 2 ? (pd.six ? 6 : 8) : 0;
+    PassCounts c;
+    for (int b = 0; b < pd.B; ++b) {
+        const uint32_t cnt = s->pin->cnt[b];
+        if (cnt == kSpecFailed) {  // repeat without the guess
+            c.guess_failed = true;
+        } else {
+            c.mx = std::max(c.mx, cnt);
+            c.sum += cnt;
+        }
+        c.coarse += s->pin->coarse[b];
+        s->stats.mid_survivors += s->pin->coarse[kMfmaQueries + b];
+        if (pd.six) s->stats.narrow_survivors += s->pin->coarse[2 * kMfmaQueries + b];
+    }
+    s->stats.coarse_survivors += c.coarse;
+    s->stats.mid_copy = pd.mid ? 1 : 0;
+    return c;
+}
+
+// AUTO: a corpus whose coarse screen keeps letting thousands of rows per query through gets its mid copy (built by the
+// next search call, before its passes: open_search), and so does one where the survivors' f32 rows are a visible share
+// of the pass's traffic (a survivor pulls every 128-byte line its 16-byte pieces lie in: 12 KB at 384-d, 24 KB at 768-d;
+// measured gain of the copy: 12.5M x 384 3.5 %, 50M x 768 3.8 %, nothing at 100M x 384 where the share is 1.2 %)
+void note_mid_trigger(pcv_searcher* s, int64_t coarse) {
+    const int64_t fine_bytes = coarse * (int64_t)s->Dp * 32;
+    if (s->pending.src == 2 && !s->pending.mid &&
+        (coarse > kMidTrigger * (int64_t)s->pending.B || fine_bytes * kMidShare > (int64_t)s->pending.int8_bytes))
+        s->mid_hot_passes += 1;
+    else
+        s->mid_hot_passes = 0;
+}
+
+// The pass is complete: the guess, if it had one, held, and teaches about the gap (scan.h: spec_gap).
+void guess_held(pcv_searcher* s) {
+    s->spec_hold = false;
+    if (s->spec_rest > 0) s->spec_rest -= 1;
+    if (s->spec_penalty > 0 && ++s->spec_clean >= 4096) s->spec_penalty = s->spec_clean = 0;
+    if (s->pending.guessing) {
+        for (int b = 0; b < s->pending.B; ++b) {
+            const float d = s->pin->kth[b] - s->pin->spec_base[b];
+            const float sp = s->pin->spec_top[b] - s->pin->spec_base[b];
+            if (d == d && std::isfinite(d) && sp == sp && std::isfinite(sp)) s->gaps.add(d, sp);
+        }
+    }
+    if (s->gaps.holdoff > 0) s->gaps.holdoff -= 1;
+}
+
+void guess_failed(pcv_searcher* s) {
+    s->stats.speculation_reruns += 1;
+    s->spec_hold = true;
+    if (s->pending.learned) {  // what was learned did not hold: start over, and not before 256 passes have gone by
+        s->gaps.reset();
+        s->gaps.holdoff = 256;
+    } else {  // the seed rows were not a fair sample for this query: no guesses for a while
+        s->spec_penalty = std::min(1024, s->spec_penalty ? 2 * s->spec_penalty : 16);
+        s->spec_rest = s->spec_penalty;
+        s->spec_clean = 0;
+    }
+}
+
+// What a list that needed `mx` entries is grown towards, before the caller's clamps (finish_pass and search_range clamp
+// differently, on purpose): what the pass needed plus a quarter.
+inline uint64_t list_need(uint32_t mx) { return (uint64_t)mx + mx / 4 + 1024; }
+
+void grow_lists(pcv_searcher* s, uint32_t mx) {
+    const uint64_t want = std::min<uint64_t>(list_need(mx), (uint64_t)s->pending.rows + 1024);
+    s->cand_cap = (uint32_t)std::max<uint64_t>(want, s->cand_cap * 2ull);
+    s->d_cand.ensure((size_t)kMfmaQueries * s->cand_cap);
+    s->d_cand_s.ensure((size_t)kMfmaQueries * s->cand_cap);
 }
 
 // Collect a queued pass: wait for the stream, book the statistics, and report whether a candidate list
@@ -1741,109 +1973,40 @@ bool finish_pass(pcv_searcher* s) {
     }
 #endif
     s->state_clean = true;  // rescore_select_kernel left the scan state as a pass expects it
-    const int B = s->pending.B;
-    const int64_t rows = s->pending.rows;
-    float ms_scan = 0, ms_total = 0;
-    (void)hipEventElapsedTime(&ms_total, s->ev[0], s->ev[3]);
-    if (s->pending.replayed) {
-        ms_scan = ms_total * s->graph_fixed_ms;
-    } else {
-        (void)hipEventElapsedTime(&ms_scan, s->ev[1], s->ev[2]);
-        s->shape_fixed_ms = ms_total > 0.0f ? std::min(1.0f, std::max(0.0f, ms_scan / ms_total)) : 0.0f;
-    }
-    s->stats.scan_ms += ms_scan;
-    s->stats.total_ms += ms_total;
-    s->stats.scan_launches += 1;
-    s->stats.rows_scanned += rows;
-    s->stats.bytes_algorithmic += rows * (int64_t)s->D * 4;
-    s->stats.bytes_streamed += s->pending.stream_bytes;
-    s->stats.screening_copy = s->pending.src;
-    s->stats.screen_bits = s->pending.src == 2 ? (s->pending.six ? 6 : 8) : 0;
-
-    const uint32_t* cnt = s->pin->cnt;
-    uint32_t mx = 0;
-    int64_t sum = 0;
-    bool guess_failed = false;
-    for (int b = 0; b < B; ++b) {
-        if (cnt[b] == kSpecFailed) {  // fewer than k rows at the speculative threshold (scan.h): repeat without it
-            guess_failed = true;
-            continue;
-        }
-        mx = std::max(mx, cnt[b]);
-        sum += cnt[b];
-    }
-    int64_t coarse = 0;
-    for (int b = 0; b < B; ++b) {
-        coarse += s->pin->coarse[b];
-        s->stats.mid_survivors += s->pin->coarse[kMfmaQueries + b];
-        if (s->pending.six) s->stats.narrow_survivors += s->pin->coarse[2 * kMfmaQueries + b];
-    }
-    s->stats.coarse_survivors += coarse;
-    s->stats.mid_copy = s->pending.mid ? 1 : 0;
+    time_pass(s);
+    const PassCounts c = book_pass(s);
     if (s->pending.range) {
         // a fixed threshold lists many rows by design: neither AUTO's mid-copy trigger nor the learned gaps hear of it, and the
         // lists are search_range's to grow
-        if (mx <= s->pending.cap) {
-            s->stats.candidates += sum;
-            return false;
-        }
-        s->stats.overflow_reruns += 1;
-        return true;
+        const bool over = c.mx > s->pending.cap;
+        if (over)
+            s->stats.overflow_reruns += 1;
+        else
+            s->stats.candidates += c.sum;
+        return over;
     }
-    // AUTO: a corpus whose coarse screen keeps letting thousands of rows per query through gets its mid copy (built by the
-    // next search call, before its passes: search_hits), and so does one where the survivors' f32 rows are a visible share
-    // of the pass's traffic (a survivor pulls every 128-byte line its 16-byte pieces lie in: 12 KB at 384-d, 24 KB at 768-d;
-    // measured gain of the copy: 12.5M x 384 3.5 %, 50M x 768 3.8 %, nothing at 100M x 384 where the share is 1.2 %)
-    const int64_t fine_bytes = coarse * (int64_t)s->Dp * 32;
-    if (s->pending.src == 2 && !s->pending.mid &&
-        (coarse > kMidTrigger * (int64_t)B || fine_bytes * kMidShare > (int64_t)s->pending.int8_bytes))
-        s->mid_hot_passes += 1;
-    else
-        s->mid_hot_passes = 0;
-    if (mx <= s->cand_cap && !guess_failed) {
-        s->stats.candidates += sum;
-        s->spec_hold = false;
-        if (s->spec_rest > 0) s->spec_rest -= 1;
-        if (s->spec_penalty > 0 && ++s->spec_clean >= 4096) s->spec_penalty = s->spec_clean = 0;
-        if (s->pending.guessing) {  // what this pass teaches about the gap (scan.h: spec_gap)
-            for (int b = 0; b < B; ++b) {
-                const float d = s->pin->kth[b] - s->pin->spec_base[b];
-                const float sp = s->pin->spec_top[b] - s->pin->spec_base[b];
-                if (d == d && std::isfinite(d) && sp == sp && std::isfinite(sp)) s->gaps.add(d, sp);
-            }
-        }
-        if (s->gaps.holdoff > 0) s->gaps.holdoff -= 1;
+    note_mid_trigger(s, c.coarse);
+    if (c.mx <= s->cand_cap && !c.guess_failed) {
+        s->stats.candidates += c.sum;
+        guess_held(s);
         return false;
     }
-    if (guess_failed) {
-        s->stats.speculation_reruns += 1;
-        s->spec_hold = true;
-        if (s->pending.learned) {  // what was learned did not hold: start over, and not before 256 passes have gone by
-            s->gaps.reset();
-            s->gaps.holdoff = 256;
-        } else {  // the seed rows were not a fair sample for this query: no guesses for a while
-            s->spec_penalty = std::min(1024, s->spec_penalty ? 2 * s->spec_penalty : 16);
-            s->spec_rest = s->spec_penalty;
-            s->spec_clean = 0;
-        }
-        if (mx <= s->cand_cap) return true;
+    if (c.guess_failed) {
+        guess_failed(s);
+        if (c.mx <= s->cand_cap) return true;
     }
     s->stats.overflow_reruns += 1;
-    uint64_t want = (uint64_t)mx + mx / 4 + 1024;
-    want = std::min<uint64_t>(want, (uint64_t)rows + 1024);
-    s->cand_cap = (uint32_t)std::max<uint64_t>(want, s->cand_cap * 2ull);
-    s->d_cand.ensure((size_t)kMfmaQueries * s->cand_cap);
-    s->d_cand_s.ensure((size_t)kMfmaQueries * s->cand_cap);
+    grow_lists(s, c.mx);
     return true;
 }
 
-// One pass, synchronously.  Leaves [B][k] hits in `d_out` (nullptr = s->d_hits) and, if `download`, in s->pin->hits.
-void run_pass(pcv_searcher* s, const float* queries_host, int B, const SelSeg* segs, int nseg, int k, int kernel,
-              pcv_hit_dev* d_out, bool download, const CeilRec* ceil_host = nullptr) {
+// One pass, synchronously: repeated — the queries still on the device — while a candidate list overflows or a guess fails.
+void run_pass(pcv_searcher* s, PassRequest r) {
     for (int attempt = 0;; ++attempt) {
-        enqueue_pass(s, attempt == 0 ? queries_host : nullptr, B, segs, nseg, k, kernel, d_out, download, nullptr, ceil_host);
+        enqueue_pass(s, r);
         if (!finish_pass(s)) return;
         PCV_REQUIRE(attempt < 7, "candidate lists still overflow after %d reruns", attempt + 1);
+        r.where = PassRequest::kResident;
     }
 }
 
@@ -1879,6 +2042,31 @@ void check_search_args(const pcv_searcher* s, const float* queries, int n_querie
     PCV_REQUIRE(k > 0 && k <= k_max, "%s: num_results %d outside [1,%d]", who, k, k_max);
 }
 
+// What every search call settles before its first pass: the device, the selected segments, the kernel and how many queries one
+// pass takes.  Nothing of the searcher changes here, so a refused kernel leaves what the caller has not touched itself.
+struct SearchPlan {
+    std::vector<SelSeg> segs;
+    int kernel = 0;
+    int qstep = 0;
+};
+SearchPlan plan_search(pcv_searcher* s, const int64_t* source_ids, int n_sources, int n_queries, bool among_ranks = false) {
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    SearchPlan plan;
+    plan.segs = select_segments(s, source_ids, n_sources);
+    plan.kernel = pick_kernel(s, n_queries);
+    plan.qstep = pass_queries(s, plan.kernel, among_ranks);
+    return plan;
+}
+// ... and what it starts with: fresh statistics and, if there are rows to search, AUTO's mid copies.  False: no selected rows —
+// the answer to that is the caller's.
+bool open_search(pcv_searcher* s, const SearchPlan& plan) {
+    s->stats = pcv_scan_stats{};
+    s->stats.kernel_used = plan.kernel;
+    if (plan.segs.empty()) return false;
+    maybe_build_mid_copies(s);
+    return true;
+}
+
 // The ceilings of the pass that follows one whose last hits are `last` (one per query; pos < 0: that pass came back short —
 // the query has all the rows there are): scan.h, CeilRec.  The band around the boundary is the fine screen's margin,
 // 2 eps32 relative to |q||x| (x <= the largest row norm for the dot metric; 1 for cosine), plus the rounding of the f64 score to f32.
@@ -1908,16 +2096,12 @@ void next_ceilings(const pcv_searcher* s, const float* queries, int B, const pcv
 void search_hits(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
                  int k, std::vector<pcv_hit_dev>& out) {
     check_search_args(s, queries, n_queries, k, "search", 1 << 24);
-    PCV_HIP(hipSetDevice(s->ctx->device));
-    std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
     const pcv_hit_dev none{NAN, -1, -1};
     out.assign((size_t)n_queries * k, none);
-    s->stats = pcv_scan_stats{};
-    const int kernel = pick_kernel(s, n_queries);
-    s->stats.kernel_used = kernel;
-    if (segs.empty()) return;
-    const int qstep = pass_queries(s, kernel);
-    maybe_build_mid_copies(s);
+    s->stats = pcv_scan_stats{};  // (also when the kernel is refused)
+    const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries);
+    if (!open_search(s, plan)) return;
+    const int qstep = plan.qstep;
     std::vector<CeilRec> ceil;
     std::vector<pcv_hit_dev> last;
     for (int q0 = 0; q0 < n_queries; q0 += qstep) {
@@ -1931,7 +2115,7 @@ void search_hits(pcv_searcher* s, const float* queries, int n_queries, const int
                 ceil.resize((size_t)B);
                 next_ceilings(s, qs, B, last.data(), ceil.data());
             }
-            run_pass(s, qs, B, segs.data(), (int)segs.size(), kk, kernel, nullptr, true, got > 0 ? ceil.data() : nullptr);
+            run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(kk, nullptr, true, nullptr, got > 0 ? ceil.data() : nullptr));
             last.resize((size_t)B);
             bool more = false;
             for (int q = 0; q < B; ++q) {  // (the hits came down with the pass)
@@ -1997,16 +2181,12 @@ RangeRec range_rec(const pcv_searcher* s, const float* q, float bound) {
 // back when the call ends, and the lists start from cand_cap again (at the price of one repeated pass for the next wide bound).
 constexpr size_t kRangeKeptBytes = (size_t)64 << 20;
 void trim_range_memory(pcv_searcher* s) {
-    const bool pinned = s->pin_range_n * sizeof(pcv_hit_dev) > kRangeKeptBytes;
+    const bool pinned = s->pin_range.n * sizeof(pcv_hit_dev) > kRangeKeptBytes;
     const bool lists = s->d_cand.n * sizeof(*s->d_cand.p) > kRangeKeptBytes && s->d_cand.n > (size_t)kMfmaQueries * s->cand_cap;
     if (!pinned && !lists) return;
     (void)hipStreamSynchronize(s->ctx->stream);  // (a call that failed may have left its pass in flight)
-    if (pinned) {
-        (void)hipHostFree(s->pin_range);
-        s->pin_range = nullptr;
-        s->pin_range_n = 0;
-    }
-    if (lists) {  // (every pass sizes them again: ensure_workspace, enqueue_pass)
+    if (pinned) s->pin_range.release();
+    if (lists) {  // (every pass sizes them again: ensure_workspace, fill_range_part)
         s->d_cand.release();
         s->d_cand_s.release();
         s->range_cap = 0;
@@ -2020,11 +2200,8 @@ void trim_range_memory(pcv_searcher* s) {
 void search_range(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, const float* bounds,
                   int64_t max_results, int64_t* out_ids, float* out_scores, int64_t* out_counts, uint8_t* out_more) {
     PCV_REQUIRE(!s->dirty, "search_range: rows were added or cleared without pcv_searcher_finalize");
-    PCV_HIP(hipSetDevice(s->ctx->device));
-    std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
-    s->stats = pcv_scan_stats{};
-    const int kernel = pick_kernel(s, n_queries);
-    s->stats.kernel_used = kernel;
+    s->stats = pcv_scan_stats{};  // (also when the kernel is refused)
+    const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries);
     for (int q = 0; q < n_queries; ++q) {
         if (out_counts) out_counts[q] = 0;
         if (out_more) out_more[q] = 0;
@@ -2035,11 +2212,10 @@ void search_range(pcv_searcher* s, const float* queries, int n_queries, const in
             if (out_scores) out_scores[(size_t)q * max_results + j] = NAN;
         }
     };
-    if (segs.empty()) {
+    if (!open_search(s, plan)) {
         for (int q = 0; q < n_queries; ++q) blank(q, 0);
         return;
     }
-    maybe_build_mid_copies(s);
     struct Trim {
         pcv_searcher* s;
         ~Trim() { trim_range_memory(s); }
@@ -2050,7 +2226,7 @@ void search_range(pcv_searcher* s, const float* queries, int n_queries, const in
     constexpr uint64_t kRangeBudget = (uint64_t)1 << 25;
     const uint32_t keep = (uint32_t)std::min<int64_t>(kRangeRun, max_results);
     uint32_t cap = std::max(s->range_cap, s->cand_cap);
-    const int qmost = pass_queries(s, kernel);
+    const int qmost = plan.qstep;
     struct Head {
         const pcv_hit_dev* at;
         const pcv_hit_dev* end;
@@ -2059,8 +2235,8 @@ void search_range(pcv_searcher* s, const float* queries, int n_queries, const in
     for (int q0 = 0; q0 < n_queries;) {
         int B = (int)std::min<uint64_t>((uint64_t)std::min(qmost, n_queries - q0), std::max<uint64_t>(1, kRangeBudget / cap));
         const float* qs = queries + (size_t)q0 * s->D;
-        RangePass rp{recs.data() + q0, cap, keep};
-        enqueue_pass(s, qs, B, segs.data(), (int)segs.size(), 1, kernel, nullptr, false, nullptr, nullptr, false, &rp);
+        PassRequest pass = PassRequest(qs, B, plan.segs, plan.kernel).in_range(recs.data() + q0, cap, keep);
+        enqueue_pass(s, pass);
         if (finish_pass(s)) {
             uint32_t mx = 0;
             int worst = 0;
@@ -2071,14 +2247,14 @@ void search_range(pcv_searcher* s, const float* queries, int n_queries, const in
                          "search_range: the pass of query %d lists %u rows, more than PCV_MAX_RANGE_ROWS (%d): use pcv_searcher_search for "
                          "such a bound",
                          worst, mx, (int)PCV_MAX_RANGE_ROWS);
-            // as finish_pass grows the top-k lists: what the pass needed plus a quarter, at least twice what they were
-            uint64_t want = (uint64_t)mx + mx / 4 + 1024;
-            want = std::max<uint64_t>(want, (uint64_t)cap * 2);
+            // what the pass needed plus a quarter, at least twice what they were
+            const uint64_t want = std::max<uint64_t>(list_need(mx), (uint64_t)cap * 2);
             cap = (uint32_t)std::max<uint64_t>(mx, std::min<uint64_t>(want, (uint64_t)PCV_MAX_RANGE_ROWS));
             s->range_cap = cap;
             B = (int)std::min<uint64_t>((uint64_t)B, std::max<uint64_t>(1, kRangeBudget / cap));
-            rp.cap = cap;
-            enqueue_pass(s, qs, B, segs.data(), (int)segs.size(), 1, kernel, nullptr, false, nullptr, nullptr, false, &rp);
+            pass.B = B;
+            pass.range.cap = cap;
+            enqueue_pass(s, pass);
             PCV_REQUIRE(!finish_pass(s), "search_range: lists sized from the counts of a pass overflowed in its repeat");
         }
         const uint32_t runs = (cap + kRangeRun - 1) / kRangeRun;
@@ -2088,9 +2264,9 @@ void search_range(pcv_searcher* s, const float* queries, int n_queries, const in
             int64_t total = 0;
             heads.clear();
             for (uint32_t r = 0; r < used; ++r) {
-                const uint32_t n = s->pin_range_cnt[(size_t)q * runs + r];
+                const uint32_t n = s->pin_range_cnt.p[(size_t)q * runs + r];
                 total += n;
-                const pcv_hit_dev* at = s->pin_range + ((size_t)q * runs + r) * keep;
+                const pcv_hit_dev* at = s->pin_range.p + ((size_t)q * runs + r) * keep;
                 if (n > 0) heads.push_back({at, at + std::min(n, keep)});
             }
             const int64_t cnt = std::min(total, max_results);
@@ -2123,18 +2299,14 @@ void device_begin(pcv_searcher* s, const float* queries, int n_queries, const in
     check_search_args(s, queries, n_queries, k, "search_device_begin");
     PCV_REQUIRE(!s->pending.active, "search_device_begin: the previous pass was not collected (search_device_end)");
     sync_view(s);
-    PCV_HIP(hipSetDevice(s->ctx->device));
-    std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
-    const int kernel = pick_kernel(s, n_queries);
+    const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries, true);
     // Only a condition every rank evaluates alike may refuse: the ranks of a sharded search must all
     // take the same protocol (the exchanged payload differs by the overflow record).
-    if (n_queries > pass_queries(s, kernel, true))
+    if (n_queries > plan.qstep)
         PCV_FAIL(PCV_ERR_UNSUPPORTED, "search_device_begin: %d queries need more than one pass%s", n_queries,
                  s->wide_sharded ? " (wide sharded passes were allowed, but not every row of THIS rank has its int8 screening copy)" : "");
     const size_t n = (size_t)n_queries * k;
-    s->stats = pcv_scan_stats{};
-    s->stats.kernel_used = kernel;
-    if (segs.empty()) {
+    if (!open_search(s, plan)) {  // (each rank builds mid copies by its own statistics: the copy changes no result and no protocol)
         // this shard holds none of the selected rows: hand over the same layout — empty lists and a clear
         // overflow record — from pinned memory; search_device_end waits for the copy like for a pass
         ensure_workspace(s);
@@ -2146,8 +2318,9 @@ void device_begin(pcv_searcher* s, const float* queries, int n_queries, const in
         s->pending.done = true;
         return;
     }
-    maybe_build_mid_copies(s);  // (each rank by its own statistics: the copy changes no result and no protocol)
-    enqueue_pass(s, queries, n_queries, segs.data(), (int)segs.size(), k, kernel, out, false, out + n, nullptr, queries_on_device);
+    PassRequest pass = PassRequest(queries, n_queries, plan.segs, plan.kernel).top_k(k, out, false, out + n);
+    if (queries_on_device) pass.where = PassRequest::kDevice;
+    enqueue_pass(s, pass);
     if (s->view_parent) launch_view_remap(s->ctx->stream, out, (int64_t)n, s->d_ppos.p, s->view_rows);  // (before any exchange)
 }
 
@@ -2519,16 +2692,11 @@ void destroy_searcher(pcv_searcher* s) {
     for (auto& src : s->sources)
         for (auto& g : src.segs) free_segment(g);
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
-    if (s->pin) (void)hipHostFree(s->pin);
-    if (s->pin_pass) (void)hipHostFree(s->pin_pass);
-    if (s->pin_range) (void)hipHostFree(s->pin_range);
-    if (s->pin_range_cnt) (void)hipHostFree(s->pin_range_cnt);
-    if (s->d_pass) (void)hipFree(s->d_pass);
     if (s->d_max_norm_bits) (void)hipFree(s->d_max_norm_bits);
     for (auto& e : s->ev)
         if (e) (void)hipEventDestroy(e);
     if (s->view_parent) s->view_parent->live_views.fetch_sub(1);
-    delete s;  // (with every DevBuf of it)
+    delete s;  // (with every DevBuf and PinBuf of it)
 }
 }  // namespace
 
@@ -3188,25 +3356,20 @@ pcv_status pcv_searcher_search_device(pcv_searcher* s, const float* queries, int
         check_search_args(s, queries, n_queries, k, "search_device");
         PCV_REQUIRE(!s->pending.active, "search_device: a pass queued by search_device_begin has not been collected");
         sync_view(s);
-        PCV_HIP(hipSetDevice(s->ctx->device));
-        std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
-        const int kernel = pick_kernel(s, n_queries);
-        const int qstep = pass_queries(s, kernel);
-        s->stats = pcv_scan_stats{};
-        s->stats.kernel_used = kernel;
+        const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries);
+        const int qstep = plan.qstep;
         pcv_hit_dev* out = (pcv_hit_dev*)d_out;
-        if (segs.empty()) {
+        if (!open_search(s, plan)) {
             const pcv_hit_dev none{NAN, -1, -1};
             std::vector<pcv_hit_dev> hits((size_t)n_queries * k, none);
             PCV_HIP(hipMemcpyAsync(out, hits.data(), hits.size() * sizeof(pcv_hit_dev), hipMemcpyHostToDevice, s->ctx->stream));
             PCV_HIP(hipStreamSynchronize(s->ctx->stream));  // `hits` dies with this scope
             return;
         }
-        maybe_build_mid_copies(s);
         // results stay on the device: every pass writes its slice of the caller's list
         for (int q0 = 0; q0 < n_queries; q0 += qstep) {
             const int B = std::min(qstep, n_queries - q0);
-            run_pass(s, queries + (size_t)q0 * s->D, B, segs.data(), (int)segs.size(), k, kernel, out + (size_t)q0 * k, false);
+            run_pass(s, PassRequest(queries + (size_t)q0 * s->D, B, plan.segs, plan.kernel).top_k(k, out + (size_t)q0 * k, false));
             if (s->view_parent) launch_view_remap(s->ctx->stream, out + (size_t)q0 * k, (int64_t)B * k, s->d_ppos.p, s->view_rows);
         }
         if (s->view_parent) PCV_HIP(hipStreamSynchronize(s->ctx->stream));
@@ -3382,8 +3545,7 @@ struct pcv_comm {
     void* comm = nullptr;
     int world = 1, rank = 0;
     DevBuf<pcv_hit_dev> d_local, d_gathered, d_merged;
-    pcv_hit_dev* pin_hits = nullptr;
-    size_t pin_cap = 0;
+    PinBuf<pcv_hit_dev> pin_hits;
 };
 }  // extern "C++"
 
@@ -3424,7 +3586,6 @@ pcv_status pcv_comm_destroy(pcv_comm* c) {
         c->d_local.release();
         c->d_gathered.release();
         c->d_merged.release();
-        if (c->pin_hits) (void)hipHostFree(c->pin_hits);
         delete c;
     });
 }
@@ -3455,19 +3616,13 @@ static pcv_status search_sharded_impl(pcv_searcher* s, pcv_comm* c, const float*
         c->d_local.ensure(n + 1);
         c->d_gathered.ensure((n + 1) * c->world);
         c->d_merged.ensure(n + 1);
-        if (c->pin_cap < n + 1) {
-            if (c->pin_hits) (void)hipHostFree(c->pin_hits);
-            c->pin_hits = nullptr;
-            c->pin_cap = 0;
-            PCV_HIP(hipHostMalloc((void**)&c->pin_hits, (n + 1) * sizeof(pcv_hit_dev), hipHostMallocDefault));
-            c->pin_cap = n + 1;
-        }
+        c->pin_hits.ensure(n + 1);
         auto exchange = [&](const pcv_hit_dev* local, size_t nq, int flagged) {  // all-gather + merge + download, queued behind the local pass
             const size_t rec = nq * k + flagged;
             rccl_check(rccl().AllGather(local, c->d_gathered.p, rec * sizeof(pcv_hit_dev), /*ncclInt8*/ 0, c->comm, st),
                        "ncclAllGather");
             launch_merge(st, c->d_gathered.p, c->world, (int)nq, k, c->d_merged.p, flagged);
-            PCV_HIP(hipMemcpyAsync(c->pin_hits, c->d_merged.p, rec * sizeof(pcv_hit_dev), hipMemcpyDeviceToHost, st));
+            PCV_HIP(hipMemcpyAsync(c->pin_hits.p, c->d_merged.p, rec * sizeof(pcv_hit_dev), hipMemcpyDeviceToHost, st));
         };
         const int qstep = pass_queries(s, pick_kernel(s, n_queries), true);  // every rank computes the same split
         std::vector<pcv_hit_dev> all(n);
@@ -3509,8 +3664,8 @@ static pcv_status search_sharded_impl(pcv_searcher* s, pcv_comm* c, const float*
                     throw;
                 }
                 finish_pass(s);  // waits for the stream (pass, all-gather, merge, download); grows this rank's lists if needed
-                const bool again = c->pin_hits[nb].pos != 0;
-                if (!again) std::memcpy(all.data() + (size_t)q0 * k, c->pin_hits, nb * sizeof(pcv_hit_dev));
+                const bool again = c->pin_hits.p[nb].pos != 0;
+                if (!again) std::memcpy(all.data() + (size_t)q0 * k, c->pin_hits.p, nb * sizeof(pcv_hit_dev));
                 accumulate();
                 if (!again) break;
                 // Some rank's pass was incomplete (a list overflowed, or a speculative threshold did not hold — one flag

@@ -1253,14 +1253,10 @@ def test_screens_agree_with_the_oracle_across_shapes(ctx, oracle, D, B, k, metri
         np.testing.assert_array_equal(mine, theirs)
 
 
-def test_speculative_threshold_is_checked_and_repeated_when_it_fails(ctx, oracle, monkeypatch):
-    # The int8 scan starts from a guess taken from the seed rows (512 blocks of 32 rows spread evenly over the first
-    # segment) and checked at the end of the pass (scan.h).  Here the guess must fail for query 0: its ten best rows
-    # ARE seed rows, one in each of the ten seed groups (position in the sample mod k), so the seed score the guess is taken from has
-    # fewer than ten rows at or above it; the pass is repeated without the guess and the answer is the oracle's.
-    # Query 1 has its best rows outside the seed blocks: its guess holds.  Afterwards the same searcher answers
-    # unrelated queries without a repeat, and a searcher with the guess switched off (PCV_SCAN_FLAGS bit 5) returns the
-    # same hits.
+def guess_breaking_rows():
+    """400 000 x 128 Gaussian rows and two queries: the ten best rows of query 0 ARE seed rows of the int8 scan, one in each of the
+    ten seed groups, so its speculative threshold fails; those of query 1 lie outside the seed blocks.
+    -> (rows, queries, k, seed_rows, other_rows, rng)"""
     rng = np.random.default_rng(77)
     N, D, k = 400_000, 128, 10
     m = rng.standard_normal((N, D)).astype(np.float32)
@@ -1274,6 +1270,19 @@ def test_speculative_threshold_is_checked_and_repeated_when_it_fails(ctx, oracle
     for j in range(k):  # graded near-copies of the queries
         m[seed_rows[j]] = q[0] + (0.02 + 0.01 * j) * rng.standard_normal(D).astype(np.float32)
         m[other_rows[j]] = q[1] + (0.02 + 0.01 * j) * rng.standard_normal(D).astype(np.float32)
+    return m, q, k, seed_rows, other_rows, rng
+
+
+def test_speculative_threshold_is_checked_and_repeated_when_it_fails(ctx, oracle, monkeypatch):
+    # The int8 scan starts from a guess taken from the seed rows (512 blocks of 32 rows spread evenly over the first
+    # segment) and checked at the end of the pass (scan.h).  Here the guess must fail for query 0: its ten best rows
+    # ARE seed rows, one in each of the ten seed groups (position in the sample mod k), so the seed score the guess is taken from has
+    # fewer than ten rows at or above it; the pass is repeated without the guess and the answer is the oracle's.
+    # Query 1 has its best rows outside the seed blocks: its guess holds.  Afterwards the same searcher answers
+    # unrelated queries without a repeat, and a searcher with the guess switched off (PCV_SCAN_FLAGS bit 5) returns the
+    # same hits.
+    m, q, k, seed_rows, other_rows, rng = guess_breaking_rows()
+    D = m.shape[1]
     s = build(ctx, m, kernel="mfma")
     ids, scores, counts = s.search_vectors(None, k, q)
     st = s.last_stats()
