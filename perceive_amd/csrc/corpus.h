@@ -1,0 +1,106 @@
+// corpus.h — launcher interface of the kernels that build and maintain a corpus segment (corpus_kernels.hip): staging, row
+// scales, the screening and mid copies of scan.h, and hiding, updating, removing, viewing and gathering stored items by id.
+#pragma once
+#include "scan.h"
+
+namespace pcv {
+
+// ---- launchers (corpus_kernels.hip); they throw pcv::Error on a bad shape or a failed HIP call ----
+void launch_pack_rows(hipStream_t st, const float* rows_rowmajor, int64_t n, int D, int D4, float4* blk, uint32_t row0);
+void launch_iota_ids(hipStream_t st, int64_t* ids, int64_t first, int64_t n);
+// scales of the rows in blocks [first_block, nblocks) of a segment
+void launch_row_scales(hipStream_t st, const float4* blk, uint32_t first_block, uint32_t nblocks, uint32_t nrows, int D4,
+                       int metric, float* scale, uint32_t* max_norm_bits);
+// screening copy of the rows in blocks [first_block, nblocks): bf16(row * scale), zeros where scale == 0
+void launch_coarse_pack(hipStream_t st, const float4* blk, const float* scale, uint4* blk16, uint32_t first_block, uint32_t nblocks,
+                        int D4);
+// int8 screening copy + quantisation scales of the rows in blocks [first_block, nblocks)
+void launch_coarse_pack8(hipStream_t st, const float4* blk, const float* scale, uint4* blk8, float* scale8, uint32_t first_block,
+                         uint32_t nblocks, int D4);
+// the 6-bit copy (scale6 included) of blocks [first_block, nblocks) / of blocks[0..n), from the int8 copy and the f32 rows
+void launch_pack6(hipStream_t st, const float4* blk, const float* scale, const uint4* blk8, const float* scale8, uint4* blk6, float4* scale6,
+                  uint32_t first_block, uint32_t nblocks, int D4);
+void launch_repack6_blocks(hipStream_t st, const float4* blk, const float* scale, const uint4* blk8, const float* scale8, const uint32_t* blocks,
+                           uint32_t n, uint4* blk6, float4* scale6, int D4);
+size_t six_copy_bytes(uint32_t nblocks, int Dp);  // bytes of blk6 for that many blocks
+// mid copy + its scales of rows [first_row, nrows) of a segment
+// (scale8: the quantisation scales of the segment's int8 copy if it covers these rows — the copy is then made block by block with
+// the blocks' scales — or nullptr: row by row, each with its own)
+void launch_mid_pack(hipStream_t st, const float4* blk, const float* scale, const float* scale8, uint4* mid16, float* scale16,
+                     uint32_t first_row, uint32_t nrows, int D4);
+// ---- hidden items (pcv_searcher_hide_ids) ----
+// A batch of ids is looked up in an open-addressed table: capacity a power of two (mask = capacity - 1), linear probing from
+// id_hash, kIdEmpty in free slots; a batch that holds kIdEmpty itself says so with has_empty instead of storing it.
+constexpr int64_t kIdEmpty = INT64_MIN;
+__host__ __device__ static inline uint32_t id_hash(int64_t id, uint32_t mask) {
+    return (uint32_t)(((uint64_t)id * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+}
+// rows [row0, row1) of a segment whose id is in the table -> out_rows (the first `cap`), their number -> *out_n (zeroed here)
+void launch_match_ids(hipStream_t st, const int64_t* ids, uint32_t row0, uint32_t row1, const int64_t* table, uint32_t tmask,
+                      bool has_empty, uint32_t* out_rows, uint32_t* out_n, uint32_t cap);
+// rows[0..n) become not searchable: scale 0, zeros in the screening copy (rows < copied_rows), mid scale NaN (rows < mid_rows)
+void launch_hide_rows(hipStream_t st, const uint32_t* rows, uint32_t n, float* scale, uint4* blk8, uint4* blk16, uint32_t copied_rows,
+                      float* scale16, uint32_t mid_rows, int D4);
+// rows[0..n) searchable again: their scales as launch_row_scales computes them
+void launch_restore_scales(hipStream_t st, const float4* blk, const uint32_t* rows, uint32_t n, int D4, int metric, float* scale);
+// ... the int8 copy of blocks[0..n), whole blocks (new block scales)
+void launch_repack8_blocks(hipStream_t st, const float4* blk, const float* scale, const uint32_t* blocks, uint32_t n, uint4* blk8,
+                           float* scale8, int D4);
+// ... the bf16 copy of rows[0..n)
+void launch_repack16_rows(hipStream_t st, const float4* blk, const float* scale, const uint32_t* rows, uint32_t n, uint4* blk16, int D4);
+// ... the mid copy: items are blocks (scale8 != nullptr: every row of each, with the block's scale) or rows; rows >= mid_rows skipped
+void launch_repack_mid(hipStream_t st, const float4* blk, const float* scale, const float* scale8, const uint32_t* items, uint32_t n,
+                       uint32_t mid_rows, uint4* mid16, float* scale16, int D4);
+// ---- updated items (pcv_searcher_update_rows) ----
+// launch_match_ids whose table also carries each id's slot in the batch (vals[h]; empty_slot for kIdEmpty): rows [row0, row1) of
+// a segment whose id is in the batch -> (out_rows[i], out_slots[i]) for the first `cap`, their number -> *out_n (zeroed here)
+void launch_match_id_slots(hipStream_t st, const int64_t* ids, uint32_t row0, uint32_t row1, const int64_t* table, const uint32_t* vals,
+                           uint32_t tmask, bool has_empty, uint32_t empty_slot, uint32_t* out_rows, uint32_t* out_slots,
+                           uint32_t* out_n, uint32_t cap);
+// rows[i] of a segment takes staged row (slots[i] & 0x7fffffff) - slot0 of `stage` ([.][D] f32) and its scale as launch_row_scales
+// computes it (max_norm_bits raised likewise); bit 31 of slots[i]: the row's id is hidden, its scale is 0
+void launch_update_rows(hipStream_t st, const float* stage, uint32_t slot0, const uint32_t* rows, const uint32_t* slots, uint32_t n,
+                        int D, int D4, int metric, float4* blk, float* scale, uint32_t* max_norm_bits);
+// ---- views (pcv_searcher_create_view) ----
+// Selection of the rows of a segment whose id is in the table, in row order: scratch flags4[view_tiles(nrows) * 256] and
+// tile_cnt[view_tiles(nrows)]; launch_view_select leaves the tiles' offsets in tile_cnt and the number of rows in *total, then
+// launch_view_compact writes the rows, ascending, to sel[0..*total).
+// `invert`: the rows whose id is NOT in the table are selected (pcv_searcher_remove_ids: the rows that stay).  `off0`: flags4 and
+// tile_off point at a later tile of the segment; rows are then numbered from that tile's first row and written from
+// sel[tile_off[tile] - off0] on.
+constexpr int kViewTile = 1024;  // rows per tile
+uint32_t view_tiles(uint32_t nrows);
+void launch_view_select(hipStream_t st, const int64_t* ids, uint32_t nrows, const int64_t* table, uint32_t tmask, bool has_empty,
+                        uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total, bool invert = false);
+void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel,
+                         uint32_t off0 = 0);
+// rows [dst_row0, dst_row0 + n_sel) of a view segment take rows sel[0..n_sel) of a parent segment (pieces, scale, id; parent
+// position pos0 + row -> dst_ppos[row of the view segment], unless dst_ppos is nullptr); rows [dst_row0 + n_sel, dst_end) become
+// padding
+void launch_view_gather(hipStream_t st, const float4* src_blk, const float* src_scale, const int64_t* src_ids, int64_t src_id0,
+                        int64_t src_pos0, const uint32_t* sel, uint32_t n_sel, int D4, uint32_t dst_row0, uint32_t dst_end,
+                        float4* dst_blk, float* dst_scale, int64_t* dst_ids, int64_t* dst_ppos);
+// ---- removed items (pcv_searcher_remove_ids) ----
+// rows [dst_row0, dst_end) of a segment take the rows at the same place inside their blocks of a bounce buffer whose block 0
+// stands for block dst_row0 / 32 (pieces, scale, id): the second launch of a compaction chunk, after launch_view_gather filled
+// the bounce buffer with dst_row0 % 32 as its first row
+void launch_compact_store(hipStream_t st, const float4* bounce_blk, const float* bounce_scale, const int64_t* bounce_ids, int D4,
+                          uint32_t dst_row0, uint32_t dst_end, float4* dst_blk, float* dst_scale, int64_t* dst_ids);
+// hits[0..n): pos in [0, nrows) -> ppos[pos]
+void launch_view_remap(hipStream_t st, pcv_hit_dev* hits, int64_t n, const int64_t* ppos, int64_t nrows);
+void launch_synth_fill(hipStream_t st, float4* blk, uint32_t nrows, uint32_t row0, int D, int D4, uint64_t seed,
+                       int64_t first_row, int normalize, uint32_t n_clusters, float noise, float amp_lo = 0.0f, float amp_hi = 0.0f);
+void launch_gather_rows(hipStream_t st, const SegDesc* d_segs, int nseg, const int64_t* d_pos, int64_t n, int D,
+                        int D4, float* out_rows, int64_t* out_ids);
+// ---- search by example (pcv_searcher_like_queries) ----
+// One stored row that goes into a query vector, with its weight: row `row` of segs[seg].
+struct LikeMember {
+    uint32_t seg, row;
+    float w;
+};
+// out[q][0..D) (row-major f32, device) = sum over members[first[q] .. first[q + 1]) of w * row, accumulated per component with one
+// f32 fused multiply-add per member, in list order (first: [n_queries + 1], ascending from 0).  Same input, same bits.
+void launch_like_queries(hipStream_t st, const SegDesc* d_segs, int nseg, const LikeMember* d_members, const uint32_t* d_first,
+                         int n_queries, int D, int D4, float* out);
+
+}  // namespace pcv

@@ -11,13 +11,6 @@
 #include "encoder.h"
 #include "synth.h"
 
-// Timing experiments (tools/exp_build_enc.sh <n> on the GPU box; results are WRONG in these builds): pieces of gemm_f32_kernel
-// taken out to see what the rest costs — 10: no epilogue (one value per lane stored), 11: no operand loads in the K loop,
-// 12: no loads, no staging writes and no barriers either (fragment reads + multiplies only).  0 = the product.
-#ifndef PCV_ENC_EXP
-#define PCV_ENC_EXP 0
-#endif
-
 namespace pcv {
 namespace {
 
@@ -261,10 +254,6 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(const float* __restric
 
     const int nk = K / BK;
     for (int kt = 0; kt < nk; ++kt) {
-#if PCV_ENC_EXP == 12
-        if (kt == 0)
-#endif
-        {
         __syncthreads();  // previous step's fragment reads are done
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -272,14 +261,10 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(const float* __restric
             *(f32x4*)&Ws[(srow + 32 * u) * LDT + c4 * 4] = rw[u];
         }
         __syncthreads();
-        }
         // next step's global loads fly under this step's MFMAs (the last step re-reads its own tile instead of branching: a
         // conditional load made the compiler park the staging registers in scratch).  The scheduling barrier keeps them HERE:
         // left alone, the scheduler sinks the loads below the multiplies to the top of the next step — right in front of the
         // LDS writes that wait for them — to save their registers, and the prefetch is gone (round 4)
-#if PCV_ENC_EXP == 11 || PCV_ENC_EXP == 12
-        if (kt == 1000)
-#endif
         fetch(min(kt + 1, nk - 1));
         __builtin_amdgcn_sched_barrier(0);
         float af[2][16], bf[2][16];
@@ -304,19 +289,6 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(const float* __restric
                     acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[a][s], bf[b][s], acc[a][b], 0, 0, 0);
     }
 
-#if PCV_ENC_EXP == 10
-    {
-        float keep = 0.0f;
-#pragma unroll
-        for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-            for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) keep += acc[a2][b2][r];
-        C[(size_t)(m0 + (tid >> 1)) * N + n0 + (tid & 1) * 64 + lane] = keep;
-        return;
-    }
-#endif
     if (m0 + BM <= M) {  // full tile (workgroup-uniform): wide epilogue through LDS
         __syncthreads();  // every wave is done with the last K-step's fragments
         store_quarter_wide<EPI>(acc, bias, resid, C, N, m0 + wr * 64, n0 + wc * 64, smem + wave * 32 * LDE, lane);

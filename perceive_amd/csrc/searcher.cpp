@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "corpus.h"
 #include "scan.h"
 
 using namespace pcv;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers and scratch of the kernels in a -save-temps gfx950 assembly file:
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -save-temps -c csrc/scan_kernels.hip -o /tmp/x.o && python tools/kernel_regs.py *gfx950*.s [name filter]"""
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -save-temps -c csrc/scan_kernels.hip -o /tmp/x.o   (or corpus_kernels.hip, encoder_kernels.hip) && python tools/kernel_regs.py *gfx950*.s [name filter]"""
 import re
 import sys
 
