@@ -8,6 +8,7 @@
 // Errors: the reference returns Result<_, ModelError/DbError/eyre::Report>; here a failing status
 // throws perceive::Error carrying pcv_last_error().
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <array>
 #include <memory>
@@ -136,6 +137,27 @@ inline std::vector<SearchItem> search_range_handle(pcv_searcher* h, const std::v
     return out;
 }
 
+// Distinct results on a searcher or a view handle (pcv_searcher_search_distinct): the ranked list of search_vector walked best first,
+// an item kept iff its cosine with every item kept before it is below `threshold`; at most `pool` entries are examined (0: the
+// default, min(PCV_MAX_DISTINCT_POOL, max(128, 8 * num_results))).  `similar`, if given: per hit, the examined items dropped in its favour.
+inline std::vector<SearchItem> search_distinct_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results,
+                                                      const std::vector<float>& vector, float threshold, size_t pool,
+                                                      std::vector<int32_t>* similar) {
+    if (similar) similar->clear();
+    if (sources.empty() || num_results == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    if (pool == 0) pool = std::min<size_t>(PCV_MAX_DISTINCT_POOL, std::max<size_t>(128, 8 * num_results));
+    std::vector<int64_t> ids(num_results);
+    std::vector<float> scores(num_results);
+    std::vector<int32_t> sim(num_results);
+    int32_t count = 0;
+    check(pcv_searcher_search_distinct(h, vector.data(), 1, sources.data(), (int)sources.size(), (int)num_results, threshold, (int)pool,
+                                       ids.data(), scores.data(), &count, sim.data(), nullptr, nullptr));
+    std::vector<SearchItem> out;
+    for (int i = 0; i < count; ++i) out.push_back({ids[(size_t)i], scores[(size_t)i]});
+    if (similar) similar->assign(sim.begin(), sim.begin() + count);
+    return out;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -174,6 +196,11 @@ public:
     std::vector<SearchItem> search_range(const std::vector<int64_t>& sources, float bound, size_t max_results, const std::vector<float>& vector,
                                          bool* more = nullptr) const {
         return search_range_handle(h_, sources, bound, max_results, vector, more);
+    }
+    // the view's best items with near-duplicates collapsed (search_distinct_handle)
+    std::vector<SearchItem> search_vector_distinct(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
+        return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
     }
     // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
     std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
@@ -258,6 +285,11 @@ public:
     std::vector<SearchItem> search_range(const std::vector<int64_t>& sources, float bound, size_t max_results, const std::vector<float>& vector,
                                          bool* more = nullptr) const {
         return search_range_handle(h_, sources, bound, max_results, vector, more);
+    }
+    // the best items with near-duplicates collapsed on the device (search_distinct_handle)
+    std::vector<SearchItem> search_vector_distinct(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
+        return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
     }
     // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the
     // item itself is the first hit unless `exclude`.  nullopt: no row carries the id.

@@ -390,6 +390,34 @@ pcv_status pcv_searcher_search_range(pcv_searcher* s, const float* queries, int 
                                      const float* bounds, int64_t max_results, int64_t* out_ids, float* out_scores,
                                      int64_t* out_counts, uint8_t* out_more);
 
+/* Distinct results: the exact top-k with near-duplicates collapsed on the device.
+ * Per query, L is the ranked list pcv_searcher_search returns (canonical score, ties -> lower position; the searchable rows of the
+ * selected sources: hidden rows and a view's restriction apply as everywhere).  L is walked best first with an empty kept set: a
+ * row is KEPT iff dup(row, j) is false for every kept row j, otherwise it is dropped and counted for the best-ranked kept row it
+ * duplicates; the walk stops right after the num_results-th kept row, or after `pool` entries of L.
+ *   dup(a, b) = canonical cosine of the two stored f32 rows >= (double)threshold
+ * — f64, products exact, sums in feature order, for BOTH metrics: near-duplicate is a scale-free notion and the
+ * rows of a dot-metric corpus differ in norm.  A row without a cosine (zero or non-finite norm) duplicates nothing.
+ *   threshold    in (-1, 1]; at exactly 1 even equal rows collapse only where the f64 quotient rounds to 1 or above (about two rows
+ *                in three): use the f32 below 1 for "exact copies"
+ *   pool         num_results .. PCV_MAX_DISTINCT_POOL: entries of L the walk may examine
+ *   out_ids      [n_queries][num_results] the kept rows, best first, -1 behind them;  out_scores likewise, NaN behind them (may be
+ *                NULL) — ids and scores are bit for bit what pcv_searcher_search reports for those rows
+ *   out_counts   [n_queries] rows kept
+ *   out_similar  [n_queries][num_results] examined rows dropped in favour of this hit, 0 behind the results (may be NULL)
+ *   out_examined [n_queries] entries of L examined (may be NULL)
+ *   out_more     [n_queries] 1: the walk stopped at `pool` with fewer than num_results kept and L had more rows (may be NULL)
+ * A NULL searcher, no queries, num_results outside [1, PCV_MAX_RESULTS], pool outside [num_results, PCV_MAX_DISTINCT_POOL] or a
+ * threshold that is NaN or outside (-1, 1] give PCV_ERR_INVALID before any device work; a searcher with pending rows fails as in
+ * pcv_searcher_search.  A call makes at most ceil(pool / PCV_MAX_RESULTS) passes per group of queries (DESIGN.md §4 "Distinct
+ * results") — each followed by a select step on the device; the host reads back counters only — and one short pass more where
+ * out_more has to be decided.  Works on views (a view walks its own rows).
+ * Not in scope: a sharded form (the walk needs the rows of every shard's hits) and device-resident output. */
+enum { PCV_MAX_DISTINCT_POOL = 4096 };
+pcv_status pcv_searcher_search_distinct(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                        int num_results, float threshold, int pool, int64_t* out_ids, float* out_scores,
+                                        int32_t* out_counts, int32_t* out_similar, int32_t* out_examined, uint8_t* out_more);
+
 /* Search by example (`perceive search --like <id>`, perceive-cli/cmd/search.rs:17-19, 64-86: the stored embedding of an item is
  * the query): query vectors are built on the device from rows the searcher already holds, found by item id.
  * Query q is built from the examples example_ids[offsets[q] .. offsets[q+1]) with the weights weights[...] (NULL: all 1);

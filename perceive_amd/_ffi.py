@@ -138,6 +138,7 @@ SYMBOLS = {
     "pcv_searcher_set_tuning": (C.c_int, [_P, C.c_uint32]),
     "pcv_searcher_search": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, _I64P, _F32P, _INTP]),
     "pcv_searcher_search_range": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, _F32P, C.c_int64, _I64P, _F32P, _I64P, _U8P]),
+    "pcv_searcher_search_distinct": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int, _I64P, _F32P, _INTP, _INTP, _INTP, _U8P]),
     "pcv_searcher_like_queries": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _F32P, _P, _U8P, _I64P]),
     "pcv_searcher_search_like": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _INTP, _U8P]),
     "pcv_searcher_set_shard_offset": (C.c_int, [_P, C.c_int64]),

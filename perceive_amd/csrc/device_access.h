@@ -1,5 +1,5 @@
-// device_access.h — the small device accessors and vector types the kernel files (scan_kernels.hip, corpus_kernels.hip) share,
-// and the two host helpers of their launchers.  Everything here is inlined: the file defines no symbol.
+// device_access.h — the small device accessors and vector types the kernel files (scan_kernels.hip, corpus_kernels.hip) share
+// (among them the one copy of the canonical score's last step), and the two host helpers of their launchers.  Everything here is inlined: the file defines no symbol.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -86,6 +86,22 @@ template <class T>
 __device__ __forceinline__ const T* uniform_ptr(const T* ptr) {  // a wave-uniform pointer, moved to scalar registers
     const uint64_t v = (uint64_t)ptr;
     return (const T*)(((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v));
+}
+
+// the canonical order of two rows: descending score, ties -> lower global position
+__device__ __forceinline__ bool better(double sa, int64_t pa, double sb, int64_t pb) {
+    return sa > sb || (sa == sb && pa < pb);
+}
+
+// canonical score from the two feature-order f64 sums (oracle/scan.c:orc_canonical_score); NaN: undefined
+__device__ __forceinline__ double finish_score(int metric, double dot, double nx, double nq) {
+    const double inf = __builtin_inf();
+    if (metric == PCV_METRIC_DOT) return (dot < inf && dot > -inf && nq < inf) ? dot : __builtin_nan("");
+    if (nq >= 0x1p-126 && nq < inf && nx >= 0x1p-126 && nx < inf) {
+        const double cc = dot / (sqrt(nq) * sqrt(nx));
+        if (cc < inf && cc > -inf) return cc;
+    }
+    return __builtin_nan("");
 }
 
 }  // namespace

@@ -227,6 +227,30 @@ struct ScanParams {
 };
 constexpr uint32_t kSpecFailed = 0xffffffffu;  // cnt_host value of a query whose speculative threshold did not hold
 
+// Distinct results (pcv_searcher_search_distinct; DESIGN.md §4 "Distinct results"): the ranked list of a query is walked best
+// first, kMaxK hits a pass, and a row is kept iff its canonical cosine with every row kept before it is below the threshold.
+// What the walk of one query has come to, between the passes (device) and as the host reads it after each (pinned):
+//   kept, examined : rows kept; entries of the ranked list walked
+//   flags          : kDistinctFull: the num_results-th row was kept; kDistinctEnd: the list ended — either way the query is
+//                    finished and distinct_select_kernel leaves its record, kept rows and counters as they are
+//   last_score/pos : the last entry walked, the ceiling of the query's next pass (scan.h, CeilRec)
+struct DistinctRec {
+    uint32_t kept, examined, flags, pad;
+    double last_score;
+    int64_t last_pos;
+};
+constexpr uint32_t kDistinctFull = 1u, kDistinctEnd = 2u;
+// The select step's own arguments (by value: nothing in it is indexed at run time).
+struct DistinctArgs {
+    DistinctRec* rec;        // [B]
+    DistinctRec* rec_host;   // [B] pinned host mirror, written after every pass
+    pcv_hit_dev* kept;       // [B][kMaxK] the kept rows, best first, as the pass listed them
+    double* kept_norm;       // [B][kMaxK] their canonical |x|^2 (f64, feature order)
+    int32_t* similar;        // [B][kMaxK] walked rows dropped in favour of each
+    int num_results;
+    double threshold;
+};
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -265,6 +289,8 @@ void launch_rescore_select(hipStream_t st, const ScanParams& p, const ScanParams
 // ---- range search (pcv_searcher_search_range) ----
 void launch_range_thresholds(hipStream_t st, const ScanParams& p, const ScanParams* dp);  // RangeRec::tau -> tau, tau_c
 void launch_range_select(hipStream_t st, const ScanParams& p, const ScanParams* dp);
+// ---- distinct results (distinct_kernels.hip): walks the p.k hits per query the pass left in p.out ----
+void launch_distinct_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DistinctArgs& a);
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);
 void launch_merge(hipStream_t st, const pcv_hit_dev* lists, int n_shards, int B, int k, pcv_hit_dev* out,
                   int flagged = 0);

@@ -2126,20 +2126,8 @@ __global__ __launch_bounds__(NH == 2 ? 256 : 768, 3) void scan_mfma8_hold_kernel
     }
 }
 
-__device__ __forceinline__ bool better(double sa, int64_t pa, double sb, int64_t pb) {
-    return sa > sb || (sa == sb && pa < pb);
-}
-
-// canonical score from the two feature-order f64 sums (oracle/scan.c:orc_canonical_score); NaN: undefined
-__device__ __forceinline__ double finish_score(int metric, double dot, double nx, double nq) {
-    const double inf = __builtin_inf();
-    if (metric == PCV_METRIC_DOT) return (dot < inf && dot > -inf && nq < inf) ? dot : __builtin_nan("");
-    if (nq >= 0x1p-126 && nq < inf && nx >= 0x1p-126 && nx < inf) {
-        const double cc = dot / (sqrt(nq) * sqrt(nx));
-        if (cc < inf && cc > -inf) return cc;
-    }
-    return __builtin_nan("");
-}
+// (better() and finish_score(), the canonical score from the two feature-order f64 sums, are in device_access.h: the select
+// kernel of distinct_kernels.hip ranks and compares by the same numbers)
 
 // Canonical f64 scores of listed survivors 0..ns) of one query, by a workgroup of 256 threads: entry(si) = (segment << 32) | row,
 // keep(si, entry, score) is called once per survivor, by one thread.  `sq`: the raw query in LDS; `stage`: COOP only, LDS room for

@@ -234,6 +234,10 @@ struct pcv_searcher {
     uint32_t range_cap = 0;
     PinBuf<pcv_hit_dev> pin_range;
     PinBuf<uint32_t> pin_range_cnt;
+    // distinct results (pcv_searcher_search_distinct): what the walks of one group of queries have come to (scan.h, DistinctRec) —
+    // records | kept hits | their norms | their counters, on the device and (records after every pass, the rest once) in pinned memory
+    DevBuf<uint8_t> d_distinct;
+    PinBuf<uint8_t> pin_distinct;
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -2292,6 +2296,113 @@ void search_range(pcv_searcher* s, const float* queries, int n_queries, const in
     }
 }
 
+// ---- distinct results (pcv_searcher_search_distinct; DESIGN.md §4 "Distinct results") ----
+// The state block of one group of up to kMfmaQueries queries (scan.h, DistinctArgs), the same layout on both sides.
+struct DistinctLayout {
+    static constexpr size_t Q = kMfmaQueries;
+    static constexpr size_t off_rec = 0;
+    static constexpr size_t off_kept = off_rec + Q * sizeof(DistinctRec);
+    static constexpr size_t off_sim = off_kept + Q * kMaxK * sizeof(pcv_hit_dev);
+    static constexpr size_t off_norm = off_sim + Q * kMaxK * sizeof(int32_t);  // (the device's alone: never downloaded)
+    static constexpr size_t total = off_norm + Q * kMaxK * sizeof(double);
+};
+
+// The ranked list of every query is walked kMaxK hits a pass: the first pass is a plain top-k pass, every later one ranks the rows
+// behind the last hit walked (its ceiling, as in search_hits), and after each the select step (distinct_kernels.hip) walks the
+// pass's lists on the device against the rows kept so far.  What comes back after a pass is one record per query — kept, examined,
+// finished or not, the last hit walked —; the kept rows and their counters come down once, at the end.  A query that is finished
+// (num_results kept, or its list at an end) gets the ceiling "nothing ranks after it" and the select step leaves it alone.
+void search_distinct(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, int k, float threshold,
+                     int pool, int64_t* out_ids, float* out_scores, int32_t* out_counts, int32_t* out_similar, int32_t* out_examined,
+                     uint8_t* out_more) {
+    check_search_args(s, queries, n_queries, k, "search_distinct");
+    s->stats = pcv_scan_stats{};  // (also when the kernel is refused)
+    const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries);
+    auto blank = [&](int q, int from) {
+        for (int j = from; j < k; ++j) {
+            if (out_ids) out_ids[(size_t)q * k + j] = -1;
+            if (out_scores) out_scores[(size_t)q * k + j] = NAN;
+            if (out_similar) out_similar[(size_t)q * k + j] = 0;
+        }
+    };
+    if (!open_search(s, plan)) {
+        for (int q = 0; q < n_queries; ++q) {
+            blank(q, 0);
+            if (out_counts) out_counts[q] = 0;
+            if (out_examined) out_examined[q] = 0;
+            if (out_more) out_more[q] = 0;
+        }
+        return;
+    }
+    using L = DistinctLayout;
+    hipStream_t st = s->ctx->stream;
+    s->d_distinct.ensure(L::total);
+    s->pin_distinct.ensure(L::off_norm);
+    DistinctRec* rec = reinterpret_cast<DistinctRec*>(s->pin_distinct.p + L::off_rec);
+    DistinctArgs args{};
+    args.rec = reinterpret_cast<DistinctRec*>(s->d_distinct.p + L::off_rec);
+    args.rec_host = rec;
+    args.kept = reinterpret_cast<pcv_hit_dev*>(s->d_distinct.p + L::off_kept);
+    args.similar = reinterpret_cast<int32_t*>(s->d_distinct.p + L::off_sim);
+    args.kept_norm = reinterpret_cast<double*>(s->d_distinct.p + L::off_norm);
+    args.num_results = k;
+    args.threshold = (double)threshold;
+    const pcv_hit_dev* kept = reinterpret_cast<const pcv_hit_dev*>(s->pin_distinct.p + L::off_kept);
+    const int32_t* similar = reinterpret_cast<const int32_t*>(s->pin_distinct.p + L::off_sim);
+    std::vector<CeilRec> ceil;
+    for (int q0 = 0; q0 < n_queries; q0 += plan.qstep) {
+        const int B = std::min(plan.qstep, n_queries - q0);
+        const float* qs = queries + (size_t)q0 * s->D;
+        for (int q = 0; q < B; ++q) rec[q] = DistinctRec{0, 0, 0, 0, INFINITY, -1};
+        PCV_HIP(hipMemcpyAsync(args.rec, rec, (size_t)B * sizeof(DistinctRec), hipMemcpyHostToDevice, st));
+        // A query still walking after a pass has walked every hit of every pass so far: `walked` is the same for all of them.
+        bool pending = true;
+        for (int walked = 0; pending && walked < pool; walked += kMaxK) {
+            const int kk = std::min(kMaxK, pool - walked);
+            if (walked > 0) {
+                ceil.resize((size_t)B);
+                std::vector<pcv_hit_dev> last((size_t)B);
+                for (int q = 0; q < B; ++q) last[(size_t)q] = rec[q].flags ? pcv_hit_dev{NAN, -1, -1} : pcv_hit_dev{rec[q].last_score, rec[q].last_pos, -1};
+                next_ceilings(s, qs, B, last.data(), ceil.data());
+            }
+            run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(kk, nullptr, false, nullptr, walked > 0 ? ceil.data() : nullptr));
+            // (the pass block is the pass's to allocate and to grow: its device address is read after the pass, never before)
+            launch_distinct_select(st, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
+            PCV_HIP(hipStreamSynchronize(st));
+            PCV_HIP(hipGetLastError());
+            pending = false;
+            for (int q = 0; q < B; ++q) pending = pending || rec[q].flags == 0;
+        }
+        // out_more: a walk that stopped at `pool` without its num_results and without seeing its list end.  Whether the list had
+        // another row is one more, short pass under the same kind of ceiling: one hit per query.
+        std::vector<uint8_t> more((size_t)B, 0);
+        if (pending && out_more) {
+            ceil.resize((size_t)B);
+            std::vector<pcv_hit_dev> last((size_t)B);
+            for (int q = 0; q < B; ++q) last[(size_t)q] = rec[q].flags ? pcv_hit_dev{NAN, -1, -1} : pcv_hit_dev{rec[q].last_score, rec[q].last_pos, -1};
+            next_ceilings(s, qs, B, last.data(), ceil.data());
+            run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(1, nullptr, true, nullptr, ceil.data()));
+            for (int q = 0; q < B; ++q) more[(size_t)q] = (rec[q].flags == 0 && s->pin->hits[q].pos >= 0) ? 1 : 0;
+        }
+        PCV_HIP(hipMemcpyAsync(s->pin_distinct.p + L::off_kept, s->d_distinct.p + L::off_kept, L::off_norm - L::off_kept, hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        for (int q = 0; q < B; ++q) {
+            const int n = (int)rec[q].kept;
+            const size_t o = (size_t)(q0 + q) * k;
+            for (int j = 0; j < n; ++j) {
+                const pcv_hit_dev& h = kept[(size_t)q * kMaxK + j];
+                if (out_ids) out_ids[o + j] = h.id;
+                if (out_scores) out_scores[o + j] = reported_score(s->metric, s->D, h.score);
+                if (out_similar) out_similar[o + j] = similar[(size_t)q * kMaxK + j];
+            }
+            blank(q0 + q, n);
+            if (out_counts) out_counts[q0 + q] = n;
+            if (out_examined) out_examined[q0 + q] = (int32_t)rec[q].examined;
+            if (out_more) out_more[q0 + q] = more[(size_t)q];
+        }
+    }
+}
+
 void sync_view(pcv_searcher* v);
 
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.
@@ -3272,6 +3383,26 @@ pcv_status pcv_searcher_search_range(pcv_searcher* s, const float* queries, int 
         PCV_REQUIRE(!s->pending.active, "search_range: a pass queued by search_device_begin has not been collected");
         sync_view(s);
         search_range(s, queries, n_queries, source_ids, n_sources, bounds, max_results, out_ids, out_scores, out_counts, out_more);
+    });
+}
+
+pcv_status pcv_searcher_search_distinct(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                        int num_results, float threshold, int pool, int64_t* out_ids, float* out_scores,
+                                        int32_t* out_counts, int32_t* out_similar, int32_t* out_examined, uint8_t* out_more) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "search_distinct: searcher is NULL");
+        PCV_REQUIRE(queries != nullptr && n_queries > 0, "search_distinct: no queries");
+        PCV_REQUIRE(num_results >= 1 && num_results <= (int)PCV_MAX_RESULTS, "search_distinct: num_results %d outside [1,%d]", num_results,
+                    (int)PCV_MAX_RESULTS);
+        PCV_REQUIRE(pool >= num_results && pool <= (int)PCV_MAX_DISTINCT_POOL, "search_distinct: pool %d outside [num_results = %d, %d]", pool,
+                    num_results, (int)PCV_MAX_DISTINCT_POOL);
+        PCV_REQUIRE(threshold == threshold, "search_distinct: threshold is NaN");
+        PCV_REQUIRE(threshold > -1.0f && threshold <= 1.0f, "search_distinct: threshold %g outside (-1, 1]", (double)threshold);
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "search_distinct: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        search_distinct(s, queries, n_queries, source_ids, n_sources, num_results, threshold, pool, out_ids, out_scores, out_counts, out_similar,
+                        out_examined, out_more);
     });
 }
 

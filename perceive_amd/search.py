@@ -12,6 +12,8 @@ import numpy as np
 from . import _ffi
 from .context import Context
 
+PCV_MAX_DISTINCT_POOL = 4096  # include/perceive_hip.h
+
 _METRICS = {"cosine": _ffi.METRIC_COSINE, "dot": _ffi.METRIC_DOT}
 _KERNELS = {"auto": _ffi.KERNEL_AUTO, "wave": _ffi.KERNEL_WAVE, "mfma": _ffi.KERNEL_MFMA}
 STAGING_SOURCE = -(1 << 63)  # PCV_STAGING_SOURCE
@@ -370,6 +372,49 @@ class Searcher:
         if not found[0]:
             raise KeyError("Item not found")
         return self.search_range_vector(sources, bound, vec[0], max_results)
+
+    # ---- distinct results (pcv_searcher_search_distinct) ---------------------------------------------
+    # The exact top-k with near-duplicates collapsed on the device: the same article under five URLs is one hit.
+    def search_distinct(self, sources, num_results, vectors, threshold, pool=None):
+        """The ranked list of search_vectors walked best first, a row kept iff its canonical cosine with every row kept before it
+        is below `threshold` (in (-1, 1]); at most `pool` entries are examined (default min(PCV_MAX_DISTINCT_POOL, max(128,
+        8 * num_results))).  vectors [B, dim] -> (ids [B, k] int64, scores [B, k] f32, counts [B] int32, similar [B, k] int32:
+        examined rows dropped in favour of each hit, examined [B] int32, more [B] bool: the walk stopped at `pool` short of
+        num_results although the list had more rows).  Ids and scores are those search_vectors returns for the same rows."""
+        q = np.ascontiguousarray(vectors, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [B, {self.dim}]")
+        B, k = q.shape[0], int(num_results)
+        if pool is None:
+            pool = min(PCV_MAX_DISTINCT_POOL, max(128, 8 * k))
+        ids = np.full((B, max(k, 0)), -1, dtype=np.int64)
+        scores = np.full((B, max(k, 0)), np.nan, dtype=np.float32)
+        similar = np.zeros((B, max(k, 0)), dtype=np.int32)
+        counts = np.zeros(max(B, 1), dtype=np.int32)
+        examined = np.zeros(max(B, 1), dtype=np.int32)
+        more = np.zeros(max(B, 1), dtype=np.uint8)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_distinct(
+                self._handle, _ffi.f32p(q), B, src, nsrc, k, float(threshold), int(pool), _ffi.i64p(ids), _ffi.f32p(scores),
+                _ffi.i32p(counts), _ffi.i32p(similar), _ffi.i32p(examined), _ffi.u8p(more),
+            )
+        )
+        return ids, scores, counts[:B], similar, examined[:B], more[:B].astype(bool)
+
+    def search_distinct_vector(self, sources, num_results, vector, threshold, pool=None):
+        """search_distinct for one vector -> list[SearchItem] (the counters are dropped: ask search_distinct for them)."""
+        ids, scores, counts, _sim, _ex, _more = self.search_distinct(
+            sources, num_results, np.asarray(vector, dtype=np.float32)[None, :], threshold, pool)
+        return [SearchItem(int(ids[0, j]), float(scores[0, j])) for j in range(int(counts[0]))]
+
+    def search_distinct_like_item(self, sources, num_results, item_id, threshold, pool=None):
+        """Distinct neighbours of the stored embedding of `item_id` (like_queries + search_distinct); as in search_like_item the
+        item itself comes first.  KeyError("Item not found") when no row carries the id."""
+        vec, found, _members = self.like_queries([[int(item_id)]])
+        if not found[0]:
+            raise KeyError("Item not found")
+        return self.search_distinct_vector(sources, num_results, vec[0], threshold, pool)
 
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):

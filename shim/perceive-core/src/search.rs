@@ -349,6 +349,51 @@ impl Searcher {
         ((0..count as usize).map(|i| SearchItem { id: ids[i], score: scores[i] }).collect(), more != 0)
     }
 
+    /// Distinct results (`pcv_searcher_search_distinct`): the ranked list of `search_vector` walked best first on the device, an
+    /// item kept only if its cosine with every item kept before it is below `threshold` — the same article under five URLs is one
+    /// hit.  At most `pool` entries of the list are examined (`None`: min(PCV_MAX_DISTINCT_POOL, max(128, 8 * num_results))).
+    /// Each hit comes with the number of examined items dropped in its favour.
+    pub fn search_vector_distinct(
+        &self,
+        sources: &[i64],
+        num_results: usize,
+        vector: Vec<f32>,
+        threshold: f32,
+        pool: Option<usize>,
+    ) -> Vec<(SearchItem, i32)> {
+        if self.handle.is_null() || num_results == 0 {
+            return Vec::new();
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        assert_eq!(vector.len(), dim as usize, "search_vector_distinct: the query has {} values, the index is {}-d", vector.len(), dim);
+        let pool = pool.unwrap_or_else(|| (ffi::PCV_MAX_DISTINCT_POOL as usize).min((8 * num_results).max(128)));
+        let mut ids = vec![-1i64; num_results];
+        let mut scores = vec![f32::NAN; num_results];
+        let mut similar = vec![0i32; num_results];
+        let mut count: i32 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_distinct(
+                self.handle,
+                vector.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                num_results as i32,
+                threshold,
+                pool as i32,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut count,
+                similar.as_mut_ptr(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        })
+        .expect("search_distinct failed");
+        (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, similar[i])).collect()
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
