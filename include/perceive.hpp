@@ -158,6 +158,28 @@ inline std::vector<SearchItem> search_distinct_handle(pcv_searcher* h, const std
     return out;
 }
 
+// One duplicate pair of find_duplicates: the item stored first, the other one, their cosine.
+struct DuplicatePair {
+    int64_t id_a, id_b;
+    float score;
+};
+// Searcher::find_duplicates / SearcherView::find_duplicates (pcv_searcher_find_duplicates): every pair of searchable items whose
+// cosine is at or above the threshold, best first, at most max_pairs; `total` receives the exact number of pairs.
+inline std::vector<DuplicatePair> find_duplicates_handle(pcv_searcher* h, const std::vector<int64_t>& sources, float threshold, size_t max_pairs,
+                                                         int64_t* total) {
+    if (total) *total = 0;
+    if (sources.empty() || max_pairs == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    max_pairs = std::min<size_t>(max_pairs, PCV_MAX_DUPLICATE_PAIRS);
+    std::vector<int64_t> a(max_pairs), b(max_pairs);
+    std::vector<float> scores(max_pairs);
+    int64_t count = 0;
+    check(pcv_searcher_find_duplicates(h, sources.data(), (int)sources.size(), threshold, (int64_t)max_pairs, a.data(), b.data(), scores.data(),
+                                       &count, total));
+    std::vector<DuplicatePair> out;
+    for (int64_t i = 0; i < count; ++i) out.push_back({a[(size_t)i], b[(size_t)i], scores[(size_t)i]});
+    return out;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -201,6 +223,11 @@ public:
     std::vector<SearchItem> search_vector_distinct(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
                                                    float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
         return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
+    }
+    // the duplicate pairs among the view's items (find_duplicates_handle)
+    std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
+                                               int64_t* total = nullptr) const {
+        return find_duplicates_handle(h_, sources, threshold, max_pairs, total);
     }
     // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
     std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
@@ -290,6 +317,11 @@ public:
     std::vector<SearchItem> search_vector_distinct(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
                                                    float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
         return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
+    }
+    // every pair of near-duplicate items, found once on the device (find_duplicates_handle)
+    std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
+                                               int64_t* total = nullptr) const {
+        return find_duplicates_handle(h_, sources, threshold, max_pairs, total);
     }
     // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the
     // item itself is the first hit unless `exclude`.  nullopt: no row carries the id.

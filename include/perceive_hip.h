@@ -418,6 +418,54 @@ pcv_status pcv_searcher_search_distinct(pcv_searcher* s, const float* queries, i
                                         int num_results, float threshold, int pool, int64_t* out_ids, float* out_scores,
                                         int32_t* out_counts, int32_t* out_similar, int32_t* out_examined, uint8_t* out_more);
 
+/* Duplicate pairs: the exact self-join of the corpus on the device — every pair of searchable rows that are near-duplicates of each
+ * other, found once and corpus-wide (what pcv_searcher_search_distinct collapses per query, for pcv_searcher_remove_ids /
+ * pcv_searcher_hide_ids to act on).
+ * The rows taking part are exactly those a pcv_searcher_search with the same source filter could return: hidden rows and
+ * unsearchable rows (scale 0) take no part, a view joins its own rows, source_ids == NULL means all sources, an empty list matches
+ * nothing (out_count = out_total = 0).  A pair is two different rows a, b with global position a < b; it is a duplicate pair iff
+ * dup(a, b) exactly as pcv_searcher_search_distinct defines it: the canonical cosine c of the two stored f32 rows — f64, products
+ * exact, sums in feature order — is >= (double)threshold, for BOTH metrics.  A row without a cosine (zero or
+ * non-finite norm) pairs with nothing.  Two rows carrying the same item id are a pair like any other (id_a == id_b).
+ *   threshold    in (-1, 1]; at exactly 1 see pcv_searcher_search_distinct: use the f32 below 1 for "exact copies"
+ *   max_pairs    1 .. PCV_MAX_DUPLICATE_PAIRS
+ *   out_id_a/b   [max_pairs] the first min(total, max_pairs) pairs in the order: descending c, ties -> lower position of a, then
+ *                lower position of b; out_id_a is the id of the lower-positioned row of the pair
+ *   out_scores   [max_pairs] (float)c (may be NULL)
+ *   out_count    pairs written
+ *   out_total    the exact number of duplicate pairs (may be NULL); total > count is the "more" signal
+ * A NULL searcher, NULL id outputs or out_count, max_pairs out of range or a threshold that is NaN or outside (-1, 1] give
+ * PCV_ERR_INVALID before any device work; a searcher with pending rows fails as in pcv_searcher_search.  If the join finds more than
+ * PCV_MAX_DUPLICATE_PAIRS pairs (or its screen lists more than four times as many candidates) the call returns
+ * PCV_ERR_UNSUPPORTED naming the count reached, before any larger list is allocated; the searcher stays usable.  A dimension whose
+ * bf16 row tile does not fit the LDS of a CU gives PCV_ERR_UNSUPPORTED.  The result does not depend on which screening copies
+ * exist, nor on pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity: the join reads the f32 rows (DESIGN.md §4
+ * "Duplicate pairs").  Not in scope: a sharded form (the pairs across shards need the rows of both) and device-resident output. */
+enum { PCV_MAX_DUPLICATE_PAIRS = 16777216 }; /* 2^24 */
+pcv_status pcv_searcher_find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs,
+                                        int64_t* out_id_a, int64_t* out_id_b, float* out_scores, int64_t* out_count,
+                                        int64_t* out_total);
+
+/* Counters of the most recent pcv_searcher_find_duplicates on this handle. */
+typedef struct pcv_duplicate_stats {
+    int64_t rows;        /* rows of the selected segments (those taking no part included) */
+    int64_t candidates;  /* pairs the bf16 screen listed and the f64 step scored            */
+    int64_t pairs;       /* duplicate pairs (the call's total)                              */
+    int32_t tile_rows;   /* rows of the LDS tile the screen kernel staged                   */
+    int32_t reruns;      /* screen launches repeated because the candidate list was short   */
+    float prep_ms;       /* hipEvent times of the three steps (a repeated screen included)  */
+    float screen_ms;
+    float rescore_ms;
+} pcv_duplicate_stats;
+pcv_status pcv_searcher_last_duplicate_stats(pcv_searcher* s, pcv_duplicate_stats* out);
+
+/* Groups of duplicates from a list of pairs (host only: needs no context and no GPU).  out_ids receives the distinct ids occurring
+ * in the n_pairs pairs, ascending, and out_group[i] the smallest id of the connected component of out_ids[i]: an item is a candidate
+ * for removal iff out_group[i] != out_ids[i].  out_n_ids receives the number of distinct ids; capacity < that gives PCV_ERR_INVALID
+ * (out_n_ids is set, nothing else is written). */
+pcv_status pcv_duplicate_groups(const int64_t* id_a, const int64_t* id_b, int64_t n_pairs, int64_t* out_ids, int64_t* out_group,
+                                int64_t capacity, int64_t* out_n_ids);
+
 /* Search by example (`perceive search --like <id>`, perceive-cli/cmd/search.rs:17-19, 64-86: the stored embedding of an item is
  * the query): query vectors are built on the device from rows the searcher already holds, found by item id.
  * Query q is built from the examples example_ids[offsets[q] .. offsets[q+1]) with the weights weights[...] (NULL: all 1);

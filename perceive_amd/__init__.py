@@ -11,6 +11,7 @@ from .search import (  # noqa: F401
     cosine_similarity_single_query,
     deserialize_embedding,
     dot_product,
+    duplicate_groups,
     encode_query,
     merge_topk,
     serialize_embedding,

@@ -104,6 +104,34 @@ __device__ __forceinline__ double finish_score(int metric, double dot, double nx
     return __builtin_nan("");
 }
 
+// Place of 16-byte piece `pc` of query row `q` inside the row's P8 pieces of the LDS tile: XOR with the row number
+// inside groups of 16 pieces, so that the 16 lanes of a ds_read_b128 group (16 consecutive rows, one piece index) hit 16
+// distinct bank quads.  P8 is a multiple of 8 (dimension padded to 64), not always of 16: a trailing group of 8 pieces is
+// swizzled inside itself (2-way conflicts there; XOR with four bits would leave the row).
+__device__ __forceinline__ int swizzle_piece(int pc, int q, int P8) {
+    return pc < (P8 & ~15) ? ((pc & ~15) | ((pc ^ q) & 15)) : ((pc & ~7) | ((pc ^ q) & 7));
+}
+
+// The feature-order f64 sums of row x with rows y[0..NU) (D4 pieces of four features each, `stride` float4 apart): the canonical
+// dot product and, for y == x, the canonical |x|^2.  The product of two f32 is exact in f64, so every step is one rounding.
+template <int NU>
+__device__ __forceinline__ void pair_sums(const float4* x, const float4* (&y)[NU], int D4, double (&acc)[NU], size_t stride = 1) {
+#pragma unroll
+    for (int u = 0; u < NU; ++u) acc[u] = 0.0;
+#pragma unroll 4
+    for (int f = 0; f < D4; ++f) {
+        const float4 v = x[(size_t)f * stride];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            const float4 w = y[u][(size_t)f * stride];
+            acc[u] += (double)v.x * (double)w.x;
+            acc[u] += (double)v.y * (double)w.y;
+            acc[u] += (double)v.z * (double)w.z;
+            acc[u] += (double)v.w * (double)w.w;
+        }
+    }
+}
+
 }  // namespace
 
 static inline unsigned cdiv64(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }

@@ -78,25 +78,7 @@ __device__ __forceinline__ void stage_rows(float4* tile, const uint64_t* src, in
     }
 }
 
-// The feature-order f64 sums of row a of tile X with rows b[0..NU) of tile Y.
-template <int NU>
-__device__ __forceinline__ void pair_sums(const float4* x, const float4* (&y)[NU], int D4, double (&acc)[NU]) {
-#pragma unroll
-    for (int u = 0; u < NU; ++u) acc[u] = 0.0;
-#pragma unroll 4
-    for (int f = 0; f < D4; ++f) {
-        const float4 v = x[f];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const float4 w = y[u][f];
-            acc[u] += (double)v.x * (double)w.x;
-            acc[u] += (double)v.y * (double)w.y;
-            acc[u] += (double)v.z * (double)w.z;
-            acc[u] += (double)v.w * (double)w.w;
-        }
-    }
-}
-
+// (the feature-order f64 sums of a row of tile X with rows of tile Y: pair_sums, device_access.h)
 // One workgroup per query.  R: rows of a tile, a power of two <= kDistinctRows; NU: chains a thread runs (R * R / 256, at least 1).
 template <int NU>
 __global__ __launch_bounds__(256) void distinct_select_kernel(const ScanParams* __restrict__ pp, const DistinctArgs a, int R, int logR) {

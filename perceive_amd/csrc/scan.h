@@ -251,6 +251,32 @@ struct DistinctArgs {
     double threshold;
 };
 
+// Duplicate pairs (pcv_searcher_find_duplicates; DESIGN.md §4 "Duplicate pairs"): rows against rows.  Rows are named by their
+// number in the launch's block numbering, block * 32 + row of the block ("launch row": the rows behind a segment's last row in its
+// last block have numbers too and take no part); launch rows ascend with the global position.
+//   rinv[launch row] : 1/|x| rounded to f32 from the row's canonical |x|^2;  0: the row takes no part (unsearchable, behind nrows,
+//                      no cosine);  kRinvWild: it takes part but |x| is outside [2^-20, 2^20], where the f32 screening score is
+//                      not certified — every pair with such a row is a candidate and the f64 step decides
+//   norm[launch row] : the canonical |x|^2 (f64, feature order)
+struct DupPair {
+    double c;            // canonical cosine
+    int64_t pos_a, pos_b;  // global positions, pos_a < pos_b
+    int64_t id_a, id_b;
+};
+constexpr float kRinvWild = -1.0f;
+struct SelfJoinArgs {
+    float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    double* norm;                   // [total_blocks * 32]
+    uint64_t* cand;                 // [cand_cap] (launch row a << 32) | launch row b, a < b
+    unsigned long long* counters;   // [0]: candidates the screen found (not capped), [1]: duplicate pairs (not capped)
+    DupPair* pairs;                 // [pair_cap]
+    unsigned long long cand_cap, pair_cap, n_cand;  // n_cand: entries of `cand` the rescore step reads
+    float screen_threshold;         // threshold - margin, rounded down
+    double threshold;
+    uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
+    uint32_t span_blocks;           // blocks of one work item's stream
+};
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -291,6 +317,11 @@ void launch_range_thresholds(hipStream_t st, const ScanParams& p, const ScanPara
 void launch_range_select(hipStream_t st, const ScanParams& p, const ScanParams* dp);
 // ---- distinct results (distinct_kernels.hip): walks the p.k hits per query the pass left in p.out ----
 void launch_distinct_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DistinctArgs& a);
+// ---- duplicate pairs (selfjoin_kernels.hip); `p` needs seg, nseg, total_blocks, D, D4 only ----
+float selfjoin_margin(int Dp);  // certified bound on |screening score - canonical cosine| (DESIGN.md §4 "Duplicate pairs")
+void launch_selfjoin_prep(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
+void launch_selfjoin_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
+void launch_selfjoin_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);
 void launch_merge(hipStream_t st, const pcv_hit_dev* lists, int n_shards, int B, int k, pcv_hit_dev* out,
                   int flagged = 0);

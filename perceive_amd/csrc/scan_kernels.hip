@@ -749,13 +749,7 @@ __device__ __forceinline__ void fine_survivors(const ScanParams& p, uint32_t mas
     }
 }
 
-// Place of 16-byte piece `pc` of query row `q` inside the row's P8 pieces of the LDS tile: XOR with the row number
-// inside groups of 16 pieces, so that the 16 lanes of a ds_read_b128 group (16 consecutive rows, one piece index) hit 16
-// distinct bank quads.  P8 is a multiple of 8 (dimension padded to 64), not always of 16: a trailing group of 8 pieces is
-// swizzled inside itself (2-way conflicts there; XOR with four bits would leave the row).
-__device__ __forceinline__ int swizzle_piece(int pc, int q, int P8) {
-    return pc < (P8 & ~15) ? ((pc & ~15) | ((pc ^ q) & 15)) : ((pc & ~7) | ((pc ^ q) & 7));
-}
+// (place of a 16-byte piece inside a row of the swizzled bf16 LDS tile: swizzle_piece, device_access.h)
 
 // SRC16: stream the segments' screening copies (bf16, scale folded in: scan.h) instead of converting the f32 rows —
 // half the bytes per row and no conversion work; a chunk is then 4 pieces per lane instead of 8.

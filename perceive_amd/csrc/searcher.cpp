@@ -238,6 +238,7 @@ struct pcv_searcher {
     // records | kept hits | their norms | their counters, on the device and (records after every pass, the rest once) in pinned memory
     DevBuf<uint8_t> d_distinct;
     PinBuf<uint8_t> pin_distinct;
+    pcv_duplicate_stats dup_stats{};  // pcv_searcher_find_duplicates (its buffers live for the call only)
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -2403,6 +2404,173 @@ void search_distinct(pcv_searcher* s, const float* queries, int n_queries, const
     }
 }
 
+// ---- duplicate pairs (pcv_searcher_find_duplicates; DESIGN.md §4 "Duplicate pairs") ----
+// The screen may list four times the pairs a call may return before the call gives up: 2^26 entries of 8 bytes.
+constexpr uint64_t kMaxJoinCandidates = (uint64_t)4 * PCV_MAX_DUPLICATE_PAIRS;
+constexpr uint32_t kJoinSpanBlocks = 256;  // blocks a work item streams against its tile (12 MB at 384-d for 196 KB of tile staging)
+
+// Three steps on the device (selfjoin_kernels.hip): norms, the bf16 screen of every tile of rows against the rows behind it, the
+// canonical f64 cosine of what the screen listed.  The pairs come down once and are ordered here.  Everything the call allocates
+// is its own and is given back when it ends: nothing of the searcher's pass state is touched.
+void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs, int64_t* out_id_a,
+                     int64_t* out_id_b, float* out_scores, int64_t* out_count, int64_t* out_total) {
+    PCV_REQUIRE(!s->dirty, "find_duplicates: rows were added or cleared without pcv_searcher_finalize");
+    s->dup_stats = pcv_duplicate_stats{};
+    *out_count = 0;
+    if (out_total) *out_total = 0;
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "find_duplicates: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    if (segs.empty()) return;
+    hipStream_t st = s->ctx->stream;
+
+    // the parameters and the segment table, as a pass has them (only what the three kernels read)
+    const size_t off_seg = align_up(sizeof(ScanParams)), bytes = off_seg + segs.size() * sizeof(SegDesc);
+    PinBuf<uint8_t> pin_p;
+    DevBuf<uint8_t> d_p;
+    pin_p.ensure(bytes);
+    d_p.ensure(bytes);
+    ScanParams& p = *new (pin_p.p) ScanParams{};
+    SegDesc* tab = reinterpret_cast<SegDesc*>(pin_p.p + off_seg);
+    uint64_t blk0 = 0;
+    int64_t rows = 0;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const Segment& g = *segs[i].g;
+        tab[i] = SegDesc{};
+        tab[i].blk = g.blk;
+        tab[i].scale = g.scale;
+        tab[i].ids = g.ids;
+        tab[i].id0 = g.id0;
+        tab[i].pos0 = g.pos0;
+        tab[i].nrows = g.nrows;
+        tab[i].nblocks = g.nblocks();
+        tab[i].blk0 = (uint32_t)blk0;
+        blk0 += g.nblocks();
+        rows += g.nrows;
+        if (blk0 * kBlockRows > 0xffffffffull) PCV_FAIL(PCV_ERR_UNSUPPORTED, "find_duplicates: more than 2^32 rows in one join");
+    }
+    p.seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
+    p.nseg = (int)segs.size();
+    p.total_blocks = (uint32_t)blk0;
+    p.D = s->D;
+    p.D4 = s->D4;
+    p.metric = s->metric;
+    const ScanParams* dp = reinterpret_cast<const ScanParams*>(d_p.p);
+
+    SelfJoinArgs a{};
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    a.span_blocks = kJoinSpanBlocks;
+    while ((p.total_blocks + a.span_blocks - 1) / a.span_blocks > 65535u) a.span_blocks *= 2;  // (the grid's second dimension)
+    // thr - margin in f64, rounded down: no pair with s below it has c >= thr
+    a.threshold = (double)threshold;
+    a.screen_threshold = std::nextafterf((float)((double)threshold - (double)selfjoin_margin(s->Dp)), -INFINITY);
+    DevBuf<float> d_rinv;
+    DevBuf<double> d_norm;
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<uint64_t> d_cand;
+    DevBuf<DupPair> d_pairs;
+    const size_t n_rinv = ((size_t)p.total_blocks + a.tile_blocks) * kBlockRows;
+    d_rinv.ensure(n_rinv);
+    d_norm.ensure((size_t)p.total_blocks * kBlockRows);
+    d_cnt.ensure(2);
+    a.cand_cap = std::min<uint64_t>(kMaxJoinCandidates, std::max<uint64_t>(65536, 2 * (uint64_t)rows));
+    d_cand.ensure(a.cand_cap);
+    a.rinv = d_rinv.p;
+    a.norm = d_norm.p;
+    a.counters = d_cnt.p;
+    a.cand = d_cand.p;
+
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    const auto drop_events = at_exit([&] {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    });
+    for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
+    unsigned long long counts[2] = {0, 0};
+    auto elapsed = [&](int from) {
+        float ms = 0.0f;
+        PCV_HIP(hipEventElapsedTime(&ms, ev[from], ev[from + 1]));
+        return ms;
+    };
+
+    PCV_HIP(hipMemcpyAsync(d_p.p, pin_p.p, bytes, hipMemcpyHostToDevice, st));
+    PCV_HIP(hipMemsetAsync(d_rinv.p, 0, n_rinv * sizeof(float), st));
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+    PCV_HIP(hipEventRecord(ev[0], st));
+    launch_selfjoin_prep(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[1], st));
+    launch_selfjoin_screen(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[2], st));
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    s->dup_stats.rows = rows;
+    s->dup_stats.tile_rows = tile;
+    s->dup_stats.prep_ms = elapsed(0);
+    s->dup_stats.screen_ms = elapsed(1);
+    const uint64_t n_cand = counts[0];
+    s->dup_stats.candidates = (int64_t)n_cand;
+    if (n_cand > kMaxJoinCandidates)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                 "find_duplicates: the screen lists %llu candidate pairs at threshold %g, more than %llu (4 x PCV_MAX_DUPLICATE_PAIRS): raise the "
+                 "threshold or join fewer rows",
+                 (unsigned long long)n_cand, (double)threshold, (unsigned long long)kMaxJoinCandidates);
+    if (n_cand > a.cand_cap) {  // once more, with the room the count asks for (the screen lists the same pairs again)
+        a.cand_cap = n_cand;
+        d_cand.ensure(a.cand_cap);
+        a.cand = d_cand.p;
+        PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+        PCV_HIP(hipEventRecord(ev[1], st));
+        launch_selfjoin_screen(st, p, dp, a);
+        PCV_HIP(hipEventRecord(ev[2], st));
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        PCV_REQUIRE(counts[0] == n_cand, "find_duplicates: the repeated screen listed %llu pairs, the first %llu", counts[0], (unsigned long long)n_cand);
+        s->dup_stats.reruns = 1;
+        s->dup_stats.screen_ms += elapsed(1);
+    }
+    if (n_cand == 0) return;
+    a.n_cand = n_cand;
+    a.pair_cap = std::min<uint64_t>(n_cand, (uint64_t)PCV_MAX_DUPLICATE_PAIRS);
+    d_pairs.ensure(a.pair_cap);
+    a.pairs = d_pairs.p;
+    PCV_HIP(hipEventRecord(ev[2], st));
+    launch_selfjoin_rescore(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[3], st));
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    s->dup_stats.rescore_ms = elapsed(2);
+    const uint64_t total = counts[1];
+    s->dup_stats.pairs = (int64_t)total;
+    if (total > (uint64_t)PCV_MAX_DUPLICATE_PAIRS)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                 "find_duplicates: %llu duplicate pairs at threshold %g, more than PCV_MAX_DUPLICATE_PAIRS (%d): raise the threshold or join "
+                 "fewer rows",
+                 (unsigned long long)total, (double)threshold, (int)PCV_MAX_DUPLICATE_PAIRS);
+    std::vector<DupPair> pairs((size_t)total);
+    if (total > 0) PCV_HIP(hipMemcpy(pairs.data(), d_pairs.p, (size_t)total * sizeof(DupPair), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)std::min<uint64_t>(total, (uint64_t)max_pairs);
+    auto before = [](const DupPair& x, const DupPair& y) {
+        if (x.c != y.c) return x.c > y.c;
+        if (x.pos_a != y.pos_a) return x.pos_a < y.pos_a;
+        return x.pos_b < y.pos_b;
+    };
+    if (n < pairs.size())
+        std::partial_sort(pairs.begin(), pairs.begin() + (std::ptrdiff_t)n, pairs.end(), before);
+    else
+        std::sort(pairs.begin(), pairs.end(), before);
+    for (size_t i = 0; i < n; ++i) {
+        out_id_a[i] = pairs[i].id_a;
+        out_id_b[i] = pairs[i].id_b;
+        if (out_scores) out_scores[i] = (float)pairs[i].c;
+    }
+    *out_count = (int64_t)n;
+    if (out_total) *out_total = (int64_t)total;
+}
+
 void sync_view(pcv_searcher* v);
 
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.
@@ -3403,6 +3571,67 @@ pcv_status pcv_searcher_search_distinct(pcv_searcher* s, const float* queries, i
         sync_view(s);
         search_distinct(s, queries, n_queries, source_ids, n_sources, num_results, threshold, pool, out_ids, out_scores, out_counts, out_similar,
                         out_examined, out_more);
+    });
+}
+
+pcv_status pcv_searcher_find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs,
+                                        int64_t* out_id_a, int64_t* out_id_b, float* out_scores, int64_t* out_count,
+                                        int64_t* out_total) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "find_duplicates: searcher is NULL");
+        PCV_REQUIRE(out_id_a != nullptr && out_id_b != nullptr && out_count != nullptr, "find_duplicates: out_id_a, out_id_b or out_count is NULL");
+        PCV_REQUIRE(max_pairs >= 1 && max_pairs <= (int64_t)PCV_MAX_DUPLICATE_PAIRS, "find_duplicates: max_pairs %lld outside [1,%d]",
+                    (long long)max_pairs, (int)PCV_MAX_DUPLICATE_PAIRS);
+        PCV_REQUIRE(threshold == threshold, "find_duplicates: threshold is NaN");
+        PCV_REQUIRE(threshold > -1.0f && threshold <= 1.0f, "find_duplicates: threshold %g outside (-1, 1]", (double)threshold);
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "find_duplicates: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        find_duplicates(s, source_ids, n_sources, threshold, max_pairs, out_id_a, out_id_b, out_scores, out_count, out_total);
+    });
+}
+
+pcv_status pcv_searcher_last_duplicate_stats(pcv_searcher* s, pcv_duplicate_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_duplicate_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->dup_stats;
+    });
+}
+
+// Union-find over the distinct ids of the pairs, by their index in ascending order: a root is always the smallest index of its
+// component, so the label of a component is its smallest id.
+pcv_status pcv_duplicate_groups(const int64_t* id_a, const int64_t* id_b, int64_t n_pairs, int64_t* out_ids, int64_t* out_group,
+                                int64_t capacity, int64_t* out_n_ids) {
+    return guarded([&] {
+        PCV_REQUIRE(out_n_ids != nullptr, "duplicate_groups: out_n_ids is NULL");
+        PCV_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || (id_a != nullptr && id_b != nullptr)), "duplicate_groups: %lld pairs without their ids",
+                    (long long)n_pairs);
+        std::vector<int64_t> ids;
+        ids.reserve((size_t)n_pairs * 2);
+        ids.insert(ids.end(), id_a, id_a + n_pairs);
+        ids.insert(ids.end(), id_b, id_b + n_pairs);
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        const int64_t n = (int64_t)ids.size();
+        *out_n_ids = n;
+        PCV_REQUIRE(capacity >= n, "duplicate_groups: %lld ids, room for %lld", (long long)n, (long long)capacity);
+        PCV_REQUIRE(n == 0 || (out_ids != nullptr && out_group != nullptr), "duplicate_groups: out_ids or out_group is NULL");
+        std::vector<int64_t> parent((size_t)n);
+        std::iota(parent.begin(), parent.end(), (int64_t)0);
+        auto find = [&](int64_t i) {
+            while (parent[(size_t)i] != i) i = parent[(size_t)i] = parent[(size_t)parent[(size_t)i]];
+            return i;
+        };
+        for (int64_t k = 0; k < n_pairs; ++k) {
+            const int64_t x = find(std::lower_bound(ids.begin(), ids.end(), id_a[k]) - ids.begin());
+            const int64_t y = find(std::lower_bound(ids.begin(), ids.end(), id_b[k]) - ids.begin());
+            if (x != y) parent[(size_t)std::max(x, y)] = std::min(x, y);
+        }
+        for (int64_t i = 0; i < n; ++i) {
+            out_ids[i] = ids[(size_t)i];
+            out_group[i] = ids[(size_t)find(i)];
+        }
     });
 }
 

@@ -1,0 +1,332 @@
+// selfjoin_kernels.hip — the three steps of pcv_searcher_find_duplicates (DESIGN.md §4 "Duplicate pairs"): every pair of
+// participating rows whose canonical cosine is at or above a threshold, exact, computed where the rows live.
+//
+//   1. selfjoin_prep_kernel     one thread per row: the canonical |x|^2 (f64, feature order) and rinv = 1/|x| in f32 (scan.h,
+//                               SelfJoinArgs: 0 = the row takes no part).  Reads the corpus once.
+//   2. selfjoin_screen_kernel   the 128-query bf16 scan with rows in the place of queries: a workgroup stages a tile of up to 128
+//                               consecutive rows in LDS as bf16 (the layout scan_mfma_kernel uses for its query tile) and streams a
+//                               span of the blocks at and after the tile's first block out of the blocked f32 layout, rounding a
+//                               lane's 16-byte pieces to bf16 on the way — they are the A fragment of v_mfma_f32_32x32x16_bf16.
+//                               s = acc * rinv_a * rinv_b; a pair with s >= threshold - margin (selfjoin_margin: a certified bound
+//                               on |s - c|) and row a before row b is appended to one device list.  Only the upper triangle is
+//                               computed.  Appends past the list's capacity are counted, not stored: the host repeats the launch
+//                               once with the capacity the count asks for.
+//   3. selfjoin_rescore_kernel  one thread per candidate: the canonical f64 cosine (pair_sums and finish_score, device_access.h —
+//                               the arithmetic of distinct_select_kernel), kept iff c >= threshold.
+#include "device_access.h"
+#include "scan.h"
+
+namespace pcv {
+namespace {
+
+constexpr int kJoinWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
+
+__device__ __forceinline__ unsigned long long g_atomic_add64(unsigned long long* p, unsigned long long v) {
+    return __hip_atomic_fetch_add((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// last table entry with blk0 <= gb
+__device__ __forceinline__ int find_seg(const ScanParams& p, uint32_t gb, int from = 0) {
+    int lo = from, hi = p.nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (gld(&p.seg[mid].blk0) <= gb)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// Launch row `lr` (scan.h): its segment, its row there and where its first piece is.
+struct RowRef {
+    const SegDesc* sg;
+    uint32_t row;
+    const float4* x;
+};
+__device__ __forceinline__ RowRef row_ref(const ScanParams& p, uint32_t lr) {
+    const uint32_t gb = lr >> 5;
+    const SegDesc* sg = &p.seg[find_seg(p, gb)];
+    const uint32_t lb = gb - gld(&sg->blk0);
+    return {sg, lb * 32 + (lr & 31), gld(&sg->blk) + (size_t)lb * p.D4 * 32 + (lr & 31)};
+}
+
+__global__ __launch_bounds__(256) void selfjoin_prep_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
+    const ScanParams& p = *pp;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint64_t)p.total_blocks * 32) return;
+    const RowRef r = row_ref(p, (uint32_t)i);
+    float rinv = 0.0f;
+    double n = 0.0;
+    if (r.row < gld(&r.sg->nrows) && gld(&gld(&r.sg->scale)[r.row]) != 0.0f) {
+        const float4* y[1] = {r.x};
+        double acc[1];
+        pair_sums<1>(r.x, y, p.D4, acc, 32);
+        n = acc[0];
+        if (n >= 0x1p-126 && n < __builtin_inf())  // (finish_score's condition for a cosine)
+            rinv = (n >= 0x1p-40 && n <= 0x1p40) ? (float)(1.0 / sqrt(n)) : kRinvWild;
+    }
+    gst(&a.rinv[i], rinv);
+    gst(&a.norm[i], n);
+}
+
+// The segment a wave's stream is in (all of it wave-uniform, in scalar registers: scan_kernels.hip, seek_seg).
+struct JoinSeg {
+    int si = -1;
+    uint32_t begin = 0, end = 0;
+    const float4* blk = nullptr;
+};
+__device__ __forceinline__ void join_seek(const ScanParams& p, JoinSeg& c, uint32_t gb) {
+    if (gb < c.end) return;
+    const int lo = find_seg(p, gb, c.si + 1);
+    c.si = lo;
+    c.begin = uniform(gld(&p.seg[lo].blk0));
+    c.end = c.begin + uniform(gld(&p.seg[lo].nblocks));
+    c.blk = uniform_ptr(gld(&p.seg[lo].blk));
+}
+struct JoinCursor {
+    uint32_t gb;
+    int ch;
+    JoinSeg sc;
+    __amdgpu_buffer_rsrc_t rows;
+};
+
+// grid: x = tile (tile_blocks = NT consecutive blocks), y = span: the blocks [tile's first + y * span_blocks, + span_blocks) of the
+// launch, cut at its end.  A (tile, span) that starts behind the end has nothing to do.  Consecutive workgroups stream nearly the
+// same blocks, NT blocks apart: what one brings into the L2 the next ones find there.
+// D[row of the streamed block][row of the tile]: lane (c = lane & 31, h = lane >> 5) holds tile rows 32 t + c and, in
+// accumulator i, block row (i & 3) + 8 (i >> 2) + 4 h.
+template <int NT>
+__global__ __launch_bounds__(kJoinWaves * 64) void selfjoin_screen_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
+    const ScanParams& p = *pp;
+    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
+    __shared__ const float4* tbase[NT];
+    const int D4 = p.D4, P8 = D4 >> 1, NCH = D4 >> 4;
+    const uint32_t TB = p.total_blocks;
+    const uint32_t tb0 = blockIdx.x * NT;
+    const uint64_t first = (uint64_t)tb0 + (uint64_t)blockIdx.y * a.span_blocks;
+    if (first >= TB) return;  // (the whole workgroup)
+    const uint32_t b0 = (uint32_t)first;
+    const uint32_t b1 = (uint32_t)min((uint64_t)TB, first + a.span_blocks);
+
+    if (threadIdx.x < NT) {
+        const uint32_t gb = tb0 + threadIdx.x;
+        const float4* base = nullptr;
+        if (gb < TB) {
+            const SegDesc& sg = p.seg[find_seg(p, gb)];
+            base = gld(&sg.blk) + (size_t)(gb - gld(&sg.blk0)) * D4 * 32;
+        }
+        tbase[threadIdx.x] = base;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < NT * 32 * P8; i += kJoinWaves * 64) {
+        const int r = i & 31, rest = i >> 5;
+        const int tb = rest / P8, pc = rest - tb * P8;
+        const float4* base = tbase[tb];
+        bf16x8 v8 = {};
+        if (base) {
+            const float4 lo = gld4(base + (size_t)(2 * pc) * 32 + r), hi = gld4(base + (size_t)(2 * pc + 1) * 32 + r);
+            const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            v8 = __builtin_convertvector(v, bf16x8);
+        }
+        const int row = tb * 32 + r;
+        lq[row * P8 + swizzle_piece(pc, row, P8)] = __builtin_bit_cast(uint4, v8);
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    if (b0 + wave >= b1) return;
+    float ra[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) ra[t] = gld(&a.rinv[(size_t)(tb0 + t) * 32 + c]);  // (zero behind the launch's last block)
+    const float thr = a.screen_threshold;
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+
+    auto enter_block = [&](JoinCursor& k, uint32_t gb) {
+        k.gb = gb;
+        k.ch = 0;
+        if (gb < b1) {
+            join_seek(p, k.sc, gb);
+            k.rows = row_rsrc(k.sc.blk + (size_t)(gb - k.sc.begin) * D4 * 32, (uint32_t)D4 * 512u);
+        }
+    };
+    const uint32_t lane_off = (uint32_t)(h * 64 + c) * 16u;  // the lane's bytes inside a block
+    JoinCursor cons, prod;
+    enter_block(cons, b0 + wave);
+    prod = cons;
+
+    float4 buf[2][8];
+    // (always issues its loads: past the end of the wave's stream they read a chunk of its last block again — scan_mfma_kernel)
+    auto produce = [&](float4 (&b)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
+        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + kJoinWaves);
+    };
+
+    f32x4 rb[4];  // rinv of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
+    auto rb_prefetch = [&]() {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rb[j] = *(const PCV_GLOBAL f32x4*)(a.rinv + (size_t)cons.gb * 32 + 8 * j + 4 * h);
+    };
+
+    auto passes = [&](int t, int i, bool diagonal) -> bool {
+        const float rbi = rb[i >> 2][i & 3];
+        const float s = acc[t][i] * ra[t] * rbi;
+        bool ok = (ra[t] > 0.0f && rbi > 0.0f) ? s >= thr : (ra[t] != 0.0f && rbi != 0.0f);  // (a wild row: every pair, scan.h)
+        if (diagonal) ok = ok && (tb0 + t) * 32u + (uint32_t)c < cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h);
+        return ok;
+    };
+
+    auto epilogue = [&]() {
+        if (NCH < 2) rb_prefetch();
+        const bool diagonal = cons.gb < tb0 + NT;  // the block is one of the tile's own: row a before row b only
+        bool any = false;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) any |= passes(t, i, diagonal);
+        if (__any(any)) {  // rare
+            uint32_t mask[NT];
+            uint32_t n = 0;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                mask[t] = 0;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) mask[t] |= passes(t, i, diagonal) ? (1u << i) : 0u;
+                n += (uint32_t)__builtin_popcount(mask[t]);
+            }
+            if (n) {
+                unsigned long long at = g_atomic_add64(&a.counters[0], n);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    uint32_t m = mask[t];
+                    while (m) {
+                        const int i = __builtin_ctz(m);
+                        m &= m - 1;
+                        if (at < a.cand_cap)
+                            gst(&a.cand[at], ((uint64_t)((tb0 + t) * 32u + (uint32_t)c) << 32) | (cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h)));
+                        ++at;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    };
+
+    auto consume = [&](const float4 (&b)[8]) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const f32x8 v = {b[2 * ks].x, b[2 * ks].y, b[2 * ks].z, b[2 * ks].w, b[2 * ks + 1].x, b[2 * ks + 1].y, b[2 * ks + 1].z, b[2 * ks + 1].w};
+            const bf16x8 av = __builtin_convertvector(v, bf16x8);
+            const int pc = 2 * (cons.ch * 4 + ks) + h;
+            const int ph = swizzle_piece(pc, c, P8);  // (tile row 32 t + c: the same low four bits as c)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const bf16x8 q8 = *(const bf16x8*)&lq[(32 * t + c) * P8 + ph];
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q8, acc[t], 0, 0, 0);
+            }
+        }
+        if (++cons.ch == NCH) {
+            epilogue();
+            enter_block(cons, cons.gb + kJoinWaves);
+        }
+    };
+
+    // one chunk of loads in flight while one feeds the matrix cores (every buf[] index a literal, or the array moves to scratch);
+    // the block's rinv values are requested one chunk ahead of the epilogue and before that step's row loads
+#define PCV_JOIN_STEP(REFILL, CONS)                      \
+    if (NCH >= 2 && cons.ch == NCH - 2) rb_prefetch();   \
+    produce(buf[REFILL]);                                \
+    consume(buf[CONS]);                                  \
+    if (cons.gb >= b1) return;
+    produce(buf[0]);
+    while (true) {
+        PCV_JOIN_STEP(1, 0)
+        PCV_JOIN_STEP(0, 1)
+    }
+#undef PCV_JOIN_STEP
+}
+
+__global__ __launch_bounds__(256) void selfjoin_rescore_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
+    const ScanParams& p = *pp;
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_cand) return;
+    const uint64_t cd = gld(&a.cand[i]);
+    const uint32_t la = (uint32_t)(cd >> 32), lb = (uint32_t)cd;
+    const RowRef ra = row_ref(p, la), rb = row_ref(p, lb);
+    const float4* y[1] = {rb.x};
+    double acc[1];
+    pair_sums<1>(ra.x, y, p.D4, acc, 32);
+    const double cc = finish_score(PCV_METRIC_COSINE, acc[0], gld(&a.norm[la]), gld(&a.norm[lb]));
+    if (!(cc >= a.threshold)) return;
+    const unsigned long long at = g_atomic_add64(&a.counters[1], 1ull);
+    if (at >= a.pair_cap) return;
+    auto id_of = [](const RowRef& r) {
+        const int64_t* ids = gld(&r.sg->ids);
+        return ids ? gld(&ids[r.row]) : gld(&r.sg->id0) + (int64_t)r.row;
+    };
+    const int64_t pa = gld(&ra.sg->pos0) + (int64_t)ra.row, pb = gld(&rb.sg->pos0) + (int64_t)rb.row;
+    const int64_t ia = id_of(ra), ib = id_of(rb);
+    const bool fwd = pa < pb;
+    DupPair* out = &a.pairs[at];
+    gst(&out->c, cc);
+    gst(&out->pos_a, fwd ? pa : pb);
+    gst(&out->pos_b, fwd ? pb : pa);
+    gst(&out->id_a, fwd ? ia : ib);
+    gst(&out->id_b, fwd ? ib : ia);
+}
+
+}  // namespace
+
+// |s - c| for s = fl(fl(acc ra) rb) (DESIGN.md §4 "Duplicate pairs"), relative to |a||b| = 1 after the two rinv factors:
+//   two bf16 operand roundings, u = 2^-8 each:   u (2 + u)                      = 0.0078278
+//   f32 accumulation over Dp terms, any order:   eps32 (1 + u)^2,  eps32 = (Dp + 16) 2^-23 as for the scans
+//   two rinv roundings and two multiplies:       4 * 2^-24 (1 + the above), and what f64 leaves of the canonical sums: all in 1e-6
+float selfjoin_margin(int Dp) { return 0.00783f + 1.02f * ((float)(Dp + 16) * 1.2e-7f) + 1e-6f; }
+
+void launch_selfjoin_prep(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a) {
+    if (p.total_blocks == 0) return;
+    selfjoin_prep_kernel<<<cdiv64((int64_t)p.total_blocks * 32, 256), 256, 0, st>>>(dp, a);
+    PCV_LAUNCHED();
+}
+
+void launch_selfjoin_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a) {
+    if (p.total_blocks == 0) return;
+    const uint32_t NT = a.tile_blocks;
+    PCV_REQUIRE((NT == 1 || NT == 2 || NT == 4) && a.span_blocks >= NT, "self-join screen: bad tile (%u blocks, spans of %u)", NT, a.span_blocks);
+    const size_t lds = (size_t)NT * 32 * p.D4 * 4 * sizeof(uint16_t);
+    const unsigned tiles = (p.total_blocks + NT - 1) / NT;
+    const unsigned spans = (p.total_blocks + a.span_blocks - 1) / a.span_blocks;
+    PCV_REQUIRE(spans <= 65535u, "self-join screen: %u spans", spans);
+    const dim3 grid(tiles, spans);
+#define PCV_JOIN(N)                                                        \
+    allow_dynamic_lds((const void*)selfjoin_screen_kernel<N>, lds);        \
+    selfjoin_screen_kernel<N><<<grid, kJoinWaves * 64, lds, st>>>(dp, a);
+    if (NT == 4) {
+        PCV_JOIN(4)
+    } else if (NT == 2) {
+        PCV_JOIN(2)
+    } else {
+        PCV_JOIN(1)
+    }
+#undef PCV_JOIN
+    PCV_LAUNCHED();
+}
+
+void launch_selfjoin_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a) {
+    if (a.n_cand == 0) return;
+    selfjoin_rescore_kernel<<<cdiv64((int64_t)a.n_cand, 256), 256, 0, st>>>(dp, a);
+    PCV_LAUNCHED();
+}
+
+}  // namespace pcv

@@ -13,6 +13,7 @@ from . import _ffi
 from .context import Context
 
 PCV_MAX_DISTINCT_POOL = 4096  # include/perceive_hip.h
+PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 
 _METRICS = {"cosine": _ffi.METRIC_COSINE, "dot": _ffi.METRIC_DOT}
 _KERNELS = {"auto": _ffi.KERNEL_AUTO, "wave": _ffi.KERNEL_WAVE, "mfma": _ffi.KERNEL_MFMA}
@@ -416,6 +417,35 @@ class Searcher:
             raise KeyError("Item not found")
         return self.search_distinct_vector(sources, num_results, vec[0], threshold, pool)
 
+    # ---- duplicate pairs (pcv_searcher_find_duplicates) ----------------------------------------------
+    # The exact self-join of the corpus: what search_distinct collapses per query, found once for remove_items / hide_items.
+    def find_duplicates(self, sources, threshold, max_pairs=1 << 20):
+        """Every pair of searchable rows of `sources` whose canonical cosine is >= `threshold` (in (-1, 1]; both metrics), best
+        first (ties: lower position of the first row, then of the second), at most max_pairs of them -> (id_a [n] int64, id_b [n]
+        int64, scores [n] f32, total): id_a belongs to the row stored first, total is the exact number of pairs (total > n: there
+        are more than were returned).  A view joins its own rows."""
+        m = int(max_pairs)
+        if not 1 <= m <= PCV_MAX_DUPLICATE_PAIRS:
+            raise ValueError("max_pairs outside [1, 2^24]")
+        id_a = np.empty(m, dtype=np.int64)
+        id_b = np.empty(m, dtype=np.int64)
+        scores = np.empty(m, dtype=np.float32)
+        count, total = C.c_int64(), C.c_int64()
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_find_duplicates(
+                self._handle, src, nsrc, float(threshold), m, _ffi.i64p(id_a), _ffi.i64p(id_b), _ffi.f32p(scores), C.byref(count),
+                C.byref(total),
+            )
+        )
+        n = count.value
+        return id_a[:n].copy(), id_b[:n].copy(), scores[:n].copy(), total.value
+
+    def last_duplicate_stats(self):
+        st = _ffi.DuplicateStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_duplicate_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.DuplicateStats._fields_}
+
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):
         _ffi.check(_ffi.lib().pcv_searcher_set_kernel(self._handle, _KERNELS[kernel]))
@@ -638,6 +668,26 @@ class SearcherView(Searcher):
             if self.ctx._h:
                 _ffi.lib().pcv_searcher_destroy(self._h)
             self._h = C.c_void_p()
+
+
+def duplicate_groups(id_a, id_b):
+    """Groups of duplicates from the pairs of find_duplicates (host only) -> (ids [n] int64: the distinct ids of the pairs,
+    ascending; group [n] int64: the smallest id of each one's connected component).  ids[group != ids] are the items to remove to
+    keep one of every group."""
+    a = np.ascontiguousarray(id_a, dtype=np.int64).reshape(-1)
+    b = np.ascontiguousarray(id_b, dtype=np.int64).reshape(-1)
+    if a.size != b.size:
+        raise ValueError("id_a and id_b differ in length")
+    cap = max(1, 2 * a.size)
+    ids = np.empty(cap, dtype=np.int64)
+    group = np.empty(cap, dtype=np.int64)
+    n = C.c_int64()
+    _ffi.check(
+        _ffi.lib().pcv_duplicate_groups(
+            _ffi.i64p(a) if a.size else None, _ffi.i64p(b) if b.size else None, a.size, _ffi.i64p(ids), _ffi.i64p(group), cap, C.byref(n)
+        )
+    )
+    return ids[: n.value].copy(), group[: n.value].copy()
 
 
 def encode_query(model, query):

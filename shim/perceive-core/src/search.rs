@@ -394,6 +394,38 @@ impl Searcher {
         (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, similar[i])).collect()
     }
 
+    /// Duplicate pairs (`pcv_searcher_find_duplicates`): every pair of searchable items of `sources` whose cosine is at or above
+    /// `threshold`, best first, at most `max_pairs` of them (clamped to PCV_MAX_DUPLICATE_PAIRS) — the same page under several
+    /// URLs, found once for the whole index.  Returns the pairs as (id of the item stored first, id of the other, cosine) and the
+    /// exact number of pairs there are.
+    pub fn find_duplicates(&self, sources: &[i64], threshold: f32, max_pairs: usize) -> (Vec<(i64, i64, f32)>, i64) {
+        if self.handle.is_null() || max_pairs == 0 {
+            return (Vec::new(), 0);
+        }
+        let max_pairs = max_pairs.min(ffi::PCV_MAX_DUPLICATE_PAIRS as usize);
+        let mut id_a = vec![-1i64; max_pairs];
+        let mut id_b = vec![-1i64; max_pairs];
+        let mut scores = vec![f32::NAN; max_pairs];
+        let mut count: i64 = 0;
+        let mut total: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_find_duplicates(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                threshold,
+                max_pairs as i64,
+                id_a.as_mut_ptr(),
+                id_b.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut count,
+                &mut total,
+            )
+        })
+        .expect("find_duplicates failed");
+        ((0..count as usize).map(|i| (id_a[i], id_b[i], scores[i])).collect(), total)
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)

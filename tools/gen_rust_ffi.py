@@ -17,7 +17,7 @@ SCALARS = {
     "size_t": "usize", "float": "f32", "double": "f64", "uint8_t": "u8", "char": "c_char", "void": "c_void",
     "pcv_ctx": "pcv_ctx", "pcv_searcher": "pcv_searcher", "pcv_model": "pcv_model", "pcv_tokenizer": "pcv_tokenizer",
     "pcv_comm": "pcv_comm", "pcv_hit": "pcv_hit", "pcv_scan_stats": "pcv_scan_stats", "pcv_model_desc": "pcv_model_desc",
-    "pcv_encode_stats": "pcv_encode_stats",
+    "pcv_encode_stats": "pcv_encode_stats", "pcv_duplicate_stats": "pcv_duplicate_stats",
 }
 
 
