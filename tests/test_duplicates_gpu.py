@@ -4,7 +4,6 @@ score bits, count and total are compared for equality.
 
 The reference calls the oracle for every pair whose f64 cosine by numpy is within 1e-6 of the threshold or above it: the two f64
 computations differ by D * 2^-53 at most, so a pair further below cannot reach the threshold in the oracle either."""
-import ctypes as C
 import os
 import subprocess
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import perceive_amd as pa
+from duplicates_ref import bits, build, check, make_ids, neighbour, reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -20,69 +20,6 @@ pytestmark = pytest.mark.gpu
 D = 384
 PCV_ERR_UNSUPPORTED = 3
 BELOW_ONE = float(np.nextafter(np.float32(1.0), np.float32(0.0)))
-_FP = C.POINTER(C.c_float)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def reference(oracle, rows, ids, threshold, part=None):
-    """-> (id_a, id_b, f32 scores) of all duplicate pairs among rows[part] (positions ascending; None: all rows), in the call's order"""
-    rows = np.ascontiguousarray(rows, dtype=np.float32)
-    part = np.arange(rows.shape[0]) if part is None else np.asarray(part, dtype=np.int64)
-    thr = float(np.float32(threshold))  # (double)threshold
-    R = rows[part].astype(np.float64)
-    nrm = np.sqrt((R * R).sum(axis=1))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        G = (R @ R.T) / np.outer(nrm, nrm)
-    ia, ib = np.nonzero(np.triu(G >= thr - 1e-6, k=1))
-    dim = rows.shape[1]
-    ptr = {int(i): C.cast(rows.ctypes.data + int(part[i]) * dim * 4, _FP) for i in np.union1d(ia, ib)}
-    found = []
-    for a, b in zip(ia.tolist(), ib.tolist()):
-        c = oracle.lib.orc_canonical_score(ptr[a], ptr[b], dim, 0)
-        if c >= thr:
-            found.append((-c, a, b))
-    found.sort()
-    a = np.array([part[f[1]] for f in found], dtype=np.int64)
-    b = np.array([part[f[2]] for f in found], dtype=np.int64)
-    c = np.array([-f[0] for f in found], dtype=np.float64)
-    return ids[a], ids[b], c.astype(np.float32)
-
-
-def check(got, want, max_pairs=None):
-    id_a, id_b, scores, total = got
-    w_a, w_b, w_s = want
-    n = len(w_a) if max_pairs is None else min(len(w_a), max_pairs)
-    print("pairs %d/%d total %d/%d" % (len(id_a), n, total, len(w_a)))
-    assert total == len(w_a)
-    assert len(id_a) == len(id_b) == len(scores) == n
-    np.testing.assert_array_equal(id_a, w_a[:n])
-    np.testing.assert_array_equal(id_b, w_b[:n])
-    np.testing.assert_array_equal(bits(scores), bits(w_s[:n]))
-
-
-def neighbour(rng, a, cos):
-    """a row at cosine `cos` of a (up to the f32 rounding of its features), of a's norm"""
-    a64 = a.astype(np.float64)
-    u = rng.standard_normal(a.shape[0])
-    u -= (u @ a64) / (a64 @ a64) * a64
-    u *= np.linalg.norm(a64) / np.linalg.norm(u)
-    return (cos * a64 + np.sqrt(max(0.0, 1.0 - cos * cos)) * u).astype(np.float32)
-
-
-def make_ids(rng, n):
-    return (rng.permutation(n) * 7 + 1000).astype(np.int64)
-
-
-def build(ctx, rows, ids, metric="cosine", sources=None):
-    """sources: [(source id, first row, end row)]; None: everything in source 1"""
-    s = pa.Searcher(ctx, rows.shape[1], metric)
-    for sid, lo, hi in sources or [(1, 0, rows.shape[0])]:
-        s.add_rows(sid, rows[lo:hi], ids[lo:hi])
-    s.finalize()
-    return s
 
 
 # ---- 1. golden corpora with planted copies and neighbours ------------------------------------------------------------------
