@@ -180,6 +180,52 @@ inline std::vector<DuplicatePair> find_duplicates_handle(pcv_searcher* h, const 
     return out;
 }
 
+// Searcher::assign / kmeans and their SearcherView forms (pcv_searcher_assign, pcv_searcher_kmeans): the exact best of K label
+// vectors for every item of `sources`, by global position; label -1 and a NaN score for an item no search could return.
+struct Assignment {
+    std::vector<int32_t> label;   // [n]
+    std::vector<float> score;     // [n] as a search reports it
+    std::vector<int64_t> ids;     // [n]
+    std::vector<int64_t> counts;  // [K] items per label
+};
+struct KMeansResult {
+    std::vector<float> centroids;  // [K][dim], those the last assignment used
+    Assignment last;
+    int iterations = 0;            // updates made
+    std::vector<int64_t> moved;    // [iterations + 1] items that changed their label in each assignment
+};
+inline KMeansResult kmeans_handle(pcv_searcher* h, const std::vector<int64_t>& sources, const std::vector<float>& init, size_t k, int max_iters,
+                                  bool cosine_kmeans) {
+    KMeansResult r;
+    r.last.counts.assign(k, 0);
+    r.centroids = init;
+    if (sources.empty() || k == 0) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    if (cosine_kmeans)
+        check(pcv_searcher_kmeans(h, init.data(), (int)k, max_iters, sources.data(), (int)sources.size(), 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, &n));
+    else
+        check(pcv_searcher_assign(h, init.data(), (int)k, sources.data(), (int)sources.size(), 0, nullptr, nullptr, nullptr, nullptr, &n));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.last.label.resize(room);
+    r.last.score.resize(room);
+    r.last.ids.resize(room);
+    r.moved.assign((size_t)std::max(max_iters, 0) + 1, 0);
+    int32_t iters = 0;
+    if (cosine_kmeans)
+        check(pcv_searcher_kmeans(h, init.data(), (int)k, max_iters, sources.data(), (int)sources.size(), (int64_t)room, r.centroids.data(),
+                                  r.last.label.data(), r.last.score.data(), r.last.ids.data(), r.last.counts.data(), &iters, r.moved.data(), &n));
+    else
+        check(pcv_searcher_assign(h, init.data(), (int)k, sources.data(), (int)sources.size(), (int64_t)room, r.last.label.data(),
+                                  r.last.score.data(), r.last.ids.data(), r.last.counts.data(), &n));
+    r.last.label.resize((size_t)n);
+    r.last.score.resize((size_t)n);
+    r.last.ids.resize((size_t)n);
+    r.iterations = iters;
+    r.moved.resize((size_t)iters + 1);
+    return r;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -228,6 +274,19 @@ public:
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
                                                int64_t* total = nullptr) const {
         return find_duplicates_handle(h_, sources, threshold, max_pairs, total);
+    }
+    // the best of the k label vectors `labels` [k][dim] for every item (kmeans_handle)
+    Assignment assign(const std::vector<int64_t>& sources, const std::vector<float>& labels, size_t k) const {
+        return kmeans_handle(h_, sources, labels, k, 0, false).last;
+    }
+    // spherical k-means by cosine from `init` [k][dim], at most max_iters updates (kmeans_handle)
+    KMeansResult kmeans(const std::vector<int64_t>& sources, const std::vector<float>& init, size_t k, int max_iters = 20) const {
+        return kmeans_handle(h_, sources, init, k, max_iters, true);
+    }
+    pcv_assign_stats last_assign_stats() const {
+        pcv_assign_stats st;
+        check(pcv_searcher_last_assign_stats(h_, &st));
+        return st;
     }
     // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
     std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
@@ -322,6 +381,19 @@ public:
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
                                                int64_t* total = nullptr) const {
         return find_duplicates_handle(h_, sources, threshold, max_pairs, total);
+    }
+    // the best of the k label vectors `labels` [k][dim] for every item (kmeans_handle)
+    Assignment assign(const std::vector<int64_t>& sources, const std::vector<float>& labels, size_t k) const {
+        return kmeans_handle(h_, sources, labels, k, 0, false).last;
+    }
+    // spherical k-means by cosine from `init` [k][dim], at most max_iters updates (kmeans_handle)
+    KMeansResult kmeans(const std::vector<int64_t>& sources, const std::vector<float>& init, size_t k, int max_iters = 20) const {
+        return kmeans_handle(h_, sources, init, k, max_iters, true);
+    }
+    pcv_assign_stats last_assign_stats() const {
+        pcv_assign_stats st;
+        check(pcv_searcher_last_assign_stats(h_, &st));
+        return st;
     }
     // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the
     // item itself is the first hit unless `exclude`.  nullopt: no row carries the id.

@@ -459,6 +459,84 @@ typedef struct pcv_duplicate_stats {
 } pcv_duplicate_stats;
 pcv_status pcv_searcher_last_duplicate_stats(pcv_searcher* s, pcv_duplicate_stats* out);
 
+/* Item labels: the exact best of K label vectors for EVERY row — the transpose of a search (which rows are best for a few vectors).
+ * A host encodes K tag or topic prompts and wants each stored item tagged with its best one and a count per tag; every Lloyd
+ * iteration of k-means is the same pass.  Computed where the rows live, in one pass over the f32 rows per tile of labels.
+ * The rows concerned are those of the selected segments in global position order, n of them (hidden and unsearchable rows
+ * included: they keep their place); source_ids == NULL means all sources, an empty list selects nothing (n = 0); a view assigns
+ * its own rows.  A row TAKES PART iff a pcv_searcher_search with the same filter could return it (searchable, not hidden,
+ * scale != 0).  For such a row r, c(r, j) = the canonical score of labels[j] in the query's place and the stored f32 row — f64,
+ * products exact, sums in feature order, with the searcher's metric — and label(r) is the j with the largest
+ * defined c(r, j), ties to the lower j.  If no c(r, j) is defined (under cosine: a row or label of zero or non-finite norm), or the
+ * row takes no part, label = -1 and the score is NaN.
+ *   labels       host [K][dim] f32, 1 <= K <= PCV_MAX_LABELS, every value finite
+ *   capacity     entries the per-row outputs have room for; the call fails with PCV_ERR_INVALID if capacity < n (out_n is set)
+ *   out_label    [capacity] int32
+ *   out_score    [capacity] what pcv_searcher_search reports for that (label vector, row) pair, bit for bit: cosine (float)c, dot
+ *                the f32 distance (may be NULL)
+ *   out_ids      [capacity] the item id of every position (may be NULL)
+ *   out_counts   [K] rows per label (may be NULL)
+ *   out_n        n.  With out_label == NULL and capacity == 0 the call only reports n (the style of pcv_searcher_hidden_ids) and does no
+ *                device work
+ * A NULL searcher, labels or out_n, K out of range, a NaN or Inf in a label, or out_label == NULL with capacity != 0 give
+ * PCV_ERR_INVALID before any device work; a searcher with pending rows fails as in pcv_searcher_search.  A dimension whose bf16
+ * label tile does not fit the LDS of a CU gives PCV_ERR_UNSUPPORTED, and so does a call whose bf16 screen lists more than 2^28
+ * (row, label) candidates (thousands of near-identical labels over millions of rows).  The result does not depend on which screening
+ * copies exist, nor on pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity: the pass reads the f32 rows and touches no
+ * pass state (DESIGN.md §4 "Item labels").  Everything the call allocates on the device is given back when it returns.
+ * Not in scope: the top-m labels per row, a sharded form, device-resident output. */
+enum { PCV_MAX_LABELS = 4096 };
+pcv_status pcv_searcher_assign(pcv_searcher* s, const float* labels, int n_labels, const int64_t* source_ids, int n_sources, int64_t capacity,
+                               int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts, int64_t* out_n);
+
+/* The integer sums of the unit rows of every label, reproducible bit for bit.  labels[n] names a label in [0, K) for every position of
+ * the selected rows (as pcv_searcher_assign orders them; a negative value: none).  With rinv_r = (float)(1 / sqrt(|x_r|^2)) from the
+ * canonical f64 |x_r|^2 and t(r, d) = rint((double)x[r][d] * (double)rinv_r * 2^32) as int64 — the product of two f32 is exact in
+ * f64, so one rounding, half to even —
+ *   out_sums[j][d] = sum of t(r, d) over the rows with labels[r] == j that have a cosine (squared norm in [2^-126, inf))
+ *   out_counts[j]  = how many rows that were (may be NULL)
+ * Integer addition is associative: whatever order the device adds in, the bits are the same, and three lines of numpy reproduce
+ * them.  |t| <= 2^32 (1 + 2^-23), so a label with more than 2^30 members is refused (PCV_ERR_UNSUPPORTED).  A row that takes
+ * no part in pcv_searcher_assign (hidden, or unsearchable: scale 0) adds nothing and is not counted, whatever label it is given, like
+ * a row without a cosine.  Any dimension is accepted (the sums need no label tile).  n must be the n of pcv_searcher_assign for
+ * the same filter, K in [1, PCV_MAX_LABELS], no label >= K (PCV_ERR_INVALID).  centroid[j][d] = (float)((double)out_sums[j][d] * 2^-32)
+ * is the mean direction up to length, which a cosine ignores. */
+pcv_status pcv_searcher_label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const int32_t* labels, int64_t n, int n_labels,
+                                   int64_t* out_sums, int64_t* out_counts);
+
+/* Spherical k-means (Lloyd) on the device, reproducible bit for bit.  It clusters by the canonical cosine for BOTH searcher metrics,
+ * as pcv_searcher_find_duplicates does.  Starting from centroids = init[K][dim]:
+ *   assignment i labels every row with the current centroids exactly as pcv_searcher_assign does under cosine; moved[i] is the
+ *   number of rows whose label differs from the assignment before (before the first: every row has label -1);
+ *   if moved[i] == 0, or max_iters updates have been made, the call ends; otherwise update: centroid[j] becomes
+ *   (float)((double)S[j][d] * 2^-32) with S the sums of pcv_searcher_label_sums for these labels — not normalised; a label without a
+ *   member keeps its vector — and the next assignment follows.
+ *   out_centroids [K][dim] the centroids the LAST assignment used
+ *   out_label, out_score, out_ids, out_counts, capacity, out_n   of the last assignment, as in pcv_searcher_assign (out_label may be
+ *                 NULL here only together with capacity == 0, which reports n alone)
+ *   out_iters     updates made (may be NULL);   out_moved  [max_iters + 1], entries 0 .. *out_iters filled (may be NULL)
+ * max_iters = 0 is pcv_searcher_assign with the cosine metric.  The labels stay on the device between the steps; per update only the
+ * K x dim sums come to the host, where the centroids are formed.  Errors as pcv_searcher_assign, plus max_iters < 0 and a NULL init
+ * or out_centroids (PCV_ERR_INVALID) and a label with more than 2^30 members (PCV_ERR_UNSUPPORTED).  Not in scope: seeding
+ * (k-means++), a sharded form, device-resident output. */
+pcv_status pcv_searcher_kmeans(pcv_searcher* s, const float* init, int n_labels, int max_iters, const int64_t* source_ids, int n_sources,
+                               int64_t capacity, float* out_centroids, int32_t* out_label, float* out_score, int64_t* out_ids,
+                               int64_t* out_counts, int32_t* out_iters, int64_t* out_moved, int64_t* out_n);
+
+/* Counters of the most recent pcv_searcher_assign or pcv_searcher_kmeans on this handle (k-means: times summed over its
+ * assignments, the other counters those of the last one). */
+typedef struct pcv_assign_stats {
+    int64_t rows;         /* rows of the selected segments (those taking no part included)       */
+    int64_t candidates;   /* (row, label) pairs the bf16 screen listed                            */
+    int32_t label_tiles;  /* label tiles = passes over the f32 rows                               */
+    int32_t tile_labels;  /* labels of one LDS tile (128, 64 or 32)                               */
+    int32_t reruns;       /* screens repeated because the candidate list was short                */
+    float prep_ms;        /* hipEvent times of the three steps (a repeated screen included)       */
+    float screen_ms;
+    float rescore_ms;
+} pcv_assign_stats;
+pcv_status pcv_searcher_last_assign_stats(pcv_searcher* s, pcv_assign_stats* out);
+
 /* Groups of duplicates from a list of pairs (host only: needs no context and no GPU).  out_ids receives the distinct ids occurring
  * in the n_pairs pairs, ascending, and out_group[i] the smallest id of the connected component of out_ids[i]: an item is a candidate
  * for removal iff out_group[i] != out_ids[i].  out_n_ids receives the number of distinct ids; capacity < that gives PCV_ERR_INVALID

@@ -63,6 +63,19 @@ class DuplicateStats(C.Structure):
     ]
 
 
+class AssignStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("candidates", C.c_int64),
+        ("label_tiles", C.c_int32),
+        ("tile_labels", C.c_int32),
+        ("reruns", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("screen_ms", C.c_float),
+        ("rescore_ms", C.c_float),
+    ]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32),
@@ -154,6 +167,11 @@ SYMBOLS = {
     "pcv_searcher_search_distinct": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int, _I64P, _F32P, _INTP, _INTP, _INTP, _U8P]),
     "pcv_searcher_find_duplicates": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_last_duplicate_stats": (C.c_int, [_P, C.POINTER(DuplicateStats)]),
+    "pcv_searcher_assign": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int64, _INTP, _F32P, _I64P, _I64P, C.POINTER(C.c_int64)]),
+    "pcv_searcher_label_sums": (C.c_int, [_P, _I64P, C.c_int, _INTP, C.c_int64, C.c_int, _I64P, _I64P]),
+    "pcv_searcher_kmeans": (C.c_int, [_P, _F32P, C.c_int, C.c_int, _I64P, C.c_int, C.c_int64, _F32P, _INTP, _F32P, _I64P, _I64P,
+                                      C.POINTER(C.c_int32), _I64P, C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_assign_stats": (C.c_int, [_P, C.POINTER(AssignStats)]),
     "pcv_duplicate_groups": (C.c_int, [_I64P, _I64P, C.c_int64, _I64P, _I64P, C.c_int64, C.POINTER(C.c_int64)]),
     "pcv_searcher_like_queries": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _F32P, _P, _U8P, _I64P]),
     "pcv_searcher_search_like": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _INTP, _U8P]),

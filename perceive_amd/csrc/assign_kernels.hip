@@ -1,0 +1,415 @@
+// assign_kernels.hip — the device steps of pcv_searcher_assign, _label_sums and _kmeans (DESIGN.md §4 "Item labels"): the best of K
+// label vectors for every row, exact, and the integer sum of the unit rows of every label.  The transpose of a search: the reduction
+// runs across the LDS tile (the labels), not along the stream (the rows).
+//
+//   prep     the labels are a small corpus in the blocked f32 layout, so selfjoin_prep_kernel gives their canonical |l|^2 and rinv as
+//            it gives the rows' (launch_selfjoin_prep, called twice); assign_labels_kernel then writes each label's screening
+//            constants (w, mg: scan.h, AssignArgs) and its bf16 pieces in the swizzled order of the LDS tile.
+//   screen   assign_screen_kernel: a workgroup stages one label tile in LDS and its waves stream row blocks out of the blocked f32
+//            layout as the A fragment of v_mfma_f32_32x32x16_bf16 (the streaming discipline of selfjoin_screen_kernel).  Per block the
+//            epilogue reduces s - mg over the tile's labels for each of the 32 rows, joins it with the bound the earlier tiles left
+//            (lb) and lists every (row, label) with s + mg >= that bound.
+//   rescore  assign_rescore_kernel: the canonical f64 score of every candidate that passes the FINAL bound (pair_sums, finish_score:
+//            the arithmetic of selfjoin_rescore_kernel) and an atomic max of its order-preserving image per row;
+//            assign_pick_kernel: an atomic min of the label among the candidates that reach that maximum — (c descending, label
+//            ascending), whatever order the atomics land in;  assign_finish_kernel: labels, reported scores, ids, counts.
+//   sums     label_sums_kernel: S[label][d] += rint(x[r][d] * rinv_r * 2^32) in int64 — associative, so any order gives the same bits.
+#include "device_access.h"
+#include "launch_rows.h"
+#include "scan.h"
+
+namespace pcv {
+namespace {
+
+constexpr int kAssignWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
+
+__device__ __forceinline__ unsigned long long g_atomic_max64(unsigned long long* p, unsigned long long v) {
+    return __hip_atomic_fetch_max((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t g_atomic_min(uint32_t* p, uint32_t v) {
+    return __hip_atomic_fetch_min((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void g_atomic_add_i64(long long* p, long long v) {
+    (void)__hip_atomic_fetch_add((PCV_GLOBAL long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// one thread per (label slot, 16-byte piece of 8 bf16); the thread of piece 0 also writes the label's constants
+__global__ __launch_bounds__(256) void assign_labels_kernel(const AssignArgs a, int D4) {
+    const int P8 = D4 >> 1;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint64_t)a.label_blocks * 32 * P8) return;
+    const uint32_t slot = (uint32_t)(i / P8);
+    const int pc = (int)(i - (uint64_t)slot * P8);
+    const float4* base = a.lab_blk + (size_t)(slot >> 5) * D4 * 32 + (slot & 31);
+    const float4 lo = gld4(base + (size_t)(2 * pc) * 32), hi = gld4(base + (size_t)(2 * pc + 1) * 32);
+    const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const bf16x8 v8 = __builtin_convertvector(v, bf16x8);  // round to nearest even, as the screens round the rows
+    a.lab_tile[(size_t)slot * P8 + swizzle_piece(pc, (int)slot, P8)] = __builtin_bit_cast(uint4, v8);
+    if (pc != 0) return;
+    const float rinv = gld(&a.lab_rinv[slot]);
+    float w = rinv, mg = a.margin;
+    if (a.metric == PCV_METRIC_DOT) {
+        const double n = gld(&a.lab_norm[slot]);
+        if ((int)slot >= a.K) {
+            w = 0.0f;
+        } else if (rinv > 0.0f || n == 0.0) {  // (the zero label: every product is an exact zero)
+            w = 1.0f;
+            mg = __double2float_ru((double)a.margin * sqrt(n) * (1.0 + 0x1p-40));
+        } else {
+            w = kRinvWild;
+        }
+    }
+    gst(&a.w[slot], w);
+    gst(&a.mg[slot], mg);
+}
+
+// one thread per launch row: the state an assignment starts from
+__global__ __launch_bounds__(256) void assign_begin_kernel(const ScanParams* __restrict__ pp, const AssignArgs a) {
+    const ScanParams& p = *pp;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint64_t)p.total_blocks * 32) return;
+    gst(&a.lb[i], -__builtin_inff());
+    gst(&a.best_key[i], 0ull);
+    gst(&a.best_lab[i], 0xffffffffu);
+    if (a.metric == PCV_METRIC_DOT && gld(&a.rinv[i]) == 0.0f) {  // no cosine, but its dot products are defined: the f64 step decides
+        const RowRef r = row_ref(p, (uint32_t)i);
+        if (r.row < gld(&r.sg->nrows) && gld(&gld(&r.sg->scale)[r.row]) != 0.0f) gst(&a.rinv[i], kRinvWild);
+    }
+}
+
+// grid: x = span of row blocks [x * span_blocks, + span_blocks), cut at the launch's end; wave w of the workgroup takes the blocks
+// first + w, first + w + kAssignWaves, ...  The label tile is a.tile.
+// D[row of the streamed block][label of the tile]: lane (c = lane & 31, h = lane >> 5) holds labels 32 t + c of the tile and, in
+// accumulator i, block row (i & 3) + 8 (i >> 2) + 4 h — the reduction over the labels of a row is over t in the lane and over the 32
+// lanes of a half.
+template <int NT>
+__global__ __launch_bounds__(kAssignWaves * 64) void assign_screen_kernel(const ScanParams* __restrict__ pp, const AssignArgs a) {
+    const ScanParams& p = *pp;
+    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
+    const int D4 = p.D4, P8 = D4 >> 1, NCH = D4 >> 4;
+    const uint32_t TB = p.total_blocks;
+    const uint64_t first = (uint64_t)blockIdx.x * a.span_blocks;
+    if (first >= TB) return;  // (the whole workgroup)
+    const uint32_t b0 = (uint32_t)first;
+    const uint32_t b1 = (uint32_t)min((uint64_t)TB, first + a.span_blocks);
+
+    {
+        const u32x4* src = (const u32x4*)(a.lab_tile + (size_t)a.tile * NT * 32 * P8);
+        for (int i = threadIdx.x; i < NT * 32 * P8; i += kAssignWaves * 64) lq[i] = __builtin_bit_cast(uint4, *(const PCV_GLOBAL u32x4*)(src + i));
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    if (b0 + wave >= b1) return;
+    const uint32_t l0 = a.tile * NT * 32;
+    float w[NT], mg[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        w[t] = gld(&a.w[l0 + 32 * t + c]);
+        mg[t] = gld(&a.mg[l0 + 32 * t + c]);
+    }
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+
+    auto enter_block = [&](JoinCursor& k, uint32_t gb) {
+        k.gb = gb;
+        k.ch = 0;
+        if (gb < b1) {
+            join_seek(p, k.sc, gb);
+            k.rows = row_rsrc(k.sc.blk + (size_t)(gb - k.sc.begin) * D4 * 32, (uint32_t)D4 * 512u);
+        }
+    };
+    const uint32_t lane_off = (uint32_t)(h * 64 + c) * 16u;  // the lane's bytes inside a block
+    JoinCursor cons, prod;
+    enter_block(cons, b0 + wave);
+    prod = cons;
+
+    float4 buf[2][8];
+    // (always issues its loads: past the end of the wave's stream they read a chunk of its last block again — scan_mfma_kernel)
+    auto produce = [&](float4 (&b)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
+        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + kAssignWaves);
+    };
+
+    f32x4 rb[4], lbv[4];  // rinv and the carried bound of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
+    auto rb_prefetch = [&]() {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            rb[j] = *(const PCV_GLOBAL f32x4*)(a.rinv + (size_t)cons.gb * 32 + 8 * j + 4 * h);
+            lbv[j] = *(const PCV_GLOBAL f32x4*)(a.lb + (size_t)cons.gb * 32 + 8 * j + 4 * h);
+        }
+    };
+
+    auto epilogue = [&]() {
+        if (NCH < 2) rb_prefetch();
+        // the row's bound: the largest certified lower end s - mg over the tile's labels, joined with what earlier tiles left
+        float lo[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float rbi = rb[i >> 2][i & 3];
+            float m = -__builtin_inff();
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const float s = acc[t][i] * rbi * w[t];
+                m = (rbi > 0.0f && w[t] > 0.0f) ? fmaxf(m, s - mg[t]) : m;
+            }
+            lo[i] = m;
+        }
+#pragma unroll
+        for (int off = 1; off < 32; off <<= 1)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) lo[i] = fmaxf(lo[i], __shfl_xor(lo[i], off));
+#pragma unroll
+        for (int i = 0; i < 16; ++i) lo[i] = fmaxf(lo[i], lbv[i >> 2][i & 3]);
+        if (c == 0) {  // (this wave is the only one that has the block in this launch; launches follow each other on the stream)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 v = {lo[4 * j], lo[4 * j + 1], lo[4 * j + 2], lo[4 * j + 3]};
+                *(PCV_GLOBAL f32x4*)(a.lb + (size_t)cons.gb * 32 + 8 * j + 4 * h) = v;
+            }
+        }
+        // a wild row or label: every defined pair (scan.h); otherwise the certified upper end against the bound
+        auto passes = [&](int t, int i) -> bool {
+            const float rbi = rb[i >> 2][i & 3];
+            if (rbi == 0.0f || w[t] == 0.0f) return false;
+            if (rbi < 0.0f || w[t] < 0.0f) return true;
+            return acc[t][i] * rbi * w[t] + mg[t] >= lo[i];
+        };
+        uint32_t mask[NT];
+        uint32_t n = 0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            mask[t] = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mask[t] |= passes(t, i) ? (1u << i) : 0u;
+            n += (uint32_t)__builtin_popcount(mask[t]);
+        }
+        if (n) {
+            unsigned long long at = g_atomic_add64(&a.counters[0], n);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    if (mask[t] & (1u << i)) {
+                        if (at < a.cand_cap) {
+                            const float rbi = rb[i >> 2][i & 3];
+                            const float s = (rbi < 0.0f || w[t] < 0.0f) ? __builtin_inff() : acc[t][i] * rbi * w[t];
+                            gst(&a.cand[at], ((uint64_t)(cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h)) << 32) | (l0 + 32u * t + (uint32_t)c));
+                            gst(&a.cand_s[at], s);
+                        }
+                        ++at;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    };
+
+    auto consume = [&](const float4 (&b)[8]) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const f32x8 v = {b[2 * ks].x, b[2 * ks].y, b[2 * ks].z, b[2 * ks].w, b[2 * ks + 1].x, b[2 * ks + 1].y, b[2 * ks + 1].z, b[2 * ks + 1].w};
+            const bf16x8 av = __builtin_convertvector(v, bf16x8);
+            const int pc = 2 * (cons.ch * 4 + ks) + h;
+            const int ph = swizzle_piece(pc, c, P8);  // (tile label 32 t + c: the same low four bits as c)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const bf16x8 q8 = *(const bf16x8*)&lq[(32 * t + c) * P8 + ph];
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q8, acc[t], 0, 0, 0);
+            }
+        }
+        if (++cons.ch == NCH) {
+            epilogue();
+            enter_block(cons, cons.gb + kAssignWaves);
+        }
+    };
+
+    // one chunk of loads in flight while one feeds the matrix cores (every buf[] index a literal, or the array moves to scratch);
+    // the block's rinv and bound are requested one chunk ahead of the epilogue and before that step's row loads
+#define PCV_ASSIGN_STEP(REFILL, CONS)                    \
+    if (NCH >= 2 && cons.ch == NCH - 2) rb_prefetch();   \
+    produce(buf[REFILL]);                                \
+    consume(buf[CONS]);                                  \
+    if (cons.gb >= b1) return;
+    produce(buf[0]);
+    while (true) {
+        PCV_ASSIGN_STEP(1, 0)
+        PCV_ASSIGN_STEP(0, 1)
+    }
+#undef PCV_ASSIGN_STEP
+}
+
+// one thread per candidate: its canonical score if it passes the final bound, and the row's running maximum
+__global__ __launch_bounds__(256) void assign_rescore_kernel(const ScanParams* __restrict__ pp, const AssignArgs a) {
+    const ScanParams& p = *pp;
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_cand) return;
+    const uint64_t cd = gld(&a.cand[i]);
+    const uint32_t lr = (uint32_t)(cd >> 32), j = (uint32_t)cd;
+    unsigned long long key = 0;
+    if (gld(&a.cand_s[i]) + gld(&a.mg[j]) >= gld(&a.lb[lr])) {
+        const RowRef r = row_ref(p, lr);
+        const float4* y[1] = {a.lab_blk + (size_t)(j >> 5) * p.D4 * 32 + (j & 31)};
+        double acc[1];
+        pair_sums<1>(r.x, y, p.D4, acc, 32);
+        const double cc = finish_score(a.metric, acc[0], gld(&a.norm[lr]), gld(&a.lab_norm[j]));
+        if (cc == cc) {
+            key = f64_key(cc);
+            g_atomic_max64(&a.best_key[lr], key);
+        }
+    }
+    gst(&a.cand_key[i], key);
+}
+
+// ... and the lowest label among those that reach it
+__global__ __launch_bounds__(256) void assign_pick_kernel(const AssignArgs a) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_cand) return;
+    const unsigned long long key = gld(&a.cand_key[i]);
+    if (key == 0) return;
+    const uint64_t cd = gld(&a.cand[i]);
+    const uint32_t lr = (uint32_t)(cd >> 32);
+    if (key == gld(&a.best_key[lr])) g_atomic_min(&a.best_lab[lr], (uint32_t)cd);
+}
+
+// one thread per launch row: the outputs by position among the selected rows, the histogram, the rows that changed their label
+__global__ __launch_bounds__(256) void assign_finish_kernel(const ScanParams* __restrict__ pp, const AssignArgs a) {
+    const ScanParams& p = *pp;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (uint64_t)p.total_blocks * 32) return;
+    const RowRef r = row_ref(p, (uint32_t)i);
+    int32_t label = -1;
+    if (r.row < gld(&r.sg->nrows)) {
+        const unsigned long long key = gld(&a.best_key[i]);
+        float score = __builtin_nanf("");
+        if (key != 0) {
+            label = (int32_t)gld(&a.best_lab[i]);
+            score = reported_score(a.metric, p.D, key_f64(key));
+            g_atomic_add_i64(&a.out_counts[label], 1ll);
+        }
+        const int64_t o = gld(&a.seg_out0[r.sg - p.seg]) + (int64_t)r.row;
+        const int64_t* ids = gld(&r.sg->ids);
+        gst(&a.out_label[o], label);
+        gst(&a.out_score[o], score);
+        gst(&a.out_ids[o], ids ? gld(&ids[r.row]) : gld(&r.sg->id0) + (int64_t)r.row);
+    }
+    const unsigned long long moved = __ballot(gld(&a.row_label[i]) != label);  // (row_label starts at -1)
+    if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(moved | (1ull << 63)) && moved) g_atomic_add64(&a.counters[1], (unsigned long long)__builtin_popcountll(moved));
+    gst(&a.row_label[i], label);
+}
+
+constexpr int kSumBlocks = 8;  // row blocks of one label_sums workgroup
+
+// grid: x = kSumBlocks row blocks; thread = one 16-byte piece of four features (pieces tid, tid + 256, ...).  The rows are walked in
+// order and a run of rows with one label is summed in registers before it goes to S: fewer atomics where neighbours share a label,
+// the same bits either way.
+__global__ __launch_bounds__(256) void label_sums_kernel(const ScanParams* __restrict__ pp, const AssignArgs a) {
+    const ScanParams& p = *pp;
+    const int D4 = p.D4, Dp = D4 * 4;
+    const uint32_t gb0 = blockIdx.x * kSumBlocks, gb1 = min(p.total_blocks, gb0 + kSumBlocks);
+    for (int f = threadIdx.x; f < D4; f += 256) {
+        long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, members = 0;
+        int cur = -1;
+        auto flush = [&]() {
+            if (cur >= 0) {
+                if (f == 0) g_atomic_add_i64(&a.sum_counts[cur], members);
+                long long* d = a.sums + (size_t)cur * Dp + 4 * f;
+                if (s0) g_atomic_add_i64(d, s0);
+                if (s1) g_atomic_add_i64(d + 1, s1);
+                if (s2) g_atomic_add_i64(d + 2, s2);
+                if (s3) g_atomic_add_i64(d + 3, s3);
+            }
+            s0 = s1 = s2 = s3 = members = 0;
+        };
+        int si = -1;
+        for (uint32_t gb = gb0; gb < gb1; ++gb) {
+            si = find_seg(p, gb, si < 0 ? 0 : si);
+            const SegDesc* sg = &p.seg[si];
+            const float4* blk = gld(&sg->blk) + ((size_t)(gb - gld(&sg->blk0)) * D4 + f) * 32;
+            for (int r = 0; r < 32; ++r) {
+                const size_t lr = (size_t)gb * 32 + r;
+                const int lab = gld(&a.row_label[lr]);
+                if (lab < 0 || lab >= a.K) continue;
+                const double n = gld(&a.norm[lr]);
+                if (!(n >= 0x1p-126 && n < __builtin_inf())) continue;  // no cosine: the row adds nothing
+                if (lab != cur) {
+                    flush();
+                    cur = lab;
+                }
+                const double rs = (double)(float)(1.0 / sqrt(n)) * 0x1p32;  // (the f32 rinv of the prep step, also where that marks wild)
+                const float4 v = gld4(blk + r);
+                s0 += (long long)rint((double)v.x * rs);
+                s1 += (long long)rint((double)v.y * rs);
+                s2 += (long long)rint((double)v.z * rs);
+                s3 += (long long)rint((double)v.w * rs);
+                ++members;
+            }
+        }
+        flush();
+    }
+}
+
+}  // namespace
+
+void launch_assign_labels(hipStream_t st, const ScanParams& p, const AssignArgs& a) {
+    assign_labels_kernel<<<cdiv64((int64_t)a.label_blocks * 32 * (p.D4 / 2), 256), 256, 0, st>>>(a, p.D4);
+    PCV_LAUNCHED();
+}
+
+void launch_assign_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a) {
+    if (p.total_blocks == 0) return;
+    assign_begin_kernel<<<cdiv64((int64_t)p.total_blocks * 32, 256), 256, 0, st>>>(dp, a);
+    PCV_LAUNCHED();
+}
+
+void launch_assign_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a) {
+    if (p.total_blocks == 0) return;
+    const uint32_t NT = a.tile_blocks;
+    PCV_REQUIRE((NT == 1 || NT == 2 || NT == 4) && a.span_blocks >= 1 && (a.tile + 1) * NT <= a.label_blocks,
+                "assign screen: bad tile (%u blocks, tile %u of %u label blocks, spans of %u)", NT, a.tile, a.label_blocks, a.span_blocks);
+    const size_t lds = (size_t)NT * 32 * p.D4 * 4 * sizeof(uint16_t);
+    const unsigned grid = (p.total_blocks + a.span_blocks - 1) / a.span_blocks;
+#define PCV_ASSIGN(N)                                                    \
+    allow_dynamic_lds((const void*)assign_screen_kernel<N>, lds);        \
+    assign_screen_kernel<N><<<grid, kAssignWaves * 64, lds, st>>>(dp, a);
+    if (NT == 4) {
+        PCV_ASSIGN(4)
+    } else if (NT == 2) {
+        PCV_ASSIGN(2)
+    } else {
+        PCV_ASSIGN(1)
+    }
+#undef PCV_ASSIGN
+    PCV_LAUNCHED();
+}
+
+void launch_assign_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a) {
+    if (a.n_cand == 0) return;
+    assign_rescore_kernel<<<cdiv64((int64_t)a.n_cand, 256), 256, 0, st>>>(dp, a);
+    assign_pick_kernel<<<cdiv64((int64_t)a.n_cand, 256), 256, 0, st>>>(a);
+    PCV_LAUNCHED();
+}
+
+void launch_assign_finish(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a) {
+    if (p.total_blocks == 0) return;
+    assign_finish_kernel<<<cdiv64((int64_t)p.total_blocks * 32, 256), 256, 0, st>>>(dp, a);
+    PCV_LAUNCHED();
+}
+
+void launch_label_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a) {
+    if (p.total_blocks == 0) return;
+    label_sums_kernel<<<(p.total_blocks + kSumBlocks - 1) / kSumBlocks, 256, 0, st>>>(dp, a);
+    PCV_LAUNCHED();
+}
+
+}  // namespace pcv

@@ -1,0 +1,63 @@
+// launch_rows.h — what the kernels that walk a launch's rows by number share (selfjoin_kernels.hip, assign_kernels.hip): finding the
+// segment of a launch row (scan.h, "launch row") and the wave-uniform cursor of a stream of row blocks.  Everything here is inlined:
+// the file defines no symbol.
+#pragma once
+#include "device_access.h"
+#include "scan.h"
+
+namespace pcv {
+namespace {
+
+__device__ __forceinline__ unsigned long long g_atomic_add64(unsigned long long* p, unsigned long long v) {
+    return __hip_atomic_fetch_add((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// last table entry with blk0 <= gb
+__device__ __forceinline__ int find_seg(const ScanParams& p, uint32_t gb, int from = 0) {
+    int lo = from, hi = p.nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (gld(&p.seg[mid].blk0) <= gb)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// Launch row `lr` (scan.h): its segment, its row there and where its first piece is.
+struct RowRef {
+    const SegDesc* sg;
+    uint32_t row;
+    const float4* x;
+};
+__device__ __forceinline__ RowRef row_ref(const ScanParams& p, uint32_t lr) {
+    const uint32_t gb = lr >> 5;
+    const SegDesc* sg = &p.seg[find_seg(p, gb)];
+    const uint32_t lb = gb - gld(&sg->blk0);
+    return {sg, lb * 32 + (lr & 31), gld(&sg->blk) + (size_t)lb * p.D4 * 32 + (lr & 31)};
+}
+
+// The segment a wave's stream is in (all of it wave-uniform, in scalar registers: scan_kernels.hip, seek_seg).
+struct JoinSeg {
+    int si = -1;
+    uint32_t begin = 0, end = 0;
+    const float4* blk = nullptr;
+};
+__device__ __forceinline__ void join_seek(const ScanParams& p, JoinSeg& c, uint32_t gb) {
+    if (gb < c.end) return;
+    const int lo = find_seg(p, gb, c.si + 1);
+    c.si = lo;
+    c.begin = uniform(gld(&p.seg[lo].blk0));
+    c.end = c.begin + uniform(gld(&p.seg[lo].nblocks));
+    c.blk = uniform_ptr(gld(&p.seg[lo].blk));
+}
+struct JoinCursor {
+    uint32_t gb;
+    int ch;
+    JoinSeg sc;
+    __amdgpu_buffer_rsrc_t rows;
+};
+
+}  // namespace
+}  // namespace pcv

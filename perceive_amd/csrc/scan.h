@@ -277,6 +277,52 @@ struct SelfJoinArgs {
     uint32_t span_blocks;           // blocks of one work item's stream
 };
 
+// Item labels (pcv_searcher_assign, _label_sums, _kmeans; DESIGN.md §4 "Item labels"): every row against K label vectors.  Rows are
+// launch rows as above, with rinv / norm exactly as selfjoin_prep_kernel leaves them (under the dot metric a participating row
+// without a cosine is then marked kRinvWild: its dot products are still defined).  The labels are a small corpus of their own: one
+// segment in the blocked f32 layout, `label_blocks` blocks (a whole number of tiles; scale 1 for the K labels, 0 behind them), so
+// that the prep and rescore arithmetic of the rows is the labels' too.
+//   w[label], mg[label] : the screening score of (row, label) is s = acc * rinv_row * w and |s - c'| <= mg, c' the canonical score
+//                         in the row's units (cosine: c; dot: c / |x|).  cosine: w = 1/|l|, mg = selfjoin_margin; dot: w = 1,
+//                         mg = selfjoin_margin * |l| rounded up.  w = 0: no score with this label is defined (or it is padding);
+//                         w = kRinvWild: |l| outside [2^-20, 2^20], every participating row lists the label
+//   lb[launch row]      : the largest s - mg seen so far over the tiles launched, a lower bound of the row's best c'; -inf at first
+//   cand / cand_s       : (launch row << 32) | label and the s it was listed with (+inf for a wild row or label)
+//   best_key / best_lab : per launch row, the order-preserving image of the largest c (0: none) and the lowest label reaching it
+struct AssignArgs {
+    float* rinv;                    // [total_blocks * 32]
+    const double* norm;             // [total_blocks * 32]
+    const float4* lab_blk;          // [label_blocks][D4][32] the labels, blocked f32
+    const float* lab_rinv;          // [label_blocks * 32]
+    const double* lab_norm;         // [label_blocks * 32]
+    uint4* lab_tile;                // [label_blocks * 32][Dp / 8] bf16 pieces in the swizzled order of the LDS tile
+    float* w;                       // [label_blocks * 32]
+    float* mg;                      // [label_blocks * 32]
+    float* lb;                      // [total_blocks * 32]
+    uint64_t* cand;                 // [cand_cap]
+    float* cand_s;                  // [cand_cap]
+    unsigned long long* cand_key;   // [n_cand] image of c per candidate (0: below the final bound or undefined)
+    unsigned long long* counters;   // [0]: candidates listed (not capped), [1]: rows whose label changed
+    unsigned long long* best_key;   // [total_blocks * 32]
+    uint32_t* best_lab;             // [total_blocks * 32]
+    int32_t* row_label;             // [total_blocks * 32] the label of every launch row (-1: none, and before the first assignment),
+                                    // kept between k-means steps: the finish step counts the rows whose entry it changes
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    int32_t* out_label;             // [rows]
+    float* out_score;               // [rows]
+    int64_t* out_ids;               // [rows]
+    long long* out_counts;          // [K]
+    long long* sums;                // [K][Dp] integer sums of pcv_searcher_label_sums
+    long long* sum_counts;          // [K] rows that went into them
+    unsigned long long cand_cap, n_cand;
+    float margin;                   // selfjoin_margin(Dp)
+    int K, metric;
+    uint32_t tile_blocks;           // blocks of one label tile (4, 2 or 1)
+    uint32_t label_blocks;
+    uint32_t tile;                  // the tile of this screen launch
+    uint32_t span_blocks;           // row blocks one screen workgroup streams (a multiple of its waves)
+};
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -287,6 +333,15 @@ __host__ __device__ static inline float key_f32(uint32_t k) {
     return __builtin_bit_cast(float, u);
 }
 constexpr uint32_t kKeyNegInf = 0x007fffffu;  // f32_key(-inf)
+// the same for a double (no finite value has key 0)
+__host__ __device__ static inline uint64_t f64_key(double d) {
+    uint64_t u = __builtin_bit_cast(uint64_t, d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__host__ __device__ static inline double key_f64(uint64_t k) {
+    uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __builtin_bit_cast(double, u);
+}
 
 // The f32 score a result carries, from the canonical f64 score c (the reference's convention: cosine (float)c; dot: the distance
 // max(0, 1 - c/D), search.rs:275-277).  The one copy of this arithmetic: the top-k outputs, the range outputs and the in-range
@@ -322,6 +377,13 @@ float selfjoin_margin(int Dp);  // certified bound on |screening score - canonic
 void launch_selfjoin_prep(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
 void launch_selfjoin_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
 void launch_selfjoin_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
+// ---- item labels (assign_kernels.hip); `p` as for the duplicate pairs, plus metric ----
+void launch_assign_labels(hipStream_t st, const ScanParams& p, const AssignArgs& a);  // lab_rinv, lab_norm -> w, mg, lab_tile
+void launch_assign_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // lb, best_*, dot marks
+void launch_assign_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // one label tile
+void launch_assign_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
+void launch_assign_finish(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // winners -> outputs
+void launch_label_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);
 void launch_merge(hipStream_t st, const pcv_hit_dev* lists, int n_shards, int B, int k, pcv_hit_dev* out,
                   int flagged = 0);

@@ -239,6 +239,7 @@ struct pcv_searcher {
     DevBuf<uint8_t> d_distinct;
     PinBuf<uint8_t> pin_distinct;
     pcv_duplicate_stats dup_stats{};  // pcv_searcher_find_duplicates (its buffers live for the call only)
+    pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -2409,6 +2410,31 @@ void search_distinct(pcv_searcher* s, const float* queries, int n_queries, const
 constexpr uint64_t kMaxJoinCandidates = (uint64_t)4 * PCV_MAX_DUPLICATE_PAIRS;
 constexpr uint32_t kJoinSpanBlocks = 256;  // blocks a work item streams against its tile (12 MB at 384-d for 196 KB of tile staging)
 
+// The segment table of a launch over `segs` as the row-against-row kernels read it (selfjoin_kernels.hip, assign_kernels.hip: blk,
+// scale, ids, positions and the launch's block numbering; no screening copy).  out0, if given, receives the output index of each
+// segment's row 0.  -> the blocks of the launch; `rows` receives the rows of the segments.
+uint32_t fill_row_table(const std::vector<SelSeg>& segs, SegDesc* tab, int64_t* out0, int64_t& rows, const char* what) {
+    uint64_t blk0 = 0;
+    rows = 0;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const Segment& g = *segs[i].g;
+        tab[i] = SegDesc{};
+        tab[i].blk = g.blk;
+        tab[i].scale = g.scale;
+        tab[i].ids = g.ids;
+        tab[i].id0 = g.id0;
+        tab[i].pos0 = g.pos0;
+        tab[i].nrows = g.nrows;
+        tab[i].nblocks = g.nblocks();
+        tab[i].blk0 = (uint32_t)blk0;
+        if (out0) out0[i] = rows;
+        blk0 += g.nblocks();
+        rows += g.nrows;
+        if (blk0 * kBlockRows > 0xffffffffull) PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: more than 2^32 rows in one call", what);
+    }
+    return (uint32_t)blk0;
+}
+
 // Three steps on the device (selfjoin_kernels.hip): norms, the bf16 screen of every tile of rows against the rows behind it, the
 // canonical f64 cosine of what the screen listed.  The pairs come down once and are ordered here.  Everything the call allocates
 // is its own and is given back when it ends: nothing of the searcher's pass state is touched.
@@ -2433,26 +2459,11 @@ void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, 
     d_p.ensure(bytes);
     ScanParams& p = *new (pin_p.p) ScanParams{};
     SegDesc* tab = reinterpret_cast<SegDesc*>(pin_p.p + off_seg);
-    uint64_t blk0 = 0;
     int64_t rows = 0;
-    for (size_t i = 0; i < segs.size(); ++i) {
-        const Segment& g = *segs[i].g;
-        tab[i] = SegDesc{};
-        tab[i].blk = g.blk;
-        tab[i].scale = g.scale;
-        tab[i].ids = g.ids;
-        tab[i].id0 = g.id0;
-        tab[i].pos0 = g.pos0;
-        tab[i].nrows = g.nrows;
-        tab[i].nblocks = g.nblocks();
-        tab[i].blk0 = (uint32_t)blk0;
-        blk0 += g.nblocks();
-        rows += g.nrows;
-        if (blk0 * kBlockRows > 0xffffffffull) PCV_FAIL(PCV_ERR_UNSUPPORTED, "find_duplicates: more than 2^32 rows in one join");
-    }
+    const uint32_t total_blocks = fill_row_table(segs, tab, nullptr, rows, "find_duplicates");
     p.seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
     p.nseg = (int)segs.size();
-    p.total_blocks = (uint32_t)blk0;
+    p.total_blocks = total_blocks;
     p.D = s->D;
     p.D4 = s->D4;
     p.metric = s->metric;
@@ -2569,6 +2580,342 @@ void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, 
     }
     *out_count = (int64_t)n;
     if (out_total) *out_total = (int64_t)total;
+}
+
+// ---- item labels (pcv_searcher_assign, _label_sums, _kmeans; DESIGN.md §4 "Item labels") ----
+constexpr uint64_t kMaxAssignCandidates = (uint64_t)1 << 28;  // (row, label) pairs the screen may list: 20 bytes each
+constexpr int64_t kMaxLabelMembers = (int64_t)1 << 30;        // |t| <= 2^32 (1 + 2^-23): the int64 sums hold 2^30 of them
+
+// Everything one call allocates, its own and given back when it ends: nothing of the searcher's pass state is touched.  The steps
+// on the device are those of assign_kernels.hip; the rows' norms are selfjoin_prep_kernel's, and so are the labels' — they are
+// uploaded as one small segment in the blocked layout.
+struct AssignJob {
+    pcv_searcher* s;
+    hipStream_t st;
+    int K, tile;
+    int64_t rows = 0;
+    PinBuf<uint8_t> pin_p, pin_l;
+    DevBuf<uint8_t> d_p, d_l;
+    ScanParams* p = nullptr;   // the rows
+    ScanParams* pl = nullptr;  // the labels
+    const ScanParams *dp = nullptr, *dpl = nullptr;
+    float4* lab_blk = nullptr;  // pinned, blocked
+    size_t bytes_l = 0;
+    DevBuf<float> d_rinv, d_lab_rinv, d_w, d_mg, d_lb, d_cand_s, d_out_score;
+    DevBuf<double> d_norm, d_lab_norm;
+    DevBuf<uint4> d_lab_tile;
+    DevBuf<uint64_t> d_cand;
+    DevBuf<unsigned long long> d_cnt, d_best_key, d_cand_key;
+    DevBuf<uint32_t> d_best_lab;
+    DevBuf<int32_t> d_row_label, d_out_label;
+    DevBuf<int64_t> d_out_ids;
+    DevBuf<long long> d_counts, d_sums;
+    AssignArgs a{};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    pcv_assign_stats stats{};
+
+    AssignJob(pcv_searcher* s_, int K_, int metric) : s(s_), st(s_->ctx->stream), K(K_), tile(mfma_pass_queries(s_->Dp)) { a.metric = metric; }
+    ~AssignJob() {
+        (void)hipStreamSynchronize(st);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    float elapsed(int from) {
+        float ms = 0.0f;
+        PCV_HIP(hipEventElapsedTime(&ms, ev[from], ev[from + 1]));
+        return ms;
+    }
+    size_t launch_rows() const { return (size_t)p->total_blocks * kBlockRows; }
+
+    // the table of the rows and their norms: all that the sums need
+    void open_rows(const std::vector<SelSeg>& segs) {
+        for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
+        const size_t off_seg = align_up(sizeof(ScanParams)), off_out0 = align_up(off_seg + segs.size() * sizeof(SegDesc));
+        const size_t bytes = off_out0 + segs.size() * sizeof(int64_t);
+        pin_p.ensure(bytes);
+        d_p.ensure(bytes);
+        p = new (pin_p.p) ScanParams{};
+        p->total_blocks = fill_row_table(segs, reinterpret_cast<SegDesc*>(pin_p.p + off_seg), reinterpret_cast<int64_t*>(pin_p.p + off_out0), rows, "assign");
+        p->seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
+        p->nseg = (int)segs.size();
+        p->D = s->D;
+        p->D4 = s->D4;
+        p->metric = a.metric;
+        dp = reinterpret_cast<const ScanParams*>(d_p.p);
+        a.seg_out0 = reinterpret_cast<const int64_t*>(d_p.p + off_out0);
+        a.K = K;
+
+        const size_t nr = launch_rows();
+        d_rinv.ensure(nr);
+        d_norm.ensure(nr);
+        d_row_label.ensure(nr);
+        a.rinv = d_rinv.p;
+        a.norm = d_norm.p;
+        a.row_label = d_row_label.p;
+        SelfJoinArgs prep{};
+        prep.rinv = d_rinv.p;
+        prep.norm = d_norm.p;
+        PCV_HIP(hipMemcpyAsync(d_p.p, pin_p.p, bytes, hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemsetAsync(d_row_label.p, 0xff, nr * sizeof(int32_t), st));  // (-1: no label yet)
+        PCV_HIP(hipEventRecord(ev[0], st));
+        launch_selfjoin_prep(st, *p, dp, prep);
+        PCV_HIP(hipEventRecord(ev[1], st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        stats.rows = rows;
+        stats.prep_ms = elapsed(0);
+    }
+
+    // ... and what an assignment needs on top: the labels' table (a whole number of tiles), the per-row state, the candidate list
+    // and the outputs
+    void open_labels() {
+        a.tile_blocks = (uint32_t)tile / kBlockRows;
+        const uint32_t tiles = ((uint32_t)K + (uint32_t)tile - 1) / (uint32_t)tile;
+        a.label_blocks = tiles * a.tile_blocks;
+        const size_t slots = (size_t)a.label_blocks * kBlockRows;
+        // [ScanParams][SegDesc][scale][blocked rows]
+        const size_t off_lseg = align_up(sizeof(ScanParams)), off_scale = align_up(off_lseg + sizeof(SegDesc));
+        const size_t off_blk = align_up(off_scale + slots * sizeof(float));
+        bytes_l = off_blk + slots * s->Dp * sizeof(float);
+        pin_l.ensure(bytes_l);
+        d_l.ensure(bytes_l);
+        std::memset(pin_l.p, 0, bytes_l);
+        pl = new (pin_l.p) ScanParams{};
+        SegDesc* lt = new (pin_l.p + off_lseg) SegDesc{};
+        float* lscale = reinterpret_cast<float*>(pin_l.p + off_scale);
+        for (int j = 0; j < K; ++j) lscale[j] = 1.0f;
+        lab_blk = reinterpret_cast<float4*>(pin_l.p + off_blk);
+        lt->blk = reinterpret_cast<const float4*>(d_l.p + off_blk);
+        lt->scale = reinterpret_cast<const float*>(d_l.p + off_scale);
+        lt->nrows = (uint32_t)K;
+        lt->nblocks = a.label_blocks;
+        pl->seg = reinterpret_cast<const SegDesc*>(d_l.p + off_lseg);
+        pl->nseg = 1;
+        pl->total_blocks = a.label_blocks;
+        pl->D = s->D;
+        pl->D4 = s->D4;
+        dpl = reinterpret_cast<const ScanParams*>(d_l.p);
+        a.lab_blk = lt->blk;
+
+        const size_t nr = launch_rows();
+        d_lb.ensure(nr);
+        d_best_key.ensure(nr);
+        d_best_lab.ensure(nr);
+        d_lab_rinv.ensure(slots);
+        d_lab_norm.ensure(slots);
+        d_w.ensure(slots);
+        d_mg.ensure(slots);
+        d_lab_tile.ensure(slots * (size_t)(s->Dp / 8));
+        d_cnt.ensure(2);
+        d_out_label.ensure((size_t)rows);
+        d_out_score.ensure((size_t)rows);
+        d_out_ids.ensure((size_t)rows);
+        d_counts.ensure((size_t)K);
+        a.cand_cap = std::min<uint64_t>(kMaxAssignCandidates, std::max<uint64_t>(65536, 4 * (uint64_t)rows));
+        d_cand.ensure(a.cand_cap);
+        d_cand_s.ensure(a.cand_cap);
+        a.lab_rinv = d_lab_rinv.p;
+        a.lab_norm = d_lab_norm.p;
+        a.lab_tile = d_lab_tile.p;
+        a.w = d_w.p;
+        a.mg = d_mg.p;
+        a.lb = d_lb.p;
+        a.cand = d_cand.p;
+        a.cand_s = d_cand_s.p;
+        a.counters = d_cnt.p;
+        a.best_key = d_best_key.p;
+        a.best_lab = d_best_lab.p;
+        a.out_label = d_out_label.p;
+        a.out_score = d_out_score.p;
+        a.out_ids = d_out_ids.p;
+        a.out_counts = d_counts.p;
+        a.margin = selfjoin_margin(s->Dp);
+        // a workgroup stages a whole tile for its span: spans of two per CU, and not so short that the staging shows
+        const uint32_t per = (p->total_blocks + 2 * (uint32_t)s->ctx->num_cus - 1) / (2 * (uint32_t)std::max(1, s->ctx->num_cus));
+        a.span_blocks = std::max<uint32_t>(32, (per + 7) / 8 * 8);
+        stats.tile_labels = tile;
+        stats.label_tiles = (int32_t)tiles;
+    }
+
+    void screen_all() {
+        for (uint32_t t = 0; t < (uint32_t)stats.label_tiles; ++t) {
+            a.tile = t;
+            launch_assign_screen(st, *p, dp, a);
+        }
+    }
+
+    // one assignment with labels[K][D] (host): row_label, the outputs on the device, counters[1] = rows whose label changed
+    uint64_t assign(const float* labels) {
+        const int D = s->D, D4 = s->D4;
+        for (int j = 0; j < K; ++j) {
+            float* dst = reinterpret_cast<float*>(lab_blk + (size_t)(j >> 5) * D4 * 32 + (j & 31));  // piece f of label j: dst + f * 128 floats
+            for (int d = 0; d < D; ++d) dst[(size_t)(d >> 2) * 128 + (d & 3)] = labels[(size_t)j * D + d];
+        }
+        unsigned long long counts[2] = {0, 0};
+        SelfJoinArgs prep{};
+        prep.rinv = d_lab_rinv.p;
+        prep.norm = d_lab_norm.p;
+        PCV_HIP(hipMemcpyAsync(d_l.p, pin_l.p, bytes_l, hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_counts.p, 0, (size_t)K * sizeof(long long), st));
+        PCV_HIP(hipEventRecord(ev[0], st));
+        launch_selfjoin_prep(st, *pl, dpl, prep);
+        launch_assign_labels(st, *p, a);
+        launch_assign_begin(st, *p, dp, a);
+        PCV_HIP(hipEventRecord(ev[1], st));
+        screen_all();
+        PCV_HIP(hipEventRecord(ev[2], st));
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        stats.prep_ms += elapsed(0);
+        stats.screen_ms += elapsed(1);
+        uint64_t n_cand = counts[0];
+        stats.candidates = (int64_t)n_cand;
+        if (n_cand > kMaxAssignCandidates)
+            PCV_FAIL(PCV_ERR_UNSUPPORTED, "assign: the screen lists %llu (row, label) candidates, more than %llu: fewer or less alike labels, or fewer rows",
+                     (unsigned long long)n_cand, (unsigned long long)kMaxAssignCandidates);
+        if (n_cand > a.cand_cap) {  // once more, with the room the count asks for; the bounds the first run left only shorten the list
+            a.cand_cap = n_cand;
+            d_cand.ensure(a.cand_cap);
+            d_cand_s.ensure(a.cand_cap);
+            a.cand = d_cand.p;
+            a.cand_s = d_cand_s.p;
+            PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+            PCV_HIP(hipEventRecord(ev[1], st));
+            screen_all();
+            PCV_HIP(hipEventRecord(ev[2], st));
+            PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+            PCV_HIP(hipStreamSynchronize(st));
+            PCV_HIP(hipGetLastError());
+            PCV_REQUIRE(counts[0] <= n_cand, "assign: the repeated screen listed %llu candidates, the first %llu", counts[0], (unsigned long long)n_cand);
+            n_cand = counts[0];
+            stats.reruns += 1;
+            stats.screen_ms += elapsed(1);
+        }
+        a.n_cand = n_cand;
+        d_cand_key.ensure((size_t)std::max<uint64_t>(1, n_cand));
+        a.cand_key = d_cand_key.p;
+        PCV_HIP(hipEventRecord(ev[2], st));
+        launch_assign_rescore(st, *p, dp, a);
+        launch_assign_finish(st, *p, dp, a);
+        PCV_HIP(hipEventRecord(ev[3], st));
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        stats.rescore_ms += elapsed(2);
+        return counts[1];
+    }
+
+    // the integer sums of the labels in row_label -> host [K][Dp] and the members per label
+    void sums(std::vector<long long>& S, std::vector<long long>& members) {
+        const size_t n = (size_t)K * s->Dp;
+        d_sums.ensure(n + (size_t)K);
+        a.sums = d_sums.p;
+        a.sum_counts = d_sums.p + n;
+        S.resize(n);
+        members.resize((size_t)K);
+        PCV_HIP(hipMemsetAsync(d_sums.p, 0, (n + (size_t)K) * sizeof(long long), st));
+        launch_label_sums(st, *p, dp, a);
+        PCV_HIP(hipMemcpyAsync(S.data(), d_sums.p, n * sizeof(long long), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipMemcpyAsync(members.data(), d_sums.p + n, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+    }
+
+    void download(int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts) {
+        const size_t n = (size_t)rows;
+        PCV_HIP(hipMemcpy(out_label, d_out_label.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (out_score) PCV_HIP(hipMemcpy(out_score, d_out_score.p, n * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (out_counts) PCV_HIP(hipMemcpy(out_counts, d_counts.p, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+};
+
+int64_t selected_rows(const std::vector<SelSeg>& segs) {
+    int64_t n = 0;
+    for (const SelSeg& g : segs) n += g.g->nrows;
+    return n;
+}
+
+void check_labels(pcv_searcher* s, const float* labels, int K, const char* what) {
+    for (size_t i = 0, e = (size_t)K * s->D; i < e; ++i)
+        PCV_REQUIRE(std::isfinite(labels[i]), "%s: label %d has a NaN or Inf at feature %d", what, (int)(i / s->D), (int)(i % s->D));
+}
+
+// assign (max_iters = 0, the searcher's metric, no centroids) and k-means (cosine); the caller has checked the arguments
+void assign_or_kmeans(pcv_searcher* s, const char* what, const float* init, int K, int max_iters, int metric, const int64_t* source_ids, int n_sources,
+                      int64_t capacity, float* out_centroids, int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts,
+                      int32_t* out_iters, int64_t* out_moved, int64_t* out_n) {
+    PCV_REQUIRE(!s->dirty, "%s: rows were added or cleared without pcv_searcher_finalize", what);
+    check_labels(s, init, K, what);
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_n = n;
+    if (out_iters) *out_iters = 0;
+    if (out_label == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "%s: the outputs have room for %lld rows, the selected sources have %lld", what, (long long)capacity, (long long)n);
+    s->assign_stats = pcv_assign_stats{};
+    if (mfma_pass_queries(s->Dp) == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: a bf16 tile of %d-d labels does not fit the LDS", what, s->D);
+    const size_t KD = (size_t)K * s->D;
+    if (out_centroids) std::memcpy(out_centroids, init, KD * sizeof(float));
+    if (out_counts) std::fill(out_counts, out_counts + K, (int64_t)0);
+    if (out_moved) out_moved[0] = 0;
+    if (n == 0) return;
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    AssignJob job(s, K, metric);
+    job.open_rows(segs);
+    job.open_labels();
+    const auto keep_stats = at_exit([&] { s->assign_stats = job.stats; });
+    std::vector<float> cent(init, init + KD);
+    std::vector<long long> S, members;
+    int updates = 0;
+    while (true) {
+        const uint64_t moved = job.assign(cent.data());
+        if (out_moved) out_moved[updates] = (int64_t)moved;
+        if (moved == 0 || updates == max_iters) break;
+        job.sums(S, members);
+        for (int j = 0; j < K; ++j) {
+            if (members[(size_t)j] > kMaxLabelMembers)
+                PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: label %d has %lld members, more than 2^30", what, j, members[(size_t)j]);
+            if (members[(size_t)j] == 0) continue;  // (keeps its vector)
+            for (int d = 0; d < s->D; ++d) cent[(size_t)j * s->D + d] = (float)((double)S[(size_t)j * s->Dp + d] * 0x1p-32);
+        }
+        ++updates;
+    }
+    if (out_iters) *out_iters = updates;
+    if (out_centroids) std::memcpy(out_centroids, cent.data(), KD * sizeof(float));
+    job.download(out_label, out_score, out_ids, out_counts);
+}
+
+void label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const int32_t* labels, int64_t n, int K, int64_t* out_sums,
+                int64_t* out_counts) {
+    PCV_REQUIRE(!s->dirty, "label_sums: rows were added or cleared without pcv_searcher_finalize");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    PCV_REQUIRE(n == selected_rows(segs), "label_sums: %lld labels for %lld rows of the selected sources", (long long)n, (long long)selected_rows(segs));
+    for (int64_t i = 0; i < n; ++i) PCV_REQUIRE(labels[i] < K, "label_sums: row %lld has label %d of %d", (long long)i, labels[i], K);
+    std::fill(out_sums, out_sums + (size_t)K * s->D, (int64_t)0);
+    if (out_counts) std::fill(out_counts, out_counts + K, (int64_t)0);
+    if (n == 0) return;
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    AssignJob job(s, K, PCV_METRIC_COSINE);
+    job.open_rows(segs);  // (the sums need no label tile: any dimension)
+    std::vector<int32_t> by_row(job.launch_rows(), -1);
+    size_t lr = 0;
+    int64_t at = 0;
+    for (const SelSeg& g : segs) {
+        for (uint32_t r = 0; r < g.g->nrows; ++r) by_row[lr + r] = labels[at + r] < 0 ? -1 : labels[at + r];
+        lr += (size_t)g.g->nblocks() * kBlockRows;
+        at += g.g->nrows;
+    }
+    PCV_HIP(hipMemcpy(job.d_row_label.p, by_row.data(), by_row.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    std::vector<long long> S, members;
+    job.sums(S, members);
+    for (int j = 0; j < K; ++j) {
+        if (members[(size_t)j] > kMaxLabelMembers) PCV_FAIL(PCV_ERR_UNSUPPORTED, "label_sums: label %d has %lld members, more than 2^30", j, members[(size_t)j]);
+        for (int d = 0; d < s->D; ++d) out_sums[(size_t)j * s->D + d] = (int64_t)S[(size_t)j * s->Dp + d];
+        if (out_counts) out_counts[j] = (int64_t)members[(size_t)j];
+    }
 }
 
 void sync_view(pcv_searcher* v);
@@ -3596,6 +3943,60 @@ pcv_status pcv_searcher_last_duplicate_stats(pcv_searcher* s, pcv_duplicate_stat
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_duplicate_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->dup_stats;
+    });
+}
+
+pcv_status pcv_searcher_assign(pcv_searcher* s, const float* labels, int n_labels, const int64_t* source_ids, int n_sources, int64_t capacity,
+                               int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(labels != nullptr && out_n != nullptr, "assign: labels or out_n is NULL");
+        PCV_REQUIRE(n_labels >= 1 && n_labels <= (int)PCV_MAX_LABELS, "assign: %d labels, outside [1,%d]", n_labels, (int)PCV_MAX_LABELS);
+        PCV_REQUIRE(capacity >= 0 && (out_label != nullptr || capacity == 0), "assign: out_label is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "assign: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "assign: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        assign_or_kmeans(s, "assign", labels, n_labels, 0, s->metric, source_ids, n_sources, capacity, nullptr, out_label, out_score, out_ids, out_counts,
+                         nullptr, nullptr, out_n);
+    });
+}
+
+pcv_status pcv_searcher_kmeans(pcv_searcher* s, const float* init, int n_labels, int max_iters, const int64_t* source_ids, int n_sources,
+                               int64_t capacity, float* out_centroids, int32_t* out_label, float* out_score, int64_t* out_ids,
+                               int64_t* out_counts, int32_t* out_iters, int64_t* out_moved, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(init != nullptr && out_n != nullptr, "kmeans: init or out_n is NULL");
+        PCV_REQUIRE(n_labels >= 1 && n_labels <= (int)PCV_MAX_LABELS, "kmeans: %d centroids, outside [1,%d]", n_labels, (int)PCV_MAX_LABELS);
+        PCV_REQUIRE(max_iters >= 0, "kmeans: max_iters %d is negative", max_iters);
+        PCV_REQUIRE(capacity >= 0 && (out_label != nullptr || capacity == 0), "kmeans: out_label is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(out_centroids != nullptr || (out_label == nullptr && capacity == 0), "kmeans: out_centroids is NULL");
+        PCV_REQUIRE(s != nullptr, "kmeans: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "kmeans: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        assign_or_kmeans(s, "kmeans", init, n_labels, max_iters, PCV_METRIC_COSINE, source_ids, n_sources, capacity, out_centroids, out_label, out_score,
+                         out_ids, out_counts, out_iters, out_moved, out_n);
+    });
+}
+
+pcv_status pcv_searcher_label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const int32_t* labels, int64_t n, int n_labels,
+                                   int64_t* out_sums, int64_t* out_counts) {
+    return guarded([&] {
+        PCV_REQUIRE(out_sums != nullptr && n >= 0 && (labels != nullptr || n == 0), "label_sums: labels or out_sums is NULL");
+        PCV_REQUIRE(n_labels >= 1 && n_labels <= (int)PCV_MAX_LABELS, "label_sums: %d labels, outside [1,%d]", n_labels, (int)PCV_MAX_LABELS);
+        PCV_REQUIRE(s != nullptr, "label_sums: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "label_sums: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        label_sums(s, source_ids, n_sources, labels, n, n_labels, out_sums, out_counts);
+    });
+}
+
+pcv_status pcv_searcher_last_assign_stats(pcv_searcher* s, pcv_assign_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_assign_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->assign_stats;
     });
 }
 

@@ -14,42 +14,13 @@
 //   3. selfjoin_rescore_kernel  one thread per candidate: the canonical f64 cosine (pair_sums and finish_score, device_access.h —
 //                               the arithmetic of distinct_select_kernel), kept iff c >= threshold.
 #include "device_access.h"
+#include "launch_rows.h"
 #include "scan.h"
 
 namespace pcv {
 namespace {
 
 constexpr int kJoinWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
-
-__device__ __forceinline__ unsigned long long g_atomic_add64(unsigned long long* p, unsigned long long v) {
-    return __hip_atomic_fetch_add((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// last table entry with blk0 <= gb
-__device__ __forceinline__ int find_seg(const ScanParams& p, uint32_t gb, int from = 0) {
-    int lo = from, hi = p.nseg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (gld(&p.seg[mid].blk0) <= gb)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-// Launch row `lr` (scan.h): its segment, its row there and where its first piece is.
-struct RowRef {
-    const SegDesc* sg;
-    uint32_t row;
-    const float4* x;
-};
-__device__ __forceinline__ RowRef row_ref(const ScanParams& p, uint32_t lr) {
-    const uint32_t gb = lr >> 5;
-    const SegDesc* sg = &p.seg[find_seg(p, gb)];
-    const uint32_t lb = gb - gld(&sg->blk0);
-    return {sg, lb * 32 + (lr & 31), gld(&sg->blk) + (size_t)lb * p.D4 * 32 + (lr & 31)};
-}
 
 __global__ __launch_bounds__(256) void selfjoin_prep_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
     const ScanParams& p = *pp;
@@ -69,27 +40,6 @@ __global__ __launch_bounds__(256) void selfjoin_prep_kernel(const ScanParams* __
     gst(&a.rinv[i], rinv);
     gst(&a.norm[i], n);
 }
-
-// The segment a wave's stream is in (all of it wave-uniform, in scalar registers: scan_kernels.hip, seek_seg).
-struct JoinSeg {
-    int si = -1;
-    uint32_t begin = 0, end = 0;
-    const float4* blk = nullptr;
-};
-__device__ __forceinline__ void join_seek(const ScanParams& p, JoinSeg& c, uint32_t gb) {
-    if (gb < c.end) return;
-    const int lo = find_seg(p, gb, c.si + 1);
-    c.si = lo;
-    c.begin = uniform(gld(&p.seg[lo].blk0));
-    c.end = c.begin + uniform(gld(&p.seg[lo].nblocks));
-    c.blk = uniform_ptr(gld(&p.seg[lo].blk));
-}
-struct JoinCursor {
-    uint32_t gb;
-    int ch;
-    JoinSeg sc;
-    __amdgpu_buffer_rsrc_t rows;
-};
 
 // grid: x = tile (tile_blocks = NT consecutive blocks), y = span: the blocks [tile's first + y * span_blocks, + span_blocks) of the
 // launch, cut at its end.  A (tile, span) that starts behind the end has nothing to do.  Consecutive workgroups stream nearly the

@@ -446,6 +446,90 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_last_duplicate_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.DuplicateStats._fields_}
 
+    # ---- item labels (pcv_searcher_assign / _label_sums / _kmeans) ----------------------------------
+    # The transpose of a search: the best of K vectors for every row, and spherical k-means built on it.
+    def _assign_rows(self, src, nsrc):
+        n = C.c_int64()
+        one = np.zeros((1, self.dim), dtype=np.float32)
+        _ffi.check(_ffi.lib().pcv_searcher_assign(self._handle, _ffi.f32p(one), 1, src, nsrc, 0, None, None, None, None, C.byref(n)))
+        return n.value
+
+    def assign(self, sources, labels):
+        """The best of the K vectors `labels` [K, dim] for every row of `sources`, exact (the canonical score with the label in the
+        query's place; ties: the lower label) -> (label [n] int32, score [n] f32 as search reports it, ids [n] int64, counts [K]
+        int64), by global position.  A row no search could return has label -1 and a NaN score.  A view assigns its own rows."""
+        lab = np.ascontiguousarray(labels, dtype=np.float32)
+        if lab.ndim != 2 or lab.shape[1] != self.dim:
+            raise ValueError(f"labels must be [K, {self.dim}]")
+        K = lab.shape[0]
+        src, nsrc, _keep = _source_filter(sources)
+        n = self._assign_rows(src, nsrc)
+        label = np.empty(max(n, 1), dtype=np.int32)
+        score = np.empty(max(n, 1), dtype=np.float32)
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        counts = np.zeros(max(K, 1), dtype=np.int64)
+        got = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_assign(
+                self._handle, _ffi.f32p(lab), K, src, nsrc, max(n, 1), _ffi.i32p(label), _ffi.f32p(score), _ffi.i64p(ids), _ffi.i64p(counts),
+                C.byref(got),
+            )
+        )
+        return label[:n], score[:n], ids[:n], counts[:K]
+
+    def label_sums(self, sources, labels, k):
+        """sums [k, dim] int64 of rint(x * rinv * 2^32) over the rows of each label (labels [n] int32 by position as assign returns
+        them; negative: none) and the members [k] int64 that went into them: the same bits in any order of addition."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        sums = np.zeros((int(k), self.dim), dtype=np.int64)
+        members = np.zeros(int(k), dtype=np.int64)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_label_sums(
+                self._handle, src, nsrc, _ffi.i32p(lab) if lab.size else None, lab.size, int(k), _ffi.i64p(sums), _ffi.i64p(members)
+            )
+        )
+        return sums, members
+
+    def kmeans(self, sources, k, init, max_iters=20):
+        """Spherical k-means by canonical cosine (both metrics), reproducible bit for bit.  init: [k, dim] vectors, or k item ids
+        (their stored embeddings, through like_queries).  -> (centroids [k, dim] f32 of the last assignment, label [n] int32,
+        score [n] f32, ids [n] int64, counts [k] int64, iterations, moved [iterations + 1] int64: rows that changed their label in
+        each assignment).  It stops after an assignment that moved no row, or after max_iters updates."""
+        init = np.asarray(init)
+        if init.ndim == 1:
+            if init.size != int(k):
+                raise ValueError(f"{init.size} item ids for k = {k}")
+            vec, found, _members = self.like_queries([[int(i)] for i in init])
+            if not found.all():
+                raise ValueError("kmeans: an init item id that no row carries")
+            init = vec
+        init = np.ascontiguousarray(init, dtype=np.float32)
+        if init.shape != (int(k), self.dim):
+            raise ValueError(f"init must be [{k}, {self.dim}] vectors or {k} item ids")
+        K, iters = int(k), int(max_iters)
+        src, nsrc, _keep = _source_filter(sources)
+        n = self._assign_rows(src, nsrc)
+        cent = np.empty((K, self.dim), dtype=np.float32)
+        label = np.empty(max(n, 1), dtype=np.int32)
+        score = np.empty(max(n, 1), dtype=np.float32)
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        counts = np.zeros(K, dtype=np.int64)
+        moved = np.zeros(max(iters, 0) + 1, dtype=np.int64)
+        done, got = C.c_int32(), C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_kmeans(
+                self._handle, _ffi.f32p(init), K, iters, src, nsrc, max(n, 1), _ffi.f32p(cent), _ffi.i32p(label), _ffi.f32p(score),
+                _ffi.i64p(ids), _ffi.i64p(counts), C.byref(done), _ffi.i64p(moved), C.byref(got),
+            )
+        )
+        return cent, label[:n], score[:n], ids[:n], counts, done.value, moved[: done.value + 1].copy()
+
+    def last_assign_stats(self):
+        st = _ffi.AssignStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_assign_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.AssignStats._fields_}
+
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):
         _ffi.check(_ffi.lib().pcv_searcher_set_kernel(self._handle, _KERNELS[kernel]))

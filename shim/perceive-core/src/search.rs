@@ -426,6 +426,81 @@ impl Searcher {
         ((0..count as usize).map(|i| (id_a[i], id_b[i], scores[i])).collect(), total)
     }
 
+    /// Item labels (`pcv_searcher_assign`): the exact best of the `k` vectors `labels` (`k * dim` values) for every item of
+    /// `sources`, by global position.  Returns (label, score as a search reports it, item id) per item — label -1 and a NaN
+    /// score for an item no search could return — and the number of items per label.
+    pub fn assign(&self, sources: &[i64], labels: &[f32], k: usize) -> (Vec<(i32, f32, i64)>, Vec<i64>) {
+        let (_, rows, counts, _, _) = self.assign_or_kmeans(sources, labels, k, None);
+        (rows, counts)
+    }
+
+    /// Spherical k-means by cosine (`pcv_searcher_kmeans`) from the `k` vectors `init`, at most `max_iters` updates; the same
+    /// input gives the same bits.  Returns the centroids of the last assignment, that assignment as in `assign`, its counts,
+    /// the updates made and the items that changed their label in each assignment.
+    pub fn kmeans(&self, sources: &[i64], init: &[f32], k: usize, max_iters: usize) -> (Vec<f32>, Vec<(i32, f32, i64)>, Vec<i64>, usize, Vec<i64>) {
+        self.assign_or_kmeans(sources, init, k, Some(max_iters))
+    }
+
+    fn assign_or_kmeans(&self, sources: &[i64], vectors: &[f32], k: usize, max_iters: Option<usize>) -> (Vec<f32>, Vec<(i32, f32, i64)>, Vec<i64>, usize, Vec<i64>) {
+        let mut counts = vec![0i64; k];
+        if self.handle.is_null() || k == 0 || sources.is_empty() {
+            return (vectors.to_vec(), Vec::new(), counts, 0, vec![0]);
+        }
+        let iters = max_iters.unwrap_or(0) as i32;
+        let mut n: i64 = 0;
+        let null_i32 = std::ptr::null_mut::<i32>();
+        let null_f32 = std::ptr::null_mut::<f32>();
+        let null_i64 = std::ptr::null_mut::<i64>();
+        hip::check(unsafe {
+            ffi::pcv_searcher_assign(self.handle, vectors.as_ptr(), k as i32, sources.as_ptr(), sources.len() as i32, 0, null_i32, null_f32, null_i64, null_i64, &mut n)
+        })
+        .expect("assign failed");
+        let room = (n.max(1)) as usize;
+        let mut label = vec![-1i32; room];
+        let mut score = vec![f32::NAN; room];
+        let mut ids = vec![-1i64; room];
+        let mut centroids = vectors.to_vec();
+        let mut moved = vec![0i64; iters as usize + 1];
+        let mut done: i32 = 0;
+        hip::check(unsafe {
+            match max_iters {
+                Some(_) => ffi::pcv_searcher_kmeans(
+                    self.handle,
+                    vectors.as_ptr(),
+                    k as i32,
+                    iters,
+                    sources.as_ptr(),
+                    sources.len() as i32,
+                    room as i64,
+                    centroids.as_mut_ptr(),
+                    label.as_mut_ptr(),
+                    score.as_mut_ptr(),
+                    ids.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                    &mut done,
+                    moved.as_mut_ptr(),
+                    &mut n,
+                ),
+                None => ffi::pcv_searcher_assign(
+                    self.handle,
+                    vectors.as_ptr(),
+                    k as i32,
+                    sources.as_ptr(),
+                    sources.len() as i32,
+                    room as i64,
+                    label.as_mut_ptr(),
+                    score.as_mut_ptr(),
+                    ids.as_mut_ptr(),
+                    counts.as_mut_ptr(),
+                    &mut n,
+                ),
+            }
+        })
+        .expect("assign / kmeans failed");
+        moved.truncate(done as usize + 1);
+        ((centroids), (0..n as usize).map(|i| (label[i], score[i], ids[i])).collect(), counts, done as usize, moved)
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
