@@ -226,6 +226,35 @@ inline KMeansResult kmeans_handle(pcv_searcher* h, const std::vector<int64_t>& s
     return r;
 }
 
+// Searcher::neighbors / SearcherView::neighbors (pcv_searcher_neighbors): for every item of `sources`, by global position, its
+// exact k best other items by cosine, best first; an item no search could return has none.
+struct NeighborTable {
+    size_t k = 0;
+    std::vector<int64_t> ids;           // [n]
+    std::vector<int64_t> neighbor_ids;  // [n][k], unused slots -1
+    std::vector<float> scores;          // [n][k], unused slots NaN
+    std::vector<int32_t> counts;        // [n]
+};
+inline NeighborTable neighbors_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t k) {
+    NeighborTable r;
+    r.k = k;
+    if (sources.empty() || k == 0) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    check(pcv_searcher_neighbors(h, sources.data(), (int)sources.size(), (int)k, 0, nullptr, nullptr, nullptr, nullptr, &n));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.ids.resize(room);
+    r.neighbor_ids.resize(room * k);
+    r.scores.resize(room * k);
+    r.counts.resize(room);
+    check(pcv_searcher_neighbors(h, sources.data(), (int)sources.size(), (int)k, (int64_t)room, r.ids.data(), r.neighbor_ids.data(), r.scores.data(),
+                                 r.counts.data(), &n));
+    r.ids.resize((size_t)n);
+    r.neighbor_ids.resize((size_t)n * k);
+    r.scores.resize((size_t)n * k);
+    r.counts.resize((size_t)n);
+    return r;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -286,6 +315,13 @@ public:
     pcv_assign_stats last_assign_stats() const {
         pcv_assign_stats st;
         check(pcv_searcher_last_assign_stats(h_, &st));
+        return st;
+    }
+    // the k nearest other items of every item of the view (neighbors_handle)
+    NeighborTable neighbors(const std::vector<int64_t>& sources, size_t k) const { return neighbors_handle(h_, sources, k); }
+    pcv_neighbor_stats last_neighbor_stats() const {
+        pcv_neighbor_stats st;
+        check(pcv_searcher_last_neighbor_stats(h_, &st));
         return st;
     }
     // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
@@ -393,6 +429,13 @@ public:
     pcv_assign_stats last_assign_stats() const {
         pcv_assign_stats st;
         check(pcv_searcher_last_assign_stats(h_, &st));
+        return st;
+    }
+    // the k nearest other items of every item, found once on the device (neighbors_handle)
+    NeighborTable neighbors(const std::vector<int64_t>& sources, size_t k) const { return neighbors_handle(h_, sources, k); }
+    pcv_neighbor_stats last_neighbor_stats() const {
+        pcv_neighbor_stats st;
+        check(pcv_searcher_last_neighbor_stats(h_, &st));
         return st;
     }
     // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the

@@ -537,6 +537,54 @@ typedef struct pcv_assign_stats {
 } pcv_assign_stats;
 pcv_status pcv_searcher_last_assign_stats(pcv_searcher* s, pcv_assign_stats* out);
 
+/* Item neighbours: the k-nearest-neighbour table of the corpus — for EVERY stored item its exact k best other items, computed where
+ * the rows live (a "related items" panel without a search at view time, the distance to the k-th neighbour as an outlier score,
+ * label propagation, density and graph clustering, a 2-D map of a library).
+ * The rows concerned are those of the selected segments in global position order, n of them, as in pcv_searcher_assign (hidden and
+ * unsearchable rows included: they keep their place); source_ids == NULL means all sources, an empty list selects nothing (n = 0); a
+ * view lists its own rows.  A row TAKES PART under exactly the rules of pcv_searcher_find_duplicates: a pcv_searcher_search with the
+ * same filter could return it (scale != 0, not hidden) and it has a cosine (canonical |x|^2 in [2^-126, inf)).  For a participating
+ * row r and every other participating row p (another position; the same item id is a neighbour like any other),
+ * c(r, p) = the canonical cosine of the two stored f32 rows — f64, products exact, sums in feature order — for BOTH
+ * metrics.  The neighbours of r are the k partners with the largest c, ties to the lower global position, ordered by (c descending,
+ * position ascending).
+ *   k                 1 .. PCV_MAX_NEIGHBORS
+ *   capacity          rows the outputs have room for; capacity < n gives PCV_ERR_INVALID (out_rows is set)
+ *   out_ids           [capacity] the item id of every position
+ *   out_neighbor_ids  [capacity][k] the neighbours' item ids, best first; unused slots -1
+ *   out_scores        [capacity][k] (float)c; unused slots NaN
+ *   out_counts        [capacity] int32: min(k, participating rows - 1); 0 for a row that takes no part (it is nobody's neighbour)
+ *   out_rows          n.  With all four arrays NULL and capacity == 0 the call only reports n and does no device work
+ * A NULL out_rows or searcher, k out of range, a negative capacity or a NULL array with capacity != 0 give PCV_ERR_INVALID before the
+ * handle is looked at; a searcher with pending rows fails as in pcv_searcher_search.  A dimension whose bf16 row tile does not fit the
+ * LDS of a CU (above 2496) gives PCV_ERR_UNSUPPORTED, and so does a call whose screen lists more than 2^30 (row, partner) candidates
+ * (more than a thousand near-identical rows per row across a million), before the larger list is allocated.  The result does not
+ * depend on which screening copies exist, nor on pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity: the call reads the
+ * f32 rows and touches no pass state (DESIGN.md §4 "Item neighbours").  Everything it allocates on the device is given back when it
+ * returns.  Not in scope: a sharded searcher (pcv_searcher_set_shard_offset != 0 or a pcv_comm: a row's neighbours lie in every
+ * shard) — PCV_ERR_INVALID — and device-resident output. */
+enum { PCV_MAX_NEIGHBORS = 64 };
+pcv_status pcv_searcher_neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int64_t capacity, int64_t* out_ids,
+                                  int64_t* out_neighbor_ids, float* out_scores, int32_t* out_counts, int64_t* out_rows);
+
+/* Counters of the most recent pcv_searcher_neighbors on this handle. */
+typedef struct pcv_neighbor_stats {
+    int64_t rows;           /* rows of the selected segments (those taking no part included)                  */
+    int64_t candidates;     /* directed (row, partner) pairs the bf16 list pass left and the f64 step scored  */
+    int64_t listed;         /* neighbours written (the sum of out_counts)                                     */
+    int32_t k;
+    int32_t tile_rows;      /* rows of the LDS tile the screen kernel staged                                  */
+    int32_t sample_stride;  /* the bound pass streamed every sample_stride-th block of partners               */
+    int32_t spans;          /* disjoint partner sets whose maxima bound a row's k-th best score               */
+    int32_t reruns;         /* list passes repeated because the candidate list was short                      */
+    float prep_ms;          /* hipEvent times of the steps (a repeated list pass included in screen_ms)       */
+    float bound_ms;
+    float screen_ms;
+    float rescore_ms;
+    float select_ms;
+} pcv_neighbor_stats;
+pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats* out);
+
 /* Groups of duplicates from a list of pairs (host only: needs no context and no GPU).  out_ids receives the distinct ids occurring
  * in the n_pairs pairs, ascending, and out_group[i] the smallest id of the connected component of out_ids[i]: an item is a candidate
  * for removal iff out_group[i] != out_ids[i].  out_n_ids receives the number of distinct ids; capacity < that gives PCV_ERR_INVALID

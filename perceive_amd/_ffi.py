@@ -76,6 +76,24 @@ class AssignStats(C.Structure):
     ]
 
 
+class NeighborStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("candidates", C.c_int64),
+        ("listed", C.c_int64),
+        ("k", C.c_int32),
+        ("tile_rows", C.c_int32),
+        ("sample_stride", C.c_int32),
+        ("spans", C.c_int32),
+        ("reruns", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("bound_ms", C.c_float),
+        ("screen_ms", C.c_float),
+        ("rescore_ms", C.c_float),
+        ("select_ms", C.c_float),
+    ]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32),
@@ -172,6 +190,8 @@ SYMBOLS = {
     "pcv_searcher_kmeans": (C.c_int, [_P, _F32P, C.c_int, C.c_int, _I64P, C.c_int, C.c_int64, _F32P, _INTP, _F32P, _I64P, _I64P,
                                       C.POINTER(C.c_int32), _I64P, C.POINTER(C.c_int64)]),
     "pcv_searcher_last_assign_stats": (C.c_int, [_P, C.POINTER(AssignStats)]),
+    "pcv_searcher_neighbors": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int64, _I64P, _I64P, _F32P, _INTP, C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_neighbor_stats": (C.c_int, [_P, C.POINTER(NeighborStats)]),
     "pcv_duplicate_groups": (C.c_int, [_I64P, _I64P, C.c_int64, _I64P, _I64P, C.c_int64, C.POINTER(C.c_int64)]),
     "pcv_searcher_like_queries": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _F32P, _P, _U8P, _I64P]),
     "pcv_searcher_search_like": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _INTP, _U8P]),

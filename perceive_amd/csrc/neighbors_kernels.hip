@@ -1,0 +1,424 @@
+// neighbors_kernels.hip — the device steps of pcv_searcher_neighbors (DESIGN.md §4 "Item neighbours"): for every participating row
+// its k best other participating rows by the canonical f64 cosine, exact, computed where the rows live.  The norms come from
+// selfjoin_prep_kernel (launch_selfjoin_prep); then
+//
+//   1. neighbors_screen_kernel<NT, false>   the bound pass: the tile-in-LDS, stream-the-blocks screen of selfjoin_screen_kernel over a
+//                                           SAMPLE of the partner blocks (every stride-th), cut into spans.  Per tile row and span it
+//                                           leaves the largest certified screening score s = acc * rinv_a * rinv_b (span_max).
+//   2. neighbors_threshold_kernel           a wave per row: thr = (k-th largest span maximum) - 2 margin.  The spans are disjoint
+//                                           partner sets, so k maxima are k distinct partners with c >= s - margin: the k-th best c
+//                                           of the row is >= kth_s - margin, and a member of the true top k has s >= kth_s - 2 margin.
+//   3. neighbors_screen_kernel<NT, true>    the list pass: the same stream over ALL blocks, the full square.  (owner a, partner b) is
+//                                           a candidate iff both take part, a != b and s >= thr[a] — a threshold per tile row, in
+//                                           registers beside rinv_a.  Appends past the list's capacity are counted, not stored: the
+//                                           host repeats the launch once with the capacity the count asks for.
+//   4. count / offsets / rescore            candidates per owner, their exclusive scan, and one thread per candidate: the canonical
+//                                           f64 cosine (pair_sums and finish_score: the arithmetic of selfjoin_rescore_kernel), its
+//                                           f64_key image and the partner stored in the owner's stretch of the sorted arrays.
+//   5. neighbors_select_kernel              a wave per owner: k rounds, each the best entry (c descending, partner ascending) strictly
+//                                           behind the one picked before — no entry is changed, so the order the atomics of step 4
+//                                           landed in cannot show.  It writes ids, neighbour ids, (float)c and counts.
+#include "device_access.h"
+#include "launch_rows.h"
+#include "scan.h"
+
+namespace pcv {
+namespace {
+
+constexpr int kNbrWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
+
+__device__ __forceinline__ void g_atomic_max32(uint32_t* p, uint32_t v) {
+    (void)__hip_atomic_fetch_max((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t g_atomic_add32(uint32_t* p, uint32_t v) {
+    return __hip_atomic_fetch_add((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// grid: x = tile (NT consecutive blocks: the owners), y = walk: the sampled blocks [y * walk_len, + walk_len) of the launch, cut at
+// its end; sampled block j is launch block j * stride.  Wave w takes the sampled blocks first + w, first + w + kNbrWaves, ...
+// D[row of the streamed block][row of the tile]: lane (c = lane & 31, h = lane >> 5) holds tile rows 32 t + c and, in accumulator
+// i, block row (i & 3) + 8 (i >> 2) + 4 h.
+template <int NT, bool LIST>
+__global__ __launch_bounds__(kNbrWaves * 64) void neighbors_screen_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
+    const ScanParams& p = *pp;
+    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
+    __shared__ const float4* tbase[NT];
+    const int D4 = p.D4, P8 = D4 >> 1, NCH = D4 >> 4;
+    const uint32_t TB = p.total_blocks;
+    const uint32_t tb0 = blockIdx.x * NT;
+    const uint32_t step = kNbrWaves * a.stride;  // launch blocks between two blocks of a wave
+    const uint32_t SB = (TB + a.stride - 1) / a.stride;
+    const uint64_t first = (uint64_t)blockIdx.y * a.walk_len;
+    if (first >= SB) return;  // (the whole workgroup)
+    const uint32_t b0 = (uint32_t)first * a.stride;
+    const uint32_t b1 = (uint32_t)min((uint64_t)SB, first + a.walk_len) * a.stride;  // every sampled block below it is below TB
+
+    if (threadIdx.x < NT) {
+        const uint32_t gb = tb0 + threadIdx.x;
+        const float4* base = nullptr;
+        if (gb < TB) {
+            const SegDesc& sg = p.seg[find_seg(p, gb)];
+            base = gld(&sg.blk) + (size_t)(gb - gld(&sg.blk0)) * D4 * 32;
+        }
+        tbase[threadIdx.x] = base;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < NT * 32 * P8; i += kNbrWaves * 64) {
+        const int r = i & 31, rest = i >> 5;
+        const int tb = rest / P8, pc = rest - tb * P8;
+        const float4* base = tbase[tb];
+        bf16x8 v8 = {};
+        if (base) {
+            const float4 lo = gld4(base + (size_t)(2 * pc) * 32 + r), hi = gld4(base + (size_t)(2 * pc + 1) * 32 + r);
+            const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            v8 = __builtin_convertvector(v, bf16x8);
+        }
+        const int row = tb * 32 + r;
+        lq[row * P8 + swizzle_piece(pc, row, P8)] = __builtin_bit_cast(uint4, v8);
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    if (b0 + wave * a.stride >= b1) return;  // (no workgroup barrier behind this point)
+    // ra: rinv of the lane's tile rows (zero behind the launch's last block);  bd: the list pass's threshold of each, the bound
+    // pass's running maximum of each over the blocks of the span so far
+    float ra[NT], bd[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        ra[t] = gld(&a.rinv[(size_t)(tb0 + t) * 32 + c]);
+        bd[t] = LIST ? gld(&a.thr[(size_t)(tb0 + t) * 32 + c]) : -__builtin_inff();
+    }
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+
+    auto enter_block = [&](JoinCursor& k, uint32_t gb) {
+        k.gb = gb;
+        k.ch = 0;
+        if (gb < b1) {
+            join_seek(p, k.sc, gb);
+            k.rows = row_rsrc(k.sc.blk + (size_t)(gb - k.sc.begin) * D4 * 32, (uint32_t)D4 * 512u);
+        }
+    };
+    const uint32_t lane_off = (uint32_t)(h * 64 + c) * 16u;  // the lane's bytes inside a block
+    JoinCursor cons, prod;
+    enter_block(cons, b0 + wave * a.stride);
+    prod = cons;
+
+    float4 buf[2][8];
+    // (always issues its loads: past the end of the wave's stream they read a chunk of its last block again — scan_mfma_kernel)
+    auto produce = [&](float4 (&b)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
+        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + step);
+    };
+
+    f32x4 rb[4];  // rinv of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
+    auto rb_prefetch = [&]() {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rb[j] = *(const PCV_GLOBAL f32x4*)(a.rinv + (size_t)cons.gb * 32 + 8 * j + 4 * h);
+    };
+    auto partner_row = [&](int i) { return cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h); };
+
+    // the list pass: (owner 32 t + c of the tile, partner i of the block) is a candidate
+    auto passes = [&](int t, int i, bool own) -> bool {
+        const float rbi = rb[i >> 2][i & 3];
+        const float s = acc[t][i] * ra[t] * rbi;
+        bool ok = (ra[t] > 0.0f && rbi > 0.0f) ? s >= bd[t] : (ra[t] != 0.0f && rbi != 0.0f);  // (a wild row: every pair, scan.h)
+        if (own) ok = ok && (tb0 + t) * 32u + (uint32_t)c != partner_row(i);
+        return ok;
+    };
+
+    auto epilogue = [&]() {
+        if (NCH < 2) rb_prefetch();
+        const bool own = cons.gb >= tb0 && cons.gb < tb0 + NT;  // the block is one of the tile's own: a row is no partner of itself
+        if (LIST) {
+            uint32_t n = 0;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) n += passes(t, i, own) ? 1u : 0u;
+            if (n) {  // rare; the pairs are judged again instead of kept as masks: four registers the <4> form does not have
+                unsigned long long at = g_atomic_add64(&a.counters[0], n);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        if (passes(t, i, own)) {
+                            if (at < a.cand_cap) gst(&a.cand[at], ((uint64_t)((tb0 + t) * 32u + (uint32_t)c) << 32) | partner_row(i));
+                            ++at;
+                        }
+                    }
+                }
+            }
+        } else {
+            // the running maximum of the certified scores: partners that take part with a certified s (a wild partner adds nothing)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                float m = bd[t];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float rbi = rb[i >> 2][i & 3];
+                    const float s = acc[t][i] * ra[t] * rbi;
+                    bool ok = rbi > 0.0f;
+                    if (own) ok = ok && (tb0 + t) * 32u + (uint32_t)c != partner_row(i);
+                    m = ok ? fmaxf(m, s) : m;
+                }
+                bd[t] = m;
+            }
+            // the wave's next block lies in another span, or there is none: publish.  Max commutes, so span_max does not depend on
+            // which wave lands first
+            const uint32_t per = a.stride * a.span_len;  // launch blocks a span covers
+            const uint32_t span = cons.gb / per, next = cons.gb + step;
+            if (next >= b1 || next / per != span) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const float m = fmaxf(bd[t], __shfl_xor(bd[t], 32));
+                    if (h == 0 && ra[t] > 0.0f && m > -__builtin_inff())
+                        g_atomic_max32(&a.span_max[(size_t)span * TB * 32 + (size_t)(tb0 + t) * 32 + c], f32_key(m));
+                    bd[t] = -__builtin_inff();
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+    };
+
+    auto consume = [&](const float4 (&b)[8]) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const f32x8 v = {b[2 * ks].x, b[2 * ks].y, b[2 * ks].z, b[2 * ks].w, b[2 * ks + 1].x, b[2 * ks + 1].y, b[2 * ks + 1].z, b[2 * ks + 1].w};
+            const bf16x8 av = __builtin_convertvector(v, bf16x8);
+            const int pc = 2 * (cons.ch * 4 + ks) + h;
+            const int ph = swizzle_piece(pc, c, P8);  // (tile row 32 t + c: the same low four bits as c)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const bf16x8 q8 = *(const bf16x8*)&lq[(32 * t + c) * P8 + ph];
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q8, acc[t], 0, 0, 0);
+            }
+        }
+        if (++cons.ch == NCH) {
+            epilogue();
+            enter_block(cons, cons.gb + step);
+        }
+    };
+
+    // one chunk of loads in flight while one feeds the matrix cores (every buf[] index a literal, or the array moves to scratch);
+    // the block's rinv values are requested one chunk ahead of the epilogue and before that step's row loads
+#define PCV_NBR_STEP(REFILL, CONS)                       \
+    if (NCH >= 2 && cons.ch == NCH - 2) rb_prefetch();   \
+    produce(buf[REFILL]);                                \
+    consume(buf[CONS]);                                  \
+    if (cons.gb >= b1) return;
+    produce(buf[0]);
+    while (true) {
+        PCV_NBR_STEP(1, 0)
+        PCV_NBR_STEP(0, 1)
+    }
+#undef PCV_NBR_STEP
+}
+
+// a wave per launch row: the k-th largest of the row's span maxima, found bit by bit from the top on their order-preserving images
+// (the largest T with at least k images >= T; 0 when fewer than k are defined), less twice the margin, rounded down
+__global__ __launch_bounds__(256) void neighbors_threshold_kernel(const NeighborArgs a, uint32_t launch_rows) {
+    const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= launch_rows) return;  // (the whole wave)
+    const int lane = threadIdx.x & 63;
+    uint32_t v[kMaxNeighborSpans / 64];
+#pragma unroll
+    for (int j = 0; j < (int)(kMaxNeighborSpans / 64); ++j) {
+        const uint32_t sp = (uint32_t)j * 64 + lane;
+        v[j] = sp < a.spans ? gld(&a.span_max[(size_t)sp * launch_rows + row]) : 0u;
+    }
+    uint32_t T = 0;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        int n = 0;
+#pragma unroll
+        for (int j = 0; j < (int)(kMaxNeighborSpans / 64); ++j) n += __builtin_popcountll(__ballot(v[j] >= cand));
+        if (n >= a.k) T = cand;
+    }
+    if (lane != 0) return;
+    float thr = -__builtin_inff();
+    if (T != 0 && gld(&a.rinv[row]) > 0.0f) thr = __double2float_rd((double)key_f32(T) - 2.0 * (double)a.margin);
+    gst(&a.thr[row], thr);
+}
+
+// one thread per candidate: its owner has one more
+__global__ __launch_bounds__(256) void neighbors_count_kernel(const NeighborArgs a) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_cand) return;
+    (void)g_atomic_add32(&a.row_cnt[(uint32_t)(gld(&a.cand[i]) >> 32)], 1u);
+}
+
+// one workgroup: row_off = the exclusive scan of row_cnt, 1024 rows a step; row_off[n] = the total
+__global__ __launch_bounds__(1024) void neighbors_offsets_kernel(const NeighborArgs a, uint32_t launch_rows) {
+    __shared__ uint32_t wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint64_t base = 0; base < launch_rows; base += 1024) {
+        const uint64_t i = base + threadIdx.x;
+        const uint32_t x = i < launch_rows ? gld(&a.row_cnt[i]) : 0u;
+        uint32_t inc = x;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = __shfl_up(inc, off);
+            if (lane >= off) inc += y;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            before += w < wave ? wsum[w] : 0u;
+            total += wsum[w];
+        }
+        if (i < launch_rows) gst(&a.row_off[i], carry + before + inc - x);
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) gst(&a.row_off[launch_rows], carry);
+}
+
+// one thread per candidate: the canonical cosine, stored with the partner in a slot of the owner's stretch.  row_cnt counts down:
+// which slot a candidate gets depends on the order the atomics land in, what the select step reads from the stretch does not.
+__global__ __launch_bounds__(256) void neighbors_rescore_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
+    const ScanParams& p = *pp;
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_cand) return;
+    const uint64_t cd = gld(&a.cand[i]);
+    const uint32_t la = (uint32_t)(cd >> 32), lb = (uint32_t)cd;
+    const RowRef ra = row_ref(p, la), rb = row_ref(p, lb);
+    const float4* y[1] = {rb.x};
+    double acc[1];
+    pair_sums<1>(ra.x, y, p.D4, acc, 32);
+    const double cc = finish_score(PCV_METRIC_COSINE, acc[0], gld(&a.norm[la]), gld(&a.norm[lb]));
+    const uint32_t slot = gld(&a.row_off[la]) + g_atomic_add32(&a.row_cnt[la], 0xffffffffu) - 1u;
+    gst(&a.sorted_key[slot], cc == cc ? f64_key(cc) : 0ull);  // (both rows have a cosine: c is a number)
+    gst(&a.sorted_row[slot], lb);
+}
+
+// (key descending, partner ascending): x comes before y
+__device__ __forceinline__ bool nbr_before(unsigned long long kx, uint32_t rx, unsigned long long ky, uint32_t ry) {
+    return kx > ky || (kx == ky && rx < ry);
+}
+
+// a wave per launch row.  An owner's entries are distinct (a partner is listed once per owner), so "the best entry strictly behind
+// the last pick" walks them in order without marking any.
+__global__ __launch_bounds__(256) void neighbors_select_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
+    const ScanParams& p = *pp;
+    const uint32_t lr = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (lr >= p.total_blocks * 32) return;  // (the whole wave)
+    const int lane = threadIdx.x & 63;
+    const RowRef r = row_ref(p, lr);
+    if (r.row >= gld(&r.sg->nrows)) return;
+    const int64_t o = gld(&a.seg_out0[r.sg - p.seg]) + (int64_t)r.row;
+    const uint32_t e0 = gld(&a.row_off[lr]), e1 = gld(&a.row_off[lr + 1]);
+    auto id_of = [](const RowRef& q) {
+        const int64_t* ids = gld(&q.sg->ids);
+        return ids ? gld(&ids[q.row]) : gld(&q.sg->id0) + (int64_t)q.row;
+    };
+    unsigned long long last_key = ~0ull;  // (no image is all ones: that would be a NaN)
+    uint32_t last_row = 0;
+    int n = 0;
+    for (; n < a.k; ++n) {
+        unsigned long long bk = 0;
+        uint32_t br = 0xffffffffu;
+        for (uint32_t e = e0 + lane; e < e1; e += 64) {
+            const unsigned long long key = gld(&a.sorted_key[e]);
+            const uint32_t row = gld(&a.sorted_row[e]);
+            if (key != 0 && nbr_before(last_key, last_row, key, row) && nbr_before(key, row, bk, br)) {
+                bk = key;
+                br = row;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long ok = __shfl_xor(bk, off);
+            const uint32_t orow = __shfl_xor(br, off);
+            if (nbr_before(ok, orow, bk, br)) {
+                bk = ok;
+                br = orow;
+            }
+        }
+        if (bk == 0) break;  // (wave-uniform after the exchange)
+        last_key = bk;
+        last_row = br;
+        if (lane == 0) {
+            gst(&a.out_nbr[o * a.k + n], id_of(row_ref(p, br)));
+            gst(&a.out_score[o * a.k + n], (float)key_f64(bk));
+        }
+    }
+    for (int j = n + lane; j < a.k; j += 64) {
+        gst(&a.out_nbr[o * a.k + j], (int64_t)-1);
+        gst(&a.out_score[o * a.k + j], __builtin_nanf(""));
+    }
+    if (lane == 0) {
+        gst(&a.out_ids[o], id_of(r));
+        gst(&a.out_count[o], (int32_t)n);
+    }
+}
+
+template <bool LIST>
+void launch_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) {
+    if (p.total_blocks == 0) return;
+    const uint32_t NT = a.tile_blocks;
+    PCV_REQUIRE((NT == 1 || NT == 2 || NT == 4) && a.stride >= 1 && a.span_len >= 1 && a.walk_len >= 1 && (LIST ? a.stride == 1 : a.spans <= kMaxNeighborSpans),
+                "neighbors screen: bad shape (tile of %u blocks, stride %u, spans of %u, walks of %u)", NT, a.stride, a.span_len, a.walk_len);
+    const size_t lds = (size_t)NT * 32 * p.D4 * 4 * sizeof(uint16_t);
+    const unsigned tiles = (p.total_blocks + NT - 1) / NT;
+    const unsigned sampled = (p.total_blocks + a.stride - 1) / a.stride;
+    const unsigned walks = (sampled + a.walk_len - 1) / a.walk_len;
+    PCV_REQUIRE(walks <= 65535u, "neighbors screen: %u walks", walks);
+    PCV_REQUIRE(LIST || (sampled + a.span_len - 1) / a.span_len == a.spans, "neighbors screen: %u spans of %u for %u sampled blocks", a.spans, a.span_len, sampled);
+    const dim3 grid(tiles, walks);
+#define PCV_NBR(N)                                                                \
+    allow_dynamic_lds((const void*)neighbors_screen_kernel<N, LIST>, lds);        \
+    neighbors_screen_kernel<N, LIST><<<grid, kNbrWaves * 64, lds, st>>>(dp, a);
+    if (NT == 4) {
+        PCV_NBR(4)
+    } else if (NT == 2) {
+        PCV_NBR(2)
+    } else {
+        PCV_NBR(1)
+    }
+#undef PCV_NBR
+    PCV_LAUNCHED();
+}
+
+}  // namespace
+
+void launch_neighbors_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) { launch_screen<false>(st, p, dp, a); }
+
+void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) { launch_screen<true>(st, p, dp, a); }
+
+void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const NeighborArgs& a) {
+    if (p.total_blocks == 0) return;
+    PCV_REQUIRE(a.spans >= 1 && a.spans <= kMaxNeighborSpans && a.k >= 1, "neighbors threshold: %u spans, k = %d", a.spans, a.k);
+    const uint32_t launch_rows = p.total_blocks * 32;
+    neighbors_threshold_kernel<<<cdiv64((int64_t)launch_rows, 4), 256, 0, st>>>(a, launch_rows);
+    PCV_LAUNCHED();
+}
+
+void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) {
+    if (p.total_blocks == 0) return;
+    if (a.n_cand) neighbors_count_kernel<<<cdiv64((int64_t)a.n_cand, 256), 256, 0, st>>>(a);
+    neighbors_offsets_kernel<<<1, 1024, 0, st>>>(a, p.total_blocks * 32);
+    if (a.n_cand) neighbors_rescore_kernel<<<cdiv64((int64_t)a.n_cand, 256), 256, 0, st>>>(dp, a);
+    PCV_LAUNCHED();
+}
+
+void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) {
+    if (p.total_blocks == 0) return;
+    neighbors_select_kernel<<<cdiv64((int64_t)p.total_blocks * 32, 4), 256, 0, st>>>(dp, a);
+    PCV_LAUNCHED();
+}
+
+}  // namespace pcv

@@ -323,6 +323,45 @@ struct AssignArgs {
     uint32_t span_blocks;           // row blocks one screen workgroup streams (a multiple of its waves)
 };
 
+// Item neighbours (pcv_searcher_neighbors; DESIGN.md §4 "Item neighbours"): the k best other rows of every row.  Rows are launch
+// rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  A launch block with number gb is SAMPLED iff gb is a multiple of
+// stride; sampled block j = gb / stride belongs to span j / span_len.
+//   span_max[span][launch row] : the order-preserving image (f32_key) of the largest certified screening score of the row with a
+//                                partner of that span's sampled blocks, 0: none.  The spans are disjoint sets of partners.
+//   thr[launch row]            : (k-th largest defined span maximum) - 2 margin, rounded down; -inf: fewer than k are defined, or
+//                                the row is wild — every participating partner is a candidate
+//   cand                       : (owner launch row << 32) | partner launch row, DIRECTED: the pair (a, b) is listed for owner a
+//                                iff s >= thr[a], and again for owner b iff s >= thr[b]
+//   row_off[launch row]        : where the owner's candidates start in sorted_key / sorted_row (an exclusive scan of row_cnt;
+//                                entry launch rows: the total); row_cnt is counted up, then counted down as the slots are taken
+//   sorted_key / sorted_row    : per owner, in any order: the f64_key image of c and the partner's launch row
+struct NeighborArgs {
+    float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    double* norm;                   // [total_blocks * 32]
+    uint32_t* span_max;             // [spans][total_blocks * 32]
+    float* thr;                     // [(total_blocks + tile_blocks) * 32]
+    uint64_t* cand;                 // [cand_cap]
+    unsigned long long* counters;   // [0]: candidates the list pass found (not capped)
+    uint32_t* row_cnt;              // [total_blocks * 32]
+    uint32_t* row_off;              // [total_blocks * 32 + 1]
+    unsigned long long* sorted_key; // [n_cand]
+    uint32_t* sorted_row;           // [n_cand]
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    int64_t* out_ids;               // [rows]
+    int64_t* out_nbr;               // [rows][k], unused slots -1
+    float* out_score;               // [rows][k], unused slots NaN
+    int32_t* out_count;             // [rows]
+    unsigned long long cand_cap, n_cand;
+    float margin;                   // selfjoin_margin(Dp)
+    int k;
+    uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
+    uint32_t stride;                // every stride-th block is a partner block of this launch (the list pass: 1)
+    uint32_t span_len;              // sampled blocks of one span
+    uint32_t spans;                 // ceil(sampled blocks / span_len), at most kMaxNeighborSpans
+    uint32_t walk_len;              // sampled blocks one workgroup streams against its tile
+};
+constexpr uint32_t kMaxNeighborSpans = 512;  // (the threshold kernel keeps a row's maxima in eight registers a lane)
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -384,6 +423,12 @@ void launch_assign_screen(hipStream_t st, const ScanParams& p, const ScanParams*
 void launch_assign_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
 void launch_assign_finish(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // winners -> outputs
 void launch_label_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
+// ---- item neighbours (neighbors_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_neighbors_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);    // -> span_max
+void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const NeighborArgs& a);                      // span_max -> thr
+void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);     // thr -> cand
+void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);  // cand -> sorted_*
+void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);   // sorted_* -> outputs
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);
 void launch_merge(hipStream_t st, const pcv_hit_dev* lists, int n_shards, int B, int k, pcv_hit_dev* out,
                   int flagged = 0);

@@ -240,6 +240,7 @@ struct pcv_searcher {
     PinBuf<uint8_t> pin_distinct;
     pcv_duplicate_stats dup_stats{};  // pcv_searcher_find_duplicates (its buffers live for the call only)
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
+    pcv_neighbor_stats nbr_stats{};   // pcv_searcher_neighbors (likewise)
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -2918,6 +2919,179 @@ void label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const
     }
 }
 
+// ---- item neighbours (pcv_searcher_neighbors; DESIGN.md §4 "Item neighbours") ----
+constexpr uint64_t kMaxNeighborCandidates = (uint64_t)1 << 30;  // directed (owner, partner) pairs the list pass may leave: 20 bytes each
+constexpr uint32_t kNeighborWalkBlocks = 256;  // sampled blocks a workgroup streams against its tile (kJoinSpanBlocks)
+
+// Prep, bound pass, thresholds, list pass, rescore, select (neighbors_kernels.hip).  Everything the call allocates is its own and
+// is given back when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
+void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int64_t capacity, int64_t* out_ids, int64_t* out_neighbor_ids,
+               float* out_scores, int32_t* out_counts, int64_t* out_rows) {
+    PCV_REQUIRE(!s->dirty, "neighbors: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "neighbors: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_rows = n;
+    if (out_ids == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "neighbors: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    s->nbr_stats = pcv_neighbor_stats{};
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "neighbors: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (n == 0) return;
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+
+    const size_t off_seg = align_up(sizeof(ScanParams)), off_out0 = align_up(off_seg + segs.size() * sizeof(SegDesc));
+    const size_t bytes = off_out0 + segs.size() * sizeof(int64_t);
+    PinBuf<uint8_t> pin_p;
+    DevBuf<uint8_t> d_p;
+    pin_p.ensure(bytes);
+    d_p.ensure(bytes);
+    ScanParams& p = *new (pin_p.p) ScanParams{};
+    int64_t rows = 0;
+    p.total_blocks = fill_row_table(segs, reinterpret_cast<SegDesc*>(pin_p.p + off_seg), reinterpret_cast<int64_t*>(pin_p.p + off_out0), rows, "neighbors");
+    p.seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
+    p.nseg = (int)segs.size();
+    p.D = s->D;
+    p.D4 = s->D4;
+    p.metric = PCV_METRIC_COSINE;
+    const ScanParams* dp = reinterpret_cast<const ScanParams*>(d_p.p);
+
+    // The sample and its spans (DESIGN.md §4 "Item neighbours", measurement): no result depends on them, only the list's length.
+    NeighborArgs a{};
+    a.k = k;
+    a.margin = selfjoin_margin(s->Dp);
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    const uint32_t TB = p.total_blocks;
+    a.stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / (uint32_t)std::max(64, 4 * k)));
+    const uint32_t sampled = (TB + a.stride - 1) / a.stride;
+    const uint32_t want_spans = std::min<uint32_t>(sampled, std::min<uint32_t>(kMaxNeighborSpans, (uint32_t)std::max(64, 8 * k)));
+    a.span_len = (sampled + want_spans - 1) / want_spans;
+    a.spans = (sampled + a.span_len - 1) / a.span_len;
+    a.walk_len = kNeighborWalkBlocks;
+    while ((TB + a.walk_len - 1) / a.walk_len > 65535u) a.walk_len *= 2;  // (the grid's second dimension)
+
+    const size_t nr = (size_t)TB * kBlockRows, n_pad = ((size_t)TB + a.tile_blocks) * kBlockRows;
+    DevBuf<float> d_rinv, d_thr, d_out_score;
+    DevBuf<double> d_norm;
+    DevBuf<uint32_t> d_span_max, d_cnt_off, d_sorted_row;
+    DevBuf<unsigned long long> d_cnt, d_sorted_key;
+    DevBuf<uint64_t> d_cand;
+    DevBuf<int64_t> d_out_ids, d_out_nbr;
+    DevBuf<int32_t> d_out_count;
+    d_rinv.ensure(n_pad);
+    d_thr.ensure(n_pad);
+    d_norm.ensure(nr);
+    d_span_max.ensure((size_t)a.spans * nr);
+    d_cnt_off.ensure(2 * nr + 1);
+    d_cnt.ensure(1);
+    a.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)k * (uint64_t)rows));
+    d_cand.ensure(a.cand_cap);
+    d_out_ids.ensure((size_t)rows);
+    d_out_nbr.ensure((size_t)rows * k);
+    d_out_score.ensure((size_t)rows * k);
+    d_out_count.ensure((size_t)rows);
+    a.rinv = d_rinv.p;
+    a.thr = d_thr.p;
+    a.norm = d_norm.p;
+    a.span_max = d_span_max.p;
+    a.row_cnt = d_cnt_off.p;
+    a.row_off = d_cnt_off.p + nr;
+    a.counters = d_cnt.p;
+    a.cand = d_cand.p;
+    a.seg_out0 = reinterpret_cast<const int64_t*>(d_p.p + off_out0);
+    a.out_ids = d_out_ids.p;
+    a.out_nbr = d_out_nbr.p;
+    a.out_score = d_out_score.p;
+    a.out_count = d_out_count.p;
+
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const auto drop_events = at_exit([&] {
+        (void)hipStreamSynchronize(st);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    });
+    for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
+    auto elapsed = [&](int from) {
+        float ms = 0.0f;
+        PCV_HIP(hipEventElapsedTime(&ms, ev[from], ev[from + 1]));
+        return ms;
+    };
+    pcv_neighbor_stats& stats = s->nbr_stats;
+    stats.rows = rows;
+    stats.k = k;
+    stats.tile_rows = tile;
+    stats.sample_stride = (int32_t)a.stride;
+    stats.spans = (int32_t)a.spans;
+
+    SelfJoinArgs prep{};
+    prep.rinv = d_rinv.p;
+    prep.norm = d_norm.p;
+    unsigned long long count = 0;
+    PCV_HIP(hipMemcpyAsync(d_p.p, pin_p.p, bytes, hipMemcpyHostToDevice, st));
+    PCV_HIP(hipMemsetAsync(d_rinv.p, 0, n_pad * sizeof(float), st));
+    PCV_HIP(hipMemsetAsync(d_thr.p, 0, n_pad * sizeof(float), st));
+    PCV_HIP(hipMemsetAsync(d_span_max.p, 0, (size_t)a.spans * nr * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+    PCV_HIP(hipEventRecord(ev[0], st));
+    launch_selfjoin_prep(st, p, dp, prep);
+    PCV_HIP(hipEventRecord(ev[1], st));
+    launch_neighbors_bound(st, p, dp, a);
+    launch_neighbors_threshold(st, p, a);
+    PCV_HIP(hipEventRecord(ev[2], st));
+    a.stride = 1;  // the list pass: every block
+    launch_neighbors_list(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[3], st));
+    PCV_HIP(hipMemcpyAsync(&count, d_cnt.p, sizeof(count), hipMemcpyDeviceToHost, st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    stats.prep_ms = elapsed(0);
+    stats.bound_ms = elapsed(1);
+    stats.screen_ms = elapsed(2);
+    const uint64_t n_cand = count;
+    stats.candidates = (int64_t)n_cand;
+    if (n_cand > kMaxNeighborCandidates)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED, "neighbors: the list pass leaves %llu candidates for k = %d, more than %llu: ask for fewer neighbours or fewer rows",
+                 (unsigned long long)n_cand, k, (unsigned long long)kMaxNeighborCandidates);
+    if (n_cand > a.cand_cap) {  // once more, with the room the count asks for (the pass lists the same pairs again)
+        a.cand_cap = n_cand;
+        d_cand.ensure(a.cand_cap);
+        a.cand = d_cand.p;
+        PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+        PCV_HIP(hipEventRecord(ev[2], st));
+        launch_neighbors_list(st, p, dp, a);
+        PCV_HIP(hipEventRecord(ev[3], st));
+        PCV_HIP(hipMemcpyAsync(&count, d_cnt.p, sizeof(count), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        PCV_REQUIRE(count == n_cand, "neighbors: the repeated list pass left %llu candidates, the first %llu", count, (unsigned long long)n_cand);
+        stats.reruns = 1;
+        stats.screen_ms += elapsed(2);
+    }
+    a.n_cand = n_cand;
+    d_sorted_key.ensure((size_t)std::max<uint64_t>(1, n_cand));
+    d_sorted_row.ensure((size_t)std::max<uint64_t>(1, n_cand));
+    a.sorted_key = d_sorted_key.p;
+    a.sorted_row = d_sorted_row.p;
+    PCV_HIP(hipEventRecord(ev[3], st));
+    launch_neighbors_rescore(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[4], st));
+    launch_neighbors_select(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[5], st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    stats.rescore_ms = elapsed(3);
+    stats.select_ms = elapsed(4);
+    PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_neighbor_ids, d_out_nbr.p, (size_t)rows * k * sizeof(int64_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_scores, d_out_score.p, (size_t)rows * k * sizeof(float), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_counts, d_out_count.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t listed = 0;
+    for (int64_t i = 0; i < rows; ++i) listed += out_counts[i];
+    stats.listed = listed;
+}
+
 void sync_view(pcv_searcher* v);
 
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.
@@ -3997,6 +4171,31 @@ pcv_status pcv_searcher_last_assign_stats(pcv_searcher* s, pcv_assign_stats* out
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_assign_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->assign_stats;
+    });
+}
+
+pcv_status pcv_searcher_neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int64_t capacity, int64_t* out_ids,
+                                  int64_t* out_neighbor_ids, float* out_scores, int32_t* out_counts, int64_t* out_rows) {
+    return guarded([&] {
+        PCV_REQUIRE(out_rows != nullptr, "neighbors: out_rows is NULL");
+        PCV_REQUIRE(k >= 1 && k <= (int)PCV_MAX_NEIGHBORS, "neighbors: k %d outside [1,%d]", k, (int)PCV_MAX_NEIGHBORS);
+        PCV_REQUIRE(capacity >= 0, "neighbors: capacity %lld is negative", (long long)capacity);
+        const bool all = out_ids != nullptr && out_neighbor_ids != nullptr && out_scores != nullptr && out_counts != nullptr;
+        const bool none = out_ids == nullptr && out_neighbor_ids == nullptr && out_scores == nullptr && out_counts == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "neighbors: an output array is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "neighbors: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "neighbors: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        neighbors(s, source_ids, n_sources, k, capacity, out_ids, out_neighbor_ids, out_scores, out_counts, out_rows);
+    });
+}
+
+pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_neighbor_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->nbr_stats;
     });
 }
 

@@ -14,6 +14,7 @@ from .context import Context
 
 PCV_MAX_DISTINCT_POOL = 4096  # include/perceive_hip.h
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
+PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
 
 _METRICS = {"cosine": _ffi.METRIC_COSINE, "dot": _ffi.METRIC_DOT}
 _KERNELS = {"auto": _ffi.KERNEL_AUTO, "wave": _ffi.KERNEL_WAVE, "mfma": _ffi.KERNEL_MFMA}
@@ -529,6 +530,37 @@ class Searcher:
         st = _ffi.AssignStats()
         _ffi.check(_ffi.lib().pcv_searcher_last_assign_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.AssignStats._fields_}
+
+    # ---- item neighbours (pcv_searcher_neighbors) --------------------------------------------------
+    # The k-nearest-neighbour table of the corpus: what N / 256 search_like calls would give, in one call that no search setting touches.
+    def neighbors(self, sources, k):
+        """For every row of `sources` its exact k best other rows by canonical cosine (both metrics; ties: the row stored first) ->
+        (ids [n] int64, neighbor_ids [n, k] int64, scores [n, k] f32, counts [n] int32), by global position; row i has counts[i]
+        neighbours, best first, the unused slots -1 / NaN.  A row no search could return, or without a cosine, has none and is
+        nobody's neighbour.  A view lists its own rows."""
+        k = int(k)
+        if not 1 <= k <= PCV_MAX_NEIGHBORS:
+            raise ValueError("k outside [1, %d]" % PCV_MAX_NEIGHBORS)
+        src, nsrc, _keep = _source_filter(sources)
+        n = C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_neighbors(self._handle, src, nsrc, k, 0, None, None, None, None, C.byref(n)))
+        n = n.value
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        nbr = np.empty((max(n, 1), k), dtype=np.int64)
+        scores = np.empty((max(n, 1), k), dtype=np.float32)
+        counts = np.empty(max(n, 1), dtype=np.int32)
+        got = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_neighbors(
+                self._handle, src, nsrc, k, max(n, 1), _ffi.i64p(ids), _ffi.i64p(nbr), _ffi.f32p(scores), _ffi.i32p(counts), C.byref(got)
+            )
+        )
+        return ids[:n], nbr[:n], scores[:n], counts[:n]
+
+    def last_neighbor_stats(self):
+        st = _ffi.NeighborStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_neighbor_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.NeighborStats._fields_}
 
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):

@@ -60,6 +60,24 @@ pub struct pcv_assign_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_neighbor_stats {
+    pub rows: i64,
+    pub candidates: i64,
+    pub listed: i64,
+    pub k: i32,
+    pub tile_rows: i32,
+    pub sample_stride: i32,
+    pub spans: i32,
+    pub reruns: i32,
+    pub prep_ms: f32,
+    pub bound_ms: f32,
+    pub screen_ms: f32,
+    pub rescore_ms: f32,
+    pub select_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_hit {
     pub score: f64,
     pub pos: i64,
@@ -144,6 +162,7 @@ pub const PCV_MAX_RANGE_ROWS: c_int = 16777216;
 pub const PCV_MAX_DISTINCT_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
+pub const PCV_MAX_NEIGHBORS: c_int = 64;
 pub const PCV_GELU_ERF: c_int = 0;
 pub const PCV_GELU_TANH: c_int = 1;
 pub const PCV_POOL_MEAN: c_int = 0;
@@ -222,6 +241,8 @@ extern "C" {
     pub fn pcv_searcher_label_sums(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, labels: *const i32, n: i64, n_labels: c_int, out_sums: *mut i64, out_counts: *mut i64) -> c_int;
     pub fn pcv_searcher_kmeans(s: *mut pcv_searcher, init: *const f32, n_labels: c_int, max_iters: c_int, source_ids: *const i64, n_sources: c_int, capacity: i64, out_centroids: *mut f32, out_label: *mut i32, out_score: *mut f32, out_ids: *mut i64, out_counts: *mut i64, out_iters: *mut i32, out_moved: *mut i64, out_n: *mut i64) -> c_int;
     pub fn pcv_searcher_last_assign_stats(s: *mut pcv_searcher, out: *mut pcv_assign_stats) -> c_int;
+    pub fn pcv_searcher_neighbors(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, capacity: i64, out_ids: *mut i64, out_neighbor_ids: *mut i64, out_scores: *mut f32, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_last_neighbor_stats(s: *mut pcv_searcher, out: *mut pcv_neighbor_stats) -> c_int;
     pub fn pcv_duplicate_groups(id_a: *const i64, id_b: *const i64, n_pairs: i64, out_ids: *mut i64, out_group: *mut i64, capacity: i64, out_n_ids: *mut i64) -> c_int;
     pub fn pcv_searcher_like_queries(s: *mut pcv_searcher, example_ids: *const i64, weights: *const f32, offsets: *const i64, n_queries: c_int, out_queries: *mut f32, d_out_queries: *mut c_void, out_found: *mut u8, out_member_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_search_like(s: *mut pcv_searcher, example_ids: *const i64, weights: *const f32, offsets: *const i64, n_queries: c_int, source_ids: *const i64, n_sources: c_int, k: c_int, exclude_examples: c_int, out_ids: *mut i64, out_scores: *mut f32, out_counts: *mut c_int, out_found: *mut u8) -> c_int;

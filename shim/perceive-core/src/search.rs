@@ -501,6 +501,53 @@ impl Searcher {
         ((centroids), (0..n as usize).map(|i| (label[i], score[i], ids[i])).collect(), counts, done as usize, moved)
     }
 
+    /// Item neighbours (`pcv_searcher_neighbors`): for every item of `sources`, by global position, its exact `k` best other
+    /// items by cosine (clamped to PCV_MAX_NEIGHBORS), best first — the table a "related items" panel reads without a search.
+    /// Returns (item id, its neighbours as (id, cosine)) per item; an item no search could return has none.
+    pub fn neighbors(&self, sources: &[i64], k: usize) -> Vec<(i64, Vec<(i64, f32)>)> {
+        if self.handle.is_null() || k == 0 || sources.is_empty() {
+            return Vec::new();
+        }
+        let k = k.min(ffi::PCV_MAX_NEIGHBORS as usize);
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_neighbors(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                k as i32,
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                &mut n,
+            )
+        })
+        .expect("neighbors failed");
+        let room = n.max(1) as usize;
+        let mut ids = vec![-1i64; room];
+        let mut nbr = vec![-1i64; room * k];
+        let mut scores = vec![f32::NAN; room * k];
+        let mut counts = vec![0i32; room];
+        hip::check(unsafe {
+            ffi::pcv_searcher_neighbors(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                k as i32,
+                room as i64,
+                ids.as_mut_ptr(),
+                nbr.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("neighbors failed");
+        (0..n as usize).map(|i| (ids[i], (0..counts[i] as usize).map(|j| (nbr[i * k + j], scores[i * k + j])).collect())).collect()
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
