@@ -158,6 +158,35 @@ inline std::vector<SearchItem> search_distinct_handle(pcv_searcher* h, const std
     return out;
 }
 
+// One hit of search_vector_grouped: the best member of a group, the group's key (PCV_NO_GROUP: an item without a group, which is
+// a group of its own) and the examined items collapsed into it.
+struct GroupedItem {
+    SearchItem item;
+    int64_t group;
+    int32_t collapsed;
+};
+// Grouped results on a searcher or a view handle (pcv_searcher_search_grouped): the ranked list of search_vector walked best first,
+// an item kept iff no kept item has its group (Searcher::set_groups; a view reads its parent's); at most `pool` entries are
+// examined (0: the default, min(PCV_MAX_GROUPED_POOL, max(128, 8 * num_results))).  `more`, if given: the walk stopped at `pool`
+// short of num_results although the list went on.
+inline std::vector<GroupedItem> search_grouped_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results,
+                                                      const std::vector<float>& vector, size_t pool, bool* more) {
+    if (more) *more = false;
+    if (sources.empty() || num_results == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    if (pool == 0) pool = std::min<size_t>(PCV_MAX_GROUPED_POOL, std::max<size_t>(128, 8 * num_results));
+    std::vector<int64_t> ids(num_results), groups(num_results);
+    std::vector<float> scores(num_results);
+    std::vector<int32_t> collapsed(num_results);
+    int32_t count = 0;
+    uint8_t m = 0;
+    check(pcv_searcher_search_grouped(h, vector.data(), 1, sources.data(), (int)sources.size(), (int)num_results, (int)pool, ids.data(),
+                                      scores.data(), groups.data(), &count, collapsed.data(), nullptr, &m));
+    if (more) *more = m != 0;
+    std::vector<GroupedItem> out;
+    for (int i = 0; i < count; ++i) out.push_back({{ids[(size_t)i], scores[(size_t)i]}, groups[(size_t)i], collapsed[(size_t)i]});
+    return out;
+}
+
 // One duplicate pair of find_duplicates: the item stored first, the other one, their cosine.
 struct DuplicatePair {
     int64_t id_a, id_b;
@@ -299,6 +328,11 @@ public:
                                                    float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
         return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
     }
+    // the view's best groups, one item each, by the parent's group table (search_grouped_handle)
+    std::vector<GroupedItem> search_vector_grouped(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   size_t pool = 0, bool* more = nullptr) const {
+        return search_grouped_handle(h_, sources, num_results, vector, pool, more);
+    }
     // the duplicate pairs among the view's items (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
                                                int64_t* total = nullptr) const {
@@ -412,6 +446,24 @@ public:
     std::vector<SearchItem> search_vector_distinct(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
                                                    float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
         return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
+    }
+    // the group table (pcv_searcher_set_groups): item ids[i] belongs to group groups[i] (>= 0; PCV_NO_GROUP ungroups); the last
+    // occurrence of an id holds.  Keyed by id: it survives remove_items and rebuild_source.
+    void set_groups(const std::vector<int64_t>& ids, const std::vector<int64_t>& groups) {
+        if (ids.size() != groups.size()) throw std::invalid_argument("set_groups: ids and groups differ in length");
+        check(pcv_searcher_set_groups(h_, ids.data(), groups.data(), (int64_t)ids.size()));
+    }
+    void clear_groups() { check(pcv_searcher_clear_groups(h_)); }
+    // the group of every id, PCV_NO_GROUP where it has none
+    std::vector<int64_t> groups_of(const std::vector<int64_t>& ids) const {
+        std::vector<int64_t> out(ids.size(), PCV_NO_GROUP);
+        check(pcv_searcher_get_groups(h_, ids.data(), (int64_t)ids.size(), out.data()));
+        return out;
+    }
+    // the best groups, one item each: "the k closest documents" over chunk rows (search_grouped_handle)
+    std::vector<GroupedItem> search_vector_grouped(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   size_t pool = 0, bool* more = nullptr) const {
+        return search_grouped_handle(h_, sources, num_results, vector, pool, more);
     }
     // every pair of near-duplicate items, found once on the device (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,

@@ -418,6 +418,69 @@ pcv_status pcv_searcher_search_distinct(pcv_searcher* s, const float* queries, i
                                         int num_results, float threshold, int pool, int64_t* out_ids, float* out_scores,
                                         int32_t* out_counts, int32_t* out_similar, int32_t* out_examined, uint8_t* out_more);
 
+/* Grouped results: the exact top-k collapsed by a stored group key per item ("which k documents are closest, when every document is
+ * stored as several rows").
+ *
+ * The group table is state of a searcher: an open-addressed hash table on the device from item id to group key.
+ *   - A group key is any int64 >= 0; PCV_NO_GROUP (-1) means "no group".  An id without an entry, or with PCV_NO_GROUP, is a
+ *     group of its own — and such a singleton is the ROW, not the id: two ungrouped rows that share an item id do not collapse,
+ *     two rows that share an id with a group do (they share the group).
+ *   - Keyed by id, not by row: hide, update, remove, replace_source and the screening copies know nothing of it, and an entry
+ *     SURVIVES pcv_searcher_remove_ids, clear_source and replace_source — an id that comes back has its group again.  Only
+ *     pcv_searcher_clear_groups forgets (everything: the searcher is then as created, counters included).
+ *   - It lives with the root searcher.  A view reads its parent's table at call time (a set_groups on the parent is seen by the
+ *     view's next search); the three mutators on a view fail as every change of a view does.
+ *   - Memory: 16 bytes per slot, slots a power of two >= 2 * entries, 1024 at least: 100M grouped ids take 2^28 slots, 4.3 GB.
+ *     While a set_groups call runs it holds 4 bytes per slot more, and up to 2^22 ids of the batch at a time (84 MB).
+ * pcv_searcher_set_groups: an upsert of (ids[i], groups[i]), i < n.  groups[i] == PCV_NO_GROUP ungroups the id (its entry stays;
+ *   there are no tombstones); any other negative group, a NULL list with n > 0 or n < 0 give PCV_ERR_INVALID before any device
+ *   work.  Of an id that occurs more than once in a batch the LAST occurrence holds.  A batch is one growth decision: the table is
+ *   sized for entries + n before the batch goes in (ids already present count twice there: growth may come one batch early).
+ *   More than 2^30 entries give PCV_ERR_UNSUPPORTED before anything is allocated; a failed allocation (PCV_ERR_DEVICE) leaves
+ *   the table as it was.
+ * pcv_searcher_get_groups: out_groups[i] = the group of ids[i], PCV_NO_GROUP if it has none.  Works on a view (the parent's table).
+ * pcv_searcher_group_stats: ids with a group >= 0 / occupied slots / capacity / growths by rehash since creation (or the last
+ *   clear_groups) / device time of the last set_groups, growth included (hipEvent). */
+#define PCV_NO_GROUP (-1)
+typedef struct pcv_group_stats {
+    int64_t ids;
+    int64_t entries;
+    int64_t slots;
+    int32_t rehashes;
+    float last_set_ms;
+} pcv_group_stats;
+pcv_status pcv_searcher_set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int64_t n);
+pcv_status pcv_searcher_clear_groups(pcv_searcher* s);
+pcv_status pcv_searcher_get_groups(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_groups);
+pcv_status pcv_searcher_group_stats(pcv_searcher* s, pcv_group_stats* out);
+/* pcv_searcher_search_grouped.  Per query, L is the ranked list pcv_searcher_search returns (canonical score, ties -> lower
+ * position; the searchable rows of the selected sources: hidden rows and a view's restriction apply as everywhere).  L is walked
+ * best first and only its first `pool` entries are examined: a row is KEPT iff no kept row has its group, otherwise it is COLLAPSED
+ * into that kept row; the walk stops right after the num_results-th kept row, or at the end of the examined prefix.  A kept row is
+ * therefore the best-scoring member of its group among the selected rows, and with out_more == 0 the kept rows are the
+ * num_results best groups of the corpus by best member.
+ *   pool          num_results .. PCV_MAX_GROUPED_POOL: entries of L the walk may examine
+ *   out_ids       [n_queries][num_results] the kept rows, best first, -1 behind them;  out_scores likewise, NaN behind them (may be
+ *                 NULL) — ids and scores are bit for bit what pcv_searcher_search reports for those rows
+ *   out_groups    [n_queries][num_results] the group key of each kept row, PCV_NO_GROUP for an ungrouped row and behind the results
+ *                 (may be NULL)
+ *   out_counts    [n_queries] rows kept
+ *   out_collapsed [n_queries][num_results] examined rows collapsed into this hit, 0 behind the results (may be NULL)
+ *   out_examined  [n_queries] entries of L examined (may be NULL)
+ *   out_more      [n_queries] 1: the walk stopped at `pool` with fewer than num_results kept and L had another row (may be NULL)
+ * A NULL searcher, no queries, num_results outside [1, PCV_MAX_RESULTS] or pool outside [num_results, PCV_MAX_GROUPED_POOL] give
+ * PCV_ERR_INVALID before any device work; a searcher with pending rows fails as in pcv_searcher_search.  An empty table is legal:
+ * the result is the plain top-num_results.  A call makes at most ceil(pool / PCV_MAX_RESULTS) passes per group of queries, each
+ * followed by a select step on the device whose cost is fixed (DESIGN.md §4 "Grouped results"), and one short pass more where
+ * out_more has to be decided.  Known limit: a large group near a query costs passes — a 500-row document costs four; `pool`
+ * bounds that and out_more reports it.
+ * Not in scope: group-aware neighbours / duplicates / search by example, a sharded form, device-resident output, more than one
+ * member per group. */
+enum { PCV_MAX_GROUPED_POOL = 4096 };
+pcv_status pcv_searcher_search_grouped(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                       int num_results, int pool, int64_t* out_ids, float* out_scores, int64_t* out_groups,
+                                       int32_t* out_counts, int32_t* out_collapsed, int32_t* out_examined, uint8_t* out_more);
+
 /* Duplicate pairs: the exact self-join of the corpus on the device — every pair of searchable rows that are near-duplicates of each
  * other, found once and corpus-wide (what pcv_searcher_search_distinct collapses per query, for pcv_searcher_remove_ids /
  * pcv_searcher_hide_ids to act on).

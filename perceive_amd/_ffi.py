@@ -94,6 +94,16 @@ class NeighborStats(C.Structure):
     ]
 
 
+class GroupStats(C.Structure):
+    _fields_ = [
+        ("ids", C.c_int64),
+        ("entries", C.c_int64),
+        ("slots", C.c_int64),
+        ("rehashes", C.c_int32),
+        ("last_set_ms", C.c_float),
+    ]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32),
@@ -183,6 +193,11 @@ SYMBOLS = {
     "pcv_searcher_search": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, _I64P, _F32P, _INTP]),
     "pcv_searcher_search_range": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, _F32P, C.c_int64, _I64P, _F32P, _I64P, _U8P]),
     "pcv_searcher_search_distinct": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int, _I64P, _F32P, _INTP, _INTP, _INTP, _U8P]),
+    "pcv_searcher_set_groups": (C.c_int, [_P, _I64P, _I64P, C.c_int64]),
+    "pcv_searcher_clear_groups": (C.c_int, [_P]),
+    "pcv_searcher_get_groups": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
+    "pcv_searcher_group_stats": (C.c_int, [_P, C.POINTER(GroupStats)]),
+    "pcv_searcher_search_grouped": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _I64P, _INTP, _INTP, _INTP, _U8P]),
     "pcv_searcher_find_duplicates": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_last_duplicate_stats": (C.c_int, [_P, C.POINTER(DuplicateStats)]),
     "pcv_searcher_assign": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int64, _INTP, _F32P, _I64P, _I64P, C.POINTER(C.c_int64)]),

@@ -1,5 +1,6 @@
 // corpus.h — launcher interface of the kernels that build and maintain a corpus segment (corpus_kernels.hip): staging, row
-// scales, the screening and mid copies of scan.h, and hiding, updating, removing, viewing and gathering stored items by id.
+// scales, the screening and mid copies of scan.h, and hiding, updating, removing, viewing and gathering stored items by id — and of the group table
+// (grouped_kernels.hip), which shares the id hash.
 #pragma once
 #include "scan.h"
 
@@ -51,6 +52,31 @@ void launch_repack16_rows(hipStream_t st, const float4* blk, const float* scale,
 // ... the mid copy: items are blocks (scale8 != nullptr: every row of each, with the block's scale) or rows; rows >= mid_rows skipped
 void launch_repack_mid(hipStream_t st, const float4* blk, const float* scale, const float* scale8, const uint32_t* items, uint32_t n,
                        uint32_t mid_rows, uint4* mid16, float* scale16, int D4);
+// ---- the group table (pcv_searcher_set_groups; grouped_kernels.hip; DESIGN.md §4 "Grouped results") ----
+// Item id -> group key, resident on the device: keys[slots] and vals[slots] (int64 each), slots a power of two, linear probing from
+// id_hash, kIdEmpty in free slots.  The id kIdEmpty has no slot: its value lives in the head block, beside the two counters.
+struct GroupHead {
+    int64_t entries;        // ids that have an entry (the side slot included)
+    int64_t ids;            // ... and a group >= 0
+    int64_t side_val;       // the group of id kIdEmpty (-1: none)
+    uint32_t side_claim;    // its word of `claim`
+    uint32_t side_present;  // 1: id kIdEmpty has an entry
+};
+constexpr uint32_t kGroupSideSlot = 0xffffffffu;  // slot_of[] of id kIdEmpty
+constexpr uint32_t kGroupBatch = 1u << 22;        // most ids of one upsert or lookup launch (the host feeds a longer batch in order)
+// every slot free, every value -1
+void launch_group_fill(hipStream_t st, int64_t* keys, int64_t* vals, uint64_t slots);
+// Upsert of (ids[i], groups[i]), i < n <= kGroupBatch: of an id that occurs more than once the LAST occurrence is stored, whatever
+// order the atomics land in.  claim[slots] is all 0 before and after; slot_of[n] is scratch.  The table must have n free slots
+// and stay half empty.
+void launch_group_upsert(hipStream_t st, int64_t* keys, int64_t* vals, uint32_t mask, uint32_t* claim, GroupHead* head, const int64_t* ids,
+                         const int64_t* groups, uint32_t n, uint32_t* slot_of);
+// every entry of an old table into a new one (launch_group_fill'ed, at least as large)
+void launch_group_rehash(hipStream_t st, const int64_t* old_keys, const int64_t* old_vals, uint64_t old_slots, int64_t* keys, int64_t* vals,
+                         uint32_t mask);
+// out[i] = group of ids[i], -1 if it has none (keys == nullptr: a table without slots)
+void launch_group_lookup(hipStream_t st, const int64_t* keys, const int64_t* vals, uint32_t mask, const GroupHead* head, const int64_t* ids,
+                         uint32_t n, int64_t* out);
 // ---- updated items (pcv_searcher_update_rows) ----
 // launch_match_ids whose table also carries each id's slot in the batch (vals[h]; empty_slot for kIdEmpty): rows [row0, row1) of
 // a segment whose id is in the batch -> (out_rows[i], out_slots[i]) for the first `cap`, their number -> *out_n (zeroed here)

@@ -251,6 +251,22 @@ struct DistinctArgs {
     double threshold;
 };
 
+// Grouped results (pcv_searcher_search_grouped; DESIGN.md §4 "Grouped results"): the same walk, kMaxK hits a pass, with another
+// relation — a row is kept iff no kept row carries its group key (the searcher's group table, corpus.h).  The walk's record is
+// DistinctRec, with the same meaning of every field.
+struct GroupedArgs {
+    DistinctRec* rec;        // [B]
+    DistinctRec* rec_host;   // [B] pinned host mirror, written after every pass
+    pcv_hit_dev* kept;       // [B][kMaxK] the kept rows, best first, as the pass listed them
+    int64_t* kept_group;     // [B][kMaxK] their group keys (-1: a row without a group)
+    int32_t* collapsed;      // [B][kMaxK] walked rows collapsed into each
+    const int64_t* keys;     // the group table (nullptr: it has no slots — every row is a group of its own)
+    const int64_t* vals;
+    uint32_t mask;
+    int64_t side_val;        // the group of id INT64_MIN, which has no slot (-1: none)
+    int num_results;
+};
+
 // Duplicate pairs (pcv_searcher_find_duplicates; DESIGN.md §4 "Duplicate pairs"): rows against rows.  Rows are named by their
 // number in the launch's block numbering, block * 32 + row of the block ("launch row": the rows behind a segment's last row in its
 // last block have numbers too and take no part); launch rows ascend with the global position.
@@ -411,6 +427,8 @@ void launch_range_thresholds(hipStream_t st, const ScanParams& p, const ScanPara
 void launch_range_select(hipStream_t st, const ScanParams& p, const ScanParams* dp);
 // ---- distinct results (distinct_kernels.hip): walks the p.k hits per query the pass left in p.out ----
 void launch_distinct_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DistinctArgs& a);
+// ---- grouped results (grouped_kernels.hip): likewise, against the group table ----
+void launch_grouped_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const GroupedArgs& a);
 // ---- duplicate pairs (selfjoin_kernels.hip); `p` needs seg, nseg, total_blocks, D, D4 only ----
 float selfjoin_margin(int Dp);  // certified bound on |screening score - canonical cosine| (DESIGN.md §4 "Duplicate pairs")
 void launch_selfjoin_prep(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);

@@ -238,6 +238,21 @@ struct pcv_searcher {
     // records | kept hits | their norms | their counters, on the device and (records after every pass, the rest once) in pinned memory
     DevBuf<uint8_t> d_distinct;
     PinBuf<uint8_t> pin_distinct;
+    // the group table (pcv_searcher_set_groups; corpus.h "the group table"): keys | vals on the device, the head block beside them
+    // and the host's copy of it as of the last set_groups (every one ends with a synchronised download).  A view has none: it
+    // reads its parent's.  The scratch of a set_groups / get_groups call is kept for the next unless it is large.
+    struct Groups {
+        int64_t* keys = nullptr;
+        int64_t* vals = nullptr;
+        uint64_t slots = 0;
+        GroupHead head{0, 0, -1, 0, 0};
+        DevBuf<GroupHead> d_head;
+        PinBuf<GroupHead> pin_head;
+        int32_t rehashes = 0;
+        float last_set_ms = 0.0f;
+        DevBuf<uint32_t> d_claim, d_slot;
+        DevBuf<int64_t> d_batch;
+    } groups;
     pcv_duplicate_stats dup_stats{};  // pcv_searcher_find_duplicates (its buffers live for the call only)
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
     pcv_neighbor_stats nbr_stats{};   // pcv_searcher_neighbors (likewise)
@@ -2310,6 +2325,49 @@ struct DistinctLayout {
     static constexpr size_t total = off_norm + Q * kMaxK * sizeof(double);
 };
 
+// The walk of one group of B queries, shared by the calls that collapse a ranked list (search_distinct, search_grouped): passes of
+// kMaxK hits until every query is finished or `pool` entries are walked, `select` (the call's select step, queued on the stream
+// after each pass) keeping the records `rec` (pinned; `d_rec` on the device) up to date.  -> per query, whether its walk stopped
+// at `pool` unfinished with more of its list to come (decided only if `want_more`).
+template <class Select>
+std::vector<uint8_t> walk_ranked_lists(pcv_searcher* s, const SearchPlan& plan, const float* qs, int B, int pool, DistinctRec* rec,
+                                       DistinctRec* d_rec, bool want_more, Select select) {
+    hipStream_t st = s->ctx->stream;
+    std::vector<CeilRec> ceil;
+    for (int q = 0; q < B; ++q) rec[q] = DistinctRec{0, 0, 0, 0, INFINITY, -1};
+    PCV_HIP(hipMemcpyAsync(d_rec, rec, (size_t)B * sizeof(DistinctRec), hipMemcpyHostToDevice, st));
+    // A query still walking after a pass has walked every hit of every pass so far: `walked` is the same for all of them.
+    bool pending = true;
+    for (int walked = 0; pending && walked < pool; walked += kMaxK) {
+        const int kk = std::min(kMaxK, pool - walked);
+        if (walked > 0) {
+            ceil.resize((size_t)B);
+            std::vector<pcv_hit_dev> last((size_t)B);
+            for (int q = 0; q < B; ++q) last[(size_t)q] = rec[q].flags ? pcv_hit_dev{NAN, -1, -1} : pcv_hit_dev{rec[q].last_score, rec[q].last_pos, -1};
+            next_ceilings(s, qs, B, last.data(), ceil.data());
+        }
+        run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(kk, nullptr, false, nullptr, walked > 0 ? ceil.data() : nullptr));
+        // (the pass block is the pass's to allocate and to grow: its device address is read after the pass, never before)
+        select();
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        pending = false;
+        for (int q = 0; q < B; ++q) pending = pending || rec[q].flags == 0;
+    }
+    // out_more: a walk that stopped at `pool` without its num_results and without seeing its list end.  Whether the list had
+    // another row is one more, short pass under the same kind of ceiling: one hit per query.
+    std::vector<uint8_t> more((size_t)B, 0);
+    if (pending && want_more) {
+        ceil.resize((size_t)B);
+        std::vector<pcv_hit_dev> last((size_t)B);
+        for (int q = 0; q < B; ++q) last[(size_t)q] = rec[q].flags ? pcv_hit_dev{NAN, -1, -1} : pcv_hit_dev{rec[q].last_score, rec[q].last_pos, -1};
+        next_ceilings(s, qs, B, last.data(), ceil.data());
+        run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(1, nullptr, true, nullptr, ceil.data()));
+        for (int q = 0; q < B; ++q) more[(size_t)q] = (rec[q].flags == 0 && s->pin->hits[q].pos >= 0) ? 1 : 0;
+    }
+    return more;
+}
+
 // The ranked list of every query is walked kMaxK hits a pass: the first pass is a plain top-k pass, every later one ranks the rows
 // behind the last hit walked (its ceiling, as in search_hits), and after each the select step (distinct_kernels.hip) walks the
 // pass's lists on the device against the rows kept so far.  What comes back after a pass is one record per query — kept, examined,
@@ -2352,41 +2410,12 @@ void search_distinct(pcv_searcher* s, const float* queries, int n_queries, const
     args.threshold = (double)threshold;
     const pcv_hit_dev* kept = reinterpret_cast<const pcv_hit_dev*>(s->pin_distinct.p + L::off_kept);
     const int32_t* similar = reinterpret_cast<const int32_t*>(s->pin_distinct.p + L::off_sim);
-    std::vector<CeilRec> ceil;
     for (int q0 = 0; q0 < n_queries; q0 += plan.qstep) {
         const int B = std::min(plan.qstep, n_queries - q0);
         const float* qs = queries + (size_t)q0 * s->D;
-        for (int q = 0; q < B; ++q) rec[q] = DistinctRec{0, 0, 0, 0, INFINITY, -1};
-        PCV_HIP(hipMemcpyAsync(args.rec, rec, (size_t)B * sizeof(DistinctRec), hipMemcpyHostToDevice, st));
-        // A query still walking after a pass has walked every hit of every pass so far: `walked` is the same for all of them.
-        bool pending = true;
-        for (int walked = 0; pending && walked < pool; walked += kMaxK) {
-            const int kk = std::min(kMaxK, pool - walked);
-            if (walked > 0) {
-                ceil.resize((size_t)B);
-                std::vector<pcv_hit_dev> last((size_t)B);
-                for (int q = 0; q < B; ++q) last[(size_t)q] = rec[q].flags ? pcv_hit_dev{NAN, -1, -1} : pcv_hit_dev{rec[q].last_score, rec[q].last_pos, -1};
-                next_ceilings(s, qs, B, last.data(), ceil.data());
-            }
-            run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(kk, nullptr, false, nullptr, walked > 0 ? ceil.data() : nullptr));
-            // (the pass block is the pass's to allocate and to grow: its device address is read after the pass, never before)
+        const std::vector<uint8_t> more = walk_ranked_lists(s, plan, qs, B, pool, rec, args.rec, out_more != nullptr, [&] {
             launch_distinct_select(st, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
-            PCV_HIP(hipStreamSynchronize(st));
-            PCV_HIP(hipGetLastError());
-            pending = false;
-            for (int q = 0; q < B; ++q) pending = pending || rec[q].flags == 0;
-        }
-        // out_more: a walk that stopped at `pool` without its num_results and without seeing its list end.  Whether the list had
-        // another row is one more, short pass under the same kind of ceiling: one hit per query.
-        std::vector<uint8_t> more((size_t)B, 0);
-        if (pending && out_more) {
-            ceil.resize((size_t)B);
-            std::vector<pcv_hit_dev> last((size_t)B);
-            for (int q = 0; q < B; ++q) last[(size_t)q] = rec[q].flags ? pcv_hit_dev{NAN, -1, -1} : pcv_hit_dev{rec[q].last_score, rec[q].last_pos, -1};
-            next_ceilings(s, qs, B, last.data(), ceil.data());
-            run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(1, nullptr, true, nullptr, ceil.data()));
-            for (int q = 0; q < B; ++q) more[(size_t)q] = (rec[q].flags == 0 && s->pin->hits[q].pos >= 0) ? 1 : 0;
-        }
+        });
         PCV_HIP(hipMemcpyAsync(s->pin_distinct.p + L::off_kept, s->d_distinct.p + L::off_kept, L::off_norm - L::off_kept, hipMemcpyDeviceToHost, st));
         PCV_HIP(hipStreamSynchronize(st));
         for (int q = 0; q < B; ++q) {
@@ -2397,6 +2426,203 @@ void search_distinct(pcv_searcher* s, const float* queries, int n_queries, const
                 if (out_ids) out_ids[o + j] = h.id;
                 if (out_scores) out_scores[o + j] = reported_score(s->metric, s->D, h.score);
                 if (out_similar) out_similar[o + j] = similar[(size_t)q * kMaxK + j];
+            }
+            blank(q0 + q, n);
+            if (out_counts) out_counts[q0 + q] = n;
+            if (out_examined) out_examined[q0 + q] = (int32_t)rec[q].examined;
+            if (out_more) out_more[q0 + q] = more[(size_t)q];
+        }
+    }
+}
+
+// ---- grouped results (pcv_searcher_set_groups / _search_grouped; DESIGN.md §4 "Grouped results") ----
+constexpr int64_t kMaxGroupEntries = (int64_t)1 << 30;
+constexpr uint64_t kMinGroupSlots = 1024;
+constexpr size_t kGroupKeptBytes = (size_t)64 << 20;  // scratch of a set_groups / get_groups call beyond this is given back
+
+// The table of `s` gets `slots` slots (a power of two, more than it has): the entries move by a rehash on the device.  If the
+// allocation fails the old table stays as it is.
+void grow_groups(pcv_searcher* s, uint64_t slots) {
+    pcv_searcher::Groups& t = s->groups;
+    hipStream_t st = s->ctx->stream;
+    int64_t *keys = nullptr, *vals = nullptr;
+    const hipError_t e = alloc_with_scales(s->fail_copy_alloc, &keys, slots * sizeof(int64_t), &vals, slots * sizeof(int64_t));
+    if (e != hipSuccess)
+        PCV_FAIL(PCV_ERR_DEVICE, "set_groups: hipMalloc of %.2f GB for a group table of %llu slots failed: %s (the table is unchanged)",
+                 slots * 16 / 1e9, (unsigned long long)slots, hipGetErrorString(e));
+    try {
+        launch_group_fill(st, keys, vals, slots);
+        launch_group_rehash(st, t.keys, t.vals, t.slots, keys, vals, (uint32_t)(slots - 1));
+        PCV_HIP(hipStreamSynchronize(st));
+    } catch (...) {
+        (void)hipFree(keys);
+        (void)hipFree(vals);
+        throw;
+    }
+    if (t.keys) (void)hipFree(t.keys);
+    if (t.vals) (void)hipFree(t.vals);
+    if (t.slots > 0) t.rehashes += 1;
+    t.keys = keys;
+    t.vals = vals;
+    t.slots = slots;
+}
+
+void trim_group_scratch(pcv_searcher* s) {
+    pcv_searcher::Groups& t = s->groups;
+    if (t.d_claim.n * sizeof(uint32_t) > kGroupKeptBytes) t.d_claim.release();
+    if (t.d_slot.n * sizeof(uint32_t) > kGroupKeptBytes) t.d_slot.release();
+    if (t.d_batch.n * sizeof(int64_t) > kGroupKeptBytes) t.d_batch.release();
+}
+
+// The upsert of a batch (s->mu held, s no view, the arguments checked): one growth decision, then the batch kGroupBatch ids at a
+// time, in order — a later occurrence of an id overrides an earlier one inside a launch (launch_group_upsert) and across launches.
+void set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int64_t n) {
+    pcv_searcher::Groups& t = s->groups;
+    if (n == 0) return;
+    if (t.head.entries + n > kMaxGroupEntries)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED, "set_groups: %lld entries and %lld ids more exceed the table's limit of 2^30 entries",
+                 (long long)t.head.entries, (long long)n);
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    if (!t.d_head.p) {
+        t.pin_head.ensure(1);
+        t.d_head.ensure(1);
+        *t.pin_head.p = t.head;
+        PCV_HIP(hipMemcpyAsync(t.d_head.p, t.pin_head.p, sizeof(GroupHead), hipMemcpyHostToDevice, st));
+    }
+    hipEvent_t ev[2] = {nullptr, nullptr};  // (the call's own: a searcher without rows has none yet)
+    const auto drop_events = at_exit([&] {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    });
+    for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
+    PCV_HIP(hipEventRecord(ev[0], st));
+    uint64_t slots = std::max(t.slots, kMinGroupSlots);
+    while (slots < 2 * (uint64_t)(t.head.entries + n)) slots *= 2;
+    if (slots != t.slots) grow_groups(s, slots);
+    auto trim = at_exit([&] { trim_group_scratch(s); });
+    t.d_claim.ensure(t.slots);
+    PCV_HIP(hipMemsetAsync(t.d_claim.p, 0, t.slots * sizeof(uint32_t), st));
+    const size_t m_most = (size_t)std::min<int64_t>(n, kGroupBatch);
+    t.d_batch.ensure(2 * m_most);
+    t.d_slot.ensure(m_most);
+    for (int64_t i0 = 0; i0 < n; i0 += kGroupBatch) {
+        const size_t m = (size_t)std::min<int64_t>(kGroupBatch, n - i0);
+        PCV_HIP(hipMemcpyAsync(t.d_batch.p, ids + i0, m * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemcpyAsync(t.d_batch.p + m_most, groups + i0, m * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        launch_group_upsert(st, t.keys, t.vals, (uint32_t)(t.slots - 1), t.d_claim.p, t.d_head.p, t.d_batch.p, t.d_batch.p + m_most,
+                            (uint32_t)m, t.d_slot.p);
+    }
+    PCV_HIP(hipMemcpyAsync(t.pin_head.p, t.d_head.p, sizeof(GroupHead), hipMemcpyDeviceToHost, st));
+    PCV_HIP(hipEventRecord(ev[1], st));
+    PCV_HIP(hipStreamSynchronize(st));
+    t.head = *t.pin_head.p;
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+    t.last_set_ms = ms;
+}
+
+// The searcher is as created: no table, every counter 0.
+void clear_groups(pcv_searcher* s) {
+    pcv_searcher::Groups& t = s->groups;
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    PCV_HIP(hipStreamSynchronize(s->ctx->stream));
+    if (t.keys) (void)hipFree(t.keys);
+    if (t.vals) (void)hipFree(t.vals);
+    t.keys = t.vals = nullptr;
+    t.slots = 0;
+    t.head = GroupHead{0, 0, -1, 0, 0};
+    t.d_head.release();  // (the next set_groups uploads a fresh one)
+    t.d_claim.release();
+    t.rehashes = 0;
+    t.last_set_ms = 0.0f;
+}
+
+// out[i] = group of ids[i] in the table of `owner` (locked by the caller); the scratch is owner's too.
+void get_groups(pcv_searcher* owner, const int64_t* ids, int64_t n, int64_t* out) {
+    pcv_searcher::Groups& t = owner->groups;
+    if (!t.d_head.p) {  // nothing was ever set
+        for (int64_t i = 0; i < n; ++i) out[i] = PCV_NO_GROUP;
+        return;
+    }
+    PCV_HIP(hipSetDevice(owner->ctx->device));
+    hipStream_t st = owner->ctx->stream;
+    auto trim = at_exit([&] { trim_group_scratch(owner); });
+    const size_t m_most = (size_t)std::min<int64_t>(n, kGroupBatch);
+    t.d_batch.ensure(2 * m_most);
+    for (int64_t i0 = 0; i0 < n; i0 += kGroupBatch) {
+        const size_t m = (size_t)std::min<int64_t>(kGroupBatch, n - i0);
+        PCV_HIP(hipMemcpyAsync(t.d_batch.p, ids + i0, m * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        launch_group_lookup(st, t.keys, t.vals, (uint32_t)(t.slots ? t.slots - 1 : 0), t.d_head.p, t.d_batch.p, (uint32_t)m, t.d_batch.p + m_most);
+        PCV_HIP(hipMemcpyAsync(out + i0, t.d_batch.p + m_most, m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+    }
+}
+
+// search_distinct's walk (walk_ranked_lists) with membership as the relation: after each pass grouped_select_kernel looks the
+// hits' ids up in the group table of `owner` (s itself, or the parent of a view; locked by the caller), keeps the first row of
+// every group not kept yet and counts the others for the kept row of their group.  The state block is the one search_distinct
+// uses, with the kept rows' group keys where that call has their norms — and these come down with the kept rows.
+void search_grouped(pcv_searcher* s, const pcv_searcher* owner, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                    int k, int pool, int64_t* out_ids, float* out_scores, int64_t* out_groups, int32_t* out_counts, int32_t* out_collapsed,
+                    int32_t* out_examined, uint8_t* out_more) {
+    check_search_args(s, queries, n_queries, k, "search_grouped");
+    s->stats = pcv_scan_stats{};  // (also when the kernel is refused)
+    const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries);
+    auto blank = [&](int q, int from) {
+        for (int j = from; j < k; ++j) {
+            if (out_ids) out_ids[(size_t)q * k + j] = -1;
+            if (out_scores) out_scores[(size_t)q * k + j] = NAN;
+            if (out_groups) out_groups[(size_t)q * k + j] = PCV_NO_GROUP;
+            if (out_collapsed) out_collapsed[(size_t)q * k + j] = 0;
+        }
+    };
+    if (!open_search(s, plan)) {
+        for (int q = 0; q < n_queries; ++q) {
+            blank(q, 0);
+            if (out_counts) out_counts[q] = 0;
+            if (out_examined) out_examined[q] = 0;
+            if (out_more) out_more[q] = 0;
+        }
+        return;
+    }
+    using L = DistinctLayout;
+    static_assert(sizeof(int64_t) == sizeof(double), "the group keys take the place of the norms");
+    hipStream_t st = s->ctx->stream;
+    s->d_distinct.ensure(L::total);
+    s->pin_distinct.ensure(L::total);
+    DistinctRec* rec = reinterpret_cast<DistinctRec*>(s->pin_distinct.p + L::off_rec);
+    GroupedArgs args{};
+    args.rec = reinterpret_cast<DistinctRec*>(s->d_distinct.p + L::off_rec);
+    args.rec_host = rec;
+    args.kept = reinterpret_cast<pcv_hit_dev*>(s->d_distinct.p + L::off_kept);
+    args.collapsed = reinterpret_cast<int32_t*>(s->d_distinct.p + L::off_sim);
+    args.kept_group = reinterpret_cast<int64_t*>(s->d_distinct.p + L::off_norm);
+    args.keys = owner->groups.slots ? owner->groups.keys : nullptr;
+    args.vals = owner->groups.vals;
+    args.mask = owner->groups.slots ? (uint32_t)(owner->groups.slots - 1) : 0;
+    args.side_val = owner->groups.head.side_val;
+    args.num_results = k;
+    const pcv_hit_dev* kept = reinterpret_cast<const pcv_hit_dev*>(s->pin_distinct.p + L::off_kept);
+    const int32_t* collapsed = reinterpret_cast<const int32_t*>(s->pin_distinct.p + L::off_sim);
+    const int64_t* kept_group = reinterpret_cast<const int64_t*>(s->pin_distinct.p + L::off_norm);
+    for (int q0 = 0; q0 < n_queries; q0 += plan.qstep) {
+        const int B = std::min(plan.qstep, n_queries - q0);
+        const float* qs = queries + (size_t)q0 * s->D;
+        const std::vector<uint8_t> more = walk_ranked_lists(s, plan, qs, B, pool, rec, args.rec, out_more != nullptr, [&] {
+            launch_grouped_select(st, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
+        });
+        PCV_HIP(hipMemcpyAsync(s->pin_distinct.p + L::off_kept, s->d_distinct.p + L::off_kept, L::total - L::off_kept, hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        for (int q = 0; q < B; ++q) {
+            const int n = (int)rec[q].kept;
+            const size_t o = (size_t)(q0 + q) * k;
+            for (int j = 0; j < n; ++j) {
+                const pcv_hit_dev& h = kept[(size_t)q * kMaxK + j];
+                if (out_ids) out_ids[o + j] = h.id;
+                if (out_scores) out_scores[o + j] = reported_score(s->metric, s->D, h.score);
+                if (out_groups) out_groups[o + j] = kept_group[(size_t)q * kMaxK + j];
+                if (out_collapsed) out_collapsed[o + j] = collapsed[(size_t)q * kMaxK + j];
             }
             blank(q0 + q, n);
             if (out_counts) out_counts[q0 + q] = n;
@@ -3492,6 +3718,8 @@ void destroy_searcher(pcv_searcher* s) {
     }
     for (auto& src : s->sources)
         for (auto& g : src.segs) free_segment(g);
+    if (s->groups.keys) (void)hipFree(s->groups.keys);
+    if (s->groups.vals) (void)hipFree(s->groups.vals);
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
     if (s->d_max_norm_bits) (void)hipFree(s->d_max_norm_bits);
     for (auto& e : s->ev)
@@ -4092,6 +4320,72 @@ pcv_status pcv_searcher_search_distinct(pcv_searcher* s, const float* queries, i
         sync_view(s);
         search_distinct(s, queries, n_queries, source_ids, n_sources, num_results, threshold, pool, out_ids, out_scores, out_counts, out_similar,
                         out_examined, out_more);
+    });
+}
+
+pcv_status pcv_searcher_set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int64_t n) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "set_groups: searcher is NULL");
+        PCV_REQUIRE(n >= 0 && ((ids != nullptr && groups != nullptr) || n == 0), "set_groups: bad lists (NULL with n > 0, or n < 0)");
+        for (int64_t i = 0; i < n; ++i)
+            PCV_REQUIRE(groups[i] >= PCV_NO_GROUP, "set_groups: group %lld of id %lld (element %lld) is negative and not PCV_NO_GROUP",
+                        (long long)groups[i], (long long)ids[i], (long long)i);
+        refuse_view(s, "set_groups");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "set_groups: a queued pass has not been collected");
+        set_groups(s, ids, groups, n);
+    });
+}
+
+pcv_status pcv_searcher_clear_groups(pcv_searcher* s) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "clear_groups: searcher is NULL");
+        refuse_view(s, "clear_groups");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "clear_groups: a queued pass has not been collected");
+        clear_groups(s);
+    });
+}
+
+pcv_status pcv_searcher_get_groups(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_groups) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "get_groups: searcher is NULL");
+        PCV_REQUIRE(n >= 0 && ((ids != nullptr && out_groups != nullptr) || n == 0), "get_groups: bad lists (NULL with n > 0, or n < 0)");
+        pcv_searcher* owner = s->view_parent ? s->view_parent : s;
+        std::lock_guard<std::mutex> lk(owner->mu);
+        PCV_REQUIRE(!owner->pending.active, "get_groups: a queued pass has not been collected");
+        get_groups(owner, ids, n, out_groups);
+    });
+}
+
+pcv_status pcv_searcher_group_stats(pcv_searcher* s, pcv_group_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "group_stats: NULL argument");
+        pcv_searcher* owner = s->view_parent ? s->view_parent : s;
+        std::lock_guard<std::mutex> lk(owner->mu);
+        const pcv_searcher::Groups& t = owner->groups;
+        *out = pcv_group_stats{t.head.ids, t.head.entries, (int64_t)t.slots, t.rehashes, t.last_set_ms};
+    });
+}
+
+pcv_status pcv_searcher_search_grouped(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                       int num_results, int pool, int64_t* out_ids, float* out_scores, int64_t* out_groups,
+                                       int32_t* out_counts, int32_t* out_collapsed, int32_t* out_examined, uint8_t* out_more) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "search_grouped: searcher is NULL");
+        PCV_REQUIRE(queries != nullptr && n_queries > 0, "search_grouped: no queries");
+        PCV_REQUIRE(num_results >= 1 && num_results <= (int)PCV_MAX_RESULTS, "search_grouped: num_results %d outside [1,%d]", num_results,
+                    (int)PCV_MAX_RESULTS);
+        PCV_REQUIRE(pool >= num_results && pool <= (int)PCV_MAX_GROUPED_POOL, "search_grouped: pool %d outside [num_results = %d, %d]", pool,
+                    num_results, (int)PCV_MAX_GROUPED_POOL);
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "search_grouped: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        // (a view reads its parent's table: the parent stays locked while the kernels may follow its pointers)
+        std::unique_lock<std::mutex> plk;
+        if (s->view_parent) plk = std::unique_lock<std::mutex>(s->view_parent->mu);
+        search_grouped(s, s->view_parent ? s->view_parent : s, queries, n_queries, source_ids, n_sources, num_results, pool, out_ids,
+                       out_scores, out_groups, out_counts, out_collapsed, out_examined, out_more);
     });
 }
 

@@ -13,6 +13,8 @@ from . import _ffi
 from .context import Context
 
 PCV_MAX_DISTINCT_POOL = 4096  # include/perceive_hip.h
+PCV_MAX_GROUPED_POOL = 4096  # include/perceive_hip.h
+PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_of / search_grouped
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
 
@@ -417,6 +419,79 @@ class Searcher:
         if not found[0]:
             raise KeyError("Item not found")
         return self.search_distinct_vector(sources, num_results, vec[0], threshold, pool)
+
+    # ---- grouped results (pcv_searcher_set_groups / _search_grouped) ---------------------------------
+    # The exact top-k collapsed by a stored group key per item: "the k closest documents" over a corpus of chunk rows.
+    def set_groups(self, ids, groups):
+        """Upsert of the group table: item ids[i] belongs to group groups[i] (any int64 >= 0; PCV_NO_GROUP ungroups the id).  Of an
+        id that occurs more than once the last occurrence holds.  Keyed by id: entries survive remove_items, clear_source and
+        replace_source.  A view is read-only (PcvError): set the groups on its parent."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
+        groups = np.ascontiguousarray(groups, dtype=np.int64).ravel()
+        if ids.shape != groups.shape:
+            raise ValueError("ids and groups must have the same length")
+        _ffi.check(_ffi.lib().pcv_searcher_set_groups(self._handle, _ffi.i64p(ids), _ffi.i64p(groups), ids.shape[0]))
+
+    def clear_groups(self):
+        """Forget every group: the table is released and its counters start from 0."""
+        _ffi.check(_ffi.lib().pcv_searcher_clear_groups(self._handle))
+
+    def groups_of(self, ids):
+        """ids [n] -> groups [n] int64, PCV_NO_GROUP for an id without a group (a view answers from its parent's table)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
+        out = np.full(ids.shape[0], PCV_NO_GROUP, dtype=np.int64)
+        _ffi.check(_ffi.lib().pcv_searcher_get_groups(self._handle, _ffi.i64p(ids), ids.shape[0], _ffi.i64p(out)))
+        return out
+
+    def group_stats(self):
+        """{"ids": ids with a group, "entries": occupied slots, "slots": capacity, "rehashes": growths, "last_set_ms": device time of
+        the last set_groups} (pcv_group_stats)."""
+        st = _ffi.GroupStats()
+        _ffi.check(_ffi.lib().pcv_searcher_group_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.GroupStats._fields_}
+
+    def search_grouped(self, sources, num_results, vectors, pool=None):
+        """The ranked list of search_vectors walked best first, a row kept iff no kept row has its group (set_groups; a row without
+        a group is a group of its own); at most `pool` entries are examined (default min(PCV_MAX_GROUPED_POOL, max(128,
+        8 * num_results))).  vectors [B, dim] -> (ids [B, k] int64, scores [B, k] f32, groups [B, k] int64: PCV_NO_GROUP for a
+        row without one, counts [B] int32, collapsed [B, k] int32: examined rows collapsed into each hit, examined [B] int32,
+        more [B] bool: the walk stopped at `pool` short of num_results although the list had more rows).  Ids and scores are
+        those search_vectors returns for the same rows."""
+        q = np.ascontiguousarray(vectors, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [B, {self.dim}]")
+        B, k = q.shape[0], int(num_results)
+        if pool is None:
+            pool = min(PCV_MAX_GROUPED_POOL, max(128, 8 * k))
+        ids = np.full((B, max(k, 0)), -1, dtype=np.int64)
+        scores = np.full((B, max(k, 0)), np.nan, dtype=np.float32)
+        groups = np.full((B, max(k, 0)), PCV_NO_GROUP, dtype=np.int64)
+        collapsed = np.zeros((B, max(k, 0)), dtype=np.int32)
+        counts = np.zeros(max(B, 1), dtype=np.int32)
+        examined = np.zeros(max(B, 1), dtype=np.int32)
+        more = np.zeros(max(B, 1), dtype=np.uint8)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_grouped(
+                self._handle, _ffi.f32p(q), B, src, nsrc, k, int(pool), _ffi.i64p(ids), _ffi.f32p(scores), _ffi.i64p(groups),
+                _ffi.i32p(counts), _ffi.i32p(collapsed), _ffi.i32p(examined), _ffi.u8p(more),
+            )
+        )
+        return ids, scores, groups, counts[:B], collapsed, examined[:B], more[:B].astype(bool)
+
+    def search_grouped_vector(self, sources, num_results, vector, pool=None):
+        """search_grouped for one vector -> list[(SearchItem, group, collapsed)]: the best member of each of the closest groups."""
+        ids, scores, groups, counts, collapsed, _ex, _more = self.search_grouped(
+            sources, num_results, np.asarray(vector, dtype=np.float32)[None, :], pool)
+        return [(SearchItem(int(ids[0, j]), float(scores[0, j])), int(groups[0, j]), int(collapsed[0, j])) for j in range(int(counts[0]))]
+
+    def search_grouped_like_item(self, sources, num_results, item_id, pool=None):
+        """The groups closest to the stored embedding of `item_id` (like_queries + search_grouped); as in search_like_item the item
+        itself comes first.  KeyError("Item not found") when no row carries the id."""
+        vec, found, _members = self.like_queries([[int(item_id)]])
+        if not found[0]:
+            raise KeyError("Item not found")
+        return self.search_grouped_vector(sources, num_results, vec[0], pool)
 
     # ---- duplicate pairs (pcv_searcher_find_duplicates) ----------------------------------------------
     # The exact self-join of the corpus: what search_distinct collapses per query, found once for remove_items / hide_items.

@@ -394,6 +394,64 @@ impl Searcher {
         (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, similar[i])).collect()
     }
 
+    /// The group table (`pcv_searcher_set_groups`): item `ids[i]` belongs to group `groups[i]` (any i64 >= 0; `ffi::PCV_NO_GROUP`
+    /// ungroups the id); of an id that occurs more than once the last occurrence holds.  The table is keyed by item id and lives on
+    /// the device: it survives `remove_items` and a rebuilt source.  A chunking ingester calls this after it has added the rows.
+    pub fn set_groups(&mut self, ids: &[i64], groups: &[i64]) {
+        assert_eq!(ids.len(), groups.len(), "set_groups: {} ids, {} groups", ids.len(), groups.len());
+        if self.handle.is_null() || ids.is_empty() {
+            return;
+        }
+        hip::check(unsafe { ffi::pcv_searcher_set_groups(self.handle, ids.as_ptr(), groups.as_ptr(), ids.len() as i64) })
+            .expect("set_groups failed");
+    }
+
+    /// Grouped results (`pcv_searcher_search_grouped`): the ranked list of `search_vector` walked best first on the device, an item
+    /// kept only if no kept item has its group (`set_groups`; an item without a group is a group of its own) — the k closest
+    /// documents of an index of chunks.  At most `pool` entries of the list are examined (`None`: min(PCV_MAX_GROUPED_POOL,
+    /// max(128, 8 * num_results))).  Each hit comes with its group key (`ffi::PCV_NO_GROUP`: none) and the number of examined
+    /// items collapsed into it.
+    pub fn search_vector_grouped(
+        &self,
+        sources: &[i64],
+        num_results: usize,
+        vector: Vec<f32>,
+        pool: Option<usize>,
+    ) -> Vec<(SearchItem, i64, i32)> {
+        if self.handle.is_null() || num_results == 0 {
+            return Vec::new();
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        assert_eq!(vector.len(), dim as usize, "search_vector_grouped: the query has {} values, the index is {}-d", vector.len(), dim);
+        let pool = pool.unwrap_or_else(|| (ffi::PCV_MAX_GROUPED_POOL as usize).min((8 * num_results).max(128)));
+        let mut ids = vec![-1i64; num_results];
+        let mut scores = vec![f32::NAN; num_results];
+        let mut groups = vec![ffi::PCV_NO_GROUP; num_results];
+        let mut collapsed = vec![0i32; num_results];
+        let mut count: i32 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_grouped(
+                self.handle,
+                vector.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                num_results as i32,
+                pool as i32,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                groups.as_mut_ptr(),
+                &mut count,
+                collapsed.as_mut_ptr(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        })
+        .expect("search_grouped failed");
+        (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, groups[i], collapsed[i])).collect()
+    }
+
     /// Duplicate pairs (`pcv_searcher_find_duplicates`): every pair of searchable items of `sources` whose cosine is at or above
     /// `threshold`, best first, at most `max_pairs` of them (clamped to PCV_MAX_DUPLICATE_PAIRS) — the same page under several
     /// URLs, found once for the whole index.  Returns the pairs as (id of the item stored first, id of the other, cosine) and the

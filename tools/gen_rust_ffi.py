@@ -18,7 +18,7 @@ SCALARS = {
     "pcv_ctx": "pcv_ctx", "pcv_searcher": "pcv_searcher", "pcv_model": "pcv_model", "pcv_tokenizer": "pcv_tokenizer",
     "pcv_comm": "pcv_comm", "pcv_hit": "pcv_hit", "pcv_scan_stats": "pcv_scan_stats", "pcv_model_desc": "pcv_model_desc",
     "pcv_encode_stats": "pcv_encode_stats", "pcv_duplicate_stats": "pcv_duplicate_stats",
-    "pcv_assign_stats": "pcv_assign_stats", "pcv_neighbor_stats": "pcv_neighbor_stats",
+    "pcv_assign_stats": "pcv_assign_stats", "pcv_neighbor_stats": "pcv_neighbor_stats", "pcv_group_stats": "pcv_group_stats",
 }
 
 
@@ -126,6 +126,8 @@ def main():
         lines.append(f"pub const {name}: c_int = {value};")
     for m in re.finditer(r"#define\s+(PCV_\w+)\s+INT64_MIN\b", strip_comments(text)):
         lines.append(f"pub const {m.group(1)}: i64 = i64::MIN;")
+    for m in re.finditer(r"#define\s+(PCV_\w+)\s+\((-?\d+)\)", strip_comments(text)):  # (an id or a group key: 64 bits)
+        lines.append(f"pub const {m.group(1)}: i64 = {m.group(2)};")
     lines.append("")
     for ret, name, params in callbacks(text):
         SCALARS[name] = name
