@@ -284,6 +284,34 @@ inline NeighborTable neighbors_handle(pcv_searcher* h, const std::vector<int64_t
     return r;
 }
 
+// Searcher::seeds / SearcherView::seeds (pcv_searcher_seeds): up to k items that cover `sources`, in the order they were picked —
+// the init of kmeans (k-means++), or a representative sample with its covering radii (farthest first).
+enum class SeedMethod { Farthest = PCV_SEED_FARTHEST, KMeansPP = PCV_SEED_KMEANSPP };
+struct SeedItems {
+    std::vector<int64_t> ids;        // [n], n <= k: the picks stop when no row is left uncovered
+    std::vector<int64_t> positions;  // [n] global positions
+    std::vector<int64_t> totals;     // [n] the potential before each pick, in units of 2^-32
+    std::vector<float> cover;        // [n] the pick's largest cosine with the seeds before it; NaN at step 0
+};
+inline SeedItems seeds_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t k, SeedMethod method, uint64_t seed,
+                              std::optional<int64_t> first_id) {
+    SeedItems r;
+    if (sources.empty() || k == 0) return r;  // `sources.contains(..)` matches nothing
+    r.ids.resize(k);
+    r.positions.resize(k);
+    r.totals.resize(k);
+    r.cover.resize(k);
+    int32_t n = 0;
+    const int64_t first = first_id.value_or(0);
+    check(pcv_searcher_seeds(h, sources.data(), (int)sources.size(), (int)k, (int)method, seed, first_id ? &first : nullptr, r.ids.data(),
+                             r.positions.data(), r.totals.data(), r.cover.data(), &n));
+    r.ids.resize((size_t)n);
+    r.positions.resize((size_t)n);
+    r.totals.resize((size_t)n);
+    r.cover.resize((size_t)n);
+    return r;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -349,6 +377,16 @@ public:
     pcv_assign_stats last_assign_stats() const {
         pcv_assign_stats st;
         check(pcv_searcher_last_assign_stats(h_, &st));
+        return st;
+    }
+    // up to k seed items of the view (seeds_handle)
+    SeedItems seeds(const std::vector<int64_t>& sources, size_t k, SeedMethod method = SeedMethod::KMeansPP, uint64_t seed = 0,
+                    std::optional<int64_t> first_id = std::nullopt) const {
+        return seeds_handle(h_, sources, k, method, seed, first_id);
+    }
+    pcv_seed_stats last_seed_stats() const {
+        pcv_seed_stats st;
+        check(pcv_searcher_last_seed_stats(h_, &st));
         return st;
     }
     // the k nearest other items of every item of the view (neighbors_handle)
@@ -481,6 +519,16 @@ public:
     pcv_assign_stats last_assign_stats() const {
         pcv_assign_stats st;
         check(pcv_searcher_last_assign_stats(h_, &st));
+        return st;
+    }
+    // up to k seed items, picked on the device (seeds_handle)
+    SeedItems seeds(const std::vector<int64_t>& sources, size_t k, SeedMethod method = SeedMethod::KMeansPP, uint64_t seed = 0,
+                    std::optional<int64_t> first_id = std::nullopt) const {
+        return seeds_handle(h_, sources, k, method, seed, first_id);
+    }
+    pcv_seed_stats last_seed_stats() const {
+        pcv_seed_stats st;
+        check(pcv_searcher_last_seed_stats(h_, &st));
         return st;
     }
     // the k nearest other items of every item, found once on the device (neighbors_handle)

@@ -580,8 +580,8 @@ pcv_status pcv_searcher_label_sums(pcv_searcher* s, const int64_t* source_ids, i
  *   out_iters     updates made (may be NULL);   out_moved  [max_iters + 1], entries 0 .. *out_iters filled (may be NULL)
  * max_iters = 0 is pcv_searcher_assign with the cosine metric.  The labels stay on the device between the steps; per update only the
  * K x dim sums come to the host, where the centroids are formed.  Errors as pcv_searcher_assign, plus max_iters < 0 and a NULL init
- * or out_centroids (PCV_ERR_INVALID) and a label with more than 2^30 members (PCV_ERR_UNSUPPORTED).  Not in scope: seeding
- * (k-means++), a sharded form, device-resident output. */
+ * or out_centroids (PCV_ERR_INVALID) and a label with more than 2^30 members (PCV_ERR_UNSUPPORTED).  init comes from the caller, or from
+ * pcv_searcher_seeds (k-means++) through pcv_searcher_like_queries.  Not in scope: a sharded form, device-resident output. */
 pcv_status pcv_searcher_kmeans(pcv_searcher* s, const float* init, int n_labels, int max_iters, const int64_t* source_ids, int n_sources,
                                int64_t capacity, float* out_centroids, int32_t* out_label, float* out_score, int64_t* out_ids,
                                int64_t* out_counts, int32_t* out_iters, int64_t* out_moved, int64_t* out_n);
@@ -647,6 +647,61 @@ typedef struct pcv_neighbor_stats {
     float select_ms;
 } pcv_neighbor_stats;
 pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats* out);
+
+/* Seed items: k stored items that cover the corpus, picked one after the other where the rows live — the init pcv_searcher_kmeans
+ * asks for (k-means++), or a representative sample whose covering radii tell how many topics a library holds (farthest first).
+ * The rows concerned are those of the selected segments in global position order, as in pcv_searcher_neighbors; source_ids == NULL
+ * means all sources, an empty list selects nothing; a view seeds its own rows (and numbers positions from 0, in its parent's
+ * order).  A row TAKES PART under exactly the rules of pcv_searcher_neighbors / _find_duplicates: a pcv_searcher_search with the same
+ * filter could return it (scale != 0, not hidden) and it has a cosine (canonical |x|^2 in [2^-126, inf)).  c(r, s) is the canonical
+ * cosine of two stored f32 rows — f64, products exact, sums in feature order — for BOTH metrics.
+ *   cover_j(r)   the largest c(r, s) over the seeds s_0 .. s_{j-1} picked so far (undefined before the first)
+ *   w_0(r) = 1;  w_j(r) = (int64) rint(max(0, 1 - cover_j(r)) * 2^32), ties to even, for j >= 1: an integer in [0, 2^33]; a seed's own
+ *                weight is 0 (c(r, r) is within 2^-51 of 1)
+ *   T_j          the sum of w_j over the participating rows — exact, the addition is in integers, whatever its order
+ * Step j = 0 .. k-1: if T_j == 0 the call stops with *out_count = j (every row left points the way of some seed, or there are no
+ * rows).  Otherwise
+ *   PCV_SEED_FARTHEST  picks the participating row with the largest w_j, ties to the lower global position (step 0: the first
+ *                      participating row);
+ *   PCV_SEED_KMEANSPP  draws t = pcv_seed_draw(seed, j, T_j) and picks the first row by global position whose inclusive prefix sum
+ *                      of w_j exceeds t: row r with probability w_j(r) / T_j.
+ * first_id (may be NULL): step 0 picks the first participating row by position that carries this item id instead; if none does the
+ * call fails with PCV_ERR_INVALID and writes no output.
+ *   k              1 .. PCV_MAX_SEEDS
+ *   out_ids        [k] the seeds' item ids; unused slots -1
+ *   out_positions  [k] their global positions; unused slots -1
+ *   out_totals     [k] T_j, the potential before pick j in units of 2^-32; unused slots 0
+ *   out_cover      [k] (float)cover_j(s_j), NaN at step 0 and in unused slots; under the farthest rule 1 - out_cover[j] is the covering
+ *                  radius the first j seeds leave
+ *   out_count      steps taken
+ * The result is a pure function of rows, filter, k, method, seed and first id: it does not depend on which screening copies exist,
+ * nor on pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity.  The call reads the f32 rows and touches no pass state
+ * (DESIGN.md §4 "Seed items"); everything it allocates on the device — 20 bytes per row and 24 per 256 rows — is given back when it
+ * returns.  A NULL searcher or output, k or method out of range give PCV_ERR_INVALID before the handle is looked at; a searcher with
+ * pending rows fails as in pcv_searcher_search.  More than 2^30 participating rows give PCV_ERR_UNSUPPORTED (the int64 potential).
+ * Not in scope: a sharded searcher (pcv_searcher_set_shard_offset != 0 or a pcv_comm) — PCV_ERR_INVALID — and device-resident output. */
+enum { PCV_SEED_FARTHEST = 0, PCV_SEED_KMEANSPP = 1 };
+enum { PCV_MAX_SEEDS = 4096 };
+pcv_status pcv_searcher_seeds(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int method, uint64_t seed,
+                              const int64_t* first_id, int64_t* out_ids, int64_t* out_positions, int64_t* out_totals,
+                              float* out_cover, int32_t* out_count);
+
+/* Counters of the most recent pcv_searcher_seeds on this handle. */
+typedef struct pcv_seed_stats {
+    int64_t rows;           /* rows of the selected segments (those taking no part included)              */
+    int64_t participating;  /* rows that take part (T_0)                                                  */
+    int32_t steps;          /* seeds picked                                                               */
+    int32_t method;
+    float prep_ms;          /* hipEvent times: the norms (selfjoin_prep_kernel), then every cover and pick */
+    float steps_ms;
+} pcv_seed_stats;
+pcv_status pcv_searcher_last_seed_stats(pcv_searcher* s, pcv_seed_stats* out);
+
+/* The draw of step `step` (host only: needs no context and no GPU; the device calls the same function):
+ * floor(z * total / 2^64) with z the splitmix64 finaliser of seed + (step + 1) * 0x9E3779B97F4A7C15 (mod 2^64):
+ *   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ * always below total.  total == 0, step < 0 or a NULL out_t give PCV_ERR_INVALID. */
+pcv_status pcv_seed_draw(uint64_t seed, int step, uint64_t total, uint64_t* out_t);
 
 /* Groups of duplicates from a list of pairs (host only: needs no context and no GPU).  out_ids receives the distinct ids occurring
  * in the n_pairs pairs, ascending, and out_group[i] the smallest id of the connected component of out_ids[i]: an item is a candidate

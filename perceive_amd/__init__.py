@@ -14,6 +14,7 @@ from .search import (  # noqa: F401
     duplicate_groups,
     encode_query,
     merge_topk,
+    seed_draw,
     serialize_embedding,
 )
 from .sharded import HIT_DTYPE, NativeComm, ShardedSearcher, merge_topk_host, shard_bounds  # noqa: F401,E402

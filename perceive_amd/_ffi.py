@@ -104,6 +104,17 @@ class GroupStats(C.Structure):
     ]
 
 
+class SeedStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("participating", C.c_int64),
+        ("steps", C.c_int32),
+        ("method", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("steps_ms", C.c_float),
+    ]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32),
@@ -207,6 +218,9 @@ SYMBOLS = {
     "pcv_searcher_last_assign_stats": (C.c_int, [_P, C.POINTER(AssignStats)]),
     "pcv_searcher_neighbors": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int64, _I64P, _I64P, _F32P, _INTP, C.POINTER(C.c_int64)]),
     "pcv_searcher_last_neighbor_stats": (C.c_int, [_P, C.POINTER(NeighborStats)]),
+    "pcv_searcher_seeds": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int, C.c_uint64, _I64P, _I64P, _I64P, _I64P, _F32P, _INTP]),
+    "pcv_searcher_last_seed_stats": (C.c_int, [_P, C.POINTER(SeedStats)]),
+    "pcv_seed_draw": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "pcv_duplicate_groups": (C.c_int, [_I64P, _I64P, C.c_int64, _I64P, _I64P, C.c_int64, C.POINTER(C.c_int64)]),
     "pcv_searcher_like_queries": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _F32P, _P, _U8P, _I64P]),
     "pcv_searcher_search_like": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _INTP, _U8P]),

@@ -378,6 +378,67 @@ struct NeighborArgs {
 };
 constexpr uint32_t kMaxNeighborSpans = 512;  // (the threshold kernel keeps a row's maxima in eight registers a lane)
 
+// Seed items (pcv_searcher_seeds; DESIGN.md §4 "Seed items"): k picks, one after the other, each by the weights the picks before it
+// leave.  Rows are launch rows, rinv / norm exactly as selfjoin_prep_kernel leaves them (rinv != 0: the row takes part).  Workgroup
+// g of the begin and cover kernels owns the launch rows [g * kSeedSpanRows, + kSeedSpanRows): launch rows ascend with the global
+// position, so the order of the partials is the order of the prefix sums.
+//   cover[launch row] : the largest canonical cosine with a seed so far; -inf before the first (the weight of step 0 is 1, not
+//                       seed_weight(cover))
+//   part[g]           : the sum of the span's weights, and its best (largest weight, lower launch row on ties; w = 0: none)
+//   state             : what one step leaves for the next, and the call for the host
+constexpr int kSeedSpanRows = 256;
+struct SeedPart {
+    unsigned long long sum;
+    unsigned long long w;
+    uint32_t row, pad;
+};
+struct SeedState {
+    uint32_t centre;   // launch row of the last pick
+    uint32_t done;     // a step found T == 0, or an error: every later kernel of the call returns at once
+    int32_t count;     // picks made
+    uint32_t error;    // kSeedNoFirst, kSeedTooManyRows, kSeedInternal
+};
+constexpr uint32_t kSeedNoFirst = 1u, kSeedTooManyRows = 2u, kSeedInternal = 3u;
+constexpr unsigned long long kMaxSeedRows = 1ull << 30;  // weights <= 2^33: the int64 totals hold 2^30 of them
+struct SeedArgs {
+    const float* rinv;              // [total_blocks * 32]
+    const double* norm;             // [total_blocks * 32]
+    double* cover;                  // [total_blocks * 32]
+    SeedPart* part;                 // [parts]
+    SeedState* state;
+    int64_t* out_ids;               // [k]
+    int64_t* out_pos;               // [k]
+    int64_t* out_totals;            // [k]
+    float* out_cover;               // [k]
+    uint32_t parts;                 // ceil(launch rows / kSeedSpanRows)
+    int step;                       // of this launch
+    int method;
+    int has_first;                  // step 0 picks the first participating row carrying first_id
+    int64_t first_id;
+    uint64_t seed;
+};
+
+// The weight a row has once a seed exists (perceive_hip.h): rint(max(0, 1 - cover) * 2^32), ties to even.  One rounding in the
+// subtraction; the product with 2^32 is exact.
+__host__ __device__ static inline unsigned long long seed_weight(double cover) {
+    const double d = 1.0 - cover;
+    return (unsigned long long)__builtin_rint((d > 0.0 ? d : 0.0) * 0x1p32);
+}
+// The draw of step j among `total` units (perceive_hip.h, pcv_seed_draw): the one copy, for seed_pick_kernel and the host.
+__host__ __device__ static inline uint64_t seed_draw(uint64_t seed, uint32_t j, uint64_t total) {
+    uint64_t z = seed + (uint64_t)(j + 1u) * 0x9E3779B97F4A7C15ull;
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(z, total);
+#else
+    return (uint64_t)(((unsigned __int128)z * total) >> 64);
+#endif
+}
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -447,6 +508,10 @@ void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const Neigh
 void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);     // thr -> cand
 void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);  // cand -> sorted_*
 void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);   // sorted_* -> outputs
+// ---- seed items (seed_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_seed_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // cover = none, the partials of step 0
+void launch_seed_cover(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // the last pick -> cover, the partials of a.step
+void launch_seed_pick(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);   // the partials -> pick a.step, its outputs
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);
 void launch_merge(hipStream_t st, const pcv_hit_dev* lists, int n_shards, int B, int k, pcv_hit_dev* out,
                   int flagged = 0);

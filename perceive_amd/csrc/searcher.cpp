@@ -256,6 +256,7 @@ struct pcv_searcher {
     pcv_duplicate_stats dup_stats{};  // pcv_searcher_find_duplicates (its buffers live for the call only)
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
     pcv_neighbor_stats nbr_stats{};   // pcv_searcher_neighbors (likewise)
+    pcv_seed_stats seed_stats{};      // pcv_searcher_seeds (likewise)
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -3318,6 +3319,118 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     stats.listed = listed;
 }
 
+// ---- seed items (pcv_searcher_seeds; DESIGN.md §4 "Seed items") ----
+// Prep, begin, then k picks with a cover step between them (seed_kernels.hip): 2k launches queued on the searcher's stream and one
+// wait behind the last.  Everything the call allocates is its own and is given back when it ends: nothing of the searcher's pass
+// state is touched, and only the f32 rows are read.  The outputs are written last, after every check.
+void seeds(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int method, uint64_t seed, const int64_t* first_id, int64_t* out_ids,
+           int64_t* out_positions, int64_t* out_totals, float* out_cover, int32_t* out_count) {
+    PCV_REQUIRE(!s->dirty, "seeds: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "seeds: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    s->seed_stats = pcv_seed_stats{};
+    s->seed_stats.method = method;
+    std::vector<int64_t> ids((size_t)k, -1), pos((size_t)k, -1), totals((size_t)k, 0);
+    std::vector<float> cover((size_t)k, NAN);
+    SeedState state{};
+    if (!segs.empty()) {
+        PCV_HIP(hipSetDevice(s->ctx->device));
+        hipStream_t st = s->ctx->stream;
+        const size_t off_seg = align_up(sizeof(ScanParams)), bytes = off_seg + segs.size() * sizeof(SegDesc);
+        PinBuf<uint8_t> pin_p;
+        DevBuf<uint8_t> d_p;
+        pin_p.ensure(bytes);
+        d_p.ensure(bytes);
+        ScanParams& p = *new (pin_p.p) ScanParams{};
+        int64_t rows = 0;
+        p.total_blocks = fill_row_table(segs, reinterpret_cast<SegDesc*>(pin_p.p + off_seg), nullptr, rows, "seeds");
+        p.seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
+        p.nseg = (int)segs.size();
+        p.D = s->D;
+        p.D4 = s->D4;
+        p.metric = PCV_METRIC_COSINE;
+        const ScanParams* dp = reinterpret_cast<const ScanParams*>(d_p.p);
+        s->seed_stats.rows = rows;
+
+        const size_t nr = (size_t)p.total_blocks * kBlockRows;
+        DevBuf<float> d_rinv, d_out_cover;
+        DevBuf<double> d_norm, d_cover;
+        DevBuf<SeedPart> d_part;
+        DevBuf<SeedState> d_state;
+        DevBuf<int64_t> d_out;  // ids, positions, totals
+        SeedArgs a{};
+        a.parts = (uint32_t)((nr + kSeedSpanRows - 1) / kSeedSpanRows);
+        d_rinv.ensure(nr);
+        d_norm.ensure(nr);
+        d_cover.ensure(nr);
+        d_part.ensure(a.parts);
+        d_state.ensure(1);
+        d_out.ensure((size_t)3 * k);
+        d_out_cover.ensure((size_t)k);
+        a.rinv = d_rinv.p;
+        a.norm = d_norm.p;
+        a.cover = d_cover.p;
+        a.part = d_part.p;
+        a.state = d_state.p;
+        a.out_ids = d_out.p;
+        a.out_pos = d_out.p + k;
+        a.out_totals = d_out.p + 2 * (size_t)k;
+        a.out_cover = d_out_cover.p;
+        a.method = method;
+        a.seed = seed;
+        a.has_first = first_id != nullptr;
+        a.first_id = first_id ? *first_id : 0;
+
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        const auto drop_events = at_exit([&] {
+            (void)hipStreamSynchronize(st);
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        });
+        for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
+        SelfJoinArgs prep{};
+        prep.rinv = d_rinv.p;
+        prep.norm = d_norm.p;
+        PCV_HIP(hipMemcpyAsync(d_p.p, pin_p.p, bytes, hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemsetAsync(d_state.p, 0, sizeof(SeedState), st));
+        PCV_HIP(hipEventRecord(ev[0], st));
+        launch_selfjoin_prep(st, p, dp, prep);
+        PCV_HIP(hipEventRecord(ev[1], st));
+        launch_seed_begin(st, p, dp, a);
+        for (int j = 0; j < k; ++j) {
+            a.step = j;
+            if (j > 0) launch_seed_cover(st, p, dp, a);
+            launch_seed_pick(st, p, dp, a);
+        }
+        PCV_HIP(hipEventRecord(ev[2], st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        PCV_HIP(hipEventElapsedTime(&s->seed_stats.prep_ms, ev[0], ev[1]));
+        PCV_HIP(hipEventElapsedTime(&s->seed_stats.steps_ms, ev[1], ev[2]));
+        PCV_HIP(hipMemcpy(&state, d_state.p, sizeof(state), hipMemcpyDeviceToHost));
+        if (state.error == kSeedTooManyRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "seeds: more than 2^30 participating rows");
+        if (state.error != 0 && state.error != kSeedNoFirst) PCV_FAIL(PCV_ERR_INTERNAL, "seeds: a draw outside the prefix sums (step %d)", (int)state.count);
+        if (state.error == 0 && state.count > 0) {
+            PCV_REQUIRE(state.count <= k, "seeds: %d picks for k = %d", (int)state.count, k);
+            const size_t n = (size_t)state.count;
+            PCV_HIP(hipMemcpy(ids.data(), a.out_ids, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+            PCV_HIP(hipMemcpy(pos.data(), a.out_pos, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+            PCV_HIP(hipMemcpy(totals.data(), a.out_totals, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+            PCV_HIP(hipMemcpy(cover.data(), a.out_cover, n * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
+    // (no segment selected, or no participating row: nothing carries the id either)
+    if (first_id && (state.error == kSeedNoFirst || state.count == 0))
+        PCV_FAIL(PCV_ERR_INVALID, "seeds: no participating row of the selected sources carries first_id %lld", (long long)*first_id);
+    s->seed_stats.steps = state.count;
+    s->seed_stats.participating = state.count > 0 ? totals[0] : 0;
+    std::copy(ids.begin(), ids.end(), out_ids);
+    std::copy(pos.begin(), pos.end(), out_positions);
+    std::copy(totals.begin(), totals.end(), out_totals);
+    std::copy(cover.begin(), cover.end(), out_cover);
+    *out_count = state.count;
+}
+
 void sync_view(pcv_searcher* v);
 
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.
@@ -4490,6 +4603,39 @@ pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats*
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_neighbor_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->nbr_stats;
+    });
+}
+
+pcv_status pcv_searcher_seeds(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int method, uint64_t seed,
+                              const int64_t* first_id, int64_t* out_ids, int64_t* out_positions, int64_t* out_totals,
+                              float* out_cover, int32_t* out_count) {
+    return guarded([&] {
+        PCV_REQUIRE(out_ids != nullptr && out_positions != nullptr && out_totals != nullptr && out_cover != nullptr && out_count != nullptr,
+                    "seeds: an output is NULL");
+        PCV_REQUIRE(k >= 1 && k <= (int)PCV_MAX_SEEDS, "seeds: k %d outside [1,%d]", k, (int)PCV_MAX_SEEDS);
+        PCV_REQUIRE(method == PCV_SEED_FARTHEST || method == PCV_SEED_KMEANSPP, "seeds: method %d is neither PCV_SEED_FARTHEST nor PCV_SEED_KMEANSPP", method);
+        PCV_REQUIRE(s != nullptr, "seeds: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "seeds: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        seeds(s, source_ids, n_sources, k, method, seed, first_id, out_ids, out_positions, out_totals, out_cover, out_count);
+    });
+}
+
+pcv_status pcv_searcher_last_seed_stats(pcv_searcher* s, pcv_seed_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_seed_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->seed_stats;
+    });
+}
+
+pcv_status pcv_seed_draw(uint64_t seed, int step, uint64_t total, uint64_t* out_t) {
+    return guarded([&] {
+        PCV_REQUIRE(out_t != nullptr, "seed_draw: out_t is NULL");
+        PCV_REQUIRE(step >= 0, "seed_draw: step %d is negative", step);
+        PCV_REQUIRE(total != 0, "seed_draw: total is 0");
+        *out_t = seed_draw(seed, (uint32_t)step, total);
     });
 }
 

@@ -17,6 +17,8 @@ PCV_MAX_GROUPED_POOL = 4096  # include/perceive_hip.h
 PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_of / search_grouped
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
+PCV_MAX_SEEDS = 4096  # include/perceive_hip.h
+_SEED_METHODS = {"farthest": 0, "kmeans++": 1}  # PCV_SEED_FARTHEST, PCV_SEED_KMEANSPP
 
 _METRICS = {"cosine": _ffi.METRIC_COSINE, "dot": _ffi.METRIC_DOT}
 _KERNELS = {"auto": _ffi.KERNEL_AUTO, "wave": _ffi.KERNEL_WAVE, "mfma": _ffi.KERNEL_MFMA}
@@ -567,11 +569,17 @@ class Searcher:
         )
         return sums, members
 
-    def kmeans(self, sources, k, init, max_iters=20):
+    def kmeans(self, sources, k, init, max_iters=20, seed=0):
         """Spherical k-means by canonical cosine (both metrics), reproducible bit for bit.  init: [k, dim] vectors, or k item ids
-        (their stored embeddings, through like_queries).  -> (centroids [k, dim] f32 of the last assignment, label [n] int32,
+        (their stored embeddings, through like_queries), or "kmeans++" / "farthest": the k items seeds(sources, k, init, seed)
+        picks (ValueError if it finds fewer than k).  -> (centroids [k, dim] f32 of the last assignment, label [n] int32,
         score [n] f32, ids [n] int64, counts [k] int64, iterations, moved [iterations + 1] int64: rows that changed their label in
         each assignment).  It stops after an assignment that moved no row, or after max_iters updates."""
+        if isinstance(init, str):
+            picked = self.seeds(sources, k, init, seed)[0]
+            if picked.size < int(k):
+                raise ValueError(f"kmeans: seeding stopped after {picked.size} of {k} items (no row is left uncovered)")
+            init = picked
         init = np.asarray(init)
         if init.ndim == 1:
             if init.size != int(k):
@@ -636,6 +644,40 @@ class Searcher:
         st = _ffi.NeighborStats()
         _ffi.check(_ffi.lib().pcv_searcher_last_neighbor_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.NeighborStats._fields_}
+
+    # ---- seed items (pcv_searcher_seeds) ------------------------------------------------------------
+    # k items that cover the corpus, picked one after the other on the device: the init of kmeans, or a representative sample.
+    def seeds(self, sources, k, method="kmeans++", seed=0, first_id=None):
+        """k seed items of `sources`: "kmeans++" draws each with probability proportional to its integer weight rint((1 - largest
+        canonical cosine with a seed so far) * 2^32) (seed_draw(seed, step, total)); "farthest" takes the largest weight (ties: the
+        row stored first).  first_id: the item step 0 picks instead.  -> (ids [n] int64, positions [n] int64, totals [n] int64: the
+        potential before each pick in units of 2^-32, cover [n] f32: the pick's largest cosine with the seeds before it, NaN at
+        step 0), n <= k: the picks stop when no row is left uncovered.  A view seeds its own rows."""
+        k = int(k)
+        if not 1 <= k <= PCV_MAX_SEEDS:
+            raise ValueError("k outside [1, %d]" % PCV_MAX_SEEDS)
+        if method not in _SEED_METHODS:
+            raise ValueError('method must be "kmeans++" or "farthest"')
+        src, nsrc, _keep = _source_filter(sources)
+        ids = np.empty(k, dtype=np.int64)
+        pos = np.empty(k, dtype=np.int64)
+        totals = np.empty(k, dtype=np.int64)
+        cover = np.empty(k, dtype=np.float32)
+        first = None if first_id is None else np.array([int(first_id)], dtype=np.int64)
+        count = C.c_int32()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_seeds(
+                self._handle, src, nsrc, k, _SEED_METHODS[method], int(seed) & 0xFFFFFFFFFFFFFFFF, None if first is None else _ffi.i64p(first),
+                _ffi.i64p(ids), _ffi.i64p(pos), _ffi.i64p(totals), _ffi.f32p(cover), C.byref(count),
+            )
+        )
+        n = count.value
+        return ids[:n].copy(), pos[:n].copy(), totals[:n].copy(), cover[:n].copy()
+
+    def last_seed_stats(self):
+        st = _ffi.SeedStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_seed_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.SeedStats._fields_}
 
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):
@@ -879,6 +921,14 @@ def duplicate_groups(id_a, id_b):
         )
     )
     return ids[: n.value].copy(), group[: n.value].copy()
+
+
+def seed_draw(seed, step, total):
+    """The draw of step `step` of Searcher.seeds among `total` units of weight (host only): floor(z * total / 2^64), z the
+    splitmix64 finaliser of seed + (step + 1) * 0x9E3779B97F4A7C15.  The device calls the same function."""
+    t = C.c_uint64()
+    _ffi.check(_ffi.lib().pcv_seed_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(total), C.byref(t)))
+    return t.value
 
 
 def encode_query(model, query):

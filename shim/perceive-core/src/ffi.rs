@@ -88,6 +88,17 @@ pub struct pcv_neighbor_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_seed_stats {
+    pub rows: i64,
+    pub participating: i64,
+    pub steps: i32,
+    pub method: i32,
+    pub prep_ms: f32,
+    pub steps_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_hit {
     pub score: f64,
     pub pos: i64,
@@ -174,6 +185,9 @@ pub const PCV_MAX_GROUPED_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
 pub const PCV_MAX_NEIGHBORS: c_int = 64;
+pub const PCV_SEED_FARTHEST: c_int = 0;
+pub const PCV_SEED_KMEANSPP: c_int = 1;
+pub const PCV_MAX_SEEDS: c_int = 4096;
 pub const PCV_GELU_ERF: c_int = 0;
 pub const PCV_GELU_TANH: c_int = 1;
 pub const PCV_POOL_MEAN: c_int = 0;
@@ -260,6 +274,9 @@ extern "C" {
     pub fn pcv_searcher_last_assign_stats(s: *mut pcv_searcher, out: *mut pcv_assign_stats) -> c_int;
     pub fn pcv_searcher_neighbors(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, capacity: i64, out_ids: *mut i64, out_neighbor_ids: *mut i64, out_scores: *mut f32, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_last_neighbor_stats(s: *mut pcv_searcher, out: *mut pcv_neighbor_stats) -> c_int;
+    pub fn pcv_searcher_seeds(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, method: c_int, seed: u64, first_id: *const i64, out_ids: *mut i64, out_positions: *mut i64, out_totals: *mut i64, out_cover: *mut f32, out_count: *mut i32) -> c_int;
+    pub fn pcv_searcher_last_seed_stats(s: *mut pcv_searcher, out: *mut pcv_seed_stats) -> c_int;
+    pub fn pcv_seed_draw(seed: u64, step: c_int, total: u64, out_t: *mut u64) -> c_int;
     pub fn pcv_duplicate_groups(id_a: *const i64, id_b: *const i64, n_pairs: i64, out_ids: *mut i64, out_group: *mut i64, capacity: i64, out_n_ids: *mut i64) -> c_int;
     pub fn pcv_searcher_like_queries(s: *mut pcv_searcher, example_ids: *const i64, weights: *const f32, offsets: *const i64, n_queries: c_int, out_queries: *mut f32, d_out_queries: *mut c_void, out_found: *mut u8, out_member_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_search_like(s: *mut pcv_searcher, example_ids: *const i64, weights: *const f32, offsets: *const i64, n_queries: c_int, source_ids: *const i64, n_sources: c_int, k: c_int, exclude_examples: c_int, out_ids: *mut i64, out_scores: *mut f32, out_counts: *mut c_int, out_found: *mut u8) -> c_int;

@@ -606,6 +606,40 @@ impl Searcher {
         (0..n as usize).map(|i| (ids[i], (0..counts[i] as usize).map(|j| (nbr[i * k + j], scores[i * k + j])).collect())).collect()
     }
 
+    /// Seed items (`pcv_searcher_seeds`): up to `k` items (clamped to PCV_MAX_SEEDS) that cover `sources`, in the order they were
+    /// picked — `kmeanspp`: the k-means++ draw of `seed`, else farthest first; `first_id`: the item step 0 picks instead.
+    /// Returns (item id, global position, potential before the pick in units of 2^-32, largest cosine with the seeds before it:
+    /// NaN at step 0) per pick; fewer than `k` when no row is left uncovered.
+    pub fn seeds(&self, sources: &[i64], k: usize, kmeanspp: bool, seed: u64, first_id: Option<i64>) -> Vec<(i64, i64, i64, f32)> {
+        if self.handle.is_null() || k == 0 || sources.is_empty() {
+            return Vec::new();
+        }
+        let k = k.min(ffi::PCV_MAX_SEEDS as usize);
+        let mut ids = vec![-1i64; k];
+        let mut positions = vec![-1i64; k];
+        let mut totals = vec![0i64; k];
+        let mut cover = vec![f32::NAN; k];
+        let mut n: i32 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_seeds(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                k as i32,
+                if kmeanspp { ffi::PCV_SEED_KMEANSPP } else { ffi::PCV_SEED_FARTHEST },
+                seed,
+                first_id.as_ref().map_or(std::ptr::null(), |id| id as *const i64),
+                ids.as_mut_ptr(),
+                positions.as_mut_ptr(),
+                totals.as_mut_ptr(),
+                cover.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("seeds failed");
+        (0..n as usize).map(|i| (ids[i], positions[i], totals[i], cover[i])).collect()
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
