@@ -312,6 +312,74 @@ inline SeedItems seeds_handle(pcv_searcher* h, const std::vector<int64_t>& sourc
     return r;
 }
 
+// Searcher::moments / principal_axes / project (pcv_searcher_moments, _principal_axes, _project): a PCA where the rows live.
+struct Moments {
+    int64_t n = 0;                // participating rows
+    std::vector<int64_t> sums;    // [dim] S_d, the sums of the fixed-point unit rows
+    std::vector<double> matrix;   // [dim][dim] C * 2^-64, or centered (n C - S S^T) * 2^-64; empty when not asked for
+};
+struct PrincipalAxes {
+    int64_t n = 0;
+    std::vector<float> axes;       // [m][dim]
+    std::vector<double> offsets;   // [m] the mean unit row along each axis
+    std::vector<double> variance;  // [m]
+};
+struct Projection {
+    std::vector<float> coords;  // [n][m]; NaN for a row that takes no part
+    std::vector<int64_t> ids;   // [n]
+};
+inline size_t dim_of_handle(pcv_searcher* h) {
+    int dim = 0;
+    check(pcv_searcher_dim(h, &dim));
+    return (size_t)dim;
+}
+inline Moments moments_handle(pcv_searcher* h, const std::vector<int64_t>& sources, bool centered, bool matrix) {
+    Moments r;
+    const size_t dim = dim_of_handle(h);
+    r.sums.assign(dim, 0);
+    if (matrix) r.matrix.assign(dim * dim, 0.0);
+    if (sources.empty()) return r;  // `sources.contains(..)` matches nothing
+    check(pcv_searcher_moments(h, sources.data(), (int)sources.size(), centered ? 1 : 0, r.sums.data(), matrix ? r.matrix.data() : nullptr, &r.n));
+    return r;
+}
+inline PrincipalAxes principal_axes_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t m) {
+    PrincipalAxes r;
+    const size_t dim = dim_of_handle(h);
+    r.axes.assign(m * dim, 0.0f);
+    r.offsets.assign(m, 0.0);
+    r.variance.assign(m, 0.0);
+    if (sources.empty()) throw Error(PCV_ERR_INVALID, "principal_axes: no source selected");
+    check(pcv_searcher_principal_axes(h, sources.data(), (int)sources.size(), (int)m, r.axes.data(), r.offsets.data(), r.variance.data(), &r.n));
+    return r;
+}
+inline Projection project_handle(pcv_searcher* h, const std::vector<int64_t>& sources, const std::vector<float>& axes, size_t m,
+                                 const std::vector<double>* offsets) {
+    Projection r;
+    if (axes.size() != m * dim_of_handle(h) || (offsets && offsets->size() != m)) throw Error(PCV_ERR_INVALID, "project: axes must be [m][dim], offsets [m]");
+    if (sources.empty()) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    const double* off = offsets ? offsets->data() : nullptr;
+    check(pcv_searcher_project(h, axes.data(), off, (int)m, sources.data(), (int)sources.size(), 0, nullptr, nullptr, &n));
+    r.coords.resize((size_t)std::max<int64_t>(n, 1) * m);
+    r.ids.resize((size_t)std::max<int64_t>(n, 1));
+    check(pcv_searcher_project(h, axes.data(), off, (int)m, sources.data(), (int)sources.size(), std::max<int64_t>(n, 1), r.coords.data(), r.ids.data(), &n));
+    r.coords.resize((size_t)n * m);
+    r.ids.resize((size_t)n);
+    return r;
+}
+// pcv_symmetric_eigen (host only, offline): values descending, vectors[i] the unit eigenvector of values[i]
+struct Eigen {
+    std::vector<double> values, vectors;
+};
+inline Eigen symmetric_eigen(const std::vector<double>& a, size_t n) {
+    Eigen r;
+    if (a.size() != n * n) throw Error(PCV_ERR_INVALID, "symmetric_eigen: a must be [n][n]");
+    r.values.assign(n, 0.0);
+    r.vectors.assign(n * n, 0.0);
+    check(pcv_symmetric_eigen(a.data(), (int)n, r.values.data(), r.vectors.data()));
+    return r;
+}
+
 // Searcher::view: a read-only searcher over the rows carrying one of a set of item ids (pcv_searcher_create_view).  It searches
 // like a searcher built from only those rows and follows every later change of its parent; it must go before its parent does.
 class SearcherView {
@@ -387,6 +455,24 @@ public:
     pcv_seed_stats last_seed_stats() const {
         pcv_seed_stats st;
         check(pcv_searcher_last_seed_stats(h_, &st));
+        return st;
+    }
+    // integer moments of the unit rows, their principal axes, and every row's coordinates along given axes (moments_handle, ...)
+    Moments moments(const std::vector<int64_t>& sources, bool centered = false, bool matrix = true) const {
+        return moments_handle(h_, sources, centered, matrix);
+    }
+    PrincipalAxes principal_axes(const std::vector<int64_t>& sources, size_t m) const { return principal_axes_handle(h_, sources, m); }
+    Projection project(const std::vector<int64_t>& sources, const std::vector<float>& axes, size_t m, const std::vector<double>* offsets = nullptr) const {
+        return project_handle(h_, sources, axes, m, offsets);
+    }
+    pcv_moment_stats last_moment_stats() const {
+        pcv_moment_stats st;
+        check(pcv_searcher_last_moment_stats(h_, &st));
+        return st;
+    }
+    pcv_project_stats last_project_stats() const {
+        pcv_project_stats st;
+        check(pcv_searcher_last_project_stats(h_, &st));
         return st;
     }
     // the k nearest other items of every item of the view (neighbors_handle)
@@ -529,6 +615,24 @@ public:
     pcv_seed_stats last_seed_stats() const {
         pcv_seed_stats st;
         check(pcv_searcher_last_seed_stats(h_, &st));
+        return st;
+    }
+    // integer moments of the unit rows, their principal axes, and every row's coordinates along given axes (moments_handle, ...)
+    Moments moments(const std::vector<int64_t>& sources, bool centered = false, bool matrix = true) const {
+        return moments_handle(h_, sources, centered, matrix);
+    }
+    PrincipalAxes principal_axes(const std::vector<int64_t>& sources, size_t m) const { return principal_axes_handle(h_, sources, m); }
+    Projection project(const std::vector<int64_t>& sources, const std::vector<float>& axes, size_t m, const std::vector<double>* offsets = nullptr) const {
+        return project_handle(h_, sources, axes, m, offsets);
+    }
+    pcv_moment_stats last_moment_stats() const {
+        pcv_moment_stats st;
+        check(pcv_searcher_last_moment_stats(h_, &st));
+        return st;
+    }
+    pcv_project_stats last_project_stats() const {
+        pcv_project_stats st;
+        check(pcv_searcher_last_project_stats(h_, &st));
         return st;
     }
     // the k nearest other items of every item, found once on the device (neighbors_handle)

@@ -703,6 +703,96 @@ pcv_status pcv_searcher_last_seed_stats(pcv_searcher* s, pcv_seed_stats* out);
  * always below total.  total == 0, step < 0 or a NULL out_t give PCV_ERR_INVALID. */
 pcv_status pcv_seed_draw(uint64_t seed, int step, uint64_t total, uint64_t* out_t);
 
+/* Corpus moments and principal axes: the mean direction of a corpus, how its variance is spread over directions, and every row's
+ * position along a handful of directions — a PCA where the rows live, without downloading N x dim floats and without a LAPACK.
+ * Rules shared by pcv_searcher_moments, _principal_axes and _project: the rows concerned are those of the selected segments in global
+ * position order, as in pcv_searcher_neighbors; source_ids == NULL means all sources, an empty list selects nothing; a view uses its
+ * own rows.  A row TAKES PART under exactly the rules of pcv_searcher_neighbors / _label_sums: a pcv_searcher_search with the same
+ * filter could return it (scale != 0, not hidden) and it has a cosine (canonical |x|^2 in [2^-126, inf)).  rinv_r =
+ * (float)(1 / sqrt(|x_r|^2)) and t(r, d) = (int64) rint((double)x[r][d] * (double)rinv_r * 2^32) are those of pcv_searcher_label_sums:
+ * both metrics work on unit rows, as k-means, neighbours and seeds do.  The calls read the f32 rows, touch no pass state and depend on
+ * no screening copy, kernel or tuning setting; every device allocation is given back on return.  Argument errors are reported before
+ * the handle is looked at; a searcher with pending rows fails as in pcv_searcher_search; a sharded searcher
+ * (pcv_searcher_set_shard_offset != 0 or a pcv_comm) gives PCV_ERR_INVALID.  Not in scope: a sharded form, device-resident output,
+ * incremental moments, partial eigen-solvers (DESIGN.md §4 "Corpus moments and principal axes").
+ *
+ * pcv_searcher_moments: the integer first and second moments of the unit rows, the same bits in any order of addition.
+ *   out_n        n, the number of participating rows
+ *   out_sums     [dim] int64: S_d = sum over the participating rows of t(r, d); the mean unit row is S_d * 2^-32 / n
+ *   out_matrix   [dim][dim] f64, or NULL: then only the sums are computed and the rows are not streamed a second time.  With
+ *                C_de = sum of t(r, d) * t(r, e), an exact integer of up to 94 bits,
+ *                  centered == 0: (double)C_de * 2^-64                        n times the second moment
+ *                  centered != 0: (double)(n * C_de - S_d * S_e) * 2^-64      n^2 times the covariance
+ *                the one rounding is that of the exact integer to double, to nearest even; the power of two is exact
+ * More than 2^30 participating rows, or dim > 2048, give PCV_ERR_UNSUPPORTED.  The device holds 12 bytes per row and three
+ * Dp x Dp int64 matrices (Dp: dim rounded up to 64) for the call. */
+pcv_status pcv_searcher_moments(pcv_searcher* s, const int64_t* source_ids, int n_sources, int centered, int64_t* out_sums,
+                                double* out_matrix, int64_t* out_n);
+
+/* The host finish of pcv_searcher_moments (host only: needs no context and no GPU; pcv_searcher_moments calls it).  hh, hl, ll are
+ * [dim][dim] int64 limb sums over the participating rows with t = h * 2^16 + l, h = t >> 16 (arithmetic), l = t & 0xffff:
+ * hh[d][e] = sum h_d h_e, hl[d][e] = sum h_d l_e, ll[d][e] = sum l_d l_e; hh and ll are read on and above the diagonal only.  In 128-bit
+ * integers C_de = hh[d][e] * 2^32 + (hl[d][e] + hl[e][d]) * 2^16 + ll[d][e], then out_matrix[d][e] = out_matrix[e][d] as defined above
+ * (sums [dim] and n are read only when centered != 0).  n in [0, 2^30], dim >= 1, else PCV_ERR_INVALID. */
+pcv_status pcv_moments_finish(const int64_t* hh, const int64_t* hl, const int64_t* ll, const int64_t* sums, int64_t n, int dim,
+                              int centered, double* out_matrix);
+
+/* Counters of the most recent pcv_searcher_moments (or _principal_axes) on this handle. */
+typedef struct pcv_moment_stats {
+    int64_t rows;           /* rows of the selected segments (those taking no part included)                   */
+    int64_t participating;  /* n                                                                               */
+    int32_t tile_features;  /* a workgroup of the second-moment kernel owns tile_features x tile_features outputs */
+    int32_t row_ranges;     /* row ranges the rows were cut in: one f64 accumulation chain each (0: no matrix)  */
+    float prep_ms;          /* hipEvent times: the norms (selfjoin_prep_kernel), the sums, the second moments   */
+    float sums_ms;
+    float syrk_ms;
+} pcv_moment_stats;
+pcv_status pcv_searcher_last_moment_stats(pcv_searcher* s, pcv_moment_stats* out);
+
+/* Eigenvalues and eigenvectors of a symmetric matrix by cyclic Jacobi rotations (host only: needs no context and no GPU, no LAPACK).
+ * a is [n][n] f64, read from the upper triangle (a[i][j], i <= j); every value read must be finite.
+ *   out_values   [n] descending
+ *   out_vectors  [n][n]: out_vectors[i] is the unit eigenvector of out_values[i], its sign fixed so that its component of largest
+ *                magnitude (the lowest index on ties) is positive
+ * The sequence of rotations is deterministic, but no bit-for-bit promise is made across compilers (FMA contraction).  1 <= n <= 2048,
+ * else PCV_ERR_INVALID.  An OFFLINE call: O(n^3) per sweep on one thread, seconds at n = 384. */
+pcv_status pcv_symmetric_eigen(const double* a, int n, double* out_values, double* out_vectors);
+
+/* The m leading principal axes of the unit rows: pcv_searcher_moments with centered = 1, then pcv_symmetric_eigen.
+ *   out_axes      [m][dim] f32: (float) of eigenvector j of the covariance, j < m
+ *   out_offsets   [m] f64: the feature-order f64 sum of (double)out_axes[j][d] * ((double)S_d * 2^-32 / (double)n) — the mean unit row
+ *                 along axis j, what pcv_searcher_project subtracts
+ *   out_variance  [m] f64: lambda_j / n^2, the variance of the unit rows along axis j
+ *   out_n         n
+ * 1 <= m <= PCV_MAX_AXES and m <= dim (PCV_ERR_INVALID); n == 0 gives PCV_ERR_INVALID (out_n is set). */
+enum { PCV_MAX_AXES = 64 };
+pcv_status pcv_searcher_principal_axes(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m, float* out_axes,
+                                       double* out_offsets, double* out_variance, int64_t* out_n);
+
+/* The canonical score of every row against m vectors, written out in full: principal coordinates, linear probes, hand-made "topic
+ * axes".  axes is host [m][dim] f32, every value finite; offsets host [m] f64 (finite), or NULL: zeros.  For a participating row
+ *   coord(r, j) = (float)(a(r, j) * (double)rinv_r - offsets[j])
+ * with a(r, j) the canonical f64 dot of axes[j] with the stored row — products exact, summed in feature order starting from +0
+ *  — and the multiplication and the subtraction rounded separately (no fused multiply-add).  Rows that take no part
+ * get NaN in all m slots.
+ *   capacity     rows the outputs have room for; capacity < n gives PCV_ERR_INVALID (out_n is set)
+ *   out_coords   [capacity][m] f32, in global position order
+ *   out_ids      [capacity] the item id of every position (may be NULL)
+ *   out_n        n, the rows of the selected segments.  With out_coords == NULL and capacity == 0 the call only reports n
+ * 1 <= m <= PCV_MAX_AXES, else PCV_ERR_INVALID. */
+pcv_status pcv_searcher_project(pcv_searcher* s, const float* axes, const double* offsets, int m, const int64_t* source_ids,
+                                int n_sources, int64_t capacity, float* out_coords, int64_t* out_ids, int64_t* out_n);
+
+/* Counters of the most recent pcv_searcher_project on this handle. */
+typedef struct pcv_project_stats {
+    int64_t rows;       /* rows of the selected segments (those taking no part included)      */
+    int32_t axes;       /* m                                                                  */
+    int32_t group;      /* axes scored per pass over a row's pieces (2 or 8)                  */
+    float prep_ms;      /* hipEvent times: the norms (selfjoin_prep_kernel), the projection   */
+    float project_ms;
+} pcv_project_stats;
+pcv_status pcv_searcher_last_project_stats(pcv_searcher* s, pcv_project_stats* out);
+
 /* Groups of duplicates from a list of pairs (host only: needs no context and no GPU).  out_ids receives the distinct ids occurring
  * in the n_pairs pairs, ascending, and out_group[i] the smallest id of the connected component of out_ids[i]: an item is a candidate
  * for removal iff out_group[i] != out_ids[i].  out_n_ids receives the number of distinct ids; capacity < that gives PCV_ERR_INVALID

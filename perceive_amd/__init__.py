@@ -16,6 +16,7 @@ from .search import (  # noqa: F401
     merge_topk,
     seed_draw,
     serialize_embedding,
+    symmetric_eigen,
 )
 from .sharded import HIT_DTYPE, NativeComm, ShardedSearcher, merge_topk_host, shard_bounds  # noqa: F401,E402
 from .model import (  # noqa: F401,E402

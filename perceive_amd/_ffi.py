@@ -115,6 +115,28 @@ class SeedStats(C.Structure):
     ]
 
 
+class MomentStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("participating", C.c_int64),
+        ("tile_features", C.c_int32),
+        ("row_ranges", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("sums_ms", C.c_float),
+        ("syrk_ms", C.c_float),
+    ]
+
+
+class ProjectStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("axes", C.c_int32),
+        ("group", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("project_ms", C.c_float),
+    ]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int32),
@@ -150,6 +172,7 @@ _I64P = C.c_void_p  # int64_t*
 _F32P = C.c_void_p  # float*
 _U8P = C.c_void_p  # uint8_t*
 _INTP = C.c_void_p  # int* / int32_t*
+_F64P = C.c_void_p  # double*
 # int visit(void* user, const char* name, const int64_t* shape, int rank, int dtype, const float* values, int64_t numel)
 TENSOR_VISITOR = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64)
 SYMBOLS = {
@@ -221,6 +244,13 @@ SYMBOLS = {
     "pcv_searcher_seeds": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int, C.c_uint64, _I64P, _I64P, _I64P, _I64P, _F32P, _INTP]),
     "pcv_searcher_last_seed_stats": (C.c_int, [_P, C.POINTER(SeedStats)]),
     "pcv_seed_draw": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "pcv_searcher_moments": (C.c_int, [_P, _I64P, C.c_int, C.c_int, _I64P, _F64P, C.POINTER(C.c_int64)]),
+    "pcv_moments_finish": (C.c_int, [_I64P, _I64P, _I64P, _I64P, C.c_int64, C.c_int, C.c_int, _F64P]),
+    "pcv_searcher_last_moment_stats": (C.c_int, [_P, C.POINTER(MomentStats)]),
+    "pcv_symmetric_eigen": (C.c_int, [_F64P, C.c_int, _F64P, _F64P]),
+    "pcv_searcher_principal_axes": (C.c_int, [_P, _I64P, C.c_int, C.c_int, _F32P, _F64P, _F64P, C.POINTER(C.c_int64)]),
+    "pcv_searcher_project": (C.c_int, [_P, _F32P, _F64P, C.c_int, _I64P, C.c_int, C.c_int64, _F32P, _I64P, C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_project_stats": (C.c_int, [_P, C.POINTER(ProjectStats)]),
     "pcv_duplicate_groups": (C.c_int, [_I64P, _I64P, C.c_int64, _I64P, _I64P, C.c_int64, C.POINTER(C.c_int64)]),
     "pcv_searcher_like_queries": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _F32P, _P, _U8P, _I64P]),
     "pcv_searcher_search_like": (C.c_int, [_P, _I64P, _F32P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _INTP, _U8P]),

@@ -29,9 +29,6 @@ __device__ __forceinline__ unsigned long long g_atomic_max64(unsigned long long*
 __device__ __forceinline__ uint32_t g_atomic_min(uint32_t* p, uint32_t v) {
     return __hip_atomic_fetch_min((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void g_atomic_add_i64(long long* p, long long v) {
-    (void)__hip_atomic_fetch_add((PCV_GLOBAL long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // one thread per (label slot, 16-byte piece of 8 bf16); the thread of piece 0 also writes the label's constants
 __global__ __launch_bounds__(256) void assign_labels_kernel(const AssignArgs a, int D4) {
@@ -341,17 +338,17 @@ __global__ __launch_bounds__(256) void label_sums_kernel(const ScanParams* __res
                 const int lab = gld(&a.row_label[lr]);
                 if (lab < 0 || lab >= a.K) continue;
                 const double n = gld(&a.norm[lr]);
-                if (!(n >= 0x1p-126 && n < __builtin_inf())) continue;  // no cosine: the row adds nothing
+                if (!has_cosine(n)) continue;  // the row adds nothing
                 if (lab != cur) {
                     flush();
                     cur = lab;
                 }
-                const double rs = (double)(float)(1.0 / sqrt(n)) * 0x1p32;  // (the f32 rinv of the prep step, also where that marks wild)
+                const double rs = unit_scale(n);
                 const float4 v = gld4(blk + r);
-                s0 += (long long)rint((double)v.x * rs);
-                s1 += (long long)rint((double)v.y * rs);
-                s2 += (long long)rint((double)v.z * rs);
-                s3 += (long long)rint((double)v.w * rs);
+                s0 += unit_int(v.x, rs);
+                s1 += unit_int(v.y, rs);
+                s2 += unit_int(v.z, rs);
+                s3 += unit_int(v.w, rs);
                 ++members;
             }
         }

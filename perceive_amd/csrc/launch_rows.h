@@ -12,6 +12,17 @@ __device__ __forceinline__ unsigned long long g_atomic_add64(unsigned long long*
     return __hip_atomic_fetch_add((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+__device__ __forceinline__ void g_atomic_add_i64(long long* p, long long v) {
+    (void)__hip_atomic_fetch_add((PCV_GLOBAL long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The fixed-point unit row (perceive_hip.h, pcv_searcher_label_sums): t(r, d) = unit_int(x[r][d], unit_scale(|x_r|^2)) — the f32 rinv
+// of the prep step (also where that marks a row wild) times 2^32, exact; the product of two f32 is exact in f64, so rint is the one
+// rounding.  The one copy of this arithmetic: label_sums_kernel and the kernels of moments_kernels.hip call it.
+__device__ __forceinline__ bool has_cosine(double n) { return n >= 0x1p-126 && n < __builtin_inf(); }
+__device__ __forceinline__ double unit_scale(double n) { return (double)(float)(1.0 / sqrt(n)) * 0x1p32; }
+__device__ __forceinline__ long long unit_int(float x, double rs) { return (long long)rint((double)x * rs); }
+
 // last table entry with blk0 <= gb
 __device__ __forceinline__ int find_seg(const ScanParams& p, uint32_t gb, int from = 0) {
     int lo = from, hi = p.nseg - 1;

@@ -439,6 +439,38 @@ __host__ __device__ static inline uint64_t seed_draw(uint64_t seed, uint32_t j, 
 #endif
 }
 
+// Corpus moments and projection (pcv_searcher_moments, _project; DESIGN.md §4 "Corpus moments and principal axes").  Rows are launch
+// rows, rinv / norm exactly as selfjoin_prep_kernel leaves them (rinv != 0: the row takes part).  t(r, d) is the fixed-point unit row
+// of pcv_searcher_label_sums (launch_rows.h, unit_int), cut in two limbs t = h * 2^16 + l, h = t >> 16 in [-65537, 65536],
+// l = t & 0xffff: both exact in f32, every limb product below 2^32.01, so an f64 sum of up to 2^20 of them is exact in any order.
+//   sums[d]          : S_d = sum of t(r, d);  sums[Dp]: the participating rows
+//   hh, hl, ll       : [Dp][Dp] int64, HH = H^T H, HL = H^T L, LL = L^T L summed over the participating rows; hh and ll hold the 64 x 64
+//                      super-tiles on and above the diagonal only, hl all of them
+//   range_blocks     : row blocks of one workgroup's accumulation chain, at most kMomentChainBlocks
+constexpr uint32_t kMomentChainBlocks = 1u << 15;
+static_assert((uint64_t)kMomentChainBlocks * kBlockRows <= (1ull << 20), "an f64 chain of more than 2^20 limb products is not exact");
+constexpr int kMomentSide = 64;  // features of one side of a super-tile
+struct MomentArgs {
+    const double* norm;             // [total_blocks * 32]
+    long long* sums;                // [Dp + 1]
+    long long* hh;                  // [Dp][Dp]
+    long long* hl;
+    long long* ll;
+    uint32_t range_blocks;
+};
+// Projection: the canonical f64 dot of every participating row with m axes.  The axes are packed like rows: axis j is lane j & 31 of
+// block j >> 5 of a blocked f32 matrix with zero padding up to a whole number of blocks.
+struct ProjectArgs {
+    const float* rinv;              // [total_blocks * 32]
+    const double* norm;             // [total_blocks * 32]
+    const float4* axes;             // [ceil(m / 32)][D4][32]
+    const double* offsets;          // [m]
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    float* out_coords;              // [rows][m]
+    int64_t* out_ids;               // [rows]
+    int m;
+};
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -512,6 +544,11 @@ void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanPara
 void launch_seed_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // cover = none, the partials of step 0
 void launch_seed_cover(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // the last pick -> cover, the partials of a.step
 void launch_seed_pick(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);   // the partials -> pick a.step, its outputs
+// ---- corpus moments and projection (moments_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_moment_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const MomentArgs& a);  // norm -> sums
+void launch_moment_syrk(hipStream_t st, const ScanParams& p, const ScanParams* dp, const MomentArgs& a);  // norm -> hh, hl, ll
+uint32_t moment_row_ranges(const ScanParams& p, const MomentArgs& a);
+void launch_project(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ProjectArgs& a);
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);
 void launch_merge(hipStream_t st, const pcv_hit_dev* lists, int n_shards, int B, int k, pcv_hit_dev* out,
                   int flagged = 0);

@@ -257,6 +257,8 @@ struct pcv_searcher {
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
     pcv_neighbor_stats nbr_stats{};   // pcv_searcher_neighbors (likewise)
     pcv_seed_stats seed_stats{};      // pcv_searcher_seeds (likewise)
+    pcv_moment_stats moment_stats{};  // pcv_searcher_moments / _principal_axes (likewise)
+    pcv_project_stats project_stats{};  // pcv_searcher_project (likewise)
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
     bool fail_copy_alloc = false;  // PCV_TUNE_FAIL_COPY_ALLOC
     int mid_copy = PCV_MID_COPY_AUTO;        // pcv_searcher_set_mid_copy
@@ -3431,6 +3433,222 @@ void seeds(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int
     *out_count = state.count;
 }
 
+// ---- corpus moments and principal axes (pcv_searcher_moments, _principal_axes, _project) ----
+constexpr int64_t kMaxMomentRows = (int64_t)1 << 30;  // |t| <= 2^32 (1 + 2^-23): the int64 limb sums and the 128-bit finish hold 2^30 rows
+constexpr int kMaxMomentDim = 2048;
+
+// The table of a launch over `segs`, its norms and the events of a call: what the two calls below share.  Everything is the call's
+// own and is given back when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
+struct RowsJob {
+    hipStream_t st;
+    PinBuf<uint8_t> pin_p;
+    DevBuf<uint8_t> d_p;
+    ScanParams* p = nullptr;
+    const ScanParams* dp = nullptr;
+    const int64_t* seg_out0 = nullptr;
+    int64_t rows = 0;
+    size_t nr = 0;
+    DevBuf<float> d_rinv;
+    DevBuf<double> d_norm;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    RowsJob(pcv_searcher* s, const std::vector<SelSeg>& segs, const char* what) : st(s->ctx->stream) {
+        for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
+        const size_t off_seg = align_up(sizeof(ScanParams)), off_out0 = align_up(off_seg + segs.size() * sizeof(SegDesc));
+        const size_t bytes = off_out0 + segs.size() * sizeof(int64_t);
+        pin_p.ensure(bytes);
+        d_p.ensure(bytes);
+        p = new (pin_p.p) ScanParams{};
+        p->total_blocks = fill_row_table(segs, reinterpret_cast<SegDesc*>(pin_p.p + off_seg), reinterpret_cast<int64_t*>(pin_p.p + off_out0), rows, what);
+        p->seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
+        p->nseg = (int)segs.size();
+        p->D = s->D;
+        p->D4 = s->D4;
+        p->metric = PCV_METRIC_COSINE;
+        dp = reinterpret_cast<const ScanParams*>(d_p.p);
+        seg_out0 = reinterpret_cast<const int64_t*>(d_p.p + off_out0);
+        nr = (size_t)p->total_blocks * kBlockRows;
+        d_rinv.ensure(nr);
+        d_norm.ensure(nr);
+        SelfJoinArgs prep{};
+        prep.rinv = d_rinv.p;
+        prep.norm = d_norm.p;
+        PCV_HIP(hipMemcpyAsync(d_p.p, pin_p.p, bytes, hipMemcpyHostToDevice, st));
+        PCV_HIP(hipEventRecord(ev[0], st));
+        launch_selfjoin_prep(st, *p, dp, prep);
+        PCV_HIP(hipEventRecord(ev[1], st));
+    }
+    ~RowsJob() {
+        (void)hipStreamSynchronize(st);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    float elapsed(int from) {
+        float ms = 0.0f;
+        PCV_HIP(hipEventElapsedTime(&ms, ev[from], ev[from + 1]));
+        return ms;
+    }
+};
+
+// Prep, sums, and — with a matrix asked for — the limb SYRK (moments_kernels.hip) and its 128-bit finish on the host.  The outputs
+// are written last, after every check.
+void moments(pcv_searcher* s, const int64_t* source_ids, int n_sources, int centered, int64_t* out_sums, double* out_matrix, int64_t* out_n) {
+    PCV_REQUIRE(!s->dirty, "moments: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "moments: a sharded searcher (set_shard_offset) is not supported");
+    if (s->D > kMaxMomentDim) PCV_FAIL(PCV_ERR_UNSUPPORTED, "moments: dimension %d is above %d", s->D, kMaxMomentDim);
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    s->moment_stats = pcv_moment_stats{};
+    s->moment_stats.tile_features = kMomentSide;
+    const size_t D = (size_t)s->D, Dp = (size_t)s->Dp;
+    std::vector<long long> S(Dp + 1, 0);
+    std::vector<int64_t> hh, hl, ll;
+    if (!segs.empty()) {
+        PCV_HIP(hipSetDevice(s->ctx->device));
+        RowsJob job(s, segs, "moments");
+        hipStream_t st = job.st;
+        s->moment_stats.rows = job.rows;
+        DevBuf<long long> d_sums, d_mat;
+        MomentArgs a{};
+        d_sums.ensure(Dp + 1);
+        a.norm = job.d_norm.p;
+        a.sums = d_sums.p;
+        PCV_HIP(hipMemsetAsync(d_sums.p, 0, (Dp + 1) * sizeof(long long), st));
+        if (out_matrix) {
+            d_mat.ensure(3 * Dp * Dp);
+            a.hh = d_mat.p;
+            a.hl = d_mat.p + Dp * Dp;
+            a.ll = d_mat.p + 2 * Dp * Dp;
+            PCV_HIP(hipMemsetAsync(d_mat.p, 0, 3 * Dp * Dp * sizeof(long long), st));
+            // some workgroups per CU over all the super-tiles; a chain not so short that its closing atomics show, nor above its bound
+            const uint32_t TB = job.p->total_blocks, pairs = (uint32_t)((Dp / kMomentSide) * (Dp / kMomentSide));
+            const uint32_t want = std::max<uint32_t>(1, 8 * (uint32_t)std::max(1, s->ctx->num_cus) / pairs);
+            a.range_blocks = std::min<uint32_t>(kMomentChainBlocks, std::max<uint32_t>(8, (TB + want - 1) / want));
+        }
+        PCV_HIP(hipEventRecord(job.ev[1], st));  // (behind the memsets)
+        launch_moment_sums(st, *job.p, job.dp, a);
+        PCV_HIP(hipEventRecord(job.ev[2], st));
+        if (out_matrix) {
+            launch_moment_syrk(st, *job.p, job.dp, a);
+            s->moment_stats.row_ranges = (int32_t)moment_row_ranges(*job.p, a);
+        }
+        PCV_HIP(hipEventRecord(job.ev[3], st));
+        PCV_HIP(hipMemcpyAsync(S.data(), d_sums.p, (Dp + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        s->moment_stats.prep_ms = job.elapsed(0);
+        s->moment_stats.sums_ms = job.elapsed(1);
+        s->moment_stats.syrk_ms = out_matrix ? job.elapsed(2) : 0.0f;
+        s->moment_stats.participating = (int64_t)S[Dp];
+        if ((int64_t)S[Dp] > kMaxMomentRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "moments: more than 2^30 participating rows");
+        if (out_matrix) {  // [Dp][Dp] on the device -> [D][D]
+            std::vector<long long> m(3 * Dp * Dp);
+            PCV_HIP(hipMemcpy(m.data(), d_mat.p, m.size() * sizeof(long long), hipMemcpyDeviceToHost));
+            hh.resize(D * D);
+            hl.resize(D * D);
+            ll.resize(D * D);
+            for (size_t d = 0; d < D; ++d)
+                for (size_t e = 0; e < D; ++e) {
+                    hh[d * D + e] = (int64_t)m[d * Dp + e];
+                    hl[d * D + e] = (int64_t)m[Dp * Dp + d * Dp + e];
+                    ll[d * D + e] = (int64_t)m[2 * Dp * Dp + d * Dp + e];
+                }
+        }
+    }
+    std::vector<int64_t> sums(D);
+    for (size_t d = 0; d < D; ++d) sums[d] = (int64_t)S[d];
+    if (out_matrix) {
+        if (hh.empty()) {
+            std::fill(out_matrix, out_matrix + D * D, 0.0);
+        } else {
+            const pcv_status fin = pcv_moments_finish(hh.data(), hl.data(), ll.data(), sums.data(), (int64_t)S[Dp], s->D, centered, out_matrix);
+            if (fin != PCV_OK) throw Error{fin};
+        }
+    }
+    std::copy(sums.begin(), sums.end(), out_sums);
+    *out_n = (int64_t)S[Dp];
+}
+
+void principal_axes(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m, float* out_axes, double* out_offsets, double* out_variance,
+                    int64_t* out_n) {
+    PCV_REQUIRE(m <= s->D, "principal_axes: %d axes of a %d-d space", m, s->D);
+    const size_t D = (size_t)s->D;
+    std::vector<int64_t> sums(D);
+    std::vector<double> cov(D * D), values(D), vectors(D * D);
+    int64_t n = 0;
+    moments(s, source_ids, n_sources, 1, sums.data(), cov.data(), &n);
+    *out_n = n;
+    PCV_REQUIRE(n > 0, "principal_axes: no participating row in the selected sources");
+    const pcv_status eig = pcv_symmetric_eigen(cov.data(), s->D, values.data(), vectors.data());
+    if (eig != PCV_OK) throw Error{eig};
+    const double nn = (double)n;
+    for (int j = 0; j < m; ++j) {
+        double off = 0.0;
+        for (size_t d = 0; d < D; ++d) {
+            const float ax = (float)vectors[(size_t)j * D + d];
+            out_axes[(size_t)j * D + d] = ax;
+            const double mean = (double)sums[d] * 0x1p-32 / nn, term = (double)ax * mean;  // (no contraction: the sum is of rounded products)
+            off = off + term;
+        }
+        out_offsets[j] = off;
+        out_variance[j] = values[(size_t)j] / (nn * nn);
+    }
+}
+
+// Prep, then one pass per group of axes inside project_kernel.  The axes are packed here into the rows' piece layout.
+void project(pcv_searcher* s, const float* axes, const double* offsets, int m, const int64_t* source_ids, int n_sources, int64_t capacity,
+             float* out_coords, int64_t* out_ids, int64_t* out_n) {
+    PCV_REQUIRE(!s->dirty, "project: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "project: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_n = n;
+    if (out_coords == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "project: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    s->project_stats = pcv_project_stats{};
+    s->project_stats.axes = m;
+    s->project_stats.group = m <= 2 ? 2 : 8;
+    if (n == 0) return;
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    const size_t D = (size_t)s->D, D4 = (size_t)s->D4, blocks = ((size_t)m + 31) / 32;
+    std::vector<float> packed(blocks * D4 * 128, 0.0f);
+    for (int j = 0; j < m; ++j) {
+        float* dst = packed.data() + ((size_t)(j >> 5) * D4 * 32 + (size_t)(j & 31)) * 4;  // piece f of axis j: dst + f * 128 floats
+        for (size_t d = 0; d < D; ++d) dst[(d >> 2) * 128 + (d & 3)] = axes[(size_t)j * D + d];
+    }
+    std::vector<double> off((size_t)m, 0.0);
+    if (offsets) std::copy(offsets, offsets + m, off.begin());
+    RowsJob job(s, segs, "project");
+    hipStream_t st = job.st;
+    s->project_stats.rows = job.rows;
+    DevBuf<float> d_axes, d_coords;
+    DevBuf<double> d_off;
+    DevBuf<int64_t> d_ids;
+    d_axes.ensure(packed.size());
+    d_off.ensure((size_t)m);
+    d_coords.ensure((size_t)n * m);
+    if (out_ids) d_ids.ensure((size_t)n);
+    ProjectArgs a{};
+    a.rinv = job.d_rinv.p;
+    a.norm = job.d_norm.p;
+    a.axes = reinterpret_cast<const float4*>(d_axes.p);
+    a.offsets = d_off.p;
+    a.seg_out0 = job.seg_out0;
+    a.out_coords = d_coords.p;
+    a.out_ids = out_ids ? d_ids.p : nullptr;
+    a.m = m;
+    PCV_HIP(hipMemcpyAsync(d_axes.p, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    PCV_HIP(hipMemcpyAsync(d_off.p, off.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+    PCV_HIP(hipEventRecord(job.ev[1], st));  // (behind the uploads)
+    launch_project(st, *job.p, job.dp, a);
+    PCV_HIP(hipEventRecord(job.ev[2], st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    s->project_stats.prep_ms = job.elapsed(0);
+    s->project_stats.project_ms = job.elapsed(1);
+    PCV_HIP(hipMemcpy(out_coords, d_coords.p, (size_t)n * m * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_ids.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+}
+
 void sync_view(pcv_searcher* v);
 
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.
@@ -4636,6 +4854,64 @@ pcv_status pcv_seed_draw(uint64_t seed, int step, uint64_t total, uint64_t* out_
         PCV_REQUIRE(step >= 0, "seed_draw: step %d is negative", step);
         PCV_REQUIRE(total != 0, "seed_draw: total is 0");
         *out_t = seed_draw(seed, (uint32_t)step, total);
+    });
+}
+
+pcv_status pcv_searcher_moments(pcv_searcher* s, const int64_t* source_ids, int n_sources, int centered, int64_t* out_sums, double* out_matrix,
+                                int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(out_sums != nullptr && out_n != nullptr, "moments: out_sums or out_n is NULL");
+        PCV_REQUIRE(s != nullptr, "moments: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "moments: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        moments(s, source_ids, n_sources, centered, out_sums, out_matrix, out_n);
+    });
+}
+
+pcv_status pcv_searcher_last_moment_stats(pcv_searcher* s, pcv_moment_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_moment_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->moment_stats;
+    });
+}
+
+pcv_status pcv_searcher_principal_axes(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m, float* out_axes, double* out_offsets,
+                                       double* out_variance, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(out_axes != nullptr && out_offsets != nullptr && out_variance != nullptr && out_n != nullptr, "principal_axes: an output is NULL");
+        PCV_REQUIRE(m >= 1 && m <= (int)PCV_MAX_AXES, "principal_axes: m %d outside [1,%d]", m, (int)PCV_MAX_AXES);
+        PCV_REQUIRE(s != nullptr, "principal_axes: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "principal_axes: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        principal_axes(s, source_ids, n_sources, m, out_axes, out_offsets, out_variance, out_n);
+    });
+}
+
+pcv_status pcv_searcher_project(pcv_searcher* s, const float* axes, const double* offsets, int m, const int64_t* source_ids, int n_sources,
+                                int64_t capacity, float* out_coords, int64_t* out_ids, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(axes != nullptr && out_n != nullptr, "project: axes or out_n is NULL");
+        PCV_REQUIRE(m >= 1 && m <= (int)PCV_MAX_AXES, "project: m %d outside [1,%d]", m, (int)PCV_MAX_AXES);
+        PCV_REQUIRE(capacity >= 0 && (out_coords != nullptr || capacity == 0), "project: out_coords is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(out_coords != nullptr || out_ids == nullptr, "project: out_ids without out_coords");
+        PCV_REQUIRE(s != nullptr, "project: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (int64_t i = 0; i < (int64_t)m * s->D; ++i) PCV_REQUIRE(std::isfinite(axes[i]), "project: axis %lld has a value that is not finite", (long long)(i / s->D));
+        for (int j = 0; offsets && j < m; ++j) PCV_REQUIRE(std::isfinite(offsets[j]), "project: offset %d is not finite", j);
+        PCV_REQUIRE(!s->pending.active, "project: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        project(s, axes, offsets, m, source_ids, n_sources, capacity, out_coords, out_ids, out_n);
+    });
+}
+
+pcv_status pcv_searcher_last_project_stats(pcv_searcher* s, pcv_project_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_project_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->project_stats;
     });
 }
 

@@ -18,6 +18,7 @@ PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_o
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
 PCV_MAX_SEEDS = 4096  # include/perceive_hip.h
+PCV_MAX_AXES = 64  # include/perceive_hip.h
 _SEED_METHODS = {"farthest": 0, "kmeans++": 1}  # PCV_SEED_FARTHEST, PCV_SEED_KMEANSPP
 
 _METRICS = {"cosine": _ffi.METRIC_COSINE, "dot": _ffi.METRIC_DOT}
@@ -679,6 +680,75 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_last_seed_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.SeedStats._fields_}
 
+    # ---- corpus moments and principal axes (pcv_searcher_moments / _principal_axes / _project) -----
+    # A PCA where the rows live: integer moments of the unit rows, a Jacobi solve on the host, every row's coordinates.
+    def moments(self, sources, centered=False, matrix=True):
+        """The integer moments of the unit rows of `sources` -> (sums [dim] int64: S_d = sum of t(r, d) = rint(x * rinv * 2^32), matrix
+        [dim, dim] f64 or None, n: the participating rows).  With C = T^T T in exact integers the matrix is C * 2^-64 (n times the
+        second moment), or with centered (n C - S S^T) * 2^-64 (n^2 times the covariance), rounded once.  matrix=False: the sums alone."""
+        src, nsrc, _keep = _source_filter(sources)
+        sums = np.zeros(self.dim, dtype=np.int64)
+        mat = np.zeros((self.dim, self.dim), dtype=np.float64) if matrix else None
+        n = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_moments(self._handle, src, nsrc, 1 if centered else 0, _ffi.i64p(sums), None if mat is None else mat.ctypes.data, C.byref(n))
+        )
+        return sums, mat, n.value
+
+    def last_moment_stats(self):
+        st = _ffi.MomentStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_moment_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.MomentStats._fields_}
+
+    def principal_axes(self, sources, m):
+        """The m leading principal axes of the unit rows of `sources` -> (axes [m, dim] f32, offsets [m] f64: the mean unit row along
+        each axis, what project subtracts, variance [m] f64 along each axis, n: the participating rows)."""
+        m = int(m)
+        if not 1 <= m <= PCV_MAX_AXES:
+            raise ValueError("m outside [1, %d]" % PCV_MAX_AXES)
+        src, nsrc, _keep = _source_filter(sources)
+        axes = np.zeros((m, self.dim), dtype=np.float32)
+        offsets = np.zeros(m, dtype=np.float64)
+        variance = np.zeros(m, dtype=np.float64)
+        n = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_principal_axes(self._handle, src, nsrc, m, _ffi.f32p(axes), offsets.ctypes.data, variance.ctypes.data, C.byref(n))
+        )
+        return axes, offsets, variance, n.value
+
+    def project(self, sources, axes, offsets=None):
+        """coord(r, j) = (float)(canonical f64 dot(axes[j], row r) * rinv_r - offsets[j]) for every row of `sources` and every axis
+        (axes [m, dim] f32, offsets [m] f64 or None: zeros) -> (coords [n, m] f32, ids [n] int64), by global position; a row that
+        takes no part has NaN in all m slots."""
+        ax = np.ascontiguousarray(axes, dtype=np.float32)
+        if ax.ndim != 2 or ax.shape[1] != self.dim:
+            raise ValueError(f"axes must be [m, {self.dim}]")
+        m = ax.shape[0]
+        if not 1 <= m <= PCV_MAX_AXES:
+            raise ValueError("m outside [1, %d]" % PCV_MAX_AXES)
+        off = None
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, dtype=np.float64)
+            if off.shape != (m,):
+                raise ValueError(f"offsets must be [{m}]")
+        src, nsrc, _keep = _source_filter(sources)
+        n = C.c_int64()
+        poff = None if off is None else off.ctypes.data
+        _ffi.check(_ffi.lib().pcv_searcher_project(self._handle, _ffi.f32p(ax), poff, m, src, nsrc, 0, None, None, C.byref(n)))
+        n = n.value
+        coords = np.empty((max(n, 1), m), dtype=np.float32)
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        got = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_project(self._handle, _ffi.f32p(ax), poff, m, src, nsrc, max(n, 1), _ffi.f32p(coords), _ffi.i64p(ids), C.byref(got))
+        )
+        return coords[:n], ids[:n]
+
+    def last_project_stats(self):
+        st = _ffi.ProjectStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_project_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.ProjectStats._fields_}
+
     # ---- introspection ------------------------------------------------------------------------
     def set_kernel(self, kernel="auto"):
         _ffi.check(_ffi.lib().pcv_searcher_set_kernel(self._handle, _KERNELS[kernel]))
@@ -929,6 +999,19 @@ def seed_draw(seed, step, total):
     t = C.c_uint64()
     _ffi.check(_ffi.lib().pcv_seed_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(total), C.byref(t)))
     return t.value
+
+
+def symmetric_eigen(a):
+    """Eigenvalues (descending) and unit eigenvectors (rows; the component of largest magnitude positive) of the symmetric matrix `a`
+    [n, n] f64, read from its upper triangle, by cyclic Jacobi on the host (pcv_symmetric_eigen): an offline call, seconds at n = 384."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError("a must be [n, n]")
+    n = a.shape[0]
+    values = np.zeros(n, dtype=np.float64)
+    vectors = np.zeros((n, n), dtype=np.float64)
+    _ffi.check(_ffi.lib().pcv_symmetric_eigen(a.ctypes.data, n, values.ctypes.data, vectors.ctypes.data))
+    return values, vectors
 
 
 def encode_query(model, query):

@@ -99,6 +99,28 @@ pub struct pcv_seed_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_moment_stats {
+    pub rows: i64,
+    pub participating: i64,
+    pub tile_features: i32,
+    pub row_ranges: i32,
+    pub prep_ms: f32,
+    pub sums_ms: f32,
+    pub syrk_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_project_stats {
+    pub rows: i64,
+    pub axes: i32,
+    pub group: i32,
+    pub prep_ms: f32,
+    pub project_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_hit {
     pub score: f64,
     pub pos: i64,
@@ -188,6 +210,7 @@ pub const PCV_MAX_NEIGHBORS: c_int = 64;
 pub const PCV_SEED_FARTHEST: c_int = 0;
 pub const PCV_SEED_KMEANSPP: c_int = 1;
 pub const PCV_MAX_SEEDS: c_int = 4096;
+pub const PCV_MAX_AXES: c_int = 64;
 pub const PCV_GELU_ERF: c_int = 0;
 pub const PCV_GELU_TANH: c_int = 1;
 pub const PCV_POOL_MEAN: c_int = 0;
@@ -277,6 +300,13 @@ extern "C" {
     pub fn pcv_searcher_seeds(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, method: c_int, seed: u64, first_id: *const i64, out_ids: *mut i64, out_positions: *mut i64, out_totals: *mut i64, out_cover: *mut f32, out_count: *mut i32) -> c_int;
     pub fn pcv_searcher_last_seed_stats(s: *mut pcv_searcher, out: *mut pcv_seed_stats) -> c_int;
     pub fn pcv_seed_draw(seed: u64, step: c_int, total: u64, out_t: *mut u64) -> c_int;
+    pub fn pcv_searcher_moments(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, centered: c_int, out_sums: *mut i64, out_matrix: *mut f64, out_n: *mut i64) -> c_int;
+    pub fn pcv_moments_finish(hh: *const i64, hl: *const i64, ll: *const i64, sums: *const i64, n: i64, dim: c_int, centered: c_int, out_matrix: *mut f64) -> c_int;
+    pub fn pcv_searcher_last_moment_stats(s: *mut pcv_searcher, out: *mut pcv_moment_stats) -> c_int;
+    pub fn pcv_symmetric_eigen(a: *const f64, n: c_int, out_values: *mut f64, out_vectors: *mut f64) -> c_int;
+    pub fn pcv_searcher_principal_axes(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, m: c_int, out_axes: *mut f32, out_offsets: *mut f64, out_variance: *mut f64, out_n: *mut i64) -> c_int;
+    pub fn pcv_searcher_project(s: *mut pcv_searcher, axes: *const f32, offsets: *const f64, m: c_int, source_ids: *const i64, n_sources: c_int, capacity: i64, out_coords: *mut f32, out_ids: *mut i64, out_n: *mut i64) -> c_int;
+    pub fn pcv_searcher_last_project_stats(s: *mut pcv_searcher, out: *mut pcv_project_stats) -> c_int;
     pub fn pcv_duplicate_groups(id_a: *const i64, id_b: *const i64, n_pairs: i64, out_ids: *mut i64, out_group: *mut i64, capacity: i64, out_n_ids: *mut i64) -> c_int;
     pub fn pcv_searcher_like_queries(s: *mut pcv_searcher, example_ids: *const i64, weights: *const f32, offsets: *const i64, n_queries: c_int, out_queries: *mut f32, d_out_queries: *mut c_void, out_found: *mut u8, out_member_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_search_like(s: *mut pcv_searcher, example_ids: *const i64, weights: *const f32, offsets: *const i64, n_queries: c_int, source_ids: *const i64, n_sources: c_int, k: c_int, exclude_examples: c_int, out_ids: *mut i64, out_scores: *mut f32, out_counts: *mut c_int, out_found: *mut u8) -> c_int;

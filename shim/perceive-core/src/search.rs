@@ -640,6 +640,107 @@ impl Searcher {
         (0..n as usize).map(|i| (ids[i], positions[i], totals[i], cover[i])).collect()
     }
 
+    /// Corpus moments (`pcv_searcher_moments`): the integer sums S_d of the fixed-point unit rows of `sources`, the participating
+    /// rows n, and — with `matrix` — C * 2^-64 (`centered`: (n C - S S^T) * 2^-64) as [dim][dim] f64, C = T^T T in exact integers.
+    pub fn moments(&self, sources: &[i64], centered: bool, matrix: bool) -> (Vec<i64>, Vec<f64>, i64) {
+        if self.handle.is_null() {
+            return (Vec::new(), Vec::new(), 0);
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("dim failed");
+        let dim = dim as usize;
+        let mut sums = vec![0i64; dim];
+        let mut mat = vec![0f64; if matrix { dim * dim } else { 0 }];
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_moments(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                centered as i32,
+                sums.as_mut_ptr(),
+                if matrix { mat.as_mut_ptr() } else { std::ptr::null_mut() },
+                &mut n,
+            )
+        })
+        .expect("moments failed");
+        (sums, mat, n)
+    }
+
+    /// Principal axes (`pcv_searcher_principal_axes`): the `m` leading axes (clamped to PCV_MAX_AXES) of the unit rows of
+    /// `sources` as ([m][dim] axes, [m] offsets: the mean along each axis, [m] variances, participating rows).
+    pub fn principal_axes(&self, sources: &[i64], m: usize) -> (Vec<f32>, Vec<f64>, Vec<f64>, i64) {
+        if self.handle.is_null() || m == 0 || sources.is_empty() {
+            return (Vec::new(), Vec::new(), Vec::new(), 0);
+        }
+        let m = m.min(ffi::PCV_MAX_AXES as usize);
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("dim failed");
+        let mut axes = vec![0f32; m * dim as usize];
+        let mut offsets = vec![0f64; m];
+        let mut variance = vec![0f64; m];
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_principal_axes(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                m as i32,
+                axes.as_mut_ptr(),
+                offsets.as_mut_ptr(),
+                variance.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("principal_axes failed");
+        (axes, offsets, variance, n)
+    }
+
+    /// Projection (`pcv_searcher_project`): (float)(canonical dot(axes[j], row) * rinv - offsets[j]) for every item of `sources`, by
+    /// global position, as (item id, its m coordinates); NaN for an item no search could return.  `axes` is [m][dim].
+    pub fn project(&self, sources: &[i64], axes: &[f32], offsets: Option<&[f64]>, m: usize) -> Vec<(i64, Vec<f32>)> {
+        if self.handle.is_null() || m == 0 || sources.is_empty() {
+            return Vec::new();
+        }
+        assert!(m <= ffi::PCV_MAX_AXES as usize && axes.len() % m == 0 && offsets.map_or(true, |o| o.len() == m));
+        let off = offsets.map_or(std::ptr::null(), |o| o.as_ptr());
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_project(
+                self.handle,
+                axes.as_ptr(),
+                off,
+                m as i32,
+                sources.as_ptr(),
+                sources.len() as i32,
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                &mut n,
+            )
+        })
+        .expect("project failed");
+        let room = n.max(1) as usize;
+        let mut coords = vec![f32::NAN; room * m];
+        let mut ids = vec![-1i64; room];
+        hip::check(unsafe {
+            ffi::pcv_searcher_project(
+                self.handle,
+                axes.as_ptr(),
+                off,
+                m as i32,
+                sources.as_ptr(),
+                sources.len() as i32,
+                room as i64,
+                coords.as_mut_ptr(),
+                ids.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("project failed");
+        (0..n as usize).map(|i| (ids[i], coords[i * m..(i + 1) * m].to_vec())).collect()
+    }
+
     pub fn search(&self, model: &Model, sources: &[i64], num_results: usize, query: &str) -> Vec<SearchItem> {
         let term_embedding = encode_query(model, query);
         self.search_vector(sources, num_results, term_embedding)
