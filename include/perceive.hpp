@@ -284,6 +284,34 @@ inline NeighborTable neighbors_handle(pcv_searcher* h, const std::vector<int64_t
     return r;
 }
 
+// Searcher::density_clusters / SearcherView::density_clusters (pcv_searcher_density_clusters): DBSCAN under the cosine over the items
+// of `sources`, by global position — the clusters, their number and the noise, with no number of groups to choose.
+struct DensityClusters {
+    std::vector<int64_t> ids;      // [n]
+    std::vector<int32_t> labels;   // [n] the cluster; -1: noise, or the item takes no part
+    std::vector<int8_t> kinds;     // [n] PCV_DENSITY_CORE, _BORDER, _NOISE or _NONE
+    std::vector<int32_t> degrees;  // [n] the other items within the threshold
+    int32_t clusters = 0;
+};
+inline DensityClusters density_clusters_handle(pcv_searcher* h, const std::vector<int64_t>& sources, float threshold, int min_items) {
+    DensityClusters r;
+    if (sources.empty()) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    check(pcv_searcher_density_clusters(h, sources.data(), (int)sources.size(), threshold, min_items, 0, nullptr, nullptr, nullptr, nullptr, &n, nullptr));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.ids.resize(room);
+    r.labels.resize(room);
+    r.kinds.resize(room);
+    r.degrees.resize(room);
+    check(pcv_searcher_density_clusters(h, sources.data(), (int)sources.size(), threshold, min_items, (int64_t)room, r.ids.data(), r.labels.data(),
+                                        r.kinds.data(), r.degrees.data(), &n, &r.clusters));
+    r.ids.resize((size_t)n);
+    r.labels.resize((size_t)n);
+    r.kinds.resize((size_t)n);
+    r.degrees.resize((size_t)n);
+    return r;
+}
+
 // Searcher::seeds / SearcherView::seeds (pcv_searcher_seeds): up to k items that cover `sources`, in the order they were picked —
 // the init of kmeans (k-means++), or a representative sample with its covering radii (farthest first).
 enum class SeedMethod { Farthest = PCV_SEED_FARTHEST, KMeansPP = PCV_SEED_KMEANSPP };
@@ -475,6 +503,15 @@ public:
         check(pcv_searcher_last_project_stats(h_, &st));
         return st;
     }
+    // density clusters of the view's items (density_clusters_handle)
+    DensityClusters density_clusters(const std::vector<int64_t>& sources, float threshold, int min_items) const {
+        return density_clusters_handle(h_, sources, threshold, min_items);
+    }
+    pcv_density_stats last_density_stats() const {
+        pcv_density_stats st;
+        check(pcv_searcher_last_density_stats(h_, &st));
+        return st;
+    }
     // the k nearest other items of every item of the view (neighbors_handle)
     NeighborTable neighbors(const std::vector<int64_t>& sources, size_t k) const { return neighbors_handle(h_, sources, k); }
     pcv_neighbor_stats last_neighbor_stats() const {
@@ -633,6 +670,15 @@ public:
     pcv_project_stats last_project_stats() const {
         pcv_project_stats st;
         check(pcv_searcher_last_project_stats(h_, &st));
+        return st;
+    }
+    // density clusters (DBSCAN under the cosine) of the items, found on the device (density_clusters_handle)
+    DensityClusters density_clusters(const std::vector<int64_t>& sources, float threshold, int min_items) const {
+        return density_clusters_handle(h_, sources, threshold, min_items);
+    }
+    pcv_density_stats last_density_stats() const {
+        pcv_density_stats st;
+        check(pcv_searcher_last_density_stats(h_, &st));
         return st;
     }
     // the k nearest other items of every item, found once on the device (neighbors_handle)

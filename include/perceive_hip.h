@@ -648,6 +648,69 @@ typedef struct pcv_neighbor_stats {
 } pcv_neighbor_stats;
 pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats* out);
 
+/* Density clusters: DBSCAN under the cosine over the stored items, exact, computed where the rows live — which topics a library
+ * holds, how many, and which items belong to none, without the caller choosing a number of groups; degree(r) is a density and
+ * outlier score of its own.
+ * The rows concerned are those of the selected segments in global position order, n of them, exactly as in
+ * pcv_searcher_find_duplicates and pcv_searcher_neighbors (hidden and unsearchable rows included: they keep their place);
+ * source_ids == NULL means all sources, an empty list selects nothing (n = 0); a view clusters its own rows.  A row TAKES PART iff a
+ * pcv_searcher_search with the same filter could return it (scale != 0, not hidden) and it has a cosine (canonical |x|^2 in
+ * [2^-126, inf)).  For two different participating positions a, b: near(a, b) <=> c(a, b) >= (double)threshold, c the canonical
+ * cosine of the two stored f32 rows — f64, products exact, sums in feature order — for BOTH metrics.
+ *   degree(r)   the number of other participating rows p with near(r, p)
+ *   core        r is a core row iff degree(r) + 1 >= min_items (min_items counts the item itself: DBSCAN's min_samples)
+ *   clusters    the connected components of the graph on the core rows with the edges near; numbered 0, 1, ... in ascending order
+ *               of the lowest global position among their core rows
+ *   border      a participating row that is not core and has a core row near it; it takes the label of the core row near it with
+ *               the LOWEST GLOBAL POSITION (no score enters this rule)
+ *   noise       every other participating row
+ *   threshold   in (-1, 1]
+ *   min_items   >= 1
+ *   capacity    rows the outputs have room for; capacity < n gives PCV_ERR_INVALID (out_rows is set)
+ *   out_ids     [capacity] the item id of every position; may be NULL
+ *   out_label   [capacity] the cluster, or -1 for noise and for rows that take no part
+ *   out_kind    [capacity] PCV_DENSITY_CORE, _BORDER, _NOISE, or _NONE (the row takes no part)
+ *   out_degree  [capacity] degree; 0 for _NONE rows; may be NULL
+ *   out_rows    n.  With every array NULL and capacity == 0 the call only reports n and does no device work (out_clusters may be
+ *               NULL then, and is not written)
+ *   out_clusters the number of clusters
+ * A NULL searcher or out_rows, a NaN or out-of-range threshold, min_items < 1, a negative capacity, a NULL out_label, out_kind or
+ * out_clusters with the other arrays given or capacity != 0, capacity < n, and a sharded searcher (pcv_searcher_set_shard_offset
+ * != 0 or a pcv_comm: a cluster lies in every shard) give PCV_ERR_INVALID before any device work; a searcher with pending rows fails
+ * as in pcv_searcher_search.  PCV_ERR_UNSUPPORTED, with the searcher still usable: a dimension whose bf16 row tile does not fit the
+ * LDS of a CU (above 2496); more than 2^30 rows; more than 2^28 pairs that the bf16 screen cannot decide (pairs within its certified
+ * margin of the threshold, and every pair with a row whose length is outside [2^-20, 2^20]) — the message names the count, and the
+ * error comes before the larger list is allocated.  Pairs the screen decides are counted and linked inside its kernel and never
+ * listed, so the number of near pairs is not limited.  The result does not depend on which screening copies exist, nor on
+ * pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity: the call reads the f32 rows and touches no pass state (DESIGN.md §4
+ * "Density clusters").  Everything it allocates on the device is given back when it returns.  Not in scope: a sharded form and
+ * device-resident output. */
+enum { PCV_DENSITY_NONE = -1, PCV_DENSITY_NOISE = 0, PCV_DENSITY_BORDER = 1, PCV_DENSITY_CORE = 2 };
+pcv_status pcv_searcher_density_clusters(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int min_items,
+                                         int64_t capacity, int64_t* out_ids, int32_t* out_label, int8_t* out_kind, int32_t* out_degree,
+                                         int64_t* out_rows, int32_t* out_clusters);
+
+/* Counters of the most recent pcv_searcher_density_clusters on this handle (all zero after a call that only reported n). */
+typedef struct pcv_density_stats {
+    int64_t rows;           /* rows of the selected segments (those taking no part included)                   */
+    int64_t participating;  /* rows that take part                                                             */
+    int64_t sure_pairs;     /* near pairs the bf16 screen decided alone (never listed, never rescored)         */
+    int64_t candidates;     /* band pairs the screen listed for the f64 step                                   */
+    int64_t confirmed;      /* band pairs with c >= threshold                                                  */
+    int64_t core;
+    int64_t border;
+    int64_t noise;
+    int32_t clusters;
+    int32_t tile_rows;      /* rows of the LDS tile the screen kernel staged                                   */
+    int32_t reruns;         /* degree passes repeated because the band list was short                          */
+    float prep_ms;          /* hipEvent times of the steps (a repeated degree pass included in degree_ms)      */
+    float degree_ms;
+    float rescore_ms;
+    float link_ms;
+    float label_ms;
+} pcv_density_stats;
+pcv_status pcv_searcher_last_density_stats(pcv_searcher* s, pcv_density_stats* out);
+
 /* Seed items: k stored items that cover the corpus, picked one after the other where the rows live — the init pcv_searcher_kmeans
  * asks for (k-means++), or a representative sample whose covering radii tell how many topics a library holds (farthest first).
  * The rows concerned are those of the selected segments in global position order, as in pcv_searcher_neighbors; source_ids == NULL

@@ -94,6 +94,27 @@ class NeighborStats(C.Structure):
     ]
 
 
+class DensityStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("participating", C.c_int64),
+        ("sure_pairs", C.c_int64),
+        ("candidates", C.c_int64),
+        ("confirmed", C.c_int64),
+        ("core", C.c_int64),
+        ("border", C.c_int64),
+        ("noise", C.c_int64),
+        ("clusters", C.c_int32),
+        ("tile_rows", C.c_int32),
+        ("reruns", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("degree_ms", C.c_float),
+        ("rescore_ms", C.c_float),
+        ("link_ms", C.c_float),
+        ("label_ms", C.c_float),
+    ]
+
+
 class GroupStats(C.Structure):
     _fields_ = [
         ("ids", C.c_int64),
@@ -172,6 +193,7 @@ _I64P = C.c_void_p  # int64_t*
 _F32P = C.c_void_p  # float*
 _U8P = C.c_void_p  # uint8_t*
 _INTP = C.c_void_p  # int* / int32_t*
+_I8P = C.c_void_p  # int8_t*
 _F64P = C.c_void_p  # double*
 # int visit(void* user, const char* name, const int64_t* shape, int rank, int dtype, const float* values, int64_t numel)
 TENSOR_VISITOR = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int64)
@@ -241,6 +263,9 @@ SYMBOLS = {
     "pcv_searcher_last_assign_stats": (C.c_int, [_P, C.POINTER(AssignStats)]),
     "pcv_searcher_neighbors": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int64, _I64P, _I64P, _F32P, _INTP, C.POINTER(C.c_int64)]),
     "pcv_searcher_last_neighbor_stats": (C.c_int, [_P, C.POINTER(NeighborStats)]),
+    "pcv_searcher_density_clusters": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int, C.c_int64, _I64P, _INTP, _I8P, _INTP,
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "pcv_searcher_last_density_stats": (C.c_int, [_P, C.POINTER(DensityStats)]),
     "pcv_searcher_seeds": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int, C.c_uint64, _I64P, _I64P, _I64P, _I64P, _F32P, _INTP]),
     "pcv_searcher_last_seed_stats": (C.c_int, [_P, C.POINTER(SeedStats)]),
     "pcv_seed_draw": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -346,4 +371,8 @@ def u8p(a):
 
 
 def i32p(a):
+    return a.ctypes.data
+
+
+def i8p(a):
     return a.ctypes.data

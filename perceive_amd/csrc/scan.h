@@ -471,6 +471,53 @@ struct ProjectArgs {
     int m;
 };
 
+// Density clusters (pcv_searcher_density_clusters; DESIGN.md §4 "Density clusters"): DBSCAN under the canonical cosine.  Rows are
+// launch rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  near(a, b) <=> c(a, b) >= threshold; the screening score s
+// of a pair of certified rows decides it alone where s >= hi (near: a SURE pair) or s < lo (not near); the band between, and every
+// pair with a wild row, is listed and decided by the f64 step.
+//   degree[launch row] : partners near the row (sure pairs and confirmed band pairs, each counted once for both rows)
+//   core[launch row]   : 1 iff the row takes part and degree + 1 >= min_items
+//   parent[launch row] : the union-find forest over the core rows; parent[r] <= r always, so a component's root is its core row of
+//                        the lowest global position
+//   attach[launch row] : the lowest core launch row near a row that is not core (UINT32_MAX: none)
+//   root / rank        : after the link step: the root of a core row's component, or of the component a border row attaches to
+//                        (UINT32_MAX: noise or no part); rank[r] = roots at launch rows below r = the cluster number of root r
+struct DensityArgs {
+    float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    double* norm;                   // [total_blocks * 32]
+    uint64_t* cand;                 // [cand_cap] band pairs, (launch row a << 32) | launch row b, a < b
+    uint64_t* conf;                 // [n_cand] the band pairs with c >= threshold, in any order
+    unsigned long long* counters;   // kDensity* below
+    uint32_t* degree;               // [(total_blocks + tile_blocks) * 32]
+    uint8_t* core;                  // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    uint32_t* parent;               // [total_blocks * 32]
+    uint32_t* attach;               // [total_blocks * 32]
+    uint32_t* root;                 // [total_blocks * 32]
+    uint32_t* rank;                 // [total_blocks * 32]
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    int32_t* out_label;             // [rows]
+    int8_t* out_kind;               // [rows]
+    int32_t* out_degree;            // [rows]
+    int64_t* out_ids;               // [rows]
+    unsigned long long cand_cap, n_cand;
+    float hi, lo;                   // threshold + margin rounded up, threshold - margin rounded down
+    double threshold;
+    int min_items;
+    uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
+    uint32_t span_blocks;           // blocks of one work item's stream
+};
+enum : int {
+    kDensityBand = 0,       // band pairs the degree pass found (not capped)
+    kDensityConfirmed,      // band pairs with c >= threshold
+    kDensitySure,           // pairs the screen decided alone
+    kDensityParticipating,
+    kDensityCore,
+    kDensityBorder,
+    kDensityNoise,
+    kDensityClusters,
+    kDensityCounters
+};
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -540,6 +587,12 @@ void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const Neigh
 void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);     // thr -> cand
 void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);  // cand -> sorted_*
 void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);   // sorted_* -> outputs
+// ---- density clusters (density_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_density_degree(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);   // -> degree, cand, counters
+void launch_density_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);  // cand -> degree, conf
+void launch_density_core(hipStream_t st, const ScanParams& p, const DensityArgs& a);                           // degree -> core, parent, attach
+void launch_density_link(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);     // sure pairs, conf -> parent, attach
+void launch_density_labels(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);   // parent, attach -> outputs
 // ---- seed items (seed_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
 void launch_seed_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // cover = none, the partials of step 0
 void launch_seed_cover(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // the last pick -> cover, the partials of a.step

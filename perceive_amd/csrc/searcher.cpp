@@ -257,6 +257,7 @@ struct pcv_searcher {
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
     pcv_neighbor_stats nbr_stats{};   // pcv_searcher_neighbors (likewise)
     pcv_seed_stats seed_stats{};      // pcv_searcher_seeds (likewise)
+    pcv_density_stats density_stats{};  // pcv_searcher_density_clusters (likewise)
     pcv_moment_stats moment_stats{};  // pcv_searcher_moments / _principal_axes (likewise)
     pcv_project_stats project_stats{};  // pcv_searcher_project (likewise)
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning
@@ -3321,6 +3322,189 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     stats.listed = listed;
 }
 
+// ---- density clusters (pcv_searcher_density_clusters; DESIGN.md §4 "Density clusters") ----
+constexpr uint64_t kMaxDensityBand = (uint64_t)1 << 28;  // band pairs the degree pass may list: 8 bytes each, and 8 more if confirmed
+constexpr int64_t kMaxDensityRows = (int64_t)1 << 30;
+
+// Prep, degree pass, rescore of the band, core flags, link pass, labels (density_kernels.hip), with find_duplicates' plumbing: the
+// row table, the tile choice, the spans and the rerun-once rule for a short band list.  The host waits where the band count decides
+// an allocation and at the end.  Everything the call allocates is its own and is given back when it ends: nothing of the searcher's
+// pass state is touched, and only the f32 rows are read.
+void density_clusters(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int min_items, int64_t capacity,
+                      int64_t* out_ids, int32_t* out_label, int8_t* out_kind, int32_t* out_degree, int64_t* out_rows, int32_t* out_clusters) {
+    PCV_REQUIRE(!s->dirty, "density_clusters: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "density_clusters: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_rows = n;
+    s->density_stats = pcv_density_stats{};
+    if (out_label == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "density_clusters: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity,
+                (long long)n);
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "density_clusters: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (n > kMaxDensityRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "density_clusters: %lld rows, more than 2^30", (long long)n);
+    *out_clusters = 0;
+    if (n == 0) return;
+    PCV_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+
+    const size_t off_seg = align_up(sizeof(ScanParams)), off_out0 = align_up(off_seg + segs.size() * sizeof(SegDesc));
+    const size_t bytes = off_out0 + segs.size() * sizeof(int64_t);
+    PinBuf<uint8_t> pin_p;
+    DevBuf<uint8_t> d_p;
+    pin_p.ensure(bytes);
+    d_p.ensure(bytes);
+    ScanParams& p = *new (pin_p.p) ScanParams{};
+    int64_t rows = 0;
+    p.total_blocks = fill_row_table(segs, reinterpret_cast<SegDesc*>(pin_p.p + off_seg), reinterpret_cast<int64_t*>(pin_p.p + off_out0), rows,
+                                    "density_clusters");
+    p.seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
+    p.nseg = (int)segs.size();
+    p.D = s->D;
+    p.D4 = s->D4;
+    p.metric = PCV_METRIC_COSINE;
+    const ScanParams* dp = reinterpret_cast<const ScanParams*>(d_p.p);
+
+    DensityArgs a{};
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    a.span_blocks = kJoinSpanBlocks;
+    while ((p.total_blocks + a.span_blocks - 1) / a.span_blocks > 65535u) a.span_blocks *= 2;  // (the grid's second dimension)
+    // thr + margin rounded up, thr - margin rounded down, both from f64: s >= hi certifies c >= thr, s < lo certifies c < thr
+    const double margin = (double)selfjoin_margin(s->Dp);
+    a.threshold = (double)threshold;
+    a.hi = std::nextafterf((float)((double)threshold + margin), INFINITY);
+    a.lo = std::nextafterf((float)((double)threshold - margin), -INFINITY);
+    a.min_items = min_items;
+    const size_t nr = (size_t)p.total_blocks * kBlockRows, n_pad = ((size_t)p.total_blocks + a.tile_blocks) * kBlockRows;
+    DevBuf<float> d_rinv;
+    DevBuf<double> d_norm;
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<uint64_t> d_cand, d_conf;
+    DevBuf<uint32_t> d_degree, d_rows4;  // d_rows4: parent, attach, root, rank
+    DevBuf<uint8_t> d_core;
+    DevBuf<int32_t> d_label, d_out_degree;
+    DevBuf<int8_t> d_kind;
+    DevBuf<int64_t> d_out_ids;
+    d_rinv.ensure(n_pad);
+    d_norm.ensure(nr);
+    d_cnt.ensure(kDensityCounters);
+    d_degree.ensure(n_pad);
+    d_core.ensure(n_pad);
+    d_rows4.ensure(4 * nr);
+    d_label.ensure((size_t)rows);
+    d_out_degree.ensure((size_t)rows);
+    d_kind.ensure((size_t)rows);
+    d_out_ids.ensure((size_t)rows);
+    a.cand_cap = std::min<uint64_t>(kMaxDensityBand, std::max<uint64_t>(65536, 2 * (uint64_t)rows));
+    d_cand.ensure(a.cand_cap);
+    a.rinv = d_rinv.p;
+    a.norm = d_norm.p;
+    a.counters = d_cnt.p;
+    a.cand = d_cand.p;
+    a.degree = d_degree.p;
+    a.core = d_core.p;
+    a.parent = d_rows4.p;
+    a.attach = d_rows4.p + nr;
+    a.root = d_rows4.p + 2 * nr;
+    a.rank = d_rows4.p + 3 * nr;
+    a.seg_out0 = reinterpret_cast<const int64_t*>(d_p.p + off_out0);
+    a.out_label = d_label.p;
+    a.out_kind = d_kind.p;
+    a.out_degree = d_out_degree.p;
+    a.out_ids = d_out_ids.p;
+
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const auto drop_events = at_exit([&] {
+        (void)hipStreamSynchronize(st);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    });
+    for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
+    auto elapsed = [&](int from) {
+        float ms = 0.0f;
+        PCV_HIP(hipEventElapsedTime(&ms, ev[from], ev[from + 1]));
+        return ms;
+    };
+    pcv_density_stats& stats = s->density_stats;
+    stats.rows = rows;
+    stats.tile_rows = tile;
+
+    SelfJoinArgs prep{};
+    prep.rinv = d_rinv.p;
+    prep.norm = d_norm.p;
+    unsigned long long counts[kDensityCounters] = {};
+    PCV_HIP(hipMemcpyAsync(d_p.p, pin_p.p, bytes, hipMemcpyHostToDevice, st));
+    PCV_HIP(hipMemsetAsync(d_rinv.p, 0, n_pad * sizeof(float), st));
+    PCV_HIP(hipMemsetAsync(d_degree.p, 0, n_pad * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_core.p, 0, n_pad * sizeof(uint8_t), st));
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kDensityCounters * sizeof(unsigned long long), st));
+    PCV_HIP(hipEventRecord(ev[0], st));
+    launch_selfjoin_prep(st, p, dp, prep);
+    PCV_HIP(hipEventRecord(ev[1], st));
+    launch_density_degree(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[2], st));
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    stats.prep_ms = elapsed(0);
+    stats.degree_ms = elapsed(1);
+    const uint64_t n_cand = counts[kDensityBand];
+    stats.candidates = (int64_t)n_cand;
+    stats.sure_pairs = (int64_t)counts[kDensitySure];
+    if (n_cand > kMaxDensityBand)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                 "density_clusters: %llu pairs lie within the screen's margin of threshold %g or hold a row it is not certified for, more than "
+                 "%llu (2^28): move the threshold or cluster fewer rows",
+                 (unsigned long long)n_cand, (double)threshold, (unsigned long long)kMaxDensityBand);
+    if (n_cand > a.cand_cap) {  // once more, with the room the count asks for (the pass finds the same pairs again)
+        a.cand_cap = n_cand;
+        d_cand.ensure(a.cand_cap);
+        a.cand = d_cand.p;
+        PCV_HIP(hipMemsetAsync(d_degree.p, 0, n_pad * sizeof(uint32_t), st));
+        PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kDensityCounters * sizeof(unsigned long long), st));
+        PCV_HIP(hipEventRecord(ev[1], st));
+        launch_density_degree(st, p, dp, a);
+        PCV_HIP(hipEventRecord(ev[2], st));
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        PCV_REQUIRE(counts[kDensityBand] == n_cand && counts[kDensitySure] == (unsigned long long)stats.sure_pairs,
+                    "density_clusters: the repeated degree pass found %llu band and %llu sure pairs, the first %llu and %lld", counts[kDensityBand],
+                    counts[kDensitySure], (unsigned long long)n_cand, (long long)stats.sure_pairs);
+        stats.reruns = 1;
+        stats.degree_ms += elapsed(1);
+    }
+    a.n_cand = n_cand;
+    d_conf.ensure((size_t)std::max<uint64_t>(1, n_cand));
+    a.conf = d_conf.p;
+    PCV_HIP(hipEventRecord(ev[2], st));
+    launch_density_rescore(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[3], st));
+    launch_density_core(st, p, a);
+    launch_density_link(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[4], st));
+    launch_density_labels(st, p, dp, a);
+    PCV_HIP(hipEventRecord(ev[5], st));
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    PCV_HIP(hipStreamSynchronize(st));
+    PCV_HIP(hipGetLastError());
+    stats.rescore_ms = elapsed(2);
+    stats.link_ms = elapsed(3);
+    stats.label_ms = elapsed(4);
+    stats.confirmed = (int64_t)counts[kDensityConfirmed];
+    stats.participating = (int64_t)counts[kDensityParticipating];
+    stats.core = (int64_t)counts[kDensityCore];
+    stats.border = (int64_t)counts[kDensityBorder];
+    stats.noise = (int64_t)counts[kDensityNoise];
+    stats.clusters = (int32_t)counts[kDensityClusters];
+    PCV_HIP(hipMemcpy(out_label, d_label.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_kind, d_kind.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
+    if (out_degree) PCV_HIP(hipMemcpy(out_degree, d_out_degree.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    *out_clusters = stats.clusters;
+}
+
 // ---- seed items (pcv_searcher_seeds; DESIGN.md §4 "Seed items") ----
 // Prep, begin, then k picks with a cover step between them (seed_kernels.hip): 2k launches queued on the searcher's stream and one
 // wait behind the last.  Everything the call allocates is its own and is given back when it ends: nothing of the searcher's pass
@@ -4821,6 +5005,35 @@ pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats*
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_neighbor_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->nbr_stats;
+    });
+}
+
+pcv_status pcv_searcher_density_clusters(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int min_items,
+                                         int64_t capacity, int64_t* out_ids, int32_t* out_label, int8_t* out_kind, int32_t* out_degree,
+                                         int64_t* out_rows, int32_t* out_clusters) {
+    return guarded([&] {
+        PCV_REQUIRE(out_rows != nullptr, "density_clusters: out_rows is NULL");
+        PCV_REQUIRE(threshold == threshold, "density_clusters: threshold is NaN");
+        PCV_REQUIRE(threshold > -1.0f && threshold <= 1.0f, "density_clusters: threshold %g outside (-1, 1]", (double)threshold);
+        PCV_REQUIRE(min_items >= 1, "density_clusters: min_items %d is below 1", min_items);
+        PCV_REQUIRE(capacity >= 0, "density_clusters: capacity %lld is negative", (long long)capacity);
+        const bool all = out_label != nullptr && out_kind != nullptr && out_clusters != nullptr;
+        const bool none = out_label == nullptr && out_kind == nullptr && out_degree == nullptr && out_ids == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "density_clusters: out_label, out_kind or out_clusters is NULL with capacity %lld",
+                    (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "density_clusters: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "density_clusters: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        density_clusters(s, source_ids, n_sources, threshold, min_items, capacity, out_ids, out_label, out_kind, out_degree, out_rows, out_clusters);
+    });
+}
+
+pcv_status pcv_searcher_last_density_stats(pcv_searcher* s, pcv_density_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_density_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->density_stats;
     });
 }
 

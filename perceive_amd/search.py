@@ -18,6 +18,7 @@ PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_o
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
 PCV_MAX_SEEDS = 4096  # include/perceive_hip.h
+PCV_DENSITY_NONE, PCV_DENSITY_NOISE, PCV_DENSITY_BORDER, PCV_DENSITY_CORE = -1, 0, 1, 2  # include/perceive_hip.h: out_kind
 PCV_MAX_AXES = 64  # include/perceive_hip.h
 _SEED_METHODS = {"farthest": 0, "kmeans++": 1}  # PCV_SEED_FARTHEST, PCV_SEED_KMEANSPP
 
@@ -645,6 +646,41 @@ class Searcher:
         st = _ffi.NeighborStats()
         _ffi.check(_ffi.lib().pcv_searcher_last_neighbor_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.NeighborStats._fields_}
+
+    # ---- density clusters (pcv_searcher_density_clusters) -------------------------------------------
+    # DBSCAN under the canonical cosine: the clusters, their number and the noise, with no number of groups to choose.
+    def density_clusters(self, sources, threshold, min_items):
+        """Two rows are near iff their canonical cosine is >= threshold (both metrics); a row with min_items - 1 near rows or more
+        is a core row; clusters are the connected components of the core rows, numbered by their first core row; a row near a core
+        row takes the label of the one stored first (a border row); the rest is noise.  -> (ids [n] int64, labels [n] int32: -1 for
+        noise and for rows that take no part, kinds [n] int8: PCV_DENSITY_CORE / _BORDER / _NOISE / _NONE, degrees [n] int32: the
+        near rows of each row, n_clusters), by global position.  A view clusters its own rows."""
+        threshold, min_items = float(threshold), int(min_items)
+        if not -1.0 < threshold <= 1.0:
+            raise ValueError("threshold outside (-1, 1]")
+        if min_items < 1:
+            raise ValueError("min_items below 1")
+        src, nsrc, _keep = _source_filter(sources)
+        n = C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_density_clusters(self._handle, src, nsrc, threshold, min_items, 0, None, None, None, None, C.byref(n), None))
+        n = n.value
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        labels = np.empty(max(n, 1), dtype=np.int32)
+        kinds = np.empty(max(n, 1), dtype=np.int8)
+        degrees = np.empty(max(n, 1), dtype=np.int32)
+        got, clusters = C.c_int64(), C.c_int32()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_density_clusters(
+                self._handle, src, nsrc, threshold, min_items, max(n, 1), _ffi.i64p(ids), _ffi.i32p(labels),
+                _ffi.i8p(kinds), _ffi.i32p(degrees), C.byref(got), C.byref(clusters),
+            )
+        )
+        return ids[:n], labels[:n], kinds[:n], degrees[:n], clusters.value
+
+    def last_density_stats(self):
+        st = _ffi.DensityStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_density_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.DensityStats._fields_}
 
     # ---- seed items (pcv_searcher_seeds) ------------------------------------------------------------
     # k items that cover the corpus, picked one after the other on the device: the init of kmeans, or a representative sample.

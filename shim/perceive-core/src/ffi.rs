@@ -5,6 +5,7 @@
 //! counts, integer widths, struct fields).
 #![allow(non_camel_case_types, dead_code)]
 use std::os::raw::{c_char, c_int, c_void};
+pub type int8_t = i8;
 
 /// opaque handle
 #[repr(C)]
@@ -84,6 +85,27 @@ pub struct pcv_neighbor_stats {
     pub screen_ms: f32,
     pub rescore_ms: f32,
     pub select_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_density_stats {
+    pub rows: i64,
+    pub participating: i64,
+    pub sure_pairs: i64,
+    pub candidates: i64,
+    pub confirmed: i64,
+    pub core: i64,
+    pub border: i64,
+    pub noise: i64,
+    pub clusters: i32,
+    pub tile_rows: i32,
+    pub reruns: i32,
+    pub prep_ms: f32,
+    pub degree_ms: f32,
+    pub rescore_ms: f32,
+    pub link_ms: f32,
+    pub label_ms: f32,
 }
 
 #[repr(C)]
@@ -207,6 +229,10 @@ pub const PCV_MAX_GROUPED_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
 pub const PCV_MAX_NEIGHBORS: c_int = 64;
+pub const PCV_DENSITY_NONE: c_int = -1;
+pub const PCV_DENSITY_NOISE: c_int = 0;
+pub const PCV_DENSITY_BORDER: c_int = 1;
+pub const PCV_DENSITY_CORE: c_int = 2;
 pub const PCV_SEED_FARTHEST: c_int = 0;
 pub const PCV_SEED_KMEANSPP: c_int = 1;
 pub const PCV_MAX_SEEDS: c_int = 4096;
@@ -297,6 +323,8 @@ extern "C" {
     pub fn pcv_searcher_last_assign_stats(s: *mut pcv_searcher, out: *mut pcv_assign_stats) -> c_int;
     pub fn pcv_searcher_neighbors(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, capacity: i64, out_ids: *mut i64, out_neighbor_ids: *mut i64, out_scores: *mut f32, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_last_neighbor_stats(s: *mut pcv_searcher, out: *mut pcv_neighbor_stats) -> c_int;
+    pub fn pcv_searcher_density_clusters(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, min_items: c_int, capacity: i64, out_ids: *mut i64, out_label: *mut i32, out_kind: *mut int8_t, out_degree: *mut i32, out_rows: *mut i64, out_clusters: *mut i32) -> c_int;
+    pub fn pcv_searcher_last_density_stats(s: *mut pcv_searcher, out: *mut pcv_density_stats) -> c_int;
     pub fn pcv_searcher_seeds(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, method: c_int, seed: u64, first_id: *const i64, out_ids: *mut i64, out_positions: *mut i64, out_totals: *mut i64, out_cover: *mut f32, out_count: *mut i32) -> c_int;
     pub fn pcv_searcher_last_seed_stats(s: *mut pcv_searcher, out: *mut pcv_seed_stats) -> c_int;
     pub fn pcv_seed_draw(seed: u64, step: c_int, total: u64, out_t: *mut u64) -> c_int;

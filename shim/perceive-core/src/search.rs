@@ -606,6 +606,59 @@ impl Searcher {
         (0..n as usize).map(|i| (ids[i], (0..counts[i] as usize).map(|j| (nbr[i * k + j], scores[i * k + j])).collect())).collect()
     }
 
+    /// Density clusters (`pcv_searcher_density_clusters`): DBSCAN under the cosine over the items of `sources`, by global
+    /// position.  Two items are near iff their cosine is at least `threshold`; an item with `min_items - 1` near items or more is a
+    /// core item; clusters are the connected components of the core items, numbered by their first core item.
+    /// Returns ((item id, cluster or -1, kind: ffi::PCV_DENSITY_CORE / _BORDER / _NOISE / _NONE, near items) per item, clusters).
+    pub fn density_clusters(&self, sources: &[i64], threshold: f32, min_items: usize) -> (Vec<(i64, i32, i8, i32)>, usize) {
+        if self.handle.is_null() || sources.is_empty() {
+            return (Vec::new(), 0);
+        }
+        let min_items = min_items.clamp(1, i32::MAX as usize) as i32;
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_density_clusters(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                threshold,
+                min_items,
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                &mut n,
+                std::ptr::null_mut(),
+            )
+        })
+        .expect("density_clusters failed");
+        let room = n.max(1) as usize;
+        let mut ids = vec![-1i64; room];
+        let mut labels = vec![-1i32; room];
+        let mut kinds = vec![ffi::PCV_DENSITY_NONE as i8; room];
+        let mut degrees = vec![0i32; room];
+        let mut clusters: i32 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_density_clusters(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                threshold,
+                min_items,
+                room as i64,
+                ids.as_mut_ptr(),
+                labels.as_mut_ptr(),
+                kinds.as_mut_ptr(),
+                degrees.as_mut_ptr(),
+                &mut n,
+                &mut clusters,
+            )
+        })
+        .expect("density_clusters failed");
+        ((0..n as usize).map(|i| (ids[i], labels[i], kinds[i], degrees[i])).collect(), clusters as usize)
+    }
+
     /// Seed items (`pcv_searcher_seeds`): up to `k` items (clamped to PCV_MAX_SEEDS) that cover `sources`, in the order they were
     /// picked — `kmeanspp`: the k-means++ draw of `seed`, else farthest first; `first_id`: the item step 0 picks instead.
     /// Returns (item id, global position, potential before the pick in units of 2^-32, largest cosine with the seeds before it:

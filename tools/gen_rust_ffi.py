@@ -20,6 +20,8 @@ SCALARS = {
     "pcv_encode_stats": "pcv_encode_stats", "pcv_duplicate_stats": "pcv_duplicate_stats",
     "pcv_assign_stats": "pcv_assign_stats", "pcv_neighbor_stats": "pcv_neighbor_stats", "pcv_group_stats": "pcv_group_stats",
     "pcv_seed_stats": "pcv_seed_stats", "pcv_moment_stats": "pcv_moment_stats", "pcv_project_stats": "pcv_project_stats",
+    "pcv_density_stats": "pcv_density_stats",
+    "int8_t": "int8_t",  # (an alias of i8 declared in the file: tests/test_rust_shim.py compares this one type by its C name)
 }
 
 
@@ -113,6 +115,7 @@ def main():
         "//! counts, integer widths, struct fields).",
         "#![allow(non_camel_case_types, dead_code)]",
         "use std::os::raw::{c_char, c_int, c_void};",
+        "pub type int8_t = i8;",
         "",
     ]
     for h in ("pcv_ctx", "pcv_searcher", "pcv_model", "pcv_tokenizer", "pcv_comm"):
