@@ -91,6 +91,13 @@ def test_repacked_copies_are_the_built_ones(ctx, oracle, D, metric, screen, mid,
             np.testing.assert_array_equal(ids_b, ids_a)
             np.testing.assert_array_equal(sc_b.view(np.uint32), sc_a.view(np.uint32))
             np.testing.assert_array_equal(cnt_b, cnt_a)
+    # A's hits are the oracle's (which gives the all-zero row under cosine and the non-finite row no score, as the searcher does)
+    ids_a, sc_a, cnt_a = a.search_vectors(None, 10, queries)
+    opos, osc, ocnt = oracle.topk(queries, final, 10, metric=1 if metric == "dot" else 0)
+    assert (ocnt == 10).all() and not np.isin(opos, [INF_ROW] + ([ZERO_ROW] if metric == "cosine" else [])).any()
+    np.testing.assert_array_equal(ids_a, ids[opos])
+    np.testing.assert_allclose(sc_a, reported(osc, metric, D), rtol=0, atol=1e-7)
+    np.testing.assert_array_equal(cnt_a, ocnt)
     got_a = a.search_range(None, bounds, queries, 256)
     st_a = a.last_stats()
     got_b = b.search_range(None, bounds, queries, 256)
