@@ -16,7 +16,7 @@
 //   sums     label_sums_kernel: S[label][d] += rint(x[r][d] * rinv_r * 2^32) in int64 — associative, so any order gives the same bits.
 #include "device_access.h"
 #include "launch_rows.h"
-#include "scan.h"
+#include "row_jobs.h"
 
 namespace pcv {
 namespace {

@@ -21,7 +21,7 @@
 //                                        labels, kinds, degrees, ids and the counters.
 #include "device_access.h"
 #include "launch_rows.h"
-#include "scan.h"
+#include "row_jobs.h"
 
 namespace pcv {
 namespace {

@@ -1,9 +1,9 @@
 // launch_rows.h — what the kernels that walk a launch's rows by number share (selfjoin_kernels.hip, assign_kernels.hip): finding the
-// segment of a launch row (scan.h, "launch row") and the wave-uniform cursor of a stream of row blocks.  Everything here is inlined:
+// segment of a launch row (row_jobs.h, "launch row") and the wave-uniform cursor of a stream of row blocks.  Everything here is inlined:
 // the file defines no symbol.
 #pragma once
 #include "device_access.h"
-#include "scan.h"
+#include "row_jobs.h"
 
 namespace pcv {
 namespace {
@@ -36,7 +36,7 @@ __device__ __forceinline__ int find_seg(const ScanParams& p, uint32_t gb, int fr
     return lo;
 }
 
-// Launch row `lr` (scan.h): its segment, its row there and where its first piece is.
+// Launch row `lr` (row_jobs.h): its segment, its row there and where its first piece is.
 struct RowRef {
     const SegDesc* sg;
     uint32_t row;

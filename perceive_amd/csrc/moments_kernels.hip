@@ -13,7 +13,7 @@
 //                            wave-uniform pointers, then (float)(a * rinv - offset), the two steps rounded separately.
 #include "device_access.h"
 #include "launch_rows.h"
-#include "scan.h"
+#include "row_jobs.h"
 
 namespace pcv {
 namespace {

@@ -20,7 +20,7 @@
 //                                           landed in cannot show.  It writes ids, neighbour ids, (float)c and counts.
 #include "device_access.h"
 #include "launch_rows.h"
-#include "scan.h"
+#include "row_jobs.h"
 
 namespace pcv {
 namespace {

@@ -1,0 +1,1298 @@
+// row_jobs.cpp — host side of the calls that run kernels over the stored rows themselves (row_jobs.h): duplicate pairs, item labels,
+// neighbours, density clusters, seeds, moments and projection, with their entry points of the C ABI.  They are one kind of call:
+// select segments, open a RowsJob over them, run the call's kernels over its launch rows, bring the result down.  Everything is
+// allocated for the call and given back when it ends; nothing of the searcher's pass state is touched.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <numeric>
+#include <vector>
+
+#include "common.h"
+#include "row_jobs.h"
+#include "searcher_internal.h"
+
+using namespace pcv;
+
+namespace {
+
+// The segment table of a launch over `segs` as the row-against-row kernels read it (selfjoin_kernels.hip, assign_kernels.hip: blk,
+// scale, ids, positions and the launch's block numbering; no screening copy).  out0 receives the output index of each segment's
+// row 0.  -> the blocks of the launch; `rows` receives the rows of the segments.
+uint32_t fill_row_table(const std::vector<SelSeg>& segs, SegDesc* tab, int64_t* out0, int64_t& rows, const char* what) {
+    uint64_t blk0 = 0;
+    rows = 0;
+    for (size_t i = 0; i < segs.size(); ++i) {
+        const Segment& g = *segs[i].g;
+        tab[i] = SegDesc{};
+        tab[i].blk = g.blk;
+        tab[i].scale = g.scale;
+        tab[i].ids = g.ids;
+        tab[i].id0 = g.id0;
+        tab[i].pos0 = g.pos0;
+        tab[i].nrows = g.nrows;
+        tab[i].nblocks = g.nblocks();
+        tab[i].blk0 = (uint32_t)blk0;
+        out0[i] = rows;
+        blk0 += g.nblocks();
+        rows += g.nrows;
+        if (blk0 * kBlockRows > 0xffffffffull) PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: more than 2^32 rows in one call", what);
+    }
+    return (uint32_t)blk0;
+}
+
+// What every call of this file opens over the segments it selected: the parameter block of the launch (ScanParams | SegDesc[nseg] |
+// seg_out0[nseg], built in pinned memory with its device mirror), the rows' rinv / norm as selfjoin_prep_kernel leaves them, and
+// the events the call times its steps with.  Only the f32 rows are read.  A call declares its own buffers BEFORE its job: the job
+// then goes first, and it waits for the stream before an event is destroyed or a buffer that a queued kernel may still read is freed.
+struct RowsJob {
+    hipStream_t st;
+    PinBuf<uint8_t> pin_p;
+    DevBuf<uint8_t> d_p;
+    size_t bytes = 0;
+    ScanParams* p = nullptr;  // (pinned)
+    const ScanParams* dp = nullptr;
+    const int64_t* seg_out0 = nullptr;  // [nseg] output index of each segment's row 0 (device)
+    int64_t rows = 0;
+    size_t nr = 0, n_rinv = 0;  // launch rows; entries of rinv
+    DevBuf<float> d_rinv;
+    DevBuf<double> d_norm;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // (the longest call brackets five steps)
+
+    // pad_blocks: the blocks of rinv behind total_blocks that must be there and zero (a tile kernel's tile_blocks; 0: none)
+    RowsJob(pcv_searcher* s, const std::vector<SelSeg>& segs, const char* what, int metric, uint32_t pad_blocks) : st(s->ctx->stream) {
+        PCV_HIP(hipSetDevice(s->ctx->device));
+        const size_t off_seg = align_up(sizeof(ScanParams)), off_out0 = align_up(off_seg + segs.size() * sizeof(SegDesc));
+        bytes = off_out0 + segs.size() * sizeof(int64_t);
+        pin_p.ensure(bytes);
+        d_p.ensure(bytes);
+        p = new (pin_p.p) ScanParams{};
+        p->total_blocks = fill_row_table(segs, reinterpret_cast<SegDesc*>(pin_p.p + off_seg), reinterpret_cast<int64_t*>(pin_p.p + off_out0), rows, what);
+        p->seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
+        p->nseg = (int)segs.size();
+        p->D = s->D;
+        p->D4 = s->D4;
+        p->metric = metric;
+        dp = reinterpret_cast<const ScanParams*>(d_p.p);
+        seg_out0 = reinterpret_cast<const int64_t*>(d_p.p + off_out0);
+        nr = (size_t)p->total_blocks * kBlockRows;
+        n_rinv = nr + (size_t)pad_blocks * kBlockRows;
+        d_rinv.ensure(n_rinv);
+        d_norm.ensure(nr);
+    }
+    ~RowsJob() {
+        (void)hipStreamSynchronize(st);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    RowsJob(const RowsJob&) = delete;
+    RowsJob& operator=(const RowsJob&) = delete;
+
+    // queues the upload of the block and, between ev[0] and ev[1], the prep step; once per job, behind the memsets of the call
+    void prep() {
+        SelfJoinArgs a{};
+        a.rinv = d_rinv.p;
+        a.norm = d_norm.p;
+        PCV_HIP(hipMemcpyAsync(d_p.p, pin_p.p, bytes, hipMemcpyHostToDevice, st));
+        if (n_rinv > nr) PCV_HIP(hipMemsetAsync(d_rinv.p, 0, n_rinv * sizeof(float), st));
+        record(0);
+        launch_selfjoin_prep(st, *p, dp, a);
+        record(1);
+    }
+    void record(int i) {  // (an event is made when the call first records it: a short call pays for no more than it uses)
+        if (!ev[i]) PCV_HIP(hipEventCreate(&ev[i]));
+        PCV_HIP(hipEventRecord(ev[i], st));
+    }
+    void wait() {
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+    }
+    float elapsed(int from) {
+        float ms = 0.0f;
+        PCV_HIP(hipEventElapsedTime(&ms, ev[from], ev[from + 1]));
+        return ms;
+    }
+};
+
+// The rule of the four screens for a candidate list that was too short.  `queue` queues the launches that list into room for
+// `cap` entries and count everything they find, listed or not, in d_count[0]; the N counters at d_count come down into `first`.
+// If the count is above `cap` — and not above `limit`, where the caller gives up with a message of its own — the list was too short:
+// once more, with the room the count asks for.  The buffers `cand` grow to it (`queue` takes their addresses when it runs), `reset`
+// queues what puts the counters, and whatever else the listing adds to, back where the first run found them, and the counters of the
+// repeat come down into `again`.  Whether the two runs agree is the caller's to check.  The first run is timed from ev[from], which
+// the caller has recorded behind the step before, to ev[from + 1]; the repeat between the two events behind ev[from], so that every
+// event up to ev[from] keeps what the call recorded.
+struct Listing {
+    bool repeated = false;
+    float ms = 0.0f, again_ms = 0.0f;
+};
+template <size_t N, class Queue, class Reset, class... T>
+Listing list_candidates(RowsJob& job, int from, const unsigned long long* d_count, unsigned long long (&first)[N], unsigned long long (&again)[N],
+                        unsigned long long& cap, uint64_t limit, Queue queue, Reset reset, DevBuf<T>&... cand) {
+    auto run = [&](int e, unsigned long long* counts) {
+        queue();
+        job.record(e + 1);
+        PCV_HIP(hipMemcpyAsync(counts, d_count, N * sizeof(unsigned long long), hipMemcpyDeviceToHost, job.st));
+        job.wait();
+        return job.elapsed(e);
+    };
+    Listing l;
+    l.ms = run(from, first);
+    if (first[0] <= cap || first[0] > limit) return l;
+    cap = first[0];
+    (cand.ensure((size_t)cap), ...);
+    reset();
+    job.record(from + 1);
+    l.again_ms = run(from + 1, again);
+    l.repeated = true;
+    return l;
+}
+
+// What an entry point does once its arguments are checked: it takes the searcher's lock, refuses a call between search_device_begin
+// and search_device_end, and brings a view up to date.
+std::unique_lock<std::mutex> enter(pcv_searcher* s, const char* call) {
+    std::unique_lock<std::mutex> lk(s->mu);
+    PCV_REQUIRE(!s->pending.active, "%s: a pass queued by search_device_begin has not been collected", call);
+    sync_view(s);
+    return lk;
+}
+
+// ---- duplicate pairs (pcv_searcher_find_duplicates; DESIGN.md §4 "Duplicate pairs") ----
+// The screen may list four times the pairs a call may return before the call gives up: 2^26 entries of 8 bytes.
+constexpr uint64_t kMaxJoinCandidates = (uint64_t)4 * PCV_MAX_DUPLICATE_PAIRS;
+constexpr uint32_t kJoinSpanBlocks = 256;  // blocks a work item streams against its tile (12 MB at 384-d for 196 KB of tile staging)
+
+// Three steps on the device (selfjoin_kernels.hip): norms, the bf16 screen of every tile of rows against the rows behind it, the
+// canonical f64 cosine of what the screen listed.  The pairs come down once and are ordered here.  Everything the call allocates
+// is its own and is given back when it ends: nothing of the searcher's pass state is touched.
+void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs, int64_t* out_id_a,
+                     int64_t* out_id_b, float* out_scores, int64_t* out_count, int64_t* out_total) {
+    PCV_REQUIRE(!s->dirty, "find_duplicates: rows were added or cleared without pcv_searcher_finalize");
+    s->dup_stats = pcv_duplicate_stats{};
+    *out_count = 0;
+    if (out_total) *out_total = 0;
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "find_duplicates: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    if (segs.empty()) return;
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<uint64_t> d_cand;
+    DevBuf<DupPair> d_pairs;
+    SelfJoinArgs a{};
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    RowsJob job(s, segs, "find_duplicates", s->metric, a.tile_blocks);
+    hipStream_t st = job.st;
+    const ScanParams& p = *job.p;
+    const ScanParams* dp = job.dp;
+    const int64_t rows = job.rows;
+
+    a.span_blocks = kJoinSpanBlocks;
+    while ((p.total_blocks + a.span_blocks - 1) / a.span_blocks > 65535u) a.span_blocks *= 2;  // (the grid's second dimension)
+    // thr - margin in f64, rounded down: no pair with s below it has c >= thr
+    a.threshold = (double)threshold;
+    a.screen_threshold = std::nextafterf((float)((double)threshold - (double)selfjoin_margin(s->Dp)), -INFINITY);
+    d_cnt.ensure(2);
+    a.cand_cap = std::min<uint64_t>(kMaxJoinCandidates, std::max<uint64_t>(65536, 2 * (uint64_t)rows));
+    d_cand.ensure(a.cand_cap);
+    a.rinv = job.d_rinv.p;
+    a.norm = job.d_norm.p;
+    a.counters = d_cnt.p;
+
+    unsigned long long counts[2] = {0, 0}, again[2] = {0, 0};
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+    job.prep();
+    const Listing screen = list_candidates(
+        job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxJoinCandidates,
+        [&] {
+            a.cand = d_cand.p;
+            launch_selfjoin_screen(st, p, dp, a);
+        },
+        [&] { PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st)); }, d_cand);
+    s->dup_stats.rows = rows;
+    s->dup_stats.tile_rows = tile;
+    s->dup_stats.prep_ms = job.elapsed(0);
+    s->dup_stats.screen_ms = screen.ms;
+    const uint64_t n_cand = counts[0];
+    s->dup_stats.candidates = (int64_t)n_cand;
+    if (n_cand > kMaxJoinCandidates)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                 "find_duplicates: the screen lists %llu candidate pairs at threshold %g, more than %llu (4 x PCV_MAX_DUPLICATE_PAIRS): raise the "
+                 "threshold or join fewer rows",
+                 (unsigned long long)n_cand, (double)threshold, (unsigned long long)kMaxJoinCandidates);
+    if (screen.repeated) {  // (the screen lists the same pairs again)
+        PCV_REQUIRE(again[0] == n_cand, "find_duplicates: the repeated screen listed %llu pairs, the first %llu", again[0], (unsigned long long)n_cand);
+        s->dup_stats.reruns = 1;
+        s->dup_stats.screen_ms += screen.again_ms;
+    }
+    if (n_cand == 0) return;
+    a.n_cand = n_cand;
+    a.pair_cap = std::min<uint64_t>(n_cand, (uint64_t)PCV_MAX_DUPLICATE_PAIRS);
+    d_pairs.ensure(a.pair_cap);
+    a.pairs = d_pairs.p;
+    job.record(2);
+    launch_selfjoin_rescore(st, p, dp, a);
+    job.record(3);
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    job.wait();
+    s->dup_stats.rescore_ms = job.elapsed(2);
+    const uint64_t total = counts[1];
+    s->dup_stats.pairs = (int64_t)total;
+    if (total > (uint64_t)PCV_MAX_DUPLICATE_PAIRS)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                 "find_duplicates: %llu duplicate pairs at threshold %g, more than PCV_MAX_DUPLICATE_PAIRS (%d): raise the threshold or join "
+                 "fewer rows",
+                 (unsigned long long)total, (double)threshold, (int)PCV_MAX_DUPLICATE_PAIRS);
+    std::vector<DupPair> pairs((size_t)total);
+    if (total > 0) PCV_HIP(hipMemcpy(pairs.data(), d_pairs.p, (size_t)total * sizeof(DupPair), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)std::min<uint64_t>(total, (uint64_t)max_pairs);
+    auto before = [](const DupPair& x, const DupPair& y) {
+        if (x.c != y.c) return x.c > y.c;
+        if (x.pos_a != y.pos_a) return x.pos_a < y.pos_a;
+        return x.pos_b < y.pos_b;
+    };
+    if (n < pairs.size())
+        std::partial_sort(pairs.begin(), pairs.begin() + (std::ptrdiff_t)n, pairs.end(), before);
+    else
+        std::sort(pairs.begin(), pairs.end(), before);
+    for (size_t i = 0; i < n; ++i) {
+        out_id_a[i] = pairs[i].id_a;
+        out_id_b[i] = pairs[i].id_b;
+        if (out_scores) out_scores[i] = (float)pairs[i].c;
+    }
+    *out_count = (int64_t)n;
+    if (out_total) *out_total = (int64_t)total;
+}
+
+// ---- item labels (pcv_searcher_assign, _label_sums, _kmeans; DESIGN.md §4 "Item labels") ----
+constexpr uint64_t kMaxAssignCandidates = (uint64_t)1 << 28;  // (row, label) pairs the screen may list: 20 bytes each
+constexpr int64_t kMaxLabelMembers = (int64_t)1 << 30;        // |t| <= 2^32 (1 + 2^-23): the int64 sums hold 2^30 of them
+
+// Everything one call allocates, its own and given back when it ends: nothing of the searcher's pass state is touched.  The steps
+// on the device are those of assign_kernels.hip; the rows' norms are selfjoin_prep_kernel's, and so are the labels' — they are
+// uploaded as one small segment in the blocked layout.
+struct AssignJob {
+    pcv_searcher* s;
+    hipStream_t st;
+    int K, tile;
+    PinBuf<uint8_t> pin_l;
+    DevBuf<uint8_t> d_l;
+    ScanParams* pl = nullptr;  // the labels
+    const ScanParams* dpl = nullptr;
+    float4* lab_blk = nullptr;  // pinned, blocked
+    size_t bytes_l = 0;
+    DevBuf<float> d_lab_rinv, d_w, d_mg, d_lb, d_cand_s, d_out_score;
+    DevBuf<double> d_lab_norm;
+    DevBuf<uint4> d_lab_tile;
+    DevBuf<uint64_t> d_cand;
+    DevBuf<unsigned long long> d_cnt, d_best_key, d_cand_key;
+    DevBuf<uint32_t> d_best_lab;
+    DevBuf<int32_t> d_row_label, d_out_label;
+    DevBuf<int64_t> d_out_ids;
+    DevBuf<long long> d_counts, d_sums;
+    AssignArgs a{};
+    pcv_assign_stats stats{};
+    RowsJob rj;  // the rows.  The last member: it goes first, and waits for the stream before the buffers above are freed
+
+    // the table of the rows and their norms: all that the sums need
+    AssignJob(pcv_searcher* s_, const std::vector<SelSeg>& segs, int K_, int metric)
+        : s(s_), st(s_->ctx->stream), K(K_), tile(mfma_pass_queries(s_->Dp)), rj(s_, segs, "assign", metric, 0) {
+        a.metric = metric;
+        a.seg_out0 = rj.seg_out0;
+        a.K = K;
+        d_row_label.ensure(rj.nr);
+        a.rinv = rj.d_rinv.p;
+        a.norm = rj.d_norm.p;
+        a.row_label = d_row_label.p;
+        PCV_HIP(hipMemsetAsync(d_row_label.p, 0xff, rj.nr * sizeof(int32_t), st));  // (-1: no label yet)
+        rj.prep();
+        rj.wait();
+        stats.rows = rj.rows;
+        stats.prep_ms = rj.elapsed(0);
+    }
+
+    // ... and what an assignment needs on top: the labels' table (a whole number of tiles), the per-row state, the candidate list
+    // and the outputs
+    void open_labels() {
+        a.tile_blocks = (uint32_t)tile / kBlockRows;
+        const uint32_t tiles = ((uint32_t)K + (uint32_t)tile - 1) / (uint32_t)tile;
+        a.label_blocks = tiles * a.tile_blocks;
+        const size_t slots = (size_t)a.label_blocks * kBlockRows;
+        // [ScanParams][SegDesc][scale][blocked rows]
+        const size_t off_lseg = align_up(sizeof(ScanParams)), off_scale = align_up(off_lseg + sizeof(SegDesc));
+        const size_t off_blk = align_up(off_scale + slots * sizeof(float));
+        bytes_l = off_blk + slots * s->Dp * sizeof(float);
+        pin_l.ensure(bytes_l);
+        d_l.ensure(bytes_l);
+        std::memset(pin_l.p, 0, bytes_l);
+        pl = new (pin_l.p) ScanParams{};
+        SegDesc* lt = new (pin_l.p + off_lseg) SegDesc{};
+        float* lscale = reinterpret_cast<float*>(pin_l.p + off_scale);
+        for (int j = 0; j < K; ++j) lscale[j] = 1.0f;
+        lab_blk = reinterpret_cast<float4*>(pin_l.p + off_blk);
+        lt->blk = reinterpret_cast<const float4*>(d_l.p + off_blk);
+        lt->scale = reinterpret_cast<const float*>(d_l.p + off_scale);
+        lt->nrows = (uint32_t)K;
+        lt->nblocks = a.label_blocks;
+        pl->seg = reinterpret_cast<const SegDesc*>(d_l.p + off_lseg);
+        pl->nseg = 1;
+        pl->total_blocks = a.label_blocks;
+        pl->D = s->D;
+        pl->D4 = s->D4;
+        dpl = reinterpret_cast<const ScanParams*>(d_l.p);
+        a.lab_blk = lt->blk;
+
+        const size_t nr = rj.nr;
+        d_lb.ensure(nr);
+        d_best_key.ensure(nr);
+        d_best_lab.ensure(nr);
+        d_lab_rinv.ensure(slots);
+        d_lab_norm.ensure(slots);
+        d_w.ensure(slots);
+        d_mg.ensure(slots);
+        d_lab_tile.ensure(slots * (size_t)(s->Dp / 8));
+        d_cnt.ensure(2);
+        d_out_label.ensure((size_t)rj.rows);
+        d_out_score.ensure((size_t)rj.rows);
+        d_out_ids.ensure((size_t)rj.rows);
+        d_counts.ensure((size_t)K);
+        a.cand_cap = std::min<uint64_t>(kMaxAssignCandidates, std::max<uint64_t>(65536, 4 * (uint64_t)rj.rows));
+        d_cand.ensure(a.cand_cap);
+        d_cand_s.ensure(a.cand_cap);
+        a.lab_rinv = d_lab_rinv.p;
+        a.lab_norm = d_lab_norm.p;
+        a.lab_tile = d_lab_tile.p;
+        a.w = d_w.p;
+        a.mg = d_mg.p;
+        a.lb = d_lb.p;
+        a.cand = d_cand.p;
+        a.cand_s = d_cand_s.p;
+        a.counters = d_cnt.p;
+        a.best_key = d_best_key.p;
+        a.best_lab = d_best_lab.p;
+        a.out_label = d_out_label.p;
+        a.out_score = d_out_score.p;
+        a.out_ids = d_out_ids.p;
+        a.out_counts = d_counts.p;
+        a.margin = selfjoin_margin(s->Dp);
+        // a workgroup stages a whole tile for its span: spans of two per CU, and not so short that the staging shows
+        const uint32_t per = (rj.p->total_blocks + 2 * (uint32_t)s->ctx->num_cus - 1) / (2 * (uint32_t)std::max(1, s->ctx->num_cus));
+        a.span_blocks = std::max<uint32_t>(32, (per + 7) / 8 * 8);
+        stats.tile_labels = tile;
+        stats.label_tiles = (int32_t)tiles;
+    }
+
+    // one assignment with labels[K][D] (host): row_label, the outputs on the device, counters[1] = rows whose label changed
+    uint64_t assign(const float* labels) {
+        const int D = s->D, D4 = s->D4;
+        for (int j = 0; j < K; ++j) {
+            float* dst = reinterpret_cast<float*>(lab_blk + (size_t)(j >> 5) * D4 * 32 + (j & 31));  // piece f of label j: dst + f * 128 floats
+            for (int d = 0; d < D; ++d) dst[(size_t)(d >> 2) * 128 + (d & 3)] = labels[(size_t)j * D + d];
+        }
+        unsigned long long counts[2] = {0, 0}, again[2] = {0, 0};
+        SelfJoinArgs prep{};
+        prep.rinv = d_lab_rinv.p;
+        prep.norm = d_lab_norm.p;
+        PCV_HIP(hipMemcpyAsync(d_l.p, pin_l.p, bytes_l, hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_counts.p, 0, (size_t)K * sizeof(long long), st));
+        rj.record(0);
+        launch_selfjoin_prep(st, *pl, dpl, prep);
+        launch_assign_labels(st, *rj.p, a);
+        launch_assign_begin(st, *rj.p, rj.dp, a);
+        rj.record(1);
+        const Listing screen = list_candidates(
+            rj, 1, d_cnt.p, counts, again, a.cand_cap, kMaxAssignCandidates,
+            [&] {
+                a.cand = d_cand.p;
+                a.cand_s = d_cand_s.p;
+                for (uint32_t t = 0; t < (uint32_t)stats.label_tiles; ++t) {
+                    a.tile = t;
+                    launch_assign_screen(st, *rj.p, rj.dp, a);
+                }
+            },
+            [&] { PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st)); }, d_cand, d_cand_s);
+        stats.prep_ms += rj.elapsed(0);
+        stats.screen_ms += screen.ms;
+        uint64_t n_cand = counts[0];
+        stats.candidates = (int64_t)n_cand;
+        if (n_cand > kMaxAssignCandidates)
+            PCV_FAIL(PCV_ERR_UNSUPPORTED, "assign: the screen lists %llu (row, label) candidates, more than %llu: fewer or less alike labels, or fewer rows",
+                     (unsigned long long)n_cand, (unsigned long long)kMaxAssignCandidates);
+        if (screen.repeated) {  // (the bounds the first run left only shorten the list)
+            PCV_REQUIRE(again[0] <= n_cand, "assign: the repeated screen listed %llu candidates, the first %llu", again[0], (unsigned long long)n_cand);
+            n_cand = again[0];
+            stats.reruns += 1;
+            stats.screen_ms += screen.again_ms;
+        }
+        a.n_cand = n_cand;
+        d_cand_key.ensure((size_t)std::max<uint64_t>(1, n_cand));
+        a.cand_key = d_cand_key.p;
+        rj.record(2);
+        launch_assign_rescore(st, *rj.p, rj.dp, a);
+        launch_assign_finish(st, *rj.p, rj.dp, a);
+        rj.record(3);
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        rj.wait();
+        stats.rescore_ms += rj.elapsed(2);
+        return counts[1];
+    }
+
+    // the integer sums of the labels in row_label -> host [K][Dp] and the members per label
+    void sums(std::vector<long long>& S, std::vector<long long>& members) {
+        const size_t n = (size_t)K * s->Dp;
+        d_sums.ensure(n + (size_t)K);
+        a.sums = d_sums.p;
+        a.sum_counts = d_sums.p + n;
+        S.resize(n);
+        members.resize((size_t)K);
+        PCV_HIP(hipMemsetAsync(d_sums.p, 0, (n + (size_t)K) * sizeof(long long), st));
+        launch_label_sums(st, *rj.p, rj.dp, a);
+        PCV_HIP(hipMemcpyAsync(S.data(), d_sums.p, n * sizeof(long long), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipMemcpyAsync(members.data(), d_sums.p + n, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, st));
+        rj.wait();
+    }
+
+    void download(int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts) {
+        const size_t n = (size_t)rj.rows;
+        PCV_HIP(hipMemcpy(out_label, d_out_label.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (out_score) PCV_HIP(hipMemcpy(out_score, d_out_score.p, n * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (out_counts) PCV_HIP(hipMemcpy(out_counts, d_counts.p, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost));
+    }
+};
+
+void check_labels(pcv_searcher* s, const float* labels, int K, const char* what) {
+    for (size_t i = 0, e = (size_t)K * s->D; i < e; ++i)
+        PCV_REQUIRE(std::isfinite(labels[i]), "%s: label %d has a NaN or Inf at feature %d", what, (int)(i / s->D), (int)(i % s->D));
+}
+
+// assign (max_iters = 0, the searcher's metric, no centroids) and k-means (cosine); the caller has checked the arguments
+void assign_or_kmeans(pcv_searcher* s, const char* what, const float* init, int K, int max_iters, int metric, const int64_t* source_ids, int n_sources,
+                      int64_t capacity, float* out_centroids, int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts,
+                      int32_t* out_iters, int64_t* out_moved, int64_t* out_n) {
+    PCV_REQUIRE(!s->dirty, "%s: rows were added or cleared without pcv_searcher_finalize", what);
+    check_labels(s, init, K, what);
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_n = n;
+    if (out_iters) *out_iters = 0;
+    if (out_label == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "%s: the outputs have room for %lld rows, the selected sources have %lld", what, (long long)capacity, (long long)n);
+    s->assign_stats = pcv_assign_stats{};
+    if (mfma_pass_queries(s->Dp) == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: a bf16 tile of %d-d labels does not fit the LDS", what, s->D);
+    const size_t KD = (size_t)K * s->D;
+    if (out_centroids) std::memcpy(out_centroids, init, KD * sizeof(float));
+    if (out_counts) std::fill(out_counts, out_counts + K, (int64_t)0);
+    if (out_moved) out_moved[0] = 0;
+    if (n == 0) return;
+    AssignJob job(s, segs, K, metric);
+    job.open_labels();
+    const auto keep_stats = at_exit([&] { s->assign_stats = job.stats; });
+    std::vector<float> cent(init, init + KD);
+    std::vector<long long> S, members;
+    int updates = 0;
+    while (true) {
+        const uint64_t moved = job.assign(cent.data());
+        if (out_moved) out_moved[updates] = (int64_t)moved;
+        if (moved == 0 || updates == max_iters) break;
+        job.sums(S, members);
+        for (int j = 0; j < K; ++j) {
+            if (members[(size_t)j] > kMaxLabelMembers)
+                PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: label %d has %lld members, more than 2^30", what, j, members[(size_t)j]);
+            if (members[(size_t)j] == 0) continue;  // (keeps its vector)
+            for (int d = 0; d < s->D; ++d) cent[(size_t)j * s->D + d] = (float)((double)S[(size_t)j * s->Dp + d] * 0x1p-32);
+        }
+        ++updates;
+    }
+    if (out_iters) *out_iters = updates;
+    if (out_centroids) std::memcpy(out_centroids, cent.data(), KD * sizeof(float));
+    job.download(out_label, out_score, out_ids, out_counts);
+}
+
+void label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const int32_t* labels, int64_t n, int K, int64_t* out_sums,
+                int64_t* out_counts) {
+    PCV_REQUIRE(!s->dirty, "label_sums: rows were added or cleared without pcv_searcher_finalize");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    PCV_REQUIRE(n == selected_rows(segs), "label_sums: %lld labels for %lld rows of the selected sources", (long long)n, (long long)selected_rows(segs));
+    for (int64_t i = 0; i < n; ++i) PCV_REQUIRE(labels[i] < K, "label_sums: row %lld has label %d of %d", (long long)i, labels[i], K);
+    std::fill(out_sums, out_sums + (size_t)K * s->D, (int64_t)0);
+    if (out_counts) std::fill(out_counts, out_counts + K, (int64_t)0);
+    if (n == 0) return;
+    AssignJob job(s, segs, K, PCV_METRIC_COSINE);  // (the sums need no label tile: any dimension)
+    std::vector<int32_t> by_row(job.rj.nr, -1);
+    size_t lr = 0;
+    int64_t at = 0;
+    for (const SelSeg& g : segs) {
+        for (uint32_t r = 0; r < g.g->nrows; ++r) by_row[lr + r] = labels[at + r] < 0 ? -1 : labels[at + r];
+        lr += (size_t)g.g->nblocks() * kBlockRows;
+        at += g.g->nrows;
+    }
+    PCV_HIP(hipMemcpy(job.d_row_label.p, by_row.data(), by_row.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    std::vector<long long> S, members;
+    job.sums(S, members);
+    for (int j = 0; j < K; ++j) {
+        if (members[(size_t)j] > kMaxLabelMembers) PCV_FAIL(PCV_ERR_UNSUPPORTED, "label_sums: label %d has %lld members, more than 2^30", j, members[(size_t)j]);
+        for (int d = 0; d < s->D; ++d) out_sums[(size_t)j * s->D + d] = (int64_t)S[(size_t)j * s->Dp + d];
+        if (out_counts) out_counts[j] = (int64_t)members[(size_t)j];
+    }
+}
+
+// ---- item neighbours (pcv_searcher_neighbors; DESIGN.md §4 "Item neighbours") ----
+constexpr uint64_t kMaxNeighborCandidates = (uint64_t)1 << 30;  // directed (owner, partner) pairs the list pass may leave: 20 bytes each
+constexpr uint32_t kNeighborWalkBlocks = 256;  // sampled blocks a workgroup streams against its tile (kJoinSpanBlocks)
+
+// Prep, bound pass, thresholds, list pass, rescore, select (neighbors_kernels.hip).  Everything the call allocates is its own and
+// is given back when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
+void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int64_t capacity, int64_t* out_ids, int64_t* out_neighbor_ids,
+               float* out_scores, int32_t* out_counts, int64_t* out_rows) {
+    PCV_REQUIRE(!s->dirty, "neighbors: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "neighbors: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_rows = n;
+    if (out_ids == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "neighbors: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    s->nbr_stats = pcv_neighbor_stats{};
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "neighbors: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (n == 0) return;
+    DevBuf<float> d_thr, d_out_score;
+    DevBuf<uint32_t> d_span_max, d_cnt_off, d_sorted_row;
+    DevBuf<unsigned long long> d_cnt, d_sorted_key;
+    DevBuf<uint64_t> d_cand;
+    DevBuf<int64_t> d_out_ids, d_out_nbr;
+    DevBuf<int32_t> d_out_count;
+    NeighborArgs a{};
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    RowsJob job(s, segs, "neighbors", PCV_METRIC_COSINE, a.tile_blocks);
+    hipStream_t st = job.st;
+    const ScanParams& p = *job.p;
+    const ScanParams* dp = job.dp;
+    const int64_t rows = job.rows;
+
+    // The sample and its spans (DESIGN.md §4 "Item neighbours", measurement): no result depends on them, only the list's length.
+    a.k = k;
+    a.margin = selfjoin_margin(s->Dp);
+    const uint32_t TB = p.total_blocks;
+    a.stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / (uint32_t)std::max(64, 4 * k)));
+    const uint32_t sampled = (TB + a.stride - 1) / a.stride;
+    const uint32_t want_spans = std::min<uint32_t>(sampled, std::min<uint32_t>(kMaxNeighborSpans, (uint32_t)std::max(64, 8 * k)));
+    a.span_len = (sampled + want_spans - 1) / want_spans;
+    a.spans = (sampled + a.span_len - 1) / a.span_len;
+    a.walk_len = kNeighborWalkBlocks;
+    while ((TB + a.walk_len - 1) / a.walk_len > 65535u) a.walk_len *= 2;  // (the grid's second dimension)
+
+    const size_t nr = job.nr, n_pad = job.n_rinv;
+    d_thr.ensure(n_pad);
+    d_span_max.ensure((size_t)a.spans * nr);
+    d_cnt_off.ensure(2 * nr + 1);
+    d_cnt.ensure(1);
+    a.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)k * (uint64_t)rows));
+    d_cand.ensure(a.cand_cap);
+    d_out_ids.ensure((size_t)rows);
+    d_out_nbr.ensure((size_t)rows * k);
+    d_out_score.ensure((size_t)rows * k);
+    d_out_count.ensure((size_t)rows);
+    a.rinv = job.d_rinv.p;
+    a.thr = d_thr.p;
+    a.norm = job.d_norm.p;
+    a.span_max = d_span_max.p;
+    a.row_cnt = d_cnt_off.p;
+    a.row_off = d_cnt_off.p + nr;
+    a.counters = d_cnt.p;
+    a.seg_out0 = job.seg_out0;
+    a.out_ids = d_out_ids.p;
+    a.out_nbr = d_out_nbr.p;
+    a.out_score = d_out_score.p;
+    a.out_count = d_out_count.p;
+
+    pcv_neighbor_stats& stats = s->nbr_stats;
+    stats.rows = rows;
+    stats.k = k;
+    stats.tile_rows = tile;
+    stats.sample_stride = (int32_t)a.stride;
+    stats.spans = (int32_t)a.spans;
+
+    unsigned long long count[1] = {0}, again[1] = {0};
+    PCV_HIP(hipMemsetAsync(d_thr.p, 0, n_pad * sizeof(float), st));
+    PCV_HIP(hipMemsetAsync(d_span_max.p, 0, (size_t)a.spans * nr * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+    job.prep();
+    launch_neighbors_bound(st, p, dp, a);
+    launch_neighbors_threshold(st, p, a);
+    job.record(2);
+    a.stride = 1;  // the list pass: every block
+    const Listing list = list_candidates(
+        job, 2, d_cnt.p, count, again, a.cand_cap, kMaxNeighborCandidates,
+        [&] {
+            a.cand = d_cand.p;
+            launch_neighbors_list(st, p, dp, a);
+        },
+        [&] { PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st)); }, d_cand);
+    stats.prep_ms = job.elapsed(0);
+    stats.bound_ms = job.elapsed(1);
+    stats.screen_ms = list.ms;
+    const uint64_t n_cand = count[0];
+    stats.candidates = (int64_t)n_cand;
+    if (n_cand > kMaxNeighborCandidates)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED, "neighbors: the list pass leaves %llu candidates for k = %d, more than %llu: ask for fewer neighbours or fewer rows",
+                 (unsigned long long)n_cand, k, (unsigned long long)kMaxNeighborCandidates);
+    if (list.repeated) {  // (the pass lists the same pairs again)
+        PCV_REQUIRE(again[0] == n_cand, "neighbors: the repeated list pass left %llu candidates, the first %llu", again[0], (unsigned long long)n_cand);
+        stats.reruns = 1;
+        stats.screen_ms += list.again_ms;
+    }
+    a.n_cand = n_cand;
+    d_sorted_key.ensure((size_t)std::max<uint64_t>(1, n_cand));
+    d_sorted_row.ensure((size_t)std::max<uint64_t>(1, n_cand));
+    a.sorted_key = d_sorted_key.p;
+    a.sorted_row = d_sorted_row.p;
+    job.record(3);
+    launch_neighbors_rescore(st, p, dp, a);
+    job.record(4);
+    launch_neighbors_select(st, p, dp, a);
+    job.record(5);
+    job.wait();
+    stats.rescore_ms = job.elapsed(3);
+    stats.select_ms = job.elapsed(4);
+    PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_neighbor_ids, d_out_nbr.p, (size_t)rows * k * sizeof(int64_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_scores, d_out_score.p, (size_t)rows * k * sizeof(float), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_counts, d_out_count.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t listed = 0;
+    for (int64_t i = 0; i < rows; ++i) listed += out_counts[i];
+    stats.listed = listed;
+}
+
+// ---- density clusters (pcv_searcher_density_clusters; DESIGN.md §4 "Density clusters") ----
+constexpr uint64_t kMaxDensityBand = (uint64_t)1 << 28;  // band pairs the degree pass may list: 8 bytes each, and 8 more if confirmed
+constexpr int64_t kMaxDensityRows = (int64_t)1 << 30;
+
+// Prep, degree pass, rescore of the band, core flags, link pass, labels (density_kernels.hip), with find_duplicates' plumbing: the
+// row table, the tile choice, the spans and the rerun-once rule for a short band list.  The host waits where the band count decides
+// an allocation and at the end.  Everything the call allocates is its own and is given back when it ends: nothing of the searcher's
+// pass state is touched, and only the f32 rows are read.
+void density_clusters(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int min_items, int64_t capacity,
+                      int64_t* out_ids, int32_t* out_label, int8_t* out_kind, int32_t* out_degree, int64_t* out_rows, int32_t* out_clusters) {
+    PCV_REQUIRE(!s->dirty, "density_clusters: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "density_clusters: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_rows = n;
+    s->density_stats = pcv_density_stats{};
+    if (out_label == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "density_clusters: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity,
+                (long long)n);
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "density_clusters: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (n > kMaxDensityRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "density_clusters: %lld rows, more than 2^30", (long long)n);
+    *out_clusters = 0;
+    if (n == 0) return;
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<uint64_t> d_cand, d_conf;
+    DevBuf<uint32_t> d_degree, d_rows4;  // d_rows4: parent, attach, root, rank
+    DevBuf<uint8_t> d_core;
+    DevBuf<int32_t> d_label, d_out_degree;
+    DevBuf<int8_t> d_kind;
+    DevBuf<int64_t> d_out_ids;
+    DensityArgs a{};
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    RowsJob job(s, segs, "density_clusters", PCV_METRIC_COSINE, a.tile_blocks);
+    hipStream_t st = job.st;
+    const ScanParams& p = *job.p;
+    const ScanParams* dp = job.dp;
+    const int64_t rows = job.rows;
+
+    a.span_blocks = kJoinSpanBlocks;
+    while ((p.total_blocks + a.span_blocks - 1) / a.span_blocks > 65535u) a.span_blocks *= 2;  // (the grid's second dimension)
+    // thr + margin rounded up, thr - margin rounded down, both from f64: s >= hi certifies c >= thr, s < lo certifies c < thr
+    const double margin = (double)selfjoin_margin(s->Dp);
+    a.threshold = (double)threshold;
+    a.hi = std::nextafterf((float)((double)threshold + margin), INFINITY);
+    a.lo = std::nextafterf((float)((double)threshold - margin), -INFINITY);
+    a.min_items = min_items;
+    const size_t nr = job.nr, n_pad = job.n_rinv;
+    d_cnt.ensure(kDensityCounters);
+    d_degree.ensure(n_pad);
+    d_core.ensure(n_pad);
+    d_rows4.ensure(4 * nr);
+    d_label.ensure((size_t)rows);
+    d_out_degree.ensure((size_t)rows);
+    d_kind.ensure((size_t)rows);
+    d_out_ids.ensure((size_t)rows);
+    a.cand_cap = std::min<uint64_t>(kMaxDensityBand, std::max<uint64_t>(65536, 2 * (uint64_t)rows));
+    d_cand.ensure(a.cand_cap);
+    a.rinv = job.d_rinv.p;
+    a.norm = job.d_norm.p;
+    a.counters = d_cnt.p;
+    a.degree = d_degree.p;
+    a.core = d_core.p;
+    a.parent = d_rows4.p;
+    a.attach = d_rows4.p + nr;
+    a.root = d_rows4.p + 2 * nr;
+    a.rank = d_rows4.p + 3 * nr;
+    a.seg_out0 = job.seg_out0;
+    a.out_label = d_label.p;
+    a.out_kind = d_kind.p;
+    a.out_degree = d_out_degree.p;
+    a.out_ids = d_out_ids.p;
+
+    pcv_density_stats& stats = s->density_stats;
+    stats.rows = rows;
+    stats.tile_rows = tile;
+
+    unsigned long long counts[kDensityCounters] = {}, again[kDensityCounters] = {};
+    PCV_HIP(hipMemsetAsync(d_degree.p, 0, n_pad * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_core.p, 0, n_pad * sizeof(uint8_t), st));
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kDensityCounters * sizeof(unsigned long long), st));
+    job.prep();
+    static_assert(kDensityBand == 0, "the band count is the counter the listing rule reads");
+    const Listing degree = list_candidates(
+        job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxDensityBand,
+        [&] {
+            a.cand = d_cand.p;
+            launch_density_degree(st, p, dp, a);
+        },
+        [&] {  // (the pass adds to the degrees and to the sure pairs as well)
+            PCV_HIP(hipMemsetAsync(d_degree.p, 0, n_pad * sizeof(uint32_t), st));
+            PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kDensityCounters * sizeof(unsigned long long), st));
+        },
+        d_cand);
+    stats.prep_ms = job.elapsed(0);
+    stats.degree_ms = degree.ms;
+    const uint64_t n_cand = counts[kDensityBand];
+    stats.candidates = (int64_t)n_cand;
+    stats.sure_pairs = (int64_t)counts[kDensitySure];
+    if (n_cand > kMaxDensityBand)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                 "density_clusters: %llu pairs lie within the screen's margin of threshold %g or hold a row it is not certified for, more than "
+                 "%llu (2^28): move the threshold or cluster fewer rows",
+                 (unsigned long long)n_cand, (double)threshold, (unsigned long long)kMaxDensityBand);
+    if (degree.repeated) {  // (the pass finds the same pairs again)
+        PCV_REQUIRE(again[kDensityBand] == n_cand && again[kDensitySure] == (unsigned long long)stats.sure_pairs,
+                    "density_clusters: the repeated degree pass found %llu band and %llu sure pairs, the first %llu and %lld", again[kDensityBand],
+                    again[kDensitySure], (unsigned long long)n_cand, (long long)stats.sure_pairs);
+        stats.reruns = 1;
+        stats.degree_ms += degree.again_ms;
+    }
+    a.n_cand = n_cand;
+    d_conf.ensure((size_t)std::max<uint64_t>(1, n_cand));
+    a.conf = d_conf.p;
+    job.record(2);
+    launch_density_rescore(st, p, dp, a);
+    job.record(3);
+    launch_density_core(st, p, a);
+    launch_density_link(st, p, dp, a);
+    job.record(4);
+    launch_density_labels(st, p, dp, a);
+    job.record(5);
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    job.wait();
+    stats.rescore_ms = job.elapsed(2);
+    stats.link_ms = job.elapsed(3);
+    stats.label_ms = job.elapsed(4);
+    stats.confirmed = (int64_t)counts[kDensityConfirmed];
+    stats.participating = (int64_t)counts[kDensityParticipating];
+    stats.core = (int64_t)counts[kDensityCore];
+    stats.border = (int64_t)counts[kDensityBorder];
+    stats.noise = (int64_t)counts[kDensityNoise];
+    stats.clusters = (int32_t)counts[kDensityClusters];
+    PCV_HIP(hipMemcpy(out_label, d_label.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_kind, d_kind.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
+    if (out_degree) PCV_HIP(hipMemcpy(out_degree, d_out_degree.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    *out_clusters = stats.clusters;
+}
+
+// ---- seed items (pcv_searcher_seeds; DESIGN.md §4 "Seed items") ----
+// Prep, begin, then k picks with a cover step between them (seed_kernels.hip): 2k launches queued on the searcher's stream and one
+// wait behind the last.  Everything the call allocates is its own and is given back when it ends: nothing of the searcher's pass
+// state is touched, and only the f32 rows are read.  The outputs are written last, after every check.
+void seeds(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int method, uint64_t seed, const int64_t* first_id, int64_t* out_ids,
+           int64_t* out_positions, int64_t* out_totals, float* out_cover, int32_t* out_count) {
+    PCV_REQUIRE(!s->dirty, "seeds: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "seeds: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    s->seed_stats = pcv_seed_stats{};
+    s->seed_stats.method = method;
+    std::vector<int64_t> ids((size_t)k, -1), pos((size_t)k, -1), totals((size_t)k, 0);
+    std::vector<float> cover((size_t)k, NAN);
+    SeedState state{};
+    if (!segs.empty()) {
+        DevBuf<float> d_out_cover;
+        DevBuf<double> d_cover;
+        DevBuf<SeedPart> d_part;
+        DevBuf<SeedState> d_state;
+        DevBuf<int64_t> d_out;  // ids, positions, totals
+        RowsJob job(s, segs, "seeds", PCV_METRIC_COSINE, 0);
+        hipStream_t st = job.st;
+        const ScanParams& p = *job.p;
+        const ScanParams* dp = job.dp;
+        s->seed_stats.rows = job.rows;
+
+        SeedArgs a{};
+        a.parts = (uint32_t)((job.nr + kSeedSpanRows - 1) / kSeedSpanRows);
+        d_cover.ensure(job.nr);
+        d_part.ensure(a.parts);
+        d_state.ensure(1);
+        d_out.ensure((size_t)3 * k);
+        d_out_cover.ensure((size_t)k);
+        a.rinv = job.d_rinv.p;
+        a.norm = job.d_norm.p;
+        a.cover = d_cover.p;
+        a.part = d_part.p;
+        a.state = d_state.p;
+        a.out_ids = d_out.p;
+        a.out_pos = d_out.p + k;
+        a.out_totals = d_out.p + 2 * (size_t)k;
+        a.out_cover = d_out_cover.p;
+        a.method = method;
+        a.seed = seed;
+        a.has_first = first_id != nullptr;
+        a.first_id = first_id ? *first_id : 0;
+
+        PCV_HIP(hipMemsetAsync(d_state.p, 0, sizeof(SeedState), st));
+        job.prep();
+        launch_seed_begin(st, p, dp, a);
+        for (int j = 0; j < k; ++j) {
+            a.step = j;
+            if (j > 0) launch_seed_cover(st, p, dp, a);
+            launch_seed_pick(st, p, dp, a);
+        }
+        job.record(2);
+        job.wait();
+        s->seed_stats.prep_ms = job.elapsed(0);
+        s->seed_stats.steps_ms = job.elapsed(1);
+        PCV_HIP(hipMemcpy(&state, d_state.p, sizeof(state), hipMemcpyDeviceToHost));
+        if (state.error == kSeedTooManyRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "seeds: more than 2^30 participating rows");
+        if (state.error != 0 && state.error != kSeedNoFirst) PCV_FAIL(PCV_ERR_INTERNAL, "seeds: a draw outside the prefix sums (step %d)", (int)state.count);
+        if (state.error == 0 && state.count > 0) {
+            PCV_REQUIRE(state.count <= k, "seeds: %d picks for k = %d", (int)state.count, k);
+            const size_t n = (size_t)state.count;
+            PCV_HIP(hipMemcpy(ids.data(), a.out_ids, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+            PCV_HIP(hipMemcpy(pos.data(), a.out_pos, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+            PCV_HIP(hipMemcpy(totals.data(), a.out_totals, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+            PCV_HIP(hipMemcpy(cover.data(), a.out_cover, n * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
+    // (no segment selected, or no participating row: nothing carries the id either)
+    if (first_id && (state.error == kSeedNoFirst || state.count == 0))
+        PCV_FAIL(PCV_ERR_INVALID, "seeds: no participating row of the selected sources carries first_id %lld", (long long)*first_id);
+    s->seed_stats.steps = state.count;
+    s->seed_stats.participating = state.count > 0 ? totals[0] : 0;
+    std::copy(ids.begin(), ids.end(), out_ids);
+    std::copy(pos.begin(), pos.end(), out_positions);
+    std::copy(totals.begin(), totals.end(), out_totals);
+    std::copy(cover.begin(), cover.end(), out_cover);
+    *out_count = state.count;
+}
+
+// ---- corpus moments and principal axes (pcv_searcher_moments, _principal_axes, _project) ----
+constexpr int64_t kMaxMomentRows = (int64_t)1 << 30;  // |t| <= 2^32 (1 + 2^-23): the int64 limb sums and the 128-bit finish hold 2^30 rows
+constexpr int kMaxMomentDim = 2048;
+
+// Prep, sums, and — with a matrix asked for — the limb SYRK (moments_kernels.hip) and its 128-bit finish on the host.  The outputs
+// are written last, after every check.
+void moments(pcv_searcher* s, const int64_t* source_ids, int n_sources, int centered, int64_t* out_sums, double* out_matrix, int64_t* out_n) {
+    PCV_REQUIRE(!s->dirty, "moments: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "moments: a sharded searcher (set_shard_offset) is not supported");
+    if (s->D > kMaxMomentDim) PCV_FAIL(PCV_ERR_UNSUPPORTED, "moments: dimension %d is above %d", s->D, kMaxMomentDim);
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    s->moment_stats = pcv_moment_stats{};
+    s->moment_stats.tile_features = kMomentSide;
+    const size_t D = (size_t)s->D, Dp = (size_t)s->Dp;
+    std::vector<long long> S(Dp + 1, 0);
+    std::vector<int64_t> hh, hl, ll;
+    if (!segs.empty()) {
+        DevBuf<long long> d_sums, d_mat;
+        RowsJob job(s, segs, "moments", PCV_METRIC_COSINE, 0);
+        job.prep();  // (it runs while the sums' room is made)
+        hipStream_t st = job.st;
+        s->moment_stats.rows = job.rows;
+        MomentArgs a{};
+        d_sums.ensure(Dp + 1);
+        a.norm = job.d_norm.p;
+        a.sums = d_sums.p;
+        PCV_HIP(hipMemsetAsync(d_sums.p, 0, (Dp + 1) * sizeof(long long), st));
+        if (out_matrix) {
+            d_mat.ensure(3 * Dp * Dp);
+            a.hh = d_mat.p;
+            a.hl = d_mat.p + Dp * Dp;
+            a.ll = d_mat.p + 2 * Dp * Dp;
+            PCV_HIP(hipMemsetAsync(d_mat.p, 0, 3 * Dp * Dp * sizeof(long long), st));
+            // some workgroups per CU over all the super-tiles; a chain not so short that its closing atomics show, nor above its bound
+            const uint32_t TB = job.p->total_blocks, pairs = (uint32_t)((Dp / kMomentSide) * (Dp / kMomentSide));
+            const uint32_t want = std::max<uint32_t>(1, 8 * (uint32_t)std::max(1, s->ctx->num_cus) / pairs);
+            a.range_blocks = std::min<uint32_t>(kMomentChainBlocks, std::max<uint32_t>(8, (TB + want - 1) / want));
+        }
+        job.record(1);  // (behind the memsets)
+        launch_moment_sums(st, *job.p, job.dp, a);
+        job.record(2);
+        if (out_matrix) {
+            launch_moment_syrk(st, *job.p, job.dp, a);
+            s->moment_stats.row_ranges = (int32_t)moment_row_ranges(*job.p, a);
+        }
+        job.record(3);
+        PCV_HIP(hipMemcpyAsync(S.data(), d_sums.p, (Dp + 1) * sizeof(long long), hipMemcpyDeviceToHost, st));
+        job.wait();
+        s->moment_stats.prep_ms = job.elapsed(0);
+        s->moment_stats.sums_ms = job.elapsed(1);
+        s->moment_stats.syrk_ms = out_matrix ? job.elapsed(2) : 0.0f;
+        s->moment_stats.participating = (int64_t)S[Dp];
+        if ((int64_t)S[Dp] > kMaxMomentRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "moments: more than 2^30 participating rows");
+        if (out_matrix) {  // [Dp][Dp] on the device -> [D][D]
+            std::vector<long long> m(3 * Dp * Dp);
+            PCV_HIP(hipMemcpy(m.data(), d_mat.p, m.size() * sizeof(long long), hipMemcpyDeviceToHost));
+            hh.resize(D * D);
+            hl.resize(D * D);
+            ll.resize(D * D);
+            for (size_t d = 0; d < D; ++d)
+                for (size_t e = 0; e < D; ++e) {
+                    hh[d * D + e] = (int64_t)m[d * Dp + e];
+                    hl[d * D + e] = (int64_t)m[Dp * Dp + d * Dp + e];
+                    ll[d * D + e] = (int64_t)m[2 * Dp * Dp + d * Dp + e];
+                }
+        }
+    }
+    std::vector<int64_t> sums(D);
+    for (size_t d = 0; d < D; ++d) sums[d] = (int64_t)S[d];
+    if (out_matrix) {
+        if (hh.empty()) {
+            std::fill(out_matrix, out_matrix + D * D, 0.0);
+        } else {
+            const pcv_status fin = pcv_moments_finish(hh.data(), hl.data(), ll.data(), sums.data(), (int64_t)S[Dp], s->D, centered, out_matrix);
+            if (fin != PCV_OK) throw Error{fin};
+        }
+    }
+    std::copy(sums.begin(), sums.end(), out_sums);
+    *out_n = (int64_t)S[Dp];
+}
+
+void principal_axes(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m, float* out_axes, double* out_offsets, double* out_variance,
+                    int64_t* out_n) {
+    PCV_REQUIRE(m <= s->D, "principal_axes: %d axes of a %d-d space", m, s->D);
+    const size_t D = (size_t)s->D;
+    std::vector<int64_t> sums(D);
+    std::vector<double> cov(D * D), values(D), vectors(D * D);
+    int64_t n = 0;
+    moments(s, source_ids, n_sources, 1, sums.data(), cov.data(), &n);
+    *out_n = n;
+    PCV_REQUIRE(n > 0, "principal_axes: no participating row in the selected sources");
+    const pcv_status eig = pcv_symmetric_eigen(cov.data(), s->D, values.data(), vectors.data());
+    if (eig != PCV_OK) throw Error{eig};
+    const double nn = (double)n;
+    for (int j = 0; j < m; ++j) {
+        double off = 0.0;
+        for (size_t d = 0; d < D; ++d) {
+            const float ax = (float)vectors[(size_t)j * D + d];
+            out_axes[(size_t)j * D + d] = ax;
+            const double mean = (double)sums[d] * 0x1p-32 / nn, term = (double)ax * mean;  // (no contraction: the sum is of rounded products)
+            off = off + term;
+        }
+        out_offsets[j] = off;
+        out_variance[j] = values[(size_t)j] / (nn * nn);
+    }
+}
+
+// Prep, then one pass per group of axes inside project_kernel.  The axes are packed here into the rows' piece layout.
+void project(pcv_searcher* s, const float* axes, const double* offsets, int m, const int64_t* source_ids, int n_sources, int64_t capacity,
+             float* out_coords, int64_t* out_ids, int64_t* out_n) {
+    PCV_REQUIRE(!s->dirty, "project: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "project: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_n = n;
+    if (out_coords == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "project: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    s->project_stats = pcv_project_stats{};
+    s->project_stats.axes = m;
+    s->project_stats.group = m <= 2 ? 2 : 8;
+    if (n == 0) return;
+    const size_t D = (size_t)s->D, D4 = (size_t)s->D4, blocks = ((size_t)m + 31) / 32;
+    std::vector<float> packed(blocks * D4 * 128, 0.0f);
+    for (int j = 0; j < m; ++j) {
+        float* dst = packed.data() + ((size_t)(j >> 5) * D4 * 32 + (size_t)(j & 31)) * 4;  // piece f of axis j: dst + f * 128 floats
+        for (size_t d = 0; d < D; ++d) dst[(d >> 2) * 128 + (d & 3)] = axes[(size_t)j * D + d];
+    }
+    std::vector<double> off((size_t)m, 0.0);
+    if (offsets) std::copy(offsets, offsets + m, off.begin());
+    DevBuf<float> d_axes, d_coords;
+    DevBuf<double> d_off;
+    DevBuf<int64_t> d_ids;
+    RowsJob job(s, segs, "project", PCV_METRIC_COSINE, 0);
+    job.prep();  // (it runs while the outputs' room is made)
+    hipStream_t st = job.st;
+    s->project_stats.rows = job.rows;
+    d_axes.ensure(packed.size());
+    d_off.ensure((size_t)m);
+    d_coords.ensure((size_t)n * m);
+    if (out_ids) d_ids.ensure((size_t)n);
+    ProjectArgs a{};
+    a.rinv = job.d_rinv.p;
+    a.norm = job.d_norm.p;
+    a.axes = reinterpret_cast<const float4*>(d_axes.p);
+    a.offsets = d_off.p;
+    a.seg_out0 = job.seg_out0;
+    a.out_coords = d_coords.p;
+    a.out_ids = out_ids ? d_ids.p : nullptr;
+    a.m = m;
+    PCV_HIP(hipMemcpyAsync(d_axes.p, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    PCV_HIP(hipMemcpyAsync(d_off.p, off.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+    job.record(1);  // (behind the uploads)
+    launch_project(st, *job.p, job.dp, a);
+    job.record(2);
+    job.wait();
+    s->project_stats.prep_ms = job.elapsed(0);
+    s->project_stats.project_ms = job.elapsed(1);
+    PCV_HIP(hipMemcpy(out_coords, d_coords.p, (size_t)n * m * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_ids.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+}
+
+}  // namespace
+
+extern "C" {
+
+pcv_status pcv_searcher_find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs,
+                                        int64_t* out_id_a, int64_t* out_id_b, float* out_scores, int64_t* out_count,
+                                        int64_t* out_total) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "find_duplicates: searcher is NULL");
+        PCV_REQUIRE(out_id_a != nullptr && out_id_b != nullptr && out_count != nullptr, "find_duplicates: out_id_a, out_id_b or out_count is NULL");
+        PCV_REQUIRE(max_pairs >= 1 && max_pairs <= (int64_t)PCV_MAX_DUPLICATE_PAIRS, "find_duplicates: max_pairs %lld outside [1,%d]",
+                    (long long)max_pairs, (int)PCV_MAX_DUPLICATE_PAIRS);
+        PCV_REQUIRE(threshold == threshold, "find_duplicates: threshold is NaN");
+        PCV_REQUIRE(threshold > -1.0f && threshold <= 1.0f, "find_duplicates: threshold %g outside (-1, 1]", (double)threshold);
+        const auto lk = enter(s, "find_duplicates");
+        find_duplicates(s, source_ids, n_sources, threshold, max_pairs, out_id_a, out_id_b, out_scores, out_count, out_total);
+    });
+}
+
+pcv_status pcv_searcher_last_duplicate_stats(pcv_searcher* s, pcv_duplicate_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_duplicate_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->dup_stats;
+    });
+}
+
+pcv_status pcv_searcher_assign(pcv_searcher* s, const float* labels, int n_labels, const int64_t* source_ids, int n_sources, int64_t capacity,
+                               int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(labels != nullptr && out_n != nullptr, "assign: labels or out_n is NULL");
+        PCV_REQUIRE(n_labels >= 1 && n_labels <= (int)PCV_MAX_LABELS, "assign: %d labels, outside [1,%d]", n_labels, (int)PCV_MAX_LABELS);
+        PCV_REQUIRE(capacity >= 0 && (out_label != nullptr || capacity == 0), "assign: out_label is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "assign: searcher is NULL");
+        const auto lk = enter(s, "assign");
+        assign_or_kmeans(s, "assign", labels, n_labels, 0, s->metric, source_ids, n_sources, capacity, nullptr, out_label, out_score, out_ids, out_counts,
+                         nullptr, nullptr, out_n);
+    });
+}
+
+pcv_status pcv_searcher_kmeans(pcv_searcher* s, const float* init, int n_labels, int max_iters, const int64_t* source_ids, int n_sources,
+                               int64_t capacity, float* out_centroids, int32_t* out_label, float* out_score, int64_t* out_ids,
+                               int64_t* out_counts, int32_t* out_iters, int64_t* out_moved, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(init != nullptr && out_n != nullptr, "kmeans: init or out_n is NULL");
+        PCV_REQUIRE(n_labels >= 1 && n_labels <= (int)PCV_MAX_LABELS, "kmeans: %d centroids, outside [1,%d]", n_labels, (int)PCV_MAX_LABELS);
+        PCV_REQUIRE(max_iters >= 0, "kmeans: max_iters %d is negative", max_iters);
+        PCV_REQUIRE(capacity >= 0 && (out_label != nullptr || capacity == 0), "kmeans: out_label is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(out_centroids != nullptr || (out_label == nullptr && capacity == 0), "kmeans: out_centroids is NULL");
+        PCV_REQUIRE(s != nullptr, "kmeans: searcher is NULL");
+        const auto lk = enter(s, "kmeans");
+        assign_or_kmeans(s, "kmeans", init, n_labels, max_iters, PCV_METRIC_COSINE, source_ids, n_sources, capacity, out_centroids, out_label, out_score,
+                         out_ids, out_counts, out_iters, out_moved, out_n);
+    });
+}
+
+pcv_status pcv_searcher_label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const int32_t* labels, int64_t n, int n_labels,
+                                   int64_t* out_sums, int64_t* out_counts) {
+    return guarded([&] {
+        PCV_REQUIRE(out_sums != nullptr && n >= 0 && (labels != nullptr || n == 0), "label_sums: labels or out_sums is NULL");
+        PCV_REQUIRE(n_labels >= 1 && n_labels <= (int)PCV_MAX_LABELS, "label_sums: %d labels, outside [1,%d]", n_labels, (int)PCV_MAX_LABELS);
+        PCV_REQUIRE(s != nullptr, "label_sums: searcher is NULL");
+        const auto lk = enter(s, "label_sums");
+        label_sums(s, source_ids, n_sources, labels, n, n_labels, out_sums, out_counts);
+    });
+}
+
+pcv_status pcv_searcher_last_assign_stats(pcv_searcher* s, pcv_assign_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_assign_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->assign_stats;
+    });
+}
+
+pcv_status pcv_searcher_neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int64_t capacity, int64_t* out_ids,
+                                  int64_t* out_neighbor_ids, float* out_scores, int32_t* out_counts, int64_t* out_rows) {
+    return guarded([&] {
+        PCV_REQUIRE(out_rows != nullptr, "neighbors: out_rows is NULL");
+        PCV_REQUIRE(k >= 1 && k <= (int)PCV_MAX_NEIGHBORS, "neighbors: k %d outside [1,%d]", k, (int)PCV_MAX_NEIGHBORS);
+        PCV_REQUIRE(capacity >= 0, "neighbors: capacity %lld is negative", (long long)capacity);
+        const bool all = out_ids != nullptr && out_neighbor_ids != nullptr && out_scores != nullptr && out_counts != nullptr;
+        const bool none = out_ids == nullptr && out_neighbor_ids == nullptr && out_scores == nullptr && out_counts == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "neighbors: an output array is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "neighbors: searcher is NULL");
+        const auto lk = enter(s, "neighbors");
+        neighbors(s, source_ids, n_sources, k, capacity, out_ids, out_neighbor_ids, out_scores, out_counts, out_rows);
+    });
+}
+
+pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_neighbor_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->nbr_stats;
+    });
+}
+
+pcv_status pcv_searcher_density_clusters(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int min_items,
+                                         int64_t capacity, int64_t* out_ids, int32_t* out_label, int8_t* out_kind, int32_t* out_degree,
+                                         int64_t* out_rows, int32_t* out_clusters) {
+    return guarded([&] {
+        PCV_REQUIRE(out_rows != nullptr, "density_clusters: out_rows is NULL");
+        PCV_REQUIRE(threshold == threshold, "density_clusters: threshold is NaN");
+        PCV_REQUIRE(threshold > -1.0f && threshold <= 1.0f, "density_clusters: threshold %g outside (-1, 1]", (double)threshold);
+        PCV_REQUIRE(min_items >= 1, "density_clusters: min_items %d is below 1", min_items);
+        PCV_REQUIRE(capacity >= 0, "density_clusters: capacity %lld is negative", (long long)capacity);
+        const bool all = out_label != nullptr && out_kind != nullptr && out_clusters != nullptr;
+        const bool none = out_label == nullptr && out_kind == nullptr && out_degree == nullptr && out_ids == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "density_clusters: out_label, out_kind or out_clusters is NULL with capacity %lld",
+                    (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "density_clusters: searcher is NULL");
+        const auto lk = enter(s, "density_clusters");
+        density_clusters(s, source_ids, n_sources, threshold, min_items, capacity, out_ids, out_label, out_kind, out_degree, out_rows, out_clusters);
+    });
+}
+
+pcv_status pcv_searcher_last_density_stats(pcv_searcher* s, pcv_density_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_density_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->density_stats;
+    });
+}
+
+pcv_status pcv_searcher_seeds(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int method, uint64_t seed,
+                              const int64_t* first_id, int64_t* out_ids, int64_t* out_positions, int64_t* out_totals,
+                              float* out_cover, int32_t* out_count) {
+    return guarded([&] {
+        PCV_REQUIRE(out_ids != nullptr && out_positions != nullptr && out_totals != nullptr && out_cover != nullptr && out_count != nullptr,
+                    "seeds: an output is NULL");
+        PCV_REQUIRE(k >= 1 && k <= (int)PCV_MAX_SEEDS, "seeds: k %d outside [1,%d]", k, (int)PCV_MAX_SEEDS);
+        PCV_REQUIRE(method == PCV_SEED_FARTHEST || method == PCV_SEED_KMEANSPP, "seeds: method %d is neither PCV_SEED_FARTHEST nor PCV_SEED_KMEANSPP", method);
+        PCV_REQUIRE(s != nullptr, "seeds: searcher is NULL");
+        const auto lk = enter(s, "seeds");
+        seeds(s, source_ids, n_sources, k, method, seed, first_id, out_ids, out_positions, out_totals, out_cover, out_count);
+    });
+}
+
+pcv_status pcv_searcher_last_seed_stats(pcv_searcher* s, pcv_seed_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_seed_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->seed_stats;
+    });
+}
+
+pcv_status pcv_seed_draw(uint64_t seed, int step, uint64_t total, uint64_t* out_t) {
+    return guarded([&] {
+        PCV_REQUIRE(out_t != nullptr, "seed_draw: out_t is NULL");
+        PCV_REQUIRE(step >= 0, "seed_draw: step %d is negative", step);
+        PCV_REQUIRE(total != 0, "seed_draw: total is 0");
+        *out_t = seed_draw(seed, (uint32_t)step, total);
+    });
+}
+
+pcv_status pcv_searcher_moments(pcv_searcher* s, const int64_t* source_ids, int n_sources, int centered, int64_t* out_sums, double* out_matrix,
+                                int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(out_sums != nullptr && out_n != nullptr, "moments: out_sums or out_n is NULL");
+        PCV_REQUIRE(s != nullptr, "moments: searcher is NULL");
+        const auto lk = enter(s, "moments");
+        moments(s, source_ids, n_sources, centered, out_sums, out_matrix, out_n);
+    });
+}
+
+pcv_status pcv_searcher_last_moment_stats(pcv_searcher* s, pcv_moment_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_moment_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->moment_stats;
+    });
+}
+
+pcv_status pcv_searcher_principal_axes(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m, float* out_axes, double* out_offsets,
+                                       double* out_variance, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(out_axes != nullptr && out_offsets != nullptr && out_variance != nullptr && out_n != nullptr, "principal_axes: an output is NULL");
+        PCV_REQUIRE(m >= 1 && m <= (int)PCV_MAX_AXES, "principal_axes: m %d outside [1,%d]", m, (int)PCV_MAX_AXES);
+        PCV_REQUIRE(s != nullptr, "principal_axes: searcher is NULL");
+        const auto lk = enter(s, "principal_axes");
+        principal_axes(s, source_ids, n_sources, m, out_axes, out_offsets, out_variance, out_n);
+    });
+}
+
+pcv_status pcv_searcher_project(pcv_searcher* s, const float* axes, const double* offsets, int m, const int64_t* source_ids, int n_sources,
+                                int64_t capacity, float* out_coords, int64_t* out_ids, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(axes != nullptr && out_n != nullptr, "project: axes or out_n is NULL");
+        PCV_REQUIRE(m >= 1 && m <= (int)PCV_MAX_AXES, "project: m %d outside [1,%d]", m, (int)PCV_MAX_AXES);
+        PCV_REQUIRE(capacity >= 0 && (out_coords != nullptr || capacity == 0), "project: out_coords is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(out_coords != nullptr || out_ids == nullptr, "project: out_ids without out_coords");
+        PCV_REQUIRE(s != nullptr, "project: searcher is NULL");
+        // (the dimension is fixed when the searcher is created: reading it needs no lock)
+        for (int64_t i = 0; i < (int64_t)m * s->D; ++i) PCV_REQUIRE(std::isfinite(axes[i]), "project: axis %lld has a value that is not finite", (long long)(i / s->D));
+        for (int j = 0; offsets && j < m; ++j) PCV_REQUIRE(std::isfinite(offsets[j]), "project: offset %d is not finite", j);
+        const auto lk = enter(s, "project");
+        project(s, axes, offsets, m, source_ids, n_sources, capacity, out_coords, out_ids, out_n);
+    });
+}
+
+pcv_status pcv_searcher_last_project_stats(pcv_searcher* s, pcv_project_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_project_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->project_stats;
+    });
+}
+
+// Union-find over the distinct ids of the pairs, by their index in ascending order: a root is always the smallest index of its
+// component, so the label of a component is its smallest id.
+pcv_status pcv_duplicate_groups(const int64_t* id_a, const int64_t* id_b, int64_t n_pairs, int64_t* out_ids, int64_t* out_group,
+                                int64_t capacity, int64_t* out_n_ids) {
+    return guarded([&] {
+        PCV_REQUIRE(out_n_ids != nullptr, "duplicate_groups: out_n_ids is NULL");
+        PCV_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || (id_a != nullptr && id_b != nullptr)), "duplicate_groups: %lld pairs without their ids",
+                    (long long)n_pairs);
+        std::vector<int64_t> ids;
+        ids.reserve((size_t)n_pairs * 2);
+        ids.insert(ids.end(), id_a, id_a + n_pairs);
+        ids.insert(ids.end(), id_b, id_b + n_pairs);
+        std::sort(ids.begin(), ids.end());
+        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+        const int64_t n = (int64_t)ids.size();
+        *out_n_ids = n;
+        PCV_REQUIRE(capacity >= n, "duplicate_groups: %lld ids, room for %lld", (long long)n, (long long)capacity);
+        PCV_REQUIRE(n == 0 || (out_ids != nullptr && out_group != nullptr), "duplicate_groups: out_ids or out_group is NULL");
+        std::vector<int64_t> parent((size_t)n);
+        std::iota(parent.begin(), parent.end(), (int64_t)0);
+        auto find = [&](int64_t i) {
+            while (parent[(size_t)i] != i) i = parent[(size_t)i] = parent[(size_t)parent[(size_t)i]];
+            return i;
+        };
+        for (int64_t k = 0; k < n_pairs; ++k) {
+            const int64_t x = find(std::lower_bound(ids.begin(), ids.end(), id_a[k]) - ids.begin());
+            const int64_t y = find(std::lower_bound(ids.begin(), ids.end(), id_b[k]) - ids.begin());
+            if (x != y) parent[(size_t)std::max(x, y)] = std::min(x, y);
+        }
+        for (int64_t i = 0; i < n; ++i) {
+            out_ids[i] = ids[(size_t)i];
+            out_group[i] = ids[(size_t)find(i)];
+        }
+    });
+}
+
+}  // extern "C"

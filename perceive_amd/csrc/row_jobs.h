@@ -1,0 +1,294 @@
+// row_jobs.h — the calls that run kernels over the stored rows themselves, not over a scan's candidates (duplicate pairs, item labels,
+// neighbours, density clusters, seeds, moments, projection): the arguments of their kernels and their launchers.  The host side is
+// row_jobs.cpp; a scan pass needs nothing of this file.
+#pragma once
+#include "scan.h"
+
+namespace pcv {
+
+// Duplicate pairs (pcv_searcher_find_duplicates; DESIGN.md §4 "Duplicate pairs"): rows against rows.  Rows are named by their
+// number in the launch's block numbering, block * 32 + row of the block ("launch row": the rows behind a segment's last row in its
+// last block have numbers too and take no part); launch rows ascend with the global position.
+//   rinv[launch row] : 1/|x| rounded to f32 from the row's canonical |x|^2;  0: the row takes no part (unsearchable, behind nrows,
+//                      no cosine);  kRinvWild: it takes part but |x| is outside [2^-20, 2^20], where the f32 screening score is
+//                      not certified — every pair with such a row is a candidate and the f64 step decides
+//   norm[launch row] : the canonical |x|^2 (f64, feature order)
+struct DupPair {
+    double c;            // canonical cosine
+    int64_t pos_a, pos_b;  // global positions, pos_a < pos_b
+    int64_t id_a, id_b;
+};
+constexpr float kRinvWild = -1.0f;
+struct SelfJoinArgs {
+    float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    double* norm;                   // [total_blocks * 32]
+    uint64_t* cand;                 // [cand_cap] (launch row a << 32) | launch row b, a < b
+    unsigned long long* counters;   // [0]: candidates the screen found (not capped), [1]: duplicate pairs (not capped)
+    DupPair* pairs;                 // [pair_cap]
+    unsigned long long cand_cap, pair_cap, n_cand;  // n_cand: entries of `cand` the rescore step reads
+    float screen_threshold;         // threshold - margin, rounded down
+    double threshold;
+    uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
+    uint32_t span_blocks;           // blocks of one work item's stream
+};
+
+// Item labels (pcv_searcher_assign, _label_sums, _kmeans; DESIGN.md §4 "Item labels"): every row against K label vectors.  Rows are
+// launch rows as above, with rinv / norm exactly as selfjoin_prep_kernel leaves them (under the dot metric a participating row
+// without a cosine is then marked kRinvWild: its dot products are still defined).  The labels are a small corpus of their own: one
+// segment in the blocked f32 layout, `label_blocks` blocks (a whole number of tiles; scale 1 for the K labels, 0 behind them), so
+// that the prep and rescore arithmetic of the rows is the labels' too.
+//   w[label], mg[label] : the screening score of (row, label) is s = acc * rinv_row * w and |s - c'| <= mg, c' the canonical score
+//                         in the row's units (cosine: c; dot: c / |x|).  cosine: w = 1/|l|, mg = selfjoin_margin; dot: w = 1,
+//                         mg = selfjoin_margin * |l| rounded up.  w = 0: no score with this label is defined (or it is padding);
+//                         w = kRinvWild: |l| outside [2^-20, 2^20], every participating row lists the label
+//   lb[launch row]      : the largest s - mg seen so far over the tiles launched, a lower bound of the row's best c'; -inf at first
+//   cand / cand_s       : (launch row << 32) | label and the s it was listed with (+inf for a wild row or label)
+//   best_key / best_lab : per launch row, the order-preserving image of the largest c (0: none) and the lowest label reaching it
+struct AssignArgs {
+    float* rinv;                    // [total_blocks * 32]
+    const double* norm;             // [total_blocks * 32]
+    const float4* lab_blk;          // [label_blocks][D4][32] the labels, blocked f32
+    const float* lab_rinv;          // [label_blocks * 32]
+    const double* lab_norm;         // [label_blocks * 32]
+    uint4* lab_tile;                // [label_blocks * 32][Dp / 8] bf16 pieces in the swizzled order of the LDS tile
+    float* w;                       // [label_blocks * 32]
+    float* mg;                      // [label_blocks * 32]
+    float* lb;                      // [total_blocks * 32]
+    uint64_t* cand;                 // [cand_cap]
+    float* cand_s;                  // [cand_cap]
+    unsigned long long* cand_key;   // [n_cand] image of c per candidate (0: below the final bound or undefined)
+    unsigned long long* counters;   // [0]: candidates listed (not capped), [1]: rows whose label changed
+    unsigned long long* best_key;   // [total_blocks * 32]
+    uint32_t* best_lab;             // [total_blocks * 32]
+    int32_t* row_label;             // [total_blocks * 32] the label of every launch row (-1: none, and before the first assignment),
+                                    // kept between k-means steps: the finish step counts the rows whose entry it changes
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    int32_t* out_label;             // [rows]
+    float* out_score;               // [rows]
+    int64_t* out_ids;               // [rows]
+    long long* out_counts;          // [K]
+    long long* sums;                // [K][Dp] integer sums of pcv_searcher_label_sums
+    long long* sum_counts;          // [K] rows that went into them
+    unsigned long long cand_cap, n_cand;
+    float margin;                   // selfjoin_margin(Dp)
+    int K, metric;
+    uint32_t tile_blocks;           // blocks of one label tile (4, 2 or 1)
+    uint32_t label_blocks;
+    uint32_t tile;                  // the tile of this screen launch
+    uint32_t span_blocks;           // row blocks one screen workgroup streams (a multiple of its waves)
+};
+
+// Item neighbours (pcv_searcher_neighbors; DESIGN.md §4 "Item neighbours"): the k best other rows of every row.  Rows are launch
+// rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  A launch block with number gb is SAMPLED iff gb is a multiple of
+// stride; sampled block j = gb / stride belongs to span j / span_len.
+//   span_max[span][launch row] : the order-preserving image (f32_key) of the largest certified screening score of the row with a
+//                                partner of that span's sampled blocks, 0: none.  The spans are disjoint sets of partners.
+//   thr[launch row]            : (k-th largest defined span maximum) - 2 margin, rounded down; -inf: fewer than k are defined, or
+//                                the row is wild — every participating partner is a candidate
+//   cand                       : (owner launch row << 32) | partner launch row, DIRECTED: the pair (a, b) is listed for owner a
+//                                iff s >= thr[a], and again for owner b iff s >= thr[b]
+//   row_off[launch row]        : where the owner's candidates start in sorted_key / sorted_row (an exclusive scan of row_cnt;
+//                                entry launch rows: the total); row_cnt is counted up, then counted down as the slots are taken
+//   sorted_key / sorted_row    : per owner, in any order: the f64_key image of c and the partner's launch row
+struct NeighborArgs {
+    float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    double* norm;                   // [total_blocks * 32]
+    uint32_t* span_max;             // [spans][total_blocks * 32]
+    float* thr;                     // [(total_blocks + tile_blocks) * 32]
+    uint64_t* cand;                 // [cand_cap]
+    unsigned long long* counters;   // [0]: candidates the list pass found (not capped)
+    uint32_t* row_cnt;              // [total_blocks * 32]
+    uint32_t* row_off;              // [total_blocks * 32 + 1]
+    unsigned long long* sorted_key; // [n_cand]
+    uint32_t* sorted_row;           // [n_cand]
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    int64_t* out_ids;               // [rows]
+    int64_t* out_nbr;               // [rows][k], unused slots -1
+    float* out_score;               // [rows][k], unused slots NaN
+    int32_t* out_count;             // [rows]
+    unsigned long long cand_cap, n_cand;
+    float margin;                   // selfjoin_margin(Dp)
+    int k;
+    uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
+    uint32_t stride;                // every stride-th block is a partner block of this launch (the list pass: 1)
+    uint32_t span_len;              // sampled blocks of one span
+    uint32_t spans;                 // ceil(sampled blocks / span_len), at most kMaxNeighborSpans
+    uint32_t walk_len;              // sampled blocks one workgroup streams against its tile
+};
+constexpr uint32_t kMaxNeighborSpans = 512;  // (the threshold kernel keeps a row's maxima in eight registers a lane)
+
+// Seed items (pcv_searcher_seeds; DESIGN.md §4 "Seed items"): k picks, one after the other, each by the weights the picks before it
+// leave.  Rows are launch rows, rinv / norm exactly as selfjoin_prep_kernel leaves them (rinv != 0: the row takes part).  Workgroup
+// g of the begin and cover kernels owns the launch rows [g * kSeedSpanRows, + kSeedSpanRows): launch rows ascend with the global
+// position, so the order of the partials is the order of the prefix sums.
+//   cover[launch row] : the largest canonical cosine with a seed so far; -inf before the first (the weight of step 0 is 1, not
+//                       seed_weight(cover))
+//   part[g]           : the sum of the span's weights, and its best (largest weight, lower launch row on ties; w = 0: none)
+//   state             : what one step leaves for the next, and the call for the host
+constexpr int kSeedSpanRows = 256;
+struct SeedPart {
+    unsigned long long sum;
+    unsigned long long w;
+    uint32_t row, pad;
+};
+struct SeedState {
+    uint32_t centre;   // launch row of the last pick
+    uint32_t done;     // a step found T == 0, or an error: every later kernel of the call returns at once
+    int32_t count;     // picks made
+    uint32_t error;    // kSeedNoFirst, kSeedTooManyRows, kSeedInternal
+};
+constexpr uint32_t kSeedNoFirst = 1u, kSeedTooManyRows = 2u, kSeedInternal = 3u;
+constexpr unsigned long long kMaxSeedRows = 1ull << 30;  // weights <= 2^33: the int64 totals hold 2^30 of them
+struct SeedArgs {
+    const float* rinv;              // [total_blocks * 32]
+    const double* norm;             // [total_blocks * 32]
+    double* cover;                  // [total_blocks * 32]
+    SeedPart* part;                 // [parts]
+    SeedState* state;
+    int64_t* out_ids;               // [k]
+    int64_t* out_pos;               // [k]
+    int64_t* out_totals;            // [k]
+    float* out_cover;               // [k]
+    uint32_t parts;                 // ceil(launch rows / kSeedSpanRows)
+    int step;                       // of this launch
+    int method;
+    int has_first;                  // step 0 picks the first participating row carrying first_id
+    int64_t first_id;
+    uint64_t seed;
+};
+
+// The weight a row has once a seed exists (perceive_hip.h): rint(max(0, 1 - cover) * 2^32), ties to even.  One rounding in the
+// subtraction; the product with 2^32 is exact.
+__host__ __device__ static inline unsigned long long seed_weight(double cover) {
+    const double d = 1.0 - cover;
+    return (unsigned long long)__builtin_rint((d > 0.0 ? d : 0.0) * 0x1p32);
+}
+// The draw of step j among `total` units (perceive_hip.h, pcv_seed_draw): the one copy, for seed_pick_kernel and the host.
+__host__ __device__ static inline uint64_t seed_draw(uint64_t seed, uint32_t j, uint64_t total) {
+    uint64_t z = seed + (uint64_t)(j + 1u) * 0x9E3779B97F4A7C15ull;
+    z ^= z >> 30;
+    z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(z, total);
+#else
+    return (uint64_t)(((unsigned __int128)z * total) >> 64);
+#endif
+}
+
+// Corpus moments and projection (pcv_searcher_moments, _project; DESIGN.md §4 "Corpus moments and principal axes").  Rows are launch
+// rows, rinv / norm exactly as selfjoin_prep_kernel leaves them (rinv != 0: the row takes part).  t(r, d) is the fixed-point unit row
+// of pcv_searcher_label_sums (launch_rows.h, unit_int), cut in two limbs t = h * 2^16 + l, h = t >> 16 in [-65537, 65536],
+// l = t & 0xffff: both exact in f32, every limb product below 2^32.01, so an f64 sum of up to 2^20 of them is exact in any order.
+//   sums[d]          : S_d = sum of t(r, d);  sums[Dp]: the participating rows
+//   hh, hl, ll       : [Dp][Dp] int64, HH = H^T H, HL = H^T L, LL = L^T L summed over the participating rows; hh and ll hold the 64 x 64
+//                      super-tiles on and above the diagonal only, hl all of them
+//   range_blocks     : row blocks of one workgroup's accumulation chain, at most kMomentChainBlocks
+constexpr uint32_t kMomentChainBlocks = 1u << 15;
+static_assert((uint64_t)kMomentChainBlocks * kBlockRows <= (1ull << 20), "an f64 chain of more than 2^20 limb products is not exact");
+constexpr int kMomentSide = 64;  // features of one side of a super-tile
+struct MomentArgs {
+    const double* norm;             // [total_blocks * 32]
+    long long* sums;                // [Dp + 1]
+    long long* hh;                  // [Dp][Dp]
+    long long* hl;
+    long long* ll;
+    uint32_t range_blocks;
+};
+// Projection: the canonical f64 dot of every participating row with m axes.  The axes are packed like rows: axis j is lane j & 31 of
+// block j >> 5 of a blocked f32 matrix with zero padding up to a whole number of blocks.
+struct ProjectArgs {
+    const float* rinv;              // [total_blocks * 32]
+    const double* norm;             // [total_blocks * 32]
+    const float4* axes;             // [ceil(m / 32)][D4][32]
+    const double* offsets;          // [m]
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    float* out_coords;              // [rows][m]
+    int64_t* out_ids;               // [rows]
+    int m;
+};
+
+// Density clusters (pcv_searcher_density_clusters; DESIGN.md §4 "Density clusters"): DBSCAN under the canonical cosine.  Rows are
+// launch rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  near(a, b) <=> c(a, b) >= threshold; the screening score s
+// of a pair of certified rows decides it alone where s >= hi (near: a SURE pair) or s < lo (not near); the band between, and every
+// pair with a wild row, is listed and decided by the f64 step.
+//   degree[launch row] : partners near the row (sure pairs and confirmed band pairs, each counted once for both rows)
+//   core[launch row]   : 1 iff the row takes part and degree + 1 >= min_items
+//   parent[launch row] : the union-find forest over the core rows; parent[r] <= r always, so a component's root is its core row of
+//                        the lowest global position
+//   attach[launch row] : the lowest core launch row near a row that is not core (UINT32_MAX: none)
+//   root / rank        : after the link step: the root of a core row's component, or of the component a border row attaches to
+//                        (UINT32_MAX: noise or no part); rank[r] = roots at launch rows below r = the cluster number of root r
+struct DensityArgs {
+    float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    double* norm;                   // [total_blocks * 32]
+    uint64_t* cand;                 // [cand_cap] band pairs, (launch row a << 32) | launch row b, a < b
+    uint64_t* conf;                 // [n_cand] the band pairs with c >= threshold, in any order
+    unsigned long long* counters;   // kDensity* below
+    uint32_t* degree;               // [(total_blocks + tile_blocks) * 32]
+    uint8_t* core;                  // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    uint32_t* parent;               // [total_blocks * 32]
+    uint32_t* attach;               // [total_blocks * 32]
+    uint32_t* root;                 // [total_blocks * 32]
+    uint32_t* rank;                 // [total_blocks * 32]
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    int32_t* out_label;             // [rows]
+    int8_t* out_kind;               // [rows]
+    int32_t* out_degree;            // [rows]
+    int64_t* out_ids;               // [rows]
+    unsigned long long cand_cap, n_cand;
+    float hi, lo;                   // threshold + margin rounded up, threshold - margin rounded down
+    double threshold;
+    int min_items;
+    uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
+    uint32_t span_blocks;           // blocks of one work item's stream
+};
+enum : int {
+    kDensityBand = 0,       // band pairs the degree pass found (not capped)
+    kDensityConfirmed,      // band pairs with c >= threshold
+    kDensitySure,           // pairs the screen decided alone
+    kDensityParticipating,
+    kDensityCore,
+    kDensityBorder,
+    kDensityNoise,
+    kDensityClusters,
+    kDensityCounters
+};
+
+// ---- duplicate pairs (selfjoin_kernels.hip); `p` needs seg, nseg, total_blocks, D, D4 only ----
+float selfjoin_margin(int Dp);  // certified bound on |screening score - canonical cosine| (DESIGN.md §4 "Duplicate pairs")
+void launch_selfjoin_prep(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
+void launch_selfjoin_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
+void launch_selfjoin_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
+// ---- item labels (assign_kernels.hip); `p` as for the duplicate pairs, plus metric ----
+void launch_assign_labels(hipStream_t st, const ScanParams& p, const AssignArgs& a);  // lab_rinv, lab_norm -> w, mg, lab_tile
+void launch_assign_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // lb, best_*, dot marks
+void launch_assign_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // one label tile
+void launch_assign_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
+void launch_assign_finish(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // winners -> outputs
+void launch_label_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
+// ---- item neighbours (neighbors_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_neighbors_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);    // -> span_max
+void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const NeighborArgs& a);                      // span_max -> thr
+void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);     // thr -> cand
+void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);  // cand -> sorted_*
+void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);   // sorted_* -> outputs
+// ---- density clusters (density_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_density_degree(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);   // -> degree, cand, counters
+void launch_density_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);  // cand -> degree, conf
+void launch_density_core(hipStream_t st, const ScanParams& p, const DensityArgs& a);                           // degree -> core, parent, attach
+void launch_density_link(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);     // sure pairs, conf -> parent, attach
+void launch_density_labels(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);   // parent, attach -> outputs
+// ---- seed items (seed_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_seed_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // cover = none, the partials of step 0
+void launch_seed_cover(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // the last pick -> cover, the partials of a.step
+void launch_seed_pick(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);   // the partials -> pick a.step, its outputs
+// ---- corpus moments and projection (moments_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_moment_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const MomentArgs& a);  // norm -> sums
+void launch_moment_syrk(hipStream_t st, const ScanParams& p, const ScanParams* dp, const MomentArgs& a);  // norm -> hh, hl, ll
+uint32_t moment_row_ranges(const ScanParams& p, const MomentArgs& a);
+void launch_project(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ProjectArgs& a);
+
+}  // namespace pcv

@@ -15,7 +15,7 @@
 // prefix sum are the same in any order of addition: the pick does not depend on how the rows are cut into workgroups.
 #include "device_access.h"
 #include "launch_rows.h"
-#include "scan.h"
+#include "row_jobs.h"
 
 namespace pcv {
 namespace {

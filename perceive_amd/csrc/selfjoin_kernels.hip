@@ -15,7 +15,7 @@
 //                               the arithmetic of distinct_select_kernel), kept iff c >= threshold.
 #include "device_access.h"
 #include "launch_rows.h"
-#include "scan.h"
+#include "row_jobs.h"
 
 namespace pcv {
 namespace {

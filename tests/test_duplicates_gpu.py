@@ -219,7 +219,7 @@ def test_truncation_is_a_prefix(ctx, oracle, golden_dir):
 
 # ---- 7. a list that has to grow --------------------------------------------------------------------------------------------
 def test_candidate_list_grows(ctx, oracle):
-    """700 identical rows: 244 650 pairs, more than the list of the first launch holds (max(65536, 2 * rows), searcher.cpp)"""
+    """700 identical rows: 244 650 pairs, more than the list of the first launch holds (max(65536, 2 * rows), row_jobs.cpp)"""
     rng = np.random.default_rng(16)
     rows = rng.standard_normal((1000, D)).astype(np.float32)
     where = rng.permutation(1000)[:700]

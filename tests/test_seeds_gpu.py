@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 D = 384
-SPAN = 256  # launch rows of one workgroup of the cover kernel (scan.h, kSeedSpanRows)
+SPAN = 256  # launch rows of one workgroup of the cover kernel (row_jobs.h, kSeedSpanRows)
 _GOLDEN = {}  # (name, metric) -> (rows, ids, Reference): computed once, shared, never changed
 
 
@@ -361,6 +361,30 @@ def test_first_id(ctx, oracle):
     assert out_ids.tolist() == [0] + [-1] * (k - 1) and out_pos.tolist() == [0] + [-1] * (k - 1) and out_tot.tolist() == [5] + [0] * (k - 1)
     assert np.isnan(out_cov).all()
     few.close()
+    s.close()
+
+
+def test_a_call_that_fails_behind_its_kernels_leaves_the_searcher_as_it_was(ctx, oracle):
+    """An unknown first_id is found out on the device: the call fails with every kernel run and its buffers still to give back.  The
+    calls after it — seeds again, and a search — give what they gave before, byte for byte."""
+    rng = np.random.default_rng(82)
+    n, d, k = 200, 32, 4
+    rows = rng.standard_normal((n, d)).astype(np.float32)
+    ids = make_ids(rng, n)
+    s = build(ctx, rows, ids, sources=[(1, 0, 120), (2, 120, n)])
+    assert s.num_segments == 2
+    q = rows[:3] + np.float32(0.25) * rng.standard_normal((3, d)).astype(np.float32)
+    hits = s.search_vectors(None, 5, q)
+    first = s.seeds(None, k)
+    check(first, Reference(oracle, rows, ids).seeds(k, "kmeans++"))
+    unknown = int(ids.max()) + 1
+    assert unknown not in set(ids.tolist())
+    with pytest.raises(pa.PcvError) as e:
+        s.seeds(None, k, first_id=unknown)
+    assert e.value.status == 1  # PCV_ERR_INVALID
+    assert "seeds: no participating row of the selected sources carries first_id %d" % unknown in str(e.value)
+    same(s.seeds(None, k), first)
+    same(s.search_vectors(None, 5, q), hits)
     s.close()
 
 
