@@ -312,6 +312,56 @@ inline DensityClusters density_clusters_handle(pcv_searcher* h, const std::vecto
     return r;
 }
 
+// Searcher::linkage_tree / SearcherView::linkage_tree (pcv_searcher_linkage_tree): the single-linkage hierarchy of the items of
+// `sources` — their maximum spanning tree under the cosine, edges from best to worst — and linkage_cut, which cuts it (host only).
+struct LinkageTree {
+    std::vector<int64_t> ids;    // [n] by global position
+    std::vector<int8_t> part;    // [n] 1 iff the item takes part
+    std::vector<int64_t> pos_a;  // [e] positions into ids, pos_a < pos_b; e = participating items - 1 (or 0)
+    std::vector<int64_t> pos_b;  // [e]
+    std::vector<int64_t> id_a;   // [e]
+    std::vector<int64_t> id_b;   // [e]
+    std::vector<double> c;       // [e] the canonical cosine, descending
+};
+inline LinkageTree linkage_tree_handle(pcv_searcher* h, const std::vector<int64_t>& sources) {
+    LinkageTree r;
+    if (sources.empty()) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0, e = 0;
+    check(pcv_searcher_linkage_tree(h, sources.data(), (int)sources.size(), 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n, nullptr));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.ids.resize(room);
+    r.part.resize(room);
+    r.pos_a.resize(room);
+    r.pos_b.resize(room);
+    r.id_a.resize(room);
+    r.id_b.resize(room);
+    r.c.resize(room);
+    check(pcv_searcher_linkage_tree(h, sources.data(), (int)sources.size(), (int64_t)room, r.ids.data(), r.part.data(), r.pos_a.data(), r.pos_b.data(),
+                                    r.id_a.data(), r.id_b.data(), r.c.data(), &n, &e));
+    r.ids.resize((size_t)n);
+    r.part.resize((size_t)n);
+    r.pos_a.resize((size_t)e);
+    r.pos_b.resize((size_t)e);
+    r.id_a.resize((size_t)e);
+    r.id_b.resize((size_t)e);
+    r.c.resize((size_t)e);
+    return r;
+}
+struct LinkageCut {
+    std::vector<int32_t> labels;  // [n] the cluster, numbered by its lowest position; -1: the item takes no part
+    int32_t clusters = 0;
+};
+// edge i is kept iff c[i] >= threshold and i < e - (min_clusters - 1): a threshold alone gives the components of the graph c >= t
+// (density_clusters with min_items 1), min_clusters K with threshold -infinity gives K clusters
+inline LinkageCut linkage_cut(const LinkageTree& t, double threshold, int64_t min_clusters = 1) {
+    LinkageCut r;
+    r.labels.resize(std::max<size_t>(t.ids.size(), 1));
+    check(pcv_linkage_cut(t.pos_a.data(), t.pos_b.data(), t.c.data(), (int64_t)t.c.size(), t.part.empty() ? nullptr : t.part.data(), (int64_t)t.ids.size(),
+                          threshold, min_clusters, r.labels.data(), &r.clusters));
+    r.labels.resize(t.ids.size());
+    return r;
+}
+
 // Searcher::seeds / SearcherView::seeds (pcv_searcher_seeds): up to k items that cover `sources`, in the order they were picked —
 // the init of kmeans (k-means++), or a representative sample with its covering radii (farthest first).
 enum class SeedMethod { Farthest = PCV_SEED_FARTHEST, KMeansPP = PCV_SEED_KMEANSPP };
@@ -512,6 +562,13 @@ public:
         check(pcv_searcher_last_density_stats(h_, &st));
         return st;
     }
+    // the linkage tree of the view's items (linkage_tree_handle)
+    LinkageTree linkage_tree(const std::vector<int64_t>& sources) const { return linkage_tree_handle(h_, sources); }
+    pcv_linkage_stats last_linkage_stats() const {
+        pcv_linkage_stats st;
+        check(pcv_searcher_last_linkage_stats(h_, &st));
+        return st;
+    }
     // the k nearest other items of every item of the view (neighbors_handle)
     NeighborTable neighbors(const std::vector<int64_t>& sources, size_t k) const { return neighbors_handle(h_, sources, k); }
     pcv_neighbor_stats last_neighbor_stats() const {
@@ -679,6 +736,13 @@ public:
     pcv_density_stats last_density_stats() const {
         pcv_density_stats st;
         check(pcv_searcher_last_density_stats(h_, &st));
+        return st;
+    }
+    // the single-linkage hierarchy of the items, built on the device (linkage_tree_handle); linkage_cut cuts it
+    LinkageTree linkage_tree(const std::vector<int64_t>& sources) const { return linkage_tree_handle(h_, sources); }
+    pcv_linkage_stats last_linkage_stats() const {
+        pcv_linkage_stats st;
+        check(pcv_searcher_last_linkage_stats(h_, &st));
         return st;
     }
     // the k nearest other items of every item, found once on the device (neighbors_handle)

@@ -711,6 +711,74 @@ typedef struct pcv_density_stats {
 } pcv_density_stats;
 pcv_status pcv_searcher_last_density_stats(pcv_searcher* s, pcv_density_stats* out);
 
+/* Linkage tree: the exact single-linkage hierarchy of the stored items, computed where the rows live — the clusters of the corpus at
+ * EVERY threshold at once.  It is the maximum-cosine spanning tree of the participating rows: cutting it at t gives exactly the
+ * connected components of the graph c >= t (pcv_searcher_density_clusters with min_items = 1), dropping its K - 1 weakest edges gives
+ * K clusters, and its edge list, best first, is the merge order of a dendrogram.
+ * The rows concerned are those of the selected segments in global position order, n of them, exactly as in
+ * pcv_searcher_density_clusters (hidden and unsearchable rows included: they keep their place); source_ids == NULL means all sources,
+ * an empty list selects nothing (n = 0); a view uses its own rows.  A row TAKES PART iff a pcv_searcher_search with the same filter
+ * could return it (scale != 0, not hidden) and it has a cosine (canonical |x|^2 in [2^-126, inf)); P is the number of such rows.
+ *   weight      of the edge {a, b}, output positions a < b: c(a, b), the canonical cosine of the two stored f32 rows — f64, products
+ *               exact, sums in feature order — for BOTH metrics.  Every participating pair has a finite c: the graph
+ *               is complete
+ *   edge order  strict and total: e is BETTER than e' iff its c is larger; on equal c the lower position a wins, then the lower b
+ *   the tree    the unique spanning tree Kruskal builds when it takes the edges from best to worst: P - 1 edges (0 if P <= 1),
+ *               returned from best to worst — the single-linkage merge order
+ *   capacity    rows the outputs have room for; capacity < n gives PCV_ERR_INVALID (out_rows is set)
+ *   out_ids     [capacity] the item id of every position; may be NULL
+ *   out_part    [capacity] 1 iff the row takes part; may be NULL
+ *   out_pos_a, out_pos_b  [capacity] the edges' output positions, pos_a < pos_b
+ *   out_id_a, out_id_b    [capacity] their item ids; may be NULL (both or neither)
+ *   out_c       [capacity] the canonical cosine, f64: a cut must compare what pcv_searcher_density_clusters compares with
+ *               (double)threshold, and (float)c can land on the other side of it
+ *   out_rows    n.  With every array NULL and capacity == 0 the call only reports n and does no device work (out_edges may be NULL
+ *               then, and is not written)
+ *   out_edges   the number of edges
+ * A NULL searcher or out_rows, a negative capacity, a NULL out_pos_a, out_pos_b, out_c or out_edges with another array given or
+ * capacity != 0, one of out_id_a / out_id_b without the other, capacity < n, and a sharded searcher (pcv_searcher_set_shard_offset
+ * != 0 or a pcv_comm: the tree spans every shard) give PCV_ERR_INVALID before any device work; a searcher with pending rows fails as
+ * in pcv_searcher_search.  PCV_ERR_UNSUPPORTED, with the searcher still usable: a dimension whose bf16 row tile does not fit the LDS
+ * of a CU (above 2496); more than 2^30 rows; more than 2^28 candidate pairs in one round (the message names the count, and the error
+ * comes before the larger list is allocated).  The result does not depend on which screening copies exist, nor on
+ * pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity: the call reads the f32 rows and touches no pass state (DESIGN.md §4
+ * "Linkage tree").  Everything it allocates on the device is given back when it returns.  Not in scope: a sharded form and
+ * device-resident output. */
+pcv_status pcv_searcher_linkage_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int64_t capacity, int64_t* out_ids,
+                                     int8_t* out_part, int64_t* out_pos_a, int64_t* out_pos_b, int64_t* out_id_a, int64_t* out_id_b,
+                                     double* out_c, int64_t* out_rows, int64_t* out_edges);
+
+/* Counters of the most recent pcv_searcher_linkage_tree on this handle (all zero after a call that only reported n). */
+typedef struct pcv_linkage_stats {
+    int64_t rows;           /* rows of the selected segments (those taking no part included)                   */
+    int64_t participating;  /* rows that take part                                                             */
+    int64_t edges;          /* edges of the tree: participating - 1, or 0                                      */
+    int64_t candidates;     /* directed (row, partner) pairs rescored in f64, all rounds summed                */
+    int32_t rounds;         /* Boruvka rounds: at most ceil(log2 participating)                                */
+    int32_t tile_rows;      /* rows of the LDS tile the screen kernel staged                                   */
+    int32_t reruns;         /* list passes repeated because the candidate list was short                       */
+    float prep_ms;          /* hipEvent times of the steps, each summed over the rounds (a repeated list pass  */
+    float bound_ms;         /* included in list_ms, a repeated bound pass and the wait for its count in        */
+    float list_ms;          /* bound_ms)                                                                       */
+    float rescore_ms;
+    float merge_ms;
+} pcv_linkage_stats;
+pcv_status pcv_searcher_last_linkage_stats(pcv_searcher* s, pcv_linkage_stats* out);
+
+/* Cuts a linkage tree (host only: no context, no GPU).  The edges are those pcv_searcher_linkage_tree returned, in its order: the
+ * function checks 0 <= pos_a < pos_b < n_rows and that c is non-increasing (no NaN), PCV_ERR_INVALID otherwise.  Edge i is KEPT iff
+ * c[i] >= threshold and i < n_edges - (min_clusters - 1): threshold = -inf with min_clusters = K gives K clusters (fewer edges than
+ * K - 1: none is kept), min_clusters = 1 with threshold = t the cut at t.  The components of the kept edges are numbered 0, 1, ... in
+ * ascending order of their lowest position; a participating row with no kept edge is a cluster of its own.
+ *   part         [n_rows] as out_part; part[r] == 0 gives label -1.  NULL: every row takes part
+ *   threshold    not NaN
+ *   min_clusters >= 1
+ *   out_label    [n_rows]
+ *   out_clusters the number of clusters; may be NULL
+ * An edge with an end that takes no part is PCV_ERR_INVALID. */
+pcv_status pcv_linkage_cut(const int64_t* pos_a, const int64_t* pos_b, const double* c, int64_t n_edges, const int8_t* part, int64_t n_rows,
+                           double threshold, int64_t min_clusters, int32_t* out_label, int32_t* out_clusters);
+
 /* Seed items: k stored items that cover the corpus, picked one after the other where the rows live — the init pcv_searcher_kmeans
  * asks for (k-means++), or a representative sample whose covering radii tell how many topics a library holds (farthest first).
  * The rows concerned are those of the selected segments in global position order, as in pcv_searcher_neighbors; source_ids == NULL

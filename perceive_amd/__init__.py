@@ -17,6 +17,7 @@ from .search import (  # noqa: F401
     dot_product,
     duplicate_groups,
     encode_query,
+    linkage_cut,
     merge_topk,
     seed_draw,
     serialize_embedding,

@@ -115,6 +115,23 @@ class DensityStats(C.Structure):
     ]
 
 
+class LinkageStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("participating", C.c_int64),
+        ("edges", C.c_int64),
+        ("candidates", C.c_int64),
+        ("rounds", C.c_int32),
+        ("tile_rows", C.c_int32),
+        ("reruns", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("bound_ms", C.c_float),
+        ("list_ms", C.c_float),
+        ("rescore_ms", C.c_float),
+        ("merge_ms", C.c_float),
+    ]
+
+
 class GroupStats(C.Structure):
     _fields_ = [
         ("ids", C.c_int64),
@@ -266,6 +283,10 @@ SYMBOLS = {
     "pcv_searcher_density_clusters": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int, C.c_int64, _I64P, _INTP, _I8P, _INTP,
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "pcv_searcher_last_density_stats": (C.c_int, [_P, C.POINTER(DensityStats)]),
+    "pcv_searcher_linkage_tree": (C.c_int, [_P, _I64P, C.c_int, C.c_int64, _I64P, _I8P, _I64P, _I64P, _I64P, _I64P, _F64P,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_linkage_stats": (C.c_int, [_P, C.POINTER(LinkageStats)]),
+    "pcv_linkage_cut": (C.c_int, [_I64P, _I64P, _F64P, C.c_int64, _I8P, C.c_int64, C.c_double, C.c_int64, _INTP, C.POINTER(C.c_int32)]),
     "pcv_searcher_seeds": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int, C.c_uint64, _I64P, _I64P, _I64P, _I64P, _F32P, _INTP]),
     "pcv_searcher_last_seed_stats": (C.c_int, [_P, C.POINTER(SeedStats)]),
     "pcv_seed_draw": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -375,4 +396,8 @@ def i32p(a):
 
 
 def i8p(a):
+    return a.ctypes.data
+
+
+def f64p(a):
     return a.ctypes.data

@@ -1,9 +1,11 @@
 // row_jobs.cpp — host side of the calls that run kernels over the stored rows themselves (row_jobs.h): duplicate pairs, item labels,
-// neighbours, density clusters, seeds, moments and projection, with their entry points of the C ABI.  They are one kind of call:
+// neighbours, density clusters, the linkage tree, seeds, moments and projection, with their entry points of the C ABI.  They are one kind of call:
 // select segments, open a RowsJob over them, run the call's kernels over its launch rows, bring the result down.  Everything is
 // allocated for the call and given back when it ends; nothing of the searcher's pass state is touched.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <numeric>
@@ -806,6 +808,216 @@ void density_clusters(pcv_searcher* s, const int64_t* source_ids, int n_sources,
     *out_clusters = stats.clusters;
 }
 
+// ---- linkage tree (pcv_searcher_linkage_tree; DESIGN.md §4 "Linkage tree") ----
+constexpr uint64_t kMaxLinkageCandidates = (uint64_t)1 << 28;  // directed pairs one round's list pass may leave: 16 bytes each
+constexpr int64_t kMaxLinkageRows = (int64_t)1 << 30;
+
+// Prep, then Borůvka rounds of bound pass, thresholds, list pass, rescore and choice, merge (linkage_kernels.hip), with the
+// neighbours' plumbing: the row table, the tile choice, the sampled bound pass and the rerun-once rule for a short list.  The host
+// waits where a count decides an allocation and at the end of a round, where it checks that the round emitted one edge per
+// component it removed and at least halved their number: no loop here can run on without progress.  Everything the call allocates
+// is its own and is given back when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
+void linkage_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int64_t capacity, int64_t* out_ids, int8_t* out_part, int64_t* out_pos_a,
+                  int64_t* out_pos_b, int64_t* out_id_a, int64_t* out_id_b, double* out_c, int64_t* out_rows, int64_t* out_edges) {
+    PCV_REQUIRE(!s->dirty, "linkage_tree: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "linkage_tree: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_rows = n;
+    s->linkage_stats = pcv_linkage_stats{};
+    if (out_pos_a == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "linkage_tree: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "linkage_tree: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (n > kMaxLinkageRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "linkage_tree: %lld rows, more than 2^30", (long long)n);
+    *out_edges = 0;
+    if (n == 0) return;
+    DevBuf<unsigned long long> d_cnt, d_cand_key, d_best, d_edges;  // d_best: best_key, best_pair;  d_edges: edge_pair, edge_key
+    DevBuf<uint64_t> d_cand;
+    DevBuf<uint32_t> d_comp, d_rows3;  // d_rows3: parent, cert, comp_max
+    DevBuf<float> d_thr;
+    DevBuf<int64_t> d_out_ids;
+    DevBuf<int8_t> d_out_part;
+    DevBuf<LinkEdge> d_out_edges;
+    LinkageArgs a{};
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    RowsJob job(s, segs, "linkage_tree", PCV_METRIC_COSINE, a.tile_blocks);
+    hipStream_t st = job.st;
+    const ScanParams& p = *job.p;
+    const ScanParams* dp = job.dp;
+    const int64_t rows = job.rows;
+
+    // The sample of the bound pass (DESIGN.md §4 "Linkage tree"): no result depends on it, only the list's length.
+    const uint32_t TB = p.total_blocks;
+    const uint32_t sample_stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / 64));
+    a.margin = selfjoin_margin(s->Dp);
+    a.walk_len = kNeighborWalkBlocks;
+    while ((TB + a.walk_len - 1) / a.walk_len > 65535u) a.walk_len *= 2;  // (the grid's second dimension)
+
+    const size_t nr = job.nr, n_pad = job.n_rinv;
+    d_cnt.ensure(kLinkCounters);
+    d_comp.ensure(n_pad);
+    d_rows3.ensure(3 * nr);
+    d_thr.ensure(nr);
+    d_best.ensure(2 * nr);
+    d_edges.ensure(2 * nr);
+    d_out_ids.ensure((size_t)rows);
+    d_out_part.ensure((size_t)rows);
+    a.cand_cap = std::min<uint64_t>(kMaxLinkageCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)nr));
+    d_cand.ensure(a.cand_cap);
+    d_cand_key.ensure(a.cand_cap);
+    a.rinv = job.d_rinv.p;
+    a.norm = job.d_norm.p;
+    a.comp = d_comp.p;
+    a.parent = d_rows3.p;
+    a.cert = d_rows3.p + nr;
+    a.comp_max = d_rows3.p + 2 * nr;
+    a.thr = d_thr.p;
+    a.best_key = d_best.p;
+    a.best_pair = d_best.p + nr;
+    a.edge_pair = d_edges.p;
+    a.edge_key = d_edges.p + nr;
+    a.edge_cap = nr;
+    a.counters = d_cnt.p;
+    a.seg_out0 = job.seg_out0;
+    a.out_ids = d_out_ids.p;
+    a.out_part = d_out_part.p;
+
+    pcv_linkage_stats& stats = s->linkage_stats;
+    stats.rows = rows;
+    stats.tile_rows = tile;
+
+    unsigned long long counts[kLinkCounters] = {}, again[kLinkCounters] = {};
+    PCV_HIP(hipMemsetAsync(d_comp.p, 0, n_pad * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kLinkCounters * sizeof(unsigned long long), st));
+    job.prep();
+    launch_linkage_begin(st, p, a);
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    job.wait();
+    stats.prep_ms = job.elapsed(0);
+    const uint64_t P = counts[kLinkParticipating];
+    stats.participating = (int64_t)P;
+    PCV_REQUIRE(P <= (uint64_t)rows, "linkage_tree: %llu participating rows of %lld", (unsigned long long)P, (long long)rows);
+
+    // PCV_LINKAGE_ROUNDS_FILE (tools/bench_linkage.py): one line per round is appended to that file — round, components before and
+    // after, candidates, bound repeated at stride 1 (0 / 1), list reruns, and the round's bound, list, rescore and merge ms
+    FILE* round_log = nullptr;
+    if (const char* f = getenv("PCV_LINKAGE_ROUNDS_FILE")) round_log = std::fopen(f, "a");
+    struct CloseLog {
+        FILE* f;
+        ~CloseLog() {
+            if (f) std::fclose(f);
+        }
+    } close_log{round_log};
+
+    uint64_t components = P, emitted = 0;
+    while (components > 1) {
+        bool bound_repeated = false;
+        // 1. the bound of every component, and its threshold
+        auto queue_bound = [&](uint32_t stride) {
+            PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkUnbounded, 0, 2 * sizeof(unsigned long long), st));
+            static_assert(kLinkCertRoots == kLinkUnbounded + 1, "the two counters of the threshold step are reset together");
+            a.stride = stride;
+            launch_linkage_bound(st, p, dp, a);
+            launch_linkage_threshold(st, p, a);
+        };
+        PCV_HIP(hipMemsetAsync(d_rows3.p + nr, 0, 2 * nr * sizeof(uint32_t), st));  // cert, comp_max
+        PCV_HIP(hipMemsetAsync(d_best.p, 0, nr * sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_best.p + nr, 0xff, nr * sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkRoots, 0, sizeof(unsigned long long), st));
+        job.record(0);
+        queue_bound(sample_stride);
+        if (sample_stride > 1) {
+            // a component with a certified row that met no certified foreign row in the sample, while there is one somewhere: without
+            // a bound it would list every foreign partner of every row it has.  Once more over every block (max commutes: what the
+            // sample found stays).
+            PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+            job.wait();
+            bound_repeated = counts[kLinkUnbounded] > 0 && counts[kLinkCertRoots] >= 2;
+            if (bound_repeated) queue_bound(1);
+        }
+        job.record(1);
+        // 2. the candidates
+        a.stride = 1;
+        const Listing list = list_candidates(
+            job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxLinkageCandidates,
+            [&] {
+                a.cand = d_cand.p;
+                a.cand_key = d_cand_key.p;
+                launch_linkage_list(st, p, dp, a);
+            },
+            [&] { PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st)); }, d_cand, d_cand_key);
+        static_assert(kLinkListed == 0, "the listed count is the counter the listing rule reads");
+        const float round_bound_ms = job.elapsed(0), round_list_ms = list.ms + (list.repeated ? list.again_ms : 0.0f);
+        stats.bound_ms += round_bound_ms;
+        stats.list_ms += list.ms;
+        const uint64_t n_cand = counts[kLinkListed];
+        if (n_cand > kMaxLinkageCandidates)
+            PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                     "linkage_tree: round %d lists %llu candidate pairs, more than %llu (2^28): too many rows are nearly the same distance from their "
+                     "nearest foreign row, or lie outside the lengths the screen is certified for; build the tree of fewer rows",
+                     (int)stats.rounds, (unsigned long long)n_cand, (unsigned long long)kMaxLinkageCandidates);
+        if (list.repeated) {  // (the pass lists the same pairs again)
+            PCV_REQUIRE(again[kLinkListed] == n_cand, "linkage_tree: the repeated list pass left %llu candidates, the first %llu", again[kLinkListed],
+                        (unsigned long long)n_cand);
+            stats.reruns += 1;
+            stats.list_ms += list.again_ms;
+        }
+        stats.candidates += (int64_t)n_cand;
+        stats.rounds += 1;
+        // 3. the f64 decision, 4. the merge
+        a.n_cand = n_cand;
+        job.record(3);
+        launch_linkage_rescore(st, p, dp, a);
+        job.record(4);
+        launch_linkage_merge(st, p, a);
+        job.record(5);
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        job.wait();
+        stats.rescore_ms += job.elapsed(3);
+        stats.merge_ms += job.elapsed(4);
+        // 5. one edge per component that went, and at least every second one went
+        const uint64_t after = counts[kLinkRoots], now = counts[kLinkEmitted];
+        if (!(after >= 1 && after <= components / 2 && now - emitted == components - after))
+            PCV_FAIL(PCV_ERR_INTERNAL, "linkage_tree: round %d went from %llu components to %llu and emitted %llu edges", (int)stats.rounds - 1,
+                     (unsigned long long)components, (unsigned long long)after, (unsigned long long)(now - emitted));
+        if (round_log)
+            std::fprintf(round_log, "%d %llu %llu %llu %d %d %.4f %.4f %.4f %.4f\n", (int)stats.rounds - 1, (unsigned long long)components,
+                         (unsigned long long)after, (unsigned long long)n_cand, bound_repeated ? 1 : 0, list.repeated ? 1 : 0, round_bound_ms, round_list_ms,
+                         job.elapsed(3), job.elapsed(4));
+        components = after;
+        emitted = now;
+    }
+    PCV_REQUIRE(emitted == (P > 0 ? P - 1 : 0), "linkage_tree: %llu edges for %llu participating rows", (unsigned long long)emitted, (unsigned long long)P);
+    stats.edges = (int64_t)emitted;
+
+    a.n_edges = emitted;
+    d_out_edges.ensure((size_t)std::max<uint64_t>(1, emitted));
+    a.out_edges = d_out_edges.p;
+    launch_linkage_output(st, p, dp, a);
+    job.wait();
+    std::vector<LinkEdge> edges((size_t)emitted);
+    if (emitted > 0) PCV_HIP(hipMemcpy(edges.data(), d_out_edges.p, (size_t)emitted * sizeof(LinkEdge), hipMemcpyDeviceToHost));
+    std::sort(edges.begin(), edges.end(), [](const LinkEdge& x, const LinkEdge& y) {
+        if (x.c != y.c) return x.c > y.c;
+        if (x.pos_a != y.pos_a) return x.pos_a < y.pos_a;
+        return x.pos_b < y.pos_b;
+    });
+    for (size_t i = 0; i < edges.size(); ++i) {
+        out_pos_a[i] = edges[i].pos_a;
+        out_pos_b[i] = edges[i].pos_b;
+        out_c[i] = edges[i].c;
+        if (out_id_a) {
+            out_id_a[i] = edges[i].id_a;
+            out_id_b[i] = edges[i].id_b;
+        }
+    }
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (out_part) PCV_HIP(hipMemcpy(out_part, d_out_part.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
+    *out_edges = (int64_t)emitted;
+}
+
 // ---- seed items (pcv_searcher_seeds; DESIGN.md §4 "Seed items") ----
 // Prep, begin, then k picks with a cover step between them (seed_kernels.hip): 2k launches queued on the searcher's stream and one
 // wait behind the last.  Everything the call allocates is its own and is given back when it ends: nothing of the searcher's pass
@@ -1172,6 +1384,74 @@ pcv_status pcv_searcher_last_density_stats(pcv_searcher* s, pcv_density_stats* o
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_density_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->density_stats;
+    });
+}
+
+pcv_status pcv_searcher_linkage_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int64_t capacity, int64_t* out_ids,
+                                     int8_t* out_part, int64_t* out_pos_a, int64_t* out_pos_b, int64_t* out_id_a, int64_t* out_id_b,
+                                     double* out_c, int64_t* out_rows, int64_t* out_edges) {
+    return guarded([&] {
+        PCV_REQUIRE(out_rows != nullptr, "linkage_tree: out_rows is NULL");
+        PCV_REQUIRE(capacity >= 0, "linkage_tree: capacity %lld is negative", (long long)capacity);
+        const bool all = out_pos_a != nullptr && out_pos_b != nullptr && out_c != nullptr && out_edges != nullptr;
+        const bool none = out_pos_a == nullptr && out_pos_b == nullptr && out_c == nullptr && out_ids == nullptr && out_part == nullptr &&
+                          out_id_a == nullptr && out_id_b == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "linkage_tree: out_pos_a, out_pos_b, out_c or out_edges is NULL with capacity %lld",
+                    (long long)capacity);
+        PCV_REQUIRE((out_id_a == nullptr) == (out_id_b == nullptr), "linkage_tree: one of out_id_a and out_id_b is NULL, the other is not");
+        PCV_REQUIRE(s != nullptr, "linkage_tree: searcher is NULL");
+        const auto lk = enter(s, "linkage_tree");
+        linkage_tree(s, source_ids, n_sources, capacity, out_ids, out_part, out_pos_a, out_pos_b, out_id_a, out_id_b, out_c, out_rows, out_edges);
+    });
+}
+
+pcv_status pcv_searcher_last_linkage_stats(pcv_searcher* s, pcv_linkage_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_linkage_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->linkage_stats;
+    });
+}
+
+// Union-find over the positions: the smaller root wins, so a component's root is its lowest position, and numbering the roots in
+// ascending order numbers the clusters by their lowest position.
+pcv_status pcv_linkage_cut(const int64_t* pos_a, const int64_t* pos_b, const double* c, int64_t n_edges, const int8_t* part, int64_t n_rows,
+                           double threshold, int64_t min_clusters, int32_t* out_label, int32_t* out_clusters) {
+    return guarded([&] {
+        PCV_REQUIRE(n_edges >= 0 && n_rows >= 0, "linkage_cut: %lld edges, %lld rows", (long long)n_edges, (long long)n_rows);
+        PCV_REQUIRE(n_edges == 0 || (pos_a != nullptr && pos_b != nullptr && c != nullptr), "linkage_cut: %lld edges without their arrays", (long long)n_edges);
+        PCV_REQUIRE(n_rows == 0 || out_label != nullptr, "linkage_cut: out_label is NULL");
+        PCV_REQUIRE(n_rows <= (int64_t)INT32_MAX, "linkage_cut: %lld rows do not fit the int32 labels", (long long)n_rows);
+        PCV_REQUIRE(threshold == threshold, "linkage_cut: threshold is NaN");
+        PCV_REQUIRE(min_clusters >= 1, "linkage_cut: min_clusters %lld is below 1", (long long)min_clusters);
+        for (int64_t i = 0; i < n_edges; ++i) {
+            PCV_REQUIRE(pos_a[i] >= 0 && pos_a[i] < pos_b[i] && pos_b[i] < n_rows, "linkage_cut: edge %lld joins positions %lld and %lld of %lld rows",
+                        (long long)i, (long long)pos_a[i], (long long)pos_b[i], (long long)n_rows);
+            PCV_REQUIRE(c[i] == c[i] && (i == 0 || c[i] <= c[i - 1]), "linkage_cut: the edges are not ordered from best to worst at edge %lld", (long long)i);
+            PCV_REQUIRE(part == nullptr || (part[pos_a[i]] != 0 && part[pos_b[i]] != 0), "linkage_cut: edge %lld has an end that takes no part", (long long)i);
+        }
+        std::vector<int64_t> parent((size_t)n_rows);
+        std::iota(parent.begin(), parent.end(), (int64_t)0);
+        auto find = [&](int64_t i) {
+            while (parent[(size_t)i] != i) i = parent[(size_t)i] = parent[(size_t)parent[(size_t)i]];
+            return i;
+        };
+        const int64_t keep_below = n_edges - (min_clusters - 1);
+        for (int64_t i = 0; i < n_edges && i < keep_below; ++i) {
+            if (!(c[i] >= threshold)) break;  // (c does not rise again)
+            const int64_t x = find(pos_a[i]), y = find(pos_b[i]);
+            if (x != y) parent[(size_t)std::max(x, y)] = std::min(x, y);
+        }
+        int32_t clusters = 0;
+        for (int64_t r = 0; r < n_rows; ++r) {  // a root comes before every other row of its component
+            if (part != nullptr && part[r] == 0)
+                out_label[r] = -1;
+            else if (parent[(size_t)r] == r)
+                out_label[r] = clusters++;
+            else
+                out_label[r] = out_label[find(r)];
+        }
+        if (out_clusters) *out_clusters = clusters;
     });
 }
 

@@ -1,6 +1,6 @@
 // row_jobs.h — the calls that run kernels over the stored rows themselves, not over a scan's candidates (duplicate pairs, item labels,
-// neighbours, density clusters, seeds, moments, projection): the arguments of their kernels and their launchers.  The host side is
-// row_jobs.cpp; a scan pass needs nothing of this file.
+// neighbours, density clusters, the linkage tree, seeds, moments, projection): the arguments of their kernels and their launchers.
+// The host side is row_jobs.cpp; a scan pass needs nothing of this file.
 #pragma once
 #include "scan.h"
 
@@ -257,6 +257,61 @@ enum : int {
     kDensityCounters
 };
 
+// Linkage tree (pcv_searcher_linkage_tree; DESIGN.md §4 "Linkage tree"): the maximum-cosine spanning tree of the participating rows
+// in Borůvka rounds.  Rows are launch rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  An edge is BETTER than another
+// iff its c is larger, then its lower launch row is lower, then its higher launch row is lower (launch rows ascend with the position).
+//   comp[launch row]   : the root of the row's component as the round found it: the component's lowest launch row.  Plain loads:
+//                        no kernel that reads it writes it.  Zero behind total_blocks * 32
+//   parent[launch row] : the union-find forest the merge step works on; parent[r] <= r always ("Density clusters")
+//   cert[root]         : 1 iff the component has a certified row (rinv > 0)
+//   comp_max[root]     : the f32_key image of the largest certified screening score of a certified row of the component with a
+//                        certified row of another component, over the partner blocks streamed so far; 0: none
+//   thr[root]          : comp_max - 2 margin, rounded down; -inf: no bound — every foreign partner is a candidate
+//   cand               : (owner launch row << 32) | partner launch row, DIRECTED: listed for owner a iff comp[a] != comp[b] and
+//                        s >= thr[comp[a]] (or one of the two is wild);  cand_key: the f64_key image of its c
+//   best_key[root]     : the largest cand_key among the component's candidates (0: none);  best_pair[root]: the lowest
+//                        (lower row << 32) | higher row among those that reach it
+//   edge_pair/edge_key : the edges chosen so far, in any order
+struct LinkEdge {
+    double c;
+    int64_t pos_a, pos_b;  // output positions, pos_a < pos_b
+    int64_t id_a, id_b;
+};
+struct LinkageArgs {
+    float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
+    double* norm;                   // [total_blocks * 32]
+    uint32_t* comp;                 // [(total_blocks + tile_blocks) * 32]
+    uint32_t* parent;               // [total_blocks * 32]
+    uint32_t* cert;                 // [total_blocks * 32]
+    uint32_t* comp_max;             // [total_blocks * 32]
+    float* thr;                     // [total_blocks * 32]
+    uint64_t* cand;                 // [cand_cap]
+    unsigned long long* cand_key;   // [cand_cap]
+    unsigned long long* best_key;   // [total_blocks * 32]
+    unsigned long long* best_pair;  // [total_blocks * 32]
+    unsigned long long* edge_pair;  // [edge_cap]
+    unsigned long long* edge_key;   // [edge_cap]
+    unsigned long long* counters;   // kLink* below
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    int64_t* out_ids;               // [rows]
+    int8_t* out_part;               // [rows]
+    LinkEdge* out_edges;            // [n_edges]
+    unsigned long long cand_cap, n_cand, edge_cap, n_edges;
+    float margin;                   // selfjoin_margin(Dp)
+    uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
+    uint32_t stride;                // every stride-th block is a partner block of this launch (the list pass: 1)
+    uint32_t walk_len;              // sampled blocks one workgroup streams against its tile
+};
+enum : int {
+    kLinkListed = 0,      // candidates the list pass of this round found (not capped)
+    kLinkEmitted,         // edges chosen, all rounds
+    kLinkRoots,           // components of participating rows behind this round's merge
+    kLinkUnbounded,       // components with a certified row and no bound behind this round's bound pass
+    kLinkCertRoots,       // components with a certified row
+    kLinkParticipating,
+    kLinkCounters
+};
+
 // ---- duplicate pairs (selfjoin_kernels.hip); `p` needs seg, nseg, total_blocks, D, D4 only ----
 float selfjoin_margin(int Dp);  // certified bound on |screening score - canonical cosine| (DESIGN.md §4 "Duplicate pairs")
 void launch_selfjoin_prep(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
@@ -281,6 +336,14 @@ void launch_density_rescore(hipStream_t st, const ScanParams& p, const ScanParam
 void launch_density_core(hipStream_t st, const ScanParams& p, const DensityArgs& a);                           // degree -> core, parent, attach
 void launch_density_link(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);     // sure pairs, conf -> parent, attach
 void launch_density_labels(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);   // parent, attach -> outputs
+// ---- linkage tree (linkage_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+void launch_linkage_begin(hipStream_t st, const ScanParams& p, const LinkageArgs& a);                          // comp, parent = the row; participating
+void launch_linkage_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);     // comp -> cert, comp_max
+void launch_linkage_threshold(hipStream_t st, const ScanParams& p, const LinkageArgs& a);                      // comp_max -> thr, counters
+void launch_linkage_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);      // thr, comp -> cand
+void launch_linkage_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);   // cand -> best_key, best_pair
+void launch_linkage_merge(hipStream_t st, const ScanParams& p, const LinkageArgs& a);                          // best_pair -> edges, parent, comp, roots
+void launch_linkage_output(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);    // edges, rinv -> outputs
 // ---- seed items (seed_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
 void launch_seed_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // cover = none, the partials of step 0
 void launch_seed_cover(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // the last pick -> cover, the partials of a.step

@@ -682,6 +682,37 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_last_density_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.DensityStats._fields_}
 
+    # ---- linkage tree (pcv_searcher_linkage_tree) ---------------------------------------------------
+    # The single-linkage hierarchy: the clusters of the corpus at every threshold at once (linkage_cut cuts it).
+    def linkage_tree(self, sources):
+        """The maximum spanning tree of the participating rows of `sources` under the canonical cosine (both metrics), edges ordered
+        by (c descending, lower position, higher position): the single-linkage merge order -> (ids [n] int64, part [n] int8: 1 iff
+        the row takes part, pos_a [e] int64, pos_b [e] int64: positions into ids with pos_a < pos_b, id_a [e], id_b [e] int64,
+        c [e] float64), e = participating rows - 1 (or 0).  A view uses its own rows."""
+        src, nsrc, _keep = _source_filter(sources)
+        n = C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_linkage_tree(self._handle, src, nsrc, 0, None, None, None, None, None, None, None, C.byref(n), None))
+        n = n.value
+        cap = max(n, 1)
+        ids = np.empty(cap, dtype=np.int64)
+        part = np.empty(cap, dtype=np.int8)
+        pos_a, pos_b, id_a, id_b = (np.empty(cap, dtype=np.int64) for _ in range(4))
+        c = np.empty(cap, dtype=np.float64)
+        got, edges = C.c_int64(), C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_linkage_tree(
+                self._handle, src, nsrc, cap, _ffi.i64p(ids), _ffi.i8p(part), _ffi.i64p(pos_a), _ffi.i64p(pos_b), _ffi.i64p(id_a),
+                _ffi.i64p(id_b), _ffi.f64p(c), C.byref(got), C.byref(edges),
+            )
+        )
+        e = edges.value
+        return ids[:n], part[:n], pos_a[:e], pos_b[:e], id_a[:e], id_b[:e], c[:e]
+
+    def last_linkage_stats(self):
+        st = _ffi.LinkageStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_linkage_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.LinkageStats._fields_}
+
     # ---- seed items (pcv_searcher_seeds) ------------------------------------------------------------
     # k items that cover the corpus, picked one after the other on the device: the init of kmeans, or a representative sample.
     def seeds(self, sources, k, method="kmeans++", seed=0, first_id=None):
@@ -1027,6 +1058,30 @@ def duplicate_groups(id_a, id_b):
         )
     )
     return ids[: n.value].copy(), group[: n.value].copy()
+
+
+def linkage_cut(pos_a, pos_b, c, n_rows, part=None, threshold=-np.inf, min_clusters=1):
+    """Cuts the tree of Searcher.linkage_tree (host only): edge i is kept iff c[i] >= threshold and i < len(c) - (min_clusters - 1)
+    -> (labels [n_rows] int32: the components of the kept edges, numbered by their lowest position, -1 where part == 0; the number
+    of clusters).  threshold t alone gives the components of the graph c >= t; min_clusters K alone gives K clusters."""
+    a = np.ascontiguousarray(pos_a, dtype=np.int64).reshape(-1)
+    b = np.ascontiguousarray(pos_b, dtype=np.int64).reshape(-1)
+    cc = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+    if not a.size == b.size == cc.size:
+        raise ValueError("pos_a, pos_b and c differ in length")
+    n_rows = int(n_rows)
+    pt = None if part is None else np.ascontiguousarray(part, dtype=np.int8).reshape(-1)
+    if pt is not None and pt.size != n_rows:
+        raise ValueError("part has not n_rows entries")
+    labels = np.empty(max(n_rows, 1), dtype=np.int32)
+    clusters = C.c_int32()
+    _ffi.check(
+        _ffi.lib().pcv_linkage_cut(
+            _ffi.i64p(a) if a.size else None, _ffi.i64p(b) if a.size else None, _ffi.f64p(cc) if a.size else None, a.size,
+            _ffi.i8p(pt) if pt is not None and pt.size else None, n_rows, float(threshold), int(min_clusters), _ffi.i32p(labels), C.byref(clusters),
+        )
+    )
+    return labels[:n_rows].copy(), clusters.value
 
 
 def seed_draw(seed, step, total):

@@ -659,6 +659,64 @@ impl Searcher {
         ((0..n as usize).map(|i| (ids[i], labels[i], kinds[i], degrees[i])).collect(), clusters as usize)
     }
 
+    /// Linkage tree (`pcv_searcher_linkage_tree`): the single-linkage hierarchy of the items of `sources` — their maximum spanning
+    /// tree under the cosine, edges ordered by (cosine descending, lower position, higher position): the merge order.
+    /// Returns ((item id, takes part) per item by global position, (position a, position b, cosine) per edge, a < b).
+    /// `linkage_cut` cuts it.
+    pub fn linkage_tree(&self, sources: &[i64]) -> (Vec<(i64, bool)>, Vec<(i64, i64, f64)>) {
+        if self.handle.is_null() || sources.is_empty() {
+            return (Vec::new(), Vec::new());
+        }
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_linkage_tree(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                &mut n,
+                std::ptr::null_mut(),
+            )
+        })
+        .expect("linkage_tree failed");
+        let room = n.max(1) as usize;
+        let mut ids = vec![-1i64; room];
+        let mut part = vec![0i8; room];
+        let mut pos_a = vec![-1i64; room];
+        let mut pos_b = vec![-1i64; room];
+        let mut c = vec![f64::NAN; room];
+        let mut edges: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_linkage_tree(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                room as i64,
+                ids.as_mut_ptr(),
+                part.as_mut_ptr(),
+                pos_a.as_mut_ptr(),
+                pos_b.as_mut_ptr(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                c.as_mut_ptr(),
+                &mut n,
+                &mut edges,
+            )
+        })
+        .expect("linkage_tree failed");
+        (
+            (0..n as usize).map(|i| (ids[i], part[i] != 0)).collect(),
+            (0..edges as usize).map(|i| (pos_a[i], pos_b[i], c[i])).collect(),
+        )
+    }
+
     /// Seed items (`pcv_searcher_seeds`): up to `k` items (clamped to PCV_MAX_SEEDS) that cover `sources`, in the order they were
     /// picked — `kmeanspp`: the k-means++ draw of `seed`, else farthest first; `first_id`: the item step 0 picks instead.
     /// Returns (item id, global position, potential before the pick in units of 2^-32, largest cosine with the seeds before it:
@@ -940,4 +998,32 @@ pub fn serialize_embedding(embedding: &[f32]) -> Vec<u8> {
     })
     .expect("serialize_embedding");
     bytes_vec
+}
+
+/// Cuts the tree of `Searcher::linkage_tree` (`pcv_linkage_cut`, host only): edge i is kept iff its cosine is at least `threshold`
+/// and i < edges - (min_clusters - 1).  Returns (cluster per item, numbered by lowest position, -1: the item takes no part; clusters).
+pub fn linkage_cut(items: &[(i64, bool)], edges: &[(i64, i64, f64)], threshold: f64, min_clusters: usize) -> (Vec<i32>, usize) {
+    let part: Vec<i8> = items.iter().map(|x| x.1 as i8).collect();
+    let pos_a: Vec<i64> = edges.iter().map(|e| e.0).collect();
+    let pos_b: Vec<i64> = edges.iter().map(|e| e.1).collect();
+    let c: Vec<f64> = edges.iter().map(|e| e.2).collect();
+    let mut labels = vec![-1i32; items.len().max(1)];
+    let mut clusters: i32 = 0;
+    hip::check(unsafe {
+        ffi::pcv_linkage_cut(
+            pos_a.as_ptr(),
+            pos_b.as_ptr(),
+            c.as_ptr(),
+            edges.len() as i64,
+            part.as_ptr(),
+            items.len() as i64,
+            threshold,
+            min_clusters.max(1) as i64,
+            labels.as_mut_ptr(),
+            &mut clusters,
+        )
+    })
+    .expect("linkage_cut failed");
+    labels.truncate(items.len());
+    (labels, clusters as usize)
 }
