@@ -862,6 +862,11 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? ((SRC16 ? NBUF <= 4 : NBUF == 
                 uint32_t mask = 0;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) mask |= (!(acc[t][i] < thr[t])) ? (1u << i) : 0u;
+                // a tile row beyond the batch keeps nothing, NaN accumulators included: !(NaN < inf) holds, and a row with an inf
+                // (f32 rows, scale 0: v * 0 = NaN) used to reach fine_survivors for queries that do not exist and to count as
+                // their coarse survivor, in words that only a later pass of more queries reads and clears.  (Here, on the rare
+                // path: the block test above stays as it was.)
+                if (32 * t + c >= p.B) mask = 0;
                 fine_survivors(p, mask, t, esc, elb, ltau0, lane, D4);
             }
         }

@@ -87,6 +87,10 @@ class Rows:
             scale = np.where(np.asarray(searchable, dtype=bool), scale, np.float32(0.0)).astype(np.float32)
         self.scale = np.zeros(npad, np.float32)
         self.scale[:n] = scale
+        self.nonfinite = np.zeros(npad, bool)  # a row with an inf or a NaN: scale 0, and NaN products where a kernel multiplies anyway
+        self.nonfinite[:n] = ~finite
+        self.x = np.zeros((npad, self.Dp))     # the f32 rows themselves; zeros for a row without a scale (the fine test ends there)
+        self.x[:n, :D] = np.where(scale[:, None] != 0, rows, np.float32(0.0))
         y = np.zeros((npad, self.Dp), np.float32)
         with np.errstate(over="ignore", invalid="ignore"):
             y[:n, :D] = np.where(scale[:, None] != 0, rows * scale[:, None], np.float32(0.0))
@@ -163,9 +167,30 @@ def estimates(rows, qs):
     return est, bound
 
 
+def keep_int8(rows, qs, tau, slack=0.0):
+    """The int8 test on its own, bool [nblk * 32, B]: acc8 >= s_blk (s_q tau - c1) - V_q with the kernel's constants (the header);
+    the slack's quantities are unit, |Rhs|, s_blk c1 and V_q.  The codes are small integers: the float64 product is exact."""
+    tau = np.asarray(tau, dtype=np.float64)
+    sgn, a = (1.0 if slack >= 0 else -1.0), abs(slack)
+    s = rows.block_of_rows(rows.s_blk.astype(np.float64))[:, None]   # NaN: no comparison succeeds
+    sq = qs.s_q.astype(np.float64)[None, :]
+    with np.errstate(invalid="ignore"):
+        ssq = s * sq
+        rhs = ssq * tau[None, :]
+        nrm = rows.max_norm if rows.metric == "dot" else 1.0
+        c1 = 0.5002 * np.sqrt(float(rows.Dp8)) * nrm
+        vq = (0.5002 * qs.l1 * qs.s_q + 0.2501 * rows.Dp8 + 4.0)[None, :]
+        allow8 = a * (ssq * qs.unit[None, :] + np.abs(rhs) + s * c1 + vq)
+        eight = (rows.codes8.astype(np.float64) @ qs.qh.T.astype(np.float64)) >= rhs - s * c1 - vq - sgn * allow8
+    dead = (qs.s_q == 0)[None, :]
+    has_rows = ~np.isnan(s)
+    fill = has_rows if rows.metric == "dot" else np.zeros_like(has_rows)
+    return np.where(dead, fill, eight)
+
+
 def keeps(rows, qs, tau, slack=0.0):
     """For thresholds tau [B] on the canonical score: (six, both) bool [nblk * 32, B] — the pairs the 6-bit test keeps, and the
-    subset the int8 test keeps as well."""
+    subset the int8 test (keep_int8) keeps as well."""
     tau = np.asarray(tau, dtype=np.float64)
     sgn, a = (1.0 if slack >= 0 else -1.0), abs(slack)
     s = rows.block_of_rows(rows.s_blk.astype(np.float64))[:, None]   # NaN: no comparison succeeds
@@ -178,17 +203,11 @@ def keeps(rows, qs, tau, slack=0.0):
         L = 4.0 * (rows.u @ qs.qh.T) - 126.5 * qs.qsum[None, :] + t2
         allow = a * (ssq * qs.unit[None, :] + np.abs(rhs) + t2) + min(a, WN_SLACK) * M
         six = L - rhs >= -sgn * allow
-        nrm = rows.max_norm if rows.metric == "dot" else 1.0
-        c1 = 0.5002 * np.sqrt(float(rows.Dp8)) * nrm
-        vq = (0.5002 * qs.l1 * qs.s_q + 0.2501 * rows.Dp8 + 4.0)[None, :]
-        allow8 = a * (ssq * qs.unit[None, :] + np.abs(rhs) + s * c1 + vq)
-        eight = (rows.codes8 @ qs.qh.T) >= rhs - s * c1 - vq - sgn * allow8
     dead = (qs.s_q == 0)[None, :]
     has_rows = ~np.isnan(s)
     fill = has_rows if rows.metric == "dot" else np.zeros_like(has_rows)
     six = np.where(dead, fill, six)
-    eight = np.where(dead, fill, eight)
-    return six, six & eight
+    return six, six & keep_int8(rows, qs, tau, slack)
 
 
 def range_tau(bounds, queries, rows):
@@ -217,26 +236,51 @@ def reported(c, metric, D):
 _range_cases = {}
 
 
-def range_case(oracle, D, metric):
+def range_case(oracle, D, metric, B=64, edges=False, depth=200, shared=0.0):
     """The fixed-threshold case of test_six_paths_gpu.py, once per (D, metric): 3 007 rows, 64 queries with 30 near rows planted for
     each, and per query the reported score of its 60th best row as the bound, so that 20..200 rows are in range.  Returns
-    (corpus, queries, bounds, in_range, opos, orep): the oracle's 200 best positions per query and their reported scores."""
-    if (D, metric) in _range_cases:
-        return _range_cases[D, metric]
-    rng = np.random.default_rng(6000 + D + (1 if metric == "dot" else 0))
-    n, B, near = 3007, 64, 30
+    (corpus, queries, bounds, in_range, opos, orep): the oracle's 200 best positions per query and their reported scores.
+    The same for B queries (tests/screens_ref.py): as many near rows each as 3 007 rows allow, 30 at the most, a seed of its own,
+    the oracle's `depth` best, and with `edges` an all-zero row, a row with an inf and a row with one dominant component
+    (EDGE_ROWS; edges = "blocks": a row with a dominant component in every block).  shared > 0: every row carries N(0, shared^2)
+    times one common direction and every query +-shared times it, so that a query's scores spread far wider than 1 / sqrt(D) and
+    few rows lie within a rounding's reach of any bound.  The defaults draw what they always drew."""
+    key = (D, metric) if (B, edges, depth, shared) == (64, False, 200, 0.0) else (D, metric, B, edges, depth, shared)
+    if key in _range_cases:
+        return _range_cases[key]
+    rng = np.random.default_rng(6000 + D + (1 if metric == "dot" else 0) + (0 if len(key) == 2 else 100_000 + 7 * B))
+    n, near = 3007, min(30, 3007 // B)
     queries = rng.standard_normal((B, D)).astype(np.float32)
     corpus = rng.standard_normal((n, D))
+    if shared > 0:
+        u = rng.standard_normal(D)
+        queries = (queries + shared * rng.choice([-1.0, 1.0], (B, 1)) * u[None, :]).astype(np.float32)
+        corpus = corpus + shared * rng.standard_normal((n, 1)) * u[None, :]
     spots = rng.permutation(n)[: B * near].reshape(B, near)
     for q in range(B):  # cosines of 0.1 .. 0.45 with their query
         w = rng.uniform(0.1, 0.5, (near, 1))
         corpus[spots[q]] = w * queries[q][None, :] + corpus[spots[q]]
     corpus = (corpus * rng.uniform(0.5, 2.0, (n, 1))).astype(np.float32)
-    opos, sc, cnt = oracle.topk(queries, corpus, 200, metric=1 if metric == "dot" else 0)
-    assert (cnt == 200).all()
+    if edges:
+        zero, inf, dominant = EDGE_ROWS
+        corpus[zero] = 0.0
+        corpus[inf, 3] = np.inf
+        corpus[dominant] *= np.float32(0.01)
+        corpus[dominant, 0] = 20.0  # one component far above the rest of its block
+        if edges == "blocks":  # ... and one such row in every block: the block scales are those of one-hot rows
+            for b in range(0, n, 32):
+                r = min(b + 7, n - 1)
+                if r not in EDGE_ROWS:
+                    corpus[r] *= np.float32(0.01)
+                    corpus[r, (b // 32) % D] = 20.0
+    opos, sc, cnt = oracle.topk(queries, corpus, depth, metric=1 if metric == "dot" else 0)
+    assert (cnt == depth).all()
     orep = reported(sc, metric, D)
     bounds = orep[:, 59].copy()
     in_range = (orep <= bounds[:, None]).sum(1) if metric == "dot" else (orep >= bounds[:, None]).sum(1)
     assert (in_range >= 20).all() and (in_range < 200).all()
-    _range_cases[D, metric] = (corpus, queries, bounds, in_range, opos, orep)
-    return _range_cases[D, metric]
+    _range_cases[key] = (corpus, queries, bounds, in_range, opos, orep)
+    return _range_cases[key]
+
+
+EDGE_ROWS = (77, 1490, 2050)  # range_case(edges=True): the all-zero row, the row with an inf, the row with a dominant component
