@@ -362,6 +362,77 @@ inline LinkageCut linkage_cut(const LinkageTree& t, double threshold, int64_t mi
     return r;
 }
 
+// Searcher::reach_tree / SearcherView::reach_tree (pcv_searcher_reach_tree): the spanning tree under the mutual-reachability weight
+// w = min(core(a), core(b), c(a, b)), core the (min_items - 1)-th largest cosine of an item with another — what HDBSCAN starts from —
+// and linkage_select, which picks clusters from it (or from a LinkageTree) without a threshold (host only).
+struct ReachTree {
+    std::vector<int64_t> ids;    // [n] by global position
+    std::vector<int8_t> part;    // [n] 1 iff the item takes part
+    std::vector<double> core;    // [n] the core score, +inf for min_items 1, NaN where part is 0
+    std::vector<int64_t> pos_a;  // [e] positions into ids, pos_a < pos_b; e = participating items - 1 (or 0)
+    std::vector<int64_t> pos_b;  // [e]
+    std::vector<int64_t> id_a;   // [e]
+    std::vector<int64_t> id_b;   // [e]
+    std::vector<double> w;       // [e] the weight, descending
+    std::vector<double> c;       // [e] the canonical cosine of the edge
+};
+inline ReachTree reach_tree_handle(pcv_searcher* h, const std::vector<int64_t>& sources, int min_items) {
+    ReachTree r;
+    if (sources.empty()) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0, e = 0;
+    check(pcv_searcher_reach_tree(h, sources.data(), (int)sources.size(), min_items, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, &n, nullptr));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.ids.resize(room);
+    r.part.resize(room);
+    r.core.resize(room);
+    r.pos_a.resize(room);
+    r.pos_b.resize(room);
+    r.id_a.resize(room);
+    r.id_b.resize(room);
+    r.w.resize(room);
+    r.c.resize(room);
+    check(pcv_searcher_reach_tree(h, sources.data(), (int)sources.size(), min_items, (int64_t)room, r.ids.data(), r.part.data(), r.core.data(),
+                                  r.pos_a.data(), r.pos_b.data(), r.id_a.data(), r.id_b.data(), r.w.data(), r.c.data(), &n, &e));
+    r.ids.resize((size_t)n);
+    r.part.resize((size_t)n);
+    r.core.resize((size_t)n);
+    r.pos_a.resize((size_t)e);
+    r.pos_b.resize((size_t)e);
+    r.id_a.resize((size_t)e);
+    r.id_b.resize((size_t)e);
+    r.w.resize((size_t)e);
+    r.c.resize((size_t)e);
+    return r;
+}
+struct LinkageSelection {
+    std::vector<int32_t> labels;    // [n] the selected cluster, numbered by its lowest position; -1: noise, or the item takes no part
+    std::vector<double> stability;  // [clusters]
+    std::vector<int64_t> size;      // [clusters] items labelled with it
+};
+inline LinkageSelection linkage_select(const std::vector<int64_t>& pos_a, const std::vector<int64_t>& pos_b, const std::vector<double>& w,
+                                       const std::vector<int8_t>& part, int64_t min_cluster_size, bool allow_single = false) {
+    LinkageSelection r;
+    const size_t n = part.size();
+    const size_t room = std::max<size_t>(n / (size_t)std::max<int64_t>(min_cluster_size, 2), 1);
+    int32_t clusters = 0;
+    r.labels.resize(std::max<size_t>(n, 1));
+    r.stability.resize(room);
+    r.size.resize(room);
+    check(pcv_linkage_select(pos_a.data(), pos_b.data(), w.data(), (int64_t)w.size(), part.empty() ? nullptr : part.data(), (int64_t)n, min_cluster_size,
+                             allow_single ? 1 : 0, r.labels.data(), &clusters, r.stability.data(), r.size.data(), (int64_t)room));
+    r.labels.resize(n);
+    r.stability.resize((size_t)clusters);
+    r.size.resize((size_t)clusters);
+    return r;
+}
+inline LinkageSelection linkage_select(const ReachTree& t, int64_t min_cluster_size, bool allow_single = false) {
+    return linkage_select(t.pos_a, t.pos_b, t.w, t.part, min_cluster_size, allow_single);
+}
+inline LinkageSelection linkage_select(const LinkageTree& t, int64_t min_cluster_size, bool allow_single = false) {
+    return linkage_select(t.pos_a, t.pos_b, t.c, t.part, min_cluster_size, allow_single);
+}
+
 // Searcher::seeds / SearcherView::seeds (pcv_searcher_seeds): up to k items that cover `sources`, in the order they were picked —
 // the init of kmeans (k-means++), or a representative sample with its covering radii (farthest first).
 enum class SeedMethod { Farthest = PCV_SEED_FARTHEST, KMeansPP = PCV_SEED_KMEANSPP };
@@ -569,6 +640,13 @@ public:
         check(pcv_searcher_last_linkage_stats(h_, &st));
         return st;
     }
+    // the reach tree of the view's items (reach_tree_handle)
+    ReachTree reach_tree(const std::vector<int64_t>& sources, int min_items) const { return reach_tree_handle(h_, sources, min_items); }
+    pcv_reach_stats last_reach_stats() const {
+        pcv_reach_stats st;
+        check(pcv_searcher_last_reach_stats(h_, &st));
+        return st;
+    }
     // the k nearest other items of every item of the view (neighbors_handle)
     NeighborTable neighbors(const std::vector<int64_t>& sources, size_t k) const { return neighbors_handle(h_, sources, k); }
     pcv_neighbor_stats last_neighbor_stats() const {
@@ -743,6 +821,13 @@ public:
     pcv_linkage_stats last_linkage_stats() const {
         pcv_linkage_stats st;
         check(pcv_searcher_last_linkage_stats(h_, &st));
+        return st;
+    }
+    // the spanning tree under the mutual-reachability weight, built on the device (reach_tree_handle); linkage_select picks its clusters
+    ReachTree reach_tree(const std::vector<int64_t>& sources, int min_items) const { return reach_tree_handle(h_, sources, min_items); }
+    pcv_reach_stats last_reach_stats() const {
+        pcv_reach_stats st;
+        check(pcv_searcher_last_reach_stats(h_, &st));
         return st;
     }
     // the k nearest other items of every item, found once on the device (neighbors_handle)

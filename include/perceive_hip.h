@@ -779,6 +779,77 @@ pcv_status pcv_searcher_last_linkage_stats(pcv_searcher* s, pcv_linkage_stats* o
 pcv_status pcv_linkage_cut(const int64_t* pos_a, const int64_t* pos_b, const double* c, int64_t n_edges, const int8_t* part, int64_t n_rows,
                            double threshold, int64_t min_clusters, int32_t* out_label, int32_t* out_clusters);
 
+/* Reach tree: the spanning tree HDBSCAN starts from — the linkage tree under the MUTUAL-REACHABILITY weight, which a single stray
+ * row cannot chain through — computed where the rows live.  Rows, participation (P participating rows), c(a, b), source selection,
+ * views, the n-only form and the argument errors are exactly those of pcv_searcher_linkage_tree.
+ *   min_items   1 .. PCV_MAX_NEIGHBORS + 1; it counts the item itself, as in pcv_searcher_density_clusters.  A value out of range
+ *               gives PCV_ERR_INVALID before the handle is looked at
+ *   core(r)     the j-th largest c(r, p) over the OTHER participating rows p, j = min(min_items - 1, P - 1): the f64 value, not its
+ *               float rounding; j = 0 gives +inf
+ *   weight      of the edge {a, b}, output positions a < b: w = min(core(a), core(b), c(a, b))
+ *   edge order  strict and total: e is BETTER than e' iff its w is larger; on equal w the lower position a wins, then the lower b.
+ *               c is not a key.  Ties are the normal case: every row's j nearest partners tie at its core score
+ *   the tree    the unique spanning tree Kruskal builds when it takes the edges from best to worst: P - 1 edges (0 if P <= 1),
+ *               returned from best to worst.  With min_items == 1 it is pcv_searcher_linkage_tree's output bit for bit (w == c)
+ *   out_core    [capacity] core(r) of every position, NaN for a row that takes no part; may be NULL
+ *   out_w       [capacity] the weight of every edge, f64
+ *   out_c       [capacity] its canonical cosine, f64; may be NULL
+ *   the others  as in pcv_searcher_linkage_tree (out_w in the place of its out_c among the arrays that must be given)
+ * Cutting the tree at t (pcv_linkage_cut on out_w) and keeping the rows with core >= t gives the core rows of
+ * pcv_searcher_density_clusters(t, min_items), cluster for cluster; pcv_linkage_select picks clusters without a threshold.
+ * PCV_ERR_UNSUPPORTED, with the searcher still usable: a dimension above 2496; more than 2^30 rows; more than 2^30 candidate pairs
+ * in the core step or 2^28 in one round (the message names the count, and the error comes before the larger list is allocated).
+ * The result does not depend on which screening copies exist, nor on pcv_searcher_set_kernel, _set_tuning or
+ * _set_candidate_capacity; nothing the call allocates on the device survives it and no pass state is touched (DESIGN.md §4 "Reach
+ * tree"). */
+pcv_status pcv_searcher_reach_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int min_items, int64_t capacity,
+                                   int64_t* out_ids, int8_t* out_part, double* out_core, int64_t* out_pos_a, int64_t* out_pos_b,
+                                   int64_t* out_id_a, int64_t* out_id_b, double* out_w, double* out_c, int64_t* out_rows,
+                                   int64_t* out_edges);
+
+/* Counters of the most recent pcv_searcher_reach_tree on this handle (all zero after a call that only reported n). */
+typedef struct pcv_reach_stats {
+    int64_t rows;             /* rows of the selected segments (those taking no part included)                 */
+    int64_t participating;    /* rows that take part                                                           */
+    int64_t edges;            /* edges of the tree: participating - 1, or 0                                    */
+    int64_t core_candidates;  /* directed (row, partner) pairs the core step rescored in f64                   */
+    int64_t candidates;       /* directed (row, partner) pairs the rounds rescored in f64, all rounds summed   */
+    int32_t rounds;           /* Boruvka rounds: at most ceil(log2 participating)                              */
+    int32_t tile_rows;        /* rows of the LDS tile the screen kernels staged                                */
+    int32_t reruns;           /* list passes repeated because the candidate list was short (core step included) */
+    int32_t min_items;
+    float core_ms;            /* the core step: the neighbours' bound, list and rescore, and the k-th best     */
+    float prep_ms;            /* hipEvent times of the steps, each summed over the rounds, as in               */
+    float bound_ms;           /* pcv_linkage_stats                                                             */
+    float list_ms;
+    float rescore_ms;
+    float merge_ms;
+} pcv_reach_stats;
+pcv_status pcv_searcher_last_reach_stats(pcv_searcher* s, pcv_reach_stats* out);
+
+/* Picks clusters from a reach tree without a threshold (host only: no context, no GPU): HDBSCAN's condensed tree and excess-of-mass
+ * selection, with the cosine itself as the density level.  The edges are those of pcv_searcher_reach_tree in its order with w (or of
+ * pcv_searcher_linkage_tree with its c).  The call checks the positions and the order as pcv_linkage_cut does, that the edges span
+ * the participating rows (n_edges == P - 1, no cycle) and min_cluster_size >= 2: PCV_ERR_INVALID otherwise.
+ *   dendrogram  edge i joins the two components Kruskal had before it; the last edge is the root
+ *   condensing  from the root down, M = min_cluster_size.  At a node of weight w inside cluster C with child sizes nL, nR: both
+ *               >= M: C ends at w, two clusters are born at w and all rows of C leave C at w; exactly one < M: that child's rows
+ *               leave C at w and C goes on into the other child; both < M: all rows leave C at w.  The root cluster is born at the
+ *               weight of the last edge
+ *   stability   S(C) = the sum over C's leave events, in the order they are met walking down, of
+ *               (double)size * (w_event - w_birth): f64, one subtraction, one multiplication, one addition per event, never
+ *               contracted into an FMA
+ *   selection   bottom-up.  A cluster without child clusters has T(C) = S(C); otherwise T_children = T(left) + T(right), left the
+ *               child that holds the lower position; S(C) >= T_children: C replaces its descendants and T(C) = S(C), otherwise
+ *               T(C) = T_children.  The root is a candidate only if allow_single != 0
+ *   out_label   [n_rows] the selected cluster that is the cluster the row was in when it left, or an ancestor of it; -1 if there is
+ *               none or the row takes no part.  Selected clusters are numbered 0, 1, ... by the lowest position of their labelled rows
+ *   out_clusters      the number of selected clusters; may be NULL
+ *   out_stability, out_size  [cluster_capacity] S and the labelled rows of the first cluster_capacity selected clusters; may be NULL */
+pcv_status pcv_linkage_select(const int64_t* pos_a, const int64_t* pos_b, const double* w, int64_t n_edges, const int8_t* part,
+                              int64_t n_rows, int64_t min_cluster_size, int allow_single, int32_t* out_label, int32_t* out_clusters,
+                              double* out_stability, int64_t* out_size, int64_t cluster_capacity);
+
 /* Seed items: k stored items that cover the corpus, picked one after the other where the rows live — the init pcv_searcher_kmeans
  * asks for (k-means++), or a representative sample whose covering radii tell how many topics a library holds (farthest first).
  * The rows concerned are those of the selected segments in global position order, as in pcv_searcher_neighbors; source_ids == NULL

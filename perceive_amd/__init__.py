@@ -18,6 +18,7 @@ from .search import (  # noqa: F401
     duplicate_groups,
     encode_query,
     linkage_cut,
+    linkage_select,
     merge_topk,
     seed_draw,
     serialize_embedding,

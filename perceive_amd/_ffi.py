@@ -132,6 +132,26 @@ class LinkageStats(C.Structure):
     ]
 
 
+class ReachStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("participating", C.c_int64),
+        ("edges", C.c_int64),
+        ("core_candidates", C.c_int64),
+        ("candidates", C.c_int64),
+        ("rounds", C.c_int32),
+        ("tile_rows", C.c_int32),
+        ("reruns", C.c_int32),
+        ("min_items", C.c_int32),
+        ("core_ms", C.c_float),
+        ("prep_ms", C.c_float),
+        ("bound_ms", C.c_float),
+        ("list_ms", C.c_float),
+        ("rescore_ms", C.c_float),
+        ("merge_ms", C.c_float),
+    ]
+
+
 class GroupStats(C.Structure):
     _fields_ = [
         ("ids", C.c_int64),
@@ -287,6 +307,11 @@ SYMBOLS = {
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_last_linkage_stats": (C.c_int, [_P, C.POINTER(LinkageStats)]),
     "pcv_linkage_cut": (C.c_int, [_I64P, _I64P, _F64P, C.c_int64, _I8P, C.c_int64, C.c_double, C.c_int64, _INTP, C.POINTER(C.c_int32)]),
+    "pcv_searcher_reach_tree": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int64, _I64P, _I8P, _F64P, _I64P, _I64P, _I64P, _I64P, _F64P, _F64P,
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_reach_stats": (C.c_int, [_P, C.POINTER(ReachStats)]),
+    "pcv_linkage_select": (C.c_int, [_I64P, _I64P, _F64P, C.c_int64, _I8P, C.c_int64, C.c_int64, C.c_int, _INTP, C.POINTER(C.c_int32), _F64P,
+                                     _I64P, C.c_int64]),
     "pcv_searcher_seeds": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int, C.c_uint64, _I64P, _I64P, _I64P, _I64P, _F32P, _INTP]),
     "pcv_searcher_last_seed_stats": (C.c_int, [_P, C.POINTER(SeedStats)]),
     "pcv_seed_draw": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),

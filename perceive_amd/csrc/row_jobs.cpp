@@ -1,5 +1,5 @@
 // row_jobs.cpp — host side of the calls that run kernels over the stored rows themselves (row_jobs.h): duplicate pairs, item labels,
-// neighbours, density clusters, the linkage tree, seeds, moments and projection, with their entry points of the C ABI.  They are one kind of call:
+// neighbours, density clusters, the linkage tree, the reach tree, seeds, moments and projection, with their entry points of the C ABI.  They are one kind of call:
 // select segments, open a RowsJob over them, run the call's kernels over its launch rows, bring the result down.  Everything is
 // allocated for the call and given back when it ends; nothing of the searcher's pass state is touched.
 #include <algorithm>
@@ -1018,6 +1018,305 @@ void linkage_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int
     *out_edges = (int64_t)emitted;
 }
 
+// ---- reach tree (pcv_searcher_reach_tree; DESIGN.md §4 "Reach tree") ----
+// Prep, the core step — the neighbours' bound, thresholds, list and rescore with k = j, then the j-th best f64 c of every row and
+// its two f32 images (reach_kernels.hip) — and the rounds of linkage_tree with the capped screen and the capped weight.  The checks
+// of a round, the stride-1 repeat of the bound pass and the rerun-once rule of the lists are linkage_tree's.  The core step's buffers
+// go back before the rounds allocate theirs.  Nothing of the searcher's pass state is touched, and only the f32 rows are read.
+void reach_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int min_items, int64_t capacity, int64_t* out_ids, int8_t* out_part,
+                double* out_core, int64_t* out_pos_a, int64_t* out_pos_b, int64_t* out_id_a, int64_t* out_id_b, double* out_w, double* out_c,
+                int64_t* out_rows, int64_t* out_edges) {
+    PCV_REQUIRE(!s->dirty, "reach_tree: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "reach_tree: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_rows = n;
+    s->reach_stats = pcv_reach_stats{};
+    if (out_pos_a == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "reach_tree: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "reach_tree: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (n > kMaxLinkageRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "reach_tree: %lld rows, more than 2^30", (long long)n);
+    *out_edges = 0;
+    if (n == 0) return;
+    DevBuf<unsigned long long> d_cnt, d_cand_key, d_best, d_edges, d_sorted_key;  // d_best: best_key, best_pair;  d_edges: edge_pair, edge_key
+    DevBuf<uint64_t> d_cand;
+    DevBuf<uint32_t> d_comp, d_rows3, d_span_max, d_cnt_off, d_sorted_row;  // d_rows3: parent, cert, comp_max
+    DevBuf<float> d_thr, d_k2, d_nbr_thr;                                   // d_k2: klo, khi
+    DevBuf<double> d_core, d_out_core;
+    DevBuf<int64_t> d_out_ids;
+    DevBuf<int8_t> d_out_part;
+    DevBuf<ReachEdge> d_out_edges;
+    ReachArgs ra{};
+    LinkageArgs& a = ra.l;
+    a.tile_blocks = (uint32_t)tile / kBlockRows;
+    RowsJob job(s, segs, "reach_tree", PCV_METRIC_COSINE, a.tile_blocks);
+    hipStream_t st = job.st;
+    const ScanParams& p = *job.p;
+    const ScanParams* dp = job.dp;
+    const int64_t rows = job.rows;
+
+    // The sample of the bound pass: no result depends on it, only the list's length.
+    const uint32_t TB = p.total_blocks;
+    const uint32_t sample_stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / 64));
+    a.margin = selfjoin_margin(s->Dp);
+    a.walk_len = kNeighborWalkBlocks;
+    while ((TB + a.walk_len - 1) / a.walk_len > 65535u) a.walk_len *= 2;  // (the grid's second dimension)
+
+    const size_t nr = job.nr, n_pad = job.n_rinv;
+    constexpr int kReachListed = kLinkCounters, kReachShort = kLinkCounters + 1, kReachCounters = kLinkCounters + 2;  // the core step's two
+    d_cnt.ensure(kReachCounters);
+    d_comp.ensure(n_pad);
+    d_k2.ensure(2 * n_pad);
+    d_core.ensure(nr);
+    d_rows3.ensure(3 * nr);
+    d_thr.ensure(nr);
+    d_best.ensure(2 * nr);
+    d_edges.ensure(2 * nr);
+    d_out_ids.ensure((size_t)rows);
+    d_out_part.ensure((size_t)rows);
+    d_out_core.ensure((size_t)rows);
+    a.rinv = job.d_rinv.p;
+    a.norm = job.d_norm.p;
+    a.comp = d_comp.p;
+    a.parent = d_rows3.p;
+    a.cert = d_rows3.p + nr;
+    a.comp_max = d_rows3.p + 2 * nr;
+    a.thr = d_thr.p;
+    a.best_key = d_best.p;
+    a.best_pair = d_best.p + nr;
+    a.edge_pair = d_edges.p;
+    a.edge_key = d_edges.p + nr;
+    a.edge_cap = nr;
+    a.counters = d_cnt.p;
+    a.seg_out0 = job.seg_out0;
+    a.out_ids = d_out_ids.p;
+    a.out_part = d_out_part.p;
+    ra.core = d_core.p;
+    ra.klo = d_k2.p;
+    ra.khi = d_k2.p + n_pad;
+    ra.short_rows = d_cnt.p + kReachShort;
+    ra.out_core = d_out_core.p;
+
+    pcv_reach_stats& stats = s->reach_stats;
+    stats.rows = rows;
+    stats.tile_rows = tile;
+    stats.min_items = min_items;
+
+    unsigned long long counts[kLinkCounters] = {}, again[kLinkCounters] = {};
+    PCV_HIP(hipMemsetAsync(d_comp.p, 0, n_pad * sizeof(uint32_t), st));
+    PCV_HIP(hipMemsetAsync(d_k2.p, 0, 2 * n_pad * sizeof(float), st));
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kReachCounters * sizeof(unsigned long long), st));
+    job.prep();
+    launch_linkage_begin(st, p, a);
+    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+    job.wait();
+    stats.prep_ms = job.elapsed(0);
+    const uint64_t P = counts[kLinkParticipating];
+    stats.participating = (int64_t)P;
+    PCV_REQUIRE(P <= (uint64_t)rows, "reach_tree: %llu participating rows of %lld", (unsigned long long)P, (long long)rows);
+
+    // The core step.  j = 0: every core is +inf and the neighbours have nothing to say.
+    const int j = (int)std::min<uint64_t>((uint64_t)(min_items - 1), P > 0 ? P - 1 : 0);
+    ra.k = j;
+    if (j >= 1) {
+        NeighborArgs b{};
+        b.tile_blocks = a.tile_blocks;
+        b.k = j;
+        b.margin = a.margin;
+        b.stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / (uint32_t)std::max(64, 4 * j)));
+        const uint32_t sampled = (TB + b.stride - 1) / b.stride;
+        const uint32_t want_spans = std::min<uint32_t>(sampled, std::min<uint32_t>(kMaxNeighborSpans, (uint32_t)std::max(64, 8 * j)));
+        b.span_len = (sampled + want_spans - 1) / want_spans;
+        b.spans = (sampled + b.span_len - 1) / b.span_len;
+        b.walk_len = a.walk_len;
+        d_nbr_thr.ensure(n_pad);
+        d_span_max.ensure((size_t)b.spans * nr);
+        d_cnt_off.ensure(2 * nr + 1);
+        b.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)j * (uint64_t)rows));
+        d_cand.ensure(b.cand_cap);
+        b.rinv = job.d_rinv.p;
+        b.thr = d_nbr_thr.p;
+        b.norm = job.d_norm.p;
+        b.span_max = d_span_max.p;
+        b.row_cnt = d_cnt_off.p;
+        b.row_off = d_cnt_off.p + nr;
+        b.counters = d_cnt.p + kReachListed;
+        b.seg_out0 = job.seg_out0;
+        PCV_HIP(hipMemsetAsync(d_nbr_thr.p, 0, n_pad * sizeof(float), st));
+        PCV_HIP(hipMemsetAsync(d_span_max.p, 0, (size_t)b.spans * nr * sizeof(uint32_t), st));
+        PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
+        job.record(1);
+        launch_neighbors_bound(st, p, dp, b);
+        launch_neighbors_threshold(st, p, b);
+        job.record(2);
+        b.stride = 1;  // the list pass: every block
+        unsigned long long listed[1] = {0}, listed_again[1] = {0};
+        const Listing list = list_candidates(
+            job, 2, d_cnt.p + kReachListed, listed, listed_again, b.cand_cap, kMaxNeighborCandidates,
+            [&] {
+                b.cand = d_cand.p;
+                launch_neighbors_list(st, p, dp, b);
+            },
+            [&] { PCV_HIP(hipMemsetAsync(d_cnt.p + kReachListed, 0, sizeof(unsigned long long), st)); }, d_cand);
+        stats.core_ms = job.elapsed(1) + list.ms;
+        const uint64_t n_core = listed[0];
+        stats.core_candidates = (int64_t)n_core;
+        if (n_core > kMaxNeighborCandidates)
+            PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                     "reach_tree: the core step lists %llu candidate pairs for min_items = %d, more than %llu (2^30): ask for fewer items or fewer rows",
+                     (unsigned long long)n_core, min_items, (unsigned long long)kMaxNeighborCandidates);
+        if (list.repeated) {
+            PCV_REQUIRE(listed_again[0] == n_core, "reach_tree: the repeated list pass of the core step left %llu candidates, the first %llu", listed_again[0],
+                        (unsigned long long)n_core);
+            stats.reruns += 1;
+            stats.core_ms += list.again_ms;
+        }
+        b.n_cand = n_core;
+        d_sorted_key.ensure((size_t)std::max<uint64_t>(1, n_core));
+        d_sorted_row.ensure((size_t)std::max<uint64_t>(1, n_core));
+        b.sorted_key = d_sorted_key.p;
+        b.sorted_row = d_sorted_row.p;
+        ra.row_off = b.row_off;
+        ra.sorted_key = b.sorted_key;
+        job.record(3);
+        launch_neighbors_rescore(st, p, dp, b);
+        launch_reach_core(st, p, ra);
+        job.record(4);
+        unsigned long long short_rows = 0;
+        PCV_HIP(hipMemcpyAsync(&short_rows, d_cnt.p + kReachShort, sizeof(short_rows), hipMemcpyDeviceToHost, st));
+        job.wait();
+        stats.core_ms += job.elapsed(3);
+        if (short_rows != 0)
+            PCV_FAIL(PCV_ERR_INTERNAL, "reach_tree: %llu participating rows were left fewer than %d rescored partners", short_rows, j);
+        d_nbr_thr.release();
+        d_span_max.release();
+        d_cnt_off.release();
+        d_sorted_key.release();
+        d_sorted_row.release();
+        d_cand.release();
+    } else {
+        launch_reach_core(st, p, ra);
+    }
+    a.cand_cap = std::min<uint64_t>(kMaxLinkageCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)nr));
+    d_cand.ensure(a.cand_cap);
+    d_cand_key.ensure(a.cand_cap);
+
+    // PCV_LINKAGE_ROUNDS_FILE (tools/bench_reach.py): one line per round, as linkage_tree writes them
+    FILE* round_log = nullptr;
+    if (const char* f = getenv("PCV_LINKAGE_ROUNDS_FILE")) round_log = std::fopen(f, "a");
+    struct CloseLog {
+        FILE* f;
+        ~CloseLog() {
+            if (f) std::fclose(f);
+        }
+    } close_log{round_log};
+
+    uint64_t components = P, emitted = 0;
+    while (components > 1) {
+        bool bound_repeated = false;
+        // 1. the bound of every component, and its threshold
+        auto queue_bound = [&](uint32_t stride) {
+            PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkUnbounded, 0, 2 * sizeof(unsigned long long), st));
+            a.stride = stride;
+            launch_reach_bound(st, p, dp, ra);
+            launch_linkage_threshold(st, p, a);
+        };
+        PCV_HIP(hipMemsetAsync(d_rows3.p + nr, 0, 2 * nr * sizeof(uint32_t), st));  // cert, comp_max
+        PCV_HIP(hipMemsetAsync(d_best.p, 0, nr * sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_best.p + nr, 0xff, nr * sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st));
+        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkRoots, 0, sizeof(unsigned long long), st));
+        job.record(0);
+        queue_bound(sample_stride);
+        if (sample_stride > 1) {
+            PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+            job.wait();
+            bound_repeated = counts[kLinkUnbounded] > 0 && counts[kLinkCertRoots] >= 2;
+            if (bound_repeated) queue_bound(1);
+        }
+        job.record(1);
+        // 2. the candidates
+        a.stride = 1;
+        const Listing list = list_candidates(
+            job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxLinkageCandidates,
+            [&] {
+                a.cand = d_cand.p;
+                a.cand_key = d_cand_key.p;
+                launch_reach_list(st, p, dp, ra);
+            },
+            [&] { PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st)); }, d_cand, d_cand_key);
+        const float round_bound_ms = job.elapsed(0), round_list_ms = list.ms + (list.repeated ? list.again_ms : 0.0f);
+        stats.bound_ms += round_bound_ms;
+        stats.list_ms += list.ms;
+        const uint64_t n_cand = counts[kLinkListed];
+        if (n_cand > kMaxLinkageCandidates)
+            PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                     "reach_tree: round %d lists %llu candidate pairs, more than %llu (2^28): too many rows are nearly the same reach from their "
+                     "nearest foreign row, or lie outside the lengths the screen is certified for; build the tree of fewer rows",
+                     (int)stats.rounds, (unsigned long long)n_cand, (unsigned long long)kMaxLinkageCandidates);
+        if (list.repeated) {  // (the pass lists the same pairs again)
+            PCV_REQUIRE(again[kLinkListed] == n_cand, "reach_tree: the repeated list pass left %llu candidates, the first %llu", again[kLinkListed],
+                        (unsigned long long)n_cand);
+            stats.reruns += 1;
+            stats.list_ms += list.again_ms;
+        }
+        stats.candidates += (int64_t)n_cand;
+        stats.rounds += 1;
+        // 3. the f64 decision, 4. the merge
+        a.n_cand = n_cand;
+        job.record(3);
+        launch_reach_rescore(st, p, dp, ra);
+        job.record(4);
+        launch_linkage_merge(st, p, a);
+        job.record(5);
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        job.wait();
+        stats.rescore_ms += job.elapsed(3);
+        stats.merge_ms += job.elapsed(4);
+        // 5. one edge per component that went, and at least every second one went
+        const uint64_t after = counts[kLinkRoots], now = counts[kLinkEmitted];
+        if (!(after >= 1 && after <= components / 2 && now - emitted == components - after))
+            PCV_FAIL(PCV_ERR_INTERNAL, "reach_tree: round %d went from %llu components to %llu and emitted %llu edges", (int)stats.rounds - 1,
+                     (unsigned long long)components, (unsigned long long)after, (unsigned long long)(now - emitted));
+        if (round_log)
+            std::fprintf(round_log, "%d %llu %llu %llu %d %d %.4f %.4f %.4f %.4f\n", (int)stats.rounds - 1, (unsigned long long)components,
+                         (unsigned long long)after, (unsigned long long)n_cand, bound_repeated ? 1 : 0, list.repeated ? 1 : 0, round_bound_ms, round_list_ms,
+                         job.elapsed(3), job.elapsed(4));
+        components = after;
+        emitted = now;
+    }
+    PCV_REQUIRE(emitted == (P > 0 ? P - 1 : 0), "reach_tree: %llu edges for %llu participating rows", (unsigned long long)emitted, (unsigned long long)P);
+    stats.edges = (int64_t)emitted;
+
+    a.n_edges = emitted;
+    d_out_edges.ensure((size_t)std::max<uint64_t>(1, emitted));
+    ra.out_edges = d_out_edges.p;
+    launch_reach_output(st, p, dp, ra);
+    job.wait();
+    std::vector<ReachEdge> edges((size_t)emitted);
+    if (emitted > 0) PCV_HIP(hipMemcpy(edges.data(), d_out_edges.p, (size_t)emitted * sizeof(ReachEdge), hipMemcpyDeviceToHost));
+    std::sort(edges.begin(), edges.end(), [](const ReachEdge& x, const ReachEdge& y) {
+        if (x.w != y.w) return x.w > y.w;
+        if (x.pos_a != y.pos_a) return x.pos_a < y.pos_a;
+        return x.pos_b < y.pos_b;
+    });
+    for (size_t i = 0; i < edges.size(); ++i) {
+        out_pos_a[i] = edges[i].pos_a;
+        out_pos_b[i] = edges[i].pos_b;
+        out_w[i] = edges[i].w;
+        if (out_c) out_c[i] = edges[i].c;
+        if (out_id_a) {
+            out_id_a[i] = edges[i].id_a;
+            out_id_b[i] = edges[i].id_b;
+        }
+    }
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (out_part) PCV_HIP(hipMemcpy(out_part, d_out_part.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
+    if (out_core) PCV_HIP(hipMemcpy(out_core, d_out_core.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost));
+    *out_edges = (int64_t)emitted;
+}
+
 // ---- seed items (pcv_searcher_seeds; DESIGN.md §4 "Seed items") ----
 // Prep, begin, then k picks with a cover step between them (seed_kernels.hip): 2k launches queued on the searcher's stream and one
 // wait behind the last.  Everything the call allocates is its own and is given back when it ends: nothing of the searcher's pass
@@ -1410,6 +1709,35 @@ pcv_status pcv_searcher_last_linkage_stats(pcv_searcher* s, pcv_linkage_stats* o
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_linkage_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->linkage_stats;
+    });
+}
+
+pcv_status pcv_searcher_reach_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int min_items, int64_t capacity, int64_t* out_ids,
+                                   int8_t* out_part, double* out_core, int64_t* out_pos_a, int64_t* out_pos_b, int64_t* out_id_a, int64_t* out_id_b,
+                                   double* out_w, double* out_c, int64_t* out_rows, int64_t* out_edges) {
+    return guarded([&] {
+        PCV_REQUIRE(out_rows != nullptr, "reach_tree: out_rows is NULL");
+        PCV_REQUIRE(min_items >= 1 && min_items <= (int)PCV_MAX_NEIGHBORS + 1, "reach_tree: min_items %d outside [1,%d]", min_items,
+                    (int)PCV_MAX_NEIGHBORS + 1);
+        PCV_REQUIRE(capacity >= 0, "reach_tree: capacity %lld is negative", (long long)capacity);
+        const bool all = out_pos_a != nullptr && out_pos_b != nullptr && out_w != nullptr && out_edges != nullptr;
+        const bool none = out_pos_a == nullptr && out_pos_b == nullptr && out_w == nullptr && out_c == nullptr && out_ids == nullptr &&
+                          out_part == nullptr && out_core == nullptr && out_id_a == nullptr && out_id_b == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "reach_tree: out_pos_a, out_pos_b, out_w or out_edges is NULL with capacity %lld",
+                    (long long)capacity);
+        PCV_REQUIRE((out_id_a == nullptr) == (out_id_b == nullptr), "reach_tree: one of out_id_a and out_id_b is NULL, the other is not");
+        PCV_REQUIRE(s != nullptr, "reach_tree: searcher is NULL");
+        const auto lk = enter(s, "reach_tree");
+        reach_tree(s, source_ids, n_sources, min_items, capacity, out_ids, out_part, out_core, out_pos_a, out_pos_b, out_id_a, out_id_b, out_w, out_c,
+                   out_rows, out_edges);
+    });
+}
+
+pcv_status pcv_searcher_last_reach_stats(pcv_searcher* s, pcv_reach_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_reach_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->reach_stats;
     });
 }
 

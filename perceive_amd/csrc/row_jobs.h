@@ -1,5 +1,5 @@
 // row_jobs.h — the calls that run kernels over the stored rows themselves, not over a scan's candidates (duplicate pairs, item labels,
-// neighbours, density clusters, the linkage tree, seeds, moments, projection): the arguments of their kernels and their launchers.
+// neighbours, density clusters, the linkage tree, the reach tree, seeds, moments, projection): the arguments of their kernels and their launchers.
 // The host side is row_jobs.cpp; a scan pass needs nothing of this file.
 #pragma once
 #include "scan.h"
@@ -312,6 +312,30 @@ enum : int {
     kLinkCounters
 };
 
+// Reach tree (pcv_searcher_reach_tree; DESIGN.md §4 "Reach tree"): the spanning tree under w(a, b) = min(core(a), core(b), c(a, b)),
+// in the linkage rounds with the cap applied.  `l` is the linkage call's block, read by the linkage kernels the rounds share (begin,
+// cert, threshold, merge) and by the kernels of reach_kernels.hip; there cand_key, best_key and edge_key hold images of w, not of c.
+//   core[launch row]     : the j-th largest c of the row with another participating row, f64; +inf for j == 0; NaN: no part
+//   klo, khi[launch row] : core rounded down and up to f32 (-inf for a row that takes no part); zero behind total_blocks * 32
+//   row_off, sorted_key  : what the neighbours' rescore step left (NeighborArgs), read by the core step alone;  k = j
+struct ReachEdge {
+    double w, c;
+    int64_t pos_a, pos_b;  // output positions, pos_a < pos_b
+    int64_t id_a, id_b;
+};
+struct ReachArgs {
+    LinkageArgs l;
+    double* core;                         // [total_blocks * 32]
+    float* klo;                           // [(total_blocks + tile_blocks) * 32]
+    float* khi;                           // [(total_blocks + tile_blocks) * 32]
+    const uint32_t* row_off;              // [total_blocks * 32 + 1]
+    const unsigned long long* sorted_key; // [candidates of the core step]
+    unsigned long long* short_rows;       // participating rows with fewer than k rescored partners (never, by the neighbours' proof)
+    double* out_core;                     // [rows]
+    ReachEdge* out_edges;                 // [n_edges]
+    int k;                                // j = min(min_items - 1, P - 1)
+};
+
 // ---- duplicate pairs (selfjoin_kernels.hip); `p` needs seg, nseg, total_blocks, D, D4 only ----
 float selfjoin_margin(int Dp);  // certified bound on |screening score - canonical cosine| (DESIGN.md §4 "Duplicate pairs")
 void launch_selfjoin_prep(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SelfJoinArgs& a);
@@ -344,6 +368,12 @@ void launch_linkage_list(hipStream_t st, const ScanParams& p, const ScanParams* 
 void launch_linkage_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);   // cand -> best_key, best_pair
 void launch_linkage_merge(hipStream_t st, const ScanParams& p, const LinkageArgs& a);                          // best_pair -> edges, parent, comp, roots
 void launch_linkage_output(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);    // edges, rinv -> outputs
+// ---- reach tree (reach_kernels.hip); the core step's candidates are the neighbours', the other steps of a round the linkage tree's ----
+void launch_reach_core(hipStream_t st, const ScanParams& p, const ReachArgs& a);                               // sorted_key -> core, klo, khi
+void launch_reach_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);         // comp, klo -> cert, comp_max
+void launch_reach_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);          // thr, comp, khi -> cand
+void launch_reach_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);       // cand, core -> best_key, best_pair
+void launch_reach_output(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);        // edges, rinv, core -> outputs
 // ---- seed items (seed_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
 void launch_seed_begin(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // cover = none, the partials of step 0
 void launch_seed_cover(hipStream_t st, const ScanParams& p, const ScanParams* dp, const SeedArgs& a);  // the last pick -> cover, the partials of a.step

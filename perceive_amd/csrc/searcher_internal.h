@@ -243,6 +243,7 @@ struct pcv_searcher {
     pcv_seed_stats seed_stats{};      // pcv_searcher_seeds (likewise)
     pcv_density_stats density_stats{};  // pcv_searcher_density_clusters (likewise)
     pcv_linkage_stats linkage_stats{};  // pcv_searcher_linkage_tree (likewise)
+    pcv_reach_stats reach_stats{};      // pcv_searcher_reach_tree (likewise)
     pcv_moment_stats moment_stats{};  // pcv_searcher_moments / _principal_axes (likewise)
     pcv_project_stats project_stats{};  // pcv_searcher_project (likewise)
     uint32_t scan_flags = 0;  // tuning knobs: PCV_SCAN_FLAGS at creation, pcv_searcher_set_tuning

@@ -713,6 +713,43 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_last_linkage_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.LinkageStats._fields_}
 
+    # ---- reach tree (pcv_searcher_reach_tree) -------------------------------------------------------
+    # The spanning tree under the mutual-reachability weight: what HDBSCAN starts from (linkage_select picks the clusters).
+    def reach_tree(self, sources, min_items):
+        """The spanning tree of the participating rows of `sources` under w(a, b) = min(core(a), core(b), c(a, b)), core(r) the
+        (min_items - 1)-th largest canonical cosine of r with another participating row (+inf for min_items = 1), edges ordered by
+        (w descending, lower position, higher position) -> (ids [n] int64, part [n] int8, core [n] float64: NaN where part == 0,
+        pos_a [e], pos_b [e], id_a [e], id_b [e] int64, w [e] float64, c [e] float64), e = participating rows - 1 (or 0).  With
+        min_items = 1 it is linkage_tree's output (w == c).  A view uses its own rows."""
+        src, nsrc, _keep = _source_filter(sources)
+        n = C.c_int64()
+        lib = _ffi.lib()
+        _ffi.check(
+            lib.pcv_searcher_reach_tree(self._handle, src, nsrc, int(min_items), 0, None, None, None, None, None, None, None, None, None, C.byref(n), None)
+        )
+        n = n.value
+        cap = max(n, 1)
+        ids = np.empty(cap, dtype=np.int64)
+        part = np.empty(cap, dtype=np.int8)
+        core = np.empty(cap, dtype=np.float64)
+        pos_a, pos_b, id_a, id_b = (np.empty(cap, dtype=np.int64) for _ in range(4))
+        w = np.empty(cap, dtype=np.float64)
+        c = np.empty(cap, dtype=np.float64)
+        got, edges = C.c_int64(), C.c_int64()
+        _ffi.check(
+            lib.pcv_searcher_reach_tree(
+                self._handle, src, nsrc, int(min_items), cap, _ffi.i64p(ids), _ffi.i8p(part), _ffi.f64p(core), _ffi.i64p(pos_a), _ffi.i64p(pos_b),
+                _ffi.i64p(id_a), _ffi.i64p(id_b), _ffi.f64p(w), _ffi.f64p(c), C.byref(got), C.byref(edges),
+            )
+        )
+        e = edges.value
+        return ids[:n], part[:n], core[:n], pos_a[:e], pos_b[:e], id_a[:e], id_b[:e], w[:e], c[:e]
+
+    def last_reach_stats(self):
+        st = _ffi.ReachStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_reach_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.ReachStats._fields_}
+
     # ---- seed items (pcv_searcher_seeds) ------------------------------------------------------------
     # k items that cover the corpus, picked one after the other on the device: the init of kmeans, or a representative sample.
     def seeds(self, sources, k, method="kmeans++", seed=0, first_id=None):
@@ -1082,6 +1119,36 @@ def linkage_cut(pos_a, pos_b, c, n_rows, part=None, threshold=-np.inf, min_clust
         )
     )
     return labels[:n_rows].copy(), clusters.value
+
+
+def linkage_select(pos_a, pos_b, w, n_rows, part=None, min_cluster_size=5, allow_single=False):
+    """Picks clusters from the tree of Searcher.reach_tree (or linkage_tree, with its c) without a threshold (host only): HDBSCAN's
+    condensed tree with min_cluster_size and excess-of-mass selection, the cosine itself as the density level -> (labels [n_rows]
+    int32: the selected clusters numbered by the lowest position of their rows, -1 for noise and where part == 0; stability [k]
+    float64; size [k] int64)."""
+    a = np.ascontiguousarray(pos_a, dtype=np.int64).reshape(-1)
+    b = np.ascontiguousarray(pos_b, dtype=np.int64).reshape(-1)
+    ww = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if not a.size == b.size == ww.size:
+        raise ValueError("pos_a, pos_b and w differ in length")
+    n_rows = int(n_rows)
+    pt = None if part is None else np.ascontiguousarray(part, dtype=np.int8).reshape(-1)
+    if pt is not None and pt.size != n_rows:
+        raise ValueError("part has not n_rows entries")
+    labels = np.empty(max(n_rows, 1), dtype=np.int32)
+    cap = max(n_rows // max(int(min_cluster_size), 1), 1)  # (selected clusters are disjoint and hold min_cluster_size rows, but for the root)
+    stability = np.empty(cap, dtype=np.float64)
+    size = np.empty(cap, dtype=np.int64)
+    clusters = C.c_int32()
+    _ffi.check(
+        _ffi.lib().pcv_linkage_select(
+            _ffi.i64p(a) if a.size else None, _ffi.i64p(b) if a.size else None, _ffi.f64p(ww) if a.size else None, a.size,
+            _ffi.i8p(pt) if pt is not None and pt.size else None, n_rows, int(min_cluster_size), 1 if allow_single else 0, _ffi.i32p(labels),
+            C.byref(clusters), _ffi.f64p(stability), _ffi.i64p(size), cap,
+        )
+    )
+    k = clusters.value
+    return labels[:n_rows].copy(), stability[:k].copy(), size[:k].copy()
 
 
 def seed_draw(seed, step, total):

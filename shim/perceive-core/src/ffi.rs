@@ -127,6 +127,26 @@ pub struct pcv_linkage_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_reach_stats {
+    pub rows: i64,
+    pub participating: i64,
+    pub edges: i64,
+    pub core_candidates: i64,
+    pub candidates: i64,
+    pub rounds: i32,
+    pub tile_rows: i32,
+    pub reruns: i32,
+    pub min_items: i32,
+    pub core_ms: f32,
+    pub prep_ms: f32,
+    pub bound_ms: f32,
+    pub list_ms: f32,
+    pub rescore_ms: f32,
+    pub merge_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_seed_stats {
     pub rows: i64,
     pub participating: i64,
@@ -345,6 +365,9 @@ extern "C" {
     pub fn pcv_searcher_linkage_tree(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, capacity: i64, out_ids: *mut i64, out_part: *mut int8_t, out_pos_a: *mut i64, out_pos_b: *mut i64, out_id_a: *mut i64, out_id_b: *mut i64, out_c: *mut f64, out_rows: *mut i64, out_edges: *mut i64) -> c_int;
     pub fn pcv_searcher_last_linkage_stats(s: *mut pcv_searcher, out: *mut pcv_linkage_stats) -> c_int;
     pub fn pcv_linkage_cut(pos_a: *const i64, pos_b: *const i64, c: *const f64, n_edges: i64, part: *const int8_t, n_rows: i64, threshold: f64, min_clusters: i64, out_label: *mut i32, out_clusters: *mut i32) -> c_int;
+    pub fn pcv_searcher_reach_tree(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, min_items: c_int, capacity: i64, out_ids: *mut i64, out_part: *mut int8_t, out_core: *mut f64, out_pos_a: *mut i64, out_pos_b: *mut i64, out_id_a: *mut i64, out_id_b: *mut i64, out_w: *mut f64, out_c: *mut f64, out_rows: *mut i64, out_edges: *mut i64) -> c_int;
+    pub fn pcv_searcher_last_reach_stats(s: *mut pcv_searcher, out: *mut pcv_reach_stats) -> c_int;
+    pub fn pcv_linkage_select(pos_a: *const i64, pos_b: *const i64, w: *const f64, n_edges: i64, part: *const int8_t, n_rows: i64, min_cluster_size: i64, allow_single: c_int, out_label: *mut i32, out_clusters: *mut i32, out_stability: *mut f64, out_size: *mut i64, cluster_capacity: i64) -> c_int;
     pub fn pcv_searcher_seeds(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, method: c_int, seed: u64, first_id: *const i64, out_ids: *mut i64, out_positions: *mut i64, out_totals: *mut i64, out_cover: *mut f32, out_count: *mut i32) -> c_int;
     pub fn pcv_searcher_last_seed_stats(s: *mut pcv_searcher, out: *mut pcv_seed_stats) -> c_int;
     pub fn pcv_seed_draw(seed: u64, step: c_int, total: u64, out_t: *mut u64) -> c_int;

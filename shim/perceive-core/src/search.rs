@@ -717,6 +717,73 @@ impl Searcher {
         )
     }
 
+    /// Reach tree (`pcv_searcher_reach_tree`): the spanning tree of the items of `sources` under the mutual-reachability weight
+    /// w = min(core(a), core(b), cosine), core = the (min_items - 1)-th largest cosine of an item with another (min_items is clamped
+    /// to 1 ..= PCV_MAX_NEIGHBORS + 1), edges ordered by (w descending, lower position, higher position): what HDBSCAN starts from.
+    /// Returns ((item id, takes part, core) per item by global position, (position a, position b, w) per edge, a < b).
+    /// `linkage_select` picks the clusters, `linkage_cut` cuts it at a threshold.
+    pub fn reach_tree(&self, sources: &[i64], min_items: usize) -> (Vec<(i64, bool, f64)>, Vec<(i64, i64, f64)>) {
+        if self.handle.is_null() || sources.is_empty() {
+            return (Vec::new(), Vec::new());
+        }
+        let min_items = min_items.clamp(1, ffi::PCV_MAX_NEIGHBORS as usize + 1) as i32;
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_reach_tree(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                min_items,
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                &mut n,
+                std::ptr::null_mut(),
+            )
+        })
+        .expect("reach_tree failed");
+        let room = n.max(1) as usize;
+        let mut ids = vec![-1i64; room];
+        let mut part = vec![0i8; room];
+        let mut core = vec![f64::NAN; room];
+        let mut pos_a = vec![-1i64; room];
+        let mut pos_b = vec![-1i64; room];
+        let mut w = vec![f64::NAN; room];
+        let mut edges: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_reach_tree(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                min_items,
+                room as i64,
+                ids.as_mut_ptr(),
+                part.as_mut_ptr(),
+                core.as_mut_ptr(),
+                pos_a.as_mut_ptr(),
+                pos_b.as_mut_ptr(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                w.as_mut_ptr(),
+                std::ptr::null_mut(),
+                &mut n,
+                &mut edges,
+            )
+        })
+        .expect("reach_tree failed");
+        (
+            (0..n as usize).map(|i| (ids[i], part[i] != 0, core[i])).collect(),
+            (0..edges as usize).map(|i| (pos_a[i], pos_b[i], w[i])).collect(),
+        )
+    }
+
     /// Seed items (`pcv_searcher_seeds`): up to `k` items (clamped to PCV_MAX_SEEDS) that cover `sources`, in the order they were
     /// picked — `kmeanspp`: the k-means++ draw of `seed`, else farthest first; `first_id`: the item step 0 picks instead.
     /// Returns (item id, global position, potential before the pick in units of 2^-32, largest cosine with the seeds before it:
@@ -1026,4 +1093,39 @@ pub fn linkage_cut(items: &[(i64, bool)], edges: &[(i64, i64, f64)], threshold: 
     .expect("linkage_cut failed");
     labels.truncate(items.len());
     (labels, clusters as usize)
+}
+
+/// Picks clusters from the tree of `Searcher::reach_tree` or `linkage_tree` without a threshold (`pcv_linkage_select`, host only):
+/// HDBSCAN's condensed tree with `min_cluster_size` (at least 2) and excess-of-mass selection.  `part`: takes part, per item.
+/// Returns (cluster per item, numbered by lowest position, -1: noise or no part; (stability, items) per cluster).
+pub fn linkage_select(part: &[bool], edges: &[(i64, i64, f64)], min_cluster_size: usize, allow_single: bool) -> (Vec<i32>, Vec<(f64, i64)>) {
+    let part8: Vec<i8> = part.iter().map(|&x| x as i8).collect();
+    let pos_a: Vec<i64> = edges.iter().map(|e| e.0).collect();
+    let pos_b: Vec<i64> = edges.iter().map(|e| e.1).collect();
+    let w: Vec<f64> = edges.iter().map(|e| e.2).collect();
+    let mut labels = vec![-1i32; part.len().max(1)];
+    let room = (part.len() / min_cluster_size.max(2)).max(1);
+    let mut stability = vec![0f64; room];
+    let mut size = vec![0i64; room];
+    let mut clusters: i32 = 0;
+    hip::check(unsafe {
+        ffi::pcv_linkage_select(
+            pos_a.as_ptr(),
+            pos_b.as_ptr(),
+            w.as_ptr(),
+            edges.len() as i64,
+            part8.as_ptr(),
+            part.len() as i64,
+            min_cluster_size.max(2) as i64,
+            allow_single as i32,
+            labels.as_mut_ptr(),
+            &mut clusters,
+            stability.as_mut_ptr(),
+            size.as_mut_ptr(),
+            room as i64,
+        )
+    })
+    .expect("linkage_select failed");
+    labels.truncate(part.len());
+    (labels, (0..clusters as usize).map(|k| (stability[k], size[k])).collect())
 }

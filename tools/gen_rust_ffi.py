@@ -21,6 +21,7 @@ SCALARS = {
     "pcv_assign_stats": "pcv_assign_stats", "pcv_neighbor_stats": "pcv_neighbor_stats", "pcv_group_stats": "pcv_group_stats",
     "pcv_seed_stats": "pcv_seed_stats", "pcv_moment_stats": "pcv_moment_stats", "pcv_project_stats": "pcv_project_stats",
     "pcv_density_stats": "pcv_density_stats", "pcv_linkage_stats": "pcv_linkage_stats",
+    "pcv_reach_stats": "pcv_reach_stats",
     "int8_t": "int8_t",  # (an alias of i8 declared in the file: tests/test_rust_shim.py compares this one type by its C name)
 }
 
