@@ -6,7 +6,7 @@
 //            it gives the rows' (launch_selfjoin_prep, called twice); assign_labels_kernel then writes each label's screening
 //            constants (w, mg: scan.h, AssignArgs) and its bf16 pieces in the swizzled order of the LDS tile.
 //   screen   assign_screen_kernel: a workgroup stages one label tile in LDS and its waves stream row blocks out of the blocked f32
-//            layout as the A fragment of v_mfma_f32_32x32x16_bf16 (the streaming discipline of selfjoin_screen_kernel).  Per block the
+//            layout as the A fragment of v_mfma_f32_32x32x16_bf16 (pair_stream of pair_screen.h: DESIGN.md §4 "The row-pair screen").  Per block the
 //            epilogue reduces s - mg over the tile's labels for each of the 32 rows, joins it with the bound the earlier tiles left
 //            (lb) and lists every (row, label) with s + mg >= that bound.
 //   rescore  assign_rescore_kernel: the canonical f64 score of every candidate that passes the FINAL bound (pair_sums, finish_score:
@@ -16,16 +16,12 @@
 //   sums     label_sums_kernel: S[label][d] += rint(x[r][d] * rinv_r * 2^32) in int64 — associative, so any order gives the same bits.
 #include "device_access.h"
 #include "launch_rows.h"
+#include "pair_screen.h"
 #include "row_jobs.h"
 
 namespace pcv {
 namespace {
 
-constexpr int kAssignWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
-
-__device__ __forceinline__ unsigned long long g_atomic_max64(unsigned long long* p, unsigned long long v) {
-    return __hip_atomic_fetch_max((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ uint32_t g_atomic_min(uint32_t* p, uint32_t v) {
     return __hip_atomic_fetch_min((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -74,78 +70,28 @@ __global__ __launch_bounds__(256) void assign_begin_kernel(const ScanParams* __r
     }
 }
 
-// grid: x = span of row blocks [x * span_blocks, + span_blocks), cut at the launch's end; wave w of the workgroup takes the blocks
-// first + w, first + w + kAssignWaves, ...  The label tile is a.tile.
-// D[row of the streamed block][label of the tile]: lane (c = lane & 31, h = lane >> 5) holds labels 32 t + c of the tile and, in
-// accumulator i, block row (i & 3) + 8 (i >> 2) + 4 h — the reduction over the labels of a row is over t in the lane and over the 32
-// lanes of a half.
+// The epilogue of the label screen.  The tile holds labels, not launch rows: l0 is its first label, w and mg the screening constants of
+// the lane's labels 32 t + c, lbv the carried bound of the streamed block's rows beside rb.  ra is not used.
 template <int NT>
-__global__ __launch_bounds__(kAssignWaves * 64) void assign_screen_kernel(const ScanParams* __restrict__ pp, const AssignArgs a) {
-    const ScanParams& p = *pp;
-    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
-    const int D4 = p.D4, P8 = D4 >> 1, NCH = D4 >> 4;
-    const uint32_t TB = p.total_blocks;
-    const uint64_t first = (uint64_t)blockIdx.x * a.span_blocks;
-    if (first >= TB) return;  // (the whole workgroup)
-    const uint32_t b0 = (uint32_t)first;
-    const uint32_t b1 = (uint32_t)min((uint64_t)TB, first + a.span_blocks);
-
-    {
-        const u32x4* src = (const u32x4*)(a.lab_tile + (size_t)a.tile * NT * 32 * P8);
-        for (int i = threadIdx.x; i < NT * 32 * P8; i += kAssignWaves * 64) lq[i] = __builtin_bit_cast(uint4, *(const PCV_GLOBAL u32x4*)(src + i));
-    }
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = uniform(threadIdx.x >> 6);
-    const int c = lane & 31, h = lane >> 5;
-    if (b0 + wave >= b1) return;
-    const uint32_t l0 = a.tile * NT * 32;
+struct AssignPolicy {
+    const AssignArgs& a;
+    uint32_t l0;
     float w[NT], mg[NT];
+    f32x4 lbv[4];
+    __device__ __forceinline__ void begin(uint32_t, int c) {
+        l0 = a.tile * NT * 32;
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        w[t] = gld(&a.w[l0 + 32 * t + c]);
-        mg[t] = gld(&a.mg[l0 + 32 * t + c]);
+        for (int t = 0; t < NT; ++t) {
+            w[t] = gld(&a.w[l0 + 32 * t + c]);
+            mg[t] = gld(&a.mg[l0 + 32 * t + c]);
+        }
     }
-
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-
-    auto enter_block = [&](JoinCursor& k, uint32_t gb) {
-        k.gb = gb;
-        k.ch = 0;
-        if (gb < b1) {
-            join_seek(p, k.sc, gb);
-            k.rows = row_rsrc(k.sc.blk + (size_t)(gb - k.sc.begin) * D4 * 32, (uint32_t)D4 * 512u);
-        }
-    };
-    const uint32_t lane_off = (uint32_t)(h * 64 + c) * 16u;  // the lane's bytes inside a block
-    JoinCursor cons, prod;
-    enter_block(cons, b0 + wave);
-    prod = cons;
-
-    float4 buf[2][8];
-    // (always issues its loads: past the end of the wave's stream they read a chunk of its last block again — scan_mfma_kernel)
-    auto produce = [&](float4 (&b)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
-        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + kAssignWaves);
-    };
-
-    f32x4 rb[4], lbv[4];  // rinv and the carried bound of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
-    auto rb_prefetch = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            rb[j] = *(const PCV_GLOBAL f32x4*)(a.rinv + (size_t)cons.gb * 32 + 8 * j + 4 * h);
-            lbv[j] = *(const PCV_GLOBAL f32x4*)(a.lb + (size_t)cons.gb * 32 + 8 * j + 4 * h);
-        }
-    };
-
-    auto epilogue = [&]() {
-        if (NCH < 2) rb_prefetch();
+    __device__ __forceinline__ void prefetch(uint32_t gb, int h, int j) {
+        lbv[j] = *(const PCV_GLOBAL f32x4*)(a.lb + (size_t)gb * 32 + 8 * j + 4 * h);
+    }
+    __device__ __forceinline__ void end(const float (&)[NT], int, int) {}
+    __device__ __forceinline__ void block(const f32x16 (&acc)[NT], const float (&)[NT], const f32x4 (&rb)[4], const PairWhere& at) {
+        const int c = at.c, h = at.h;
         // the row's bound: the largest certified lower end s - mg over the tile's labels, joined with what earlier tiles left
         float lo[16];
 #pragma unroll
@@ -169,7 +115,7 @@ __global__ __launch_bounds__(kAssignWaves * 64) void assign_screen_kernel(const 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const f32x4 v = {lo[4 * j], lo[4 * j + 1], lo[4 * j + 2], lo[4 * j + 3]};
-                *(PCV_GLOBAL f32x4*)(a.lb + (size_t)cons.gb * 32 + 8 * j + 4 * h) = v;
+                *(PCV_GLOBAL f32x4*)(a.lb + (size_t)at.gb * 32 + 8 * j + 4 * h) = v;
             }
         }
         // a wild row or label: every defined pair (scan.h); otherwise the certified upper end against the bound
@@ -189,61 +135,51 @@ __global__ __launch_bounds__(kAssignWaves * 64) void assign_screen_kernel(const 
             n += (uint32_t)__builtin_popcount(mask[t]);
         }
         if (n) {
-            unsigned long long at = g_atomic_add64(&a.counters[0], n);
+            unsigned long long k = g_atomic_add64(&a.counters[0], n);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     if (mask[t] & (1u << i)) {
-                        if (at < a.cand_cap) {
+                        if (k < a.cand_cap) {
                             const float rbi = rb[i >> 2][i & 3];
                             const float s = (rbi < 0.0f || w[t] < 0.0f) ? __builtin_inff() : acc[t][i] * rbi * w[t];
-                            gst(&a.cand[at], ((uint64_t)(cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h)) << 32) | (l0 + 32u * t + (uint32_t)c));
-                            gst(&a.cand_s[at], s);
+                            gst(&a.cand[k], ((uint64_t)at.partner_row(i) << 32) | (l0 + 32u * t + (uint32_t)c));
+                            gst(&a.cand_s[k], s);
                         }
-                        ++at;
+                        ++k;
                     }
                 }
             }
         }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    };
-
-    auto consume = [&](const float4 (&b)[8]) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const f32x8 v = {b[2 * ks].x, b[2 * ks].y, b[2 * ks].z, b[2 * ks].w, b[2 * ks + 1].x, b[2 * ks + 1].y, b[2 * ks + 1].z, b[2 * ks + 1].w};
-            const bf16x8 av = __builtin_convertvector(v, bf16x8);
-            const int pc = 2 * (cons.ch * 4 + ks) + h;
-            const int ph = swizzle_piece(pc, c, P8);  // (tile label 32 t + c: the same low four bits as c)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const bf16x8 q8 = *(const bf16x8*)&lq[(32 * t + c) * P8 + ph];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q8, acc[t], 0, 0, 0);
-            }
-        }
-        if (++cons.ch == NCH) {
-            epilogue();
-            enter_block(cons, cons.gb + kAssignWaves);
-        }
-    };
-
-    // one chunk of loads in flight while one feeds the matrix cores (every buf[] index a literal, or the array moves to scratch);
-    // the block's rinv and bound are requested one chunk ahead of the epilogue and before that step's row loads
-#define PCV_ASSIGN_STEP(REFILL, CONS)                    \
-    if (NCH >= 2 && cons.ch == NCH - 2) rb_prefetch();   \
-    produce(buf[REFILL]);                                \
-    consume(buf[CONS]);                                  \
-    if (cons.gb >= b1) return;
-    produce(buf[0]);
-    while (true) {
-        PCV_ASSIGN_STEP(1, 0)
-        PCV_ASSIGN_STEP(0, 1)
     }
-#undef PCV_ASSIGN_STEP
+};
+
+// grid: x = span of row blocks [x * span_blocks, + span_blocks), cut at the launch's end; wave w of the workgroup takes the blocks
+// first + w, first + w + kScreenWaves, ...  The label tile is a.tile, already in the swizzled bf16 order of the LDS tile (lab_tile).
+// D[row of the streamed block][label of the tile] (pair_screen.h, with labels where it has tile rows) — the reduction over the labels
+// of a row is over t in the lane and over the 32 lanes of a half.
+template <int NT>
+__global__ __launch_bounds__(kScreenWaves * 64) void assign_screen_kernel(const ScanParams* __restrict__ pp, const AssignArgs a) {
+    const ScanParams& p = *pp;
+    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
+    const int P8 = p.D4 >> 1;
+    const uint32_t TB = p.total_blocks;
+    const uint64_t first = (uint64_t)blockIdx.x * a.span_blocks;
+    if (first >= TB) return;  // (the whole workgroup)
+    const uint32_t b0 = (uint32_t)first;
+    const uint32_t b1 = (uint32_t)min((uint64_t)TB, first + a.span_blocks);
+
+    {
+        const u32x4* src = (const u32x4*)(a.lab_tile + (size_t)a.tile * NT * 32 * P8);
+        for (int i = threadIdx.x; i < NT * 32 * P8; i += kScreenWaves * 64) lq[i] = __builtin_bit_cast(uint4, *(const PCV_GLOBAL u32x4*)(src + i));
+    }
+    __syncthreads();
+
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    if (b0 + wave >= b1) return;
+    AssignPolicy<NT> pol{a};
+    pair_stream<NT, false>(p, lq, a.rinv, 0, b0 + wave, b1, kScreenWaves, pol);
 }
 
 // one thread per candidate: its canonical score if it passes the final bound, and the row's running maximum
@@ -295,10 +231,9 @@ __global__ __launch_bounds__(256) void assign_finish_kernel(const ScanParams* __
             g_atomic_add_i64(&a.out_counts[label], 1ll);
         }
         const int64_t o = gld(&a.seg_out0[r.sg - p.seg]) + (int64_t)r.row;
-        const int64_t* ids = gld(&r.sg->ids);
         gst(&a.out_label[o], label);
         gst(&a.out_score[o], score);
-        gst(&a.out_ids[o], ids ? gld(&ids[r.row]) : gld(&r.sg->id0) + (int64_t)r.row);
+        gst(&a.out_ids[o], row_id(r));
     }
     const unsigned long long moved = __ballot(gld(&a.row_label[i]) != label);  // (row_label starts at -1)
     if ((threadIdx.x & 63) == (unsigned)__builtin_ctzll(moved | (1ull << 63)) && moved) g_atomic_add64(&a.counters[1], (unsigned long long)__builtin_popcountll(moved));
@@ -378,7 +313,7 @@ void launch_assign_screen(hipStream_t st, const ScanParams& p, const ScanParams*
     const unsigned grid = (p.total_blocks + a.span_blocks - 1) / a.span_blocks;
 #define PCV_ASSIGN(N)                                                    \
     allow_dynamic_lds((const void*)assign_screen_kernel<N>, lds);        \
-    assign_screen_kernel<N><<<grid, kAssignWaves * 64, lds, st>>>(dp, a);
+    assign_screen_kernel<N><<<grid, kScreenWaves * 64, lds, st>>>(dp, a);
     if (NT == 4) {
         PCV_ASSIGN(4)
     } else if (NT == 2) {

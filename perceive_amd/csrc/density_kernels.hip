@@ -2,8 +2,8 @@
 // canonical cosine, exact, computed where the rows live.  The row prep (norms, rinv, the wild marking) is selfjoin_prep_kernel
 // (launch_selfjoin_prep); then
 //
-//   1. density_screen_kernel<NT, false>  the degree pass: the tile-in-LDS, stream-the-blocks bf16 screen of selfjoin_screen_kernel (a
-//                                        second copy of its staging and MFMA loop: that kernel's code object must not move) with a
+//   1. density_screen_kernel<NT, false>  the degree pass: the tile-in-LDS, stream-the-blocks bf16 screen of selfjoin_screen_kernel (its
+//                                        own copy of the staging and MFMA loop of pair_screen.h: see the kernel) with a
 //                                        three-way epilogue.  s >= hi with both rows certified: a SURE pair, near whatever the f64
 //                                        arithmetic would say — both rows' degrees go up and the pair is never listed.  lo <= s < hi,
 //                                        or a wild row: a BAND pair, appended to one device list (overflow counted, one rerun by the
@@ -21,58 +21,22 @@
 //                                        labels, kinds, degrees, ids and the counters.
 #include "device_access.h"
 #include "launch_rows.h"
+#include "pair_screen.h"
 #include "row_jobs.h"
 
 namespace pcv {
 namespace {
 
-constexpr int kDensityWaves = 8;  // waves of a screen workgroup (selfjoin_kernels.hip, kJoinWaves)
 constexpr uint32_t kNoRow = 0xffffffffu;
 
 __device__ __forceinline__ uint32_t g_atomic_min32(uint32_t* p, uint32_t v) {
     return __hip_atomic_fetch_min((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The root of x: parents are read with agent-scope atomic loads (other workgroups hook roots while this one walks).  parent[r] <= r
-// for every r at every time, so the walk visits strictly descending rows and ends.  A stale answer — a row that was a root when it
-// was read and is hooked by now — is caught by the compare-and-swap of the caller.
-__device__ __forceinline__ uint32_t density_find(const uint32_t* parent, uint32_t x) {
-    while (true) {
-        const uint32_t q = ld_relaxed(&parent[x]);
-        if (q == x) return x;
-        x = q;
-    }
-}
-
-// Lock-free union of the components of a and b: find both roots, hook the larger under the smaller with a compare-and-swap on
-// parent[larger] that expects it to still be a root; if it is not, go on from the value the CAS returned (its new parent, a lower
-// row).  No path compression, no plain store to `parent` while this kernel runs.
-// Termination: nothing here waits for a store of another wave.  A parent is only ever replaced by a lower row (a root r gets
-// parent[r] < r, and a hooked row is never written again), so every find ends after at most r steps; and a CAS fails only because
-// another CAS succeeded on that row, of which there are fewer than the number of core rows in the whole launch.  Every loop
-// therefore ends by its own CAS succeeding or by finding equal roots, whatever the other waves do — also if they stop.
-// The result is the partition into connected components whatever the order: a successful CAS merges exactly the two components
-// whose roots it saw, and the loop does not return before a and b have one root.
-__device__ __forceinline__ void density_union(uint32_t* parent, uint32_t a, uint32_t b) {
-    while (true) {
-        a = density_find(parent, a);
-        b = density_find(parent, b);
-        if (a == b) return;
-        if (a > b) {
-            const uint32_t t = a;
-            a = b;
-            b = t;
-        }
-        const uint32_t found = g_atomic_cas(&parent[b], b, a);
-        if (found == b) return;
-        b = found;
-    }
-}
-
 // what a near pair of launch rows (la, lb) does to the forest: both core: one component; one core: it may be the other's cluster
 __device__ __forceinline__ void density_link_pair(const DensityArgs& a, uint32_t la, uint32_t lb, bool core_a, bool core_b) {
     if (core_a && core_b)
-        density_union(a.parent, la, lb);
+        row_union(a.parent, la, lb);
     else if (core_a)
         (void)g_atomic_min32(&a.attach[lb], la);
     else if (core_b)
@@ -82,8 +46,13 @@ __device__ __forceinline__ void density_link_pair(const DensityArgs& a, uint32_t
 // grid, tile, stream and accumulator layout: selfjoin_screen_kernel.  D[row of the streamed block][row of the tile]: lane
 // (c = lane & 31, h = lane >> 5) holds tile rows 32 t + c and, in accumulator i, block row (i & 3) + 8 (i >> 2) + 4 h.
 // LINK = false: the degree pass (degrees, sure-pair count, band list).  LINK = true: the link pass (sure pairs only -> parent, attach).
+// The one screen that is NOT on the skeleton of pair_screen.h (DESIGN.md §4 "The row-pair screen"): ported to it (a DensityPolicy
+// with dega, cam and wave_sure as members), no form had scratch and the registers fell (225 / 160 / 139 -> 223 / 157 / 135 and
+// 221 / 166 / 147 -> 220 / 152 / 129), but at a million rows the degree pass took 1339 ms against 1284 (4.1 % slower) and the link
+// pass 1128 against 1112 (1.5 %), outside the 0.5 % the old build's repeats span.  A fix to the stream in pair_screen.h has to be
+// made here too.
 template <int NT, bool LINK>
-__global__ __launch_bounds__(kDensityWaves * 64) void density_screen_kernel(const ScanParams* __restrict__ pp, const DensityArgs a) {
+__global__ __launch_bounds__(kScreenWaves * 64) void density_screen_kernel(const ScanParams* __restrict__ pp, const DensityArgs a) {
     const ScanParams& p = *pp;
     extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
     __shared__ const float4* tbase[NT];
@@ -105,7 +74,7 @@ __global__ __launch_bounds__(kDensityWaves * 64) void density_screen_kernel(cons
         tbase[threadIdx.x] = base;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < NT * 32 * P8; i += kDensityWaves * 64) {
+    for (int i = threadIdx.x; i < NT * 32 * P8; i += kScreenWaves * 64) {
         const int r = i & 31, rest = i >> 5;
         const int tb = rest / P8, pc = rest - tb * P8;
         const float4* base = tbase[tb];
@@ -163,7 +132,7 @@ __global__ __launch_bounds__(kDensityWaves * 64) void density_screen_kernel(cons
     auto produce = [&](float4 (&b)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
-        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + kDensityWaves);
+        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + kScreenWaves);
     };
 
     f32x4 rb[4];  // rinv of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
@@ -277,7 +246,7 @@ __global__ __launch_bounds__(kDensityWaves * 64) void density_screen_kernel(cons
         }
         if (++cons.ch == NCH) {
             epilogue();
-            enter_block(cons, cons.gb + kDensityWaves);
+            enter_block(cons, cons.gb + kScreenWaves);
         }
     };
 
@@ -400,8 +369,7 @@ __global__ __launch_bounds__(256) void density_output_kernel(const ScanParams* _
             gst(&a.out_label[o], root != kNoRow ? (int32_t)gld(&a.rank[root]) : (int32_t)-1);
             gst(&a.out_kind[o], (int8_t)kind);
             gst(&a.out_degree[o], part ? (int32_t)gld(&a.degree[i]) : (int32_t)0);
-            const int64_t* ids = gld(&r.sg->ids);
-            gst(&a.out_ids[o], ids ? gld(&ids[r.row]) : gld(&r.sg->id0) + (int64_t)r.row);
+            gst(&a.out_ids[o], row_id(r));
         }
     }
     // (no early return above: the whole wave votes)
@@ -429,7 +397,7 @@ void launch_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, co
     const dim3 grid(tiles, spans);
 #define PCV_DENSITY(N)                                                          \
     allow_dynamic_lds((const void*)density_screen_kernel<N, LINK>, lds);        \
-    density_screen_kernel<N, LINK><<<grid, kDensityWaves * 64, lds, st>>>(dp, a);
+    density_screen_kernel<N, LINK><<<grid, kScreenWaves * 64, lds, st>>>(dp, a);
     if (NT == 4) {
         PCV_DENSITY(4)
     } else if (NT == 2) {

@@ -2,8 +2,8 @@
 // the participating rows, i.e. their maximum spanning tree under the canonical f64 cosine with a strict total order of the edges,
 // exact, computed where the rows live, in Borůvka rounds.  The norms come from selfjoin_prep_kernel (launch_selfjoin_prep); a round is
 //
-//   1. linkage_screen_kernel<NT, false>   the bound pass: the tile-in-LDS, stream-the-blocks screen of neighbors_screen_kernel (a
-//                                         further copy of its staging and MFMA loop: that kernel's code object must not move) over
+//   1. linkage_screen_kernel<NT, false>   the bound pass: the tile-in-LDS, stream-the-blocks screen of pair_screen.h (DESIGN.md §4
+//                                         "The row-pair screen") on the grid of neighbors_screen_kernel, over
 //                                         every stride-th partner block.  Per tile row it keeps the largest certified screening score
 //                                         s = acc * rinv_a * rinv_b with a certified partner of ANOTHER component and publishes it
 //                                         with an atomic max into comp_max[comp of the row] when the wave's stream ends.
@@ -20,250 +20,128 @@
 //                                         row) into best_pair.  Max and min commute: nothing depends on the order of arrival.
 //   4. linkage_merge_kernel               one thread per component with a choice: the edge is emitted unless the component at its
 //                                         other end chose the same pair and has the lower root; then the lock-free union of
-//                                         density_kernels.hip.
+//                                         launch_rows.h.
 //      linkage_flatten_kernel, _settle    comp = find(row), the count of the components, parent = comp.
 // and linkage_rows_kernel / linkage_edges_kernel write the outputs by position when one component is left.
+// The reach tree (reach_kernels.hip) runs the same rounds with the cap applied: the screen's third template flag, and the cert and
+// choose steps as they are.
 #include "device_access.h"
 #include "launch_rows.h"
+#include "pair_screen.h"
 #include "row_jobs.h"
 
 namespace pcv {
 namespace {
 
-constexpr int kLinkWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
 constexpr unsigned long long kNoPair = ~0ull;
 
-__device__ __forceinline__ void g_atomic_max64(unsigned long long* p, unsigned long long v) {
-    (void)__hip_atomic_fetch_max((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void g_atomic_min64(unsigned long long* p, unsigned long long v) {
-    (void)__hip_atomic_fetch_min((PCV_GLOBAL unsigned long long*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// density_find / density_union (density_kernels.hip), word for word: parent[r] <= r at every time, a root is hooked under a lower
-// root by a compare-and-swap that expects it to still be a root, nobody waits for anybody, no plain store while the kernel runs.
-__device__ __forceinline__ uint32_t linkage_find(const uint32_t* parent, uint32_t x) {
-    while (true) {
-        const uint32_t q = ld_relaxed(&parent[x]);
-        if (q == x) return x;
-        x = q;
-    }
-}
-__device__ __forceinline__ void linkage_union(uint32_t* parent, uint32_t a, uint32_t b) {
-    while (true) {
-        a = linkage_find(parent, a);
-        b = linkage_find(parent, b);
-        if (a == b) return;
-        if (a > b) {
-            const uint32_t t = a;
-            a = b;
-            b = t;
-        }
-        const uint32_t found = g_atomic_cas(&parent[b], b, a);
-        if (found == b) return;
-        b = found;
-    }
-}
-
-// grid, tile, stream and accumulator layout: neighbors_screen_kernel.  x = tile (NT consecutive blocks: the owners), y = walk: the
-// sampled blocks [y * walk_len, + walk_len) of the launch, cut at its end; sampled block j is launch block j * stride.  Wave w takes
-// the sampled blocks first + w, first + w + kLinkWaves, ...  D[row of the streamed block][row of the tile]: lane (c = lane & 31,
-// h = lane >> 5) holds tile rows 32 t + c and, in accumulator i, block row (i & 3) + 8 (i >> 2) + 4 h.
-template <int NT, bool LIST>
-__global__ __launch_bounds__(kLinkWaves * 64) void linkage_screen_kernel(const ScanParams* __restrict__ pp, const LinkageArgs a) {
-    const ScanParams& p = *pp;
-    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
-    __shared__ const float4* tbase[NT];
-    const int D4 = p.D4, P8 = D4 >> 1, NCH = D4 >> 4;
-    const uint32_t TB = p.total_blocks;
-    const uint32_t tb0 = blockIdx.x * NT;
-    const uint32_t step = kLinkWaves * a.stride;  // launch blocks between two blocks of a wave
-    const uint32_t SB = (TB + a.stride - 1) / a.stride;
-    const uint64_t first = (uint64_t)blockIdx.y * a.walk_len;
-    if (first >= SB) return;  // (the whole workgroup)
-    const uint32_t b0 = (uint32_t)first * a.stride;
-    const uint32_t b1 = (uint32_t)min((uint64_t)SB, first + a.walk_len) * a.stride;  // every sampled block below it is below TB
-
-    if (threadIdx.x < NT) {
-        const uint32_t gb = tb0 + threadIdx.x;
-        const float4* base = nullptr;
-        if (gb < TB) {
-            const SegDesc& sg = p.seg[find_seg(p, gb)];
-            base = gld(&sg.blk) + (size_t)(gb - gld(&sg.blk0)) * D4 * 32;
-        }
-        tbase[threadIdx.x] = base;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NT * 32 * P8; i += kLinkWaves * 64) {
-        const int r = i & 31, rest = i >> 5;
-        const int tb = rest / P8, pc = rest - tb * P8;
-        const float4* base = tbase[tb];
-        bf16x8 v8 = {};
-        if (base) {
-            const float4 lo = gld4(base + (size_t)(2 * pc) * 32 + r), hi = gld4(base + (size_t)(2 * pc + 1) * 32 + r);
-            const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            v8 = __builtin_convertvector(v, bf16x8);
-        }
-        const int row = tb * 32 + r;
-        lq[row * P8 + swizzle_piece(pc, row, P8)] = __builtin_bit_cast(uint4, v8);
-    }
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = uniform(threadIdx.x >> 6);
-    const int c = lane & 31, h = lane >> 5;
-    if (b0 + wave * a.stride >= b1) return;  // (no workgroup barrier behind this point)
-    // ra: rinv of the lane's tile rows (zero behind the launch's last block);  bd: the list pass's threshold of each — that of its
-    // component, gathered here — and the bound pass's running maximum of each over the wave's whole stream;  ca: the bound pass's
-    // component of each (comp is zero behind the launch's last block, where ra is zero too)
-    float ra[NT], bd[NT];
+// The epilogues of the linkage screen and, CAP, of the reach screen (the mutual-reachability weight min(s, core of the owner, core of
+// the partner): klo / khi are each launch row's core rounded down / up to f32, reach_kernels.hip).
+//   bd: the list pass's threshold of each of the lane's tile rows — that of its component, gathered when the stream begins; CAP: +inf
+//       where the owner's khi is below it (no edge of the owner can be the component's best) — and the bound pass's running maximum
+//       of each over the wave's whole stream
+//   ca, ka: the bound pass's component and klo of each tile row (comp is zero behind the launch's last block, where ra is zero too)
+//   cb, kb: the bound pass's components and klo of the streamed block's rows, beside rb
+template <int NT, bool LIST, bool CAP>
+struct LinkPolicy {
+    const LinkageArgs& a;
+    const float* cap;  // CAP: klo of every launch row (the bound pass), khi (the list pass)
+    float bd[NT];
     uint32_t ca[LIST ? 1 : NT];
+    float ka[!LIST && CAP ? NT : 1];
+    u32x4 cb[LIST ? 1 : 4];
+    f32x4 kb[!LIST && CAP ? 4 : 1];
+    __device__ __forceinline__ void begin(uint32_t tb0, int c) {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const size_t row = (size_t)(tb0 + t) * 32 + c;
-        ra[t] = gld(&a.rinv[row]);
-        const uint32_t cr = gld(&a.comp[row]);
-        bd[t] = LIST ? gld(&a.thr[cr]) : -__builtin_inff();
-        if (!LIST) ca[t] = cr;
+        for (int t = 0; t < NT; ++t) {
+            const size_t row = (size_t)(tb0 + t) * 32 + c;
+            const uint32_t cr = gld(&a.comp[row]);
+            if (LIST) {
+                const float th = gld(&a.thr[cr]);
+                bd[t] = !CAP || gld(&cap[row]) >= th ? th : __builtin_inff();
+            } else {
+                bd[t] = -__builtin_inff();
+                ca[t] = cr;
+                if (CAP) ka[t] = gld(&cap[row]);
+            }
+        }
     }
-
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-
-    auto enter_block = [&](JoinCursor& k, uint32_t gb) {
-        k.gb = gb;
-        k.ch = 0;
-        if (gb < b1) {
-            join_seek(p, k.sc, gb);
-            k.rows = row_rsrc(k.sc.blk + (size_t)(gb - k.sc.begin) * D4 * 32, (uint32_t)D4 * 512u);
-        }
-    };
-    const uint32_t lane_off = (uint32_t)(h * 64 + c) * 16u;  // the lane's bytes inside a block
-    JoinCursor cons, prod;
-    enter_block(cons, b0 + wave * a.stride);
-    prod = cons;
-
-    float4 buf[2][8];
-    // (always issues its loads: past the end of the wave's stream they read a chunk of its last block again — scan_mfma_kernel)
-    auto produce = [&](float4 (&b)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
-        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + step);
-    };
-
-    f32x4 rb[4];  // rinv of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
-    u32x4 cb[LIST ? 1 : 4];  // the bound pass: their components
-    auto rb_prefetch = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            rb[j] = *(const PCV_GLOBAL f32x4*)(a.rinv + (size_t)cons.gb * 32 + 8 * j + 4 * h);
-            if (!LIST) cb[j] = *(const PCV_GLOBAL u32x4*)(a.comp + (size_t)cons.gb * 32 + 8 * j + 4 * h);
-        }
-    };
-    auto owner_row = [&](int t) { return (tb0 + t) * 32u + (uint32_t)c; };
-    auto partner_row = [&](int i) { return cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h); };
-
-    // the list pass: (owner 32 t + c of the tile, partner i of the block) passes the score test
-    auto passes = [&](int t, int i) -> bool {
-        const float rbi = rb[i >> 2][i & 3];
-        const float s = acc[t][i] * ra[t] * rbi;
-        return (ra[t] > 0.0f && rbi > 0.0f) ? s >= bd[t] : (ra[t] != 0.0f && rbi != 0.0f);  // (a wild row: every pair, scan.h)
-    };
-
-    auto epilogue = [&]() {
-        if (NCH < 2) rb_prefetch();
+    __device__ __forceinline__ void prefetch(uint32_t gb, int h, int j) {
+        if (LIST) return;
+        cb[j] = *(const PCV_GLOBAL u32x4*)(a.comp + (size_t)gb * 32 + 8 * j + 4 * h);
+        if (CAP) kb[j] = *(const PCV_GLOBAL f32x4*)(cap + (size_t)gb * 32 + 8 * j + 4 * h);
+    }
+    __device__ __forceinline__ void block(const f32x16 (&acc)[NT], const float (&ra)[NT], const f32x4 (&rb)[4], const PairWhere& at) {
         if (LIST) {
+            // (owner 32 t + c of the tile, partner i of the block) passes the score test
+            auto passes = [&](int t, int i) -> bool {
+                const float rbi = rb[i >> 2][i & 3];
+                const float s = acc[t][i] * ra[t] * rbi;
+                return (ra[t] > 0.0f && rbi > 0.0f) ? s >= bd[t] : (ra[t] != 0.0f && rbi != 0.0f);  // (a wild row: every pair, scan.h)
+            };
+            // the partner is of another component (a row is of its own: no pair (a, a) is listed) and, CAP, its khi reaches the owner's
+            // threshold (bd is +inf for an owner that failed its own test: no finite khi reaches that)
+            auto foreign = [&](int t, int i, uint32_t co) -> bool {
+                const uint32_t pr = at.partner_row(i);
+                return gld(&a.comp[pr]) != co && (!CAP || gld(&cap[pr]) >= bd[t]);
+            };
             uint32_t n = 0;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) n += passes(t, i) ? 1u : 0u;
-            if (n) {
-                // rare: only here are the components looked at, loaded on demand; the pairs are judged again instead of kept as
-                // masks (neighbors_screen_kernel).  A row is of its own component: no pair (a, a) is listed.
-                uint32_t nf = 0;
+            if (n == 0) return;
+            // rare: only here are the components looked at, loaded on demand, so the streaming loop holds no register for them; the
+            // pairs are judged again instead of kept as masks (neighbors_screen_kernel)
+            uint32_t nf = 0;
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const uint32_t co = gld(&a.comp[owner_row(t)]);
+            for (int t = 0; t < NT; ++t) {
+                const uint32_t co = gld(&a.comp[at.owner_row(t)]);
 #pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        if (passes(t, i)) nf += gld(&a.comp[partner_row(i)]) != co ? 1u : 0u;
-                }
-                if (nf) {
-                    unsigned long long at = g_atomic_add64(&a.counters[kLinkListed], nf);
+                for (int i = 0; i < 16; ++i)
+                    if (passes(t, i)) nf += foreign(t, i, co) ? 1u : 0u;
+            }
+            if (nf == 0) return;
+            unsigned long long k = g_atomic_add64(&a.counters[kLinkListed], nf);
 #pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        const uint32_t co = gld(&a.comp[owner_row(t)]);
+            for (int t = 0; t < NT; ++t) {
+                const uint32_t co = gld(&a.comp[at.owner_row(t)]);
 #pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            if (passes(t, i) && gld(&a.comp[partner_row(i)]) != co) {
-                                if (at < a.cand_cap) gst(&a.cand[at], ((uint64_t)owner_row(t) << 32) | partner_row(i));
-                                ++at;
-                            }
-                        }
+                for (int i = 0; i < 16; ++i) {
+                    if (passes(t, i) && foreign(t, i, co)) {
+                        if (k < a.cand_cap) gst(&a.cand[k], ((uint64_t)at.owner_row(t) << 32) | at.partner_row(i));
+                        ++k;
                     }
                 }
             }
         } else {
-            // the running maximum of the certified scores with rows of other components (a wild partner adds nothing)
+            // the running maximum of the certified scores — CAP: of min(s, klo of the owner, klo of the partner) — with rows of other
+            // components (a wild partner adds nothing)
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 float m = bd[t];
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const float rbi = rb[i >> 2][i & 3];
-                    const float s = acc[t][i] * ra[t] * rbi;
-                    const bool ok = rbi > 0.0f && cb[i >> 2][i & 3] != ca[t];
-                    m = ok ? fmaxf(m, s) : m;
+                    if (rbi > 0.0f) {  // a certified partner
+                        // (the empty statement keeps this a branch, as in the capped form, where the compiler leaves one by itself:
+                        // folded into selects, the uncapped pass waits for every load in flight before its first compare and
+                        // measured 3 to 5 % slower — DESIGN.md §4 "The row-pair screen")
+                        if (!CAP) asm volatile("");
+                        float s = acc[t][i] * ra[t] * rbi;
+                        if (CAP) s = fminf(s, fminf(ka[t], kb[i >> 2][i & 3]));
+                        m = cb[i >> 2][i & 3] != ca[t] ? fmaxf(m, s) : m;
+                    }
                 }
                 bd[t] = m;
             }
         }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    };
-
-    auto consume = [&](const float4 (&b)[8]) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const f32x8 v = {b[2 * ks].x, b[2 * ks].y, b[2 * ks].z, b[2 * ks].w, b[2 * ks + 1].x, b[2 * ks + 1].y, b[2 * ks + 1].z, b[2 * ks + 1].w};
-            const bf16x8 av = __builtin_convertvector(v, bf16x8);
-            const int pc = 2 * (cons.ch * 4 + ks) + h;
-            const int ph = swizzle_piece(pc, c, P8);  // (tile row 32 t + c: the same low four bits as c)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const bf16x8 q8 = *(const bf16x8*)&lq[(32 * t + c) * P8 + ph];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q8, acc[t], 0, 0, 0);
-            }
-        }
-        if (++cons.ch == NCH) {
-            epilogue();
-            enter_block(cons, cons.gb + step);
-        }
-    };
-
-    // one chunk of loads in flight while one feeds the matrix cores (every buf[] index a literal, or the array moves to scratch);
-    // the block's rinv values are requested one chunk ahead of the epilogue and before that step's row loads
-#define PCV_LINK_STEP(REFILL, CONS)                      \
-    if (NCH >= 2 && cons.ch == NCH - 2) rb_prefetch();   \
-    produce(buf[REFILL]);                                \
-    consume(buf[CONS]);                                  \
-    if (cons.gb >= b1) break;
-    produce(buf[0]);
-    while (true) {
-        PCV_LINK_STEP(1, 0)
-        PCV_LINK_STEP(0, 1)
     }
-#undef PCV_LINK_STEP
-    if (!LIST) {
-        // the wave's stream has ended: publish.  Max commutes, so comp_max does not depend on which wave lands first.  In the late
-        // rounds a few components hold every row and every lane of every wave publishes to the same few words: a lane whose
-        // maximum the word already holds (comp_max only rises) leaves the atomic out
+    // The wave's stream has ended: the bound pass publishes.  Max commutes, so comp_max does not depend on which wave lands first.  In
+    // the late rounds a few components hold every row and every lane of every wave publishes to the same few words: a lane whose
+    // maximum the word already holds (comp_max only rises) leaves the atomic out
+    __device__ __forceinline__ void end(const float (&ra)[NT], int, int h) {
+        if (LIST) return;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const float m = fmaxf(bd[t], __shfl_xor(bd[t], 32));
@@ -273,6 +151,37 @@ __global__ __launch_bounds__(kLinkWaves * 64) void linkage_screen_kernel(const S
             }
         }
     }
+};
+
+// grid: neighbors_screen_kernel's.  x = tile (NT consecutive blocks: the owners), y = walk: the sampled blocks [y * walk_len,
+// + walk_len) of the launch, cut at its end; sampled block j is launch block j * stride.  Wave w takes the sampled blocks first + w,
+// first + w + kScreenWaves, ...  Staging, stream and accumulator layout: pair_screen.h.
+template <int NT, bool LIST, bool CAP>
+__device__ __forceinline__ void link_screen(const ScanParams& p, const LinkageArgs& a, const float* cap) {
+    extern __shared__ uint4 lq[];
+    __shared__ const float4* tbase[NT];
+    const uint32_t TB = p.total_blocks;
+    const uint32_t tb0 = blockIdx.x * NT;
+    const uint32_t step = kScreenWaves * a.stride;  // launch blocks between two blocks of a wave
+    const uint32_t SB = (TB + a.stride - 1) / a.stride;
+    const uint64_t first = (uint64_t)blockIdx.y * a.walk_len;
+    if (first >= SB) return;  // (the whole workgroup)
+    const uint32_t b0 = (uint32_t)first * a.stride;
+    const uint32_t b1 = (uint32_t)min((uint64_t)SB, first + a.walk_len) * a.stride;  // every sampled block below it is below TB
+    pair_stage_tile<NT>(p, lq, tbase, tb0);
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    if (b0 + wave * a.stride >= b1) return;
+    LinkPolicy<NT, LIST, CAP> pol{a, cap};
+    pair_stream<NT>(p, lq, a.rinv, tb0, b0 + wave * a.stride, b1, step, pol);
+}
+// two thin kernels: the uncapped forms keep the linkage tree's kernel arguments
+template <int NT, bool LIST>
+__global__ __launch_bounds__(kScreenWaves * 64) void linkage_screen_kernel(const ScanParams* __restrict__ pp, const LinkageArgs a) {
+    link_screen<NT, LIST, false>(*pp, a, nullptr);
+}
+template <int NT, bool LIST>
+__global__ __launch_bounds__(kScreenWaves * 64) void reach_screen_kernel(const ScanParams* __restrict__ pp, const LinkageArgs a, const float* cap) {
+    link_screen<NT, LIST, true>(*pp, a, cap);
 }
 
 // comp = parent = the row itself; the participating rows are counted
@@ -367,7 +276,7 @@ __global__ __launch_bounds__(256) void linkage_merge_kernel(const LinkageArgs a,
             gst(&a.edge_key[at], gld(&a.best_key[i]));
         }
     }
-    linkage_union(a.parent, lo, hi);
+    row_union(a.parent, lo, hi);
 }
 
 // `parent` is final here: plain loads.  comp = the root; the roots of participating rows are counted
@@ -391,11 +300,6 @@ __global__ __launch_bounds__(256) void linkage_settle_kernel(const LinkageArgs a
     gst(&a.parent[i], gld(&a.comp[i]));
 }
 
-__device__ __forceinline__ int64_t linkage_id(const RowRef& q) {
-    const int64_t* ids = gld(&q.sg->ids);
-    return ids ? gld(&ids[q.row]) : gld(&q.sg->id0) + (int64_t)q.row;
-}
-
 __global__ __launch_bounds__(256) void linkage_rows_kernel(const ScanParams* __restrict__ pp, const LinkageArgs a) {
     const ScanParams& p = *pp;
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
@@ -403,7 +307,7 @@ __global__ __launch_bounds__(256) void linkage_rows_kernel(const ScanParams* __r
     const RowRef r = row_ref(p, (uint32_t)i);
     if (r.row >= gld(&r.sg->nrows)) return;
     const int64_t o = gld(&a.seg_out0[r.sg - p.seg]) + (int64_t)r.row;
-    gst(&a.out_ids[o], linkage_id(r));
+    gst(&a.out_ids[o], row_id(r));
     gst(&a.out_part[o], (int8_t)(gld(&a.rinv[i]) != 0.0f ? 1 : 0));
 }
 
@@ -417,8 +321,8 @@ __global__ __launch_bounds__(256) void linkage_edges_kernel(const ScanParams* __
     e.c = key_f64(gld(&a.edge_key[i]));
     e.pos_a = gld(&a.seg_out0[ra.sg - p.seg]) + (int64_t)ra.row;
     e.pos_b = gld(&a.seg_out0[rb.sg - p.seg]) + (int64_t)rb.row;
-    e.id_a = linkage_id(ra);
-    e.id_b = linkage_id(rb);
+    e.id_a = row_id(ra);
+    e.id_b = row_id(rb);
     PCV_GLOBAL LinkEdge* out = (PCV_GLOBAL LinkEdge*)&a.out_edges[i];
     out->c = e.c;
     out->pos_a = e.pos_a;
@@ -427,21 +331,27 @@ __global__ __launch_bounds__(256) void linkage_edges_kernel(const ScanParams* __
     out->id_b = e.id_b;
 }
 
-template <bool LIST>
-void launch_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a) {
+template <bool LIST, bool CAP>
+void launch_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a, const float* cap) {
     if (p.total_blocks == 0) return;
+    const char* what = CAP ? "reach" : "linkage";
     const uint32_t NT = a.tile_blocks;
     PCV_REQUIRE((NT == 1 || NT == 2 || NT == 4) && a.stride >= 1 && a.walk_len >= 1 && (!LIST || a.stride == 1),
-                "linkage screen: bad shape (tile of %u blocks, stride %u, walks of %u)", NT, a.stride, a.walk_len);
+                "%s screen: bad shape (tile of %u blocks, stride %u, walks of %u)", what, NT, a.stride, a.walk_len);
     const size_t lds = (size_t)NT * 32 * p.D4 * 4 * sizeof(uint16_t);
     const unsigned tiles = (p.total_blocks + NT - 1) / NT;
     const unsigned sampled = (p.total_blocks + a.stride - 1) / a.stride;
     const unsigned walks = (sampled + a.walk_len - 1) / a.walk_len;
-    PCV_REQUIRE(walks <= 65535u, "linkage screen: %u walks", walks);
+    PCV_REQUIRE(walks <= 65535u, "%s screen: %u walks", what, walks);
     const dim3 grid(tiles, walks);
-#define PCV_LINK(N)                                                             \
-    allow_dynamic_lds((const void*)linkage_screen_kernel<N, LIST>, lds);        \
-    linkage_screen_kernel<N, LIST><<<grid, kLinkWaves * 64, lds, st>>>(dp, a);
+#define PCV_LINK(N)                                                                            \
+    if constexpr (CAP) {                                                                       \
+        allow_dynamic_lds((const void*)reach_screen_kernel<N, LIST>, lds);                     \
+        reach_screen_kernel<N, LIST><<<grid, kScreenWaves * 64, lds, st>>>(dp, a, cap);        \
+    } else {                                                                                   \
+        allow_dynamic_lds((const void*)linkage_screen_kernel<N, LIST>, lds);                   \
+        linkage_screen_kernel<N, LIST><<<grid, kScreenWaves * 64, lds, st>>>(dp, a);           \
+    }
     if (NT == 4) {
         PCV_LINK(4)
     } else if (NT == 2) {
@@ -462,11 +372,14 @@ void launch_linkage_begin(hipStream_t st, const ScanParams& p, const LinkageArgs
     PCV_LAUNCHED();
 }
 
-void launch_linkage_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a) {
+void launch_linkage_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a, const float* klo) {
     if (p.total_blocks == 0) return;
     const uint32_t launch_rows = p.total_blocks * 32;
     linkage_cert_kernel<<<cdiv64((int64_t)launch_rows, 256), 256, 0, st>>>(a, launch_rows);
-    launch_screen<false>(st, p, dp, a);
+    if (klo)
+        launch_screen<false, true>(st, p, dp, a, klo);
+    else
+        launch_screen<false, false>(st, p, dp, a, nullptr);
 }
 
 void launch_linkage_threshold(hipStream_t st, const ScanParams& p, const LinkageArgs& a) {
@@ -476,11 +389,21 @@ void launch_linkage_threshold(hipStream_t st, const ScanParams& p, const Linkage
     PCV_LAUNCHED();
 }
 
-void launch_linkage_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a) { launch_screen<true>(st, p, dp, a); }
+void launch_linkage_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a, const float* khi) {
+    if (khi)
+        launch_screen<true, true>(st, p, dp, a, khi);
+    else
+        launch_screen<true, false>(st, p, dp, a, nullptr);
+}
 
 void launch_linkage_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a) {
     if (a.n_cand == 0) return;
     linkage_rescore_kernel<<<cdiv64((int64_t)a.n_cand, 256), 256, 0, st>>>(dp, a);
+    launch_linkage_choose(st, a);
+}
+
+void launch_linkage_choose(hipStream_t st, const LinkageArgs& a) {
+    if (a.n_cand == 0) return;
     linkage_choose_kernel<<<cdiv64((int64_t)a.n_cand, 256), 256, 0, st>>>(a);
     PCV_LAUNCHED();
 }

@@ -20,12 +20,11 @@
 //                                           landed in cannot show.  It writes ids, neighbour ids, (float)c and counts.
 #include "device_access.h"
 #include "launch_rows.h"
+#include "pair_screen.h"
 #include "row_jobs.h"
 
 namespace pcv {
 namespace {
-
-constexpr int kNbrWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
 
 __device__ __forceinline__ void g_atomic_max32(uint32_t* p, uint32_t v) {
     (void)__hip_atomic_fetch_max((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -34,124 +33,45 @@ __device__ __forceinline__ uint32_t g_atomic_add32(uint32_t* p, uint32_t v) {
     return __hip_atomic_fetch_add((PCV_GLOBAL uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// grid: x = tile (NT consecutive blocks: the owners), y = walk: the sampled blocks [y * walk_len, + walk_len) of the launch, cut at
-// its end; sampled block j is launch block j * stride.  Wave w takes the sampled blocks first + w, first + w + kNbrWaves, ...
-// D[row of the streamed block][row of the tile]: lane (c = lane & 31, h = lane >> 5) holds tile rows 32 t + c and, in accumulator
-// i, block row (i & 3) + 8 (i >> 2) + 4 h.
+// The epilogues of the neighbour screen.  bd: the list pass's threshold of each of the lane's tile rows, the bound pass's running
+// maximum of each over the blocks of the span so far.  step and b1 are the stream's: the bound pass publishes when the wave's next
+// block lies in another span.
 template <int NT, bool LIST>
-__global__ __launch_bounds__(kNbrWaves * 64) void neighbors_screen_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
-    const ScanParams& p = *pp;
-    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
-    __shared__ const float4* tbase[NT];
-    const int D4 = p.D4, P8 = D4 >> 1, NCH = D4 >> 4;
-    const uint32_t TB = p.total_blocks;
-    const uint32_t tb0 = blockIdx.x * NT;
-    const uint32_t step = kNbrWaves * a.stride;  // launch blocks between two blocks of a wave
-    const uint32_t SB = (TB + a.stride - 1) / a.stride;
-    const uint64_t first = (uint64_t)blockIdx.y * a.walk_len;
-    if (first >= SB) return;  // (the whole workgroup)
-    const uint32_t b0 = (uint32_t)first * a.stride;
-    const uint32_t b1 = (uint32_t)min((uint64_t)SB, first + a.walk_len) * a.stride;  // every sampled block below it is below TB
-
-    if (threadIdx.x < NT) {
-        const uint32_t gb = tb0 + threadIdx.x;
-        const float4* base = nullptr;
-        if (gb < TB) {
-            const SegDesc& sg = p.seg[find_seg(p, gb)];
-            base = gld(&sg.blk) + (size_t)(gb - gld(&sg.blk0)) * D4 * 32;
-        }
-        tbase[threadIdx.x] = base;
+struct NeighborPolicy {
+    const NeighborArgs& a;
+    uint32_t TB, step, b1;
+    float bd[NT];
+    __device__ __forceinline__ void begin(uint32_t tb0, int c) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) bd[t] = LIST ? gld(&a.thr[(size_t)(tb0 + t) * 32 + c]) : -__builtin_inff();
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NT * 32 * P8; i += kNbrWaves * 64) {
-        const int r = i & 31, rest = i >> 5;
-        const int tb = rest / P8, pc = rest - tb * P8;
-        const float4* base = tbase[tb];
-        bf16x8 v8 = {};
-        if (base) {
-            const float4 lo = gld4(base + (size_t)(2 * pc) * 32 + r), hi = gld4(base + (size_t)(2 * pc + 1) * 32 + r);
-            const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            v8 = __builtin_convertvector(v, bf16x8);
-        }
-        const int row = tb * 32 + r;
-        lq[row * P8 + swizzle_piece(pc, row, P8)] = __builtin_bit_cast(uint4, v8);
-    }
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = uniform(threadIdx.x >> 6);
-    const int c = lane & 31, h = lane >> 5;
-    if (b0 + wave * a.stride >= b1) return;  // (no workgroup barrier behind this point)
-    // ra: rinv of the lane's tile rows (zero behind the launch's last block);  bd: the list pass's threshold of each, the bound
-    // pass's running maximum of each over the blocks of the span so far
-    float ra[NT], bd[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        ra[t] = gld(&a.rinv[(size_t)(tb0 + t) * 32 + c]);
-        bd[t] = LIST ? gld(&a.thr[(size_t)(tb0 + t) * 32 + c]) : -__builtin_inff();
-    }
-
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-
-    auto enter_block = [&](JoinCursor& k, uint32_t gb) {
-        k.gb = gb;
-        k.ch = 0;
-        if (gb < b1) {
-            join_seek(p, k.sc, gb);
-            k.rows = row_rsrc(k.sc.blk + (size_t)(gb - k.sc.begin) * D4 * 32, (uint32_t)D4 * 512u);
-        }
-    };
-    const uint32_t lane_off = (uint32_t)(h * 64 + c) * 16u;  // the lane's bytes inside a block
-    JoinCursor cons, prod;
-    enter_block(cons, b0 + wave * a.stride);
-    prod = cons;
-
-    float4 buf[2][8];
-    // (always issues its loads: past the end of the wave's stream they read a chunk of its last block again — scan_mfma_kernel)
-    auto produce = [&](float4 (&b)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
-        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + step);
-    };
-
-    f32x4 rb[4];  // rinv of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
-    auto rb_prefetch = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rb[j] = *(const PCV_GLOBAL f32x4*)(a.rinv + (size_t)cons.gb * 32 + 8 * j + 4 * h);
-    };
-    auto partner_row = [&](int i) { return cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h); };
-
-    // the list pass: (owner 32 t + c of the tile, partner i of the block) is a candidate
-    auto passes = [&](int t, int i, bool own) -> bool {
-        const float rbi = rb[i >> 2][i & 3];
-        const float s = acc[t][i] * ra[t] * rbi;
-        bool ok = (ra[t] > 0.0f && rbi > 0.0f) ? s >= bd[t] : (ra[t] != 0.0f && rbi != 0.0f);  // (a wild row: every pair, scan.h)
-        if (own) ok = ok && (tb0 + t) * 32u + (uint32_t)c != partner_row(i);
-        return ok;
-    };
-
-    auto epilogue = [&]() {
-        if (NCH < 2) rb_prefetch();
-        const bool own = cons.gb >= tb0 && cons.gb < tb0 + NT;  // the block is one of the tile's own: a row is no partner of itself
+    __device__ __forceinline__ void prefetch(uint32_t, int, int) {}
+    __device__ __forceinline__ void end(const float (&)[NT], int, int) {}
+    __device__ __forceinline__ void block(const f32x16 (&acc)[NT], const float (&ra)[NT], const f32x4 (&rb)[4], const PairWhere& at) {
+        const bool own = at.gb >= at.tb0 && at.gb < at.tb0 + NT;  // the block is one of the tile's own: a row is no partner of itself
         if (LIST) {
+            // (owner 32 t + c of the tile, partner i of the block) is a candidate
+            auto passes = [&](int t, int i) -> bool {
+                const float rbi = rb[i >> 2][i & 3];
+                const float s = acc[t][i] * ra[t] * rbi;
+                bool ok = (ra[t] > 0.0f && rbi > 0.0f) ? s >= bd[t] : (ra[t] != 0.0f && rbi != 0.0f);  // (a wild row: every pair, scan.h)
+                if (own) ok = ok && at.owner_row(t) != at.partner_row(i);
+                return ok;
+            };
             uint32_t n = 0;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) n += passes(t, i, own) ? 1u : 0u;
+                for (int i = 0; i < 16; ++i) n += passes(t, i) ? 1u : 0u;
             if (n) {  // rare; the pairs are judged again instead of kept as masks: four registers the <4> form does not have
-                unsigned long long at = g_atomic_add64(&a.counters[0], n);
+                unsigned long long k = g_atomic_add64(&a.counters[0], n);
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        if (passes(t, i, own)) {
-                            if (at < a.cand_cap) gst(&a.cand[at], ((uint64_t)((tb0 + t) * 32u + (uint32_t)c) << 32) | partner_row(i));
-                            ++at;
+                        if (passes(t, i)) {
+                            if (k < a.cand_cap) gst(&a.cand[k], ((uint64_t)at.owner_row(t) << 32) | at.partner_row(i));
+                            ++k;
                         }
                     }
                 }
@@ -166,7 +86,7 @@ __global__ __launch_bounds__(kNbrWaves * 64) void neighbors_screen_kernel(const 
                     const float rbi = rb[i >> 2][i & 3];
                     const float s = acc[t][i] * ra[t] * rbi;
                     bool ok = rbi > 0.0f;
-                    if (own) ok = ok && (tb0 + t) * 32u + (uint32_t)c != partner_row(i);
+                    if (own) ok = ok && at.owner_row(t) != at.partner_row(i);
                     m = ok ? fmaxf(m, s) : m;
                 }
                 bd[t] = m;
@@ -174,55 +94,41 @@ __global__ __launch_bounds__(kNbrWaves * 64) void neighbors_screen_kernel(const 
             // the wave's next block lies in another span, or there is none: publish.  Max commutes, so span_max does not depend on
             // which wave lands first
             const uint32_t per = a.stride * a.span_len;  // launch blocks a span covers
-            const uint32_t span = cons.gb / per, next = cons.gb + step;
+            const uint32_t span = at.gb / per, next = at.gb + step;
             if (next >= b1 || next / per != span) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     const float m = fmaxf(bd[t], __shfl_xor(bd[t], 32));
-                    if (h == 0 && ra[t] > 0.0f && m > -__builtin_inff())
-                        g_atomic_max32(&a.span_max[(size_t)span * TB * 32 + (size_t)(tb0 + t) * 32 + c], f32_key(m));
+                    if (at.h == 0 && ra[t] > 0.0f && m > -__builtin_inff())
+                        g_atomic_max32(&a.span_max[(size_t)span * TB * 32 + (size_t)(at.tb0 + t) * 32 + at.c], f32_key(m));
                     bd[t] = -__builtin_inff();
                 }
             }
         }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    };
-
-    auto consume = [&](const float4 (&b)[8]) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const f32x8 v = {b[2 * ks].x, b[2 * ks].y, b[2 * ks].z, b[2 * ks].w, b[2 * ks + 1].x, b[2 * ks + 1].y, b[2 * ks + 1].z, b[2 * ks + 1].w};
-            const bf16x8 av = __builtin_convertvector(v, bf16x8);
-            const int pc = 2 * (cons.ch * 4 + ks) + h;
-            const int ph = swizzle_piece(pc, c, P8);  // (tile row 32 t + c: the same low four bits as c)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const bf16x8 q8 = *(const bf16x8*)&lq[(32 * t + c) * P8 + ph];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q8, acc[t], 0, 0, 0);
-            }
-        }
-        if (++cons.ch == NCH) {
-            epilogue();
-            enter_block(cons, cons.gb + step);
-        }
-    };
-
-    // one chunk of loads in flight while one feeds the matrix cores (every buf[] index a literal, or the array moves to scratch);
-    // the block's rinv values are requested one chunk ahead of the epilogue and before that step's row loads
-#define PCV_NBR_STEP(REFILL, CONS)                       \
-    if (NCH >= 2 && cons.ch == NCH - 2) rb_prefetch();   \
-    produce(buf[REFILL]);                                \
-    consume(buf[CONS]);                                  \
-    if (cons.gb >= b1) return;
-    produce(buf[0]);
-    while (true) {
-        PCV_NBR_STEP(1, 0)
-        PCV_NBR_STEP(0, 1)
     }
-#undef PCV_NBR_STEP
+};
+
+// grid: x = tile (NT consecutive blocks: the owners), y = walk: the sampled blocks [y * walk_len, + walk_len) of the launch, cut at
+// its end; sampled block j is launch block j * stride.  Wave w takes the sampled blocks first + w, first + w + kScreenWaves, ...
+// Staging, stream and accumulator layout: pair_screen.h.
+template <int NT, bool LIST>
+__global__ __launch_bounds__(kScreenWaves * 64) void neighbors_screen_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
+    const ScanParams& p = *pp;
+    extern __shared__ uint4 lq[];
+    __shared__ const float4* tbase[NT];
+    const uint32_t TB = p.total_blocks;
+    const uint32_t tb0 = blockIdx.x * NT;
+    const uint32_t step = kScreenWaves * a.stride;  // launch blocks between two blocks of a wave
+    const uint32_t SB = (TB + a.stride - 1) / a.stride;
+    const uint64_t first = (uint64_t)blockIdx.y * a.walk_len;
+    if (first >= SB) return;  // (the whole workgroup)
+    const uint32_t b0 = (uint32_t)first * a.stride;
+    const uint32_t b1 = (uint32_t)min((uint64_t)SB, first + a.walk_len) * a.stride;  // every sampled block below it is below TB
+    pair_stage_tile<NT>(p, lq, tbase, tb0);
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    if (b0 + wave * a.stride >= b1) return;
+    NeighborPolicy<NT, LIST> pol{a, TB, step, b1};
+    pair_stream<NT>(p, lq, a.rinv, tb0, b0 + wave * a.stride, b1, step, pol);
 }
 
 // a wave per launch row: the k-th largest of the row's span maxima, found bit by bit from the top on their order-preserving images
@@ -321,10 +227,6 @@ __global__ __launch_bounds__(256) void neighbors_select_kernel(const ScanParams*
     if (r.row >= gld(&r.sg->nrows)) return;
     const int64_t o = gld(&a.seg_out0[r.sg - p.seg]) + (int64_t)r.row;
     const uint32_t e0 = gld(&a.row_off[lr]), e1 = gld(&a.row_off[lr + 1]);
-    auto id_of = [](const RowRef& q) {
-        const int64_t* ids = gld(&q.sg->ids);
-        return ids ? gld(&ids[q.row]) : gld(&q.sg->id0) + (int64_t)q.row;
-    };
     unsigned long long last_key = ~0ull;  // (no image is all ones: that would be a NaN)
     uint32_t last_row = 0;
     int n = 0;
@@ -352,7 +254,7 @@ __global__ __launch_bounds__(256) void neighbors_select_kernel(const ScanParams*
         last_key = bk;
         last_row = br;
         if (lane == 0) {
-            gst(&a.out_nbr[o * a.k + n], id_of(row_ref(p, br)));
+            gst(&a.out_nbr[o * a.k + n], row_id(row_ref(p, br)));
             gst(&a.out_score[o * a.k + n], (float)key_f64(bk));
         }
     }
@@ -361,7 +263,7 @@ __global__ __launch_bounds__(256) void neighbors_select_kernel(const ScanParams*
         gst(&a.out_score[o * a.k + j], __builtin_nanf(""));
     }
     if (lane == 0) {
-        gst(&a.out_ids[o], id_of(r));
+        gst(&a.out_ids[o], row_id(r));
         gst(&a.out_count[o], (int32_t)n);
     }
 }
@@ -381,7 +283,7 @@ void launch_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, co
     const dim3 grid(tiles, walks);
 #define PCV_NBR(N)                                                                \
     allow_dynamic_lds((const void*)neighbors_screen_kernel<N, LIST>, lds);        \
-    neighbors_screen_kernel<N, LIST><<<grid, kNbrWaves * 64, lds, st>>>(dp, a);
+    neighbors_screen_kernel<N, LIST><<<grid, kScreenWaves * 64, lds, st>>>(dp, a);
     if (NT == 4) {
         PCV_NBR(4)
     } else if (NT == 2) {

@@ -544,6 +544,97 @@ void label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const
 constexpr uint64_t kMaxNeighborCandidates = (uint64_t)1 << 30;  // directed (owner, partner) pairs the list pass may leave: 20 bytes each
 constexpr uint32_t kNeighborWalkBlocks = 256;  // sampled blocks a workgroup streams against its tile (kJoinSpanBlocks)
 
+// sampled blocks one workgroup of a walking screen streams against its tile: the grid's second dimension holds 65535 walks
+uint32_t walk_blocks(uint32_t TB) {
+    uint32_t walk_len = kNeighborWalkBlocks;
+    while ((TB + walk_len - 1) / walk_len > 65535u) walk_len *= 2;
+    return walk_len;
+}
+
+// The sample of the neighbours' bound pass and its spans (DESIGN.md §4 "Item neighbours", measurement): no result depends on them,
+// only the list's length.
+void neighbor_sample(uint32_t TB, int k, uint32_t& stride, uint32_t& span_len, uint32_t& spans) {
+    stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / (uint32_t)std::max(64, 4 * k)));
+    const uint32_t sampled = (TB + stride - 1) / stride;
+    const uint32_t want_spans = std::min<uint32_t>(sampled, std::min<uint32_t>(kMaxNeighborSpans, (uint32_t)std::max(64, 8 * k)));
+    span_len = (sampled + want_spans - 1) / want_spans;
+    spans = (sampled + span_len - 1) / span_len;
+}
+
+// The rescored candidates of every row's k best partners, as `neighbors` and the core step of `reach_tree` get them: the sample, the
+// buffers and their wiring, then bound pass, thresholds, list pass with the rerun rule, and the rescore that leaves sorted_key /
+// sorted_row / row_off.  Declared before the call's RowsJob, as every buffer is.  The counter of the list pass is the caller's, and so
+// are the messages: `list` hands back what it counted.
+struct NeighborPlan {
+    NeighborArgs a{};
+    DevBuf<float> d_thr;
+    DevBuf<uint32_t> d_span_max, d_cnt_off, d_sorted_row;
+    DevBuf<unsigned long long> d_sorted_key;
+    DevBuf<uint64_t> d_cand;
+    size_t nr = 0, n_pad = 0;
+
+    void open(const RowsJob& job, uint32_t tile_blocks, int k, float margin, unsigned long long* counter) {
+        const uint32_t TB = job.p->total_blocks;
+        a.tile_blocks = tile_blocks;
+        a.k = k;
+        a.margin = margin;
+        neighbor_sample(TB, k, a.stride, a.span_len, a.spans);
+        a.walk_len = walk_blocks(TB);
+        nr = job.nr;
+        n_pad = job.n_rinv;
+        d_thr.ensure(n_pad);
+        d_span_max.ensure((size_t)a.spans * nr);
+        d_cnt_off.ensure(2 * nr + 1);
+        a.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)k * (uint64_t)job.rows));
+        d_cand.ensure(a.cand_cap);
+        a.rinv = job.d_rinv.p;
+        a.thr = d_thr.p;
+        a.norm = job.d_norm.p;
+        a.span_max = d_span_max.p;
+        a.row_cnt = d_cnt_off.p;
+        a.row_off = d_cnt_off.p + nr;
+        a.counters = counter;
+        a.seg_out0 = job.seg_out0;
+    }
+    void zero(hipStream_t st) {
+        PCV_HIP(hipMemsetAsync(d_thr.p, 0, n_pad * sizeof(float), st));
+        PCV_HIP(hipMemsetAsync(d_span_max.p, 0, (size_t)a.spans * nr * sizeof(uint32_t), st));
+        PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
+    }
+    // bound pass and thresholds up to ev[2], then the list pass over every block, timed from there
+    Listing list(RowsJob& job, unsigned long long (&count)[1], unsigned long long (&again)[1]) {
+        launch_neighbors_bound(job.st, *job.p, job.dp, a);
+        launch_neighbors_threshold(job.st, *job.p, a);
+        job.record(2);
+        a.stride = 1;  // the list pass: every block
+        return list_candidates(
+            job, 2, a.counters, count, again, a.cand_cap, kMaxNeighborCandidates,
+            [&] {
+                a.cand = d_cand.p;
+                launch_neighbors_list(job.st, *job.p, job.dp, a);
+            },
+            [&] { PCV_HIP(hipMemsetAsync(a.counters, 0, sizeof(unsigned long long), job.st)); }, d_cand);
+    }
+    // ev[3], then candidates per owner, their offsets and the f64 cosine of each
+    void rescore(RowsJob& job, uint64_t n_cand) {
+        a.n_cand = n_cand;
+        d_sorted_key.ensure((size_t)std::max<uint64_t>(1, n_cand));
+        d_sorted_row.ensure((size_t)std::max<uint64_t>(1, n_cand));
+        a.sorted_key = d_sorted_key.p;
+        a.sorted_row = d_sorted_row.p;
+        job.record(3);
+        launch_neighbors_rescore(job.st, *job.p, job.dp, a);
+    }
+    void release() {
+        d_thr.release();
+        d_span_max.release();
+        d_cnt_off.release();
+        d_sorted_key.release();
+        d_sorted_row.release();
+        d_cand.release();
+    }
+};
+
 // Prep, bound pass, thresholds, list pass, rescore, select (neighbors_kernels.hip).  Everything the call allocates is its own and
 // is given back when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
 void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int64_t capacity, int64_t* out_ids, int64_t* out_neighbor_ids,
@@ -559,51 +650,24 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     const int tile = mfma_pass_queries(s->Dp);
     if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "neighbors: a bf16 tile of %d-d rows does not fit the LDS", s->D);
     if (n == 0) return;
-    DevBuf<float> d_thr, d_out_score;
-    DevBuf<uint32_t> d_span_max, d_cnt_off, d_sorted_row;
-    DevBuf<unsigned long long> d_cnt, d_sorted_key;
-    DevBuf<uint64_t> d_cand;
+    NeighborPlan plan;
+    DevBuf<float> d_out_score;
+    DevBuf<unsigned long long> d_cnt;
     DevBuf<int64_t> d_out_ids, d_out_nbr;
     DevBuf<int32_t> d_out_count;
-    NeighborArgs a{};
-    a.tile_blocks = (uint32_t)tile / kBlockRows;
-    RowsJob job(s, segs, "neighbors", PCV_METRIC_COSINE, a.tile_blocks);
+    RowsJob job(s, segs, "neighbors", PCV_METRIC_COSINE, (uint32_t)tile / kBlockRows);
     hipStream_t st = job.st;
     const ScanParams& p = *job.p;
     const ScanParams* dp = job.dp;
     const int64_t rows = job.rows;
 
-    // The sample and its spans (DESIGN.md §4 "Item neighbours", measurement): no result depends on them, only the list's length.
-    a.k = k;
-    a.margin = selfjoin_margin(s->Dp);
-    const uint32_t TB = p.total_blocks;
-    a.stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / (uint32_t)std::max(64, 4 * k)));
-    const uint32_t sampled = (TB + a.stride - 1) / a.stride;
-    const uint32_t want_spans = std::min<uint32_t>(sampled, std::min<uint32_t>(kMaxNeighborSpans, (uint32_t)std::max(64, 8 * k)));
-    a.span_len = (sampled + want_spans - 1) / want_spans;
-    a.spans = (sampled + a.span_len - 1) / a.span_len;
-    a.walk_len = kNeighborWalkBlocks;
-    while ((TB + a.walk_len - 1) / a.walk_len > 65535u) a.walk_len *= 2;  // (the grid's second dimension)
-
-    const size_t nr = job.nr, n_pad = job.n_rinv;
-    d_thr.ensure(n_pad);
-    d_span_max.ensure((size_t)a.spans * nr);
-    d_cnt_off.ensure(2 * nr + 1);
     d_cnt.ensure(1);
-    a.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)k * (uint64_t)rows));
-    d_cand.ensure(a.cand_cap);
+    plan.open(job, (uint32_t)tile / kBlockRows, k, selfjoin_margin(s->Dp), d_cnt.p);
+    NeighborArgs& a = plan.a;
     d_out_ids.ensure((size_t)rows);
     d_out_nbr.ensure((size_t)rows * k);
     d_out_score.ensure((size_t)rows * k);
     d_out_count.ensure((size_t)rows);
-    a.rinv = job.d_rinv.p;
-    a.thr = d_thr.p;
-    a.norm = job.d_norm.p;
-    a.span_max = d_span_max.p;
-    a.row_cnt = d_cnt_off.p;
-    a.row_off = d_cnt_off.p + nr;
-    a.counters = d_cnt.p;
-    a.seg_out0 = job.seg_out0;
     a.out_ids = d_out_ids.p;
     a.out_nbr = d_out_nbr.p;
     a.out_score = d_out_score.p;
@@ -617,22 +681,10 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     stats.spans = (int32_t)a.spans;
 
     unsigned long long count[1] = {0}, again[1] = {0};
-    PCV_HIP(hipMemsetAsync(d_thr.p, 0, n_pad * sizeof(float), st));
-    PCV_HIP(hipMemsetAsync(d_span_max.p, 0, (size_t)a.spans * nr * sizeof(uint32_t), st));
-    PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
+    plan.zero(st);
     PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
     job.prep();
-    launch_neighbors_bound(st, p, dp, a);
-    launch_neighbors_threshold(st, p, a);
-    job.record(2);
-    a.stride = 1;  // the list pass: every block
-    const Listing list = list_candidates(
-        job, 2, d_cnt.p, count, again, a.cand_cap, kMaxNeighborCandidates,
-        [&] {
-            a.cand = d_cand.p;
-            launch_neighbors_list(st, p, dp, a);
-        },
-        [&] { PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st)); }, d_cand);
+    const Listing list = plan.list(job, count, again);
     stats.prep_ms = job.elapsed(0);
     stats.bound_ms = job.elapsed(1);
     stats.screen_ms = list.ms;
@@ -646,13 +698,7 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
         stats.reruns = 1;
         stats.screen_ms += list.again_ms;
     }
-    a.n_cand = n_cand;
-    d_sorted_key.ensure((size_t)std::max<uint64_t>(1, n_cand));
-    d_sorted_row.ensure((size_t)std::max<uint64_t>(1, n_cand));
-    a.sorted_key = d_sorted_key.p;
-    a.sorted_row = d_sorted_row.p;
-    job.record(3);
-    launch_neighbors_rescore(st, p, dp, a);
+    plan.rescore(job, n_cand);
     job.record(4);
     launch_neighbors_select(st, p, dp, a);
     job.record(5);
@@ -808,15 +854,225 @@ void density_clusters(pcv_searcher* s, const int64_t* source_ids, int n_sources,
     *out_clusters = stats.clusters;
 }
 
-// ---- linkage tree (pcv_searcher_linkage_tree; DESIGN.md §4 "Linkage tree") ----
+// ---- linkage tree and reach tree (pcv_searcher_linkage_tree, pcv_searcher_reach_tree; DESIGN.md §4 "Linkage tree", "Reach tree") ----
 constexpr uint64_t kMaxLinkageCandidates = (uint64_t)1 << 28;  // directed pairs one round's list pass may leave: 16 bytes each
 constexpr int64_t kMaxLinkageRows = (int64_t)1 << 30;
 
-// Prep, then Borůvka rounds of bound pass, thresholds, list pass, rescore and choice, merge (linkage_kernels.hip), with the
-// neighbours' plumbing: the row table, the tile choice, the sampled bound pass and the rerun-once rule for a short list.  The host
-// waits where a count decides an allocation and at the end of a round, where it checks that the round emitted one edge per
-// component it removed and at least halved their number: no loop here can run on without progress.  Everything the call allocates
-// is its own and is given back when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
+// The Borůvka rounds of both trees (linkage_kernels.hip): bound pass, thresholds, list pass, rescore and choice, merge, with the
+// neighbours' plumbing — the row table, the tile choice, the sampled bound pass and the rerun-once rule for a short list.  The host
+// waits where a count decides an allocation and at the end of a round, where it checks that the round emitted one edge per component
+// it removed and at least halved their number: no loop here can run on without progress.  The trees differ in three launches of a
+// round (bound, list, rescore), which `run` takes as callables, and in their stats structs, whose shared fields `Stats` names.
+// Declared before the call's RowsJob, as every buffer is.
+struct LinkRounds {
+    DevBuf<unsigned long long> d_cnt, d_cand_key, d_best, d_edges;  // d_best: best_key, best_pair;  d_edges: edge_pair, edge_key
+    DevBuf<uint64_t> d_cand;
+    DevBuf<uint32_t> d_comp, d_rows3;  // d_rows3: parent, cert, comp_max
+    DevBuf<float> d_thr;
+    DevBuf<int64_t> d_out_ids;
+    DevBuf<int8_t> d_out_part;
+    uint32_t sample_stride = 1;
+    size_t nr = 0, n_pad = 0;
+    uint64_t P = 0, emitted = 0;  // participating rows; edges
+    unsigned long long counts[kLinkCounters] = {}, again[kLinkCounters] = {};
+
+    // The buffers every round uses and their wiring into `a` (whose tile_blocks the caller has set), the zeroing — `zero_more` queues
+    // the caller's own between comp's and the counters', of which the caller may keep `more_counters` of its own behind kLinkCounters
+    // — prep, begin and the participating count.
+    template <class Stats, class Zero>
+    void open(RowsJob& job, const char* what, LinkageArgs& a, int Dp, int more_counters, Stats& stats, Zero zero_more) {
+        hipStream_t st = job.st;
+        // The sample of the bound pass (DESIGN.md §4 "Linkage tree"): no result depends on it, only the list's length.
+        const uint32_t TB = job.p->total_blocks;
+        sample_stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / 64));
+        a.margin = selfjoin_margin(Dp);
+        a.walk_len = walk_blocks(TB);
+
+        nr = job.nr;
+        n_pad = job.n_rinv;
+        d_cnt.ensure(kLinkCounters + more_counters);
+        d_comp.ensure(n_pad);
+        d_rows3.ensure(3 * nr);
+        d_thr.ensure(nr);
+        d_best.ensure(2 * nr);
+        d_edges.ensure(2 * nr);
+        d_out_ids.ensure((size_t)job.rows);
+        d_out_part.ensure((size_t)job.rows);
+        a.rinv = job.d_rinv.p;
+        a.norm = job.d_norm.p;
+        a.comp = d_comp.p;
+        a.parent = d_rows3.p;
+        a.cert = d_rows3.p + nr;
+        a.comp_max = d_rows3.p + 2 * nr;
+        a.thr = d_thr.p;
+        a.best_key = d_best.p;
+        a.best_pair = d_best.p + nr;
+        a.edge_pair = d_edges.p;
+        a.edge_key = d_edges.p + nr;
+        a.edge_cap = nr;
+        a.counters = d_cnt.p;
+        a.seg_out0 = job.seg_out0;
+        a.out_ids = d_out_ids.p;
+        a.out_part = d_out_part.p;
+
+        PCV_HIP(hipMemsetAsync(d_comp.p, 0, n_pad * sizeof(uint32_t), st));
+        zero_more();
+        PCV_HIP(hipMemsetAsync(d_cnt.p, 0, (kLinkCounters + more_counters) * sizeof(unsigned long long), st));
+        job.prep();
+        launch_linkage_begin(st, *job.p, a);
+        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+        job.wait();
+        stats.prep_ms = job.elapsed(0);
+        P = counts[kLinkParticipating];
+        stats.participating = (int64_t)P;
+        PCV_REQUIRE(P <= (uint64_t)job.rows, "%s: %llu participating rows of %lld", what, (unsigned long long)P, (long long)job.rows);
+    }
+
+    // The candidate buffers (allocated here, behind whatever the caller gave back since `open`), the rounds until one component is
+    // left, and the edge count.  `same`: what the rows of a list that grew too long are nearly the same of ("distance", "reach").
+    template <class Stats, class Bound, class List, class Rescore>
+    void run(RowsJob& job, const char* what, const char* same, LinkageArgs& a, Stats& stats, Bound bound, List list_pass, Rescore rescore) {
+        hipStream_t st = job.st;
+        const ScanParams& p = *job.p;
+        a.cand_cap = std::min<uint64_t>(kMaxLinkageCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)nr));
+        d_cand.ensure(a.cand_cap);
+        d_cand_key.ensure(a.cand_cap);
+
+        // PCV_LINKAGE_ROUNDS_FILE (tools/bench_linkage.py, tools/bench_reach.py): one line per round is appended to that file — round,
+        // components before and after, candidates, bound repeated at stride 1 (0 / 1), list reruns, and the round's bound, list,
+        // rescore and merge ms
+        FILE* round_log = nullptr;
+        if (const char* f = getenv("PCV_LINKAGE_ROUNDS_FILE")) round_log = std::fopen(f, "a");
+        struct CloseLog {
+            FILE* f;
+            ~CloseLog() {
+                if (f) std::fclose(f);
+            }
+        } close_log{round_log};
+
+        uint64_t components = P;
+        emitted = 0;
+        while (components > 1) {
+            bool bound_repeated = false;
+            // 1. the bound of every component, and its threshold
+            auto queue_bound = [&](uint32_t stride) {
+                PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkUnbounded, 0, 2 * sizeof(unsigned long long), st));
+                static_assert(kLinkCertRoots == kLinkUnbounded + 1, "the two counters of the threshold step are reset together");
+                a.stride = stride;
+                bound();
+                launch_linkage_threshold(st, p, a);
+            };
+            PCV_HIP(hipMemsetAsync(d_rows3.p + nr, 0, 2 * nr * sizeof(uint32_t), st));  // cert, comp_max
+            PCV_HIP(hipMemsetAsync(d_best.p, 0, nr * sizeof(unsigned long long), st));
+            PCV_HIP(hipMemsetAsync(d_best.p + nr, 0xff, nr * sizeof(unsigned long long), st));
+            PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st));
+            PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkRoots, 0, sizeof(unsigned long long), st));
+            job.record(0);
+            queue_bound(sample_stride);
+            if (sample_stride > 1) {
+                // a component with a certified row that met no certified foreign row in the sample, while there is one somewhere:
+                // without a bound it would list every foreign partner of every row it has.  Once more over every block (max commutes:
+                // what the sample found stays).
+                PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+                job.wait();
+                bound_repeated = counts[kLinkUnbounded] > 0 && counts[kLinkCertRoots] >= 2;
+                if (bound_repeated) queue_bound(1);
+            }
+            job.record(1);
+            // 2. the candidates
+            a.stride = 1;
+            const Listing list = list_candidates(
+                job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxLinkageCandidates,
+                [&] {
+                    a.cand = d_cand.p;
+                    a.cand_key = d_cand_key.p;
+                    list_pass();
+                },
+                [&] { PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st)); }, d_cand, d_cand_key);
+            static_assert(kLinkListed == 0, "the listed count is the counter the listing rule reads");
+            const float round_bound_ms = job.elapsed(0), round_list_ms = list.ms + (list.repeated ? list.again_ms : 0.0f);
+            stats.bound_ms += round_bound_ms;
+            stats.list_ms += list.ms;
+            const uint64_t n_cand = counts[kLinkListed];
+            if (n_cand > kMaxLinkageCandidates)
+                PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                         "%s: round %d lists %llu candidate pairs, more than %llu (2^28): too many rows are nearly the same %s from their "
+                         "nearest foreign row, or lie outside the lengths the screen is certified for; build the tree of fewer rows",
+                         what, (int)stats.rounds, (unsigned long long)n_cand, (unsigned long long)kMaxLinkageCandidates, same);
+            if (list.repeated) {  // (the pass lists the same pairs again)
+                PCV_REQUIRE(again[kLinkListed] == n_cand, "%s: the repeated list pass left %llu candidates, the first %llu", what, again[kLinkListed],
+                            (unsigned long long)n_cand);
+                stats.reruns += 1;
+                stats.list_ms += list.again_ms;
+            }
+            stats.candidates += (int64_t)n_cand;
+            stats.rounds += 1;
+            // 3. the f64 decision, 4. the merge
+            a.n_cand = n_cand;
+            job.record(3);
+            rescore();
+            job.record(4);
+            launch_linkage_merge(st, p, a);
+            job.record(5);
+            PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
+            job.wait();
+            stats.rescore_ms += job.elapsed(3);
+            stats.merge_ms += job.elapsed(4);
+            // 5. one edge per component that went, and at least every second one went
+            const uint64_t after = counts[kLinkRoots], now = counts[kLinkEmitted];
+            if (!(after >= 1 && after <= components / 2 && now - emitted == components - after))
+                PCV_FAIL(PCV_ERR_INTERNAL, "%s: round %d went from %llu components to %llu and emitted %llu edges", what, (int)stats.rounds - 1,
+                         (unsigned long long)components, (unsigned long long)after, (unsigned long long)(now - emitted));
+            if (round_log)
+                std::fprintf(round_log, "%d %llu %llu %llu %d %d %.4f %.4f %.4f %.4f\n", (int)stats.rounds - 1, (unsigned long long)components,
+                             (unsigned long long)after, (unsigned long long)n_cand, bound_repeated ? 1 : 0, list.repeated ? 1 : 0, round_bound_ms,
+                             round_list_ms, job.elapsed(3), job.elapsed(4));
+            components = after;
+            emitted = now;
+        }
+        PCV_REQUIRE(emitted == (P > 0 ? P - 1 : 0), "%s: %llu edges for %llu participating rows", what, (unsigned long long)emitted, (unsigned long long)P);
+        stats.edges = (int64_t)emitted;
+        a.n_edges = emitted;
+    }
+};
+
+// What both trees check before they open a job.  -> the rows of the LDS tile; 0: the count alone was asked for, or there are no rows
+int tree_arguments(pcv_searcher* s, const char* what, int64_t n, const int64_t* out_pos_a, int64_t capacity, int64_t* out_edges) {
+    if (out_pos_a == nullptr && capacity == 0) return 0;  // the count alone
+    PCV_REQUIRE(capacity >= n, "%s: the outputs have room for %lld rows, the selected sources have %lld", what, (long long)capacity, (long long)n);
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: a bf16 tile of %d-d rows does not fit the LDS", what, s->D);
+    if (n > kMaxLinkageRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: %lld rows, more than 2^30", what, (long long)n);
+    *out_edges = 0;
+    return n == 0 ? 0 : tile;
+}
+
+// The n edges the output step left in `d`, in the order the trees return them: key descending (c or w), then the two positions
+// ascending; the columns every tree has are written here.
+template <class Edge, class Key>
+std::vector<Edge> edges_in_order(const DevBuf<Edge>& d, uint64_t n, Key key, int64_t* out_pos_a, int64_t* out_pos_b, double* out_key, int64_t* out_id_a,
+                                 int64_t* out_id_b) {
+    std::vector<Edge> edges((size_t)n);
+    if (n > 0) PCV_HIP(hipMemcpy(edges.data(), d.p, (size_t)n * sizeof(Edge), hipMemcpyDeviceToHost));
+    std::sort(edges.begin(), edges.end(), [&](const Edge& x, const Edge& y) {
+        if (key(x) != key(y)) return key(x) > key(y);
+        if (x.pos_a != y.pos_a) return x.pos_a < y.pos_a;
+        return x.pos_b < y.pos_b;
+    });
+    for (size_t i = 0; i < edges.size(); ++i) {
+        out_pos_a[i] = edges[i].pos_a;
+        out_pos_b[i] = edges[i].pos_b;
+        out_key[i] = key(edges[i]);
+        if (out_id_a) {
+            out_id_a[i] = edges[i].id_a;
+            out_id_b[i] = edges[i].id_b;
+        }
+    }
+    return edges;
+}
+
+// Prep, the rounds of LinkRounds with the linkage screen, the outputs.  Everything the call allocates is its own and is given back
+// when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
 void linkage_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int64_t capacity, int64_t* out_ids, int8_t* out_part, int64_t* out_pos_a,
                   int64_t* out_pos_b, int64_t* out_id_a, int64_t* out_id_b, double* out_c, int64_t* out_rows, int64_t* out_edges) {
     PCV_REQUIRE(!s->dirty, "linkage_tree: rows were added or cleared without pcv_searcher_finalize");
@@ -825,19 +1081,9 @@ void linkage_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int
     const int64_t n = selected_rows(segs);
     *out_rows = n;
     s->linkage_stats = pcv_linkage_stats{};
-    if (out_pos_a == nullptr && capacity == 0) return;  // the count alone
-    PCV_REQUIRE(capacity >= n, "linkage_tree: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
-    const int tile = mfma_pass_queries(s->Dp);
-    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "linkage_tree: a bf16 tile of %d-d rows does not fit the LDS", s->D);
-    if (n > kMaxLinkageRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "linkage_tree: %lld rows, more than 2^30", (long long)n);
-    *out_edges = 0;
-    if (n == 0) return;
-    DevBuf<unsigned long long> d_cnt, d_cand_key, d_best, d_edges;  // d_best: best_key, best_pair;  d_edges: edge_pair, edge_key
-    DevBuf<uint64_t> d_cand;
-    DevBuf<uint32_t> d_comp, d_rows3;  // d_rows3: parent, cert, comp_max
-    DevBuf<float> d_thr;
-    DevBuf<int64_t> d_out_ids;
-    DevBuf<int8_t> d_out_part;
+    const int tile = tree_arguments(s, "linkage_tree", n, out_pos_a, capacity, out_edges);
+    if (tile == 0) return;
+    LinkRounds rounds;
     DevBuf<LinkEdge> d_out_edges;
     LinkageArgs a{};
     a.tile_blocks = (uint32_t)tile / kBlockRows;
@@ -847,182 +1093,29 @@ void linkage_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int
     const ScanParams* dp = job.dp;
     const int64_t rows = job.rows;
 
-    // The sample of the bound pass (DESIGN.md §4 "Linkage tree"): no result depends on it, only the list's length.
-    const uint32_t TB = p.total_blocks;
-    const uint32_t sample_stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / 64));
-    a.margin = selfjoin_margin(s->Dp);
-    a.walk_len = kNeighborWalkBlocks;
-    while ((TB + a.walk_len - 1) / a.walk_len > 65535u) a.walk_len *= 2;  // (the grid's second dimension)
-
-    const size_t nr = job.nr, n_pad = job.n_rinv;
-    d_cnt.ensure(kLinkCounters);
-    d_comp.ensure(n_pad);
-    d_rows3.ensure(3 * nr);
-    d_thr.ensure(nr);
-    d_best.ensure(2 * nr);
-    d_edges.ensure(2 * nr);
-    d_out_ids.ensure((size_t)rows);
-    d_out_part.ensure((size_t)rows);
-    a.cand_cap = std::min<uint64_t>(kMaxLinkageCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)nr));
-    d_cand.ensure(a.cand_cap);
-    d_cand_key.ensure(a.cand_cap);
-    a.rinv = job.d_rinv.p;
-    a.norm = job.d_norm.p;
-    a.comp = d_comp.p;
-    a.parent = d_rows3.p;
-    a.cert = d_rows3.p + nr;
-    a.comp_max = d_rows3.p + 2 * nr;
-    a.thr = d_thr.p;
-    a.best_key = d_best.p;
-    a.best_pair = d_best.p + nr;
-    a.edge_pair = d_edges.p;
-    a.edge_key = d_edges.p + nr;
-    a.edge_cap = nr;
-    a.counters = d_cnt.p;
-    a.seg_out0 = job.seg_out0;
-    a.out_ids = d_out_ids.p;
-    a.out_part = d_out_part.p;
-
     pcv_linkage_stats& stats = s->linkage_stats;
     stats.rows = rows;
     stats.tile_rows = tile;
+    rounds.open(job, "linkage_tree", a, s->Dp, 0, stats, [] {});
+    rounds.run(
+        job, "linkage_tree", "distance", a, stats, [&] { launch_linkage_bound(st, p, dp, a); }, [&] { launch_linkage_list(st, p, dp, a); },
+        [&] { launch_linkage_rescore(st, p, dp, a); });
 
-    unsigned long long counts[kLinkCounters] = {}, again[kLinkCounters] = {};
-    PCV_HIP(hipMemsetAsync(d_comp.p, 0, n_pad * sizeof(uint32_t), st));
-    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kLinkCounters * sizeof(unsigned long long), st));
-    job.prep();
-    launch_linkage_begin(st, p, a);
-    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-    job.wait();
-    stats.prep_ms = job.elapsed(0);
-    const uint64_t P = counts[kLinkParticipating];
-    stats.participating = (int64_t)P;
-    PCV_REQUIRE(P <= (uint64_t)rows, "linkage_tree: %llu participating rows of %lld", (unsigned long long)P, (long long)rows);
-
-    // PCV_LINKAGE_ROUNDS_FILE (tools/bench_linkage.py): one line per round is appended to that file — round, components before and
-    // after, candidates, bound repeated at stride 1 (0 / 1), list reruns, and the round's bound, list, rescore and merge ms
-    FILE* round_log = nullptr;
-    if (const char* f = getenv("PCV_LINKAGE_ROUNDS_FILE")) round_log = std::fopen(f, "a");
-    struct CloseLog {
-        FILE* f;
-        ~CloseLog() {
-            if (f) std::fclose(f);
-        }
-    } close_log{round_log};
-
-    uint64_t components = P, emitted = 0;
-    while (components > 1) {
-        bool bound_repeated = false;
-        // 1. the bound of every component, and its threshold
-        auto queue_bound = [&](uint32_t stride) {
-            PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkUnbounded, 0, 2 * sizeof(unsigned long long), st));
-            static_assert(kLinkCertRoots == kLinkUnbounded + 1, "the two counters of the threshold step are reset together");
-            a.stride = stride;
-            launch_linkage_bound(st, p, dp, a);
-            launch_linkage_threshold(st, p, a);
-        };
-        PCV_HIP(hipMemsetAsync(d_rows3.p + nr, 0, 2 * nr * sizeof(uint32_t), st));  // cert, comp_max
-        PCV_HIP(hipMemsetAsync(d_best.p, 0, nr * sizeof(unsigned long long), st));
-        PCV_HIP(hipMemsetAsync(d_best.p + nr, 0xff, nr * sizeof(unsigned long long), st));
-        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st));
-        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkRoots, 0, sizeof(unsigned long long), st));
-        job.record(0);
-        queue_bound(sample_stride);
-        if (sample_stride > 1) {
-            // a component with a certified row that met no certified foreign row in the sample, while there is one somewhere: without
-            // a bound it would list every foreign partner of every row it has.  Once more over every block (max commutes: what the
-            // sample found stays).
-            PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-            job.wait();
-            bound_repeated = counts[kLinkUnbounded] > 0 && counts[kLinkCertRoots] >= 2;
-            if (bound_repeated) queue_bound(1);
-        }
-        job.record(1);
-        // 2. the candidates
-        a.stride = 1;
-        const Listing list = list_candidates(
-            job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxLinkageCandidates,
-            [&] {
-                a.cand = d_cand.p;
-                a.cand_key = d_cand_key.p;
-                launch_linkage_list(st, p, dp, a);
-            },
-            [&] { PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st)); }, d_cand, d_cand_key);
-        static_assert(kLinkListed == 0, "the listed count is the counter the listing rule reads");
-        const float round_bound_ms = job.elapsed(0), round_list_ms = list.ms + (list.repeated ? list.again_ms : 0.0f);
-        stats.bound_ms += round_bound_ms;
-        stats.list_ms += list.ms;
-        const uint64_t n_cand = counts[kLinkListed];
-        if (n_cand > kMaxLinkageCandidates)
-            PCV_FAIL(PCV_ERR_UNSUPPORTED,
-                     "linkage_tree: round %d lists %llu candidate pairs, more than %llu (2^28): too many rows are nearly the same distance from their "
-                     "nearest foreign row, or lie outside the lengths the screen is certified for; build the tree of fewer rows",
-                     (int)stats.rounds, (unsigned long long)n_cand, (unsigned long long)kMaxLinkageCandidates);
-        if (list.repeated) {  // (the pass lists the same pairs again)
-            PCV_REQUIRE(again[kLinkListed] == n_cand, "linkage_tree: the repeated list pass left %llu candidates, the first %llu", again[kLinkListed],
-                        (unsigned long long)n_cand);
-            stats.reruns += 1;
-            stats.list_ms += list.again_ms;
-        }
-        stats.candidates += (int64_t)n_cand;
-        stats.rounds += 1;
-        // 3. the f64 decision, 4. the merge
-        a.n_cand = n_cand;
-        job.record(3);
-        launch_linkage_rescore(st, p, dp, a);
-        job.record(4);
-        launch_linkage_merge(st, p, a);
-        job.record(5);
-        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-        job.wait();
-        stats.rescore_ms += job.elapsed(3);
-        stats.merge_ms += job.elapsed(4);
-        // 5. one edge per component that went, and at least every second one went
-        const uint64_t after = counts[kLinkRoots], now = counts[kLinkEmitted];
-        if (!(after >= 1 && after <= components / 2 && now - emitted == components - after))
-            PCV_FAIL(PCV_ERR_INTERNAL, "linkage_tree: round %d went from %llu components to %llu and emitted %llu edges", (int)stats.rounds - 1,
-                     (unsigned long long)components, (unsigned long long)after, (unsigned long long)(now - emitted));
-        if (round_log)
-            std::fprintf(round_log, "%d %llu %llu %llu %d %d %.4f %.4f %.4f %.4f\n", (int)stats.rounds - 1, (unsigned long long)components,
-                         (unsigned long long)after, (unsigned long long)n_cand, bound_repeated ? 1 : 0, list.repeated ? 1 : 0, round_bound_ms, round_list_ms,
-                         job.elapsed(3), job.elapsed(4));
-        components = after;
-        emitted = now;
-    }
-    PCV_REQUIRE(emitted == (P > 0 ? P - 1 : 0), "linkage_tree: %llu edges for %llu participating rows", (unsigned long long)emitted, (unsigned long long)P);
-    stats.edges = (int64_t)emitted;
-
-    a.n_edges = emitted;
+    const uint64_t emitted = rounds.emitted;
     d_out_edges.ensure((size_t)std::max<uint64_t>(1, emitted));
     a.out_edges = d_out_edges.p;
     launch_linkage_output(st, p, dp, a);
     job.wait();
-    std::vector<LinkEdge> edges((size_t)emitted);
-    if (emitted > 0) PCV_HIP(hipMemcpy(edges.data(), d_out_edges.p, (size_t)emitted * sizeof(LinkEdge), hipMemcpyDeviceToHost));
-    std::sort(edges.begin(), edges.end(), [](const LinkEdge& x, const LinkEdge& y) {
-        if (x.c != y.c) return x.c > y.c;
-        if (x.pos_a != y.pos_a) return x.pos_a < y.pos_a;
-        return x.pos_b < y.pos_b;
-    });
-    for (size_t i = 0; i < edges.size(); ++i) {
-        out_pos_a[i] = edges[i].pos_a;
-        out_pos_b[i] = edges[i].pos_b;
-        out_c[i] = edges[i].c;
-        if (out_id_a) {
-            out_id_a[i] = edges[i].id_a;
-            out_id_b[i] = edges[i].id_b;
-        }
-    }
-    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (out_part) PCV_HIP(hipMemcpy(out_part, d_out_part.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
+    edges_in_order(d_out_edges, emitted, [](const LinkEdge& e) { return e.c; }, out_pos_a, out_pos_b, out_c, out_id_a, out_id_b);
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, rounds.d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (out_part) PCV_HIP(hipMemcpy(out_part, rounds.d_out_part.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
     *out_edges = (int64_t)emitted;
 }
 
-// ---- reach tree (pcv_searcher_reach_tree; DESIGN.md §4 "Reach tree") ----
-// Prep, the core step — the neighbours' bound, thresholds, list and rescore with k = j, then the j-th best f64 c of every row and
-// its two f32 images (reach_kernels.hip) — and the rounds of linkage_tree with the capped screen and the capped weight.  The checks
-// of a round, the stride-1 repeat of the bound pass and the rerun-once rule of the lists are linkage_tree's.  The core step's buffers
-// go back before the rounds allocate theirs.  Nothing of the searcher's pass state is touched, and only the f32 rows are read.
+// Prep, the core step — the neighbours' bound, thresholds, list and rescore with k = j (NeighborPlan), then the j-th best f64 c of
+// every row and its two f32 images (reach_kernels.hip) — and the rounds of LinkRounds with the capped screen and the capped weight.
+// The core step's buffers go back before the rounds allocate their candidate lists.  Nothing of the searcher's pass state is touched,
+// and only the f32 rows are read.
 void reach_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int min_items, int64_t capacity, int64_t* out_ids, int8_t* out_part,
                 double* out_core, int64_t* out_pos_a, int64_t* out_pos_b, int64_t* out_id_a, int64_t* out_id_b, double* out_w, double* out_c,
                 int64_t* out_rows, int64_t* out_edges) {
@@ -1032,20 +1125,12 @@ void reach_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m
     const int64_t n = selected_rows(segs);
     *out_rows = n;
     s->reach_stats = pcv_reach_stats{};
-    if (out_pos_a == nullptr && capacity == 0) return;  // the count alone
-    PCV_REQUIRE(capacity >= n, "reach_tree: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
-    const int tile = mfma_pass_queries(s->Dp);
-    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "reach_tree: a bf16 tile of %d-d rows does not fit the LDS", s->D);
-    if (n > kMaxLinkageRows) PCV_FAIL(PCV_ERR_UNSUPPORTED, "reach_tree: %lld rows, more than 2^30", (long long)n);
-    *out_edges = 0;
-    if (n == 0) return;
-    DevBuf<unsigned long long> d_cnt, d_cand_key, d_best, d_edges, d_sorted_key;  // d_best: best_key, best_pair;  d_edges: edge_pair, edge_key
-    DevBuf<uint64_t> d_cand;
-    DevBuf<uint32_t> d_comp, d_rows3, d_span_max, d_cnt_off, d_sorted_row;  // d_rows3: parent, cert, comp_max
-    DevBuf<float> d_thr, d_k2, d_nbr_thr;                                   // d_k2: klo, khi
+    const int tile = tree_arguments(s, "reach_tree", n, out_pos_a, capacity, out_edges);
+    if (tile == 0) return;
+    LinkRounds rounds;
+    NeighborPlan core;
+    DevBuf<float> d_k2;  // klo, khi
     DevBuf<double> d_core, d_out_core;
-    DevBuf<int64_t> d_out_ids;
-    DevBuf<int8_t> d_out_part;
     DevBuf<ReachEdge> d_out_edges;
     ReachArgs ra{};
     LinkageArgs& a = ra.l;
@@ -1056,109 +1141,33 @@ void reach_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m
     const ScanParams* dp = job.dp;
     const int64_t rows = job.rows;
 
-    // The sample of the bound pass: no result depends on it, only the list's length.
-    const uint32_t TB = p.total_blocks;
-    const uint32_t sample_stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / 64));
-    a.margin = selfjoin_margin(s->Dp);
-    a.walk_len = kNeighborWalkBlocks;
-    while ((TB + a.walk_len - 1) / a.walk_len > 65535u) a.walk_len *= 2;  // (the grid's second dimension)
-
     const size_t nr = job.nr, n_pad = job.n_rinv;
-    constexpr int kReachListed = kLinkCounters, kReachShort = kLinkCounters + 1, kReachCounters = kLinkCounters + 2;  // the core step's two
-    d_cnt.ensure(kReachCounters);
-    d_comp.ensure(n_pad);
+    constexpr int kReachListed = kLinkCounters, kReachShort = kLinkCounters + 1;  // the core step's two counters, behind the rounds'
     d_k2.ensure(2 * n_pad);
     d_core.ensure(nr);
-    d_rows3.ensure(3 * nr);
-    d_thr.ensure(nr);
-    d_best.ensure(2 * nr);
-    d_edges.ensure(2 * nr);
-    d_out_ids.ensure((size_t)rows);
-    d_out_part.ensure((size_t)rows);
     d_out_core.ensure((size_t)rows);
-    a.rinv = job.d_rinv.p;
-    a.norm = job.d_norm.p;
-    a.comp = d_comp.p;
-    a.parent = d_rows3.p;
-    a.cert = d_rows3.p + nr;
-    a.comp_max = d_rows3.p + 2 * nr;
-    a.thr = d_thr.p;
-    a.best_key = d_best.p;
-    a.best_pair = d_best.p + nr;
-    a.edge_pair = d_edges.p;
-    a.edge_key = d_edges.p + nr;
-    a.edge_cap = nr;
-    a.counters = d_cnt.p;
-    a.seg_out0 = job.seg_out0;
-    a.out_ids = d_out_ids.p;
-    a.out_part = d_out_part.p;
     ra.core = d_core.p;
     ra.klo = d_k2.p;
     ra.khi = d_k2.p + n_pad;
-    ra.short_rows = d_cnt.p + kReachShort;
     ra.out_core = d_out_core.p;
 
     pcv_reach_stats& stats = s->reach_stats;
     stats.rows = rows;
     stats.tile_rows = tile;
     stats.min_items = min_items;
-
-    unsigned long long counts[kLinkCounters] = {}, again[kLinkCounters] = {};
-    PCV_HIP(hipMemsetAsync(d_comp.p, 0, n_pad * sizeof(uint32_t), st));
-    PCV_HIP(hipMemsetAsync(d_k2.p, 0, 2 * n_pad * sizeof(float), st));
-    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, kReachCounters * sizeof(unsigned long long), st));
-    job.prep();
-    launch_linkage_begin(st, p, a);
-    PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-    job.wait();
-    stats.prep_ms = job.elapsed(0);
-    const uint64_t P = counts[kLinkParticipating];
-    stats.participating = (int64_t)P;
-    PCV_REQUIRE(P <= (uint64_t)rows, "reach_tree: %llu participating rows of %lld", (unsigned long long)P, (long long)rows);
+    rounds.open(job, "reach_tree", a, s->Dp, 2, stats, [&] { PCV_HIP(hipMemsetAsync(d_k2.p, 0, 2 * n_pad * sizeof(float), st)); });
+    ra.short_rows = a.counters + kReachShort;
+    const uint64_t P = rounds.P;
 
     // The core step.  j = 0: every core is +inf and the neighbours have nothing to say.
     const int j = (int)std::min<uint64_t>((uint64_t)(min_items - 1), P > 0 ? P - 1 : 0);
     ra.k = j;
     if (j >= 1) {
-        NeighborArgs b{};
-        b.tile_blocks = a.tile_blocks;
-        b.k = j;
-        b.margin = a.margin;
-        b.stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / (uint32_t)std::max(64, 4 * j)));
-        const uint32_t sampled = (TB + b.stride - 1) / b.stride;
-        const uint32_t want_spans = std::min<uint32_t>(sampled, std::min<uint32_t>(kMaxNeighborSpans, (uint32_t)std::max(64, 8 * j)));
-        b.span_len = (sampled + want_spans - 1) / want_spans;
-        b.spans = (sampled + b.span_len - 1) / b.span_len;
-        b.walk_len = a.walk_len;
-        d_nbr_thr.ensure(n_pad);
-        d_span_max.ensure((size_t)b.spans * nr);
-        d_cnt_off.ensure(2 * nr + 1);
-        b.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)j * (uint64_t)rows));
-        d_cand.ensure(b.cand_cap);
-        b.rinv = job.d_rinv.p;
-        b.thr = d_nbr_thr.p;
-        b.norm = job.d_norm.p;
-        b.span_max = d_span_max.p;
-        b.row_cnt = d_cnt_off.p;
-        b.row_off = d_cnt_off.p + nr;
-        b.counters = d_cnt.p + kReachListed;
-        b.seg_out0 = job.seg_out0;
-        PCV_HIP(hipMemsetAsync(d_nbr_thr.p, 0, n_pad * sizeof(float), st));
-        PCV_HIP(hipMemsetAsync(d_span_max.p, 0, (size_t)b.spans * nr * sizeof(uint32_t), st));
-        PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
+        core.open(job, a.tile_blocks, j, a.margin, a.counters + kReachListed);
+        core.zero(st);
         job.record(1);
-        launch_neighbors_bound(st, p, dp, b);
-        launch_neighbors_threshold(st, p, b);
-        job.record(2);
-        b.stride = 1;  // the list pass: every block
         unsigned long long listed[1] = {0}, listed_again[1] = {0};
-        const Listing list = list_candidates(
-            job, 2, d_cnt.p + kReachListed, listed, listed_again, b.cand_cap, kMaxNeighborCandidates,
-            [&] {
-                b.cand = d_cand.p;
-                launch_neighbors_list(st, p, dp, b);
-            },
-            [&] { PCV_HIP(hipMemsetAsync(d_cnt.p + kReachListed, 0, sizeof(unsigned long long), st)); }, d_cand);
+        const Listing list = core.list(job, listed, listed_again);
         stats.core_ms = job.elapsed(1) + list.ms;
         const uint64_t n_core = listed[0];
         stats.core_candidates = (int64_t)n_core;
@@ -1172,147 +1181,36 @@ void reach_tree(pcv_searcher* s, const int64_t* source_ids, int n_sources, int m
             stats.reruns += 1;
             stats.core_ms += list.again_ms;
         }
-        b.n_cand = n_core;
-        d_sorted_key.ensure((size_t)std::max<uint64_t>(1, n_core));
-        d_sorted_row.ensure((size_t)std::max<uint64_t>(1, n_core));
-        b.sorted_key = d_sorted_key.p;
-        b.sorted_row = d_sorted_row.p;
-        ra.row_off = b.row_off;
-        ra.sorted_key = b.sorted_key;
-        job.record(3);
-        launch_neighbors_rescore(st, p, dp, b);
+        core.rescore(job, n_core);
+        ra.row_off = core.a.row_off;
+        ra.sorted_key = core.a.sorted_key;
         launch_reach_core(st, p, ra);
         job.record(4);
         unsigned long long short_rows = 0;
-        PCV_HIP(hipMemcpyAsync(&short_rows, d_cnt.p + kReachShort, sizeof(short_rows), hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipMemcpyAsync(&short_rows, ra.short_rows, sizeof(short_rows), hipMemcpyDeviceToHost, st));
         job.wait();
         stats.core_ms += job.elapsed(3);
         if (short_rows != 0)
             PCV_FAIL(PCV_ERR_INTERNAL, "reach_tree: %llu participating rows were left fewer than %d rescored partners", short_rows, j);
-        d_nbr_thr.release();
-        d_span_max.release();
-        d_cnt_off.release();
-        d_sorted_key.release();
-        d_sorted_row.release();
-        d_cand.release();
+        core.release();
     } else {
         launch_reach_core(st, p, ra);
     }
-    a.cand_cap = std::min<uint64_t>(kMaxLinkageCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)nr));
-    d_cand.ensure(a.cand_cap);
-    d_cand_key.ensure(a.cand_cap);
+    rounds.run(
+        job, "reach_tree", "reach", a, stats, [&] { launch_linkage_bound(st, p, dp, a, ra.klo); }, [&] { launch_linkage_list(st, p, dp, a, ra.khi); },
+        [&] { launch_reach_rescore(st, p, dp, ra); });
 
-    // PCV_LINKAGE_ROUNDS_FILE (tools/bench_reach.py): one line per round, as linkage_tree writes them
-    FILE* round_log = nullptr;
-    if (const char* f = getenv("PCV_LINKAGE_ROUNDS_FILE")) round_log = std::fopen(f, "a");
-    struct CloseLog {
-        FILE* f;
-        ~CloseLog() {
-            if (f) std::fclose(f);
-        }
-    } close_log{round_log};
-
-    uint64_t components = P, emitted = 0;
-    while (components > 1) {
-        bool bound_repeated = false;
-        // 1. the bound of every component, and its threshold
-        auto queue_bound = [&](uint32_t stride) {
-            PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkUnbounded, 0, 2 * sizeof(unsigned long long), st));
-            a.stride = stride;
-            launch_reach_bound(st, p, dp, ra);
-            launch_linkage_threshold(st, p, a);
-        };
-        PCV_HIP(hipMemsetAsync(d_rows3.p + nr, 0, 2 * nr * sizeof(uint32_t), st));  // cert, comp_max
-        PCV_HIP(hipMemsetAsync(d_best.p, 0, nr * sizeof(unsigned long long), st));
-        PCV_HIP(hipMemsetAsync(d_best.p + nr, 0xff, nr * sizeof(unsigned long long), st));
-        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st));
-        PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkRoots, 0, sizeof(unsigned long long), st));
-        job.record(0);
-        queue_bound(sample_stride);
-        if (sample_stride > 1) {
-            PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-            job.wait();
-            bound_repeated = counts[kLinkUnbounded] > 0 && counts[kLinkCertRoots] >= 2;
-            if (bound_repeated) queue_bound(1);
-        }
-        job.record(1);
-        // 2. the candidates
-        a.stride = 1;
-        const Listing list = list_candidates(
-            job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxLinkageCandidates,
-            [&] {
-                a.cand = d_cand.p;
-                a.cand_key = d_cand_key.p;
-                launch_reach_list(st, p, dp, ra);
-            },
-            [&] { PCV_HIP(hipMemsetAsync(d_cnt.p + kLinkListed, 0, sizeof(unsigned long long), st)); }, d_cand, d_cand_key);
-        const float round_bound_ms = job.elapsed(0), round_list_ms = list.ms + (list.repeated ? list.again_ms : 0.0f);
-        stats.bound_ms += round_bound_ms;
-        stats.list_ms += list.ms;
-        const uint64_t n_cand = counts[kLinkListed];
-        if (n_cand > kMaxLinkageCandidates)
-            PCV_FAIL(PCV_ERR_UNSUPPORTED,
-                     "reach_tree: round %d lists %llu candidate pairs, more than %llu (2^28): too many rows are nearly the same reach from their "
-                     "nearest foreign row, or lie outside the lengths the screen is certified for; build the tree of fewer rows",
-                     (int)stats.rounds, (unsigned long long)n_cand, (unsigned long long)kMaxLinkageCandidates);
-        if (list.repeated) {  // (the pass lists the same pairs again)
-            PCV_REQUIRE(again[kLinkListed] == n_cand, "reach_tree: the repeated list pass left %llu candidates, the first %llu", again[kLinkListed],
-                        (unsigned long long)n_cand);
-            stats.reruns += 1;
-            stats.list_ms += list.again_ms;
-        }
-        stats.candidates += (int64_t)n_cand;
-        stats.rounds += 1;
-        // 3. the f64 decision, 4. the merge
-        a.n_cand = n_cand;
-        job.record(3);
-        launch_reach_rescore(st, p, dp, ra);
-        job.record(4);
-        launch_linkage_merge(st, p, a);
-        job.record(5);
-        PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
-        job.wait();
-        stats.rescore_ms += job.elapsed(3);
-        stats.merge_ms += job.elapsed(4);
-        // 5. one edge per component that went, and at least every second one went
-        const uint64_t after = counts[kLinkRoots], now = counts[kLinkEmitted];
-        if (!(after >= 1 && after <= components / 2 && now - emitted == components - after))
-            PCV_FAIL(PCV_ERR_INTERNAL, "reach_tree: round %d went from %llu components to %llu and emitted %llu edges", (int)stats.rounds - 1,
-                     (unsigned long long)components, (unsigned long long)after, (unsigned long long)(now - emitted));
-        if (round_log)
-            std::fprintf(round_log, "%d %llu %llu %llu %d %d %.4f %.4f %.4f %.4f\n", (int)stats.rounds - 1, (unsigned long long)components,
-                         (unsigned long long)after, (unsigned long long)n_cand, bound_repeated ? 1 : 0, list.repeated ? 1 : 0, round_bound_ms, round_list_ms,
-                         job.elapsed(3), job.elapsed(4));
-        components = after;
-        emitted = now;
-    }
-    PCV_REQUIRE(emitted == (P > 0 ? P - 1 : 0), "reach_tree: %llu edges for %llu participating rows", (unsigned long long)emitted, (unsigned long long)P);
-    stats.edges = (int64_t)emitted;
-
-    a.n_edges = emitted;
+    const uint64_t emitted = rounds.emitted;
     d_out_edges.ensure((size_t)std::max<uint64_t>(1, emitted));
     ra.out_edges = d_out_edges.p;
     launch_reach_output(st, p, dp, ra);
     job.wait();
-    std::vector<ReachEdge> edges((size_t)emitted);
-    if (emitted > 0) PCV_HIP(hipMemcpy(edges.data(), d_out_edges.p, (size_t)emitted * sizeof(ReachEdge), hipMemcpyDeviceToHost));
-    std::sort(edges.begin(), edges.end(), [](const ReachEdge& x, const ReachEdge& y) {
-        if (x.w != y.w) return x.w > y.w;
-        if (x.pos_a != y.pos_a) return x.pos_a < y.pos_a;
-        return x.pos_b < y.pos_b;
-    });
-    for (size_t i = 0; i < edges.size(); ++i) {
-        out_pos_a[i] = edges[i].pos_a;
-        out_pos_b[i] = edges[i].pos_b;
-        out_w[i] = edges[i].w;
-        if (out_c) out_c[i] = edges[i].c;
-        if (out_id_a) {
-            out_id_a[i] = edges[i].id_a;
-            out_id_b[i] = edges[i].id_b;
-        }
-    }
-    if (out_ids) PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (out_part) PCV_HIP(hipMemcpy(out_part, d_out_part.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
+    const std::vector<ReachEdge> edges =
+        edges_in_order(d_out_edges, emitted, [](const ReachEdge& e) { return e.w; }, out_pos_a, out_pos_b, out_w, out_id_a, out_id_b);
+    if (out_c)
+        for (size_t i = 0; i < edges.size(); ++i) out_c[i] = edges[i].c;
+    if (out_ids) PCV_HIP(hipMemcpy(out_ids, rounds.d_out_ids.p, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (out_part) PCV_HIP(hipMemcpy(out_part, rounds.d_out_part.p, (size_t)rows * sizeof(int8_t), hipMemcpyDeviceToHost));
     if (out_core) PCV_HIP(hipMemcpy(out_core, d_out_core.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost));
     *out_edges = (int64_t)emitted;
 }

@@ -314,7 +314,8 @@ enum : int {
 
 // Reach tree (pcv_searcher_reach_tree; DESIGN.md §4 "Reach tree"): the spanning tree under w(a, b) = min(core(a), core(b), c(a, b)),
 // in the linkage rounds with the cap applied.  `l` is the linkage call's block, read by the linkage kernels the rounds share (begin,
-// cert, threshold, merge) and by the kernels of reach_kernels.hip; there cand_key, best_key and edge_key hold images of w, not of c.
+// cert, the screen — given klo / khi —, threshold, choose, merge) and by the kernels of reach_kernels.hip; there cand_key, best_key
+// and edge_key hold images of w, not of c.
 //   core[launch row]     : the j-th largest c of the row with another participating row, f64; +inf for j == 0; NaN: no part
 //   klo, khi[launch row] : core rounded down and up to f32 (-inf for a row that takes no part); zero behind total_blocks * 32
 //   row_off, sorted_key  : what the neighbours' rescore step left (NeighborArgs), read by the core step alone;  k = j
@@ -361,17 +362,17 @@ void launch_density_core(hipStream_t st, const ScanParams& p, const DensityArgs&
 void launch_density_link(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);     // sure pairs, conf -> parent, attach
 void launch_density_labels(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);   // parent, attach -> outputs
 // ---- linkage tree (linkage_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+// The bound and list passes take the reach tree's cap: klo / khi of ReachArgs (the capped screen), or null (the linkage tree's).
 void launch_linkage_begin(hipStream_t st, const ScanParams& p, const LinkageArgs& a);                          // comp, parent = the row; participating
-void launch_linkage_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);     // comp -> cert, comp_max
+void launch_linkage_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a, const float* klo = nullptr);  // comp -> cert, comp_max
 void launch_linkage_threshold(hipStream_t st, const ScanParams& p, const LinkageArgs& a);                      // comp_max -> thr, counters
-void launch_linkage_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);      // thr, comp -> cand
+void launch_linkage_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a, const float* khi = nullptr);   // thr, comp -> cand
 void launch_linkage_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);   // cand -> best_key, best_pair
+void launch_linkage_choose(hipStream_t st, const LinkageArgs& a);                                              // cand_key, best_key -> best_pair (the rescore step's second half)
 void launch_linkage_merge(hipStream_t st, const ScanParams& p, const LinkageArgs& a);                          // best_pair -> edges, parent, comp, roots
 void launch_linkage_output(hipStream_t st, const ScanParams& p, const ScanParams* dp, const LinkageArgs& a);    // edges, rinv -> outputs
 // ---- reach tree (reach_kernels.hip); the core step's candidates are the neighbours', the other steps of a round the linkage tree's ----
 void launch_reach_core(hipStream_t st, const ScanParams& p, const ReachArgs& a);                               // sorted_key -> core, klo, khi
-void launch_reach_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);         // comp, klo -> cert, comp_max
-void launch_reach_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);          // thr, comp, khi -> cand
 void launch_reach_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);       // cand, core -> best_key, best_pair
 void launch_reach_output(hipStream_t st, const ScanParams& p, const ScanParams* dp, const ReachArgs& a);        // edges, rinv, core -> outputs
 // ---- seed items (seed_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----

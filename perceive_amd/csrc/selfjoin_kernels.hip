@@ -15,12 +15,11 @@
 //                               the arithmetic of distinct_select_kernel), kept iff c >= threshold.
 #include "device_access.h"
 #include "launch_rows.h"
+#include "pair_screen.h"
 #include "row_jobs.h"
 
 namespace pcv {
 namespace {
-
-constexpr int kJoinWaves = 8;  // waves of a screen workgroup: one tile in LDS per CU, two waves per SIMD
 
 __global__ __launch_bounds__(256) void selfjoin_prep_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
     const ScanParams& p = *pp;
@@ -41,170 +40,75 @@ __global__ __launch_bounds__(256) void selfjoin_prep_kernel(const ScanParams* __
     gst(&a.norm[i], n);
 }
 
+// The epilogue of the duplicate screen: a pair with s >= the screening threshold (or a wild row: every pair, scan.h) is listed; in a
+// block of the tile's own only with row a before row b.
+template <int NT>
+struct JoinPolicy {
+    const SelfJoinArgs& a;
+    __device__ __forceinline__ void begin(uint32_t, int) {}
+    __device__ __forceinline__ void prefetch(uint32_t, int, int) {}
+    __device__ __forceinline__ void end(const float (&)[NT], int, int) {}
+    __device__ __forceinline__ void block(const f32x16 (&acc)[NT], const float (&ra)[NT], const f32x4 (&rb)[4], const PairWhere& at) {
+        const float thr = a.screen_threshold;
+        const bool diagonal = at.gb < at.tb0 + NT;  // the block is one of the tile's own: row a before row b only
+        auto passes = [&](int t, int i) -> bool {
+            const float rbi = rb[i >> 2][i & 3];
+            const float s = acc[t][i] * ra[t] * rbi;
+            bool ok = (ra[t] > 0.0f && rbi > 0.0f) ? s >= thr : (ra[t] != 0.0f && rbi != 0.0f);
+            if (diagonal) ok = ok && at.owner_row(t) < at.partner_row(i);
+            return ok;
+        };
+        bool any = false;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) any |= passes(t, i);
+        if (!__any(any)) return;  // (the common case)
+        uint32_t mask[NT];
+        uint32_t n = 0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            mask[t] = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mask[t] |= passes(t, i) ? (1u << i) : 0u;
+            n += (uint32_t)__builtin_popcount(mask[t]);
+        }
+        if (n) {
+            unsigned long long k = g_atomic_add64(&a.counters[0], n);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                uint32_t m = mask[t];
+                while (m) {
+                    const int i = __builtin_ctz(m);
+                    m &= m - 1;
+                    if (k < a.cand_cap) gst(&a.cand[k], ((uint64_t)at.owner_row(t) << 32) | at.partner_row(i));
+                    ++k;
+                }
+            }
+        }
+    }
+};
+
 // grid: x = tile (tile_blocks = NT consecutive blocks), y = span: the blocks [tile's first + y * span_blocks, + span_blocks) of the
 // launch, cut at its end.  A (tile, span) that starts behind the end has nothing to do.  Consecutive workgroups stream nearly the
-// same blocks, NT blocks apart: what one brings into the L2 the next ones find there.
-// D[row of the streamed block][row of the tile]: lane (c = lane & 31, h = lane >> 5) holds tile rows 32 t + c and, in
-// accumulator i, block row (i & 3) + 8 (i >> 2) + 4 h.
+// same blocks, NT blocks apart: what one brings into the L2 the next ones find there.  Wave w takes the blocks first + w,
+// first + w + kScreenWaves, ...  Staging, stream and accumulator layout: pair_screen.h.
 template <int NT>
-__global__ __launch_bounds__(kJoinWaves * 64) void selfjoin_screen_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
+__global__ __launch_bounds__(kScreenWaves * 64) void selfjoin_screen_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
     const ScanParams& p = *pp;
-    extern __shared__ uint4 lq[];  // [NT*32][Dp/8] 16-byte pieces of 8 bf16, swizzled
+    extern __shared__ uint4 lq[];
     __shared__ const float4* tbase[NT];
-    const int D4 = p.D4, P8 = D4 >> 1, NCH = D4 >> 4;
     const uint32_t TB = p.total_blocks;
     const uint32_t tb0 = blockIdx.x * NT;
     const uint64_t first = (uint64_t)tb0 + (uint64_t)blockIdx.y * a.span_blocks;
     if (first >= TB) return;  // (the whole workgroup)
     const uint32_t b0 = (uint32_t)first;
     const uint32_t b1 = (uint32_t)min((uint64_t)TB, first + a.span_blocks);
-
-    if (threadIdx.x < NT) {
-        const uint32_t gb = tb0 + threadIdx.x;
-        const float4* base = nullptr;
-        if (gb < TB) {
-            const SegDesc& sg = p.seg[find_seg(p, gb)];
-            base = gld(&sg.blk) + (size_t)(gb - gld(&sg.blk0)) * D4 * 32;
-        }
-        tbase[threadIdx.x] = base;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NT * 32 * P8; i += kJoinWaves * 64) {
-        const int r = i & 31, rest = i >> 5;
-        const int tb = rest / P8, pc = rest - tb * P8;
-        const float4* base = tbase[tb];
-        bf16x8 v8 = {};
-        if (base) {
-            const float4 lo = gld4(base + (size_t)(2 * pc) * 32 + r), hi = gld4(base + (size_t)(2 * pc + 1) * 32 + r);
-            const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            v8 = __builtin_convertvector(v, bf16x8);
-        }
-        const int row = tb * 32 + r;
-        lq[row * P8 + swizzle_piece(pc, row, P8)] = __builtin_bit_cast(uint4, v8);
-    }
-    __syncthreads();
-
-    const int lane = threadIdx.x & 63;
+    pair_stage_tile<NT>(p, lq, tbase, tb0);
     const uint32_t wave = uniform(threadIdx.x >> 6);
-    const int c = lane & 31, h = lane >> 5;
     if (b0 + wave >= b1) return;
-    float ra[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) ra[t] = gld(&a.rinv[(size_t)(tb0 + t) * 32 + c]);  // (zero behind the launch's last block)
-    const float thr = a.screen_threshold;
-
-    f32x16 acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-
-    auto enter_block = [&](JoinCursor& k, uint32_t gb) {
-        k.gb = gb;
-        k.ch = 0;
-        if (gb < b1) {
-            join_seek(p, k.sc, gb);
-            k.rows = row_rsrc(k.sc.blk + (size_t)(gb - k.sc.begin) * D4 * 32, (uint32_t)D4 * 512u);
-        }
-    };
-    const uint32_t lane_off = (uint32_t)(h * 64 + c) * 16u;  // the lane's bytes inside a block
-    JoinCursor cons, prod;
-    enter_block(cons, b0 + wave);
-    prod = cons;
-
-    float4 buf[2][8];
-    // (always issues its loads: past the end of the wave's stream they read a chunk of its last block again — scan_mfma_kernel)
-    auto produce = [&](float4 (&b)[8]) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) b[i] = ld_piece<false>(prod.rows, lane_off + (uint32_t)((i >> 1) * 4 + (i & 1)) * 512u, (uint32_t)prod.ch * 8192u);
-        if (prod.gb < b1 && ++prod.ch == NCH) enter_block(prod, prod.gb + kJoinWaves);
-    };
-
-    f32x4 rb[4];  // rinv of the block's rows 8 j + 4 h + (0..3): accumulators 4 j + (0..3)
-    auto rb_prefetch = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rb[j] = *(const PCV_GLOBAL f32x4*)(a.rinv + (size_t)cons.gb * 32 + 8 * j + 4 * h);
-    };
-
-    auto passes = [&](int t, int i, bool diagonal) -> bool {
-        const float rbi = rb[i >> 2][i & 3];
-        const float s = acc[t][i] * ra[t] * rbi;
-        bool ok = (ra[t] > 0.0f && rbi > 0.0f) ? s >= thr : (ra[t] != 0.0f && rbi != 0.0f);  // (a wild row: every pair, scan.h)
-        if (diagonal) ok = ok && (tb0 + t) * 32u + (uint32_t)c < cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h);
-        return ok;
-    };
-
-    auto epilogue = [&]() {
-        if (NCH < 2) rb_prefetch();
-        const bool diagonal = cons.gb < tb0 + NT;  // the block is one of the tile's own: row a before row b only
-        bool any = false;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) any |= passes(t, i, diagonal);
-        if (__any(any)) {  // rare
-            uint32_t mask[NT];
-            uint32_t n = 0;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                mask[t] = 0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) mask[t] |= passes(t, i, diagonal) ? (1u << i) : 0u;
-                n += (uint32_t)__builtin_popcount(mask[t]);
-            }
-            if (n) {
-                unsigned long long at = g_atomic_add64(&a.counters[0], n);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    uint32_t m = mask[t];
-                    while (m) {
-                        const int i = __builtin_ctz(m);
-                        m &= m - 1;
-                        if (at < a.cand_cap)
-                            gst(&a.cand[at], ((uint64_t)((tb0 + t) * 32u + (uint32_t)c) << 32) | (cons.gb * 32u + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h)));
-                        ++at;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-    };
-
-    auto consume = [&](const float4 (&b)[8]) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const f32x8 v = {b[2 * ks].x, b[2 * ks].y, b[2 * ks].z, b[2 * ks].w, b[2 * ks + 1].x, b[2 * ks + 1].y, b[2 * ks + 1].z, b[2 * ks + 1].w};
-            const bf16x8 av = __builtin_convertvector(v, bf16x8);
-            const int pc = 2 * (cons.ch * 4 + ks) + h;
-            const int ph = swizzle_piece(pc, c, P8);  // (tile row 32 t + c: the same low four bits as c)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const bf16x8 q8 = *(const bf16x8*)&lq[(32 * t + c) * P8 + ph];
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, q8, acc[t], 0, 0, 0);
-            }
-        }
-        if (++cons.ch == NCH) {
-            epilogue();
-            enter_block(cons, cons.gb + kJoinWaves);
-        }
-    };
-
-    // one chunk of loads in flight while one feeds the matrix cores (every buf[] index a literal, or the array moves to scratch);
-    // the block's rinv values are requested one chunk ahead of the epilogue and before that step's row loads
-#define PCV_JOIN_STEP(REFILL, CONS)                      \
-    if (NCH >= 2 && cons.ch == NCH - 2) rb_prefetch();   \
-    produce(buf[REFILL]);                                \
-    consume(buf[CONS]);                                  \
-    if (cons.gb >= b1) return;
-    produce(buf[0]);
-    while (true) {
-        PCV_JOIN_STEP(1, 0)
-        PCV_JOIN_STEP(0, 1)
-    }
-#undef PCV_JOIN_STEP
+    JoinPolicy<NT> pol{a};
+    pair_stream<NT>(p, lq, a.rinv, tb0, b0 + wave, b1, kScreenWaves, pol);
 }
 
 __global__ __launch_bounds__(256) void selfjoin_rescore_kernel(const ScanParams* __restrict__ pp, const SelfJoinArgs a) {
@@ -221,12 +125,8 @@ __global__ __launch_bounds__(256) void selfjoin_rescore_kernel(const ScanParams*
     if (!(cc >= a.threshold)) return;
     const unsigned long long at = g_atomic_add64(&a.counters[1], 1ull);
     if (at >= a.pair_cap) return;
-    auto id_of = [](const RowRef& r) {
-        const int64_t* ids = gld(&r.sg->ids);
-        return ids ? gld(&ids[r.row]) : gld(&r.sg->id0) + (int64_t)r.row;
-    };
     const int64_t pa = gld(&ra.sg->pos0) + (int64_t)ra.row, pb = gld(&rb.sg->pos0) + (int64_t)rb.row;
-    const int64_t ia = id_of(ra), ib = id_of(rb);
+    const int64_t ia = row_id(ra), ib = row_id(rb);
     const bool fwd = pa < pb;
     DupPair* out = &a.pairs[at];
     gst(&out->c, cc);
@@ -261,7 +161,7 @@ void launch_selfjoin_screen(hipStream_t st, const ScanParams& p, const ScanParam
     const dim3 grid(tiles, spans);
 #define PCV_JOIN(N)                                                        \
     allow_dynamic_lds((const void*)selfjoin_screen_kernel<N>, lds);        \
-    selfjoin_screen_kernel<N><<<grid, kJoinWaves * 64, lds, st>>>(dp, a);
+    selfjoin_screen_kernel<N><<<grid, kScreenWaves * 64, lds, st>>>(dp, a);
     if (NT == 4) {
         PCV_JOIN(4)
     } else if (NT == 2) {
