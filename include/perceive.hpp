@@ -158,6 +158,35 @@ inline std::vector<SearchItem> search_distinct_handle(pcv_searcher* h, const std
     return out;
 }
 
+// One pick of search_vector_diverse: the item, the marginal value it was picked at and its place in the ranked list of search_vector.
+struct DiverseItem {
+    SearchItem item;
+    double marginal;
+    int32_t rank;
+};
+// Diverse results on a searcher or a view handle (pcv_searcher_search_diverse): exact greedy maximal marginal relevance over the
+// first `pool` entries of the ranked list of search_vector (0: the default, min(PCV_MAX_DIVERSE_POOL, max(128, 8 * num_results))).
+// Each pick maximises lambda * relevance - (1 - lambda) * (largest cosine with an item already picked), ties to the better rank;
+// the picks come in pick order.  `exact`, if given: the picks are provably those of the same walk over the whole list.
+inline std::vector<DiverseItem> search_diverse_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results,
+                                                      const std::vector<float>& vector, float lambda, size_t pool, bool* exact) {
+    if (exact) *exact = true;
+    if (sources.empty() || num_results == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    if (pool == 0) pool = std::min<size_t>(PCV_MAX_DIVERSE_POOL, std::max<size_t>(128, 8 * num_results));
+    std::vector<int64_t> ids(num_results);
+    std::vector<float> scores(num_results);
+    std::vector<double> marginal(num_results);
+    std::vector<int32_t> ranks(num_results);
+    int32_t count = 0;
+    uint8_t ex = 0;
+    check(pcv_searcher_search_diverse(h, vector.data(), 1, sources.data(), (int)sources.size(), (int)num_results, lambda, (int)pool,
+                                      ids.data(), scores.data(), marginal.data(), ranks.data(), &count, nullptr, &ex));
+    std::vector<DiverseItem> out;
+    for (int i = 0; i < count; ++i) out.push_back({{ids[(size_t)i], scores[(size_t)i]}, marginal[(size_t)i], ranks[(size_t)i]});
+    if (exact) *exact = ex != 0;
+    return out;
+}
+
 // One hit of search_vector_grouped: the best member of a group, the group's key (PCV_NO_GROUP: an item without a group, which is
 // a group of its own) and the examined items collapsed into it.
 struct GroupedItem {
@@ -573,6 +602,11 @@ public:
                                                    float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
         return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
     }
+    // a diverse set of the view's best items: greedy MMR on the device (search_diverse_handle)
+    std::vector<DiverseItem> search_vector_diverse(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   float lambda, size_t pool = 0, bool* exact = nullptr) const {
+        return search_diverse_handle(h_, sources, num_results, vector, lambda, pool, exact);
+    }
     // the view's best groups, one item each, by the parent's group table (search_grouped_handle)
     std::vector<GroupedItem> search_vector_grouped(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
                                                    size_t pool = 0, bool* more = nullptr) const {
@@ -742,6 +776,11 @@ public:
     std::vector<SearchItem> search_vector_distinct(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
                                                    float threshold, size_t pool = 0, std::vector<int32_t>* similar = nullptr) const {
         return search_distinct_handle(h_, sources, num_results, vector, threshold, pool, similar);
+    }
+    // a diverse set of the best items: greedy MMR on the device (search_diverse_handle)
+    std::vector<DiverseItem> search_vector_diverse(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   float lambda, size_t pool = 0, bool* exact = nullptr) const {
+        return search_diverse_handle(h_, sources, num_results, vector, lambda, pool, exact);
     }
     // the group table (pcv_searcher_set_groups): item ids[i] belongs to group groups[i] (>= 0; PCV_NO_GROUP ungroups); the last
     // occurrence of an id holds.  Keyed by id: it survives remove_items and rebuild_source.

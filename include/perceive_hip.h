@@ -481,6 +481,51 @@ pcv_status pcv_searcher_search_grouped(pcv_searcher* s, const float* queries, in
                                        int num_results, int pool, int64_t* out_ids, float* out_scores, int64_t* out_groups,
                                        int32_t* out_counts, int32_t* out_collapsed, int32_t* out_examined, uint8_t* out_more);
 
+/* Diverse results: exact greedy maximal marginal relevance (MMR), selected on the device — the graded form of what
+ * pcv_searcher_search_distinct and pcv_searcher_search_grouped do all-or-nothing.  Per query:
+ *   L      the ranked list pcv_searcher_search returns (canonical score, ties -> lower position; the searchable rows of the selected
+ *          sources: hidden rows and a view's restriction apply as everywhere; a row without a canonical score never appears).
+ *   P      the pool: the first min(pool, |L|) entries of L.  The RANK of an entry is its index in L, from 0.
+ *   rel_i  relevance, from the canonical f64 score c_i: cosine metric c_i; dot metric c_i / (double)dim, one f64 division (the
+ *          similarity whose complement that metric reports as distance, without the clamp).
+ *   div_i  redundancy: the largest cos(i, j) over the rows j picked so far, 0 while nothing is picked.  cos is the canonical cosine
+ *          of the two stored f32 rows for BOTH metrics, exactly the dup arithmetic of pcv_searcher_search_distinct — f64, products
+ *          exact, sums in feature order — and symmetric bit for bit.  A pair without a cosine (a norm that is zero or not finite)
+ *          counts as cos = 0.
+ *   m_i    marginal value: with l = (double)lambda and u = 1.0 - l in f64,  m_i = fl(fl(l * rel_i) - fl(u * div_i)) — three separate
+ *          roundings, no fused multiply-add.
+ * The walk, num_results times or until P is used up: pick the entry of P not yet picked with the largest m_i, ties -> lower rank.
+ * The first pick is therefore always L[0], and lambda = 1 gives the plain top-num_results.
+ *   lambda       in [0, 1]: 1 is relevance alone, 0 is diversity alone (after L[0])
+ *   pool         num_results .. PCV_MAX_DIVERSE_POOL: entries of L the walk chooses among
+ *   out_ids      [n_queries][num_results] the picks in pick order, -1 behind them
+ *   out_scores   likewise, NaN behind the picks (may be NULL): the reported f32 score, bit for bit what pcv_searcher_search gives
+ *                for that row
+ *   out_marginal [n_queries][num_results] f64: m of each pick at the moment it was picked, NaN behind the picks (may be NULL)
+ *   out_ranks    [n_queries][num_results] rank of each pick in L, -1 behind the picks (may be NULL)
+ *   out_counts   [n_queries] picks made = min(num_results, |P|)
+ *   out_examined [n_queries] |P| (may be NULL)
+ *   out_exact    [n_queries] 1: the picks are provably those the same walk over ALL of L would make (may be NULL).  A 1 is a proof,
+ *                a 0 is no disproof.  Set in exactly two cases: (a) |P| < pool — the list ended inside the pool; (b) every pick has
+ *                m_t > fl(fl(l * rel_last) + fl(u * d0)), rel_last the relevance of P's last entry and d0 = 1 + 2^-40: every row
+ *                outside P has rel <= rel_last, no canonical cosine falls below -d0 (the f64 quotient may round a few ulps past
+ *                -1), and rounding is monotone, so no outside row can reach m_t at any step.  (b) needs no extra pass; where
+ *                |L| == pool exactly and (b) fails the flag is 0.
+ * A NULL searcher, no queries, num_results outside [1, PCV_MAX_RESULTS], pool outside [num_results, PCV_MAX_DIVERSE_POOL] or a
+ * lambda that is NaN or outside [0, 1] give PCV_ERR_INVALID before any device work; a searcher with pending rows fails as in
+ * pcv_searcher_search.  A call makes ceil(pool / PCV_MAX_RESULTS) passes per group of queries (fewer where every list ends
+ * sooner: nothing else stops a query early), each followed by a collect step that gathers the pass's rows, and one select launch
+ * per group (DESIGN.md §4 "Diverse results"); the host reads back the result block and one record per query.  The gathered rows
+ * take pool x padded row bytes per query, at most 512 MB a group: wide rows and large pools take fewer queries a group, and what
+ * exceeds 64 MB is given back when the call ends.  Works on views (a view walks its own rows).
+ * Not in scope: a sharded form (the walk needs the rows of every shard's hits), device-resident output, a duplicate threshold
+ * combined with lambda, and group-aware diversity. */
+enum { PCV_MAX_DIVERSE_POOL = 4096 };
+pcv_status pcv_searcher_search_diverse(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                       int num_results, float lambda, int pool, int64_t* out_ids, float* out_scores,
+                                       double* out_marginal, int32_t* out_ranks, int32_t* out_counts, int32_t* out_examined,
+                                       uint8_t* out_exact);
+
 /* Duplicate pairs: the exact self-join of the corpus on the device — every pair of searchable rows that are near-duplicates of each
  * other, found once and corpus-wide (what pcv_searcher_search_distinct collapses per query, for pcv_searcher_remove_ids /
  * pcv_searcher_hide_ids to act on).

@@ -291,6 +291,7 @@ SYMBOLS = {
     "pcv_searcher_get_groups": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
     "pcv_searcher_group_stats": (C.c_int, [_P, C.POINTER(GroupStats)]),
     "pcv_searcher_search_grouped": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _I64P, _INTP, _INTP, _INTP, _U8P]),
+    "pcv_searcher_search_diverse": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int, _I64P, _F32P, _F64P, _INTP, _INTP, _INTP, _U8P]),
     "pcv_searcher_find_duplicates": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_last_duplicate_stats": (C.c_int, [_P, C.POINTER(DuplicateStats)]),
     "pcv_searcher_assign": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int64, _INTP, _F32P, _I64P, _I64P, C.POINTER(C.c_int64)]),

@@ -112,24 +112,30 @@ __device__ __forceinline__ int swizzle_piece(int pc, int q, int P8) {
     return pc < (P8 & ~15) ? ((pc & ~15) | ((pc ^ q) & 15)) : ((pc & ~7) | ((pc ^ q) & 7));
 }
 
-// The feature-order f64 sums of row x with rows y[0..NU) (D4 pieces of four features each, `stride` float4 apart): the canonical
-// dot product and, for y == x, the canonical |x|^2.  The product of two f32 is exact in f64, so every step is one rounding.
+// The feature-order f64 sums of row x with rows y[0..NU) (D4 pieces of four features each, those of x `xstride` float4 apart and
+// those of every y `ystride`): the canonical dot product and, for y == x, the canonical |x|^2.  The product of two f32 is exact
+// in f64, so every step is one rounding.
 template <int NU>
-__device__ __forceinline__ void pair_sums(const float4* x, const float4* (&y)[NU], int D4, double (&acc)[NU], size_t stride = 1) {
+__device__ __forceinline__ void pair_sums(const float4* x, size_t xstride, const float4* (&y)[NU], size_t ystride, int D4, double (&acc)[NU]) {
 #pragma unroll
     for (int u = 0; u < NU; ++u) acc[u] = 0.0;
 #pragma unroll 4
     for (int f = 0; f < D4; ++f) {
-        const float4 v = x[(size_t)f * stride];
+        const float4 v = x[(size_t)f * xstride];
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
-            const float4 w = y[u][(size_t)f * stride];
+            const float4 w = y[u][(size_t)f * ystride];
             acc[u] += (double)v.x * (double)w.x;
             acc[u] += (double)v.y * (double)w.y;
             acc[u] += (double)v.z * (double)w.z;
             acc[u] += (double)v.w * (double)w.w;
         }
     }
+}
+// ... both sides `stride` apart
+template <int NU>
+__device__ __forceinline__ void pair_sums(const float4* x, const float4* (&y)[NU], int D4, double (&acc)[NU], size_t stride = 1) {
+    pair_sums<NU>(x, stride, y, stride, D4, acc);
 }
 
 }  // namespace

@@ -22,6 +22,7 @@
 // 128 rows of 384 f32 are 192 KB and the kept rows as many again: the tiles are what fits the 160 KB of a CU (two tiles of
 // 32 rows: 97 KB at 384-d; 2 rows a tile at 8192-d).
 #include "device_access.h"
+#include "row_gather.h"
 #include "scan.h"
 
 namespace pcv {
@@ -43,41 +44,7 @@ struct DistinctLds {
     int64_t last_pos;
 };
 
-// Row `pos` (a global position, as a hit carries it) in the segments of the pass: the address of its first piece.
-__device__ __forceinline__ uint64_t row_start(const ScanParams& p, int64_t pos) {
-    for (int i = 0; i < p.nseg; ++i) {
-        const SegDesc& sg = p.seg[i];
-        const int64_t pos0 = gld(&sg.pos0);
-        const uint32_t nrows = gld(&sg.nrows);
-        if (pos >= pos0 && pos < pos0 + (int64_t)nrows) {
-            const uint32_t row = (uint32_t)(pos - pos0);
-            return (uint64_t)(gld(&sg.blk) + (size_t)(row >> 5) * p.D4 * 32 + (row & 31));
-        }
-    }
-    return 0;
-}
-
-// n rows into a tile: a wave takes rows wave, wave + 4, ...; four rows' pieces are requested before any is stored
-__device__ __forceinline__ void stage_rows(float4* tile, const uint64_t* src, int n, int D4, int tid) {
-    const int lane = tid & 63, wave = tid >> 6, W = D4 + 1;
-    for (int r0 = wave; r0 < n; r0 += 16) {
-        for (int f = lane; f < D4; f += 64) {
-            float4 t[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int r = r0 + 4 * u;
-                const float4* s = r < n ? (const float4*)src[r] : nullptr;
-                t[u] = s ? gld4(s + (size_t)f * 32) : make_float4(0, 0, 0, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int r = r0 + 4 * u;
-                if (r < n) tile[(size_t)r * W + f] = t[u];
-            }
-        }
-    }
-}
-
+// (where a hit's row starts in the blocked layout and the gather into a tile: row_start / stage_rows, row_gather.h)
 // (the feature-order f64 sums of a row of tile X with rows of tile Y: pair_sums, device_access.h)
 // One workgroup per query.  R: rows of a tile, a power of two <= kDistinctRows; NU: chains a thread runs (R * R / 256, at least 1).
 template <int NU>

@@ -267,6 +267,28 @@ struct GroupedArgs {
     int num_results;
 };
 
+// Diverse results (pcv_searcher_search_diverse; DESIGN.md §4 "Diverse results"): the first `pool` entries of a query's ranked list
+// are collected pass by pass — position, canonical score, id, and the row itself in a compact scratch —, then one select launch
+// makes the greedy MMR walk over them.  The walk's record between the passes is DistinctRec (examined: entries collected so far;
+// kept: picks, written by the select step; flags: kDistinctEnd — the list ended).
+//   rows : the scratch, piece-major per query: piece f (four features) of pool entry e of query q at rows[(q * D4 + f) * cap + e],
+//          so that threads that own consecutive entries read consecutive 16-byte pieces
+struct DiverseArgs {
+    DistinctRec* rec;        // [B]
+    DistinctRec* rec_host;   // [B] pinned host mirror, written after every pass and by the select step
+    pcv_hit_dev* entries;    // [B][cap] the pool, in list order
+    float4* rows;            // [B][D4][cap] their rows
+    int64_t* out_id;         // [B][kMaxK] the picks, in pick order
+    double* out_score;       // [B][kMaxK] their canonical scores
+    double* out_marginal;    // [B][kMaxK] m of each pick at the moment it was picked
+    int32_t* out_rank;       // [B][kMaxK] their ranks in the list
+    uint32_t* out_exact;     // [B] the certificate (perceive_hip.h)
+    int cap;                 // pool entries the lists have room for per query (a multiple of 64, >= pool)
+    int pool, num_results;
+    int walked;              // entries every unfinished query has collected before this pass
+    double lambda;
+};
+
 // float <-> order-preserving uint32 key (for atomicMax / CAS on scores)
 __host__ __device__ static inline uint32_t f32_key(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
@@ -316,6 +338,9 @@ void launch_range_thresholds(hipStream_t st, const ScanParams& p, const ScanPara
 void launch_range_select(hipStream_t st, const ScanParams& p, const ScanParams* dp);
 // ---- distinct results (distinct_kernels.hip): walks the p.k hits per query the pass left in p.out ----
 void launch_distinct_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DistinctArgs& a);
+// ---- diverse results (diverse_kernels.hip): collect appends the p.k hits per query the pass left in p.out; select walks the pool ----
+void launch_diverse_collect(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DiverseArgs& a);
+void launch_diverse_select(hipStream_t st, int B, int D, int D4, int metric, const DiverseArgs& a);
 // ---- grouped results (grouped_kernels.hip): likewise, against the group table ----
 void launch_grouped_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const GroupedArgs& a);
 void launch_reset_scan_state(hipStream_t st, uint32_t* tau, uint32_t* slots, uint32_t* cand_cnt);

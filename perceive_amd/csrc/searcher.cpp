@@ -2114,6 +2114,115 @@ void search_distinct(pcv_searcher* s, const float* queries, int n_queries, const
     }
 }
 
+// ---- diverse results (pcv_searcher_search_diverse; DESIGN.md §4 "Diverse results") ----
+// The state block of one group of up to kMfmaQueries queries: the walk's records and the result block, the same layout on both
+// sides.  (The pool lists and the row scratch are sized by the call and live beside it: scan.h, DiverseArgs.)
+struct DiverseLayout {
+    static constexpr size_t Q = kMfmaQueries;
+    static constexpr size_t off_rec = 0;
+    static constexpr size_t off_id = off_rec + Q * sizeof(DistinctRec);
+    static constexpr size_t off_score = off_id + Q * kMaxK * sizeof(int64_t);
+    static constexpr size_t off_marginal = off_score + Q * kMaxK * sizeof(double);
+    static constexpr size_t off_rank = off_marginal + Q * kMaxK * sizeof(double);
+    static constexpr size_t off_exact = off_rank + Q * kMaxK * sizeof(int32_t);
+    static constexpr size_t total = off_exact + Q * sizeof(uint32_t);
+};
+// The rows of a group's pools are gathered into one compact scratch of at most kDiverseScratchBytes: a group is as many queries
+// as fit (64 at 384-d and the largest pool), one at least.  What exceeds kDiverseKeptBytes is given back when the call ends.
+constexpr size_t kDiverseScratchBytes = (size_t)512 << 20;
+constexpr size_t kDiverseKeptBytes = (size_t)64 << 20;
+
+// The first `pool` entries of every query's ranked list are collected kMaxK hits a pass (walk_ranked_lists: nothing stops a query
+// early but the end of its list), diverse_collect_kernel appending each pass's hits and their rows to the query's pool; then one
+// launch of diverse_select_kernel makes the greedy walk of the whole group.  What comes back is one record per query after each
+// pass and the result block once.
+void search_diverse(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, int k, float lambda,
+                    int pool, int64_t* out_ids, float* out_scores, double* out_marginal, int32_t* out_ranks, int32_t* out_counts,
+                    int32_t* out_examined, uint8_t* out_exact) {
+    check_search_args(s, queries, n_queries, k, "search_diverse");
+    s->stats = pcv_scan_stats{};  // (also when the kernel is refused)
+    const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries);
+    auto blank = [&](int q, int from) {
+        for (int j = from; j < k; ++j) {
+            if (out_ids) out_ids[(size_t)q * k + j] = -1;
+            if (out_scores) out_scores[(size_t)q * k + j] = NAN;
+            if (out_marginal) out_marginal[(size_t)q * k + j] = NAN;
+            if (out_ranks) out_ranks[(size_t)q * k + j] = -1;
+        }
+    };
+    if (!open_search(s, plan)) {
+        for (int q = 0; q < n_queries; ++q) {
+            blank(q, 0);
+            if (out_counts) out_counts[q] = 0;
+            if (out_examined) out_examined[q] = 0;
+            if (out_exact) out_exact[q] = 1;  // (the list ended inside the pool)
+        }
+        return;
+    }
+    using L = DiverseLayout;
+    hipStream_t st = s->ctx->stream;
+    const size_t cap = ((size_t)pool + 63) / 64 * 64;
+    const size_t row_bytes = cap * (size_t)s->D4 * sizeof(float4);  // of one query's pool
+    const int group = (int)std::min<size_t>((size_t)std::min(plan.qstep, n_queries), std::max<size_t>(1, kDiverseScratchBytes / row_bytes));
+    const auto trim = at_exit([&] {
+        if (s->d_diverse_rows.n * sizeof(float4) <= kDiverseKeptBytes) return;
+        (void)hipStreamSynchronize(st);  // (a call that failed may have left its kernels in flight)
+        s->d_diverse_rows.release();
+    });
+    s->d_diverse.ensure(L::total);
+    s->pin_diverse.ensure(L::total);
+    s->d_diverse_entries.ensure((size_t)group * cap);
+    s->d_diverse_rows.ensure((size_t)group * cap * (size_t)s->D4);
+    DistinctRec* rec = reinterpret_cast<DistinctRec*>(s->pin_diverse.p + L::off_rec);
+    DiverseArgs args{};
+    args.rec = reinterpret_cast<DistinctRec*>(s->d_diverse.p + L::off_rec);
+    args.rec_host = rec;
+    args.entries = s->d_diverse_entries.p;
+    args.rows = s->d_diverse_rows.p;
+    args.out_id = reinterpret_cast<int64_t*>(s->d_diverse.p + L::off_id);
+    args.out_score = reinterpret_cast<double*>(s->d_diverse.p + L::off_score);
+    args.out_marginal = reinterpret_cast<double*>(s->d_diverse.p + L::off_marginal);
+    args.out_rank = reinterpret_cast<int32_t*>(s->d_diverse.p + L::off_rank);
+    args.out_exact = reinterpret_cast<uint32_t*>(s->d_diverse.p + L::off_exact);
+    args.cap = (int)cap;
+    args.pool = pool;
+    args.num_results = k;
+    args.lambda = (double)lambda;
+    const int64_t* r_id = reinterpret_cast<const int64_t*>(s->pin_diverse.p + L::off_id);
+    const double* r_score = reinterpret_cast<const double*>(s->pin_diverse.p + L::off_score);
+    const double* r_marginal = reinterpret_cast<const double*>(s->pin_diverse.p + L::off_marginal);
+    const int32_t* r_rank = reinterpret_cast<const int32_t*>(s->pin_diverse.p + L::off_rank);
+    const uint32_t* r_exact = reinterpret_cast<const uint32_t*>(s->pin_diverse.p + L::off_exact);
+    for (int q0 = 0; q0 < n_queries; q0 += group) {
+        const int B = std::min(group, n_queries - q0);
+        const float* qs = queries + (size_t)q0 * s->D;
+        args.walked = 0;
+        walk_ranked_lists(s, plan, qs, B, pool, rec, args.rec, false, [&] {
+            launch_diverse_collect(st, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
+            args.walked += kMaxK;
+        });
+        launch_diverse_select(st, B, s->D, s->D4, s->metric, args);
+        PCV_HIP(hipMemcpyAsync(s->pin_diverse.p + L::off_id, s->d_diverse.p + L::off_id, L::total - L::off_id, hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        PCV_HIP(hipGetLastError());
+        for (int q = 0; q < B; ++q) {
+            const int n = (int)rec[q].kept;
+            const size_t o = (size_t)(q0 + q) * k;
+            for (int j = 0; j < n; ++j) {
+                const size_t i = (size_t)q * kMaxK + j;
+                if (out_ids) out_ids[o + j] = r_id[i];
+                if (out_scores) out_scores[o + j] = reported_score(s->metric, s->D, r_score[i]);
+                if (out_marginal) out_marginal[o + j] = r_marginal[i];
+                if (out_ranks) out_ranks[o + j] = r_rank[i];
+            }
+            blank(q0 + q, n);
+            if (out_counts) out_counts[q0 + q] = n;
+            if (out_examined) out_examined[q0 + q] = (int32_t)rec[q].examined;
+            if (out_exact) out_exact[q0 + q] = r_exact[q] ? 1 : 0;
+        }
+    }
+}
+
 // ---- grouped results (pcv_searcher_set_groups / _search_grouped; DESIGN.md §4 "Grouped results") ----
 constexpr int64_t kMaxGroupEntries = (int64_t)1 << 30;
 constexpr uint64_t kMinGroupSlots = 1024;
@@ -3315,6 +3424,26 @@ pcv_status pcv_searcher_search_distinct(pcv_searcher* s, const float* queries, i
         sync_view(s);
         search_distinct(s, queries, n_queries, source_ids, n_sources, num_results, threshold, pool, out_ids, out_scores, out_counts, out_similar,
                         out_examined, out_more);
+    });
+}
+
+pcv_status pcv_searcher_search_diverse(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                       int num_results, float lambda, int pool, int64_t* out_ids, float* out_scores, double* out_marginal,
+                                       int32_t* out_ranks, int32_t* out_counts, int32_t* out_examined, uint8_t* out_exact) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "search_diverse: searcher is NULL");
+        PCV_REQUIRE(queries != nullptr && n_queries > 0, "search_diverse: no queries");
+        PCV_REQUIRE(num_results >= 1 && num_results <= (int)PCV_MAX_RESULTS, "search_diverse: num_results %d outside [1,%d]", num_results,
+                    (int)PCV_MAX_RESULTS);
+        PCV_REQUIRE(pool >= num_results && pool <= (int)PCV_MAX_DIVERSE_POOL, "search_diverse: pool %d outside [num_results = %d, %d]", pool,
+                    num_results, (int)PCV_MAX_DIVERSE_POOL);
+        PCV_REQUIRE(lambda == lambda, "search_diverse: lambda is NaN");
+        PCV_REQUIRE(lambda >= 0.0f && lambda <= 1.0f, "search_diverse: lambda %g outside [0, 1]", (double)lambda);
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "search_diverse: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        search_diverse(s, queries, n_queries, source_ids, n_sources, num_results, lambda, pool, out_ids, out_scores, out_marginal, out_ranks,
+                       out_counts, out_examined, out_exact);
     });
 }
 

@@ -222,6 +222,13 @@ struct pcv_searcher {
     // records | kept hits | their norms | their counters, on the device and (records after every pass, the rest once) in pinned memory
     pcv::DevBuf<uint8_t> d_distinct;
     pcv::PinBuf<uint8_t> pin_distinct;
+    // diverse results (pcv_searcher_search_diverse): records | result block of one group of queries on the device and in pinned
+    // memory, the group's pool lists, and the scratch their rows are gathered into (scan.h, DiverseArgs; given back after the call
+    // where it is large)
+    pcv::DevBuf<uint8_t> d_diverse;
+    pcv::PinBuf<uint8_t> pin_diverse;
+    pcv::DevBuf<pcv::pcv_hit_dev> d_diverse_entries;
+    pcv::DevBuf<float4> d_diverse_rows;
     // the group table (pcv_searcher_set_groups; corpus.h "the group table"): keys | vals on the device, the head block beside them
     // and the host's copy of it as of the last set_groups (every one ends with a synchronised download).  A view has none: it
     // reads its parent's.  The scratch of a set_groups / get_groups call is kept for the next unless it is large.

@@ -13,6 +13,7 @@ from . import _ffi
 from .context import Context
 
 PCV_MAX_DISTINCT_POOL = 4096  # include/perceive_hip.h
+PCV_MAX_DIVERSE_POOL = 4096  # include/perceive_hip.h
 PCV_MAX_GROUPED_POOL = 4096  # include/perceive_hip.h
 PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_of / search_grouped
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
@@ -423,6 +424,52 @@ class Searcher:
         if not found[0]:
             raise KeyError("Item not found")
         return self.search_distinct_vector(sources, num_results, vec[0], threshold, pool)
+
+    # ---- diverse results (pcv_searcher_search_diverse) -----------------------------------------------
+    # Exact greedy maximal marginal relevance on the device: results like this, but not ten versions of the same page.
+    def search_diverse(self, sources, num_results, vectors, lam, pool=None):
+        """Greedy MMR over the first `pool` entries of the ranked list of search_vectors (default min(PCV_MAX_DIVERSE_POOL,
+        max(128, 8 * num_results))): each pick maximises lam * relevance - (1 - lam) * (largest canonical cosine with a row already
+        picked), ties to the better rank; lam in [0, 1], 1 = the plain top-k.  vectors [B, dim] -> (ids [B, k] int64 in pick order,
+        scores [B, k] f32: those search_vectors returns for the same rows, marginal [B, k] f64: the value each pick was made at,
+        ranks [B, k] int32: each pick's place in the ranked list, counts [B] int32, examined [B] int32: entries in the pool,
+        exact [B] bool: the picks are provably those of the same walk over the whole list).  The arithmetic is defined in
+        include/perceive_hip.h."""
+        q = np.ascontiguousarray(vectors, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [B, {self.dim}]")
+        B, k = q.shape[0], int(num_results)
+        if pool is None:
+            pool = min(PCV_MAX_DIVERSE_POOL, max(128, 8 * k))
+        ids = np.full((B, max(k, 0)), -1, dtype=np.int64)
+        scores = np.full((B, max(k, 0)), np.nan, dtype=np.float32)
+        marginal = np.full((B, max(k, 0)), np.nan, dtype=np.float64)
+        ranks = np.full((B, max(k, 0)), -1, dtype=np.int32)
+        counts = np.zeros(max(B, 1), dtype=np.int32)
+        examined = np.zeros(max(B, 1), dtype=np.int32)
+        exact = np.zeros(max(B, 1), dtype=np.uint8)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_diverse(
+                self._handle, _ffi.f32p(q), B, src, nsrc, k, float(lam), int(pool), _ffi.i64p(ids), _ffi.f32p(scores),
+                _ffi.f64p(marginal), _ffi.i32p(ranks), _ffi.i32p(counts), _ffi.i32p(examined), _ffi.u8p(exact),
+            )
+        )
+        return ids, scores, marginal, ranks, counts[:B], examined[:B], exact[:B].astype(bool)
+
+    def search_diverse_vector(self, sources, num_results, vector, lam, pool=None):
+        """search_diverse for one vector -> list[SearchItem] in pick order (the rest is dropped: ask search_diverse for it)."""
+        ids, scores, _m, _r, counts, _ex, _exact = self.search_diverse(
+            sources, num_results, np.asarray(vector, dtype=np.float32)[None, :], lam, pool)
+        return [SearchItem(int(ids[0, j]), float(scores[0, j])) for j in range(int(counts[0]))]
+
+    def search_diverse_like_item(self, sources, num_results, item_id, lam, pool=None):
+        """A diverse set of neighbours of the stored embedding of `item_id` (like_queries + search_diverse); as in search_like_item
+        the item itself comes first.  KeyError("Item not found") when no row carries the id."""
+        vec, found, _members = self.like_queries([[int(item_id)]])
+        if not found[0]:
+            raise KeyError("Item not found")
+        return self.search_diverse_vector(sources, num_results, vec[0], lam, pool)
 
     # ---- grouped results (pcv_searcher_set_groups / _search_grouped) ---------------------------------
     # The exact top-k collapsed by a stored group key per item: "the k closest documents" over a corpus of chunk rows.

@@ -263,6 +263,7 @@ pub const PCV_MAX_RESULTS: c_int = 128;
 pub const PCV_MAX_RANGE_ROWS: c_int = 16777216;
 pub const PCV_MAX_DISTINCT_POOL: c_int = 4096;
 pub const PCV_MAX_GROUPED_POOL: c_int = 4096;
+pub const PCV_MAX_DIVERSE_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
 pub const PCV_MAX_NEIGHBORS: c_int = 64;
@@ -352,6 +353,7 @@ extern "C" {
     pub fn pcv_searcher_get_groups(s: *mut pcv_searcher, ids: *const i64, n: i64, out_groups: *mut i64) -> c_int;
     pub fn pcv_searcher_group_stats(s: *mut pcv_searcher, out: *mut pcv_group_stats) -> c_int;
     pub fn pcv_searcher_search_grouped(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, out_ids: *mut i64, out_scores: *mut f32, out_groups: *mut i64, out_counts: *mut i32, out_collapsed: *mut i32, out_examined: *mut i32, out_more: *mut u8) -> c_int;
+    pub fn pcv_searcher_search_diverse(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, lambda: f32, pool: c_int, out_ids: *mut i64, out_scores: *mut f32, out_marginal: *mut f64, out_ranks: *mut i32, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
     pub fn pcv_searcher_find_duplicates(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, max_pairs: i64, out_id_a: *mut i64, out_id_b: *mut i64, out_scores: *mut f32, out_count: *mut i64, out_total: *mut i64) -> c_int;
     pub fn pcv_searcher_last_duplicate_stats(s: *mut pcv_searcher, out: *mut pcv_duplicate_stats) -> c_int;
     pub fn pcv_searcher_assign(s: *mut pcv_searcher, labels: *const f32, n_labels: c_int, source_ids: *const i64, n_sources: c_int, capacity: i64, out_label: *mut i32, out_score: *mut f32, out_ids: *mut i64, out_counts: *mut i64, out_n: *mut i64) -> c_int;

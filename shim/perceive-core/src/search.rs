@@ -394,6 +394,54 @@ impl Searcher {
         (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, similar[i])).collect()
     }
 
+    /// Diverse results (`pcv_searcher_search_diverse`): exact greedy maximal marginal relevance on the device over the first `pool`
+    /// entries of the ranked list of `search_vector` (`None`: min(PCV_MAX_DIVERSE_POOL, max(128, 8 * num_results))).  Each pick
+    /// maximises lambda * relevance - (1 - lambda) * (largest cosine with an item already picked), ties to the better rank; lambda
+    /// in [0, 1], 1 = the plain list.  The picks come in pick order, each with the marginal value it was picked at and its place
+    /// in the ranked list.
+    pub fn search_vector_diverse(
+        &self,
+        sources: &[i64],
+        num_results: usize,
+        vector: Vec<f32>,
+        lambda: f32,
+        pool: Option<usize>,
+    ) -> Vec<(SearchItem, f64, i32)> {
+        if self.handle.is_null() || num_results == 0 {
+            return Vec::new();
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        assert_eq!(vector.len(), dim as usize, "search_vector_diverse: the query has {} values, the index is {}-d", vector.len(), dim);
+        let pool = pool.unwrap_or_else(|| (ffi::PCV_MAX_DIVERSE_POOL as usize).min((8 * num_results).max(128)));
+        let mut ids = vec![-1i64; num_results];
+        let mut scores = vec![f32::NAN; num_results];
+        let mut marginal = vec![f64::NAN; num_results];
+        let mut ranks = vec![-1i32; num_results];
+        let mut count: i32 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_diverse(
+                self.handle,
+                vector.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                num_results as i32,
+                lambda,
+                pool as i32,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                marginal.as_mut_ptr(),
+                ranks.as_mut_ptr(),
+                &mut count,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        })
+        .expect("search_diverse failed");
+        (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, marginal[i], ranks[i])).collect()
+    }
+
     /// The group table (`pcv_searcher_set_groups`): item `ids[i]` belongs to group `groups[i]` (any i64 >= 0; `ffi::PCV_NO_GROUP`
     /// ungroups the id); of an id that occurs more than once the last occurrence holds.  The table is keyed by item id and lives on
     /// the device: it survives `remove_items` and a rebuilt source.  A chunking ingester calls this after it has added the rows.
