@@ -200,7 +200,7 @@ struct ScanParams {
     // first block against it.  set_guess (quantize_queries_kernel / set_guess_kernel) therefore raises tau to the spec_rank-th LARGEST slot — a guess
     // that at least k rows of the whole pass score that high — and rescore_select_kernel checks the guess: it counts the
     // survivors whose f32 score is above it by the fine margin; fewer than k and the query reports 0xffffffff survivors,
-    // the pass is repeated without the guess (searcher.cpp: finish_pass).  A checked guess keeps the result exact:
+    // the pass is repeated without the guess (searcher_pass.cpp: finish_pass).  A checked guess keeps the result exact:
     // with k rows at or above it the true k-th best is too, and no screen drops a row at or above tau - its margin.
     // The host picks spec_rank so that, for rows in an order unrelated to the query, a guess fails with probability
     // < 1e-6 (C(k-1, j) (seed rows / rows)^j: j of the k-1 best rows of the pass would have to be seed rows).

@@ -2395,7 +2395,7 @@ __global__ __launch_bounds__(kMfmaQueries) void range_thresholds_kernel(const Sc
 //      the row staging of score_listed, inside the 160 KB of a CU — and are sorted there: bitonic network over the next power of
 //      two, padded with entries that sort last; order: c descending, ties -> lower global position (positions are unique);
 //   4. the first range_keep of them go straight to pinned host memory with the run's in-range count; the host merges the runs of
-//      a query (searcher.cpp: search_range);
+//      a query (searcher_calls.cpp: search_range);
 //   5. the workgroup that finishes last for its query reports the uncapped survivor count and the screens' statistics and
 //      leaves the query's scan state clean for the next pass (cand_cnt word 35 counts the finished runs).
 template <bool COOP>

@@ -1,0 +1,54 @@
+// searcher_calls.h — the search calls behind the C entry points (searcher_calls.cpp): plain, range, distinct, grouped and diverse
+// search, the group table, the begin half of the sharded protocol and search by example.  The entry point has checked its
+// arguments, holds s->mu, has seen that no pass is pending and has brought a view up to date (sync_view).
+#pragma once
+#include "searcher_pass.h"
+
+namespace pcv {
+
+void search_hits(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, int k,
+                 std::vector<pcv_hit_dev>& out);
+void hits_to_outputs(int metric, int D, const pcv_hit_dev* hits, int n_queries, int k, int64_t* out_ids, float* out_scores, int* out_counts);
+void search_range(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, const float* bounds,
+                  int64_t max_results, int64_t* out_ids, float* out_scores, int64_t* out_counts, uint8_t* out_more);
+void device_begin(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, int k, pcv_hit_dev* out,
+                  bool queries_on_device = false);
+
+// What the ranked calls (distinct, grouped, diverse) have in common: the queries, the selection, num_results and pool, and the
+// columns each of them writes.  `out_last`: per query, `more` (distinct, grouped) or `exact` (diverse).
+struct RankedCall {
+    pcv_searcher* s;
+    const float* queries;
+    int n_queries;
+    const int64_t* source_ids;
+    int n_sources;
+    int k, pool;
+    int64_t* out_ids;
+    float* out_scores;
+    int32_t* out_counts;
+    int32_t* out_examined;
+    uint8_t* out_last;
+};
+void search_distinct(const RankedCall& c, float threshold, int32_t* out_similar);
+void search_diverse(const RankedCall& c, float lambda, double* out_marginal, int32_t* out_ranks);
+// `owner`: whose group table is read (s itself, or the parent of a view, locked by the caller around the whole call)
+void search_grouped(const RankedCall& c, const pcv_searcher* owner, int64_t* out_groups, int32_t* out_collapsed);
+
+void set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int64_t n);
+void clear_groups(pcv_searcher* s);
+void get_groups(pcv_searcher* owner, const int64_t* ids, int64_t n, int64_t* out);
+
+int64_t check_like_args(const pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets, int n_queries,
+                        const char* who);
+std::unique_lock<std::mutex> lock_like_owner(pcv_searcher* s, pcv_searcher*& owner, const char* who);
+// What the lookup of a call's examples gives back to the host.
+struct LikeBuilt {
+    std::vector<float> vectors;         // [n_queries][D], if asked for
+    std::vector<int64_t> member_rows;   // [n_queries] rows that went into each query
+    std::vector<int64_t> carrier_rows;  // [n_queries] ... plus the rows staged under PCV_STAGING_SOURCE that carry one of its ids
+    std::vector<uint8_t> found;         // [examples]
+};
+void build_like_queries(pcv_searcher* p, const int64_t* example_ids, const float* weights, const int64_t* offsets, int n_queries,
+                        bool want_host, void* d_out, LikeBuilt& out);
+
+}  // namespace pcv

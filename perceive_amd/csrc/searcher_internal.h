@@ -1,5 +1,7 @@
-// searcher_internal.h — the Searcher handle and its building blocks as the searcher's host files share them: searcher.cpp (rows,
-// copies, passes, views, RCCL) and row_jobs.cpp (the calls that run kernels over the stored rows).  Not part of the C ABI.
+// searcher_internal.h — the Searcher handle and its building blocks as the searcher's host files share them, and what the units
+// that own its rows declare for the others: searcher_store.cpp (segments and their copies), searcher_edits.cpp (changes by id)
+// and searcher_views.cpp.  The pass pipeline and the search calls have headers of their own (searcher_pass.h, searcher_calls.h);
+// searcher.cpp holds the C entry points, row_jobs.cpp the calls that run kernels over the stored rows.  Not part of the C ABI.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -357,12 +359,82 @@ struct pcv_searcher {
 
 namespace pcv {
 
-// searcher.cpp internals used by row_jobs.cpp; the caller holds s->mu
+constexpr int64_t kStageRows = 1 << 18;                // rows per H2D staging step (384-d: 400 MB)
+constexpr int64_t kMaxSegRows = (int64_t)0xffffffc0u;  // a candidate names its row in 32 bits
+
+// the canonical order of hits
+inline bool hit_better(const pcv_hit_dev& a, const pcv_hit_dev& b) {
+    if (a.score != b.score) return a.score > b.score;
+    return a.pos < b.pos;
+}
+
+// A copy's buffer and the buffer of its scales: both or neither (then both pointers are null and the error is returned).
+// `refuse`: PCV_TUNE_FAIL_COPY_ALLOC.  Reads nothing of the searcher: the helper thread of the AUTO mid build calls it too.
+template <class A, class B>
+hipError_t alloc_with_scales(bool refuse, A** buf, size_t bytes, B** scales, size_t scale_bytes) {
+    hipError_t e = refuse ? hipErrorOutOfMemory : hipMalloc((void**)buf, bytes);
+    if (e == hipSuccess) {
+        e = hipMalloc((void**)scales, scale_bytes);
+        if (e != hipSuccess) (void)hipFree(*buf);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        *scales = nullptr;
+    }
+    return e;
+}
+
+// ---- searcher_store.cpp: segments and their derived copies (each is described there); the caller holds s->mu ----
 struct SelSeg {
     const Segment* g;
 };
 std::vector<SelSeg> select_segments(pcv_searcher* s, const int64_t* source_ids, int n_sources);  // the segments with rows of the selected sources
 int64_t selected_rows(const std::vector<SelSeg>& segs);
-void sync_view(pcv_searcher* v);  // every call on a view starts here
+void free_segment(Segment& g);
+Segment alloc_segment(pcv_searcher* s, int64_t cap_rows, bool with_ids);
+void append_rows(pcv_searcher* s, Source& src, const int64_t* ids, const void* rows, int64_t n);
+void assign_positions(pcv_searcher* s);
+void do_finalize(pcv_searcher* s);
+void extend_mid(hipStream_t st, Segment& g, int D4);
+void extend_six(hipStream_t st, Segment& g, int D4);
+std::vector<uint32_t> touched_blocks(const Segment& g, const std::vector<uint32_t>& rows);
+void repair_copies(pcv_searcher* s, Segment& g, const uint32_t* d_rows, uint32_t nr, const uint32_t* d_blocks, uint32_t nb);
+void settle_mid_build(pcv_searcher* s, bool wait);
+void build_mid_copies(pcv_searcher* s, bool must);
+void maybe_build_mid_copies(pcv_searcher* s);
+void drop_mid_copies(pcv_searcher* s);
+void drop_six_copies(pcv_searcher* s);
+bool have_six_copies(const pcv_searcher* s);
+void build_six_copies(pcv_searcher* s);
+void drop_screening_copies(pcv_searcher* s);
+void build_screening_copies(pcv_searcher* s, Source& src);
+int copy_kind_wanted(const pcv_searcher* s);
+void refresh_copy_state(pcv_searcher* s);
+void read_max_norm(pcv_searcher* s);
+
+// ---- searcher_edits.cpp: a batch of ids and what it finds, hides, rewrites and removes; the caller holds s->mu ----
+// A batch of ids (ascending, distinct), optionally with a slot number per id (an update: the place of the id's vector in the
+// call), and, once a segment with an id column needs it, its open-addressing table on the device (scan.h: id_hash): the ids in
+// s->d_idtab and, with slots, each one's slot in the same cell of s->d_idslot.  kIdEmpty marks a free cell, so that id itself
+// travels beside the table (has_empty, empty_slot).
+struct IdBatch {
+    const std::vector<int64_t>* ids = nullptr;
+    const std::vector<uint32_t>* slots = nullptr;  // slots[i] belongs to ids[i]; nullptr: no slots
+    bool uploaded = false, has_empty = false;
+    uint32_t tmask = 0, empty_slot = 0;
+};
+void upload_id_batch(pcv_searcher* s, IdBatch& b);
+std::pair<size_t, size_t> implicit_range(const std::vector<int64_t>& ids, const Segment& g, uint32_t r0, uint32_t r1);
+std::vector<std::pair<uint32_t, uint32_t>> find_slots(pcv_searcher* s, const Segment& g, IdBatch& b);
+uint32_t hide_rows_in(pcv_searcher* s, Segment& g, uint32_t r0, uint32_t r1, IdBatch& b);
+int64_t apply_id_batch(pcv_searcher* s, const std::vector<int64_t>& batch, bool hide);
+int64_t update_by_id(pcv_searcher* s, const int64_t* ids, const void* rows, int64_t n, const std::vector<uint32_t>& by_id,
+                     std::vector<uint8_t>& found);
+int64_t remove_by_id(pcv_searcher* s, const std::vector<int64_t>& batch);
+
+// ---- searcher_views.cpp ----
+void build_view(pcv_searcher* v, pcv_searcher* p);  // p->mu held
+void sync_view(pcv_searcher* v);                    // every call on a view starts here (v->mu held)
 
 }  // namespace pcv

@@ -14,7 +14,7 @@ leaves of the Dp products bf16(a_i) bf16(b_i), Dp / 16 instructions chained thro
   - Every product of two 8-bit significands is exact in f32, so acc differs from the exact sum only by the additions.  Dp - 1
     additions in ANY order, each rounded in ANY direction (relative error below 2^-23), err by at most (Dp - 1) 2^-23 sum |a^_i b^_i|:
     below eps32(D) sum |a^_i b^_i| with eps32(D) = (Dp + 16) 1.2e-7, the bound the project claims for such a chain
-    (searcher.cpp fill_params, screens_ref.bf16_slack).  screens_ref bounds the sum of magnitudes by |a^||b^|; the model has the
+    (searcher_pass.cpp fill_params, screens_ref.bf16_slack).  screens_ref bounds the sum of magnitudes by |a^||b^|; the model has the
     rows, so it takes T[a, b] = sum |a^_i b^_i| ra rb itself (T <= (1 + 2^-8)^2, some 0.64 for Gaussian rows): never looser.
   - The two multiplications by ra and rb: 2^-24 each, of |s| <= (1 + 2^-8)^2.  One ulp of each rinv (the device's f64 sqrt and
     division against numpy's, then the rounding to f32): 2^-23 each.  Together 3 * 2^-23 |s| (1 + 2^-22), which is 2^-22 |s| and

@@ -26,7 +26,7 @@ F32 = np.float32
 # ---- the query constants prep_seed* writes ------------------------------------------------------------------------------------------
 def margins(rows, qs):
     """(margin, margin32) [B] as prep_seed_kernel / prep_seed_mfma_kernel write them, in f32 arithmetic: (eps16 + eps32) unit and
-    2 eps32 unit with eps32 = (Dp + 16) 1.2e-7, eps16 = 0.0039101 + 2 eps32 (searcher.cpp, fill_params) and unit = 1 (cosine) or
+    2 eps32 unit with eps32 = (Dp + 16) 1.2e-7, eps16 = 0.0039101 + 2 eps32 (searcher_pass.cpp, fill_params) and unit = 1 (cosine) or
     (float)|q| max_norm 1.0001 (dot)."""
     e32 = F32(rows.Dp + 16) * F32(1.2e-7)
     e16 = F32(0.0039101) + F32(2.0) * e32
@@ -148,7 +148,7 @@ def keep_mid(rows, qs, tau, slack=0.0):
 def fine_slack(D):
     """s32 = dot * sc with dot an f32 FMA chain over the Dp features in the kernel's own order (wave_dot_f32: 64 lanes and a
     butterfly; drain_survivors: 8 lanes; scan_wave_kernel: two half rows): |dot sc - s32| <= eps32(D) unit, the bound the project
-    claims for an f32 FMA chain in any order (searcher.cpp, fill_params) — Dp 2^-24 is half of it, the product with sc and the
+    claims for an f32 FMA chain in any order (searcher_pass.cpp, fill_params) — Dp 2^-24 is half of it, the product with sc and the
     subtraction tau - margin32 take 2^-24 of |s32| <= unit and of |tau|.  So: eps32(D) + 2^-23 of unit + |tau|."""
     return eps32(D) + 2.0 ** -23
 

@@ -34,7 +34,7 @@ def padded(D):
 
 
 def eps32(D):
-    """the f32 screening score's error bound relative to |q||x| (searcher.cpp, fill_params); margin32 = 2 eps32 unit"""
+    """the f32 screening score's error bound relative to |q||x| (searcher_pass.cpp, fill_params); margin32 = 2 eps32 unit"""
     return (padded(D)[0] + 16) * 1.2e-7
 
 
@@ -211,7 +211,7 @@ def keeps(rows, qs, tau, slack=0.0):
 
 
 def range_tau(bounds, queries, rows):
-    """RangeRec::tau of each bound on the reported f32 score (searcher.cpp, range_rec): its canonical value, rounded towards
+    """RangeRec::tau of each bound on the reported f32 score (searcher_calls.cpp, range_rec): its canonical value, rounded towards
     "keeps more"; finite bounds only."""
     b = np.asarray(bounds, dtype=np.float32)
     if rows.metric != "dot":

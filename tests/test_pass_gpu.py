@@ -1,4 +1,4 @@
-"""The searcher's pass pipeline (csrc/searcher.cpp: enqueue_pass / finish_pass) seen through the C ABI: a pass gives the same hits
+"""The searcher's pass pipeline (csrc/searcher_pass.cpp: enqueue_pass / finish_pass) seen through the C ABI: a pass gives the same hits
 and books the same statistics whether its launches are queued plainly, captured into a graph (the third sighting of a shape) or
 replayed; every kind of pass shares one workspace without leaving anything behind for the next; and the numeric PCV_SCAN_FLAGS
 words keep their meaning.  Expected hits come from the oracle, expected byte counts from the layout documented in csrc/scan.h."""
@@ -32,7 +32,7 @@ def six_times_the_same(s, q, k, mode, want_pos, want_scores, nrows, D):
     replayed, so nothing here shows that a capture took place: the test holds what a caller can see — hits and statistics — to the
     same values over the calls in which the searcher changes how it queues the pass.
     The mid copy is switched off by the callers: at these sizes the survivors' f32 rows are a visible share of a pass, so AUTO
-    would build the copy beside the searches after two passes (searcher.cpp: note_mid_trigger) and `mid_copy` would change from
+    would build the copy beside the searches after two passes (searcher_pass.cpp: note_mid_trigger) and `mid_copy` would change from
     0 to 1 part way through the six calls — by design, and nothing to do with how the pass is queued."""
     first_ids = first_scores = first_stats = None
     for run in range(6):

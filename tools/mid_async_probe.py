@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the search calls around AUTO's decision to build the mid copy take (the build runs beside them, searcher.cpp: start_mid_build):
+"""What the search calls around AUTO's decision to build the mid copy take (the build runs beside them, searcher_store.cpp: start_mid_build):
     python tools/mid_async_probe.py [rows, default 50000000]"""
 import os
 import sys
