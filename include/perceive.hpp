@@ -313,6 +313,32 @@ inline NeighborTable neighbors_handle(pcv_searcher* h, const std::vector<int64_t
     return r;
 }
 
+// Searcher::match / SearcherView::match (pcv_searcher_match): for every item of the sources `from`, by global position, its exact k
+// best items of the sources `to` by cosine among those with cosine >= min_score (-1: no bound), best first; an item is never its own
+// match; with `from` == `to` and no bound the table is the neighbours' (NeighborTable, neighbor_ids: the matches).  An empty `to`
+// matches nothing: every count is 0.
+inline NeighborTable match_handle(pcv_searcher* h, const std::vector<int64_t>& from, const std::vector<int64_t>& to, size_t k, float min_score) {
+    NeighborTable r;
+    r.k = k;
+    if (from.empty() || k == 0) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    const int64_t none = 0;
+    const int64_t* to_ids = to.empty() ? &none : to.data();  // (a NULL list would mean every source)
+    check(pcv_searcher_match(h, from.data(), (int)from.size(), to_ids, (int)to.size(), (int)k, min_score, 0, nullptr, nullptr, nullptr, nullptr, &n));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.ids.resize(room);
+    r.neighbor_ids.resize(room * k);
+    r.scores.resize(room * k);
+    r.counts.resize(room);
+    check(pcv_searcher_match(h, from.data(), (int)from.size(), to_ids, (int)to.size(), (int)k, min_score, (int64_t)room, r.ids.data(),
+                             r.neighbor_ids.data(), r.scores.data(), r.counts.data(), &n));
+    r.ids.resize((size_t)n);
+    r.neighbor_ids.resize((size_t)n * k);
+    r.scores.resize((size_t)n * k);
+    r.counts.resize((size_t)n);
+    return r;
+}
+
 // Searcher::density_clusters / SearcherView::density_clusters (pcv_searcher_density_clusters): DBSCAN under the cosine over the items
 // of `sources`, by global position — the clusters, their number and the noise, with no number of groups to choose.
 struct DensityClusters {
@@ -688,6 +714,15 @@ public:
         check(pcv_searcher_last_neighbor_stats(h_, &st));
         return st;
     }
+    // the k best items of the sources `to` for every item of the sources `from` (match_handle)
+    NeighborTable match(const std::vector<int64_t>& from, const std::vector<int64_t>& to, size_t k, float min_score = -1.0f) const {
+        return match_handle(h_, from, to, k, min_score);
+    }
+    pcv_match_stats last_match_stats() const {
+        pcv_match_stats st;
+        check(pcv_searcher_last_match_stats(h_, &st));
+        return st;
+    }
     // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
     std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
                                                        bool exclude = false) const {
@@ -874,6 +909,15 @@ public:
     pcv_neighbor_stats last_neighbor_stats() const {
         pcv_neighbor_stats st;
         check(pcv_searcher_last_neighbor_stats(h_, &st));
+        return st;
+    }
+    // the k best items of the sources `to` for every item of the sources `from` (match_handle)
+    NeighborTable match(const std::vector<int64_t>& from, const std::vector<int64_t>& to, size_t k, float min_score = -1.0f) const {
+        return match_handle(h_, from, to, k, min_score);
+    }
+    pcv_match_stats last_match_stats() const {
+        pcv_match_stats st;
+        check(pcv_searcher_last_match_stats(h_, &st));
         return st;
     }
     // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the

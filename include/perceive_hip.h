@@ -693,6 +693,61 @@ typedef struct pcv_neighbor_stats {
 } pcv_neighbor_stats;
 pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats* out);
 
+/* Item matches: the join of two sets of stored items — for EVERY item of the sources A (`from`) its exact k best items of the
+ * sources B (`to`), computed where the rows live (which newly imported items already exist elsewhere, with a score bound; the pages of
+ * one source related to those of another; nearest-neighbour tagging from a tagged source).  The work is |A| x |B|: pcv_searcher_neighbors
+ * over the union would also pay for A x A and B x B, and an item's own set would fill its k slots.
+ * The rows concerned are those of the segments selected by from_source_ids in global position order, n of them, as in
+ * pcv_searcher_neighbors (hidden and unsearchable rows included: they keep their place); from_source_ids == NULL means all sources,
+ * an empty list selects nothing (n = 0); a view matches among its own rows.  The PARTNERS are the participating rows of the segments
+ * selected by to_source_ids, with the same NULL and empty-list rules.  The two selections may overlap, fully or partly, and lie in any
+ * position order.  A row TAKES PART under exactly the rules of pcv_searcher_neighbors: a pcv_searcher_search with the same filter could
+ * return it (scale != 0, not hidden) and it has a cosine (canonical |x|^2 in [2^-126, inf)).  A row is never its own partner (the same
+ * position); another row carrying the same item id is a partner like any other.  For a participating row r of A and a partner p,
+ * c(r, p) = the canonical cosine of the two stored f32 rows — f64, products exact, sums in feature order — for BOTH
+ * metrics.  The matches of r are, among the partners with c >= (double)min_score, the k with the largest c, ties to the lower global
+ * position, ordered by (c descending, position ascending).  Fewer than k such partners is a result, not an error: the count says so.
+ *   k               1 .. PCV_MAX_NEIGHBORS
+ *   min_score       in [-1, 1].  Exactly -1.0f means no bound: the comparison is skipped, and a c that rounds below -1 is still listed
+ *   capacity        rows the outputs have room for; capacity < n gives PCV_ERR_INVALID (out_rows is set)
+ *   out_ids         [capacity] the item id of every position
+ *   out_match_ids   [capacity][k] the matches' item ids, best first; unused slots -1
+ *   out_scores      [capacity][k] (float)c; unused slots NaN
+ *   out_counts      [capacity] int32: matches written; 0 for a row that takes no part
+ *   out_rows        n.  With all four arrays NULL and capacity == 0 the call only reports n and does no device work
+ * A NULL out_rows or searcher, k out of range, a min_score that is NaN or outside [-1, 1], a negative capacity or a NULL array with
+ * capacity != 0 give PCV_ERR_INVALID before the handle is looked at; a searcher with pending rows and a sharded searcher fail as in
+ * pcv_searcher_neighbors.  A dimension whose bf16 row tile does not fit the LDS of a CU (above 2496) gives PCV_ERR_UNSUPPORTED, and
+ * so does a call whose screen lists more than 2^30 (row, partner) candidates, before the larger list is allocated.  The result does
+ * not depend on which screening copies exist, nor on pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity: the call reads
+ * the f32 rows and touches no pass state (DESIGN.md §4 "Item matches").  Everything it allocates on the device is given back when it
+ * returns.  pcv_searcher_match(X, X, k, -1) returns bit for bit what pcv_searcher_neighbors(X, k) returns: the two calls run the same
+ * steps.  Not in scope: a second searcher handle as B, a sharded searcher and device-resident output. */
+pcv_status pcv_searcher_match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const int64_t* to_source_ids, int n_to, int k,
+                              float min_score, int64_t capacity, int64_t* out_ids, int64_t* out_match_ids, float* out_scores,
+                              int32_t* out_counts, int64_t* out_rows);
+
+/* Counters of the most recent pcv_searcher_match on this handle. */
+typedef struct pcv_match_stats {
+    int64_t rows;            /* n: rows of the segments of `from` (those taking no part included)               */
+    int64_t partner_rows;    /* rows of the segments of `to` (likewise)                                         */
+    int32_t owner_blocks;    /* 32-row blocks the screen cut its tiles from: the segments of `from`             */
+    int32_t partner_blocks;  /* 32-row blocks every tile was streamed against: the segments of `to`             */
+    int64_t candidates;      /* directed (row, partner) pairs the bf16 list pass left and the f64 step scored   */
+    int64_t listed;          /* matches written (the sum of out_counts)                                         */
+    int32_t k;
+    int32_t tile_rows;       /* rows of the LDS tile the screen kernel staged                                   */
+    int32_t sample_stride;   /* the bound pass streamed every sample_stride-th partner block                    */
+    int32_t spans;           /* disjoint partner sets whose maxima bound a row's k-th best score                */
+    int32_t reruns;          /* list passes repeated because the candidate list was short                       */
+    float prep_ms;           /* hipEvent times of the steps (a repeated list pass included in screen_ms)        */
+    float bound_ms;
+    float screen_ms;
+    float rescore_ms;
+    float select_ms;
+} pcv_match_stats;
+pcv_status pcv_searcher_last_match_stats(pcv_searcher* s, pcv_match_stats* out);
+
 /* Density clusters: DBSCAN under the cosine over the stored items, exact, computed where the rows live — which topics a library
  * holds, how many, and which items belong to none, without the caller choosing a number of groups; degree(r) is a density and
  * outlier score of its own.

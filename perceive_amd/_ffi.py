@@ -94,6 +94,27 @@ class NeighborStats(C.Structure):
     ]
 
 
+class MatchStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("partner_rows", C.c_int64),
+        ("owner_blocks", C.c_int32),
+        ("partner_blocks", C.c_int32),
+        ("candidates", C.c_int64),
+        ("listed", C.c_int64),
+        ("k", C.c_int32),
+        ("tile_rows", C.c_int32),
+        ("sample_stride", C.c_int32),
+        ("spans", C.c_int32),
+        ("reruns", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("bound_ms", C.c_float),
+        ("screen_ms", C.c_float),
+        ("rescore_ms", C.c_float),
+        ("select_ms", C.c_float),
+    ]
+
+
 class DensityStats(C.Structure):
     _fields_ = [
         ("rows", C.c_int64),
@@ -301,6 +322,9 @@ SYMBOLS = {
     "pcv_searcher_last_assign_stats": (C.c_int, [_P, C.POINTER(AssignStats)]),
     "pcv_searcher_neighbors": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int64, _I64P, _I64P, _F32P, _INTP, C.POINTER(C.c_int64)]),
     "pcv_searcher_last_neighbor_stats": (C.c_int, [_P, C.POINTER(NeighborStats)]),
+    "pcv_searcher_match": (C.c_int, [_P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, _INTP,
+                                     C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_match_stats": (C.c_int, [_P, C.POINTER(MatchStats)]),
     "pcv_searcher_density_clusters": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int, C.c_int64, _I64P, _INTP, _I8P, _INTP,
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "pcv_searcher_last_density_stats": (C.c_int, [_P, C.POINTER(DensityStats)]),

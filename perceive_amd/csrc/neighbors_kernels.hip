@@ -1,21 +1,24 @@
-// neighbors_kernels.hip — the device steps of pcv_searcher_neighbors (DESIGN.md §4 "Item neighbours"): for every participating row
-// its k best other participating rows by the canonical f64 cosine, exact, computed where the rows live.  The norms come from
-// selfjoin_prep_kernel (launch_selfjoin_prep); then
+// neighbors_kernels.hip — the device steps of pcv_searcher_neighbors and pcv_searcher_match (DESIGN.md §4 "Item neighbours", "Item
+// matches"): for every participating owner row its k best other participating partner rows by the canonical f64 cosine, exact,
+// computed where the rows live.  The owners are the launch blocks [owner_block0, total_blocks), the partners [0, partner_blocks)
+// (NeighborArgs): the whole launch twice for the neighbours, the suffix and the prefix of a launch ordered [to only | to and from |
+// from only] for the matches.  The norms come from selfjoin_prep_kernel (launch_selfjoin_prep); then
 //
 //   1. neighbors_screen_kernel<NT, false>   the bound pass: the tile-in-LDS, stream-the-blocks screen of selfjoin_screen_kernel over a
 //                                           SAMPLE of the partner blocks (every stride-th), cut into spans.  Per tile row and span it
 //                                           leaves the largest certified screening score s = acc * rinv_a * rinv_b (span_max).
-//   2. neighbors_threshold_kernel           a wave per row: thr = (k-th largest span maximum) - 2 margin.  The spans are disjoint
+//   2. neighbors_threshold_kernel           a wave per owner: thr = (k-th largest span maximum) - 2 margin, and under a score bound at
+//                                           least min_score - margin.  The spans are disjoint
 //                                           partner sets, so k maxima are k distinct partners with c >= s - margin: the k-th best c
 //                                           of the row is >= kth_s - margin, and a member of the true top k has s >= kth_s - 2 margin.
-//   3. neighbors_screen_kernel<NT, true>    the list pass: the same stream over ALL blocks, the full square.  (owner a, partner b) is
+//   3. neighbors_screen_kernel<NT, true>    the list pass: the same stream over ALL partner blocks, the full rectangle.  (owner a, partner b) is
 //                                           a candidate iff both take part, a != b and s >= thr[a] — a threshold per tile row, in
 //                                           registers beside rinv_a.  Appends past the list's capacity are counted, not stored: the
 //                                           host repeats the launch once with the capacity the count asks for.
 //   4. count / offsets / rescore            candidates per owner, their exclusive scan, and one thread per candidate: the canonical
 //                                           f64 cosine (pair_sums and finish_score: the arithmetic of selfjoin_rescore_kernel), its
-//                                           f64_key image and the partner stored in the owner's stretch of the sorted arrays.
-//   5. neighbors_select_kernel              a wave per owner: k rounds, each the best entry (c descending, partner ascending) strictly
+//                                           f64_key image (0 below the score bound) and the partner stored in the owner's stretch.
+//   5. neighbors_select_kernel              a wave per owner: k rounds, each the best entry (c descending, position ascending) strictly
 //                                           behind the one picked before — no entry is changed, so the order the atomics of step 4
 //                                           landed in cannot show.  It writes ids, neighbour ids, (float)c and counts.
 #include "device_access.h"
@@ -39,7 +42,7 @@ __device__ __forceinline__ uint32_t g_atomic_add32(uint32_t* p, uint32_t v) {
 template <int NT, bool LIST>
 struct NeighborPolicy {
     const NeighborArgs& a;
-    uint32_t TB, step, b1;
+    uint32_t owner_rows, step, b1;  // owner_rows: the launch's, the stride of span_max
     float bd[NT];
     __device__ __forceinline__ void begin(uint32_t tb0, int c) {
 #pragma unroll
@@ -100,7 +103,7 @@ struct NeighborPolicy {
                 for (int t = 0; t < NT; ++t) {
                     const float m = fmaxf(bd[t], __shfl_xor(bd[t], 32));
                     if (at.h == 0 && ra[t] > 0.0f && m > -__builtin_inff())
-                        g_atomic_max32(&a.span_max[(size_t)span * TB * 32 + (size_t)(at.tb0 + t) * 32 + at.c], f32_key(m));
+                        g_atomic_max32(&a.span_max[(size_t)span * owner_rows + (size_t)(at.tb0 - a.owner_block0 + t) * 32 + at.c], f32_key(m));
                     bd[t] = -__builtin_inff();
                 }
             }
@@ -108,40 +111,41 @@ struct NeighborPolicy {
     }
 };
 
-// grid: x = tile (NT consecutive blocks: the owners), y = walk: the sampled blocks [y * walk_len, + walk_len) of the launch, cut at
-// its end; sampled block j is launch block j * stride.  Wave w takes the sampled blocks first + w, first + w + kScreenWaves, ...
+// grid: x = tile (NT consecutive blocks from owner_block0 on: the owners), y = walk: the sampled blocks [y * walk_len, + walk_len) of
+// the partner blocks, cut at their end; sampled block j is launch block j * stride.  Wave w takes the sampled blocks first + w, first + w + kScreenWaves, ...
 // Staging, stream and accumulator layout: pair_screen.h.
 template <int NT, bool LIST>
 __global__ __launch_bounds__(kScreenWaves * 64) void neighbors_screen_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
     const ScanParams& p = *pp;
     extern __shared__ uint4 lq[];
     __shared__ const float4* tbase[NT];
-    const uint32_t TB = p.total_blocks;
-    const uint32_t tb0 = blockIdx.x * NT;
+    const uint32_t PB = a.partner_blocks;
+    const uint32_t tb0 = a.owner_block0 + blockIdx.x * NT;
     const uint32_t step = kScreenWaves * a.stride;  // launch blocks between two blocks of a wave
-    const uint32_t SB = (TB + a.stride - 1) / a.stride;
+    const uint32_t SB = (PB + a.stride - 1) / a.stride;
     const uint64_t first = (uint64_t)blockIdx.y * a.walk_len;
     if (first >= SB) return;  // (the whole workgroup)
     const uint32_t b0 = (uint32_t)first * a.stride;
-    const uint32_t b1 = (uint32_t)min((uint64_t)SB, first + a.walk_len) * a.stride;  // every sampled block below it is below TB
+    const uint32_t b1 = (uint32_t)min((uint64_t)SB, first + a.walk_len) * a.stride;  // every sampled block below it is below PB
     pair_stage_tile<NT>(p, lq, tbase, tb0);
     const uint32_t wave = uniform(threadIdx.x >> 6);
     if (b0 + wave * a.stride >= b1) return;
-    NeighborPolicy<NT, LIST> pol{a, TB, step, b1};
+    NeighborPolicy<NT, LIST> pol{a, (p.total_blocks - a.owner_block0) * 32, step, b1};
     pair_stream<NT>(p, lq, a.rinv, tb0, b0 + wave * a.stride, b1, step, pol);
 }
 
-// a wave per launch row: the k-th largest of the row's span maxima, found bit by bit from the top on their order-preserving images
-// (the largest T with at least k images >= T; 0 when fewer than k are defined), less twice the margin, rounded down
-__global__ __launch_bounds__(256) void neighbors_threshold_kernel(const NeighborArgs a, uint32_t launch_rows) {
+// a wave per owner row: the k-th largest of the row's span maxima, found bit by bit from the top on their order-preserving images
+// (the largest T with at least k images >= T; 0 when fewer than k are defined), less twice the margin, rounded down.  Under a score
+// bound no partner with s < min_score - margin can have c >= min_score: the threshold is at least that, also where T is 0.
+__global__ __launch_bounds__(256) void neighbors_threshold_kernel(const NeighborArgs a, uint32_t owner_rows) {
     const uint32_t row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= launch_rows) return;  // (the whole wave)
+    if (row >= owner_rows) return;  // (the whole wave)
     const int lane = threadIdx.x & 63;
     uint32_t v[kMaxNeighborSpans / 64];
 #pragma unroll
     for (int j = 0; j < (int)(kMaxNeighborSpans / 64); ++j) {
         const uint32_t sp = (uint32_t)j * 64 + lane;
-        v[j] = sp < a.spans ? gld(&a.span_max[(size_t)sp * launch_rows + row]) : 0u;
+        v[j] = sp < a.spans ? gld(&a.span_max[(size_t)sp * owner_rows + row]) : 0u;
     }
     uint32_t T = 0;
     for (int bit = 31; bit >= 0; --bit) {
@@ -152,9 +156,13 @@ __global__ __launch_bounds__(256) void neighbors_threshold_kernel(const Neighbor
         if (n >= a.k) T = cand;
     }
     if (lane != 0) return;
+    const uint32_t lr = a.owner_block0 * 32 + row;
     float thr = -__builtin_inff();
-    if (T != 0 && gld(&a.rinv[row]) > 0.0f) thr = __double2float_rd((double)key_f32(T) - 2.0 * (double)a.margin);
-    gst(&a.thr[row], thr);
+    if (gld(&a.rinv[lr]) > 0.0f) {
+        if (T != 0) thr = __double2float_rd((double)key_f32(T) - 2.0 * (double)a.margin);
+        if (a.min_score != -1.0f) thr = fmaxf(thr, __double2float_rd((double)a.min_score - (double)a.margin));
+    }
+    gst(&a.thr[lr], thr);
 }
 
 // one thread per candidate: its owner has one more
@@ -193,8 +201,9 @@ __global__ __launch_bounds__(1024) void neighbors_offsets_kernel(const NeighborA
     if (threadIdx.x == 0) gst(&a.row_off[launch_rows], carry);
 }
 
-// one thread per candidate: the canonical cosine, stored with the partner in a slot of the owner's stretch.  row_cnt counts down:
-// which slot a candidate gets depends on the order the atomics land in, what the select step reads from the stretch does not.
+// one thread per candidate: the canonical cosine, stored with the partner's order row in a slot of the owner's stretch (the image 0
+// where c is below the call's score bound: the f64 comparison the screen cannot make).  row_cnt counts down: which slot a candidate
+// gets depends on the order the atomics land in, what the select step reads from the stretch does not.
 __global__ __launch_bounds__(256) void neighbors_rescore_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
     const ScanParams& p = *pp;
     const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
@@ -207,20 +216,37 @@ __global__ __launch_bounds__(256) void neighbors_rescore_kernel(const ScanParams
     pair_sums<1>(ra.x, y, p.D4, acc, 32);
     const double cc = finish_score(PCV_METRIC_COSINE, acc[0], gld(&a.norm[la]), gld(&a.norm[lb]));
     const uint32_t slot = gld(&a.row_off[la]) + g_atomic_add32(&a.row_cnt[la], 0xffffffffu) - 1u;
-    gst(&a.sorted_key[slot], cc == cc ? f64_key(cc) : 0ull);  // (both rows have a cosine: c is a number)
-    gst(&a.sorted_row[slot], lb);
+    const bool in_bound = a.min_score == -1.0f || cc >= (double)a.min_score;
+    gst(&a.sorted_key[slot], (cc == cc && in_bound) ? f64_key(cc) : 0ull);  // (both rows have a cosine: c is a number)
+    gst(&a.sorted_row[slot], gld(&a.seg_ord0[rb.sg - p.seg]) + rb.row);
 }
 
-// (key descending, partner ascending): x comes before y
+// The row behind an order row (row_jobs.h): the last segment in position order whose first order row is not above it.
+__device__ __forceinline__ RowRef ord_ref(const ScanParams& p, const NeighborArgs& a, uint32_t orow) {
+    int lo = 0, hi = p.nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (gld(&a.seg_ord0[gld(&a.ord_seg[mid])]) <= orow)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    const uint32_t si = gld(&a.ord_seg[lo]);
+    const SegDesc* sg = &p.seg[si];
+    const uint32_t row = orow - gld(&a.seg_ord0[si]);
+    return {sg, row, gld(&sg->blk) + (size_t)(row >> 5) * p.D4 * 32 + (row & 31)};
+}
+
+// (key descending, partner ascending by order row, which is by global position): x comes before y
 __device__ __forceinline__ bool nbr_before(unsigned long long kx, uint32_t rx, unsigned long long ky, uint32_t ry) {
     return kx > ky || (kx == ky && rx < ry);
 }
 
-// a wave per launch row.  An owner's entries are distinct (a partner is listed once per owner), so "the best entry strictly behind
+// a wave per owner row.  An owner's entries are distinct (a partner is listed once per owner), so "the best entry strictly behind
 // the last pick" walks them in order without marking any.
 __global__ __launch_bounds__(256) void neighbors_select_kernel(const ScanParams* __restrict__ pp, const NeighborArgs a) {
     const ScanParams& p = *pp;
-    const uint32_t lr = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lr = a.owner_block0 * 32 + blockIdx.x * 4 + (threadIdx.x >> 6);
     if (lr >= p.total_blocks * 32) return;  // (the whole wave)
     const int lane = threadIdx.x & 63;
     const RowRef r = row_ref(p, lr);
@@ -254,7 +280,7 @@ __global__ __launch_bounds__(256) void neighbors_select_kernel(const ScanParams*
         last_key = bk;
         last_row = br;
         if (lane == 0) {
-            gst(&a.out_nbr[o * a.k + n], row_id(row_ref(p, br)));
+            gst(&a.out_nbr[o * a.k + n], row_id(ord_ref(p, a, br)));
             gst(&a.out_score[o * a.k + n], (float)key_f64(bk));
         }
     }
@@ -270,13 +296,14 @@ __global__ __launch_bounds__(256) void neighbors_select_kernel(const ScanParams*
 
 template <bool LIST>
 void launch_screen(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) {
-    if (p.total_blocks == 0) return;
+    if (a.owner_block0 >= p.total_blocks || a.partner_blocks == 0) return;
     const uint32_t NT = a.tile_blocks;
+    PCV_REQUIRE(a.partner_blocks <= p.total_blocks, "neighbors screen: %u partner blocks of %u", a.partner_blocks, p.total_blocks);
     PCV_REQUIRE((NT == 1 || NT == 2 || NT == 4) && a.stride >= 1 && a.span_len >= 1 && a.walk_len >= 1 && (LIST ? a.stride == 1 : a.spans <= kMaxNeighborSpans),
                 "neighbors screen: bad shape (tile of %u blocks, stride %u, spans of %u, walks of %u)", NT, a.stride, a.span_len, a.walk_len);
     const size_t lds = (size_t)NT * 32 * p.D4 * 4 * sizeof(uint16_t);
-    const unsigned tiles = (p.total_blocks + NT - 1) / NT;
-    const unsigned sampled = (p.total_blocks + a.stride - 1) / a.stride;
+    const unsigned tiles = (p.total_blocks - a.owner_block0 + NT - 1) / NT;
+    const unsigned sampled = (a.partner_blocks + a.stride - 1) / a.stride;
     const unsigned walks = (sampled + a.walk_len - 1) / a.walk_len;
     PCV_REQUIRE(walks <= 65535u, "neighbors screen: %u walks", walks);
     PCV_REQUIRE(LIST || (sampled + a.span_len - 1) / a.span_len == a.spans, "neighbors screen: %u spans of %u for %u sampled blocks", a.spans, a.span_len, sampled);
@@ -302,10 +329,10 @@ void launch_neighbors_bound(hipStream_t st, const ScanParams& p, const ScanParam
 void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) { launch_screen<true>(st, p, dp, a); }
 
 void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const NeighborArgs& a) {
-    if (p.total_blocks == 0) return;
+    if (a.owner_block0 >= p.total_blocks) return;
     PCV_REQUIRE(a.spans >= 1 && a.spans <= kMaxNeighborSpans && a.k >= 1, "neighbors threshold: %u spans, k = %d", a.spans, a.k);
-    const uint32_t launch_rows = p.total_blocks * 32;
-    neighbors_threshold_kernel<<<cdiv64((int64_t)launch_rows, 4), 256, 0, st>>>(a, launch_rows);
+    const uint32_t owner_rows = (p.total_blocks - a.owner_block0) * 32;
+    neighbors_threshold_kernel<<<cdiv64((int64_t)owner_rows, 4), 256, 0, st>>>(a, owner_rows);
     PCV_LAUNCHED();
 }
 
@@ -318,8 +345,8 @@ void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanPar
 }
 
 void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) {
-    if (p.total_blocks == 0) return;
-    neighbors_select_kernel<<<cdiv64((int64_t)p.total_blocks * 32, 4), 256, 0, st>>>(dp, a);
+    if (a.owner_block0 >= p.total_blocks) return;
+    neighbors_select_kernel<<<cdiv64((int64_t)(p.total_blocks - a.owner_block0) * 32, 4), 256, 0, st>>>(dp, a);
     PCV_LAUNCHED();
 }
 

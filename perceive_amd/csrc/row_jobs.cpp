@@ -1,5 +1,5 @@
 // row_jobs.cpp — host side of the calls that run kernels over the stored rows themselves (row_jobs.h): duplicate pairs, item labels,
-// neighbours, density clusters, the linkage tree, the reach tree, seeds, moments and projection, with their entry points of the C ABI.  They are one kind of call:
+// neighbours, matches, density clusters, the linkage tree, the reach tree, seeds, moments and projection, with their entry points of the C ABI.  They are one kind of call:
 // select segments, open a RowsJob over them, run the call's kernels over its launch rows, bring the result down.  Everything is
 // allocated for the call and given back when it ends; nothing of the searcher's pass state is touched.
 #include <algorithm>
@@ -44,8 +44,20 @@ uint32_t fill_row_table(const std::vector<SelSeg>& segs, SegDesc* tab, int64_t* 
     return (uint32_t)blk0;
 }
 
+// The segments' order by global position (row_jobs.h, NeighborArgs): ord0[i] = the launch row segment i's row 0 would have if the
+// launch were in that order, order[] = the table's indices sorted by it.  A table in position order gets ord0 = blk0 * 32.
+void fill_position_order(const SegDesc* tab, size_t nseg, uint32_t* ord0, uint32_t* order) {
+    std::iota(order, order + nseg, 0u);
+    std::sort(order, order + nseg, [&](uint32_t x, uint32_t y) { return tab[x].pos0 < tab[y].pos0; });
+    uint32_t rows = 0;
+    for (size_t i = 0; i < nseg; ++i) {
+        ord0[order[i]] = rows;
+        rows += tab[order[i]].nblocks * kBlockRows;
+    }
+}
+
 // What every call of this file opens over the segments it selected: the parameter block of the launch (ScanParams | SegDesc[nseg] |
-// seg_out0[nseg], built in pinned memory with its device mirror), the rows' rinv / norm as selfjoin_prep_kernel leaves them, and
+// seg_out0[nseg] | seg_ord0[nseg] | ord_seg[nseg], built in pinned memory with its device mirror), the rows' rinv / norm as selfjoin_prep_kernel leaves them, and
 // the events the call times its steps with.  Only the f32 rows are read.  A call declares its own buffers BEFORE its job: the job
 // then goes first, and it waits for the stream before an event is destroyed or a buffer that a queued kernel may still read is freed.
 struct RowsJob {
@@ -56,6 +68,8 @@ struct RowsJob {
     ScanParams* p = nullptr;  // (pinned)
     const ScanParams* dp = nullptr;
     const int64_t* seg_out0 = nullptr;  // [nseg] output index of each segment's row 0 (device)
+    const uint32_t* seg_ord0 = nullptr;  // [nseg], [nseg] the segments' order by global position (device; fill_position_order)
+    const uint32_t* ord_seg = nullptr;
     int64_t rows = 0;
     size_t nr = 0, n_rinv = 0;  // launch rows; entries of rinv
     DevBuf<float> d_rinv;
@@ -63,14 +77,23 @@ struct RowsJob {
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // (the longest call brackets five steps)
 
     // pad_blocks: the blocks of rinv behind total_blocks that must be there and zero (a tile kernel's tile_blocks; 0: none)
-    RowsJob(pcv_searcher* s, const std::vector<SelSeg>& segs, const char* what, int metric, uint32_t pad_blocks) : st(s->ctx->stream) {
+    // out0: the output index of each segment's row 0 where the launch order is not the output order (`match`); null: it is
+    RowsJob(pcv_searcher* s, const std::vector<SelSeg>& segs, const char* what, int metric, uint32_t pad_blocks, const int64_t* out0 = nullptr)
+        : st(s->ctx->stream) {
         PCV_HIP(hipSetDevice(s->ctx->device));
-        const size_t off_seg = align_up(sizeof(ScanParams)), off_out0 = align_up(off_seg + segs.size() * sizeof(SegDesc));
-        bytes = off_out0 + segs.size() * sizeof(int64_t);
+        const size_t nseg = segs.size();
+        const size_t off_seg = align_up(sizeof(ScanParams)), off_out0 = align_up(off_seg + nseg * sizeof(SegDesc));
+        const size_t off_ord = align_up(off_out0 + nseg * sizeof(int64_t));
+        bytes = off_ord + 2 * nseg * sizeof(uint32_t);
         pin_p.ensure(bytes);
         d_p.ensure(bytes);
         p = new (pin_p.p) ScanParams{};
-        p->total_blocks = fill_row_table(segs, reinterpret_cast<SegDesc*>(pin_p.p + off_seg), reinterpret_cast<int64_t*>(pin_p.p + off_out0), rows, what);
+        SegDesc* tab = reinterpret_cast<SegDesc*>(pin_p.p + off_seg);
+        p->total_blocks = fill_row_table(segs, tab, reinterpret_cast<int64_t*>(pin_p.p + off_out0), rows, what);
+        if (out0) std::memcpy(pin_p.p + off_out0, out0, nseg * sizeof(int64_t));
+        fill_position_order(tab, nseg, reinterpret_cast<uint32_t*>(pin_p.p + off_ord), reinterpret_cast<uint32_t*>(pin_p.p + off_ord) + nseg);
+        seg_ord0 = reinterpret_cast<const uint32_t*>(d_p.p + off_ord);
+        ord_seg = seg_ord0 + nseg;
         p->seg = reinterpret_cast<const SegDesc*>(d_p.p + off_seg);
         p->nseg = (int)segs.size();
         p->D = s->D;
@@ -551,19 +574,20 @@ uint32_t walk_blocks(uint32_t TB) {
     return walk_len;
 }
 
-// The sample of the neighbours' bound pass and its spans (DESIGN.md §4 "Item neighbours", measurement): no result depends on them,
-// only the list's length.
-void neighbor_sample(uint32_t TB, int k, uint32_t& stride, uint32_t& span_len, uint32_t& spans) {
-    stride = std::min<uint32_t>(4, std::max<uint32_t>(1, TB / (uint32_t)std::max(64, 4 * k)));
-    const uint32_t sampled = (TB + stride - 1) / stride;
+// The sample of the neighbours' bound pass over PB partner blocks and its spans (DESIGN.md §4 "Item neighbours", measurement): no
+// result depends on them, only the list's length.  No partner block: one empty span.
+void neighbor_sample(uint32_t PB, int k, uint32_t& stride, uint32_t& span_len, uint32_t& spans) {
+    stride = std::min<uint32_t>(4, std::max<uint32_t>(1, PB / (uint32_t)std::max(64, 4 * k)));
+    const uint32_t sampled = std::max<uint32_t>(1, (PB + stride - 1) / stride);
     const uint32_t want_spans = std::min<uint32_t>(sampled, std::min<uint32_t>(kMaxNeighborSpans, (uint32_t)std::max(64, 8 * k)));
     span_len = (sampled + want_spans - 1) / want_spans;
     spans = (sampled + span_len - 1) / span_len;
 }
 
-// The rescored candidates of every row's k best partners, as `neighbors` and the core step of `reach_tree` get them: the sample, the
-// buffers and their wiring, then bound pass, thresholds, list pass with the rerun rule, and the rescore that leaves sorted_key /
-// sorted_row / row_off.  Declared before the call's RowsJob, as every buffer is.  The counter of the list pass is the caller's, and so
+// The rescored candidates of every owner row's k best partners, as `neighbors`, `match` and the core step of `reach_tree` get them:
+// the sample, the buffers and their wiring, then bound pass, thresholds, list pass with the rerun rule, and the rescore that leaves
+// sorted_key / sorted_row / row_off.  The owners are the launch blocks [owner_block0, total_blocks), the partners [0, partner_blocks):
+// `neighbors` and `reach_tree` open it over the whole launch (open), `match` over its two ranges (open_ranges).  Declared before the call's RowsJob, as every buffer is.  The counter of the list pass is the caller's, and so
 // are the messages: `list` hands back what it counted.
 struct NeighborPlan {
     NeighborArgs a{};
@@ -571,21 +595,30 @@ struct NeighborPlan {
     DevBuf<uint32_t> d_span_max, d_cnt_off, d_sorted_row;
     DevBuf<unsigned long long> d_sorted_key;
     DevBuf<uint64_t> d_cand;
-    size_t nr = 0, n_pad = 0;
+    size_t nr = 0, n_pad = 0, n_span_max = 0;
 
     void open(const RowsJob& job, uint32_t tile_blocks, int k, float margin, unsigned long long* counter) {
+        open_ranges(job, tile_blocks, k, margin, counter, 0, job.p->total_blocks, -1.0f, job.rows);
+    }
+    // owner_rows: the rows of the owners' segments, which size the first candidate list
+    void open_ranges(const RowsJob& job, uint32_t tile_blocks, int k, float margin, unsigned long long* counter, uint32_t owner_block0,
+                     uint32_t partner_blocks, float min_score, int64_t owner_rows) {
         const uint32_t TB = job.p->total_blocks;
         a.tile_blocks = tile_blocks;
         a.k = k;
         a.margin = margin;
-        neighbor_sample(TB, k, a.stride, a.span_len, a.spans);
-        a.walk_len = walk_blocks(TB);
+        a.min_score = min_score;
+        a.owner_block0 = owner_block0;
+        a.partner_blocks = partner_blocks;
+        neighbor_sample(partner_blocks, k, a.stride, a.span_len, a.spans);
+        a.walk_len = walk_blocks(partner_blocks);
         nr = job.nr;
         n_pad = job.n_rinv;
+        n_span_max = (size_t)a.spans * (size_t)(TB - owner_block0) * kBlockRows;
         d_thr.ensure(n_pad);
-        d_span_max.ensure((size_t)a.spans * nr);
+        d_span_max.ensure(std::max<size_t>(1, n_span_max));
         d_cnt_off.ensure(2 * nr + 1);
-        a.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)k * (uint64_t)job.rows));
+        a.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)k * (uint64_t)owner_rows));
         d_cand.ensure(a.cand_cap);
         a.rinv = job.d_rinv.p;
         a.thr = d_thr.p;
@@ -595,13 +628,15 @@ struct NeighborPlan {
         a.row_off = d_cnt_off.p + nr;
         a.counters = counter;
         a.seg_out0 = job.seg_out0;
+        a.seg_ord0 = job.seg_ord0;
+        a.ord_seg = job.ord_seg;
     }
     void zero(hipStream_t st) {
         PCV_HIP(hipMemsetAsync(d_thr.p, 0, n_pad * sizeof(float), st));
-        PCV_HIP(hipMemsetAsync(d_span_max.p, 0, (size_t)a.spans * nr * sizeof(uint32_t), st));
+        if (n_span_max) PCV_HIP(hipMemsetAsync(d_span_max.p, 0, n_span_max * sizeof(uint32_t), st));
         PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
     }
-    // bound pass and thresholds up to ev[2], then the list pass over every block, timed from there
+    // bound pass and thresholds up to ev[2], then the list pass over every partner block, timed from there
     Listing list(RowsJob& job, unsigned long long (&count)[1], unsigned long long (&again)[1]) {
         launch_neighbors_bound(job.st, *job.p, job.dp, a);
         launch_neighbors_threshold(job.st, *job.p, a);
@@ -711,6 +746,119 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     PCV_HIP(hipMemcpy(out_counts, d_out_count.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
     int64_t listed = 0;
     for (int64_t i = 0; i < rows; ++i) listed += out_counts[i];
+    stats.listed = listed;
+}
+
+// ---- item matches (pcv_searcher_match; DESIGN.md §4 "Item matches") ----
+// The neighbours' steps over a rectangle: owners from one selection of segments, partners from another.  The launch is ordered
+// [to only | to and from | from only], each part in position order: the partners are then the block prefix every wave streams, the
+// owners the block suffix the tiles are cut from, and the work is |from| x |to| whatever the two selections share.  The launch order
+// is not the position order any more: seg_out0 carries each `from` segment's place in the outputs, and the select step breaks ties
+// by the order rows of the job (fill_position_order).  Everything the call allocates is its own and is given back when it ends.
+void match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const int64_t* to_source_ids, int n_to, int k, float min_score,
+           int64_t capacity, int64_t* out_ids, int64_t* out_match_ids, float* out_scores, int32_t* out_counts, int64_t* out_rows) {
+    PCV_REQUIRE(!s->dirty, "match: rows were added or cleared without pcv_searcher_finalize");
+    PCV_REQUIRE(s->shard_offset == 0, "match: a sharded searcher (set_shard_offset) is not supported");
+    const std::vector<SelSeg> from = select_segments(s, from_source_ids, n_from);
+    const int64_t n = selected_rows(from);
+    *out_rows = n;
+    if (out_ids == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "match: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    s->match_stats = pcv_match_stats{};
+    const int tile = mfma_pass_queries(s->Dp);
+    if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "match: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (n == 0) return;
+    const std::vector<SelSeg> to = select_segments(s, to_source_ids, n_to);
+    auto among = [](const std::vector<SelSeg>& v, const Segment* g) {
+        return std::any_of(v.begin(), v.end(), [&](const SelSeg& x) { return x.g == g; });
+    };
+    // the launch order and, beside it, the output index of each segment's row 0 (-1: no owners in it)
+    std::vector<SelSeg> segs;
+    std::vector<int64_t> out0;
+    uint32_t owner_block0 = 0, partner_blocks = 0;
+    for (const SelSeg& g : to)
+        if (!among(from, g.g)) {
+            segs.push_back(g);
+            out0.push_back(-1);
+            owner_block0 += g.g->nblocks();
+        }
+    partner_blocks = owner_block0;
+    for (int both = 1; both >= 0; --both) {
+        int64_t o = 0;
+        for (const SelSeg& g : from) {
+            if ((int)among(to, g.g) == both) {
+                segs.push_back(g);
+                out0.push_back(o);
+                if (both) partner_blocks += g.g->nblocks();
+            }
+            o += g.g->nrows;
+        }
+    }
+    NeighborPlan plan;
+    DevBuf<float> d_out_score;
+    DevBuf<unsigned long long> d_cnt;
+    DevBuf<int64_t> d_out_ids, d_out_nbr;
+    DevBuf<int32_t> d_out_count;
+    RowsJob job(s, segs, "match", PCV_METRIC_COSINE, (uint32_t)tile / kBlockRows, out0.data());
+    hipStream_t st = job.st;
+    const ScanParams& p = *job.p;
+    const ScanParams* dp = job.dp;
+
+    d_cnt.ensure(1);
+    plan.open_ranges(job, (uint32_t)tile / kBlockRows, k, selfjoin_margin(s->Dp), d_cnt.p, owner_block0, partner_blocks, min_score, n);
+    NeighborArgs& a = plan.a;
+    d_out_ids.ensure((size_t)n);
+    d_out_nbr.ensure((size_t)n * k);
+    d_out_score.ensure((size_t)n * k);
+    d_out_count.ensure((size_t)n);
+    a.out_ids = d_out_ids.p;
+    a.out_nbr = d_out_nbr.p;
+    a.out_score = d_out_score.p;
+    a.out_count = d_out_count.p;
+
+    pcv_match_stats& stats = s->match_stats;
+    stats.rows = n;
+    stats.partner_rows = selected_rows(to);
+    stats.owner_blocks = (int32_t)(p.total_blocks - owner_block0);
+    stats.partner_blocks = (int32_t)partner_blocks;
+    stats.k = k;
+    stats.tile_rows = tile;
+    stats.sample_stride = (int32_t)a.stride;
+    stats.spans = (int32_t)a.spans;
+
+    unsigned long long count[1] = {0}, again[1] = {0};
+    plan.zero(st);
+    PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+    job.prep();
+    const Listing list = plan.list(job, count, again);
+    stats.prep_ms = job.elapsed(0);
+    stats.bound_ms = job.elapsed(1);
+    stats.screen_ms = list.ms;
+    const uint64_t n_cand = count[0];
+    stats.candidates = (int64_t)n_cand;
+    if (n_cand > kMaxNeighborCandidates)
+        PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                 "match: the list pass leaves %llu candidates for k = %d and min_score %g, more than %llu: ask for fewer matches, a higher bound or "
+                 "fewer rows",
+                 (unsigned long long)n_cand, k, (double)min_score, (unsigned long long)kMaxNeighborCandidates);
+    if (list.repeated) {  // (the pass lists the same pairs again)
+        PCV_REQUIRE(again[0] == n_cand, "match: the repeated list pass left %llu candidates, the first %llu", again[0], (unsigned long long)n_cand);
+        stats.reruns = 1;
+        stats.screen_ms += list.again_ms;
+    }
+    plan.rescore(job, n_cand);
+    job.record(4);
+    launch_neighbors_select(st, p, dp, a);
+    job.record(5);
+    job.wait();
+    stats.rescore_ms = job.elapsed(3);
+    stats.select_ms = job.elapsed(4);
+    PCV_HIP(hipMemcpy(out_ids, d_out_ids.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_match_ids, d_out_nbr.p, (size_t)n * k * sizeof(int64_t), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_scores, d_out_score.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost));
+    PCV_HIP(hipMemcpy(out_counts, d_out_count.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t listed = 0;
+    for (int64_t i = 0; i < n; ++i) listed += out_counts[i];
     stats.listed = listed;
 }
 
@@ -1554,6 +1702,32 @@ pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats*
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_neighbor_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->nbr_stats;
+    });
+}
+
+pcv_status pcv_searcher_match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const int64_t* to_source_ids, int n_to, int k,
+                              float min_score, int64_t capacity, int64_t* out_ids, int64_t* out_match_ids, float* out_scores,
+                              int32_t* out_counts, int64_t* out_rows) {
+    return guarded([&] {
+        PCV_REQUIRE(out_rows != nullptr, "match: out_rows is NULL");
+        PCV_REQUIRE(k >= 1 && k <= (int)PCV_MAX_NEIGHBORS, "match: k %d outside [1,%d]", k, (int)PCV_MAX_NEIGHBORS);
+        PCV_REQUIRE(min_score == min_score, "match: min_score is NaN");
+        PCV_REQUIRE(min_score >= -1.0f && min_score <= 1.0f, "match: min_score %g outside [-1, 1]", (double)min_score);
+        PCV_REQUIRE(capacity >= 0, "match: capacity %lld is negative", (long long)capacity);
+        const bool all = out_ids != nullptr && out_match_ids != nullptr && out_scores != nullptr && out_counts != nullptr;
+        const bool none = out_ids == nullptr && out_match_ids == nullptr && out_scores == nullptr && out_counts == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "match: an output array is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "match: searcher is NULL");
+        const auto lk = enter(s, "match");
+        match(s, from_source_ids, n_from, to_source_ids, n_to, k, min_score, capacity, out_ids, out_match_ids, out_scores, out_counts, out_rows);
+    });
+}
+
+pcv_status pcv_searcher_last_match_stats(pcv_searcher* s, pcv_match_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_match_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->match_stats;
     });
 }
 

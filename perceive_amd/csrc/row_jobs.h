@@ -1,5 +1,5 @@
 // row_jobs.h — the calls that run kernels over the stored rows themselves, not over a scan's candidates (duplicate pairs, item labels,
-// neighbours, density clusters, the linkage tree, the reach tree, seeds, moments, projection): the arguments of their kernels and their launchers.
+// neighbours, matches, density clusters, the linkage tree, the reach tree, seeds, moments, projection): the arguments of their kernels and their launchers.
 // The host side is row_jobs.cpp; a scan pass needs nothing of this file.
 #pragma once
 #include "scan.h"
@@ -78,22 +78,30 @@ struct AssignArgs {
     uint32_t span_blocks;           // row blocks one screen workgroup streams (a multiple of its waves)
 };
 
-// Item neighbours (pcv_searcher_neighbors; DESIGN.md §4 "Item neighbours"): the k best other rows of every row.  Rows are launch
-// rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  A launch block with number gb is SAMPLED iff gb is a multiple of
-// stride; sampled block j = gb / stride belongs to span j / span_len.
-//   span_max[span][launch row] : the order-preserving image (f32_key) of the largest certified screening score of the row with a
+// Item neighbours and item matches (pcv_searcher_neighbors, pcv_searcher_match; DESIGN.md §4 "Item neighbours", "Item matches"): the
+// k best partner rows of every owner row.  Rows are launch rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  The OWNERS
+// are the rows of the launch blocks [owner_block0, total_blocks), the PARTNERS those of the blocks [0, partner_blocks): `neighbors`
+// and the core step of `reach_tree` pass the whole launch for both, `match` a launch ordered [to only | to and from | from only].  A
+// row is never its own partner.  A partner block with number gb is SAMPLED iff gb is a multiple of stride; sampled block
+// j = gb / stride belongs to span j / span_len.  An OWNER ROW is a launch row counted from owner_block0 * 32.
+//   span_max[span][owner row]  : the order-preserving image (f32_key) of the largest certified screening score of the row with a
 //                                partner of that span's sampled blocks, 0: none.  The spans are disjoint sets of partners.
-//   thr[launch row]            : (k-th largest defined span maximum) - 2 margin, rounded down; -inf: fewer than k are defined, or
-//                                the row is wild — every participating partner is a candidate
+//   thr[launch row]            : (k-th largest defined span maximum) - 2 margin, rounded down (-inf: fewer than k are defined), and
+//                                where the call has a score bound (min_score != -1) at least min_score - margin, rounded down;
+//                                -inf for a wild row — every participating partner is a candidate
+//   seg_ord0 / ord_seg         : the segments' order by global position, which the launch order of `match` is not: seg_ord0[i] is the
+//                                launch row segment i's row 0 would have in that order (an ORDER ROW: the tie-break of select, and
+//                                the launch row itself wherever the launch is in position order), ord_seg the segments sorted by it
 //   cand                       : (owner launch row << 32) | partner launch row, DIRECTED: the pair (a, b) is listed for owner a
 //                                iff s >= thr[a], and again for owner b iff s >= thr[b]
 //   row_off[launch row]        : where the owner's candidates start in sorted_key / sorted_row (an exclusive scan of row_cnt;
 //                                entry launch rows: the total); row_cnt is counted up, then counted down as the slots are taken
-//   sorted_key / sorted_row    : per owner, in any order: the f64_key image of c and the partner's launch row
+//   sorted_key / sorted_row    : per owner, in any order: the f64_key image of c (0: c is below the call's score bound) and the
+//                                partner's order row
 struct NeighborArgs {
     float* rinv;                    // [(total_blocks + tile_blocks) * 32], zero behind total_blocks * 32
     double* norm;                   // [total_blocks * 32]
-    uint32_t* span_max;             // [spans][total_blocks * 32]
+    uint32_t* span_max;             // [spans][(total_blocks - owner_block0) * 32]
     float* thr;                     // [(total_blocks + tile_blocks) * 32]
     uint64_t* cand;                 // [cand_cap]
     unsigned long long* counters;   // [0]: candidates the list pass found (not capped)
@@ -101,16 +109,21 @@ struct NeighborArgs {
     uint32_t* row_off;              // [total_blocks * 32 + 1]
     unsigned long long* sorted_key; // [n_cand]
     uint32_t* sorted_row;           // [n_cand]
-    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0
+    const int64_t* seg_out0;        // [nseg] output index of each segment's row 0 (segments with owners)
+    const uint32_t* seg_ord0;       // [nseg]
+    const uint32_t* ord_seg;        // [nseg]
     int64_t* out_ids;               // [rows]
     int64_t* out_nbr;               // [rows][k], unused slots -1
     float* out_score;               // [rows][k], unused slots NaN
     int32_t* out_count;             // [rows]
     unsigned long long cand_cap, n_cand;
     float margin;                   // selfjoin_margin(Dp)
+    float min_score;                // the score bound of `match`: c >= (double)min_score; exactly -1: none
     int k;
+    uint32_t owner_block0;          // the owners: launch blocks [owner_block0, total_blocks)
+    uint32_t partner_blocks;        // the partners: launch blocks [0, partner_blocks)
     uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
-    uint32_t stride;                // every stride-th block is a partner block of this launch (the list pass: 1)
+    uint32_t stride;                // every stride-th partner block is streamed by this launch (the list pass: 1)
     uint32_t span_len;              // sampled blocks of one span
     uint32_t spans;                 // ceil(sampled blocks / span_len), at most kMaxNeighborSpans
     uint32_t walk_len;              // sampled blocks one workgroup streams against its tile
@@ -349,7 +362,7 @@ void launch_assign_screen(hipStream_t st, const ScanParams& p, const ScanParams*
 void launch_assign_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
 void launch_assign_finish(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // winners -> outputs
 void launch_label_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
-// ---- item neighbours (neighbors_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
+// ---- item neighbours and item matches (neighbors_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
 void launch_neighbors_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);    // -> span_max
 void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const NeighborArgs& a);                      // span_max -> thr
 void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);     // thr -> cand

@@ -694,6 +694,40 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_last_neighbor_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.NeighborStats._fields_}
 
+    # ---- item matches (pcv_searcher_match) -----------------------------------------------------------
+    # The join of two sets of sources: `neighbors` with the owners drawn from one selection and the partners from another.
+    def match(self, from_sources, to_sources, k, min_score=-1.0):
+        """For every row of `from_sources` its exact k best rows of `to_sources` by canonical cosine (both metrics; ties: the row
+        stored first) among those with cosine >= min_score (-1.0: no bound) -> (ids [n] int64, match_ids [n, k] int64, scores [n, k]
+        f32, counts [n] int32), by global position; row i has counts[i] matches, best first, the unused slots -1 / NaN.  The two
+        selections may overlap; a row is never its own match.  match(X, X, k) is neighbors(X, k).  A view matches among its own rows."""
+        k = int(k)
+        if not 1 <= k <= PCV_MAX_NEIGHBORS:
+            raise ValueError("k outside [1, %d]" % PCV_MAX_NEIGHBORS)
+        src, nsrc, _keep = _source_filter(from_sources)
+        dst, ndst, _keep_to = _source_filter(to_sources)
+        lo = float(min_score)
+        n = C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_match(self._handle, src, nsrc, dst, ndst, k, lo, 0, None, None, None, None, C.byref(n)))
+        n = n.value
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        mids = np.empty((max(n, 1), k), dtype=np.int64)
+        scores = np.empty((max(n, 1), k), dtype=np.float32)
+        counts = np.empty(max(n, 1), dtype=np.int32)
+        got = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_match(
+                self._handle, src, nsrc, dst, ndst, k, lo, max(n, 1), _ffi.i64p(ids), _ffi.i64p(mids), _ffi.f32p(scores), _ffi.i32p(counts),
+                C.byref(got),
+            )
+        )
+        return ids[:n], mids[:n], scores[:n], counts[:n]
+
+    def last_match_stats(self):
+        st = _ffi.MatchStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_match_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.MatchStats._fields_}
+
     # ---- density clusters (pcv_searcher_density_clusters) -------------------------------------------
     # DBSCAN under the canonical cosine: the clusters, their number and the noise, with no number of groups to choose.
     def density_clusters(self, sources, threshold, min_items):

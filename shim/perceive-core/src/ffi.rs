@@ -89,6 +89,27 @@ pub struct pcv_neighbor_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_match_stats {
+    pub rows: i64,
+    pub partner_rows: i64,
+    pub owner_blocks: i32,
+    pub partner_blocks: i32,
+    pub candidates: i64,
+    pub listed: i64,
+    pub k: i32,
+    pub tile_rows: i32,
+    pub sample_stride: i32,
+    pub spans: i32,
+    pub reruns: i32,
+    pub prep_ms: f32,
+    pub bound_ms: f32,
+    pub screen_ms: f32,
+    pub rescore_ms: f32,
+    pub select_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_density_stats {
     pub rows: i64,
     pub participating: i64,
@@ -362,6 +383,8 @@ extern "C" {
     pub fn pcv_searcher_last_assign_stats(s: *mut pcv_searcher, out: *mut pcv_assign_stats) -> c_int;
     pub fn pcv_searcher_neighbors(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, capacity: i64, out_ids: *mut i64, out_neighbor_ids: *mut i64, out_scores: *mut f32, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_last_neighbor_stats(s: *mut pcv_searcher, out: *mut pcv_neighbor_stats) -> c_int;
+    pub fn pcv_searcher_match(s: *mut pcv_searcher, from_source_ids: *const i64, n_from: c_int, to_source_ids: *const i64, n_to: c_int, k: c_int, min_score: f32, capacity: i64, out_ids: *mut i64, out_match_ids: *mut i64, out_scores: *mut f32, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_last_match_stats(s: *mut pcv_searcher, out: *mut pcv_match_stats) -> c_int;
     pub fn pcv_searcher_density_clusters(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, min_items: c_int, capacity: i64, out_ids: *mut i64, out_label: *mut i32, out_kind: *mut int8_t, out_degree: *mut i32, out_rows: *mut i64, out_clusters: *mut i32) -> c_int;
     pub fn pcv_searcher_last_density_stats(s: *mut pcv_searcher, out: *mut pcv_density_stats) -> c_int;
     pub fn pcv_searcher_linkage_tree(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, capacity: i64, out_ids: *mut i64, out_part: *mut int8_t, out_pos_a: *mut i64, out_pos_b: *mut i64, out_id_a: *mut i64, out_id_b: *mut i64, out_c: *mut f64, out_rows: *mut i64, out_edges: *mut i64) -> c_int;

@@ -654,6 +654,60 @@ impl Searcher {
         (0..n as usize).map(|i| (ids[i], (0..counts[i] as usize).map(|j| (nbr[i * k + j], scores[i * k + j])).collect())).collect()
     }
 
+    /// Item matches (`pcv_searcher_match`; `match` is a keyword): for every item of the sources `from`, by global position, its
+    /// exact `k` best items of the sources `to` by cosine (clamped to PCV_MAX_NEIGHBORS) among those with cosine >= `min_score`
+    /// (-1.0: no bound), best first.  An item is never its own match; an empty `to` matches nothing.
+    /// Returns (item id, its matches as (id, cosine)) per item of `from`.
+    pub fn matches(&self, from: &[i64], to: &[i64], k: usize, min_score: f32) -> Vec<(i64, Vec<(i64, f32)>)> {
+        if self.handle.is_null() || k == 0 || from.is_empty() {
+            return Vec::new();
+        }
+        let k = k.min(ffi::PCV_MAX_NEIGHBORS as usize);
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_match(
+                self.handle,
+                from.as_ptr(),
+                from.len() as i32,
+                to.as_ptr(),
+                to.len() as i32,
+                k as i32,
+                min_score,
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                &mut n,
+            )
+        })
+        .expect("match failed");
+        let room = n.max(1) as usize;
+        let mut ids = vec![-1i64; room];
+        let mut mids = vec![-1i64; room * k];
+        let mut scores = vec![f32::NAN; room * k];
+        let mut counts = vec![0i32; room];
+        hip::check(unsafe {
+            ffi::pcv_searcher_match(
+                self.handle,
+                from.as_ptr(),
+                from.len() as i32,
+                to.as_ptr(),
+                to.len() as i32,
+                k as i32,
+                min_score,
+                room as i64,
+                ids.as_mut_ptr(),
+                mids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("match failed");
+        (0..n as usize).map(|i| (ids[i], (0..counts[i] as usize).map(|j| (mids[i * k + j], scores[i * k + j])).collect())).collect()
+    }
+
     /// Density clusters (`pcv_searcher_density_clusters`): DBSCAN under the cosine over the items of `sources`, by global
     /// position.  Two items are near iff their cosine is at least `threshold`; an item with `min_items - 1` near items or more is a
     /// core item; clusters are the connected components of the core items, numbered by their first core item.
