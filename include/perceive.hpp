@@ -339,6 +339,80 @@ inline NeighborTable match_handle(pcv_searcher* h, const std::vector<int64_t>& f
     return r;
 }
 
+// Searcher::neighbors_grouped / match_grouped / find_duplicates_grouped and their SearcherView forms (pcv_searcher_neighbors_grouped,
+// _match_grouped, _find_duplicates_grouped): neighbors, match and find_duplicates with the group table (set_groups) consulted.  flags:
+// PCV_GROUPS_SKIP_OWN — the items of the owner's own group are no partners of it; PCV_GROUPS_ONE_PER_GROUP — of every group only its
+// best member is kept; both, or 0 for the plain table.  `groups` holds the group of every reported partner, PCV_NO_GROUP for a
+// singleton and in unused slots.
+struct GroupedNeighborTable {
+    NeighborTable table;
+    std::vector<int64_t> groups;  // [n][k]
+};
+inline GroupedNeighborTable neighbors_grouped_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t k, uint32_t flags) {
+    GroupedNeighborTable g;
+    NeighborTable& r = g.table;
+    r.k = k;
+    if (sources.empty() || k == 0) return g;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    check(pcv_searcher_neighbors_grouped(h, sources.data(), (int)sources.size(), (int)k, flags, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &n));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.ids.resize(room);
+    r.neighbor_ids.resize(room * k);
+    r.scores.resize(room * k);
+    g.groups.resize(room * k);
+    r.counts.resize(room);
+    check(pcv_searcher_neighbors_grouped(h, sources.data(), (int)sources.size(), (int)k, flags, (int64_t)room, r.ids.data(), r.neighbor_ids.data(),
+                                         r.scores.data(), g.groups.data(), r.counts.data(), &n));
+    r.ids.resize((size_t)n);
+    r.neighbor_ids.resize((size_t)n * k);
+    r.scores.resize((size_t)n * k);
+    g.groups.resize((size_t)n * k);
+    r.counts.resize((size_t)n);
+    return g;
+}
+inline GroupedNeighborTable match_grouped_handle(pcv_searcher* h, const std::vector<int64_t>& from, const std::vector<int64_t>& to, size_t k,
+                                                 float min_score, uint32_t flags) {
+    GroupedNeighborTable g;
+    NeighborTable& r = g.table;
+    r.k = k;
+    if (from.empty() || k == 0) return g;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    const int64_t none = 0;
+    const int64_t* to_ids = to.empty() ? &none : to.data();  // (a NULL list would mean every source)
+    check(pcv_searcher_match_grouped(h, from.data(), (int)from.size(), to_ids, (int)to.size(), (int)k, min_score, flags, 0, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, &n));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.ids.resize(room);
+    r.neighbor_ids.resize(room * k);
+    r.scores.resize(room * k);
+    g.groups.resize(room * k);
+    r.counts.resize(room);
+    check(pcv_searcher_match_grouped(h, from.data(), (int)from.size(), to_ids, (int)to.size(), (int)k, min_score, flags, (int64_t)room, r.ids.data(),
+                                     r.neighbor_ids.data(), r.scores.data(), g.groups.data(), r.counts.data(), &n));
+    r.ids.resize((size_t)n);
+    r.neighbor_ids.resize((size_t)n * k);
+    r.scores.resize((size_t)n * k);
+    g.groups.resize((size_t)n * k);
+    r.counts.resize((size_t)n);
+    return g;
+}
+// total: the pairs of non-siblings; skipped: the sibling pairs at or above the threshold, which find_duplicates would report
+inline std::vector<DuplicatePair> find_duplicates_grouped_handle(pcv_searcher* h, const std::vector<int64_t>& sources, float threshold,
+                                                                 size_t max_pairs, int64_t* total, int64_t* skipped) {
+    if (total) *total = 0;
+    if (skipped) *skipped = 0;
+    if (sources.empty() || max_pairs == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    max_pairs = std::min<size_t>(max_pairs, PCV_MAX_DUPLICATE_PAIRS);
+    std::vector<int64_t> a(max_pairs), b(max_pairs);
+    std::vector<float> scores(max_pairs);
+    int64_t count = 0;
+    check(pcv_searcher_find_duplicates_grouped(h, sources.data(), (int)sources.size(), threshold, (int64_t)max_pairs, a.data(), b.data(),
+                                               scores.data(), &count, total, skipped));
+    std::vector<DuplicatePair> out;
+    for (int64_t i = 0; i < count; ++i) out.push_back({a[(size_t)i], b[(size_t)i], scores[(size_t)i]});
+    return out;
+}
+
 // Searcher::density_clusters / SearcherView::density_clusters (pcv_searcher_density_clusters): DBSCAN under the cosine over the items
 // of `sources`, by global position — the clusters, their number and the noise, with no number of groups to choose.
 struct DensityClusters {
@@ -723,6 +797,23 @@ public:
         check(pcv_searcher_last_match_stats(h_, &st));
         return st;
     }
+    // neighbors, match and find_duplicates with the group table consulted (neighbors_grouped_handle, ...)
+    GroupedNeighborTable neighbors_grouped(const std::vector<int64_t>& sources, size_t k, uint32_t flags = PCV_GROUPS_SKIP_OWN) const {
+        return neighbors_grouped_handle(h_, sources, k, flags);
+    }
+    GroupedNeighborTable match_grouped(const std::vector<int64_t>& from, const std::vector<int64_t>& to, size_t k, float min_score = -1.0f,
+                                       uint32_t flags = PCV_GROUPS_SKIP_OWN) const {
+        return match_grouped_handle(h_, from, to, k, min_score, flags);
+    }
+    std::vector<DuplicatePair> find_duplicates_grouped(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
+                                                       int64_t* total = nullptr, int64_t* skipped = nullptr) const {
+        return find_duplicates_grouped_handle(h_, sources, threshold, max_pairs, total, skipped);
+    }
+    pcv_pair_group_stats last_pair_group_stats() const {
+        pcv_pair_group_stats st;
+        check(pcv_searcher_last_pair_group_stats(h_, &st));
+        return st;
+    }
     // search by example among the view's items; the example is looked up in the parent (it need not be an allowed item)
     std::optional<std::vector<SearchItem>> search_like(const std::vector<int64_t>& sources, size_t num_results, int64_t item_id,
                                                        bool exclude = false) const {
@@ -918,6 +1009,23 @@ public:
     pcv_match_stats last_match_stats() const {
         pcv_match_stats st;
         check(pcv_searcher_last_match_stats(h_, &st));
+        return st;
+    }
+    // neighbors, match and find_duplicates with the group table consulted (neighbors_grouped_handle, ...)
+    GroupedNeighborTable neighbors_grouped(const std::vector<int64_t>& sources, size_t k, uint32_t flags = PCV_GROUPS_SKIP_OWN) const {
+        return neighbors_grouped_handle(h_, sources, k, flags);
+    }
+    GroupedNeighborTable match_grouped(const std::vector<int64_t>& from, const std::vector<int64_t>& to, size_t k, float min_score = -1.0f,
+                                       uint32_t flags = PCV_GROUPS_SKIP_OWN) const {
+        return match_grouped_handle(h_, from, to, k, min_score, flags);
+    }
+    std::vector<DuplicatePair> find_duplicates_grouped(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
+                                                       int64_t* total = nullptr, int64_t* skipped = nullptr) const {
+        return find_duplicates_grouped_handle(h_, sources, threshold, max_pairs, total, skipped);
+    }
+    pcv_pair_group_stats last_pair_group_stats() const {
+        pcv_pair_group_stats st;
+        check(pcv_searcher_last_pair_group_stats(h_, &st));
         return st;
     }
     // `perceive search --like <id>`: search with the stored embedding of an item, built on the device; as in the reference the

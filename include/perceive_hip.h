@@ -474,8 +474,8 @@ pcv_status pcv_searcher_group_stats(pcv_searcher* s, pcv_group_stats* out);
  * followed by a select step on the device whose cost is fixed (DESIGN.md §4 "Grouped results"), and one short pass more where
  * out_more has to be decided.  Known limit: a large group near a query costs passes — a 500-row document costs four; `pool`
  * bounds that and out_more reports it.
- * Not in scope: group-aware neighbours / duplicates / search by example, a sharded form, device-resident output, more than one
- * member per group. */
+ * Group-aware neighbours, matches and duplicate pairs: pcv_searcher_neighbors_grouped, _match_grouped, _find_duplicates_grouped below.
+ * Not in scope: group-aware search by example, a sharded form, device-resident output, more than one member per group. */
 enum { PCV_MAX_GROUPED_POOL = 4096 };
 pcv_status pcv_searcher_search_grouped(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
                                        int num_results, int pool, int64_t* out_ids, float* out_scores, int64_t* out_groups,
@@ -747,6 +747,56 @@ typedef struct pcv_match_stats {
     float select_ms;
 } pcv_match_stats;
 pcv_status pcv_searcher_last_match_stats(pcv_searcher* s, pcv_match_stats* out);
+
+/* Group-aware pairs: pcv_searcher_neighbors, pcv_searcher_match and pcv_searcher_find_duplicates over a corpus of chunks, where the
+ * group table (pcv_searcher_set_groups) says which rows are one document — "the k nearest rows of OTHER documents", "the k nearest
+ * other documents", "duplicates across documents".  The plain calls ignore the table and stay as they are.
+ * The existing rules of each call hold unchanged: which rows take part, the canonical f64 cosine, the order (c descending, position
+ * ascending), every argument rule, refusal and limit.
+ *   The GROUP of a row is the value its item id has in the table at call time (a view reads its parent's).  An id without an entry, or
+ *   with PCV_NO_GROUP, makes the ROW a singleton, exactly as in pcv_searcher_search_grouped.  Two different rows are SIBLINGS iff both
+ *   have a group >= 0 and the keys are equal: two ungrouped rows that share an id are not siblings, two rows that share an id with a
+ *   group are.
+ *   PCV_GROUPS_SKIP_OWN       a sibling of the owner is not a partner of it; the result is otherwise that of the plain call over the
+ *                             remaining partners.
+ *   PCV_GROUPS_ONE_PER_GROUP  the owner's partners are walked in order (after SKIP_OWN if set, after min_score for match); a partner is
+ *                             KEPT iff no kept partner is its sibling, and the walk ends after the k-th kept partner.  A kept partner
+ *                             is the best member of its group for this owner, the k kept are the k best groups by best member.
+ *                             Singletons never collapse.
+ *   flags == 0                the plain call, bit for bit (the partners' groups are still reported).
+ * out_neighbor_groups / out_match_groups: [capacity][k] the group key of every reported partner, PCV_NO_GROUP for a singleton and in
+ * unused slots; may be NULL.  Flags outside 0..3 give PCV_ERR_INVALID before the handle is looked at.  An empty or absent table is
+ * legal: every row is a singleton and the result is the plain call's.  The grouped calls fill pcv_searcher_last_neighbor_stats /
+ * _last_match_stats / _last_duplicate_stats as the plain ones do, and pcv_searcher_last_pair_group_stats beside them.
+ * pcv_searcher_find_duplicates_grouped always skips sibling pairs and takes no flags: out_total counts the pairs of non-siblings only,
+ * out_skipped (may be NULL) the sibling pairs with c >= threshold, which the plain call would report: out_total + out_skipped is the
+ * plain call's total.
+ * Exact (DESIGN.md §4 "Group-aware pairs"): the siblings are left out of the bound the screen's thresholds come from, and under
+ * ONE_PER_GROUP that bound counts distinct groups; every exact decision compares the 64-bit keys.  Cost beside the plain call: 12
+ * bytes per row for the rows' groups, 8 instead of 4 bytes per (row, span) of the bound pass, 8 bytes more per candidate.
+ * Not in scope: density clusters, the linkage tree and the reach tree, pcv_searcher_search_like, a sharded form, device-resident
+ * output. */
+enum { PCV_GROUPS_SKIP_OWN = 1, PCV_GROUPS_ONE_PER_GROUP = 2 };
+pcv_status pcv_searcher_neighbors_grouped(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, uint32_t flags, int64_t capacity,
+                                          int64_t* out_ids, int64_t* out_neighbor_ids, float* out_scores, int64_t* out_neighbor_groups,
+                                          int32_t* out_counts, int64_t* out_rows);
+pcv_status pcv_searcher_match_grouped(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const int64_t* to_source_ids, int n_to, int k,
+                                      float min_score, uint32_t flags, int64_t capacity, int64_t* out_ids, int64_t* out_match_ids,
+                                      float* out_scores, int64_t* out_match_groups, int32_t* out_counts, int64_t* out_rows);
+pcv_status pcv_searcher_find_duplicates_grouped(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs,
+                                                int64_t* out_id_a, int64_t* out_id_b, float* out_scores, int64_t* out_count,
+                                                int64_t* out_total, int64_t* out_skipped);
+
+/* Counters of the most recent grouped pair call on this handle (neighbors_grouped, match_grouped or find_duplicates_grouped). */
+typedef struct pcv_pair_group_stats {
+    int64_t grouped_rows;        /* launch rows that take part and have a group >= 0                                            */
+    int64_t sibling_candidates;  /* listed candidates the f64 step dropped as siblings (find_duplicates_grouped: out_skipped)   */
+    int64_t collapsed;           /* entries the select step passed over as members of a kept group (ONE_PER_GROUP)              */
+    uint32_t flags;              /* the call's flags (find_duplicates_grouped: PCV_GROUPS_SKIP_OWN)                             */
+    int32_t bound_tile_rows;     /* rows of the LDS tile of the bound pass: 64 at most in its grouped form (flags != 0)         */
+    float groups_ms;             /* hipEvent time of the step that gathers the rows' groups from the table                      */
+} pcv_pair_group_stats;
+pcv_status pcv_searcher_last_pair_group_stats(pcv_searcher* s, pcv_pair_group_stats* out);
 
 /* Density clusters: DBSCAN under the cosine over the stored items, exact, computed where the rows live — which topics a library
  * holds, how many, and which items belong to none, without the caller choosing a number of groups; degree(r) is a density and

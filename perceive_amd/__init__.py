@@ -4,6 +4,8 @@ is the thin host mirror.  Nothing here imports oracle/ (test infrastructure)."""
 from ._ffi import PcvError, LIB_PATH  # noqa: F401
 from .context import Context, device_count  # noqa: F401
 from .search import (  # noqa: F401
+    GROUPS_ONE_PER_GROUP,
+    GROUPS_SKIP_OWN,
     PCV_DENSITY_BORDER,
     PCV_DENSITY_CORE,
     PCV_DENSITY_NOISE,

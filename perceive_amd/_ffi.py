@@ -94,6 +94,17 @@ class NeighborStats(C.Structure):
     ]
 
 
+class PairGroupStats(C.Structure):
+    _fields_ = [
+        ("grouped_rows", C.c_int64),
+        ("sibling_candidates", C.c_int64),
+        ("collapsed", C.c_int64),
+        ("flags", C.c_uint32),
+        ("bound_tile_rows", C.c_int32),
+        ("groups_ms", C.c_float),
+    ]
+
+
 class MatchStats(C.Structure):
     _fields_ = [
         ("rows", C.c_int64),
@@ -325,6 +336,13 @@ SYMBOLS = {
     "pcv_searcher_match": (C.c_int, [_P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, _INTP,
                                      C.POINTER(C.c_int64)]),
     "pcv_searcher_last_match_stats": (C.c_int, [_P, C.POINTER(MatchStats)]),
+    "pcv_searcher_neighbors_grouped": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_uint32, C.c_int64, _I64P, _I64P, _F32P, _I64P, _INTP,
+                                                 C.POINTER(C.c_int64)]),
+    "pcv_searcher_match_grouped": (C.c_int, [_P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_uint32, C.c_int64, _I64P, _I64P, _F32P,
+                                             _I64P, _INTP, C.POINTER(C.c_int64)]),
+    "pcv_searcher_find_duplicates_grouped": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, C.POINTER(C.c_int64),
+                                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_pair_group_stats": (C.c_int, [_P, C.POINTER(PairGroupStats)]),
     "pcv_searcher_density_clusters": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int, C.c_int64, _I64P, _INTP, _I8P, _INTP,
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "pcv_searcher_last_density_stats": (C.c_int, [_P, C.POINTER(DensityStats)]),

@@ -17,6 +17,8 @@
 //   * grouped_select_kernel only reads the table; its own counters are integer adds in LDS, which commute.
 #include "corpus.h"
 #include "device_access.h"
+#include "group_table.h"
+#include "launch_rows.h"
 #include "scan.h"
 
 namespace pcv {
@@ -35,24 +37,6 @@ __device__ __forceinline__ int64_t key_claim(int64_t* p, int64_t id) {
 }
 __device__ __forceinline__ void count_add(int64_t* p, int64_t v) {
     __hip_atomic_fetch_add((PCV_GLOBAL u64*)p, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The slot that holds `id` (!= kIdEmpty), or the free slot its chain ends at: plain loads, for readers of a table at rest.
-// The table is never full (slots >= 2 * entries), so the walk ends.
-__device__ __forceinline__ uint32_t find_slot(const int64_t* __restrict__ keys, uint32_t mask, int64_t id) {
-    uint32_t h = id_hash(id, mask);
-    for (;; h = (h + 1) & mask) {
-        const int64_t k = gld(&keys[h]);
-        if (k == id || k == kIdEmpty) return h;
-    }
-}
-// The group of `id`, or -1.
-__device__ __forceinline__ int64_t group_of(const int64_t* __restrict__ keys, const int64_t* __restrict__ vals, uint32_t mask,
-                                            int64_t side_val, int64_t id) {
-    if (id == kIdEmpty) return side_val;
-    if (keys == nullptr) return -1;
-    const uint32_t h = find_slot(keys, mask, id);
-    return gld(&keys[h]) == id ? gld(&vals[h]) : (int64_t)-1;
 }
 
 __global__ __launch_bounds__(256) void group_fill_kernel(int64_t* __restrict__ keys, int64_t* __restrict__ vals, uint64_t slots) {
@@ -141,6 +125,23 @@ __global__ __launch_bounds__(256) void group_lookup_kernel(const int64_t* __rest
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     gst(&out[i], group_of(keys, vals, mask, gld(&head->side_val), gld(&ids[i])));
+}
+
+// The groups of a row job's launch rows (row_jobs.h, PairGroups), behind its prep step: one thread per launch row.  A row that takes
+// no part (rinv == 0) has no group here; the others get what the table holds for their id.  Plain vector stores to grp / tag, one
+// integer add per wave to the counter, nothing to the table.
+__global__ __launch_bounds__(256) void row_groups_kernel(const ScanParams* __restrict__ pp, const PairGroups a) {
+    const ScanParams& p = *pp;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    int64_t g = -1;
+    const bool in = i < (uint64_t)p.total_blocks * 32;
+    if (in && gld(&a.rinv[i]) != 0.0f) g = group_of(a.keys, a.vals, a.mask, a.side_val, row_id(row_ref(p, (uint32_t)i)));
+    if (in) {
+        gst(&a.grp[i], g);
+        gst(&a.tag[i], group_tag(g));
+    }
+    const u64 grouped = __ballot(g >= 0);
+    if ((threadIdx.x & 63) == 0 && grouped != 0) g_atomic_add64(&a.counters[kPairGroupRows], (unsigned long long)__popcll(grouped));
 }
 
 // The select step: one workgroup of kMaxK threads per query, thread t for hit t of the pass's list (p.out, best first; the hits
@@ -262,6 +263,13 @@ void launch_group_lookup(hipStream_t st, const int64_t* keys, const int64_t* val
                          uint32_t n, int64_t* out) {
     if (n == 0) return;
     group_lookup_kernel<<<cdiv64(n, 256), 256, 0, st>>>(keys, vals, mask, head, ids, n, out);
+    PCV_LAUNCHED();
+}
+
+void launch_row_groups(hipStream_t st, const ScanParams& p, const ScanParams* dp, const PairGroups& a) {
+    if (p.total_blocks == 0) return;
+    PCV_REQUIRE(a.keys == nullptr || (a.mask & (a.mask + 1)) == 0, "row groups: mask %#x", a.mask);
+    row_groups_kernel<<<cdiv64((int64_t)p.total_blocks * 32, 256), 256, 0, st>>>(dp, a);
     PCV_LAUNCHED();
 }
 

@@ -74,7 +74,7 @@ struct RowsJob {
     size_t nr = 0, n_rinv = 0;  // launch rows; entries of rinv
     DevBuf<float> d_rinv;
     DevBuf<double> d_norm;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // (the longest call brackets five steps)
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // (the longest call brackets five steps; 6, 7: the group gather)
 
     // pad_blocks: the blocks of rinv behind total_blocks that must be there and zero (a tile kernel's tile_blocks; 0: none)
     // out0: the output index of each segment's row 0 where the launch order is not the output order (`match`); null: it is
@@ -183,6 +183,53 @@ std::unique_lock<std::mutex> enter(pcv_searcher* s, const char* call) {
     return lk;
 }
 
+// The groups of a job's launch rows for the grouped calls (row_jobs.h, PairGroups; DESIGN.md §4 "Group-aware pairs"): grp, tag and the
+// three counters, filled behind the job's prep step from the group table of `owner` (s itself, or the parent of a view; locked by the
+// caller while the kernels may follow its pointers).  An empty or absent table makes every row a singleton.  Declared before the
+// call's RowsJob, as every buffer is.
+struct RowGroups {
+    PairGroups a{};
+    DevBuf<int64_t> d_grp;
+    DevBuf<uint32_t> d_tag;
+    DevBuf<unsigned long long> d_counters;
+    size_t n_tag = 0;
+
+    void open(const RowsJob& job, const pcv_searcher* owner) {
+        n_tag = job.n_rinv;
+        d_grp.ensure(std::max<size_t>(1, job.nr));
+        d_tag.ensure(std::max<size_t>(1, n_tag));
+        d_counters.ensure(kPairGroupCounters);
+        a.rinv = job.d_rinv.p;
+        a.keys = owner->groups.slots ? owner->groups.keys : nullptr;
+        a.vals = owner->groups.vals;
+        a.mask = owner->groups.slots ? (uint32_t)(owner->groups.slots - 1) : 0;
+        a.side_val = owner->groups.head.side_val;
+        a.grp = d_grp.p;
+        a.tag = d_tag.p;
+        a.counters = d_counters.p;
+    }
+    // before the job's prep, with the call's other memsets
+    void zero(hipStream_t st) {
+        PCV_HIP(hipMemsetAsync(d_tag.p, 0, std::max<size_t>(1, n_tag) * sizeof(uint32_t), st));
+        PCV_HIP(hipMemsetAsync(d_counters.p, 0, kPairGroupCounters * sizeof(unsigned long long), st));
+    }
+    // behind the job's prep: ev[6] .. ev[7]
+    void gather(RowsJob& job) {
+        job.record(6);
+        launch_row_groups(job.st, *job.p, job.dp, a);
+        job.record(7);
+    }
+    // once the job has waited: the counters and the gather's time into the call's stats
+    void finish(RowsJob& job, pcv_pair_group_stats& out) {
+        unsigned long long c[kPairGroupCounters];
+        PCV_HIP(hipMemcpy(c, d_counters.p, sizeof(c), hipMemcpyDeviceToHost));
+        out.grouped_rows = (int64_t)c[kPairGroupRows];
+        out.sibling_candidates = (int64_t)c[kPairGroupSiblings];
+        out.collapsed = (int64_t)c[kPairGroupCollapsed];
+        out.groups_ms = job.elapsed(6);
+    }
+};
+
 // ---- duplicate pairs (pcv_searcher_find_duplicates; DESIGN.md §4 "Duplicate pairs") ----
 // The screen may list four times the pairs a call may return before the call gives up: 2^26 entries of 8 bytes.
 constexpr uint64_t kMaxJoinCandidates = (uint64_t)4 * PCV_MAX_DUPLICATE_PAIRS;
@@ -191,12 +238,18 @@ constexpr uint32_t kJoinSpanBlocks = 256;  // blocks a work item streams against
 // Three steps on the device (selfjoin_kernels.hip): norms, the bf16 screen of every tile of rows against the rows behind it, the
 // canonical f64 cosine of what the screen listed.  The pairs come down once and are ordered here.  Everything the call allocates
 // is its own and is given back when it ends: nothing of the searcher's pass state is touched.
+// `groups` (find_duplicates_grouped): the searcher whose group table decides siblings; a pair of siblings with c >= threshold is
+// counted in out_skipped instead of emitted (the rescore step; the screens know nothing of groups: one threshold serves all pairs).
 void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs, int64_t* out_id_a,
-                     int64_t* out_id_b, float* out_scores, int64_t* out_count, int64_t* out_total) {
+                     int64_t* out_id_b, float* out_scores, int64_t* out_count, int64_t* out_total, const pcv_searcher* groups = nullptr,
+                     int64_t* out_skipped = nullptr) {
     PCV_REQUIRE(!s->dirty, "find_duplicates: rows were added or cleared without pcv_searcher_finalize");
     s->dup_stats = pcv_duplicate_stats{};
+    if (groups) s->pair_group_stats = pcv_pair_group_stats{};
+    if (groups) s->pair_group_stats.flags = kGroupsSkipOwn;
     *out_count = 0;
     if (out_total) *out_total = 0;
+    if (out_skipped) *out_skipped = 0;
     const int tile = mfma_pass_queries(s->Dp);
     if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "find_duplicates: a bf16 tile of %d-d rows does not fit the LDS", s->D);
     const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
@@ -204,6 +257,7 @@ void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, 
     DevBuf<unsigned long long> d_cnt;
     DevBuf<uint64_t> d_cand;
     DevBuf<DupPair> d_pairs;
+    RowGroups rg;
     SelfJoinArgs a{};
     a.tile_blocks = (uint32_t)tile / kBlockRows;
     RowsJob job(s, segs, "find_duplicates", s->metric, a.tile_blocks);
@@ -226,7 +280,17 @@ void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, 
 
     unsigned long long counts[2] = {0, 0}, again[2] = {0, 0};
     PCV_HIP(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(unsigned long long), st));
+    if (groups) {
+        rg.open(job, groups);
+        rg.zero(st);
+        a.grp = rg.a.grp;
+        a.skipped = rg.d_counters.p + kPairGroupSiblings;
+    }
     job.prep();
+    if (groups) {  // (the gather's two events lie between ev[0..1] of the prep and ev[1..2] of the screen: the screen is timed from its own)
+        rg.gather(job);
+        job.record(1);
+    }
     const Listing screen = list_candidates(
         job, 1, d_cnt.p, counts, again, a.cand_cap, kMaxJoinCandidates,
         [&] {
@@ -236,8 +300,13 @@ void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, 
         [&] { PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st)); }, d_cand);
     s->dup_stats.rows = rows;
     s->dup_stats.tile_rows = tile;
-    s->dup_stats.prep_ms = job.elapsed(0);
+    s->dup_stats.prep_ms = job.elapsed(0) - (groups ? job.elapsed(6) : 0.0f);
     s->dup_stats.screen_ms = screen.ms;
+    auto finish_groups = [&] {  // (the job has waited)
+        if (!groups) return;
+        rg.finish(job, s->pair_group_stats);
+        if (out_skipped) *out_skipped = s->pair_group_stats.sibling_candidates;
+    };
     const uint64_t n_cand = counts[0];
     s->dup_stats.candidates = (int64_t)n_cand;
     if (n_cand > kMaxJoinCandidates)
@@ -250,7 +319,10 @@ void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, 
         s->dup_stats.reruns = 1;
         s->dup_stats.screen_ms += screen.again_ms;
     }
-    if (n_cand == 0) return;
+    if (n_cand == 0) {
+        finish_groups();
+        return;
+    }
     a.n_cand = n_cand;
     a.pair_cap = std::min<uint64_t>(n_cand, (uint64_t)PCV_MAX_DUPLICATE_PAIRS);
     d_pairs.ensure(a.pair_cap);
@@ -261,6 +333,7 @@ void find_duplicates(pcv_searcher* s, const int64_t* source_ids, int n_sources, 
     PCV_HIP(hipMemcpyAsync(counts, d_cnt.p, sizeof(counts), hipMemcpyDeviceToHost, st));
     job.wait();
     s->dup_stats.rescore_ms = job.elapsed(2);
+    finish_groups();
     const uint64_t total = counts[1];
     s->dup_stats.pairs = (int64_t)total;
     if (total > (uint64_t)PCV_MAX_DUPLICATE_PAIRS)
@@ -595,8 +668,19 @@ struct NeighborPlan {
     DevBuf<uint32_t> d_span_max, d_cnt_off, d_sorted_row;
     DevBuf<unsigned long long> d_sorted_key;
     DevBuf<uint64_t> d_cand;
+    DevBuf<unsigned long long> d_span_max64;  // the grouped calls: the 64-bit span images, the partners' groups beside sorted_row
+    DevBuf<int64_t> d_sorted_grp;
     size_t nr = 0, n_pad = 0, n_span_max = 0;
 
+    // The mode, before open: off unless this is called (`neighbors`, `match` and the core step of `reach_tree` never do: their launches
+    // are the plain ones).  The rescore and select steps then carry the partners' groups; flags != 0 gives the bound pass and the
+    // thresholds their grouped form, over span images of 8 bytes instead of 4.
+    void with_groups(const RowGroups& rg, uint32_t flags) {
+        a.grp = rg.a.grp;
+        a.tag = rg.a.tag;
+        a.gcounters = rg.a.counters;
+        a.group_flags = flags;
+    }
     void open(const RowsJob& job, uint32_t tile_blocks, int k, float margin, unsigned long long* counter) {
         open_ranges(job, tile_blocks, k, margin, counter, 0, job.p->total_blocks, -1.0f, job.rows);
     }
@@ -616,7 +700,11 @@ struct NeighborPlan {
         n_pad = job.n_rinv;
         n_span_max = (size_t)a.spans * (size_t)(TB - owner_block0) * kBlockRows;
         d_thr.ensure(n_pad);
-        d_span_max.ensure(std::max<size_t>(1, n_span_max));
+        if (a.group_flags != 0) {
+            d_span_max64.ensure(std::max<size_t>(1, n_span_max));
+            a.span_max64 = d_span_max64.p;
+        }
+        d_span_max.ensure(a.group_flags != 0 ? 1 : std::max<size_t>(1, n_span_max));
         d_cnt_off.ensure(2 * nr + 1);
         a.cand_cap = std::min<uint64_t>(kMaxNeighborCandidates, std::max<uint64_t>(65536, (uint64_t)32 * (uint64_t)k * (uint64_t)owner_rows));
         d_cand.ensure(a.cand_cap);
@@ -633,7 +721,8 @@ struct NeighborPlan {
     }
     void zero(hipStream_t st) {
         PCV_HIP(hipMemsetAsync(d_thr.p, 0, n_pad * sizeof(float), st));
-        if (n_span_max) PCV_HIP(hipMemsetAsync(d_span_max.p, 0, n_span_max * sizeof(uint32_t), st));
+        if (n_span_max && a.group_flags == 0) PCV_HIP(hipMemsetAsync(d_span_max.p, 0, n_span_max * sizeof(uint32_t), st));
+        if (n_span_max && a.group_flags != 0) PCV_HIP(hipMemsetAsync(d_span_max64.p, 0, n_span_max * sizeof(unsigned long long), st));
         PCV_HIP(hipMemsetAsync(d_cnt_off.p, 0, (2 * nr + 1) * sizeof(uint32_t), st));
     }
     // bound pass and thresholds up to ev[2], then the list pass over every partner block, timed from there
@@ -657,6 +746,10 @@ struct NeighborPlan {
         d_sorted_row.ensure((size_t)std::max<uint64_t>(1, n_cand));
         a.sorted_key = d_sorted_key.p;
         a.sorted_row = d_sorted_row.p;
+        if (a.grp != nullptr) {
+            d_sorted_grp.ensure((size_t)std::max<uint64_t>(1, n_cand));
+            a.sorted_grp = d_sorted_grp.p;
+        }
         job.record(3);
         launch_neighbors_rescore(job.st, *job.p, job.dp, a);
     }
@@ -667,13 +760,17 @@ struct NeighborPlan {
         d_sorted_key.release();
         d_sorted_row.release();
         d_cand.release();
+        d_span_max64.release();
+        d_sorted_grp.release();
     }
 };
 
 // Prep, bound pass, thresholds, list pass, rescore, select (neighbors_kernels.hip).  Everything the call allocates is its own and
 // is given back when it ends: nothing of the searcher's pass state is touched, and only the f32 rows are read.
+// `groups` (neighbors_grouped): the searcher whose group table the call reads, with the PCV_GROUPS_* flags and the partners' groups.
 void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, int64_t capacity, int64_t* out_ids, int64_t* out_neighbor_ids,
-               float* out_scores, int32_t* out_counts, int64_t* out_rows) {
+               float* out_scores, int32_t* out_counts, int64_t* out_rows, const pcv_searcher* groups = nullptr, uint32_t flags = 0,
+               int64_t* out_groups = nullptr) {
     PCV_REQUIRE(!s->dirty, "neighbors: rows were added or cleared without pcv_searcher_finalize");
     PCV_REQUIRE(s->shard_offset == 0, "neighbors: a sharded searcher (set_shard_offset) is not supported");
     const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
@@ -682,13 +779,19 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     if (out_ids == nullptr && capacity == 0) return;  // the count alone
     PCV_REQUIRE(capacity >= n, "neighbors: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
     s->nbr_stats = pcv_neighbor_stats{};
+    if (groups) s->pair_group_stats = pcv_pair_group_stats{};
     const int tile = mfma_pass_queries(s->Dp);
     if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "neighbors: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (groups) {
+        s->pair_group_stats.flags = flags;
+        s->pair_group_stats.bound_tile_rows = flags != 0 ? std::min(tile, 2 * (int)kBlockRows) : tile;
+    }
     if (n == 0) return;
     NeighborPlan plan;
+    RowGroups rg;
     DevBuf<float> d_out_score;
     DevBuf<unsigned long long> d_cnt;
-    DevBuf<int64_t> d_out_ids, d_out_nbr;
+    DevBuf<int64_t> d_out_ids, d_out_nbr, d_out_grp;
     DevBuf<int32_t> d_out_count;
     RowsJob job(s, segs, "neighbors", PCV_METRIC_COSINE, (uint32_t)tile / kBlockRows);
     hipStream_t st = job.st;
@@ -697,6 +800,10 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     const int64_t rows = job.rows;
 
     d_cnt.ensure(1);
+    if (groups) {
+        rg.open(job, groups);
+        plan.with_groups(rg, flags);
+    }
     plan.open(job, (uint32_t)tile / kBlockRows, k, selfjoin_margin(s->Dp), d_cnt.p);
     NeighborArgs& a = plan.a;
     d_out_ids.ensure((size_t)rows);
@@ -707,6 +814,10 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     a.out_nbr = d_out_nbr.p;
     a.out_score = d_out_score.p;
     a.out_count = d_out_count.p;
+    if (groups) {
+        d_out_grp.ensure((size_t)rows * k);
+        a.out_grp = d_out_grp.p;
+    }
 
     pcv_neighbor_stats& stats = s->nbr_stats;
     stats.rows = rows;
@@ -718,9 +829,14 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     unsigned long long count[1] = {0}, again[1] = {0};
     plan.zero(st);
     PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+    if (groups) rg.zero(st);
     job.prep();
+    if (groups) {  // (ev[1] again behind the gather: the bound pass is timed from there, the prep up to the gather)
+        rg.gather(job);
+        job.record(1);
+    }
     const Listing list = plan.list(job, count, again);
-    stats.prep_ms = job.elapsed(0);
+    stats.prep_ms = job.elapsed(0) - (groups ? job.elapsed(6) : 0.0f);
     stats.bound_ms = job.elapsed(1);
     stats.screen_ms = list.ms;
     const uint64_t n_cand = count[0];
@@ -744,6 +860,8 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
     PCV_HIP(hipMemcpy(out_neighbor_ids, d_out_nbr.p, (size_t)rows * k * sizeof(int64_t), hipMemcpyDeviceToHost));
     PCV_HIP(hipMemcpy(out_scores, d_out_score.p, (size_t)rows * k * sizeof(float), hipMemcpyDeviceToHost));
     PCV_HIP(hipMemcpy(out_counts, d_out_count.p, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (groups && out_groups) PCV_HIP(hipMemcpy(out_groups, d_out_grp.p, (size_t)rows * k * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (groups) rg.finish(job, s->pair_group_stats);
     int64_t listed = 0;
     for (int64_t i = 0; i < rows; ++i) listed += out_counts[i];
     stats.listed = listed;
@@ -755,8 +873,10 @@ void neighbors(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k,
 // owners the block suffix the tiles are cut from, and the work is |from| x |to| whatever the two selections share.  The launch order
 // is not the position order any more: seg_out0 carries each `from` segment's place in the outputs, and the select step breaks ties
 // by the order rows of the job (fill_position_order).  Everything the call allocates is its own and is given back when it ends.
+// `groups` (match_grouped): as for the neighbours.
 void match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const int64_t* to_source_ids, int n_to, int k, float min_score,
-           int64_t capacity, int64_t* out_ids, int64_t* out_match_ids, float* out_scores, int32_t* out_counts, int64_t* out_rows) {
+           int64_t capacity, int64_t* out_ids, int64_t* out_match_ids, float* out_scores, int32_t* out_counts, int64_t* out_rows,
+           const pcv_searcher* groups = nullptr, uint32_t flags = 0, int64_t* out_groups = nullptr) {
     PCV_REQUIRE(!s->dirty, "match: rows were added or cleared without pcv_searcher_finalize");
     PCV_REQUIRE(s->shard_offset == 0, "match: a sharded searcher (set_shard_offset) is not supported");
     const std::vector<SelSeg> from = select_segments(s, from_source_ids, n_from);
@@ -765,8 +885,13 @@ void match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const in
     if (out_ids == nullptr && capacity == 0) return;  // the count alone
     PCV_REQUIRE(capacity >= n, "match: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
     s->match_stats = pcv_match_stats{};
+    if (groups) s->pair_group_stats = pcv_pair_group_stats{};
     const int tile = mfma_pass_queries(s->Dp);
     if (tile == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "match: a bf16 tile of %d-d rows does not fit the LDS", s->D);
+    if (groups) {
+        s->pair_group_stats.flags = flags;
+        s->pair_group_stats.bound_tile_rows = flags != 0 ? std::min(tile, 2 * (int)kBlockRows) : tile;
+    }
     if (n == 0) return;
     const std::vector<SelSeg> to = select_segments(s, to_source_ids, n_to);
     auto among = [](const std::vector<SelSeg>& v, const Segment* g) {
@@ -795,9 +920,10 @@ void match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const in
         }
     }
     NeighborPlan plan;
+    RowGroups rg;
     DevBuf<float> d_out_score;
     DevBuf<unsigned long long> d_cnt;
-    DevBuf<int64_t> d_out_ids, d_out_nbr;
+    DevBuf<int64_t> d_out_ids, d_out_nbr, d_out_grp;
     DevBuf<int32_t> d_out_count;
     RowsJob job(s, segs, "match", PCV_METRIC_COSINE, (uint32_t)tile / kBlockRows, out0.data());
     hipStream_t st = job.st;
@@ -805,6 +931,12 @@ void match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const in
     const ScanParams* dp = job.dp;
 
     d_cnt.ensure(1);
+    if (groups) {
+        rg.open(job, groups);
+        plan.with_groups(rg, flags);
+        d_out_grp.ensure((size_t)n * k);
+        plan.a.out_grp = d_out_grp.p;
+    }
     plan.open_ranges(job, (uint32_t)tile / kBlockRows, k, selfjoin_margin(s->Dp), d_cnt.p, owner_block0, partner_blocks, min_score, n);
     NeighborArgs& a = plan.a;
     d_out_ids.ensure((size_t)n);
@@ -829,9 +961,14 @@ void match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const in
     unsigned long long count[1] = {0}, again[1] = {0};
     plan.zero(st);
     PCV_HIP(hipMemsetAsync(d_cnt.p, 0, sizeof(unsigned long long), st));
+    if (groups) rg.zero(st);
     job.prep();
+    if (groups) {  // (as in `neighbors`)
+        rg.gather(job);
+        job.record(1);
+    }
     const Listing list = plan.list(job, count, again);
-    stats.prep_ms = job.elapsed(0);
+    stats.prep_ms = job.elapsed(0) - (groups ? job.elapsed(6) : 0.0f);
     stats.bound_ms = job.elapsed(1);
     stats.screen_ms = list.ms;
     const uint64_t n_cand = count[0];
@@ -857,6 +994,8 @@ void match(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const in
     PCV_HIP(hipMemcpy(out_match_ids, d_out_nbr.p, (size_t)n * k * sizeof(int64_t), hipMemcpyDeviceToHost));
     PCV_HIP(hipMemcpy(out_scores, d_out_score.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost));
     PCV_HIP(hipMemcpy(out_counts, d_out_count.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (groups && out_groups) PCV_HIP(hipMemcpy(out_groups, d_out_grp.p, (size_t)n * k * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (groups) rg.finish(job, s->pair_group_stats);
     int64_t listed = 0;
     for (int64_t i = 0; i < n; ++i) listed += out_counts[i];
     stats.listed = listed;
@@ -1626,6 +1765,37 @@ pcv_status pcv_searcher_find_duplicates(pcv_searcher* s, const int64_t* source_i
     });
 }
 
+// (a view reads its parent's table: the parent stays locked while the kernels may follow its pointers — pcv_searcher_search_grouped)
+static std::unique_lock<std::mutex> lock_group_owner(pcv_searcher* s) {
+    return s->view_parent ? std::unique_lock<std::mutex>(s->view_parent->mu) : std::unique_lock<std::mutex>();
+}
+
+pcv_status pcv_searcher_find_duplicates_grouped(pcv_searcher* s, const int64_t* source_ids, int n_sources, float threshold, int64_t max_pairs,
+                                                int64_t* out_id_a, int64_t* out_id_b, float* out_scores, int64_t* out_count,
+                                                int64_t* out_total, int64_t* out_skipped) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "find_duplicates_grouped: searcher is NULL");
+        PCV_REQUIRE(out_id_a != nullptr && out_id_b != nullptr && out_count != nullptr,
+                    "find_duplicates_grouped: out_id_a, out_id_b or out_count is NULL");
+        PCV_REQUIRE(max_pairs >= 1 && max_pairs <= (int64_t)PCV_MAX_DUPLICATE_PAIRS, "find_duplicates_grouped: max_pairs %lld outside [1,%d]",
+                    (long long)max_pairs, (int)PCV_MAX_DUPLICATE_PAIRS);
+        PCV_REQUIRE(threshold == threshold, "find_duplicates_grouped: threshold is NaN");
+        PCV_REQUIRE(threshold > -1.0f && threshold <= 1.0f, "find_duplicates_grouped: threshold %g outside (-1, 1]", (double)threshold);
+        const auto lk = enter(s, "find_duplicates_grouped");
+        const auto plk = lock_group_owner(s);
+        find_duplicates(s, source_ids, n_sources, threshold, max_pairs, out_id_a, out_id_b, out_scores, out_count, out_total,
+                        s->view_parent ? s->view_parent : s, out_skipped);
+    });
+}
+
+pcv_status pcv_searcher_last_pair_group_stats(pcv_searcher* s, pcv_pair_group_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_pair_group_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->pair_group_stats;
+    });
+}
+
 pcv_status pcv_searcher_last_duplicate_stats(pcv_searcher* s, pcv_duplicate_stats* out) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_duplicate_stats: NULL argument");
@@ -1697,6 +1867,26 @@ pcv_status pcv_searcher_neighbors(pcv_searcher* s, const int64_t* source_ids, in
     });
 }
 
+pcv_status pcv_searcher_neighbors_grouped(pcv_searcher* s, const int64_t* source_ids, int n_sources, int k, uint32_t flags, int64_t capacity,
+                                          int64_t* out_ids, int64_t* out_neighbor_ids, float* out_scores, int64_t* out_neighbor_groups,
+                                          int32_t* out_counts, int64_t* out_rows) {
+    return guarded([&] {
+        PCV_REQUIRE(flags <= (uint32_t)(PCV_GROUPS_SKIP_OWN | PCV_GROUPS_ONE_PER_GROUP), "neighbors_grouped: flags %#x outside 0..3", flags);
+        PCV_REQUIRE(out_rows != nullptr, "neighbors_grouped: out_rows is NULL");
+        PCV_REQUIRE(k >= 1 && k <= (int)PCV_MAX_NEIGHBORS, "neighbors_grouped: k %d outside [1,%d]", k, (int)PCV_MAX_NEIGHBORS);
+        PCV_REQUIRE(capacity >= 0, "neighbors_grouped: capacity %lld is negative", (long long)capacity);
+        const bool all = out_ids != nullptr && out_neighbor_ids != nullptr && out_scores != nullptr && out_counts != nullptr;
+        const bool none = out_ids == nullptr && out_neighbor_ids == nullptr && out_scores == nullptr && out_counts == nullptr &&
+                          out_neighbor_groups == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "neighbors_grouped: an output array is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "neighbors_grouped: searcher is NULL");
+        const auto lk = enter(s, "neighbors_grouped");
+        const auto plk = lock_group_owner(s);
+        neighbors(s, source_ids, n_sources, k, capacity, out_ids, out_neighbor_ids, out_scores, out_counts, out_rows,
+                  s->view_parent ? s->view_parent : s, flags, out_neighbor_groups);
+    });
+}
+
 pcv_status pcv_searcher_last_neighbor_stats(pcv_searcher* s, pcv_neighbor_stats* out) {
     return guarded([&] {
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_neighbor_stats: NULL argument");
@@ -1720,6 +1910,28 @@ pcv_status pcv_searcher_match(pcv_searcher* s, const int64_t* from_source_ids, i
         PCV_REQUIRE(s != nullptr, "match: searcher is NULL");
         const auto lk = enter(s, "match");
         match(s, from_source_ids, n_from, to_source_ids, n_to, k, min_score, capacity, out_ids, out_match_ids, out_scores, out_counts, out_rows);
+    });
+}
+
+pcv_status pcv_searcher_match_grouped(pcv_searcher* s, const int64_t* from_source_ids, int n_from, const int64_t* to_source_ids, int n_to, int k,
+                                      float min_score, uint32_t flags, int64_t capacity, int64_t* out_ids, int64_t* out_match_ids,
+                                      float* out_scores, int64_t* out_match_groups, int32_t* out_counts, int64_t* out_rows) {
+    return guarded([&] {
+        PCV_REQUIRE(flags <= (uint32_t)(PCV_GROUPS_SKIP_OWN | PCV_GROUPS_ONE_PER_GROUP), "match_grouped: flags %#x outside 0..3", flags);
+        PCV_REQUIRE(out_rows != nullptr, "match_grouped: out_rows is NULL");
+        PCV_REQUIRE(k >= 1 && k <= (int)PCV_MAX_NEIGHBORS, "match_grouped: k %d outside [1,%d]", k, (int)PCV_MAX_NEIGHBORS);
+        PCV_REQUIRE(min_score == min_score, "match_grouped: min_score is NaN");
+        PCV_REQUIRE(min_score >= -1.0f && min_score <= 1.0f, "match_grouped: min_score %g outside [-1, 1]", (double)min_score);
+        PCV_REQUIRE(capacity >= 0, "match_grouped: capacity %lld is negative", (long long)capacity);
+        const bool all = out_ids != nullptr && out_match_ids != nullptr && out_scores != nullptr && out_counts != nullptr;
+        const bool none = out_ids == nullptr && out_match_ids == nullptr && out_scores == nullptr && out_counts == nullptr &&
+                          out_match_groups == nullptr;
+        PCV_REQUIRE(all || (none && capacity == 0), "match_grouped: an output array is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(s != nullptr, "match_grouped: searcher is NULL");
+        const auto lk = enter(s, "match_grouped");
+        const auto plk = lock_group_owner(s);
+        match(s, from_source_ids, n_from, to_source_ids, n_to, k, min_score, capacity, out_ids, out_match_ids, out_scores, out_counts, out_rows,
+              s->view_parent ? s->view_parent : s, flags, out_match_groups);
     });
 }
 

@@ -30,7 +30,34 @@ struct SelfJoinArgs {
     double threshold;
     uint32_t tile_blocks;           // blocks of the LDS tile (4, 2 or 1)
     uint32_t span_blocks;           // blocks of one work item's stream
+    const int64_t* grp;             // [total_blocks * 32] the rows' groups (PairGroups), or null: pcv_searcher_find_duplicates_grouped
+    unsigned long long* skipped;    // with grp: sibling pairs with c >= threshold, counted and not emitted
 };
+
+// The groups of a row job's launch rows (pcv_searcher_neighbors_grouped, _match_grouped, _find_duplicates_grouped; DESIGN.md §4
+// "Group-aware pairs"), gathered once behind the prep step from the searcher's group table (corpus.h):
+//   grp[launch row] : the group key the row's id has in the table, -1: none (no entry, PCV_NO_GROUP, or the row takes no part).
+//                     Two different rows are SIBLINGS iff both have grp >= 0 and the keys are equal: every exact step compares these
+//   tag[launch row] : 0: no group, otherwise ((uint32_t)key & 0x7fffffff) + 1.  Equal keys give equal non-zero tags, different keys
+//                     may collide: only the bound pass reads it, where "same group" by mistake can only lower a lower bound.  Zero
+//                     behind total_blocks * 32
+struct PairGroups {
+    const float* rinv;              // [total_blocks * 32] as selfjoin_prep_kernel leaves it
+    const int64_t* keys;            // the table (null: no slots)
+    const int64_t* vals;
+    uint32_t mask;
+    int64_t side_val;
+    int64_t* grp;                   // [total_blocks * 32]
+    uint32_t* tag;                  // [(total_blocks + tile_blocks) * 32]
+    unsigned long long* counters;   // kPairGroup* below
+};
+enum : int {
+    kPairGroupRows = 0,   // launch rows with a group >= 0
+    kPairGroupSiblings,   // listed candidates the f64 step dropped as siblings
+    kPairGroupCollapsed,  // entries the select step passed over as members of a kept group
+    kPairGroupCounters
+};
+constexpr uint32_t kGroupsSkipOwn = 1u, kGroupsOnePerGroup = 2u;  // PCV_GROUPS_* (perceive_hip.h)
 
 // Item labels (pcv_searcher_assign, _label_sums, _kmeans; DESIGN.md §4 "Item labels"): every row against K label vectors.  Rows are
 // launch rows as above, with rinv / norm exactly as selfjoin_prep_kernel leaves them (under the dot metric a participating row
@@ -127,6 +154,15 @@ struct NeighborArgs {
     uint32_t span_len;              // sampled blocks of one span
     uint32_t spans;                 // ceil(sampled blocks / span_len), at most kMaxNeighborSpans
     uint32_t walk_len;              // sampled blocks one workgroup streams against its tile
+    // the grouped calls (PairGroups above; all null / 0 in the plain ones, whose launches do not read them)
+    const int64_t* grp;             // [total_blocks * 32]; not null: the rescore step stores sorted_grp and drops siblings under
+                                    // kGroupsSkipOwn, the select step writes out_grp and collapses under kGroupsOnePerGroup
+    const uint32_t* tag;            // [(total_blocks + tile_blocks) * 32]
+    unsigned long long* span_max64; // [spans][owner rows] group_flags != 0: (f32_key(maximum) << 32) | tag of a partner reaching it
+    int64_t* sorted_grp;            // [n_cand] the partner's group, beside sorted_row
+    int64_t* out_grp;               // [rows][k], unused slots -1
+    unsigned long long* gcounters;  // kPairGroup*
+    uint32_t group_flags;           // kGroupsSkipOwn | kGroupsOnePerGroup; != 0: the bound pass and the thresholds take their grouped form
 };
 constexpr uint32_t kMaxNeighborSpans = 512;  // (the threshold kernel keeps a row's maxima in eight registers a lane)
 
@@ -368,6 +404,8 @@ void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const Neigh
 void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);     // thr -> cand
 void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);  // cand -> sorted_*
 void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);   // sorted_* -> outputs
+// ---- the rows' groups (grouped_kernels.hip); behind launch_selfjoin_prep ----
+void launch_row_groups(hipStream_t st, const ScanParams& p, const ScanParams* dp, const PairGroups& a);  // rinv, the table -> grp, tag
 // ---- density clusters (density_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
 void launch_density_degree(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);   // -> degree, cand, counters
 void launch_density_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const DensityArgs& a);  // cand -> degree, conf

@@ -250,6 +250,7 @@ struct pcv_searcher {
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
     pcv_neighbor_stats nbr_stats{};   // pcv_searcher_neighbors (likewise)
     pcv_match_stats match_stats{};    // pcv_searcher_match (likewise)
+    pcv_pair_group_stats pair_group_stats{};  // the last of pcv_searcher_neighbors_grouped, _match_grouped, _find_duplicates_grouped
     pcv_seed_stats seed_stats{};      // pcv_searcher_seeds (likewise)
     pcv_density_stats density_stats{};  // pcv_searcher_density_clusters (likewise)
     pcv_linkage_stats linkage_stats{};  // pcv_searcher_linkage_tree (likewise)

@@ -123,6 +123,13 @@ __global__ __launch_bounds__(256) void selfjoin_rescore_kernel(const ScanParams*
     pair_sums<1>(ra.x, y, p.D4, acc, 32);
     const double cc = finish_score(PCV_METRIC_COSINE, acc[0], gld(&a.norm[la]), gld(&a.norm[lb]));
     if (!(cc >= a.threshold)) return;
+    if (a.grp != nullptr) {  // find_duplicates_grouped: a pair of siblings (the 64-bit keys, row_jobs.h PairGroups) is counted, not emitted
+        const int64_t ga = gld(&a.grp[la]);
+        if (ga >= 0 && ga == gld(&a.grp[lb])) {
+            (void)g_atomic_add64(a.skipped, 1ull);
+            return;
+        }
+    }
     const unsigned long long at = g_atomic_add64(&a.counters[1], 1ull);
     if (at >= a.pair_cap) return;
     const int64_t pa = gld(&ra.sg->pos0) + (int64_t)ra.row, pb = gld(&rb.sg->pos0) + (int64_t)rb.row;

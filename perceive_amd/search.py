@@ -18,6 +18,7 @@ PCV_MAX_GROUPED_POOL = 4096  # include/perceive_hip.h
 PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_of / search_grouped
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
+GROUPS_SKIP_OWN, GROUPS_ONE_PER_GROUP = 1, 2  # include/perceive_hip.h: PCV_GROUPS_*, the flags of the grouped pair calls
 PCV_MAX_SEEDS = 4096  # include/perceive_hip.h
 PCV_DENSITY_NONE, PCV_DENSITY_NOISE, PCV_DENSITY_BORDER, PCV_DENSITY_CORE = -1, 0, 1, 2  # include/perceive_hip.h: out_kind
 PCV_MAX_AXES = 64  # include/perceive_hip.h
@@ -727,6 +728,90 @@ class Searcher:
         st = _ffi.MatchStats()
         _ffi.check(_ffi.lib().pcv_searcher_last_match_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.MatchStats._fields_}
+
+    # ---- group-aware pairs (pcv_searcher_neighbors_grouped / _match_grouped / _find_duplicates_grouped) ----
+    # neighbors, match and find_duplicates over a corpus of chunks: the group table (set_groups) says which rows are one document.
+    def neighbors_grouped(self, sources, k, flags=GROUPS_SKIP_OWN):
+        """neighbors(sources, k) with the group table consulted -> (ids [n] int64, neighbor_ids [n, k] int64, scores [n, k] f32,
+        neighbor_groups [n, k] int64 (NO_GROUP for a singleton and in unused slots), counts [n] int32).  flags: GROUPS_SKIP_OWN —
+        the rows of the owner's own group are no partners of it; GROUPS_ONE_PER_GROUP — of every group only its best member is
+        kept, the k best groups by best member; both, or 0 for the plain result."""
+        k, flags = int(k), int(flags)
+        if not 1 <= k <= PCV_MAX_NEIGHBORS:
+            raise ValueError("k outside [1, %d]" % PCV_MAX_NEIGHBORS)
+        if not 0 <= flags <= 3:
+            raise ValueError("flags outside 0..3")
+        src, nsrc, _keep = _source_filter(sources)
+        n = C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_neighbors_grouped(self._handle, src, nsrc, k, flags, 0, None, None, None, None, None, C.byref(n)))
+        n = n.value
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        nbr = np.empty((max(n, 1), k), dtype=np.int64)
+        scores = np.empty((max(n, 1), k), dtype=np.float32)
+        groups = np.empty((max(n, 1), k), dtype=np.int64)
+        counts = np.empty(max(n, 1), dtype=np.int32)
+        got = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_neighbors_grouped(
+                self._handle, src, nsrc, k, flags, max(n, 1), _ffi.i64p(ids), _ffi.i64p(nbr), _ffi.f32p(scores), _ffi.i64p(groups),
+                _ffi.i32p(counts), C.byref(got),
+            )
+        )
+        return ids[:n], nbr[:n], scores[:n], groups[:n], counts[:n]
+
+    def match_grouped(self, from_sources, to_sources, k, min_score=-1.0, flags=GROUPS_SKIP_OWN):
+        """match(from_sources, to_sources, k, min_score) with the group table consulted, as neighbors_grouped does -> (ids [n]
+        int64, match_ids [n, k] int64, scores [n, k] f32, match_groups [n, k] int64, counts [n] int32)."""
+        k, flags = int(k), int(flags)
+        if not 1 <= k <= PCV_MAX_NEIGHBORS:
+            raise ValueError("k outside [1, %d]" % PCV_MAX_NEIGHBORS)
+        if not 0 <= flags <= 3:
+            raise ValueError("flags outside 0..3")
+        src, nsrc, _keep = _source_filter(from_sources)
+        dst, ndst, _keep_to = _source_filter(to_sources)
+        lo = float(min_score)
+        n = C.c_int64()
+        _ffi.check(_ffi.lib().pcv_searcher_match_grouped(self._handle, src, nsrc, dst, ndst, k, lo, flags, 0, None, None, None, None, None, C.byref(n)))
+        n = n.value
+        ids = np.empty(max(n, 1), dtype=np.int64)
+        mids = np.empty((max(n, 1), k), dtype=np.int64)
+        scores = np.empty((max(n, 1), k), dtype=np.float32)
+        groups = np.empty((max(n, 1), k), dtype=np.int64)
+        counts = np.empty(max(n, 1), dtype=np.int32)
+        got = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_match_grouped(
+                self._handle, src, nsrc, dst, ndst, k, lo, flags, max(n, 1), _ffi.i64p(ids), _ffi.i64p(mids), _ffi.f32p(scores),
+                _ffi.i64p(groups), _ffi.i32p(counts), C.byref(got),
+            )
+        )
+        return ids[:n], mids[:n], scores[:n], groups[:n], counts[:n]
+
+    def find_duplicates_grouped(self, sources, threshold, max_pairs=1 << 20):
+        """find_duplicates(sources, threshold, max_pairs) without the pairs of rows of one group -> (id_a [n] int64, id_b [n]
+        int64, scores [n] f32, total, skipped): total counts the pairs of non-siblings, skipped the sibling pairs at or above the
+        threshold, which find_duplicates would report."""
+        m = int(max_pairs)
+        if not 1 <= m <= PCV_MAX_DUPLICATE_PAIRS:
+            raise ValueError("max_pairs outside [1, 2^24]")
+        id_a = np.empty(m, dtype=np.int64)
+        id_b = np.empty(m, dtype=np.int64)
+        scores = np.empty(m, dtype=np.float32)
+        count, total, skipped = C.c_int64(), C.c_int64(), C.c_int64()
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_find_duplicates_grouped(
+                self._handle, src, nsrc, float(threshold), m, _ffi.i64p(id_a), _ffi.i64p(id_b), _ffi.f32p(scores), C.byref(count),
+                C.byref(total), C.byref(skipped),
+            )
+        )
+        n = count.value
+        return id_a[:n].copy(), id_b[:n].copy(), scores[:n].copy(), total.value, skipped.value
+
+    def last_pair_group_stats(self):
+        st = _ffi.PairGroupStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_pair_group_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.PairGroupStats._fields_}
 
     # ---- density clusters (pcv_searcher_density_clusters) -------------------------------------------
     # DBSCAN under the canonical cosine: the clusters, their number and the noise, with no number of groups to choose.

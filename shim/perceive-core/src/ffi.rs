@@ -110,6 +110,17 @@ pub struct pcv_match_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_pair_group_stats {
+    pub grouped_rows: i64,
+    pub sibling_candidates: i64,
+    pub collapsed: i64,
+    pub flags: u32,
+    pub bound_tile_rows: i32,
+    pub groups_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_density_stats {
     pub rows: i64,
     pub participating: i64,
@@ -288,6 +299,8 @@ pub const PCV_MAX_DIVERSE_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
 pub const PCV_MAX_NEIGHBORS: c_int = 64;
+pub const PCV_GROUPS_SKIP_OWN: c_int = 1;
+pub const PCV_GROUPS_ONE_PER_GROUP: c_int = 2;
 pub const PCV_DENSITY_NONE: c_int = -1;
 pub const PCV_DENSITY_NOISE: c_int = 0;
 pub const PCV_DENSITY_BORDER: c_int = 1;
@@ -385,6 +398,10 @@ extern "C" {
     pub fn pcv_searcher_last_neighbor_stats(s: *mut pcv_searcher, out: *mut pcv_neighbor_stats) -> c_int;
     pub fn pcv_searcher_match(s: *mut pcv_searcher, from_source_ids: *const i64, n_from: c_int, to_source_ids: *const i64, n_to: c_int, k: c_int, min_score: f32, capacity: i64, out_ids: *mut i64, out_match_ids: *mut i64, out_scores: *mut f32, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
     pub fn pcv_searcher_last_match_stats(s: *mut pcv_searcher, out: *mut pcv_match_stats) -> c_int;
+    pub fn pcv_searcher_neighbors_grouped(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, k: c_int, flags: u32, capacity: i64, out_ids: *mut i64, out_neighbor_ids: *mut i64, out_scores: *mut f32, out_neighbor_groups: *mut i64, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_match_grouped(s: *mut pcv_searcher, from_source_ids: *const i64, n_from: c_int, to_source_ids: *const i64, n_to: c_int, k: c_int, min_score: f32, flags: u32, capacity: i64, out_ids: *mut i64, out_match_ids: *mut i64, out_scores: *mut f32, out_match_groups: *mut i64, out_counts: *mut i32, out_rows: *mut i64) -> c_int;
+    pub fn pcv_searcher_find_duplicates_grouped(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, max_pairs: i64, out_id_a: *mut i64, out_id_b: *mut i64, out_scores: *mut f32, out_count: *mut i64, out_total: *mut i64, out_skipped: *mut i64) -> c_int;
+    pub fn pcv_searcher_last_pair_group_stats(s: *mut pcv_searcher, out: *mut pcv_pair_group_stats) -> c_int;
     pub fn pcv_searcher_density_clusters(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, min_items: c_int, capacity: i64, out_ids: *mut i64, out_label: *mut i32, out_kind: *mut int8_t, out_degree: *mut i32, out_rows: *mut i64, out_clusters: *mut i32) -> c_int;
     pub fn pcv_searcher_last_density_stats(s: *mut pcv_searcher, out: *mut pcv_density_stats) -> c_int;
     pub fn pcv_searcher_linkage_tree(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, capacity: i64, out_ids: *mut i64, out_part: *mut int8_t, out_pos_a: *mut i64, out_pos_b: *mut i64, out_id_a: *mut i64, out_id_b: *mut i64, out_c: *mut f64, out_rows: *mut i64, out_edges: *mut i64) -> c_int;

@@ -708,6 +708,136 @@ impl Searcher {
         (0..n as usize).map(|i| (ids[i], (0..counts[i] as usize).map(|j| (mids[i * k + j], scores[i * k + j])).collect())).collect()
     }
 
+    /// Group-aware neighbours (`pcv_searcher_neighbors_grouped`): `neighbors` with the group table (`set_groups`) consulted.  `flags`:
+    /// ffi::PCV_GROUPS_SKIP_OWN — the items of the owner's own group are no partners of it; ffi::PCV_GROUPS_ONE_PER_GROUP — of every
+    /// group only its best member is kept; both, or 0 for the plain table.
+    /// Returns (item id, its neighbours as (id, cosine, group or -1)) per item of `sources`.
+    pub fn neighbors_grouped(&self, sources: &[i64], k: usize, flags: u32) -> Vec<(i64, Vec<(i64, f32, i64)>)> {
+        if self.handle.is_null() || k == 0 || sources.is_empty() {
+            return Vec::new();
+        }
+        let k = k.min(ffi::PCV_MAX_NEIGHBORS as usize);
+        let (src, nsrc) = (sources.as_ptr(), sources.len() as i32);
+        let null = std::ptr::null_mut::<i64>();
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_neighbors_grouped(self.handle, src, nsrc, k as i32, flags, 0, null, null, std::ptr::null_mut(), null, std::ptr::null_mut(), &mut n)
+        })
+        .expect("neighbors_grouped failed");
+        let room = n.max(1) as usize;
+        let mut ids = vec![-1i64; room];
+        let mut nbr = vec![-1i64; room * k];
+        let mut scores = vec![f32::NAN; room * k];
+        let mut groups = vec![-1i64; room * k];
+        let mut counts = vec![0i32; room];
+        hip::check(unsafe {
+            ffi::pcv_searcher_neighbors_grouped(
+                self.handle,
+                src,
+                nsrc,
+                k as i32,
+                flags,
+                room as i64,
+                ids.as_mut_ptr(),
+                nbr.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                groups.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("neighbors_grouped failed");
+        (0..n as usize)
+            .map(|i| (ids[i], (0..counts[i] as usize).map(|j| (nbr[i * k + j], scores[i * k + j], groups[i * k + j])).collect()))
+            .collect()
+    }
+
+    /// Group-aware matches (`pcv_searcher_match_grouped`): `matches` with the group table consulted, as `neighbors_grouped` does.
+    /// Returns (item id, its matches as (id, cosine, group or -1)) per item of `from`.
+    pub fn matches_grouped(&self, from: &[i64], to: &[i64], k: usize, min_score: f32, flags: u32) -> Vec<(i64, Vec<(i64, f32, i64)>)> {
+        if self.handle.is_null() || k == 0 || from.is_empty() {
+            return Vec::new();
+        }
+        let k = k.min(ffi::PCV_MAX_NEIGHBORS as usize);
+        let (src, nsrc, dst, ndst) = (from.as_ptr(), from.len() as i32, to.as_ptr(), to.len() as i32);
+        let null = std::ptr::null_mut::<i64>();
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_match_grouped(
+                self.handle, src, nsrc, dst, ndst, k as i32, min_score, flags, 0, null, null, std::ptr::null_mut(), null, std::ptr::null_mut(), &mut n,
+            )
+        })
+        .expect("match_grouped failed");
+        let room = n.max(1) as usize;
+        let mut ids = vec![-1i64; room];
+        let mut mids = vec![-1i64; room * k];
+        let mut scores = vec![f32::NAN; room * k];
+        let mut groups = vec![-1i64; room * k];
+        let mut counts = vec![0i32; room];
+        hip::check(unsafe {
+            ffi::pcv_searcher_match_grouped(
+                self.handle,
+                src,
+                nsrc,
+                dst,
+                ndst,
+                k as i32,
+                min_score,
+                flags,
+                room as i64,
+                ids.as_mut_ptr(),
+                mids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                groups.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("match_grouped failed");
+        (0..n as usize)
+            .map(|i| (ids[i], (0..counts[i] as usize).map(|j| (mids[i * k + j], scores[i * k + j], groups[i * k + j])).collect()))
+            .collect()
+    }
+
+    /// Group-aware duplicate pairs (`pcv_searcher_find_duplicates_grouped`): `find_duplicates` without the pairs of items of one group.
+    /// Returns ((id_a, id_b, cosine) best first, pairs of non-siblings in all, sibling pairs at or above the threshold that were skipped).
+    pub fn find_duplicates_grouped(&self, sources: &[i64], threshold: f32, max_pairs: usize) -> (Vec<(i64, i64, f32)>, i64, i64) {
+        if self.handle.is_null() || sources.is_empty() || max_pairs == 0 {
+            return (Vec::new(), 0, 0);
+        }
+        let m = max_pairs.min(ffi::PCV_MAX_DUPLICATE_PAIRS as usize);
+        let mut a = vec![-1i64; m];
+        let mut b = vec![-1i64; m];
+        let mut scores = vec![f32::NAN; m];
+        let (mut count, mut total, mut skipped) = (0i64, 0i64, 0i64);
+        hip::check(unsafe {
+            ffi::pcv_searcher_find_duplicates_grouped(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                threshold,
+                m as i64,
+                a.as_mut_ptr(),
+                b.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                &mut count,
+                &mut total,
+                &mut skipped,
+            )
+        })
+        .expect("find_duplicates_grouped failed");
+        ((0..count as usize).map(|i| (a[i], b[i], scores[i])).collect(), total, skipped)
+    }
+
+    /// Counters of the last grouped pair call (`pcv_searcher_last_pair_group_stats`).
+    pub fn last_pair_group_stats(&self) -> ffi::pcv_pair_group_stats {
+        let mut st: ffi::pcv_pair_group_stats = unsafe { std::mem::zeroed() };
+        if !self.handle.is_null() {
+            hip::check(unsafe { ffi::pcv_searcher_last_pair_group_stats(self.handle, &mut st) }).expect("last_pair_group_stats failed");
+        }
+        st
+    }
+
     /// Density clusters (`pcv_searcher_density_clusters`): DBSCAN under the cosine over the items of `sources`, by global
     /// position.  Two items are near iff their cosine is at least `threshold`; an item with `min_items - 1` near items or more is a
     /// core item; clusters are the connected components of the core items, numbered by their first core item.
