@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <array>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -281,6 +282,39 @@ inline KMeansResult kmeans_handle(pcv_searcher* h, const std::vector<int64_t>& s
     r.last.ids.resize((size_t)n);
     r.iterations = iters;
     r.moved.resize((size_t)iters + 1);
+    return r;
+}
+
+// Searcher::assign_top / SearcherView::assign_top (pcv_searcher_assign_top): the exact m best of K label vectors for every item of
+// `sources`, by global position, best first; only labels with a score >= min_score (-infinity: no bound) are listed.
+struct TopLabels {
+    size_t m = 0;
+    std::vector<int32_t> labels;      // [n][m], unused slots -1
+    std::vector<float> scores;        // [n][m] as a search reports them, unused slots NaN
+    std::vector<int64_t> ids;         // [n]
+    std::vector<int32_t> counts;      // [n] labels listed for the item
+    std::vector<int64_t> label_rows;  // [K] items that list each label
+};
+inline TopLabels assign_top_handle(pcv_searcher* h, const std::vector<int64_t>& sources, const std::vector<float>& labels, size_t k, size_t m,
+                                   float min_score) {
+    TopLabels r;
+    r.m = m;
+    r.label_rows.assign(k, 0);
+    if (sources.empty() || k == 0 || m == 0) return r;  // `sources.contains(..)` matches nothing
+    int64_t n = 0;
+    check(pcv_searcher_assign_top(h, labels.data(), (int)k, (int)m, min_score, sources.data(), (int)sources.size(), 0, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, &n));
+    const size_t room = (size_t)std::max<int64_t>(n, 1);
+    r.labels.resize(room * m);
+    r.scores.resize(room * m);
+    r.ids.resize(room);
+    r.counts.resize(room);
+    check(pcv_searcher_assign_top(h, labels.data(), (int)k, (int)m, min_score, sources.data(), (int)sources.size(), (int64_t)room, r.labels.data(),
+                                  r.scores.data(), r.ids.data(), r.counts.data(), r.label_rows.data(), &n));
+    r.labels.resize((size_t)n * m);
+    r.scores.resize((size_t)n * m);
+    r.ids.resize((size_t)n);
+    r.counts.resize((size_t)n);
     return r;
 }
 
@@ -730,6 +764,16 @@ public:
         check(pcv_searcher_last_assign_stats(h_, &st));
         return st;
     }
+    // the m best of the k label vectors `labels` [k][dim] for every item, with a score bound (assign_top_handle)
+    TopLabels assign_top(const std::vector<int64_t>& sources, const std::vector<float>& labels, size_t k, size_t m,
+                         float min_score = -std::numeric_limits<float>::infinity()) const {
+        return assign_top_handle(h_, sources, labels, k, m, min_score);
+    }
+    pcv_assign_top_stats last_assign_top_stats() const {
+        pcv_assign_top_stats st;
+        check(pcv_searcher_last_assign_top_stats(h_, &st));
+        return st;
+    }
     // up to k seed items of the view (seeds_handle)
     SeedItems seeds(const std::vector<int64_t>& sources, size_t k, SeedMethod method = SeedMethod::KMeansPP, uint64_t seed = 0,
                     std::optional<int64_t> first_id = std::nullopt) const {
@@ -942,6 +986,16 @@ public:
     pcv_assign_stats last_assign_stats() const {
         pcv_assign_stats st;
         check(pcv_searcher_last_assign_stats(h_, &st));
+        return st;
+    }
+    // the m best of the k label vectors `labels` [k][dim] for every item, with a score bound (assign_top_handle)
+    TopLabels assign_top(const std::vector<int64_t>& sources, const std::vector<float>& labels, size_t k, size_t m,
+                         float min_score = -std::numeric_limits<float>::infinity()) const {
+        return assign_top_handle(h_, sources, labels, k, m, min_score);
+    }
+    pcv_assign_top_stats last_assign_top_stats() const {
+        pcv_assign_top_stats st;
+        check(pcv_searcher_last_assign_top_stats(h_, &st));
         return st;
     }
     // up to k seed items, picked on the device (seeds_handle)

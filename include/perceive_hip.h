@@ -592,10 +592,50 @@ pcv_status pcv_searcher_last_duplicate_stats(pcv_searcher* s, pcv_duplicate_stat
  * (row, label) candidates (thousands of near-identical labels over millions of rows).  The result does not depend on which screening
  * copies exist, nor on pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity: the pass reads the f32 rows and touches no
  * pass state (DESIGN.md §4 "Item labels").  Everything the call allocates on the device is given back when it returns.
- * Not in scope: the top-m labels per row, a sharded form, device-resident output. */
+ * The top-m labels per row are pcv_searcher_assign_top's.  Not in scope: a sharded form, device-resident output. */
 enum { PCV_MAX_LABELS = 4096 };
 pcv_status pcv_searcher_assign(pcv_searcher* s, const float* labels, int n_labels, const int64_t* source_ids, int n_sources, int64_t capacity,
                                int32_t* out_label, float* out_score, int64_t* out_ids, int64_t* out_counts, int64_t* out_n);
+
+/* Top-m labels: the exact m best of K label vectors for every row, with an optional score bound — multi-label tagging ("every topic
+ * prompt that scores at least 0.3, at most five"), soft assignment after pcv_searcher_kmeans, the runner-up label and its gap (the
+ * ambiguous items, the centroid silhouette of a clustering: INTEGRATION.md).  Rows, their order, participation and c(r, j) are those of
+ * pcv_searcher_assign.  The labels of row r are the j with c(r, j) defined and c(r, j) >= (double)min_score, ordered by (c descending,
+ * j ascending); the first m of them are kept.  min_score = -INFINITY: no bound; under dot the bound is on the raw canonical dot, not
+ * on the reported distance.
+ *   m               1 .. PCV_MAX_TOP_LABELS (m > K is allowed: the slots behind K stay unused)
+ *   out_labels      [capacity][m] int32, best first, unused slots -1
+ *   out_scores      [capacity][m] what pcv_searcher_search reports for that pair, bit for bit; unused slots NaN (may be NULL)
+ *   out_ids         [capacity] the item id of every position (may be NULL)
+ *   out_counts      [capacity] int32 labels listed for the row (0 for a row that takes no part)
+ *   out_label_rows  [K] rows that list label j in any slot (may be NULL)
+ *   out_n           n; with out_labels == NULL and capacity == 0 the call only reports n and does no device work
+ * With m = 1 and no bound, labels, scores and ids are pcv_searcher_assign's bit for bit and out_label_rows its out_counts.  Errors as
+ * pcv_searcher_assign, plus m out of range, a NaN min_score and a NULL out_counts (PCV_ERR_INVALID, before any device work).  The
+ * result does not depend on screening copies, pcv_searcher_set_kernel, _set_tuning or _set_candidate_capacity; a view assigns its own
+ * rows; everything the call allocates on the device is given back when it returns (DESIGN.md §4 "Top-m labels": two passes over the
+ * f32 rows per label tile).  Not in scope: a sharded form, device-resident output. */
+enum { PCV_MAX_TOP_LABELS = 8 };
+pcv_status pcv_searcher_assign_top(pcv_searcher* s, const float* labels, int n_labels, int m, float min_score, const int64_t* source_ids,
+                                   int n_sources, int64_t capacity, int32_t* out_labels, float* out_scores, int64_t* out_ids,
+                                   int32_t* out_counts, int64_t* out_label_rows, int64_t* out_n);
+
+/* Counters of the most recent pcv_searcher_assign_top on this handle. */
+typedef struct pcv_assign_top_stats {
+    int64_t rows;         /* rows of the selected segments (those taking no part included)       */
+    int64_t candidates;   /* (row, label) pairs the list pass listed and the f64 step scored      */
+    int64_t listed;       /* the sum of out_counts                                                */
+    int32_t m;
+    int32_t label_tiles;  /* label tiles: two passes over the f32 rows each                       */
+    int32_t tile_labels;  /* labels of one LDS tile (128, 64 or 32)                               */
+    int32_t reruns;       /* list passes repeated because the candidate list was short            */
+    float prep_ms;        /* hipEvent times of the steps (a repeated list pass included)          */
+    float bound_ms;       /* the bound passes and the merges of their column maxima               */
+    float screen_ms;      /* the list passes                                                      */
+    float rescore_ms;
+    float select_ms;
+} pcv_assign_top_stats;
+pcv_status pcv_searcher_last_assign_top_stats(pcv_searcher* s, pcv_assign_top_stats* out);
 
 /* The integer sums of the unit rows of every label, reproducible bit for bit.  labels[n] names a label in [0, K) for every position of
  * the selected rows (as pcv_searcher_assign orders them; a negative value: none).  With rinv_r = (float)(1 / sqrt(|x_r|^2)) from the

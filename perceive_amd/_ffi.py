@@ -76,6 +76,23 @@ class AssignStats(C.Structure):
     ]
 
 
+class AssignTopStats(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int64),
+        ("candidates", C.c_int64),
+        ("listed", C.c_int64),
+        ("m", C.c_int32),
+        ("label_tiles", C.c_int32),
+        ("tile_labels", C.c_int32),
+        ("reruns", C.c_int32),
+        ("prep_ms", C.c_float),
+        ("bound_ms", C.c_float),
+        ("screen_ms", C.c_float),
+        ("rescore_ms", C.c_float),
+        ("select_ms", C.c_float),
+    ]
+
+
 class NeighborStats(C.Structure):
     _fields_ = [
         ("rows", C.c_int64),
@@ -331,6 +348,9 @@ SYMBOLS = {
     "pcv_searcher_kmeans": (C.c_int, [_P, _F32P, C.c_int, C.c_int, _I64P, C.c_int, C.c_int64, _F32P, _INTP, _F32P, _I64P, _I64P,
                                       C.POINTER(C.c_int32), _I64P, C.POINTER(C.c_int64)]),
     "pcv_searcher_last_assign_stats": (C.c_int, [_P, C.POINTER(AssignStats)]),
+    "pcv_searcher_assign_top": (C.c_int, [_P, _F32P, C.c_int, C.c_int, C.c_float, _I64P, C.c_int, C.c_int64, _INTP, _F32P, _I64P, _INTP, _I64P,
+                                          C.POINTER(C.c_int64)]),
+    "pcv_searcher_last_assign_top_stats": (C.c_int, [_P, C.POINTER(AssignTopStats)]),
     "pcv_searcher_neighbors": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int64, _I64P, _I64P, _F32P, _INTP, C.POINTER(C.c_int64)]),
     "pcv_searcher_last_neighbor_stats": (C.c_int, [_P, C.POINTER(NeighborStats)]),
     "pcv_searcher_match": (C.c_int, [_P, _I64P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, _INTP,

@@ -544,6 +544,17 @@ void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanPar
     PCV_LAUNCHED();
 }
 
+void launch_owner_offsets(hipStream_t st, const uint64_t* cand, unsigned long long n_cand, uint32_t* row_cnt, uint32_t* row_off, uint32_t launch_rows) {
+    NeighborArgs a{};
+    a.cand = const_cast<uint64_t*>(cand);  // (read only)
+    a.n_cand = n_cand;
+    a.row_cnt = row_cnt;
+    a.row_off = row_off;
+    if (n_cand) neighbors_count_kernel<<<cdiv64((int64_t)n_cand, 256), 256, 0, st>>>(a);
+    neighbors_offsets_kernel<<<1, 1024, 0, st>>>(a, launch_rows);
+    PCV_LAUNCHED();
+}
+
 void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a) {
     if (a.owner_block0 >= p.total_blocks) return;
     const unsigned grid = cdiv64((int64_t)(p.total_blocks - a.owner_block0) * 32, 4);

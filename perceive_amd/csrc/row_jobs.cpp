@@ -411,7 +411,8 @@ struct AssignJob {
 
     // ... and what an assignment needs on top: the labels' table (a whole number of tiles), the per-row state, the candidate list
     // and the outputs
-    void open_labels() {
+    // (m: the labels a row may keep — assign_top; the list's first room grows with it)
+    void open_labels(int m = 1) {
         a.tile_blocks = (uint32_t)tile / kBlockRows;
         const uint32_t tiles = ((uint32_t)K + (uint32_t)tile - 1) / (uint32_t)tile;
         a.label_blocks = tiles * a.tile_blocks;
@@ -454,7 +455,7 @@ struct AssignJob {
         d_out_score.ensure((size_t)rj.rows);
         d_out_ids.ensure((size_t)rj.rows);
         d_counts.ensure((size_t)K);
-        a.cand_cap = std::min<uint64_t>(kMaxAssignCandidates, std::max<uint64_t>(65536, 4 * (uint64_t)rj.rows));
+        a.cand_cap = std::min<uint64_t>(kMaxAssignCandidates, std::max<uint64_t>(65536, 4 * (uint64_t)m * (uint64_t)rj.rows));
         d_cand.ensure(a.cand_cap);
         d_cand_s.ensure(a.cand_cap);
         a.lab_rinv = d_lab_rinv.p;
@@ -480,14 +481,14 @@ struct AssignJob {
         stats.label_tiles = (int32_t)tiles;
     }
 
-    // one assignment with labels[K][D] (host): row_label, the outputs on the device, counters[1] = rows whose label changed
-    uint64_t assign(const float* labels) {
+    // queues, between ev[0] and ev[1], what every assignment with labels[K][D] (host) starts with: the labels' upload, their norms and
+    // screening constants, the rows' state
+    void queue_prep(const float* labels) {
         const int D = s->D, D4 = s->D4;
         for (int j = 0; j < K; ++j) {
             float* dst = reinterpret_cast<float*>(lab_blk + (size_t)(j >> 5) * D4 * 32 + (j & 31));  // piece f of label j: dst + f * 128 floats
             for (int d = 0; d < D; ++d) dst[(size_t)(d >> 2) * 128 + (d & 3)] = labels[(size_t)j * D + d];
         }
-        unsigned long long counts[2] = {0, 0}, again[2] = {0, 0};
         SelfJoinArgs prep{};
         prep.rinv = d_lab_rinv.p;
         prep.norm = d_lab_norm.p;
@@ -499,6 +500,12 @@ struct AssignJob {
         launch_assign_labels(st, *rj.p, a);
         launch_assign_begin(st, *rj.p, rj.dp, a);
         rj.record(1);
+    }
+
+    // one assignment with labels[K][D] (host): row_label, the outputs on the device, counters[1] = rows whose label changed
+    uint64_t assign(const float* labels) {
+        unsigned long long counts[2] = {0, 0}, again[2] = {0, 0};
+        queue_prep(labels);
         const Listing screen = list_candidates(
             rj, 1, d_cnt.p, counts, again, a.cand_cap, kMaxAssignCandidates,
             [&] {
@@ -606,6 +613,129 @@ void assign_or_kmeans(pcv_searcher* s, const char* what, const float* init, int 
     if (out_iters) *out_iters = updates;
     if (out_centroids) std::memcpy(out_centroids, cent.data(), KD * sizeof(float));
     job.download(out_label, out_score, out_ids, out_counts);
+}
+
+// ---- top-m labels (pcv_searcher_assign_top; DESIGN.md §4 "Top-m labels") ----
+// An assignment's job with the two-pass screen in place of the carried bound: per label tile a bound pass and the merge of its column
+// maxima, then the list passes against the final thresholds, the f64 step into per-row stretches and the selection of the m best.
+struct AssignTopJob {
+    DevBuf<float> d_colmax, d_topm, d_scores;
+    DevBuf<uint32_t> d_row_cnt, d_row_off, d_sorted_lab;
+    DevBuf<unsigned long long> d_sorted_key;
+    DevBuf<int32_t> d_labels, d_count;
+    AssignTopArgs x{};
+    pcv_assign_top_stats stats{};
+    AssignJob base;  // the last member: it goes first, and waits for the stream before the buffers above are freed
+
+    AssignTopJob(pcv_searcher* s, const std::vector<SelSeg>& segs, int K, int m, float min_score) : base(s, segs, K, s->metric) {
+        base.open_labels(m);
+        const size_t nr = base.rj.nr, rows = (size_t)base.rj.rows;
+        d_colmax.ensure(nr * 32);
+        d_topm.ensure(nr * kMaxTopLabels);
+        d_row_cnt.ensure(nr);
+        d_row_off.ensure(nr + 1);
+        d_labels.ensure(rows * (size_t)m);
+        d_scores.ensure(rows * (size_t)m);
+        d_count.ensure(rows);
+        x.a = base.a;
+        x.colmax = d_colmax.p;
+        x.topm = d_topm.p;
+        x.row_cnt = d_row_cnt.p;
+        x.row_off = d_row_off.p;
+        x.out_labels = d_labels.p;
+        x.out_scores = d_scores.p;
+        x.out_count = d_count.p;
+        x.out_label_rows = base.d_counts.p;
+        x.min_score = min_score;
+        x.m = m;
+        stats.rows = base.stats.rows;
+        stats.m = m;
+        stats.label_tiles = base.stats.label_tiles;
+        stats.tile_labels = base.stats.tile_labels;
+        stats.prep_ms = base.stats.prep_ms;
+    }
+
+    void run(const float* labels) {
+        RowsJob& rj = base.rj;
+        hipStream_t st = base.st;
+        unsigned long long counts[1] = {0}, again[1] = {0};
+        base.queue_prep(labels);
+        PCV_HIP(hipMemsetAsync(d_row_cnt.p, 0, rj.nr * sizeof(uint32_t), st));
+        for (uint32_t t = 0; t < (uint32_t)stats.label_tiles; ++t) {
+            x.a.tile = t;
+            launch_assign_top_bound(st, *rj.p, rj.dp, x);
+            launch_assign_top_merge(st, *rj.p, x);
+        }
+        rj.record(2);
+        const Listing list = list_candidates(
+            rj, 2, base.d_cnt.p, counts, again, x.a.cand_cap, kMaxAssignCandidates,
+            [&] {
+                x.a.cand = base.d_cand.p;
+                x.a.cand_s = base.d_cand_s.p;
+                for (uint32_t t = 0; t < (uint32_t)stats.label_tiles; ++t) {
+                    x.a.tile = t;
+                    launch_assign_top_list(st, *rj.p, rj.dp, x);
+                }
+            },
+            [&] { PCV_HIP(hipMemsetAsync(base.d_cnt.p, 0, sizeof(unsigned long long), st)); }, base.d_cand, base.d_cand_s);
+        stats.prep_ms += rj.elapsed(0);
+        stats.bound_ms = rj.elapsed(1);
+        stats.screen_ms = list.ms;
+        const uint64_t n_cand = counts[0];
+        stats.candidates = (int64_t)n_cand;
+        if (n_cand > kMaxAssignCandidates)
+            PCV_FAIL(PCV_ERR_UNSUPPORTED, "assign_top: the screen lists %llu (row, label) candidates, more than %llu: fewer or less alike labels, a smaller m, or fewer rows",
+                     (unsigned long long)n_cand, (unsigned long long)kMaxAssignCandidates);
+        if (list.repeated) {  // (the thresholds were final before the first run: the same list)
+            PCV_REQUIRE(again[0] == n_cand, "assign_top: the repeated list pass found %llu candidates, the first %llu", again[0], (unsigned long long)n_cand);
+            stats.reruns += 1;
+            stats.screen_ms += list.again_ms;
+        }
+        x.a.n_cand = n_cand;
+        d_sorted_key.ensure((size_t)std::max<uint64_t>(1, n_cand));
+        d_sorted_lab.ensure((size_t)std::max<uint64_t>(1, n_cand));
+        x.sorted_key = d_sorted_key.p;
+        x.sorted_lab = d_sorted_lab.p;
+        rj.record(4);
+        launch_assign_top_rescore(st, *rj.p, rj.dp, x);
+        rj.record(5);
+        launch_assign_top_select(st, *rj.p, rj.dp, x);
+        rj.record(6);
+        rj.wait();
+        stats.rescore_ms = rj.elapsed(4);
+        stats.select_ms = rj.elapsed(5);
+    }
+
+    void download(int32_t* out_labels, float* out_scores, int64_t* out_ids, int32_t* out_counts, int64_t* out_label_rows) {
+        const size_t n = (size_t)base.rj.rows, m = (size_t)x.m;
+        PCV_HIP(hipMemcpy(out_labels, d_labels.p, n * m * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (out_scores) PCV_HIP(hipMemcpy(out_scores, d_scores.p, n * m * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_ids) PCV_HIP(hipMemcpy(out_ids, base.d_out_ids.p, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        PCV_HIP(hipMemcpy(out_counts, d_count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (out_label_rows) PCV_HIP(hipMemcpy(out_label_rows, base.d_counts.p, (size_t)base.K * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) stats.listed += out_counts[i];
+    }
+};
+
+// the caller has checked the arguments
+void assign_top(pcv_searcher* s, const float* labels, int K, int m, float min_score, const int64_t* source_ids, int n_sources, int64_t capacity,
+                int32_t* out_labels, float* out_scores, int64_t* out_ids, int32_t* out_counts, int64_t* out_label_rows, int64_t* out_n) {
+    PCV_REQUIRE(!s->dirty, "assign_top: rows were added or cleared without pcv_searcher_finalize");
+    check_labels(s, labels, K, "assign_top");
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    const int64_t n = selected_rows(segs);
+    *out_n = n;
+    if (out_labels == nullptr && capacity == 0) return;  // the count alone
+    PCV_REQUIRE(capacity >= n, "assign_top: the outputs have room for %lld rows, the selected sources have %lld", (long long)capacity, (long long)n);
+    s->assign_top_stats = pcv_assign_top_stats{};
+    s->assign_top_stats.m = m;
+    if (mfma_pass_queries(s->Dp) == 0) PCV_FAIL(PCV_ERR_UNSUPPORTED, "assign_top: a bf16 tile of %d-d labels does not fit the LDS", s->D);
+    if (out_label_rows) std::fill(out_label_rows, out_label_rows + K, (int64_t)0);
+    if (n == 0) return;
+    AssignTopJob job(s, segs, K, m, min_score);
+    const auto keep_stats = at_exit([&] { s->assign_top_stats = job.stats; });
+    job.run(labels);
+    job.download(out_labels, out_scores, out_ids, out_counts, out_label_rows);
 }
 
 void label_sums(pcv_searcher* s, const int64_t* source_ids, int n_sources, const int32_t* labels, int64_t n, int K, int64_t* out_sums,
@@ -1849,6 +1979,31 @@ pcv_status pcv_searcher_last_assign_stats(pcv_searcher* s, pcv_assign_stats* out
         PCV_REQUIRE(s != nullptr && out != nullptr, "last_assign_stats: NULL argument");
         std::lock_guard<std::mutex> lk(s->mu);
         *out = s->assign_stats;
+    });
+}
+
+pcv_status pcv_searcher_assign_top(pcv_searcher* s, const float* labels, int n_labels, int m, float min_score, const int64_t* source_ids,
+                                   int n_sources, int64_t capacity, int32_t* out_labels, float* out_scores, int64_t* out_ids, int32_t* out_counts,
+                                   int64_t* out_label_rows, int64_t* out_n) {
+    return guarded([&] {
+        PCV_REQUIRE(labels != nullptr && out_n != nullptr, "assign_top: labels or out_n is NULL");
+        PCV_REQUIRE(n_labels >= 1 && n_labels <= (int)PCV_MAX_LABELS, "assign_top: %d labels, outside [1,%d]", n_labels, (int)PCV_MAX_LABELS);
+        PCV_REQUIRE(m >= 1 && m <= (int)PCV_MAX_TOP_LABELS, "assign_top: m %d outside [1,%d]", m, (int)PCV_MAX_TOP_LABELS);
+        PCV_REQUIRE(min_score == min_score, "assign_top: min_score is NaN");
+        PCV_REQUIRE(capacity >= 0 && (out_labels != nullptr || capacity == 0), "assign_top: out_labels is NULL with capacity %lld", (long long)capacity);
+        PCV_REQUIRE(out_counts != nullptr || (out_labels == nullptr && capacity == 0), "assign_top: out_counts is NULL");
+        PCV_REQUIRE(s != nullptr, "assign_top: searcher is NULL");
+        const auto lk = enter(s, "assign_top");
+        assign_top(s, labels, n_labels, m, min_score, source_ids, n_sources, capacity, out_labels, out_scores, out_ids, out_counts, out_label_rows,
+                   out_n);
+    });
+}
+
+pcv_status pcv_searcher_last_assign_top_stats(pcv_searcher* s, pcv_assign_top_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "last_assign_top_stats: NULL argument");
+        std::lock_guard<std::mutex> lk(s->mu);
+        *out = s->assign_top_stats;
     });
 }
 

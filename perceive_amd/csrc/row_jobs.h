@@ -105,6 +105,34 @@ struct AssignArgs {
     uint32_t span_blocks;           // row blocks one screen workgroup streams (a multiple of its waves)
 };
 
+// Top-m labels (pcv_searcher_assign_top; DESIGN.md §4 "Top-m labels"): the m best labels of every row, in two passes over the rows per
+// label tile.  `a` is the assignment's block, read as the assign kernels read it, except
+//   a.lb[launch row]    : the row's FINAL threshold once every tile's bound pass and merge has run: the m-th largest column maximum
+//                         (-inf: fewer than m are defined), under cosine at least min_score - margin, rounded down; -inf for a wild
+//                         row.  Label j is listed for the row iff s_j + mg_j >= a.lb (or one of the two is wild)
+// and best_key / best_lab / cand_key / row_label / out_* of `a` are not used.  A COLUMN of a tile is the labels 32 t + c of one lane
+// column c: the columns of all tiles are disjoint label sets.
+//   colmax[launch row][c]  : of the tile the bound pass last ran, the largest s - mg over the column's certified labels (-inf: none)
+//   topm[launch row][8]    : the eight largest column maxima over the tiles merged so far, descending
+//   row_cnt / row_off      : as NeighborArgs: the row's candidates, counted up then down, and where its stretch starts
+//   sorted_key / sorted_lab: per row, in any order: the f64_key image of c (0: undefined, or below min_score) and the label
+struct AssignTopArgs {
+    AssignArgs a;
+    float* colmax;                  // [total_blocks * 32][32]
+    float* topm;                    // [total_blocks * 32][kMaxTopLabels]
+    uint32_t* row_cnt;              // [total_blocks * 32]
+    uint32_t* row_off;              // [total_blocks * 32 + 1]
+    unsigned long long* sorted_key; // [n_cand]
+    uint32_t* sorted_lab;           // [n_cand]
+    int32_t* out_labels;            // [rows][m], unused slots -1
+    float* out_scores;              // [rows][m], unused slots NaN
+    int32_t* out_count;             // [rows]
+    long long* out_label_rows;      // [K]
+    float min_score;                // c >= (double)min_score; -inf: no bound
+    int m;
+};
+constexpr int kMaxTopLabels = 8;    // PCV_MAX_TOP_LABELS
+
 // Item neighbours and item matches (pcv_searcher_neighbors, pcv_searcher_match; DESIGN.md §4 "Item neighbours", "Item matches"): the
 // k best partner rows of every owner row.  Rows are launch rows, rinv / norm exactly as selfjoin_prep_kernel leaves them.  The OWNERS
 // are the rows of the launch blocks [owner_block0, total_blocks), the PARTNERS those of the blocks [0, partner_blocks): `neighbors`
@@ -398,12 +426,20 @@ void launch_assign_screen(hipStream_t st, const ScanParams& p, const ScanParams*
 void launch_assign_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
 void launch_assign_finish(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);  // winners -> outputs
 void launch_label_sums(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignArgs& a);
+// ---- top-m labels (assign_kernels.hip); the prep steps are the assignment's.  Per label tile a.tile: bound, then merge; then list per tile ----
+void launch_assign_top_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignTopArgs& x);    // one label tile -> colmax
+void launch_assign_top_merge(hipStream_t st, const ScanParams& p, const AssignTopArgs& x);                          // colmax -> topm, a.lb
+void launch_assign_top_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignTopArgs& x);     // one label tile, a.lb -> cand
+void launch_assign_top_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignTopArgs& x);  // cand -> row_off, sorted_*
+void launch_assign_top_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const AssignTopArgs& x);   // sorted_* -> outputs
 // ---- item neighbours and item matches (neighbors_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----
 void launch_neighbors_bound(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);    // -> span_max
 void launch_neighbors_threshold(hipStream_t st, const ScanParams& p, const NeighborArgs& a);                      // span_max -> thr
 void launch_neighbors_list(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);     // thr -> cand
 void launch_neighbors_rescore(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);  // cand -> sorted_*
 void launch_neighbors_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const NeighborArgs& a);   // sorted_* -> outputs
+// the count and offsets steps alone, for any list of (owner launch row << 32) | x: row_cnt (zero before) counted up, row_off its scan
+void launch_owner_offsets(hipStream_t st, const uint64_t* cand, unsigned long long n_cand, uint32_t* row_cnt, uint32_t* row_off, uint32_t launch_rows);
 // ---- the rows' groups (grouped_kernels.hip); behind launch_selfjoin_prep ----
 void launch_row_groups(hipStream_t st, const ScanParams& p, const ScanParams* dp, const PairGroups& a);  // rinv, the table -> grp, tag
 // ---- density clusters (density_kernels.hip); `p` as for the duplicate pairs; the prep step is launch_selfjoin_prep ----

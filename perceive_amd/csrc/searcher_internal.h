@@ -248,6 +248,7 @@ struct pcv_searcher {
     } groups;
     pcv_duplicate_stats dup_stats{};  // pcv_searcher_find_duplicates (its buffers live for the call only)
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
+    pcv_assign_top_stats assign_top_stats{};  // pcv_searcher_assign_top (likewise)
     pcv_neighbor_stats nbr_stats{};   // pcv_searcher_neighbors (likewise)
     pcv_match_stats match_stats{};    // pcv_searcher_match (likewise)
     pcv_pair_group_stats pair_group_stats{};  // the last of pcv_searcher_neighbors_grouped, _match_grouped, _find_duplicates_grouped

@@ -664,6 +664,39 @@ class Searcher:
         _ffi.check(_ffi.lib().pcv_searcher_last_assign_stats(self._handle, C.byref(st)))
         return {f: getattr(st, f) for f, _ in _ffi.AssignStats._fields_}
 
+    def assign_top(self, sources, labels, m, min_score=None):
+        """The m best of the K vectors `labels` [K, dim] for every row of `sources`, exact: the labels j with a defined score
+        c >= min_score (None: no bound; under dot a bound on the raw dot product), ordered by (c descending, j ascending) ->
+        (labels [n, m] int32 best first with unused slots -1, scores [n, m] f32 as search reports them with unused slots NaN,
+        ids [n] int64, counts [n] int32, label_rows [K] int64: rows that list each label), by global position.  With m = 1 and no
+        bound: what assign returns.  A view assigns its own rows."""
+        lab = np.ascontiguousarray(labels, dtype=np.float32)
+        if lab.ndim != 2 or lab.shape[1] != self.dim:
+            raise ValueError(f"labels must be [K, {self.dim}]")
+        K, m = lab.shape[0], int(m)
+        bound = float("-inf") if min_score is None else float(min_score)
+        src, nsrc, _keep = _source_filter(sources)
+        n = self._assign_rows(src, nsrc)
+        room = max(n, 1)
+        out = np.empty((room, max(m, 1)), dtype=np.int32)
+        score = np.empty((room, max(m, 1)), dtype=np.float32)
+        ids = np.empty(room, dtype=np.int64)
+        counts = np.zeros(room, dtype=np.int32)
+        label_rows = np.zeros(max(K, 1), dtype=np.int64)
+        got = C.c_int64()
+        _ffi.check(
+            _ffi.lib().pcv_searcher_assign_top(
+                self._handle, _ffi.f32p(lab), K, m, bound, src, nsrc, room, _ffi.i32p(out), _ffi.f32p(score), _ffi.i64p(ids), _ffi.i32p(counts),
+                _ffi.i64p(label_rows), C.byref(got),
+            )
+        )
+        return out[:n], score[:n], ids[:n], counts[:n], label_rows[:K]
+
+    def last_assign_top_stats(self):
+        st = _ffi.AssignTopStats()
+        _ffi.check(_ffi.lib().pcv_searcher_last_assign_top_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.AssignTopStats._fields_}
+
     # ---- item neighbours (pcv_searcher_neighbors) --------------------------------------------------
     # The k-nearest-neighbour table of the corpus: what N / 256 search_like calls would give, in one call that no search setting touches.
     def neighbors(self, sources, k):

@@ -58,6 +58,23 @@ pub struct pcv_duplicate_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_assign_top_stats {
+    pub rows: i64,
+    pub candidates: i64,
+    pub listed: i64,
+    pub m: i32,
+    pub label_tiles: i32,
+    pub tile_labels: i32,
+    pub reruns: i32,
+    pub prep_ms: f32,
+    pub bound_ms: f32,
+    pub screen_ms: f32,
+    pub rescore_ms: f32,
+    pub select_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_assign_stats {
     pub rows: i64,
     pub candidates: i64,
@@ -298,6 +315,7 @@ pub const PCV_MAX_GROUPED_POOL: c_int = 4096;
 pub const PCV_MAX_DIVERSE_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
+pub const PCV_MAX_TOP_LABELS: c_int = 8;
 pub const PCV_MAX_NEIGHBORS: c_int = 64;
 pub const PCV_GROUPS_SKIP_OWN: c_int = 1;
 pub const PCV_GROUPS_ONE_PER_GROUP: c_int = 2;
@@ -391,6 +409,8 @@ extern "C" {
     pub fn pcv_searcher_find_duplicates(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, max_pairs: i64, out_id_a: *mut i64, out_id_b: *mut i64, out_scores: *mut f32, out_count: *mut i64, out_total: *mut i64) -> c_int;
     pub fn pcv_searcher_last_duplicate_stats(s: *mut pcv_searcher, out: *mut pcv_duplicate_stats) -> c_int;
     pub fn pcv_searcher_assign(s: *mut pcv_searcher, labels: *const f32, n_labels: c_int, source_ids: *const i64, n_sources: c_int, capacity: i64, out_label: *mut i32, out_score: *mut f32, out_ids: *mut i64, out_counts: *mut i64, out_n: *mut i64) -> c_int;
+    pub fn pcv_searcher_assign_top(s: *mut pcv_searcher, labels: *const f32, n_labels: c_int, m: c_int, min_score: f32, source_ids: *const i64, n_sources: c_int, capacity: i64, out_labels: *mut i32, out_scores: *mut f32, out_ids: *mut i64, out_counts: *mut i32, out_label_rows: *mut i64, out_n: *mut i64) -> c_int;
+    pub fn pcv_searcher_last_assign_top_stats(s: *mut pcv_searcher, out: *mut pcv_assign_top_stats) -> c_int;
     pub fn pcv_searcher_label_sums(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, labels: *const i32, n: i64, n_labels: c_int, out_sums: *mut i64, out_counts: *mut i64) -> c_int;
     pub fn pcv_searcher_kmeans(s: *mut pcv_searcher, init: *const f32, n_labels: c_int, max_iters: c_int, source_ids: *const i64, n_sources: c_int, capacity: i64, out_centroids: *mut f32, out_label: *mut i32, out_score: *mut f32, out_ids: *mut i64, out_counts: *mut i64, out_iters: *mut i32, out_moved: *mut i64, out_n: *mut i64) -> c_int;
     pub fn pcv_searcher_last_assign_stats(s: *mut pcv_searcher, out: *mut pcv_assign_stats) -> c_int;

@@ -607,6 +607,64 @@ impl Searcher {
         ((centroids), (0..n as usize).map(|i| (label[i], score[i], ids[i])).collect(), counts, done as usize, moved)
     }
 
+    /// Top-m labels (`pcv_searcher_assign_top`): for every item of `sources`, by global position, the exact `m` best of the `k`
+    /// vectors `labels` (clamped to PCV_MAX_TOP_LABELS) with a score of at least `min_score` (`f32::NEG_INFINITY`: no bound),
+    /// best first.  Returns (item id, its labels as (label, score as a search reports it)) per item — none for an item no search
+    /// could return — and the number of items that list each label.
+    pub fn assign_top(&self, sources: &[i64], labels: &[f32], k: usize, m: usize, min_score: f32) -> (Vec<(i64, Vec<(i32, f32)>)>, Vec<i64>) {
+        let mut label_rows = vec![0i64; k];
+        if self.handle.is_null() || k == 0 || m == 0 || sources.is_empty() {
+            return (Vec::new(), label_rows);
+        }
+        let m = m.min(ffi::PCV_MAX_TOP_LABELS as usize);
+        let mut n: i64 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_assign_top(
+                self.handle,
+                labels.as_ptr(),
+                k as i32,
+                m as i32,
+                min_score,
+                sources.as_ptr(),
+                sources.len() as i32,
+                0,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+                &mut n,
+            )
+        })
+        .expect("assign_top failed");
+        let room = n.max(1) as usize;
+        let mut out = vec![-1i32; room * m];
+        let mut score = vec![f32::NAN; room * m];
+        let mut ids = vec![-1i64; room];
+        let mut counts = vec![0i32; room];
+        hip::check(unsafe {
+            ffi::pcv_searcher_assign_top(
+                self.handle,
+                labels.as_ptr(),
+                k as i32,
+                m as i32,
+                min_score,
+                sources.as_ptr(),
+                sources.len() as i32,
+                room as i64,
+                out.as_mut_ptr(),
+                score.as_mut_ptr(),
+                ids.as_mut_ptr(),
+                counts.as_mut_ptr(),
+                label_rows.as_mut_ptr(),
+                &mut n,
+            )
+        })
+        .expect("assign_top failed");
+        let rows = (0..n as usize).map(|i| (ids[i], (0..counts[i] as usize).map(|j| (out[i * m + j], score[i * m + j])).collect())).collect();
+        (rows, label_rows)
+    }
+
     /// Item neighbours (`pcv_searcher_neighbors`): for every item of `sources`, by global position, its exact `k` best other
     /// items by cosine (clamped to PCV_MAX_NEIGHBORS), best first — the table a "related items" panel reads without a search.
     /// Returns (item id, its neighbours as (id, cosine)) per item; an item no search could return has none.

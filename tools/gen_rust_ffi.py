@@ -18,7 +18,7 @@ SCALARS = {
     "pcv_ctx": "pcv_ctx", "pcv_searcher": "pcv_searcher", "pcv_model": "pcv_model", "pcv_tokenizer": "pcv_tokenizer",
     "pcv_comm": "pcv_comm", "pcv_hit": "pcv_hit", "pcv_scan_stats": "pcv_scan_stats", "pcv_model_desc": "pcv_model_desc",
     "pcv_encode_stats": "pcv_encode_stats", "pcv_duplicate_stats": "pcv_duplicate_stats",
-    "pcv_assign_stats": "pcv_assign_stats", "pcv_neighbor_stats": "pcv_neighbor_stats", "pcv_group_stats": "pcv_group_stats",
+    "pcv_assign_stats": "pcv_assign_stats", "pcv_assign_top_stats": "pcv_assign_top_stats", "pcv_neighbor_stats": "pcv_neighbor_stats", "pcv_group_stats": "pcv_group_stats",
     "pcv_match_stats": "pcv_match_stats", "pcv_pair_group_stats": "pcv_pair_group_stats",
     "pcv_seed_stats": "pcv_seed_stats", "pcv_moment_stats": "pcv_moment_stats", "pcv_project_stats": "pcv_project_stats",
     "pcv_density_stats": "pcv_density_stats", "pcv_linkage_stats": "pcv_linkage_stats",
