@@ -217,6 +217,47 @@ inline std::vector<GroupedItem> search_grouped_handle(pcv_searcher* h, const std
     return out;
 }
 
+// A predicate over the value of an item (Searcher::set_values): an item passes iff it has a value in [lo, hi] — `outside`: a value
+// not in it —; `unset_passes`: items without a value pass too (pcv_searcher_count_where).
+struct Where {
+    int64_t lo = INT64_MIN + 1, hi = INT64_MAX;
+    bool unset_passes = false, outside = false;
+    uint32_t flags() const { return (unset_passes ? (uint32_t)PCV_WHERE_UNSET_PASSES : 0u) | (outside ? (uint32_t)PCV_WHERE_OUTSIDE : 0u); }
+};
+// One hit of search_vector_where: a passing item and its value (PCV_NO_VALUE: an item without one that passed).
+struct ValuedItem {
+    SearchItem item;
+    int64_t value;
+};
+// Filtered search on a searcher or a view handle (pcv_searcher_search_where): the ranked list of search_vector walked best first,
+// an item kept iff it passes `where` (a view reads its parent's values); at most `pool` entries are examined (0: the default,
+// min(PCV_MAX_WHERE_POOL, max(128, 8 * num_results))).  `more`, if given: the walk stopped at `pool` short of num_results although
+// the list went on — the predicate is too selective for this call: use Searcher::view_where.
+inline std::vector<ValuedItem> search_where_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results,
+                                                   const std::vector<float>& vector, const Where& where, size_t pool, bool* more) {
+    if (more) *more = false;
+    if (sources.empty() || num_results == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    if (pool == 0) pool = std::min<size_t>(PCV_MAX_WHERE_POOL, std::max<size_t>(128, 8 * num_results));
+    std::vector<int64_t> ids(num_results), values(num_results);
+    std::vector<float> scores(num_results);
+    int32_t count = 0;
+    uint8_t m = 0;
+    check(pcv_searcher_search_where(h, vector.data(), 1, sources.data(), (int)sources.size(), (int)num_results, (int)pool, where.lo, where.hi,
+                                    where.flags(), ids.data(), scores.data(), values.data(), &count, nullptr, &m));
+    if (more) *more = m != 0;
+    std::vector<ValuedItem> out;
+    for (int i = 0; i < count; ++i) out.push_back({{ids[(size_t)i], scores[(size_t)i]}, values[(size_t)i]});
+    return out;
+}
+// The items of `sources` that pass `where`, and (`searchable`, if given) those of them a search could return.
+inline int64_t count_where_handle(pcv_searcher* h, const std::vector<int64_t>& sources, const Where& where, int64_t* searchable) {
+    int64_t rows = 0, live = 0;
+    static const int64_t none = 0;  // (an empty list still needs a pointer: NULL means every source)
+    check(pcv_searcher_count_where(h, sources.empty() ? &none : sources.data(), (int)sources.size(), where.lo, where.hi, where.flags(), &rows, &live));
+    if (searchable) *searchable = live;
+    return rows;
+}
+
 // One duplicate pair of find_duplicates: the item stored first, the other one, their cosine.
 struct DuplicatePair {
     int64_t id_a, id_b;
@@ -699,6 +740,8 @@ public:
     SearcherView(pcv_searcher* parent, const std::vector<int64_t>& ids) {
         check(pcv_searcher_create_view(parent, ids.data(), (int64_t)ids.size(), &h_));
     }
+    // Searcher::view_where: the rows whose id passes the predicate, selected on the device (pcv_searcher_create_view_where)
+    SearcherView(pcv_searcher* parent, const Where& where) { check(pcv_searcher_create_view_where(parent, where.lo, where.hi, where.flags(), &h_)); }
     ~SearcherView() {
         if (h_) pcv_searcher_destroy(h_);
     }
@@ -745,6 +788,14 @@ public:
     std::vector<GroupedItem> search_vector_grouped(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
                                                    size_t pool = 0, bool* more = nullptr) const {
         return search_grouped_handle(h_, sources, num_results, vector, pool, more);
+    }
+    // the view's best items that pass a predicate on the parent's values (search_where_handle), and how many pass at all
+    std::vector<ValuedItem> search_vector_where(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                const Where& where, size_t pool = 0, bool* more = nullptr) const {
+        return search_where_handle(h_, sources, num_results, vector, where, pool, more);
+    }
+    int64_t count_where(const std::vector<int64_t>& sources, const Where& where, int64_t* searchable = nullptr) const {
+        return count_where_handle(h_, sources, where, searchable);
     }
     // the duplicate pairs among the view's items (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
@@ -970,6 +1021,32 @@ public:
                                                    size_t pool = 0, bool* more = nullptr) const {
         return search_grouped_handle(h_, sources, num_results, vector, pool, more);
     }
+    // the value table (pcv_searcher_set_values): item ids[i] has value values[i] (any int64; PCV_NO_VALUE unsets); the last occurrence
+    // of an id holds.  Keyed by id: it survives remove_items and rebuild_source.
+    void set_values(const std::vector<int64_t>& ids, const std::vector<int64_t>& values) {
+        if (ids.size() != values.size()) throw std::invalid_argument("set_values: ids and values differ in length");
+        check(pcv_searcher_set_values(h_, ids.data(), values.data(), (int64_t)ids.size()));
+    }
+    void clear_values() { check(pcv_searcher_clear_values(h_)); }
+    // the value of every id, PCV_NO_VALUE where it has none
+    std::vector<int64_t> values_of(const std::vector<int64_t>& ids) const {
+        std::vector<int64_t> out(ids.size(), PCV_NO_VALUE);
+        check(pcv_searcher_get_values(h_, ids.data(), (int64_t)ids.size(), out.data()));
+        return out;
+    }
+    pcv_value_stats value_stats() const {
+        pcv_value_stats st;
+        check(pcv_searcher_value_stats(h_, &st));
+        return st;
+    }
+    // the best items that pass a predicate on their value: "the best matches among the items modified since ..." (search_where_handle)
+    std::vector<ValuedItem> search_vector_where(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                const Where& where, size_t pool = 0, bool* more = nullptr) const {
+        return search_where_handle(h_, sources, num_results, vector, where, pool, more);
+    }
+    int64_t count_where(const std::vector<int64_t>& sources, const Where& where, int64_t* searchable = nullptr) const {
+        return count_where_handle(h_, sources, where, searchable);
+    }
     // every pair of near-duplicate items, found once on the device (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
                                                int64_t* total = nullptr) const {
@@ -1168,6 +1245,8 @@ public:
     }
     // a search restricted to `ids` (the items of a tag, of an author, earlier results): SQL gives the ids, the view searches them
     SearcherView view(const std::vector<int64_t>& ids) const { return SearcherView(h_, ids); }
+    // ... over the items that pass a predicate on their value: for predicates too selective for search_vector_where
+    SearcherView view_where(const Where& where) const { return SearcherView(h_, where); }
     // capacity hint: the rows about to be added to `source_id` land in one device segment
     void reserve(int64_t source_id, int64_t n_rows) { check(pcv_searcher_reserve(h_, source_id, n_rows)); }
     // narrow screening copy of the rows next to the f32 rows (a half / a quarter of the bytes per scan, same results):

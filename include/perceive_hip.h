@@ -481,6 +481,85 @@ pcv_status pcv_searcher_search_grouped(pcv_searcher* s, const float* queries, in
                                        int num_results, int pool, int64_t* out_ids, float* out_scores, int64_t* out_groups,
                                        int32_t* out_counts, int32_t* out_collapsed, int32_t* out_examined, uint8_t* out_more);
 
+/* Item values and filtered search: a stored int64 per item (a time stamp, a price, a version) and exact search under a range
+ * predicate on it ("the best matches among the items modified since last week") — what vector stores call metadata filtering.
+ *
+ * The value table is state of a searcher, a second instance of the table the groups live in, and its contract is that table's:
+ *   - A value is any int64 but PCV_NO_VALUE (INT64_MIN), which means "no value": negative time stamps, INT64_MAX and
+ *     INT64_MIN + 1 are values like any other.
+ *   - Keyed by id, not by row: hide, update, remove, replace_source and the screening copies know nothing of it, and an entry
+ *     SURVIVES pcv_searcher_remove_ids, clear_source and replace_source — an id that comes back has its value again.  Only
+ *     pcv_searcher_clear_values forgets (everything: the table is then as created, counters included).  Two rows that share an id
+ *     share its value.
+ *   - It lives with the root searcher.  A view reads its parent's table at call time; the two mutators on a view fail as every
+ *     change of a view does.
+ *   - Memory: 16 bytes per slot, slots a power of two >= 2 * entries, 1024 at least; 4 bytes per slot more and up to 2^22 ids of
+ *     the batch at a time while a set_values call runs.
+ * pcv_searcher_set_values: an upsert of (ids[i], values[i]), i < n.  values[i] == PCV_NO_VALUE unsets the id (its entry stays;
+ *   there are no tombstones).  A NULL list with n > 0 or n < 0 give PCV_ERR_INVALID before any device work.  Of an id that occurs
+ *   more than once in a batch the LAST occurrence holds.  A batch is one growth decision: the table is sized for entries + n before
+ *   the batch goes in.  More than 2^30 entries give PCV_ERR_UNSUPPORTED before anything is allocated; a failed allocation
+ *   (PCV_ERR_DEVICE) leaves the table as it was.  There is no host sort: the cost is the upload and two launches per 2^22 ids.
+ * pcv_searcher_get_values: out_values[i] = the value of ids[i], PCV_NO_VALUE if it has none.  Works on a view (the parent's table).
+ * pcv_searcher_value_stats: ids with a value / occupied slots / capacity / growths by rehash since creation (or the last
+ *   clear_values) / device time of the last set_values, growth included (hipEvent).
+ *
+ * A PREDICATE is (lo, hi, flags) over the value of a row's id: a row passes iff its id has a value v with lo <= v <= hi.
+ *   PCV_WHERE_UNSET_PASSES  rows whose id has no value pass too (without it they never do)
+ *   PCV_WHERE_OUTSIDE       the interval test is negated for rows that have a value (unset rows still follow the other bit only)
+ * lo > hi is legal: the empty interval.  Any other flag bit gives PCV_ERR_INVALID.
+ * pcv_searcher_count_where: *out_rows = rows of the selected sources that pass, *out_searchable = those of them a search could
+ *   return (hidden and unsearchable rows excluded); either may be NULL.  The source filter is pcv_searcher_search's
+ *   (PCV_STAGING_SOURCE rows only where that source is named); on a view the view's own rows are counted.  Exact: one kernel over
+ *   the ids of every selected segment, integer sums on the device, one 16-byte download.  Pending rows fail as in a search. */
+#define PCV_NO_VALUE (INT64_MIN)
+enum { PCV_WHERE_UNSET_PASSES = 1, PCV_WHERE_OUTSIDE = 2 };
+typedef struct pcv_value_stats {
+    int64_t ids;
+    int64_t entries;
+    int64_t slots;
+    int32_t rehashes;
+    float last_set_ms;
+} pcv_value_stats;
+pcv_status pcv_searcher_set_values(pcv_searcher* s, const int64_t* ids, const int64_t* values, int64_t n);
+pcv_status pcv_searcher_clear_values(pcv_searcher* s);
+pcv_status pcv_searcher_get_values(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_values);
+pcv_status pcv_searcher_value_stats(pcv_searcher* s, pcv_value_stats* out);
+pcv_status pcv_searcher_count_where(pcv_searcher* s, const int64_t* source_ids, int n_sources, int64_t lo, int64_t hi, uint32_t flags,
+                                    int64_t* out_rows, int64_t* out_searchable);
+/* pcv_searcher_search_where: for BROAD predicates.  Per query, L is the ranked list pcv_searcher_search returns (canonical score,
+ * ties -> lower position; the searchable rows of the selected sources: hidden rows and a view's restriction apply as everywhere).  L
+ * is walked best first and only its first `pool` entries are examined: a row is KEPT iff it passes; the walk stops right after the
+ * num_results-th kept row, or at the end of the examined prefix.  With out_more == 0 the kept rows are the exact top num_results
+ * of the passing rows.
+ *   pool          num_results .. PCV_MAX_WHERE_POOL: entries of L the walk may examine
+ *   out_ids       [n_queries][num_results] the kept rows, best first, -1 behind them;  out_scores likewise, NaN behind them (may be
+ *                 NULL) — ids and scores are bit for bit what pcv_searcher_search reports for those rows
+ *   out_values    [n_queries][num_results] the value of each kept row, PCV_NO_VALUE for an unset row that passed and behind the
+ *                 results (may be NULL)
+ *   out_counts    [n_queries] rows kept
+ *   out_examined  [n_queries] entries of L examined (may be NULL)
+ *   out_more      [n_queries] 1: the walk stopped at `pool` with fewer than num_results kept and L had another row (may be NULL)
+ * A NULL searcher, no queries, num_results outside [1, PCV_MAX_RESULTS], pool outside [num_results, PCV_MAX_WHERE_POOL] or an
+ * unknown flag bit give PCV_ERR_INVALID before any device work; a searcher with pending rows fails as in pcv_searcher_search.  An
+ * empty table is legal.  A call makes at most ceil(pool / PCV_MAX_RESULTS) passes per group of queries, each followed by a select
+ * step on the device whose cost is fixed, and one short pass more where out_more has to be decided.  Known limit: a predicate that
+ * passes a fraction p of the rows near a query needs about num_results / p examined entries, and `pool` caps that at 4096 —
+ * p = 0.25 % for ten results.  Below that use pcv_searcher_create_view_where; pcv_searcher_count_where reports p.
+ * Not in scope: the predicate inside the scan, a sharded form, several values per item, float values. */
+enum { PCV_MAX_WHERE_POOL = 4096 };
+pcv_status pcv_searcher_search_where(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                     int num_results, int pool, int64_t lo, int64_t hi, uint32_t flags, int64_t* out_ids, float* out_scores,
+                                     int64_t* out_values, int32_t* out_counts, int32_t* out_examined, uint8_t* out_more);
+/* pcv_searcher_create_view_where: for SELECTIVE predicates.  A view (see pcv_searcher_create_view) in every respect — the same handle
+ * type, every search entry point takes it, positions are the parent's, read-only, the copy kind its parent keeps — whose rows are
+ * those whose id passes the predicate: there is no stored id list (pcv_searcher_view_stats reports 0 ids), the rows are selected
+ * on the device from the parent's value table, id columns and implicit ids alike, with no host work per id.  It is stale, and copies
+ * its rows again at its next call, when the parent changed as for every view OR the parent's value table changed (set_values with
+ * n > 0, clear_values); views made by pcv_searcher_create_view never look at the value table.  Unknown flag bits, a NULL argument or
+ * a view as the parent give PCV_ERR_INVALID; a failed allocation PCV_ERR_DEVICE, with nothing left allocated. */
+pcv_status pcv_searcher_create_view_where(pcv_searcher* parent, int64_t lo, int64_t hi, uint32_t flags, pcv_searcher** out_view);
+
 /* Diverse results: exact greedy maximal marginal relevance (MMR), selected on the device — the graded form of what
  * pcv_searcher_search_distinct and pcv_searcher_search_grouped do all-or-nothing.  Per query:
  *   L      the ranked list pcv_searcher_search returns (canonical score, ties -> lower position; the searchable rows of the selected

@@ -10,9 +10,12 @@ from .search import (  # noqa: F401
     PCV_DENSITY_CORE,
     PCV_DENSITY_NOISE,
     PCV_DENSITY_NONE,
+    PCV_NO_VALUE,
     SearchItem,
     Searcher,
     SearcherView,
+    WHERE_OUTSIDE,
+    WHERE_UNSET_PASSES,
     cosine_similarity_multi_query,
     cosine_similarity_single_query,
     deserialize_embedding,

@@ -211,6 +211,16 @@ class GroupStats(C.Structure):
     ]
 
 
+class ValueStats(C.Structure):
+    _fields_ = [
+        ("ids", C.c_int64),
+        ("entries", C.c_int64),
+        ("slots", C.c_int64),
+        ("rehashes", C.c_int32),
+        ("last_set_ms", C.c_float),
+    ]
+
+
 class SeedStats(C.Structure):
     _fields_ = [
         ("rows", C.c_int64),
@@ -325,6 +335,7 @@ SYMBOLS = {
     "pcv_searcher_update_blobs": (C.c_int, [_P, _I64P, _U8P, C.c_int64, _U8P, _I64P]),
     "pcv_searcher_create_view": (C.c_int, [_P, _I64P, C.c_int64, C.POINTER(_P)]),
     "pcv_searcher_view_stats": (C.c_int, [_P, _I64P, _I64P, _INTP, _F32P]),
+    "pcv_searcher_create_view_where": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(_P)]),
     "pcv_searcher_set_kernel": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_screening_copy": (C.c_int, [_P, C.c_int]),
     "pcv_searcher_set_mid_copy": (C.c_int, [_P, C.c_int]),
@@ -340,6 +351,13 @@ SYMBOLS = {
     "pcv_searcher_get_groups": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
     "pcv_searcher_group_stats": (C.c_int, [_P, C.POINTER(GroupStats)]),
     "pcv_searcher_search_grouped": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, _I64P, _F32P, _I64P, _INTP, _INTP, _INTP, _U8P]),
+    "pcv_searcher_set_values": (C.c_int, [_P, _I64P, _I64P, C.c_int64]),
+    "pcv_searcher_clear_values": (C.c_int, [_P]),
+    "pcv_searcher_get_values": (C.c_int, [_P, _I64P, C.c_int64, _I64P]),
+    "pcv_searcher_value_stats": (C.c_int, [_P, C.POINTER(ValueStats)]),
+    "pcv_searcher_count_where": (C.c_int, [_P, _I64P, C.c_int, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pcv_searcher_search_where": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_uint32, _I64P, _F32P,
+                                            _I64P, _INTP, _INTP, _U8P]),
     "pcv_searcher_search_diverse": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int, _I64P, _F32P, _F64P, _INTP, _INTP, _INTP, _U8P]),
     "pcv_searcher_find_duplicates": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_last_duplicate_stats": (C.c_int, [_P, C.POINTER(DuplicateStats)]),

@@ -1,6 +1,6 @@
 // corpus.h — launcher interface of the kernels that build and maintain a corpus segment (corpus_kernels.hip): staging, row
-// scales, the screening and mid copies of scan.h, and hiding, updating, removing, viewing and gathering stored items by id — and of the group table
-// (grouped_kernels.hip), which shares the id hash.
+// scales, the screening and mid copies of scan.h, and hiding, updating, removing, viewing and gathering stored items by id — and of the
+// id-keyed tables (grouped_kernels.hip), which share the id hash, and the predicate kernels over the value table (where_kernels.hip).
 #pragma once
 #include "scan.h"
 
@@ -52,31 +52,35 @@ void launch_repack16_rows(hipStream_t st, const float4* blk, const float* scale,
 // ... the mid copy: items are blocks (scale8 != nullptr: every row of each, with the block's scale) or rows; rows >= mid_rows skipped
 void launch_repack_mid(hipStream_t st, const float4* blk, const float* scale, const float* scale8, const uint32_t* items, uint32_t n,
                        uint32_t mid_rows, uint4* mid16, float* scale16, int D4);
-// ---- the group table (pcv_searcher_set_groups; grouped_kernels.hip; DESIGN.md §4 "Grouped results") ----
-// Item id -> group key, resident on the device: keys[slots] and vals[slots] (int64 each), slots a power of two, linear probing from
+// ---- the id-keyed tables (pcv_searcher_set_groups, pcv_searcher_set_values; grouped_kernels.hip; DESIGN.md §4 "Grouped results",
+// "Item values and filtered search") ----
+// Item id -> int64, resident on the device: keys[slots] and vals[slots] (int64 each), slots a power of two, linear probing from
 // id_hash, kIdEmpty in free slots.  The id kIdEmpty has no slot: its value lives in the head block, beside the two counters.
+// One table type, two instances: what `none` is — the value that says "an entry and nothing else" — is a parameter of the table.
+constexpr int64_t kNoGroup = -1;         // the group table's (PCV_NO_GROUP)
+constexpr int64_t kNoValue = INT64_MIN;  // the value table's (PCV_NO_VALUE)
 struct GroupHead {
     int64_t entries;        // ids that have an entry (the side slot included)
-    int64_t ids;            // ... and a group >= 0
-    int64_t side_val;       // the group of id kIdEmpty (-1: none)
+    int64_t ids;            // ... and a value other than `none`
+    int64_t side_val;       // the value of id kIdEmpty (`none`: none)
     uint32_t side_claim;    // its word of `claim`
     uint32_t side_present;  // 1: id kIdEmpty has an entry
 };
 constexpr uint32_t kGroupSideSlot = 0xffffffffu;  // slot_of[] of id kIdEmpty
 constexpr uint32_t kGroupBatch = 1u << 22;        // most ids of one upsert or lookup launch (the host feeds a longer batch in order)
-// every slot free, every value -1
-void launch_group_fill(hipStream_t st, int64_t* keys, int64_t* vals, uint64_t slots);
+// every slot free, every value `none`
+void launch_group_fill(hipStream_t st, int64_t* keys, int64_t* vals, uint64_t slots, int64_t none);
 // Upsert of (ids[i], groups[i]), i < n <= kGroupBatch: of an id that occurs more than once the LAST occurrence is stored, whatever
 // order the atomics land in.  claim[slots] is all 0 before and after; slot_of[n] is scratch.  The table must have n free slots
-// and stay half empty.
+// and stay half empty.  head->ids counts the transitions none -> set and set -> none.
 void launch_group_upsert(hipStream_t st, int64_t* keys, int64_t* vals, uint32_t mask, uint32_t* claim, GroupHead* head, const int64_t* ids,
-                         const int64_t* groups, uint32_t n, uint32_t* slot_of);
+                         const int64_t* groups, uint32_t n, uint32_t* slot_of, int64_t none);
 // every entry of an old table into a new one (launch_group_fill'ed, at least as large)
 void launch_group_rehash(hipStream_t st, const int64_t* old_keys, const int64_t* old_vals, uint64_t old_slots, int64_t* keys, int64_t* vals,
                          uint32_t mask);
-// out[i] = group of ids[i], -1 if it has none (keys == nullptr: a table without slots)
+// out[i] = what the table holds for ids[i], `none` if nothing (keys == nullptr: a table without slots)
 void launch_group_lookup(hipStream_t st, const int64_t* keys, const int64_t* vals, uint32_t mask, const GroupHead* head, const int64_t* ids,
-                         uint32_t n, int64_t* out);
+                         uint32_t n, int64_t* out, int64_t none);
 // ---- updated items (pcv_searcher_update_rows) ----
 // launch_match_ids whose table also carries each id's slot in the batch (vals[h]; empty_slot for kIdEmpty): rows [row0, row1) of
 // a segment whose id is in the batch -> (out_rows[i], out_slots[i]) for the first `cap`, their number -> *out_n (zeroed here)
@@ -100,6 +104,42 @@ void launch_view_select(hipStream_t st, const int64_t* ids, uint32_t nrows, cons
                         uint32_t* flags4, uint32_t* tile_cnt, uint32_t* total, bool invert = false);
 void launch_view_compact(hipStream_t st, const uint32_t* flags4, const uint32_t* tile_off, uint32_t nrows, uint32_t* sel,
                          uint32_t off0 = 0);
+// the second half of launch_view_select alone: tile_cnt[0..ntiles) -> exclusive prefix sums in place, their sum -> *total
+void launch_view_scan(hipStream_t st, uint32_t* tile_cnt, uint32_t ntiles, uint32_t* total);
+// ---- filtered search (pcv_searcher_count_where / _search_where / _create_view_where; where_kernels.hip; DESIGN.md §4 "Item
+// values and filtered search") ----
+// The value table as its readers get it (keys == nullptr: a table without slots — no id has a value but, maybe, kIdEmpty), and
+// a predicate over the value of a row's id (value_table.h: where_passes).
+struct ValueTable {
+    const int64_t* keys;
+    const int64_t* vals;
+    uint32_t mask;
+    int64_t side_val;  // the value of id kIdEmpty, which has no slot (kNoValue: none)
+};
+struct WherePred {
+    int64_t lo, hi;
+    uint32_t flags;  // kWhere*
+};
+constexpr uint32_t kWhereUnsetPasses = 1u, kWhereOutside = 2u;  // PCV_WHERE_*
+// Rows of a segment that pass: launch_view_select's first launch with the predicate in place of the id batch — the same flags4 /
+// tile_cnt pair, so launch_view_scan and launch_view_compact follow unchanged — and tile_live[tile] = the flagged rows of the tile
+// with scale != 0.  A row's id is ids ? ids[row] : id0 + row.  Reads the table, writes nothing to it.
+void launch_where_mark(hipStream_t st, const int64_t* ids, int64_t id0, const float* scale, uint32_t nrows, const ValueTable& t,
+                       const WherePred& w, uint32_t* flags4, uint32_t* tile_cnt, uint32_t* tile_live);
+// acc[0] += sum of tile_cnt[0..ntiles), acc[1] += sum of tile_live[0..ntiles): integer adds, one workgroup
+void launch_where_sum(hipStream_t st, const uint32_t* tile_cnt, const uint32_t* tile_live, uint32_t ntiles, int64_t* acc);
+// The select step of pcv_searcher_search_where: the walk of search_grouped (scan.h, DistinctRec) with the predicate as the test —
+// a hit is kept iff the value of its id passes.
+struct WhereArgs {
+    DistinctRec* rec;        // [B]
+    DistinctRec* rec_host;   // [B] pinned host mirror, written after every pass
+    pcv_hit_dev* kept;       // [B][kMaxK] the kept rows, best first, as the pass listed them
+    int64_t* kept_value;     // [B][kMaxK] their values (kNoValue: an unset row that passed)
+    ValueTable table;
+    WherePred where;
+    int num_results;
+};
+void launch_where_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const WhereArgs& a);
 // rows [dst_row0, dst_row0 + n_sel) of a view segment take rows sel[0..n_sel) of a parent segment (pieces, scale, id; parent
 // position pos0 + row -> dst_ppos[row of the view segment], unless dst_ppos is nullptr); rows [dst_row0 + n_sel, dst_end) become
 // padding

@@ -992,7 +992,11 @@ void launch_view_select(hipStream_t st, const int64_t* ids, uint32_t nrows, cons
     }
     view_mark_kernel<<<nt, 256, 0, st>>>(ids, nrows, table, tmask, has_empty ? 1 : 0, invert ? 1 : 0, flags4, tile_cnt);
     PCV_LAUNCHED();
-    view_scan_kernel<<<1, 256, 0, st>>>(tile_cnt, nt, total);
+    launch_view_scan(st, tile_cnt, nt, total);
+}
+
+void launch_view_scan(hipStream_t st, uint32_t* tile_cnt, uint32_t ntiles, uint32_t* total) {
+    view_scan_kernel<<<1, 256, 0, st>>>(tile_cnt, ntiles, total);
     PCV_LAUNCHED();
 }
 

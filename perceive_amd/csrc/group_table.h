@@ -1,5 +1,6 @@
-// group_table.h — the probe of the group table (corpus.h; DESIGN.md §4 "Grouped results"): the one copy, for every kernel that reads
-// the table at rest (group_lookup_kernel, grouped_select_kernel, row_groups_kernel).  Everything here is inlined: the file defines no symbol.
+// group_table.h — the probe of an id-keyed table (corpus.h; DESIGN.md §4 "Grouped results", "Item values and filtered search"):
+// the one copy, for every kernel that reads such a table at rest (group_lookup_kernel, grouped_select_kernel, row_groups_kernel; the
+// value table's readers go through value_table.h).  Everything here is inlined: the file defines no symbol.
 #pragma once
 #include "corpus.h"
 #include "device_access.h"
@@ -16,13 +17,13 @@ __device__ __forceinline__ uint32_t find_slot(const int64_t* __restrict__ keys, 
         if (k == id || k == kIdEmpty) return h;
     }
 }
-// The group of `id`, or -1.
+// What the table maps `id` to, or `none` (the table's own "no value": kNoGroup for the group table, kNoValue for the value table).
 __device__ __forceinline__ int64_t group_of(const int64_t* __restrict__ keys, const int64_t* __restrict__ vals, uint32_t mask,
-                                            int64_t side_val, int64_t id) {
+                                            int64_t side_val, int64_t id, int64_t none) {
     if (id == kIdEmpty) return side_val;
-    if (keys == nullptr) return -1;
+    if (keys == nullptr) return none;
     const uint32_t h = find_slot(keys, mask, id);
-    return gld(&keys[h]) == id ? gld(&vals[h]) : (int64_t)-1;
+    return gld(&keys[h]) == id ? gld(&vals[h]) : none;
 }
 
 // The 32-bit tag of a group key (row_jobs.h, PairGroups): 0 for none, equal keys give equal non-zero tags, different keys may collide.

@@ -1,17 +1,20 @@
-// grouped_kernels.hip — the group table of a searcher and the select step of pcv_searcher_search_grouped (DESIGN.md §4 "Grouped
-// results").
+// grouped_kernels.hip — the id-keyed tables of a searcher (groups, values) and the select step of pcv_searcher_search_grouped
+// (DESIGN.md §4 "Grouped results").
 //
-// The table maps item id -> group key: open addressing, capacity a power of two, linear probing from id_hash, kIdEmpty in free
+// A table maps item id -> int64 (a group key, a value): open addressing, capacity a power of two, linear probing from id_hash, kIdEmpty in free
 // slots (corpus.h: the definitions the batch tables of hide / update / views use).  The id kIdEmpty itself has no slot: its value
-// lives in GroupHead::side_val.  Values are >= 0 (a group) or PCV_NO_GROUP (-1: the id has an entry and no group); a slot that was
-// never stored to reads -1 as well.  There are no tombstones: an entry, once made, stays until the table is cleared.
+// lives in GroupHead::side_val.  One value of the table, `none`, means "the id has an entry and nothing else": a slot that was never
+// stored to reads `none` as well, and the counter of ids follows the transitions none <-> anything else.  The table is instantiated
+// twice (corpus.h): the group table with none = kNoGroup (-1; the host admits no other negative group) and the value table of
+// DESIGN.md §4 "Item values and filtered search" with none = kNoValue (INT64_MIN).  There are no tombstones: an entry, once made,
+// stays until the table is cleared.
 //
 // Nothing here depends on the order in which an atomic lands:
 //   * an upsert is two launches.  group_claim_kernel: every element of the batch finds or claims the slot of its id (64-bit
 //     compare-and-swap on the key; whoever loses a race for a free slot sees the winner's key and either has found its own id or
 //     probes on) and raises the slot's word of `claim` to its batch index + 1 (atomic max).  group_store_kernel: the one element
 //     whose index IS that maximum — the last occurrence of the id in the batch — reads the old value, stores the new one and
-//     counts none -> group / group -> none.  Which slot an id lands in may differ from run to run (two ids racing for one free
+//     counts none -> set / set -> none.  Which slot an id lands in may differ from run to run (two ids racing for one free
 //     slot), what the table maps it to does not: a probe walks the whole chain up to the first free slot;
 //   * group_rehash_kernel moves distinct keys: the same argument, without values in dispute;
 //   * grouped_select_kernel only reads the table; its own counters are integer adds in LDS, which commute.
@@ -39,11 +42,11 @@ __device__ __forceinline__ void count_add(int64_t* p, int64_t v) {
     __hip_atomic_fetch_add((PCV_GLOBAL u64*)p, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(256) void group_fill_kernel(int64_t* __restrict__ keys, int64_t* __restrict__ vals, uint64_t slots) {
+__global__ __launch_bounds__(256) void group_fill_kernel(int64_t* __restrict__ keys, int64_t* __restrict__ vals, uint64_t slots, int64_t none) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < slots) {
         gst(&keys[i], kIdEmpty);
-        gst(&vals[i], (int64_t)-1);
+        gst(&vals[i], none);
     }
 }
 
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(256) void group_claim_kernel(int64_t* __restrict__ 
 // The highest bidder of each slot stores its value.
 __global__ __launch_bounds__(256) void group_store_kernel(int64_t* __restrict__ vals, uint32_t* __restrict__ claim,
                                                           GroupHead* __restrict__ head, const int64_t* __restrict__ groups, uint32_t n,
-                                                          const uint32_t* __restrict__ slot_of) {
+                                                          const uint32_t* __restrict__ slot_of, int64_t none) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint32_t h = gld(&slot_of[i]);
@@ -99,8 +102,8 @@ __global__ __launch_bounds__(256) void group_store_kernel(int64_t* __restrict__ 
         gst(&vals[h], g);
         gst(&claim[h], 0u);  // (the words are all 0 again when the launch is through: the next batch starts from that)
     }
-    if (old < 0 && g >= 0) count_add(&head->ids, 1);
-    if (old >= 0 && g < 0) count_add(&head->ids, -1);
+    if (old == none && g != none) count_add(&head->ids, 1);
+    if (old != none && g == none) count_add(&head->ids, -1);
 }
 
 // Every entry of the old table into the new one (filled with free slots, at least as large).
@@ -121,10 +124,10 @@ __global__ __launch_bounds__(256) void group_rehash_kernel(const int64_t* __rest
 
 __global__ __launch_bounds__(256) void group_lookup_kernel(const int64_t* __restrict__ keys, const int64_t* __restrict__ vals, uint32_t mask,
                                                            const GroupHead* __restrict__ head, const int64_t* __restrict__ ids, uint32_t n,
-                                                           int64_t* __restrict__ out) {
+                                                           int64_t* __restrict__ out, int64_t none) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    gst(&out[i], group_of(keys, vals, mask, gld(&head->side_val), gld(&ids[i])));
+    gst(&out[i], group_of(keys, vals, mask, gld(&head->side_val), gld(&ids[i]), none));
 }
 
 // The groups of a row job's launch rows (row_jobs.h, PairGroups), behind its prep step: one thread per launch row.  A row that takes
@@ -135,7 +138,7 @@ __global__ __launch_bounds__(256) void row_groups_kernel(const ScanParams* __res
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     int64_t g = -1;
     const bool in = i < (uint64_t)p.total_blocks * 32;
-    if (in && gld(&a.rinv[i]) != 0.0f) g = group_of(a.keys, a.vals, a.mask, a.side_val, row_id(row_ref(p, (uint32_t)i)));
+    if (in && gld(&a.rinv[i]) != 0.0f) g = group_of(a.keys, a.vals, a.mask, a.side_val, row_id(row_ref(p, (uint32_t)i)), kNoGroup);
     if (in) {
         gst(&a.grp[i], g);
         gst(&a.tag[i], group_tag(g));
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(kMaxK) void grouped_select_kernel(const ScanParams*
     }
     s_kept_group[t] = t < nk0 ? gld(&a.kept_group[o + t]) : (int64_t)-1;
     s_count[t] = t < nk0 ? gld(&a.collapsed[o + t]) : 0;
-    const int64_t g = live ? group_of(a.keys, a.vals, a.mask, a.side_val, h.id) : (int64_t)-1;
+    const int64_t g = live ? group_of(a.keys, a.vals, a.mask, a.side_val, h.id, kNoGroup) : (int64_t)-1;
     s_group[t] = g;
     __syncthreads();
     if (live) atomicAdd(&s_n_new, 1u);
@@ -232,21 +235,21 @@ __global__ __launch_bounds__(kMaxK) void grouped_select_kernel(const ScanParams*
 
 }  // namespace
 
-void launch_group_fill(hipStream_t st, int64_t* keys, int64_t* vals, uint64_t slots) {
+void launch_group_fill(hipStream_t st, int64_t* keys, int64_t* vals, uint64_t slots, int64_t none) {
     if (slots == 0) return;
-    group_fill_kernel<<<cdiv64((int64_t)slots, 256), 256, 0, st>>>(keys, vals, slots);
+    group_fill_kernel<<<cdiv64((int64_t)slots, 256), 256, 0, st>>>(keys, vals, slots, none);
     PCV_LAUNCHED();
 }
 
 void launch_group_upsert(hipStream_t st, int64_t* keys, int64_t* vals, uint32_t mask, uint32_t* claim, GroupHead* head, const int64_t* ids,
-                         const int64_t* groups, uint32_t n, uint32_t* slot_of) {
+                         const int64_t* groups, uint32_t n, uint32_t* slot_of, int64_t none) {
     if (n == 0) return;
     PCV_REQUIRE(keys != nullptr && vals != nullptr && claim != nullptr && (mask & (mask + 1)) == 0 && n <= kGroupBatch,
                 "group upsert: bad shape (%u ids, mask %#x)", n, mask);
     const unsigned grid = cdiv64(n, 256);
     group_claim_kernel<<<grid, 256, 0, st>>>(keys, mask, claim, head, ids, n, slot_of);
     PCV_LAUNCHED();
-    group_store_kernel<<<grid, 256, 0, st>>>(vals, claim, head, groups, n, slot_of);
+    group_store_kernel<<<grid, 256, 0, st>>>(vals, claim, head, groups, n, slot_of, none);
     PCV_LAUNCHED();
 }
 
@@ -260,9 +263,9 @@ void launch_group_rehash(hipStream_t st, const int64_t* old_keys, const int64_t*
 }
 
 void launch_group_lookup(hipStream_t st, const int64_t* keys, const int64_t* vals, uint32_t mask, const GroupHead* head, const int64_t* ids,
-                         uint32_t n, int64_t* out) {
+                         uint32_t n, int64_t* out, int64_t none) {
     if (n == 0) return;
-    group_lookup_kernel<<<cdiv64(n, 256), 256, 0, st>>>(keys, vals, mask, head, ids, n, out);
+    group_lookup_kernel<<<cdiv64(n, 256), 256, 0, st>>>(keys, vals, mask, head, ids, n, out, none);
     PCV_LAUNCHED();
 }
 

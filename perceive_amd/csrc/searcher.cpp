@@ -7,6 +7,7 @@
 // (scan.h).  Searching streams the selected segments once; see scan_kernels.hip for the pipeline.
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <iterator>
 #include <numeric>
 
@@ -90,8 +91,10 @@ void destroy_searcher(pcv_searcher* s) {
     }
     for (auto& src : s->sources)
         for (auto& g : src.segs) free_segment(g);
-    if (s->groups.keys) (void)hipFree(s->groups.keys);
-    if (s->groups.vals) (void)hipFree(s->groups.vals);
+    for (pcv_searcher::IdTable* t : {&s->groups, &s->values}) {
+        if (t->keys) (void)hipFree(t->keys);
+        if (t->vals) (void)hipFree(t->vals);
+    }
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
     if (s->d_max_norm_bits) (void)hipFree(s->d_max_norm_bits);
     for (auto& e : s->ev)
@@ -110,6 +113,42 @@ pcv_status pcv_searcher_destroy(pcv_searcher* s) {
     });
 }
 
+namespace {
+// What both kinds of view are made by (parent->mu held, the arguments checked): `setup` gives the fresh handle its allow list or its
+// predicate, then the rows are copied.
+pcv_searcher* make_view(pcv_searcher* parent, const char* who, const std::function<void(pcv_searcher*)>& setup) {
+    PCV_REQUIRE(!parent->dirty, "%s: pending rows; call pcv_searcher_finalize first", who);
+    PCV_REQUIRE(!parent->pending.active, "%s: a queued pass has not been collected", who);
+    PCV_HIP(hipSetDevice(parent->ctx->device));
+    pcv_searcher* v = new pcv_searcher();
+    v->ctx = parent->ctx;
+    v->D = parent->D;
+    v->Dp = parent->Dp;
+    v->D4 = parent->D4;
+    v->metric = parent->metric;
+    v->kernel = parent->kernel;
+    v->scan_flags = parent->scan_flags;
+    v->cand_cap = parent->cand_cap;
+    v->use_graph = parent->use_graph;
+    setup(v);
+    v->view_parent = parent;
+    parent->live_views.fetch_add(1);  // (given back by destroy_searcher, also if the build fails)
+    try {
+        build_view(v, parent);
+    } catch (...) {
+        destroy_searcher(v);
+        throw;
+    }
+    return v;
+}
+
+// The predicate of the filtered calls: any flag bit but the two known ones is refused.
+WherePred check_where(int64_t lo, int64_t hi, uint32_t flags, const char* who) {
+    PCV_REQUIRE((flags & ~(uint32_t)(PCV_WHERE_UNSET_PASSES | PCV_WHERE_OUTSIDE)) == 0, "%s: unknown flag bits in %#x", who, flags);
+    return WherePred{lo, hi, flags};
+}
+}  // namespace
+
 pcv_status pcv_searcher_create_view(pcv_searcher* parent, const int64_t* ids, int64_t n, pcv_searcher** out_view) {
     return guarded([&] {
         PCV_REQUIRE(parent != nullptr && out_view != nullptr, "create_view: NULL argument");
@@ -120,29 +159,21 @@ pcv_status pcv_searcher_create_view(pcv_searcher* parent, const int64_t* ids, in
         std::sort(allow.begin(), allow.end());
         allow.erase(std::unique(allow.begin(), allow.end()), allow.end());
         std::lock_guard<std::mutex> lk(parent->mu);
-        PCV_REQUIRE(!parent->dirty, "create_view: pending rows; call pcv_searcher_finalize first");
-        PCV_REQUIRE(!parent->pending.active, "create_view: a queued pass has not been collected");
-        PCV_HIP(hipSetDevice(parent->ctx->device));
-        pcv_searcher* v = new pcv_searcher();
-        v->ctx = parent->ctx;
-        v->D = parent->D;
-        v->Dp = parent->Dp;
-        v->D4 = parent->D4;
-        v->metric = parent->metric;
-        v->kernel = parent->kernel;
-        v->scan_flags = parent->scan_flags;
-        v->cand_cap = parent->cand_cap;
-        v->use_graph = parent->use_graph;
-        v->view_ids.swap(allow);
-        v->view_parent = parent;
-        parent->live_views.fetch_add(1);  // (given back by destroy_searcher, also if the build fails)
-        try {
-            build_view(v, parent);
-        } catch (...) {
-            destroy_searcher(v);
-            throw;
-        }
-        *out_view = v;
+        *out_view = make_view(parent, "create_view", [&](pcv_searcher* v) { v->view_ids.swap(allow); });
+    });
+}
+
+pcv_status pcv_searcher_create_view_where(pcv_searcher* parent, int64_t lo, int64_t hi, uint32_t flags, pcv_searcher** out_view) {
+    return guarded([&] {
+        PCV_REQUIRE(parent != nullptr && out_view != nullptr, "create_view_where: NULL argument");
+        *out_view = nullptr;
+        const WherePred w = check_where(lo, hi, flags, "create_view_where");
+        PCV_REQUIRE(parent->view_parent == nullptr, "create_view_where: the parent is itself a view");
+        std::lock_guard<std::mutex> lk(parent->mu);
+        *out_view = make_view(parent, "create_view_where", [&](pcv_searcher* v) {
+            v->view_by_value = true;
+            v->view_where = w;
+        });
     });
 }
 
@@ -154,7 +185,7 @@ pcv_status pcv_searcher_view_stats(pcv_searcher* v, int64_t* out_rows, int64_t* 
         PCV_REQUIRE(!v->pending.active, "view_stats: a queued pass has not been collected");
         sync_view(v);
         if (out_rows) *out_rows = v->view_rows;
-        if (out_ids) *out_ids = (int64_t)v->view_ids.size();
+        if (out_ids) *out_ids = (int64_t)v->view_ids.size();  // (0 for a predicate view: it stores no list)
         if (out_refreshes) *out_refreshes = v->view_refreshes;
         if (out_build_ms) *out_build_ms = v->view_build_ms;
     });
@@ -715,7 +746,7 @@ pcv_status pcv_searcher_set_groups(pcv_searcher* s, const int64_t* ids, const in
         refuse_view(s, "set_groups");
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->pending.active, "set_groups: a queued pass has not been collected");
-        set_groups(s, ids, groups, n);
+        set_table(s, s->groups, "set_groups", ids, groups, n);
     });
 }
 
@@ -725,7 +756,7 @@ pcv_status pcv_searcher_clear_groups(pcv_searcher* s) {
         refuse_view(s, "clear_groups");
         std::lock_guard<std::mutex> lk(s->mu);
         PCV_REQUIRE(!s->pending.active, "clear_groups: a queued pass has not been collected");
-        clear_groups(s);
+        clear_table(s, s->groups);
     });
 }
 
@@ -736,7 +767,7 @@ pcv_status pcv_searcher_get_groups(pcv_searcher* s, const int64_t* ids, int64_t 
         pcv_searcher* owner = s->view_parent ? s->view_parent : s;
         std::lock_guard<std::mutex> lk(owner->mu);
         PCV_REQUIRE(!owner->pending.active, "get_groups: a queued pass has not been collected");
-        get_groups(owner, ids, n, out_groups);
+        get_table(owner, owner->groups, ids, n, out_groups);
     });
 }
 
@@ -745,7 +776,7 @@ pcv_status pcv_searcher_group_stats(pcv_searcher* s, pcv_group_stats* out) {
         PCV_REQUIRE(s != nullptr && out != nullptr, "group_stats: NULL argument");
         pcv_searcher* owner = s->view_parent ? s->view_parent : s;
         std::lock_guard<std::mutex> lk(owner->mu);
-        const pcv_searcher::Groups& t = owner->groups;
+        const pcv_searcher::IdTable& t = owner->groups;
         *out = pcv_group_stats{t.head.ids, t.head.entries, (int64_t)t.slots, t.rehashes, t.last_set_ms};
     });
 }
@@ -763,6 +794,83 @@ pcv_status pcv_searcher_search_grouped(pcv_searcher* s, const float* queries, in
         if (s->view_parent) plk = std::unique_lock<std::mutex>(s->view_parent->mu);
         search_grouped(RankedCall{s, queries, n_queries, source_ids, n_sources, num_results, pool, out_ids, out_scores, out_counts, out_examined, out_more},
                        s->view_parent ? s->view_parent : s, out_groups, out_collapsed);
+    });
+}
+
+pcv_status pcv_searcher_set_values(pcv_searcher* s, const int64_t* ids, const int64_t* values, int64_t n) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "set_values: searcher is NULL");
+        PCV_REQUIRE(n >= 0 && ((ids != nullptr && values != nullptr) || n == 0), "set_values: bad lists (NULL with n > 0, or n < 0)");
+        refuse_view(s, "set_values");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "set_values: a queued pass has not been collected");
+        if (n == 0) return;
+        const auto bump = at_exit([&] { s->values_gen += 1; });  // (also when the call fails half way: the table may have changed)
+        set_table(s, s->values, "set_values", ids, values, n);
+    });
+}
+
+pcv_status pcv_searcher_clear_values(pcv_searcher* s) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "clear_values: searcher is NULL");
+        refuse_view(s, "clear_values");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "clear_values: a queued pass has not been collected");
+        const auto bump = at_exit([&] { s->values_gen += 1; });
+        clear_table(s, s->values);
+    });
+}
+
+pcv_status pcv_searcher_get_values(pcv_searcher* s, const int64_t* ids, int64_t n, int64_t* out_values) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "get_values: searcher is NULL");
+        PCV_REQUIRE(n >= 0 && ((ids != nullptr && out_values != nullptr) || n == 0), "get_values: bad lists (NULL with n > 0, or n < 0)");
+        pcv_searcher* owner = s->view_parent ? s->view_parent : s;
+        std::lock_guard<std::mutex> lk(owner->mu);
+        PCV_REQUIRE(!owner->pending.active, "get_values: a queued pass has not been collected");
+        get_table(owner, owner->values, ids, n, out_values);
+    });
+}
+
+pcv_status pcv_searcher_value_stats(pcv_searcher* s, pcv_value_stats* out) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr && out != nullptr, "value_stats: NULL argument");
+        pcv_searcher* owner = s->view_parent ? s->view_parent : s;
+        std::lock_guard<std::mutex> lk(owner->mu);
+        const pcv_searcher::IdTable& t = owner->values;
+        *out = pcv_value_stats{t.head.ids, t.head.entries, (int64_t)t.slots, t.rehashes, t.last_set_ms};
+    });
+}
+
+pcv_status pcv_searcher_count_where(pcv_searcher* s, const int64_t* source_ids, int n_sources, int64_t lo, int64_t hi, uint32_t flags,
+                                    int64_t* out_rows, int64_t* out_searchable) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "count_where: searcher is NULL");
+        PCV_REQUIRE(n_sources >= 0 && (source_ids != nullptr || n_sources == 0), "count_where: bad source list (NULL with n_sources > 0, or n_sources < 0)");
+        const WherePred w = check_where(lo, hi, flags, "count_where");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "count_where: a queued pass has not been collected");
+        sync_view(s);
+        std::unique_lock<std::mutex> plk;  // (as in search_grouped: the parent's table is read)
+        if (s->view_parent) plk = std::unique_lock<std::mutex>(s->view_parent->mu);
+        count_where(s, s->view_parent ? s->view_parent : s, source_ids, n_sources, w, out_rows, out_searchable);
+    });
+}
+
+pcv_status pcv_searcher_search_where(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                     int num_results, int pool, int64_t lo, int64_t hi, uint32_t flags, int64_t* out_ids, float* out_scores,
+                                     int64_t* out_values, int32_t* out_counts, int32_t* out_examined, uint8_t* out_more) {
+    return guarded([&] {
+        check_ranked_args(s, queries, n_queries, num_results, pool, "search_where", (int)PCV_MAX_WHERE_POOL);
+        const WherePred w = check_where(lo, hi, flags, "search_where");
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "search_where: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        // (a view reads its parent's table: the parent stays locked while the kernels may follow its pointers)
+        std::unique_lock<std::mutex> plk;
+        if (s->view_parent) plk = std::unique_lock<std::mutex>(s->view_parent->mu);
+        search_where(RankedCall{s, queries, n_queries, source_ids, n_sources, num_results, pool, out_ids, out_scores, out_counts, out_examined, out_more},
+                     s->view_parent ? s->view_parent : s, w, out_values);
     });
 }
 

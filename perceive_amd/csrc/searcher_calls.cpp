@@ -448,23 +448,22 @@ void search_diverse(const RankedCall& c, float lambda, double* out_marginal, int
     });
 }
 
-// ---- grouped results (pcv_searcher_set_groups / _search_grouped; DESIGN.md §4 "Grouped results") ----
+// ---- the id-keyed tables (pcv_searcher_set_groups / _set_values; DESIGN.md §4 "Grouped results", "Item values and filtered search") ----
 constexpr int64_t kMaxGroupEntries = (int64_t)1 << 30;
 constexpr uint64_t kMinGroupSlots = 1024;
-constexpr size_t kGroupKeptBytes = (size_t)64 << 20;  // scratch of a set_groups / get_groups call beyond this is given back
+constexpr size_t kGroupKeptBytes = (size_t)64 << 20;  // scratch of a set / get call beyond this is given back
 
-// The table of `s` gets `slots` slots (a power of two, more than it has): the entries move by a rehash on the device.  If the
+// Table `t` of `s` gets `slots` slots (a power of two, more than it has): the entries move by a rehash on the device.  If the
 // allocation fails the old table stays as it is.
-static void grow_groups(pcv_searcher* s, uint64_t slots) {
-    pcv_searcher::Groups& t = s->groups;
+static void grow_table(pcv_searcher* s, pcv_searcher::IdTable& t, const char* who, uint64_t slots) {
     hipStream_t st = s->ctx->stream;
     int64_t *keys = nullptr, *vals = nullptr;
     const hipError_t e = alloc_with_scales(s->fail_copy_alloc, &keys, slots * sizeof(int64_t), &vals, slots * sizeof(int64_t));
     if (e != hipSuccess)
-        PCV_FAIL(PCV_ERR_DEVICE, "set_groups: hipMalloc of %.2f GB for a group table of %llu slots failed: %s (the table is unchanged)",
-                 slots * 16 / 1e9, (unsigned long long)slots, hipGetErrorString(e));
+        PCV_FAIL(PCV_ERR_DEVICE, "%s: hipMalloc of %.2f GB for a %s table of %llu slots failed: %s (the table is unchanged)", who,
+                 slots * 16 / 1e9, t.what, (unsigned long long)slots, hipGetErrorString(e));
     try {
-        launch_group_fill(st, keys, vals, slots);
+        launch_group_fill(st, keys, vals, slots, t.none);
         launch_group_rehash(st, t.keys, t.vals, t.slots, keys, vals, (uint32_t)(slots - 1));
         PCV_HIP(hipStreamSynchronize(st));
     } catch (...) {
@@ -480,20 +479,19 @@ static void grow_groups(pcv_searcher* s, uint64_t slots) {
     t.slots = slots;
 }
 
-static void trim_group_scratch(pcv_searcher* s) {
-    pcv_searcher::Groups& t = s->groups;
+static void trim_table_scratch(pcv_searcher::IdTable& t) {
     if (t.d_claim.n * sizeof(uint32_t) > kGroupKeptBytes) t.d_claim.release();
     if (t.d_slot.n * sizeof(uint32_t) > kGroupKeptBytes) t.d_slot.release();
     if (t.d_batch.n * sizeof(int64_t) > kGroupKeptBytes) t.d_batch.release();
 }
 
-// The upsert of a batch (s->mu held, s no view, the arguments checked): one growth decision, then the batch kGroupBatch ids at a
-// time, in order — a later occurrence of an id overrides an earlier one inside a launch (launch_group_upsert) and across launches.
-void set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int64_t n) {
-    pcv_searcher::Groups& t = s->groups;
+// The upsert of a batch into table `t` of `s` (s->mu held, s no view, the arguments checked): one growth decision, then the batch
+// kGroupBatch ids at a time, in order — a later occurrence of an id overrides an earlier one inside a launch (launch_group_upsert)
+// and across launches.
+void set_table(pcv_searcher* s, pcv_searcher::IdTable& t, const char* who, const int64_t* ids, const int64_t* vals, int64_t n) {
     if (n == 0) return;
     if (t.head.entries + n > kMaxGroupEntries)
-        PCV_FAIL(PCV_ERR_UNSUPPORTED, "set_groups: %lld entries and %lld ids more exceed the table's limit of 2^30 entries",
+        PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: %lld entries and %lld ids more exceed the table's limit of 2^30 entries", who,
                  (long long)t.head.entries, (long long)n);
     PCV_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
@@ -512,8 +510,8 @@ void set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int6
     PCV_HIP(hipEventRecord(ev[0], st));
     uint64_t slots = std::max(t.slots, kMinGroupSlots);
     while (slots < 2 * (uint64_t)(t.head.entries + n)) slots *= 2;
-    if (slots != t.slots) grow_groups(s, slots);
-    auto trim = at_exit([&] { trim_group_scratch(s); });
+    if (slots != t.slots) grow_table(s, t, who, slots);
+    auto trim = at_exit([&] { trim_table_scratch(t); });
     t.d_claim.ensure(t.slots);
     PCV_HIP(hipMemsetAsync(t.d_claim.p, 0, t.slots * sizeof(uint32_t), st));
     const size_t m_most = (size_t)std::min<int64_t>(n, kGroupBatch);
@@ -522,9 +520,9 @@ void set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int6
     for (int64_t i0 = 0; i0 < n; i0 += kGroupBatch) {
         const size_t m = (size_t)std::min<int64_t>(kGroupBatch, n - i0);
         PCV_HIP(hipMemcpyAsync(t.d_batch.p, ids + i0, m * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        PCV_HIP(hipMemcpyAsync(t.d_batch.p + m_most, groups + i0, m * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        PCV_HIP(hipMemcpyAsync(t.d_batch.p + m_most, vals + i0, m * sizeof(int64_t), hipMemcpyHostToDevice, st));
         launch_group_upsert(st, t.keys, t.vals, (uint32_t)(t.slots - 1), t.d_claim.p, t.d_head.p, t.d_batch.p, t.d_batch.p + m_most,
-                            (uint32_t)m, t.d_slot.p);
+                            (uint32_t)m, t.d_slot.p, t.none);
     }
     PCV_HIP(hipMemcpyAsync(t.pin_head.p, t.d_head.p, sizeof(GroupHead), hipMemcpyDeviceToHost, st));
     PCV_HIP(hipEventRecord(ev[1], st));
@@ -535,43 +533,43 @@ void set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int6
     t.last_set_ms = ms;
 }
 
-// The searcher is as created: no table, every counter 0.
-void clear_groups(pcv_searcher* s) {
-    pcv_searcher::Groups& t = s->groups;
+// The table is as created: no slots, every counter 0.
+void clear_table(pcv_searcher* s, pcv_searcher::IdTable& t) {
     PCV_HIP(hipSetDevice(s->ctx->device));
     PCV_HIP(hipStreamSynchronize(s->ctx->stream));
     if (t.keys) (void)hipFree(t.keys);
     if (t.vals) (void)hipFree(t.vals);
     t.keys = t.vals = nullptr;
     t.slots = 0;
-    t.head = GroupHead{0, 0, -1, 0, 0};
-    t.d_head.release();  // (the next set_groups uploads a fresh one)
+    t.head = GroupHead{0, 0, t.none, 0, 0};
+    t.d_head.release();  // (the next upsert uploads a fresh one)
     t.d_claim.release();
     t.rehashes = 0;
     t.last_set_ms = 0.0f;
 }
 
-// out[i] = group of ids[i] in the table of `owner` (locked by the caller); the scratch is owner's too.
-void get_groups(pcv_searcher* owner, const int64_t* ids, int64_t n, int64_t* out) {
-    pcv_searcher::Groups& t = owner->groups;
+// out[i] = what table `t` of `owner` (locked by the caller) holds for ids[i]; the scratch is owner's too.
+void get_table(pcv_searcher* owner, pcv_searcher::IdTable& t, const int64_t* ids, int64_t n, int64_t* out) {
     if (!t.d_head.p) {  // nothing was ever set
-        for (int64_t i = 0; i < n; ++i) out[i] = PCV_NO_GROUP;
+        for (int64_t i = 0; i < n; ++i) out[i] = t.none;
         return;
     }
     PCV_HIP(hipSetDevice(owner->ctx->device));
     hipStream_t st = owner->ctx->stream;
-    auto trim = at_exit([&] { trim_group_scratch(owner); });
+    auto trim = at_exit([&] { trim_table_scratch(t); });
     const size_t m_most = (size_t)std::min<int64_t>(n, kGroupBatch);
     t.d_batch.ensure(2 * m_most);
     for (int64_t i0 = 0; i0 < n; i0 += kGroupBatch) {
         const size_t m = (size_t)std::min<int64_t>(kGroupBatch, n - i0);
         PCV_HIP(hipMemcpyAsync(t.d_batch.p, ids + i0, m * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        launch_group_lookup(st, t.keys, t.vals, (uint32_t)(t.slots ? t.slots - 1 : 0), t.d_head.p, t.d_batch.p, (uint32_t)m, t.d_batch.p + m_most);
+        launch_group_lookup(st, t.keys, t.vals, (uint32_t)(t.slots ? t.slots - 1 : 0), t.d_head.p, t.d_batch.p, (uint32_t)m, t.d_batch.p + m_most,
+                            t.none);
         PCV_HIP(hipMemcpyAsync(out + i0, t.d_batch.p + m_most, m * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         PCV_HIP(hipStreamSynchronize(st));
     }
 }
 
+// ---- grouped results (pcv_searcher_search_grouped; DESIGN.md §4 "Grouped results") ----
 // search_distinct's walk (walk_ranked_lists) with membership as the relation: after each pass grouped_select_kernel looks the
 // hits' ids up in the group table of `owner` (s itself, or the parent of a view; locked by the caller), keeps the first row of
 // every group not kept yet and counts the others for the kept row of their group.  The state block is the one search_distinct
@@ -600,6 +598,82 @@ void search_grouped(const RankedCall& c, const pcv_searcher* owner, int64_t* out
     collapse_ranked(c, plan, v, DistinctLayout::total, [&] {
         launch_grouped_select(s->ctx->stream, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
     }, extra);
+}
+
+// ---- filtered search (pcv_searcher_search_where / _count_where; DESIGN.md §4 "Item values and filtered search") ----
+ValueTable value_table_of(const pcv_searcher* owner) {
+    const pcv_searcher::IdTable& t = owner->values;
+    return ValueTable{t.slots ? t.keys : nullptr, t.vals, t.slots ? (uint32_t)(t.slots - 1) : 0u, t.head.side_val};
+}
+
+// The third client of the ranked-call frame: the walk of search_grouped with the predicate as the test.  After each pass
+// where_select_kernel looks the hits' ids up in the value table of `owner` and keeps the hits that pass; the state block is
+// DistinctLayout's, with the kept rows' values where search_grouped has their group keys (and no counters: nothing is collapsed).
+void search_where(const RankedCall& c, const pcv_searcher* owner, const WherePred& w, int64_t* out_values) {
+    pcv_searcher* s = c.s;
+    DistinctViews v;  // (as in search_distinct)
+    auto extra = [&](size_t at, const size_t* i) {
+        if (out_values) out_values[at] = i ? v.pin.group[*i] : kNoValue;
+    };
+    SearchPlan plan;
+    if (!open_ranked(c, "search_where", plan, 0, extra)) return;
+    v = distinct_views(s);
+    WhereArgs args{};
+    args.rec = v.dev.rec;
+    args.rec_host = v.pin.rec;
+    args.kept = v.dev.kept;
+    args.kept_value = v.dev.group;
+    args.table = value_table_of(owner);
+    args.where = w;
+    args.num_results = c.k;
+    collapse_ranked(c, plan, v, DistinctLayout::total, [&] {
+        launch_where_select(s->ctx->stream, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
+    }, extra);
+}
+
+// The exact count: where_mark_kernel over every selected segment (the scratch of one segment at a time: launches of one stream
+// follow each other), the tile counts summed on the device into two int64, which come down once.
+void count_where(pcv_searcher* s, const pcv_searcher* owner, const int64_t* source_ids, int n_sources, const WherePred& w,
+                 int64_t* out_rows, int64_t* out_searchable) {
+    PCV_REQUIRE(!s->dirty, "count_where: rows were added or cleared without pcv_searcher_finalize");
+    int64_t got[2] = {0, 0};
+    const std::vector<SelSeg> segs = select_segments(s, source_ids, n_sources);
+    if (!segs.empty()) {
+        PCV_HIP(hipSetDevice(s->ctx->device));
+        hipStream_t st = s->ctx->stream;
+        uint32_t most = 0;
+        for (const SelSeg& g : segs) most = std::max(most, view_tiles(g.g->nrows));
+        // (the call's scratch is the searcher's, kept for the next call unless it is large)
+        DevBuf<uint32_t>&flags4 = s->d_where_flags, &tiles = s->d_where_tiles;
+        DevBuf<int64_t>& acc = s->d_where_acc;
+        PinBuf<int64_t>& pin_acc = s->pin_where_acc;
+        const auto trim = at_exit([&] {
+            if (flags4.n * sizeof(uint32_t) > kGroupKeptBytes) flags4.release();
+        });
+        flags4.ensure((size_t)most * 256);
+        tiles.ensure((size_t)most * 2);
+        acc.ensure(2);
+        pin_acc.ensure(2);
+        const ValueTable t = value_table_of(owner);
+        try {
+            PCV_HIP(hipMemsetAsync(acc.p, 0, 2 * sizeof(int64_t), st));
+            for (const SelSeg& g : segs) {
+                const uint32_t nt = view_tiles(g.g->nrows);
+                launch_where_mark(st, g.g->ids, g.g->id0, g.g->scale, g.g->nrows, t, w, flags4.p, tiles.p, tiles.p + most);
+                launch_where_sum(st, tiles.p, tiles.p + most, nt, acc.p);
+            }
+            PCV_HIP(hipMemcpyAsync(pin_acc.p, acc.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            PCV_HIP(hipStreamSynchronize(st));
+            PCV_HIP(hipGetLastError());
+        } catch (...) {
+            (void)hipStreamSynchronize(st);  // (the scratch may be released)
+            throw;
+        }
+        got[0] = pin_acc.p[0];
+        got[1] = pin_acc.p[1];
+    }
+    if (out_rows) *out_rows = got[0];
+    if (out_searchable) *out_searchable = got[1];
 }
 
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.

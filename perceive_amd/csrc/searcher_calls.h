@@ -1,5 +1,5 @@
-// searcher_calls.h — the search calls behind the C entry points (searcher_calls.cpp): plain, range, distinct, grouped and diverse
-// search, the group table, the begin half of the sharded protocol and search by example.  The entry point has checked its
+// searcher_calls.h — the search calls behind the C entry points (searcher_calls.cpp): plain, range, distinct, grouped, diverse and
+// filtered search, the id-keyed tables (groups, values), the begin half of the sharded protocol and search by example.  The entry point has checked its
 // arguments, holds s->mu, has seen that no pass is pending and has brought a view up to date (sync_view).
 #pragma once
 #include "searcher_pass.h"
@@ -34,9 +34,17 @@ void search_diverse(const RankedCall& c, float lambda, double* out_marginal, int
 // `owner`: whose group table is read (s itself, or the parent of a view, locked by the caller around the whole call)
 void search_grouped(const RankedCall& c, const pcv_searcher* owner, int64_t* out_groups, int32_t* out_collapsed);
 
-void set_groups(pcv_searcher* s, const int64_t* ids, const int64_t* groups, int64_t n);
-void clear_groups(pcv_searcher* s);
-void get_groups(pcv_searcher* owner, const int64_t* ids, int64_t n, int64_t* out);
+// The id-keyed tables of a searcher (searcher_internal.h, IdTable: s->groups, s->values); `who` names the entry point in messages.
+void set_table(pcv_searcher* s, pcv_searcher::IdTable& t, const char* who, const int64_t* ids, const int64_t* vals, int64_t n);
+void clear_table(pcv_searcher* s, pcv_searcher::IdTable& t);
+void get_table(pcv_searcher* owner, pcv_searcher::IdTable& t, const int64_t* ids, int64_t n, int64_t* out);
+
+// Filtered search (DESIGN.md §4 "Item values and filtered search").  `owner`: whose value table is read, as in search_grouped.
+ValueTable value_table_of(const pcv_searcher* owner);
+void search_where(const RankedCall& c, const pcv_searcher* owner, const WherePred& w, int64_t* out_values);
+// rows of the selected sources of `s` that pass / those of them a search could return (s->mu and owner's lock held)
+void count_where(pcv_searcher* s, const pcv_searcher* owner, const int64_t* source_ids, int n_sources, const WherePred& w,
+                 int64_t* out_rows, int64_t* out_searchable);
 
 int64_t check_like_args(const pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets, int n_queries,
                         const char* who);

@@ -231,21 +231,32 @@ struct pcv_searcher {
     pcv::PinBuf<uint8_t> pin_diverse;
     pcv::DevBuf<pcv::pcv_hit_dev> d_diverse_entries;
     pcv::DevBuf<float4> d_diverse_rows;
-    // the group table (pcv_searcher_set_groups; corpus.h "the group table"): keys | vals on the device, the head block beside them
-    // and the host's copy of it as of the last set_groups (every one ends with a synchronised download).  A view has none: it
-    // reads its parent's.  The scratch of a set_groups / get_groups call is kept for the next unless it is large.
-    struct Groups {
+    // the id-keyed tables (corpus.h "the id-keyed tables"): keys | vals on the device, the head block beside them and the host's
+    // copy of it as of the last upsert (every one ends with a synchronised download).  One type, two instances: the group table
+    // (pcv_searcher_set_groups; none = kNoGroup) and the value table (pcv_searcher_set_values; none = kNoValue).  A view has
+    // neither: it reads its parent's.  The scratch of a set / get call is kept for the next unless it is large.
+    struct IdTable {
+        const int64_t none;      // the value that means "an entry and nothing else"
+        const char* const what;  // "group" / "value": for messages
         int64_t* keys = nullptr;
         int64_t* vals = nullptr;
         uint64_t slots = 0;
-        pcv::GroupHead head{0, 0, -1, 0, 0};
+        pcv::GroupHead head;
         pcv::DevBuf<pcv::GroupHead> d_head;
         pcv::PinBuf<pcv::GroupHead> pin_head;
         int32_t rehashes = 0;
         float last_set_ms = 0.0f;
         pcv::DevBuf<uint32_t> d_claim, d_slot;
         pcv::DevBuf<int64_t> d_batch;
-    } groups;
+        IdTable(int64_t none_, const char* what_) : none(none_), what(what_), head{0, 0, none_, 0, 0} {}
+    };
+    IdTable groups{pcv::kNoGroup, "group"};
+    IdTable values{pcv::kNoValue, "value"};
+    // pcv_searcher_count_where: flags and tile counts of one segment, the two sums on the device and in pinned memory
+    pcv::DevBuf<uint32_t> d_where_flags, d_where_tiles;
+    pcv::DevBuf<int64_t> d_where_acc;
+    pcv::PinBuf<int64_t> pin_where_acc;
+    uint64_t values_gen = 0;  // counts the calls that changed the value table (what predicate views watch beside `gen`)
     pcv_duplicate_stats dup_stats{};  // pcv_searcher_find_duplicates (its buffers live for the call only)
     pcv_assign_stats assign_stats{};  // pcv_searcher_assign / _kmeans (likewise)
     pcv_assign_top_stats assign_top_stats{};  // pcv_searcher_assign_top (likewise)
@@ -335,13 +346,16 @@ struct pcv_searcher {
         uint32_t cap = 0;       // ... and the length its lists had
     } pending;
     // views (pcv_searcher_create_view; DESIGN.md §3 "Views").  As a parent: `gen` counts the calls that may have changed a search
-    // result, `live_views` the views that read its rows.  As a view: the parent, the allow list (ascending, distinct), the
-    // parent's `gen` the rows were copied at, and each row's parent position (d_ppos[view position]).
+    // result, `live_views` the views that read its rows.  As a view: the parent, the allow list (ascending, distinct) or — a
+    // predicate view, pcv_searcher_create_view_where — the predicate in its place, the parent's `gen` (and, a predicate view, its
+    // `values_gen`) the rows were copied at, and each row's parent position (d_ppos[view position]).
     uint64_t gen = 0;
     std::atomic<int> live_views{0};
     pcv_searcher* view_parent = nullptr;
     std::vector<int64_t> view_ids;
-    uint64_t view_gen = 0;
+    bool view_by_value = false;
+    pcv::WherePred view_where{0, 0, 0};
+    uint64_t view_gen = 0, view_values_gen = 0;
     int32_t view_refreshes = 0;
     float view_build_ms = 0.0f;
     int64_t view_rows = 0;

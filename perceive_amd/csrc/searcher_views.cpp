@@ -1,6 +1,6 @@
 // searcher_views.cpp — views (pcv_searcher_create_view; DESIGN.md §3 "Views"): the copy of the allowed rows of a parent and
 // its refresh.  build_view is called with the parent's lock held, sync_view with the view's own (it takes the parent's).
-#include "searcher_pass.h"
+#include "searcher_calls.h"
 
 namespace pcv {
 namespace {
@@ -40,7 +40,8 @@ Segment alloc_view_segment(pcv_searcher* v, int64_t rows) {
 
 }  // namespace
 
-// (Re)build view v from its parent p (p->mu held): per parent source, the rows whose id is in the allow list become ONE view
+// (Re)build view v from its parent p (p->mu held): per parent source, the rows whose id is in the allow list (a predicate view:
+// whose id's value passes the predicate) become ONE view
 // segment, in parent source order and row order — so a view position grows with the parent position it stands for —, copied
 // with their scales (a hidden or unsearchable row keeps scale 0).  Then the screening copies the parent holds, and a mid copy if
 // the parent's mode is ON, are made from the view's own blocks: an int8 block scale depends on which rows share the block.  All
@@ -76,13 +77,30 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
     const auto give_back = at_exit([v] { v->d_idtab.release(); });
     int64_t rows = 0;
     try {
-        // 1. which rows: an id column is matched on the device (order-keeping selection), implicit ids (id0 + row) on the host
+        // 1. which rows.  An id-list view: an id column is matched on the device (order-keeping selection), implicit ids (id0 + row)
+        // on the host.  A predicate view: every segment alike on the device — where_mark_kernel tests the value of each row's id
+        // against the predicate (the parent's value table; p->mu is held), the scan and the compaction follow as for an id column.
+        const ValueTable vt = value_table_of(p);
         for (const auto& src : p->sources) {
             SrcPlan sp{src.id, {}, 0};
             for (const auto& g : src.segs) {
-                if (g.nrows == 0 || v->view_ids.empty()) continue;
+                if (g.nrows == 0 || (!v->view_by_value && v->view_ids.empty())) continue;
                 Part pt{&g, {}, 0};
-                if (!g.ids) {
+                if (v->view_by_value) {
+                    const uint32_t nt = view_tiles(g.nrows);
+                    flags4.ensure((size_t)nt * 256);
+                    tiles.ensure((size_t)nt * 2);
+                    total.ensure(1);
+                    launch_where_mark(st, g.ids, g.id0, g.scale, g.nrows, vt, v->view_where, flags4.p, tiles.p, tiles.p + nt);
+                    launch_view_scan(st, tiles.p, nt, total.p);
+                    PCV_HIP(hipMemcpyAsync(&pt.n, total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                    PCV_HIP(hipStreamSynchronize(st));
+                    if (pt.n) {
+                        pt.sel.ensure(pt.n);
+                        launch_view_compact(st, flags4.p, tiles.p, g.nrows, pt.sel.p);
+                        PCV_HIP(hipStreamSynchronize(st));  // (flags4 / tiles are the next segment's)
+                    }
+                } else if (!g.ids) {
                     const auto in = implicit_range(v->view_ids, g, 0, g.nrows);
                     std::vector<uint32_t> sel;
                     for (size_t i = in.first; i < in.second; ++i) sel.push_back((uint32_t)(v->view_ids[i] - g.id0));
@@ -155,6 +173,7 @@ void build_view(pcv_searcher* v, pcv_searcher* p) {
     v->view_build_ms = ms;
     v->view_rows = rows;
     v->view_gen = p->gen;
+    v->view_values_gen = p->values_gen;
 }
 
 // Every call on a view starts here (v->mu held): if its parent changed since the rows were copied, they are copied again, under
@@ -163,7 +182,8 @@ void sync_view(pcv_searcher* v) {
     if (!v->view_parent) return;
     pcv_searcher* p = v->view_parent;
     std::lock_guard<std::mutex> lk(p->mu);
-    if (v->view_gen == p->gen) return;
+    // (an id-list view never looks at the value table: set_values leaves it as it is)
+    if (v->view_gen == p->gen && (!v->view_by_value || v->view_values_gen == p->values_gen)) return;
     build_view(v, p);
     v->view_refreshes += 1;
 }

@@ -16,6 +16,9 @@ PCV_MAX_DISTINCT_POOL = 4096  # include/perceive_hip.h
 PCV_MAX_DIVERSE_POOL = 4096  # include/perceive_hip.h
 PCV_MAX_GROUPED_POOL = 4096  # include/perceive_hip.h
 PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_of / search_grouped
+PCV_MAX_WHERE_POOL = 4096  # include/perceive_hip.h
+PCV_NO_VALUE = -(1 << 63)  # include/perceive_hip.h: "no value" in set_values / values_of / search_where
+WHERE_UNSET_PASSES, WHERE_OUTSIDE = 1, 2  # include/perceive_hip.h: PCV_WHERE_*, the flags of a predicate
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
 GROUPS_SKIP_OWN, GROUPS_ONE_PER_GROUP = 1, 2  # include/perceive_hip.h: PCV_GROUPS_*, the flags of the grouped pair calls
@@ -544,6 +547,98 @@ class Searcher:
         if not found[0]:
             raise KeyError("Item not found")
         return self.search_grouped_vector(sources, num_results, vec[0], pool)
+
+    # ---- item values and filtered search (pcv_searcher_set_values / _count_where / _search_where / _create_view_where) ----
+    # A stored int64 per item and exact search under a range predicate on it: "the best matches among the items modified since ...".
+    def set_values(self, ids, values):
+        """Upsert of the value table: item ids[i] has value values[i] (any int64; PCV_NO_VALUE unsets the id).  Of an id that occurs
+        more than once the last occurrence holds.  Keyed by id: entries survive remove_items, clear_source and replace_source.  A
+        view is read-only (PcvError): set the values on its parent."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
+        values = np.ascontiguousarray(values, dtype=np.int64).ravel()
+        if ids.shape != values.shape:
+            raise ValueError("ids and values must have the same length")
+        _ffi.check(_ffi.lib().pcv_searcher_set_values(self._handle, _ffi.i64p(ids), _ffi.i64p(values), ids.shape[0]))
+
+    def clear_values(self):
+        """Forget every value: the table is released and its counters start from 0."""
+        _ffi.check(_ffi.lib().pcv_searcher_clear_values(self._handle))
+
+    def values_of(self, ids):
+        """ids [n] -> values [n] int64, PCV_NO_VALUE for an id without a value (a view answers from its parent's table)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).ravel()
+        out = np.full(ids.shape[0], PCV_NO_VALUE, dtype=np.int64)
+        _ffi.check(_ffi.lib().pcv_searcher_get_values(self._handle, _ffi.i64p(ids), ids.shape[0], _ffi.i64p(out)))
+        return out
+
+    def value_stats(self):
+        """{"ids": ids with a value, "entries": occupied slots, "slots": capacity, "rehashes": growths, "last_set_ms": device time of
+        the last set_values} (pcv_value_stats)."""
+        st = _ffi.ValueStats()
+        _ffi.check(_ffi.lib().pcv_searcher_value_stats(self._handle, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in _ffi.ValueStats._fields_}
+
+    @staticmethod
+    def _where_flags(unset_passes, outside):
+        return (WHERE_UNSET_PASSES if unset_passes else 0) | (WHERE_OUTSIDE if outside else 0)
+
+    def count_where(self, sources, lo, hi, unset_passes=False, outside=False):
+        """-> (rows, searchable): the rows of `sources` whose id has a value in [lo, hi] (`outside`: a value not in it; `unset_passes`:
+        rows whose id has no value count too), and those of them a search could return (hidden rows left out).  Exact."""
+        rows, live = C.c_int64(), C.c_int64()
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(_ffi.lib().pcv_searcher_count_where(self._handle, src, nsrc, int(lo), int(hi), self._where_flags(unset_passes, outside),
+                                                       C.byref(rows), C.byref(live)))
+        return rows.value, live.value
+
+    def search_where(self, sources, num_results, vectors, lo, hi, unset_passes=False, outside=False, pool=None):
+        """The ranked list of search_vectors walked best first, a row kept iff the value of its id passes the predicate (count_where);
+        at most `pool` entries are examined (default min(PCV_MAX_WHERE_POOL, max(128, 8 * num_results))).  vectors [B, dim] ->
+        (ids [B, k] int64, scores [B, k] f32, values [B, k] int64: PCV_NO_VALUE for an unset row that passed, counts [B] int32,
+        examined [B] int32, more [B] bool: the walk stopped at `pool` short of num_results although the list had more rows).  Ids
+        and scores are those search_vectors returns for the same rows.  For a predicate few rows pass, use view_where."""
+        q = np.ascontiguousarray(vectors, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [B, {self.dim}]")
+        B, k = q.shape[0], int(num_results)
+        if pool is None:
+            pool = min(PCV_MAX_WHERE_POOL, max(128, 8 * k))
+        ids = np.full((B, max(k, 0)), -1, dtype=np.int64)
+        scores = np.full((B, max(k, 0)), np.nan, dtype=np.float32)
+        values = np.full((B, max(k, 0)), PCV_NO_VALUE, dtype=np.int64)
+        counts = np.zeros(max(B, 1), dtype=np.int32)
+        examined = np.zeros(max(B, 1), dtype=np.int32)
+        more = np.zeros(max(B, 1), dtype=np.uint8)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_where(
+                self._handle, _ffi.f32p(q), B, src, nsrc, k, int(pool), int(lo), int(hi), self._where_flags(unset_passes, outside),
+                _ffi.i64p(ids), _ffi.f32p(scores), _ffi.i64p(values), _ffi.i32p(counts), _ffi.i32p(examined), _ffi.u8p(more),
+            )
+        )
+        return ids, scores, values, counts[:B], examined[:B], more[:B].astype(bool)
+
+    def search_where_vector(self, sources, num_results, vector, lo, hi, unset_passes=False, outside=False, pool=None):
+        """search_where for one vector -> list[(SearchItem, value)]: the best passing rows."""
+        ids, scores, values, counts, _ex, _more = self.search_where(
+            sources, num_results, np.asarray(vector, dtype=np.float32)[None, :], lo, hi, unset_passes, outside, pool)
+        return [(SearchItem(int(ids[0, j]), float(scores[0, j])), int(values[0, j])) for j in range(int(counts[0]))]
+
+    def search_where_like_item(self, sources, num_results, item_id, lo, hi, unset_passes=False, outside=False, pool=None):
+        """The passing rows closest to the stored embedding of `item_id` (like_queries + search_where); the item itself comes first if
+        it passes.  KeyError("Item not found") when no row carries the id."""
+        vec, found, _members = self.like_queries([[int(item_id)]])
+        if not found[0]:
+            raise KeyError("Item not found")
+        return self.search_where_vector(sources, num_results, vec[0], lo, hi, unset_passes, outside, pool)
+
+    def view_where(self, lo, hi, unset_passes=False, outside=False):
+        """A read-only searcher over the rows whose id passes the predicate (count_where): a view like view(item_ids) without an id
+        list — the rows are selected on the device from the value table, and the view follows every later change of this searcher
+        and of its values."""
+        h = C.c_void_p()
+        _ffi.check(_ffi.lib().pcv_searcher_create_view_where(self._handle, int(lo), int(hi), self._where_flags(unset_passes, outside), C.byref(h)))
+        return SearcherView(self, h)
 
     # ---- duplicate pairs (pcv_searcher_find_duplicates) ----------------------------------------------
     # The exact self-join of the corpus: what search_distinct collapses per query, found once for remove_items / hide_items.
@@ -1267,6 +1362,9 @@ class SearcherView(Searcher):
         return {"rows": rows.value, "ids": ids.value, "refreshes": ref.value, "build_ms": ms.value}
 
     def view(self, item_ids):
+        raise _ffi.PcvError(1, "a view cannot be the parent of a view")
+
+    def view_where(self, lo, hi, unset_passes=False, outside=False):
         raise _ffi.PcvError(1, "a view cannot be the parent of a view")
 
     def close(self):

@@ -45,6 +45,16 @@ pub struct pcv_group_stats {
 
 #[repr(C)]
 #[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_value_stats {
+    pub ids: i64,
+    pub entries: i64,
+    pub slots: i64,
+    pub rehashes: i32,
+    pub last_set_ms: f32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
 pub struct pcv_duplicate_stats {
     pub rows: i64,
     pub candidates: i64,
@@ -312,6 +322,9 @@ pub const PCV_MAX_RESULTS: c_int = 128;
 pub const PCV_MAX_RANGE_ROWS: c_int = 16777216;
 pub const PCV_MAX_DISTINCT_POOL: c_int = 4096;
 pub const PCV_MAX_GROUPED_POOL: c_int = 4096;
+pub const PCV_WHERE_UNSET_PASSES: c_int = 1;
+pub const PCV_WHERE_OUTSIDE: c_int = 2;
+pub const PCV_MAX_WHERE_POOL: c_int = 4096;
 pub const PCV_MAX_DIVERSE_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
@@ -344,6 +357,7 @@ pub const PCV_TENSOR_BF16: c_int = 2;
 pub const PCV_TENSOR_F64: c_int = 3;
 pub const PCV_TENSOR_OTHER: c_int = 4;
 pub const PCV_STAGING_SOURCE: i64 = i64::MIN;
+pub const PCV_NO_VALUE: i64 = i64::MIN;
 pub const PCV_NO_GROUP: i64 = -1;
 
 pub type pcv_tensor_visitor = Option<unsafe extern "C" fn(user: *mut c_void, name: *const c_char, shape: *const i64, rank: c_int, dtype: c_int, values: *const f32, numel: i64) -> c_int>;
@@ -405,6 +419,13 @@ extern "C" {
     pub fn pcv_searcher_get_groups(s: *mut pcv_searcher, ids: *const i64, n: i64, out_groups: *mut i64) -> c_int;
     pub fn pcv_searcher_group_stats(s: *mut pcv_searcher, out: *mut pcv_group_stats) -> c_int;
     pub fn pcv_searcher_search_grouped(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, out_ids: *mut i64, out_scores: *mut f32, out_groups: *mut i64, out_counts: *mut i32, out_collapsed: *mut i32, out_examined: *mut i32, out_more: *mut u8) -> c_int;
+    pub fn pcv_searcher_set_values(s: *mut pcv_searcher, ids: *const i64, values: *const i64, n: i64) -> c_int;
+    pub fn pcv_searcher_clear_values(s: *mut pcv_searcher) -> c_int;
+    pub fn pcv_searcher_get_values(s: *mut pcv_searcher, ids: *const i64, n: i64, out_values: *mut i64) -> c_int;
+    pub fn pcv_searcher_value_stats(s: *mut pcv_searcher, out: *mut pcv_value_stats) -> c_int;
+    pub fn pcv_searcher_count_where(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, lo: i64, hi: i64, flags: u32, out_rows: *mut i64, out_searchable: *mut i64) -> c_int;
+    pub fn pcv_searcher_search_where(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, lo: i64, hi: i64, flags: u32, out_ids: *mut i64, out_scores: *mut f32, out_values: *mut i64, out_counts: *mut i32, out_examined: *mut i32, out_more: *mut u8) -> c_int;
+    pub fn pcv_searcher_create_view_where(parent: *mut pcv_searcher, lo: i64, hi: i64, flags: u32, out_view: *mut *mut pcv_searcher) -> c_int;
     pub fn pcv_searcher_search_diverse(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, lambda: f32, pool: c_int, out_ids: *mut i64, out_scores: *mut f32, out_marginal: *mut f64, out_ranks: *mut i32, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
     pub fn pcv_searcher_find_duplicates(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, max_pairs: i64, out_id_a: *mut i64, out_id_b: *mut i64, out_scores: *mut f32, out_count: *mut i64, out_total: *mut i64) -> c_int;
     pub fn pcv_searcher_last_duplicate_stats(s: *mut pcv_searcher, out: *mut pcv_duplicate_stats) -> c_int;

@@ -500,6 +500,78 @@ impl Searcher {
         (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, groups[i], collapsed[i])).collect()
     }
 
+    /// The value table (`pcv_searcher_set_values`): item `ids[i]` has value `values[i]` — `Item::modified` as a Unix time stamp, say —
+    /// (any i64; `ffi::PCV_NO_VALUE` unsets the id); of an id that occurs more than once the last occurrence holds.  The table is
+    /// keyed by item id and lives on the device: it survives `remove_items` and a rebuilt source.
+    pub fn set_values(&mut self, ids: &[i64], values: &[i64]) {
+        assert_eq!(ids.len(), values.len(), "set_values: {} ids, {} values", ids.len(), values.len());
+        if self.handle.is_null() || ids.is_empty() {
+            return;
+        }
+        hip::check(unsafe { ffi::pcv_searcher_set_values(self.handle, ids.as_ptr(), values.as_ptr(), ids.len() as i64) })
+            .expect("set_values failed");
+    }
+
+    /// Filtered search (`pcv_searcher_search_where`): the ranked list of `search_vector` walked best first on the device, an item
+    /// kept only if its value (`set_values`) lies in `lo ..= hi` — "the best matches among the items modified since last week".
+    /// `flags`: `ffi::PCV_WHERE_UNSET_PASSES`, `ffi::PCV_WHERE_OUTSIDE` or 0.  At most `pool` entries of the list are examined
+    /// (`None`: min(PCV_MAX_WHERE_POOL, max(128, 8 * num_results))): for a predicate that few items pass use `view_where`.  Each
+    /// hit comes with its value (`ffi::PCV_NO_VALUE`: an item without one that passed).
+    pub fn search_vector_where(
+        &self,
+        sources: &[i64],
+        num_results: usize,
+        vector: Vec<f32>,
+        lo: i64,
+        hi: i64,
+        flags: u32,
+        pool: Option<usize>,
+    ) -> Vec<(SearchItem, i64)> {
+        if self.handle.is_null() || num_results == 0 {
+            return Vec::new();
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        assert_eq!(vector.len(), dim as usize, "search_vector_where: the query has {} values, the index is {}-d", vector.len(), dim);
+        let pool = pool.unwrap_or_else(|| (ffi::PCV_MAX_WHERE_POOL as usize).min((8 * num_results).max(128)));
+        let mut ids = vec![-1i64; num_results];
+        let mut scores = vec![f32::NAN; num_results];
+        let mut values = vec![ffi::PCV_NO_VALUE; num_results];
+        let mut count: i32 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_where(
+                self.handle,
+                vector.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                num_results as i32,
+                pool as i32,
+                lo,
+                hi,
+                flags,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                values.as_mut_ptr(),
+                &mut count,
+                std::ptr::null_mut(),
+                std::ptr::null_mut(),
+            )
+        })
+        .expect("search_where failed");
+        (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, values[i])).collect()
+    }
+
+    /// A search restricted to the items whose value passes a predicate (`pcv_searcher_create_view_where`): a view like `view`
+    /// without an id list — the rows are selected on the device from the value table — that also follows every later `set_values`.
+    pub fn view_where(&self, lo: i64, hi: i64, flags: u32) -> Result<SearcherView<'_>, HipError> {
+        let mut handle: *mut ffi::pcv_searcher = ptr::null_mut();
+        if !self.handle.is_null() {
+            hip::check(unsafe { ffi::pcv_searcher_create_view_where(self.handle, lo, hi, flags, &mut handle) })?;
+        }
+        Ok(SearcherView { handle, _parent: PhantomData })
+    }
+
     /// Duplicate pairs (`pcv_searcher_find_duplicates`): every pair of searchable items of `sources` whose cosine is at or above
     /// `threshold`, best first, at most `max_pairs` of them (clamped to PCV_MAX_DUPLICATE_PAIRS) — the same page under several
     /// URLs, found once for the whole index.  Returns the pairs as (id of the item stored first, id of the other, cosine) and the

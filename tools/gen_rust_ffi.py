@@ -19,6 +19,7 @@ SCALARS = {
     "pcv_comm": "pcv_comm", "pcv_hit": "pcv_hit", "pcv_scan_stats": "pcv_scan_stats", "pcv_model_desc": "pcv_model_desc",
     "pcv_encode_stats": "pcv_encode_stats", "pcv_duplicate_stats": "pcv_duplicate_stats",
     "pcv_assign_stats": "pcv_assign_stats", "pcv_assign_top_stats": "pcv_assign_top_stats", "pcv_neighbor_stats": "pcv_neighbor_stats", "pcv_group_stats": "pcv_group_stats",
+    "pcv_value_stats": "pcv_value_stats",
     "pcv_match_stats": "pcv_match_stats", "pcv_pair_group_stats": "pcv_pair_group_stats",
     "pcv_seed_stats": "pcv_seed_stats", "pcv_moment_stats": "pcv_moment_stats", "pcv_project_stats": "pcv_project_stats",
     "pcv_density_stats": "pcv_density_stats", "pcv_linkage_stats": "pcv_linkage_stats",
@@ -130,7 +131,7 @@ def main():
         lines += ["}", ""]
     for name, value in enums(text):
         lines.append(f"pub const {name}: c_int = {value};")
-    for m in re.finditer(r"#define\s+(PCV_\w+)\s+INT64_MIN\b", strip_comments(text)):
+    for m in re.finditer(r"#define\s+(PCV_\w+)\s+\(?INT64_MIN\b\)?", strip_comments(text)):
         lines.append(f"pub const {m.group(1)}: i64 = i64::MIN;")
     for m in re.finditer(r"#define\s+(PCV_\w+)\s+\((-?\d+)\)", strip_comments(text)):  # (an id or a group key: 64 bits)
         lines.append(f"pub const {m.group(1)}: i64 = {m.group(2)};")
