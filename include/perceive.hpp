@@ -258,6 +258,53 @@ inline int64_t count_where_handle(pcv_searcher* h, const std::vector<int64_t>& s
     return rows;
 }
 
+// A boost over the value of an item (Searcher::set_values): piecewise linear through (values[j], boosts[j]) — values strictly
+// increasing, at most PCV_MAX_BOOST_KNOTS knots —, constant beyond both ends, `unset` for an item without a value
+// (pcv_searcher_search_boosted).
+struct Boost {
+    std::vector<int64_t> values;
+    std::vector<double> boosts;
+    double unset = 0.0;
+    pcv_boost raw() const {
+        if (values.size() != boosts.size()) throw std::invalid_argument("Boost: values and boosts differ in length");
+        pcv_boost b{};
+        b.n_knots = (int32_t)std::min<size_t>(values.size(), (size_t)PCV_MAX_BOOST_KNOTS + 1);  // (none or too many: the library refuses)
+        for (size_t j = 0; j < values.size() && j < (size_t)PCV_MAX_BOOST_KNOTS; ++j) b.knot_values[j] = values[j], b.knot_boosts[j] = boosts[j];
+        b.unset_boost = unset;
+        return b;
+    }
+};
+// One hit of search_vector_boosted: the item, its boosted score m = relevance + boost(value), its value (PCV_NO_VALUE: none) and
+// its rank in the list search_vector returns.
+struct BoostedItem {
+    SearchItem item;
+    double boosted;
+    int64_t value;
+    int32_t rank;
+};
+// Boosted search on a searcher or a view handle (pcv_searcher_search_boosted): the top num_results under m, ties to the better
+// rank; at most `pool` entries of the ranked list are examined (0: the default, min(PCV_MAX_BOOST_POOL, max(128, 8 * num_results))).
+// `exact`, if given: the rows are provably the top num_results of the whole list.
+inline std::vector<BoostedItem> search_boosted_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results,
+                                                      const std::vector<float>& vector, const Boost& boost, size_t pool, bool* exact) {
+    if (exact) *exact = true;
+    if (sources.empty() || num_results == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    if (pool == 0) pool = std::min<size_t>(PCV_MAX_BOOST_POOL, std::max<size_t>(128, 8 * num_results));
+    const pcv_boost b = boost.raw();
+    std::vector<int64_t> ids(num_results), values(num_results);
+    std::vector<float> scores(num_results);
+    std::vector<double> boosted(num_results);
+    std::vector<int32_t> ranks(num_results);
+    int32_t count = 0;
+    uint8_t e = 0;
+    check(pcv_searcher_search_boosted(h, vector.data(), 1, sources.data(), (int)sources.size(), (int)num_results, (int)pool, &b, ids.data(),
+                                      scores.data(), boosted.data(), values.data(), ranks.data(), &count, nullptr, &e));
+    if (exact) *exact = e != 0;
+    std::vector<BoostedItem> out;
+    for (int i = 0; i < count; ++i) out.push_back({{ids[(size_t)i], scores[(size_t)i]}, boosted[(size_t)i], values[(size_t)i], ranks[(size_t)i]});
+    return out;
+}
+
 // One duplicate pair of find_duplicates: the item stored first, the other one, their cosine.
 struct DuplicatePair {
     int64_t id_a, id_b;
@@ -797,6 +844,11 @@ public:
     int64_t count_where(const std::vector<int64_t>& sources, const Where& where, int64_t* searchable = nullptr) const {
         return count_where_handle(h_, sources, where, searchable);
     }
+    // the view's best items under score plus a boost from the parent's values (search_boosted_handle)
+    std::vector<BoostedItem> search_vector_boosted(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   const Boost& boost, size_t pool = 0, bool* exact = nullptr) const {
+        return search_boosted_handle(h_, sources, num_results, vector, boost, pool, exact);
+    }
     // the duplicate pairs among the view's items (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
                                                int64_t* total = nullptr) const {
@@ -1046,6 +1098,11 @@ public:
     }
     int64_t count_where(const std::vector<int64_t>& sources, const Where& where, int64_t* searchable = nullptr) const {
         return count_where_handle(h_, sources, where, searchable);
+    }
+    // the best items under score plus a boost from their value: "the best matches, recent items a little higher" (search_boosted_handle)
+    std::vector<BoostedItem> search_vector_boosted(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
+                                                   const Boost& boost, size_t pool = 0, bool* exact = nullptr) const {
+        return search_boosted_handle(h_, sources, num_results, vector, boost, pool, exact);
     }
     // every pair of near-duplicate items, found once on the device (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,

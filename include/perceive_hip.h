@@ -605,6 +605,64 @@ pcv_status pcv_searcher_search_diverse(pcv_searcher* s, const float* queries, in
                                        double* out_marginal, int32_t* out_ranks, int32_t* out_counts, int32_t* out_examined,
                                        uint8_t* out_exact);
 
+/* Boosted results: the exact top-k under score plus a prior from the item's value ("the best matches, with recent items ranked a
+ * little higher") — the graded form of what pcv_searcher_search_where does all-or-nothing, re-ranked on the device, with a
+ * certificate that says when the answer is that of the whole list.  Per query:
+ *   L      the ranked list pcv_searcher_search returns (canonical f64 score, ties -> lower position; the searchable rows of the
+ *          selected sources: hidden rows and a view's restriction apply as everywhere).  The RANK of an entry is its index in L.
+ *   rel_i  relevance, exactly as in diverse results: cosine metric c_i; dot metric c_i / (double)dim, one f64 division.
+ *   b_i    boost(v), piecewise linear in the value v of the row's id (pcv_searcher_set_values; a view reads its parent's table):
+ *            no value                 unset_boost
+ *            v <= knot_values[0]      knot_boosts[0];      v >= knot_values[n-1]   knot_boosts[n-1]
+ *            otherwise, with knot_values[j] <= v < knot_values[j+1]:
+ *              num = (double)(uint64_t)(v - knot_values[j]), den = (double)(uint64_t)(knot_values[j+1] - knot_values[j]) — both
+ *              differences in wrapping 64-bit arithmetic, so they are exact for any pair of int64 —, t = num / den and
+ *              b = fl(knot_boosts[j] + fl(t * fl(knot_boosts[j+1] - knot_boosts[j]))): separate roundings, no fused multiply-add;
+ *              then b is clamped into [min, max] of the segment's two knot boosts (t can round to 1 and the sum land an ulp past
+ *              the knot: the clamp keeps b_max below a true bound).
+ *          A step function is two knots at v and v + 1; one knot is a constant.
+ *   m_i    the boosted score fl(rel_i + b_i).  ORDER: m descending, ties -> lower rank in L.
+ *   b_max  the maximum over all knot_boosts and unset_boost.
+ * The walk: the examined prefix of L grows in steps of PCV_MAX_RESULTS entries (the last step shorter, so that the prefix never
+ * exceeds `pool`).  After each step the KEPT rows are the first min(num_results, examined) entries of the prefix in the order above,
+ * and the walk ends at the first step where one of these holds:
+ *   (a) the list delivered fewer entries than the step asked for — it ended: exact = 1;
+ *   (b) num_results rows are kept and m_k >= fl(rel_last + b_max), m_k the last kept row's m and rel_last the relevance of the last
+ *       examined entry: exact = 1.  A row outside the prefix has rel <= rel_last and b <= b_max, rounding is monotone, so its m is
+ *       at most the bound; it also has a higher rank than every examined row, so it loses a tie: >= suffices;
+ *   (c) examined == pool: exact = 0.  Where |L| == pool exactly and (b) fails the flag is 0, as in diverse results.
+ * A 1 is a proof, a 0 is no disproof.
+ *   pool          num_results .. PCV_MAX_BOOST_POOL: entries of L the walk may examine
+ *   boost         n_knots in 1 .. PCV_MAX_BOOST_KNOTS; knot_values strictly increasing, none PCV_NO_VALUE; every boost finite
+ *   out_ids       [n_queries][num_results] the kept rows, best first, -1 behind them
+ *   out_scores    likewise, NaN behind (may be NULL): the plain f32 score, bit for bit what pcv_searcher_search reports for the row
+ *   out_boosted   [n_queries][num_results] f64: m of each kept row, NaN behind (may be NULL)
+ *   out_values    [n_queries][num_results] the value of each kept row, PCV_NO_VALUE for an unset row and behind (may be NULL)
+ *   out_ranks     [n_queries][num_results] rank of each kept row in L, -1 behind (may be NULL)
+ *   out_counts    [n_queries] rows kept
+ *   out_examined  [n_queries] entries of L examined (may be NULL)
+ *   out_exact     [n_queries] the certificate (may be NULL)
+ * A NULL searcher, no queries, num_results outside [1, PCV_MAX_RESULTS], pool outside [num_results, PCV_MAX_BOOST_POOL], a NULL
+ * boost, n_knots outside [1, PCV_MAX_BOOST_KNOTS], knot values not strictly increasing or equal to PCV_NO_VALUE, or a boost that is
+ * not finite give PCV_ERR_INVALID before any device work; a searcher with pending rows fails as in pcv_searcher_search.  An empty
+ * value table is legal: every row then gets unset_boost, and the result is the plain top-k.  No selected rows give the blank answer
+ * with exact = 1.  A call makes at most ceil(pool / PCV_MAX_RESULTS) passes per group of queries, each followed by a select step on
+ * the device whose cost is fixed (DESIGN.md §4 "Boosted results"); there is no extra pass.  Works on views.
+ * Not in scope: a sharded form, device-resident output, a predicate combined with the boost, boosts from the group table, float
+ * values. */
+enum { PCV_MAX_BOOST_KNOTS = 16, PCV_MAX_BOOST_POOL = 4096 };
+struct pcv_boost {
+    int32_t n_knots;                          /* 1 .. PCV_MAX_BOOST_KNOTS */
+    int64_t knot_values[PCV_MAX_BOOST_KNOTS]; /* strictly increasing; none is PCV_NO_VALUE */
+    double knot_boosts[PCV_MAX_BOOST_KNOTS];  /* finite */
+    double unset_boost;                       /* finite: the boost of an item without a value */
+};
+typedef struct pcv_boost pcv_boost;
+pcv_status pcv_searcher_search_boosted(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                       int num_results, int pool, const pcv_boost* boost, int64_t* out_ids, float* out_scores,
+                                       double* out_boosted, int64_t* out_values, int32_t* out_ranks, int32_t* out_counts,
+                                       int32_t* out_examined, uint8_t* out_exact);
+
 /* Duplicate pairs: the exact self-join of the corpus on the device — every pair of searchable rows that are near-duplicates of each
  * other, found once and corpus-wide (what pcv_searcher_search_distinct collapses per query, for pcv_searcher_remove_ids /
  * pcv_searcher_hide_ids to act on).

@@ -10,6 +10,8 @@ from .search import (  # noqa: F401
     PCV_DENSITY_CORE,
     PCV_DENSITY_NOISE,
     PCV_DENSITY_NONE,
+    PCV_MAX_BOOST_KNOTS,
+    PCV_MAX_BOOST_POOL,
     PCV_NO_VALUE,
     SearchItem,
     Searcher,
@@ -25,6 +27,7 @@ from .search import (  # noqa: F401
     linkage_cut,
     linkage_select,
     merge_topk,
+    recency_boost,
     seed_draw,
     serialize_embedding,
     symmetric_eigen,

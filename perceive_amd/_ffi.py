@@ -221,6 +221,16 @@ class ValueStats(C.Structure):
     ]
 
 
+class Boost(C.Structure):
+    """pcv_boost: the piecewise-linear boost of pcv_searcher_search_boosted (PCV_MAX_BOOST_KNOTS = 16 knots at most)"""
+    _fields_ = [
+        ("n_knots", C.c_int32),
+        ("knot_values", C.c_int64 * 16),
+        ("knot_boosts", C.c_double * 16),
+        ("unset_boost", C.c_double),
+    ]
+
+
 class SeedStats(C.Structure):
     _fields_ = [
         ("rows", C.c_int64),
@@ -358,6 +368,8 @@ SYMBOLS = {
     "pcv_searcher_count_where": (C.c_int, [_P, _I64P, C.c_int, C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_search_where": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_uint32, _I64P, _F32P,
                                             _I64P, _INTP, _INTP, _U8P]),
+    "pcv_searcher_search_boosted": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, C.POINTER(Boost), _I64P, _F32P, _F64P, _I64P, _INTP,
+                                              _INTP, _INTP, _U8P]),
     "pcv_searcher_search_diverse": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int, _I64P, _F32P, _F64P, _INTP, _INTP, _INTP, _U8P]),
     "pcv_searcher_find_duplicates": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_last_duplicate_stats": (C.c_int, [_P, C.POINTER(DuplicateStats)]),

@@ -1,6 +1,7 @@
 // corpus.h — launcher interface of the kernels that build and maintain a corpus segment (corpus_kernels.hip): staging, row
 // scales, the screening and mid copies of scan.h, and hiding, updating, removing, viewing and gathering stored items by id — and of the
-// id-keyed tables (grouped_kernels.hip), which share the id hash, and the predicate kernels over the value table (where_kernels.hip).
+// id-keyed tables (grouped_kernels.hip), which share the id hash, and the predicate kernels over the value table (where_kernels.hip)
+// and the boosted select step that reads it (boost_kernels.hip).
 #pragma once
 #include "scan.h"
 
@@ -140,6 +141,23 @@ struct WhereArgs {
     int num_results;
 };
 void launch_where_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const WhereArgs& a);
+// ---- boosted results (pcv_searcher_search_boosted; boost_kernels.hip; DESIGN.md §4 "Boosted results") ----
+// The select step: the same walk and record (scan.h, DistinctRec), but every pass's hits are re-ranked with the rows kept so far
+// under m = fl(rel + boost(value)), ties -> lower rank.  kDistinctFull: the certificate holds; kDistinctEnd: the list ended.
+// The knots are read with constant indices only (by value: nothing in it is indexed at run time).
+struct BoostArgs {
+    DistinctRec* rec;        // [B]
+    DistinctRec* rec_host;   // [B] pinned host mirror, written after every pass
+    pcv_hit_dev* kept;       // [B][kMaxK] the kept rows, best first in the boosted order
+    double* kept_m;          // [B][kMaxK] their boosted scores
+    int64_t* kept_value;     // [B][kMaxK] their values (kNoValue: an unset row)
+    int32_t* kept_rank;      // [B][kMaxK] their ranks in the list
+    ValueTable table;
+    pcv_boost boost;
+    double b_max;            // max over the knot boosts and unset_boost
+    int num_results;
+};
+void launch_boost_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const BoostArgs& a);
 // rows [dst_row0, dst_row0 + n_sel) of a view segment take rows sel[0..n_sel) of a parent segment (pieces, scale, id; parent
 // position pos0 + row -> dst_ppos[row of the view segment], unless dst_ppos is nullptr); rows [dst_row0 + n_sel, dst_end) become
 // padding

@@ -104,6 +104,9 @@ __device__ __forceinline__ double finish_score(int metric, double dot, double nx
     return __builtin_nan("");
 }
 
+// relevance of a row from its canonical score (diverse and boosted results): cosine c; dot c / dim, one f64 division
+__device__ __forceinline__ double relevance(int metric, int D, double c) { return metric == PCV_METRIC_DOT ? c / (double)D : c; }
+
 // Place of 16-byte piece `pc` of query row `q` inside the row's P8 pieces of the LDS tile: XOR with the row number
 // inside groups of 16 pieces, so that the 16 lanes of a ds_read_b128 group (16 consecutive rows, one piece index) hit 16
 // distinct bank quads.  P8 is a multiple of 8 (dimension padded to 64), not always of 16: a trailing group of 8 pieces is

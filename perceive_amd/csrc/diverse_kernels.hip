@@ -82,7 +82,6 @@ __device__ __forceinline__ double outside_bound(double lambda, double mu, double
     const double y = mu * d0;
     return x + y;
 }
-__device__ __forceinline__ double relevance(int metric, int D, double c) { return metric == PCV_METRIC_DOT ? c / (double)D : c; }
 
 struct DiverseLds {
     double red_m[kDiverseWaves];

@@ -874,6 +874,37 @@ pcv_status pcv_searcher_search_where(pcv_searcher* s, const float* queries, int 
     });
 }
 
+pcv_status pcv_searcher_search_boosted(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources,
+                                       int num_results, int pool, const pcv_boost* boost, int64_t* out_ids, float* out_scores,
+                                       double* out_boosted, int64_t* out_values, int32_t* out_ranks, int32_t* out_counts,
+                                       int32_t* out_examined, uint8_t* out_exact) {
+    return guarded([&] {
+        check_ranked_args(s, queries, n_queries, num_results, pool, "search_boosted", (int)PCV_MAX_BOOST_POOL);
+        PCV_REQUIRE(boost != nullptr, "search_boosted: boost is NULL");
+        PCV_REQUIRE(boost->n_knots >= 1 && boost->n_knots <= (int)PCV_MAX_BOOST_KNOTS, "search_boosted: n_knots %d outside [1,%d]", boost->n_knots,
+                    (int)PCV_MAX_BOOST_KNOTS);
+        pcv_boost b{};  // (the knots in use and nothing else: what lies behind them never reaches the device)
+        b.n_knots = boost->n_knots;
+        b.unset_boost = boost->unset_boost;
+        PCV_REQUIRE(std::isfinite(b.unset_boost), "search_boosted: unset_boost is not finite");
+        for (int j = 0; j < b.n_knots; ++j) {
+            b.knot_values[j] = boost->knot_values[j];
+            b.knot_boosts[j] = boost->knot_boosts[j];
+            PCV_REQUIRE(b.knot_values[j] != PCV_NO_VALUE, "search_boosted: knot value %d is PCV_NO_VALUE", j);
+            PCV_REQUIRE(j == 0 || b.knot_values[j] > b.knot_values[j - 1], "search_boosted: knot values are not strictly increasing (knot %d)", j);
+            PCV_REQUIRE(std::isfinite(b.knot_boosts[j]), "search_boosted: knot boost %d is not finite", j);
+        }
+        std::lock_guard<std::mutex> lk(s->mu);
+        PCV_REQUIRE(!s->pending.active, "search_boosted: a pass queued by search_device_begin has not been collected");
+        sync_view(s);
+        // (a view reads its parent's table: the parent stays locked while the kernels may follow its pointers)
+        std::unique_lock<std::mutex> plk;
+        if (s->view_parent) plk = std::unique_lock<std::mutex>(s->view_parent->mu);
+        search_boosted(RankedCall{s, queries, n_queries, source_ids, n_sources, num_results, pool, out_ids, out_scores, out_counts, out_examined, out_exact},
+                       s->view_parent ? s->view_parent : s, b, out_boosted, out_values, out_ranks);
+    });
+}
+
 pcv_status pcv_searcher_like_queries(pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets,
                                      int n_queries, float* out_queries, void* d_out_queries, uint8_t* out_found,
                                      int64_t* out_member_rows) {

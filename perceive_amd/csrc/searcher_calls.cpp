@@ -631,6 +631,74 @@ void search_where(const RankedCall& c, const pcv_searcher* owner, const WherePre
     }, extra);
 }
 
+// ---- boosted results (pcv_searcher_search_boosted; DESIGN.md §4 "Boosted results") ----
+// The state block of one group of Q queries: the walk's records and, per kept row, the hit, its boosted score, its value and its
+// rank — two 8-byte columns and one 4-byte column, so a layout of its own, the same on both sides.  The columns are packed for the
+// group's own number of queries, so that what comes down at the end is one copy of what the group wrote and no more.
+namespace {
+struct BoostLayout {
+    size_t off_kept, off_m, off_value, off_rank, total;
+    explicit BoostLayout(size_t Q) {
+        off_kept = (size_t)kMfmaQueries * sizeof(DistinctRec);
+        off_m = off_kept + Q * kMaxK * sizeof(pcv_hit_dev);
+        off_value = off_m + Q * kMaxK * sizeof(double);
+        off_rank = off_value + Q * kMaxK * sizeof(int64_t);
+        total = off_rank + Q * kMaxK * sizeof(int32_t);
+    }
+};
+}  // namespace
+
+// The fourth client of the ranked-call frame: the walk of search_where with a re-ranking in place of the test.  After each pass
+// boost_select_kernel merges the pass's hits into the kept rows under m = fl(rel + boost(value)) and tests the certificate; a query
+// is finished when the certificate holds or its list ended, and what stops at `pool` unfinished is not exact.  There is no "more"
+// pass: the last column is the record's flag.
+void search_boosted(const RankedCall& c, const pcv_searcher* owner, const pcv_boost& boost, double* out_boosted, int64_t* out_values,
+                    int32_t* out_ranks) {
+    pcv_searcher* s = c.s;
+    const pcv_hit_dev* r_kept = nullptr;  // (of the pinned block, once the call has rows to search)
+    const double* r_m = nullptr;
+    const int64_t* r_value = nullptr;
+    const int32_t* r_rank = nullptr;
+    auto extra = [&](size_t at, const size_t* i) {
+        if (out_boosted) out_boosted[at] = i ? r_m[*i] : NAN;
+        if (out_values) out_values[at] = i ? r_value[*i] : kNoValue;
+        if (out_ranks) out_ranks[at] = i ? r_rank[*i] : -1;
+    };
+    SearchPlan plan;
+    if (!open_ranked(c, "search_boosted", plan, 1, extra)) return;  // (exact: the list ended before the pool did)
+    hipStream_t st = s->ctx->stream;
+    s->d_boost.ensure(BoostLayout(kMfmaQueries).total);
+    s->pin_boost.ensure(BoostLayout(kMfmaQueries).total);
+    uint8_t *dev = s->d_boost.p, *pin = s->pin_boost.p;
+    DistinctRec* rec = reinterpret_cast<DistinctRec*>(pin);
+    BoostArgs args{};
+    args.rec = reinterpret_cast<DistinctRec*>(dev);
+    args.rec_host = rec;
+    args.table = value_table_of(owner);
+    args.boost = boost;
+    args.b_max = boost.unset_boost;
+    for (int j = 0; j < boost.n_knots; ++j) args.b_max = std::max(args.b_max, boost.knot_boosts[j]);
+    args.num_results = c.k;
+    each_query_group(c, plan.qstep, [&](int q0, int B, const float* qs) {
+        const BoostLayout L((size_t)B);
+        args.kept = reinterpret_cast<pcv_hit_dev*>(dev + L.off_kept);
+        args.kept_m = reinterpret_cast<double*>(dev + L.off_m);
+        args.kept_value = reinterpret_cast<int64_t*>(dev + L.off_value);
+        args.kept_rank = reinterpret_cast<int32_t*>(dev + L.off_rank);
+        r_kept = reinterpret_cast<const pcv_hit_dev*>(pin + L.off_kept);
+        r_m = reinterpret_cast<const double*>(pin + L.off_m);
+        r_value = reinterpret_cast<const int64_t*>(pin + L.off_value);
+        r_rank = reinterpret_cast<const int32_t*>(pin + L.off_rank);
+        walk_ranked_lists(s, plan, qs, B, c.pool, rec, args.rec, false, [&] {
+            launch_boost_select(st, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
+        });
+        PCV_HIP(hipMemcpyAsync(pin + L.off_kept, dev + L.off_kept, L.total - L.off_kept, hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        for (int q = 0; q < B; ++q)
+            write_ranked(c, q0 + q, q, (int)rec[q].kept, (int32_t)rec[q].examined, rec[q].flags != 0 ? 1 : 0, [&](size_t i) { return r_kept[i]; }, extra);
+    });
+}
+
 // The exact count: where_mark_kernel over every selected segment (the scratch of one segment at a time: launches of one stream
 // follow each other), the tile counts summed on the device into two int64, which come down once.
 void count_where(pcv_searcher* s, const pcv_searcher* owner, const int64_t* source_ids, int n_sources, const WherePred& w,

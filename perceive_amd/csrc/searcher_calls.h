@@ -1,5 +1,5 @@
-// searcher_calls.h — the search calls behind the C entry points (searcher_calls.cpp): plain, range, distinct, grouped, diverse and
-// filtered search, the id-keyed tables (groups, values), the begin half of the sharded protocol and search by example.  The entry point has checked its
+// searcher_calls.h — the search calls behind the C entry points (searcher_calls.cpp): plain, range, distinct, grouped, diverse,
+// filtered and boosted search, the id-keyed tables (groups, values), the begin half of the sharded protocol and search by example.  The entry point has checked its
 // arguments, holds s->mu, has seen that no pass is pending and has brought a view up to date (sync_view).
 #pragma once
 #include "searcher_pass.h"
@@ -42,6 +42,9 @@ void get_table(pcv_searcher* owner, pcv_searcher::IdTable& t, const int64_t* ids
 // Filtered search (DESIGN.md §4 "Item values and filtered search").  `owner`: whose value table is read, as in search_grouped.
 ValueTable value_table_of(const pcv_searcher* owner);
 void search_where(const RankedCall& c, const pcv_searcher* owner, const WherePred& w, int64_t* out_values);
+// Boosted results (DESIGN.md §4 "Boosted results").  `owner` as above; c.out_last is the `exact` column.
+void search_boosted(const RankedCall& c, const pcv_searcher* owner, const pcv_boost& boost, double* out_boosted, int64_t* out_values,
+                    int32_t* out_ranks);
 // rows of the selected sources of `s` that pass / those of them a search could return (s->mu and owner's lock held)
 void count_where(pcv_searcher* s, const pcv_searcher* owner, const int64_t* source_ids, int n_sources, const WherePred& w,
                  int64_t* out_rows, int64_t* out_searchable);

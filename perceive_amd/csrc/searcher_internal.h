@@ -231,6 +231,10 @@ struct pcv_searcher {
     pcv::PinBuf<uint8_t> pin_diverse;
     pcv::DevBuf<pcv::pcv_hit_dev> d_diverse_entries;
     pcv::DevBuf<float4> d_diverse_rows;
+    // boosted results (pcv_searcher_search_boosted): records | kept hits | their boosted scores | values | ranks of one group of
+    // queries, on the device and (records after every pass, the rest once) in pinned memory
+    pcv::DevBuf<uint8_t> d_boost;
+    pcv::PinBuf<uint8_t> pin_boost;
     // the id-keyed tables (corpus.h "the id-keyed tables"): keys | vals on the device, the head block beside them and the host's
     // copy of it as of the last upsert (every one ends with a synchronised download).  One type, two instances: the group table
     // (pcv_searcher_set_groups; none = kNoGroup) and the value table (pcv_searcher_set_values; none = kNoValue).  A view has

@@ -1,5 +1,5 @@
 // value_table.h — the value of an item id and the predicate over it (corpus.h, "filtered search"; DESIGN.md §4 "Item values and
-// filtered search"): the one copy, for every kernel that tests a row against a predicate (where_mark_kernel, where_select_kernel).
+// filtered search"): the one copy, for every kernel that tests a row against a predicate (where_mark_kernel, where_select_kernel) or reads its value (boost_select_kernel).
 // The table is the id-keyed table of group_table.h with kNoValue as its `none`.  Everything here is inlined: the file defines no symbol.
 #pragma once
 #include "group_table.h"

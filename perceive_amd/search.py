@@ -19,6 +19,8 @@ PCV_NO_GROUP = -1  # include/perceive_hip.h: "no group" in set_groups / groups_o
 PCV_MAX_WHERE_POOL = 4096  # include/perceive_hip.h
 PCV_NO_VALUE = -(1 << 63)  # include/perceive_hip.h: "no value" in set_values / values_of / search_where
 WHERE_UNSET_PASSES, WHERE_OUTSIDE = 1, 2  # include/perceive_hip.h: PCV_WHERE_*, the flags of a predicate
+PCV_MAX_BOOST_KNOTS = 16  # include/perceive_hip.h: most knots of a boost (search_boosted)
+PCV_MAX_BOOST_POOL = 4096  # include/perceive_hip.h
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
 GROUPS_SKIP_OWN, GROUPS_ONE_PER_GROUP = 1, 2  # include/perceive_hip.h: PCV_GROUPS_*, the flags of the grouped pair calls
@@ -68,6 +70,26 @@ def _source_filter(sources):
     if n == 0:
         sa = np.zeros(1, dtype=np.int64)
     return _ffi.i64p(sa), n, sa
+
+
+def recency_boost(now, half_life, weight, knots=PCV_MAX_BOOST_KNOTS):
+    """Knots for search_boosted that sample weight * 2 ** -((now - v) / half_life): -> (knot_values, knot_boosts), values
+    ascending.  The last knot is at `now` (boost `weight`: newer items get no more); going back, knot i lies
+    round(half_life * (2 ** (i / 3) - 1)) before `now` (one more where that would repeat an age), so the gaps grow geometrically —
+    fine where the curve bends, 31 half-lives back with 16 knots — and items older than the first knot keep its boost.  A plain
+    function of its arguments: `now` and `half_life` are integers in the unit of the stored values."""
+    now, half_life, knots = int(now), int(half_life), int(knots)
+    if half_life < 1 or not 1 <= knots <= PCV_MAX_BOOST_KNOTS:
+        raise ValueError("half_life must be >= 1 and knots in [1, PCV_MAX_BOOST_KNOTS]")
+    ages = []
+    for i in range(knots):
+        age = int(round(half_life * (2.0 ** (i / 3.0) - 1.0)))
+        ages.append(age if not ages else max(age, ages[-1] + 1))
+    if now - ages[-1] <= PCV_NO_VALUE:
+        raise ValueError("the oldest knot falls below the smallest value")
+    values = [now - a for a in reversed(ages)]
+    boosts = [float(weight) * 2.0 ** -(a / half_life) for a in reversed(ages)]
+    return values, boosts
 
 
 class Searcher:
@@ -639,6 +661,70 @@ class Searcher:
         h = C.c_void_p()
         _ffi.check(_ffi.lib().pcv_searcher_create_view_where(self._handle, int(lo), int(hi), self._where_flags(unset_passes, outside), C.byref(h)))
         return SearcherView(self, h)
+
+    # ---- boosted results (pcv_searcher_search_boosted) -------------------------------------------------
+    # The exact top-k under score plus a prior from the item's value: "the best matches, with recent items ranked a little higher".
+    @staticmethod
+    def _boost(knot_values, knot_boosts, unset_boost):
+        kv = [int(v) for v in np.asarray(knot_values, dtype=object).ravel().tolist()]
+        kb = np.asarray(knot_boosts, dtype=np.float64).ravel()
+        if len(kv) != kb.shape[0]:
+            raise ValueError("knot_values and knot_boosts must have the same length")
+        b = _ffi.Boost()
+        b.n_knots = len(kv)  # (more than PCV_MAX_BOOST_KNOTS, or none: the library refuses the call)
+        for j in range(min(len(kv), PCV_MAX_BOOST_KNOTS)):
+            b.knot_values[j] = kv[j]
+            b.knot_boosts[j] = float(kb[j])
+        b.unset_boost = float(unset_boost)
+        return b
+
+    def search_boosted(self, sources, num_results, vectors, knot_values, knot_boosts, unset_boost=0.0, pool=None):
+        """The top num_results under m = relevance + boost(value of the item) (set_values), ties to the better rank in the list of
+        search_vectors.  boost is piecewise linear through (knot_values[j], knot_boosts[j]) — values strictly increasing, at most
+        PCV_MAX_BOOST_KNOTS —, constant beyond both ends, `unset_boost` for an item without a value.  The list is examined
+        PCV_MAX_RESULTS entries at a time until the k-th boosted score is out of reach of every row not yet seen, or `pool`
+        entries (default min(PCV_MAX_BOOST_POOL, max(128, 8 * num_results))) are examined.  vectors [B, dim] -> (ids [B, k] int64
+        best first, scores [B, k] f32: those search_vectors returns for the same rows, boosted [B, k] f64: m, values [B, k] int64:
+        PCV_NO_VALUE for an unset row, ranks [B, k] int32: each row's place in the ranked list, counts [B] int32, examined [B]
+        int32, exact [B] bool: the rows are provably the top num_results of the whole list).  The arithmetic is defined in
+        include/perceive_hip.h."""
+        q = np.ascontiguousarray(vectors, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"vectors must be [B, {self.dim}]")
+        B, k = q.shape[0], int(num_results)
+        if pool is None:
+            pool = min(PCV_MAX_BOOST_POOL, max(128, 8 * k))
+        boost = self._boost(knot_values, knot_boosts, unset_boost)
+        ids = np.full((B, max(k, 0)), -1, dtype=np.int64)
+        scores = np.full((B, max(k, 0)), np.nan, dtype=np.float32)
+        boosted = np.full((B, max(k, 0)), np.nan, dtype=np.float64)
+        values = np.full((B, max(k, 0)), PCV_NO_VALUE, dtype=np.int64)
+        ranks = np.full((B, max(k, 0)), -1, dtype=np.int32)
+        counts = np.zeros(max(B, 1), dtype=np.int32)
+        examined = np.zeros(max(B, 1), dtype=np.int32)
+        exact = np.zeros(max(B, 1), dtype=np.uint8)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_boosted(
+                self._handle, _ffi.f32p(q), B, src, nsrc, k, int(pool), C.byref(boost), _ffi.i64p(ids), _ffi.f32p(scores),
+                _ffi.f64p(boosted), _ffi.i64p(values), _ffi.i32p(ranks), _ffi.i32p(counts), _ffi.i32p(examined), _ffi.u8p(exact),
+            )
+        )
+        return ids, scores, boosted, values, ranks, counts[:B], examined[:B], exact[:B].astype(bool)
+
+    def search_boosted_vector(self, sources, num_results, vector, knot_values, knot_boosts, unset_boost=0.0, pool=None):
+        """search_boosted for one vector -> list[(SearchItem, boosted score, value)], best first."""
+        ids, scores, boosted, values, _r, counts, _ex, _exact = self.search_boosted(
+            sources, num_results, np.asarray(vector, dtype=np.float32)[None, :], knot_values, knot_boosts, unset_boost, pool)
+        return [(SearchItem(int(ids[0, j]), float(scores[0, j])), float(boosted[0, j]), int(values[0, j])) for j in range(int(counts[0]))]
+
+    def search_boosted_like_item(self, sources, num_results, item_id, knot_values, knot_boosts, unset_boost=0.0, pool=None):
+        """The boosted neighbours of the stored embedding of `item_id` (like_queries + search_boosted); under a zero boost the item
+        itself comes first.  KeyError("Item not found") when no row carries the id."""
+        vec, found, _members = self.like_queries([[int(item_id)]])
+        if not found[0]:
+            raise KeyError("Item not found")
+        return self.search_boosted_vector(sources, num_results, vec[0], knot_values, knot_boosts, unset_boost, pool)
 
     # ---- duplicate pairs (pcv_searcher_find_duplicates) ----------------------------------------------
     # The exact self-join of the corpus: what search_distinct collapses per query, found once for remove_items / hide_items.

@@ -299,6 +299,15 @@ pub struct pcv_encode_stats {
     pub seq_len: i32,
 }
 
+#[repr(C)]
+#[derive(Debug, Clone, Copy, Default)]
+pub struct pcv_boost {
+    pub n_knots: i32,
+    pub knot_values: [i64; 16],
+    pub knot_boosts: [f64; 16],
+    pub unset_boost: f64,
+}
+
 pub const PCV_OK: c_int = 0;
 pub const PCV_ERR_INVALID: c_int = 1;
 pub const PCV_ERR_DEVICE: c_int = 2;
@@ -326,6 +335,8 @@ pub const PCV_WHERE_UNSET_PASSES: c_int = 1;
 pub const PCV_WHERE_OUTSIDE: c_int = 2;
 pub const PCV_MAX_WHERE_POOL: c_int = 4096;
 pub const PCV_MAX_DIVERSE_POOL: c_int = 4096;
+pub const PCV_MAX_BOOST_KNOTS: c_int = 16;
+pub const PCV_MAX_BOOST_POOL: c_int = 4096;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
 pub const PCV_MAX_TOP_LABELS: c_int = 8;
@@ -427,6 +438,7 @@ extern "C" {
     pub fn pcv_searcher_search_where(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, lo: i64, hi: i64, flags: u32, out_ids: *mut i64, out_scores: *mut f32, out_values: *mut i64, out_counts: *mut i32, out_examined: *mut i32, out_more: *mut u8) -> c_int;
     pub fn pcv_searcher_create_view_where(parent: *mut pcv_searcher, lo: i64, hi: i64, flags: u32, out_view: *mut *mut pcv_searcher) -> c_int;
     pub fn pcv_searcher_search_diverse(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, lambda: f32, pool: c_int, out_ids: *mut i64, out_scores: *mut f32, out_marginal: *mut f64, out_ranks: *mut i32, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
+    pub fn pcv_searcher_search_boosted(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, boost: *const pcv_boost, out_ids: *mut i64, out_scores: *mut f32, out_boosted: *mut f64, out_values: *mut i64, out_ranks: *mut i32, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
     pub fn pcv_searcher_find_duplicates(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, max_pairs: i64, out_id_a: *mut i64, out_id_b: *mut i64, out_scores: *mut f32, out_count: *mut i64, out_total: *mut i64) -> c_int;
     pub fn pcv_searcher_last_duplicate_stats(s: *mut pcv_searcher, out: *mut pcv_duplicate_stats) -> c_int;
     pub fn pcv_searcher_assign(s: *mut pcv_searcher, labels: *const f32, n_labels: c_int, source_ids: *const i64, n_sources: c_int, capacity: i64, out_label: *mut i32, out_score: *mut f32, out_ids: *mut i64, out_counts: *mut i64, out_n: *mut i64) -> c_int;

@@ -562,6 +562,66 @@ impl Searcher {
         (0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, values[i])).collect()
     }
 
+    /// Boosted search (`pcv_searcher_search_boosted`): the top `num_results` under relevance plus a boost that is piecewise linear in
+    /// the item's value (`set_values`) through `knots` — (value, boost) pairs, values strictly increasing, at most
+    /// `ffi::PCV_MAX_BOOST_KNOTS` —, constant beyond both ends and `unset_boost` for an item without a value: "the best matches, with
+    /// recent items ranked a little higher".  At most `pool` entries of the ranked list are examined (`None`:
+    /// min(PCV_MAX_BOOST_POOL, max(128, 8 * num_results))).  Each hit comes with its boosted score and its value
+    /// (`ffi::PCV_NO_VALUE`: none); the flag says whether the hits are provably the top of the whole list.
+    pub fn search_vector_boosted(
+        &self,
+        sources: &[i64],
+        num_results: usize,
+        vector: Vec<f32>,
+        knots: &[(i64, f64)],
+        unset_boost: f64,
+        pool: Option<usize>,
+    ) -> (Vec<(SearchItem, f64, i64)>, bool) {
+        if self.handle.is_null() || num_results == 0 {
+            return (Vec::new(), true);
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        assert_eq!(vector.len(), dim as usize, "search_vector_boosted: the query has {} values, the index is {}-d", vector.len(), dim);
+        assert!(knots.len() <= ffi::PCV_MAX_BOOST_KNOTS as usize, "search_vector_boosted: {} knots", knots.len());
+        let mut boost = ffi::pcv_boost::default();
+        boost.n_knots = knots.len() as i32;
+        for (j, (v, b)) in knots.iter().enumerate() {
+            boost.knot_values[j] = *v;
+            boost.knot_boosts[j] = *b;
+        }
+        boost.unset_boost = unset_boost;
+        let pool = pool.unwrap_or_else(|| (ffi::PCV_MAX_BOOST_POOL as usize).min((8 * num_results).max(128)));
+        let mut ids = vec![-1i64; num_results];
+        let mut scores = vec![f32::NAN; num_results];
+        let mut boosted = vec![f64::NAN; num_results];
+        let mut values = vec![ffi::PCV_NO_VALUE; num_results];
+        let mut count: i32 = 0;
+        let mut exact: u8 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_boosted(
+                self.handle,
+                vector.as_ptr(),
+                1,
+                sources.as_ptr(),
+                sources.len() as i32,
+                num_results as i32,
+                pool as i32,
+                &boost,
+                ids.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                boosted.as_mut_ptr(),
+                values.as_mut_ptr(),
+                std::ptr::null_mut(),
+                &mut count,
+                std::ptr::null_mut(),
+                &mut exact,
+            )
+        })
+        .expect("search_boosted failed");
+        ((0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, boosted[i], values[i])).collect(), exact != 0)
+    }
+
     /// A search restricted to the items whose value passes a predicate (`pcv_searcher_create_view_where`): a view like `view`
     /// without an id list — the rows are selected on the device from the value table — that also follows every later `set_values`.
     pub fn view_where(&self, lo: i64, hi: i64, flags: u32) -> Result<SearcherView<'_>, HipError> {

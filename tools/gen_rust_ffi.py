@@ -19,7 +19,7 @@ SCALARS = {
     "pcv_comm": "pcv_comm", "pcv_hit": "pcv_hit", "pcv_scan_stats": "pcv_scan_stats", "pcv_model_desc": "pcv_model_desc",
     "pcv_encode_stats": "pcv_encode_stats", "pcv_duplicate_stats": "pcv_duplicate_stats",
     "pcv_assign_stats": "pcv_assign_stats", "pcv_assign_top_stats": "pcv_assign_top_stats", "pcv_neighbor_stats": "pcv_neighbor_stats", "pcv_group_stats": "pcv_group_stats",
-    "pcv_value_stats": "pcv_value_stats",
+    "pcv_value_stats": "pcv_value_stats", "pcv_boost": "pcv_boost",
     "pcv_match_stats": "pcv_match_stats", "pcv_pair_group_stats": "pcv_pair_group_stats",
     "pcv_seed_stats": "pcv_seed_stats", "pcv_moment_stats": "pcv_moment_stats", "pcv_project_stats": "pcv_project_stats",
     "pcv_density_stats": "pcv_density_stats", "pcv_linkage_stats": "pcv_linkage_stats",
@@ -87,6 +87,27 @@ def structs(text):
         yield m.group(1), fields
 
 
+def array_structs(text):
+    """`struct pcv_x { ... };` followed by `typedef struct pcv_x pcv_x;` — the form of a struct that has array fields, whose lengths
+    are enum constants of the header.  -> (name, [(ctype, field name, length or None)])"""
+    consts = dict(enums(text))
+    text = strip_comments(text)
+    for m in re.finditer(r"^struct (\w+) \{(.*?)\};\s*typedef struct \1 \1;", text, flags=re.S | re.M):
+        fields = []
+        for decl in m.group(2).split(";"):
+            decl = decl.strip()
+            if not decl:
+                continue
+            ctype, name = decl.split(None, 1)
+            arr = re.match(r"(\w+)\[(\w+)\]$", name.strip())
+            if arr:
+                n = arr.group(2)
+                fields.append((ctype, arr.group(1), int(n) if n.isdigit() else consts[n]))
+            else:
+                fields.append((ctype, name.strip(), None))
+        yield m.group(1), fields
+
+
 def callbacks(text):
     """`typedef int (*pcv_x)(void* user, ...);` -> (ret, name, [(ctype, pname)])"""
     text = strip_comments(text)
@@ -128,6 +149,11 @@ def main():
         lines += ["#[repr(C)]", "#[derive(Debug, Clone, Copy, Default)]", f"pub struct {name} {{"]
         for ctype, fname in fields:
             lines.append(f"    pub {fname}: {SCALARS[ctype]},")
+        lines += ["}", ""]
+    for name, fields in array_structs(text):
+        lines += ["#[repr(C)]", "#[derive(Debug, Clone, Copy, Default)]", f"pub struct {name} {{"]
+        for ctype, fname, n in fields:
+            lines.append(f"    pub {fname}: {SCALARS[ctype] if n is None else '[%s; %d]' % (SCALARS[ctype], n)},")
         lines += ["}", ""]
     for name, value in enums(text):
         lines.append(f"pub const {name}: c_int = {value};")
