@@ -305,6 +305,79 @@ inline std::vector<BoostedItem> search_boosted_handle(pcv_searcher* h, const std
     return out;
 }
 
+// A compound query (pcv_searcher_search_compound): the rows wanted under ALL or ANY of `want` (1 .. PCV_MAX_COMPOUND_PARTS vectors), less
+// a hinge penalty for resembling one of `avoid` (0 .. PCV_MAX_COMPOUND_PARTS vectors).
+struct Compound {
+    std::vector<std::vector<float>> want, avoid;
+};
+enum class CompoundMode { All = PCV_COMPOUND_ALL, Any = PCV_COMPOUND_ANY };
+// One hit of search_compound: the item's id, m = base - penalty, the score search_vector reports for it under each wanted vector,
+// and the penalty.
+struct CompoundItem {
+    int64_t id;
+    double combined;
+    std::vector<float> part_scores;
+    double penalty;
+};
+namespace detail {
+inline std::vector<CompoundItem> compound_items(size_t parts, int32_t count, const std::vector<int64_t>& ids, const std::vector<double>& combined,
+                                                const std::vector<float>& scores, const std::vector<double>& penalties) {
+    std::vector<CompoundItem> out;
+    for (int i = 0; i < count; ++i) {
+        const float* p = scores.data() + (size_t)i * PCV_MAX_COMPOUND_PARTS;
+        out.push_back({ids[(size_t)i], combined[(size_t)i], std::vector<float>(p, p + parts), penalties[(size_t)i]});
+    }
+    return out;
+}
+}  // namespace detail
+// Compound search on a searcher or a view handle: the top num_results under m, ties to the lower position; at most `pool` entries of
+// each wanted vector's ranked list are walked (0: the default, min(PCV_MAX_COMPOUND_POOL, max(128, 8 * num_results))).  `exact`, if
+// given: the rows are provably the top num_results of all rows.
+inline std::vector<CompoundItem> search_compound_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results, const Compound& c,
+                                                        CompoundMode mode, float avoid_weight, size_t pool, bool* exact) {
+    if (exact) *exact = true;
+    if (sources.empty() || num_results == 0) return {};  // `sources.contains(..)` matches nothing; room for nothing
+    if (pool == 0) pool = std::min<size_t>(PCV_MAX_COMPOUND_POOL, std::max<size_t>(128, 8 * num_results));
+    std::vector<float> want, avoid;
+    for (const auto& v : c.want) want.insert(want.end(), v.begin(), v.end());
+    for (const auto& v : c.avoid) avoid.insert(avoid.end(), v.begin(), v.end());
+    const int64_t want_off[2] = {0, (int64_t)c.want.size()}, avoid_off[2] = {0, (int64_t)c.avoid.size()};
+    std::vector<int64_t> ids(num_results);
+    std::vector<double> combined(num_results), penalties(num_results);
+    std::vector<float> scores(num_results * PCV_MAX_COMPOUND_PARTS);
+    int32_t count = 0;
+    uint8_t e = 0;
+    check(pcv_searcher_search_compound(h, sources.data(), (int)sources.size(), (int)num_results, (int)pool, (int)mode, avoid_weight, want.data(),
+                                       want_off, avoid.empty() ? nullptr : avoid.data(), avoid_off, 1, ids.data(), combined.data(), scores.data(),
+                                       penalties.data(), &count, nullptr, &e));
+    if (exact) *exact = e != 0;
+    return detail::compound_items(c.want.size(), count, ids, combined, scores, penalties);
+}
+// ... with every vector built on the device from stored items (pcv_searcher_search_compound_like): want[p] / avoid[p] are the item ids
+// whose rows are summed into part p.  exclude_examples: no row carrying a wanted example id is returned.
+inline std::vector<CompoundItem> search_compound_like_handle(pcv_searcher* h, const std::vector<int64_t>& sources, size_t num_results,
+                                                             const std::vector<std::vector<int64_t>>& want, const std::vector<std::vector<int64_t>>& avoid,
+                                                             CompoundMode mode, float avoid_weight, size_t pool, bool exclude_examples, bool* exact) {
+    if (exact) *exact = true;
+    if (sources.empty() || num_results == 0) return {};
+    if (pool == 0) pool = std::min<size_t>(PCV_MAX_COMPOUND_POOL, std::max<size_t>(128, 8 * num_results));
+    std::vector<int64_t> w_ids, w_ex{0}, a_ids, a_ex{0};
+    for (const auto& part : want) w_ids.insert(w_ids.end(), part.begin(), part.end()), w_ex.push_back((int64_t)w_ids.size());
+    for (const auto& part : avoid) a_ids.insert(a_ids.end(), part.begin(), part.end()), a_ex.push_back((int64_t)a_ids.size());
+    const int64_t want_off[2] = {0, (int64_t)want.size()}, avoid_off[2] = {0, (int64_t)avoid.size()};
+    std::vector<int64_t> ids(num_results);
+    std::vector<double> combined(num_results), penalties(num_results);
+    std::vector<float> scores(num_results * PCV_MAX_COMPOUND_PARTS);
+    int32_t count = 0;
+    uint8_t e = 0;
+    check(pcv_searcher_search_compound_like(h, sources.data(), (int)sources.size(), (int)num_results, (int)pool, (int)mode, avoid_weight,
+                                            w_ids.empty() ? nullptr : w_ids.data(), nullptr, w_ex.data(), want_off, a_ids.empty() ? nullptr : a_ids.data(),
+                                            nullptr, a_ex.data(), avoid_off, 1, exclude_examples ? 1 : 0, ids.data(), combined.data(), scores.data(),
+                                            penalties.data(), &count, nullptr, &e));
+    if (exact) *exact = e != 0;
+    return detail::compound_items(want.size(), count, ids, combined, scores, penalties);
+}
+
 // One duplicate pair of find_duplicates: the item stored first, the other one, their cosine.
 struct DuplicatePair {
     int64_t id_a, id_b;
@@ -849,6 +922,19 @@ public:
                                                    const Boost& boost, size_t pool = 0, bool* exact = nullptr) const {
         return search_boosted_handle(h_, sources, num_results, vector, boost, pool, exact);
     }
+    // the view's best items under all / any of several vectors, less a penalty for resembling others (search_compound_handle)
+    std::vector<CompoundItem> search_compound(const std::vector<int64_t>& sources, size_t num_results, const Compound& compound,
+                                              CompoundMode mode = CompoundMode::All, float avoid_weight = 1.0f, size_t pool = 0,
+                                              bool* exact = nullptr) const {
+        return search_compound_handle(h_, sources, num_results, compound, mode, avoid_weight, pool, exact);
+    }
+    std::vector<CompoundItem> search_compound_like_items(const std::vector<int64_t>& sources, size_t num_results,
+                                                         const std::vector<std::vector<int64_t>>& want,
+                                                         const std::vector<std::vector<int64_t>>& avoid = {}, CompoundMode mode = CompoundMode::All,
+                                                         float avoid_weight = 1.0f, size_t pool = 0, bool exclude_examples = true,
+                                                         bool* exact = nullptr) const {
+        return search_compound_like_handle(h_, sources, num_results, want, avoid, mode, avoid_weight, pool, exclude_examples, exact);
+    }
     // the duplicate pairs among the view's items (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,
                                                int64_t* total = nullptr) const {
@@ -1103,6 +1189,19 @@ public:
     std::vector<BoostedItem> search_vector_boosted(const std::vector<int64_t>& sources, size_t num_results, const std::vector<float>& vector,
                                                    const Boost& boost, size_t pool = 0, bool* exact = nullptr) const {
         return search_boosted_handle(h_, sources, num_results, vector, boost, pool, exact);
+    }
+    // the best items under all / any of several vectors, less a penalty for resembling others (search_compound_handle)
+    std::vector<CompoundItem> search_compound(const std::vector<int64_t>& sources, size_t num_results, const Compound& compound,
+                                              CompoundMode mode = CompoundMode::All, float avoid_weight = 1.0f, size_t pool = 0,
+                                              bool* exact = nullptr) const {
+        return search_compound_handle(h_, sources, num_results, compound, mode, avoid_weight, pool, exact);
+    }
+    std::vector<CompoundItem> search_compound_like_items(const std::vector<int64_t>& sources, size_t num_results,
+                                                         const std::vector<std::vector<int64_t>>& want,
+                                                         const std::vector<std::vector<int64_t>>& avoid = {}, CompoundMode mode = CompoundMode::All,
+                                                         float avoid_weight = 1.0f, size_t pool = 0, bool exclude_examples = true,
+                                                         bool* exact = nullptr) const {
+        return search_compound_like_handle(h_, sources, num_results, want, avoid, mode, avoid_weight, pool, exclude_examples, exact);
     }
     // every pair of near-duplicate items, found once on the device (find_duplicates_handle)
     std::vector<DuplicatePair> find_duplicates(const std::vector<int64_t>& sources, float threshold, size_t max_pairs = 1 << 20,

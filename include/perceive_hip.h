@@ -663,6 +663,79 @@ pcv_status pcv_searcher_search_boosted(pcv_searcher* s, const float* queries, in
                                        double* out_boosted, int64_t* out_values, int32_t* out_ranks, int32_t* out_counts,
                                        int32_t* out_examined, uint8_t* out_exact);
 
+/* Compound queries: the exact top-k under "all of these", "any of these" and "but not like that" — the three requests that are not
+ * linear in the row and so are no single query vector (a sum A + B is topped by rows excellent for one part and indifferent to the
+ * other; q - w n pushes down every row in proportion to its similarity to n, related to n or not).  A compound has W wanted vectors
+ * (1 .. PCV_MAX_COMPOUND_PARTS) and A avoided vectors (0 .. PCV_MAX_COMPOUND_PARTS), the call a mode and an avoid_weight w >= 0 (f32,
+ * widened to f64).  For a searchable row x of the selected sources (hidden rows and a view's restriction apply as everywhere):
+ *   rel_j(x)  relevance of x under vector j, exactly as in boosted and diverse results: with c_j the canonical f64 score of the pair
+ *             (the bits pcv_searcher_search ranks by), cosine metric c_j; dot metric c_j / (double)dim, one f64 division.
+ *   base(x)   PCV_COMPOUND_ALL: min over the wanted vectors of rel_j(x); PCV_COMPOUND_ANY: max.
+ *   pen(x)    fl(w * max(0, max over the avoided vectors of rel_n(x))): a hinge — a row that does not resemble any avoided vector pays
+ *             nothing; 0 when A = 0.
+ *   m(x)      fl(base(x) - pen(x)): every operation rounded once, no fused multiply-add.  With A = 0, m = base bit for bit.
+ * ORDER: m descending, ties -> lower global position (the library's canonical order).  A row whose score is undefined under any of
+ * the compound's vectors (a zero row under the cosine) is no candidate.  The answer is the first num_results rows in that order, each
+ * row at most once.
+ * The walk (Fagin's threshold algorithm, the random accesses done where the rows live): the W ranked lists of the wanted vectors are
+ * walked in lockstep, PCV_MAX_RESULTS entries of each a step (the last step shorter, so that no list is walked past `pool`); the
+ * avoided vectors are never ranked.  After each step every row met for the first time is scored under ALL the compound's vectors — m
+ * does not depend on which list brought it in — and the KEPT rows are the first min(num_results, rows met) in the order above.  With
+ * T = min (ALL) or max (ANY) over the lists of the relevance of the last entry walked, the walk ends at the first step where one of
+ * these holds:
+ *   (a) a list delivered fewer entries than the step asked for: every selectable row has been met — exact = 1;
+ *   (b) num_results rows are kept and the last of them has m > T: exact = 1.  A row met in NO list has each rel_j at most its list's
+ *       last relevance, so base <= T; pen >= 0 and both roundings are monotone, so m <= T.  The test is STRICT: an unmet row with
+ *       m == T may have a lower position than the kept one, and then it wins the tie;
+ *   (c) `pool` entries of each list are walked: exact = 0 — the best rows met so far.  A 1 is a proof, a 0 is no disproof.
+ *   want, want_offsets    [sum W][dim] f32; compound i owns vectors want_offsets[i] .. want_offsets[i + 1] ([n_compounds + 1], from 0)
+ *   avoid, avoid_offsets  likewise [sum A][dim] and [n_compounds + 1]; both NULL: no avoided vectors anywhere
+ *   pool              num_results .. PCV_MAX_COMPOUND_POOL: entries of each list the walk may examine
+ *   out_ids           [n_compounds][num_results] the kept rows, best first, -1 behind them (may be NULL, as every output)
+ *   out_combined      [n_compounds][num_results] f64: m, NaN behind
+ *   out_part_scores   [n_compounds][num_results][PCV_MAX_COMPOUND_PARTS] f32: the score pcv_searcher_search reports for the row under
+ *                     each wanted vector, bit for bit; NaN behind W and behind the kept rows
+ *   out_penalties     [n_compounds][num_results] f64: pen, NaN behind
+ *   out_counts        [n_compounds] rows kept;  out_examined  [n_compounds] entries walked per list (of the longest walk, where an
+ *                     undefined score shortened another);  out_exact  [n_compounds] the certificate
+ * A NULL searcher, n_compounds <= 0, num_results outside [1, PCV_MAX_RESULTS], pool outside [num_results, PCV_MAX_COMPOUND_POOL], an
+ * unknown mode, a negative or non-finite avoid_weight, NULL or non-ascending offsets (offsets[0] != 0; one of avoid / avoid_offsets
+ * NULL alone), W outside [1, PCV_MAX_COMPOUND_PARTS], A outside [0, PCV_MAX_COMPOUND_PARTS], a vector value that is not finite and,
+ * under the cosine, a vector whose squared norm (f64, feature order) lies outside [2^-126, inf) give PCV_ERR_INVALID before any
+ * device work; pending rows and a queued pass fail as in pcv_searcher_search_boosted.  The wanted vectors of a compound share the
+ * passes of one group of queries: a compound with more wanted vectors than a pass takes (4 with PCV_KERNEL_WAVE) gives
+ * PCV_ERR_UNSUPPORTED, naming both numbers, before any launch.  No selected rows give the blank answer with exact = 1.  Works on views.
+ * Not in scope: a sharded form, device-resident output, a weighted-sum mode (that is one query vector today), a combination with the
+ * group table, the value table or distinct results. */
+enum { PCV_MAX_COMPOUND_PARTS = 8, PCV_MAX_COMPOUND_POOL = 4096 };
+enum { PCV_COMPOUND_ALL = 0, PCV_COMPOUND_ANY = 1 };
+pcv_status pcv_searcher_search_compound(pcv_searcher* s, const int64_t* source_ids, int n_sources, int num_results, int pool, int mode,
+                                        float avoid_weight, const float* want, const int64_t* want_offsets, const float* avoid,
+                                        const int64_t* avoid_offsets, int n_compounds, int64_t* out_ids, double* out_combined,
+                                        float* out_part_scores, double* out_penalties, int32_t* out_counts, int32_t* out_examined,
+                                        uint8_t* out_exact);
+/* The same call with every vector built on the device from stored items, as pcv_searcher_like_queries builds them: part p of the
+ * wanted side is the weighted sum of the rows that carry want_ids[want_example_offsets[p] .. want_example_offsets[p + 1]) (weights
+ * NULL: all 1), compound i owns parts want_offsets[i] .. want_offsets[i + 1]; likewise the avoided side, whose four arrays may all
+ * be NULL.  A view looks its examples up in its parent.  The built vectors are held to the checks above (a part none of whose
+ * examples is stored is a zero vector: PCV_ERR_INVALID under the cosine).  exclude_examples != 0: rows that carry one of the compound's
+ * WANTED example ids are left out of its answer, as in pcv_searcher_search_like — the walk keeps num_results plus the number of such
+ * rows (the largest over the compounds), which must not exceed PCV_MAX_RESULTS (else PCV_ERR_UNSUPPORTED), and the host drops
+ * them: a certified walk of the longer answer certifies the shorter one. */
+pcv_status pcv_searcher_search_compound_like(pcv_searcher* s, const int64_t* source_ids, int n_sources, int num_results, int pool, int mode,
+                                             float avoid_weight, const int64_t* want_ids, const float* want_weights,
+                                             const int64_t* want_example_offsets, const int64_t* want_offsets, const int64_t* avoid_ids,
+                                             const float* avoid_weights, const int64_t* avoid_example_offsets,
+                                             const int64_t* avoid_offsets, int n_compounds, int exclude_examples, int64_t* out_ids,
+                                             double* out_combined, float* out_part_scores, double* out_penalties, int32_t* out_counts,
+                                             int32_t* out_examined, uint8_t* out_exact);
+
+/* The select steps of the most recent ranked call on this handle (pcv_searcher_search_distinct, _grouped, _where, _boosted, _diverse,
+ * _compound): the hipEvent time of the launches that follow the passes — events recorded right before and after each, summed — and
+ * their number.  A diagnostic beside pcv_searcher_last_stats, whose total_ms times the passes themselves (tools/bench_compound.py).
+ * Either output may be NULL. */
+pcv_status pcv_searcher_last_select_stats(pcv_searcher* s, float* out_ms, int32_t* out_launches);
+
 /* Duplicate pairs: the exact self-join of the corpus on the device — every pair of searchable rows that are near-duplicates of each
  * other, found once and corpus-wide (what pcv_searcher_search_distinct collapses per query, for pcv_searcher_remove_ids /
  * pcv_searcher_hide_ids to act on).

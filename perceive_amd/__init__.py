@@ -12,6 +12,8 @@ from .search import (  # noqa: F401
     PCV_DENSITY_NONE,
     PCV_MAX_BOOST_KNOTS,
     PCV_MAX_BOOST_POOL,
+    PCV_MAX_COMPOUND_PARTS,
+    PCV_MAX_COMPOUND_POOL,
     PCV_NO_VALUE,
     SearchItem,
     Searcher,

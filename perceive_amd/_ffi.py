@@ -370,6 +370,11 @@ SYMBOLS = {
                                             _I64P, _INTP, _INTP, _U8P]),
     "pcv_searcher_search_boosted": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_int, C.POINTER(Boost), _I64P, _F32P, _F64P, _I64P, _INTP,
                                               _INTP, _INTP, _U8P]),
+    "pcv_searcher_last_select_stats": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "pcv_searcher_search_compound": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _F32P, _I64P, _F32P, _I64P, C.c_int, _I64P, _F64P,
+                                               _F32P, _F64P, _INTP, _INTP, _U8P]),
+    "pcv_searcher_search_compound_like": (C.c_int, [_P, _I64P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _I64P, _F32P, _I64P, _I64P, _I64P, _F32P,
+                                                    _I64P, _I64P, C.c_int, C.c_int, _I64P, _F64P, _F32P, _F64P, _INTP, _INTP, _U8P]),
     "pcv_searcher_search_diverse": (C.c_int, [_P, _F32P, C.c_int, _I64P, C.c_int, C.c_int, C.c_float, C.c_int, _I64P, _F32P, _F64P, _INTP, _INTP, _INTP, _U8P]),
     "pcv_searcher_find_duplicates": (C.c_int, [_P, _I64P, C.c_int, C.c_float, C.c_int64, _I64P, _I64P, _F32P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pcv_searcher_last_duplicate_stats": (C.c_int, [_P, C.POINTER(DuplicateStats)]),

@@ -1,7 +1,7 @@
 // corpus.h — launcher interface of the kernels that build and maintain a corpus segment (corpus_kernels.hip): staging, row
 // scales, the screening and mid copies of scan.h, and hiding, updating, removing, viewing and gathering stored items by id — and of the
 // id-keyed tables (grouped_kernels.hip), which share the id hash, and the predicate kernels over the value table (where_kernels.hip)
-// and the boosted select step that reads it (boost_kernels.hip).
+// and the boosted select step that reads it (boost_kernels.hip), and of the select step of compound queries (compound_kernels.hip).
 #pragma once
 #include "scan.h"
 
@@ -158,6 +158,36 @@ struct BoostArgs {
     int num_results;
 };
 void launch_boost_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const BoostArgs& a);
+// ---- compound queries (pcv_searcher_search_compound; compound_kernels.hip; DESIGN.md §4 "Compound queries") ----
+// The select step: the wanted vectors of a compound are adjacent queries of the pass, walked in lockstep; after each pass the hits
+// of all its lists are candidates, each scored under every vector of the compound, merged with the kept rows under
+// m = fl(base - pen), ties -> lower position.  Every part query's record carries the compound's kept, examined and flags and its own
+// last hit.  kDistinctFull: the certificate holds; kDistinctEnd: a list ended.
+constexpr int kMaxCompoundParts = PCV_MAX_COMPOUND_PARTS;
+struct CompoundDesc {
+    int32_t first_query;  // of the pass: the compound's first wanted vector; the others follow it
+    int32_t n_want;       // 1 .. kMaxCompoundParts
+    int32_t first_avoid;  // row of CompoundArgs::avoid
+    int32_t n_avoid;      // 0 .. kMaxCompoundParts
+};
+struct CompoundArgs {
+    DistinctRec* rec;            // [B] one per part query
+    DistinctRec* rec_host;       // [B] pinned host mirror, written after every pass
+    const CompoundDesc* desc;    // [n_compounds] of the group (device)
+    const double* want_norm;     // [B] canonical |q|^2 of the pass's queries
+    const float* avoid;          // [.][Dp] the call's avoided vectors, zero padded
+    const double* avoid_norm;    // [.] their canonical |q|^2
+    pcv_hit_dev* kept;           // [n_compounds][kMaxK] the kept rows, best first; score: m
+    double* kept_pen;            // [n_compounds][kMaxK] their penalties
+    double* kept_part;           // [n_compounds][kMaxK][kMaxCompoundParts] their canonical scores under each wanted vector
+    int n_compounds;
+    int max_want;                // the largest n_want of the group: the workgroup has kMaxK threads for each
+    int max_vectors;             // the largest n_want + n_avoid of the group: what the LDS staging is sized for
+    int num_results;
+    int mode;                    // PCV_COMPOUND_*
+    double lambda;
+};
+void launch_compound_select(hipStream_t st, const ScanParams& p, const ScanParams* dp, const CompoundArgs& a);
 // rows [dst_row0, dst_row0 + n_sel) of a view segment take rows sel[0..n_sel) of a parent segment (pieces, scale, id; parent
 // position pos0 + row -> dst_ppos[row of the view segment], unless dst_ppos is nullptr); rows [dst_row0 + n_sel, dst_end) become
 // padding

@@ -905,6 +905,167 @@ pcv_status pcv_searcher_search_boosted(pcv_searcher* s, const float* queries, in
     });
 }
 
+// What both compound calls ask of their scalar arguments and of the two levels of offsets, before anything touches the searcher.
+static void check_compound_args(const pcv_searcher* s, int n_compounds, int num_results, int pool, int mode, float avoid_weight, const char* who) {
+    PCV_REQUIRE(s != nullptr, "%s: searcher is NULL", who);
+    PCV_REQUIRE(n_compounds > 0 && n_compounds <= (1 << 20), "%s: n_compounds %d outside [1,%d]", who, n_compounds, 1 << 20);
+    PCV_REQUIRE(num_results >= 1 && num_results <= (int)PCV_MAX_RESULTS, "%s: num_results %d outside [1,%d]", who, num_results,
+                (int)PCV_MAX_RESULTS);
+    PCV_REQUIRE(pool >= num_results && pool <= (int)PCV_MAX_COMPOUND_POOL, "%s: pool %d outside [num_results = %d, %d]", who, pool, num_results,
+                (int)PCV_MAX_COMPOUND_POOL);
+    PCV_REQUIRE(mode == PCV_COMPOUND_ALL || mode == PCV_COMPOUND_ANY, "%s: unknown mode %d", who, mode);
+    PCV_REQUIRE(std::isfinite(avoid_weight) && avoid_weight >= 0.0f, "%s: avoid_weight %g is negative or not finite", who, (double)avoid_weight);
+}
+// offsets[n + 1] of one side: from 0, ascending, every compound with lo .. PCV_MAX_COMPOUND_PARTS vectors
+static void check_compound_offsets(const int64_t* off, int n, int lo, const char* side, const char* who) {
+    PCV_REQUIRE(off != nullptr, "%s: %s_offsets is NULL", who, side);
+    PCV_REQUIRE(off[0] == 0, "%s: %s_offsets[0] must be 0", who, side);
+    for (int i = 0; i < n; ++i) {
+        PCV_REQUIRE(off[i + 1] >= off[i], "%s: %s_offsets are not ascending (%s_offsets[%d] < %s_offsets[%d])", who, side, side, i + 1, side, i);
+        const int64_t w = off[i + 1] - off[i];
+        PCV_REQUIRE(w >= lo && w <= (int64_t)PCV_MAX_COMPOUND_PARTS, "%s: compound %d has %lld %s vectors, outside [%d,%d]", who, i, (long long)w,
+                    side, lo, (int)PCV_MAX_COMPOUND_PARTS);
+    }
+}
+// n vectors of one side: every value finite and, under the cosine, a squared norm finish_score accepts
+static void check_compound_vectors(const pcv_searcher* s, const float* v, int64_t n, const char* side, const char* who) {
+    for (int64_t q = 0; q < n; ++q) {
+        const float* x = v + (size_t)q * s->D;
+        for (int i = 0; i < s->D; ++i)
+            PCV_REQUIRE(std::isfinite(x[i]), "%s: value %d of %s vector %lld is not finite", who, i, side, (long long)q);
+        if (s->metric != PCV_METRIC_COSINE) continue;
+        const double nq = query_norm2(x, s->D);
+        PCV_REQUIRE(nq >= 0x1p-126 && nq < (double)INFINITY, "%s: %s vector %lld has squared norm %g: no cosine is defined for it", who, side,
+                    (long long)q, nq);
+    }
+}
+
+pcv_status pcv_searcher_search_compound(pcv_searcher* s, const int64_t* source_ids, int n_sources, int num_results, int pool, int mode,
+                                        float avoid_weight, const float* want, const int64_t* want_offsets, const float* avoid,
+                                        const int64_t* avoid_offsets, int n_compounds, int64_t* out_ids, double* out_combined,
+                                        float* out_part_scores, double* out_penalties, int32_t* out_counts, int32_t* out_examined,
+                                        uint8_t* out_exact) {
+    return guarded([&] {
+        const char* who = "search_compound";
+        check_compound_args(s, n_compounds, num_results, pool, mode, avoid_weight, who);
+        check_compound_offsets(want_offsets, n_compounds, 1, "want", who);
+        PCV_REQUIRE(want != nullptr, "%s: want is NULL", who);
+        PCV_REQUIRE(avoid == nullptr || avoid_offsets != nullptr, "%s: avoid is given without avoid_offsets", who);
+        if (avoid_offsets) {
+            check_compound_offsets(avoid_offsets, n_compounds, 0, "avoid", who);
+            PCV_REQUIRE(avoid != nullptr || avoid_offsets[n_compounds] == 0, "%s: avoid is NULL with %lld avoided vectors", who,
+                        (long long)avoid_offsets[n_compounds]);
+        }
+        std::lock_guard<std::mutex> lk(s->mu);
+        check_compound_vectors(s, want, want_offsets[n_compounds], "wanted", who);
+        if (avoid_offsets) check_compound_vectors(s, avoid, avoid_offsets[n_compounds], "avoided", who);
+        PCV_REQUIRE(!s->pending.active, "%s: a pass queued by search_device_begin has not been collected", who);
+        sync_view(s);
+        search_compound(CompoundCall{s, source_ids, n_sources, num_results, pool, mode, (double)avoid_weight, want, want_offsets, avoid, avoid_offsets,
+                                     n_compounds, out_ids, out_combined, out_part_scores, out_penalties, out_counts, out_examined, out_exact});
+    });
+}
+
+pcv_status pcv_searcher_search_compound_like(pcv_searcher* s, const int64_t* source_ids, int n_sources, int num_results, int pool, int mode,
+                                             float avoid_weight, const int64_t* want_ids, const float* want_weights,
+                                             const int64_t* want_example_offsets, const int64_t* want_offsets, const int64_t* avoid_ids,
+                                             const float* avoid_weights, const int64_t* avoid_example_offsets,
+                                             const int64_t* avoid_offsets, int n_compounds, int exclude_examples, int64_t* out_ids,
+                                             double* out_combined, float* out_part_scores, double* out_penalties, int32_t* out_counts,
+                                             int32_t* out_examined, uint8_t* out_exact) {
+    return guarded([&] {
+        const char* who = "search_compound_like";
+        check_compound_args(s, n_compounds, num_results, pool, mode, avoid_weight, who);
+        check_compound_offsets(want_offsets, n_compounds, 1, "want", who);
+        const int n_want = (int)want_offsets[n_compounds];
+        check_like_args(s, want_ids, want_weights, want_example_offsets, n_want, who);
+        const bool avoiding = avoid_offsets != nullptr;
+        PCV_REQUIRE(avoiding == (avoid_example_offsets != nullptr) && (avoiding || (avoid_ids == nullptr && avoid_weights == nullptr)),
+                    "%s: the avoided side must be given whole (offsets at both levels) or left NULL", who);
+        int n_avoid = 0;
+        if (avoiding) {
+            check_compound_offsets(avoid_offsets, n_compounds, 0, "avoid", who);
+            n_avoid = (int)avoid_offsets[n_compounds];
+            check_like_args(s, avoid_ids, avoid_weights, avoid_example_offsets, n_avoid, who);
+        }
+        std::lock_guard<std::mutex> lk(s->mu);
+        sync_view(s);
+        LikeBuilt wanted, avoided;
+        {
+            pcv_searcher* owner = nullptr;
+            const auto owner_lock = lock_like_owner(s, owner, who);
+            build_like_queries(owner, want_ids, want_weights, want_example_offsets, n_want, true, nullptr, wanted);
+            if (avoiding) build_like_queries(owner, avoid_ids, avoid_weights, avoid_example_offsets, n_avoid, true, nullptr, avoided);
+        }
+        check_compound_vectors(s, wanted.vectors.data(), n_want, "wanted", who);
+        if (avoiding) check_compound_vectors(s, avoided.vectors.data(), n_avoid, "avoided", who);
+        CompoundCall call{s, source_ids, n_sources, num_results, pool, mode, (double)avoid_weight, wanted.vectors.data(), want_offsets,
+                          avoiding ? avoided.vectors.data() : nullptr, avoid_offsets, n_compounds, out_ids, out_combined, out_part_scores,
+                          out_penalties, out_counts, out_examined, out_exact};
+        // Exclusion: at most `spare` rows carry a wanted example id of any one compound, so the first num_results + spare rows of its
+        // answer hold the num_results best of the others; what certifies the longer answer certifies its head.
+        int64_t spare = 0;
+        if (exclude_examples)
+            for (int i = 0; i < n_compounds; ++i) {
+                int64_t n = 0;
+                for (int64_t p = want_offsets[i]; p < want_offsets[i + 1]; ++p) n += wanted.carrier_rows[(size_t)p];
+                spare = std::max(spare, n);
+            }
+        if (spare == 0) {
+            search_compound(call);
+            return;
+        }
+        if ((int64_t)num_results + spare > (int64_t)PCV_MAX_RESULTS)
+            PCV_FAIL(PCV_ERR_UNSUPPORTED, "%s: num_results %d plus %lld example rows to leave out is more than %d", who, num_results,
+                     (long long)spare, (int)PCV_MAX_RESULTS);
+        const int k = num_results, kk = num_results + (int)spare, P = (int)PCV_MAX_COMPOUND_PARTS;
+        const size_t n = (size_t)n_compounds * kk;
+        std::vector<int64_t> ids(n);
+        std::vector<double> combined(n), penalties(n);
+        std::vector<float> parts(n * P);
+        std::vector<int32_t> counts((size_t)n_compounds);
+        call.k = kk;
+        call.pool = std::max(pool, kk);
+        call.out_ids = ids.data(), call.out_combined = combined.data(), call.out_part_scores = parts.data(), call.out_penalties = penalties.data();
+        call.out_counts = counts.data();
+        search_compound(call);
+        std::vector<int64_t> own;
+        for (int i = 0; i < n_compounds; ++i) {
+            own.assign(want_ids + want_example_offsets[want_offsets[i]], want_ids + want_example_offsets[want_offsets[i + 1]]);
+            std::sort(own.begin(), own.end());
+            int at = 0;
+            for (int j = 0; j < kk; ++j) {
+                const size_t from = (size_t)i * kk + j, to = (size_t)i * k + at;
+                const bool take = j < counts[(size_t)i] && at < k && !std::binary_search(own.begin(), own.end(), ids[from]);
+                if (!take) continue;
+                if (out_ids) out_ids[to] = ids[from];
+                if (out_combined) out_combined[to] = combined[from];
+                if (out_penalties) out_penalties[to] = penalties[from];
+                if (out_part_scores) std::memcpy(out_part_scores + to * P, parts.data() + from * P, (size_t)P * sizeof(float));
+                ++at;
+            }
+            if (out_counts) out_counts[i] = at;
+            for (; at < k; ++at) {
+                const size_t to = (size_t)i * k + at;
+                if (out_ids) out_ids[to] = -1;
+                if (out_combined) out_combined[to] = NAN;
+                if (out_penalties) out_penalties[to] = NAN;
+                if (out_part_scores)
+                    for (int u = 0; u < P; ++u) out_part_scores[to * P + u] = NAN;
+            }
+        }
+    });
+}
+
+pcv_status pcv_searcher_last_select_stats(pcv_searcher* s, float* out_ms, int32_t* out_launches) {
+    return guarded([&] {
+        PCV_REQUIRE(s != nullptr, "last_select_stats: searcher is NULL");
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (out_ms) *out_ms = s->select_ms;
+        if (out_launches) *out_launches = s->select_launches;
+    });
+}
+
 pcv_status pcv_searcher_like_queries(pcv_searcher* s, const int64_t* example_ids, const float* weights, const int64_t* offsets,
                                      int n_queries, float* out_queries, void* d_out_queries, uint8_t* out_found,
                                      int64_t* out_member_rows) {

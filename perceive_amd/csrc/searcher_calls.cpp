@@ -231,6 +231,8 @@ template <class Extra>
 bool open_ranked(const RankedCall& c, const char* who, SearchPlan& plan, uint8_t last, Extra extra) {
     check_search_args(c.s, c.queries, c.n_queries, c.k, who);
     c.s->stats = pcv_scan_stats{};  // (also when the kernel is refused)
+    c.s->select_ms = 0.0f;
+    c.s->select_launches = 0;
     plan = plan_search(c.s, c.source_ids, c.n_sources, c.n_queries);
     if (open_search(c.s, plan)) return true;
     for (int q = 0; q < c.n_queries; ++q) write_ranked(c, q, 0, 0, 0, last, [](size_t) { return pcv_hit_dev{}; }, extra);
@@ -253,6 +255,13 @@ std::vector<uint8_t> walk_ranked_lists(pcv_searcher* s, const SearchPlan& plan, 
     hipStream_t st = s->ctx->stream;
     std::vector<CeilRec> ceil((size_t)B);
     std::vector<pcv_hit_dev> last((size_t)B);
+    // (the walk's own pair of events around every select step: pcv_searcher_last_select_stats)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const auto drop_events = at_exit([&] {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    });
+    for (hipEvent_t& e : ev) PCV_HIP(hipEventCreate(&e));
     // the ceilings behind the last hit each query has walked (a finished query: nothing ranks after it)
     auto ceilings = [&] {
         for (int q = 0; q < B; ++q) last[(size_t)q] = rec[q].flags ? pcv_hit_dev{NAN, -1, -1} : pcv_hit_dev{rec[q].last_score, rec[q].last_pos, -1};
@@ -267,9 +276,15 @@ std::vector<uint8_t> walk_ranked_lists(pcv_searcher* s, const SearchPlan& plan, 
         const int kk = std::min(kMaxK, pool - walked);
         run_pass(s, PassRequest(qs, B, plan.segs, plan.kernel).top_k(kk, nullptr, false, nullptr, walked > 0 ? ceilings() : nullptr));
         // (the pass block is the pass's to allocate and to grow: its device address is read after the pass, never before)
+        PCV_HIP(hipEventRecord(ev[0], st));
         select();
+        PCV_HIP(hipEventRecord(ev[1], st));
         PCV_HIP(hipStreamSynchronize(st));
         PCV_HIP(hipGetLastError());
+        float ms = 0.0f;
+        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+        s->select_ms += ms;
+        s->select_launches += 1;
         pending = false;
         for (int q = 0; q < B; ++q) pending = pending || rec[q].flags == 0;
     }
@@ -697,6 +712,155 @@ void search_boosted(const RankedCall& c, const pcv_searcher* owner, const pcv_bo
         for (int q = 0; q < B; ++q)
             write_ranked(c, q0 + q, q, (int)rec[q].kept, (int32_t)rec[q].examined, rec[q].flags != 0 ? 1 : 0, [&](size_t i) { return r_kept[i]; }, extra);
     });
+}
+
+// ---- compound queries (pcv_searcher_search_compound; DESIGN.md §4 "Compound queries") ----
+// The state block of one group of compounds: the walk's records — one per PART query, as walk_ranked_lists wants them — and, per
+// kept row of each of the group's C compounds, the hit (its score: m), its penalty and its canonical score under each wanted
+// vector; the same layout on both sides, packed for the group's own number of compounds as BoostLayout is.
+namespace {
+struct CompoundLayout {
+    size_t off_kept, off_pen, off_part, total;
+    explicit CompoundLayout(size_t C) {
+        off_kept = (size_t)kMfmaQueries * sizeof(DistinctRec);
+        off_pen = off_kept + C * kMaxK * sizeof(pcv_hit_dev);
+        off_part = off_pen + C * kMaxK * sizeof(double);
+        total = off_part + C * kMaxK * kMaxCompoundParts * sizeof(double);
+    }
+};
+}  // namespace
+
+double query_norm2(const float* q, int D) {
+    double nq = 0.0;
+    for (int i = 0; i < D; ++i) nq += (double)q[i] * (double)q[i];
+    return nq;
+}
+
+// The fifth client of the ranked-call frame: the wanted vectors of a compound are adjacent queries of one group, walked in lockstep,
+// and after each pass compound_select_kernel scores the rows met for the first time under every vector of their compound, merges them
+// into the kept rows and tests the certificate.  The avoided vectors are uploaded once, with the descriptors and the norms; a group
+// takes whole compounds, as many as fit a pass.  The last column is the record's flag, as in search_boosted.
+void search_compound(const CompoundCall& c) {
+    pcv_searcher* s = c.s;
+    const int D = s->D, Dp = s->D4 * 4;
+    const int n_want = (int)c.want_off[c.n], n_avoid = c.avoid_off ? (int)c.avoid_off[c.n] : 0;
+    auto width = [&](int i) { return (int)(c.want_off[i + 1] - c.want_off[i]); };
+    auto blank = [&](int i, int from) {
+        for (int j = from; j < c.k; ++j) {
+            const size_t at = (size_t)i * c.k + j;
+            if (c.out_ids) c.out_ids[at] = -1;
+            if (c.out_combined) c.out_combined[at] = NAN;
+            if (c.out_penalties) c.out_penalties[at] = NAN;
+            if (c.out_part_scores)
+                for (int u = 0; u < kMaxCompoundParts; ++u) c.out_part_scores[at * kMaxCompoundParts + u] = NAN;
+        }
+    };
+    // (the frame's opening — argument check, statistics, plan, open_search — with the wanted vectors as the call's queries: the
+    // kernel is picked for all of them; its blank answer is per query, so the compounds' is written here)
+    const RankedCall frame{s, c.want, n_want, c.source_ids, c.n_sources, c.k, c.pool, nullptr, nullptr, nullptr, nullptr, nullptr};
+    check_search_args(s, c.want, n_want, c.k, "search_compound");
+    {
+        const int qstep = pass_queries(s, pick_kernel(s, n_want));
+        for (int i = 0; i < c.n; ++i)
+            if (width(i) > qstep)
+                PCV_FAIL(PCV_ERR_UNSUPPORTED,
+                         "search_compound: compound %d has %d wanted vectors, but a pass of this searcher's kernel takes %d queries "
+                         "(the wave kernel: use PCV_KERNEL_MFMA or PCV_KERNEL_AUTO)",
+                         i, width(i), qstep);
+    }
+    SearchPlan plan;
+    if (!open_ranked(frame, "search_compound", plan, 1, [](size_t, const size_t*) {})) {
+        for (int i = 0; i < c.n; ++i) {  // (exact: there is nothing to miss)
+            blank(i, 0);
+            if (c.out_counts) c.out_counts[i] = 0;
+            if (c.out_examined) c.out_examined[i] = 0;
+            if (c.out_exact) c.out_exact[i] = 1;
+        }
+        return;
+    }
+    hipStream_t st = s->ctx->stream;
+    // the call's tables: descriptors | norms of the wanted vectors | norms of the avoided vectors | the avoided vectors, zero padded
+    const size_t off_wn = (size_t)c.n * sizeof(CompoundDesc), off_an = off_wn + (size_t)n_want * sizeof(double);
+    const size_t off_av = off_an + (size_t)(n_avoid + 1) * sizeof(double), tab_bytes = off_av + (size_t)(n_avoid + 1) * Dp * sizeof(float);
+    std::vector<uint8_t> tab(tab_bytes, 0);
+    CompoundDesc* desc = reinterpret_cast<CompoundDesc*>(tab.data());
+    double* wn = reinterpret_cast<double*>(tab.data() + off_wn);
+    double* an = reinterpret_cast<double*>(tab.data() + off_an);
+    float* av = reinterpret_cast<float*>(tab.data() + off_av);
+    for (int q = 0; q < n_want; ++q) wn[q] = query_norm2(c.want + (size_t)q * D, D);
+    for (int q = 0; q < n_avoid; ++q) {
+        an[q] = query_norm2(c.avoid + (size_t)q * D, D);
+        std::memcpy(av + (size_t)q * Dp, c.avoid + (size_t)q * D, (size_t)D * sizeof(float));
+    }
+    // groups of whole compounds: as many as a pass takes queries
+    std::vector<int> first{0};  // first compound of every group, and the end
+    for (int i = 0, used = 0; i < c.n; ++i) {
+        if (used + width(i) > plan.qstep) first.push_back(i), used = 0;
+        desc[i].first_query = used;
+        desc[i].n_want = width(i);
+        desc[i].first_avoid = c.avoid_off ? (int32_t)c.avoid_off[i] : 0;
+        desc[i].n_avoid = c.avoid_off ? (int32_t)(c.avoid_off[i + 1] - c.avoid_off[i]) : 0;
+        used += width(i);
+    }
+    first.push_back(c.n);
+    size_t most = 0;
+    for (size_t g = 0; g + 1 < first.size(); ++g) most = std::max(most, (size_t)(first[g + 1] - first[g]));
+    s->d_compound.ensure(CompoundLayout(most).total);
+    s->pin_compound.ensure(CompoundLayout(most).total);
+    s->d_compound_tab.ensure(tab_bytes);
+    PCV_HIP(hipMemcpyAsync(s->d_compound_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
+    PCV_HIP(hipStreamSynchronize(st));  // (`tab` is pageable and the call's own)
+    uint8_t *dev = s->d_compound.p, *pin = s->pin_compound.p, *dtab = s->d_compound_tab.p;
+    DistinctRec* rec = reinterpret_cast<DistinctRec*>(pin);
+    CompoundArgs args{};
+    args.rec = reinterpret_cast<DistinctRec*>(dev);
+    args.rec_host = rec;
+    args.avoid = reinterpret_cast<const float*>(dtab + off_av);
+    args.avoid_norm = reinterpret_cast<const double*>(dtab + off_an);
+    args.num_results = c.k;
+    args.mode = c.mode;
+    args.lambda = c.lambda;
+    for (size_t g = 0; g + 1 < first.size(); ++g) {
+        const int c0 = first[g], C = first[g + 1] - c0, q0 = (int)c.want_off[c0], B = (int)c.want_off[c0 + C] - q0;
+        const CompoundLayout L((size_t)C);
+        args.desc = reinterpret_cast<const CompoundDesc*>(dtab) + c0;
+        args.want_norm = reinterpret_cast<const double*>(dtab + off_wn) + q0;
+        args.kept = reinterpret_cast<pcv_hit_dev*>(dev + L.off_kept);
+        args.kept_pen = reinterpret_cast<double*>(dev + L.off_pen);
+        args.kept_part = reinterpret_cast<double*>(dev + L.off_part);
+        args.n_compounds = C;
+        args.max_want = args.max_vectors = 0;
+        for (int i = c0; i < c0 + C; ++i) {
+            args.max_want = std::max(args.max_want, desc[i].n_want);
+            args.max_vectors = std::max(args.max_vectors, desc[i].n_want + desc[i].n_avoid);
+        }
+        walk_ranked_lists(s, plan, c.want + (size_t)q0 * D, B, c.pool, rec, args.rec, false, [&] {
+            launch_compound_select(st, pass_params(s), reinterpret_cast<const ScanParams*>(s->d_pass.p), args);
+        });
+        PCV_HIP(hipMemcpyAsync(pin + L.off_kept, dev + L.off_kept, L.total - L.off_kept, hipMemcpyDeviceToHost, st));
+        PCV_HIP(hipStreamSynchronize(st));
+        const pcv_hit_dev* r_kept = reinterpret_cast<const pcv_hit_dev*>(pin + L.off_kept);
+        const double* r_pen = reinterpret_cast<const double*>(pin + L.off_pen);
+        const double* r_part = reinterpret_cast<const double*>(pin + L.off_part);
+        for (int i = c0; i < c0 + C; ++i) {
+            const DistinctRec& r = rec[desc[i].first_query];  // (every part's record carries the compound's counters and flags)
+            const int n = (int)r.kept;
+            for (int j = 0; j < n; ++j) {
+                const size_t at = (size_t)i * c.k + j, from = (size_t)(i - c0) * kMaxK + j;
+                if (c.out_ids) c.out_ids[at] = r_kept[from].id;
+                if (c.out_combined) c.out_combined[at] = r_kept[from].score;
+                if (c.out_penalties) c.out_penalties[at] = r_pen[from];
+                if (c.out_part_scores)
+                    for (int u = 0; u < kMaxCompoundParts; ++u)
+                        c.out_part_scores[at * kMaxCompoundParts + u] =
+                            u < desc[i].n_want ? reported_score(s->metric, D, r_part[from * kMaxCompoundParts + u]) : NAN;
+            }
+            blank(i, n);
+            if (c.out_counts) c.out_counts[i] = n;
+            if (c.out_examined) c.out_examined[i] = (int32_t)r.examined;
+            if (c.out_exact) c.out_exact[i] = r.flags != 0 ? 1 : 0;
+        }
+    }
 }
 
 // The exact count: where_mark_kernel over every selected segment (the scratch of one segment at a time: launches of one stream

@@ -1,5 +1,5 @@
 // searcher_calls.h — the search calls behind the C entry points (searcher_calls.cpp): plain, range, distinct, grouped, diverse,
-// filtered and boosted search, the id-keyed tables (groups, values), the begin half of the sharded protocol and search by example.  The entry point has checked its
+// filtered, boosted and compound search, the id-keyed tables (groups, values), the begin half of the sharded protocol and search by example.  The entry point has checked its
 // arguments, holds s->mu, has seen that no pass is pending and has brought a view up to date (sync_view).
 #pragma once
 #include "searcher_pass.h"
@@ -45,6 +45,31 @@ void search_where(const RankedCall& c, const pcv_searcher* owner, const WherePre
 // Boosted results (DESIGN.md §4 "Boosted results").  `owner` as above; c.out_last is the `exact` column.
 void search_boosted(const RankedCall& c, const pcv_searcher* owner, const pcv_boost& boost, double* out_boosted, int64_t* out_values,
                     int32_t* out_ranks);
+// Compound queries (DESIGN.md §4 "Compound queries"): n compounds, compound i with wanted vectors want[want_off[i] .. want_off[i + 1])
+// and avoided vectors avoid[avoid_off[i] .. avoid_off[i + 1]) (avoid_off nullptr: none), [.][D] each; the entry point has checked
+// the offsets, the values and the norms.  Outputs as pcv_searcher_search_compound declares them, all nullable.
+struct CompoundCall {
+    pcv_searcher* s;
+    const int64_t* source_ids;
+    int n_sources;
+    int k, pool, mode;
+    double lambda;
+    const float* want;
+    const int64_t* want_off;
+    const float* avoid;
+    const int64_t* avoid_off;
+    int n;
+    int64_t* out_ids;
+    double* out_combined;
+    float* out_part_scores;
+    double* out_penalties;
+    int32_t* out_counts;
+    int32_t* out_examined;
+    uint8_t* out_exact;
+};
+void search_compound(const CompoundCall& c);
+// canonical |q|^2: f64, feature order (what the ranking pass and the compound select step divide by)
+double query_norm2(const float* q, int D);
 // rows of the selected sources of `s` that pass / those of them a search could return (s->mu and owner's lock held)
 void count_where(pcv_searcher* s, const pcv_searcher* owner, const int64_t* source_ids, int n_sources, const WherePred& w,
                  int64_t* out_rows, int64_t* out_searchable);

@@ -235,6 +235,15 @@ struct pcv_searcher {
     // queries, on the device and (records after every pass, the rest once) in pinned memory
     pcv::DevBuf<uint8_t> d_boost;
     pcv::PinBuf<uint8_t> pin_boost;
+    // compound queries (pcv_searcher_search_compound): records | kept rows | their penalties | part scores of one group of compounds,
+    // on the device and (records after every pass, the rest once) in pinned memory; and the call's tables: compound descriptors |
+    // vector norms | avoided vectors
+    // hipEvent time of the select steps of the most recent ranked call, and their number (pcv_searcher_last_select_stats)
+    float select_ms = 0.0f;
+    int32_t select_launches = 0;
+    pcv::DevBuf<uint8_t> d_compound;
+    pcv::PinBuf<uint8_t> pin_compound;
+    pcv::DevBuf<uint8_t> d_compound_tab;
     // the id-keyed tables (corpus.h "the id-keyed tables"): keys | vals on the device, the head block beside them and the host's
     // copy of it as of the last upsert (every one ends with a synchronised download).  One type, two instances: the group table
     // (pcv_searcher_set_groups; none = kNoGroup) and the value table (pcv_searcher_set_values; none = kNoValue).  A view has

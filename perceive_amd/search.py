@@ -21,6 +21,9 @@ PCV_NO_VALUE = -(1 << 63)  # include/perceive_hip.h: "no value" in set_values / 
 WHERE_UNSET_PASSES, WHERE_OUTSIDE = 1, 2  # include/perceive_hip.h: PCV_WHERE_*, the flags of a predicate
 PCV_MAX_BOOST_KNOTS = 16  # include/perceive_hip.h: most knots of a boost (search_boosted)
 PCV_MAX_BOOST_POOL = 4096  # include/perceive_hip.h
+PCV_MAX_COMPOUND_PARTS = 8  # include/perceive_hip.h: most wanted, and most avoided, vectors of a compound (search_compound)
+PCV_MAX_COMPOUND_POOL = 4096  # include/perceive_hip.h
+COMPOUND_MODES = {"all": 0, "any": 1}  # include/perceive_hip.h: PCV_COMPOUND_ALL, PCV_COMPOUND_ANY
 PCV_MAX_DUPLICATE_PAIRS = 1 << 24  # include/perceive_hip.h
 PCV_MAX_NEIGHBORS = 64  # include/perceive_hip.h
 GROUPS_SKIP_OWN, GROUPS_ONE_PER_GROUP = 1, 2  # include/perceive_hip.h: PCV_GROUPS_*, the flags of the grouped pair calls
@@ -725,6 +728,115 @@ class Searcher:
         if not found[0]:
             raise KeyError("Item not found")
         return self.search_boosted_vector(sources, num_results, vec[0], knot_values, knot_boosts, unset_boost, pool)
+
+    def last_select_stats(self):
+        """The select steps of the most recent ranked call (search_distinct, _grouped, _where, _boosted, _diverse, _compound) ->
+        (hipEvent ms of their launches, summed; number of launches)."""
+        ms, n = C.c_float(0.0), C.c_int32(0)
+        _ffi.check(_ffi.lib().pcv_searcher_last_select_stats(self._handle, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    # ---- compound queries (pcv_searcher_search_compound / _search_compound_like) ------------------------
+    # The exact top-k under "all of these" (min), "any of these" (max) and "but not like that" (a hinge penalty).
+    @staticmethod
+    def _compound_side(parts, dim):
+        """parts: a list of [n_i, dim] arrays (one vector may be given as [dim]), or None -> (vectors f32 [sum n_i, dim],
+        offsets int64 [len(parts) + 1]); None -> (None, None)"""
+        if parts is None:
+            return None, None
+        mats = []
+        for x in parts:
+            m = np.asarray(x, dtype=np.float32)
+            m = m.reshape(-1, dim) if m.size else np.zeros((0, dim), dtype=np.float32)
+            mats.append(m)
+        offsets = np.zeros(len(mats) + 1, dtype=np.int64)
+        if mats:
+            np.cumsum([m.shape[0] for m in mats], out=offsets[1:])
+        vec = np.ascontiguousarray(np.concatenate(mats) if mats else np.zeros((0, dim), dtype=np.float32), dtype=np.float32)
+        return vec, offsets
+
+    @staticmethod
+    def _compound_mode(mode):
+        return COMPOUND_MODES[mode] if mode in COMPOUND_MODES else int(mode)
+
+    @staticmethod
+    def _compound_outputs(n, k):
+        k0 = max(k, 0)
+        return (np.full((n, k0), -1, dtype=np.int64), np.full((n, k0), np.nan, dtype=np.float64),
+                np.full((n, k0, PCV_MAX_COMPOUND_PARTS), np.nan, dtype=np.float32), np.full((n, k0), np.nan, dtype=np.float64),
+                np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint8))
+
+    def search_compound(self, sources, num_results, wants, avoids=None, mode="all", avoid_weight=1.0, pool=None):
+        """The top num_results under m = base - avoid_weight * max(0, max_n rel_n): base is the min ("all") or the max ("any") of the
+        row's relevance under the compound's wanted vectors, rel_n its relevance under the avoided ones; ties to the lower position.
+        wants: a list of [W_i, dim] arrays, one compound each (W_i in 1 .. PCV_MAX_COMPOUND_PARTS); avoids: None, or a list of
+        [A_i, dim] arrays of the same length (A_i may be 0).  The W_i ranked lists are walked PCV_MAX_RESULTS entries at a time until
+        the k-th kept row beats what any row not yet met can reach, or `pool` entries of each (default
+        min(PCV_MAX_COMPOUND_POOL, max(128, 8 * num_results))) are walked.  -> (ids [n, k] int64 best first, combined [n, k] f64: m,
+        part_scores [n, k, PCV_MAX_COMPOUND_PARTS] f32: what search_vectors reports for the row under each wanted vector, NaN behind
+        W_i, penalties [n, k] f64, counts [n] int32, examined [n] int32, exact [n] bool: the rows are provably the top num_results).
+        The arithmetic is defined in include/perceive_hip.h."""
+        want, want_off = self._compound_side(wants, self.dim)
+        avoid, avoid_off = self._compound_side(avoids, self.dim)
+        n, k = want_off.size - 1, int(num_results)
+        if avoid_off is not None and avoid_off.size != want_off.size:
+            raise ValueError(f"{avoid_off.size - 1} avoid lists for {n} compounds")
+        if pool is None:
+            pool = min(PCV_MAX_COMPOUND_POOL, max(128, 8 * k))
+        ids, combined, parts, penalties, counts, examined, exact = self._compound_outputs(n, k)
+        src, nsrc, _keep = _source_filter(sources)
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_compound(
+                self._handle, src, nsrc, k, int(pool), self._compound_mode(mode), float(avoid_weight), _ffi.f32p(want), _ffi.i64p(want_off),
+                _ffi.f32p(avoid) if avoid is not None and avoid.size else None, _ffi.i64p(avoid_off) if avoid_off is not None else None, n,
+                _ffi.i64p(ids), _ffi.f64p(combined), _ffi.f32p(parts), _ffi.f64p(penalties), _ffi.i32p(counts), _ffi.i32p(examined), _ffi.u8p(exact),
+            )
+        )
+        return ids, combined, parts, penalties, counts[:n], examined[:n], exact[:n].astype(bool)
+
+    @staticmethod
+    def _compound_like_side(parts):
+        """parts: per compound a list of parts, each part a list of item ids or of (id, weight) pairs; None -> four Nones.
+        -> (ids int64, weights f32, example_offsets int64 [parts + 1], offsets int64 [compounds + 1])"""
+        if parts is None:
+            return None, None, None, None
+        ids, weights, ex_off, off = [], [], [0], [0]
+        for compound in parts:
+            for part in compound:
+                for e in part:
+                    pair = isinstance(e, (tuple, list))
+                    ids.append(int(e[0]) if pair else int(e))
+                    weights.append(float(e[1]) if pair else 1.0)
+                ex_off.append(len(ids))
+            off.append(len(ex_off) - 1)
+        return (np.asarray(ids, dtype=np.int64), np.asarray(weights, dtype=np.float32), np.asarray(ex_off, dtype=np.int64),
+                np.asarray(off, dtype=np.int64))
+
+    def search_compound_like_items(self, sources, num_results, wants, avoids=None, mode="all", avoid_weight=1.0, pool=None,
+                                   exclude_examples=True):
+        """search_compound with every vector built on the device from stored items, as like_queries builds them: wants[i] is the list
+        of compound i's parts, a part a list of item ids (or (id, weight) pairs) whose rows are summed; avoids likewise or None.
+        exclude_examples: no row that carries one of a compound's wanted example ids is in its answer.  Returns what search_compound
+        returns."""
+        w_ids, w_w, w_ex, w_off = self._compound_like_side(wants)
+        a_ids, a_w, a_ex, a_off = self._compound_like_side(avoids)
+        n, k = w_off.size - 1, int(num_results)
+        if a_off is not None and a_off.size != w_off.size:
+            raise ValueError(f"{a_off.size - 1} avoid lists for {n} compounds")
+        if pool is None:
+            pool = min(PCV_MAX_COMPOUND_POOL, max(128, 8 * k))
+        ids, combined, parts, penalties, counts, examined, exact = self._compound_outputs(n, k)
+        src, nsrc, _keep = _source_filter(sources)
+        ptr = lambda a, f: f(a) if a is not None and a.size else None  # noqa: E731
+        _ffi.check(
+            _ffi.lib().pcv_searcher_search_compound_like(
+                self._handle, src, nsrc, k, int(pool), self._compound_mode(mode), float(avoid_weight), ptr(w_ids, _ffi.i64p), ptr(w_w, _ffi.f32p),
+                _ffi.i64p(w_ex), _ffi.i64p(w_off), ptr(a_ids, _ffi.i64p), ptr(a_w, _ffi.f32p), _ffi.i64p(a_ex) if a_ex is not None else None,
+                _ffi.i64p(a_off) if a_off is not None else None, n, 1 if exclude_examples else 0, _ffi.i64p(ids), _ffi.f64p(combined),
+                _ffi.f32p(parts), _ffi.f64p(penalties), _ffi.i32p(counts), _ffi.i32p(examined), _ffi.u8p(exact),
+            )
+        )
+        return ids, combined, parts, penalties, counts[:n], examined[:n], exact[:n].astype(bool)
 
     # ---- duplicate pairs (pcv_searcher_find_duplicates) ----------------------------------------------
     # The exact self-join of the corpus: what search_distinct collapses per query, found once for remove_items / hide_items.

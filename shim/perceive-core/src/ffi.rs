@@ -337,6 +337,10 @@ pub const PCV_MAX_WHERE_POOL: c_int = 4096;
 pub const PCV_MAX_DIVERSE_POOL: c_int = 4096;
 pub const PCV_MAX_BOOST_KNOTS: c_int = 16;
 pub const PCV_MAX_BOOST_POOL: c_int = 4096;
+pub const PCV_MAX_COMPOUND_PARTS: c_int = 8;
+pub const PCV_MAX_COMPOUND_POOL: c_int = 4096;
+pub const PCV_COMPOUND_ALL: c_int = 0;
+pub const PCV_COMPOUND_ANY: c_int = 1;
 pub const PCV_MAX_DUPLICATE_PAIRS: c_int = 16777216;
 pub const PCV_MAX_LABELS: c_int = 4096;
 pub const PCV_MAX_TOP_LABELS: c_int = 8;
@@ -439,6 +443,9 @@ extern "C" {
     pub fn pcv_searcher_create_view_where(parent: *mut pcv_searcher, lo: i64, hi: i64, flags: u32, out_view: *mut *mut pcv_searcher) -> c_int;
     pub fn pcv_searcher_search_diverse(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, lambda: f32, pool: c_int, out_ids: *mut i64, out_scores: *mut f32, out_marginal: *mut f64, out_ranks: *mut i32, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
     pub fn pcv_searcher_search_boosted(s: *mut pcv_searcher, queries: *const f32, n_queries: c_int, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, boost: *const pcv_boost, out_ids: *mut i64, out_scores: *mut f32, out_boosted: *mut f64, out_values: *mut i64, out_ranks: *mut i32, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
+    pub fn pcv_searcher_search_compound(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, mode: c_int, avoid_weight: f32, want: *const f32, want_offsets: *const i64, avoid: *const f32, avoid_offsets: *const i64, n_compounds: c_int, out_ids: *mut i64, out_combined: *mut f64, out_part_scores: *mut f32, out_penalties: *mut f64, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
+    pub fn pcv_searcher_search_compound_like(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, num_results: c_int, pool: c_int, mode: c_int, avoid_weight: f32, want_ids: *const i64, want_weights: *const f32, want_example_offsets: *const i64, want_offsets: *const i64, avoid_ids: *const i64, avoid_weights: *const f32, avoid_example_offsets: *const i64, avoid_offsets: *const i64, n_compounds: c_int, exclude_examples: c_int, out_ids: *mut i64, out_combined: *mut f64, out_part_scores: *mut f32, out_penalties: *mut f64, out_counts: *mut i32, out_examined: *mut i32, out_exact: *mut u8) -> c_int;
+    pub fn pcv_searcher_last_select_stats(s: *mut pcv_searcher, out_ms: *mut f32, out_launches: *mut i32) -> c_int;
     pub fn pcv_searcher_find_duplicates(s: *mut pcv_searcher, source_ids: *const i64, n_sources: c_int, threshold: f32, max_pairs: i64, out_id_a: *mut i64, out_id_b: *mut i64, out_scores: *mut f32, out_count: *mut i64, out_total: *mut i64) -> c_int;
     pub fn pcv_searcher_last_duplicate_stats(s: *mut pcv_searcher, out: *mut pcv_duplicate_stats) -> c_int;
     pub fn pcv_searcher_assign(s: *mut pcv_searcher, labels: *const f32, n_labels: c_int, source_ids: *const i64, n_sources: c_int, capacity: i64, out_label: *mut i32, out_score: *mut f32, out_ids: *mut i64, out_counts: *mut i64, out_n: *mut i64) -> c_int;

@@ -622,6 +622,143 @@ impl Searcher {
         ((0..count as usize).map(|i| (SearchItem { id: ids[i], score: scores[i] }, boosted[i], values[i])).collect(), exact != 0)
     }
 
+    /// Compound search (`pcv_searcher_search_compound`): the top `num_results` under m = base - `avoid_weight` * max(0, max_n rel_n),
+    /// where base is the minimum (`any == false`: relevant to ALL of `want`) or the maximum (`any == true`: to ANY of them) of the
+    /// row's relevance under the wanted vectors and rel_n its relevance under the avoided ones — a hinge: only rows that resemble an
+    /// avoided vector pay.  `want` holds 1 ..= `ffi::PCV_MAX_COMPOUND_PARTS` vectors, `avoid` up to as many.  At most `pool` entries
+    /// of each wanted vector's ranked list are walked (`None`: min(PCV_MAX_COMPOUND_POOL, max(128, 8 * num_results))).  Each hit is
+    /// (item id, m, the score `search_vector` reports under each wanted vector, penalty); the flag says whether the hits are provably
+    /// the top of all rows.
+    pub fn search_compound(
+        &self,
+        sources: &[i64],
+        num_results: usize,
+        want: &[Vec<f32>],
+        avoid: &[Vec<f32>],
+        any: bool,
+        avoid_weight: f32,
+        pool: Option<usize>,
+    ) -> (Vec<(i64, f64, Vec<f32>, f64)>, bool) {
+        if self.handle.is_null() || num_results == 0 {
+            return (Vec::new(), true);
+        }
+        let mut dim: i32 = 0;
+        hip::check(unsafe { ffi::pcv_searcher_dim(self.handle, &mut dim) }).expect("searcher_dim failed");
+        for v in want.iter().chain(avoid.iter()) {
+            assert_eq!(v.len(), dim as usize, "search_compound: a vector has {} values, the index is {}-d", v.len(), dim);
+        }
+        let parts = ffi::PCV_MAX_COMPOUND_PARTS as usize;
+        let want_flat: Vec<f32> = want.iter().flatten().copied().collect();
+        let avoid_flat: Vec<f32> = avoid.iter().flatten().copied().collect();
+        let want_off = [0i64, want.len() as i64];
+        let avoid_off = [0i64, avoid.len() as i64];
+        let mode = if any { ffi::PCV_COMPOUND_ANY } else { ffi::PCV_COMPOUND_ALL };
+        let pool = pool.unwrap_or_else(|| (ffi::PCV_MAX_COMPOUND_POOL as usize).min((8 * num_results).max(128)));
+        let mut ids = vec![-1i64; num_results];
+        let mut combined = vec![f64::NAN; num_results];
+        let mut scores = vec![f32::NAN; num_results * parts];
+        let mut penalties = vec![f64::NAN; num_results];
+        let mut count: i32 = 0;
+        let mut exact: u8 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_compound(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                num_results as i32,
+                pool as i32,
+                mode,
+                avoid_weight,
+                want_flat.as_ptr(),
+                want_off.as_ptr(),
+                if avoid_flat.is_empty() { std::ptr::null() } else { avoid_flat.as_ptr() },
+                avoid_off.as_ptr(),
+                1,
+                ids.as_mut_ptr(),
+                combined.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                penalties.as_mut_ptr(),
+                &mut count,
+                std::ptr::null_mut(),
+                &mut exact,
+            )
+        })
+        .expect("search_compound failed");
+        let hits = (0..count as usize).map(|i| (ids[i], combined[i], scores[i * parts..i * parts + want.len()].to_vec(), penalties[i])).collect();
+        (hits, exact != 0)
+    }
+
+    /// `search_compound` with every vector built on the device from stored items (`pcv_searcher_search_compound_like`): part p of
+    /// `want` / `avoid` is the sum of the rows that carry its item ids.  `exclude_examples`: no row that carries a wanted example id
+    /// is returned.
+    pub fn search_compound_like_items(
+        &self,
+        sources: &[i64],
+        num_results: usize,
+        want: &[Vec<i64>],
+        avoid: &[Vec<i64>],
+        any: bool,
+        avoid_weight: f32,
+        pool: Option<usize>,
+        exclude_examples: bool,
+    ) -> Result<(Vec<(i64, f64, Vec<f32>, f64)>, bool), HipError> {
+        if self.handle.is_null() || num_results == 0 {
+            return Ok((Vec::new(), true));
+        }
+        let parts = ffi::PCV_MAX_COMPOUND_PARTS as usize;
+        let csr = |groups: &[Vec<i64>]| -> (Vec<i64>, Vec<i64>) {
+            let mut ids = Vec::new();
+            let mut off = vec![0i64];
+            for g in groups {
+                ids.extend_from_slice(g);
+                off.push(ids.len() as i64);
+            }
+            (ids, off)
+        };
+        let (w_ids, w_ex) = csr(want);
+        let (a_ids, a_ex) = csr(avoid);
+        let want_off = [0i64, want.len() as i64];
+        let avoid_off = [0i64, avoid.len() as i64];
+        let mode = if any { ffi::PCV_COMPOUND_ANY } else { ffi::PCV_COMPOUND_ALL };
+        let pool = pool.unwrap_or_else(|| (ffi::PCV_MAX_COMPOUND_POOL as usize).min((8 * num_results).max(128)));
+        let mut ids = vec![-1i64; num_results];
+        let mut combined = vec![f64::NAN; num_results];
+        let mut scores = vec![f32::NAN; num_results * parts];
+        let mut penalties = vec![f64::NAN; num_results];
+        let mut count: i32 = 0;
+        let mut exact: u8 = 0;
+        hip::check(unsafe {
+            ffi::pcv_searcher_search_compound_like(
+                self.handle,
+                sources.as_ptr(),
+                sources.len() as i32,
+                num_results as i32,
+                pool as i32,
+                mode,
+                avoid_weight,
+                if w_ids.is_empty() { std::ptr::null() } else { w_ids.as_ptr() },
+                std::ptr::null(),
+                w_ex.as_ptr(),
+                want_off.as_ptr(),
+                if a_ids.is_empty() { std::ptr::null() } else { a_ids.as_ptr() },
+                std::ptr::null(),
+                a_ex.as_ptr(),
+                avoid_off.as_ptr(),
+                1,
+                exclude_examples as i32,
+                ids.as_mut_ptr(),
+                combined.as_mut_ptr(),
+                scores.as_mut_ptr(),
+                penalties.as_mut_ptr(),
+                &mut count,
+                std::ptr::null_mut(),
+                &mut exact,
+            )
+        })?;
+        let hits = (0..count as usize).map(|i| (ids[i], combined[i], scores[i * parts..i * parts + want.len()].to_vec(), penalties[i])).collect();
+        Ok((hits, exact != 0))
+    }
+
     /// A search restricted to the items whose value passes a predicate (`pcv_searcher_create_view_where`): a view like `view`
     /// without an id list — the rows are selected on the device from the value table — that also follows every later `set_values`.
     pub fn view_where(&self, lo: i64, hi: i64, flags: u32) -> Result<SearcherView<'_>, HipError> {
