@@ -2731,19 +2731,32 @@ static void launch_mfma8_variant(hipStream_t st, const ScanParams* dp, unsigned 
     allow_dynamic_lds((const void*)scan_mfma8_kernel<NT, NTL, WPB, NBUF, DRAIN, NCHT, SIX>, lds);
     scan_mfma8_kernel<NT, NTL, WPB, NBUF, DRAIN, NCHT, SIX><<<grid, WPB * 64, lds, st>>>(dp);
 }
-// The 6-bit form: 5..64 queries (the DRAIN form), rows of up to 384 features (chunk counts 1..3), non-temporal loads, four chunk
-// buffers — the shapes the copy is built for.  The searcher asks mfma8_six_pass before it sets kFlagSix.
+// The 6-bit form: 5..64 queries (the DRAIN form), rows of up to 384 features (chunk counts 1..3), non-temporal loads, three or four
+// chunk buffers (kSixChunkBufs) — the shapes the copy is built for.  The searcher asks mfma8_six_pass before it sets kFlagSix.
+// The comparison switches of the int8 scan name int8 kernels, so a pass that carries one keeps to the int8 form: the four-wave form,
+// plain loads, and bits 24..27 = 3, which selects the three-buffer build of the int8 DRAIN form at 33..64 queries (below).  The
+// 6-bit form has one buffer count and takes none from the flags; any other value of those bits means nothing to either form.
 bool mfma8_six_pass(int B, int Dp, uint32_t flags, int nseg) {
     const int nt = B <= 32 ? 1 : 2;
     return B > 4 && B <= 64 && ((Dp + 127) & ~127) <= kSixMaxDp8 && !(flags & kFlagFourWave) && !(flags & kFlagPlainLoads) && flags_chunk_bufs(flags) != 3 &&
            nseg < (1 << kRingSegBits) && mfma8_lds(nt, Dp) + 68 * 1024 <= 156 * 1024;
 }
+// 33..64 queries (two query tiles, NT = 2): three chunk buffers, not the int8 form's four — two chunks of 3 KB in flight per wave
+// while one is multiplied, 66 KB per CU with its eleven streaming waves, 17 MB across the chip.  Measured at 100M x 384, 64 queries,
+// builds alternating on one box (kernel ms, median of four): 3 buffers 4.520, 2 buffers 4.547, 4 buffers 4.586-4.614, 5 buffers
+// 4.690; 4 buffers with every s_waitcnt vmcnt(0) taken out of the streaming loop 4.652.  Why is not established: more requests than
+// the memory system needs queueing in front of its channels, or the shorter loop (at three chunks per block lcm(3, 3) steps = one
+// block of code instead of four) — the two were not told apart, and two buffers are slower again.
+// 5..32 queries (one tile, half the multiplies per chunk): four buffers.  With three the pass is slower, 4.494 -> 4.618 ms a step
+// at 32 queries and 4.453 -> 4.631 at 8 (100M x 384; no difference at D = 128).  DESIGN.md, "The 6-bit screen in the DRAIN form".
+template <int NT>
+constexpr int kSixChunkBufs = NT == 2 ? 3 : 4;
 template <int NT>
 static void launch_mfma8_six(hipStream_t st, const ScanParams* dp, unsigned grid, size_t lds, int nch) {
     switch (nch) {
-        case 1: launch_mfma8_variant<NT, true, 12, 4, true, 1, true>(st, dp, grid, lds); break;
-        case 2: launch_mfma8_variant<NT, true, 12, 4, true, 2, true>(st, dp, grid, lds); break;
-        case 3: launch_mfma8_variant<NT, true, 12, 4, true, 3, true>(st, dp, grid, lds); break;
+        case 1: launch_mfma8_variant<NT, true, 12, kSixChunkBufs<NT>, true, 1, true>(st, dp, grid, lds); break;
+        case 2: launch_mfma8_variant<NT, true, 12, kSixChunkBufs<NT>, true, 2, true>(st, dp, grid, lds); break;
+        case 3: launch_mfma8_variant<NT, true, 12, kSixChunkBufs<NT>, true, 3, true>(st, dp, grid, lds); break;
         default: PCV_FAIL(PCV_ERR_INTERNAL, "6-bit screen: %d chunks per block", nch);
     }
 }
