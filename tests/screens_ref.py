@@ -41,7 +41,11 @@ def margins(rows, qs):
 def bf16(x):
     """f32 -> bf16 by round-to-nearest-even (what (__bf16)x and __builtin_convertvector do), returned as f32"""
     u = np.ascontiguousarray(x, dtype=F32).view(np.uint32)
-    r = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    r = u >> np.uint32(16)  # u + 0x7FFF + ((u >> 16) & 1), cut to the high half: one array, worked in place
+    r &= np.uint32(1)
+    r += np.uint32(0x7FFF)
+    r += u
+    r &= np.uint32(0xFFFF0000)
     return r.view(F32)
 
 
@@ -89,7 +93,7 @@ def keep_bf16(rows, qs, tau, slack=0.0, f32_rows=False):
     the kernel counts it as a coarse survivor and sheds it at its scale in fine_survivors.  Slack: allow = |slack| (unit + |thr|)."""
     tau = np.asarray(tau, dtype=np.float64)
     sgn, a = _split(slack)
-    s16 = _memo(rows, qs, "s16", lambda: bf16(rows.y.astype(F32)).astype(np.float64) @ bf16(qs.qp.astype(F32)).astype(np.float64).T)
+    s16 = _memo(rows, qs, "s16", lambda: bf16(rows.y32).astype(np.float64) @ bf16(qs.qp.astype(F32)).astype(np.float64).T)
     thr = (tau - margins(rows, qs)[0])[None, :]
     keep = ~(s16 < thr - sgn * a * (qs.unit[None, :] + np.abs(thr)))
     if f32_rows:
@@ -123,7 +127,7 @@ def mid_codes(rows):
         s2 = (rows.s_blk.astype(F32) * (F32(32766.0) / F32(127.0))).astype(F32)
         s2r = rows.block_of_rows(s2)
         safe = np.where(np.isnan(s2r), F32(0.0), s2r).astype(F32)
-        Y = np.clip(np.rint(rows.y.astype(F32) * safe[:, None]), -32767, 32767).astype(np.float64)
+        Y = np.clip(np.rint(rows.y32 * safe[:, None]), -32767, 32767).astype(np.float64)
         Y[rows.scale == 0] = 0.0
         rows._screens_mid = (Y, s2r.astype(np.float64))
     return rows._screens_mid

@@ -23,6 +23,8 @@ Slack.  Each test takes a relative slack: positive loosens, negative tightens it
     |slack| (s_blk s_q unit + |s_blk s_q tau| + s_blk c1 + V_q)               int8
 unit = the size of a score, 1 (cosine) or |q| max|x| (dot).  kernel_slack(D) is the value that covers what the kernels add to the
 test on purpose; its derivation is in its docstring."""
+import functools
+
 import numpy as np
 
 WN_SLACK = 2.0 ** -20 + 2.0 ** -21
@@ -58,8 +60,9 @@ def sum_squares(x):
     """|x|^2 per row, f64, accumulated in feature order (row_sum_squares)"""
     nx = np.zeros(x.shape[0])
     with np.errstate(over="ignore", invalid="ignore"):
-        for j in range(x.shape[1]):
-            nx += x[:, j].astype(np.float64) ** 2
+        for j in range(0, x.shape[1], 64):  # (the same additions in the same order, over contiguous columns, 64 at a time)
+            for col in np.ascontiguousarray(x[:, j:j + 64].T, dtype=np.float64):
+                nx += col ** 2
     return nx
 
 
@@ -90,32 +93,57 @@ class Rows:
         self.nonfinite = np.zeros(npad, bool)  # a row with an inf or a NaN: scale 0, and NaN products where a kernel multiplies anyway
         self.nonfinite[:n] = ~finite
         self.x = np.zeros((npad, self.Dp))     # the f32 rows themselves; zeros for a row without a scale (the fine test ends there)
-        self.x[:n, :D] = np.where(scale[:, None] != 0, rows, np.float32(0.0))
+        self.x[:n, :D] = rows
+        self.x[:n][scale == 0] = 0.0
         y = np.zeros((npad, self.Dp), np.float32)
+        y[:n, :D] = rows
         with np.errstate(over="ignore", invalid="ignore"):
-            y[:n, :D] = np.where(scale[:, None] != 0, rows * scale[:, None], np.float32(0.0))
-        mx = np.abs(y).max(axis=1)
+            y[:n, :D] *= scale[:, None]  # (an f32 product)
+        y[:n][scale == 0] = 0.0
+        mx = np.maximum(y.max(axis=1), -y.min(axis=1))  # max |y|, NaN where the row has one
         self.live = (self.scale != 0) & (mx < np.inf)
         y[~self.live] = 0.0
-        self.y = y.astype(np.float64)
-        yb = y.reshape(self.nblk, 32, self.Dp)
+        self.y32 = y                           # y as the device has it; `y` is the same in f64, made when it is first read
         liveb = self.live.reshape(self.nblk, 32)
         bm = np.where(liveb, mx.reshape(self.nblk, 32), np.float32(0.0)).max(axis=1).astype(np.float32)
         with np.errstate(divide="ignore"):
             s = np.where(bm > 0, np.float32(127.0) / bm, np.float32(1.0)).astype(np.float32)
         self.s_blk = np.where(liveb.any(axis=1), s, np.float32(np.nan)).astype(np.float32)
-        s_safe = np.where(liveb.any(axis=1), s, np.float32(1.0)).astype(np.float32)
-        codes = np.clip(np.rint(yb * s_safe[:, None, None]), -127, 127).astype(np.int64)  # (the product is an f32 one)
-        codes[~liveb] = 0
-        self.codes8 = codes.reshape(npad, self.Dp)
-        h = self.codes8 >> 2
-        self.u = h + 32
-        inv_s = 1.0 / s_safe.astype(np.float64)
-        xt = (4.0 * h.reshape(self.nblk, 32, self.Dp) + 1.5) * inv_s[:, None, None]
-        err = np.sqrt(((yb.astype(np.float64) - xt) ** 2).sum(axis=2))
+        self._s_safe = np.where(liveb.any(axis=1), s, np.float32(1.0)).astype(np.float32)
+
+    # The int8 and 6-bit codes and the 6-bit residual bounds are made when they are first read: a model that never reads them (a
+    # screen without such a copy) does not pay for them.
+    @functools.cached_property
+    def y(self):
+        return self.y32.astype(np.float64)
+
+    @functools.cached_property
+    def codes8(self):
+        yb = self.y32.reshape(self.nblk, 32, self.Dp)
+        codes = np.clip(np.rint(yb * self._s_safe[:, None, None]), -127, 127).astype(np.int64)  # (the product is an f32 one)
+        codes[~self.live.reshape(self.nblk, 32)] = 0
+        return codes.reshape(self.nblk * 32, self.Dp)
+
+    @functools.cached_property
+    def u(self):
+        return (self.codes8 >> 2) + 32
+
+    @functools.cached_property
+    def _six_bounds(self):
+        liveb = self.live.reshape(self.nblk, 32)
+        inv_s = 1.0 / self._s_safe.astype(np.float64)
+        xt = (4.0 * (self.codes8 >> 2).reshape(self.nblk, 32, self.Dp) + 1.5) * inv_s[:, None, None]
+        err = np.sqrt(((self.y.reshape(self.nblk, 32, self.Dp) - xt) ** 2).sum(axis=2))
         nrm = np.sqrt((xt ** 2).sum(axis=2))
-        self.r_blk = np.where(liveb, err, 0.0).max(axis=1)
-        self.n_blk = np.where(liveb, nrm, 0.0).max(axis=1)
+        return np.where(liveb, err, 0.0).max(axis=1), np.where(liveb, nrm, 0.0).max(axis=1)
+
+    @property
+    def r_blk(self):
+        return self._six_bounds[0]
+
+    @property
+    def n_blk(self):
+        return self._six_bounds[1]
 
     def block_of_rows(self, per_block):
         return np.repeat(per_block, 32)
@@ -167,12 +195,21 @@ def estimates(rows, qs):
     return est, bound
 
 
+def _acc8(rows, qs):
+    """sum x^_i q^_i [nblk * 32, B], once per (rows, queries): it does not depend on the thresholds"""
+    store = rows.__dict__.setdefault("_acc8_memo", {})
+    if id(qs) not in store:
+        store[id(qs)] = (qs, rows.codes8.astype(np.float64) @ qs.qh.T.astype(np.float64))  # (the queries are held: their id stays theirs)
+    return store[id(qs)][1]
+
+
 def keep_int8(rows, qs, tau, slack=0.0):
     """The int8 test on its own, bool [nblk * 32, B]: acc8 >= s_blk (s_q tau - c1) - V_q with the kernel's constants (the header);
-    the slack's quantities are unit, |Rhs|, s_blk c1 and V_q.  The codes are small integers: the float64 product is exact."""
+    the slack's quantities are unit, |Rhs|, s_blk c1 and V_q.  The codes are small integers: the float64 product is exact.
+    The right-hand side is the same for the 32 rows of a block: it is worked out per block and repeated."""
     tau = np.asarray(tau, dtype=np.float64)
     sgn, a = (1.0 if slack >= 0 else -1.0), abs(slack)
-    s = rows.block_of_rows(rows.s_blk.astype(np.float64))[:, None]   # NaN: no comparison succeeds
+    s = rows.s_blk.astype(np.float64)[:, None]   # [nblk, 1]; NaN: no comparison succeeds
     sq = qs.s_q.astype(np.float64)[None, :]
     with np.errstate(invalid="ignore"):
         ssq = s * sq
@@ -181,9 +218,11 @@ def keep_int8(rows, qs, tau, slack=0.0):
         c1 = 0.5002 * np.sqrt(float(rows.Dp8)) * nrm
         vq = (0.5002 * qs.l1 * qs.s_q + 0.2501 * rows.Dp8 + 4.0)[None, :]
         allow8 = a * (ssq * qs.unit[None, :] + np.abs(rhs) + s * c1 + vq)
-        eight = (rows.codes8.astype(np.float64) @ qs.qh.T.astype(np.float64)) >= rhs - s * c1 - vq - sgn * allow8
+        eight = _acc8(rows, qs) >= np.repeat(rhs - s * c1 - vq - sgn * allow8, 32, axis=0)
     dead = (qs.s_q == 0)[None, :]
-    has_rows = ~np.isnan(s)
+    if not dead.any():
+        return eight
+    has_rows = np.repeat(~np.isnan(s), 32, axis=0)
     fill = has_rows if rows.metric == "dot" else np.zeros_like(has_rows)
     return np.where(dead, fill, eight)
 
