@@ -353,7 +353,28 @@ enum { PCV_MAX_RESULTS = 128 };
  * Result order: COSINE descending cosine, DOT ascending distance; ties -> lower global position.
  * Rows whose norm is 0 or not finite (cosine undefined; the reference would yield NaN and panic at
  * search.rs:179) are never returned.  Exactness: the returned set is the exact top-k under the
- * canonical f64 score (DESIGN.md §canonical ranking), not an approximation. */
+ * canonical f64 score (DESIGN.md §canonical ranking), not an approximation.
+ * Magnitudes (DESIGN.md §4 "Magnitudes").  A result differs from the canonical one only together with an error status.
+ * COSINE: exact for every row and query whose squared norm (f64, feature order) lies in [2^-126, inf), whatever the magnitudes:
+ * subnormal features, norms up to sqrt(dim) * FLT_MAX.  DOT: rows and queries enter the f32 screens unnormalised; per quantity —
+ *   rows         exact for every row of finite squared norm.  The quantisation scales of the screening copies, 127 / max|x_i| of a
+ *                block and 32766 / max|x_i| of a row, are capped at 2^100: no feature is too small.
+ *   queries      a query with a non-zero feature whose largest |q_i| is below 2^-120 is refused with PCV_ERR_INVALID (the message
+ *                names s_q = 127 / max|q_i|, which is inf below 3.73e-37);
+ *   |q| max|x|   max|x| the LARGEST row norm the searcher has held (one huge row widens the screens' margins, multiples of this
+ *                product, for every row): a query for which it is non-zero and outside [2^-120, 2^127] is refused with
+ *                PCV_ERR_INVALID (the message names unit).  This covers every case in which a single product q_i x_i, and so an
+ *                f32 accumulator, could pass FLT_MAX.
+ * Both refusals come from the call that brings the query (pcv_searcher_search, _search_range, _search_device, the ranked calls and
+ * _search_compound) before anything is queued.  The calls of the sharded protocol with host queries
+ * (pcv_searcher_search_device_begin, _search_sharded) refuse by the query alone (s_q): max|x| differs from rank to rank, and among
+ * ranks only a condition all of them evaluate alike may refuse; |q| max|x| is the caller's to keep there.  Queries that are
+ * already on the device (pcv_searcher_search_device_begin_dq, _search_sharded_dq, the like_item calls) are not read on the host
+ * at all: there the whole query envelope is the caller's to keep.  The threshold of the int8 and 6-bit screens in units of the
+ * quantised query, up to 127 sqrt(dim) max|x| whatever the query's scale, is capped at FLT_MAX in the kernels (exact).  Inside it
+ * rows and queries may differ by any power of two (tested: 2^-60 x 2^-60 up to 2^40 x 2^40, one row 2^40 above and one block
+ * 2^40 below the rest, blocks and whole segments of features 2^-122).  An all-zero query and a query with a value that is not finite
+ * are answered as before (every row scores 0; no hits). */
 pcv_status pcv_searcher_search(pcv_searcher* s, const float* queries, int n_queries,
                                const int64_t* source_ids, int n_sources, int k, int64_t* out_ids,
                                float* out_scores, int* out_counts);

@@ -77,6 +77,13 @@ __device__ __forceinline__ uint4 bf16_piece(const float4* __restrict__ blk, floa
     return out;
 }
 
+// The largest quantisation scale a copy is given.  127 / max (int8) and 32766 / max (mid) are inf once the largest feature of a
+// dot-metric block or row is below 127 / FLT_MAX = 3.73e-37 (9.6e-35 for the mid scale) — still normal f32 values.  Any scale s at
+// or below 127 / max (32766 / max) keeps the codes inside their range and |y_i - code_i / s| <= 0.5 / s, which is all the bounds of
+// scan.h use — the tests are the same inequalities with this s — so the scale is capped: such a block gets all-zero codes and
+// |y_i| <= 0.5 / s = 2^-101 is true of it.  Under the cosine max|y_i| >= 1 / sqrt(dim): the cap is never reached.
+constexpr float kMaxCopyScale = 0x1p100f;
+
 // Int8 screening copy of block b by one wave: lane (r, h) owns row r and every other 16-feature piece.  Pass 1: max |y_i| over
 // the BLOCK's searchable rows (y = x * scale); pass 2: x^_i = rint(y_i * s_blk),
 // s_blk = 127 / max: one scale for the 32 rows, so the scan's test of a block needs one float and its right-hand side is the same
@@ -105,7 +112,7 @@ __device__ __forceinline__ void pack8_block(const float4* __restrict__ blk, cons
 #pragma unroll
     for (int off = 16; off > 0; off >>= 1) bm = fmaxf(bm, __shfl_xor(bm, off));
     const bool any_row = __any(searchable);
-    const float s_blk = !any_row ? __builtin_nanf("") : (bm > 0.0f ? 127.0f / bm : 1.0f);
+    const float s_blk = !any_row ? __builtin_nanf("") : (bm > 0.0f ? fminf(127.0f / bm, kMaxCopyScale) : 1.0f);
     for (int g = h; g < D16; g += 2) {
         uint32_t w[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -161,7 +168,7 @@ __device__ __forceinline__ void mid_pack_row(const float4* __restrict__ blk, con
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
         searchable = sc != 0.0f && mx < __builtin_inff();
-        s2 = !searchable ? 0.0f : (mx > 0.0f ? 32766.0f / mx : 1.0f);
+        s2 = !searchable ? 0.0f : (mx > 0.0f ? fminf(32766.0f / mx, kMaxCopyScale) : 1.0f);
     }
     for (int j = lane; j < P8; j += 64) {
         const float4 a = src[(size_t)(2 * j) * 32], b = src[(size_t)(2 * j + 1) * 32];

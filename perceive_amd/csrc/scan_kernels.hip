@@ -131,6 +131,17 @@ __device__ __forceinline__ void offer_slot_wave(const ScanParams& p, int q, floa
     }
 }
 
+// The f32 screening score of a row: the f32 dot product of the scan-side query with the UNSCALED row, times the row's scale.  The
+// partial sums are bounded by |x| (cosine) or |q||x| (dot), not by the score: a row of norm 2^128 and more under the cosine (its
+// scale is a subnormal f32), or |q||x| beyond FLT_MAX under the dot metric, can take them to +-inf or NaN while the canonical score
+// is finite.  Such a value says nothing about the row — -inf failed every threshold and +inf stood above every ceiling (ceil_class:
+// "returned by an earlier pass"), so the row was lost — and becomes NaN here: NaN fails no threshold test (they are written
+// !(s < thr)), is class 1 of a ceiling, raises no threshold (isfinite) and leaves the row to the exact f64 rescoring.
+__device__ __forceinline__ float screen_score(float dot, float scale) {
+    const float s = dot * scale;
+    return isfinite(s) ? s : __builtin_nanf("");
+}
+
 // Where a row with screening score s stands to the pass's ceiling for query q (scan.h, CeilRec): 0 = it counts and may raise
 // the thresholds, 1 = it counts but must not raise them, 2 = it does not count.  No ceiling: 0.
 __device__ __forceinline__ int ceil_class(const ScanParams& p, int q, float s) {
@@ -607,7 +618,7 @@ __global__ __launch_bounds__(256) void scan_wave_kernel(const ScanParams* __rest
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 acc[b] += __shfl_xor(acc[b], 32);
-                s[b] = acc[b] * sc_cur;
+                s[b] = screen_score(acc[b], sc_cur);
                 thr[b] = key_f32(max(tau0[b], tk[b])) - mrg[b];
                 any |= (h == 0) && (sc_cur != 0.0f) && !(s[b] < thr[b]);
                 acc[b] = 0.0f;
@@ -732,9 +743,9 @@ __device__ __forceinline__ void fine_survivors(const ScanParams& p, uint32_t mas
             }
             const float dot = wave_dot_f32(p.qf32 + (size_t)q * Dp, bbase + rib, D4, lane);
             if (sc == 0.0f) continue;  // padding / unsearchable row
-            const float s32 = dot * sc;
+            const float s32 = screen_score(dot, sc);
             const float taun = key_f32(max(ltau0[q], tkey));
-            if (s32 < taun - m32) continue;
+            if (s32 < taun - m32) continue;  // (NaN: kept)
             const int cc = ceil_class(p, q, s32);
             if (cc == 2) continue;
             if (lane == 0) {
@@ -948,6 +959,13 @@ __global__ __launch_bounds__(WPB * 64, WPB == 4 ? ((SRC16 ? NBUF <= 4 : NBUF == 
     }
 #undef PCV_STEP
 }
+
+// T_q = (tau - e32) s_q of the int8 and 6-bit tests, in units of the quantised query.  Under the dot metric tau <= |q| max|x| and
+// s_q = 127 / max|q_i|, so T_q reaches 127 sqrt(D) max|x| whatever the query's own scale: +inf for rows of norm 2^120 and more,
+// and then T - |T| * 2e-6 is NaN, the right-hand side NaN, and no row of the query passed.  A smaller T only keeps more rows:
+// capped at FLT_MAX (a right-hand side that still overflows to +inf is right: no integer dot product reaches it; c1 = inf gives
+// -inf, every row kept).  -inf (no threshold yet) stays.
+__device__ __forceinline__ float int8_threshold(float tau, float e32, float s_q) { return fminf((tau - e32) * s_q, 3.402823466e+38f); }
 
 // MFMA scan over the int8 screening copies (scan.h): the same flat (block, chunk) stream as scan_mfma_kernel with
 // chunks of 128 features (4 k-steps of v_mfma_i32_32x32x32_i8, 4 pieces of 16 bytes per lane), 384 B per 384-d row.
@@ -1315,7 +1333,7 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
         }
 #pragma unroll
         for (int off = 4; off > 0; off >>= 1) dot += __shfl_xor(dot, off);
-        const float s32 = dot * sc;
+        const float s32 = screen_score(dot, sc);
         const float taun = key_f32(max(ltau0[q], tkey));
         const int cc = on ? ceil_class(p, q, s32) : 2;
         const bool cand = go && !(s32 < taun - m32) && cc != 2;
@@ -1343,7 +1361,7 @@ __device__ __forceinline__ void drain_survivors(const ScanParams& p, SurvRing& r
     auto refresh = [&](bool fetch) {
         const uint32_t tau_now = my_tau;
         if (fetch) my_tau = ld_relaxed(&p.tau_c[ql]);
-        const float T = (key_f32(max(my_tau0, tau_now)) - my_e32) * my_sq;
+        const float T = int8_threshold(key_f32(max(my_tau0, tau_now)), my_e32, my_sq);
         myU = ql < p.B ? (my_sq != 0.0f ? (T - fabsf(T) * 2e-6f) - c1 : dead) : __builtin_inff();
         myT = ql < p.B && my_sq != 0.0f ? T : -__builtin_inff();
         if (lane < NQ) __hip_atomic_store(&lU[lane], myU, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1599,7 +1617,7 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
     // U_q of the test for the running threshold `tau_key` (derivation: the epilogue below)
     auto u_of = [&](int q, uint32_t tau_key, float e32q) -> float {
         const float sqq = lsq[q];
-        const float T = (key_f32(max(ltau0[q], tau_key)) - e32q) * sqq;
+        const float T = int8_threshold(key_f32(max(ltau0[q], tau_key)), e32q, sqq);
         return (q < p.B) ? (sqq != 0.0f ? (T - fabsf(T) * 2e-6f) - c1 : dead_u) : __builtin_inff();
     };
     if constexpr (ULDS) {  // the first U of every query (the drain wave keeps them fresh from here on)
@@ -1608,7 +1626,7 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
             const float e32q = q < p.B ? 0.5f * gld(&p.margin32[q]) : 0.0f;
             lU[q] = u_of(q, tk, e32q);
             if constexpr (SIX) {
-                const float T = (key_f32(max(ltau0[q], tk)) - e32q) * lsq[q];
+                const float T = int8_threshold(key_f32(max(ltau0[q], tk)), e32q, lsq[q]);
                 lT6[q] = (q < p.B) ? (lsq[q] != 0.0f ? T - fabsf(T) * 2e-6f : dead_u) : __builtin_inff();
             }
         }
@@ -1721,7 +1739,7 @@ __global__ __launch_bounds__(WPB * 64, NT == 4 ? 2 : 3) void scan_mfma8_kernel(c
                 continue;
             }
             const int q = 32 * t + c;
-            const float T = (key_f32(max(tau0[t], tauk[t])) - e32[t]) * sq[t];
+            const float T = int8_threshold(key_f32(max(tau0[t], tauk[t])), e32[t], sq[t]);
             // lowered by 2e-6 relative (f32 rounding of T and of the product with s_row) and by the |x^|_1 term
             // s_q = 0: a dead query.  Cosine: no row has a score, none is kept; dot (an all-zero query): every row scores 0,
             // all are kept and the fine screen sorts it out.
@@ -1984,7 +2002,7 @@ __global__ __launch_bounds__(NH == 2 ? 256 : 768, 3) void scan_mfma8_hold_kernel
     // U_q of the test for the running threshold `tau_key` (derivation: scan_mfma8_kernel)
     auto u_of = [&](int q, uint32_t tau_key) -> float {
         const float sq = lsq[q];
-        const float T = (key_f32(max(ltau0[q], tau_key)) - le32[q]) * sq;
+        const float T = int8_threshold(key_f32(max(ltau0[q], tau_key)), le32[q], sq);
         const float live = (T - fabsf(T) * 2e-6f) - c1;
         return q < p.B ? (sq != 0.0f ? live : dead) : __builtin_inff();
     };

@@ -114,6 +114,7 @@ static void trim_range_memory(pcv_searcher* s) {
 void search_range(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, const float* bounds,
                   int64_t max_results, int64_t* out_ids, float* out_scores, int64_t* out_counts, uint8_t* out_more) {
     PCV_REQUIRE(!s->dirty, "search_range: rows were added or cleared without pcv_searcher_finalize");
+    if (queries != nullptr && n_queries > 0) check_dot_envelope(s, queries, n_queries, "search_range");
     s->stats = pcv_scan_stats{};  // (also when the kernel is refused)
     const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries);
     for (int q = 0; q < n_queries; ++q) {
@@ -911,7 +912,8 @@ void count_where(pcv_searcher* s, const pcv_searcher* owner, const int64_t* sour
 // The per-shard pass of the begin/end protocol; the caller holds s->mu.
 void device_begin(pcv_searcher* s, const float* queries, int n_queries, const int64_t* source_ids, int n_sources, int k,
                   pcv_hit_dev* out, bool queries_on_device) {
-    check_search_args(s, queries, n_queries, k, "search_device_begin");
+    // (a device pointer is not read on the host; host queries: only what every rank evaluates alike)
+    check_search_args(s, queries, n_queries, k, "search_device_begin", kMaxK, queries_on_device ? kEnvelopeNone : kEnvelopeQuery);
     PCV_REQUIRE(!s->pending.active, "search_device_begin: the previous pass was not collected (search_device_end)");
     sync_view(s);
     const SearchPlan plan = plan_search(s, source_ids, n_sources, n_queries, true);

@@ -206,7 +206,7 @@ static pcv_status search_sharded_impl(pcv_searcher* s, pcv_comm* c, const float*
         // the whole step — local pass, exchange, merge, collection — is one critical section of the searcher:
         // it shares the pass workspace, the pinned blocks and the stream with plain searches
         std::lock_guard<std::mutex> lk(s->mu);
-        check_search_args(s, queries, n_queries, k, "search_sharded");
+        check_search_args(s, queries, n_queries, k, "search_sharded", kMaxK, queries_on_device ? kEnvelopeNone : kEnvelopeQuery);
         PCV_REQUIRE(!s->pending.active, "search_sharded: a pass queued by search_device_begin has not been collected");
         sync_view(s);  // (before the split into passes is chosen)
         const size_t n = (size_t)n_queries * k;

@@ -596,10 +596,45 @@ int pass_queries(const pcv_searcher* s, int kernel, bool among_ranks) {
     return mfma_pass_queries(s->Dp);
 }
 
-void check_search_args(const pcv_searcher* s, const float* queries, int n_queries, int k, const char* who, int k_max) {
+// The dot metric's f32 envelope (perceive_hip.h, DESIGN.md §4 "Magnitudes"): queries enter the screens unnormalised, and two of
+// the quantities the scans form from them leave f32 while the canonical score is still finite.  Both are known before anything is
+// queued — the query on the host, max_norm read back by the last finalize / update — so such a query is refused:
+//   s_q = 127 / max|q_i| (quantize_queries_kernel) is inf below 127 / FLT_MAX = 3.73e-37: refused below 2^-120;
+//   unit = |q| max_norm (both seed kernels), of which every margin is a multiple: inf beyond FLT_MAX — also whenever a single
+//   product q_i x_i could pass FLT_MAX, the f32 accumulators' case; refused above 2^127.  Far below, sums of subnormal products
+//   round by up to Dp * 2^-150 absolutely, which margin32 = 2 eps32 unit, a relative bound with Dp * 2^-24 unit to spare, covers
+//   down to unit ~ 2^-125: refused below 2^-120 (margin32 is a subnormal from 2^-112 on; its own rounding is inside that spare).
+// An all-zero query (every row scores 0) and a corpus of all-zero rows pass.  Not finite values fail no check here: such a query
+// is dead in the kernels (no hits), as before.  `what`: kEnvelopeQuery leaves the unit test out — max_norm differs from rank to
+// rank, and among the ranks of a sharded search only a condition all of them evaluate alike may refuse; kEnvelopeNone: the queries
+// are on the device and are not looked at.
+void check_dot_envelope(const pcv_searcher* s, const float* queries, int n_queries, const char* who, int what) {
+    if (s->metric != PCV_METRIC_DOT || what == kEnvelopeNone) return;
+    for (int q = 0; q < n_queries; ++q) {
+        const float* v = queries + (size_t)q * s->D;
+        double nq = 0.0;  // (a bound, not the canonical sum)
+        float mx = 0.0f;
+        for (int i = 0; i < s->D; ++i) {
+            nq += (double)v[i] * (double)v[i];
+            mx = std::max(mx, std::fabs(v[i]));
+        }
+        if (!(nq > 0.0) || !(nq < INFINITY)) continue;
+        PCV_REQUIRE(mx >= 0x1p-120f,
+                    "%s: query %d: largest |q_i| = %g is below 2^-120: the query quantisation scale s_q = 127 / max|q_i| leaves f32 "
+                    "(dot metric envelope, perceive_hip.h)", who, q, (double)mx);
+        if (what != kEnvelopeFull) continue;
+        const double unit = std::sqrt(nq) * (double)s->max_norm;
+        PCV_REQUIRE(unit == 0.0 || (unit >= 0x1p-120 && unit <= 0x1p127),
+                    "%s: query %d: unit = |q| * max_norm = %g * %g is outside [2^-120, 2^127]: the screens' margins, multiples of it, "
+                    "leave f32 (dot metric envelope, perceive_hip.h)", who, q, std::sqrt(nq), (double)s->max_norm);
+    }
+}
+
+void check_search_args(const pcv_searcher* s, const float* queries, int n_queries, int k, const char* who, int k_max, int envelope) {
     PCV_REQUIRE(!s->dirty, "%s: rows were added or cleared without pcv_searcher_finalize", who);
     PCV_REQUIRE(queries != nullptr && n_queries > 0, "%s: no queries", who);
     PCV_REQUIRE(k > 0 && k <= k_max, "%s: num_results %d outside [1,%d]", who, k, k_max);
+    check_dot_envelope(s, queries, n_queries, who, envelope);
 }
 
 // (SearchPlan: searcher_pass.h)

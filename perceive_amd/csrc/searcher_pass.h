@@ -68,7 +68,10 @@ void drop_pass_graph(pcv_searcher* s);
 
 int pick_kernel(const pcv_searcher* s, int B);
 int pass_queries(const pcv_searcher* s, int kernel, bool among_ranks = false);
-void check_search_args(const pcv_searcher* s, const float* queries, int n_queries, int k, const char* who, int k_max = kMaxK);
+enum { kEnvelopeFull = 0, kEnvelopeQuery = 1, kEnvelopeNone = 2 };  // what check_dot_envelope may look at (searcher_pass.cpp)
+void check_search_args(const pcv_searcher* s, const float* queries, int n_queries, int k, const char* who, int k_max = kMaxK,
+                       int envelope = kEnvelopeFull);
+void check_dot_envelope(const pcv_searcher* s, const float* queries, int n_queries, const char* who, int what = kEnvelopeFull);  // dot metric: PCV_ERR_INVALID outside the f32 envelope
 
 // What every search call settles before its first pass: the device, the selected segments, the kernel and how many queries one
 // pass takes.  Nothing of the searcher changes here, so a refused kernel leaves what the caller has not touched itself.
